@@ -1,7 +1,7 @@
 """bench.py — headline metric of BASELINE.json: real-time factor (24 kHz audio seconds / wall seconds)
 and codec-frames/sec of Qwen3-TTS-0.6B synthesis on MI355X, "0.6B @ b1/b64".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--frames F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--frames F] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the whole hot path over one batch of B utterances per GPU: prompt assembly,
@@ -9,7 +9,7 @@ talker prefill, F frames of [sampler + 15 code-predictor passes + talker decode]
 hipGraph, then the 12 Hz codec decode to 24 kHz PCM.  Default workload = BASELINE.json configs[1]:
 0.6B, batch 1, sampled (temp 0.8 / top-k 50 / top-p 0.95), max-tokens 2048, 16-token prompt; weights
 are seeded synthetic (no checkpoint in the image), EOS is suppressed so every utterance runs the full
-2048 frames (random weights never learnt to stop).  The default line also carries the rest of the
+2048 frames (random weights never learnt to stop).  With --full the line also carries the rest of the
 metric ("0.6B @ b1/b64", north_star "batch 1/8/64") as sub-records run in the same process after the
 timed region of `value`: "b64" = configs[2] (64 utterances in one batch x 256 frames, 5 timed steps),
 "b8", "b64_f2048" (64 x 2048 frames: the length configs[1] and the reference default state), and the
@@ -17,6 +17,12 @@ same long workloads with the talker KV cache in bf16 ("b64_f2048_kv_bf16", "b1_f
 with its own `roofline`; "b8_1p7b_clone" = configs[4] (1.7B dims, batch 8, the --ref voice-clone front end — wav -> resample ->
 log-mel -> speaker encoder -> speaker row — inside the timed region); "capacity" = three 128-slot engines stepping concurrently
 (labelled: not a BASELINE config).  `stages` carries per-stage device time incl. `prefill` (bytes and fraction of HBM).
+
+A plain run does only what the headline needs: set-up, W warmup steps, the K timed steps, the result line (`value`, `ms_per_step`,
+`roofline` from the timed steps' counters).  Everything that takes runs of its own — the sub-records above, `stages`,
+`first_2s_audio_latency_ms`, `cpu_baseline` — runs only with `--full`, after the timed region.  `--dump-outputs DIR` writes what the
+last timed step returned (codes, frame counts, PCM; float32 / float64 .npy, 64 MiB at most) so that two builds can be compared output
+for output: the inputs depend only on the arguments (seeded weights, prompts and sampling seeds).
 
 Multi-GPU (configs[3]): utterances are independent, each rank runs its own batch on its own GPU
 (weak scaling); RCCL carries only the final gather of codes + PCM lengths.  `--gpus N` with
@@ -368,6 +374,7 @@ def run_workload(q3tts, cfg, local_rank, B, F, sp_kwargs, steps, warmup, rank, n
     rng = np.random.default_rng(1 + rank)
     toks = [np.array([IM_START, ASSISTANT, TTS_BOS] + list(rng.integers(0, 151643, 16)) + [TTS_EOS, IM_END], np.int64) for _ in range(B)]
     gathered = {"utterances": 0, "pcm_samples": 0}
+    last = {}   # what the last timed step returned to its caller (--dump-outputs)
 
     def barrier():
         if dist is not None:
@@ -377,6 +384,8 @@ def run_workload(q3tts, cfg, local_rank, B, F, sp_kwargs, steps, warmup, rank, n
 
     def step(i):
         pcm, codes, nfr = eng.synthesize_batch(toks, sp, lang=0, seed=100 + i, ignore_eos=True, want_codes=True)
+        if i == steps - 1:
+            last.update(pcm=pcm, codes=codes, nfr=nfr)
         if dist is not None:  # the only exchange on the path: gather of the generated codes + PCM lengths (RCCL over xGMI)
             import q3dist
             dev = torch.device("cuda", local_rank) if backend == "nccl" else None
@@ -404,7 +413,34 @@ def run_workload(q3tts, cfg, local_rank, B, F, sp_kwargs, steps, warmup, rank, n
         samples += s
     barrier()
     dt = time.perf_counter() - t0
-    return eng, toks, sp, dt, frames, samples, eng.counters(), gathered
+    return eng, toks, sp, dt, frames, samples, eng.counters(), gathered, last
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, last, suffix=""):
+    """--dump-outputs: the last timed step's results as float32 / float64 .npy files.  codes [B][F][16] (ids are exact in float32),
+    frames [B], pcm [B][samples] — ragged lengths are concatenated instead.  An array over its share of DUMP_BYTES is replaced by a
+    fixed seeded sample of its flattened values (the same positions for the same arguments)."""
+    os.makedirs(d, exist_ok=True)
+
+    def flat_or_stack(arrs, dtype):
+        arrs = [np.asarray(a, dtype) for a in arrs]
+        return np.stack(arrs) if len({a.shape for a in arrs}) == 1 else np.concatenate(arrs)
+
+    def fit(a, limit):
+        if a.nbytes <= limit:
+            return a
+        a = a.reshape(-1)
+        idx = np.unique(np.random.default_rng(0).integers(0, a.size, limit // a.itemsize))
+        return a[idx]
+
+    out = {"frames": np.asarray(last["nfr"], np.float64),
+           "codes": fit(flat_or_stack(last["codes"], np.float32), DUMP_BYTES // 4),
+           "pcm": fit(flat_or_stack(last["pcm"], np.float32), DUMP_BYTES // 4 * 3 - (1 << 20))}
+    for name, a in out.items():
+        np.save(os.path.join(d, name + suffix + ".npy"), a)
 
 
 def write_sweep_wav(path, seconds, f0, f1, sr=24000):
@@ -578,7 +614,12 @@ def main():
     ap.add_argument("--hooks", action="store_true", help="create the engines with Q3TTS_FLAG_TEST_HOOKS so that the A/B environment knobs "
                     "(Q3TTS_SEAM, Q3TTS_GEMM3_LA, ...) are honoured — A/B measurement runs only; the line then says so")
     ap.add_argument("--dry-launch", action="store_true", help="only the N-rank launch + gloo rendezvous + gather plumbing, on CPU")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything that takes runs of its own: the sub-records, "
+                    "stages, first-audio latency and the CPU baseline (--no-b64 / --no-long / --no-cpu-baseline thin it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's codes, frame counts and PCM to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     global HOOKS
     HOOKS = args.hooks
 
@@ -614,8 +655,11 @@ def main():
     B, F = args.batch, args.frames
     sp_kwargs = dict(temperature=1.0, top_p=1.0, top_k=1) if args.greedy else dict(temperature=0.8, top_p=0.95, top_k=50)
     sampling_txt = "greedy top_k=1" if args.greedy else "sampled temp=0.8 top-k=50 top-p=0.95"
-    eng, toks, sp, dt, frames, samples, ctr, gathered = run_workload(q3tts, cfg, local_rank, B, F, sp_kwargs, args.steps, args.warmup, rank,
-                                                                     args.no_graph, dist, torch, world, backend, kv_bf16=args.kv_bf16)
+    eng, toks, sp, dt, frames, samples, ctr, gathered, last = run_workload(q3tts, cfg, local_rank, B, F, sp_kwargs, args.steps, args.warmup,
+                                                                           rank, args.no_graph, dist, torch, world, backend, kv_bf16=args.kv_bf16)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, "" if world == 1 else "_rank%d" % rank)
+    del last
 
     if dist is not None:
         v = torch.tensor([dt, float(frames), float(samples)], dtype=torch.float64, device="cuda")
@@ -626,7 +670,7 @@ def main():
         frames, samples = int(v[1]), int(v[2])
 
     first_audio = None
-    if world == 1 and dist is None:
+    if args.full and world == 1 and dist is None:
         # serving-side extra (not the headline): wall time from token ids to the first 2 s of PCM for one utterance —
         # prompt assembly + prefill + 25 frames + codec decode of those frames (a causal decoder: exactly the first
         # samples of the full utterance)
@@ -641,7 +685,7 @@ def main():
         first_audio = round(min(ts), 2)
 
     stages = None
-    if world == 1 and dist is None and not args.no_graph:
+    if args.full and world == 1 and dist is None and not args.no_graph:
         try:
             stages = stage_report(eng, cfg, toks, sp, B, F, ctr, args.kv_bf16)
         except Exception as ex:   # a reported extra, never the measurement
@@ -664,13 +708,14 @@ def main():
             "pcm_samples": samples,
             "decode_ms_per_frame_step": round(step_ms, 4),
             "codec_decode_ms_per_frame": round(ctr["codec_ms"] / max(ctr["codec_frames"], 1), 5),
-            "first_2s_audio_latency_ms": first_audio,
             "roofline": roofline_record(cfg, B, F, step_ms, args.model, args.kv_bf16),
             # round 5: kernels are compiled without packed fp32 instructions — with them results depended on what else the GPU was running
             # (profiles/r05_hunt/README.txt); costs 2-3 % of the b=1 step, nothing at batch 64 or in the codec
             "build": {"library": os.path.basename(q3tts.LIB_PATH),
                       "packed_fp32_instructions": "none in the default build (tests/test_kernel_resources.py checks the code objects)"},
         }
+        if args.full:
+            out["first_2s_audio_latency_ms"] = first_audio
         if HOOKS:
             out["ab_knobs"] = {k: v for k, v in os.environ.items() if k.startswith("Q3TTS_")}   # an A/B run: which knobs were set
         if dist is not None:
@@ -682,14 +727,15 @@ def main():
             out["stages"] = stages
         eng.close()
         eng = None
-        if world == 1 and dist is None and B == 1 and args.model == "0.6b" and not args.no_b64 and not args.no_graph:
+        full_b1 = args.full and world == 1 and dist is None and B == 1 and args.model == "0.6b" and not args.no_b64 and not args.no_graph
+        if full_b1:
             # the rest of BASELINE.json's metric ("0.6B @ b1/b64", north_star: "batch 1/8/64"), same process, after the timed region of `value`:
             #   b64       configs[2], 64 utterances in one batch x 256 frames, 5 timed steps
             #   b64_f2048 the same batch at the length configs[1] and the reference default (tts_onnx.h:65) state: 64 x 2048 frames, 1 timed step
             #   b8        8 utterances x 256 frames
             def sub_record(B2, F2, steps2, warm2, with_stages, kvb=False):
-                e2, toks2, sp2, dt2, fr2, smp2, ctr2, _ = run_workload(q3tts, cfg, local_rank, B2, F2, sp_kwargs, steps2, warm2, rank, False, kv_bf16=kvb,
-                                                                       warm_frames=0)   # full-length warmup: a short one left the vocoder's arenas (~30 GB at 64 x 2048 frames) to be allocated inside the timed job — 610 vs 664x between runs of one build
+                e2, toks2, sp2, dt2, fr2, smp2, ctr2, _, _ = run_workload(q3tts, cfg, local_rank, B2, F2, sp_kwargs, steps2, warm2, rank, False, kv_bf16=kvb,
+                                                                          warm_frames=0)   # full-length warmup: a short one left the vocoder's arenas (~30 GB at 64 x 2048 frames) to be allocated inside the timed job — 610 vs 664x between runs of one build
                 sm2 = ctr2["decode_ms"] / max(ctr2["decode_steps"], 1)
                 rec = {"config": {"workload": f"{MODEL}, batch={B2}/GPU, 16-token prompt, {sampling_txt}, max-tokens={F2} (EOS suppressed), "
                                               "hipGraph decode loop, synthetic seeded weights", "batch_per_gpu": B2, "frames_per_utterance": F2},
@@ -717,7 +763,7 @@ def main():
                     out[key] = sub_record(B2, F2, steps2, warm2, with_stages, kvb)
                 except Exception as ex:
                     out[key] = {"error": str(ex)}
-        if world == 1 and dist is None and B == 1 and args.model == "0.6b" and not args.no_b64 and not args.no_graph:
+        if full_b1:
             try:      # BASELINE configs[4]: 1.7B dims, --ref voice-clone path, batch 8
                 out["b8_1p7b_clone"] = clone_record(q3tts, local_rank, sp_kwargs, sampling_txt)
             except Exception as ex:
@@ -727,7 +773,7 @@ def main():
                     out["capacity"] = capacity_record(q3tts, cfg, local_rank, sp_kwargs)
                 except Exception as ex:
                     out["capacity"] = {"error": str(ex)}
-        if world == 1 and dist is None and not args.no_cpu_baseline:
+        if args.full and world == 1 and dist is None and not args.no_cpu_baseline:
             try:
                 e3 = q3tts.Engine(cfg, device=local_rank, max_batch=1, max_ctx=64)   # weights only: the oracle copies the same seeded tensors
                 e3.fill_synthetic(seed=0)

@@ -16,18 +16,14 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "leaxer-qwen3-tts_amd"))
 
 import build_ref  # noqa: E402
+from ref_io import RefIO  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def ref():
-    so = build_ref.build()
-    if not so or not os.path.exists(so):
-        pytest.skip("oracle/_ref/libleaxer_ref.so not built (needs /root/reference)")
-    L = C.CDLL(so)
-    L.ref_read_wav.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.ref_resample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
-    L.ref_mel.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    return L
+    L = RefIO(build_ref.build())   # the live library where it can be built, else its recorded answers
+    yield L
+    L.save()
 
 
 def ref_read(L, path, cap=1 << 22):

@@ -22,6 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "leaxer-qwen3-tts_amd"))
 
 import build_ref  # noqa: E402
+from ref_io import RefIO  # noqa: E402
 
 
 def _self_mapped(b):
@@ -147,12 +148,7 @@ def write_files(d, seed=0, drop_frac=0.08):
 
 class Ref:
     def __init__(self):
-        so = build_ref.build()
-        if not so or not os.path.exists(so):
-            pytest.skip("oracle/_ref/libleaxer_ref.so not built (needs /root/reference)")
-        self.L = C.CDLL(so)
-        self.L.ref_tok_load.argtypes = [C.c_char_p, C.c_char_p]
-        self.L.ref_tokenize.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.c_int]
+        self.L = RefIO(build_ref.build())   # the live library where it can be built, else its recorded answers
 
     def encode(self, b):
         buf = (C.c_int32 * (4 * len(b) + 16))()
@@ -215,6 +211,7 @@ def pair(tmp_path_factory):
     stages["full"] = ([ref.encode(p) for p in probe], [list(tok.encode(p)) for p in probe], r3, ref.L.ref_tok_ready(), tok.ready)
     yield ref, tok, stages, d
     tok.close()
+    ref.L.save()
 
 
 def test_load_stages_match_reference(pair):

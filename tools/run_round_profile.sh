@@ -28,14 +28,14 @@ for CFG in ${PMC_CFGS:-1:1032:fp32:0.6b 64:136:fp32:0.6b 8:136:fp32:0.6b 64:1032
   rm -rf $O/pmc_f_${T}_* $O/pmc_w_${T}_*
 done
 cp $O/decode_step_traffic.json profiles/decode_step_traffic.json   # on the box only: the committed copy is made from gpurun_out/ afterwards
-timeout -k 10 600 python bench.py > $O/bench_default_with_traffic.json 2> $O/bench_default_with_traffic.err
+timeout -k 10 600 python bench.py --full > $O/bench_default_with_traffic.json 2> $O/bench_default_with_traffic.err
 python -c "import json;j=json.load(open('$O/bench_default_with_traffic.json'));print('b1', j['value'], j['roofline']['frac'], j['roofline']['traffic'], '| b64', j['b64']['value'], j['b64']['roofline']['traffic'])"
 exit 0
 fi
 # 1. full GPU test suite
 if [ "$3" != "--skip-tests" ]; then timeout -k 10 1000 python -m pytest tests -m gpu -x -q --timeout 600 -s > $O/gpu_tests.log 2>&1 || true; grep -E "passed|failed|free-running|teacher" $O/gpu_tests.log | tail -8; fi
-# 2. headline bench (configs[1] + the b64 sub-record + cpu baseline), then b=8 and 1.7B b=8
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+# 2. headline bench with --full (configs[1] + the b64 sub-record + cpu baseline), then b=8 and 1.7B b=8
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python -c "import json;j=json.load(open('$O/bench_default.json'));print('b1', j['value'], j['decode_ms_per_frame_step'], j['roofline']['frac'], *[(k, j[k].get('value'), j[k].get('decode_ms_per_frame_step'), (j[k].get('roofline') or {}).get('frac')) for k in ('b64','b8','b64_f2048','b64_f2048_kv_bf16','b1_f2048_kv_bf16') if k in j], '| cpu', j['cpu_baseline']['value'])"
 timeout -k 10 600 python bench.py --model 1.7b --batch 8 --frames 256 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_1p7b_b8.json 2> $O/bench_1p7b_b8.err
 timeout -k 10 600 python bench.py --batch 128 --frames 256 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_b128.json 2> $O/bench_b128.err
