@@ -77,6 +77,10 @@ struct GemvArgs {
     int pS = 0, pchunk = 0, pn_new = 1, pslot_offset = 0, pheads = 0, pd = 0;
     const int* ppos_dev = nullptr;
     int ppos_scalar = 0;
+    // optional (gate/up, fast path): the activation rows are x + the o_proj partial rows of the 8 kv heads, psum[(h * M + m) * K + k],
+    // summed in kv-head order; every workgroup stores its slice of that sum to xmid [M][K] (the down projection's residual)
+    const float* psum = nullptr;
+    float* xmid = nullptr;
 };
 void launch_gemv(const GemvArgs& a, hipStream_t s);
 bool gemv_fast_path(const GemvArgs& a); // single-pass kernel available (M <= 2, K in {1024,2048,3072})
@@ -152,6 +156,12 @@ struct CpAttnOprojArgs {
 };
 bool cp_attn_oproj_ok(const CpAttnOprojArgs& a, int n_new);
 void launch_cp_attn_oproj(const CpAttnOprojArgs& a, int n_new, hipStream_t s);
+// o_proj split by kv head (b = 1): one fp32 partial row per (kv head, row) into part[(h * n_new + m) * N], x left as it is; the gate/up
+// GEMV adds them (GemvArgs::psum).  The predictor's attention + o_proj (same shapes as cp_attn_oproj_ok), and the talker's split-T merge +
+// o_proj (a COMB GemvArgs of one row)
+void launch_cp_attn_kvh(const CpAttnOprojArgs& a, int n_new, float* part, hipStream_t s);
+bool oproj_kvh_ok(const GemvArgs& a);
+void launch_oproj_kvh(const GemvArgs& a, float* part, hipStream_t s);
 void launch_attn_combine(const AttnArgs& a, hipStream_t s); // partials -> a.out
 
 // Skinny-M bf16-MFMA GEMM (q3_gemm_kernels.hip): activations as (hi, lo) bf16 planes, fp32 accumulate

@@ -243,7 +243,9 @@ static void gemv_r(const GemvArgs& a, hipStream_t s) {
 // k_gemv1 — single-pass decode GEMV for M <= 2 rows and K = NCH*512: every weight load of the wave
 // (RW rows x NCH x 16 B/lane) is issued before anything else, the activation row is read once into
 // registers (its RMSNorm statistics come from those same registers), so the kernel is one memory
-// latency deep.  COMB: the activation rows are the combination of split-T attention partials.
+// latency deep.  COMB: the activation rows are the combination of split-T attention partials.  PSUM (gate/up after a kv-head-split
+// o_proj): the activation rows are x + the 8 o_proj partial rows, summed in a fixed order; the workgroup shares the sum through LDS
+// and stores its slice of it to a.xmid, the down projection's residual operand.
 // ================================================================================================
 static __device__ __forceinline__ uint4 ldw_rt(const bf16_t* p, bool nt) {
     u32x4 v;
@@ -255,7 +257,7 @@ static __device__ __forceinline__ uint4 ldw_rt(const bf16_t* p, bool nt) {
 // The leading scalar parameters repeat the fields the first loads need: the file is built with -amdgpu-kernarg-preload-count=16, so the
 // command processor hands them to the wave in SGPRs at launch instead of the wave fetching its kernarg segment first (~0.35 us per
 // launch on a chain of dependent GEMVs; a by-value struct is not preloadable).
-template <int MT, int NCH, int RW, int EPI, bool NORM, bool COMB>
+template <int MT, int NCH, int RW, int EPI, bool NORM, bool COMB, bool PSUM = false>
 __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* pW2, const float* px, const float* pgamma, const float* pepi,
                                                 int pN, int pM, int pldx, int pldepi, int pnt, GemvArgs a) {
     constexpr int K = NCH * 512;
@@ -263,7 +265,7 @@ __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* p
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // provably wave-uniform: row addresses stay scalar
     const int n0 = (blockIdx.x * 4 + wave) * RW;
     const int N = pN, M = pM;
-    __shared__ float xs[COMB ? MT * K : 1];
+    __shared__ float xs[(COMB || PSUM) ? MT * K : 1];
 
     KP_MARK(30); KP_MARK(31);   // back to back: the first one absorbs the kernarg fetch, their distance is the cost of a mark
     KP_MARK(8);
@@ -287,9 +289,59 @@ __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* p
             if (m < M && n < N) epi_in = EPI == EPI_RESIDUAL ? pepi[(size_t)m * pldepi + n] : pepi[n];
         }
     }
+    float g[NORM ? NCH : 1][8];
+    auto load_gamma = [&]() {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const float4 g0 = *reinterpret_cast<const float4*>(pgamma + c * 512 + lane * 8);
+            const float4 g1 = *reinterpret_cast<const float4*>(pgamma + c * 512 + lane * 8 + 4);
+            g[c][0] = g0.x; g[c][1] = g0.y; g[c][2] = g0.z; g[c][3] = g0.w; g[c][4] = g1.x; g[c][5] = g1.y; g[c][6] = g1.z; g[c][7] = g1.w;
+        }
+    };
     // 2. activations
     float xv[MT][NCH][8];
-    if (COMB) {
+    if (PSUM) {
+        // thread t owns elements 4 t + 1024 i: x and the 8 partial rows (kv heads ascending) are loaded in one round with gamma, then
+        // x + (p0 + p1 + ... + p7) goes to LDS and, for the chunks this workgroup owns (chunk % grid == block), to a.xmid
+        constexpr int NI = K / 1024, NP = 8;
+        static_assert(K % 1024 == 0, "PSUM: K must be a multiple of 1024");
+        float4 xin[MT][NI], pin[MT][NI][NP];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const int mr = m < M ? m : 0;
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int k4 = i * 1024 + threadIdx.x * 4;
+                xin[m][i] = *reinterpret_cast<const float4*>(px + (size_t)mr * pldx + k4);
+#pragma unroll
+                for (int h = 0; h < NP; ++h) pin[m][i][h] = *reinterpret_cast<const float4*>(a.psum + ((size_t)h * M + mr) * K + k4);
+            }
+        }
+        if (NORM) load_gamma();
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int k4 = i * 1024 + threadIdx.x * 4;
+                float4 ps = pin[m][i][0];
+#pragma unroll
+                for (int h = 1; h < NP; ++h) { ps.x += pin[m][i][h].x; ps.y += pin[m][i][h].y; ps.z += pin[m][i][h].z; ps.w += pin[m][i][h].w; }
+                const float4 v = make_float4(xin[m][i].x + ps.x, xin[m][i].y + ps.y, xin[m][i].z + ps.z, xin[m][i].w + ps.w);
+                *reinterpret_cast<float4*>(&xs[m * K + k4]) = v;
+                if (m < M && (k4 / 4) % gridDim.x == blockIdx.x) *reinterpret_cast<float4*>(a.xmid + (size_t)m * K + k4) = v;
+            }
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                const float4 x0 = *reinterpret_cast<const float4*>(&xs[m * K + c * 512 + lane * 8]);
+                const float4 x1 = *reinterpret_cast<const float4*>(&xs[m * K + c * 512 + lane * 8 + 4]);
+                xv[m][c][0] = x0.x; xv[m][c][1] = x0.y; xv[m][c][2] = x0.z; xv[m][c][3] = x0.w;
+                xv[m][c][4] = x1.x; xv[m][c][5] = x1.y; xv[m][c][6] = x1.z; xv[m][c][7] = x1.w;
+            }
+    } else if (COMB) {
         for (int k8 = threadIdx.x * 8; k8 < K; k8 += 2048) {
             const int head = k8 / a.pd, e0 = k8 % a.pd;
 #pragma unroll
@@ -359,15 +411,7 @@ __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* p
                 xv[m][c][4] = x1.x; xv[m][c][5] = x1.y; xv[m][c][6] = x1.z; xv[m][c][7] = x1.w;
             }
     }
-    float g[NORM ? NCH : 1][8];
-    if (NORM) {
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const float4 g0 = *reinterpret_cast<const float4*>(pgamma + c * 512 + lane * 8);
-            const float4 g1 = *reinterpret_cast<const float4*>(pgamma + c * 512 + lane * 8 + 4);
-            g[c][0] = g0.x; g[c][1] = g0.y; g[c][2] = g0.z; g[c][3] = g0.w; g[c][4] = g1.x; g[c][5] = g1.y; g[c][6] = g1.z; g[c][7] = g1.w;
-        }
-    }
+    if (NORM && !PSUM) load_gamma();
     KP_MARK(9);
     __builtin_amdgcn_sched_barrier(0); // all loads of the kernel are in flight past this point
     if (NORM) {
@@ -447,15 +491,22 @@ bool gemv_fast_path(const GemvArgs& a) {
     const bool norm = a.gamma != nullptr, comb = a.po != nullptr;
     if (comb && (norm || a.epi != EPI_RESIDUAL || a.pd % 8 != 0 || a.pheads * a.pd != a.K)) return false;
     if (norm && a.epi != EPI_STORE && a.epi != EPI_SWIGLU) return false;
+    if (a.psum && (!norm || a.epi != EPI_SWIGLU || a.K % 1024 != 0 || a.K > 2048 || a.xmid == nullptr || a.xn_out || gemv1_rw(a) > 3)) return false;
     return true;
 }
 
 template <int MT, int NCH, int RW>
 static void gemv1_launch(const GemvArgs& a, int grid, hipStream_t s) {
     const bool norm = a.gamma != nullptr, comb = a.po != nullptr;
-#define Q3_G1(EPI, NORM, COMB) hipLaunchKernelGGL((k_gemv1<MT, NCH, RW, EPI, NORM, COMB>), dim3(grid), dim3(256), 0, s, a.W, a.W2, a.x, a.gamma, \
+#define Q3_G1(EPI, NORM, COMB) Q3_G1P(EPI, NORM, COMB, false)
+#define Q3_G1P(EPI, NORM, COMB, PSUM) hipLaunchKernelGGL((k_gemv1<MT, NCH, RW, EPI, NORM, COMB, PSUM>), dim3(grid), dim3(256), 0, s, a.W, a.W2, a.x, a.gamma, \
         (a.epi == EPI_RESIDUAL ? a.res : a.bias), a.N, a.M, a.ldx, a.ldres, (int)a.nt, a)
     if (comb) { Q3_G1(EPI_RESIDUAL, false, true); return; }
+    if (a.psum) {   // gemv_fast_path: SwiGLU + norm, K = 1024 or 2048 (wider ones would spill)
+        if constexpr (RW <= 3 && NCH % 2 == 0 && NCH <= 4) Q3_G1P(EPI_SWIGLU, true, false, true);
+        else throw Error("gemv: partial-sum prologue not built for this shape");
+        return;
+    }
     switch (a.epi) {
     case EPI_STORE: if (norm) Q3_G1(EPI_STORE, true, false); else Q3_G1(EPI_STORE, false, false); break;
     case EPI_SWIGLU:   // gemv1_rw never gives a SwiGLU launch four rows per wave (two weight matrices: the register file); not instantiated
@@ -467,6 +518,7 @@ static void gemv1_launch(const GemvArgs& a, int grid, hipStream_t s) {
     default: Q3_G1(EPI_BIAS_SILU, false, false); break;
     }
 #undef Q3_G1
+#undef Q3_G1P
 }
 template <int MT, int NCH>
 static void gemv1_rwsel(const GemvArgs& a, hipStream_t s) {
@@ -2008,6 +2060,293 @@ void launch_cp_attn_oproj(const CpAttnOprojArgs& a, int n_new, hipStream_t s) {
 bool cp_attn_oproj_ok(const CpAttnOprojArgs& a, int n_new) {
     return (n_new == 1 || (n_new == 2 && a.base <= 12)) && a.nq == 16 && a.nkv == 8 && a.d == 128 && a.K == 2048 && a.base >= 0 && a.base <= 16 &&
            a.base + n_new <= a.page_tokens && a.q_norm && a.k_norm && a.ld_qkv == 4096 && a.N >= 1 && a.N < 65536 && a.ldx < 65536 && a.page_tokens < 65536;
+}
+
+// ================================================================================================
+// o_proj split by kv head (b = 1).  Workgroup (column chunk c, kv head h) = blockIdx c * 8 + h: it forms the attention
+// output of h's two query heads only (256 of o_proj's 2048 K) and multiplies it by W_o[32 columns of chunk c][h's 256 K],
+// 16 KB of weights.  The result is one fp32 partial row per (kv head, row): part[(h * M + m) * N + n].  The cross-head sum
+// moves into the next launch, the RMSNorm + gate/up GEMV (k_gemv1 PSUM), which adds x + part[0] + ... + part[7] in that
+// fixed order.  Before, every one of the 256 workgroups redid all 16 heads' attention (or split-T merge) for a 4-column
+// GEMV.  Workgroups of one kv head share blockIdx % 8, the XCD of the round-robin dispatch: a head's K/V or partials fill one L2.
+// Wave w of a workgroup owns columns c * 32 + 8 w .. + 7; half-wave hw of it reads K elements (lane & 31) * 8 .. + 7 of rows 2 i + hw.
+// ================================================================================================
+#define KVH_COLS 32
+static __device__ __forceinline__ void kvh_load_w(uint4 (&w)[4], const bf16_t* pW, int N, int K, int n0, int k0, int lane) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        int n = n0 + 2 * i + (lane >> 5);
+        n = n < N ? n : N - 1;
+        w[i] = ldw_rt(pW + (size_t)n * K + k0 + (lane & 31) * 8, false);
+    }
+}
+// dot of the 4 row pairs with the 256-element LDS vector xs; lane 0 / 32 of the wave store rows 2 i / 2 i + 1
+static __device__ __forceinline__ void kvh_gemv_store(const uint4 (&w)[4], const float* xs, float* out, int N, int n0, int lane) {
+    const float* xr = xs + (lane & 31) * 8;
+    const float4 x0 = *reinterpret_cast<const float4*>(xr), x1 = *reinterpret_cast<const float4*>(xr + 4);
+    const float xv[8] = { x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w };
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t wu[4] = { w[i].x, w[i].y, w[i].z, w[i].w };
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { s = fmaf(xv[2 * j], bf_lo(wu[j]), s); s = fmaf(xv[2 * j + 1], bf_hi(wu[j]), s); }
+        s = row_sum16(s);
+        s += wave_xor_lane_f<16>(s, lane);
+        const int n = n0 + 2 * i + (lane >> 5);
+        if ((lane & 31) == 0 && n < N) out[n] = s;
+    }
+}
+
+// The code predictor's attention + o_proj K-slice (replaces k_cp_attn_oproj's 16-head redo).  Waves 0 and 1 are query heads 2 h and
+// 2 h + 1 and do exactly what a wave of k_cp_attn_oproj does for its head; waves 2 and 3 only hold weights.  All addresses are known at
+// launch (host-known position, contiguous per-slot cache): weights, q/k/v rows, norm / RoPE operands and h's cached K/V are one memory
+// round.  Column chunk 0 of head h appends h's new K/V rows to the cache.  NEW = new rows (1, or 2 for the first pass), U as there.
+template <int NEW, int U>
+__global__ __launch_bounds__(256) void k_cp_attn_kvh(const bf16_t* pW, const float* pqkv, const float* pkc, const float* pvc, float* ppart,
+                                                     const float* pcos, const float* psin, uint32_t pk0, uint32_t pk1, CpAttnOprojArgs a) {
+    // leading scalars preloaded into SGPRs (see k_gemv1): pk0 = base | page_tokens << 16, pk1 = N
+    const int pbase = (int)(pk0 & 0xFFFFu), ppage_tokens = (int)(pk0 >> 16), pN = (int)pk1;
+    constexpr int LDQ = 4096;
+    constexpr int D = 128, HALF = 64, EPL = 8, G = 2, NKV = 8, NQ = 16, K = 2048, KS = G * D;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kvh = blockIdx.x % NKV, chunk = blockIdx.x / NKV;
+    const int head = kvh * G + (wave & 1);
+    const int base = pbase;
+    const int n0 = chunk * KVH_COLS + wave * 8;
+
+    __shared__ float q_s[G][NEW][D];
+    __shared__ float knew[G][NEW][D];
+    __shared__ float vnew[G][NEW][D];
+    __shared__ float attn_s[NEW][KS];
+
+    // ---- the one memory round ----
+    uint4 w[4];
+    kvh_load_w(w, pW, pN, K, n0, kvh * KS, lane);
+    __builtin_amdgcn_sched_barrier(0);
+
+    if (wave < G) {
+        struct VecOps { float x0, x1, v0, v1, n0, n1, cs, sn; };
+        constexpr int NVEC = 2 * NEW;            // this head's query rows, then the new keys of its kv group
+        VecOps vec[NVEC];
+#pragma unroll
+        for (int v = 0; v < NVEC; ++v) {
+            const bool is_q = v < NEW;
+            const int j = is_q ? v : v - NEW;
+            const float* rowp = pqkv + (size_t)j * LDQ;
+            const float* src = rowp + (is_q ? head * D : (NQ + kvh) * D);
+            const float* vs = rowp + (NQ + NKV + kvh) * D;
+            const float* nw = is_q ? a.q_norm : a.k_norm;
+            vec[v].x0 = src[lane]; vec[v].x1 = src[lane + HALF];
+            vec[v].v0 = vs[lane]; vec[v].v1 = vs[lane + HALF];
+            vec[v].n0 = nw[lane]; vec[v].n1 = nw[lane + HALF];
+            vec[v].cs = pcos[(size_t)(base + j) * HALF + lane]; vec[v].sn = psin[(size_t)(base + j) * HALF + lane];
+        }
+        const int tg = lane >> 4, sub = lane & 15;
+        float kr[U][EPL], vr[U][EPL];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            int t = tg + 4 * u;                  // clamped, unconditional
+            t = t < base ? t : base - 1;
+            t = t > 0 ? t : 0;
+            const size_t off = ((size_t)kvh * ppage_tokens + t) * D + sub * EPL;
+            const float4 k0 = *reinterpret_cast<const float4*>(pkc + off), k1 = *reinterpret_cast<const float4*>(pkc + off + 4);
+            const float4 v0 = *reinterpret_cast<const float4*>(pvc + off), v1 = *reinterpret_cast<const float4*>(pvc + off + 4);
+            kr[u][0] = k0.x; kr[u][1] = k0.y; kr[u][2] = k0.z; kr[u][3] = k0.w; kr[u][4] = k1.x; kr[u][5] = k1.y; kr[u][6] = k1.z; kr[u][7] = k1.w;
+            vr[u][0] = v0.x; vr[u][1] = v0.y; vr[u][2] = v0.z; vr[u][3] = v0.w; vr[u][4] = v1.x; vr[u][5] = v1.y; vr[u][6] = v1.z; vr[u][7] = v1.w;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+
+        // ---- 1. q / k RMSNorm + RoPE; wave-private staging ----
+#pragma unroll
+        for (int v = 0; v < NVEC; ++v) {
+            const bool is_q = v < NEW;
+            const int j = is_q ? v : v - NEW;
+            const float ss = wave_sum(vec[v].x0 * vec[v].x0 + vec[v].x1 * vec[v].x1);
+            const float rr = 1.0f / sqrtf(ss / (float)D + a.eps);
+            const float x0 = vec[v].n0 * (vec[v].x0 * rr), x1 = vec[v].n1 * (vec[v].x1 * rr);
+            const float y0 = x0 * vec[v].cs + (-x1) * vec[v].sn;
+            const float y1 = x1 * vec[v].cs + x0 * vec[v].sn;
+            if (is_q) { q_s[wave][j][lane] = y0; q_s[wave][j][lane + HALF] = y1; }
+            else {
+                knew[wave][j][lane] = y0; knew[wave][j][lane + HALF] = y1;
+                vnew[wave][j][lane] = vec[v].v0; vnew[wave][j][lane + HALF] = vec[v].v1;
+                if (chunk == 0 && wave == 0) {
+                    const size_t off = ((size_t)kvh * a.page_tokens + base + j) * D;
+                    a.kc[off + lane] = y0; a.kc[off + lane + HALF] = y1;
+                    a.vc[off + lane] = vec[v].v0; a.vc[off + lane + HALF] = vec[v].v1;
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+        // ---- 2. scores and weighted values: token group tg owns cached tokens tg, tg+4, ... and new token j if (j & 3) == tg ----
+        float kn[NEW][EPL], vn[NEW][EPL];
+#pragma unroll
+        for (int j = 0; j < NEW; ++j)
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) { kn[j][e] = knew[wave][j][sub * EPL + e]; vn[j][e] = vnew[wave][j][sub * EPL + e]; }
+#pragma unroll
+        for (int inew = 0; inew < NEW; ++inew) {
+            float qr[EPL];
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) qr[e] = q_s[wave][inew][sub * EPL + e];
+            float sc[U + NEW];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                float sdot = 0.f;
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) sdot = fmaf(qr[e], kr[u][e], sdot);
+                sdot = row_sum16(sdot) * a.scale;
+                sc[u] = tg + 4 * u < base ? sdot : -INFINITY;
+            }
+#pragma unroll
+            for (int j = 0; j < NEW; ++j) {
+                float sdot = 0.f;
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) sdot = fmaf(qr[e], kn[j][e], sdot);
+                sdot = row_sum16(sdot) * a.scale;
+                sc[U + j] = (j <= inew && (j & 3) == tg) ? sdot : -INFINITY;   // causal among the new rows
+            }
+            float mx = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < U + NEW; ++i) mx = fmaxf(mx, sc[i]);
+            float l = 0.f, o[EPL];
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) o[e] = 0.f;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const float pw = mx == -INFINITY ? 0.f : __expf(sc[u] - mx);
+                l += pw;
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) o[e] = fmaf(pw, tg + 4 * u < base ? vr[u][e] : 0.f, o[e]);   // never-written cache rows may hold NaN
+            }
+#pragma unroll
+            for (int j = 0; j < NEW; ++j) {
+                const float pw = mx == -INFINITY ? 0.f : __expf(sc[U + j] - mx);
+                l += pw;
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) o[e] = fmaf(pw, vn[j][e], o[e]);
+            }
+            const float mall = wave_max(mx);
+            const float wgt = mx == -INFINITY ? 0.f : __expf(mx - mall);
+            l *= wgt;
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) o[e] *= wgt;
+            l += wave_xor_lane_f<16>(l, lane);
+            l += wave_xor_lane_f<32>(l, lane);
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) { o[e] += wave_xor_lane_f<16>(o[e], lane); o[e] += wave_xor_lane_f<32>(o[e], lane); }
+            if (tg == 0) {
+                const float il = 1.0f / l;
+                float* dst = &attn_s[inew][wave * D + sub * EPL];
+                *reinterpret_cast<float4*>(dst) = make_float4(o[0] * il, o[1] * il, o[2] * il, o[3] * il);
+                *reinterpret_cast<float4*>(dst + 4) = make_float4(o[4] * il, o[5] * il, o[6] * il, o[7] * il);
+            }
+        }
+    }
+    __syncthreads();
+    // ---- 3. o_proj K-slice: partial rows of kv head h ----
+#pragma unroll
+    for (int m = 0; m < NEW; ++m) kvh_gemv_store(w, attn_s[m], ppart + ((size_t)kvh * NEW + m) * pN, pN, n0, lane);
+}
+
+void launch_cp_attn_kvh(const CpAttnOprojArgs& a, int n_new, float* part, hipStream_t s) {
+    if (!cp_attn_oproj_ok(a, n_new) || part == nullptr) throw Error("cp_attn_kvh: unsupported shape");
+    const int U = a.base <= 4 ? 1 : (a.base <= 8 ? 2 : (a.base <= 12 ? 3 : 4));
+    const dim3 grid(((a.N + KVH_COLS - 1) / KVH_COLS) * 8), block(256);
+#define Q3_CAK(NEW, UU) hipLaunchKernelGGL((k_cp_attn_kvh<NEW, UU>), grid, block, 0, s, a.W, a.qkv, (const float*)a.kc, (const float*)a.vc, part, \
+        a.rope_cos, a.rope_sin, (uint32_t)a.base | (uint32_t)a.page_tokens << 16, (uint32_t)a.N, a)
+    if (n_new == 1) { if (U == 1) Q3_CAK(1, 1); else if (U == 2) Q3_CAK(1, 2); else if (U == 3) Q3_CAK(1, 3); else Q3_CAK(1, 4); }
+    else { if (U == 1) Q3_CAK(2, 1); else if (U == 2) Q3_CAK(2, 2); else Q3_CAK(2, 3); }   // cp_attn_oproj_ok: two new rows only over <= 12 cached tokens
+#undef Q3_CAK
+    Q3_HIP_CHECK(hipGetLastError());
+}
+
+// The talker's o_proj after split-T attention (b = 1, one row): workgroup (c, h) merges the split partials of h's two query heads
+// only, then does the same K-slice GEMV.  Thread t merges 8 dims (t & 31) of the slice over splits (t >> 5) + 8 q, q < 8 — the 64
+// splits the engine allows in one memory round — and the 8 split groups meet in LDS in a fixed order.  pos: the row's position
+// (pos_dev[slot] when given), which sets the live splits nact = pos / chunk + 1.
+__global__ __launch_bounds__(256) void k_oproj_kvh(const bf16_t* pW, const float* ppo, const float* ppm, const float* ppl, float* ppart,
+                                                   const int* ppos_dev, int ppos, int pS, int pchunk, int pN, int pK, int pd) {
+    constexpr int NKV = 8, G = 2, KS = 256, SG = 8, CQ = 8;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kvh = blockIdx.x % NKV, chunk = blockIdx.x / NKV;
+    const int n0 = chunk * KVH_COLS + wave * 8;
+    __shared__ float sm[SG][32], sl[SG][32];
+    __shared__ float so[SG][32][8];
+    __shared__ float xs[KS];
+
+    const int pos = ppos_dev ? ppos_dev[0] : ppos;   // scalar load, issued ahead of the weights
+    uint4 w[4];
+    kvh_load_w(w, pW, pN, pK, n0, kvh * KS, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    int nact = pos / pchunk + 1;
+    nact = nact < pS ? nact : pS;
+    const int eg = tid & 31, sg = tid >> 5;
+    const int head = kvh * G + (eg >> 4), e0 = (eg & 15) * 8;
+    const size_t idx = (size_t)head * pS;
+    float pmv[CQ], plv[CQ];
+    float4 o0[CQ], o1[CQ];
+#pragma unroll
+    for (int q = 0; q < CQ; ++q) {   // clamped addresses, zero weight past nact
+        int sp = sg + SG * q;
+        sp = sp < nact ? sp : nact - 1;
+        pmv[q] = ppm[idx + sp]; plv[q] = ppl[idx + sp];
+        o0[q] = *reinterpret_cast<const float4*>(ppo + (idx + sp) * pd + e0);
+        o1[q] = *reinterpret_cast<const float4*>(ppo + (idx + sp) * pd + e0 + 4);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    float mx = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < CQ; ++q) if (sg + SG * q < nact) mx = fmaxf(mx, pmv[q]);
+    float L = 0.f, O[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < CQ; ++q) {
+        const float wgt = sg + SG * q < nact ? __expf(pmv[q] - mx) : 0.f;
+        L += wgt * plv[q];
+        O[0] += wgt * o0[q].x; O[1] += wgt * o0[q].y; O[2] += wgt * o0[q].z; O[3] += wgt * o0[q].w;
+        O[4] += wgt * o1[q].x; O[5] += wgt * o1[q].y; O[6] += wgt * o1[q].z; O[7] += wgt * o1[q].w;
+    }
+    sm[sg][eg] = mx; sl[sg][eg] = L;
+    *reinterpret_cast<float4*>(&so[sg][eg][0]) = make_float4(O[0], O[1], O[2], O[3]);
+    *reinterpret_cast<float4*>(&so[sg][eg][4]) = make_float4(O[4], O[5], O[6], O[7]);
+    __syncthreads();
+    if (tid < 32) {   // split groups 0..7 in order (group 0 always holds split 0: its max is finite)
+        float m = sm[0][eg];
+#pragma unroll
+        for (int g = 1; g < SG; ++g) m = fmaxf(m, sm[g][eg]);
+        float l = 0.f, o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int g = 0; g < SG; ++g) {
+            const float wgt = sm[g][eg] == -INFINITY ? 0.f : __expf(sm[g][eg] - m);
+            l += wgt * sl[g][eg];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] += wgt * so[g][eg][j];
+        }
+        const float il = 1.0f / l;
+        float* dst = &xs[eg * 8];
+        *reinterpret_cast<float4*>(dst) = make_float4(o[0] * il, o[1] * il, o[2] * il, o[3] * il);
+        *reinterpret_cast<float4*>(dst + 4) = make_float4(o[4] * il, o[5] * il, o[6] * il, o[7] * il);
+    }
+    __syncthreads();
+    kvh_gemv_store(w, xs, ppart + (size_t)kvh * pN, pN, n0, lane);
+}
+
+bool oproj_kvh_ok(const GemvArgs& a) {
+    return a.M == 1 && a.po && a.pm && a.pl && a.pheads == 16 && a.pd == 128 && a.K == 2048 && a.pS >= 1 && a.pS <= 64 && a.pchunk >= 1 &&
+           a.pn_new == 1 && a.N >= 1 && a.epi == EPI_RESIDUAL && a.gamma == nullptr;
+}
+void launch_oproj_kvh(const GemvArgs& a, float* part, hipStream_t s) {
+    if (!oproj_kvh_ok(a) || part == nullptr) throw Error("oproj_kvh: unsupported shape");
+    const dim3 grid(((a.N + KVH_COLS - 1) / KVH_COLS) * 8), block(256);
+    hipLaunchKernelGGL(k_oproj_kvh, grid, block, 0, s, a.W, a.po, a.pm, a.pl, part, a.ppos_dev ? a.ppos_dev + a.pslot_offset : nullptr, a.ppos_scalar,
+                       a.pS, a.pchunk, a.N, a.K, a.pd);
+    Q3_HIP_CHECK(hipGetLastError());
 }
 
 // ================================================================================================

@@ -192,6 +192,7 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
     attn_keep_splits = knob("Q3TTS_ATTN_KEEP_SPLITS") != nullptr;
     if (const char* sv = knob("Q3TTS_ATTN_STREAM")) attn_stream = atoi(sv) != 0;
     if (const char* sv = knob("Q3TTS_ATTN_STREAM_ONE")) attn_stream_one = atoi(sv) != 0;
+    if (const char* sv = knob("Q3TTS_KVH_OPROJ")) kvh_oproj = atoi(sv) != 0;
     null_stream = getenv("Q3TTS_NULL_STREAM") && getenv("Q3TTS_NULL_STREAM")[0] == '1';
     if (null_stream) { stream = nullptr; flags |= Q3TTS_FLAG_NO_GRAPH; }
     else if (const char* cm = knob("Q3TTS_STREAM_CU_MASK")) {   // experiment aid (tools/overlap_probe.py): this engine's stream on a subset of the CUs;
@@ -270,6 +271,8 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
     pl1h = (bf16_t*)dmalloc((size_t)rows_max * ldp * 2); pl1l = (bf16_t*)dmalloc((size_t)rows_max * ldp * 2);
     slab_d = fm((size_t)16 * rows_max * H);
     qkv_slab_d = fm((size_t)4 * rows_max * std::max(QKV, QKVp));
+    oproj_part_d = fm((size_t)8 * 2 * std::max(H, Hc));
+    xmid_d = fm((size_t)2 * std::max(H, Hc));
     {   // seam flag lines: <= 3 seam launches per layer pass, <= (ffn / 64) x 2 row blocks units of 16 words (one 64-byte line) each
         const size_t per_launch = (size_t)(std::max(std::max(c.ffn, c.cp_ffn), H) / 64 + 1) * 2 * 16;
         const size_t launches = (size_t)3 * ((size_t)c.n_layers + (size_t)(c.n_groups - 1) * c.cp_layers) + 8;
@@ -582,14 +585,22 @@ bool Engine::run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new,
             f.q_norm = w.q_norm; f.k_norm = w.k_norm; f.eps = W.eps; f.rope_cos = W.rope_cos; f.rope_sin = W.rope_sin;
             f.scale = 1.0f / sqrtf((float)W.d); f.nq = W.nq; f.nkv = W.nkv; f.d = W.d; f.W = w.o; f.K = AO; f.N = W.H; f.x = x; f.ldx = ldx;
             if (cp_attn_oproj_ok(f, n_new)) {
-                launch_cp_attn_oproj(f, n_new, stream);
                 GemvArgs fg;
                 fg.W = w.gate; fg.W2 = w.up; fg.x = x; fg.ldx = ldx; fg.gamma = w.post_norm; fg.eps = W.eps; fg.out = act; fg.ldo = W.ffn;
                 fg.M = M; fg.N = W.ffn; fg.K = W.H; fg.epi = EPI_SWIGLU; fg.nt = W.nt;
-                launch_gemv(fg, stream);
                 GemvArgs dg;
                 dg.W = w.down; dg.x = act; dg.ldx = W.ffn; dg.res = x; dg.ldres = ldx; dg.out = x; dg.ldo = ldx;
                 dg.M = M; dg.N = W.H; dg.K = W.ffn; dg.epi = EPI_RESIDUAL; dg.nt = W.nt;
+                // o_proj split by kv head: 8 partial rows, summed into x by the gate/up launch, which leaves x + o_proj in xmid_d for down
+                fg.psum = oproj_part_d; fg.xmid = xmid_d;
+                if (kvh_oproj && gemv_fast_path(fg)) {
+                    launch_cp_attn_kvh(f, n_new, oproj_part_d, stream);
+                    dg.res = xmid_d; dg.ldres = W.H;
+                } else {
+                    fg.psum = nullptr; fg.xmid = nullptr;
+                    launch_cp_attn_oproj(f, n_new, stream);
+                }
+                launch_gemv(fg, stream);
                 launch_gemv(dg, stream);
                 continue;
             }
@@ -669,19 +680,31 @@ bool Engine::run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new,
         o.M = M; o.N = W.H; o.K = AO; o.epi = EPI_RESIDUAL; o.nt = W.nt;
         o.po = W.po; o.pm = W.pm; o.pl = W.pl; o.pS = W.n_splits; o.pchunk = W.chunk; o.pn_new = n_new; o.pslot_offset = slot_offset;
         o.pheads = W.nq; o.pd = W.d; o.ppos_dev = pos_dev; o.ppos_scalar = pos_scalar;
-        if (direct_rows) { o.po = nullptr; o.pm = nullptr; o.pl = nullptr; }
-        else if (!gemv_fast_path(o)) { // partials -> attn rows, then a GEMV without the combine prologue
-            launch_attn_combine(a, stream);
-            o.po = nullptr; o.pm = nullptr; o.pl = nullptr;
-        }
-        launch_gemv(o, stream);
         GemvArgs f;
         f.W = w.gate; f.W2 = w.up; f.x = x; f.ldx = ldx; f.gamma = w.post_norm; f.eps = W.eps; f.out = act; f.ldo = W.ffn;
         f.M = M; f.N = W.ffn; f.K = W.H; f.epi = EPI_SWIGLU; f.nt = W.nt;
-        launch_gemv(f, stream);
         GemvArgs d;
         d.W = w.down; d.x = act; d.ldx = W.ffn; d.res = x; d.ldres = ldx; d.out = x; d.ldo = ldx;
         d.M = M; d.N = W.H; d.K = W.ffn; d.epi = EPI_RESIDUAL; d.nt = W.nt;
+        // one row over split-T partials: the o_proj launch merges and projects per kv head (partial rows), gate/up sums them into x
+        bool kvh = false;
+        if (!direct_rows && kvh_oproj && W.nkv == 8 && W.nq == 16 && oproj_kvh_ok(o) && gemv_fast_path(o)) {
+            f.psum = oproj_part_d; f.xmid = xmid_d;
+            kvh = gemv_fast_path(f);
+            if (!kvh) { f.psum = nullptr; f.xmid = nullptr; }
+        }
+        if (kvh) {
+            launch_oproj_kvh(o, oproj_part_d, stream);
+            d.res = xmid_d; d.ldres = W.H;
+        } else {
+            if (direct_rows) { o.po = nullptr; o.pm = nullptr; o.pl = nullptr; }
+            else if (!gemv_fast_path(o)) { // partials -> attn rows, then a GEMV without the combine prologue
+                launch_attn_combine(a, stream);
+                o.po = nullptr; o.pm = nullptr; o.pl = nullptr;
+            }
+            launch_gemv(o, stream);
+        }
+        launch_gemv(f, stream);
         launch_gemv(d, stream);
     }
     return mfma && final_gamma != nullptr;

@@ -236,6 +236,10 @@ public:
     float* gu_slab_d = nullptr;  // gate | up split-K partial sums, 2 x [<=4][rows][ffn]
     float* cp_logit_slab_d = nullptr; // split-K partial sums of the batched predictor heads [4][B][sub_vocab]: the sampler sums them
     float* qkv_slab_d = nullptr; // split-K partial sums of the QKV projection [<=4][rows][QKV]
+    // o_proj split by kv head (b = 1, both stacks): the 8 heads' partial rows [8][<= 2 rows][H] that the gate/up GEMV adds to x, and the sum
+    // x + o_proj [<= 2][H] it leaves for the down projection's residual operand
+    float *oproj_part_d = nullptr, *xmid_d = nullptr;
+    bool kvh_oproj = true;       // Q3TTS_KVH_OPROJ=0 at engine creation: o_proj keeps the whole K in one launch (k_cp_attn_oproj / COMB GEMV; A/B knob, tests' second path)
     // split-K seam of the batched step (GemmArgs::seam): arrival / claim counters, one region per seam launch of the step (generation-valued words:
     // never reset), and the per-(row, 64-column tile) sums of squares behind the two residual seams of a layer
     unsigned* seam_cnt_d = nullptr; size_t seam_cnt_words = 0, seam_cnt_used = 0;
