@@ -47,7 +47,15 @@ typedef struct q3tts_config {
     int32_t cp_hidden;
 } q3tts_config;
 
-/* SamplingParams, reference src/tts_onnx.h:99-105 (repetition_penalty is never read there) */
+/* SamplingParams, reference src/tts_onnx.h:99-105.  The reference declares repetition_penalty and never reads it; here it is the
+ * standard logits processor (transformers RepetitionPenaltyLogitsProcessor) on the FIRST codebook: for every code0 id the utterance
+ * has emitted so far (frames 0 .. n-1 of this utterance; the prompt contributes nothing, an id seen many times counts once) the raw
+ * fp32 logit becomes x > 0 ? x / p : x * p — before the special-token suppression, temperature, top-k and top-p.  The 15 sub-codes
+ * (other codebooks, a separate predictor) are not penalised.  1.0 and 0.0 (a zero-initialised struct) switch it off: the output is
+ * then bit-identical to an engine without the field.  0 < p < 1 rewards repeats.  A negative or non-finite value is refused by every
+ * entry point that starts a generation or samples with a history ("repetition_penalty must be positive").  It applies in the fused
+ * generation (q3tts_slot_begin + q3tts_decode_steps, q3tts_synthesize_*) and in q3tts_sample_hist_*; q3tts_sample_host / _dev and
+ * q3tts_code_predictor_dev have no code0 history and ignore it. */
 typedef struct q3tts_sampling {
     float temperature, top_p;
     int32_t top_k;
@@ -191,6 +199,14 @@ int q3tts_sample_dev(q3tts_engine* e, const float* logits, int batch, int n, con
 /* sample_token, tts_onnx.cpp:878-905, on device; u in [0,1) replaces the mt19937 draw.
  * suppress != 0 applies the special-token suppression of tts_onnx.cpp:803-807 first. */
 int q3tts_sample_host(q3tts_engine* e, const float* logits, int n, const q3tts_sampling* p, float u, int suppress, int64_t* token);
+/* the same with p->repetition_penalty applied to the ids in history[0 .. n_history) first (duplicates count once, ids outside [0, n)
+ * are ignored): what the fused loop's code0 sampler computes for an utterance that has emitted those ids */
+int q3tts_sample_hist_host(q3tts_engine* e, const float* logits, int n, const q3tts_sampling* p, float u, int suppress,
+                           const int64_t* history, int n_history, int64_t* token);
+/* batch form on DEVICE pointers (see q3tts_sample_dev; returns at once): history[batch][hist_ld] int64, hist_len[batch] int32 (row b
+ * uses its first hist_len[b] <= hist_ld ids) */
+int q3tts_sample_hist_dev(q3tts_engine* e, const float* logits, int batch, int n, const q3tts_sampling* p, const float* u, int suppress,
+                          const int64_t* history, int hist_ld, const int32_t* hist_len, int64_t* ids, void* stream);
 float q3tts_rng_uniform(uint64_t seed, uint32_t stream, uint32_t frame, uint32_t group);
 
 /* ---- host logic of the path, mirrored (build_prompt_embeddings, tts_onnx.cpp:442-539) ---- */

@@ -1,5 +1,5 @@
 // leaxer-tts — command line of the MI355X engine.  Flag set of the reference CLI
-// (reference src/main_onnx.cpp:60-77, 99-124): -m -p -o --lang --ref --temp --top-k --top-p --max-tokens -h,
+// (reference src/main_onnx.cpp:60-77, 99-124): -m -p -o --lang --ref --temp --top-k --top-p --max-tokens -h, plus --rep-penalty (an extension),
 // unknown flags ignored, 16-bit mono WAV at 24 kHz (clip to [-1,1], truncate x*32767).  Additions:
 // --tokens "id,id,..." (pre-tokenised text between TTS_BOS and TTS_EOS, bypassing vocab.json/merges.txt),
 // --seed N.
@@ -43,6 +43,7 @@ static void usage(const char* prog) {
     printf("  --ref PATH            reference audio for voice clone (WAV; resampled to 24 kHz, ECAPA speaker encoder on the GPU)\n");
     printf("  --temp FLOAT          temperature (default: 0.8; 0 samples at T=1 like the reference, use --top-k 1 for greedy)\n");
     printf("  --top-k N             top-k (default: 50)\n  --top-p FLOAT         top-p (default: 0.95)\n");
+    printf("  --rep-penalty FLOAT   repetition penalty on the first codebook's ids (default: 1.0 = off; not a flag of the reference CLI)\n");
     printf("  --max-tokens N        max codec frames (default: 2048)\n  --seed N              sampling seed (default: 0)\n");
     printf("  --stream-chunk N      with --tokens: decode audio every N frames while generating (same samples as the one-shot decode)\n  -h, --help\n");
 }
@@ -74,6 +75,7 @@ int main(int argc, char** argv) {
         else if (a == "--temp" && more) sp.temperature = (float)atof(argv[++i]);
         else if (a == "--top-k" && more) sp.top_k = atoi(argv[++i]);
         else if (a == "--top-p" && more) sp.top_p = (float)atof(argv[++i]);
+        else if (a == "--rep-penalty" && more) sp.repetition_penalty = (float)atof(argv[++i]);
         else if (a == "--max-tokens" && more) sp.max_new_tokens = atoi(argv[++i]);
         else if (a == "--seed" && more) seed = strtoull(argv[++i], nullptr, 10);
         else if (a == "--stream-chunk" && more) stream_chunk = atoi(argv[++i]);

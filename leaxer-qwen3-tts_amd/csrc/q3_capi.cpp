@@ -318,6 +318,15 @@ int q3tts_sample_host(q3tts_engine* h, const float* logits, int n, const q3tts_s
     Q3_API_BEGIN(h) h->e->sample(logits, n, *p, u, suppress, token); return 0; Q3_API_END(h)
 }
 
+int q3tts_sample_hist_host(q3tts_engine* h, const float* logits, int n, const q3tts_sampling* p, float u, int suppress,
+                           const int64_t* history, int n_history, int64_t* token) {
+    Q3_API_BEGIN(h)
+    if (!logits || !p || !token) throw q3::Error("sample_hist: null argument");
+    h->e->sample_hist(logits, n, *p, u, suppress, history, n_history, token);
+    return 0;
+    Q3_API_END(h)
+}
+
 static uint64_t mix64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -410,6 +419,7 @@ int q3tts_synthesize_schedule_host(q3tts_engine* h, int n_utt, const int64_t* id
     if (n_utt <= 0) return 0;
     if (!ids || !offsets || !p) throw q3::Error("synthesize: null argument");
     if (pcm_cap < 0) throw q3::Error("synthesize: negative pcm_cap");
+    (void)Engine::checked_penalty(*p);   // refused before any slot is touched
     for (int b = 0; b < B; ++b) e.slot_release(b);
     const int row_frames = std::max(1, std::min(p->max_new_tokens, e.max_frames_cap));
     e.codec_async_prepare(row_frames, n_utt);
@@ -673,6 +683,11 @@ int q3tts_code_predictor_dev(q3tts_engine* h, const float* last_hidden, const in
 int q3tts_sample_dev(q3tts_engine* h, const float* logits, int batch, int n, const q3tts_sampling* p, const float* u, int suppress, int64_t* ids, void* stream) {
     if (!p) return -1;
     Q3_DEV_CALL(h, stream, h->e->sample_dev(logits, batch, n, *p, u, suppress, ids))
+}
+int q3tts_sample_hist_dev(q3tts_engine* h, const float* logits, int batch, int n, const q3tts_sampling* p, const float* u, int suppress,
+                          const int64_t* history, int hist_ld, const int32_t* hist_len, int64_t* ids, void* stream) {
+    if (!p) return -1;
+    Q3_DEV_CALL(h, stream, h->e->sample_hist_dev(logits, batch, n, *p, u, suppress, history, hist_ld, hist_len, ids))
 }
 int q3tts_measure_skip_frames(q3tts_engine* h, int n_frames) {
     Q3_API_BEGIN(h)

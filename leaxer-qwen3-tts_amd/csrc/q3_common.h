@@ -214,7 +214,7 @@ struct SlotState { // device-resident per-slot generation state
     int32_t ignore_eos;
     float temperature, top_p;
     uint32_t stream_id;
-    uint32_t pad0;
+    float rep_penalty;    // repetition penalty on code0 (group 0 sampler); 0 and 1 = off
     uint64_t seed;
     uint32_t pad1[2]; // 64 bytes: read by the sampler as four 16-byte loads
 };
@@ -233,6 +233,13 @@ struct SampleArgs {
     const float* u_dev = nullptr;   // standalone mode, optional: row b draws with u_dev[b] instead of u (q3tts_sample_dev)
     int suppress = 0;
     int64_t* token_out = nullptr;
+    // repetition penalty (group 0 / standalone rows only; both null -> the sampler instantiation without the penalty step).
+    // generation mode: seen = per-slot bitmaps of the code0 ids the utterance has emitted, [nb][seen_ld] words, seen_ld >= ceil(V / 32);
+    // the sampler reads row b, penalises by SlotState::rep_penalty and sets the bit of the id it records.
+    // standalone mode: hist = ids already used, [nb][hist_ld] (ids outside [0, V) are ignored), hist_len[b] of them valid; rep_penalty.
+    uint32_t* seen = nullptr; int seen_ld = 0;
+    const int64_t* hist = nullptr; int hist_ld = 0; const int32_t* hist_len = nullptr;
+    float rep_penalty = 1.f;
     // fused epilogue (generation mode)
     const bf16_t* embed = nullptr; // [V][H] embedding table of the sampled codebook
     int H = 0;

@@ -2593,7 +2593,11 @@ static __device__ __forceinline__ float kth_largest_of_lanes(float v, int k) {
 #else
 #define SP_MARK(k) do { } while (0)
 #endif
-template <bool SLABS, int PW>   // SLABS: the logits row is the ordered sum of a.nslab (<= 4) split-K partial slabs of the head projection
+// PEN: the repetition-penalty step (transformers' RepetitionPenaltyLogitsProcessor on the raw logits: x > 0 ? x / p : x * p for every id the
+// utterance has used).  Generation mode reads the slot's seen bitmap (SampleArgs::seen) in round trip 1 and sets the bit of the id it
+// records; standalone mode builds the same bitmap in LDS from SampleArgs::hist.  The launcher picks PEN only where a bitmap or a history
+// was passed (the code0 sampler of the fused step, q3tts_sample_hist_*): the other fifteen samplers of a frame run the code without it.
+template <bool SLABS, int PW, bool PEN>   // SLABS: the logits row is the ordered sum of a.nslab (<= 4) split-K partial slabs of the head projection
 __global__ __launch_bounds__(256) void k_sample(const float* plogits, SlotState* pst, int pld, int pV, SampleArgs a) {   // leading scalars: preloaded (see k_gemv1)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2610,6 +2614,7 @@ __global__ __launch_bounds__(256) void k_sample(const float* plogits, SlotState*
     __shared__ __attribute__((aligned(16))) float sb[3][64];                  // wave 0: staging of the left-fold sums (draw_small)
     __shared__ float sh_f[4];
     __shared__ int sh_i[4];
+    __shared__ uint32_t hbits[PEN ? SAMP_MAXV / 32 : 1];   // standalone mode: the history as a bitmap
 
     SP_MARK(0);
     if (a.step_gen != nullptr && b == 0 && tid == 0) *a.step_gen += 1u;   // first launch of a step: the generation its seam flags will carry
@@ -2650,6 +2655,20 @@ __global__ __launch_bounds__(256) void k_sample(const float* plogits, SlotState*
             x[jj] = lg[i < V ? i : V - 1];           // clamped, unconditional
         }
     }
+    // seen-bitmap words of this wave's slices (element i -> word i >> 5: two addresses per wave and slice), in the same round trip.
+    // Unconditional like the logits loads: without a bitmap (standalone mode) the address falls into the logits row, whose V words
+    // cover the ceil(V / 32) read here, and the words are replaced from LDS below.
+    uint32_t bw[PEN ? PW : 1];
+    uint32_t* seen_r = nullptr;
+    if (PEN) {
+        seen_r = a.seen ? a.seen + (size_t)b * a.seen_ld : nullptr;
+        const uint32_t* wsrc = seen_r ? seen_r : reinterpret_cast<const uint32_t*>(lg);
+#pragma unroll
+        for (int jj = 0; jj < PW; ++jj) {
+            const int i = (wave * PW + jj) * 64 + lane;
+            bw[jj] = wsrc[(i < V ? i : V - 1) >> 5];
+        }
+    }
     __builtin_amdgcn_sched_barrier(0);
     if (st) {
         if (!sl.active || sl.finished) return;
@@ -2660,9 +2679,38 @@ __global__ __launch_bounds__(256) void k_sample(const float* plogits, SlotState*
         suppress = a.group == 0;
         keep_eos = !sl.ignore_eos;
     }
+    float pen = a.rep_penalty;
+    if (PEN) {
+        if (st) pen = sl.rep_penalty;
+        if (!seen_r) {   // standalone mode (block-uniform): history ids -> LDS bitmap -> this thread's words
+            const int nh = a.hist_len ? min(max(a.hist_len[b], 0), a.hist_ld) : 0;
+            const int64_t* hr = a.hist + (size_t)b * a.hist_ld;
+            if (tid < SAMP_MAXV / 32) hbits[tid] = 0u;
+            __syncthreads();
+            for (int k = tid; k < nh; k += 256) {
+                const int64_t id = hr[k];
+                if (id >= 0 && id < V) atomicOr(&hbits[id >> 5], 1u << (id & 31));
+            }
+            __syncthreads();
+#pragma unroll
+            for (int jj = 0; jj < PW; ++jj) bw[jj] = hbits[((wave * PW + jj) * 64 + lane) >> 5];
+        }
+    }
+    const bool pen_on = PEN && pen != 0.0f && pen != 1.0f;   // 0 (a zero-initialised struct) and 1 switch the penalty off
     SP_MARK(1);
     const unsigned long long lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));
 
+    // repetition penalty on the raw logits of the ids already used, before suppression and temperature: one IEEE divide or multiply per
+    // element.  Block-uniform branch: a slot with the penalty off (and every frame's first launch of such a slot) skips the divisions.
+    if (PEN && pen_on) {
+#pragma unroll
+        for (int jj = 0; jj < PW; ++jj) {
+            const float v = x[jj];
+            const bool hit = (bw[jj] >> (lane & 31)) & 1u;
+            const float vp = v > 0.0f ? v / pen : v * pen;
+            x[jj] = hit ? vp : v;
+        }
+    }
     // suppress (:803-807) + temperature (:882-884)
     const bool use_temp = temperature > 0.0f && temperature != 1.0f;
     float lmax = -INFINITY;
@@ -2906,6 +2954,7 @@ __global__ __launch_bounds__(256) void k_sample(const float* plogits, SlotState*
     // ---- fused epilogue of the generation loop (tts_onnx.cpp:812-842, 864-868), all 256 threads ----
     if (a.group == 0 && tok == a.eos_id) { if (tid == 0) st->finished = 1; return; } // :812 — no frame recorded
     if (tid == 0) a.codes[((size_t)b * a.max_frames_cap + frame) * a.n_groups + a.group] = tok;
+    if (PEN && seen_r && tid == 0) atomicOr(seen_r + (tok >> 5), 1u << (tok & 31));   // this workgroup alone touches the slot's bitmap; launches of a slot are stream-ordered
     const bf16_t* er = a.embed + (size_t)tok * a.H;
     const bool last_group = a.group == a.n_groups - 1;
     const float* text = nullptr;
@@ -2996,9 +3045,14 @@ void launch_sample(const SampleArgs& a, hipStream_t s) {
     if (a.nslab < 1 || a.nslab > 4) throw Error("sample: 1..4 logits slabs");
     if (a.pl_h && (a.H > 2048 || a.H % 4 || !a.pl_l || !a.gamma0 || !a.ssq_out || a.ssq_nt < 1 || a.ssq_nt > 256 || a.pl_ldp % 4 || (a.lh && a.pl_row_add < 1)))
         throw Error("sample: bad plane-output arguments");
-#define Q3_SAMP(SL, PW_) hipLaunchKernelGGL((k_sample<SL, PW_>), dim3(a.nb), dim3(256), 0, s, a.logits, a.st, a.ld, a.V, a)
-    if (a.nslab > 1) { if (a.V <= 2048) Q3_SAMP(true, 8); else if (a.V <= 3072) Q3_SAMP(true, 12); else Q3_SAMP(true, 16); }
-    else { if (a.V <= 2048) Q3_SAMP(false, 8); else if (a.V <= 3072) Q3_SAMP(false, 12); else Q3_SAMP(false, 16); }
+    const bool pen = a.seen != nullptr || a.hist != nullptr;
+    if (pen && a.nslab > 1) throw Error("sample: the repetition penalty takes plain logits rows (no split-K slabs)");
+    if (a.seen && (!a.st || a.group != 0 || a.seen_ld < (a.V + 31) / 32)) throw Error("sample: bad seen-bitmap arguments");
+    if (a.hist && (a.st || a.seen || a.hist_ld < 0 || !a.hist_len)) throw Error("sample: bad history arguments");
+#define Q3_SAMP(SL, PW_, PEN_) hipLaunchKernelGGL((k_sample<SL, PW_, PEN_>), dim3(a.nb), dim3(256), 0, s, a.logits, a.st, a.ld, a.V, a)
+    if (a.nslab > 1) { if (a.V <= 2048) Q3_SAMP(true, 8, false); else if (a.V <= 3072) Q3_SAMP(true, 12, false); else Q3_SAMP(true, 16, false); }
+    else if (pen) { if (a.V <= 2048) Q3_SAMP(false, 8, true); else if (a.V <= 3072) Q3_SAMP(false, 12, true); else Q3_SAMP(false, 16, true); }
+    else { if (a.V <= 2048) Q3_SAMP(false, 8, false); else if (a.V <= 3072) Q3_SAMP(false, 12, false); else Q3_SAMP(false, 16, false); }
 #undef Q3_SAMP
 }
 

@@ -296,6 +296,9 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
     st_d = (SlotState*)dmalloc((size_t)B * sizeof(SlotState));
     st_h.assign(B, SlotState{});
     Q3_HIP_CHECK(hipMemsetAsync(st_d, 0, (size_t)B * sizeof(SlotState), stream));
+    seen_ld = (c.vocab + 31) / 32;   // repetition penalty: one bit per code0 id and slot, cleared when the slot is armed
+    seen_d = (uint32_t*)dmalloc((size_t)B * seen_ld * sizeof(uint32_t));
+    Q3_HIP_CHECK(hipMemsetAsync(seen_d, 0, (size_t)B * seen_ld * sizeof(uint32_t), stream));
     active_d = (int32_t*)dmalloc(sizeof(int32_t));
     Q3_HIP_CHECK(hipHostMalloc((void**)&active_h, sizeof(int32_t)));
 
@@ -373,6 +376,7 @@ Engine::~Engine() {
     for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
     if (proj_ids_d) (void)hipFree(proj_ids_d);
     if (proj_out_d) (void)hipFree(proj_out_d);
+    if (hist_d) (void)hipFree(hist_d);
     codec_free();
     speaker_free();
     free_packed_weights();
@@ -1013,6 +1017,53 @@ void Engine::sample_dev(const float* logits, int nb, int V, const q3tts_sampling
     launch_sample(a, stream);
 }
 
+// q3tts_sampling::repetition_penalty as the sampler takes it: 0 (a zero-initialised struct) and 1 are "off", anything else must be a
+// positive finite factor (below 1 rewards repeats, as the logits processor it restates permits)
+float Engine::checked_penalty(const q3tts_sampling& p) {
+    const float r = p.repetition_penalty;
+    if (!(r >= 0.0f) || std::isinf(r)) throw Error("repetition_penalty must be positive");
+    return r;
+}
+
+// sample_dev with a repetition penalty: row b's history is hist[b * hist_ld .. + hist_len[b]) (device ids; outside [0, V): ignored)
+void Engine::sample_hist_dev(const float* logits, int nb, int V, const q3tts_sampling& p, const float* u, int suppress, const int64_t* hist, int hist_ld,
+                             const int32_t* hist_len, int64_t* ids) {
+    if (nb < 1 || nb > 65535) throw Error("sample_hist_dev: batch out of range");
+    if (V < 1 || V > 4096) throw Error("sample: n out of range");
+    if (!logits || !u || !ids || !hist || !hist_len || hist_ld < 0) throw Error("sample_hist_dev: null argument");
+    SampleArgs a;
+    a.logits = logits; a.ld = V; a.V = V; a.nb = nb; a.sup_begin = c.suppress_begin; a.sup_end = c.suppress_end; a.eos_id = c.codec_eos;
+    a.temperature = p.temperature; a.top_p = p.top_p; a.top_k = p.top_k; a.u_dev = u; a.suppress = suppress; a.token_out = ids;
+    a.hist = hist; a.hist_ld = hist_ld; a.hist_len = hist_len; a.rep_penalty = checked_penalty(p);
+    launch_sample(a, stream);
+}
+
+void Engine::sample_hist(const float* logits, int n, const q3tts_sampling& p, float u, int suppress, const int64_t* hist, int n_hist, int64_t* tok) {
+    if (n < 1 || n > 4096) throw Error("sample: n out of range");
+    if (n_hist < 0 || (n_hist > 0 && !hist)) throw Error("sample_hist: bad history");
+    const float pen = checked_penalty(p);
+    const size_t need = (size_t)n_hist * sizeof(int64_t) + 16;   // the ids, then the length
+    if (need > hist_cap) {
+        sync();
+        if (hist_d) (void)hipFree(hist_d);
+        hist_d = nullptr; hist_cap = 0;
+        Q3_HIP_CHECK(hipMalloc((void**)&hist_d, need * 2));
+        hist_cap = need * 2;
+    }
+    const int32_t len = n_hist;
+    int32_t* len_d = reinterpret_cast<int32_t*>(hist_d + n_hist);
+    Q3_HIP_CHECK(hipMemcpyAsync(logits_p, logits, (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
+    if (n_hist > 0) Q3_HIP_CHECK(hipMemcpyAsync(hist_d, hist, (size_t)n_hist * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    Q3_HIP_CHECK(hipMemcpyAsync(len_d, &len, sizeof len, hipMemcpyHostToDevice, stream));
+    SampleArgs a;
+    a.logits = logits_p; a.ld = n; a.V = n; a.nb = 1; a.sup_begin = c.suppress_begin; a.sup_end = c.suppress_end; a.eos_id = c.codec_eos;
+    a.temperature = p.temperature; a.top_p = p.top_p; a.top_k = p.top_k; a.u = u; a.suppress = suppress; a.token_out = tok_d;
+    a.hist = hist_d; a.hist_ld = n_hist; a.hist_len = len_d; a.rep_penalty = pen;
+    launch_sample(a, stream);
+    Q3_HIP_CHECK(hipMemcpyAsync(tok, tok_d, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    sync();
+}
+
 void Engine::code_predictor(const float* seq, int n, int step, float* logits) {
     if (!finalized) throw Error("weights not finalized");
     if (n < 1 || n > 16 || step < 0 || step >= c.n_groups - 1) throw Error("code_predictor arguments out of range");
@@ -1148,7 +1199,7 @@ void Engine::predictor_passes(int nb, const SampleArgs& s0, bool sp0, bool spn, 
         s.logits = nsl > 1 ? cp_logit_slab_d : logits_cp; s.nslab = nsl; s.slab_stride = (size_t)nb * SV;
         s.ld = SV; s.V = SV; s.group = j + 1; s.embed = cp_embed_w[j];
         s.x_next = j + 1 < G - 1 ? x_cp1 : nullptr; s.ld_xnext = H;
-        s.pl_h = nullptr; s.lh = nullptr; s.step_gen = nullptr;
+        s.pl_h = nullptr; s.lh = nullptr; s.step_gen = nullptr; s.seen = nullptr;   // the penalty is the first codebook's alone
         if (spn && s.x_next) with_planes(s, 1, 0, nullptr, 0);
         launch_sample(s, stream);
         mark();
@@ -1162,6 +1213,7 @@ void Engine::record_step(int nb) {
     s0.group = 0; s0.n_groups = G; s0.st = st_d; s0.embed = codec_embed_w; s0.H = H;
     s0.x_next = x_cp + H; s0.ld_xnext = 2 * H; s0.sum = sum; s0.x_talk = x_talk; s0.trailing = trailing_d; s0.max_trailing = max_trailing;
     s0.tts_pad = tts_pad_d; s0.codes = codes_d; s0.max_frames_cap = max_frames_cap; s0.talker_pos = talker_pos_d;
+    s0.seen = seen_d; s0.seen_ld = seen_ld;   // code0 ids each slot has emitted: read (penalty) and updated by this sampler alone
     // stage_profile(): events between the stages of the step (eager launches only)
     size_t mk = 0;
     auto mark = [&]() { if (!stage_ev.empty()) Q3_HIP_CHECK(hipEventRecord(stage_ev[mk++], stream)); };
@@ -1299,6 +1351,7 @@ void Engine::slot_begin(int slot, const float* prompt, int S, const float* trail
 void Engine::slots_begin(const SlotInit* in, int n, const q3tts_sampling& p, uint64_t seed, int ignore_eos) {
     if (!finalized) throw Error("weights not finalized");
     const int H = c.hidden, V = c.vocab;
+    const float rep_penalty = checked_penalty(p);   // before anything is reserved or armed
     for (int i = 0; i < n; ++i) {
         if (in[i].slot < 0 || in[i].slot >= B) throw Error("slot out of range");
         if (in[i].n_trailing < 0 || in[i].n_trailing > max_trailing) throw Error("too many trailing text rows");
@@ -1374,7 +1427,9 @@ void Engine::slots_begin(const SlotInit* in, int n, const q3tts_sampling& p, uin
         SlotState& s = st_h[q.slot];
         s.n_frames = 0; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.trailing_len = q.n_trailing;
         s.max_frames = q.max_frames > 0 ? std::min(q.max_frames, p.max_new_tokens) : p.max_new_tokens;
-        s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.pad0 = 0; s.seed = seed;
+        s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
+        // a new utterance (a re-admission after a preemption included) starts with an empty code0 history: ordered before its first step
+        Q3_HIP_CHECK(hipMemsetAsync(seen_d + (size_t)q.slot * seen_ld, 0, (size_t)seen_ld * sizeof(uint32_t), stream));
         Q3_HIP_CHECK(hipMemcpyAsync(st_d + q.slot, &s, sizeof(SlotState), hipMemcpyHostToDevice, stream));
     }
     sync();

@@ -103,6 +103,7 @@ public:
     void talker_decode(int slot, const float* embed, float* logits, float* last_hidden);
     void code_predictor(const float* seq, int n, int step, float* logits);
     void sample(const float* logits, int n, const q3tts_sampling& p, float u, int suppress, int64_t* tok);
+    void sample_hist(const float* logits, int n, const q3tts_sampling& p, float u, int suppress, const int64_t* hist, int n_hist, int64_t* tok);   // + repetition penalty over the ids in hist
     void build_prompt(const int64_t* ids, int n_ids, int lang, const float* speaker, float* prompt, int* S,
                       float* trailing, int cap_rows, int* n_trailing);
     void build_prompts(const int64_t* ids, const int32_t* offsets, int n_utt, int lang, const float* const* speakers,
@@ -139,6 +140,9 @@ public:
     void code_predictor_dev(const float* last_hidden, const int64_t* code0, int nb, const q3tts_sampling& p, uint64_t seed, uint32_t stream0,
                             uint32_t frame, int32_t* sub);
     void sample_dev(const float* logits, int nb, int V, const q3tts_sampling& p, const float* u, int suppress, int64_t* ids);
+    void sample_hist_dev(const float* logits, int nb, int V, const q3tts_sampling& p, const float* u, int suppress, const int64_t* hist, int hist_ld,
+                         const int32_t* hist_len, int64_t* ids);
+    static float checked_penalty(const q3tts_sampling& p);   // throws unless repetition_penalty is 0 (off) or a positive finite factor
     void dev_scratch(int nb);                  // lazily allocated workspaces of the four calls above
     float* dev_logits_d = nullptr; int* dev_flags_d = nullptr; int32_t* dev_pos_d = nullptr; int32_t* dev_pos_dummy_d = nullptr;
     SlotState* dev_st_d = nullptr; int32_t* dev_codes_d = nullptr;
@@ -256,6 +260,8 @@ public:
     int32_t* talker_pos_d = nullptr;
     int* slot_map_d = nullptr;      // [128] slots of a batched prefill over scattered slots
     float* logits_g = nullptr;      // [128][vocab] its head output before the scatter
+    uint32_t* seen_d = nullptr; int seen_ld = 0;   // [B][seen_ld] bitmaps of the code0 ids each slot's utterance has emitted (repetition penalty)
+    int64_t* hist_d = nullptr; size_t hist_cap = 0; // sample_hist staging (grow-only): the history ids, then their count
     SlotState* st_d = nullptr;
     std::vector<SlotState> st_h;
     int32_t* active_d = nullptr;

@@ -38,7 +38,7 @@ struct SamplingParams {
     float temperature = config::DEFAULT_TEMPERATURE;
     float top_p = config::DEFAULT_TOP_P;
     int top_k = config::DEFAULT_TOP_K;
-    float repetition_penalty = 1.0f; // never read, as in the reference
+    float repetition_penalty = 1.0f; // on the first codebook's ids an utterance has emitted (include/q3tts.h: q3tts_sampling); 1 = off.  The reference declares it and never reads it
     int max_new_tokens = config::MAX_NEW_TOKENS;
 };
 

@@ -89,6 +89,7 @@ EXPORTS = [
     "q3tts_synthesize_clone_batch_host", "q3tts_synthesize_schedule_host", "q3tts_read_wav_host", "q3tts_resample_host", "q3tts_mel_host",
     "q3tts_has_speaker_encoder", "q3tts_speaker_encoder_host", "q3tts_extract_speaker_embedding_host",
     "q3tts_codec_decode_chunked_host", "q3tts_slot_codec_decode_range_host", "q3tts_slot_logits_host", "q3tts_step_logits_host",
+    "q3tts_sample_hist_host", "q3tts_sample_hist_dev",
 ]
 
 _lib = None
@@ -397,6 +398,16 @@ class Engine:
         self._ck(self.L.q3tts_sample_host(self.h, _p(a), a.size, C.byref(sp), C.c_float(u), int(suppress), C.byref(tok)))
         return int(tok.value)
 
+    def sample_hist(self, logits, sp, u, history, suppress=False):
+        """sample() with sp.repetition_penalty applied to the ids in `history` first (q3tts_sample_hist_host)"""
+        a = np.ascontiguousarray(logits, dtype=np.float32)
+        hist = np.ascontiguousarray(history, dtype=np.int64).reshape(-1)
+        tok = C.c_int64(0)
+        self.L.q3tts_sample_hist_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        self._ck(self.L.q3tts_sample_hist_host(self.h, _p(a), a.size, C.byref(sp), C.c_float(u), int(suppress), _p(hist) if hist.size else None,
+                                               hist.size, C.byref(tok)))
+        return int(tok.value)
+
     def build_prompt(self, ids, lang=0, speaker=None, cap_rows=1024):
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         prompt = np.zeros((16, self.cfg.hidden), np.float32)
@@ -566,6 +577,12 @@ class Engine:
     def sample_dev(self, logits_ptr, batch, n, sp, u_ptr, suppress, ids_ptr, stream=0):
         self.L.q3tts_sample_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         self._ck(self.L.q3tts_sample_dev(self.h, logits_ptr, batch, n, C.byref(sp), u_ptr, int(suppress), ids_ptr, stream or None))
+
+    def sample_hist_dev(self, logits_ptr, batch, n, sp, u_ptr, suppress, hist_ptr, hist_ld, hist_len_ptr, ids_ptr, stream=0):
+        self.L.q3tts_sample_hist_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
+        self._ck(self.L.q3tts_sample_hist_dev(self.h, logits_ptr, batch, n, C.byref(sp), u_ptr, int(suppress), hist_ptr, hist_ld, hist_len_ptr, ids_ptr,
+                                              stream or None))
 
     def poison_workspace(self):
         """test hook (FLAG_TEST_HOOKS engines): NaN bytes over the vocoder's reusable workspace (q3tts_test_poison_workspace)"""
