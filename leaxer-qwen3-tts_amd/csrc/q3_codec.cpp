@@ -169,7 +169,10 @@ void Engine::codec_finalize() {
             memcpy(&amax, &bits, sizeof amax);
             int e = 0;
             if (amax > 0.f && std::isfinite(amax)) (void)frexpf(amax, &e);   // amax = m * 2^e, m in [0.5, 1)
-            const int k = amax > 0.f ? 12 - e : 0;
+            // k <= 126: 2^k (the pre-scale) and 2^-k (the epilogue's acc_scale) both finite and normal.  A tensor whose largest magnitude is
+            // below 2^-115 would ask for more (2^k = inf: planes of inf / nan); it keeps 2^126 and sits lower in the planes instead, at
+            // an absolute resolution of 2^-150, beyond fp32's own.  e <= 128, so k >= -116 needs no bound.
+            const int k = amax > 0.f ? std::min(12 - e, 126) : 0;
             bf16_t *hi = nullptr, *lo = nullptr;   // one allocation, lo right behind hi: k_conv_split addresses both planes as base + 32-bit offset
             const size_t np = (n + 7) / 8 * 8;
             Q3_HIP_CHECK(hipMalloc((void**)&hi, 2 * np * sizeof(bf16_t)));

@@ -222,6 +222,11 @@ __global__ __launch_bounds__(256) void k_conv_mfma(ConvKArgs a) {
 // Range: weights are pre-scaled per tensor by a power of two (k_split_planes; undone in the epilogue) so their
 // low plane stays normal; activations beyond +-65504 would saturate the high plane — it is clamped, the low plane
 // takes the remainder (exact to +-131008), values the codec's audio-scale features never approach.
+// Supported weights: any finite fp32 tensor.  The pre-scale 2^k puts the largest magnitude in [2^11, 2^12) for tensors whose
+// largest magnitude is at least 2^-115; k is bounded at 126 (2^k and 2^-k finite and normal), so a tensor below that sits
+// lower in the planes, still resolved to 2^-150 absolute; an all-zero tensor takes k = 0.  Within one tensor an element
+// 2^-r below the largest keeps 22 bits up to r = 13 and 35 - r beyond (its low plane turns subnormal, step 2^-24 of the scaled
+// value; DESIGN.md section 4 has the measured table).
 // Workgroup tile TM x TN = (WM*MB*32) x (WN*NB*32); K is walked as (C_in chunk of 32) x (tap).  The activation
 // rows of a chunk are staged ONCE with their tap halo (rows m0-halo .. m0+TM) and split to hi/lo on the way into
 // LDS; every tap reads the same rows at a shifted offset, so a 7-tap conv reads and splits its input once, not

@@ -305,6 +305,7 @@ def test_codec_split_precision_matrix_path_full_size(full):
     err32 = float(np.sqrt(np.mean((pcm32 - ref) ** 2)))
     assert err32 < 1e-4 and float(np.sqrt(np.mean((pcm - pcm32) ** 2))) < 1e-4
     print("codec rms error vs oracle: split-fp16 %.3g, fp32-mfma %.3g, signal rms %.3g; weight tensors on 2 / 3 products: %s" % (err, err32, rms_ref, eng.codec_plane_stats()))
+    assert eng.codec_plane_stats()[1] == 0      # bf16-origin weights: the two-product kernels (tests/test_gpu_codec_fp32_weights.py has the three-product ones)
 
 
 def test_chunked_codec_full_size(full):
