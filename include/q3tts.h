@@ -271,6 +271,21 @@ int q3tts_has_speaker_encoder(q3tts_engine* e);
 int q3tts_speaker_encoder_host(q3tts_engine* e, const float* mel, int frames, float* embed);
 /* extract_speaker_embedding (tts_onnx.cpp:331-365): wav -> 24 kHz -> mel -> speaker encoder */
 int q3tts_extract_speaker_embedding_host(q3tts_engine* e, const char* wav_path, float* embed);
+/* The same front end on the GPU for reference audio that is already in memory (mono float samples, any rate; callers mix channels
+ * down as read_wav does).  Each call stages its audio in one pinned copy, runs on the engine's stream in a workspace the engine owns
+ * (grow-only, freed by q3tts_destroy; at most about 1 GiB per group of clips, larger batches are processed group after group) and
+ * ends with one stream synchronisation.  -1 with q3tts_last_error on failure; nothing is written to the outputs then. */
+/* io::resample (wav_reader.cpp:145-164) on the GPU: the same samples as q3tts_resample_host, bit for bit; returns the output length
+ * and writes min(length, cap) samples when out != NULL */
+int64_t q3tts_resample_gpu_host(q3tts_engine* e, const float* in, int64_t n, int32_t src_rate, int32_t dst_rate, float* out, int64_t cap);
+/* resample to 24 kHz (when sample_rate != 24000) + MelExtractor::extract on the GPU: mel[128][*frames]; mel == NULL only sizes.
+ * Needs finalized weights.  Differs from q3tts_mel_host by the rounding of logf only; -1 for an empty clip, as q3tts_mel_host. */
+int q3tts_mel_gpu_host(q3tts_engine* e, const float* audio, int64_t n, int32_t sample_rate, float* mel, int64_t cap, int32_t* frames);
+/* extract_speaker_embedding (tts_onnx.cpp:331-365) for n_clips clips at once: embeds[n_clips][spk_enc_dim].  Every clip needs 5 to
+ * 16384 mel frames (about 0.1 s to 175 s); an error names the clip index.  A clip's embedding does not depend on the rest of the
+ * batch, nor on how the batch was split into workspace groups. */
+int q3tts_speaker_embed_pcm_batch_host(q3tts_engine* e, int n_clips, const float* const* pcm, const int64_t* n_samples,
+                                       const int32_t* sample_rates, float* embeds);
 
 /* ---- text front end: the reference's byte-level BPE tokenizer ---- */
 /* Replaces leaxer_qwen::io::load_vocab / load_merges / is_tokenizer_ready / tokenize (reference

@@ -120,17 +120,10 @@ std::vector<float> resample_linear(const std::vector<float>& a, int src_rate, in
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-struct MelPlan {
-    MelSpec spec;
-    int n = 0, bins = 0;              // FFT length (power of two >= n_fft), kept bins
-    std::vector<float> window;
-    std::vector<float> tw_re, tw_im;  // exp(-2 pi i k / n), k < n/2
-    std::vector<uint32_t> rev;
-    std::vector<int> lo, mid, hi;     // triangle corners per mel band
-};
-
 float hz_to_mel(float hz) { return 2595.0f * log10f(1.0f + hz / 700.0f); }
 float mel_to_hz(float m) { return 700.0f * (powf(10.0f, m / 2595.0f) - 1.0f); }
+
+} // namespace
 
 MelPlan make_plan(const MelSpec& s) {
     MelPlan p;
@@ -166,6 +159,8 @@ MelPlan make_plan(const MelSpec& s) {
     p.hi.assign(corner.begin() + 2, corner.end());
     return p;
 }
+
+namespace {
 
 // in-place decimation-in-time radix-2 FFT on bit-reversed input
 void fft_pow2(const MelPlan& p, float* re, float* im) {

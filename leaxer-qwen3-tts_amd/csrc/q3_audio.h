@@ -20,6 +20,17 @@ struct MelSpec { // the settings of tts_onnx.cpp:347-354
     int sample_rate = 24000, n_fft = 1024, hop = 256, win = 1024, n_mels = 128;
     float fmin = 0.0f, fmax = 12000.0f;
 };
+// the tables of the extractor (window, FFT twiddles, bit reversal, triangle corners), computed once per MelSpec.  The GPU front end
+// (k_logmel, q3_speaker_kernels.hip) uploads exactly these, so the two implementations cannot drift.
+struct MelPlan {
+    MelSpec spec;
+    int n = 0, bins = 0;              // FFT length (power of two >= n_fft), kept bins
+    std::vector<float> window;
+    std::vector<float> tw_re, tw_im;  // exp(-2 pi i k / n), k < n/2
+    std::vector<uint32_t> rev;
+    std::vector<int> lo, mid, hi;     // triangle corners per mel band
+};
+MelPlan make_plan(const MelSpec& spec);
 // log-mel, layout [n_mels][frames] like the reference's MelExtractor::extract; *frames receives the frame count
 std::vector<float> log_mel(const std::vector<float>& audio, const MelSpec& spec, int* frames);
 

@@ -620,6 +620,24 @@ int q3tts_extract_speaker_embedding_host(q3tts_engine* h, const char* wav_path, 
     Q3_API_END(h)
 }
 
+// ---- the same front end on the GPU, for audio already in memory (q3_speaker.cpp) ----
+int64_t q3tts_resample_gpu_host(q3tts_engine* h, const float* in, int64_t n, int32_t src_rate, int32_t dst_rate, float* out, int64_t cap) {
+    Q3_API_BEGIN(h) return h->e->resample_gpu(in, n, src_rate, dst_rate, out, cap); Q3_API_END(h)
+}
+int q3tts_mel_gpu_host(q3tts_engine* h, const float* audio, int64_t n, int32_t sample_rate, float* mel, int64_t cap, int32_t* frames) {
+    Q3_API_BEGIN(h)
+    int f = 0;
+    const bool any = h->e->mel_gpu(audio, n, sample_rate, mel, cap, &f);
+    *frames = f;
+    if (!any) throw q3::Error("Failed to extract mel spectrogram");   // an empty clip, as q3tts_mel_host
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_speaker_embed_pcm_batch_host(q3tts_engine* h, int n_clips, const float* const* pcm, const int64_t* n_samples, const int32_t* sample_rates,
+                                       float* embeds) {
+    Q3_API_BEGIN(h) h->e->speaker_embed_pcm(n_clips, pcm, n_samples, sample_rates, embeds); return 0; Q3_API_END(h)
+}
+
 int q3tts_last_decode_ms(q3tts_engine* h, float* ms, int* steps) {
     Q3_API_BEGIN(h)
     if (ms) *ms = h->e->last_decode_ms;

@@ -330,7 +330,15 @@ void launch_dwconv_ln(const float* x, int T, int C, const float* dw_w, const flo
                       const float* ln_b, float* out, hipStream_t s, int rows_per_utt = 0);
 
 
-// ---- speaker encoder (q3_speaker_kernels.hip) ----
+// ---- speaker encoder + GPU audio front end of the clone path (q3_speaker_kernels.hip) ----
+// One reference clip of a batch.  Activations of a batch lie clip after clip along time ([sum T][C]); every kernel that looks across
+// time takes the clip from the grid and stays inside [row_off, row_off + T).
+struct SpkClip {
+    int32_t in_off = 0, n_in = 0;       // the caller's samples in the raw-audio buffer
+    int32_t src_rate = 0, dst_rate = 0; // equal: the clip is used as it is
+    int32_t rs_off = 0, n_rs = 0;       // resampled samples (n_rs == n_in, rs_off unused, when the rates are equal)
+    int32_t row_off = 0, T = 0;         // mel frames / activation rows
+};
 struct SpkConvArgs {
     const float* x = nullptr; int ldx = 0;   // [T][ldx] time-major (or [Cin][ldx] when x_channel_major)
     const float* x2 = nullptr; int ldx2 = 0; // optional second input added to x before the convolution
@@ -340,12 +348,26 @@ struct SpkConvArgs {
     const float* W = nullptr;                 // [k][Cin][Cout]
     const float* bias = nullptr;
     float* y = nullptr; int ldy = 0;
+    // batch of clips (blockIdx.z): x, x2, y are the batch's buffers, T the longest clip (grid), min_T the shortest (reflect padding);
+    // channel-major input is [Cin][T of the clip] per clip, clip after clip
+    const SpkClip* clips = nullptr; int n_clips = 1, min_T = 0;
 };
 void launch_spk_conv(const SpkConvArgs& a, hipStream_t s);
 void launch_spk_repack(const float* w, float* out, int cout, int cin, int k, hipStream_t s);
-void launch_spk_colstats(const float* x, int ld, int T, int C, float* mean, float* sd, hipStream_t s);
-void launch_spk_se_gate(const float* y, const float* g, float* h, float* cat, int ld_cat, int T, int C, hipStream_t s);
-void launch_spk_asp_input(const float* x, const float* mean, const float* sd, float* out, int T, int C, hipStream_t s);
-void launch_spk_asp_pool(const float* scores, const float* x, int T, int C, float* out, hipStream_t s);
+// clips == null: one clip of T rows.  Otherwise T is the longest clip and the per-clip vectors (mean, sd, gate, pooled) are [clip][C].
+void launch_spk_colstats(const float* x, int ld, int T, int C, float* mean, float* sd, hipStream_t s, const SpkClip* clips = nullptr, int n_clips = 1);
+void launch_spk_se_gate(const float* y, const float* g, float* h, float* cat, int ld_cat, int T, int C, hipStream_t s, const SpkClip* clips = nullptr, int n_clips = 1);
+void launch_spk_asp_input(const float* x, const float* mean, const float* sd, float* out, int T, int C, hipStream_t s, const SpkClip* clips = nullptr, int n_clips = 1);
+void launch_spk_asp_pool(const float* scores, const float* x, int T, int C, float* out, hipStream_t s, const SpkClip* clips = nullptr, int n_clips = 1);
+
+// linear resampler of q3::resample_linear for the clips whose rates differ: rs[rs_off + i], i < n_rs, from raw[in_off ..]
+void launch_resample_linear(const float* raw, float* rs, const SpkClip* clips, int n_clips, int max_n_rs, hipStream_t s);
+// log-mel of q3::log_mel for the clone path's MelSpec (n_fft = win = 1024, hop 256, 128 bands): mel + 128 * row_off is the clip's [128][T]
+struct MelTablesDev {
+    const float *window = nullptr, *tw_re = nullptr, *tw_im = nullptr;   // [1024], [512], [512]
+    const uint32_t* rev = nullptr;                                       // [1024]
+    const int32_t *lo = nullptr, *mid = nullptr, *hi = nullptr;          // [128] triangle corners
+};
+void launch_logmel(const float* raw, const float* rs, const SpkClip* clips, int n_clips, int max_T, const MelTablesDev& tb, float* mel, hipStream_t s);
 
 } // namespace q3

@@ -56,6 +56,7 @@ struct DecStack {
 
 struct CodecW; // q3_codec.cpp
 struct SpeakerW; // q3_speaker.cpp
+struct SpkFront; // q3_speaker.cpp
 
 class Engine {
 public:
@@ -211,6 +212,16 @@ public:
     void speaker_free();
     // mel [spk_mel][frames] (the reference MelExtractor layout) on the host -> embedding [spk_enc_dim] on the host
     void speaker_encode(const float* mel, int frames, float* out);
+    // GPU front end for audio already in memory (mono float, any rate).  Each call stages its clips in one pinned copy, runs on the
+    // engine's stream in the engine-owned workspace (grow-only, freed with the engine) and ends with one stream sync.
+    SpkFront* spkf = nullptr;
+    void front_finalize();                      // the log-mel tables of q3_audio.cpp's make_plan, uploaded once
+    // q3::resample_linear on the GPU, bit for bit; returns the output length, writes min(length, cap) samples when out != null
+    int64_t resample_gpu(const float* in, int64_t n, int src_rate, int dst_rate, float* out, int64_t cap);
+    // resample to 24 kHz (when sample_rate != 24000) + q3::log_mel: mel [128][*frames]; mel == null only sizes.  false: no frame (empty clip)
+    bool mel_gpu(const float* audio, int64_t n, int sample_rate, float* mel, int64_t cap, int* frames);
+    // n_clips clips -> out [n_clips][spk_enc_dim]; a clip's embedding does not depend on the rest of the batch
+    void speaker_embed_pcm(int n_clips, const float* const* pcm, const int64_t* n_samples, const int32_t* rates, float* out);
 
     // ---- internals ----
     DecStack talker, cp;

@@ -172,6 +172,19 @@ std::vector<float> TTSEngine::extract_speaker_embedding(const std::string& audio
     return embed;
 }
 
+std::vector<float> TTSEngine::extract_speaker_embedding(const std::vector<float>& pcm, int sample_rate) {
+    if (!has_speaker_encoder()) return {};
+    std::vector<float> embed((size_t)spk_dim_);
+    const float* clip = pcm.data();
+    const int64_t n = (int64_t)pcm.size();
+    const int32_t rate = sample_rate;
+    if (q3tts_speaker_embed_pcm_batch_host(h_, 1, &clip, &n, &rate, embed.data()) != 0) {
+        std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl;
+        return {};
+    }
+    return embed;
+}
+
 std::vector<std::vector<float>> TTSEngine::synthesize_tokens_batch(const std::vector<std::vector<int64_t>>& token_ids,
                                                                    Language lang, const SamplingParams& params) {
     std::vector<std::vector<float>> out(token_ids.size());

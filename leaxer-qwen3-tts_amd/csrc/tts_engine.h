@@ -62,6 +62,8 @@ public:
     std::vector<float> synthesize_tokens(const std::vector<int64_t>& token_ids, Language lang = Language::Auto,
                                          const SamplingParams& params = SamplingParams());
     std::vector<float> extract_speaker_embedding(const std::string& audio_path);
+    // the same for reference audio already in memory (mono samples at sample_rate): resampling, log-mel and encoder all run on the GPU
+    std::vector<float> extract_speaker_embedding(const std::vector<float>& pcm, int sample_rate);
 
     // batch extension: independent utterances share one decode loop (one result per utterance)
     std::vector<std::vector<float>> synthesize_tokens_batch(const std::vector<std::vector<int64_t>>& token_ids,

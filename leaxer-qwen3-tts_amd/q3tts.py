@@ -88,6 +88,7 @@ EXPORTS = [
     "q3tts_tokenizer_ready", "q3tts_tokenize",
     "q3tts_synthesize_clone_batch_host", "q3tts_synthesize_schedule_host", "q3tts_read_wav_host", "q3tts_resample_host", "q3tts_mel_host",
     "q3tts_has_speaker_encoder", "q3tts_speaker_encoder_host", "q3tts_extract_speaker_embedding_host",
+    "q3tts_resample_gpu_host", "q3tts_mel_gpu_host", "q3tts_speaker_embed_pcm_batch_host",
     "q3tts_codec_decode_chunked_host", "q3tts_slot_codec_decode_range_host", "q3tts_slot_logits_host", "q3tts_step_logits_host",
     "q3tts_sample_hist_host", "q3tts_sample_hist_dev",
 ]
@@ -162,6 +163,10 @@ def lib():
     L.q3tts_has_speaker_encoder.argtypes = [vp]
     L.q3tts_speaker_encoder_host.argtypes = [vp, vp, i32, vp]
     L.q3tts_extract_speaker_embedding_host.argtypes = [vp, C.c_char_p, vp]
+    L.q3tts_resample_gpu_host.restype = i64
+    L.q3tts_resample_gpu_host.argtypes = [vp, vp, i64, i32, i32, vp, i64]
+    L.q3tts_mel_gpu_host.argtypes = [vp, vp, i64, i32, vp, i64, C.POINTER(C.c_int32)]
+    L.q3tts_speaker_embed_pcm_batch_host.argtypes = [vp, i32, vp, vp, vp, vp]
     L.q3tts_codec_decode_chunked_host.argtypes = [vp, vp, i32, i32, i32, vp, i64, C.POINTER(i64)]
     L.q3tts_slot_codec_decode_range_host.argtypes = [vp, i32, i32, i32, i32, vp, i64, C.POINTER(i64)]
     L.q3tts_tokenizer_create.restype = vp
@@ -494,6 +499,41 @@ class Engine:
     def extract_speaker_embedding(self, wav_path):
         out = np.zeros(self.cfg.spk_enc_dim, np.float32)
         self._ck(self.L.q3tts_extract_speaker_embedding_host(self.h, os.fsencode(wav_path), _p(out)))
+        return out
+
+    def resample_gpu(self, audio, src_rate, dst_rate):
+        """io::resample on the GPU (q3tts_resample_gpu_host): the samples of q3tts.resample, bit for bit"""
+        a = np.ascontiguousarray(audio, np.float32)
+        n = self._ck(self.L.q3tts_resample_gpu_host(self.h, _p(a), a.size, src_rate, dst_rate, None, 0))
+        out = np.zeros(max(n, 1), np.float32)
+        self._ck(self.L.q3tts_resample_gpu_host(self.h, _p(a), a.size, src_rate, dst_rate, _p(out), n))
+        return out[:n]
+
+    def log_mel_gpu(self, audio, sample_rate=24000):
+        """resample to 24 kHz + MelExtractor::extract on the GPU (q3tts_mel_gpu_host): [128][frames]; (128, 0) for an empty clip"""
+        a = np.ascontiguousarray(audio, np.float32)
+        fr = C.c_int32(0)
+        if self.L.q3tts_mel_gpu_host(self.h, _p(a), a.size, sample_rate, None, 0, C.byref(fr)) != 0:
+            if fr.value == 0 and b"Failed to extract mel" in self.L.q3tts_last_error(self.h):
+                return np.zeros((128, 0), np.float32)
+            raise RuntimeError(self.L.q3tts_last_error(self.h).decode())
+        out = np.zeros((128, fr.value), np.float32)
+        self._ck(self.L.q3tts_mel_gpu_host(self.h, _p(a), a.size, sample_rate, _p(out), out.size, C.byref(fr)))
+        return out
+
+    def speaker_embeddings(self, clips, sample_rates):
+        """extract_speaker_embedding for clips already in memory (mono float arrays, any rate; a scalar rate applies to all):
+        [len(clips)][spk_enc_dim] from one batched call (q3tts_speaker_embed_pcm_batch_host)"""
+        n = len(clips)
+        keep = [None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1) for a in clips]
+        rates = [int(sample_rates)] * n if np.isscalar(sample_rates) else [int(r) for r in sample_rates]
+        if len(rates) != n:
+            raise ValueError("sample_rates: one rate per clip, or one for all")
+        ptrs = (C.c_void_p * max(n, 1))(*[None if a is None else a.ctypes.data for a in keep])
+        ns = np.array([0 if a is None else a.size for a in keep], np.int64)
+        rt = np.array(rates, np.int32)
+        out = np.zeros((n, self.cfg.spk_enc_dim), np.float32)
+        self._ck(self.L.q3tts_speaker_embed_pcm_batch_host(self.h, n, ptrs, _p(ns) if n else None, _p(rt) if n else None, _p(out) if out.size else None))
         return out
 
     def synthesize_batch(self, token_lists, sp, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None, max_new_per_utt=None):
