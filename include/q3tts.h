@@ -174,6 +174,21 @@ int q3tts_codec_stream_end(q3tts_engine* e, int stream_id);
 /* the same for frames of a slot that is still generating: call after q3tts_decode_steps has produced frame_end frames */
 int q3tts_slot_codec_decode_range_host(q3tts_engine* e, int slot, int frame_begin, int frame_end, int left_context, float* pcm, int64_t cap,
                                        int64_t* out_len);
+/* run_vocoder (tts_onnx.cpp:759-776) for the NEXT frames of many carried-state streams at once — the reference decodes one whole
+ * utterance per call.  Stream stream_ids[s] receives frames codes[frame_offsets[s] .. frame_offsets[s+1]) (n_groups ids each) and
+ * pcm_out[s] the samples they own (up to pcm_cap; pcm_len[s] their count).  All streams' new rows go through the pre-transformer in ONE
+ * set of launches per layer (each at its own position, over its own sliding K / V buffer), their windows through the conv decoder as one
+ * batch per left-context length: the launch count does not depend on n_streams.  Every result equals the single pushes' to fp32 rounding.
+ * A stream without frames is left untouched (pcm_len[s] = 0).  Everything is validated before any stream advances — ids distinct and
+ * open, offsets non-decreasing from 0, codes inside the codebook, no stream beyond its max_frames: on error no stream has moved. */
+int q3tts_codec_stream_push_batch_host(q3tts_engine* e, int n_streams, const int32_t* stream_ids, const int64_t* codes, const int32_t* frame_offsets,
+                                       float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len);
+/* run_vocoder (tts_onnx.cpp:759-776) over what the listed slots have generated since their previous streaming call, in batched passes:
+ * slot slots[i] gets the samples of its frames [frame_begin[i], frame_end[i]) (frame_end = the slot's frame count now; an empty range
+ * gives pcm_len[i] = 0).  Runs on the slot's implicit stream — the one q3tts_slot_codec_decode_range_host uses in exact mode, so the two
+ * may alternate on a slot — and reads the codes where the sampler left them: they never leave HBM.  Slots must be distinct. */
+int q3tts_slots_codec_decode_new_host(q3tts_engine* e, int n_slots, const int32_t* slots, float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len,
+                                      int32_t* frame_begin, int32_t* frame_end);
 /* ---- the same sessions, batch-first, on DEVICE pointers ----
  * For a host application that keeps embeddings, logits and ids in HBM: no PCIe round trip per call.  Row b of a call is slot b of the
  * engine (batch <= max_batch).  Tensors (float / id buffers) are device pointers on the engine's GPU, any allocator; control arrays
@@ -257,6 +272,20 @@ int q3tts_synthesize_clone_batch_host(q3tts_engine* e, int n_utt, const int64_t*
 int q3tts_synthesize_schedule_host(q3tts_engine* e, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                    const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                    float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out);
+/* q3tts_synthesize_schedule_host that delivers audio while it generates (the reference returns an utterance's samples from one
+ * run_vocoder call at its end, tts_onnx.cpp:759-776 / :430).  The loop: advance the live slots chunk_frames steps; decode every slot's
+ * new frames in batched passes (q3tts_slots_codec_decode_new_host's); call cb once per utterance that has new audio — pcm holds the
+ * samples of frames [frame_begin, frame_end) and is valid during the call only.  A finished slot delivers its tail with finished = 1,
+ * exactly once and as that utterance's last call (n_samples may be 0), and is re-armed from the queue.  The vocoder passes run between the
+ * decode chunks on the engine's stream, not beside them.  Codes, n_frames and (pcm_out non-NULL) the concatenated PCM are returned as by
+ * the schedule entry.  A non-zero return from cb ends the job with the error "cancelled by callback" and releases the slots.
+ * On a pooled engine (q3tts_create_pooled) an utterance is admitted only when prompt + cap fit the pool: there is no on-demand growth
+ * and no preemption here, because audio that has been delivered cannot be taken back. */
+typedef int (*q3tts_audio_cb)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished);
+int q3tts_synthesize_stream_host(q3tts_engine* e, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                 const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                 float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                                 int chunk_frames, q3tts_audio_cb cb, void* user);
 /* io::read_wav (src/io/wav_reader.h:13, wav_reader.cpp:28-143): mono float samples; -1 when the reference
  * returns an empty vector.  Call with out == NULL to learn *n_samples. */
 int q3tts_read_wav_host(const char* path, float* out, int64_t cap, int64_t* n_samples, int32_t* sample_rate);

@@ -294,6 +294,20 @@ int q3tts_codec_stream_end(q3tts_engine* h, int stream_id) {
     return 0;
     Q3_API_END(h)
 }
+int q3tts_codec_stream_push_batch_host(q3tts_engine* h, int n_streams, const int32_t* stream_ids, const int64_t* codes, const int32_t* frame_offsets,
+                                       float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len) {
+    Q3_API_BEGIN(h)
+    h->e->codec_stream_push_batch_host(n_streams, stream_ids, codes, frame_offsets, pcm_out, pcm_cap, pcm_len);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_slots_codec_decode_new_host(q3tts_engine* h, int n_slots, const int32_t* slots, float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len,
+                                      int32_t* frame_begin, int32_t* frame_end) {
+    Q3_API_BEGIN(h)
+    h->e->slots_codec_decode_new(n_slots, slots, pcm_out, pcm_cap, pcm_len, frame_begin, frame_end);
+    return 0;
+    Q3_API_END(h)
+}
 int q3tts_slot_codec_decode_range_host(q3tts_engine* h, int slot, int frame_begin, int frame_end, int left_context, float* pcm, int64_t cap,
                                        int64_t* out_len) {
     Q3_API_BEGIN(h)
@@ -565,6 +579,119 @@ int q3tts_synthesize_schedule_host(q3tts_engine* h, int n_utt, const int64_t* id
 }
 
 // ---- voice-clone front end (host audio code + the speaker encoder on the GPU) ----
+// q3tts_synthesize_schedule_host with the audio delivered chunk by chunk: decode chunk_frames steps, vocode every live slot's new frames
+// in batched passes (Engine::slots_codec_decode_new), call back, retire / re-arm.  Admission reserves prompt + cap for every utterance
+// (no growth, no preemption: delivered audio cannot be taken back), so the loop needs none of the schedule entry's page policy.
+int q3tts_synthesize_stream_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                 const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                 float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                                 int chunk_frames, q3tts_audio_cb cb, void* user) {
+    Q3_API_BEGIN(h)
+    Engine& e = *h->e;
+    const int H = e.c.hidden, G = e.c.n_groups, B = e.B;
+    if (n_utt <= 0) return 0;
+    if (!ids || !offsets || !p) throw q3::Error("synthesize: null argument");
+    if (!cb) throw q3::Error("synthesize_stream: null callback");
+    if (chunk_frames < 1) throw q3::Error("synthesize_stream: chunk_frames must be positive");
+    if (pcm_cap < 0) throw q3::Error("synthesize: negative pcm_cap");
+    (void)Engine::checked_penalty(*p);
+    for (int b = 0; b < B; ++b) e.slot_release(b);
+    struct Prep { int S = 0, nt = 0; size_t poff = 0, toff = 0; };
+    std::vector<Prep> prep((size_t)n_utt);
+    std::vector<float> prompts, trailing;
+    {
+        size_t prow = 0, trow = 0;
+        for (int u = 0; u < n_utt; ++u) {
+            prep[(size_t)u].poff = prow; prep[(size_t)u].toff = trow;
+            prow += 16; trow += (size_t)std::max(1, offsets[u + 1] - offsets[u] - 3);
+        }
+        prompts.resize(prow * H); trailing.resize(trow * H);
+        std::vector<size_t> toffs((size_t)n_utt);
+        std::vector<int> Ss((size_t)n_utt), nts((size_t)n_utt);
+        for (int u = 0; u < n_utt; ++u) toffs[(size_t)u] = prep[(size_t)u].toff;
+        e.build_prompts(ids, offsets, n_utt, lang, speakers, prompts.data(), Ss.data(), trailing.data(), toffs.data(), nts.data());
+        for (int u = 0; u < n_utt; ++u) { prep[(size_t)u].S = Ss[(size_t)u]; prep[(size_t)u].nt = nts[(size_t)u]; }
+    }
+    auto cap_of = [&](int u) { return max_new_per_utt ? std::min(std::max(1, (int)max_new_per_utt[u]), p->max_new_tokens) : p->max_new_tokens; };
+    std::deque<int> pending;
+    for (int u = 0; u < n_utt; ++u) {
+        if (e.kv_pages_for(prep[(size_t)u].S + cap_of(u)) > e.kv_total_pages())
+            throw q3::Error("synthesize: one utterance (prompt + max_new_tokens) needs more KV pages than the pool holds");
+        pending.push_back(u);
+        if (pcm_len) pcm_len[u] = 0;
+        if (n_frames) n_frames[u] = 0;
+    }
+    const int cf = std::min(chunk_frames, e.max_frames_cap);   // samples of cf frames at the start of an utterance / further in
+    const int64_t chunk_cap = std::max(q3tts_codec_decode_len(&e.c, cf), q3tts_codec_decode_len(&e.c, cf + 1) - q3tts_codec_decode_len(&e.c, 1));
+    std::vector<float> chunk_pcm((size_t)B * chunk_cap);
+    std::vector<float*> pcm_ptr((size_t)B);
+    std::vector<int32_t> slots, fb((size_t)B), fe((size_t)B);
+    std::vector<int64_t> plen((size_t)B), written((size_t)n_utt, 0);
+    std::vector<Engine::SlotInit> init;
+    std::vector<int> slot_utt((size_t)B, -1), fresh;
+    std::vector<q3::SlotState> st;
+    int live = 0;
+    e.sched_admitted = e.sched_preempted = 0; e.sched_peak_live = 0;
+    try {
+        while (!pending.empty() || live > 0) {
+            fresh.clear();
+            {   // admission in queue order, every utterance with the pages of its whole length
+                std::vector<int> free_slots, need;
+                for (int b = 0; b < B; ++b) if (slot_utt[(size_t)b] < 0) free_slots.push_back(b);
+                for (size_t i = 0; i < pending.size() && i < free_slots.size(); ++i) need.push_back(e.kv_pages_for(prep[(size_t)pending[i]].S + cap_of(pending[i])));
+                const int n_adm = q3::sched_admit_count(e.kv, need, (int)free_slots.size(), live, true);
+                for (int i = 0; i < n_adm; ++i) { slot_utt[(size_t)free_slots[(size_t)i]] = pending.front(); pending.pop_front(); fresh.push_back(free_slots[(size_t)i]); }
+            }
+            if (!fresh.empty()) {
+                init.assign(fresh.size(), Engine::SlotInit());
+                for (size_t i = 0; i < fresh.size(); ++i) {
+                    const int b = fresh[i], u = slot_utt[(size_t)b];
+                    const Prep& pr = prep[(size_t)u];
+                    Engine::SlotInit& q = init[i];
+                    q.slot = b; q.prompt = prompts.data() + pr.poff * H; q.S = pr.S; q.trailing = trailing.data() + pr.toff * H; q.n_trailing = pr.nt;
+                    q.stream_id = (uint32_t)u;
+                    q.max_frames = max_new_per_utt ? std::max(1, (int)max_new_per_utt[u]) : 0;
+                    q.kv_tokens = 0;   // prompt + cap, reserved now
+                }
+                e.slots_begin(init.data(), (int)init.size(), *p, seed, ignore_eos);
+                live += (int)fresh.size();
+                e.sched_admitted += (int64_t)fresh.size();
+                e.sched_peak_live = std::max(e.sched_peak_live, live);
+            }
+            if (live == 0) throw q3::Error("synthesize_stream: no utterance could be admitted");
+            e.decode_steps(chunk_frames);
+            slots.clear();
+            for (int b = 0; b < B; ++b) if (slot_utt[(size_t)b] >= 0) { pcm_ptr[slots.size()] = chunk_pcm.data() + slots.size() * (size_t)chunk_cap; slots.push_back(b); }
+            e.slots_codec_decode_new((int)slots.size(), slots.data(), pcm_ptr.data(), chunk_cap, plen.data(), fb.data(), fe.data());
+            e.slots_state(B, st);
+            for (size_t i = 0; i < slots.size(); ++i) {
+                const int b = slots[i], u = slot_utt[(size_t)b];
+                const q3::SlotState& s = st[(size_t)b];
+                const bool fin = s.finished || s.n_frames >= s.max_frames;
+                if (plen[i] > chunk_cap) throw q3::Error("synthesize_stream: a chunk produced more samples than its buffer holds");
+                if (pcm_out && pcm_out[u] && plen[i] > 0 && written[(size_t)u] < pcm_cap)
+                    memcpy(pcm_out[u] + written[(size_t)u], pcm_ptr[i], (size_t)std::min(plen[i], pcm_cap - written[(size_t)u]) * sizeof(float));
+                written[(size_t)u] += plen[i];
+                if (fin) {   // retired before the callback: whatever it does, the slot is free and the outputs are complete
+                    if (n_frames) n_frames[u] = s.n_frames;
+                    if (pcm_len) pcm_len[u] = written[(size_t)u];
+                    if (codes_out) e.slot_codes(b, codes_out + (size_t)u * p->max_new_tokens * G, p->max_new_tokens);
+                    e.slot_release(b);
+                    slot_utt[(size_t)b] = -1;
+                    --live;
+                }
+                if (plen[i] > 0 || fin)
+                    if (cb(user, u, fb[i], fe[i], pcm_ptr[i], plen[i], fin ? 1 : 0) != 0) throw q3::Error("cancelled by callback");
+            }
+        }
+    } catch (...) {
+        for (int b = 0; b < B; ++b) { try { e.slot_release(b); } catch (...) { } }
+        throw;
+    }
+    return 0;
+    Q3_API_END(h)
+}
+
 int q3tts_read_wav_host(const char* path, float* out, int64_t cap, int64_t* n_samples, int32_t* sample_rate) {
     if (!path || !n_samples || !sample_rate) return -1;
     try {

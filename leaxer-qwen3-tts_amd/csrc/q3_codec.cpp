@@ -70,6 +70,12 @@ struct CodecW {
     std::vector<Stream> streams;
     char* stream_arena = nullptr; size_t stream_arena_bytes = 0;
     std::vector<int> slot_stream;          // slot -> stream id (-1: none): q3tts_slot_codec_decode_range_host's implicit stream
+    // batched push (Engine::codec_stream_push_batch): work buffers of all streams' new rows and of one group's window behind the
+    // transformer, the descriptor table of a push (host copy + device), the host codes' staging area; all grow-only
+    char* sbatch_arena = nullptr; size_t sbatch_arena_bytes = 0;
+    CodecStreamDesc* sbatch_desc = nullptr; size_t sbatch_desc_n = 0;
+    std::vector<CodecStreamDesc> sbatch_desc_h;
+    int32_t* sbatch_codes = nullptr; size_t sbatch_codes_n = 0;
 };
 
 void Engine::codec_free() {
@@ -96,6 +102,9 @@ void Engine::codec_free() {
     if (codec->page_table) (void)hipFree(codec->page_table);
     for (auto& s : codec->streams) { if (s.kv) (void)hipFree(s.kv); if (s.hpost) (void)hipFree(s.hpost); }
     if (codec->stream_arena) (void)hipFree(codec->stream_arena);
+    if (codec->sbatch_arena) (void)hipFree(codec->sbatch_arena);
+    if (codec->sbatch_desc) (void)hipFree(codec->sbatch_desc);
+    if (codec->sbatch_codes) (void)hipFree(codec->sbatch_codes);
     delete codec;
     codec = nullptr;
 }
@@ -428,6 +437,33 @@ int64_t Engine::codec_run(const int32_t* codes_dev, int F, float** pcm_dev, int 
 }
 
 
+// ConvNeXt upsampling stages over row blocks [sequence][*per] (T rows in all): the transposed convs have kernel == stride (every input row
+// expands on its own), the depthwise causal conv stops at each sequence's first row, the pointwise layers are plain GEMMs.  take(n)
+// hands out n floats of the caller's arena, conv(a) launches with the caller's slab and weight planes.  Shared by codec_pre_batch (whole
+// utterances) and the batched push (the streams' windows).  *per leaves as the rows per sequence of the result.
+template <class Take, class Conv>
+static float* upsample_blocks(const q3tts_config& c, const CodecW& W, float* cur, int T, int* per, Take&& take, Conv&& conv, hipStream_t stream) {
+    const int CH = c.cd_hidden;
+    int Tc = T;
+    for (int s2 = 0; s2 < c.cd_n_up; ++s2) {
+        const CodecW::Up& U = W.up[s2];
+        const int f = c.cd_up_ratios[s2];
+        if (U.tconv.k != f) throw Error("codec: batched upsampling needs kernel == stride");
+        const int To = Tc * f;
+        float* y = take((size_t)To * CH);
+        float* ln = take((size_t)To * CH);
+        float* a4 = take((size_t)To * 4 * CH);
+        { ConvArgs a; a.in = cur; a.T_in = Tc; a.C_in = CH; a.out = y; a.T_out = To; a.C_out = CH; a.W = U.tconv.w; a.bias = U.tconv.b;
+          a.taps = f; a.transposed = 1; a.stride = f; a.left = 0; conv(a); }
+        *per *= f;
+        launch_dwconv_ln(y, To, CH, U.dw_w, U.dw_b, U.ln_w, U.ln_b, ln, stream, *per);
+        { ConvArgs a; a.in = ln; a.T_in = To; a.C_in = CH; a.out = a4; a.T_out = To; a.C_out = 4 * CH; a.W = U.pw1_w; a.bias = U.pw1_b; a.act = 1; conv(a); }
+        { ConvArgs a; a.in = a4; a.T_in = To; a.C_in = 4 * CH; a.out = y; a.T_out = To; a.C_out = CH; a.W = U.pw2_w; a.bias = U.pw2_b; a.res_scale = U.gamma; a.res = y; conv(a); }
+        cur = y; Tc = To;
+    }
+    return cur;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Pre-transformer of a whole job in one pass: the utterances' frames are laid out as [utterance][Fp] rows (Fp = the longest, shorter
 // ones padded: attention is causal, so padding rows never reach a real one), every linear layer is ONE matrix-core GEMM over all rows
@@ -516,26 +552,8 @@ const float* Engine::codec_pre_batch(const int32_t* codes_dev, int codes_stride_
     launch_rmsnorm_rows(h, W.norm, c.cd_rms_eps, T, CH, h, stream);
     if (rows_per_utt_out) *rows_per_utt_out = Fp;
     if (!with_upsampling) return h;
-    // ---- ConvNeXt upsampling stages over all utterances: the transposed convs have kernel == stride (every input row expands on its
-    // own), the depthwise causal conv stops at each utterance's first row, the pointwise layers are plain GEMMs ----
-    float* cur = h;
-    int Tc = T, per = Fp;
-    for (int s2 = 0; s2 < c.cd_n_up; ++s2) {
-        const CodecW::Up& U = W.up[s2];
-        const int f = c.cd_up_ratios[s2];
-        if (U.tconv.k != f) throw Error("codec_pre_batch: upsampling kernel != stride");
-        const int To = Tc * f;
-        float* y = take((size_t)To * CH);
-        float* ln = take((size_t)To * CH);
-        float* a4 = take((size_t)To * 4 * CH);
-        { ConvArgs a; a.in = cur; a.T_in = Tc; a.C_in = CH; a.out = y; a.T_out = To; a.C_out = CH; a.W = U.tconv.w; a.bias = U.tconv.b;
-          a.taps = f; a.transposed = 1; a.stride = f; a.left = 0; conv(a); }
-        per *= f;
-        launch_dwconv_ln(y, To, CH, U.dw_w, U.dw_b, U.ln_w, U.ln_b, ln, stream, per);
-        { ConvArgs a; a.in = ln; a.T_in = To; a.C_in = CH; a.out = a4; a.T_out = To; a.C_out = 4 * CH; a.W = U.pw1_w; a.bias = U.pw1_b; a.act = 1; conv(a); }
-        { ConvArgs a; a.in = a4; a.T_in = To; a.C_in = 4 * CH; a.out = y; a.T_out = To; a.C_out = CH; a.W = U.pw2_w; a.bias = U.pw2_b; a.res_scale = U.gamma; a.res = y; conv(a); }
-        cur = y; Tc = To;
-    }
+    int per = Fp;
+    float* cur = upsample_blocks(c, W, h, T, &per, take, conv, stream);
     if (rows_per_utt_out) *rows_per_utt_out = per;
     return cur;
 }
@@ -862,6 +880,270 @@ int64_t Engine::codec_stream_push_host(int sid, const int64_t* codes, int n, flo
     return n_own;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Batched push: n new frames for each of g streams in ONE set of launches per layer (a server with 64 live callers otherwise makes 64
+// latency-bound pushes back to back every chunk: ~10 small launches per layer each, on grids of a handful of workgroups).  Rows are packed
+// [stream][its new frames] (ragged n), every linear layer is one GEMM over all rows — weights streamed once — and the kernels that look
+// at a position or at a stream's own buffers (code gather, RoPE + cache store, windowed attention, the final norm's scatter into hpost)
+// find them in a descriptor table uploaded once per push (CodecStreamDesc).  Stream state stays where codec_stream_fit keeps it: the
+// table carries pointers, so streams of different P mix freely and keep / move / grow work per stream as before.
+// Behind the transformer the streams' windows [kept rows | new rows] are gathered into [g][Tw][hidden] blocks, upsampled together
+// (upsample_blocks) and decoded with codec_run(nbatch = g).  A stream younger than codec_stage_b_context() frames has a shorter left
+// context — its window starts at the utterance's first row, where the causal convs see nothing, not a neighbour's rows — so streams are
+// grouped by left-context length; inside a group shorter pushes are right-padded with zero rows (exact: every layer is causal).
+// Everything runs on the engine's stream, serially with the decode chain (vocoding beside decoding costs every decode step 12 %:
+// profiles/r01_negative_results.txt).  PCM goes to the callers' host buffers; the call returns once it is there.
+// ------------------------------------------------------------------------------------------------
+void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
+    if (!codec) throw Error("codec decoder not finalized");
+    CodecW& W = *codec;
+    const int CH = c.cd_hidden, NH = c.cd_heads, HD = c.cd_head_dim, FF = c.cd_ffn;
+    if (NH * HD != CH) throw Error("codec: heads*head_dim must equal hidden");
+    // ---- every argument is checked before any stream's buffers are touched ----
+    std::vector<int> live;
+    for (int i = 0; i < g_all; ++i) {
+        StreamPush& q = ps[i];
+        q.n_own = 0;
+        if (q.sid < 0 || q.sid >= (int)W.streams.size() || !W.streams[(size_t)q.sid].used) throw Error("codec_stream_push_batch: no such stream");
+        for (int k = 0; k < i; ++k) if (ps[k].sid == q.sid) throw Error("codec_stream_push_batch: stream listed twice");
+        if (q.n < 0) throw Error("codec_stream_push_batch: negative frame count");
+        if (W.streams[(size_t)q.sid].n_done + q.n > W.streams[(size_t)q.sid].cap) throw Error("codec_stream_push_batch: more frames than the stream was opened for");
+        if (q.n > 0 && !q.codes_dev) throw Error("codec_stream_push_batch: null codes");
+        if (q.n > 0) live.push_back(i);
+    }
+    const int g = (int)live.size();
+    if (g == 0) return;
+    if (g > 65535) throw Error("codec_stream_push_batch: at most 65535 streams per call");
+    const int ctxB = codec_stage_b_context();
+    // group key: left-context length min(a0, ctxB); mature streams (the common case) first
+    std::stable_sort(live.begin(), live.end(), [&](int x, int y) {
+        return std::min(W.streams[(size_t)ps[x].sid].n_done, ctxB) > std::min(W.streams[(size_t)ps[y].sid].n_done, ctxB); });
+    std::vector<CodecStreamDesc>& D = W.sbatch_desc_h;
+    D.assign((size_t)g, CodecStreamDesc());
+    int T = 0, n_max = 0;
+    for (int i = 0; i < g; ++i) {
+        const StreamPush& q = ps[live[(size_t)i]];
+        codec_stream_fit(q.sid, q.n);
+        const CodecW::Stream& S = W.streams[(size_t)q.sid];
+        CodecStreamDesc& d = D[(size_t)i];
+        d.kv = S.kv; d.hpost = S.hpost; d.codes = q.codes_dev; d.P = S.P; d.k0 = S.kv_rows; d.h0 = S.h_rows; d.a0 = S.n_done; d.n = q.n; d.row_off = T;
+        d.ctx = std::min(S.n_done, ctxB);
+        if (d.k0 + d.n > S.P || d.h0 + d.n > S.h_cap) throw Error("codec_stream_push_batch: the stream's buffers do not hold the push");
+        if (d.h0 < d.ctx) throw Error("codec_stream_push_batch: the kept transformer rows do not cover the look-back window");
+        if (W.rope_P < d.a0 + d.n) throw Error("codec_stream_push_batch: RoPE tables not prepared");
+        T += q.n; n_max = std::max(n_max, q.n);
+    }
+    // groups [i0, i1) of equal left context, cut so that a group's conv decoder stays inside ~16 GB of workspace (4.7 MB per frame at 0.6B dims)
+    struct Group { int i0, i1, Tw; };
+    std::vector<Group> groups;
+    int64_t up_front = 1, up = 1;
+    for (int i = 0; i < c.cd_n_up; ++i) up_front *= c.cd_up_ratios[i];
+    up = up_front;
+    for (int i = 0; i < c.cd_n_blocks; ++i) up *= c.cd_up_rates[i];
+    size_t back_rows = 0;   // rows of the largest group's gathered block
+    for (int i0 = 0; i0 < g;) {
+        int i1 = i0, Tw = 0;
+        while (i1 < g && D[(size_t)i1].ctx == D[(size_t)i0].ctx) {
+            const int Tw1 = std::max(Tw, D[(size_t)i1].ctx + D[(size_t)i1].n);
+            if (i1 > i0 && (int64_t)(i1 - i0 + 1) * Tw1 * 4700000 > ((int64_t)16 << 30)) break;
+            Tw = Tw1; ++i1;
+        }
+        for (int i = i0; i < i1; ++i) D[(size_t)i].blk = i - i0;
+        groups.push_back(Group{ i0, i1, Tw });
+        back_rows = std::max(back_rows, (size_t)(i1 - i0) * Tw);
+        i0 = i1;
+    }
+    // ---- workspace ----
+    auto bytes_of = [](size_t nfloat) { return (nfloat * sizeof(float) + 255) & ~(size_t)255; };
+    const size_t kslab_floats = (size_t)32 * 128 * 4096;
+    size_t need = bytes_of((size_t)T * CH) * 3 + bytes_of((size_t)T * 3 * CH) + bytes_of((size_t)T * FF) * 2 + bytes_of(kslab_floats) + bytes_of(back_rows * CH);
+    { size_t r = back_rows; for (int s2 = 0; s2 < c.cd_n_up; ++s2) { r *= (size_t)c.cd_up_ratios[s2]; need += bytes_of(r * CH) * 2 + bytes_of(r * 4 * CH); } }
+    if (W.sbatch_arena_bytes < need) {
+        sync();
+        if (W.sbatch_arena) (void)hipFree(W.sbatch_arena);
+        W.sbatch_arena = nullptr; W.sbatch_arena_bytes = 0;
+        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_arena, need));
+        W.sbatch_arena_bytes = need;
+    }
+    if (W.sbatch_desc_n < (size_t)g) {
+        sync();
+        if (W.sbatch_desc) (void)hipFree(W.sbatch_desc);
+        W.sbatch_desc = nullptr; W.sbatch_desc_n = 0;
+        const size_t cap = std::max((size_t)64, (size_t)g);
+        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_desc, cap * sizeof(CodecStreamDesc)));
+        W.sbatch_desc_n = cap;
+    }
+    Q3_HIP_CHECK(hipMemcpyAsync(W.sbatch_desc, D.data(), (size_t)g * sizeof(CodecStreamDesc), hipMemcpyHostToDevice, stream));
+    size_t off = 0;
+    auto take = [&](size_t nfloat) { float* p = (float*)(W.sbatch_arena + off); off += bytes_of(nfloat); return p; };
+    float* h = take((size_t)T * CH);
+    float* hn = take((size_t)T * CH);
+    float* att = take((size_t)T * CH);
+    float* qkvb = take((size_t)T * 3 * CH);
+    float* ub = take((size_t)T * FF);
+    float* gb = take((size_t)T * FF);
+    float* kslab = take(kslab_floats);
+    float* win = take(back_rows * CH);
+    const size_t off_back = off;
+    auto conv = [&](ConvArgs a) {
+        a.slab = kslab; a.slab_floats = kslab_floats;
+        const auto it = W.planes.find(a.W);
+        if (it != W.planes.end()) { a.Wh = it->second.hi; a.Wl = it->second.lo; a.Whc = it->second.cm; a.w_scale_inv = it->second.scale_inv; a.w_lo_zero = it->second.lo_zero; }
+        launch_conv(a, stream);
+    };
+    auto gemm = [&](const float* in, int Cin, const float* Wm, int Cout, float* out) {
+        ConvArgs a; a.in = in; a.T_in = T; a.C_in = Cin; a.out = out; a.T_out = T; a.C_out = Cout; a.W = Wm;
+        return a;
+    };
+    Q3_HIP_CHECK(hipEventRecord(ev0, stream));
+    // ---- the pre-transformer on all streams' new rows ----
+    const CodecStreamDesc* dd = W.sbatch_desc;
+    const bool win_attn = attn_streams_windowed(NH, HD, c.cd_window, 3 * CH, CH);
+    launch_code_embed_mean_streams(W.code_embed, dd, g, n_max, c.n_groups, c.cd_codebook, CH, h, stream);
+    for (int l = 0; l < c.cd_layers; ++l) {
+        const CodecW::Layer& L = W.layers[l];
+        launch_rmsnorm_rows(h, L.in_norm, c.cd_rms_eps, T, CH, hn, stream);
+        conv(gemm(hn, CH, L.qkv, 3 * CH, qkvb));
+        launch_rope_store_streams(qkvb, 3 * CH, dd, g, n_max, l, NH, NH, HD, W.rope_cos, W.rope_sin, stream);
+        if (win_attn) launch_attn_streams(qkvb, 3 * CH, att, CH, dd, g, n_max, l, NH, HD, c.cd_window, 1.0f / sqrtf((float)HD), stream);
+        else for (int i = 0; i < g; ++i) {   // head sizes k_attn_win does not take (tiny configs): k_attn, exactly the single push's launch
+            const CodecStreamDesc& d = D[(size_t)i];
+            AttnArgs a;
+            a.qkv = qkvb + (size_t)d.row_off * 3 * CH; a.ld_qkv = 3 * CH; a.out = att + (size_t)d.row_off * CH; a.ld_out = CH;
+            a.kcache = d.kv + (size_t)l * 2 * NH * d.P * HD; a.vcache = a.kcache + (size_t)NH * d.P * HD;
+            a.page_table = W.page_table; a.pages_per_slot = 1; a.page_shift = W.streams[(size_t)ps[live[(size_t)i]].sid].pshift; a.layer = 0; a.n_layers = 1;
+            a.pos_scalar = d.k0; a.slot_offset = 0; a.nb = 1; a.n_new = d.n; a.nq = NH; a.nkv = NH; a.d = HD;
+            a.scale = 1.0f / sqrtf((float)HD); a.window = c.cd_window; a.new_from_raw = 0;
+            launch_attn(a, stream);
+        }
+        { ConvArgs a = gemm(att, CH, L.o, CH, h); a.res_scale = L.attn_scale; a.res = h; conv(a); }
+        launch_rmsnorm_rows(h, L.post_norm, c.cd_rms_eps, T, CH, hn, stream);
+        conv(gemm(hn, CH, L.up, FF, ub));
+        { ConvArgs a = gemm(hn, CH, L.gate, FF, gb); a.act = 2; a.mul = ub; conv(a); }
+        { ConvArgs a = gemm(gb, FF, L.down, CH, h); a.res_scale = L.mlp_scale; a.res = h; conv(a); }
+    }
+    launch_rmsnorm_rows_streams(h, W.norm, c.cd_rms_eps, dd, g, n_max, CH, stream);
+    // ---- everything behind the transformer, one group of equal left context at a time ----
+    auto len_of = [&](int nfr) -> int64_t { return nfr <= 0 ? 0 : q3tts_codec_decode_len(&c, nfr); };
+    const bool batchable = codec_batchable();
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const Group& G = groups[gi];
+        const int gk = G.i1 - G.i0;
+        launch_gather_stream_rows(dd + G.i0, gk, G.Tw, CH, win, stream);
+        off = off_back;
+        int per = G.Tw;
+        const float* hup = upsample_blocks(c, W, win, gk * G.Tw, &per, take, conv, stream);
+        const size_t ustride = (size_t)per * CH;
+        const bool last_group = gi + 1 == groups.size();
+        auto deliver = [&](int i, const float* pcm_seq, int64_t Tp) {   // stream i's own samples out of its window's
+            const CodecStreamDesc& d = D[(size_t)i];
+            StreamPush& q = ps[live[(size_t)i]];
+            const int64_t first = len_of(d.a0) - up * (d.a0 - d.ctx), n_own = len_of(d.a0 + d.n) - len_of(d.a0);
+            if (first < 0 || first + n_own > Tp || (d.ctx + d.n == G.Tw && first + n_own != Tp)) throw Error("codec_stream_push_batch: window arithmetic does not match the decoder length formula");
+            q.n_own = n_own;
+            const int64_t m = std::min(n_own, q.cap);
+            if (m > 0 && q.pcm) Q3_HIP_CHECK(hipMemcpyAsync(q.pcm, pcm_seq + first, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, stream));
+        };
+        if (batchable && gk > 1) {   // the conv decoder of the whole group in one set of launches
+            float* pcm_d = nullptr;
+            const int64_t Tp = codec_run(nullptr, G.Tw, &pcm_d, 0, hup, 2, gk, ustride);
+            if (last_group) Q3_HIP_CHECK(hipEventRecord(ev1, stream));
+            for (int i = G.i0; i < G.i1; ++i) deliver(i, pcm_d + (size_t)(i - G.i0) * Tp, Tp);
+        } else {                     // one stream in the group, or a decoder the batched conv kernels do not cover: sequence by sequence
+            for (int i = G.i0; i < G.i1; ++i) {
+                float* pcm_d = nullptr;
+                const int64_t Tp = codec_run(nullptr, G.Tw, &pcm_d, 0, hup + (size_t)(i - G.i0) * ustride, 2);
+                if (last_group && i + 1 == G.i1) Q3_HIP_CHECK(hipEventRecord(ev1, stream));
+                deliver(i, pcm_d, Tp);
+            }
+        }
+    }
+    sync();
+    Q3_HIP_CHECK(hipEventElapsedTime(&last_codec_ms, ev0, ev1));
+    total_codec_ms += last_codec_ms; total_codec_frames += T;
+    for (int i = 0; i < g; ++i) {   // the streams advance only now: a failure above leaves every one of them where it was
+        const CodecStreamDesc& d = D[(size_t)i];
+        CodecW::Stream& S = W.streams[(size_t)ps[live[(size_t)i]].sid];
+        S.n_done = d.a0 + d.n; S.kv_rows = d.k0 + d.n; S.h_rows = d.h0 + d.n;
+    }
+}
+
+// host codes: stream s receives frames codes[frame_offsets[s] .. frame_offsets[s + 1]); validated as a whole before anything moves
+void Engine::codec_stream_push_batch_host(int n_streams, const int32_t* sids, const int64_t* codes, const int32_t* frame_offsets, float* const* pcm_out,
+                                          int64_t cap, int64_t* pcm_len) {
+    if (!codec) throw Error("codec decoder not finalized");
+    if (n_streams < 0) throw Error("codec_stream_push_batch: negative stream count");
+    if (n_streams == 0) return;
+    if (!sids || !frame_offsets) throw Error("codec_stream_push_batch: null argument");
+    if (cap < 0) throw Error("codec_stream_push_batch: negative pcm_cap");
+    CodecW& W = *codec;
+    const int G = c.n_groups;
+    if (frame_offsets[0] != 0) throw Error("codec_stream_push_batch: frame_offsets must start at 0");
+    for (int i = 0; i < n_streams; ++i)
+        if (frame_offsets[i + 1] < frame_offsets[i]) throw Error("codec_stream_push_batch: frame_offsets must not decrease");
+    const size_t total = (size_t)frame_offsets[n_streams] * G;
+    if (total > 0 && !codes) throw Error("codec_stream_push_batch: null codes");
+    std::vector<int32_t> tmp(total);
+    for (size_t i = 0; i < total; ++i) {
+        if (codes[i] < 0 || codes[i] >= c.cd_codebook) throw Error("codec_decode: code out of range");
+        tmp[i] = (int32_t)codes[i];
+    }
+    std::vector<StreamPush> ps((size_t)n_streams);
+    for (int i = 0; i < n_streams; ++i) {   // the checks codec_stream_push_batch repeats, made here before the staging buffer may grow
+        ps[(size_t)i].sid = sids[i]; ps[(size_t)i].n = frame_offsets[i + 1] - frame_offsets[i];
+        ps[(size_t)i].pcm = pcm_out ? pcm_out[i] : nullptr; ps[(size_t)i].cap = cap;
+        if (pcm_len) pcm_len[i] = 0;
+    }
+    if (W.sbatch_codes_n < total) {
+        sync();
+        if (W.sbatch_codes) (void)hipFree(W.sbatch_codes);
+        W.sbatch_codes = nullptr; W.sbatch_codes_n = 0;
+        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_codes, total * sizeof(int32_t)));
+        W.sbatch_codes_n = total;
+    }
+    if (total > 0) Q3_HIP_CHECK(hipMemcpyAsync(W.sbatch_codes, tmp.data(), total * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    for (int i = 0; i < n_streams; ++i) ps[(size_t)i].codes_dev = W.sbatch_codes + (size_t)frame_offsets[i] * G;
+    try { codec_stream_push_batch(ps.data(), n_streams); } catch (...) { try { sync(); } catch (...) { } throw; }   // tmp must outlive the upload
+    if (pcm_len) for (int i = 0; i < n_streams; ++i) pcm_len[i] = ps[(size_t)i].n_own;
+}
+
+// For every listed slot: the frames generated since the slot's previous streaming call, through the slot's implicit stream (the one
+// slot_codec_stream_range uses: the two interleave), all slots in batched passes.  The codes are read where the sampler wrote them.
+void Engine::slots_codec_decode_new(int n_slots, const int32_t* slots, float* const* pcm_out, int64_t cap, int64_t* pcm_len, int32_t* frame_begin, int32_t* frame_end) {
+    if (!codec) throw Error("codec decoder not finalized");
+    if (n_slots < 0) throw Error("slots_codec_decode_new: negative slot count");
+    if (n_slots == 0) return;
+    if (!slots) throw Error("slots_codec_decode_new: null argument");
+    if (cap < 0) throw Error("slots_codec_decode_new: negative pcm_cap");
+    CodecW& W = *codec;
+    for (int i = 0; i < n_slots; ++i) {
+        if (slots[i] < 0 || slots[i] >= B) throw Error("slot out of range");
+        for (int k = 0; k < i; ++k) if (slots[k] == slots[i]) throw Error("slots_codec_decode_new: slot listed twice");
+    }
+    std::vector<SlotState> st;
+    slots_state(B, st);
+    if ((int)W.slot_stream.size() < B) W.slot_stream.assign((size_t)B, -1);
+    std::vector<StreamPush> ps((size_t)n_slots);
+    for (int i = 0; i < n_slots; ++i) {
+        const int slot = slots[i], nf = st[(size_t)slot].active ? std::min(st[(size_t)slot].n_frames, max_frames_cap) : 0;
+        int sid = W.slot_stream[(size_t)slot];
+        if (sid < 0 || !W.streams[(size_t)sid].used || W.streams[(size_t)sid].n_done > nf) {   // first call of the utterance, or a restart
+            if (sid >= 0 && W.streams[(size_t)sid].used) codec_stream_end(sid);
+            sid = codec_stream_begin(max_frames_cap);
+            W.slot_stream[(size_t)slot] = sid;
+        }
+        const int a = W.streams[(size_t)sid].n_done;
+        StreamPush& q = ps[(size_t)i];
+        q.sid = sid; q.n = nf - a; q.codes_dev = codes_d + ((size_t)slot * max_frames_cap + a) * c.n_groups;
+        q.pcm = pcm_out ? pcm_out[i] : nullptr; q.cap = cap;
+        if (frame_begin) frame_begin[i] = a;
+        if (frame_end) frame_end[i] = nf;
+        if (pcm_len) pcm_len[i] = 0;
+    }
+    codec_stream_push_batch(ps.data(), n_slots);
+    if (pcm_len) for (int i = 0; i < n_slots; ++i) pcm_len[i] = ps[(size_t)i].n_own;
+}
+
 // the implicit stream behind q3tts_slot_codec_decode_range_host: consecutive exact ranges of a slot ([0, b1), [b1, b2), ...) are pushes
 int64_t Engine::slot_codec_stream_range(int slot, int a, int b, float* pcm, int64_t cap) {
     CodecW& W = *codec;
@@ -909,6 +1191,9 @@ void Engine::codec_poison() {
     }
     if (W.batch_arena) Q3_HIP_CHECK(hipMemset(W.batch_arena, 0xFF, W.batch_arena_bytes));
     if (W.stream_arena) Q3_HIP_CHECK(hipMemset(W.stream_arena, 0xFF, W.stream_arena_bytes));
+    if (W.sbatch_arena) Q3_HIP_CHECK(hipMemset(W.sbatch_arena, 0xFF, W.sbatch_arena_bytes));
+    if (W.sbatch_desc) Q3_HIP_CHECK(hipMemset(W.sbatch_desc, 0xFF, W.sbatch_desc_n * sizeof(CodecStreamDesc)));   // uploaded anew by every push
+    if (W.sbatch_codes) Q3_HIP_CHECK(hipMemset(W.sbatch_codes, 0xFF, W.sbatch_codes_n * sizeof(int32_t)));
     if (W.job_codes) Q3_HIP_CHECK(hipMemset(W.job_codes, 0xFF, W.job_codes_n * sizeof(int32_t)));   // -1: clamped to code 0 by the gather, never out of the table
     Q3_HIP_CHECK(hipDeviceSynchronize());
 }

@@ -1407,4 +1407,87 @@ void launch_dwconv_ln(const float* x, int T, int C, const float* dw_w, const flo
     if (T > 0) hipLaunchKernelGGL(k_dwconv_ln, dim3(T), dim3(256), (size_t)C * sizeof(float), s, x, T, C, dw_w, dw_b, ln_w, ln_b, out, rows_per_utt);
 }
 
+// ---- batched carried-state push: the per-position kernels above with a stream descriptor per blockIdx.y (grid: longest n x streams) ----
+__global__ void k_code_embed_mean_streams(const float* table, const CodecStreamDesc* descs, int G, int codebook, int C, float* out0) {
+    const CodecStreamDesc S = descs[blockIdx.y];
+    const int t = blockIdx.x;
+    if (t >= S.n) return;
+    float* out = out0 + (size_t)(S.row_off + t) * C;
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        float s = 0.f;
+        for (int g = 0; g < G; ++g) {
+            int code = S.codes[(size_t)t * G + g];
+            code = code < 0 ? 0 : (code < codebook ? code : codebook - 1);
+            s += table[((size_t)g * codebook + code) * C + c];
+        }
+        out[c] = s / (float)G;
+    }
+}
+void launch_code_embed_mean_streams(const float* table, const CodecStreamDesc* descs, int g, int n_max, int G, int codebook, int C, float* out, hipStream_t s) {
+    if (g > 0 && n_max > 0) hipLaunchKernelGGL(k_code_embed_mean_streams, dim3(n_max, g), dim3(256), 0, s, table, descs, G, codebook, C, out);
+}
+
+// k_rope_store for packed rows: row t of stream y is position a0 + t (the tables' row) and goes to row k0 + t of the stream's own cache
+__global__ void k_rope_store_streams(float* qkv, int ld, const CodecStreamDesc* descs, int layer, int nq, int nkv, int d, const float* cs, const float* sn) {
+    const CodecStreamDesc S = descs[blockIdx.y];
+    const int t = blockIdx.x, half = d / 2;
+    if (t >= S.n) return;
+    float* row = qkv + (size_t)(S.row_off + t) * ld;
+    const size_t P = (size_t)S.P;
+    float* kc = S.kv + (size_t)layer * 2 * nkv * P * d;
+    float* vc = kc + (size_t)nkv * P * d;
+    const size_t tp = (size_t)(S.a0 + t) * half, tr = (size_t)(S.k0 + t);
+    for (int i = threadIdx.x; i < (nq + nkv) * half; i += blockDim.x) {
+        const int h = i / half, e = i % half;
+        float* v = row + (size_t)h * d;
+        const float c = cs[tp + e], s = sn[tp + e];
+        const float x0 = v[e], x1 = v[e + half];
+        const float y0 = x0 * c + (-x1) * s, y1 = x1 * c + x0 * s;
+        if (h < nq) { v[e] = y0; v[e + half] = y1; }
+        else {
+            float* dst = kc + ((size_t)(h - nq) * P + tr) * d;
+            dst[e] = y0; dst[e + half] = y1;
+        }
+    }
+    for (int i = threadIdx.x; i < nkv * d; i += blockDim.x) {
+        const int kh = i / d, e = i % d;
+        vc[((size_t)kh * P + tr) * d + e] = row[(size_t)(nq + nkv + kh) * d + e];
+    }
+}
+void launch_rope_store_streams(float* qkv, int ld, const CodecStreamDesc* descs, int g, int n_max, int layer, int nq, int nkv, int d,
+                               const float* cs, const float* sn, hipStream_t s) {
+    if (g > 0 && n_max > 0) hipLaunchKernelGGL(k_rope_store_streams, dim3(n_max, g), dim3(256), 0, s, qkv, ld, descs, layer, nq, nkv, d, cs, sn);
+}
+
+// k_rmsnorm_rows whose output row is the stream's own: packed row row_off + t -> hpost[h0 + t]
+__global__ __launch_bounds__(256) void k_rmsnorm_rows_streams(const float* x, const float* w, float eps, const CodecStreamDesc* descs, int C) {
+    __shared__ float red[4];
+    const CodecStreamDesc S = descs[blockIdx.y];
+    const int t = blockIdx.x;
+    if (t >= S.n) return;   // the whole workgroup leaves: no barrier is skipped by a part of it
+    const float* xr = x + (size_t)(S.row_off + t) * C;
+    float* out = S.hpost + (size_t)(S.h0 + t) * C;
+    float ss = 0.f;
+    for (int c = threadIdx.x; c < C; c += 256) ss += xr[c] * xr[c];
+    ss = block_sum256(ss, red);
+    const float r = 1.0f / sqrtf(ss / (float)C + eps);
+    for (int c = threadIdx.x; c < C; c += 256) out[c] = w[c] * (xr[c] * r);
+}
+void launch_rmsnorm_rows_streams(const float* x, const float* w, float eps, const CodecStreamDesc* descs, int g, int n_max, int C, hipStream_t s) {
+    if (g > 0 && n_max > 0) hipLaunchKernelGGL(k_rmsnorm_rows_streams, dim3(n_max, g), dim3(256), 0, s, x, w, eps, descs, C);
+}
+
+// the window the stages behind the transformer decode: kept rows + new rows of every stream of a group, one [Tw][C] sequence each
+__global__ void k_gather_stream_rows(const CodecStreamDesc* descs, int Tw, int C, float* out0) {
+    const CodecStreamDesc S = descs[blockIdx.y];
+    const int t = blockIdx.x;
+    float* out = out0 + ((size_t)S.blk * Tw + t) * C;
+    const bool live = t < S.ctx + S.n;
+    const float* src = S.hpost + (size_t)(S.h0 - S.ctx + (live ? t : 0)) * C;
+    for (int c = threadIdx.x; c < C; c += blockDim.x) out[c] = live ? src[c] : 0.f;
+}
+void launch_gather_stream_rows(const CodecStreamDesc* descs, int g, int Tw, int C, float* out, hipStream_t s) {
+    if (g > 0 && Tw > 0) hipLaunchKernelGGL(k_gather_stream_rows, dim3(Tw, g), dim3(256), 0, s, descs, Tw, C, out);
+}
+
 } // namespace q3

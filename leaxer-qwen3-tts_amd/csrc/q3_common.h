@@ -329,6 +329,31 @@ void launch_rope_store(float* qkv, int ld, int T, int nq, int nkv, int d, const 
 void launch_dwconv_ln(const float* x, int T, int C, const float* dw_w, const float* dw_b, const float* ln_w,
                       const float* ln_b, float* out, hipStream_t s, int rows_per_utt = 0);
 
+// ---- batched carried-state push (Engine::codec_stream_push_batch): n new frames for each of g streams in one set of launches ----
+// Activation rows are packed [stream][its new frames]; a table of these descriptors, uploaded once per push, tells every kernel that
+// looks at a position or at a stream's own buffers where stream blockIdx.z (or .y) lives.  Grids cover the longest n; workgroups
+// beyond a stream's n exit.
+struct CodecStreamDesc {
+    float* kv = nullptr;              // the stream's sliding K / V buffer [layer][k | v][head][P][d]
+    float* hpost = nullptr;           // its kept transformer output rows [h_cap][hidden]
+    const int32_t* codes = nullptr;   // the new frames' codes [n][groups] (device)
+    int32_t P = 0;                    // rows per (layer, k | v, head) block of kv
+    int32_t k0 = 0, h0 = 0;           // first new row in kv / in hpost
+    int32_t a0 = 0;                   // absolute position of the first new frame (RoPE)
+    int32_t n = 0, row_off = 0;       // new frames, first packed row
+    int32_t ctx = 0, blk = 0;         // stages behind the transformer: kept rows in front of the new ones, sequence index in its group's block
+};
+void launch_code_embed_mean_streams(const float* table, const CodecStreamDesc* descs, int g, int n_max, int G, int codebook, int C, float* out, hipStream_t s);
+void launch_rope_store_streams(float* qkv, int ld, const CodecStreamDesc* descs, int g, int n_max, int layer, int nq, int nkv, int d,
+                               const float* cs, const float* sn, hipStream_t s);
+// sliding-window attention of the packed rows over each stream's own cache (q roped, K / V stored: after launch_rope_store_streams)
+void launch_attn_streams(const float* qkv, int ld_qkv, float* out, int ld_out, const CodecStreamDesc* descs, int g, int n_max, int layer,
+                         int heads, int d, int window, float scale, hipStream_t s);
+bool attn_streams_windowed(int heads, int d, int window, int ld_qkv, int ld_out);   // launch_attn_streams covers these dims (k_attn_win's sibling); others keep k_attn, stream by stream
+void launch_rmsnorm_rows_streams(const float* x, const float* w, float eps, const CodecStreamDesc* descs, int g, int n_max, int C, hipStream_t s);   // row -> hpost[h0 + t]
+// out [g][Tw][C]: sequence blk = the stream's hpost rows [h0 - ctx, h0 + n), zeros behind them
+void launch_gather_stream_rows(const CodecStreamDesc* descs, int g, int Tw, int C, float* out, hipStream_t s);
+
 
 // ---- speaker encoder + GPU audio front end of the clone path (q3_speaker_kernels.hip) ----
 // One reference clip of a batch.  Activations of a batch lie clip after clip along time ([sum T][C]); every kernel that looks across

@@ -1585,23 +1585,18 @@ __global__ __launch_bounds__(128) void k_attn_tiny2(const float* pqkv, const flo
 // [8 j, 8 j + 8).  Which lane handles which window offset depends on the offset alone, so a chunked decode (the carried-state stream)
 // and the one-shot decode sum in the same order.  fp32 throughout, __expf as in k_attn.
 // ================================================================================================
+// The tile (32 queries of one head of one sequence) is a device function shared by the two kernels below: kc / vc = the head's cache rows,
+// base = cache row of the sequence's first new row, qrow0 / orow0 = that row's q and output (this head's columns).
 template <int D, int WMAX>
-__global__ __launch_bounds__(256, 2) void k_attn_win(AttnArgs a) {
+__device__ __forceinline__ void attn_win_tile(const float* kc, const float* vc, const float* qrow0, int ld_qkv, float* orow0, int ld_out,
+                                              int base, int n_new, int q0, int W, float scale) {
     constexpr int QB = 32, ROWS = QB + WMAX - 1, LDK = D + 4, NM = (WMAX + 7) / 8;
     __shared__ __attribute__((aligned(16))) float Ks[ROWS][LDK];
     __shared__ __attribute__((aligned(16))) float Vs[ROWS][LDK];
     __shared__ float Ss[NM][256];                                // a thread's scores between the two passes (its own column: no conflicts, no barrier)
-    const int kvh = blockIdx.x, q0 = blockIdx.y * QB, bi = blockIdx.z;
     const int tid = threadIdx.x, qi = tid >> 3, j = tid & 7;
-    const int base = a.pos_scalar, W = a.window;
     const int wbase = base + q0 - (W - 1);                       // position of staged row 0
-    const int last = base + a.n_new - 1;                         // newest position the cache holds
-    const int slot = a.slot_offset + bi;
-    const int page = a.page_table[(size_t)slot * a.pages_per_slot];
-    const int P = 1 << a.page_shift;
-    const size_t cb = (((size_t)page * a.n_layers + a.layer) * a.nkv + kvh) * (size_t)P * D;
-    const float* kc = a.kcache + cb;
-    const float* vc = a.vcache + cb;
+    const int last = base + n_new - 1;                           // newest position the cache holds
     const int nrows = QB + W - 1;
     constexpr int NIT = (ROWS * (D / 4) + 255) / 256;             // every staging load of the workgroup in flight at once (7 x 2 per thread)
     f32x4 kst[NIT], vst[NIT];
@@ -1624,8 +1619,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_win(AttnArgs a) {
         }
     }
     const int inew = q0 + qi;
-    const int irow = inew < a.n_new ? inew : a.n_new - 1;         // clamped: the loads stay unconditional, the store is masked
-    const float* qrow = a.qkv + (size_t)(bi * a.n_new + irow) * a.ld_qkv + kvh * D;
+    const int irow = inew < n_new ? inew : n_new - 1;             // clamped: the loads stay unconditional, the store is masked
+    const float* qrow = qrow0 + (size_t)irow * ld_qkv;
     float q[D];
 #pragma unroll
     for (int d = 0; d < D; d += 4) {
@@ -1662,7 +1657,7 @@ __global__ __launch_bounds__(256, 2) void k_attn_win(AttnArgs a) {
             const f32x4 kv = *reinterpret_cast<const f32x4*>(&Ks[row][d]);
             s = fmaf(q[d], kv.x, s); s = fmaf(q[d + 1], kv.y, s); s = fmaf(q[d + 2], kv.z, s); s = fmaf(q[d + 3], kv.w, s);
         }
-        const float scv = valid ? s * a.scale : -INFINITY;
+        const float scv = valid ? s * scale : -INFINITY;
         Ss[m][tid] = scv;
         mx = fmaxf(mx, scv);
     }
@@ -1688,8 +1683,8 @@ __global__ __launch_bounds__(256, 2) void k_attn_win(AttnArgs a) {
     l = dpp8_sum(l);
 #pragma unroll
     for (int d = 0; d < D; ++d) oacc[d] = dpp8_sum(oacc[d]);
-    if (inew < a.n_new) {
-        float* out = a.out + (size_t)(bi * a.n_new + inew) * a.ld_out + kvh * D;
+    if (inew < n_new) {
+        float* out = orow0 + (size_t)inew * ld_out;
         const float inv = 1.0f / l;
 #pragma unroll
         for (int e8 = 0; e8 < D / 8; ++e8) {                     // lane j stores dims [8 j, 8 j + 8) (statically indexed registers: a select per 8-dim block)
@@ -1700,6 +1695,43 @@ __global__ __launch_bounds__(256, 2) void k_attn_win(AttnArgs a) {
             }
         }
     }
+}
+// the whole-sequence launch (codec_run, codec_pre_batch, one stream's push): base, the row count and the cache block are launch-wide
+template <int D, int WMAX>
+__global__ __launch_bounds__(256, 2) void k_attn_win(AttnArgs a) {
+    const int kvh = blockIdx.x, q0 = blockIdx.y * 32, bi = blockIdx.z;
+    const int slot = a.slot_offset + bi;
+    const int page = a.page_table[(size_t)slot * a.pages_per_slot];
+    const int P = 1 << a.page_shift;
+    const size_t cb = (((size_t)page * a.n_layers + a.layer) * a.nkv + kvh) * (size_t)P * D;
+    attn_win_tile<D, WMAX>(a.kcache + cb, a.vcache + cb, a.qkv + (size_t)bi * a.n_new * a.ld_qkv + kvh * D, a.ld_qkv,
+                           a.out + (size_t)bi * a.n_new * a.ld_out + kvh * D, a.ld_out, a.pos_scalar, a.n_new, q0, a.window, a.scale);
+}
+// its sibling for a batched push: blockIdx.z selects a stream descriptor — the stream's own cache, its first new cache row k0, its n and
+// its packed rows.  Same tile, same lane-to-window-offset mapping: a query's sums do not depend on which launch computes them.  grid.y
+// covers the longest n; tiles beyond a stream's n exit (the whole workgroup: no barrier is left behind).
+template <int D, int WMAX>
+__global__ __launch_bounds__(256, 2) void k_attn_win_streams(const CodecStreamDesc* descs, const float* qkv, int ld_qkv, float* out, int ld_out,
+                                                             int layer, int heads, int W, float scale) {
+    const CodecStreamDesc S = descs[blockIdx.z];
+    const int h = blockIdx.x, q0 = blockIdx.y * 32;
+    if (q0 >= S.n) return;
+    const size_t blk = (size_t)S.P * D;
+    const float* kc = S.kv + ((size_t)layer * 2 * heads + h) * blk;
+    attn_win_tile<D, WMAX>(kc, kc + (size_t)heads * blk, qkv + (size_t)S.row_off * ld_qkv + h * D, ld_qkv, out + (size_t)S.row_off * ld_out + h * D, ld_out,
+                           S.k0, S.n, q0, W, scale);
+}
+bool attn_streams_windowed(int heads, int d, int window, int ld_qkv, int ld_out) {
+    return d == 64 && window > 0 && window <= 72 && heads >= 1 && heads <= 65535 && ld_qkv % 4 == 0 && ld_out % 4 == 0;
+}
+void launch_attn_streams(const float* qkv, int ld_qkv, float* out, int ld_out, const CodecStreamDesc* descs, int g, int n_max, int layer,
+                         int heads, int d, int window, float scale, hipStream_t s) {
+    if (g < 1 || n_max < 1) return;
+    if (g > 65535 || n_max > 65535 * 32) throw Error("attn (streams): at most 65535 streams and 2^21 rows per stream");
+    // other head sizes / windows (tiny configs): the caller keeps k_attn, one launch per stream (Engine::codec_stream_push_batch)
+    if (!attn_streams_windowed(heads, d, window, ld_qkv, ld_out)) throw Error("attn (streams): head_dim 64, window 1..72");
+    hipLaunchKernelGGL((k_attn_win_streams<64, 72>), dim3(heads, (n_max + 31) / 32, g), dim3(256), 0, s, descs, qkv, ld_qkv, out, ld_out, layer, heads, window, scale);
+    Q3_HIP_CHECK(hipGetLastError());
 }
 static bool attn_win_ok(const AttnArgs& a) {
     const bool off = knob("Q3TTS_ATTN_WIN") && atoi(knob("Q3TTS_ATTN_WIN")) == 0;   // A/B knob: back to k_attn

@@ -129,6 +129,13 @@ public:
     int codec_stream_frames(int sid) const;
     int codec_stage_b_context() const;          // frames the stages behind the pre-transformer look back
     int64_t slot_codec_stream_range(int slot, int a, int b, float* pcm, int64_t cap);
+    // batched push: n new frames (device codes) for each of g distinct streams in one set of launches; n == 0 leaves a stream untouched.
+    // PCM lands in the callers' host buffers (min(n_own, cap) samples); validated as a whole before any stream advances
+    struct StreamPush { int sid = -1; const int32_t* codes_dev = nullptr; int n = 0; float* pcm = nullptr; int64_t cap = 0; int64_t n_own = 0; };
+    void codec_stream_push_batch(StreamPush* ps, int g);
+    void codec_stream_push_batch_host(int n_streams, const int32_t* sids, const int64_t* codes, const int32_t* frame_offsets, float* const* pcm_out,
+                                      int64_t cap, int64_t* pcm_len);
+    void slots_codec_decode_new(int n_slots, const int32_t* slots, float* const* pcm_out, int64_t cap, int64_t* pcm_len, int32_t* frame_begin, int32_t* frame_end);
     void slot_codec_stream_reset(int slot);
     void codec_rope_tables(int P);
 

@@ -246,6 +246,27 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
     return done;
 }
 
+std::vector<int> TTSEngine::synthesize_tokens_batch_streaming(const std::vector<std::vector<int64_t>>& token_ids, Language lang, const SamplingParams& params,
+                                                              int chunk_frames, const std::function<bool(int, const float*, size_t, bool)>& on_audio) {
+    if (!ready_ || token_ids.empty() || chunk_frames < 1 || !on_audio) return {};
+    q3tts_sampling sp{ params.temperature, params.top_p, params.top_k, params.repetition_penalty, params.max_new_tokens };
+    std::vector<int64_t> flat;
+    std::vector<int32_t> offs(1, 0);
+    for (const auto& t : token_ids) { flat.insert(flat.end(), t.begin(), t.end()); offs.push_back((int32_t)flat.size()); }
+    std::vector<int32_t> frames(token_ids.size(), 0);
+    struct Ctx { const std::function<bool(int, const float*, size_t, bool)>* f; } ctx{ &on_audio };
+    const q3tts_audio_cb cb = [](void* user, int utt, int, int, const float* pcm, int64_t n, int finished) -> int {
+        return (*static_cast<Ctx*>(user)->f)(utt, pcm, (size_t)n, finished != 0) ? 1 : 0;
+    };
+    const int rc = q3tts_synthesize_stream_host(h_, (int)token_ids.size(), flat.data(), offs.data(), lang_index(lang), nullptr, &sp, nullptr, seed_, 0,
+                                                nullptr, 0, nullptr, frames.data(), nullptr, chunk_frames, cb, &ctx);
+    if (rc != 0) {
+        std::cerr << "[TTSEngine] Synthesis error: " << q3tts_last_error(h_) << std::endl;
+        return {};
+    }
+    return std::vector<int>(frames.begin(), frames.end());
+}
+
 std::vector<float> TTSEngine::synthesize_tokens(const std::vector<int64_t>& token_ids, Language lang, const SamplingParams& params) {
     if (!ready_) return {};
     auto r = synthesize_tokens_batch({ token_ids }, lang, params);

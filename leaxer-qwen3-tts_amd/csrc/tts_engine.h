@@ -76,6 +76,11 @@ public:
     // Returns the number of frames generated, -1 on error.
     int synthesize_tokens_streaming(const std::vector<int64_t>& token_ids, Language lang, const SamplingParams& params, int chunk_frames,
                                     int left_context_frames, const std::function<void(const float*, size_t)>& on_audio);
+    // the same for a batch: every chunk_frames steps each utterance with new audio gets on_audio(utt, pcm, n, finished) — its tail with
+    // finished = true, once and last; more utterances than slots queue.  A true return from on_audio cancels the job.  Returns the
+    // frames generated per utterance (empty on error).
+    std::vector<int> synthesize_tokens_batch_streaming(const std::vector<std::vector<int64_t>>& token_ids, Language lang, const SamplingParams& params,
+                                                       int chunk_frames, const std::function<bool(int, const float*, size_t, bool)>& on_audio);
     void set_seed(uint64_t seed) { seed_ = seed; }
     // ids of `text` from the loaded tokenizer (reference io::tokenize, src/io/tokenizer.h:22)
     std::vector<int32_t> tokenize(const std::string& text) const;

@@ -91,7 +91,11 @@ EXPORTS = [
     "q3tts_resample_gpu_host", "q3tts_mel_gpu_host", "q3tts_speaker_embed_pcm_batch_host",
     "q3tts_codec_decode_chunked_host", "q3tts_slot_codec_decode_range_host", "q3tts_slot_logits_host", "q3tts_step_logits_host",
     "q3tts_sample_hist_host", "q3tts_sample_hist_dev",
+    "q3tts_codec_stream_push_batch_host", "q3tts_slots_codec_decode_new_host", "q3tts_synthesize_stream_host",
 ]
+
+# q3tts_audio_cb: int (*)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished)
+AUDIO_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int64, C.c_int)
 
 _lib = None
 
@@ -385,6 +389,46 @@ class Engine:
         self._ck(self.L.q3tts_codec_stream_push_host(self.h, sid, _p(c), c.shape[0], _p(pcm), cap, C.byref(n)))
         return pcm[: n.value]
 
+    def codec_stream_push_batch(self, sids, codes_list):
+        """the next frames of many streams in one batched pass (q3tts_codec_stream_push_batch_host): one [n_s][n_groups] code array per
+        stream (n_s may be 0: the stream is left untouched) -> one PCM array each"""
+        n = len(sids)
+        if n == 0:
+            return []
+        if len(codes_list) != n:
+            raise ValueError("codec_stream_push_batch: one code array per stream")
+        cs = [np.ascontiguousarray(c_, np.int64).reshape(-1, self.cfg.n_groups) for c_ in codes_list]
+        return self._push_batch(np.ascontiguousarray(sids, np.int32), cs, np.cumsum([0] + [c_.shape[0] for c_ in cs]).astype(np.int32))
+
+    def _push_batch(self, ids, cs, offs):
+        n = len(ids)
+        flat = np.ascontiguousarray(np.concatenate(cs)) if sum(c_.shape[0] for c_ in cs) else np.zeros((1, self.cfg.n_groups), np.int64)
+        cap = self.codec_decode_len(max(max(c_.shape[0] for c_ in cs), 1)) + 4096
+        pcm = [np.empty(cap, np.float32) for _ in range(n)]
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in pcm])
+        pcm_len = np.zeros(n, np.int64)
+        self.L.q3tts_codec_stream_push_batch_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        self._ck(self.L.q3tts_codec_stream_push_batch_host(self.h, n, _p(ids), _p(flat), _p(offs), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len)))
+        return [pcm[i][: pcm_len[i]] for i in range(n)]
+
+    def slots_codec_decode_new(self, slots, max_new_frames=None):
+        """samples of the frames each listed slot has generated since its previous streaming call, all slots in batched passes
+        (q3tts_slots_codec_decode_new_host) -> [(frame_begin, frame_end, pcm)] per slot.  max_new_frames bounds the new frames of
+        a slot (default: the slots' frame counts, asked for first)"""
+        n = len(slots)
+        if n == 0:
+            return []
+        ids = np.ascontiguousarray(slots, np.int32)
+        if not max_new_frames:
+            max_new_frames = max(self.slot_status(int(b))[0] for b in slots)
+        cap = self.codec_decode_len(max(int(max_new_frames), 1)) + 4096
+        pcm = [np.empty(cap, np.float32) for _ in range(n)]
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in pcm])
+        pcm_len, fb, fe = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self.L.q3tts_slots_codec_decode_new_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._ck(self.L.q3tts_slots_codec_decode_new_host(self.h, n, _p(ids), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(fb), _p(fe)))
+        return [(int(fb[i]), int(fe[i]), pcm[i][: pcm_len[i]]) for i in range(n)]
+
     def codec_stream_end(self, sid):
         self.L.q3tts_codec_stream_end.argtypes = [C.c_void_p, C.c_int]
         self._ck(self.L.q3tts_codec_stream_end(self.h, sid))
@@ -565,6 +609,56 @@ class Engine:
         self._ck(self.L.q3tts_synthesize_schedule_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
                                                        seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr),
                                                        _p(codes) if want_codes else None))
+        outs = [pcm[i][: pcm_len[i]] for i in range(n)]
+        cl = [codes[i, : nfr[i]] for i in range(n)] if want_codes else None
+        return outs, cl, nfr
+
+    def synthesize_stream(self, token_lists, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
+                          max_new_per_utt=None):
+        """synthesize_batch that delivers audio while it generates (q3tts_synthesize_stream_host): every chunk_frames steps
+        on_audio(utt, frame_begin, frame_end, pcm, finished) is called once per utterance with new audio (pcm: a copy); a truthy return
+        cancels the job (RuntimeError "cancelled by callback").  Returns what synthesize_batch returns."""
+        n = len(token_lists)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int64) for t in token_lists]))
+        offs = np.zeros(n + 1, np.int32)
+        offs[1:] = np.cumsum([len(t) for t in token_lists])
+        cap = self.codec_decode_len(sp.max_new_tokens)
+        pcm = [np.zeros(cap, np.float32) for _ in range(n)]
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in pcm])
+        pcm_len = np.zeros(n, np.int64)
+        nfr = np.zeros(n, np.int32)
+        codes = np.zeros((n, sp.max_new_tokens, self.cfg.n_groups), np.int64) if want_codes else None
+        spk_keep, spk_ptrs = [], None
+        if speakers is not None:
+            if len(speakers) != n:
+                raise ValueError("speakers: one entry (embedding or None) per utterance")
+            spk_keep = [None if s_ is None else np.ascontiguousarray(s_, np.float32) for s_ in speakers]
+            for a in spk_keep:
+                if a is not None and a.size != self.cfg.hidden:
+                    raise ValueError("speaker embedding has %d values, the model needs %d" % (a.size, self.cfg.hidden))
+            spk_ptrs = C.cast((C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in spk_keep]), C.c_void_p)
+        caps = None if max_new_per_utt is None else np.ascontiguousarray(max_new_per_utt, np.int32)
+        if caps is not None and caps.shape != (n,):
+            raise ValueError("max_new_per_utt: one entry per utterance")
+        raised = []
+
+        def tramp(_user, utt, fb, fe, p, ns, fin):
+            try:
+                a = np.ctypeslib.as_array(p, shape=(ns,)).copy() if ns > 0 else np.zeros(0, np.float32)
+                return 1 if on_audio(utt, fb, fe, a, bool(fin)) else 0
+            except BaseException as ex:   # an exception must not cross the C frames: cancel the job, re-raise behind it
+                raised.append(ex)
+                return 1
+        cb = AUDIO_CB(tramp)
+        vp = C.c_void_p
+        self.L.q3tts_synthesize_stream_host.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.POINTER(Sampling), vp, C.c_uint64, C.c_int, vp, C.c_int64, vp, vp, vp,
+                                                        C.c_int, AUDIO_CB, vp]
+        rc = self.L.q3tts_synthesize_stream_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
+                                                 seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr),
+                                                 _p(codes) if want_codes else None, int(chunk_frames), cb, None)
+        if raised:
+            raise raised[0]
+        self._ck(rc)
         outs = [pcm[i][: pcm_len[i]] for i in range(n)]
         cl = [codes[i, : nfr[i]] for i in range(n)] if want_codes else None
         return outs, cl, nfr
