@@ -263,11 +263,15 @@ struct SampleArgs {
     int pl_row_mul = 1, pl_row_add = 0;
     const float* lh = nullptr; int ld_lh = 0;
     unsigned* step_gen = nullptr;  // group 0 only: the step's generation counter (split-K seam flags), bumped by workgroup 0
+    // optional (one-slot engines, groups 1 .. n_groups - 2): the next predictor pass's layer-0 QKV projection, looked up instead of
+    // computed — qkv_tab [V][qkv_n] is this group's slab of Engine::cp_qkv_tab, row `token` is copied to qkv_out [qkv_n]
+    const float* qkv_tab = nullptr; float* qkv_out = nullptr; int qkv_n = 0;
 };
 void launch_sample(const SampleArgs& a, hipStream_t s);
 
 void launch_gather_rows_bf16(const bf16_t* table, int H, const int64_t* ids_dev, int n, float* out, int ldo, hipStream_t s);
 void launch_fill_synth(void* dst, int is_bf16, int64_t n, uint64_t key, float mean, float stddev, hipStream_t s);
+void launch_bf16_to_f32(const bf16_t* src, float* dst, int64_t n, hipStream_t s);
 void launch_copy_rows(const float* src, int lds, float* dst, int ldd, int rows, int cols, hipStream_t s);
 // rows whose flag is 0 are skipped (flags: device ints, one per row)
 void launch_copy_rows_masked(const float* src, int lds, float* dst, int ldd, int rows, int cols, const int* flags_dev, hipStream_t s);

@@ -2629,7 +2629,10 @@ static __device__ __forceinline__ float kth_largest_of_lanes(float v, int k) {
 // utterance has used).  Generation mode reads the slot's seen bitmap (SampleArgs::seen) in round trip 1 and sets the bit of the id it
 // records; standalone mode builds the same bitmap in LDS from SampleArgs::hist.  The launcher picks PEN only where a bitmap or a history
 // was passed (the code0 sampler of the fused step, q3tts_sample_hist_*): the other fifteen samplers of a frame run the code without it.
-template <bool SLABS, int PW, bool PEN>   // SLABS: the logits row is the ordered sum of a.nslab (<= 4) split-K partial slabs of the head projection
+// TAB (b = 1 predictor samplers of groups 1 .. n_groups - 2): the next predictor pass's layer-0 QKV row is a pure function of (group, code)
+// — W_qkv[0] . RMSNorm(embedding row), no activation enters it — so the epilogue copies it from the engine's table (SampleArgs::qkv_tab)
+// into the pass's qkv row, in the load round of its embedding gather, and the pass starts at its attention launch.
+template <bool SLABS, int PW, bool PEN, bool TAB = false>   // SLABS: the logits row is the ordered sum of a.nslab (<= 4) split-K partial slabs of the head projection
 __global__ __launch_bounds__(256) void k_sample(const float* plogits, SlotState* pst, int pld, int pV, SampleArgs a) {   // leading scalars: preloaded (see k_gemv1)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2996,6 +2999,18 @@ __global__ __launch_bounds__(256) void k_sample(const float* plogits, SlotState*
     const bool planes = a.pl_h != nullptr && a.x_next != nullptr;   // uniform: the next pass's input planes are made here (launcher: H <= 2048)
     const float* lh_r = planes && a.lh ? a.lh + (size_t)b * a.ld_lh : nullptr;
     float ss_e = 0.f, ss_l = 0.f;
+    constexpr int TAB_IT = 4;   // launcher: qkv_n <= 4096 floats = 256 threads x 4 x 16 bytes
+    float tq[TAB ? TAB_IT : 1][4];
+    if (TAB) {   // table row of the sampled code: issued with the gather's loads below (clamped, unconditional), stored behind them
+        const float* tr = a.qkv_tab + (size_t)tok * a.qkv_n;
+#pragma unroll
+        for (int it = 0; it < TAB_IT; ++it) {
+            int q = (it * 256 + tid) * 4;
+            q = q < a.qkv_n ? q : a.qkv_n - 4;
+            const float4 v = *reinterpret_cast<const float4*>(tr + q);
+            tq[it][0] = v.x; tq[it][1] = v.y; tq[it][2] = v.z; tq[it][3] = v.w;
+        }
+    }
     for (int h0 = 0; h0 < a.H; h0 += 1024 * EP_MAX) {
         float e[EP_MAX][4], sm[EP_MAX][4], tx[EP_MAX][4], g0[EP_MAX][4], lhv[EP_MAX][4];
 #pragma unroll
@@ -3055,6 +3070,13 @@ __global__ __launch_bounds__(256) void k_sample(const float* plogits, SlotState*
             }
         }
     }
+    if (TAB) {
+#pragma unroll
+        for (int it = 0; it < TAB_IT; ++it) {
+            const int q = (it * 256 + tid) * 4;
+            if (q < a.qkv_n) *reinterpret_cast<float4*>(a.qkv_out + q) = make_float4(tq[it][0], tq[it][1], tq[it][2], tq[it][3]);
+        }
+    }
     if (planes) {   // the rows' sums of squares: waves in order, then one partial per row (the consumer sums ssq_nt partials: the rest are zero)
         ss_e = wave_sum(ss_e); ss_l = wave_sum(ss_l);
         __syncthreads();                       // sh_f is free again (the token has been read)
@@ -3081,6 +3103,10 @@ void launch_sample(const SampleArgs& a, hipStream_t s) {
     if (pen && a.nslab > 1) throw Error("sample: the repetition penalty takes plain logits rows (no split-K slabs)");
     if (a.seen && (!a.st || a.group != 0 || a.seen_ld < (a.V + 31) / 32)) throw Error("sample: bad seen-bitmap arguments");
     if (a.hist && (a.st || a.seen || a.hist_ld < 0 || !a.hist_len)) throw Error("sample: bad history arguments");
+    // the table copy is built for the one-slot predictor samplers: generation mode, one plain logits row of at most 2048 ids, no planes
+    if (a.qkv_tab && (!a.st || !a.qkv_out || !a.x_next || a.nb != 1 || a.nslab > 1 || pen || a.pl_h || a.V > 2048 || a.qkv_n < 4 || a.qkv_n > 4096 || a.qkv_n % 4))
+        throw Error("sample: bad QKV-table arguments");
+    if (a.qkv_tab) { hipLaunchKernelGGL((k_sample<false, 8, false, true>), dim3(1), dim3(256), 0, s, a.logits, a.st, a.ld, a.V, a); return; }
 #define Q3_SAMP(SL, PW_, PEN_) hipLaunchKernelGGL((k_sample<SL, PW_, PEN_>), dim3(a.nb), dim3(256), 0, s, a.logits, a.st, a.ld, a.V, a)
     if (a.nslab > 1) { if (a.V <= 2048) Q3_SAMP(true, 8, false); else if (a.V <= 3072) Q3_SAMP(true, 12, false); else Q3_SAMP(true, 16, false); }
     else if (pen) { if (a.V <= 2048) Q3_SAMP(false, 8, true); else if (a.V <= 3072) Q3_SAMP(false, 12, true); else Q3_SAMP(false, 16, true); }
@@ -3098,6 +3124,18 @@ __global__ void k_gather_rows_bf16(const bf16_t* table, int H, const int64_t* id
 }
 void launch_gather_rows_bf16(const bf16_t* table, int H, const int64_t* ids_dev, int n, float* out, int ldo, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_gather_rows_bf16, dim3(n), dim3(256), 0, s, table, H, ids_dev, out, ldo);
+}
+
+// bf16 -> fp32 of n contiguous elements (exact): the embedding rows the QKV-table builder feeds to the GEMV, as the sampler writes them
+__global__ void k_bf16_to_f32(const bf16_t* src, float* dst, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = __uint_as_float((uint32_t)src[i] << 16);
+}
+void launch_bf16_to_f32(const bf16_t* src, float* dst, int64_t n, hipStream_t s) {
+    if (n <= 0) return;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_bf16_to_f32, dim3((int)blocks), dim3(256), 0, s, src, dst, n);
 }
 
 __global__ void k_copy_rows(const float* src, int lds, float* dst, int ldd, int cols) {

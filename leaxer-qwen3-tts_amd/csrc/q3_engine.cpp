@@ -193,6 +193,7 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
     if (const char* sv = knob("Q3TTS_ATTN_STREAM")) attn_stream = atoi(sv) != 0;
     if (const char* sv = knob("Q3TTS_ATTN_STREAM_ONE")) attn_stream_one = atoi(sv) != 0;
     if (const char* sv = knob("Q3TTS_KVH_OPROJ")) kvh_oproj = atoi(sv) != 0;
+    if (const char* sv = knob("Q3TTS_CP_QKV_TABLE")) cp_qkv_table_on = atoi(sv) != 0;
     null_stream = getenv("Q3TTS_NULL_STREAM") && getenv("Q3TTS_NULL_STREAM")[0] == '1';
     if (null_stream) { stream = nullptr; flags |= Q3TTS_FLAG_NO_GRAPH; }
     else if (const char* cm = knob("Q3TTS_STREAM_CU_MASK")) {   // experiment aid (tools/overlap_probe.py): this engine's stream on a subset of the CUs;
@@ -374,6 +375,7 @@ Engine::~Engine() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
     for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
+    graphs.clear();
     if (proj_ids_d) (void)hipFree(proj_ids_d);
     if (proj_out_d) (void)hipFree(proj_out_d);
     if (hist_d) (void)hipFree(hist_d);
@@ -439,6 +441,7 @@ void Engine::fill_synthetic(uint64_t seed) {
 // Fragment-packed copies of every matrix the matrix-core decode kernels stream (q3_common.h: launch_pack_mfma_b): + one copy of the
 // bf16 projection weights (1.05 GB at 0.6B dims, 3 GB at 1.7B), registered under the row-major pointer the launch sites keep using.
 void Engine::free_packed_weights() {
+    free_cp_qkv_table();   // derived from the same weights: dropped and rebuilt with the packed copies
     for (auto& pr : packed_w) { unregister_packed_weight(pr.first); (void)hipFree(pr.second); }
     packed_w.clear();
 }
@@ -467,6 +470,64 @@ void Engine::pack_mfma_weights() {
     for (auto& pr : packed_w) register_packed_weight(pr.first, pr.second);
 }
 
+// ------------------------------------------------------------------------------------------------
+// layer-0 QKV table of the b = 1 predictor passes (q3_engine.h: cp_qkv_tab)
+// ------------------------------------------------------------------------------------------------
+GemvArgs Engine::qkv_gemv_args(const DecStack& W, int l, const float* x, int ldx, float* out, int M) const {
+    const int QKV = (W.nq + 2 * W.nkv) * W.d;
+    const DecLayerW& w = W.layers[l];
+    GemvArgs g;
+    g.W = w.qkv; g.x = x; g.ldx = ldx; g.gamma = w.in_norm; g.eps = W.eps; g.out = out; g.ldo = QKV;
+    g.M = M; g.N = QKV; g.K = W.H; g.epi = EPI_STORE; g.nt = W.nt;
+    return g;
+}
+
+// The engine is one of one or two slots, the table copy of k_sample covers the row, and a one-row predictor pass takes the fused
+// attention + o_proj launches (run_layers' gates for them, at a position a later pass runs at).
+bool Engine::cp_qkv_table_applies() const {
+    if (!cp_qkv_table_on || B > 2 || cp_projected() || (flags & Q3TTS_FLAG_NO_FUSED_CP) || cp.layers.empty() || c.n_groups < 3) return false;
+    const int QKV = (cp.nq + 2 * cp.nkv) * cp.d, AO = cp.nq * cp.d;
+    if (c.sub_vocab < 1 || c.sub_vocab > 2048 || QKV < 4 || QKV > 4096 || QKV % 4) return false;
+    if (cp.n_splits != 1 || cp.pages_per_slot != 1 || cp.kv_bf16 || cp.kv_round) return false;
+    const DecLayerW& w = cp.layers[0];
+    CpAttnOprojArgs f;
+    f.ld_qkv = QKV; f.page_tokens = 1 << cp.page_shift; f.base = 1; f.q_norm = w.q_norm; f.k_norm = w.k_norm;
+    f.nq = cp.nq; f.nkv = cp.nkv; f.d = cp.d; f.K = AO; f.N = cp.H; f.ldx = cp.H;
+    return gemv_fast_path(qkv_gemv_args(cp, 0, x_cp1, cp.H, qkv, 1)) && cp_attn_oproj_ok(f, 1);
+}
+
+void Engine::free_cp_qkv_table() {
+    for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
+    graphs.clear();
+    if (cp_qkv_tab) (void)hipFree(cp_qkv_tab);
+    cp_qkv_tab = nullptr;
+}
+
+// One GEMV launch per (group, code), each the launch run_layers would issue for that input row: the bf16 embedding widened to fp32
+// (what the sampler leaves in x_cp1) through the k_gemv1 instantiation of the step, same gamma / eps / nt.  (n_groups - 2) x sub_vocab
+// launches on the engine's stream, back to back.
+void Engine::build_cp_qkv_table() {
+    free_cp_qkv_table();
+    if (!cp_qkv_table_applies()) return;
+    const int H = c.hidden, SV = c.sub_vocab, NG = c.n_groups - 2, QKV = (cp.nq + 2 * cp.nkv) * cp.d;
+    float* rows = nullptr;
+    try {
+        Q3_HIP_CHECK(hipMalloc((void**)&cp_qkv_tab, (size_t)NG * SV * QKV * sizeof(float)));
+        Q3_HIP_CHECK(hipMalloc((void**)&rows, (size_t)SV * H * sizeof(float)));
+        for (int j = 0; j < NG; ++j) {
+            launch_bf16_to_f32(cp_embed_w[j], rows, (int64_t)SV * H, stream);
+            for (int code = 0; code < SV; ++code)
+                launch_gemv(qkv_gemv_args(cp, 0, rows + (size_t)code * H, cp.H, cp_qkv_tab + ((size_t)j * SV + code) * QKV, 1), stream);
+        }
+        sync();
+    } catch (...) {
+        if (rows) (void)hipFree(rows);
+        free_cp_qkv_table();
+        throw;
+    }
+    (void)hipFree(rows);
+}
+
 void Engine::finalize() {
     auto fp = [&](const std::string& n) { return (const float*)T(n).dev; };
     auto bp = [&](const std::string& n) { return (const bf16_t*)T(n).dev; };
@@ -493,6 +554,7 @@ void Engine::finalize() {
     codec_finalize();
     speaker_finalize();
     pack_mfma_weights();
+    build_cp_qkv_table();
     finalized = true;
     // tts_pad_embed_ = text_project(TTS_PAD) (tts_onnx.cpp:459-463), model-wide constant kept on device
     if (TTS_PAD < c.text_vocab) {
@@ -556,6 +618,9 @@ bool Engine::run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new,
     const bool planes_in = planes_in_ready;   // the sampler made planes0 + ssq_b (record_step checked seam_applies for this pass)
     planes_in_ready = false;
     if (planes_in && !seam) throw Error("run_layers: input planes announced without the seam");
+    const bool qkv_in = qkv_in_ready;         // the sampler copied layer 0's qkv row from cp_qkv_tab: the pass starts at its attention launch
+    qkv_in_ready = false;
+    if (qkv_in && (mfma || M != 1 || &W != &cp)) throw Error("run_layers: QKV row announced for a pass that cannot take it");
     auto seam_counters = [&](int n_tiles) -> unsigned* {   // this launch's counter region
         const size_t need = (size_t)n_tiles * 2 * 16;
         if (seam_cnt_used + need > seam_cnt_words) throw Error("split-K seam: counter buffer too small for this step");
@@ -571,11 +636,8 @@ bool Engine::run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new,
             GemmArgs g; // split-K slabs; the attention prologue sums them
             g.W = w.qkv; g.xh = pl0h; g.xl = pl0l; g.ldx = ldp; g.out = qkv_slab_d; g.ldo = QKV; g.M = M; g.N = QKV; g.K = W.H; g.epi = EPI_SLAB; g.nt = W.nt;
             launch_gemm2(g, ks_q, 4, stream);
-        } else {
-            GemvArgs g;
-            g.W = w.qkv; g.x = x; g.ldx = ldx; g.gamma = w.in_norm; g.eps = W.eps; g.out = qkv; g.ldo = QKV;
-            g.M = M; g.N = QKV; g.K = W.H; g.epi = EPI_STORE; g.nt = W.nt;
-            launch_gemv(g, stream);
+        } else if (!(qkv_in && l == 0)) {
+            launch_gemv(qkv_gemv_args(W, l, x, ldx, qkv, M), stream);
         }
         if (!mfma && nb == 1 && pos_dev == nullptr && slot_map == nullptr && W.n_splits == 1 && W.pages_per_slot == 1 && !W.kv_bf16 && !W.kv_round &&
             !(flags & Q3TTS_FLAG_NO_FUSED_CP)) {
@@ -1182,11 +1244,15 @@ void Engine::predictor_passes(int nb, const SampleArgs& s0, bool sp0, bool spn, 
         s.pl_h = pl0h; s.pl_l = pl0l; s.pl_ldp = ldp; s.gamma0 = cp.layers[0].in_norm; s.ssq_out = ssq_b_d; s.ssq_nt = Hc / 64;
         s.pl_row_mul = mul; s.pl_row_add = add; s.lh = lh; s.ld_lh = ld_lh;
     };
+    const int QKVp = (cp.nq + 2 * cp.nkv) * cp.d;
+    bool qkv_filled = false;   // the sampler in front of this pass copied its layer-0 qkv row from cp_qkv_tab
     for (int j = 0; j < G - 1; ++j) {
         // pass 0: rows [last_hidden, embed(code0)] of every utterance; later passes: the embedding of the code just sampled
         float* xin = j == 0 ? cp_project(x_cp, H, nb * 2) : cp_project(x_cp1, H, nb);
         bool pr;
         planes_in_ready = j == 0 ? sp0 : spn;                   // the sampler in front of this pass made its input planes
+        qkv_in_ready = qkv_filled;
+        qkv_filled = false;
         if (j == 0) pr = run_layers(cp, xin, Hc, nb, 2, 0, nullptr, 0, cp_norm, c.cp_rms_eps);
         else pr = run_layers(cp, xin, Hc, nb, 1, 0, nullptr, j + 1, cp_norm, c.cp_rms_eps);
         // head j on the last row of every utterance (pass 0 holds two rows per utterance: planes row b*2+1)
@@ -1201,6 +1267,10 @@ void Engine::predictor_passes(int nb, const SampleArgs& s0, bool sp0, bool spn, 
         s.x_next = j + 1 < G - 1 ? x_cp1 : nullptr; s.ld_xnext = H;
         s.pl_h = nullptr; s.lh = nullptr; s.step_gen = nullptr; s.seen = nullptr;   // the penalty is the first codebook's alone
         if (spn && s.x_next) with_planes(s, 1, 0, nullptr, 0);
+        if (nb == 1 && cp_qkv_tab && s.x_next && !s.pl_h && nsl == 1) {   // one slot: pass j + 1 takes its layer-0 qkv row from the table
+            s.qkv_tab = cp_qkv_tab + (size_t)j * SV * QKVp; s.qkv_out = qkv; s.qkv_n = QKVp;
+            qkv_filled = true;
+        }
         launch_sample(s, stream);
         mark();
     }

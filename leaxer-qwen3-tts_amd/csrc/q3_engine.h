@@ -261,6 +261,19 @@ public:
     // o_proj split by kv head (b = 1, both stacks): the 8 heads' partial rows [8][<= 2 rows][H] that the gate/up GEMV adds to x, and the sum
     // x + o_proj [<= 2][H] it leaves for the down projection's residual operand
     float *oproj_part_d = nullptr, *xmid_d = nullptr;
+    // Layer-0 QKV rows of predictor passes 1 .. n_groups - 2 at b = 1, looked up instead of computed.  The input row of such a pass is
+    // cp_embed_w[g - 1][code], so W_qkv[0] . RMSNorm(in_norm[0])(row) depends on the weights and (g, code) alone: cp_qkv_tab
+    // [n_groups - 2][sub_vocab][QKV] fp32 (470 MB at 0.6B dims) holds every such row, made at finalize by the very GEMV launch the step
+    // would issue (qkv_gemv_args: bit-identical).  The sampler of group g copies row (g, code) into qkv (SampleArgs::qkv_tab) and
+    // announces it through qkv_in_ready; run_layers then starts the pass at its attention launch.  Built only by engines of one or two
+    // slots whose predictor takes the fused b = 1 path (cp_qkv_table_applies); wider engines keep the GEMV when they drain to one slot.
+    float* cp_qkv_tab = nullptr;
+    bool cp_qkv_table_on = true;   // Q3TTS_CP_QKV_TABLE=0 at engine creation: no table, the GEMV is launched (A/B knob, tests' second path)
+    bool qkv_in_ready = false;     // predictor_passes -> run_layers: the sampler in front already wrote layer 0's qkv row
+    bool cp_qkv_table_applies() const;
+    void build_cp_qkv_table();
+    void free_cp_qkv_table();      // also drops the captured graphs: an nb = 1 graph has the table's address baked in
+    GemvArgs qkv_gemv_args(const DecStack& W, int l, const float* x, int ldx, float* out, int M) const;   // a layer's QKV projection on the GEMV path
     bool kvh_oproj = true;       // Q3TTS_KVH_OPROJ=0 at engine creation: o_proj keeps the whole K in one launch (k_cp_attn_oproj / COMB GEMV; A/B knob, tests' second path)
     // split-K seam of the batched step (GemmArgs::seam): arrival / claim counters, one region per seam launch of the step (generation-valued words:
     // never reset), and the per-(row, 64-column tile) sums of squares behind the two residual seams of a layer
