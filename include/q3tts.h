@@ -123,8 +123,11 @@ int q3tts_text_project_host(q3tts_engine* e, const int64_t* ids, int n, float* o
 int q3tts_codec_embed_host(q3tts_engine* e, const int64_t* ids, int n, float* out);
 /* run_code_predictor_embed, tts_onnx.cpp:592-613 */
 int q3tts_cp_embed_host(q3tts_engine* e, int64_t id, int generation_step, float* out);
-/* run_prefill, tts_onnx.cpp:615-665: embeds[S][hidden] -> logits[S][vocab], last_hidden[hidden];
- * the KV cache of `slot` is reset and stays device-resident (replaces KVCache, tts_onnx.h:108-115) */
+/* run_prefill, tts_onnx.cpp:615-665: embeds[S][hidden] -> logits[S][vocab], last_hidden[hidden]; 1 <= S <= max_ctx; either output
+ * may be NULL.  The KV cache of `slot` is reset and stays device-resident (replaces KVCache, tts_onnx.h:108-115).  Up to 16 rows (the
+ * reference's own prompt is 8-10) take one pass; a longer prompt — an instruction or any other prefix in front of it — is walked in
+ * chunks of up to 128 rows, each attending causally over what the chunks before it left in the cache.  `logits`, when given, still
+ * receives all S rows; with logits == NULL the codec head runs on the last row only. */
 int q3tts_talker_prefill_host(q3tts_engine* e, int slot, const float* embeds, int S, float* logits, float* last_hidden);
 /* run_decode, tts_onnx.cpp:667-732: one token appended to `slot` */
 int q3tts_talker_decode_host(q3tts_engine* e, int slot, const float* embed, float* logits, float* last_hidden);
@@ -197,9 +200,10 @@ int q3tts_slots_codec_decode_new_host(q3tts_engine* e, int n_slots, const int32_
  * work — the call is ordered inside the caller's stream like a kernel launch.  The calls that track positions on the host
  * (prefill / decode / code_predictor) return after their launches have completed; q3tts_sample_dev returns at once.
  * Per-slot state is shared with the "_host" entry points and the fused generation (positions, KV cache, the armed logits row). */
-/* run_prefill, tts_onnx.cpp:615-665: embeds[batch][S][hidden] (row block b: lens[b] <= S <= 16 rows; lens NULL = S for all) ->
+/* run_prefill, tts_onnx.cpp:615-665: embeds[batch][S][hidden] (row block b: lens[b] <= S <= max_ctx rows; lens NULL = S for all) ->
  * logits_last[batch][vocab] (the last prompt row's, all the reference consumes, :797-798), last_hidden[batch][hidden]; either may be NULL.
- * Consecutive slots with equal lengths share one pass through the layers; a slot on its own takes q3tts_talker_prefill_host's launches. */
+ * Consecutive slots with equal lengths share one pass through the layers; a slot on its own takes q3tts_talker_prefill_host's launches, and a slot with lens[b] > 16 its chunked
+ * long-prompt path, one slot at a time. */
 int q3tts_talker_prefill_dev(q3tts_engine* e, const float* embeds, int batch, int S, const int32_t* lens, float* logits_last, float* last_hidden, void* stream);
 /* run_decode, tts_onnx.cpp:667-732: embeds[batch][hidden] -> logits[batch][vocab], last_hidden[batch][hidden]; one token appended to every
  * slot whose active_mask[b] != 0 (NULL: all).  Masked rows keep the batch's shape and leave outputs, position and slot state untouched. */
@@ -229,6 +233,20 @@ float q3tts_rng_uniform(uint64_t seed, uint32_t stream, uint32_t frame, uint32_t
  * trailing[cap_rows][hidden] receives trailing_text_hidden_, *n_trailing its row count. */
 int q3tts_build_prompt_host(q3tts_engine* e, const int64_t* ids, int n_ids, int lang, const float* speaker,
                             float* prompt, int* S, float* trailing, int cap_rows, int* n_trailing);
+/* Voice instructions — the reference README's roadmap row "Voice instructions (--instruct), 1.7B-VoiceDesign: Planned".  The prompt of
+ * build_prompt_embeddings (tts_onnx.cpp:442-539) with an instruction in front of it: rows 0 .. n_instruct-1 of prompt[cap_prompt_rows][hidden]
+ * are text_project(instruct_ids) (run_text_project, :541-559), the rest is exactly what q3tts_build_prompt_host produces; *S = n_instruct +
+ * its row count (needs cap_prompt_rows >= n_instruct + 16).  n_instruct == 0 gives that prompt unchanged.  The caller supplies the
+ * instruction already framed (q3tts_frame_instruct_ids): this entry does not know the chat template. */
+int q3tts_build_prompt_instruct_host(q3tts_engine* e, const int64_t* ids, int n_ids, int lang, const float* speaker,
+                                     const int64_t* instruct_ids, int n_instruct,
+                                     float* prompt, int cap_prompt_rows, int* S, float* trailing, int cap_rows, int* n_trailing);
+/* [HINT], unpinned.  Frames a tokenised instruction as a chat turn: <|im_start|>user\n ... <|im_end|>\n, i.e.
+ * [151644, 872, 198] + text_ids + [151645, 198] — the upstream Qwen3-TTS instruct template as recalled; the reference has not implemented
+ * it (README roadmap) and no VoiceDesign checkpoint was available to confirm it.  Should a checkpoint show another template, these five
+ * constants are the only thing to change.  Host-only: needs no engine and no GPU.  Returns the framed length n + 5 and writes
+ * min(n + 5, cap) ids (out may be NULL with cap = 0 to size); -1 on a bad argument. */
+int64_t q3tts_frame_instruct_ids(const int32_t* text_ids, int64_t n, int64_t* out, int64_t cap);
 
 /* ---- fused, batched generation (generate_codes + predict_subcodes, tts_onnx.cpp:782-872) ---- */
 /* Admit an utterance into `slot`: uploads prompt + trailing rows, runs prefill, arms the slot.
@@ -286,6 +304,17 @@ int q3tts_synthesize_stream_host(q3tts_engine* e, int n_utt, const int64_t* ids,
                                  const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                  float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                  int chunk_frames, q3tts_audio_cb cb, void* user);
+/* The scheduler entries with a voice instruction per utterance (README roadmap row "--instruct"): instruct_ids / instruct_offsets
+ * [n_utt + 1] give utterance u the framed instruction ids [instruct_offsets[u], instruct_offsets[u + 1]); an empty range means none, and
+ * instruct_ids == NULL none for any.  An instructed utterance's prompt is q3tts_build_prompt_instruct_host's and is prefilled on its own
+ * (long-prompt path); the others share their pass as before.  cb != NULL: q3tts_synthesize_stream_host's delivery; cb == NULL:
+ * q3tts_synthesize_schedule_host (chunk_frames and user are ignored).  One implementation behind all three; results do not depend on the
+ * schedule (RNG stream = utterance index). */
+int q3tts_synthesize_instruct_host(q3tts_engine* e, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                                   int chunk_frames, q3tts_audio_cb cb, void* user,
+                                   const int64_t* instruct_ids, const int32_t* instruct_offsets);
 /* io::read_wav (src/io/wav_reader.h:13, wav_reader.cpp:28-143): mono float samples; -1 when the reference
  * returns an empty vector.  Call with out == NULL to learn *n_samples. */
 int q3tts_read_wav_host(const char* path, float* out, int64_t cap, int64_t* n_samples, int32_t* sample_rate);
@@ -349,7 +378,8 @@ int q3tts_stage_profile(q3tts_engine* e, int n_steps, double* out_ms /* [4] */);
 /* Device time of the prefill stage (run_prefill, tts_onnx.cpp:615-665): `reps` batched prefill passes of slots 0..n_slots-1 (all free)
  * over n_rows synthetic prompt rows each, already in HBM — the launches a job's equal-length prompts take (groups of up to 128 rows
  * share one pass over the talker's weights) — with HIP events around each pass; *ms_per_pass = mean device milliseconds.  The slots
- * are released again.  bench.py's stages.prefill. */
+ * are released again.  bench.py's stages.prefill.  n_slots == 1 also takes n_rows up to max_ctx: the chunked long-prompt prefill
+ * (tools/prefill_long_bench.py). */
 int q3tts_prefill_profile(q3tts_engine* e, int n_slots, int n_rows, int reps, double* ms_per_pass);
 /* Measurement aid (engines created with Q3TTS_FLAG_TEST_HOOKS only): every armed slot jumps n_frames ahead without generating them — frame
  * counters and talker positions advance, the skipped frames' codes are zero and the talker's KV cache is refilled with seeded synthetic rows.

@@ -2,7 +2,8 @@
 // (reference src/main_onnx.cpp:60-77, 99-124): -m -p -o --lang --ref --temp --top-k --top-p --max-tokens -h, plus --rep-penalty (an extension),
 // unknown flags ignored, 16-bit mono WAV at 24 kHz (clip to [-1,1], truncate x*32767).  Additions:
 // --tokens "id,id,..." (pre-tokenised text between TTS_BOS and TTS_EOS, bypassing vocab.json/merges.txt),
-// --seed N.
+// --seed N, --instruct TEXT / --instruct-tokens "id,id,..." (a voice instruction in front of the prompt: the reference README's roadmap
+// row "Voice instructions (--instruct)"; combines with --ref).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -40,6 +41,8 @@ static void usage(const char* prog) {
     printf("      --tokens IDS      comma-separated text token ids (framed as IM_START ASSISTANT TTS_BOS ids TTS_EOS IM_END)\n");
     printf("  -o, --output PATH     output WAV file (default: output.wav)\n");
     printf("  --lang LANG           auto, en, zh, ja, ko (default: auto)\n");
+    printf("  --instruct TEXT       voice instruction placed in front of the prompt (tokenised with the loaded vocab; combines with --ref)\n");
+    printf("  --instruct-tokens IDS comma-separated text token ids of the instruction (for synthetic: models, like --tokens)\n");
     printf("  --ref PATH            reference audio for voice clone (WAV; resampled to 24 kHz, ECAPA speaker encoder on the GPU)\n");
     printf("  --temp FLOAT          temperature (default: 0.8; 0 samples at T=1 like the reference, use --top-k 1 for greedy)\n");
     printf("  --top-k N             top-k (default: 50)\n  --top-p FLOAT         top-p (default: 0.95)\n");
@@ -57,7 +60,7 @@ static Language lang_of(const std::string& s) {
 }
 
 int main(int argc, char** argv) {
-    std::string model, prompt, tokens, output = "output.wav", lang = "auto", ref;
+    std::string model, prompt, tokens, output = "output.wav", lang = "auto", ref, instruct, instruct_tokens;
     bool have_prompt = false;
     SamplingParams sp;
     uint64_t seed = 0;
@@ -72,6 +75,8 @@ int main(int argc, char** argv) {
         else if ((a == "-o" || a == "--output") && more) output = argv[++i];
         else if (a == "--lang" && more) lang = argv[++i];
         else if (a == "--ref" && more) ref = argv[++i];
+        else if (a == "--instruct" && more) instruct = argv[++i];
+        else if (a == "--instruct-tokens" && more) instruct_tokens = argv[++i];
         else if (a == "--temp" && more) sp.temperature = (float)atof(argv[++i]);
         else if (a == "--top-k" && more) sp.top_k = atoi(argv[++i]);
         else if (a == "--top-p" && more) sp.top_p = (float)atof(argv[++i]);
@@ -110,7 +115,22 @@ int main(int argc, char** argv) {
         ids.push_back(config::TTS_EOS);
         ids.push_back(config::IM_END);
     }
-    if (!ref.empty() && !ids.empty()) {
+    if (!instruct.empty() || !instruct_tokens.empty()) {   // a voice instruction in front of the prompt, with or without a cloned voice
+        std::vector<int32_t> ins;
+        if (!instruct_tokens.empty())
+            for (char* tok = strtok(&instruct_tokens[0], ", "); tok; tok = strtok(nullptr, ", ")) ins.push_back((int32_t)strtol(tok, nullptr, 10));
+        else ins = engine.tokenize(instruct);
+        if (ins.empty()) { fprintf(stderr, "Error: the instruction has no tokens (--instruct needs vocab.json + merges.txt)\n"); return 1; }
+        std::vector<float> spk;
+        if (!ref.empty()) {
+            spk = engine.extract_speaker_embedding(ref);
+            if (spk.empty()) { fprintf(stderr, "[TTSEngine] Failed to extract speaker embedding\n"); return 1; }
+        }
+        printf("Instruction: %zu tokens\n", ins.size());
+        if (!ids.empty()) audio = engine.synthesize_tokens_instruct(ids, ins, spk, lang_of(lang), sp);
+        else if (!instruct_tokens.empty()) { fprintf(stderr, "Error: --instruct-tokens goes with --tokens\n"); return 1; }
+        else audio = engine.synthesize_instruct(prompt, instruct, spk, lang_of(lang), sp);
+    } else if (!ref.empty() && !ids.empty()) {
         const std::vector<float> spk = engine.extract_speaker_embedding(ref);
         if (spk.empty()) { fprintf(stderr, "[TTSEngine] Failed to extract speaker embedding\n"); }
         else audio = engine.synthesize_tokens_clone(ids, spk, lang_of(lang), sp);

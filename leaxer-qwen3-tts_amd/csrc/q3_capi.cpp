@@ -353,6 +353,31 @@ float q3tts_rng_uniform(uint64_t seed, uint32_t stream, uint32_t frame, uint32_t
     return (float)(k >> 40) * (1.0f / 16777216.0f);
 }
 
+// [HINT], unpinned (include/q3tts.h): the chat-turn frame of an instruction
+static const int64_t INSTRUCT_HEAD[3] = { 151644, 872, 198 }, INSTRUCT_TAIL[2] = { 151645, 198 };
+int64_t q3tts_frame_instruct_ids(const int32_t* text_ids, int64_t n, int64_t* out, int64_t cap) {
+    if (n < 0 || (n > 0 && !text_ids) || cap < 0 || (cap > 0 && !out)) return -1;
+    const int64_t total = n + 5;
+    for (int64_t i = 0; i < total && i < cap; ++i)
+        out[i] = i < 3 ? INSTRUCT_HEAD[i] : (i < 3 + n ? (int64_t)text_ids[i - 3] : INSTRUCT_TAIL[i - 3 - n]);
+    return total;
+}
+
+int q3tts_build_prompt_instruct_host(q3tts_engine* h, const int64_t* ids, int n_ids, int lang, const float* speaker,
+                                     const int64_t* instruct_ids, int n_instruct,
+                                     float* prompt, int cap_prompt_rows, int* S, float* trailing, int cap_rows, int* n_trailing) {
+    Q3_API_BEGIN(h)
+    if (n_instruct < 0 || (n_instruct > 0 && !instruct_ids)) throw q3::Error("build_prompt_instruct: bad instruction");
+    if (!prompt || !S || cap_prompt_rows < n_instruct + 16) throw q3::Error("build_prompt_instruct: the prompt buffer needs n_instruct + 16 rows");
+    const size_t H = (size_t)h->e->c.hidden;
+    if (n_instruct > 0) h->e->text_project(instruct_ids, n_instruct, prompt);
+    int S0 = 0;
+    h->e->build_prompt(ids, n_ids, lang, speaker, prompt + (size_t)n_instruct * H, &S0, trailing, cap_rows, n_trailing);
+    *S = n_instruct + S0;
+    return 0;
+    Q3_API_END(h)
+}
+
 int q3tts_build_prompt_host(q3tts_engine* h, const int64_t* ids, int n_ids, int lang, const float* speaker,
                             float* prompt, int* S, float* trailing, int cap_rows, int* n_trailing) {
     Q3_API_BEGIN(h) h->e->build_prompt(ids, n_ids, lang, speaker, prompt, S, trailing, cap_rows, n_trailing); return 0; Q3_API_END(h)
@@ -423,10 +448,81 @@ int q3tts_synthesize_clone_batch_host(q3tts_engine* h, int n_utt, const int64_t*
     return q3tts_synthesize_schedule_host(h, n_utt, ids, offsets, lang, speakers, p, nullptr, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out);
 }
 
+// Prompt rows of every utterance of a job, assembled before the first step in one projection pass (Engine::build_prompts: one utterance
+// at a time it is a handful of small synchronous device round trips each).  Utterance u's prompt starts at row prep[u].poff of `prompts`;
+// with an instruction (include/q3tts.h: q3tts_synthesize_instruct_host) its text_project rows come first, all instructions of the job
+// through one further projection pass.
+struct Prep { int S = 0, nt = 0; size_t poff = 0, toff = 0; };
+static void assemble_prompts(Engine& e, int n_utt, const int64_t* ids, const int32_t* offsets, int lang, const float* const* speakers,
+                             const int64_t* instruct_ids, const int32_t* instruct_offsets,
+                             std::vector<Prep>& prep, std::vector<float>& prompts, std::vector<float>& trailing) {
+    const size_t H = (size_t)e.c.hidden;
+    prep.assign((size_t)n_utt, Prep());
+    if (instruct_ids && !instruct_offsets) throw q3::Error("synthesize: instruct_ids without instruct_offsets");
+    auto n_ins = [&](int u) { return instruct_ids ? (int)(instruct_offsets[u + 1] - instruct_offsets[u]) : 0; };
+    size_t prow = 0, trow = 0, n_ins_all = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        if (n_ins(u) < 0) throw q3::Error("synthesize: instruct_offsets must not decrease");
+        prep[(size_t)u].poff = prow; prep[(size_t)u].toff = trow;
+        prow += 16 + (size_t)n_ins(u); n_ins_all += (size_t)n_ins(u);
+        trow += (size_t)std::max(1, offsets[u + 1] - offsets[u] - 3);   // trailing rows: text tokens minus the first, plus tts_eos
+    }
+    trailing.resize(trow * H);
+    std::vector<size_t> toffs((size_t)n_utt);
+    std::vector<int> Ss((size_t)n_utt), nts((size_t)n_utt);
+    for (int u = 0; u < n_utt; ++u) toffs[(size_t)u] = prep[(size_t)u].toff;
+    if (n_ins_all == 0) {
+        prompts.resize(prow * H);
+        e.build_prompts(ids, offsets, n_utt, lang, speakers, prompts.data(), Ss.data(), trailing.data(), toffs.data(), nts.data());
+    } else {
+        std::vector<float> base((size_t)n_utt * 16 * H), ins(n_ins_all * H);
+        e.build_prompts(ids, offsets, n_utt, lang, speakers, base.data(), Ss.data(), trailing.data(), toffs.data(), nts.data());
+        const int64_t i0 = instruct_offsets[0];
+        if (n_ins_all > (size_t)e.max_ctx * (size_t)n_utt) throw q3::Error("synthesize: instructions longer than max_ctx");
+        e.text_project(instruct_ids + i0, (int)n_ins_all, ins.data());
+        prompts.resize(prow * H);
+        for (int u = 0; u < n_utt; ++u) {
+            float* dst = prompts.data() + prep[(size_t)u].poff * H;
+            const size_t ni = (size_t)n_ins(u);
+            if (ni > 0) memcpy(dst, ins.data() + (size_t)(instruct_offsets[u] - i0) * H, ni * H * sizeof(float));
+            memcpy(dst + ni * H, base.data() + (size_t)u * 16 * H, (size_t)Ss[(size_t)u] * H * sizeof(float));
+            Ss[(size_t)u] += (int)ni;
+        }
+    }
+    for (int u = 0; u < n_utt; ++u) { prep[(size_t)u].S = Ss[(size_t)u]; prep[(size_t)u].nt = nts[(size_t)u]; }
+}
+
+static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                  const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                  float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                                  int chunk_frames, q3tts_audio_cb cb, void* user, const int64_t* instruct_ids, const int32_t* instruct_offsets);
+static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                    const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                    float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
+                                    int64_t* codes_out, const int64_t* instruct_ids, const int32_t* instruct_offsets);
+
 int q3tts_synthesize_schedule_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                    const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                    float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
                                    int64_t* codes_out) {
+    return synthesize_schedule_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out, nullptr, nullptr);
+}
+
+int q3tts_synthesize_instruct_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                                   int chunk_frames, q3tts_audio_cb cb, void* user,
+                                   const int64_t* instruct_ids, const int32_t* instruct_offsets) {
+    if (!cb) return synthesize_schedule_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
+                                             instruct_ids, instruct_offsets);
+    return synthesize_stream_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
+                                  chunk_frames, cb, user, instruct_ids, instruct_offsets);
+}
+
+static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                    const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                    float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
+                                    int64_t* codes_out, const int64_t* instruct_ids, const int32_t* instruct_offsets) {
     Q3_API_BEGIN(h)
     Engine& e = *h->e;
     const int H = e.c.hidden, G = e.c.n_groups, B = e.B;
@@ -438,24 +534,9 @@ int q3tts_synthesize_schedule_host(q3tts_engine* h, int n_utt, const int64_t* id
     const int row_frames = std::max(1, std::min(p->max_new_tokens, e.max_frames_cap));
     e.codec_async_prepare(row_frames, n_utt);
     std::vector<int32_t> got_frames((size_t)n_utt, 0);
-    // Prompt rows of every utterance are assembled before the first step, all in one projection pass (Engine::build_prompts): one
-    // utterance at a time it is a handful of small synchronous device round trips each.
-    struct Prep { int S = 0, nt = 0; size_t poff = 0, toff = 0; };
-    std::vector<Prep> prep((size_t)n_utt);
+    std::vector<Prep> prep;
     std::vector<float> prompts, trailing;
-    {
-        size_t prow = 0, trow = 0;
-        for (int u = 0; u < n_utt; ++u) {
-            prep[(size_t)u].poff = prow; prep[(size_t)u].toff = trow;
-            prow += 16; trow += (size_t)std::max(1, offsets[u + 1] - offsets[u] - 3);   // trailing rows: text tokens minus the first, plus tts_eos
-        }
-        prompts.resize(prow * H); trailing.resize(trow * H);
-        std::vector<size_t> toffs((size_t)n_utt);
-        std::vector<int> Ss((size_t)n_utt), nts((size_t)n_utt);
-        for (int u = 0; u < n_utt; ++u) toffs[(size_t)u] = prep[(size_t)u].toff;
-        e.build_prompts(ids, offsets, n_utt, lang, speakers, prompts.data(), Ss.data(), trailing.data(), toffs.data(), nts.data());
-        for (int u = 0; u < n_utt; ++u) { prep[(size_t)u].S = Ss[(size_t)u]; prep[(size_t)u].nt = nts[(size_t)u]; }
-    }
+    assemble_prompts(e, n_utt, ids, offsets, lang, speakers, instruct_ids, instruct_offsets, prep, prompts, trailing);
     // KV pages.  With EOS suppressed every length is known: an utterance is admitted when the pool holds prompt + cap and never waits again.
     // Otherwise a slot owns what its context has reached plus the coming look (on-demand growth), so utterances that end early never hold
     // the pages of their cap; when the pool runs dry the YOUNGEST live utterance is preempted — its pages go back, it returns to the head
@@ -586,6 +667,13 @@ int q3tts_synthesize_stream_host(q3tts_engine* h, int n_utt, const int64_t* ids,
                                  const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                  float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                  int chunk_frames, q3tts_audio_cb cb, void* user) {
+    return synthesize_stream_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
+                                  chunk_frames, cb, user, nullptr, nullptr);
+}
+static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                  const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                  float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                                  int chunk_frames, q3tts_audio_cb cb, void* user, const int64_t* instruct_ids, const int32_t* instruct_offsets) {
     Q3_API_BEGIN(h)
     Engine& e = *h->e;
     const int H = e.c.hidden, G = e.c.n_groups, B = e.B;
@@ -596,22 +684,9 @@ int q3tts_synthesize_stream_host(q3tts_engine* h, int n_utt, const int64_t* ids,
     if (pcm_cap < 0) throw q3::Error("synthesize: negative pcm_cap");
     (void)Engine::checked_penalty(*p);
     for (int b = 0; b < B; ++b) e.slot_release(b);
-    struct Prep { int S = 0, nt = 0; size_t poff = 0, toff = 0; };
-    std::vector<Prep> prep((size_t)n_utt);
+    std::vector<Prep> prep;
     std::vector<float> prompts, trailing;
-    {
-        size_t prow = 0, trow = 0;
-        for (int u = 0; u < n_utt; ++u) {
-            prep[(size_t)u].poff = prow; prep[(size_t)u].toff = trow;
-            prow += 16; trow += (size_t)std::max(1, offsets[u + 1] - offsets[u] - 3);
-        }
-        prompts.resize(prow * H); trailing.resize(trow * H);
-        std::vector<size_t> toffs((size_t)n_utt);
-        std::vector<int> Ss((size_t)n_utt), nts((size_t)n_utt);
-        for (int u = 0; u < n_utt; ++u) toffs[(size_t)u] = prep[(size_t)u].toff;
-        e.build_prompts(ids, offsets, n_utt, lang, speakers, prompts.data(), Ss.data(), trailing.data(), toffs.data(), nts.data());
-        for (int u = 0; u < n_utt; ++u) { prep[(size_t)u].S = Ss[(size_t)u]; prep[(size_t)u].nt = nts[(size_t)u]; }
-    }
+    assemble_prompts(e, n_utt, ids, offsets, lang, speakers, instruct_ids, instruct_offsets, prep, prompts, trailing);
     auto cap_of = [&](int u) { return max_new_per_utt ? std::min(std::max(1, (int)max_new_per_utt[u]), p->max_new_tokens) : p->max_new_tokens; };
     std::deque<int> pending;
     for (int u = 0; u < n_utt; ++u) {

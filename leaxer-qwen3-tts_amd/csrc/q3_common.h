@@ -163,6 +163,11 @@ void launch_cp_attn_kvh(const CpAttnOprojArgs& a, int n_new, float* part, hipStr
 bool oproj_kvh_ok(const GemvArgs& a);
 void launch_oproj_kvh(const GemvArgs& a, float* part, hipStream_t s);
 void launch_attn_combine(const AttnArgs& a, hipStream_t s); // partials -> a.out
+// Long-prompt prefill (run_prefill, reference tts_onnx.cpp:615-665, past 16 rows): a chunk of n_new <= 128 rows of ONE slot (nb = 1, slot =
+// slot_offset) at the host-known position pos_scalar.  Two launches: the rows' K / V appended (k_attn's prologue, same rounding point),
+// then causal attention of every row over cache tokens [0, pos_scalar + its index] read from the cache alone.  n_splits = 1: normalised
+// rows (out) and / or planes (oh, ol)
+void launch_attn_prefill(const AttnArgs& a, hipStream_t s);
 
 // Skinny-M bf16-MFMA GEMM (q3_gemm_kernels.hip): activations as (hi, lo) bf16 planes, fp32 accumulate
 struct GemmArgs {

@@ -1887,6 +1887,240 @@ void launch_attn_combine(const AttnArgs& a, hipStream_t s) {
 }
 
 // ================================================================================================
+// Long-prompt prefill attention (run_prefill over a prompt of more than ATT_MAX_NEW rows, reference src/tts_onnx.cpp:615-665): one chunk
+// of n_new <= 128 rows of ONE slot, starting at cache position base = pos_scalar.  Two launches per layer.
+//   k_prefill_append — workgroup (one wave) = (kv head, new row j): k_attn's prologue for a key (split-K slabs summed in slab order,
+//     RMSNorm with k_norm, RoPE at base + j, bf16 rounding under kv_bf16 / kv_round) and the K / V rows stored at position base + j.
+//   k_attn_prefill — workgroup = (kv head, tile of TQ query rows): the tile's q heads through RMSNorm + RoPE into LDS, then the cache
+//     pages [0, (base + last row of the tile) / 64] one at a time: K page staged in LDS (row stride D + 1: lane = token reads its row
+//     without a bank conflict), lane t scores token t against the wave's R rows x G heads (q read as LDS broadcasts), causal mask by a
+//     select (never-written rows may hold NaN), online softmax per (row, head) across the wave, probabilities through wave-private LDS,
+//     P.V with lane = output dim and V read from the cache (L2: every workgroup of a kv head walks the same pages).  Pages behind the
+//     tile's last position are never touched.  fp32 throughout; the cache reader is the only place the storage format shows, so the
+//     16-bit cache and fp32 storage of the rounded rows give the same bits.  Output: normalised fp32 rows and / or (hi, lo) planes.
+// ================================================================================================
+template <int D, bool KVB>
+__global__ __launch_bounds__(64) void k_prefill_append(const int* ppage_table, const float* pqkv, const float* pcos, const float* psin, AttnArgs a) {
+    constexpr int HALF = D / 2;
+    const int kvh = blockIdx.x, j = blockIdx.y, lane = threadIdx.x;
+    const int p = a.pos_scalar + j;
+    const int pshift = a.page_shift, page_tokens = 1 << pshift;
+    const int page = ppage_table[(size_t)a.slot_offset * a.pages_per_slot + (p >> pshift)];
+    const size_t off = ((((size_t)page * a.n_layers + a.layer) * a.nkv + kvh) * page_tokens + (p & (page_tokens - 1))) * D;
+    const int hl = lane < HALF ? lane : 0;
+    const float* rowp = pqkv + (size_t)j * a.ld_qkv;
+    const float* ks = rowp + (a.nq + kvh) * D;
+    const float* vs = rowp + (a.nq + a.nkv + kvh) * D;
+    float x0 = ks[hl], x1 = ks[hl + HALF], v0 = vs[hl], v1 = vs[hl + HALF];
+    for (int sb = 1; sb < a.qkv_nslab; ++sb) {
+        const size_t so = (size_t)sb * a.qkv_slab_stride;
+        x0 += ks[so + hl]; x1 += ks[so + hl + HALF]; v0 += vs[so + hl]; v1 += vs[so + hl + HALF];
+    }
+    x0 = lane < HALF ? x0 : 0.f; x1 = lane < HALF ? x1 : 0.f;
+    if (a.k_norm != nullptr) {
+        const float ss = wave_sum(x0 * x0 + x1 * x1);
+        const float rr = 1.0f / sqrtf(ss / (float)D + a.eps);
+        x0 = a.k_norm[hl] * (x0 * rr); x1 = a.k_norm[hl + HALF] * (x1 * rr);
+    }
+    const float cs = pcos[(size_t)p * HALF + hl], sn = psin[(size_t)p * HALF + hl];
+    float y0 = x0 * cs + (-x1) * sn;
+    float y1 = x1 * cs + x0 * sn;
+    if (KVB || a.kv_round) { y0 = bf16_round_f(y0); y1 = bf16_round_f(y1); v0 = bf16_round_f(v0); v1 = bf16_round_f(v1); }
+    if (lane < HALF) {
+        if (KVB) {
+            uint16_t* kc16 = reinterpret_cast<uint16_t*>(a.kcache); uint16_t* vc16 = reinterpret_cast<uint16_t*>(a.vcache);
+            kc16[off + lane] = (uint16_t)(__float_as_uint(y0) >> 16); kc16[off + lane + HALF] = (uint16_t)(__float_as_uint(y1) >> 16);
+            vc16[off + lane] = (uint16_t)(__float_as_uint(v0) >> 16); vc16[off + lane + HALF] = (uint16_t)(__float_as_uint(v1) >> 16);
+        } else {
+            a.kcache[off + lane] = y0; a.kcache[off + lane + HALF] = y1;
+            a.vcache[off + lane] = v0; a.vcache[off + lane + HALF] = v1;
+        }
+    }
+}
+
+template <int D, int G, bool KVB>
+__global__ __launch_bounds__(256) void k_attn_prefill(const int* ppage_table, const float* pqkv, const float* pkcache, const float* pvcache,
+                                                       const float* pcos, const float* psin, AttnArgs a) {
+    constexpr int HALF = D / 2;
+    constexpr int TQ = G <= 2 ? 16 : 8;   // query rows per workgroup
+    constexpr int R = TQ / 4;             // rows per wave
+    constexpr int NP = R * G;             // (row, head) pairs per wave
+    constexpr int KS = D + 1;             // LDS row stride of the K page
+    constexpr int NE = D >= 64 ? D / 64 : 1;   // output dims per lane
+    __shared__ __attribute__((aligned(16))) float q_s[TQ * G][D];
+    __shared__ float k_s[64 * KS];
+    __shared__ __attribute__((aligned(16))) float p_s[4][NP][64];
+    const int kvh = blockIdx.x, r0 = blockIdx.y * TQ;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = a.nq / a.nkv, base = a.pos_scalar, n_new = a.n_new;
+    const int* pt = ppage_table + (size_t)a.slot_offset * a.pages_per_slot;
+
+    // ---- the tile's query heads: slabs summed in slab order, RMSNorm, RoPE (rows past the chunk and heads past the group repeat the last) ----
+    const int hl = lane < HALF ? lane : 0;
+    for (int v = wave; v < TQ * G; v += 4) {
+        const int r = v / G, h = v % G;
+        const int row = r0 + r < n_new ? r0 + r : n_new - 1, hh = h < grp ? h : grp - 1;
+        const float* src = pqkv + (size_t)row * a.ld_qkv + (kvh * grp + hh) * D;
+        float x0 = src[hl], x1 = src[hl + HALF];
+        for (int sb = 1; sb < a.qkv_nslab; ++sb) {
+            const size_t so = (size_t)sb * a.qkv_slab_stride;
+            x0 += src[so + hl]; x1 += src[so + hl + HALF];
+        }
+        x0 = lane < HALF ? x0 : 0.f; x1 = lane < HALF ? x1 : 0.f;
+        if (a.q_norm != nullptr) {
+            const float ss = wave_sum(x0 * x0 + x1 * x1);
+            const float rr = 1.0f / sqrtf(ss / (float)D + a.eps);
+            x0 = a.q_norm[hl] * (x0 * rr); x1 = a.q_norm[hl + HALF] * (x1 * rr);
+        }
+        const int p = base + row;
+        const float cs = pcos[(size_t)p * HALF + hl], sn = psin[(size_t)p * HALF + hl];
+        if (lane < HALF) {
+            q_s[v][lane] = x0 * cs + (-x1) * sn;
+            q_s[v][lane + HALF] = x1 * cs + x0 * sn;
+        }
+    }
+
+    const int last_row = (r0 + TQ < n_new ? r0 + TQ : n_new) - 1;
+    const int last_pos = base + last_row;
+    const int n_pages = (last_pos >> 6) + 1;
+    float m[NP], l[NP], o[NP][NE];
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        m[q] = -INFINITY; l[q] = 0.f;
+#pragma unroll
+        for (int k = 0; k < NE; ++k) o[q][k] = 0.f;
+    }
+    __syncthreads();   // q_s complete
+    for (int pi = 0; pi < n_pages; ++pi) {
+        // (the barrier behind the scores of page pi - 1 has released k_s; p_s is wave-private)
+        const int page = pt[pi];
+        const size_t pbase = (((size_t)page * a.n_layers + a.layer) * a.nkv + kvh) * 64 * D;
+        if (KVB) {
+            const uint16_t* kc16 = reinterpret_cast<const uint16_t*>(pkcache) + pbase;
+            for (int i = tid; i < 64 * D / 2; i += 256) {
+                const uint32_t u = *reinterpret_cast<const uint32_t*>(kc16 + 2 * i);
+                const int t = (2 * i) / D, e = (2 * i) % D;
+                k_s[t * KS + e] = bf_lo(u); k_s[t * KS + e + 1] = bf_hi(u);
+            }
+        } else {
+            for (int i = tid; i < 64 * D / 4; i += 256) {
+                const float4 k4 = *reinterpret_cast<const float4*>(pkcache + pbase + 4 * i);
+                const int t = (4 * i) / D, e = (4 * i) % D;
+                k_s[t * KS + e] = k4.x; k_s[t * KS + e + 1] = k4.y; k_s[t * KS + e + 2] = k4.z; k_s[t * KS + e + 3] = k4.w;
+            }
+        }
+        __syncthreads();
+        // ---- scores: lane = token pi * 64 + lane ----
+        float sc[NP];
+#pragma unroll
+        for (int q = 0; q < NP; ++q) sc[q] = 0.f;
+        const float* kr = k_s + lane * KS;
+        for (int e = 0; e < D; e += 4) {
+            const float k0 = kr[e], k1 = kr[e + 1], k2 = kr[e + 2], k3 = kr[e + 3];
+#pragma unroll
+            for (int q = 0; q < NP; ++q) {
+                const float4 q4 = *reinterpret_cast<const float4*>(&q_s[wave * NP + q][e]);
+                sc[q] = fmaf(q4.x, k0, sc[q]); sc[q] = fmaf(q4.y, k1, sc[q]); sc[q] = fmaf(q4.z, k2, sc[q]); sc[q] = fmaf(q4.w, k3, sc[q]);
+            }
+        }
+        const int tok = pi * 64 + lane;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            const int pos_q = base + r0 + wave * R + q / G;
+            const bool valid = tok <= (pos_q < last_pos ? pos_q : last_pos);   // causal; never-written rows (possibly NaN) end here
+            const float sv = valid ? sc[q] * a.scale : -INFINITY;
+            const float mn = fmaxf(m[q], wave_max(sv));     // token 0 is valid for every row: finite from the first page on
+            const float corr = __expf(m[q] - mn);           // exp(-inf) = 0 on the first page
+            const float pw = __expf(sv - mn);               // 0 for masked tokens
+            l[q] = l[q] * corr + wave_sum(pw);
+#pragma unroll
+            for (int k = 0; k < NE; ++k) o[q][k] *= corr;
+            m[q] = mn;
+            p_s[wave][q][lane] = pw;
+        }
+        __syncthreads();
+        // ---- P.V: lane = output dims lane + 64 k; only tokens up to the tile's last position (all written) ----
+        const int tmax = last_pos + 1 - pi * 64 < 64 ? last_pos + 1 - pi * 64 : 64;
+        const int ev = lane & (D - 1);
+        for (int t0 = 0; t0 < tmax; t0 += 4) {
+            float vv[4][NE];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const bool in = t0 + u < tmax;
+                const size_t vo = pbase + (size_t)(in ? t0 + u : t0) * D + ev;
+#pragma unroll
+                for (int k = 0; k < NE; ++k) {
+                    const float x = KVB ? bf_lo((uint32_t)(reinterpret_cast<const uint16_t*>(pvcache)[vo + 64 * k])) : pvcache[vo + 64 * k];
+                    vv[u][k] = in ? x : 0.f;
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < NP; ++q) {
+                const float4 p4 = *reinterpret_cast<const float4*>(&p_s[wave][q][t0]);
+#pragma unroll
+                for (int k = 0; k < NE; ++k) {
+                    o[q][k] = fmaf(p4.x, vv[0][k], o[q][k]); o[q][k] = fmaf(p4.y, vv[1][k], o[q][k]);
+                    o[q][k] = fmaf(p4.z, vv[2][k], o[q][k]); o[q][k] = fmaf(p4.w, vv[3][k], o[q][k]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const int row = r0 + wave * R + q / G, h = q % G;
+        if (row >= n_new || h >= grp) continue;
+        const int head = kvh * grp + h;
+#pragma unroll
+        for (int k = 0; k < NE; ++k) {
+            const int e = lane + 64 * k;
+            if (e >= D) continue;
+            const float ov = o[q][k] / l[q];
+            if (a.out) a.out[(size_t)row * a.ld_out + head * D + e] = ov;
+            if (a.oh) {
+                const uint32_t u = __float_as_uint(ov);
+                const bf16_t hi = (bf16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+                const float rem = ov - __uint_as_float((uint32_t)hi << 16);
+                const uint32_t w = __float_as_uint(rem);
+                a.oh[(size_t)row * a.ldp + head * D + e] = hi;
+                a.ol[(size_t)row * a.ldp + head * D + e] = (bf16_t)((w + 0x7FFFu + ((w >> 16) & 1u)) >> 16);
+            }
+        }
+    }
+}
+
+void launch_attn_prefill(const AttnArgs& a, hipStream_t s) {
+    const int grp = a.nkv > 0 ? a.nq / a.nkv : 0;
+    if (grp < 1 || grp > ATT_MAX_GRP || a.nq % a.nkv) throw Error("attn (prefill): unsupported GQA group size");
+    if (a.nb != 1 || a.n_new < 1 || a.n_new > 128) throw Error("attn (prefill): one slot, 1..128 new rows per launch");
+    if (!a.new_from_raw || a.window != 0 || a.pos_dev != nullptr || a.slot_map != nullptr || a.ssq_in != nullptr || a.n_splits != 1 || a.po != nullptr)
+        throw Error("attn (prefill): raw rows at a host-known position, no window, no slot map, no deferred RMSNorm, no split-T partials");
+    if (a.page_shift != 6) throw Error("attn (prefill): 64-token KV pages");
+    if (a.pos_scalar < 0 || a.pos_scalar + a.n_new > (a.pages_per_slot << 6)) throw Error("attn (prefill): rows past the slot's pages");
+    if (a.qkv_nslab < 1 || a.qkv_nslab > 4) throw Error("attn (prefill): 1..4 QKV slabs");
+    if (a.kv_bf16 && a.kv_round) throw Error("attn (prefill): kv_bf16 and kv_round exclude each other");
+    if (!a.out && !a.oh) throw Error("attn (prefill): no output");
+    if (!a.rope_cos || !a.rope_sin || !a.page_table) throw Error("attn (prefill): null table");
+    const int G = grp <= 2 ? grp : 4, TQ = G <= 2 ? 16 : 8;
+    const dim3 ga(a.nkv, a.n_new), gb(a.nkv, (a.n_new + TQ - 1) / TQ);
+#define Q3_PF_ARGS a.page_table, a.qkv, (const float*)a.kcache, (const float*)a.vcache, a.rope_cos, a.rope_sin, a
+#define Q3_PF_G(D_, B_) do { \
+        hipLaunchKernelGGL((k_prefill_append<D_, B_>), ga, dim3(64), 0, s, a.page_table, a.qkv, a.rope_cos, a.rope_sin, a); \
+        if (G == 1) hipLaunchKernelGGL((k_attn_prefill<D_, 1, B_>), gb, dim3(256), 0, s, Q3_PF_ARGS); \
+        else if (G == 2) hipLaunchKernelGGL((k_attn_prefill<D_, 2, B_>), gb, dim3(256), 0, s, Q3_PF_ARGS); \
+        else hipLaunchKernelGGL((k_attn_prefill<D_, 4, B_>), gb, dim3(256), 0, s, Q3_PF_ARGS); } while (0)
+#define Q3_PF(D_) do { if (a.kv_bf16) Q3_PF_G(D_, true); else Q3_PF_G(D_, false); } while (0)
+    if (a.d == 128) Q3_PF(128);
+    else if (a.d == 64) Q3_PF(64);
+    else if (a.d == 16) Q3_PF(16);
+    else throw Error("attn (prefill): head_dim must be 16, 64 or 128");
+#undef Q3_PF
+#undef Q3_PF_G
+#undef Q3_PF_ARGS
+    Q3_HIP_CHECK(hipGetLastError());
+}
+
+// ================================================================================================
 // k_cp_attn_oproj — the code predictor's attention AND its output projection in one launch (b = 1).
 // The predictor context is at most 17 tokens, so attention is a few KB of L2-resident K/V per head; what a
 // separate attention launch costs is its dependent-launch slot (~4.6 us of the 2.67 ms step, 75 per frame).

@@ -194,6 +194,7 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
     if (const char* sv = knob("Q3TTS_ATTN_STREAM_ONE")) attn_stream_one = atoi(sv) != 0;
     if (const char* sv = knob("Q3TTS_KVH_OPROJ")) kvh_oproj = atoi(sv) != 0;
     if (const char* sv = knob("Q3TTS_CP_QKV_TABLE")) cp_qkv_table_on = atoi(sv) != 0;
+    if (const char* sv = knob("Q3TTS_PREFILL_CHUNK")) prefill_chunk = std::min(128, std::max(16, atoi(sv)));
     null_stream = getenv("Q3TTS_NULL_STREAM") && getenv("Q3TTS_NULL_STREAM")[0] == '1';
     if (null_stream) { stream = nullptr; flags |= Q3TTS_FLAG_NO_GRAPH; }
     else if (const char* cm = knob("Q3TTS_STREAM_CU_MASK")) {   // experiment aid (tools/overlap_probe.py): this engine's stream on a subset of the CUs;
@@ -244,6 +245,7 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
 
     // ---- workspaces ----
     rows_max = std::max(2 * B, 16);
+    ws_rows = rows_max;
     max_trailing = 1024;
     max_frames_cap = max_ctx;
     const int QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, QKVp = (c.cp_heads + 2 * c.cp_kv_heads) * c.cp_head_dim;
@@ -379,6 +381,7 @@ Engine::~Engine() {
     if (proj_ids_d) (void)hipFree(proj_ids_d);
     if (proj_out_d) (void)hipFree(proj_out_d);
     if (hist_d) (void)hipFree(hist_d);
+    if (long_x_d) (void)hipFree(long_x_d);
     codec_free();
     speaker_free();
     free_packed_weights();
@@ -639,7 +642,7 @@ bool Engine::run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new,
         } else if (!(qkv_in && l == 0)) {
             launch_gemv(qkv_gemv_args(W, l, x, ldx, qkv, M), stream);
         }
-        if (!mfma && nb == 1 && pos_dev == nullptr && slot_map == nullptr && W.n_splits == 1 && W.pages_per_slot == 1 && !W.kv_bf16 && !W.kv_round &&
+        if (!mfma && !chunk_attn && nb == 1 && pos_dev == nullptr && slot_map == nullptr && W.n_splits == 1 && W.pages_per_slot == 1 && !W.kv_bf16 && !W.kv_round &&
             !(flags & Q3TTS_FLAG_NO_FUSED_CP)) {
             // code predictor at b = 1: attention + o_proj + residual in one launch (identity page table: slot s owns page s).  The gate is
             // stack-agnostic — a talker with max_ctx <= 64 matches it too — and the fused kernel reads and writes an fp32 cache without
@@ -694,11 +697,14 @@ bool Engine::run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new,
                                   W.nq % W.nkv == 0 && grp_w == 2;   // the kernel is built for two query heads per kv head (0.6B and 1.7B talkers)
         if (stream_shape && a.n_splits > 1) { a.stream = 1; a.n_splits = W.n_splits_stream; a.chunk = W.chunk_stream; }
         else if (stream_shape && attn_stream_one && a.n_splits == 1) a.stream = 1;
+        // a chunk of a long prompt: one workgroup owns its query rows over the whole context, no split-T partials
+        if (chunk_attn) { a.stream = 0; a.n_splits = 1; a.chunk = 1 << 30; }
         const bool direct_planes = mfma && a.n_splits == 1;     // one split: the attention kernel normalises and writes the planes itself
         if (direct_planes) { a.out = nullptr; a.po = nullptr; a.pm = nullptr; a.pl = nullptr; a.oh = pl1h; a.ol = pl1l; a.ldp = ldp; }
         const bool direct_rows = !mfma && a.n_splits == 1;      // likewise for the GEMV family: normalised fp32 rows, nothing to combine
         if (direct_rows) { a.po = nullptr; a.pm = nullptr; a.pl = nullptr; }
-        launch_attn(a, stream);
+        if (chunk_attn) launch_attn_prefill(a, stream);
+        else launch_attn(a, stream);
         if (mfma) {
             if (!direct_planes) {
                 a.out = nullptr; a.oh = pl1h; a.ol = pl1l; a.ldp = ldp;
@@ -715,16 +721,16 @@ bool Engine::run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new,
             // x += sum(slabs); planes0 = RMSNorm(post_norm)(x)
             if (!seam) launch_finish(x, ldx, slab_d, ks_o, (size_t)M * W.H, W.H, w.post_norm, W.eps, M, W.H, pl0h, pl0l, ldp, nullptr, 0, stream);
             GemmArgs f; // gate and up as split-K slab pairs, SwiGLU applied by the finish kernel
-            f.W = w.gate; f.W2 = w.up; f.xh = pl0h; f.xl = pl0l; f.ldx = ldp; f.out = gu_slab_d; f.out2 = gu_slab_d + (size_t)4 * rows_max * W.ffn; f.ldo = W.ffn;
+            f.W = w.gate; f.W2 = w.up; f.xh = pl0h; f.xl = pl0l; f.ldx = ldp; f.out = gu_slab_d; f.out2 = gu_slab_d + (size_t)4 * ws_rows * W.ffn; f.ldo = W.ffn;
             f.M = M; f.N = W.ffn; f.K = W.H; f.epi = EPI_SLAB2; f.nt = W.nt;
             const int ks_gu = seam ? seam_gu_ksplit(W.H) : ks_q;
-            f.out2 = gu_slab_d + (size_t)ks_gu * rows_max * W.ffn;
+            f.out2 = gu_slab_d + (size_t)ks_gu * ws_rows * W.ffn;
             if (seam) {   // planes1 = SwiGLU of the slab sums scaled by 1 / rms(x) (from ssq_a)
                 f.seam = 2; f.seam_gen = seam_gen_d; f.seam_spin = seam_spin; f.seam_cnt = seam_counters(W.ffn / 64); f.oh = pl1h; f.ol = pl1l; f.ldp = ldp;
                 f.ssq_in = ssq_a_d; f.ssq_in_nt = NTH; f.seps = W.eps;
             }
             launch_gemm2(f, ks_gu, 4, stream);
-            if (!seam) launch_finish_swiglu(gu_slab_d, gu_slab_d + (size_t)ks_gu * rows_max * W.ffn, ks_q, (size_t)M * W.ffn, M, W.ffn, pl1h, pl1l, ldp, stream);
+            if (!seam) launch_finish_swiglu(gu_slab_d, gu_slab_d + (size_t)ks_gu * ws_rows * W.ffn, ks_q, (size_t)M * W.ffn, M, W.ffn, pl1h, pl1l, ldp, stream);
             GemmArgs d;
             d.W = w.down; d.xh = pl1h; d.xl = pl1l; d.ldx = ldp; d.out = slab_d; d.ldo = W.H; d.M = M; d.N = W.H; d.K = W.ffn; d.epi = EPI_SLAB; d.nt = W.nt;
             if (seam && l + 1 < W.L) {   // x += sum(slabs); planes0 = gamma(next input norm) * x; ssq_b for the next layer's attention
@@ -865,6 +871,7 @@ void Engine::cp_embed(int64_t id, int step, float* out) {
 // run_prefill's device work for one slot whose S prompt rows sit in xp: layers, final norm + codec head on every row (logits_p [S][V],
 // normalised rows hn [S][H]), the fused path armed with the last row, position = S.  Shared by the host and the device-pointer entry.
 void Engine::prefill_rows_in_xp(int slot, int S) {
+    if (S < 1 || S > 16) throw Error("prefill_rows_in_xp: 1..16 rows (longer prompts: prefill_rows_long)");
     const int H = c.hidden, V = c.vocab;
     const bool pr = run_layers(talker, xp, H, 1, S, slot, nullptr, 0, talker_norm, c.rms_eps, hn, H);
     // final norm + codec head on every row; normalised rows kept for last_hidden
@@ -878,11 +885,86 @@ void Engine::prefill_rows_in_xp(int slot, int S) {
     Q3_HIP_CHECK(hipMemcpyAsync(talker_pos_d + slot, &pos, sizeof(int32_t), hipMemcpyHostToDevice, stream));
 }
 
+float* Engine::long_rows(int S) {
+    if ((size_t)S > long_x_rows) {
+        sync();
+        if (long_x_d) (void)hipFree(long_x_d);
+        long_x_d = nullptr; long_x_rows = 0;
+        const size_t rows = std::min((size_t)max_ctx, std::max((size_t)S, (size_t)256));
+        Q3_HIP_CHECK(hipMalloc((void**)&long_x_d, rows * c.hidden * sizeof(float)));
+        long_x_rows = rows;
+    }
+    return long_x_d;
+}
+
+void Engine::long_ws_swap() {
+    std::swap(qkv, lws.qkv); std::swap(attn, lws.attn); std::swap(act, lws.act); std::swap(slab_d, lws.slab); std::swap(gu_slab_d, lws.gu_slab);
+    std::swap(qkv_slab_d, lws.qkv_slab); std::swap(pl0h, lws.p0h); std::swap(pl0l, lws.p0l); std::swap(pl1h, lws.p1h); std::swap(pl1l, lws.p1l);
+    std::swap(ws_rows, lws.rows);
+}
+
+// run_prefill (tts_onnx.cpp:615-665) for a prompt of more than 16 rows: see q3_engine.h.  A chunk of >= mfma_min_rows rows on
+// 128-multiple dims streams the weights once through the slab GEMMs; shorter chunks and other dims take the GEMV family, as run_layers
+// decides for any pass.  Never under the split-K seam (seam_step is false outside the decode step).
+void Engine::prefill_rows_long(int slot, float* x, int S, float* logits_host) {
+    const int H = c.hidden, V = c.vocab, CH = 128;
+    if (slot < 0 || slot >= B) throw Error("slot out of range");
+    if (S < 1 || S > max_ctx) throw Error("prefill length must be 1..max_ctx rows");
+    if (seam_step) throw Error("prefill_rows_long: not inside a decode step");
+    if (lws.rows == 0) {   // first long prefill: the 128-row workspace (sizes as the constructor's, rows_max -> 128)
+        const int QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim;
+        auto fm = [&](size_t n) { return (float*)dmalloc(n * sizeof(float)); };
+        lws.qkv = fm((size_t)CH * QKV); lws.attn = fm((size_t)CH * AO); lws.act = fm((size_t)CH * c.ffn);
+        lws.slab = fm((size_t)16 * CH * H); lws.qkv_slab = fm((size_t)4 * CH * QKV); lws.gu_slab = fm((size_t)2 * 8 * CH * c.ffn);
+        lws.hn = fm((size_t)CH * H); lws.logits = fm((size_t)CH * V);
+        lws.p0h = (bf16_t*)dmalloc((size_t)CH * ldp * 2); lws.p0l = (bf16_t*)dmalloc((size_t)CH * ldp * 2);
+        lws.p1h = (bf16_t*)dmalloc((size_t)CH * ldp * 2); lws.p1l = (bf16_t*)dmalloc((size_t)CH * ldp * 2);
+        lws.rows = CH;
+    }
+    struct Scope { Engine& e; explicit Scope(Engine& en) : e(en) { e.long_ws_swap(); e.chunk_attn = true; } ~Scope() { e.chunk_attn = false; e.long_ws_swap(); } } scope(*this);
+    float* const hnw = lws.hn; float* const lgw = lws.logits;   // not swapped: the chunk's normalised rows and logits
+    const float* last_lg = nullptr;
+    int n_last = 0;
+    for (int base = 0; base < S; base += prefill_chunk) {
+        const int n = std::min(prefill_chunk, S - base);
+        const bool last = base + n == S;
+        float* xc = x + (size_t)base * H;
+        const bool pr = run_layers(talker, xc, H, 1, n, slot, nullptr, base, talker_norm, c.rms_eps, hnw, H);
+        if (logits_host) {   // every row through the final norm + codec head
+            head_proj(codec_head, xc, H, talker_norm, c.rms_eps, hnw, H, lgw, V, n, V, H, true, pr);
+            Q3_HIP_CHECK(hipMemcpyAsync(logits_host + (size_t)base * V, lgw, (size_t)n * V * sizeof(float), hipMemcpyDeviceToHost, stream));
+            last_lg = lgw + (size_t)(n - 1) * V;
+        } else if (last) {   // the last row alone (all the reference consumes, :797-798)
+            head_proj(codec_head, xc + (size_t)(n - 1) * H, H, talker_norm, c.rms_eps, hnw + (size_t)(n - 1) * H, H, lgw, V, 1, V, H, true, pr, n - 1, 1);
+            last_lg = lgw;
+        }
+        n_last = n;
+    }
+    long_last_logits = last_lg; long_last_hidden = hnw + (size_t)(n_last - 1) * H;
+    launch_copy_rows(long_last_logits, V, logits_t + (size_t)slot * V, V, 1, V, stream);
+    launch_copy_rows(long_last_hidden, H, x_cp + (size_t)slot * 2 * H, H, 1, H, stream);
+    st_h[slot].prompt_len = S;
+    st_h[slot].n_frames = 0;
+    const int32_t pos = S;
+    Q3_HIP_CHECK(hipMemcpyAsync(talker_pos_d + slot, &pos, sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    sync();   // `pos` and the caller's logits buffer are read by the copies above
+}
+
 void Engine::talker_prefill(int slot, const float* embeds, int S, float* logits, float* last_hidden) {
     if (!finalized) throw Error("weights not finalized");
     if (slot < 0 || slot >= B) throw Error("slot out of range");
-    if (S < 1 || S > 16) throw Error("prefill length must be 1..16 rows");
+    if (S < 1 || S > max_ctx) throw Error("prefill length must be 1..max_ctx rows");
+    if (!embeds) throw Error("talker_prefill: null input");
     const int H = c.hidden, V = c.vocab;
+    if (S > 16) {   // long prompt: chunks of up to 128 rows; short ones keep their launches
+        float* x = long_rows(S);
+        kv_reserve(slot, S, false);
+        Q3_HIP_CHECK(hipMemcpyAsync(x, embeds, (size_t)S * H * sizeof(float), hipMemcpyHostToDevice, stream));
+        prefill_rows_long(slot, x, S, logits);
+        if (last_hidden) Q3_HIP_CHECK(hipMemcpyAsync(last_hidden, long_last_hidden, (size_t)H * sizeof(float), hipMemcpyDeviceToHost, stream));
+        sync();
+        return;
+    }
     kv_reserve(slot, S, false);
     Q3_HIP_CHECK(hipMemcpyAsync(xp, embeds, (size_t)S * H * sizeof(float), hipMemcpyHostToDevice, stream));
     prefill_rows_in_xp(slot, S);
@@ -947,7 +1029,7 @@ void Engine::dev_scratch(int nb) {
 void Engine::talker_prefill_dev(const float* embeds, int nb, int S, const int32_t* lens, float* logits_last, float* last_hidden) {
     if (!finalized) throw Error("weights not finalized");
     dev_scratch(nb);
-    if (S < 1 || S > 16) throw Error("prefill length must be 1..16 rows");
+    if (S < 1 || S > max_ctx) throw Error("prefill length must be 1..max_ctx rows");
     if (!embeds) throw Error("talker_prefill_dev: null input");
     const int H = c.hidden, V = c.vocab;
     for (int b = 0; b < nb; ++b) if (lens && (lens[b] < 1 || lens[b] > S)) throw Error("talker_prefill_dev: lens[b] must be 1..S");
@@ -956,10 +1038,19 @@ void Engine::talker_prefill_dev(const float* embeds, int nb, int S, const int32_
     std::vector<int32_t> pos_h;
     int b0 = 0;
     while (b0 < nb) {
-        const int L = len_of(b0), cap = mfma_ok ? std::max(1, std::min(std::min(rows_max, 128) / L, 128)) : 1;
+        const int L = len_of(b0), cap = mfma_ok && L <= 16 ? std::max(1, std::min(std::min(rows_max, 128) / L, 128)) : 1;
         int g = 1;
         while (b0 + g < nb && g < cap && len_of(b0 + g) == L) ++g;
         for (int k = 0; k < g; ++k) kv_reserve(b0 + k, L, false);
+        if (L > 16) {   // a long prompt: one slot at a time through the chunked path
+            float* x = long_rows(L);
+            Q3_HIP_CHECK(hipMemcpyAsync(x, embeds + (size_t)b0 * S * H, (size_t)L * H * sizeof(float), hipMemcpyDeviceToDevice, stream));
+            prefill_rows_long(b0, x, L, nullptr);
+            if (logits_last) launch_copy_rows(long_last_logits, V, logits_last + (size_t)b0 * V, V, 1, V, stream);
+            if (last_hidden) launch_copy_rows(long_last_hidden, H, last_hidden + (size_t)b0 * H, H, 1, H, stream);
+            b0 += 1;
+            continue;
+        }
         if (g == 1 || g * L < mfma_min_rows) {
             for (int k = 0; k < g; ++k) {
                 const int slot = b0 + k;
@@ -1346,7 +1437,7 @@ void Engine::stage_profile(int n_steps, double* out) {
 // over the weights), HIP events on the engine's stream around each pass.  Slots 0..nb-1 must be free; they are released again afterwards.
 void Engine::prefill_profile(int nb, int S, int reps, double* ms_per_pass) {
     if (!finalized) throw Error("weights not finalized");
-    if (nb < 1 || nb > B || S < 1 || S > 16 || reps < 1) throw Error("prefill_profile: bad shape");
+    if (nb < 1 || nb > B || S < 1 || (S > 16 && (nb != 1 || S > max_ctx)) || reps < 1) throw Error("prefill_profile: bad shape (more than 16 rows: one slot, up to max_ctx)");
     for (int b = 0; b < nb; ++b) if (st_h[b].active) throw Error("prefill_profile: slots in use");
     float* emb = nullptr;
     const size_t n = (size_t)nb * S * c.hidden;
@@ -1425,7 +1516,7 @@ void Engine::slots_begin(const SlotInit* in, int n, const q3tts_sampling& p, uin
     for (int i = 0; i < n; ++i) {
         if (in[i].slot < 0 || in[i].slot >= B) throw Error("slot out of range");
         if (in[i].n_trailing < 0 || in[i].n_trailing > max_trailing) throw Error("too many trailing text rows");
-        if (in[i].S < 1 || in[i].S > 16) throw Error("prefill length must be 1..16 rows");
+        if (in[i].S < 1 || in[i].S > max_ctx) throw Error("prefill length must be 1..max_ctx rows");
         if (p.max_new_tokens < 1 || in[i].S + p.max_new_tokens > max_ctx) throw Error("prompt + max_new_tokens exceeds max_ctx");
     }
     {   // KV pages for the prompt and every frame the slot may generate, all or nothing: nothing is armed if the pool cannot hold the set
@@ -1451,7 +1542,8 @@ void Engine::slots_begin(const SlotInit* in, int n, const q3tts_sampling& p, uin
         // a group: entries with the same S, at most rows_max / S of them (and <= 128 rows); consecutive slot ids write their results in
         // place, scattered ones (the scheduler re-arming whatever finished) go through a slot map and a scatter of the head's rows
         const bool mfma_ok = H % 128 == 0 && (c.n_heads * c.head_dim) % 128 == 0 && c.ffn % 128 == 0 && H <= 4096;   // run_layers' MFMA condition
-        const int S = in[i0].S, cap = mfma_ok ? std::max(1, std::min(std::min(rows_max, 128) / S, 128)) : 1;
+        // (a prompt of more than 16 rows is prefilled on its own, in chunks: talker_prefill's long path)
+        const int S = in[i0].S, cap = mfma_ok && S <= 16 ? std::max(1, std::min(std::min(rows_max, 128) / S, 128)) : 1;
         int g = 1;
         bool consecutive = true;
         while (i0 + g < n && g < cap && in[i0 + g].S == S) { consecutive = consecutive && in[i0 + g].slot == in[i0].slot + g; ++g; }

@@ -101,6 +101,22 @@ public:
     void cp_embed(int64_t id, int step, float* out);
     void talker_prefill(int slot, const float* embeds, int S, float* logits, float* last_hidden);
     void prefill_rows_in_xp(int slot, int S);   // run_prefill's device work for the S rows in xp (shared by the host and the device-pointer entry)
+    // ---- long prompts (S > 16: an instruction or any other long prefix in front of the reference's 8-10 rows) ----
+    // The prompt is walked in chunks of prefill_chunk <= 128 rows: run_layers(nb = 1, n_new = chunk, pos_scalar = base) with
+    // launch_attn_prefill in place of k_attn, in a 128-row workspace of its own (allocated by the first long prefill, freed with the
+    // engine; rows_max and every short-prompt launch stay as they are).  x: the S prompt rows on the device, overwritten.  logits_host
+    // non-null: the codec head runs on every row and the S rows land there; otherwise on the last row only.  Arms the slot like
+    // prefill_rows_in_xp and leaves the last row's logits / normalised hidden row at long_last_logits / long_last_hidden.
+    void prefill_rows_long(int slot, float* x, int S, float* logits_host);
+    float* long_rows(int S);                    // device staging for S prompt rows (grow-only)
+    struct LongWs { float *qkv = nullptr, *attn = nullptr, *act = nullptr, *slab = nullptr, *gu_slab = nullptr, *qkv_slab = nullptr, *hn = nullptr, *logits = nullptr;
+                    bf16_t *p0h = nullptr, *p0l = nullptr, *p1h = nullptr, *p1l = nullptr; int rows = 0; } lws;
+    void long_ws_swap();                        // exchanges run_layers' row workspaces (and ws_rows) with lws
+    float* long_x_d = nullptr; size_t long_x_rows = 0;
+    const float *long_last_logits = nullptr, *long_last_hidden = nullptr;
+    int prefill_chunk = 128;                    // Q3TTS_PREFILL_CHUNK (16..128) at engine creation: A/B knob, lets a test cross chunk boundaries at a short prompt
+    bool chunk_attn = false;                    // prefill_rows_long -> run_layers: the attention launch is launch_attn_prefill
+    int ws_rows = 0;                            // rows the slab workspaces in use are laid out for (rows_max; 128 inside a long prefill)
     void talker_decode(int slot, const float* embed, float* logits, float* last_hidden);
     void code_predictor(const float* seq, int n, int step, float* logits);
     void sample(const float* logits, int n, const q3tts_sampling& p, float u, int suppress, int64_t* tok);

@@ -30,6 +30,7 @@ TTSEngine::TTSEngine(const std::string& model_dir) {
     max_batch_ = env_b ? std::max(1, std::atoi(env_b)) : 1;
     const int device = std::getenv("Q3TTS_DEVICE") ? std::atoi(std::getenv("Q3TTS_DEVICE")) : 0;
     const int max_ctx = config::MAX_NEW_TOKENS + 64;
+    max_ctx_ = max_ctx;
     q3tts_config cfg;
     if (model_dir.rfind("synthetic:", 0) == 0 || model_dir.rfind("synthetic-1.7b:", 0) == 0) {   // seeded weights at the 0.6B / 1.7B dims
         const bool big = model_dir[9] == '-';
@@ -150,6 +151,51 @@ std::vector<float> TTSEngine::synthesize_tokens_clone(const std::vector<int64_t>
     int64_t len = 0;
     int32_t frames = 0;
     if (q3tts_synthesize_clone_batch_host(h_, 1, token_ids.data(), offs, lang_index(lang), &spk, &sp, seed_, 0, &ptr, cap, &len, &frames, nullptr) != 0) {
+        std::cerr << "[TTSEngine] Synthesis error: " << q3tts_last_error(h_) << std::endl;
+        return {};
+    }
+    pcm.resize((size_t)std::min<int64_t>(len, cap));
+    return pcm;
+}
+
+std::vector<float> TTSEngine::synthesize_instruct(const std::string& text, const std::string& instruct, Language lang, const SamplingParams& params) {
+    return synthesize_instruct(text, instruct, std::vector<float>(), lang, params);
+}
+
+std::vector<float> TTSEngine::synthesize_instruct(const std::string& text, const std::string& instruct, const std::vector<float>& speaker_embed,
+                                                  Language lang, const SamplingParams& params) {
+    if (!ready_) return {};
+    std::vector<int64_t> ids;
+    if (!wrap_text(text, ids)) return {};
+    return synthesize_tokens_instruct(ids, instruct.empty() ? std::vector<int32_t>() : tokenize(instruct), speaker_embed, lang, params);
+}
+
+std::vector<float> TTSEngine::synthesize_tokens_instruct(const std::vector<int64_t>& token_ids, const std::vector<int32_t>& instruct_text_ids,
+                                                         const std::vector<float>& speaker_embed, Language lang, const SamplingParams& params) {
+    if (!ready_) return {};
+    if (instruct_text_ids.empty()) return synthesize_tokens_clone(token_ids, speaker_embed, lang, params);
+    if (!speaker_embed.empty() && (int)speaker_embed.size() != cfg_hidden_) {
+        std::cerr << "[TTSEngine] Synthesis error: speaker embedding has " << speaker_embed.size() << " values, the model needs " << cfg_hidden_ << std::endl;
+        return {};
+    }
+    std::vector<int64_t> framed((size_t)instruct_text_ids.size() + 5);
+    if (q3tts_frame_instruct_ids(instruct_text_ids.data(), (int64_t)instruct_text_ids.size(), framed.data(), (int64_t)framed.size()) != (int64_t)framed.size()) return {};
+    q3tts_sampling sp{ params.temperature, params.top_p, params.top_k, params.repetition_penalty, params.max_new_tokens };
+    // prompt rows: the instruction + at most 16; the frames that still fit the context behind them
+    sp.max_new_tokens = std::min(sp.max_new_tokens, max_ctx_ - (int)framed.size() - 16);
+    if (sp.max_new_tokens < 1) {
+        std::cerr << "[TTSEngine] Synthesis error: the instruction does not fit the engine's context" << std::endl;
+        return {};
+    }
+    const int32_t offs[2] = { 0, (int32_t)token_ids.size() }, ioffs[2] = { 0, (int32_t)framed.size() };
+    const int64_t cap = (int64_t)sp.max_new_tokens * 1920 + 1920;
+    std::vector<float> pcm((size_t)cap);
+    float* ptr = pcm.data();
+    const float* spk = speaker_embed.empty() ? nullptr : speaker_embed.data();
+    int64_t len = 0;
+    int32_t frames = 0;
+    if (q3tts_synthesize_instruct_host(h_, 1, token_ids.data(), offs, lang_index(lang), &spk, &sp, nullptr, seed_, 0, &ptr, cap, &len, &frames, nullptr,
+                                       0, nullptr, nullptr, framed.data(), ioffs) != 0) {
         std::cerr << "[TTSEngine] Synthesis error: " << q3tts_last_error(h_) << std::endl;
         return {};
     }

@@ -88,6 +88,19 @@ public:
     // clone with a ready speaker embedding (what synthesize_clone does after extract_speaker_embedding)
     std::vector<float> synthesize_tokens_clone(const std::vector<int64_t>& token_ids, const std::vector<float>& speaker_embed,
                                                Language lang = Language::Auto, const SamplingParams& params = SamplingParams());
+    // Voice instructions (the reference README's roadmap row "Voice instructions (--instruct), 1.7B-VoiceDesign: Planned"; these sit
+    // beside the reference's methods).  `instruct` is tokenised with the loaded vocab, framed as a chat turn (q3tts_frame_instruct_ids:
+    // [HINT], unpinned) and its projected rows go in front of the prompt (q3tts_build_prompt_instruct_host).  The speaker_embed overload
+    // combines it with voice clone (--ref + --instruct).  An empty instruction is plain synthesis.  max_new_tokens is lowered where
+    // prompt + max_new_tokens would pass the engine's context.
+    std::vector<float> synthesize_instruct(const std::string& text, const std::string& instruct, Language lang = Language::Auto,
+                                           const SamplingParams& params = SamplingParams());
+    std::vector<float> synthesize_instruct(const std::string& text, const std::string& instruct, const std::vector<float>& speaker_embed,
+                                           Language lang = Language::Auto, const SamplingParams& params = SamplingParams());
+    // the same over ids: token_ids framed as synthesize_tokens takes them, instruct_text_ids the instruction's text ids (framed here)
+    std::vector<float> synthesize_tokens_instruct(const std::vector<int64_t>& token_ids, const std::vector<int32_t>& instruct_text_ids,
+                                                  const std::vector<float>& speaker_embed, Language lang = Language::Auto,
+                                                  const SamplingParams& params = SamplingParams());
     bool has_speaker_encoder() const; // true when the weight file carries the spk.* tensors (reference: speaker_encoder.onnx present)
     bool is_ready() const { return ready_; }
     const std::string& get_error() const { return error_msg_; }
@@ -102,6 +115,7 @@ private:
     int max_batch_ = 1;
     int spk_dim_ = 0;
     int cfg_hidden_ = 1024;
+    int max_ctx_ = 0;
 };
 
 inline int64_t language_to_codec_id(Language lang) { // reference src/tts_onnx.h:230-238

@@ -92,6 +92,7 @@ EXPORTS = [
     "q3tts_codec_decode_chunked_host", "q3tts_slot_codec_decode_range_host", "q3tts_slot_logits_host", "q3tts_step_logits_host",
     "q3tts_sample_hist_host", "q3tts_sample_hist_dev",
     "q3tts_codec_stream_push_batch_host", "q3tts_slots_codec_decode_new_host", "q3tts_synthesize_stream_host",
+    "q3tts_build_prompt_instruct_host", "q3tts_frame_instruct_ids", "q3tts_synthesize_instruct_host",
 ]
 
 # q3tts_audio_cb: int (*)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished)
@@ -139,6 +140,11 @@ def lib():
     L.q3tts_rng_uniform.restype = f32
     L.q3tts_rng_uniform.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
     L.q3tts_build_prompt_host.argtypes = [vp, vp, i32, i32, vp, vp, C.POINTER(i32), vp, i32, C.POINTER(i32)]
+    L.q3tts_build_prompt_instruct_host.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, i32, C.POINTER(i32), vp, i32, C.POINTER(i32)]
+    L.q3tts_frame_instruct_ids.restype = i64
+    L.q3tts_frame_instruct_ids.argtypes = [vp, i64, vp, i64]
+    L.q3tts_synthesize_instruct_host.argtypes = [vp, i32, vp, vp, i32, vp, C.POINTER(Sampling), vp, C.c_uint64, i32, vp, i64, vp, vp, vp,
+                                                 i32, AUDIO_CB, vp, vp, vp]
     L.q3tts_slot_begin.argtypes = [vp, i32, vp, i32, vp, i32, C.POINTER(Sampling), C.c_uint64, C.c_uint32, i32]
     L.q3tts_decode_steps.argtypes = [vp, i32]
     L.q3tts_slot_status.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -315,6 +321,7 @@ class Engine:
         return out
 
     def prefill(self, embeds, slot=0):
+        """run_prefill over embeds [S][hidden], 1 <= S <= max_ctx (more than 16 rows: the chunked long-prompt path)"""
         e = np.ascontiguousarray(embeds, dtype=np.float32)
         S = e.shape[0]
         logits = np.empty((S, self.cfg.vocab), np.float32)
@@ -457,14 +464,21 @@ class Engine:
                                                hist.size, C.byref(tok)))
         return int(tok.value)
 
-    def build_prompt(self, ids, lang=0, speaker=None, cap_rows=1024):
+    def build_prompt(self, ids, lang=0, speaker=None, cap_rows=1024, instruct_ids=None):
+        """build_prompt_embeddings; instruct_ids (already framed: frame_instruct_ids) puts the instruction's projected rows in front"""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
-        prompt = np.zeros((16, self.cfg.hidden), np.float32)
+        ins = None if instruct_ids is None else np.ascontiguousarray(instruct_ids, dtype=np.int64).reshape(-1)
+        prompt = np.zeros((16 + (0 if ins is None else ins.size), self.cfg.hidden), np.float32)
         trailing = np.zeros((cap_rows, self.cfg.hidden), np.float32)
         S, nt = C.c_int(0), C.c_int(0)
         sp = np.ascontiguousarray(speaker, dtype=np.float32) if speaker is not None else None
         if sp is not None and sp.size != self.cfg.hidden:
             raise ValueError("speaker embedding has %d values, the model needs %d" % (sp.size, self.cfg.hidden))
+        if ins is not None:
+            self._ck(self.L.q3tts_build_prompt_instruct_host(self.h, _p(ids), ids.size, lang, _p(sp) if sp is not None else None,
+                                                             _p(ins) if ins.size else None, ins.size, _p(prompt), prompt.shape[0], C.byref(S),
+                                                             _p(trailing), cap_rows, C.byref(nt)))
+            return prompt[: S.value].copy(), trailing[: nt.value].copy()
         self._ck(self.L.q3tts_build_prompt_host(self.h, _p(ids), ids.size, lang, _p(sp) if sp is not None else None,
                                                 _p(prompt), C.byref(S), _p(trailing), cap_rows, C.byref(nt)))
         return prompt[: S.value].copy(), trailing[: nt.value].copy()
@@ -580,7 +594,20 @@ class Engine:
         self._ck(self.L.q3tts_speaker_embed_pcm_batch_host(self.h, n, ptrs, _p(ns) if n else None, _p(rt) if n else None, _p(out) if out.size else None))
         return out
 
-    def synthesize_batch(self, token_lists, sp, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None, max_new_per_utt=None):
+    @staticmethod
+    def _instruct_args(instructs, n):
+        """flat framed ids + offsets [n + 1] of a job's per-utterance instructions (None / empty: none for that utterance)"""
+        if instructs is None:
+            return None, None
+        if len(instructs) != n:
+            raise ValueError("instructs: one entry (framed ids or None) per utterance")
+        rows = [np.zeros(0, np.int64) if t is None else np.asarray(t, np.int64).reshape(-1) for t in instructs]
+        flat = np.ascontiguousarray(np.concatenate(rows + [np.zeros(1, np.int64)]))   # never empty: a valid pointer
+        offs = np.zeros(n + 1, np.int32)
+        offs[1:] = np.cumsum([r.size for r in rows])
+        return flat, offs
+
+    def synthesize_batch(self, token_lists, sp, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None, max_new_per_utt=None, instructs=None):
         """synthesize_tokens (reference src/tts_onnx.cpp:405-436) for a batch of utterances; `speakers` (one
         [hidden] embedding or None per utterance) makes it synthesize_clone (:264-318).  More utterances than slots queue
         (continuous batching); max_new_per_utt caps each utterance separately."""
@@ -606,15 +633,21 @@ class Engine:
         caps = None if max_new_per_utt is None else np.ascontiguousarray(max_new_per_utt, np.int32)
         if caps is not None and caps.shape != (n,):
             raise ValueError("max_new_per_utt: one entry per utterance")
-        self._ck(self.L.q3tts_synthesize_schedule_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
-                                                       seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr),
-                                                       _p(codes) if want_codes else None))
+        ins_flat, ins_offs = self._instruct_args(instructs, n)
+        if ins_flat is not None:   # voice instructions (framed ids per utterance): q3tts_synthesize_instruct_host without a callback
+            self._ck(self.L.q3tts_synthesize_instruct_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
+                                                           seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr),
+                                                           _p(codes) if want_codes else None, 0, AUDIO_CB(), None, _p(ins_flat), _p(ins_offs)))
+        else:
+            self._ck(self.L.q3tts_synthesize_schedule_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
+                                                           seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr),
+                                                           _p(codes) if want_codes else None))
         outs = [pcm[i][: pcm_len[i]] for i in range(n)]
         cl = [codes[i, : nfr[i]] for i in range(n)] if want_codes else None
         return outs, cl, nfr
 
     def synthesize_stream(self, token_lists, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
-                          max_new_per_utt=None):
+                          max_new_per_utt=None, instructs=None):
         """synthesize_batch that delivers audio while it generates (q3tts_synthesize_stream_host): every chunk_frames steps
         on_audio(utt, frame_begin, frame_end, pcm, finished) is called once per utterance with new audio (pcm: a copy); a truthy return
         cancels the job (RuntimeError "cancelled by callback").  Returns what synthesize_batch returns."""
@@ -653,9 +686,15 @@ class Engine:
         vp = C.c_void_p
         self.L.q3tts_synthesize_stream_host.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.POINTER(Sampling), vp, C.c_uint64, C.c_int, vp, C.c_int64, vp, vp, vp,
                                                         C.c_int, AUDIO_CB, vp]
-        rc = self.L.q3tts_synthesize_stream_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
-                                                 seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr),
-                                                 _p(codes) if want_codes else None, int(chunk_frames), cb, None)
+        ins_flat, ins_offs = self._instruct_args(instructs, n)
+        if ins_flat is not None:
+            rc = self.L.q3tts_synthesize_instruct_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
+                                                       seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr),
+                                                       _p(codes) if want_codes else None, int(chunk_frames), cb, None, _p(ins_flat), _p(ins_offs))
+        else:
+            rc = self.L.q3tts_synthesize_stream_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
+                                                     seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr),
+                                                     _p(codes) if want_codes else None, int(chunk_frames), cb, None)
         if raised:
             raise raised[0]
         self._ck(rc)
@@ -851,6 +890,19 @@ class Tokenizer:
             self.close()
         except Exception:
             pass
+
+
+def frame_instruct_ids(text_ids):
+    """[HINT], unpinned (include/q3tts.h: q3tts_frame_instruct_ids): a tokenised instruction framed as the chat turn
+    <|im_start|>user\\n ... <|im_end|>\\n — what build_prompt(instruct_ids=...) and synthesize_batch(instructs=...) take.  Host-only."""
+    t = np.ascontiguousarray(text_ids, np.int32).reshape(-1)
+    L = lib()
+    n = L.q3tts_frame_instruct_ids(_p(t) if t.size else None, t.size, None, 0)
+    if n < 0:
+        raise ValueError("frame_instruct_ids: bad argument")
+    out = np.zeros(n, np.int64)
+    L.q3tts_frame_instruct_ids(_p(t) if t.size else None, t.size, _p(out), n)
+    return out
 
 
 def rng_uniform(seed, stream, frame, group):
