@@ -117,6 +117,12 @@ int q3tts_load_weights_file(q3tts_engine* e, const char* path);   /* set_tensor 
 int q3tts_save_weights_file(q3tts_engine* e, const char* path);
 
 /* ---- session-shaped entry points, host I/O, one per reference run_* ---- */
+/* The talker input row of a finished frame, tts_onnx.cpp:824-842: codes[n][n_groups] -> out[n][hidden], row i = codec_embed[code0] +
+ * cp_embed[0][sub0] + ... + cp_embed[n_groups-2][sub_last], accumulated in fp32 in that order, + the text row of frame frame0 + i:
+ * trailing[frame0 + i] when that index is < n_trailing, else the tts_pad row.  This is exactly what the fused generation loop feeds the
+ * talker after sampling that frame (bit for bit: the result is determined by the order of the adds), made by one launch on the device
+ * instead of 16 embedding round trips per frame.  code0 in [0, vocab), sub-codes in [0, sub_vocab); n <= max_ctx per call. */
+int q3tts_frame_rows_host(q3tts_engine* e, const int64_t* codes, int n, int frame0, const float* trailing, int n_trailing, float* out);
 /* run_text_project, tts_onnx.cpp:545-559: ids[n] -> out[n][hidden] */
 int q3tts_text_project_host(q3tts_engine* e, const int64_t* ids, int n, float* out);
 /* run_codec_embed / run_codec_embed_batch, tts_onnx.cpp:561-590 */
@@ -174,7 +180,9 @@ int q3tts_codec_stream_begin(q3tts_engine* e, int max_frames, int* stream_id);
 /* codes[n_frames][n_groups] of the NEXT n_frames frames of the stream -> the samples those frames own (*out_len of them) */
 int q3tts_codec_stream_push_host(q3tts_engine* e, int stream_id, const int64_t* codes, int n_frames, float* pcm, int64_t cap, int64_t* out_len);
 int q3tts_codec_stream_end(q3tts_engine* e, int stream_id);
-/* the same for frames of a slot that is still generating: call after q3tts_decode_steps has produced frame_end frames */
+/* the same for frames of a slot that is still generating: call after q3tts_decode_steps has produced frame_end frames.  Behind
+ * q3tts_slot_begin_codes the slot's frames start with the prefix: (slot, n_prefix, n_frames, left_context >= n_prefix) returns the new
+ * frames' samples with the prefix as history — the audio that joins what the prefix's own decode ended with, without a seam. */
 int q3tts_slot_codec_decode_range_host(q3tts_engine* e, int slot, int frame_begin, int frame_end, int left_context, float* pcm, int64_t cap,
                                        int64_t* out_len);
 /* run_vocoder (tts_onnx.cpp:759-776) for the NEXT frames of many carried-state streams at once — the reference decodes one whole
@@ -253,6 +261,23 @@ int64_t q3tts_frame_instruct_ids(const int32_t* text_ids, int64_t n, int64_t* ou
  * stream_id selects the RNG stream; ignore_eos keeps EOS suppressed (fixed-length benchmark mode). */
 int q3tts_slot_begin(q3tts_engine* e, int slot, const float* prompt, int S, const float* trailing, int n_trailing,
                      const q3tts_sampling* p, uint64_t seed, uint32_t stream_id, int ignore_eos);
+/* Continue from codes (tts_onnx.cpp:824-842 is the arithmetic of a frame's row; the reference itself can only start at frame 0).
+ * q3tts_slot_begin with prefix_codes[n_prefix][n_groups] teacher-forced behind the prompt: the slot is left in the state q3tts_slot_begin
+ * with the same arguments would have after generating exactly these as its first n_prefix frames — the talker's KV rows, the
+ * repetition penalty's code0 history, the frame index behind the text rows (trailing[frame], then tts_pad) and the RNG draws
+ * (q3tts_rng_uniform(seed, stream_id, frame, group)), and the slot's code buffer, which the vocoder reads for left context.  The
+ * forced frames cost a chunked prefill (the weights streamed once per 128 rows) instead of one decode step each.  n_prefix == 0 is
+ * q3tts_slot_begin, bit for bit.  p->max_new_tokens counts NEW frames; q3tts_slot_status, q3tts_slot_codes_host and
+ * q3tts_slot_codec_decode_host then see n_prefix + new frames.  Refused before anything is reserved or armed: n_prefix < 0,
+ * S + n_prefix + max_new_tokens > max_ctx, a code0 outside [0, vocab) or inside [suppress_begin, suppress_end) (EOS included: a
+ * recorded frame never holds it), a sub-code outside [0, sub_vocab) — the message names frame and group.  KV pages are taken for
+ * S + n_prefix + max_new_tokens; a pool that cannot hold them fails with "KV page pool exhausted" and arms nothing.
+ * Uses: the next sentence of a document conditioned on the previous one's text and codes; in-context voice clone from reference codes
+ * + reference text ([HINT], INTEGRATION.md section 5c: how upstream frames that prompt is unpinned, the arithmetic is verified, its
+ * effect on audio is not: no checkpoint was available); resuming an utterance from its codes on another engine. */
+int q3tts_slot_begin_codes(q3tts_engine* e, int slot, const float* prompt, int S, const float* trailing, int n_trailing,
+                           const int64_t* prefix_codes, int n_prefix,
+                           const q3tts_sampling* p, uint64_t seed, uint32_t stream_id, int ignore_eos);
 /* Advance every armed slot by n_steps frames (one hipGraph replay per frame).  Returns the number
  * of slots still active, <0 on error. */
 int q3tts_decode_steps(q3tts_engine* e, int n_steps);
@@ -315,6 +340,19 @@ int q3tts_synthesize_instruct_host(q3tts_engine* e, int n_utt, const int64_t* id
                                    float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                    int chunk_frames, q3tts_audio_cb cb, void* user,
                                    const int64_t* instruct_ids, const int32_t* instruct_offsets);
+/* q3tts_synthesize_schedule_host with teacher-forced frames per utterance (tts_onnx.cpp:824-842; q3tts_slot_begin_codes is the begin):
+ * prefix_codes / prefix_offsets [n_utt + 1], in FRAMES, give utterance u the frames [prefix_offsets[u], prefix_offsets[u + 1]) of
+ * prefix_codes[.][n_groups]; an empty range means none, and prefix_codes == NULL none for any.  A prefixed utterance is begun on its own
+ * (like an instructed one); a preempted one is re-admitted through the same forced begin.  n_frames[u] and codes_out cover prefix + new
+ * frames: codes_out (optional) is [n_utt][P + max_new_tokens][n_groups], P the longest prefix of the job.  pcm_out[u] receives only
+ * the samples the NEW frames own, out of the decode of all the utterance's frames (the decoder is causal: that slice is exact, and it
+ * joins the prefix's own audio without a seam), pcm_len[u] their count.  An utterance without a prefix gets what
+ * q3tts_synthesize_schedule_host gives it, bit for bit.  Non-streaming only: delivery through a q3tts_audio_cb with a prefix is not
+ * implemented. */
+int q3tts_synthesize_continue_host(q3tts_engine* e, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                                   const int64_t* prefix_codes, const int32_t* prefix_offsets);
 /* io::read_wav (src/io/wav_reader.h:13, wav_reader.cpp:28-143): mono float samples; -1 when the reference
  * returns an empty vector.  Call with out == NULL to learn *n_samples. */
 int q3tts_read_wav_host(const char* path, float* out, int64_t cap, int64_t* n_samples, int32_t* sample_rate);

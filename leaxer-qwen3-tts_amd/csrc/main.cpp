@@ -3,7 +3,8 @@
 // unknown flags ignored, 16-bit mono WAV at 24 kHz (clip to [-1,1], truncate x*32767).  Additions:
 // --tokens "id,id,..." (pre-tokenised text between TTS_BOS and TTS_EOS, bypassing vocab.json/merges.txt),
 // --seed N, --instruct TEXT / --instruct-tokens "id,id,..." (a voice instruction in front of the prompt: the reference README's roadmap
-// row "Voice instructions (--instruct)"; combines with --ref).
+// row "Voice instructions (--instruct)"; combines with --ref), --save-codes FILE / --continue-codes FILE (with --tokens: write the
+// utterance's codec frames, one per line; generate behind recorded frames — the WAV then holds the new audio only).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -43,12 +44,52 @@ static void usage(const char* prog) {
     printf("  --lang LANG           auto, en, zh, ja, ko (default: auto)\n");
     printf("  --instruct TEXT       voice instruction placed in front of the prompt (tokenised with the loaded vocab; combines with --ref)\n");
     printf("  --instruct-tokens IDS comma-separated text token ids of the instruction (for synthetic: models, like --tokens)\n");
+    printf("  --save-codes FILE     with --tokens: write the utterance's codec frames, one frame per line (--continue-codes frames included)\n");
+    printf("  --continue-codes FILE with --tokens: generate behind the recorded frames of FILE (as --save-codes writes them); the WAV holds the new audio only\n");
     printf("  --ref PATH            reference audio for voice clone (WAV; resampled to 24 kHz, ECAPA speaker encoder on the GPU)\n");
     printf("  --temp FLOAT          temperature (default: 0.8; 0 samples at T=1 like the reference, use --top-k 1 for greedy)\n");
     printf("  --top-k N             top-k (default: 50)\n  --top-p FLOAT         top-p (default: 0.95)\n");
     printf("  --rep-penalty FLOAT   repetition penalty on the first codebook's ids (default: 1.0 = off; not a flag of the reference CLI)\n");
     printf("  --max-tokens N        max codec frames (default: 2048)\n  --seed N              sampling seed (default: 0)\n");
     printf("  --stream-chunk N      with --tokens: decode audio every N frames while generating (same samples as the one-shot decode)\n  -h, --help\n");
+}
+
+// one frame per line, the same number of integers on every line (blanks or commas between them); false with a message on stderr
+static bool read_codes_file(const std::string& path, std::vector<int64_t>& codes, size_t& per_frame) {
+    FILE* f = fopen(path.c_str(), "r");
+    if (!f) { fprintf(stderr, "Error: cannot read codes file: %s\n", path.c_str()); return false; }
+    std::string line;
+    per_frame = 0;
+    int lineno = 0, ch = 0;
+    while (ch != EOF) {
+        line.clear();
+        while ((ch = fgetc(f)) != EOF && ch != '\n') line.push_back((char)ch);
+        ++lineno;
+        size_t n = 0;
+        const char* q = line.c_str();
+        for (;;) {
+            while (*q == ' ' || *q == '\t' || *q == ',' || *q == '\r') ++q;
+            if (!*q) break;
+            char* end = nullptr;
+            const long long v = strtoll(q, &end, 10);
+            if (end == q) { fprintf(stderr, "Error: %s line %d: not an integer: %s\n", path.c_str(), lineno, q); fclose(f); return false; }
+            codes.push_back((int64_t)v);
+            ++n;
+            q = end;
+        }
+        if (n == 0) continue;
+        if (per_frame == 0) per_frame = n;
+        else if (n != per_frame) { fprintf(stderr, "Error: %s line %d: %zu codes, the lines before have %zu\n", path.c_str(), lineno, n, per_frame); fclose(f); return false; }
+    }
+    fclose(f);
+    return true;
+}
+
+static bool write_codes_file(const std::string& path, const std::vector<int64_t>& codes, size_t per_frame) {
+    FILE* f = fopen(path.c_str(), "w");
+    if (!f) return false;
+    for (size_t i = 0; i < codes.size(); ++i) fprintf(f, "%lld%c", (long long)codes[i], (i + 1) % per_frame == 0 ? '\n' : ' ');
+    return fclose(f) == 0;
 }
 
 static Language lang_of(const std::string& s) {
@@ -60,7 +101,7 @@ static Language lang_of(const std::string& s) {
 }
 
 int main(int argc, char** argv) {
-    std::string model, prompt, tokens, output = "output.wav", lang = "auto", ref, instruct, instruct_tokens;
+    std::string model, prompt, tokens, output = "output.wav", lang = "auto", ref, instruct, instruct_tokens, save_codes, continue_codes;
     bool have_prompt = false;
     SamplingParams sp;
     uint64_t seed = 0;
@@ -77,6 +118,8 @@ int main(int argc, char** argv) {
         else if (a == "--ref" && more) ref = argv[++i];
         else if (a == "--instruct" && more) instruct = argv[++i];
         else if (a == "--instruct-tokens" && more) instruct_tokens = argv[++i];
+        else if (a == "--save-codes" && more) save_codes = argv[++i];
+        else if (a == "--continue-codes" && more) continue_codes = argv[++i];
         else if (a == "--temp" && more) sp.temperature = (float)atof(argv[++i]);
         else if (a == "--top-k" && more) sp.top_k = atoi(argv[++i]);
         else if (a == "--top-p" && more) sp.top_p = (float)atof(argv[++i]);
@@ -89,6 +132,18 @@ int main(int argc, char** argv) {
         fprintf(stderr, "Error: --model and --prompt (or --tokens) are required\n");
         usage(argv[0]);
         return 1;
+    }
+    std::vector<int64_t> prefix;
+    size_t prefix_groups = 0;
+    if (!save_codes.empty() || !continue_codes.empty()) {
+        if (tokens.empty() || !ref.empty() || !instruct.empty() || !instruct_tokens.empty() || stream_chunk > 0) {
+            fprintf(stderr, "Error: --save-codes / --continue-codes go with --tokens (without --ref, --instruct, --stream-chunk)\n");
+            return 1;
+        }
+        if (!continue_codes.empty()) {
+            if (!read_codes_file(continue_codes, prefix, prefix_groups)) return 1;
+            printf("Continue from: %s (%zu frames of %zu codes)\n", continue_codes.c_str(), prefix_groups ? prefix.size() / prefix_groups : 0, prefix_groups);
+        }
     }
     struct stat stbuf;
     if (model.rfind("synthetic:", 0) != 0 && model.rfind("synthetic-1.7b:", 0) != 0 && stat(model.c_str(), &stbuf) != 0) {
@@ -144,6 +199,19 @@ int main(int argc, char** argv) {
         });
         if (nf < 0) audio.clear();
         else printf("Streamed %d frames in %zu chunks\n", nf, chunks);
+    } else if (!ids.empty() && (!save_codes.empty() || !continue_codes.empty())) {
+        if (!prefix.empty() && prefix_groups != (size_t)engine.n_groups()) {
+            fprintf(stderr, "Error: %s has %zu codes per frame, the model has %d\n", continue_codes.c_str(), prefix_groups, engine.n_groups());
+            return 1;
+        }
+        std::vector<int64_t> all;
+        audio = engine.synthesize_tokens_continue(ids, prefix, lang_of(lang), sp, &all);
+        const size_t G = (size_t)engine.n_groups();
+        if (!audio.empty()) printf("Frames: %zu recorded + %zu new\n", prefix.size() / G, all.size() / G - prefix.size() / G);
+        if (!audio.empty() && !save_codes.empty()) {
+            if (!write_codes_file(save_codes, all, G)) { fprintf(stderr, "Error: failed to write %s\n", save_codes.c_str()); return 1; }
+            printf("Codes saved to: %s\n", save_codes.c_str());
+        }
     } else if (!ids.empty()) {
         audio = engine.synthesize_tokens(ids, lang_of(lang), sp);
     } else audio = engine.synthesize(prompt, lang_of(lang), sp);

@@ -199,6 +199,9 @@ int q3tts_finalize(q3tts_engine* h) {
 int q3tts_text_project_host(q3tts_engine* h, const int64_t* ids, int n, float* out) {
     Q3_API_BEGIN(h) h->e->text_project(ids, n, out); return 0; Q3_API_END(h)
 }
+int q3tts_frame_rows_host(q3tts_engine* h, const int64_t* codes, int n, int frame0, const float* trailing, int n_trailing, float* out) {
+    Q3_API_BEGIN(h) h->e->frame_rows(codes, n, frame0, trailing, n_trailing, out); return 0; Q3_API_END(h)
+}
 int q3tts_codec_embed_host(q3tts_engine* h, const int64_t* ids, int n, float* out) {
     Q3_API_BEGIN(h) h->e->codec_embed(ids, n, out); return 0; Q3_API_END(h)
 }
@@ -387,6 +390,18 @@ int q3tts_slot_begin(q3tts_engine* h, int slot, const float* prompt, int S, cons
                      const q3tts_sampling* p, uint64_t seed, uint32_t stream_id, int ignore_eos) {
     Q3_API_BEGIN(h) h->e->slot_begin(slot, prompt, S, trailing, n_trailing, *p, seed, stream_id, ignore_eos); return 0; Q3_API_END(h)
 }
+int q3tts_slot_begin_codes(q3tts_engine* h, int slot, const float* prompt, int S, const float* trailing, int n_trailing,
+                           const int64_t* prefix_codes, int n_prefix,
+                           const q3tts_sampling* p, uint64_t seed, uint32_t stream_id, int ignore_eos) {
+    Q3_API_BEGIN(h)
+    if (!p) throw q3::Error("slot_begin_codes: null argument");
+    Engine::SlotInit in;
+    in.slot = slot; in.prompt = prompt; in.S = S; in.trailing = trailing; in.n_trailing = n_trailing; in.stream_id = stream_id;
+    in.prefix = prefix_codes; in.n_prefix = n_prefix;
+    h->e->slots_begin(&in, 1, *p, seed, ignore_eos);
+    return 0;
+    Q3_API_END(h)
+}
 int q3tts_decode_steps(q3tts_engine* h, int n_steps) {
     Q3_API_BEGIN(h) return h->e->decode_steps(n_steps); Q3_API_END(h)
 }
@@ -499,13 +514,22 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
 static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                     const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                     float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
-                                    int64_t* codes_out, const int64_t* instruct_ids, const int32_t* instruct_offsets);
+                                    int64_t* codes_out, const int64_t* instruct_ids, const int32_t* instruct_offsets,
+                                    const int64_t* prefix_codes = nullptr, const int32_t* prefix_offsets = nullptr);
 
 int q3tts_synthesize_schedule_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                    const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                    float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
                                    int64_t* codes_out) {
     return synthesize_schedule_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out, nullptr, nullptr);
+}
+
+int q3tts_synthesize_continue_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                                   const int64_t* prefix_codes, const int32_t* prefix_offsets) {
+    return synthesize_schedule_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
+                                    nullptr, nullptr, prefix_codes, prefix_offsets);
 }
 
 int q3tts_synthesize_instruct_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
@@ -522,7 +546,8 @@ int q3tts_synthesize_instruct_host(q3tts_engine* h, int n_utt, const int64_t* id
 static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                     const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                     float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
-                                    int64_t* codes_out, const int64_t* instruct_ids, const int32_t* instruct_offsets) {
+                                    int64_t* codes_out, const int64_t* instruct_ids, const int32_t* instruct_offsets,
+                                    const int64_t* prefix_codes, const int32_t* prefix_offsets) {
     Q3_API_BEGIN(h)
     Engine& e = *h->e;
     const int H = e.c.hidden, G = e.c.n_groups, B = e.B;
@@ -530,8 +555,20 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
     if (!ids || !offsets || !p) throw q3::Error("synthesize: null argument");
     if (pcm_cap < 0) throw q3::Error("synthesize: negative pcm_cap");
     (void)Engine::checked_penalty(*p);   // refused before any slot is touched
+    // teacher-forced frames per utterance (q3tts_synthesize_continue_host): pf(u) of them behind utterance u's prompt, P the longest
+    if (prefix_codes && !prefix_offsets) throw q3::Error("synthesize: prefix_codes without prefix_offsets");
+    auto pf = [&](int u) { return prefix_codes ? (int)(prefix_offsets[u + 1] - prefix_offsets[u]) : 0; };
+    auto pcodes = [&](int u) { return prefix_codes + (size_t)prefix_offsets[u] * (size_t)G; };
+    int P = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        if (pf(u) < 0 || (prefix_codes && prefix_offsets[u] < 0)) throw q3::Error("synthesize: prefix_offsets must start at >= 0 and not decrease");
+        if (pf(u) > 0 && pf(u) + p->max_new_tokens > e.max_frames_cap) throw q3::Error("synthesize: utterance " + std::to_string(u) + ": prefix frames + max_new_tokens exceeds the slot's frame capacity");
+        try { if (pf(u) > 0) e.check_frame_codes(pcodes(u), pf(u), true); }
+        catch (const q3::Error& ex) { throw q3::Error("synthesize: utterance " + std::to_string(u) + ": " + ex.msg); }
+        P = std::max(P, pf(u));
+    }
     for (int b = 0; b < B; ++b) e.slot_release(b);
-    const int row_frames = std::max(1, std::min(p->max_new_tokens, e.max_frames_cap));
+    const int row_frames = std::max(1, std::min(P + p->max_new_tokens, e.max_frames_cap));
     e.codec_async_prepare(row_frames, n_utt);
     std::vector<int32_t> got_frames((size_t)n_utt, 0);
     std::vector<Prep> prep;
@@ -547,7 +584,9 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
     std::deque<int> pending;
     auto cap_of = [&](int u) { return max_new_per_utt ? std::min(std::max(1, (int)max_new_per_utt[u]), p->max_new_tokens) : p->max_new_tokens; };
     for (int u = 0; u < n_utt; ++u) {
-        if (e.kv_pages_for(prep[(size_t)u].S + cap_of(u)) > e.kv_total_pages())
+        if (pf(u) > 0 && prep[(size_t)u].S + pf(u) + p->max_new_tokens > e.max_ctx)
+            throw q3::Error("synthesize: utterance " + std::to_string(u) + ": prompt + prefix frames + max_new_tokens exceeds max_ctx");
+        if (e.kv_pages_for(prep[(size_t)u].S + pf(u) + cap_of(u)) > e.kv_total_pages())
             throw q3::Error("synthesize: one utterance (prompt + max_new_tokens) needs more KV pages than the pool holds");
         pending.push_back(u);
     }
@@ -568,8 +607,8 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
                 std::vector<int> free_slots, need;
                 for (int b = 0; b < B; ++b) if (slot_utt[(size_t)b] < 0) free_slots.push_back(b);
                 for (size_t i = 0; i < pending.size() && i < free_slots.size(); ++i) {
-                    const int u = pending[i], all = prep[(size_t)u].S + cap_of(u);
-                    int pages = e.kv_pages_for(reserve_all ? all : std::min(all, prep[(size_t)u].S + first_look));
+                    const int u = pending[i], all = prep[(size_t)u].S + pf(u) + cap_of(u);
+                    int pages = e.kv_pages_for(reserve_all ? all : std::min(all, prep[(size_t)u].S + pf(u) + first_look));
                     if (hold_pages[(size_t)u] > 0 && n_retired == hold_mark[(size_t)u] && live > 0) pages = std::max(pages, std::min(hold_pages[(size_t)u], e.kv_total_pages()));
                     need.push_back(pages);
                 }
@@ -577,17 +616,22 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
                 for (int i = 0; i < n_adm; ++i) { slot_utt[(size_t)free_slots[(size_t)i]] = pending.front(); pending.pop_front(); fresh.push_back(free_slots[(size_t)i]); }
             }
             if (!fresh.empty()) {
-                init.assign(fresh.size(), Engine::SlotInit());
+                init.clear();
                 for (size_t i = 0; i < fresh.size(); ++i) {
                     const int b = fresh[i], u = slot_utt[(size_t)b];
                     const Prep& pr = prep[(size_t)u];
-                    Engine::SlotInit& q = init[i];
+                    Engine::SlotInit q;
                     q.slot = b; q.prompt = prompts.data() + pr.poff * H; q.S = pr.S; q.trailing = trailing.data() + pr.toff * H; q.n_trailing = pr.nt;
                     q.stream_id = (uint32_t)u;
                     q.max_frames = max_new_per_utt ? std::max(1, (int)max_new_per_utt[u]) : 0;
-                    q.kv_tokens = reserve_all ? 0 : pr.S + first_look;
+                    q.kv_tokens = reserve_all ? 0 : pr.S + pf(u) + first_look;
+                    if (pf(u) > 0) {   // forced begin, on its own (a re-admission after a preemption too); the slot starts pf(u) frames in
+                        q.prefix = pcodes(u); q.n_prefix = pf(u);
+                        e.slots_begin(&q, 1, *p, seed, ignore_eos);
+                        done_frames[(size_t)b] = pf(u);
+                    } else init.push_back(q);
                 }
-                e.slots_begin(init.data(), (int)init.size(), *p, seed, ignore_eos);   // equal-length prompts in consecutive slots share one prefill pass
+                if (!init.empty()) e.slots_begin(init.data(), (int)init.size(), *p, seed, ignore_eos);   // equal-length prompts in consecutive slots share one prefill pass
                 live += (int)fresh.size();
                 e.sched_admitted += (int64_t)fresh.size();
                 e.sched_peak_live = std::max(e.sched_peak_live, live);
@@ -596,7 +640,7 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
             int rem = p->max_new_tokens;
             for (int b = 0; b < B; ++b) {
                 const int u = slot_utt[(size_t)b];
-                if (u >= 0) rem = std::min(rem, cap_of(u) - done_frames[(size_t)b]);
+                if (u >= 0) rem = std::min(rem, pf(u) + cap_of(u) - done_frames[(size_t)b]);
             }
             // (with EOS suppressed nothing can finish earlier than that, so the look-ahead only bounds how long the host is away)
             // While utterances wait in the queue a look is at least `quantum` steps away: a finished slot idles a few (masked, nearly free)
@@ -613,7 +657,7 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
                     return done_frames[(size_t)x] != done_frames[(size_t)y] ? done_frames[(size_t)x] > done_frames[(size_t)y] : slot_utt[(size_t)x] < slot_utt[(size_t)y]; });
                 for (int b : order) {
                     const int u = slot_utt[(size_t)b];
-                    want.push_back(std::min(prep[(size_t)u].S + cap_of(u), prep[(size_t)u].S + done_frames[(size_t)b] + steps));
+                    want.push_back(std::min(prep[(size_t)u].S + pf(u) + cap_of(u), prep[(size_t)u].S + done_frames[(size_t)b] + steps));
                 }
                 const std::vector<int> victims = q3::sched_grow(e.kv, order, want, &changed);
                 for (int vb : victims) {          // youngest first: pushed to the front one by one, the oldest of them ends up first in the queue
@@ -643,7 +687,7 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
             }
             for (int b : retired) {
                 const int u = slot_utt[(size_t)b];
-                if (codes_out) e.slot_codes(b, codes_out + (size_t)u * p->max_new_tokens * G, p->max_new_tokens);
+                if (codes_out) e.slot_codes(b, codes_out + (size_t)u * (size_t)(P + p->max_new_tokens) * G, P + p->max_new_tokens);
                 e.slot_release(b);
                 slot_utt[(size_t)b] = -1; done_frames[(size_t)b] = 0;
                 --live; ++n_retired;
@@ -654,7 +698,25 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
         for (int b = 0; b < B; ++b) { try { e.slot_release(b); } catch (...) { } }
         throw;
     }
-    vocoder_job(e, n_utt, got_frames, row_frames, pcm_out, pcm_cap, pcm_len);
+    if (P == 0) { vocoder_job(e, n_utt, got_frames, row_frames, pcm_out, pcm_cap, pcm_len); return 0; }
+    // With prefixes every utterance is decoded whole into a buffer of the job's own, and the caller receives the samples its new frames
+    // own: [L(prefix), L(all)) of the whole decode (causal decoder: exact).  An utterance without a prefix receives all of its decode.
+    std::vector<std::vector<float>> whole((size_t)n_utt);
+    std::vector<float*> wp((size_t)n_utt, nullptr);
+    std::vector<int64_t> wl((size_t)n_utt, 0);
+    int64_t wcap = 1;
+    for (int u = 0; u < n_utt; ++u) {
+        const int64_t L = got_frames[(size_t)u] > 0 ? q3tts_codec_decode_len(&e.c, got_frames[(size_t)u]) : 0;
+        if (pcm_out && pcm_out[u]) { whole[(size_t)u].resize((size_t)std::max<int64_t>(L, 1)); wp[(size_t)u] = whole[(size_t)u].data(); }
+        wcap = std::max(wcap, L);
+    }
+    for (int u = 0; u < n_utt; ++u) if (wp[(size_t)u]) { whole[(size_t)u].resize((size_t)wcap); wp[(size_t)u] = whole[(size_t)u].data(); }   // one capacity for the job
+    vocoder_job(e, n_utt, got_frames, row_frames, pcm_out ? wp.data() : nullptr, wcap, wl.data());
+    for (int u = 0; u < n_utt; ++u) {
+        const int64_t first = pf(u) > 0 ? q3tts_codec_decode_len(&e.c, pf(u)) : 0, own = std::max<int64_t>(0, wl[(size_t)u] - first);
+        if (pcm_len) pcm_len[u] = own;
+        if (wp[(size_t)u] && own > 0) memcpy(pcm_out[u], wp[(size_t)u] + first, (size_t)std::min(own, pcm_cap) * sizeof(float));
+    }
     return 0;
     Q3_API_END(h)
 }

@@ -274,6 +274,24 @@ struct SampleArgs {
 };
 void launch_sample(const SampleArgs& a, hipStream_t s);
 
+// Frames that were not sampled here -> the talker input rows the sampler's fused epilogue would have left in x_talk for them (reference
+// tts_onnx.cpp:824-842): row i = codec_embed[code0] + cp_embed[0][sub0] + ... + cp_embed[n_groups - 2][sub_last] (fp32, in that order)
+// + the text row of frame frame0 + i.  One workgroup per frame of ONE slot.  Optionally the launch also records the frames as the
+// sampler does: the ids as int32 into codes_out [n][n_groups] and the code0 bits into the slot's repetition-penalty bitmap.
+struct FrameRowsArgs {
+    const int64_t* codes = nullptr;  // [n][n_groups] (device), validated by the caller; the kernel clamps them all the same
+    int n = 0, n_groups = 0, H = 0;
+    const bf16_t* embed0 = nullptr; int V0 = 0;       // codec_embed_w [V0][H]
+    const bf16_t* embed_sub[31] = {}; int SV = 0;     // cp_embed_w[g - 1] [SV][H]; launch_frame_rows points the unused entries at the last table
+    const float* trailing = nullptr; // [.][H]: row i is the text row of frame frame0 + i (read while frame0 + i < trailing_len)
+    int frame0 = 0, trailing_len = 0;
+    const float* tts_pad = nullptr;  // [H]
+    float* out = nullptr; int ldo = 0;
+    int32_t* codes_out = nullptr;    // optional
+    uint32_t* seen = nullptr;        // optional: the slot's bitmap row, >= ceil(V0 / 32) words
+};
+void launch_frame_rows(FrameRowsArgs a, hipStream_t s);
+
 void launch_gather_rows_bf16(const bf16_t* table, int H, const int64_t* ids_dev, int n, float* out, int ldo, hipStream_t s);
 void launch_fill_synth(void* dst, int is_bf16, int64_t n, uint64_t key, float mean, float stddev, hipStream_t s);
 void launch_bf16_to_f32(const bf16_t* src, float* dst, int64_t n, hipStream_t s);

@@ -3349,6 +3349,70 @@ void launch_sample(const SampleArgs& a, hipStream_t s) {
 }
 
 // ================================================================================================
+// teacher-forced frames -> talker input rows (FrameRowsArgs, q3_common.h)
+// ================================================================================================
+// The row k_sample's epilogue above leaves in x_talk for a frame it sampled, for a frame that is given: 16 bf16 embedding rows unpacked
+// the same way and added in fp32 in the order code0, sub0 .. sub14, then the text row (reference tts_onnx.cpp:824-842).  Adds only, so
+// the result is determined by their order.  Per 1024 columns every thread issues the text load and the gathers of 16 groups (8-byte
+// bf16 loads, clamped addresses, no branch) before its first add; a config with more than 16 groups takes a second batch of gathers.
+template <int G0>
+__device__ __forceinline__ void frame_rows_batch(const FrameRowsArgs& a, const int* ids, int hc, float acc[4]) {
+    uint2 raw[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int g = G0 + k;   // compile-time: the table pointer is a fixed kernel argument
+        const bf16_t* tab = g == 0 ? a.embed0 : a.embed_sub[g - 1 < 31 ? g - 1 : 30];
+        raw[k] = *reinterpret_cast<const uint2*>(tab + (size_t)ids[g] * a.H + hc);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int g = G0 + k;
+        if (g < a.n_groups) {   // uniform
+            const float e0 = __uint_as_float(raw[k].x << 16), e1 = __uint_as_float(raw[k].x & 0xFFFF0000u);
+            const float e2 = __uint_as_float(raw[k].y << 16), e3 = __uint_as_float(raw[k].y & 0xFFFF0000u);
+            if (g == 0) { acc[0] = e0; acc[1] = e1; acc[2] = e2; acc[3] = e3; }
+            else { acc[0] = acc[0] + e0; acc[1] = acc[1] + e1; acc[2] = acc[2] + e2; acc[3] = acc[3] + e3; }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_frame_rows(const FrameRowsArgs a) {
+    const int i = blockIdx.x, tid = threadIdx.x;
+    __shared__ int ids[32];
+    if (tid < 32) {   // the frame's ids, clamped into their tables; groups past n_groups repeat the last one (their gathers are discarded)
+        const int g = tid < a.n_groups ? tid : a.n_groups - 1;
+        const int64_t v = a.codes[(size_t)i * a.n_groups + g];
+        const int64_t top = (g == 0 ? a.V0 : a.SV) - 1;
+        const int id = (int)(v < 0 ? 0 : (v > top ? top : v));
+        ids[tid] = id;
+        if (tid < a.n_groups && a.codes_out) a.codes_out[(size_t)i * a.n_groups + tid] = id;
+        if (tid == 0 && a.seen) atomicOr(a.seen + (id >> 5), 1u << (id & 31));   // the frames of a slot share its bitmap
+    }
+    __syncthreads();
+    const float* text = a.frame0 + i < a.trailing_len ? a.trailing + (size_t)i * a.H : a.tts_pad;   // :833-842
+    float* out = a.out + (size_t)i * a.ldo;
+    for (int h0 = 0; h0 < a.H; h0 += 1024) {
+        const int h = h0 + tid * 4;
+        const int hc = h < a.H ? h : a.H - 4;
+        const float4 tx = *reinterpret_cast<const float4*>(text + hc);
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        frame_rows_batch<0>(a, ids, hc, acc);
+        if (a.n_groups > 16) frame_rows_batch<16>(a, ids, hc, acc);
+        if (h < a.H) *reinterpret_cast<float4*>(out + h) = make_float4(acc[0] + tx.x, acc[1] + tx.y, acc[2] + tx.z, acc[3] + tx.w);
+    }
+}
+
+void launch_frame_rows(FrameRowsArgs a, hipStream_t s) {
+    if (a.n <= 0) return;
+    if (a.n_groups < 2 || a.n_groups > 32 || a.H < 4 || a.H % 4 || a.ldo < a.H || a.ldo % 4 || a.V0 < 1 || a.SV < 1) throw Error("frame_rows: dims out of range");
+    if (!a.codes || !a.embed0 || !a.tts_pad || !a.out || a.frame0 < 0 || (a.trailing_len > a.frame0 && !a.trailing)) throw Error("frame_rows: bad arguments");
+    for (int g = 0; g < a.n_groups - 1; ++g) if (!a.embed_sub[g]) throw Error("frame_rows: missing predictor embedding table");
+    for (int g = a.n_groups - 1; g < 31; ++g) a.embed_sub[g] = a.embed_sub[a.n_groups - 2];   // clamped gathers of the groups the config lacks
+    hipLaunchKernelGGL(k_frame_rows, dim3(a.n), dim3(256), 0, s, a);
+}
+
+// ================================================================================================
 // small helpers
 // ================================================================================================
 __global__ void k_gather_rows_bf16(const bf16_t* table, int H, const int64_t* ids, float* out, int ldo) {

@@ -382,6 +382,8 @@ Engine::~Engine() {
     if (proj_out_d) (void)hipFree(proj_out_d);
     if (hist_d) (void)hipFree(hist_d);
     if (long_x_d) (void)hipFree(long_x_d);
+    if (frame_codes_d) (void)hipFree(frame_codes_d);
+    if (frame_text_d) (void)hipFree(frame_text_d);
     codec_free();
     speaker_free();
     free_packed_weights();
@@ -1518,7 +1520,15 @@ void Engine::slots_begin(const SlotInit* in, int n, const q3tts_sampling& p, uin
         if (in[i].n_trailing < 0 || in[i].n_trailing > max_trailing) throw Error("too many trailing text rows");
         if (in[i].S < 1 || in[i].S > max_ctx) throw Error("prefill length must be 1..max_ctx rows");
         if (p.max_new_tokens < 1 || in[i].S + p.max_new_tokens > max_ctx) throw Error("prompt + max_new_tokens exceeds max_ctx");
+        if (in[i].n_prefix < 0 || (in[i].n_prefix > 0 && !in[i].prefix)) throw Error("prefix codes: n_prefix must be >= 0 (and the codes given)");
+        if (in[i].n_prefix > 0) {
+            if (in[i].S + in[i].n_prefix + p.max_new_tokens > max_ctx) throw Error("prompt + prefix frames + max_new_tokens exceeds max_ctx");
+            if (in[i].n_prefix + p.max_new_tokens > max_frames_cap) throw Error("prefix frames + max_new_tokens exceeds the slot's frame capacity");
+            if (n != 1) throw Error("slots_begin: a slot with prefix codes is begun on its own");
+            check_frame_codes(in[i].prefix, in[i].n_prefix, true);
+        }
     }
+    if (n == 1 && in[0].n_prefix > 0) { slot_begin_forced(in[0], p, seed, ignore_eos, rep_penalty); return; }
     {   // KV pages for the prompt and every frame the slot may generate, all or nothing: nothing is armed if the pool cannot hold the set
         int need = 0;
         auto tokens_of = [&](const SlotInit& q) {
@@ -1594,6 +1604,103 @@ void Engine::slots_begin(const SlotInit* in, int n, const q3tts_sampling& p, uin
         Q3_HIP_CHECK(hipMemsetAsync(seen_d + (size_t)q.slot * seen_ld, 0, (size_t)seen_ld * sizeof(uint32_t), stream));
         Q3_HIP_CHECK(hipMemcpyAsync(st_d + q.slot, &s, sizeof(SlotState), hipMemcpyHostToDevice, stream));
     }
+    sync();
+}
+
+void Engine::check_frame_codes(const int64_t* codes, int n, bool strict) const {
+    const int G = c.n_groups;
+    for (int f = 0; f < n; ++f)
+        for (int g = 0; g < G; ++g) {
+            const int64_t v = codes[(size_t)f * G + g];
+            const bool ok = g == 0 ? v >= 0 && v < c.vocab && !(strict && ((v >= c.suppress_begin && v < c.suppress_end) || v == c.codec_eos)) : v >= 0 && v < c.sub_vocab;
+            if (!ok) {
+                char msg[200];
+                snprintf(msg, sizeof msg, "frame codes: frame %d group %d holds %lld, outside %s", f, g, (long long)v,
+                         g != 0 ? "[0, sub_vocab)" : (strict ? "[0, vocab) without the suppressed ids (EOS among them)" : "[0, vocab)"));
+                throw Error(msg);
+            }
+        }
+}
+
+void Engine::frame_rows_launch(const int64_t* codes, int n, int frame0, const float* trailing_dev, int trailing_len, float* out_dev,
+                               int32_t* codes_out, uint32_t* seen) {
+    const int G = c.n_groups;
+    if ((size_t)n * G > frame_codes_cap) {
+        sync();
+        if (frame_codes_d) (void)hipFree(frame_codes_d);
+        frame_codes_d = nullptr; frame_codes_cap = 0;
+        const size_t cap = std::max((size_t)n, (size_t)256) * G;
+        Q3_HIP_CHECK(hipMalloc((void**)&frame_codes_d, cap * sizeof(int64_t)));
+        frame_codes_cap = cap;
+    }
+    Q3_HIP_CHECK(hipMemcpyAsync(frame_codes_d, codes, (size_t)n * G * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    FrameRowsArgs a;
+    a.codes = frame_codes_d; a.n = n; a.n_groups = G; a.H = c.hidden;
+    a.embed0 = codec_embed_w; a.V0 = c.vocab; a.SV = c.sub_vocab;
+    for (int g = 0; g < G - 1; ++g) a.embed_sub[g] = cp_embed_w[(size_t)g];
+    a.trailing = trailing_dev; a.frame0 = frame0; a.trailing_len = trailing_len; a.tts_pad = tts_pad_d;
+    a.out = out_dev; a.ldo = c.hidden; a.codes_out = codes_out; a.seen = seen;
+    launch_frame_rows(a, stream);
+}
+
+// q3tts_frame_rows_host: the kernel on its own, for callers and tests
+void Engine::frame_rows(const int64_t* codes, int n, int frame0, const float* trailing, int n_trailing, float* out) {
+    if (!finalized) throw Error("weights not finalized");
+    if (n < 0 || frame0 < 0 || n_trailing < 0) throw Error("frame_rows: negative argument");
+    if (n == 0) return;
+    if (!codes || !out || (n_trailing > 0 && !trailing)) throw Error("frame_rows: null argument");
+    if (n > max_ctx) throw Error("frame_rows: more frames than max_ctx in one call");
+    check_frame_codes(codes, n, false);
+    const int H = c.hidden;
+    const int n_text = std::max(0, std::min(n_trailing - frame0, n));   // frames frame0 .. frame0 + n_text - 1 have a text row, the rest tts_pad
+    if ((size_t)n_text > frame_text_rows) {
+        sync();
+        if (frame_text_d) (void)hipFree(frame_text_d);
+        frame_text_d = nullptr; frame_text_rows = 0;
+        const size_t rows = std::max((size_t)n_text, (size_t)64);
+        Q3_HIP_CHECK(hipMalloc((void**)&frame_text_d, rows * H * sizeof(float)));
+        frame_text_rows = rows;
+    }
+    float* x = long_rows(n);
+    if (n_text > 0) Q3_HIP_CHECK(hipMemcpyAsync(frame_text_d, trailing + (size_t)frame0 * H, (size_t)n_text * H * sizeof(float), hipMemcpyHostToDevice, stream));
+    frame_rows_launch(codes, n, frame0, frame_text_d, frame0 + n_text, x, nullptr, nullptr);
+    Q3_HIP_CHECK(hipMemcpyAsync(out, x, (size_t)n * H * sizeof(float), hipMemcpyDeviceToHost, stream));
+    sync();
+}
+
+// Forced begin (include/q3tts.h: q3tts_slot_begin_codes): the slot as q3tts_slot_begin would have it after generating exactly q.prefix
+// as its first frames.  The forced frames' rows are made on the device behind the prompt rows and the S + F0 rows take the prefill the
+// same rows would take as a prompt (one pass up to 16 rows, causal chunks beyond); the launch that makes the rows also records the
+// frames (codes, code0 bitmap).  Validated by slots_begin.
+void Engine::slot_begin_forced(const SlotInit& q, const q3tts_sampling& p, uint64_t seed, int ignore_eos, float rep_penalty) {
+    const int H = c.hidden, G = c.n_groups, S = q.S, F0 = q.n_prefix, R = S + F0, slot = q.slot;
+    const int new_cap = q.max_frames > 0 ? std::min(q.max_frames, p.max_new_tokens) : p.max_new_tokens;
+    {   // KV pages for prompt, prefix and every new frame (or what the caller grows from): nothing is armed if the pool cannot hold them
+        const int all = R + new_cap, tokens = q.kv_tokens > 0 ? std::min(all, std::max(q.kv_tokens, R)) : all;
+        const int need = kv_pages_for(tokens) - kv_slot_pages(slot);
+        if (need > kv_free_pages()) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "KV page pool exhausted: 1 slots need %d more pages, %d of %d free", need, kv_free_pages(), kv_total_pages());
+            throw Error(msg);
+        }
+        kv_reserve(slot, tokens, true);
+    }
+    float* x = R <= 16 ? xp : long_rows(R);
+    float* tr = trailing_d + (size_t)slot * max_trailing * H;
+    uint32_t* seen = seen_d + (size_t)slot * seen_ld;
+    Q3_HIP_CHECK(hipMemcpyAsync(x, q.prompt, (size_t)S * H * sizeof(float), hipMemcpyHostToDevice, stream));
+    if (q.n_trailing > 0) Q3_HIP_CHECK(hipMemcpyAsync(tr, q.trailing, (size_t)q.n_trailing * H * sizeof(float), hipMemcpyHostToDevice, stream));
+    // the code0 history starts empty and then holds the prefix: cleared before the launch that sets its bits, and not again behind it
+    Q3_HIP_CHECK(hipMemsetAsync(seen, 0, (size_t)seen_ld * sizeof(uint32_t), stream));
+    frame_rows_launch(q.prefix, F0, 0, tr, q.n_trailing, x + (size_t)S * H, codes_d + (size_t)slot * max_frames_cap * G, seen);
+    if (R <= 16) prefill_rows_in_xp(slot, R);
+    else prefill_rows_long(slot, x, R, nullptr);
+    slot_codec_stream_reset(slot);
+    SlotState& s = st_h[slot];   // after the prefill, which writes prompt_len = R and n_frames = 0
+    s.n_frames = F0; s.finished = 0; s.active = 1; s.prompt_len = S; s.trailing_len = q.n_trailing;
+    s.max_frames = F0 + new_cap;
+    s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
+    Q3_HIP_CHECK(hipMemcpyAsync(st_d + slot, &s, sizeof(SlotState), hipMemcpyHostToDevice, stream));
     sync();
 }
 

@@ -176,10 +176,24 @@ public:
     // ---- fused generation ----
     struct SlotInit { int slot = 0; const float* prompt = nullptr; int S = 0; const float* trailing = nullptr; int n_trailing = 0; uint32_t stream_id = 0;
                       int max_frames = 0; /* 0: the call's max_new_tokens */
-                      int kv_tokens = 0;  /* KV pages reserved now, in tokens; 0: prompt + max_frames (the slot never needs more) */ };
+                      int kv_tokens = 0;  /* KV pages reserved now, in tokens; 0: prompt + max_frames (the slot never needs more) */
+                      // Teacher-forced frames behind the prompt (continue from codes): prefix[n_prefix][n_groups] on the host.  The slot is
+                      // left as if it had generated exactly these as its first n_prefix frames; max_frames and max_new_tokens count the
+                      // frames behind them.  Such a slot is begun on its own (slots_begin with n == 1), like any long prompt.
+                      const int64_t* prefix = nullptr; int n_prefix = 0; };
     void slots_begin(const SlotInit* in, int n, const q3tts_sampling& p, uint64_t seed, int ignore_eos); // batched prefill of equal-length prompts
     void slot_begin(int slot, const float* prompt, int S, const float* trailing, int n_trailing,
                     const q3tts_sampling& p, uint64_t seed, uint32_t stream_id, int ignore_eos);
+    void slot_begin_forced(const SlotInit& q, const q3tts_sampling& p, uint64_t seed, int ignore_eos, float rep_penalty);   // slots_begin's path for n_prefix > 0
+    // forced-begin validation of recorded frames: code0 in [0, vocab) outside [suppress_begin, suppress_end) (a recorded frame never holds
+    // EOS), sub-codes in [0, sub_vocab); strict == false (frame_rows): code0 anywhere in [0, vocab).  The error names frame and group.
+    void check_frame_codes(const int64_t* codes, int n, bool strict) const;
+    // rows of n given frames (FrameRowsArgs) on the engine's stream: codes from the host, everything else on the device
+    void frame_rows_launch(const int64_t* codes, int n, int frame0, const float* trailing_dev, int trailing_len, float* out_dev,
+                           int32_t* codes_out, uint32_t* seen);
+    void frame_rows(const int64_t* codes, int n, int frame0, const float* trailing, int n_trailing, float* out);   // session-shaped, host I/O
+    int64_t* frame_codes_d = nullptr; size_t frame_codes_cap = 0;   // staging of the given frames' ids (grow-only)
+    float* frame_text_d = nullptr; size_t frame_text_rows = 0;      // frame_rows: the text rows it reads (grow-only)
     int decode_steps(int n_steps);
     void slot_status(int slot, int* n_frames, int* finished);
     void slot_codes(int slot, int64_t* codes, int cap_frames);

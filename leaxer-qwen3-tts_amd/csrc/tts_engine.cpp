@@ -47,6 +47,7 @@ TTSEngine::TTSEngine(const std::string& model_dir) {
     }
     spk_dim_ = cfg.spk_enc_dim;
     cfg_hidden_ = cfg.hidden;
+    n_groups_ = cfg.n_groups;
     // tokenizer files: where the reference looks (tts_onnx.cpp:110-121: <parent of model_dir>/models/
     // Qwen3-TTS-12Hz-0.6B-Base/{vocab.json,merges.txt}), then model_dir itself.  Present but unreadable is
     // an error, absent is a warning and text synthesis stays unavailable — as in the reference.
@@ -199,6 +200,39 @@ std::vector<float> TTSEngine::synthesize_tokens_instruct(const std::vector<int64
         std::cerr << "[TTSEngine] Synthesis error: " << q3tts_last_error(h_) << std::endl;
         return {};
     }
+    pcm.resize((size_t)std::min<int64_t>(len, cap));
+    return pcm;
+}
+
+std::vector<float> TTSEngine::synthesize_tokens_continue(const std::vector<int64_t>& token_ids, const std::vector<int64_t>& prefix_codes, Language lang,
+                                                         const SamplingParams& params, std::vector<int64_t>* all_codes) {
+    if (all_codes) all_codes->clear();
+    if (!ready_) return {};
+    const size_t G = (size_t)n_groups_;
+    if (prefix_codes.size() % G != 0) {
+        std::cerr << "[TTSEngine] Synthesis error: prefix codes are not whole frames of " << G << " ids" << std::endl;
+        return {};
+    }
+    const int F0 = (int)(prefix_codes.size() / G);
+    q3tts_sampling sp{ params.temperature, params.top_p, params.top_k, params.repetition_penalty, params.max_new_tokens };
+    sp.max_new_tokens = std::min(sp.max_new_tokens, max_ctx_ - F0 - 16);   // prompt rows: at most 16
+    if (sp.max_new_tokens < 1) {
+        std::cerr << "[TTSEngine] Synthesis error: the prefix does not fit the engine's context" << std::endl;
+        return {};
+    }
+    const int32_t offs[2] = { 0, (int32_t)token_ids.size() }, poffs[2] = { 0, F0 };
+    const int64_t cap = (int64_t)sp.max_new_tokens * 1920 + 1920;
+    std::vector<float> pcm((size_t)cap);
+    std::vector<int64_t> codes((size_t)(F0 + sp.max_new_tokens) * G);
+    float* ptr = pcm.data();
+    int64_t len = 0;
+    int32_t frames = 0;
+    if (q3tts_synthesize_continue_host(h_, 1, token_ids.data(), offs, lang_index(lang), nullptr, &sp, nullptr, seed_, 0, &ptr, cap, &len, &frames, codes.data(),
+                                       F0 > 0 ? prefix_codes.data() : nullptr, F0 > 0 ? poffs : nullptr) != 0) {
+        std::cerr << "[TTSEngine] Synthesis error: " << q3tts_last_error(h_) << std::endl;
+        return {};
+    }
+    if (all_codes) all_codes->assign(codes.begin(), codes.begin() + (size_t)frames * G);
     pcm.resize((size_t)std::min<int64_t>(len, cap));
     return pcm;
 }

@@ -101,6 +101,16 @@ public:
     std::vector<float> synthesize_tokens_instruct(const std::vector<int64_t>& token_ids, const std::vector<int32_t>& instruct_text_ids,
                                                   const std::vector<float>& speaker_embed, Language lang = Language::Auto,
                                                   const SamplingParams& params = SamplingParams());
+    // Continue from codes (include/q3tts.h: q3tts_synthesize_continue_host; beside the reference's methods).  prefix_codes holds recorded
+    // frames, n_groups() ids each, frame-major: the utterance is generated as if these had been its first frames (the previous sentence
+    // of a document with its text in token_ids, the reference codes of an in-context clone, an utterance to resume), and the returned
+    // samples are those of the NEW frames only — they join the prefix's own audio without a seam.  all_codes (optional) receives prefix
+    // + new frames.  An empty prefix is synthesize_tokens.  max_new_tokens is lowered where prompt + prefix + max_new_tokens would pass
+    // the engine's context.
+    std::vector<float> synthesize_tokens_continue(const std::vector<int64_t>& token_ids, const std::vector<int64_t>& prefix_codes,
+                                                  Language lang = Language::Auto, const SamplingParams& params = SamplingParams(),
+                                                  std::vector<int64_t>* all_codes = nullptr);
+    int n_groups() const { return n_groups_; }
     bool has_speaker_encoder() const; // true when the weight file carries the spk.* tensors (reference: speaker_encoder.onnx present)
     bool is_ready() const { return ready_; }
     const std::string& get_error() const { return error_msg_; }
@@ -116,6 +126,7 @@ private:
     int spk_dim_ = 0;
     int cfg_hidden_ = 1024;
     int max_ctx_ = 0;
+    int n_groups_ = config::NUM_CODE_GROUPS;
 };
 
 inline int64_t language_to_codec_id(Language lang) { // reference src/tts_onnx.h:230-238

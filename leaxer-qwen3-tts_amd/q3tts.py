@@ -93,6 +93,7 @@ EXPORTS = [
     "q3tts_sample_hist_host", "q3tts_sample_hist_dev",
     "q3tts_codec_stream_push_batch_host", "q3tts_slots_codec_decode_new_host", "q3tts_synthesize_stream_host",
     "q3tts_build_prompt_instruct_host", "q3tts_frame_instruct_ids", "q3tts_synthesize_instruct_host",
+    "q3tts_frame_rows_host", "q3tts_slot_begin_codes", "q3tts_synthesize_continue_host",
 ]
 
 # q3tts_audio_cb: int (*)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished)
@@ -146,6 +147,9 @@ def lib():
     L.q3tts_synthesize_instruct_host.argtypes = [vp, i32, vp, vp, i32, vp, C.POINTER(Sampling), vp, C.c_uint64, i32, vp, i64, vp, vp, vp,
                                                  i32, AUDIO_CB, vp, vp, vp]
     L.q3tts_slot_begin.argtypes = [vp, i32, vp, i32, vp, i32, C.POINTER(Sampling), C.c_uint64, C.c_uint32, i32]
+    L.q3tts_slot_begin_codes.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, C.POINTER(Sampling), C.c_uint64, C.c_uint32, i32]
+    L.q3tts_frame_rows_host.argtypes = [vp, vp, i32, i32, vp, i32, vp]
+    L.q3tts_synthesize_continue_host.argtypes = [vp, i32, vp, vp, i32, vp, C.POINTER(Sampling), vp, C.c_uint64, i32, vp, i64, vp, vp, vp, vp, vp]
     L.q3tts_decode_steps.argtypes = [vp, i32]
     L.q3tts_slot_status.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.q3tts_slot_codes_host.argtypes = [vp, i32, vp, i32]
@@ -320,6 +324,33 @@ class Engine:
         self._ck(self.L.q3tts_cp_embed_host(self.h, int(tok), int(step), _p(out)))
         return out
 
+    def _frames(self, codes, what):
+        """codes as a contiguous int64 [n][n_groups] array"""
+        c = np.ascontiguousarray(codes, dtype=np.int64)
+        if c.size == 0:
+            return c.reshape(0, self.cfg.n_groups)
+        if c.ndim != 2 or c.shape[1] != self.cfg.n_groups:
+            raise ValueError("%s: expected [frames][%d] codes, got shape %s" % (what, self.cfg.n_groups, c.shape))
+        return c
+
+    def frame_rows(self, codes, frame0=0, trailing=None):
+        """talker input rows of given frames (q3tts_frame_rows_host): codes [n][n_groups] -> [n][hidden]; row i carries the text row
+        trailing[frame0 + i] while that index exists, then tts_pad — what the fused loop feeds the talker after sampling that frame"""
+        c = self._frames(codes, "frame_rows")
+        if int(frame0) < 0:
+            raise ValueError("frame_rows: frame0 must be >= 0")
+        out = np.empty((c.shape[0], self.cfg.hidden), np.float32)
+        if c.shape[0] == 0:
+            return out
+        t = None
+        if trailing is not None:
+            t = np.ascontiguousarray(trailing, dtype=np.float32)
+            if t.size and (t.ndim != 2 or t.shape[1] != self.cfg.hidden):
+                raise ValueError("frame_rows: trailing must be [rows][%d]" % self.cfg.hidden)
+        nt = 0 if t is None or t.size == 0 else t.shape[0]
+        self._ck(self.L.q3tts_frame_rows_host(self.h, _p(c), c.shape[0], int(frame0), _p(t) if nt else None, nt, _p(out)))
+        return out
+
     def prefill(self, embeds, slot=0):
         """run_prefill over embeds [S][hidden], 1 <= S <= max_ctx (more than 16 rows: the chunked long-prompt path)"""
         e = np.ascontiguousarray(embeds, dtype=np.float32)
@@ -484,11 +515,18 @@ class Engine:
         return prompt[: S.value].copy(), trailing[: nt.value].copy()
 
     # ---- fused generation ----
-    def slot_begin(self, slot, prompt, trailing, sp, seed=0, stream_id=0, ignore_eos=False):
+    def slot_begin(self, slot, prompt, trailing, sp, seed=0, stream_id=0, ignore_eos=False, prefix_codes=None):
+        """prefix_codes [F0][n_groups]: continue from codes (q3tts_slot_begin_codes) — the slot is armed as if it had generated exactly
+        these as its first F0 frames; sp.max_new_tokens counts the frames behind them"""
         p = np.ascontiguousarray(prompt, dtype=np.float32)
         t = np.ascontiguousarray(trailing, dtype=np.float32)
-        self._ck(self.L.q3tts_slot_begin(self.h, slot, _p(p), p.shape[0], _p(t), t.shape[0], C.byref(sp), seed,
-                                         stream_id, int(ignore_eos)))
+        if prefix_codes is None:
+            self._ck(self.L.q3tts_slot_begin(self.h, slot, _p(p), p.shape[0], _p(t), t.shape[0], C.byref(sp), seed,
+                                             stream_id, int(ignore_eos)))
+            return
+        c = self._frames(prefix_codes, "slot_begin(prefix_codes)")
+        self._ck(self.L.q3tts_slot_begin_codes(self.h, slot, _p(p), p.shape[0], _p(t), t.shape[0], _p(c) if c.shape[0] else None, c.shape[0],
+                                               C.byref(sp), seed, stream_id, int(ignore_eos)))
 
     def decode_steps(self, n):
         return self._ck(self.L.q3tts_decode_steps(self.h, n))
@@ -645,6 +683,44 @@ class Engine:
         outs = [pcm[i][: pcm_len[i]] for i in range(n)]
         cl = [codes[i, : nfr[i]] for i in range(n)] if want_codes else None
         return outs, cl, nfr
+
+    def synthesize_continue(self, token_lists, prefix_codes, sp, lang=0, seed=0, ignore_eos=False, speakers=None, max_new_per_utt=None):
+        """synthesize_batch with teacher-forced frames per utterance (q3tts_synthesize_continue_host): prefix_codes holds one
+        [F0_u][n_groups] array (or None / empty: no prefix) per utterance.  Returns (pcm, codes, n_frames): codes[u] and n_frames[u]
+        cover prefix + new frames, pcm[u] holds the NEW frames' samples only (they join the prefix's audio without a seam)."""
+        n = len(token_lists)
+        if prefix_codes is None or len(prefix_codes) != n:
+            raise ValueError("prefix_codes: one entry (codes or None) per utterance")
+        pres = [self._frames(np.zeros((0, self.cfg.n_groups), np.int64) if c_ is None else c_, "synthesize_continue(prefix_codes)") for c_ in prefix_codes]
+        poffs = np.zeros(n + 1, np.int32)
+        poffs[1:] = np.cumsum([c_.shape[0] for c_ in pres])
+        pflat = np.ascontiguousarray(np.concatenate(pres + [np.zeros((1, self.cfg.n_groups), np.int64)]))   # never empty: a valid pointer
+        P = max(c_.shape[0] for c_ in pres) if n else 0
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int64) for t in token_lists]))
+        offs = np.zeros(n + 1, np.int32)
+        offs[1:] = np.cumsum([len(t) for t in token_lists])
+        cap = self.codec_decode_len(P + sp.max_new_tokens)
+        pcm = [np.zeros(cap, np.float32) for _ in range(n)]
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in pcm])
+        pcm_len = np.zeros(n, np.int64)
+        nfr = np.zeros(n, np.int32)
+        codes = np.zeros((n, P + sp.max_new_tokens, self.cfg.n_groups), np.int64)
+        spk_keep, spk_ptrs = [], None
+        if speakers is not None:
+            if len(speakers) != n:
+                raise ValueError("speakers: one entry (embedding or None) per utterance")
+            spk_keep = [None if s_ is None else np.ascontiguousarray(s_, np.float32) for s_ in speakers]
+            for a in spk_keep:
+                if a is not None and a.size != self.cfg.hidden:
+                    raise ValueError("speaker embedding has %d values, the model needs %d" % (a.size, self.cfg.hidden))
+            spk_ptrs = C.cast((C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in spk_keep]), C.c_void_p)
+        caps = None if max_new_per_utt is None else np.ascontiguousarray(max_new_per_utt, np.int32)
+        if caps is not None and caps.shape != (n,):
+            raise ValueError("max_new_per_utt: one entry per utterance")
+        self._ck(self.L.q3tts_synthesize_continue_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
+                                                       seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr), _p(codes),
+                                                       _p(pflat), _p(poffs)))
+        return [pcm[i][: pcm_len[i]] for i in range(n)], [codes[i, : nfr[i]] for i in range(n)], nfr
 
     def synthesize_stream(self, token_lists, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
                           max_new_per_utt=None, instructs=None):
@@ -903,6 +979,26 @@ def frame_instruct_ids(text_ids):
     out = np.zeros(n, np.int64)
     L.q3tts_frame_instruct_ids(_p(t) if t.size else None, t.size, _p(out), n)
     return out
+
+
+def save_codes(path, codes):
+    """the text format of leaxer-tts --save-codes / --continue-codes: one frame per line, n_groups integers.  Host-only."""
+    c = np.asarray(codes, np.int64)
+    if c.ndim != 2:
+        raise ValueError("save_codes: expected [frames][n_groups]")
+    with open(path, "w") as f:
+        for row in c:
+            f.write(" ".join(str(int(v)) for v in row) + "\n")
+
+
+def load_codes(path):
+    """reads what save_codes / leaxer-tts --save-codes wrote: int64 [frames][n_groups].  Host-only."""
+    rows = [[int(v) for v in line.replace(",", " ").split()] for line in open(path) if line.strip()]
+    if not rows:
+        return np.zeros((0, 0), np.int64)
+    if any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError("load_codes: lines of different lengths in %s" % path)
+    return np.array(rows, np.int64)
 
 
 def rng_uniform(seed, stream, frame, group):
