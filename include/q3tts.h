@@ -353,6 +353,40 @@ int q3tts_synthesize_continue_host(q3tts_engine* e, int n_utt, const int64_t* id
                                    const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                    float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                    const int64_t* prefix_codes, const int32_t* prefix_offsets);
+/* ---- shared prompt prefix: run_prefill (tts_onnx.cpp:615-665) once for rows that many utterances have in front of their prompts ----
+ * A prefix is n_rows talker input rows (an instruction's text_project rows, say), 1 <= n_rows < max_ctx, prefilled once in a borrowed
+ * free slot; the K / V rows of its positions are kept on the engine in a compact store.  Slots begun behind it get a COPY of those rows
+ * in their own pages (no page is shared: a slot owns pages for prefix + prompt + frames like any slot) and only their own rows are
+ * prefilled, at base position n_rows; causality makes that exact (the rows of positions [0, P) depend on rows [0, P) alone).  Up to 64
+ * prefixes are live at a time; ids are never reused.  Nothing is changed when a call fails (no free slot, pool too small, 65th prefix). */
+int q3tts_prefix_create(q3tts_engine* e, const float* rows, int n_rows, int* prefix_id);   /* run_prefill, tts_onnx.cpp:615-665 */
+/* text_project (tts_onnx.cpp:615-665 consumes its rows) of framed instruction ids (q3tts_frame_instruct_ids), then q3tts_prefix_create */
+int q3tts_prefix_create_instruct(q3tts_engine* e, const int64_t* framed_ids, int n, int* prefix_id);
+/* n_rows and the bytes of the store: n_rows x n_layers x n_kv_heads x head_dim x 2 (K and V) x element size (4, or 2 with Q3TTS_FLAG_KV_BF16) */
+int q3tts_prefix_info(q3tts_engine* e, int prefix_id, int* n_rows, int64_t* bytes);
+/* frees the store; refused while a running q3tts_synthesize_prefixed_host job uses the prefix (its callback may try) */
+int q3tts_prefix_release(q3tts_engine* e, int prefix_id);
+/* q3tts_slot_begin / q3tts_slot_begin_codes behind prefix prefix_id (-1: none, then exactly those entries; run_prefill,
+ * tts_onnx.cpp:615-665, for the prompt's rows at base P).  P + S + n_prefix_frames + max_new_tokens <= max_ctx.  The slot's frames,
+ * status and codes are as without a prefix; its context starts at P + S (+ n_prefix_frames). */
+int q3tts_slot_begin_prefixed(q3tts_engine* e, int slot, int prefix_id, const float* prompt, int S, const float* trailing, int n_trailing,
+                              const int64_t* prefix_codes, int n_prefix_frames, const q3tts_sampling* p, uint64_t seed, uint32_t stream_id, int ignore_eos);
+/* n slots at once (run_prefill, tts_onnx.cpp:615-665, batched): everything is validated first (ids live, lengths, slots distinct), pages
+ * are reserved all or nothing, each prefix is copied into its slots in one launch, and members with equal S <= 16 share one pass through
+ * the talker (up to 128 rows, each member at its own base; a member with prefix_ids[i] == -1 sits at base 0).  Members with S > 16, and
+ * engines whose dims are not multiples of 128, are begun one at a time.  prefix_ids == NULL or all -1: q3tts_slot_begin's launches. */
+int q3tts_slots_begin_prefixed(q3tts_engine* e, int n, const int32_t* slots, const int32_t* prefix_ids, const float* const* prompts, const int32_t* S,
+                               const float* const* trailing, const int32_t* n_trailing, const q3tts_sampling* p, uint64_t seed,
+                               const uint32_t* stream_ids, int ignore_eos);
+/* q3tts_synthesize_instruct_host with prefix_ids[n_utt] (-1: none) in place of the instruction ranges (run_prefill, tts_onnx.cpp:615-665,
+ * per utterance only for its own rows): utterance u's prompt is q3tts_build_prompt_host's, begun behind prefix prefix_ids[u].  Utterances
+ * admitted in the same look with equal S share their pass; a preempted utterance is re-admitted through the same prefixed begin; the
+ * job's prefixes cannot be released while it runs.  cb as in q3tts_synthesize_instruct_host.  Results do not depend on the schedule
+ * (RNG stream = utterance index). */
+int q3tts_synthesize_prefixed_host(q3tts_engine* e, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                                   int chunk_frames, q3tts_audio_cb cb, void* user, const int32_t* prefix_ids);
 /* io::read_wav (src/io/wav_reader.h:13, wav_reader.cpp:28-143): mono float samples; -1 when the reference
  * returns an empty vector.  Call with out == NULL to learn *n_samples. */
 int q3tts_read_wav_host(const char* path, float* out, int64_t cap, int64_t* n_samples, int32_t* sample_rate);

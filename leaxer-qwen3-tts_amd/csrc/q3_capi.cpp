@@ -402,6 +402,65 @@ int q3tts_slot_begin_codes(q3tts_engine* h, int slot, const float* prompt, int S
     return 0;
     Q3_API_END(h)
 }
+// ---- shared prompt prefix (run_prefill, tts_onnx.cpp:615-665, once for many utterances): Engine::prefix_create / slots_begin_prefixed ----
+int q3tts_prefix_create(q3tts_engine* h, const float* rows, int n_rows, int* prefix_id) {
+    Q3_API_BEGIN(h)
+    if (!prefix_id) throw q3::Error("prefix_create: null output");
+    *prefix_id = h->e->prefix_create(rows, n_rows);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_prefix_create_instruct(q3tts_engine* h, const int64_t* framed_ids, int n, int* prefix_id) {
+    Q3_API_BEGIN(h)
+    if (!prefix_id || !framed_ids) throw q3::Error("prefix_create_instruct: null argument");
+    if (n < 1 || n >= h->e->max_ctx) throw q3::Error("prefix_create: 1 <= rows < max_ctx");
+    std::vector<float> rows((size_t)n * (size_t)h->e->c.hidden);
+    h->e->text_project(framed_ids, n, rows.data());
+    *prefix_id = h->e->prefix_create(rows.data(), n);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_prefix_info(q3tts_engine* h, int prefix_id, int* n_rows, int64_t* bytes) {
+    Q3_API_BEGIN(h)
+    const Engine::Prefix& pf = h->e->prefix_get(prefix_id);
+    if (n_rows) *n_rows = pf.P;
+    if (bytes) *bytes = pf.bytes;
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_prefix_release(q3tts_engine* h, int prefix_id) {
+    Q3_API_BEGIN(h) h->e->prefix_release(prefix_id); return 0; Q3_API_END(h)
+}
+int q3tts_slot_begin_prefixed(q3tts_engine* h, int slot, int prefix_id, const float* prompt, int S, const float* trailing, int n_trailing,
+                              const int64_t* prefix_codes, int n_prefix_frames, const q3tts_sampling* p, uint64_t seed, uint32_t stream_id, int ignore_eos) {
+    Q3_API_BEGIN(h)
+    if (!p) throw q3::Error("slot_begin_prefixed: null argument");
+    Engine::SlotInit in;
+    in.slot = slot; in.prompt = prompt; in.S = S; in.trailing = trailing; in.n_trailing = n_trailing; in.stream_id = stream_id;
+    in.prefix = prefix_codes; in.n_prefix = n_prefix_frames; in.prefix_id = prefix_id;
+    h->e->slots_begin_prefixed(&in, 1, *p, seed, ignore_eos);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_slots_begin_prefixed(q3tts_engine* h, int n, const int32_t* slots, const int32_t* prefix_ids, const float* const* prompts, const int32_t* S,
+                               const float* const* trailing, const int32_t* n_trailing, const q3tts_sampling* p, uint64_t seed,
+                               const uint32_t* stream_ids, int ignore_eos) {
+    Q3_API_BEGIN(h)
+    if (n < 1) return 0;
+    if (!p || !slots || !prompts || !S) throw q3::Error("slots_begin_prefixed: null argument");
+    std::vector<Engine::SlotInit> in((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        Engine::SlotInit& q = in[(size_t)i];
+        q.slot = slots[i]; q.prompt = prompts[i]; q.S = S[i];
+        q.n_trailing = n_trailing ? n_trailing[i] : 0; q.trailing = trailing && q.n_trailing > 0 ? trailing[i] : nullptr;
+        if (q.n_trailing > 0 && !q.trailing) throw q3::Error("slots_begin_prefixed: trailing rows announced but not given");
+        q.stream_id = stream_ids ? stream_ids[i] : (uint32_t)i;
+        q.prefix_id = prefix_ids ? prefix_ids[i] : -1;
+    }
+    h->e->slots_begin_prefixed(in.data(), n, *p, seed, ignore_eos);
+    return 0;
+    Q3_API_END(h)
+}
 int q3tts_decode_steps(q3tts_engine* h, int n_steps) {
     Q3_API_BEGIN(h) return h->e->decode_steps(n_steps); Q3_API_END(h)
 }
@@ -510,12 +569,33 @@ static void assemble_prompts(Engine& e, int n_utt, const int64_t* ids, const int
 static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
-                                  int chunk_frames, q3tts_audio_cb cb, void* user, const int64_t* instruct_ids, const int32_t* instruct_offsets);
+                                  int chunk_frames, q3tts_audio_cb cb, void* user, const int64_t* instruct_ids, const int32_t* instruct_offsets,
+                                  const int32_t* prefix_ids = nullptr);
 static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                     const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                     float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
                                     int64_t* codes_out, const int64_t* instruct_ids, const int32_t* instruct_offsets,
-                                    const int64_t* prefix_codes = nullptr, const int32_t* prefix_offsets = nullptr);
+                                    const int64_t* prefix_codes = nullptr, const int32_t* prefix_offsets = nullptr, const int32_t* prefix_ids = nullptr);
+
+// The job's shared prompt prefixes (q3tts_synthesize_prefixed_host): validated up front, held against q3tts_prefix_release while the job runs
+struct PrefixHold {
+    Engine& e; std::vector<int> ids;
+    PrefixHold(Engine& en, const int32_t* prefix_ids, int n_utt) : e(en) {
+        for (int u = 0; prefix_ids && u < n_utt; ++u) if (prefix_ids[u] != -1) (void)e.prefix_get(prefix_ids[u]);   // throws on an unknown id, nothing held yet
+        for (int u = 0; prefix_ids && u < n_utt; ++u) if (prefix_ids[u] != -1) { e.prefix_pin(prefix_ids[u], 1); ids.push_back(prefix_ids[u]); }
+    }
+    ~PrefixHold() { for (int id : ids) { try { e.prefix_pin(id, -1); } catch (...) { } } }
+};
+
+int q3tts_synthesize_prefixed_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                                   int chunk_frames, q3tts_audio_cb cb, void* user, const int32_t* prefix_ids) {
+    if (!cb) return synthesize_schedule_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
+                                             nullptr, nullptr, nullptr, nullptr, prefix_ids);
+    return synthesize_stream_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
+                                  chunk_frames, cb, user, nullptr, nullptr, prefix_ids);
+}
 
 int q3tts_synthesize_schedule_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                    const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
@@ -547,7 +627,7 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
                                     const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                     float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
                                     int64_t* codes_out, const int64_t* instruct_ids, const int32_t* instruct_offsets,
-                                    const int64_t* prefix_codes, const int32_t* prefix_offsets) {
+                                    const int64_t* prefix_codes, const int32_t* prefix_offsets, const int32_t* prefix_ids) {
     Q3_API_BEGIN(h)
     Engine& e = *h->e;
     const int H = e.c.hidden, G = e.c.n_groups, B = e.B;
@@ -555,6 +635,9 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
     if (!ids || !offsets || !p) throw q3::Error("synthesize: null argument");
     if (pcm_cap < 0) throw q3::Error("synthesize: negative pcm_cap");
     (void)Engine::checked_penalty(*p);   // refused before any slot is touched
+    PrefixHold hold(e, prefix_ids, n_utt);
+    // rows of the shared prompt prefix in front of utterance u's prompt (0 without one): part of its context, not of prep[u].S
+    auto pl = [&](int u) { return prefix_ids && prefix_ids[u] != -1 ? e.prefix_get(prefix_ids[u]).P : 0; };
     // teacher-forced frames per utterance (q3tts_synthesize_continue_host): pf(u) of them behind utterance u's prompt, P the longest
     if (prefix_codes && !prefix_offsets) throw q3::Error("synthesize: prefix_codes without prefix_offsets");
     auto pf = [&](int u) { return prefix_codes ? (int)(prefix_offsets[u + 1] - prefix_offsets[u]) : 0; };
@@ -584,9 +667,9 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
     std::deque<int> pending;
     auto cap_of = [&](int u) { return max_new_per_utt ? std::min(std::max(1, (int)max_new_per_utt[u]), p->max_new_tokens) : p->max_new_tokens; };
     for (int u = 0; u < n_utt; ++u) {
-        if (pf(u) > 0 && prep[(size_t)u].S + pf(u) + p->max_new_tokens > e.max_ctx)
-            throw q3::Error("synthesize: utterance " + std::to_string(u) + ": prompt + prefix frames + max_new_tokens exceeds max_ctx");
-        if (e.kv_pages_for(prep[(size_t)u].S + pf(u) + cap_of(u)) > e.kv_total_pages())
+        if ((pf(u) > 0 || pl(u) > 0) && pl(u) + prep[(size_t)u].S + pf(u) + p->max_new_tokens > e.max_ctx)
+            throw q3::Error("synthesize: utterance " + std::to_string(u) + ": prefix + prompt + prefix frames + max_new_tokens exceeds max_ctx");
+        if (e.kv_pages_for(pl(u) + prep[(size_t)u].S + pf(u) + cap_of(u)) > e.kv_total_pages())
             throw q3::Error("synthesize: one utterance (prompt + max_new_tokens) needs more KV pages than the pool holds");
         pending.push_back(u);
     }
@@ -607,8 +690,8 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
                 std::vector<int> free_slots, need;
                 for (int b = 0; b < B; ++b) if (slot_utt[(size_t)b] < 0) free_slots.push_back(b);
                 for (size_t i = 0; i < pending.size() && i < free_slots.size(); ++i) {
-                    const int u = pending[i], all = prep[(size_t)u].S + pf(u) + cap_of(u);
-                    int pages = e.kv_pages_for(reserve_all ? all : std::min(all, prep[(size_t)u].S + pf(u) + first_look));
+                    const int u = pending[i], all = pl(u) + prep[(size_t)u].S + pf(u) + cap_of(u);
+                    int pages = e.kv_pages_for(reserve_all ? all : std::min(all, pl(u) + prep[(size_t)u].S + pf(u) + first_look));
                     if (hold_pages[(size_t)u] > 0 && n_retired == hold_mark[(size_t)u] && live > 0) pages = std::max(pages, std::min(hold_pages[(size_t)u], e.kv_total_pages()));
                     need.push_back(pages);
                 }
@@ -624,14 +707,18 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
                     q.slot = b; q.prompt = prompts.data() + pr.poff * H; q.S = pr.S; q.trailing = trailing.data() + pr.toff * H; q.n_trailing = pr.nt;
                     q.stream_id = (uint32_t)u;
                     q.max_frames = max_new_per_utt ? std::max(1, (int)max_new_per_utt[u]) : 0;
-                    q.kv_tokens = reserve_all ? 0 : pr.S + pf(u) + first_look;
+                    q.kv_tokens = reserve_all ? 0 : pl(u) + pr.S + pf(u) + first_look;
+                    if (prefix_ids) q.prefix_id = prefix_ids[u];
                     if (pf(u) > 0) {   // forced begin, on its own (a re-admission after a preemption too); the slot starts pf(u) frames in
                         q.prefix = pcodes(u); q.n_prefix = pf(u);
                         e.slots_begin(&q, 1, *p, seed, ignore_eos);
                         done_frames[(size_t)b] = pf(u);
                     } else init.push_back(q);
                 }
-                if (!init.empty()) e.slots_begin(init.data(), (int)init.size(), *p, seed, ignore_eos);   // equal-length prompts in consecutive slots share one prefill pass
+                if (!init.empty()) {   // equal-length prompts share one prefill pass (behind their prefixes: at per-member bases)
+                    if (prefix_ids) e.slots_begin_prefixed(init.data(), (int)init.size(), *p, seed, ignore_eos);
+                    else e.slots_begin(init.data(), (int)init.size(), *p, seed, ignore_eos);
+                }
                 live += (int)fresh.size();
                 e.sched_admitted += (int64_t)fresh.size();
                 e.sched_peak_live = std::max(e.sched_peak_live, live);
@@ -657,12 +744,12 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
                     return done_frames[(size_t)x] != done_frames[(size_t)y] ? done_frames[(size_t)x] > done_frames[(size_t)y] : slot_utt[(size_t)x] < slot_utt[(size_t)y]; });
                 for (int b : order) {
                     const int u = slot_utt[(size_t)b];
-                    want.push_back(std::min(prep[(size_t)u].S + pf(u) + cap_of(u), prep[(size_t)u].S + done_frames[(size_t)b] + steps));
+                    want.push_back(pl(u) + std::min(prep[(size_t)u].S + pf(u) + cap_of(u), prep[(size_t)u].S + done_frames[(size_t)b] + steps));
                 }
                 const std::vector<int> victims = q3::sched_grow(e.kv, order, want, &changed);
                 for (int vb : victims) {          // youngest first: pushed to the front one by one, the oldest of them ends up first in the queue
                     const int vu = slot_utt[(size_t)vb];
-                    hold_pages[(size_t)vu] = e.kv_pages_for(prep[(size_t)vu].S + done_frames[(size_t)vb]) + 1;
+                    hold_pages[(size_t)vu] = e.kv_pages_for(pl(vu) + prep[(size_t)vu].S + done_frames[(size_t)vb]) + 1;
                     hold_mark[(size_t)vu] = n_retired;
                     e.slot_release(vb);           // deactivates the slot (its pages are already back in the pool)
                     pending.push_front(vu);
@@ -735,7 +822,8 @@ int q3tts_synthesize_stream_host(q3tts_engine* h, int n_utt, const int64_t* ids,
 static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
-                                  int chunk_frames, q3tts_audio_cb cb, void* user, const int64_t* instruct_ids, const int32_t* instruct_offsets) {
+                                  int chunk_frames, q3tts_audio_cb cb, void* user, const int64_t* instruct_ids, const int32_t* instruct_offsets,
+                                  const int32_t* prefix_ids) {
     Q3_API_BEGIN(h)
     Engine& e = *h->e;
     const int H = e.c.hidden, G = e.c.n_groups, B = e.B;
@@ -745,6 +833,8 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     if (chunk_frames < 1) throw q3::Error("synthesize_stream: chunk_frames must be positive");
     if (pcm_cap < 0) throw q3::Error("synthesize: negative pcm_cap");
     (void)Engine::checked_penalty(*p);
+    PrefixHold hold(e, prefix_ids, n_utt);
+    auto pl = [&](int u) { return prefix_ids && prefix_ids[u] != -1 ? e.prefix_get(prefix_ids[u]).P : 0; };   // rows of utterance u's shared prefix
     for (int b = 0; b < B; ++b) e.slot_release(b);
     std::vector<Prep> prep;
     std::vector<float> prompts, trailing;
@@ -752,7 +842,9 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     auto cap_of = [&](int u) { return max_new_per_utt ? std::min(std::max(1, (int)max_new_per_utt[u]), p->max_new_tokens) : p->max_new_tokens; };
     std::deque<int> pending;
     for (int u = 0; u < n_utt; ++u) {
-        if (e.kv_pages_for(prep[(size_t)u].S + cap_of(u)) > e.kv_total_pages())
+        if (pl(u) > 0 && pl(u) + prep[(size_t)u].S + p->max_new_tokens > e.max_ctx)
+            throw q3::Error("synthesize: utterance " + std::to_string(u) + ": prefix + prompt + max_new_tokens exceeds max_ctx");
+        if (e.kv_pages_for(pl(u) + prep[(size_t)u].S + cap_of(u)) > e.kv_total_pages())
             throw q3::Error("synthesize: one utterance (prompt + max_new_tokens) needs more KV pages than the pool holds");
         pending.push_back(u);
         if (pcm_len) pcm_len[u] = 0;
@@ -775,7 +867,7 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
             {   // admission in queue order, every utterance with the pages of its whole length
                 std::vector<int> free_slots, need;
                 for (int b = 0; b < B; ++b) if (slot_utt[(size_t)b] < 0) free_slots.push_back(b);
-                for (size_t i = 0; i < pending.size() && i < free_slots.size(); ++i) need.push_back(e.kv_pages_for(prep[(size_t)pending[i]].S + cap_of(pending[i])));
+                for (size_t i = 0; i < pending.size() && i < free_slots.size(); ++i) need.push_back(e.kv_pages_for(pl(pending[i]) + prep[(size_t)pending[i]].S + cap_of(pending[i])));
                 const int n_adm = q3::sched_admit_count(e.kv, need, (int)free_slots.size(), live, true);
                 for (int i = 0; i < n_adm; ++i) { slot_utt[(size_t)free_slots[(size_t)i]] = pending.front(); pending.pop_front(); fresh.push_back(free_slots[(size_t)i]); }
             }
@@ -789,8 +881,10 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
                     q.stream_id = (uint32_t)u;
                     q.max_frames = max_new_per_utt ? std::max(1, (int)max_new_per_utt[u]) : 0;
                     q.kv_tokens = 0;   // prompt + cap, reserved now
+                    if (prefix_ids) q.prefix_id = prefix_ids[u];
                 }
-                e.slots_begin(init.data(), (int)init.size(), *p, seed, ignore_eos);
+                if (prefix_ids) e.slots_begin_prefixed(init.data(), (int)init.size(), *p, seed, ignore_eos);
+                else e.slots_begin(init.data(), (int)init.size(), *p, seed, ignore_eos);
                 live += (int)fresh.size();
                 e.sched_admitted += (int64_t)fresh.size();
                 e.sched_peak_live = std::max(e.sched_peak_live, live);

@@ -166,8 +166,21 @@ void launch_attn_combine(const AttnArgs& a, hipStream_t s); // partials -> a.out
 // Long-prompt prefill (run_prefill, reference tts_onnx.cpp:615-665, past 16 rows): a chunk of n_new <= 128 rows of ONE slot (nb = 1, slot =
 // slot_offset) at the host-known position pos_scalar.  Two launches: the rows' K / V appended (k_attn's prologue, same rounding point),
 // then causal attention of every row over cache tokens [0, pos_scalar + its index] read from the cache alone.  n_splits = 1: normalised
-// rows (out) and / or planes (oh, ol)
+// rows (out) and / or planes (oh, ol).  Group form (slots begun behind a shared prefix): nb members of n_new <= 16 rows, nb * n_new <= 128,
+// member bi in slot slot_map[bi] (slot_offset + bi without a map) at its own base pos_dev[bi] (device); pos_scalar then carries the
+// largest of those bases for the launch's bounds check
 void launch_attn_prefill(const AttnArgs& a, hipStream_t s);
+// KV rows of positions [0, P) between a slot's pages and a compact store [layer][kvh][P][d] (k_kv_prefix_copy)
+struct KvPrefixCopyArgs {
+    void* kcache = nullptr; void* vcache = nullptr;   // [page][layer][kvh][64][d], either element type
+    void* kstore = nullptr; void* vstore = nullptr;   // [layer][kvh][P][d], the same element type
+    const int* page_table = nullptr; int pages_per_slot = 0;
+    const int* slots = nullptr; int n_dst = 1;         // scatter: the destination slots (device); gather: null, one source slot0
+    int slot0 = 0, scatter = 0;
+    int n_lk = 0;                                      // n_layers * n_kv_heads
+    int P = 0, row16 = 0;                              // positions; 16-byte units per token row
+};
+void launch_kv_prefix_copy(const KvPrefixCopyArgs& a, hipStream_t s);
 
 // Skinny-M bf16-MFMA GEMM (q3_gemm_kernels.hip): activations as (hi, lo) bf16 planes, fp32 accumulate
 struct GemmArgs {
@@ -221,7 +234,8 @@ struct SlotState { // device-resident per-slot generation state
     uint32_t stream_id;
     float rep_penalty;    // repetition penalty on code0 (group 0 sampler); 0 and 1 = off
     uint64_t seed;
-    uint32_t pad1[2]; // 64 bytes: read by the sampler as four 16-byte loads
+    int32_t prefix_len;   // rows of a shared prompt prefix in front of the prompt (0: none): the talker position is prefix_len + prompt_len + frame
+    uint32_t pad1;    // 64 bytes: read by the sampler as four 16-byte loads
 };
 static_assert(sizeof(SlotState) == 64, "SlotState must be 64 bytes");
 

@@ -1888,7 +1888,11 @@ void launch_attn_combine(const AttnArgs& a, hipStream_t s) {
 
 // ================================================================================================
 // Long-prompt prefill attention (run_prefill over a prompt of more than ATT_MAX_NEW rows, reference src/tts_onnx.cpp:615-665): one chunk
-// of n_new <= 128 rows of ONE slot, starting at cache position base = pos_scalar.  Two launches per layer.
+// of n_new <= 128 rows of ONE slot, starting at cache position base = pos_scalar, or a GROUP of nb members of n_new <= 16 rows each
+// (nb * n_new <= 128; prefixed begin): member bi = blockIdx.z belongs to slot slot_map[bi] (slot_offset + bi without a map), starts at
+// its own base pos_dev[bi] and owns qkv / out rows bi * n_new + row.  Slot, base, last position, page count and page-table row are
+// workgroup-uniform scalars read once; nb = 1 with pos_scalar is member 0 at row offset 0 — the same loads, sums and stores in the
+// same order as the one-slot form.  A member whose device base does not fit the slot's pages is skipped whole.  Two launches per layer.
 //   k_prefill_append — workgroup (one wave) = (kv head, new row j): k_attn's prologue for a key (split-K slabs summed in slab order,
 //     RMSNorm with k_norm, RoPE at base + j, bf16 rounding under kv_bf16 / kv_round) and the K / V rows stored at position base + j.
 //   k_attn_prefill — workgroup = (kv head, tile of TQ query rows): the tile's q heads through RMSNorm + RoPE into LDS, then the cache
@@ -1902,13 +1906,19 @@ void launch_attn_combine(const AttnArgs& a, hipStream_t s) {
 template <int D, bool KVB>
 __global__ __launch_bounds__(64) void k_prefill_append(const int* ppage_table, const float* pqkv, const float* pcos, const float* psin, AttnArgs a) {
     constexpr int HALF = D / 2;
-    const int kvh = blockIdx.x, j = blockIdx.y, lane = threadIdx.x;
-    const int p = a.pos_scalar + j;
+    const int kvh = blockIdx.x, j = blockIdx.y, bi = blockIdx.z, lane = threadIdx.x;
+    const int slot = a.slot_map ? a.slot_map[bi] : a.slot_offset + bi;
     const int pshift = a.page_shift, page_tokens = 1 << pshift;
-    const int page = ppage_table[(size_t)a.slot_offset * a.pages_per_slot + (p >> pshift)];
+    int base = a.pos_scalar;
+    if (a.pos_dev) {
+        base = a.pos_dev[bi];
+        if (base < 0 || base + a.n_new > (a.pages_per_slot << pshift)) return;
+    }
+    const int p = base + j;
+    const int page = ppage_table[(size_t)slot * a.pages_per_slot + (p >> pshift)];
     const size_t off = ((((size_t)page * a.n_layers + a.layer) * a.nkv + kvh) * page_tokens + (p & (page_tokens - 1))) * D;
     const int hl = lane < HALF ? lane : 0;
-    const float* rowp = pqkv + (size_t)j * a.ld_qkv;
+    const float* rowp = pqkv + ((size_t)bi * a.n_new + j) * a.ld_qkv;
     const float* ks = rowp + (a.nq + kvh) * D;
     const float* vs = rowp + (a.nq + a.nkv + kvh) * D;
     float x0 = ks[hl], x1 = ks[hl + HALF], v0 = vs[hl], v1 = vs[hl + HALF];
@@ -1950,18 +1960,25 @@ __global__ __launch_bounds__(256) void k_attn_prefill(const int* ppage_table, co
     __shared__ __attribute__((aligned(16))) float q_s[TQ * G][D];
     __shared__ float k_s[64 * KS];
     __shared__ __attribute__((aligned(16))) float p_s[4][NP][64];
-    const int kvh = blockIdx.x, r0 = blockIdx.y * TQ;
+    const int kvh = blockIdx.x, r0 = blockIdx.y * TQ, bi = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = a.nq / a.nkv, base = a.pos_scalar, n_new = a.n_new;
-    const int* pt = ppage_table + (size_t)a.slot_offset * a.pages_per_slot;
+    const int grp = a.nq / a.nkv, n_new = a.n_new;
+    const int slot = a.slot_map ? a.slot_map[bi] : a.slot_offset + bi;
+    int base = a.pos_scalar;
+    if (a.pos_dev) {
+        base = a.pos_dev[bi];
+        if (base < 0 || base + n_new > (a.pages_per_slot << 6)) return;   // before any barrier: the whole workgroup leaves
+    }
+    const int* pt = ppage_table + (size_t)slot * a.pages_per_slot;
+    const size_t rb = (size_t)bi * n_new;   // the member's first qkv / out row
 
     // ---- the tile's query heads: slabs summed in slab order, RMSNorm, RoPE (rows past the chunk and heads past the group repeat the last) ----
     const int hl = lane < HALF ? lane : 0;
     for (int v = wave; v < TQ * G; v += 4) {
         const int r = v / G, h = v % G;
         const int row = r0 + r < n_new ? r0 + r : n_new - 1, hh = h < grp ? h : grp - 1;
-        const float* src = pqkv + (size_t)row * a.ld_qkv + (kvh * grp + hh) * D;
+        const float* src = pqkv + (rb + row) * a.ld_qkv + (kvh * grp + hh) * D;
         float x0 = src[hl], x1 = src[hl + HALF];
         for (int sb = 1; sb < a.qkv_nslab; ++sb) {
             const size_t so = (size_t)sb * a.qkv_slab_stride;
@@ -2076,14 +2093,14 @@ __global__ __launch_bounds__(256) void k_attn_prefill(const int* ppage_table, co
             const int e = lane + 64 * k;
             if (e >= D) continue;
             const float ov = o[q][k] / l[q];
-            if (a.out) a.out[(size_t)row * a.ld_out + head * D + e] = ov;
+            if (a.out) a.out[(rb + row) * a.ld_out + head * D + e] = ov;
             if (a.oh) {
                 const uint32_t u = __float_as_uint(ov);
                 const bf16_t hi = (bf16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
                 const float rem = ov - __uint_as_float((uint32_t)hi << 16);
                 const uint32_t w = __float_as_uint(rem);
-                a.oh[(size_t)row * a.ldp + head * D + e] = hi;
-                a.ol[(size_t)row * a.ldp + head * D + e] = (bf16_t)((w + 0x7FFFu + ((w >> 16) & 1u)) >> 16);
+                a.oh[(rb + row) * a.ldp + head * D + e] = hi;
+                a.ol[(rb + row) * a.ldp + head * D + e] = (bf16_t)((w + 0x7FFFu + ((w >> 16) & 1u)) >> 16);
             }
         }
     }
@@ -2092,17 +2109,20 @@ __global__ __launch_bounds__(256) void k_attn_prefill(const int* ppage_table, co
 void launch_attn_prefill(const AttnArgs& a, hipStream_t s) {
     const int grp = a.nkv > 0 ? a.nq / a.nkv : 0;
     if (grp < 1 || grp > ATT_MAX_GRP || a.nq % a.nkv) throw Error("attn (prefill): unsupported GQA group size");
-    if (a.nb != 1 || a.n_new < 1 || a.n_new > 128) throw Error("attn (prefill): one slot, 1..128 new rows per launch");
-    if (!a.new_from_raw || a.window != 0 || a.pos_dev != nullptr || a.slot_map != nullptr || a.ssq_in != nullptr || a.n_splits != 1 || a.po != nullptr)
-        throw Error("attn (prefill): raw rows at a host-known position, no window, no slot map, no deferred RMSNorm, no split-T partials");
+    if (a.nb < 1 || a.n_new < 1 || a.nb * a.n_new > 128 || (a.nb > 1 && a.n_new > ATT_MAX_NEW))
+        throw Error("attn (prefill): one slot with 1..128 new rows, or a group of members with up to 16 rows each and 128 in all");
+    if ((a.nb > 1 || a.slot_map != nullptr) && a.pos_dev == nullptr) throw Error("attn (prefill): a group takes its members' bases from pos_dev");
+    if (!a.new_from_raw || a.window != 0 || a.ssq_in != nullptr || a.n_splits != 1 || a.po != nullptr)
+        throw Error("attn (prefill): raw rows, no window, no deferred RMSNorm, no split-T partials");
     if (a.page_shift != 6) throw Error("attn (prefill): 64-token KV pages");
+    // pos_dev: pos_scalar carries the largest base of the group (host-known), the kernels skip a member whose device base does not fit
     if (a.pos_scalar < 0 || a.pos_scalar + a.n_new > (a.pages_per_slot << 6)) throw Error("attn (prefill): rows past the slot's pages");
     if (a.qkv_nslab < 1 || a.qkv_nslab > 4) throw Error("attn (prefill): 1..4 QKV slabs");
     if (a.kv_bf16 && a.kv_round) throw Error("attn (prefill): kv_bf16 and kv_round exclude each other");
     if (!a.out && !a.oh) throw Error("attn (prefill): no output");
     if (!a.rope_cos || !a.rope_sin || !a.page_table) throw Error("attn (prefill): null table");
     const int G = grp <= 2 ? grp : 4, TQ = G <= 2 ? 16 : 8;
-    const dim3 ga(a.nkv, a.n_new), gb(a.nkv, (a.n_new + TQ - 1) / TQ);
+    const dim3 ga(a.nkv, a.n_new, a.nb), gb(a.nkv, (a.n_new + TQ - 1) / TQ, a.nb);
 #define Q3_PF_ARGS a.page_table, a.qkv, (const float*)a.kcache, (const float*)a.vcache, a.rope_cos, a.rope_sin, a
 #define Q3_PF_G(D_, B_) do { \
         hipLaunchKernelGGL((k_prefill_append<D_, B_>), ga, dim3(64), 0, s, a.page_table, a.qkv, a.rope_cos, a.rope_sin, a); \
@@ -2117,6 +2137,35 @@ void launch_attn_prefill(const AttnArgs& a, hipStream_t s) {
 #undef Q3_PF
 #undef Q3_PF_G
 #undef Q3_PF_ARGS
+    Q3_HIP_CHECK(hipGetLastError());
+}
+
+// ================================================================================================
+// KV prefix copy (shared prompt prefix): the K / V rows of positions [0, P) between a slot's pages [page][layer][kvh][64][d] and a
+// compact store [layer][kvh][P][d] in the cache's element type.  The payload is opaque: 16-byte units, row16 of them per token row
+// (d * element size / 16), so fp32 and bf16 caches share the code.  Grid = (units of one (layer, kv head) / 256, layer * nkv + kvh,
+// 2 * destination: K then V); scatter == 0 gathers from slot slot0, scatter == 1 writes the store into every slot of `slots`.
+// ================================================================================================
+__global__ __launch_bounds__(256) void k_kv_prefix_copy(KvPrefixCopyArgs a) {
+    const int unit = blockIdx.x * 256 + threadIdx.x;
+    const int lk = blockIdx.y, which = blockIdx.z & 1, di = blockIdx.z >> 1;
+    if (unit >= a.P * a.row16) return;
+    const int slot = a.slots ? a.slots[di] : a.slot0;
+    const int tok = unit / a.row16, w = unit - tok * a.row16;
+    const int page = a.page_table[(size_t)slot * a.pages_per_slot + (tok >> 6)];
+    const size_t co = (((size_t)page * a.n_lk + lk) * 64 + (tok & 63)) * a.row16 + w;
+    const size_t so = ((size_t)lk * a.P + tok) * a.row16 + w;
+    uint4* cache = reinterpret_cast<uint4*>(which ? a.vcache : a.kcache);
+    uint4* store = reinterpret_cast<uint4*>(which ? a.vstore : a.kstore);
+    if (a.scatter) cache[co] = store[so];
+    else store[so] = cache[co];
+}
+void launch_kv_prefix_copy(const KvPrefixCopyArgs& a, hipStream_t s) {
+    if (!a.kcache || !a.vcache || !a.kstore || !a.vstore || !a.page_table) throw Error("kv prefix copy: null argument");
+    if (a.P < 1 || a.P > (a.pages_per_slot << 6) || a.row16 < 1 || a.n_lk < 1 || a.n_lk > 65535) throw Error("kv prefix copy: bad shape");
+    if (a.scatter ? (a.n_dst < 1 || a.n_dst > 128 || !a.slots) : (a.n_dst != 1 || a.slots != nullptr)) throw Error("kv prefix copy: 1..128 destination slots, one source");
+    const dim3 grid((a.P * a.row16 + 255) / 256, a.n_lk, 2 * a.n_dst);
+    hipLaunchKernelGGL(k_kv_prefix_copy, grid, dim3(256), 0, s, a);
     Q3_HIP_CHECK(hipGetLastError());
 }
 
@@ -3324,7 +3373,7 @@ __global__ __launch_bounds__(256) void k_sample(const float* plogits, SlotState*
     }
     if (last_group && tid == 0) {
         st->n_frames = frame + 1;
-        a.talker_pos[b] = sl.prompt_len + frame; // position of the token the talker decodes next
+        a.talker_pos[b] = sl.prefix_len + sl.prompt_len + frame; // position of the token the talker decodes next
     }
 }
 

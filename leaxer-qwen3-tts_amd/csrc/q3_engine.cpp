@@ -382,6 +382,7 @@ Engine::~Engine() {
     if (proj_out_d) (void)hipFree(proj_out_d);
     if (hist_d) (void)hipFree(hist_d);
     if (long_x_d) (void)hipFree(long_x_d);
+    for (auto& it : prefixes) { if (it.second.k) (void)hipFree(it.second.k); if (it.second.v) (void)hipFree(it.second.v); }
     if (frame_codes_d) (void)hipFree(frame_codes_d);
     if (frame_text_d) (void)hipFree(frame_text_d);
     codec_free();
@@ -908,11 +909,8 @@ void Engine::long_ws_swap() {
 // run_prefill (tts_onnx.cpp:615-665) for a prompt of more than 16 rows: see q3_engine.h.  A chunk of >= mfma_min_rows rows on
 // 128-multiple dims streams the weights once through the slab GEMMs; shorter chunks and other dims take the GEMV family, as run_layers
 // decides for any pass.  Never under the split-K seam (seam_step is false outside the decode step).
-void Engine::prefill_rows_long(int slot, float* x, int S, float* logits_host) {
+void Engine::long_ws_ensure() {
     const int H = c.hidden, V = c.vocab, CH = 128;
-    if (slot < 0 || slot >= B) throw Error("slot out of range");
-    if (S < 1 || S > max_ctx) throw Error("prefill length must be 1..max_ctx rows");
-    if (seam_step) throw Error("prefill_rows_long: not inside a decode step");
     if (lws.rows == 0) {   // first long prefill: the 128-row workspace (sizes as the constructor's, rows_max -> 128)
         const int QKV = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim, AO = c.n_heads * c.head_dim;
         auto fm = [&](size_t n) { return (float*)dmalloc(n * sizeof(float)); };
@@ -923,6 +921,14 @@ void Engine::prefill_rows_long(int slot, float* x, int S, float* logits_host) {
         lws.p1h = (bf16_t*)dmalloc((size_t)CH * ldp * 2); lws.p1l = (bf16_t*)dmalloc((size_t)CH * ldp * 2);
         lws.rows = CH;
     }
+}
+
+void Engine::prefill_rows_long(int slot, float* x, int S, float* logits_host, int base0) {
+    const int H = c.hidden, V = c.vocab;
+    if (slot < 0 || slot >= B) throw Error("slot out of range");
+    if (S < 1 || base0 < 0 || base0 + S > max_ctx) throw Error("prefill length must be 1..max_ctx rows");
+    if (seam_step) throw Error("prefill_rows_long: not inside a decode step");
+    long_ws_ensure();
     struct Scope { Engine& e; explicit Scope(Engine& en) : e(en) { e.long_ws_swap(); e.chunk_attn = true; } ~Scope() { e.chunk_attn = false; e.long_ws_swap(); } } scope(*this);
     float* const hnw = lws.hn; float* const lgw = lws.logits;   // not swapped: the chunk's normalised rows and logits
     const float* last_lg = nullptr;
@@ -931,7 +937,7 @@ void Engine::prefill_rows_long(int slot, float* x, int S, float* logits_host) {
         const int n = std::min(prefill_chunk, S - base);
         const bool last = base + n == S;
         float* xc = x + (size_t)base * H;
-        const bool pr = run_layers(talker, xc, H, 1, n, slot, nullptr, base, talker_norm, c.rms_eps, hnw, H);
+        const bool pr = run_layers(talker, xc, H, 1, n, slot, nullptr, base0 + base, talker_norm, c.rms_eps, hnw, H);
         if (logits_host) {   // every row through the final norm + codec head
             head_proj(codec_head, xc, H, talker_norm, c.rms_eps, hnw, H, lgw, V, n, V, H, true, pr);
             Q3_HIP_CHECK(hipMemcpyAsync(logits_host + (size_t)base * V, lgw, (size_t)n * V * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -947,7 +953,7 @@ void Engine::prefill_rows_long(int slot, float* x, int S, float* logits_host) {
     launch_copy_rows(long_last_hidden, H, x_cp + (size_t)slot * 2 * H, H, 1, H, stream);
     st_h[slot].prompt_len = S;
     st_h[slot].n_frames = 0;
-    const int32_t pos = S;
+    const int32_t pos = base0 + S;
     Q3_HIP_CHECK(hipMemcpyAsync(talker_pos_d + slot, &pos, sizeof(int32_t), hipMemcpyHostToDevice, stream));
     sync();   // `pos` and the caller's logits buffer are read by the copies above
 }
@@ -1597,7 +1603,7 @@ void Engine::slots_begin(const SlotInit* in, int n, const q3tts_sampling& p, uin
             Q3_HIP_CHECK(hipMemcpyAsync(trailing_d + (size_t)q.slot * max_trailing * H, q.trailing, (size_t)q.n_trailing * H * sizeof(float), hipMemcpyHostToDevice, stream));
         slot_codec_stream_reset(q.slot);   // a new utterance: its streaming vocoder state starts over
         SlotState& s = st_h[q.slot];
-        s.n_frames = 0; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.trailing_len = q.n_trailing;
+        s.n_frames = 0; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.prefix_len = 0; s.trailing_len = q.n_trailing;
         s.max_frames = q.max_frames > 0 ? std::min(q.max_frames, p.max_new_tokens) : p.max_new_tokens;
         s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
         // a new utterance (a re-admission after a preemption included) starts with an empty code0 history: ordered before its first step
@@ -1672,11 +1678,11 @@ void Engine::frame_rows(const int64_t* codes, int n, int frame0, const float* tr
 // as its first frames.  The forced frames' rows are made on the device behind the prompt rows and the S + F0 rows take the prefill the
 // same rows would take as a prompt (one pass up to 16 rows, causal chunks beyond); the launch that makes the rows also records the
 // frames (codes, code0 bitmap).  Validated by slots_begin.
-void Engine::slot_begin_forced(const SlotInit& q, const q3tts_sampling& p, uint64_t seed, int ignore_eos, float rep_penalty) {
+void Engine::slot_begin_forced(const SlotInit& q, const q3tts_sampling& p, uint64_t seed, int ignore_eos, float rep_penalty, int base) {
     const int H = c.hidden, G = c.n_groups, S = q.S, F0 = q.n_prefix, R = S + F0, slot = q.slot;
     const int new_cap = q.max_frames > 0 ? std::min(q.max_frames, p.max_new_tokens) : p.max_new_tokens;
     {   // KV pages for prompt, prefix and every new frame (or what the caller grows from): nothing is armed if the pool cannot hold them
-        const int all = R + new_cap, tokens = q.kv_tokens > 0 ? std::min(all, std::max(q.kv_tokens, R)) : all;
+        const int all = base + R + new_cap, tokens = q.kv_tokens > 0 ? std::min(all, std::max(q.kv_tokens, base + R)) : all;
         const int need = kv_pages_for(tokens) - kv_slot_pages(slot);
         if (need > kv_free_pages()) {
             char msg[160];
@@ -1693,14 +1699,216 @@ void Engine::slot_begin_forced(const SlotInit& q, const q3tts_sampling& p, uint6
     // the code0 history starts empty and then holds the prefix: cleared before the launch that sets its bits, and not again behind it
     Q3_HIP_CHECK(hipMemsetAsync(seen, 0, (size_t)seen_ld * sizeof(uint32_t), stream));
     frame_rows_launch(q.prefix, F0, 0, tr, q.n_trailing, x + (size_t)S * H, codes_d + (size_t)slot * max_frames_cap * G, seen);
-    if (R <= 16) prefill_rows_in_xp(slot, R);
-    else prefill_rows_long(slot, x, R, nullptr);
+    if (R <= 16 && base == 0) prefill_rows_in_xp(slot, R);
+    else prefill_rows_long(slot, x, R, nullptr, base);   // behind a shared prefix: the chunk path at base, whatever R
     slot_codec_stream_reset(slot);
     SlotState& s = st_h[slot];   // after the prefill, which writes prompt_len = R and n_frames = 0
-    s.n_frames = F0; s.finished = 0; s.active = 1; s.prompt_len = S; s.trailing_len = q.n_trailing;
+    s.n_frames = F0; s.finished = 0; s.active = 1; s.prompt_len = S; s.prefix_len = base; s.trailing_len = q.n_trailing;
     s.max_frames = F0 + new_cap;
     s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
     Q3_HIP_CHECK(hipMemcpyAsync(st_d + slot, &s, sizeof(SlotState), hipMemcpyHostToDevice, stream));
+    sync();
+}
+
+// ------------------------------------------------------------------------------------------------
+// shared prompt prefix (q3_engine.h)
+// ------------------------------------------------------------------------------------------------
+const Engine::Prefix& Engine::prefix_get(int id) const {
+    auto it = prefixes.find(id);
+    if (it == prefixes.end()) throw Error("unknown prefix id " + std::to_string(id) + " (never created, or released)");
+    return it->second;
+}
+
+void Engine::prefix_pin(int id, int delta) {
+    auto it = prefixes.find(id);
+    if (it == prefixes.end()) throw Error("unknown prefix id " + std::to_string(id) + " (never created, or released)");
+    it->second.users += delta;
+}
+
+void Engine::kv_prefix_copy(const Prefix& pf, const int* slots_dev, int n_dst, int slot0, bool scatter) {
+    KvPrefixCopyArgs a;
+    a.kcache = talker.kc; a.vcache = talker.vc; a.kstore = pf.k; a.vstore = pf.v;
+    a.page_table = talker.page_table; a.pages_per_slot = talker.pages_per_slot;
+    a.slots = slots_dev; a.n_dst = n_dst; a.slot0 = slot0; a.scatter = scatter ? 1 : 0;
+    a.n_lk = talker.L * talker.nkv; a.P = pf.P; a.row16 = talker.d * (talker.kv_bf16 ? 2 : 4) / 16;
+    if (talker.page_shift != 6 || (talker.d * (talker.kv_bf16 ? 2 : 4)) % 16 != 0) throw Error("kv prefix copy: 64-token pages and token rows of whole 16-byte units");
+    launch_kv_prefix_copy(a, stream);
+}
+
+int Engine::prefix_create(const float* rows, int P) {
+    if (!finalized) throw Error("weights not finalized");
+    if (!rows) throw Error("prefix_create: null rows");
+    if (P < 1 || P >= max_ctx) throw Error("prefix_create: 1 <= rows < max_ctx");
+    if ((int)prefixes.size() >= kMaxPrefixes) throw Error("prefix_create: " + std::to_string(kMaxPrefixes) + " prefixes are live already (release one)");
+    int slot = -1;   // borrowed: not armed and holding no pages (a session-shaped prefill's cache rows are left alone)
+    for (int b = B - 1; b >= 0 && slot < 0; --b) if (!st_h[b].active && kv_slot_pages(b) == 0) slot = b;
+    if (slot < 0) throw Error("prefix_create: no free slot to prefill the prefix in (every slot is armed or holds KV pages)");
+    if (kv_pages_for(P) > kv_free_pages()) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "KV page pool exhausted: a prefix of %d rows needs %d pages, %d of %d free", P, kv_pages_for(P), kv_free_pages(), kv_total_pages());
+        throw Error(msg);
+    }
+    const int H = c.hidden;
+    Prefix pf;
+    pf.P = P;
+    const size_t half = (size_t)P * talker.L * talker.nkv * talker.d * (talker.kv_bf16 ? 2 : 4);
+    pf.bytes = (int64_t)(2 * half);
+    float* x = P <= 16 ? xp : long_rows(P);   // before the store exists: long_rows may throw
+    Q3_HIP_CHECK(hipMalloc(&pf.k, half));
+    if (hipMalloc(&pf.v, half) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(pf.k); throw Error("prefix_create: out of device memory for the store"); }
+    const SlotState keep = st_h[slot];
+    try {
+        kv_reserve(slot, P, true);
+        Q3_HIP_CHECK(hipMemcpyAsync(x, rows, (size_t)P * H * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (P <= 16) { prefill_rows_in_xp(slot, P); sync(); }
+        else prefill_rows_long(slot, x, P, nullptr);
+        kv_prefix_copy(pf, nullptr, 1, slot, false);
+        sync();
+    } catch (...) {
+        st_h[slot] = keep;
+        try { kv_release(slot); sync(); } catch (...) { }
+        (void)hipFree(pf.k); (void)hipFree(pf.v);
+        throw;
+    }
+    st_h[slot] = keep;
+    kv_release(slot);
+    sync();   // the table row's upload reads the host mirror
+    const int id = prefix_next_id++;
+    prefixes[id] = pf;
+    return id;
+}
+
+void Engine::prefix_release(int id) {
+    auto it = prefixes.find(id);
+    if (it == prefixes.end()) throw Error("unknown prefix id " + std::to_string(id) + " (never created, or released)");
+    if (it->second.users > 0) throw Error("prefix_release: prefix " + std::to_string(id) + " is in use by a running job");
+    sync();
+    (void)hipFree(it->second.k); (void)hipFree(it->second.v);
+    prefixes.erase(it);
+}
+
+// run_prefill (tts_onnx.cpp:615-665) for slots begun behind shared prefixes: see q3_engine.h.
+void Engine::slots_begin_prefixed(const SlotInit* in, int n, const q3tts_sampling& p, uint64_t seed, int ignore_eos) {
+    bool any = false;
+    for (int i = 0; i < n; ++i) any = any || in[i].prefix_id != -1;
+    if (!any) { slots_begin(in, n, p, seed, ignore_eos); return; }   // no prefix anywhere: today's path, untouched
+    if (!finalized) throw Error("weights not finalized");
+    const int H = c.hidden, V = c.vocab;
+    const float rep_penalty = checked_penalty(p);
+    std::vector<int> Pof((size_t)n, 0);
+    for (int i = 0; i < n; ++i) {
+        const SlotInit& q = in[i];
+        if (q.slot < 0 || q.slot >= B) throw Error("slot out of range");
+        if (q.n_trailing < 0 || q.n_trailing > max_trailing) throw Error("too many trailing text rows");
+        if (q.S < 1 || q.S > max_ctx) throw Error("prefill length must be 1..max_ctx rows");
+        if (!q.prompt) throw Error("slots_begin_prefixed: null prompt");
+        if (q.prefix_id != -1) Pof[(size_t)i] = prefix_get(q.prefix_id).P;
+        if (q.n_prefix < 0 || (q.n_prefix > 0 && !q.prefix)) throw Error("prefix codes: n_prefix must be >= 0 (and the codes given)");
+        if (p.max_new_tokens < 1 || Pof[(size_t)i] + q.S + q.n_prefix + p.max_new_tokens > max_ctx) throw Error("prefix + prompt + prefix frames + max_new_tokens exceeds max_ctx");
+        if (q.n_prefix > 0) {
+            if (q.n_prefix + p.max_new_tokens > max_frames_cap) throw Error("prefix frames + max_new_tokens exceeds the slot's frame capacity");
+            check_frame_codes(q.prefix, q.n_prefix, true);
+        }
+        for (int j = 0; j < i; ++j) if (in[j].slot == q.slot) throw Error("slots_begin_prefixed: slot listed twice");
+    }
+    auto cap_of = [&](const SlotInit& q) { return q.max_frames > 0 ? std::min(q.max_frames, p.max_new_tokens) : p.max_new_tokens; };
+    auto tokens_of = [&](int i) {
+        const SlotInit& q = in[i];
+        const int own = Pof[(size_t)i] + q.S + q.n_prefix, all = own + cap_of(q);
+        return q.kv_tokens > 0 ? std::min(all, std::max(q.kv_tokens, own)) : all;
+    };
+    {   // KV pages for the whole set, all or nothing (as slots_begin)
+        int need = 0;
+        for (int i = 0; i < n; ++i) need += kv_pages_for(tokens_of(i)) - kv_slot_pages(in[i].slot);
+        if (need > kv_free_pages()) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "KV page pool exhausted: %d slots need %d more pages, %d of %d free", n, need, kv_free_pages(), kv_total_pages());
+            throw Error(msg);
+        }
+        for (int pass = 0; pass < 2; ++pass)
+            for (int i = 0; i < n; ++i)
+                if ((kv_pages_for(tokens_of(i)) <= kv_slot_pages(in[i].slot)) == (pass == 0)) kv_reserve(in[i].slot, tokens_of(i), true);
+    }
+    if (!grp_pos_d) { grp_pos_d = (int*)dmalloc(128 * sizeof(int)); grp_x_d = (float*)dmalloc((size_t)128 * H * sizeof(float)); }
+    std::vector<int32_t> pos_h, map_h;
+    {   // each prefix's rows into the pages of its slots: one launch per prefix (per 128 slots)
+        std::vector<char> done((size_t)n, 0);
+        for (int i = 0; i < n; ++i) {
+            if (done[(size_t)i] || in[i].prefix_id == -1) continue;
+            map_h.clear();
+            for (int j = i; j < n; ++j) if (in[j].prefix_id == in[i].prefix_id) { map_h.push_back(in[j].slot); done[(size_t)j] = 1; }
+            const Prefix& pf = prefix_get(in[i].prefix_id);
+            for (size_t o = 0; o < map_h.size(); o += 128) {
+                const int m = (int)std::min<size_t>(128, map_h.size() - o);
+                Q3_HIP_CHECK(hipMemcpyAsync(slot_map_d, map_h.data() + o, (size_t)m * sizeof(int), hipMemcpyHostToDevice, stream));
+                kv_prefix_copy(pf, slot_map_d, m, 0, true);
+                sync();   // map_h and slot_map_d are reused
+            }
+        }
+    }
+    const bool mfma_ok = H % 128 == 0 && (c.n_heads * c.head_dim) % 128 == 0 && c.ffn % 128 == 0 && H <= 4096;   // run_layers' MFMA condition
+    auto batchable = [&](int i) { return mfma_ok && in[i].S <= 16 && in[i].n_prefix == 0; };
+    std::vector<char> armed((size_t)n, 0);   // the forced begin arms its slot itself
+    int i0 = 0;
+    while (i0 < n) {
+        const int S = in[i0].S, cap = batchable(i0) ? 128 / S : 1;
+        int g = 1;
+        while (i0 + g < n && g < cap && batchable(i0 + g) && in[i0 + g].S == S) ++g;
+        if (g == 1 || g * S < mfma_min_rows) {   // one at a time: the single-slot chunk path at base P (no prefix: what slots_begin does)
+            for (int k = 0; k < g; ++k) {
+                const SlotInit& q = in[i0 + k];
+                const int P = Pof[(size_t)(i0 + k)];
+                if (q.n_prefix > 0) { slot_begin_forced(q, p, seed, ignore_eos, rep_penalty, P); armed[(size_t)(i0 + k)] = 1; }
+                else if (q.prefix_id == -1) talker_prefill(q.slot, q.prompt, S, nullptr, nullptr);
+                else {
+                    float* x = long_rows(S);
+                    Q3_HIP_CHECK(hipMemcpyAsync(x, q.prompt, (size_t)S * H * sizeof(float), hipMemcpyHostToDevice, stream));
+                    prefill_rows_long(q.slot, x, S, nullptr, P);
+                }
+            }
+        } else {   // one pass for the group: chunk attention at per-member bases, the codec head on each member's last row
+            long_ws_ensure();
+            pos_h.resize((size_t)g); map_h.resize((size_t)g);
+            int pmax = 0;
+            for (int k = 0; k < g; ++k) {
+                Q3_HIP_CHECK(hipMemcpyAsync(grp_x_d + (size_t)k * S * H, in[i0 + k].prompt, (size_t)S * H * sizeof(float), hipMemcpyHostToDevice, stream));
+                pos_h[(size_t)k] = Pof[(size_t)(i0 + k)]; map_h[(size_t)k] = in[i0 + k].slot;
+                pmax = std::max(pmax, Pof[(size_t)(i0 + k)]);
+            }
+            Q3_HIP_CHECK(hipMemcpyAsync(grp_pos_d, pos_h.data(), (size_t)g * sizeof(int), hipMemcpyHostToDevice, stream));
+            Q3_HIP_CHECK(hipMemcpyAsync(slot_map_d, map_h.data(), (size_t)g * sizeof(int), hipMemcpyHostToDevice, stream));
+            {
+                struct Scope { Engine& e; explicit Scope(Engine& en) : e(en) { e.long_ws_swap(); e.chunk_attn = true; } ~Scope() { e.chunk_attn = false; e.long_ws_swap(); } } scope(*this);
+                float* const hnw = lws.hn;   // not swapped
+                const bool pr = run_layers(talker, grp_x_d, H, g, S, 0, grp_pos_d, pmax, talker_norm, c.rms_eps, hnw, H, slot_map_d);
+                if (!pr) throw Error("batched prefill expects the MFMA path");
+                head_proj(codec_head, grp_x_d, H, talker_norm, c.rms_eps, nullptr, 0, logits_g, V, g, V, H, true, true, S - 1, S);
+                for (int k = 0; k < g; ++k) {
+                    const int sl = in[i0 + k].slot;
+                    launch_copy_rows(logits_g + (size_t)k * V, V, logits_t + (size_t)sl * V, V, 1, V, stream);
+                    launch_copy_rows(hnw + (size_t)(k * S + S - 1) * H, H, x_cp + (size_t)sl * 2 * H, 2 * H, 1, H, stream);
+                    pos_h[(size_t)k] += S;
+                }
+            }
+            for (int k = 0; k < g; ++k)
+                Q3_HIP_CHECK(hipMemcpyAsync(talker_pos_d + in[i0 + k].slot, &pos_h[(size_t)k], sizeof(int32_t), hipMemcpyHostToDevice, stream));
+            sync();   // pos_h / map_h are reused by the next group
+        }
+        i0 += g;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (armed[(size_t)i]) continue;
+        const SlotInit& q = in[i];
+        if (q.n_trailing > 0)
+            Q3_HIP_CHECK(hipMemcpyAsync(trailing_d + (size_t)q.slot * max_trailing * H, q.trailing, (size_t)q.n_trailing * H * sizeof(float), hipMemcpyHostToDevice, stream));
+        slot_codec_stream_reset(q.slot);
+        SlotState& s = st_h[q.slot];
+        s.n_frames = 0; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.prefix_len = Pof[(size_t)i]; s.trailing_len = q.n_trailing;
+        s.max_frames = cap_of(q);
+        s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
+        Q3_HIP_CHECK(hipMemsetAsync(seen_d + (size_t)q.slot * seen_ld, 0, (size_t)seen_ld * sizeof(uint32_t), stream));
+        Q3_HIP_CHECK(hipMemcpyAsync(st_d + q.slot, &s, sizeof(SlotState), hipMemcpyHostToDevice, stream));
+    }
     sync();
 }
 
@@ -1950,7 +2158,7 @@ void Engine::step_bytes(double* wbytes, double* kvbytes) {
         if (!st_h[b].active) continue;
         int nf = 0;
         slot_status(b, &nf, nullptr);
-        const double Tt = st_h[b].prompt_len + nf;
+        const double Tt = st_h[b].prefix_len + st_h[b].prompt_len + nf;
         kv += Tt * c.n_layers * 2.0 * c.n_kv_heads * c.head_dim * (talker.kv_bf16 ? 2.0 : 4.0);   // fp32 cache, bf16 under Q3TTS_FLAG_KV_BF16
         double tp = 0;
         for (int j = 0; j < P; ++j) tp += j + 2;

@@ -107,7 +107,10 @@ public:
     // engine; rows_max and every short-prompt launch stay as they are).  x: the S prompt rows on the device, overwritten.  logits_host
     // non-null: the codec head runs on every row and the S rows land there; otherwise on the last row only.  Arms the slot like
     // prefill_rows_in_xp and leaves the last row's logits / normalised hidden row at long_last_logits / long_last_hidden.
-    void prefill_rows_long(int slot, float* x, int S, float* logits_host);
+    // base0 > 0 (a slot begun behind a shared prefix): the rows take positions [base0, base0 + S) behind cache rows [0, base0) that are
+    // already in the slot's pages; prompt_len stays S, the talker position becomes base0 + S.
+    void prefill_rows_long(int slot, float* x, int S, float* logits_host, int base0 = 0);
+    void long_ws_ensure();                      // the 128-row workspace (allocated once)
     float* long_rows(int S);                    // device staging for S prompt rows (grow-only)
     struct LongWs { float *qkv = nullptr, *attn = nullptr, *act = nullptr, *slab = nullptr, *gu_slab = nullptr, *qkv_slab = nullptr, *hn = nullptr, *logits = nullptr;
                     bf16_t *p0h = nullptr, *p0l = nullptr, *p1h = nullptr, *p1l = nullptr; int rows = 0; } lws;
@@ -180,11 +183,29 @@ public:
                       // Teacher-forced frames behind the prompt (continue from codes): prefix[n_prefix][n_groups] on the host.  The slot is
                       // left as if it had generated exactly these as its first n_prefix frames; max_frames and max_new_tokens count the
                       // frames behind them.  Such a slot is begun on its own (slots_begin with n == 1), like any long prompt.
-                      const int64_t* prefix = nullptr; int n_prefix = 0; };
+                      const int64_t* prefix = nullptr; int n_prefix = 0;
+                      int prefix_id = -1; /* slots_begin_prefixed: the shared prompt prefix in front of the prompt (-1: none) */ };
     void slots_begin(const SlotInit* in, int n, const q3tts_sampling& p, uint64_t seed, int ignore_eos); // batched prefill of equal-length prompts
     void slot_begin(int slot, const float* prompt, int S, const float* trailing, int n_trailing,
                     const q3tts_sampling& p, uint64_t seed, uint32_t stream_id, int ignore_eos);
-    void slot_begin_forced(const SlotInit& q, const q3tts_sampling& p, uint64_t seed, int ignore_eos, float rep_penalty);   // slots_begin's path for n_prefix > 0
+    void slot_begin_forced(const SlotInit& q, const q3tts_sampling& p, uint64_t seed, int ignore_eos, float rep_penalty, int base = 0);   // slots_begin's path for n_prefix > 0 (base: rows of a shared prefix in front)
+    // ---- shared prompt prefix (run_prefill, tts_onnx.cpp:615-665, once for many utterances) ----
+    // A prefix is P talker input rows prefilled once in a borrowed slot; their K / V rows are kept in a compact store
+    // [layer][kvh][P][head_dim] per cache (the cache's element type).  slots_begin_prefixed copies the store into each slot's own pages
+    // (no page is shared) and prefills only the utterance's rows at base P: members with equal S <= 16 share one pass through the
+    // layers (launch_attn_prefill's group form at per-member bases, up to 128 rows), the rest go one at a time through
+    // prefill_rows_long(base0 = P).  Every prefix_id == -1: exactly slots_begin.
+    struct Prefix { int P = 0; void* k = nullptr; void* v = nullptr; int64_t bytes = 0; int users = 0; };
+    std::unordered_map<int, Prefix> prefixes;   // live prefixes by id (ids are never reused)
+    int prefix_next_id = 0;
+    static constexpr int kMaxPrefixes = 64;
+    int prefix_create(const float* rows, int P);
+    void prefix_release(int id);
+    const Prefix& prefix_get(int id) const;     // throws on an unknown or released id
+    void prefix_pin(int id, int delta);         // a running job holds its prefixes: prefix_release refuses them
+    void slots_begin_prefixed(const SlotInit* in, int n, const q3tts_sampling& p, uint64_t seed, int ignore_eos);
+    void kv_prefix_copy(const Prefix& pf, const int* slots_dev, int n_dst, int slot0, bool scatter);
+    float* grp_x_d = nullptr; int* grp_pos_d = nullptr;   // a prefixed group's rows [128][H] and per-member bases [128]
     // forced-begin validation of recorded frames: code0 in [0, vocab) outside [suppress_begin, suppress_end) (a recorded frame never holds
     // EOS), sub-codes in [0, sub_vocab); strict == false (frame_rows): code0 anywhere in [0, vocab).  The error names frame and group.
     void check_frame_codes(const int64_t* codes, int n, bool strict) const;

@@ -292,6 +292,37 @@ std::vector<std::vector<float>> TTSEngine::synthesize_tokens_batch(const std::ve
     return out;
 }
 
+std::vector<std::vector<float>> TTSEngine::synthesize_tokens_batch_instruct_shared(const std::vector<std::vector<int64_t>>& token_ids,
+                                                                                   const std::vector<int64_t>& framed_instruct_ids,
+                                                                                   Language lang, const SamplingParams& params) {
+    if (framed_instruct_ids.empty()) return synthesize_tokens_batch(token_ids, lang, params);
+    std::vector<std::vector<float>> out(token_ids.size());
+    if (!ready_ || token_ids.empty()) return out;
+    q3tts_sampling sp{ params.temperature, params.top_p, params.top_k, params.repetition_penalty, params.max_new_tokens };
+    std::vector<int64_t> flat;
+    std::vector<int32_t> offs(1, 0);
+    for (const auto& t : token_ids) { flat.insert(flat.end(), t.begin(), t.end()); offs.push_back((int32_t)flat.size()); }
+    auto fail = [&]() {   // reference tts_onnx.cpp:432-435: log, return empty
+        std::cerr << "[TTSEngine] Synthesis error: " << q3tts_last_error(h_) << std::endl;
+        for (auto& v : out) v.clear();
+        return out;
+    };
+    for (int b = 0; b < max_batch_; ++b) (void)q3tts_slot_release(h_, b);   // the prefix is prefilled in a free slot
+    int pid = -1;
+    if (q3tts_prefix_create_instruct(h_, framed_instruct_ids.data(), (int)framed_instruct_ids.size(), &pid) != 0) return fail();
+    const int64_t cap = (int64_t)params.max_new_tokens * 1920 + 1920;
+    std::vector<float*> ptrs(token_ids.size());
+    for (size_t i = 0; i < token_ids.size(); ++i) { out[i].resize((size_t)cap); ptrs[i] = out[i].data(); }
+    std::vector<int64_t> lens(token_ids.size(), 0);
+    std::vector<int32_t> frames(token_ids.size(), 0), pids(token_ids.size(), pid);
+    const int rc = q3tts_synthesize_prefixed_host(h_, (int)token_ids.size(), flat.data(), offs.data(), lang_index(lang), nullptr, &sp, nullptr, seed_, 0,
+                                                  ptrs.data(), cap, lens.data(), frames.data(), nullptr, 0, nullptr, nullptr, pids.data());
+    if (rc != 0) { (void)fail(); (void)q3tts_prefix_release(h_, pid); return out; }
+    (void)q3tts_prefix_release(h_, pid);
+    for (size_t i = 0; i < out.size(); ++i) out[i].resize((size_t)std::min<int64_t>(lens[i], cap));
+    return out;
+}
+
 int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids, Language lang, const SamplingParams& params, int chunk_frames,
                                            int left_context_frames, const std::function<void(const float*, size_t)>& on_audio) {
     if (!ready_ || chunk_frames < 1) return -1;

@@ -101,6 +101,13 @@ public:
     std::vector<float> synthesize_tokens_instruct(const std::vector<int64_t>& token_ids, const std::vector<int32_t>& instruct_text_ids,
                                                   const std::vector<float>& speaker_embed, Language lang = Language::Auto,
                                                   const SamplingParams& params = SamplingParams());
+    // A batch read in one designed voice: the instruction (already framed ids, q3tts_frame_instruct_ids) is prefilled ONCE as a shared
+    // prompt prefix (include/q3tts.h: q3tts_prefix_create_instruct) and every utterance is begun behind a copy of its KV rows
+    // (q3tts_synthesize_prefixed_host); the prefix is released when the job is done.  An empty instruction is synthesize_tokens_batch.
+    std::vector<std::vector<float>> synthesize_tokens_batch_instruct_shared(const std::vector<std::vector<int64_t>>& token_ids,
+                                                                            const std::vector<int64_t>& framed_instruct_ids,
+                                                                            Language lang = Language::Auto,
+                                                                            const SamplingParams& params = SamplingParams());
     // Continue from codes (include/q3tts.h: q3tts_synthesize_continue_host; beside the reference's methods).  prefix_codes holds recorded
     // frames, n_groups() ids each, frame-major: the utterance is generated as if these had been its first frames (the previous sentence
     // of a document with its text in token_ids, the reference codes of an in-context clone, an utterance to resume), and the returned

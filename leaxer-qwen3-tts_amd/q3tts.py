@@ -94,6 +94,8 @@ EXPORTS = [
     "q3tts_codec_stream_push_batch_host", "q3tts_slots_codec_decode_new_host", "q3tts_synthesize_stream_host",
     "q3tts_build_prompt_instruct_host", "q3tts_frame_instruct_ids", "q3tts_synthesize_instruct_host",
     "q3tts_frame_rows_host", "q3tts_slot_begin_codes", "q3tts_synthesize_continue_host",
+    "q3tts_prefix_create", "q3tts_prefix_create_instruct", "q3tts_prefix_info", "q3tts_prefix_release",
+    "q3tts_slot_begin_prefixed", "q3tts_slots_begin_prefixed", "q3tts_synthesize_prefixed_host",
 ]
 
 # q3tts_audio_cb: int (*)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished)
@@ -150,6 +152,14 @@ def lib():
     L.q3tts_slot_begin_codes.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, C.POINTER(Sampling), C.c_uint64, C.c_uint32, i32]
     L.q3tts_frame_rows_host.argtypes = [vp, vp, i32, i32, vp, i32, vp]
     L.q3tts_synthesize_continue_host.argtypes = [vp, i32, vp, vp, i32, vp, C.POINTER(Sampling), vp, C.c_uint64, i32, vp, i64, vp, vp, vp, vp, vp]
+    L.q3tts_prefix_create.argtypes = [vp, vp, i32, C.POINTER(i32)]
+    L.q3tts_prefix_create_instruct.argtypes = [vp, vp, i32, C.POINTER(i32)]
+    L.q3tts_prefix_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i64)]
+    L.q3tts_prefix_release.argtypes = [vp, i32]
+    L.q3tts_slot_begin_prefixed.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, C.POINTER(Sampling), C.c_uint64, C.c_uint32, i32]
+    L.q3tts_slots_begin_prefixed.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, C.POINTER(Sampling), C.c_uint64, vp, i32]
+    L.q3tts_synthesize_prefixed_host.argtypes = [vp, i32, vp, vp, i32, vp, C.POINTER(Sampling), vp, C.c_uint64, i32, vp, i64, vp, vp, vp,
+                                                 i32, AUDIO_CB, vp, vp]
     L.q3tts_decode_steps.argtypes = [vp, i32]
     L.q3tts_slot_status.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.q3tts_slot_codes_host.argtypes = [vp, i32, vp, i32]
@@ -515,11 +525,62 @@ class Engine:
         return prompt[: S.value].copy(), trailing[: nt.value].copy()
 
     # ---- fused generation ----
-    def slot_begin(self, slot, prompt, trailing, sp, seed=0, stream_id=0, ignore_eos=False, prefix_codes=None):
+    # ---- shared prompt prefix ----
+    def prefix_create(self, rows):
+        """rows [P][hidden] prefilled once and kept as compact KV rows on the engine (q3tts_prefix_create); returns the prefix id"""
+        r = np.ascontiguousarray(rows, dtype=np.float32)
+        if r.ndim != 2 or r.shape[1] != self.cfg.hidden:
+            raise ValueError("prefix rows must be [P][hidden]")
+        pid = C.c_int(-1)
+        self._ck(self.L.q3tts_prefix_create(self.h, _p(r) if r.size else None, r.shape[0], C.byref(pid)))
+        return pid.value
+
+    def prefix_create_instruct(self, framed_ids):
+        """text_project of framed instruction ids (frame_instruct_ids) + prefix_create"""
+        ids = np.ascontiguousarray(framed_ids, dtype=np.int64).reshape(-1)
+        pid = C.c_int(-1)
+        self._ck(self.L.q3tts_prefix_create_instruct(self.h, _p(ids) if ids.size else None, ids.size, C.byref(pid)))
+        return pid.value
+
+    def prefix_info(self, prefix_id):
+        """(rows, bytes of the store)"""
+        n, b = C.c_int(0), C.c_int64(0)
+        self._ck(self.L.q3tts_prefix_info(self.h, int(prefix_id), C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def prefix_release(self, prefix_id):
+        self._ck(self.L.q3tts_prefix_release(self.h, int(prefix_id)))
+
+    def slots_begin_prefixed(self, slots, prefix_ids, prompts, trailings, sp, seed=0, stream_ids=None, ignore_eos=False):
+        """q3tts_slots_begin_prefixed: slot slots[i] begun behind prefix prefix_ids[i] (None / -1: none) with prompts[i] / trailings[i];
+        members with equal prompt lengths <= 16 share one pass through the talker"""
+        n = len(slots)
+        if not (len(prompts) == n and len(trailings) == n and (prefix_ids is None or len(prefix_ids) == n) and (stream_ids is None or len(stream_ids) == n)):
+            raise ValueError("slots_begin_prefixed: one entry per slot")
+        ps = [np.ascontiguousarray(a, dtype=np.float32) for a in prompts]
+        ts = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1, self.cfg.hidden) for a in trailings]
+        pp = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in ps])
+        tp = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in ts])
+        sl = np.ascontiguousarray(slots, np.int32)
+        ids = np.array([-1 if (prefix_ids is None or v is None) else int(v) for v in (prefix_ids if prefix_ids is not None else [None] * n)], np.int32)
+        S = np.array([a.shape[0] for a in ps], np.int32)
+        nt = np.array([a.shape[0] for a in ts], np.int32)
+        st = np.arange(n, dtype=np.uint32) if stream_ids is None else np.ascontiguousarray(stream_ids, np.uint32)
+        self._ck(self.L.q3tts_slots_begin_prefixed(self.h, n, _p(sl), _p(ids), C.cast(pp, C.c_void_p), _p(S), C.cast(tp, C.c_void_p), _p(nt),
+                                                   C.byref(sp), seed, _p(st), int(ignore_eos)))
+
+    def slot_begin(self, slot, prompt, trailing, sp, seed=0, stream_id=0, ignore_eos=False, prefix_codes=None, prefix_id=None):
         """prefix_codes [F0][n_groups]: continue from codes (q3tts_slot_begin_codes) — the slot is armed as if it had generated exactly
-        these as its first F0 frames; sp.max_new_tokens counts the frames behind them"""
+        these as its first F0 frames; sp.max_new_tokens counts the frames behind them.  prefix_id: begun behind that shared prompt
+        prefix (q3tts_slot_begin_prefixed)"""
         p = np.ascontiguousarray(prompt, dtype=np.float32)
         t = np.ascontiguousarray(trailing, dtype=np.float32)
+        if prefix_id is not None:
+            c = None if prefix_codes is None else self._frames(prefix_codes, "slot_begin(prefix_codes)")
+            nc = 0 if c is None else c.shape[0]
+            self._ck(self.L.q3tts_slot_begin_prefixed(self.h, slot, int(prefix_id), _p(p), p.shape[0], _p(t), t.shape[0], _p(c) if nc else None, nc,
+                                                      C.byref(sp), seed, stream_id, int(ignore_eos)))
+            return
         if prefix_codes is None:
             self._ck(self.L.q3tts_slot_begin(self.h, slot, _p(p), p.shape[0], _p(t), t.shape[0], C.byref(sp), seed,
                                              stream_id, int(ignore_eos)))
@@ -567,9 +628,9 @@ class Engine:
     def slot_release(self, slot):
         self._ck(self.L.q3tts_slot_release(self.h, slot))
 
-    def generate(self, prompt, trailing, sp, seed=0, stream_id=0, ignore_eos=False, slot=0, chunk=32):
+    def generate(self, prompt, trailing, sp, seed=0, stream_id=0, ignore_eos=False, slot=0, chunk=32, prefix_id=None):
         """generate_codes (reference src/tts_onnx.cpp:782-849) for one utterance on the fused path."""
-        self.slot_begin(slot, prompt, trailing, sp, seed, stream_id, ignore_eos)
+        self.slot_begin(slot, prompt, trailing, sp, seed, stream_id, ignore_eos, prefix_id=prefix_id)
         left = sp.max_new_tokens
         while left > 0:
             n = min(chunk, left)
@@ -645,11 +706,81 @@ class Engine:
         offs[1:] = np.cumsum([r.size for r in rows])
         return flat, offs
 
-    def synthesize_batch(self, token_lists, sp, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None, max_new_per_utt=None, instructs=None):
+    def synthesize_prefixed(self, token_lists, prefix_ids, sp, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None, max_new_per_utt=None,
+                            chunk_frames=0, on_audio=None):
+        """synthesize_batch with utterance u begun behind shared prompt prefix prefix_ids[u] (None / -1: none): q3tts_synthesize_prefixed_host.
+        on_audio: synthesize_stream's delivery, every chunk_frames steps."""
+        n = len(token_lists)
+        if prefix_ids is None or len(prefix_ids) != n:
+            raise ValueError("prefix_ids: one entry (id or None) per utterance")
+        ids = np.array([-1 if v is None else int(v) for v in prefix_ids], np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int64) for t in token_lists]))
+        offs = np.zeros(n + 1, np.int32)
+        offs[1:] = np.cumsum([len(t) for t in token_lists])
+        cap = self.codec_decode_len(sp.max_new_tokens)
+        pcm = [np.zeros(cap, np.float32) for _ in range(n)]
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in pcm])
+        pcm_len = np.zeros(n, np.int64)
+        nfr = np.zeros(n, np.int32)
+        codes = np.zeros((n, sp.max_new_tokens, self.cfg.n_groups), np.int64) if want_codes else None
+        spk_keep, spk_ptrs = [], None
+        if speakers is not None:
+            if len(speakers) != n:
+                raise ValueError("speakers: one entry (embedding or None) per utterance")
+            spk_keep = [None if s_ is None else np.ascontiguousarray(s_, np.float32) for s_ in speakers]
+            for a in spk_keep:
+                if a is not None and a.size != self.cfg.hidden:
+                    raise ValueError("speaker embedding has %d values, the model needs %d" % (a.size, self.cfg.hidden))
+            spk_ptrs = C.cast((C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in spk_keep]), C.c_void_p)
+        caps = None if max_new_per_utt is None else np.ascontiguousarray(max_new_per_utt, np.int32)
+        if caps is not None and caps.shape != (n,):
+            raise ValueError("max_new_per_utt: one entry per utterance")
+        raised = []
+
+        def tramp(_user, utt, fb, fe, p, ns, fin):
+            try:
+                a = np.ctypeslib.as_array(p, shape=(ns,)).copy() if ns > 0 else np.zeros(0, np.float32)
+                return 1 if on_audio(utt, fb, fe, a, bool(fin)) else 0
+            except BaseException as ex:   # an exception must not cross the C frames: cancel the job, re-raise behind it
+                raised.append(ex)
+                return 1
+        cb = AUDIO_CB(tramp) if on_audio is not None else AUDIO_CB()
+        rc = self.L.q3tts_synthesize_prefixed_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
+                                                   seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr),
+                                                   _p(codes) if want_codes else None, int(chunk_frames), cb, None, _p(ids))
+        if raised:
+            raise raised[0]
+        self._ck(rc)
+        outs = [pcm[i][: pcm_len[i]] for i in range(n)]
+        cl = [codes[i, : nfr[i]] for i in range(n)] if want_codes else None
+        return outs, cl, nfr
+
+    def synthesize_batch(self, token_lists, sp, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None, max_new_per_utt=None, instructs=None,
+                         share_instructs=False):
         """synthesize_tokens (reference src/tts_onnx.cpp:405-436) for a batch of utterances; `speakers` (one
         [hidden] embedding or None per utterance) makes it synthesize_clone (:264-318).  More utterances than slots queue
-        (continuous batching); max_new_per_utt caps each utterance separately."""
+        (continuous batching); max_new_per_utt caps each utterance separately.  share_instructs: byte-equal instruction arrays become
+        one shared prompt prefix each (prefilled once), the job runs through synthesize_prefixed and the prefixes are released after it."""
         n = len(token_lists)
+        if share_instructs and instructs is not None:
+            if len(instructs) != n:
+                raise ValueError("instructs: one entry (framed ids or None) per utterance")
+            made, ids = {}, []
+            try:
+                for t in instructs:
+                    a = None if t is None else np.ascontiguousarray(t, np.int64).reshape(-1)
+                    if a is None or a.size == 0:
+                        ids.append(-1)
+                        continue
+                    key = a.tobytes()
+                    if key not in made:
+                        made[key] = self.prefix_create_instruct(a)
+                    ids.append(made[key])
+                return self.synthesize_prefixed(token_lists, ids, sp, lang=lang, seed=seed, ignore_eos=ignore_eos, want_codes=want_codes,
+                                                speakers=speakers, max_new_per_utt=max_new_per_utt)
+            finally:
+                for pid in made.values():
+                    self.prefix_release(pid)
         flat = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int64) for t in token_lists]))
         offs = np.zeros(n + 1, np.int32)
         offs[1:] = np.cumsum([len(t) for t in token_lists])
