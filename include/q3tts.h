@@ -75,6 +75,9 @@ typedef struct q3tts_engine q3tts_engine;
 #define Q3TTS_FLAG_KV_ROUND_BF16 16u /* test aid: fp32 KV storage holding the bf16-ROUNDED rows — the arithmetic of Q3TTS_FLAG_KV_BF16 without its 16-bit storage;
                                      * the two modes must agree bit for bit (tests/test_gpu_full.py), which pins the bf16 load / store / convert path */
 #define Q3TTS_FLAG_TEST_HOOKS 32u  /* honour the fault-injection environment hooks of the test suite (Q3TTS_TEST_FAIL_VOCODER_SUBMIT); without it they are ignored */
+#define Q3TTS_FLAG_RAGGED_PREFILL 64u /* scheduler: the utterances of an admission look that are begun on their own today (instructed, continued,
+                                       * behind a shared prefix with more than 16 rows of their own) are begun with ONE q3tts_slots_begin_ragged call.
+                                       * Opt-in: without it every entry point keeps its launches and its bits */
 #define Q3TTS_FLAG_FP32_CODEC 4u  /* codec decoder on the exact-fp32 matrix-core path instead of the fp16 (hi, lo) split-operand path */
 
 /* ---- lifecycle (replaces TTSEngine ctor / load_model, tts_onnx.cpp:84-232) ---- */
@@ -378,6 +381,22 @@ int q3tts_slot_begin_prefixed(q3tts_engine* e, int slot, int prefix_id, const fl
 int q3tts_slots_begin_prefixed(q3tts_engine* e, int n, const int32_t* slots, const int32_t* prefix_ids, const float* const* prompts, const int32_t* S,
                                const float* const* trailing, const int32_t* n_trailing, const q3tts_sampling* p, uint64_t seed,
                                const uint32_t* stream_ids, int ignore_eos);
+/* Ragged begin (run_prefill, tts_onnx.cpp:615-665, and the frame loop's talker input rows, :824-842, for many slots at once): the
+ * n-slot form of q3tts_slot_begin_prefixed.  Member i is slot slots[i] behind prefix prefix_ids[i] (NULL or -1: none) with an own
+ * prompt of ANY S[i] and n_prefix_frames[i] teacher-forced frames prefix_codes[i][.][n_groups] (either array NULL: none; an entry may be
+ * NULL where its count is 0).  Everything is validated first (q3tts_slot_begin_prefixed's checks and messages, slots distinct), KV pages
+ * are reserved all or nothing, and on failure no slot is armed and no page moves.  The members' rows (prompt rows, then the forced
+ * frames' rows) are laid end to end in call order and cut into chunks of 128 rows; a chunk may hold rows of many slots, a member that does
+ * not fit the rest of a chunk continues in the next.  One pass through the talker per chunk; the codec head runs on each member's last
+ * row.  Each slot is left exactly as q3tts_slot_begin_prefixed leaves it (frames, status, codes, context, RNG stream).
+ * Exact (bit for bit): n == 1 against q3tts_slot_begin_prefixed; the same call twice; Q3TTS_FLAG_KV_BF16 against
+ * Q3TTS_FLAG_KV_ROUND_BF16; engines whose dims are not multiples of 128 and calls of fewer than 12 rows (members begun one at a time).
+ * Within 2e-4 of the reference arithmetic (4e-3 with the bf16 cache), not bit-identical: a member of a multi-member call against the same
+ * member begun alone — the projections see a different row count, as in every batched path here. */
+int q3tts_slots_begin_ragged(q3tts_engine* e, int n, const int32_t* slots, const int32_t* prefix_ids, const float* const* prompts, const int32_t* S,
+                             const float* const* trailing, const int32_t* n_trailing,
+                             const int64_t* const* prefix_codes /* entries may be NULL */, const int32_t* n_prefix_frames,
+                             const q3tts_sampling* p, uint64_t seed, const uint32_t* stream_ids, int ignore_eos);
 /* q3tts_synthesize_instruct_host with prefix_ids[n_utt] (-1: none) in place of the instruction ranges (run_prefill, tts_onnx.cpp:615-665,
  * per utterance only for its own rows): utterance u's prompt is q3tts_build_prompt_host's, begun behind prefix prefix_ids[u].  Utterances
  * admitted in the same look with equal S share their pass; a preempted utterance is re-admitted through the same prefixed begin; the

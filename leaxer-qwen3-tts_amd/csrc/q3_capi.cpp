@@ -461,6 +461,27 @@ int q3tts_slots_begin_prefixed(q3tts_engine* h, int n, const int32_t* slots, con
     return 0;
     Q3_API_END(h)
 }
+int q3tts_slots_begin_ragged(q3tts_engine* h, int n, const int32_t* slots, const int32_t* prefix_ids, const float* const* prompts, const int32_t* S,
+                             const float* const* trailing, const int32_t* n_trailing, const int64_t* const* prefix_codes, const int32_t* n_prefix_frames,
+                             const q3tts_sampling* p, uint64_t seed, const uint32_t* stream_ids, int ignore_eos) {
+    Q3_API_BEGIN(h)
+    if (n < 1) return 0;
+    if (!p || !slots || !prompts || !S) throw q3::Error("slots_begin_ragged: null argument");
+    std::vector<Engine::SlotInit> in((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        Engine::SlotInit& q = in[(size_t)i];
+        q.slot = slots[i]; q.prompt = prompts[i]; q.S = S[i];
+        q.n_trailing = n_trailing ? n_trailing[i] : 0; q.trailing = trailing && q.n_trailing > 0 ? trailing[i] : nullptr;
+        if (q.n_trailing > 0 && !q.trailing) throw q3::Error("slots_begin_ragged: trailing rows announced but not given");
+        q.stream_id = stream_ids ? stream_ids[i] : (uint32_t)i;
+        q.prefix_id = prefix_ids ? prefix_ids[i] : -1;
+        q.n_prefix = n_prefix_frames ? n_prefix_frames[i] : 0;
+        q.prefix = prefix_codes && q.n_prefix != 0 ? prefix_codes[i] : nullptr;
+    }
+    h->e->slots_begin_ragged(in.data(), n, *p, seed, ignore_eos);
+    return 0;
+    Q3_API_END(h)
+}
 int q3tts_decode_steps(q3tts_engine* h, int n_steps) {
     Q3_API_BEGIN(h) return h->e->decode_steps(n_steps); Q3_API_END(h)
 }
@@ -661,7 +682,8 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
     // Otherwise a slot owns what its context has reached plus the coming look (on-demand growth), so utterances that end early never hold
     // the pages of their cap; when the pool runs dry the YOUNGEST live utterance is preempted — its pages go back, it returns to the head
     // of the queue and is generated again from its prompt later (same RNG stream, same codes) — so the oldest always finishes.
-    std::vector<Engine::SlotInit> init;
+    std::vector<Engine::SlotInit> init, rag;
+    const bool ragged = (e.flags & Q3TTS_FLAG_RAGGED_PREFILL) != 0;
     std::vector<int> slot_utt((size_t)B, -1), done_frames((size_t)B, 0), fresh, retired;
     std::vector<q3::SlotState> st;
     std::deque<int> pending;
@@ -709,12 +731,16 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
                     q.max_frames = max_new_per_utt ? std::max(1, (int)max_new_per_utt[u]) : 0;
                     q.kv_tokens = reserve_all ? 0 : pl(u) + pr.S + pf(u) + first_look;
                     if (prefix_ids) q.prefix_id = prefix_ids[u];
-                    if (pf(u) > 0) {   // forced begin, on its own (a re-admission after a preemption too); the slot starts pf(u) frames in
+                    if (ragged && (pf(u) > 0 || q.S > 16)) {   // Q3TTS_FLAG_RAGGED_PREFILL: what would be begun on its own joins one ragged begin
+                        if (pf(u) > 0) { q.prefix = pcodes(u); q.n_prefix = pf(u); done_frames[(size_t)b] = pf(u); }
+                        rag.push_back(q);
+                    } else if (pf(u) > 0) {   // forced begin, on its own (a re-admission after a preemption too); the slot starts pf(u) frames in
                         q.prefix = pcodes(u); q.n_prefix = pf(u);
                         e.slots_begin(&q, 1, *p, seed, ignore_eos);
                         done_frames[(size_t)b] = pf(u);
                     } else init.push_back(q);
                 }
+                if (!rag.empty()) { e.slots_begin_ragged(rag.data(), (int)rag.size(), *p, seed, ignore_eos); rag.clear(); }
                 if (!init.empty()) {   // equal-length prompts share one prefill pass (behind their prefixes: at per-member bases)
                     if (prefix_ids) e.slots_begin_prefixed(init.data(), (int)init.size(), *p, seed, ignore_eos);
                     else e.slots_begin(init.data(), (int)init.size(), *p, seed, ignore_eos);
@@ -883,7 +909,15 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
                     q.kv_tokens = 0;   // prompt + cap, reserved now
                     if (prefix_ids) q.prefix_id = prefix_ids[u];
                 }
-                if (prefix_ids) e.slots_begin_prefixed(init.data(), (int)init.size(), *p, seed, ignore_eos);
+                if (e.flags & Q3TTS_FLAG_RAGGED_PREFILL) {   // the long prompts of the look in one ragged begin, the rest as before
+                    std::vector<Engine::SlotInit> rag;
+                    size_t keep = 0;
+                    for (size_t i = 0; i < init.size(); ++i) { if (init[i].S > 16) rag.push_back(init[i]); else init[keep++] = init[i]; }
+                    init.resize(keep);
+                    if (!rag.empty()) e.slots_begin_ragged(rag.data(), (int)rag.size(), *p, seed, ignore_eos);
+                }
+                if (init.empty()) { }
+                else if (prefix_ids) e.slots_begin_prefixed(init.data(), (int)init.size(), *p, seed, ignore_eos);
                 else e.slots_begin(init.data(), (int)init.size(), *p, seed, ignore_eos);
                 live += (int)fresh.size();
                 e.sched_admitted += (int64_t)fresh.size();

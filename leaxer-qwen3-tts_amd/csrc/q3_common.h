@@ -139,6 +139,10 @@ struct AttnArgs {
     // 1: k_attn_stream — the batched step's long-context kernel (one new token per row, d = 128, splits on page boundaries, K/V walked in
     // a two-deep register ring); the engine asks for it where the launch is bound by the KV bytes it streams
     int stream = 0;
+    // launch_attn_prefill's segment form (ragged prefill): the chunk's n_new rows belong to n_seg segments.  Device tables of ints:
+    // seg [n_seg][4] = {slot, cache position of the segment's first row, first row in the chunk, n_rows}, row_seg [n_new] = row -> segment,
+    // tiles [n_tiles][2] = {segment, first row of the tile within the segment}.  Null: the one-slot / group forms.
+    const int* seg = nullptr; const int* row_seg = nullptr; const int* tiles = nullptr; int n_seg = 0, n_tiles = 0;
 };
 void launch_attn(const AttnArgs& a, hipStream_t s);
 // code-predictor attention + o_proj (+ residual) for one utterance: see k_cp_attn_oproj
@@ -168,8 +172,15 @@ void launch_attn_combine(const AttnArgs& a, hipStream_t s); // partials -> a.out
 // then causal attention of every row over cache tokens [0, pos_scalar + its index] read from the cache alone.  n_splits = 1: normalised
 // rows (out) and / or planes (oh, ol).  Group form (slots begun behind a shared prefix): nb members of n_new <= 16 rows, nb * n_new <= 128,
 // member bi in slot slot_map[bi] (slot_offset + bi without a map) at its own base pos_dev[bi] (device); pos_scalar then carries the
-// largest of those bases for the launch's bounds check
+// largest of those bases for the launch's bounds check.  Segment form (a.seg non-null, ragged prefill): nb = 1, the n_new <= 128 rows
+// are cut into segments of any lengths, slots and bases (AttnArgs::seg); a tile of query rows never straddles two segments, so the
+// per-row arithmetic is the one-slot form's and a chunk of one segment gives its bits.  The caller (host) vouches that every segment
+// fits its slot's pages; the kernels skip one that does not.
 void launch_attn_prefill(const AttnArgs& a, hipStream_t s);
+bool attn_prefill_seg_ok(int d, int nq, int nkv);   // the segment form is built for these dims
+int attn_prefill_tile_rows(int nq, int nkv);        // TQ: query rows per tile (16, or 8 for GQA groups of 3-4)
+// dst row i = src row idx[i] (device indices): the rows a ragged chunk hands to the codec head
+void launch_gather_rows_f32(const float* src, int lds, const int* idx_dev, int n, float* dst, int ldd, int cols, hipStream_t s);
 // KV rows of positions [0, P) between a slot's pages and a compact store [layer][kvh][P][d] (k_kv_prefix_copy)
 struct KvPrefixCopyArgs {
     void* kcache = nullptr; void* vcache = nullptr;   // [page][layer][kvh][64][d], either element type

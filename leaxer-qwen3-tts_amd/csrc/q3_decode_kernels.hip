@@ -1903,22 +1903,31 @@ void launch_attn_combine(const AttnArgs& a, hipStream_t s) {
 //     tile's last position are never touched.  fp32 throughout; the cache reader is the only place the storage format shows, so the
 //     16-bit cache and fp32 storage of the rounded rows give the same bits.  Output: normalised fp32 rows and / or (hi, lo) planes.
 // ================================================================================================
-template <int D, bool KVB>
+template <int D, bool KVB, bool SEG = false>
 __global__ __launch_bounds__(64) void k_prefill_append(const int* ppage_table, const float* pqkv, const float* pcos, const float* psin, AttnArgs a) {
     constexpr int HALF = D / 2;
-    const int kvh = blockIdx.x, j = blockIdx.y, bi = blockIdx.z, lane = threadIdx.x;
-    const int slot = a.slot_map ? a.slot_map[bi] : a.slot_offset + bi;
+    const int kvh = blockIdx.x, lane = threadIdx.x;
     const int pshift = a.page_shift, page_tokens = 1 << pshift;
-    int base = a.pos_scalar;
-    if (a.pos_dev) {
-        base = a.pos_dev[bi];
-        if (base < 0 || base + a.n_new > (a.pages_per_slot << pshift)) return;
+    int j = blockIdx.y, bi = blockIdx.z, slot, base;
+    size_t rb;   // the member's (segment's) first qkv row
+    if constexpr (SEG) {   // grid (nkv, rows of the chunk): the row's segment names slot, base and first row
+        const int* sg = a.seg + 4 * a.row_seg[j];
+        slot = sg[0]; base = sg[1]; rb = (size_t)sg[2]; j -= sg[2]; bi = 0;
+        if (base < 0 || base + sg[3] > (a.pages_per_slot << pshift)) return;   // a segment that does not fit its slot's pages is skipped whole
+    } else {
+        slot = a.slot_map ? a.slot_map[bi] : a.slot_offset + bi;
+        base = a.pos_scalar;
+        if (a.pos_dev) {
+            base = a.pos_dev[bi];
+            if (base < 0 || base + a.n_new > (a.pages_per_slot << pshift)) return;
+        }
+        rb = (size_t)bi * a.n_new;
     }
     const int p = base + j;
     const int page = ppage_table[(size_t)slot * a.pages_per_slot + (p >> pshift)];
     const size_t off = ((((size_t)page * a.n_layers + a.layer) * a.nkv + kvh) * page_tokens + (p & (page_tokens - 1))) * D;
     const int hl = lane < HALF ? lane : 0;
-    const float* rowp = pqkv + ((size_t)bi * a.n_new + j) * a.ld_qkv;
+    const float* rowp = pqkv + (rb + j) * a.ld_qkv;
     const float* ks = rowp + (a.nq + kvh) * D;
     const float* vs = rowp + (a.nq + a.nkv + kvh) * D;
     float x0 = ks[hl], x1 = ks[hl + HALF], v0 = vs[hl], v1 = vs[hl + HALF];
@@ -1948,7 +1957,7 @@ __global__ __launch_bounds__(64) void k_prefill_append(const int* ppage_table, c
     }
 }
 
-template <int D, int G, bool KVB>
+template <int D, int G, bool KVB, bool SEG = false>
 __global__ __launch_bounds__(256) void k_attn_prefill(const int* ppage_table, const float* pqkv, const float* pkcache, const float* pvcache,
                                                        const float* pcos, const float* psin, AttnArgs a) {
     constexpr int HALF = D / 2;
@@ -1960,18 +1969,29 @@ __global__ __launch_bounds__(256) void k_attn_prefill(const int* ppage_table, co
     __shared__ __attribute__((aligned(16))) float q_s[TQ * G][D];
     __shared__ float k_s[64 * KS];
     __shared__ __attribute__((aligned(16))) float p_s[4][NP][64];
-    const int kvh = blockIdx.x, r0 = blockIdx.y * TQ, bi = blockIdx.z;
+    const int kvh = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = a.nq / a.nkv, n_new = a.n_new;
-    const int slot = a.slot_map ? a.slot_map[bi] : a.slot_offset + bi;
-    int base = a.pos_scalar;
-    if (a.pos_dev) {
-        base = a.pos_dev[bi];
+    const int grp = a.nq / a.nkv;
+    int r0, n_new, slot, base;
+    size_t rb;   // the member's (segment's) first qkv / out row
+    if constexpr (SEG) {   // grid (nkv, tiles): the tile names its segment and its first row in it; n_new is the segment's row count
+        const int* tl = a.tiles + 2 * blockIdx.y;
+        const int* sg = a.seg + 4 * tl[0];
+        slot = sg[0]; base = sg[1]; rb = (size_t)sg[2]; n_new = sg[3]; r0 = tl[1];
         if (base < 0 || base + n_new > (a.pages_per_slot << 6)) return;   // before any barrier: the whole workgroup leaves
+    } else {
+        const int bi = blockIdx.z;
+        r0 = blockIdx.y * TQ; n_new = a.n_new;
+        slot = a.slot_map ? a.slot_map[bi] : a.slot_offset + bi;
+        base = a.pos_scalar;
+        if (a.pos_dev) {
+            base = a.pos_dev[bi];
+            if (base < 0 || base + n_new > (a.pages_per_slot << 6)) return;   // before any barrier: the whole workgroup leaves
+        }
+        rb = (size_t)bi * n_new;
     }
     const int* pt = ppage_table + (size_t)slot * a.pages_per_slot;
-    const size_t rb = (size_t)bi * n_new;   // the member's first qkv / out row
 
     // ---- the tile's query heads: slabs summed in slab order, RMSNorm, RoPE (rows past the chunk and heads past the group repeat the last) ----
     const int hl = lane < HALF ? lane : 0;
@@ -2106,6 +2126,37 @@ __global__ __launch_bounds__(256) void k_attn_prefill(const int* ppage_table, co
     }
 }
 
+bool attn_prefill_seg_ok(int d, int nq, int nkv) {
+    if (nkv < 1 || nq % nkv) return false;
+    const int grp = nq / nkv;
+    return (d == 64 && (grp == 1 || grp == 2 || grp == 4)) || (d == 128 && grp == 2);
+}
+int attn_prefill_tile_rows(int nq, int nkv) { return nq / nkv <= 2 ? 16 : 8; }
+
+// Segment form: the same two kernels with SEG = true, grids (nkv, rows) and (nkv, tiles).  Instantiated for the dims
+// attn_prefill_seg_ok names (head_dim 64 with groups of 1 / 2 / 4, head_dim 128 with groups of 2; either cache format).
+static void launch_attn_prefill_seg(const AttnArgs& a, hipStream_t s) {
+    if (!attn_prefill_seg_ok(a.d, a.nq, a.nkv)) throw Error("attn (prefill, segments): head_dim 64 with 1, 2 or 4 query heads per kv head, or head_dim 128 with 2");
+    if (a.nb != 1 || a.n_new < 1 || a.n_new > 128 || a.slot_map != nullptr || a.pos_dev != nullptr)
+        throw Error("attn (prefill, segments): one chunk of 1..128 rows, slots and bases from the segment table");
+    const int TQ = attn_prefill_tile_rows(a.nq, a.nkv);
+    if (!a.row_seg || !a.tiles || a.n_seg < 1 || a.n_seg > a.n_new || a.n_tiles < (a.n_new + TQ - 1) / TQ || a.n_tiles > a.n_new)
+        throw Error("attn (prefill, segments): bad segment tables");
+    const int grp = a.nq / a.nkv;
+    const dim3 ga(a.nkv, a.n_new), gb(a.nkv, a.n_tiles);
+#define Q3_PF_ARGS a.page_table, a.qkv, (const float*)a.kcache, (const float*)a.vcache, a.rope_cos, a.rope_sin, a
+#define Q3_PFS_G(D_, B_) do { \
+        hipLaunchKernelGGL((k_prefill_append<D_, B_, true>), ga, dim3(64), 0, s, a.page_table, a.qkv, a.rope_cos, a.rope_sin, a); \
+        if (D_ == 128 || grp == 2) hipLaunchKernelGGL((k_attn_prefill<D_, 2, B_, true>), gb, dim3(256), 0, s, Q3_PF_ARGS); \
+        else if (grp == 1) hipLaunchKernelGGL((k_attn_prefill<64, 1, B_, true>), gb, dim3(256), 0, s, Q3_PF_ARGS); \
+        else hipLaunchKernelGGL((k_attn_prefill<64, 4, B_, true>), gb, dim3(256), 0, s, Q3_PF_ARGS); } while (0)
+    if (a.d == 128) { if (a.kv_bf16) Q3_PFS_G(128, true); else Q3_PFS_G(128, false); }
+    else { if (a.kv_bf16) Q3_PFS_G(64, true); else Q3_PFS_G(64, false); }
+#undef Q3_PFS_G
+#undef Q3_PF_ARGS
+    Q3_HIP_CHECK(hipGetLastError());
+}
+
 void launch_attn_prefill(const AttnArgs& a, hipStream_t s) {
     const int grp = a.nkv > 0 ? a.nq / a.nkv : 0;
     if (grp < 1 || grp > ATT_MAX_GRP || a.nq % a.nkv) throw Error("attn (prefill): unsupported GQA group size");
@@ -2116,11 +2167,13 @@ void launch_attn_prefill(const AttnArgs& a, hipStream_t s) {
         throw Error("attn (prefill): raw rows, no window, no deferred RMSNorm, no split-T partials");
     if (a.page_shift != 6) throw Error("attn (prefill): 64-token KV pages");
     // pos_dev: pos_scalar carries the largest base of the group (host-known), the kernels skip a member whose device base does not fit
-    if (a.pos_scalar < 0 || a.pos_scalar + a.n_new > (a.pages_per_slot << 6)) throw Error("attn (prefill): rows past the slot's pages");
+    // (segment form: the bases are in the table, checked by the host that built it and again by the kernels)
+    if (a.seg == nullptr && (a.pos_scalar < 0 || a.pos_scalar + a.n_new > (a.pages_per_slot << 6))) throw Error("attn (prefill): rows past the slot's pages");
     if (a.qkv_nslab < 1 || a.qkv_nslab > 4) throw Error("attn (prefill): 1..4 QKV slabs");
     if (a.kv_bf16 && a.kv_round) throw Error("attn (prefill): kv_bf16 and kv_round exclude each other");
     if (!a.out && !a.oh) throw Error("attn (prefill): no output");
     if (!a.rope_cos || !a.rope_sin || !a.page_table) throw Error("attn (prefill): null table");
+    if (a.seg != nullptr) { launch_attn_prefill_seg(a, s); return; }
     const int G = grp <= 2 ? grp : 4, TQ = G <= 2 ? 16 : 8;
     const dim3 ga(a.nkv, a.n_new, a.nb), gb(a.nkv, (a.n_new + TQ - 1) / TQ, a.nb);
 #define Q3_PF_ARGS a.page_table, a.qkv, (const float*)a.kcache, (const float*)a.vcache, a.rope_cos, a.rope_sin, a
@@ -3491,6 +3544,14 @@ __global__ void k_copy_rows(const float* src, int lds, float* dst, int ldd, int 
 }
 void launch_copy_rows(const float* src, int lds, float* dst, int ldd, int rows, int cols, hipStream_t s) {
     if (rows > 0) hipLaunchKernelGGL(k_copy_rows, dim3(rows), dim3(256), 0, s, src, lds, dst, ldd, cols);
+}
+__global__ void k_gather_rows_f32(const float* src, int lds, const int* idx, float* dst, int ldd, int cols) {
+    const int r = blockIdx.x;
+    const size_t sr = (size_t)idx[r];
+    for (int c = threadIdx.x; c < cols; c += blockDim.x) dst[(size_t)r * ldd + c] = src[sr * lds + c];
+}
+void launch_gather_rows_f32(const float* src, int lds, const int* idx_dev, int n, float* dst, int ldd, int cols, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(k_gather_rows_f32, dim3(n), dim3(256), 0, s, src, lds, idx_dev, dst, ldd, cols);
 }
 
 __global__ void k_copy_rows_masked(const float* src, int lds, float* dst, int ldd, int cols, const int* flags) {

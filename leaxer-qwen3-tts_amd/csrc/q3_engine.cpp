@@ -195,6 +195,7 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
     if (const char* sv = knob("Q3TTS_KVH_OPROJ")) kvh_oproj = atoi(sv) != 0;
     if (const char* sv = knob("Q3TTS_CP_QKV_TABLE")) cp_qkv_table_on = atoi(sv) != 0;
     if (const char* sv = knob("Q3TTS_PREFILL_CHUNK")) prefill_chunk = std::min(128, std::max(16, atoi(sv)));
+    if (flags & Q3TTS_FLAG_TEST_HOOKS) if (const char* sv = knob("Q3TTS_PREFILL_SEG")) prefill_seg = atoi(sv) != 0;   // this engine's own flag: a default engine beside a hook engine keeps its launches
     null_stream = getenv("Q3TTS_NULL_STREAM") && getenv("Q3TTS_NULL_STREAM")[0] == '1';
     if (null_stream) { stream = nullptr; flags |= Q3TTS_FLAG_NO_GRAPH; }
     else if (const char* cm = knob("Q3TTS_STREAM_CU_MASK")) {   // experiment aid (tools/overlap_probe.py): this engine's stream on a subset of the CUs;
@@ -385,6 +386,8 @@ Engine::~Engine() {
     for (auto& it : prefixes) { if (it.second.k) (void)hipFree(it.second.k); if (it.second.v) (void)hipFree(it.second.v); }
     if (frame_codes_d) (void)hipFree(frame_codes_d);
     if (frame_text_d) (void)hipFree(frame_text_d);
+    if (rag_x_d) (void)hipFree(rag_x_d);
+    if (seg_tab_d) (void)hipFree(seg_tab_d);
     codec_free();
     speaker_free();
     free_packed_weights();
@@ -702,6 +705,7 @@ bool Engine::run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new,
         else if (stream_shape && attn_stream_one && a.n_splits == 1) a.stream = 1;
         // a chunk of a long prompt: one workgroup owns its query rows over the whole context, no split-T partials
         if (chunk_attn) { a.stream = 0; a.n_splits = 1; a.chunk = 1 << 30; }
+        if (chunk_attn && seg_attn) { a.seg = seg_attn->seg; a.row_seg = seg_attn->row_seg; a.tiles = seg_attn->tiles; a.n_seg = seg_attn->n_seg; a.n_tiles = seg_attn->n_tiles; }
         const bool direct_planes = mfma && a.n_splits == 1;     // one split: the attention kernel normalises and writes the planes itself
         if (direct_planes) { a.out = nullptr; a.po = nullptr; a.pm = nullptr; a.pl = nullptr; a.oh = pl1h; a.ol = pl1l; a.ldp = ldp; }
         const bool direct_rows = !mfma && a.n_splits == 1;      // likewise for the GEMV family: normalised fp32 rows, nothing to combine
@@ -933,11 +937,27 @@ void Engine::prefill_rows_long(int slot, float* x, int S, float* logits_host, in
     float* const hnw = lws.hn; float* const lgw = lws.logits;   // not swapped: the chunk's normalised rows and logits
     const float* last_lg = nullptr;
     int n_last = 0;
-    for (int base = 0; base < S; base += prefill_chunk) {
+    // Q3TTS_PREFILL_SEG: every chunk as ONE segment of the segment kernels (the same rows, slot and base: the same bits)
+    const bool as_seg = prefill_seg && attn_prefill_seg_ok(talker.d, talker.nq, talker.nkv);
+    std::vector<SegChunk> sch;
+    if (as_seg) {
+        std::vector<SegMember> one(1);
+        one[0].slot = slot; one[0].base = base0; one[0].rows = S;
+        seg_tables_build(one, sch);
+    }
+    struct SegScope { Engine& e; ~SegScope() { e.seg_attn = nullptr; } } seg_scope{*this};
+    SegAttn sa;
+    for (int base = 0, ci = 0; base < S; base += prefill_chunk, ++ci) {
         const int n = std::min(prefill_chunk, S - base);
         const bool last = base + n == S;
         float* xc = x + (size_t)base * H;
-        const bool pr = run_layers(talker, xc, H, 1, n, slot, nullptr, base0 + base, talker_norm, c.rms_eps, hnw, H);
+        if (as_seg) {
+            const SegChunk& ch = sch[(size_t)ci];
+            if (ch.row0 != base || ch.rows != n) throw Error("prefill_rows_long: segment tables out of step with the chunks");
+            sa.seg = seg_tab_d + ch.seg; sa.row_seg = seg_tab_d + ch.row_seg; sa.tiles = seg_tab_d + ch.tiles; sa.n_seg = ch.n_seg; sa.n_tiles = ch.n_tiles;
+            seg_attn = &sa;
+        }
+        const bool pr = run_layers(talker, xc, H, 1, n, as_seg ? 0 : slot, nullptr, as_seg ? 0 : base0 + base, talker_norm, c.rms_eps, hnw, H);
         if (logits_host) {   // every row through the final norm + codec head
             head_proj(codec_head, xc, H, talker_norm, c.rms_eps, hnw, H, lgw, V, n, V, H, true, pr);
             Q3_HIP_CHECK(hipMemcpyAsync(logits_host + (size_t)base * V, lgw, (size_t)n * V * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -1910,6 +1930,188 @@ void Engine::slots_begin_prefixed(const SlotInit* in, int n, const q3tts_samplin
         Q3_HIP_CHECK(hipMemcpyAsync(st_d + q.slot, &s, sizeof(SlotState), hipMemcpyHostToDevice, stream));
     }
     sync();
+}
+
+// ------------------------------------------------------------------------------------------------
+// ragged prefill (q3_engine.h)
+// ------------------------------------------------------------------------------------------------
+float* Engine::rag_rows(size_t rows) {
+    if (rows > rag_x_rows) {
+        sync();
+        if (rag_x_d) (void)hipFree(rag_x_d);
+        rag_x_d = nullptr; rag_x_rows = 0;
+        const size_t cap = std::max(rows, (size_t)512);
+        Q3_HIP_CHECK(hipMalloc((void**)&rag_x_d, cap * c.hidden * sizeof(float)));
+        rag_x_rows = cap;
+    }
+    return rag_x_d;
+}
+
+void Engine::seg_tables_build(const std::vector<SegMember>& members, std::vector<SegChunk>& chunks) {
+    const int TQ = attn_prefill_tile_rows(talker.nq, talker.nkv), CH = prefill_chunk;
+    sync();   // seg_tab_h may still be read by the previous call's upload
+    seg_tab_h.clear();
+    chunks.clear();
+    std::vector<int32_t> seg, row_seg, tiles, last;
+    auto flush = [&](SegChunk& ch) {
+        ch.n_seg = (int)seg.size() / 4; ch.n_tiles = (int)tiles.size() / 2; ch.n_last = (int)last.size();
+        ch.seg = seg_tab_h.size(); seg_tab_h.insert(seg_tab_h.end(), seg.begin(), seg.end());
+        ch.row_seg = seg_tab_h.size(); seg_tab_h.insert(seg_tab_h.end(), row_seg.begin(), row_seg.end());
+        ch.tiles = seg_tab_h.size(); seg_tab_h.insert(seg_tab_h.end(), tiles.begin(), tiles.end());
+        ch.last = seg_tab_h.size(); seg_tab_h.insert(seg_tab_h.end(), last.begin(), last.end());
+        chunks.push_back(ch);
+        seg.clear(); row_seg.clear(); tiles.clear(); last.clear();
+    };
+    SegChunk cur;
+    int row = 0;   // rows staged so far
+    for (size_t mi = 0; mi < members.size(); ++mi) {
+        const SegMember& m = members[mi];
+        if (m.rows < 1 || m.base < 0 || m.slot < 0 || m.slot >= B || m.base + m.rows > kv_slot_pages(m.slot) * 64)
+            throw Error("ragged prefill: a member's rows do not fit its slot's pages");
+        for (int done = 0; done < m.rows;) {
+            if (cur.rows == CH) { flush(cur); cur = SegChunk(); cur.row0 = row; }
+            const int n = std::min(m.rows - done, CH - cur.rows), si = (int)seg.size() / 4;
+            seg.push_back(m.slot); seg.push_back(m.base + done); seg.push_back(cur.rows); seg.push_back(n);
+            for (int r = 0; r < n; ++r) row_seg.push_back(si);
+            for (int r = 0; r < n; r += TQ) { tiles.push_back(si); tiles.push_back(r); }
+            cur.rows += n; done += n; row += n;
+            if (done == m.rows) { last.push_back(cur.rows - 1); cur.last_member.push_back((int)mi); }
+        }
+    }
+    if (cur.rows > 0) flush(cur);
+    if (seg_tab_h.size() > seg_tab_cap) {
+        if (seg_tab_d) (void)hipFree(seg_tab_d);
+        seg_tab_d = nullptr; seg_tab_cap = 0;
+        const size_t cap = std::max(seg_tab_h.size(), (size_t)4096);
+        Q3_HIP_CHECK(hipMalloc((void**)&seg_tab_d, cap * sizeof(int32_t)));
+        seg_tab_cap = cap;
+    }
+    Q3_HIP_CHECK(hipMemcpyAsync(seg_tab_d, seg_tab_h.data(), seg_tab_h.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+}
+
+// run_prefill (tts_onnx.cpp:615-665) and the frame loop's talker input rows (:824-842) for many slots at once: see q3_engine.h.
+void Engine::slots_begin_ragged(const SlotInit* in, int n, const q3tts_sampling& p, uint64_t seed, int ignore_eos) {
+    if (n < 1) return;
+    if (n == 1) { slots_begin_prefixed(in, 1, p, seed, ignore_eos); return; }   // one member: exactly its one-at-a-time begin
+    if (!finalized) throw Error("weights not finalized");
+    const int H = c.hidden, V = c.vocab, G = c.n_groups;
+    const float rep_penalty = checked_penalty(p);
+    std::vector<int> Pof((size_t)n, 0);
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) {   // slots_begin_prefixed's checks and messages, for every member before anything is reserved
+        const SlotInit& q = in[i];
+        if (q.slot < 0 || q.slot >= B) throw Error("slot out of range");
+        if (q.n_trailing < 0 || q.n_trailing > max_trailing) throw Error("too many trailing text rows");
+        if (q.S < 1 || q.S > max_ctx) throw Error("prefill length must be 1..max_ctx rows");
+        if (!q.prompt) throw Error("slots_begin_ragged: null prompt");
+        if (q.n_trailing > 0 && !q.trailing) throw Error("slots_begin_ragged: trailing rows announced but not given");
+        if (q.prefix_id != -1) Pof[(size_t)i] = prefix_get(q.prefix_id).P;
+        if (q.n_prefix < 0 || (q.n_prefix > 0 && !q.prefix)) throw Error("prefix codes: n_prefix must be >= 0 (and the codes given)");
+        if (p.max_new_tokens < 1 || Pof[(size_t)i] + q.S + q.n_prefix + p.max_new_tokens > max_ctx) throw Error("prefix + prompt + prefix frames + max_new_tokens exceeds max_ctx");
+        if (q.n_prefix > 0) {
+            if (q.n_prefix + p.max_new_tokens > max_frames_cap) throw Error("prefix frames + max_new_tokens exceeds the slot's frame capacity");
+            check_frame_codes(q.prefix, q.n_prefix, true);
+        }
+        for (int j = 0; j < i; ++j) if (in[j].slot == q.slot) throw Error("slots_begin_ragged: slot listed twice");
+        total += (size_t)(q.S + q.n_prefix);
+    }
+    auto cap_of = [&](const SlotInit& q) { return q.max_frames > 0 ? std::min(q.max_frames, p.max_new_tokens) : p.max_new_tokens; };
+    auto tokens_of = [&](int i) {
+        const SlotInit& q = in[i];
+        const int own = Pof[(size_t)i] + q.S + q.n_prefix, all = own + cap_of(q);
+        return q.kv_tokens > 0 ? std::min(all, std::max(q.kv_tokens, own)) : all;
+    };
+    {   // KV pages for the whole set, all or nothing (as slots_begin)
+        int need = 0;
+        for (int i = 0; i < n; ++i) need += kv_pages_for(tokens_of(i)) - kv_slot_pages(in[i].slot);
+        if (need > kv_free_pages()) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "KV page pool exhausted: %d slots need %d more pages, %d of %d free", n, need, kv_free_pages(), kv_total_pages());
+            throw Error(msg);
+        }
+        for (int pass = 0; pass < 2; ++pass)
+            for (int i = 0; i < n; ++i)
+                if ((kv_pages_for(tokens_of(i)) <= kv_slot_pages(in[i].slot)) == (pass == 0)) kv_reserve(in[i].slot, tokens_of(i), true);
+    }
+    const bool mfma_ok = H % 128 == 0 && (c.n_heads * c.head_dim) % 128 == 0 && c.ffn % 128 == 0 && H <= 4096;   // run_layers' MFMA condition
+    if (!mfma_ok || !attn_prefill_seg_ok(talker.d, talker.nq, talker.nkv) || total < (size_t)mfma_min_rows || seam_step) {
+        // the members one at a time, each exactly as its own begin (its pages are reserved already: that call's reservation changes nothing)
+        for (int i = 0; i < n; ++i) slots_begin_prefixed(in + i, 1, p, seed, ignore_eos);
+        return;
+    }
+    std::vector<int32_t> map_h;
+    {   // each prefix's rows into the pages of its slots: one launch per prefix (per 128 slots), as slots_begin_prefixed
+        std::vector<char> done((size_t)n, 0);
+        for (int i = 0; i < n; ++i) {
+            if (done[(size_t)i] || in[i].prefix_id == -1) continue;
+            map_h.clear();
+            for (int j = i; j < n; ++j) if (in[j].prefix_id == in[i].prefix_id) { map_h.push_back(in[j].slot); done[(size_t)j] = 1; }
+            const Prefix& pf = prefix_get(in[i].prefix_id);
+            for (size_t o = 0; o < map_h.size(); o += 128) {
+                const int m = (int)std::min<size_t>(128, map_h.size() - o);
+                Q3_HIP_CHECK(hipMemcpyAsync(slot_map_d, map_h.data() + o, (size_t)m * sizeof(int), hipMemcpyHostToDevice, stream));
+                kv_prefix_copy(pf, slot_map_d, m, 0, true);
+                sync();   // map_h and slot_map_d are reused
+            }
+        }
+    }
+    // ---- the members' rows, contiguous in call order: prompt rows from the host, forced frames' rows made on the device ----
+    float* const x = rag_rows(total);
+    long_ws_ensure();
+    if (!rag_last_x_d) { rag_last_x_d = (float*)dmalloc((size_t)128 * H * sizeof(float)); rag_last_hn_d = (float*)dmalloc((size_t)128 * H * sizeof(float)); }
+    std::vector<SegMember> members((size_t)n);
+    {
+        size_t r = 0;
+        for (int i = 0; i < n; ++i) {
+            const SlotInit& q = in[i];
+            float* tr = trailing_d + (size_t)q.slot * max_trailing * H;
+            uint32_t* seen = seen_d + (size_t)q.slot * seen_ld;
+            Q3_HIP_CHECK(hipMemcpyAsync(x + r * H, q.prompt, (size_t)q.S * H * sizeof(float), hipMemcpyHostToDevice, stream));
+            if (q.n_trailing > 0) Q3_HIP_CHECK(hipMemcpyAsync(tr, q.trailing, (size_t)q.n_trailing * H * sizeof(float), hipMemcpyHostToDevice, stream));
+            // the code0 history starts empty and then holds the forced frames: cleared before the launch that sets its bits, not behind it
+            Q3_HIP_CHECK(hipMemsetAsync(seen, 0, (size_t)seen_ld * sizeof(uint32_t), stream));
+            if (q.n_prefix > 0)
+                frame_rows_launch(q.prefix, q.n_prefix, 0, tr, q.n_trailing, x + (r + (size_t)q.S) * H, codes_d + (size_t)q.slot * max_frames_cap * G, seen);
+            members[(size_t)i].slot = q.slot; members[(size_t)i].base = Pof[(size_t)i]; members[(size_t)i].rows = q.S + q.n_prefix;
+            r += (size_t)(q.S + q.n_prefix);
+        }
+    }
+    std::vector<SegChunk> chunks;
+    seg_tables_build(members, chunks);
+    {
+        struct Scope { Engine& e; explicit Scope(Engine& en) : e(en) { e.long_ws_swap(); e.chunk_attn = true; } ~Scope() { e.seg_attn = nullptr; e.chunk_attn = false; e.long_ws_swap(); } } scope(*this);
+        float* const hnw = lws.hn;   // not swapped
+        SegAttn sa;
+        for (const SegChunk& ch : chunks) {
+            sa.seg = seg_tab_d + ch.seg; sa.row_seg = seg_tab_d + ch.row_seg; sa.tiles = seg_tab_d + ch.tiles; sa.n_seg = ch.n_seg; sa.n_tiles = ch.n_tiles;
+            seg_attn = &sa;
+            float* xc = x + (size_t)ch.row0 * H;
+            run_layers(talker, xc, H, 1, ch.rows, 0, nullptr, 0, talker_norm, c.rms_eps, hnw, H);
+            ++ragged_passes;
+            if (ch.n_last == 0) continue;
+            // final norm + codec head on the rows that end a member: gathered by row index, then scattered to their slots
+            launch_gather_rows_f32(xc, H, seg_tab_d + ch.last, ch.n_last, rag_last_x_d, H, H, stream);
+            head_proj(codec_head, rag_last_x_d, H, talker_norm, c.rms_eps, rag_last_hn_d, H, logits_g, V, ch.n_last, V, H, true);
+            for (int k = 0; k < ch.n_last; ++k) {
+                const int sl = in[ch.last_member[(size_t)k]].slot;
+                launch_copy_rows(logits_g + (size_t)k * V, V, logits_t + (size_t)sl * V, V, 1, V, stream);
+                launch_copy_rows(rag_last_hn_d + (size_t)k * H, H, x_cp + (size_t)sl * 2 * H, 2 * H, 1, H, stream);
+            }
+        }
+    }
+    std::vector<int32_t> pos_h((size_t)n);
+    for (int i = 0; i < n; ++i) {   // the armed state, per slot what its one-at-a-time begin sets
+        const SlotInit& q = in[i];
+        pos_h[(size_t)i] = Pof[(size_t)i] + q.S + q.n_prefix;
+        Q3_HIP_CHECK(hipMemcpyAsync(talker_pos_d + q.slot, &pos_h[(size_t)i], sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        slot_codec_stream_reset(q.slot);
+        SlotState& s = st_h[q.slot];
+        s.n_frames = q.n_prefix; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.prefix_len = Pof[(size_t)i]; s.trailing_len = q.n_trailing;
+        s.max_frames = q.n_prefix + cap_of(q);
+        s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
+        Q3_HIP_CHECK(hipMemcpyAsync(st_d + q.slot, &s, sizeof(SlotState), hipMemcpyHostToDevice, stream));
+    }
+    sync();   // pos_h, the tables' host copy and the callers' rows are read by the copies above
 }
 
 int Engine::decode_steps(int n_steps) {

@@ -206,6 +206,29 @@ public:
     void slots_begin_prefixed(const SlotInit* in, int n, const q3tts_sampling& p, uint64_t seed, int ignore_eos);
     void kv_prefix_copy(const Prefix& pf, const int* slots_dev, int n_dst, int slot0, bool scatter);
     float* grp_x_d = nullptr; int* grp_pos_d = nullptr;   // a prefixed group's rows [128][H] and per-member bases [128]
+    // ---- ragged prefill: rows of many slots, with any lengths, bases and forced frames, share 128-row chunks ----
+    // Members as in slots_begin_prefixed (optional prefix_id, own prompt of any S, optional forced frames).  Everything is validated
+    // and the KV pages reserved (all or nothing) before anything is armed; the members' rows are staged contiguously in call order,
+    // cut into chunks of prefill_chunk rows (a member that does not fit the rest of a chunk continues in the next one at base + rows
+    // done) and every chunk takes ONE run_layers pass in the long workspace with the segment form of the chunk attention; the final
+    // norm + codec head run on the rows that end a member.  n == 1, dims off run_layers' MFMA condition or off the segment kernels'
+    // instantiations, and calls of fewer than mfma_min_rows rows begin their members one at a time (slots_begin_prefixed with n = 1).
+    void slots_begin_ragged(const SlotInit* in, int n, const q3tts_sampling& p, uint64_t seed, int ignore_eos);
+    struct SegMember { int slot = 0, base = 0, rows = 0; };
+    struct SegChunk { int row0 = 0, rows = 0, n_seg = 0, n_tiles = 0, n_last = 0;      // rows [row0, row0 + rows) of the staged sequence
+                      size_t seg = 0, row_seg = 0, tiles = 0, last = 0;                 // offsets (ints) of the chunk's tables in seg_tab_d
+                      std::vector<int> last_member; };                                 // the members whose last row is in the chunk, in row order
+    // cuts the members' rows into chunks, builds every chunk's tables in seg_tab_h and uploads them in one copy (the stream is
+    // synchronised first: the previous call's upload may still read seg_tab_h)
+    void seg_tables_build(const std::vector<SegMember>& members, std::vector<SegChunk>& chunks);
+    std::vector<int32_t> seg_tab_h; int32_t* seg_tab_d = nullptr; size_t seg_tab_cap = 0;
+    struct SegAttn { const int* seg = nullptr; const int* row_seg = nullptr; const int* tiles = nullptr; int n_seg = 0, n_tiles = 0; };
+    const SegAttn* seg_attn = nullptr;          // slots_begin_ragged / prefill_rows_long -> run_layers: the chunk attention's segment tables
+    float* rag_x_d = nullptr; size_t rag_x_rows = 0;   // the staged rows of a ragged call (grow-only)
+    float* rag_rows(size_t rows);
+    float *rag_last_x_d = nullptr, *rag_last_hn_d = nullptr;   // a chunk's member-ending rows [128][H] before / after the final norm
+    bool prefill_seg = false;                   // Q3TTS_PREFILL_SEG=1 at creation (hook engines): prefill_rows_long issues its chunks through the segment kernels as one segment (A/B knob, tests' pin)
+    int64_t ragged_passes = 0;                  // run_layers passes issued by slots_begin_ragged's chunk path (diagnostic, tools/ragged_prefill_bench.py)
     // forced-begin validation of recorded frames: code0 in [0, vocab) outside [suppress_begin, suppress_end) (a recorded frame never holds
     // EOS), sub-codes in [0, sub_vocab); strict == false (frame_rows): code0 anywhere in [0, vocab).  The error names frame and group.
     void check_frame_codes(const int64_t* codes, int n, bool strict) const;

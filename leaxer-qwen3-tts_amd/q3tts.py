@@ -71,6 +71,7 @@ FLAG_NO_GRAPH = 1
 FLAG_NO_FUSED_CP = 2
 FLAG_FP32_CODEC = 4
 FLAG_KV_ROUND_BF16 = 16   # test aid: fp32 KV storage of the bf16-rounded rows (must equal FLAG_KV_BF16 bit for bit)
+FLAG_RAGGED_PREFILL = 64   # the scheduler begins the long prompts / forced begins of an admission look with one slots_begin_ragged call
 FLAG_TEST_HOOKS = 32   # the engine honours the test suite's fault-injection environment hooks
 FLAG_KV_BF16 = 8   # talker KV cache in bf16 (rounded on append, fp32 math); the oracle has the same switch (Oracle(kv_bf16=True))
 
@@ -95,7 +96,7 @@ EXPORTS = [
     "q3tts_build_prompt_instruct_host", "q3tts_frame_instruct_ids", "q3tts_synthesize_instruct_host",
     "q3tts_frame_rows_host", "q3tts_slot_begin_codes", "q3tts_synthesize_continue_host",
     "q3tts_prefix_create", "q3tts_prefix_create_instruct", "q3tts_prefix_info", "q3tts_prefix_release",
-    "q3tts_slot_begin_prefixed", "q3tts_slots_begin_prefixed", "q3tts_synthesize_prefixed_host",
+    "q3tts_slot_begin_prefixed", "q3tts_slots_begin_prefixed", "q3tts_slots_begin_ragged", "q3tts_synthesize_prefixed_host",
 ]
 
 # q3tts_audio_cb: int (*)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished)
@@ -158,6 +159,7 @@ def lib():
     L.q3tts_prefix_release.argtypes = [vp, i32]
     L.q3tts_slot_begin_prefixed.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, i32, C.POINTER(Sampling), C.c_uint64, C.c_uint32, i32]
     L.q3tts_slots_begin_prefixed.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, C.POINTER(Sampling), C.c_uint64, vp, i32]
+    L.q3tts_slots_begin_ragged.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Sampling), C.c_uint64, vp, i32]
     L.q3tts_synthesize_prefixed_host.argtypes = [vp, i32, vp, vp, i32, vp, C.POINTER(Sampling), vp, C.c_uint64, i32, vp, i64, vp, vp, vp,
                                                  i32, AUDIO_CB, vp, vp]
     L.q3tts_decode_steps.argtypes = [vp, i32]
@@ -568,6 +570,29 @@ class Engine:
         st = np.arange(n, dtype=np.uint32) if stream_ids is None else np.ascontiguousarray(stream_ids, np.uint32)
         self._ck(self.L.q3tts_slots_begin_prefixed(self.h, n, _p(sl), _p(ids), C.cast(pp, C.c_void_p), _p(S), C.cast(tp, C.c_void_p), _p(nt),
                                                    C.byref(sp), seed, _p(st), int(ignore_eos)))
+
+    def slots_begin_ragged(self, slots, prompts, trailings, sp, prefix_ids=None, prefix_codes=None, seed=0, stream_ids=None, ignore_eos=False):
+        """q3tts_slots_begin_ragged: slot slots[i] begun behind prefix prefix_ids[i] (None / -1: none) with prompts[i] of any length,
+        trailings[i] and the teacher-forced frames prefix_codes[i] ([F0][n_groups]; None: none).  The members' rows share 128-row
+        chunks: one pass through the talker per chunk, whatever the lengths"""
+        n = len(slots)
+        if not (len(prompts) == n and len(trailings) == n and (prefix_ids is None or len(prefix_ids) == n)
+                and (prefix_codes is None or len(prefix_codes) == n) and (stream_ids is None or len(stream_ids) == n)):
+            raise ValueError("slots_begin_ragged: one entry per slot")
+        ps = [np.ascontiguousarray(a, dtype=np.float32) for a in prompts]
+        ts = [np.ascontiguousarray(a, dtype=np.float32).reshape(-1, self.cfg.hidden) for a in trailings]
+        cs = [None if (prefix_codes is None or a is None) else self._frames(a, "slots_begin_ragged(prefix_codes)") for a in (prefix_codes if prefix_codes is not None else [None] * n)]
+        pp = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in ps])
+        tp = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in ts])
+        cp = (C.c_void_p * max(n, 1))(*[a.ctypes.data if (a is not None and a.shape[0]) else None for a in cs])
+        sl = np.ascontiguousarray(slots, np.int32)
+        ids = np.array([-1 if (prefix_ids is None or v is None) else int(v) for v in (prefix_ids if prefix_ids is not None else [None] * n)], np.int32)
+        S = np.array([a.shape[0] for a in ps], np.int32)
+        nt = np.array([a.shape[0] for a in ts], np.int32)
+        nc = np.array([0 if a is None else a.shape[0] for a in cs], np.int32)
+        st = np.arange(n, dtype=np.uint32) if stream_ids is None else np.ascontiguousarray(stream_ids, np.uint32)
+        self._ck(self.L.q3tts_slots_begin_ragged(self.h, n, _p(sl), _p(ids), C.cast(pp, C.c_void_p), _p(S), C.cast(tp, C.c_void_p), _p(nt),
+                                                 C.cast(cp, C.c_void_p), _p(nc), C.byref(sp), seed, _p(st), int(ignore_eos)))
 
     def slot_begin(self, slot, prompt, trailing, sp, seed=0, stream_id=0, ignore_eos=False, prefix_codes=None, prefix_id=None):
         """prefix_codes [F0][n_groups]: continue from codes (q3tts_slot_begin_codes) — the slot is armed as if it had generated exactly
