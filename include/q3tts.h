@@ -244,6 +244,12 @@ float q3tts_rng_uniform(uint64_t seed, uint32_t stream, uint32_t frame, uint32_t
  * trailing[cap_rows][hidden] receives trailing_text_hidden_, *n_trailing its row count. */
 int q3tts_build_prompt_host(q3tts_engine* e, const int64_t* ids, int n_ids, int lang, const float* speaker,
                             float* prompt, int* S, float* trailing, int cap_rows, int* n_trailing);
+/* q3tts_build_prompt_host for a text whose end is not known (live text; tts_onnx.cpp:531-536 / :833-842): ids[0..2] are the role,
+ * ids[3] the first text id, every later id becomes a trailing row — none is held back as the chat template's tail, no tts_eos row is
+ * added, *n_trailing = n_ids - 4 (n_ids >= 4).  The prompt rows equal q3tts_build_prompt_host's for any whole text with the same first
+ * four ids, bit for bit.  Begin a slot with the result, then q3tts_slot_text_open. */
+int q3tts_build_prompt_open_host(q3tts_engine* e, const int64_t* ids, int n_ids, int lang, const float* speaker,
+                                 float* prompt, int* S, float* trailing, int cap_rows, int* n_trailing);
 /* Voice instructions — the reference README's roadmap row "Voice instructions (--instruct), 1.7B-VoiceDesign: Planned".  The prompt of
  * build_prompt_embeddings (tts_onnx.cpp:442-539) with an instruction in front of it: rows 0 .. n_instruct-1 of prompt[cap_prompt_rows][hidden]
  * are text_project(instruct_ids) (run_text_project, :541-559), the rest is exactly what q3tts_build_prompt_host produces; *S = n_instruct +
@@ -285,6 +291,32 @@ int q3tts_slot_begin_codes(q3tts_engine* e, int slot, const float* prompt, int S
  * of slots still active, <0 on error. */
 int q3tts_decode_steps(q3tts_engine* e, int n_steps);
 int q3tts_slot_status(q3tts_engine* e, int slot, int* n_frames, int* finished);
+
+/* ---- live text: append text to a generating slot, stall when starved ----
+ * The reference builds an utterance's trailing text block once (tts_onnx.cpp:531-536) and frame f's talker input row reads row f of it
+ * and nothing else (:833-842), tts_pad beyond its end.  A slot therefore only has to be ONE text row ahead of its frame counter: an
+ * open slot whose next frame has no row yet does not take tts_pad, it stalls — the step leaves it exactly as it was (codes, frame
+ * counter, logits, KV rows) — and goes on, bit for bit as if it had held the whole text from the start, once the row is there.
+ * q3tts_decode_steps keeps its meaning (its return counts stalled slots as active); a stalled slot never reaches max_frames on its own,
+ * so a caller that feeds text looks at q3tts_slot_text_status.
+ * Every call validates everything before anything moves: on error no slot has changed. */
+/* Opens the slot's text (tts_onnx.cpp:531-536: the block is no longer final).  After any q3tts_slot_begin* variant (plain, codes, prefixed,
+ * ragged member) and before the slot's first step; refused once the slot has stepped.  q3tts_decode_steps then fails, naming the
+ * slot, while an open slot that has not stepped holds no row for its first frame (:833-842 reads it in that very step).
+ * A slot begun behind teacher-forced frames must already hold those frames' text rows at its begin (they were read there): the open
+ * is refused when it holds fewer rows than forced frames. */
+int q3tts_slot_text_open(q3tts_engine* e, int slot);
+/* n_rows projected rows [n_rows][hidden] (q3tts_text_project_host's) go behind the slot's text rows (the block of tts_onnx.cpp:531-536); close = 1
+ * puts the tts_eos row behind them (:535) and ends the text: from then on frames beyond it take tts_pad (:833-842).  n_rows == 0 with
+ * close = 1 just closes.  Errors: "not armed", "text already closed", "text too long for the trailing buffer". */
+int q3tts_slot_text_append_host(q3tts_engine* e, int slot, const float* rows, int n_rows, int close);
+/* The same for n distinct slots from token ids (tts_onnx.cpp:531-536 projects them into the block; :833-842 reads them): slot slots[i] takes
+ * ids[offsets[i] .. offsets[i + 1]), close (optional) [n].  One text_project pass over all the ids on the device and one scatter launch,
+ * whatever n.  Further errors: "duplicate slots", "text id out of range [0, text_vocab)". */
+int q3tts_slots_text_append_ids(q3tts_engine* e, int n, const int32_t* slots, const int64_t* ids, const int32_t* offsets, const uint8_t* close);
+/* n_text_rows: text rows the slot holds (tts_onnx.cpp:531-536, the tts_eos row included once closed); open; starved = open and
+ * n_frames >= n_text_rows (:833-842 would need a row that has not arrived).  Any output may be NULL. */
+int q3tts_slot_text_status(q3tts_engine* e, int slot, int* n_text_rows, int* open, int* starved);
 /* codes[cap_frames][n_groups], int64 like the reference (tts_onnx.cpp:421-427) */
 int q3tts_slot_codes_host(q3tts_engine* e, int slot, int64_t* codes, int cap_frames);
 /* run_decode's outputs (tts_onnx.cpp:714-719) as the fused path holds them for the slot: logits[vocab] the slot's next code0 will be
@@ -332,6 +364,24 @@ int q3tts_synthesize_stream_host(q3tts_engine* e, int n_utt, const int64_t* ids,
                                  const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                  float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                  int chunk_frames, q3tts_audio_cb cb, void* user);
+/* q3tts_synthesize_stream_host (same audio callback, same outputs, no preemption) for texts that arrive while their audio is generated:
+ * a pull callback takes the place of ids / offsets (tts_onnx.cpp:531-536 builds the text block from the whole text; :833-842 reads
+ * one row of it per frame, which is all a slot has to be ahead).  text_cb is called on the caller's thread between decode chunks, for
+ * utterance u while its text is open: write up to cap new ids, set *n (0: nothing yet) and *closed (1: no more text will come).  A
+ * non-zero return cancels the job ("cancelled by callback").  A callback with nothing to give should block or sleep: when every live
+ * slot is starved and nothing can be admitted the loop polls again at once.
+ * The ids of an utterance are those of the other entries: 3 role ids, the text, and the chat template's two-id tail, which every
+ * entry drops (tts_onnx.cpp:531: text_end = n - 2) — the last two ids received are therefore held back until the text is closed.
+ * An utterance is queued from the start and admitted once it holds 5 usable ids (role, first text id, the row of frame 0) or is
+ * closed with at least 4 ids.  Admission keeps the queue order (RNG stream and slot use as in the stream entry): an utterance
+ * whose text has not arrived yet holds back the ones queued behind it, ready or not.  Per loop turn: poll every open utterance (live or queued), admit, append the new ids of all live slots
+ * in ONE q3tts_slots_text_append_ids call, decode chunk_frames steps, vocode and deliver the new frames.  A stalled slot has an empty
+ * frame range and gets no audio callback that turn.  Codes and frame counts equal q3tts_synthesize_stream_host's on the same ids. */
+typedef int (*q3tts_text_cb)(void* user, int utt, int64_t* ids, int cap, int32_t* n, int32_t* closed);
+int q3tts_synthesize_live_host(q3tts_engine* e, int n_utt, q3tts_text_cb text_cb, void* text_user, int lang,
+                               const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                               float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                               int chunk_frames, q3tts_audio_cb cb, void* user);
 /* The scheduler entries with a voice instruction per utterance (README roadmap row "--instruct"): instruct_ids / instruct_offsets
  * [n_utt + 1] give utterance u the framed instruction ids [instruct_offsets[u], instruct_offsets[u + 1]); an empty range means none, and
  * instruct_ids == NULL none for any.  An instructed utterance's prompt is q3tts_build_prompt_instruct_host's and is prefilled on its own

@@ -51,7 +51,8 @@ static void usage(const char* prog) {
     printf("  --top-k N             top-k (default: 50)\n  --top-p FLOAT         top-p (default: 0.95)\n");
     printf("  --rep-penalty FLOAT   repetition penalty on the first codebook's ids (default: 1.0 = off; not a flag of the reference CLI)\n");
     printf("  --max-tokens N        max codec frames (default: 2048)\n  --seed N              sampling seed (default: 0)\n");
-    printf("  --stream-chunk N      with --tokens: decode audio every N frames while generating (same samples as the one-shot decode)\n  -h, --help\n");
+    printf("  --stream-chunk N      with --tokens: decode audio every N frames while generating (same samples as the one-shot decode)\n");
+    printf("  --feed K              with --stream-chunk: hand the text to the engine K tokens at a time while it generates (live text; same codes, and with --save-codes the same samples as without --feed)\n  -h, --help\n");
 }
 
 // one frame per line, the same number of integers on every line (blanks or commas between them); false with a message on stderr
@@ -105,7 +106,7 @@ int main(int argc, char** argv) {
     bool have_prompt = false;
     SamplingParams sp;
     uint64_t seed = 0;
-    int stream_chunk = 0;
+    int stream_chunk = 0, feed = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         const bool more = i + 1 < argc;
@@ -127,17 +128,22 @@ int main(int argc, char** argv) {
         else if (a == "--max-tokens" && more) sp.max_new_tokens = atoi(argv[++i]);
         else if (a == "--seed" && more) seed = strtoull(argv[++i], nullptr, 10);
         else if (a == "--stream-chunk" && more) stream_chunk = atoi(argv[++i]);
+        else if (a == "--feed" && more) feed = atoi(argv[++i]);
     }
     if (model.empty() || (!have_prompt && tokens.empty())) {
         fprintf(stderr, "Error: --model and --prompt (or --tokens) are required\n");
         usage(argv[0]);
         return 1;
     }
+    if (feed != 0 && (feed < 1 || stream_chunk < 1 || !ref.empty() || !instruct.empty() || !instruct_tokens.empty() || !continue_codes.empty())) {
+        fprintf(stderr, "Error: --feed K (K >= 1) needs --stream-chunk (without --ref, --instruct, --continue-codes)\n");
+        return 1;
+    }
     std::vector<int64_t> prefix;
     size_t prefix_groups = 0;
     if (!save_codes.empty() || !continue_codes.empty()) {
-        if (tokens.empty() || !ref.empty() || !instruct.empty() || !instruct_tokens.empty() || stream_chunk > 0) {
-            fprintf(stderr, "Error: --save-codes / --continue-codes go with --tokens (without --ref, --instruct, --stream-chunk)\n");
+        if (tokens.empty() || !ref.empty() || !instruct.empty() || !instruct_tokens.empty() || (stream_chunk > 0 && !continue_codes.empty())) {
+            fprintf(stderr, "Error: --save-codes / --continue-codes go with --tokens (without --ref, --instruct; --continue-codes without --stream-chunk)\n");
             return 1;
         }
         if (!continue_codes.empty()) {
@@ -191,6 +197,42 @@ int main(int argc, char** argv) {
         else audio = engine.synthesize_tokens_clone(ids, spk, lang_of(lang), sp);
     } else if (!ref.empty()) {
         audio = engine.synthesize_clone(prompt, ref, lang_of(lang), sp);
+    } else if (stream_chunk > 0 && (feed > 0 || !save_codes.empty())) {
+        // the batch scheduler's delivery for one utterance; --feed: its ids reach the engine K at a time, one piece per poll (live text)
+        if (ids.empty()) {   // -p: the framing of --tokens around the tokenised text
+            const std::vector<int32_t> t = engine.tokenize(prompt);
+            if (t.empty()) { fprintf(stderr, "Error: the text has no tokens (-p needs vocab.json + merges.txt)\n"); return 1; }
+            ids = { config::IM_START, config::ASSISTANT, config::TTS_BOS };
+            ids.insert(ids.end(), t.begin(), t.end());
+            ids.push_back(config::TTS_EOS);
+            ids.push_back(config::IM_END);
+        }
+        size_t chunks = 0, given = 0, polls = 0;
+        auto on_audio = [&](int, const float* p, size_t n, bool) {
+            if (n > 0 && chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / config::SAMPLE_RATE);
+            audio.insert(audio.end(), p, p + n);
+            return false;
+        };
+        std::vector<std::vector<int64_t>> codes;
+        std::vector<int> nf;
+        if (feed > 0) {
+            nf = engine.synthesize_tokens_live(1, [&](int, std::vector<int64_t>& out, bool& closed) {
+                const size_t m = std::min((size_t)feed, ids.size() - given);
+                out.insert(out.end(), ids.begin() + (std::ptrdiff_t)given, ids.begin() + (std::ptrdiff_t)(given + m));
+                given += m; ++polls;
+                closed = given == ids.size();
+                return true;
+            }, lang_of(lang), sp, stream_chunk, on_audio, save_codes.empty() ? nullptr : &codes);
+        } else nf = engine.synthesize_tokens_batch_streaming({ ids }, lang_of(lang), sp, stream_chunk, on_audio, &codes);
+        if (nf.empty()) audio.clear();
+        else {
+            printf("Streamed %d frames in %zu chunks\n", nf[0], chunks);
+            if (feed > 0) printf("Text fed in %zu pieces of up to %d tokens\n", polls, feed);
+        }
+        if (!nf.empty() && !save_codes.empty()) {
+            if (!write_codes_file(save_codes, codes[0], (size_t)engine.n_groups())) { fprintf(stderr, "Error: failed to write %s\n", save_codes.c_str()); return 1; }
+            printf("Codes saved to: %s\n", save_codes.c_str());
+        }
     } else if (!ids.empty() && stream_chunk > 0) {   // chunks of audio as their frames are generated; the file holds their concatenation
         size_t chunks = 0;
         const int nf = engine.synthesize_tokens_streaming(ids, lang_of(lang), sp, stream_chunk, -1, [&](const float* p, size_t n) {

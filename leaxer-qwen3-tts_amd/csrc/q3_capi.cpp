@@ -386,6 +386,11 @@ int q3tts_build_prompt_host(q3tts_engine* h, const int64_t* ids, int n_ids, int 
     Q3_API_BEGIN(h) h->e->build_prompt(ids, n_ids, lang, speaker, prompt, S, trailing, cap_rows, n_trailing); return 0; Q3_API_END(h)
 }
 
+int q3tts_build_prompt_open_host(q3tts_engine* h, const int64_t* ids, int n_ids, int lang, const float* speaker,
+                                 float* prompt, int* S, float* trailing, int cap_rows, int* n_trailing) {
+    Q3_API_BEGIN(h) h->e->build_prompt_open(ids, n_ids, lang, speaker, prompt, S, trailing, cap_rows, n_trailing); return 0; Q3_API_END(h)
+}
+
 int q3tts_slot_begin(q3tts_engine* h, int slot, const float* prompt, int S, const float* trailing, int n_trailing,
                      const q3tts_sampling* p, uint64_t seed, uint32_t stream_id, int ignore_eos) {
     Q3_API_BEGIN(h) h->e->slot_begin(slot, prompt, S, trailing, n_trailing, *p, seed, stream_id, ignore_eos); return 0; Q3_API_END(h)
@@ -487,6 +492,30 @@ int q3tts_decode_steps(q3tts_engine* h, int n_steps) {
 }
 int q3tts_slot_status(q3tts_engine* h, int slot, int* n_frames, int* finished) {
     Q3_API_BEGIN(h) h->e->slot_status(slot, n_frames, finished); return 0; Q3_API_END(h)
+}
+// ---- live text (Engine::slot_text_open / slots_text_append / slot_text_status; tts_onnx.cpp:531-536, :833-842) ----
+int q3tts_slot_text_open(q3tts_engine* h, int slot) {
+    Q3_API_BEGIN(h) h->e->slot_text_open(slot); return 0; Q3_API_END(h)
+}
+int q3tts_slot_text_append_host(q3tts_engine* h, int slot, const float* rows, int n_rows, int close) {
+    Q3_API_BEGIN(h)
+    if (n_rows < 0 || (n_rows > 0 && !rows)) throw q3::Error("text_append: bad arguments");
+    const int32_t sl = slot, offsets[2] = { 0, n_rows };
+    const uint8_t cl = close ? 1 : 0;
+    if (n_rows > 0) h->e->slots_text_append(1, &sl, rows, nullptr, offsets, &cl);
+    else h->e->slots_text_append(1, &sl, nullptr, nullptr, offsets, &cl);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_slots_text_append_ids(q3tts_engine* h, int n, const int32_t* slots, const int64_t* ids, const int32_t* offsets, const uint8_t* close) {
+    Q3_API_BEGIN(h)
+    if (n < 0) throw q3::Error("text_append: bad arguments");
+    h->e->slots_text_append(n, slots, nullptr, ids, offsets, close);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_slot_text_status(q3tts_engine* h, int slot, int* n_text_rows, int* open, int* starved) {
+    Q3_API_BEGIN(h) h->e->slot_text_status(slot, n_text_rows, open, starved); return 0; Q3_API_END(h)
 }
 int q3tts_slot_codes_host(q3tts_engine* h, int slot, int64_t* codes, int cap_frames) {
     Q3_API_BEGIN(h) h->e->slot_codes(slot, codes, cap_frames); return 0; Q3_API_END(h)
@@ -591,7 +620,7 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                   int chunk_frames, q3tts_audio_cb cb, void* user, const int64_t* instruct_ids, const int32_t* instruct_offsets,
-                                  const int32_t* prefix_ids = nullptr);
+                                  const int32_t* prefix_ids = nullptr, q3tts_text_cb tcb = nullptr, void* tuser = nullptr);
 static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                     const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                     float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
@@ -845,16 +874,26 @@ int q3tts_synthesize_stream_host(q3tts_engine* h, int n_utt, const int64_t* ids,
     return synthesize_stream_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
                                   chunk_frames, cb, user, nullptr, nullptr);
 }
+// The same loop with the texts pulled through a callback while the audio is generated (include/q3tts.h; tts_onnx.cpp:531-536, :833-842)
+int q3tts_synthesize_live_host(q3tts_engine* h, int n_utt, q3tts_text_cb text_cb, void* text_user, int lang,
+                               const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                               float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                               int chunk_frames, q3tts_audio_cb cb, void* user) {
+    if (!text_cb) { if (h) h->err = "synthesize_live: null text callback"; return -1; }
+    return synthesize_stream_impl(h, n_utt, nullptr, nullptr, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
+                                  chunk_frames, cb, user, nullptr, nullptr, nullptr, text_cb, text_user);
+}
 static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                   int chunk_frames, q3tts_audio_cb cb, void* user, const int64_t* instruct_ids, const int32_t* instruct_offsets,
-                                  const int32_t* prefix_ids) {
+                                  const int32_t* prefix_ids, q3tts_text_cb tcb, void* tuser) {
     Q3_API_BEGIN(h)
     Engine& e = *h->e;
     const int H = e.c.hidden, G = e.c.n_groups, B = e.B;
     if (n_utt <= 0) return 0;
-    if (!ids || !offsets || !p) throw q3::Error("synthesize: null argument");
+    const bool live_text = tcb != nullptr;   // q3tts_synthesize_live_host: the texts arrive through tcb, prompts are built at admission
+    if ((!live_text && (!ids || !offsets)) || !p) throw q3::Error("synthesize: null argument");
     if (!cb) throw q3::Error("synthesize_stream: null callback");
     if (chunk_frames < 1) throw q3::Error("synthesize_stream: chunk_frames must be positive");
     if (pcm_cap < 0) throw q3::Error("synthesize: negative pcm_cap");
@@ -864,7 +903,21 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     for (int b = 0; b < B; ++b) e.slot_release(b);
     std::vector<Prep> prep;
     std::vector<float> prompts, trailing;
-    assemble_prompts(e, n_utt, ids, offsets, lang, speakers, instruct_ids, instruct_offsets, prep, prompts, trailing);
+    if (!live_text) assemble_prompts(e, n_utt, ids, offsets, lang, speakers, instruct_ids, instruct_offsets, prep, prompts, trailing);
+    else { prep.assign((size_t)n_utt, Prep()); for (int u = 0; u < n_utt; ++u) prep[(size_t)u].S = 16; }   // the most a prompt takes, for the page checks; set at admission
+    // live text: what each utterance has received (got), whether its source is done, and how many ids are in its slot (prompt or appended).
+    // The last two ids received are the chat template's tail once the text closes (every entry drops them): held back while it is open.
+    std::vector<std::vector<int64_t>> got((size_t)(live_text ? n_utt : 0));
+    std::vector<uint8_t> t_closed((size_t)n_utt, 0), t_sealed((size_t)n_utt, 0);
+    std::vector<int> t_fed((size_t)n_utt, 0);
+    std::vector<uint8_t> t_gave((size_t)n_utt, 0);   // the source returned ids (or closed) at this turn's poll
+    std::vector<int32_t> flim((size_t)h->e->B, 0), held((size_t)h->e->B, 0), target((size_t)h->e->B, 0), deliv((size_t)h->e->B, 0);
+    auto usable = [&](int u) { const int n = (int)got[(size_t)u].size(); return t_closed[(size_t)u] ? std::max(4, n - 2) : std::max(0, n - 2); };
+    auto admissible = [&](int u) { return !live_text || usable(u) >= 5 || (t_closed[(size_t)u] && got[(size_t)u].size() >= 4); };
+    std::vector<int64_t> poll_ids(256), app_ids;
+    std::vector<int32_t> app_slots, app_off;
+    std::vector<uint8_t> app_close;
+    std::vector<int32_t> tl_host((size_t)B, 0), nf_host((size_t)B, 0);   // live text: each live slot's text rows and frames as of the last look
     auto cap_of = [&](int u) { return max_new_per_utt ? std::min(std::max(1, (int)max_new_per_utt[u]), p->max_new_tokens) : p->max_new_tokens; };
     std::deque<int> pending;
     for (int u = 0; u < n_utt; ++u) {
@@ -887,15 +940,108 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     std::vector<q3::SlotState> st;
     int live = 0;
     e.sched_admitted = e.sched_preempted = 0; e.sched_peak_live = 0;
+    // Live text: audio leaves in the pushes q3tts_synthesize_stream_host makes — frames up to the next multiple of chunk_frames, one
+    // push per round — so a text that arrives in time gives the very samples of the whole text.  Frames past the last multiple
+    // wait (held), except those of a finished slot (its tail) and of a starved slot whose source had nothing this turn (a
+    // silent source must not hold audio back).  Without live text there is one round and every slot is at its frame count.
+    auto plan_delivery = [&]() {   // live text: how far each live slot's audio may go this turn
+        for (int b = 0; b < B; ++b) {
+            const int u = slot_utt[(size_t)b];
+            if (u < 0) continue;
+            const q3::SlotState& s = st[(size_t)b];
+            const bool fin = s.finished || s.n_frames >= s.max_frames;
+            const bool flush = fin || (s.text_open && s.n_frames >= s.trailing_len && !t_gave[(size_t)u]);
+            target[(size_t)b] = flush ? s.n_frames : s.n_frames / cf * cf;
+            nf_host[(size_t)b] = s.n_frames;
+        }
+    };
+    // one push per live slot with frames to deliver (live text: up to its limit of this round) and the callbacks behind it; a finished
+    // slot is retired with its last frames.  false: no slot had anything left.
+    auto deliver_round = [&](bool first) -> bool {
+        slots.clear();
+        for (int b = 0; b < B; ++b) {
+            if (slot_utt[(size_t)b] < 0) continue;
+            const q3::SlotState& s = st[(size_t)b];
+            const bool fin = s.finished || s.n_frames >= s.max_frames;
+            if (live_text) {
+                if (!(deliv[(size_t)b] < target[(size_t)b] || (fin && first))) continue;   // nothing of this slot leaves in this round
+                flim[slots.size()] = std::min(target[(size_t)b], (deliv[(size_t)b] / cf + 1) * cf);
+            }
+            pcm_ptr[slots.size()] = chunk_pcm.data() + slots.size() * (size_t)chunk_cap;
+            slots.push_back(b);
+        }
+        if (slots.empty()) return false;
+        e.slots_codec_decode_new((int)slots.size(), slots.data(), pcm_ptr.data(), chunk_cap, plen.data(), fb.data(), fe.data(), live_text ? flim.data() : nullptr);
+        for (size_t i = 0; i < slots.size(); ++i) {
+            const int b = slots[i], u = slot_utt[(size_t)b];
+            const q3::SlotState& s = st[(size_t)b];
+            // live text: finished AND its last frames are in this round; without live text fe[i] is always the frame count
+            const bool fin = (s.finished || s.n_frames >= s.max_frames) && (!live_text || fe[i] >= s.n_frames);
+            deliv[(size_t)b] = fe[i];
+            held[(size_t)b] = fin ? 0 : s.n_frames - fe[i];
+            if (plen[i] > chunk_cap) throw q3::Error("synthesize_stream: a chunk produced more samples than its buffer holds");
+            if (pcm_out && pcm_out[u] && plen[i] > 0 && written[(size_t)u] < pcm_cap)
+                memcpy(pcm_out[u] + written[(size_t)u], pcm_ptr[i], (size_t)std::min(plen[i], pcm_cap - written[(size_t)u]) * sizeof(float));
+            written[(size_t)u] += plen[i];
+            if (fin) {   // retired before the callback: whatever it does, the slot is free and the outputs are complete
+                if (n_frames) n_frames[u] = s.n_frames;
+                if (pcm_len) pcm_len[u] = written[(size_t)u];
+                if (codes_out) e.slot_codes(b, codes_out + (size_t)u * p->max_new_tokens * G, p->max_new_tokens);
+                e.slot_release(b);
+                slot_utt[(size_t)b] = -1;
+                deliv[(size_t)b] = 0;
+                --live;
+            }
+            if (plen[i] > 0 || fin)
+                if (cb(user, u, fb[i], fe[i], pcm_ptr[i], plen[i], fin ? 1 : 0) != 0) throw q3::Error("cancelled by callback");
+        }
+        return true;
+    };
     try {
         while (!pending.empty() || live > 0) {
             fresh.clear();
+            bool skip_decode = false;
+            if (live_text) {   // poll every utterance whose text is open, live or queued
+                for (int u = 0; u < n_utt; ++u) {
+                    if (t_closed[(size_t)u]) continue;
+                    bool known = false;
+                    for (int b = 0; b < B && !known; ++b) known = slot_utt[(size_t)b] == u;
+                    for (size_t i = 0; i < pending.size() && !known; ++i) known = pending[i] == u;
+                    if (!known) continue;
+                    int32_t n_new = 0, cl = 0;
+                    t_gave[(size_t)u] = 0;
+                    if (tcb(tuser, u, poll_ids.data(), (int)poll_ids.size(), &n_new, &cl) != 0) throw q3::Error("cancelled by callback");
+                    if (n_new < 0 || n_new > (int)poll_ids.size()) throw q3::Error("synthesize_live: the text callback returned a bad id count");
+                    got[(size_t)u].insert(got[(size_t)u].end(), poll_ids.begin(), poll_ids.begin() + n_new);
+                    t_gave[(size_t)u] = n_new > 0 || cl;
+                    if (cl) {
+                        t_closed[(size_t)u] = 1;
+                        if (got[(size_t)u].size() < 4) throw q3::Error("token sequence too short: need at least 4 ids (the reference indexes input_ids[3])");
+                    }
+                }
+            }
+            size_t n_ready = 0;   // queued utterances, from the front, that hold enough text to begin
+            while (n_ready < pending.size() && admissible(pending[n_ready])) ++n_ready;
             {   // admission in queue order, every utterance with the pages of its whole length
                 std::vector<int> free_slots, need;
                 for (int b = 0; b < B; ++b) if (slot_utt[(size_t)b] < 0) free_slots.push_back(b);
-                for (size_t i = 0; i < pending.size() && i < free_slots.size(); ++i) need.push_back(e.kv_pages_for(pl(pending[i]) + prep[(size_t)pending[i]].S + cap_of(pending[i])));
+                for (size_t i = 0; i < n_ready && i < free_slots.size(); ++i) need.push_back(e.kv_pages_for(pl(pending[i]) + prep[(size_t)pending[i]].S + cap_of(pending[i])));
                 const int n_adm = q3::sched_admit_count(e.kv, need, (int)free_slots.size(), live, true);
                 for (int i = 0; i < n_adm; ++i) { slot_utt[(size_t)free_slots[(size_t)i]] = pending.front(); pending.pop_front(); fresh.push_back(free_slots[(size_t)i]); }
+            }
+            if (live_text && !fresh.empty()) {   // the prompts of this look's admissions, from the ids they hold now (build_prompt_open)
+                prompts.assign(fresh.size() * 16 * (size_t)H, 0.f);
+                size_t trow = 0;
+                for (size_t i = 0; i < fresh.size(); ++i) { prep[(size_t)slot_utt[(size_t)fresh[i]]].toff = trow; trow += (size_t)std::max(1, usable(slot_utt[(size_t)fresh[i]]) - 4); }
+                trailing.assign(trow * (size_t)H, 0.f);
+                for (size_t i = 0; i < fresh.size(); ++i) {
+                    const int u = slot_utt[(size_t)fresh[i]], nu = usable(u);
+                    Prep& pr = prep[(size_t)u];
+                    pr.poff = i * 16;
+                    e.build_prompt_open(got[(size_t)u].data(), nu, lang, speakers ? speakers[u] : nullptr, prompts.data() + pr.poff * H, &pr.S,
+                                        trailing.data() + pr.toff * H, e.max_trailing, &pr.nt);
+                    t_fed[(size_t)u] = nu;
+                }
             }
             if (!fresh.empty()) {
                 init.assign(fresh.size(), Engine::SlotInit());
@@ -923,31 +1069,43 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
                 e.sched_admitted += (int64_t)fresh.size();
                 e.sched_peak_live = std::max(e.sched_peak_live, live);
             }
-            if (live == 0) throw q3::Error("synthesize_stream: no utterance could be admitted");
-            e.decode_steps(chunk_frames);
-            slots.clear();
-            for (int b = 0; b < B; ++b) if (slot_utt[(size_t)b] >= 0) { pcm_ptr[slots.size()] = chunk_pcm.data() + slots.size() * (size_t)chunk_cap; slots.push_back(b); }
-            e.slots_codec_decode_new((int)slots.size(), slots.data(), pcm_ptr.data(), chunk_cap, plen.data(), fb.data(), fe.data());
-            e.slots_state(B, st);
-            for (size_t i = 0; i < slots.size(); ++i) {
-                const int b = slots[i], u = slot_utt[(size_t)b];
-                const q3::SlotState& s = st[(size_t)b];
-                const bool fin = s.finished || s.n_frames >= s.max_frames;
-                if (plen[i] > chunk_cap) throw q3::Error("synthesize_stream: a chunk produced more samples than its buffer holds");
-                if (pcm_out && pcm_out[u] && plen[i] > 0 && written[(size_t)u] < pcm_cap)
-                    memcpy(pcm_out[u] + written[(size_t)u], pcm_ptr[i], (size_t)std::min(plen[i], pcm_cap - written[(size_t)u]) * sizeof(float));
-                written[(size_t)u] += plen[i];
-                if (fin) {   // retired before the callback: whatever it does, the slot is free and the outputs are complete
-                    if (n_frames) n_frames[u] = s.n_frames;
-                    if (pcm_len) pcm_len[u] = written[(size_t)u];
-                    if (codes_out) e.slot_codes(b, codes_out + (size_t)u * p->max_new_tokens * G, p->max_new_tokens);
-                    e.slot_release(b);
-                    slot_utt[(size_t)b] = -1;
-                    --live;
+            if (live_text) {
+                for (int b : fresh) { e.slot_text_open(b); tl_host[(size_t)b] = prep[(size_t)slot_utt[(size_t)b]].nt; nf_host[(size_t)b] = 0; }
+                // the new ids of every live slot, and the close of those whose source is done, in one call
+                app_slots.clear(); app_ids.clear(); app_off.assign(1, 0); app_close.clear();
+                for (int b = 0; b < B; ++b) {
+                    const int u = slot_utt[(size_t)b];
+                    if (u < 0 || t_sealed[(size_t)u]) continue;
+                    const int nu = usable(u);
+                    if (nu == t_fed[(size_t)u] && !t_closed[(size_t)u]) continue;
+                    app_slots.push_back(b);
+                    app_ids.insert(app_ids.end(), got[(size_t)u].begin() + t_fed[(size_t)u], got[(size_t)u].begin() + nu);
+                    app_off.push_back((int32_t)app_ids.size());
+                    app_close.push_back(t_closed[(size_t)u]);
+                    tl_host[(size_t)b] += nu - t_fed[(size_t)u] + (t_closed[(size_t)u] ? 1 : 0);
+                    t_fed[(size_t)u] = nu;
+                    if (t_closed[(size_t)u]) t_sealed[(size_t)u] = 1;
                 }
-                if (plen[i] > 0 || fin)
-                    if (cb(user, u, fb[i], fe[i], pcm_ptr[i], plen[i], fin ? 1 : 0) != 0) throw q3::Error("cancelled by callback");
+                if (!app_slots.empty()) e.slots_text_append((int)app_slots.size(), app_slots.data(), nullptr, app_ids.data(), app_off.data(), app_close.data());
+                if (live == 0) {
+                    if (n_ready > 0) throw q3::Error("synthesize_stream: no utterance could be admitted");
+                    continue;   // every queued utterance waits for text: poll again
+                }
+                bool all_starved = true;
+                for (int b = 0; b < B && all_starved; ++b) {
+                    const int u = slot_utt[(size_t)b];
+                    if (u >= 0 && (t_sealed[(size_t)u] || nf_host[(size_t)b] < tl_host[(size_t)b])) all_starved = false;
+                }
+                bool any_held = false;   // frames generated but not delivered yet (held for the chunk cadence, below)
+                for (int b = 0; b < B; ++b) if (slot_utt[(size_t)b] >= 0 && held[(size_t)b] > 0) any_held = true;
+                if (all_starved && !any_held) continue;   // nothing would move: poll again at once
+                skip_decode = all_starved;                // no step would move a slot, but a silent source releases the held frames
             }
+            if (live == 0) throw q3::Error("synthesize_stream: no utterance could be admitted");
+            if (!skip_decode) e.decode_steps(chunk_frames);
+            e.slots_state(B, st);
+            if (live_text) plan_delivery();
+            for (bool first = true; deliver_round(first) && live_text; first = false) { }
         }
     } catch (...) {
         for (int b = 0; b < B; ++b) { try { e.slot_release(b); } catch (...) { } }

@@ -1109,7 +1109,8 @@ void Engine::codec_stream_push_batch_host(int n_streams, const int32_t* sids, co
 
 // For every listed slot: the frames generated since the slot's previous streaming call, through the slot's implicit stream (the one
 // slot_codec_stream_range uses: the two interleave), all slots in batched passes.  The codes are read where the sampler wrote them.
-void Engine::slots_codec_decode_new(int n_slots, const int32_t* slots, float* const* pcm_out, int64_t cap, int64_t* pcm_len, int32_t* frame_begin, int32_t* frame_end) {
+void Engine::slots_codec_decode_new(int n_slots, const int32_t* slots, float* const* pcm_out, int64_t cap, int64_t* pcm_len, int32_t* frame_begin, int32_t* frame_end,
+                                   const int32_t* frame_limit) {
     if (!codec) throw Error("codec decoder not finalized");
     if (n_slots < 0) throw Error("slots_codec_decode_new: negative slot count");
     if (n_slots == 0) return;
@@ -1125,8 +1126,12 @@ void Engine::slots_codec_decode_new(int n_slots, const int32_t* slots, float* co
     if ((int)W.slot_stream.size() < B) W.slot_stream.assign((size_t)B, -1);
     std::vector<StreamPush> ps((size_t)n_slots);
     for (int i = 0; i < n_slots; ++i) {
-        const int slot = slots[i], nf = st[(size_t)slot].active ? std::min(st[(size_t)slot].n_frames, max_frames_cap) : 0;
+        const int slot = slots[i];
+        int nf = st[(size_t)slot].active ? std::min(st[(size_t)slot].n_frames, max_frames_cap) : 0;
         int sid = W.slot_stream[(size_t)slot];
+        // frame_limit (the live-text scheduler): frames past it wait for a later call; never below what the stream has already pushed
+        if (frame_limit && sid >= 0 && W.streams[(size_t)sid].used && W.streams[(size_t)sid].n_done <= nf) nf = std::min(nf, std::max(frame_limit[i], W.streams[(size_t)sid].n_done));
+        else if (frame_limit) nf = std::min(nf, std::max(frame_limit[i], 0));
         if (sid < 0 || !W.streams[(size_t)sid].used || W.streams[(size_t)sid].n_done > nf) {   // first call of the utterance, or a restart
             if (sid >= 0 && W.streams[(size_t)sid].used) codec_stream_end(sid);
             sid = codec_stream_begin(max_frames_cap);

@@ -246,8 +246,8 @@ struct SlotState { // device-resident per-slot generation state
     float rep_penalty;    // repetition penalty on code0 (group 0 sampler); 0 and 1 = off
     uint64_t seed;
     int32_t prefix_len;   // rows of a shared prompt prefix in front of the prompt (0: none): the talker position is prefix_len + prompt_len + frame
-    uint32_t pad1;    // 64 bytes: read by the sampler as four 16-byte loads
-};
+    uint32_t text_open;   // 0: frames at or beyond trailing_len take tts_pad; 1: more text may arrive (live text), the slot stalls there instead
+};                        // 64 bytes: read by the sampler as four 16-byte loads
 static_assert(sizeof(SlotState) == 64, "SlotState must be 64 bytes");
 
 struct SampleArgs {
@@ -325,6 +325,19 @@ void launch_copy_rows(const float* src, int lds, float* dst, int ldd, int rows, 
 void launch_copy_rows_masked(const float* src, int lds, float* dst, int ldd, int rows, int cols, const int* flags_dev, hipStream_t s);
 void launch_bump_u32(unsigned* counter, hipStream_t s);   // *counter += 1 (the split-K seam's step generation outside the fused step)
 void launch_count_active(const SlotState* st, int nb, int32_t* out, hipStream_t s);
+
+// Live text (reference tts_onnx.cpp:531-536 builds the trailing block once; :833-842 reads row `frame` of it): new text rows of n slots
+// go behind the rows each slot already holds, in one launch.  desc: n records of 8 ints {slot, src0, n_rows, dst0, close, 0, 0, 0} —
+// rows [src0, src0 + n_rows) of `rows` ([.][H], end to end) land in trailing[slot][dst0 .. dst0 + n_rows); with close the tts_eos row
+// follows them; then SlotState::trailing_len = dst0 + n_rows + close and text_open = !close.  Rows at or past max_trailing are dropped
+// (the caller validates; the kernel never writes outside the slot's block).
+struct TextScatterArgs {
+    const float* rows = nullptr; const int32_t* desc = nullptr; int n = 0, max_rows = 0;   // max_rows: the largest n_rows + close of the call
+    float* trailing = nullptr; int max_trailing = 0, H = 0, n_slots = 0;
+    const float* tts_eos = nullptr;
+    SlotState* st = nullptr;
+};
+void launch_text_scatter(const TextScatterArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // codec decoder launchers (q3_codec_kernels.hip)

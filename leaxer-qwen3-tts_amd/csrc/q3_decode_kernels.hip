@@ -3044,6 +3044,28 @@ __global__ __launch_bounds__(256) void k_sample(const float* plogits, SlotState*
     if (st) {
         if (!sl.active || sl.finished) return;
         if (a.group == 0 && sl.n_frames >= sl.max_frames) { if (tid == 0) st->finished = 1; return; }
+        if (sl.text_open && sl.n_frames >= sl.trailing_len) {   // live text: the frame's text row has not arrived, the slot stalls this step (all n_groups samplers alike)
+            // The talker decodes the slot's row in this step all the same, and its residual stream runs in place: x_talk holds the last
+            // layer's output, not the row of the frame before.  The last sampler puts that row back — the frame's running sum (groups
+            // 0 .. n_groups - 2 left it in `sum`), the recorded last code's embedding and the frame's text row, added as the epilogue below
+            // adds them — so the talker rewrites the same K / V row, logits row and last-hidden row: the step changes nothing.
+            if (a.group == a.n_groups - 1 && a.group != 0 && sl.n_frames > 0) {
+                const int f = sl.n_frames - 1;
+                int tk = a.codes[((size_t)b * a.max_frames_cap + f) * a.n_groups + a.group];
+                tk = tk < 0 ? 0 : (tk < V ? tk : V - 1);
+                const bf16_t* er = a.embed + (size_t)tk * a.H;
+                const float* text = f < sl.trailing_len ? a.trailing + ((size_t)b * a.max_trailing + f) * a.H : a.tts_pad;
+                for (int h = tid * 4; h < a.H; h += 1024) {
+                    const uint2 raw = *reinterpret_cast<const uint2*>(er + h);
+                    const float4 sm = *reinterpret_cast<const float4*>(a.sum + (size_t)b * a.H + h);
+                    const float4 tx = *reinterpret_cast<const float4*>(text + h);
+                    const float e0 = __uint_as_float(raw.x << 16), e1 = __uint_as_float(raw.x & 0xFFFF0000u);
+                    const float e2 = __uint_as_float(raw.y << 16), e3 = __uint_as_float(raw.y & 0xFFFF0000u);
+                    *reinterpret_cast<float4*>(a.x_talk + (size_t)b * a.H + h) = make_float4((sm.x + e0) + tx.x, (sm.y + e1) + tx.y, (sm.z + e2) + tx.z, (sm.w + e3) + tx.w);
+                }
+            }
+            return;
+        }
         temperature = sl.temperature; top_p = sl.top_p; top_k = sl.top_k;
         frame = sl.n_frames;
         u = rng_uniform_dev(sl.seed, sl.stream_id, (uint32_t)frame, (uint32_t)a.group);
@@ -3564,6 +3586,31 @@ void launch_copy_rows_masked(const float* src, int lds, float* dst, int ldd, int
 }
 __global__ void k_bump_u32(unsigned* p) { *p += 1u; }
 void launch_bump_u32(unsigned* counter, hipStream_t s) { hipLaunchKernelGGL(k_bump_u32, dim3(1), dim3(1), 0, s, counter); }
+
+// live text (TextScatterArgs, q3_common.h): workgroup (i, y) copies rows y, y + gridDim.y, ... of record i as 16-byte units
+__global__ __launch_bounds__(256) void k_text_scatter(const TextScatterArgs a) {
+    const int32_t* d = a.desc + (size_t)blockIdx.x * 8;
+    const int slot = d[0], src0 = d[1], n_rows = d[2], dst0 = d[3], close = d[4] ? 1 : 0;
+    if (slot < 0 || slot >= a.n_slots || n_rows < 0 || dst0 < 0 || src0 < 0) return;
+    float* dst_b = a.trailing + (size_t)slot * a.max_trailing * a.H;
+    for (int r = blockIdx.y; r < n_rows + close; r += gridDim.y) {
+        if (dst0 + r >= a.max_trailing) break;
+        const float* src = r < n_rows ? a.rows + (size_t)(src0 + r) * a.H : a.tts_eos;
+        float* dst = dst_b + (size_t)(dst0 + r) * a.H;
+        for (int h = threadIdx.x * 4; h < a.H; h += 1024) *reinterpret_cast<float4*>(dst + h) = *reinterpret_cast<const float4*>(src + h);
+    }
+    if (blockIdx.y == 0 && threadIdx.x == 0) {
+        SlotState* st = a.st + slot;
+        st->trailing_len = min(dst0 + n_rows + close, a.max_trailing);
+        st->text_open = close ? 0u : 1u;
+    }
+}
+void launch_text_scatter(const TextScatterArgs& a, hipStream_t s) {
+    if (a.n <= 0) return;
+    if (!a.desc || !a.trailing || !a.st || !a.tts_eos || (a.max_rows > 0 && !a.rows)) throw Error("text_scatter: bad arguments");
+    if (a.H < 4 || a.H % 4 || a.max_trailing < 1 || a.n_slots < 1 || a.max_rows < 0) throw Error("text_scatter: dims out of range");
+    hipLaunchKernelGGL(k_text_scatter, dim3(a.n, std::max(1, std::min(a.max_rows, 32))), dim3(256), 0, s, a);
+}
 
 __global__ void k_count_active(const SlotState* st, int nb, int32_t* out) {
     int n = 0;

@@ -268,6 +268,7 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
     logits_p = fm((size_t)16 * std::max(c.vocab, c.sub_vocab));
     trailing_d = fm((size_t)B * max_trailing * H);
     tts_pad_d = fm(H);
+    tts_eos_d = fm(H);
     text_tmp = fm((size_t)16 * c.text_hidden);
     text_tmp2 = fm((size_t)16 * c.text_hidden);
     ldp = (std::max(std::max(H, AO), std::max(c.ffn, c.cp_ffn)) + 7) / 8 * 8;
@@ -299,6 +300,8 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
     Q3_HIP_CHECK(hipMemsetAsync(talker_pos_d, 0, (size_t)B * sizeof(int32_t), stream));
     st_d = (SlotState*)dmalloc((size_t)B * sizeof(SlotState));
     st_h.assign(B, SlotState{});
+    stepped_h.assign(B, 0);
+    text_desc_d = (int32_t*)dmalloc((size_t)B * 8 * sizeof(int32_t));
     Q3_HIP_CHECK(hipMemsetAsync(st_d, 0, (size_t)B * sizeof(SlotState), stream));
     seen_ld = (c.vocab + 31) / 32;   // repetition penalty: one bit per code0 id and slot, cleared when the slot is armed
     seen_d = (uint32_t*)dmalloc((size_t)B * seen_ld * sizeof(uint32_t));
@@ -572,6 +575,12 @@ void Engine::finalize() {
         text_project(&id, 1, pad.data());
         Q3_HIP_CHECK(hipMemcpy(tts_pad_d, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
     }
+    if (TTS_EOS < c.text_vocab) {   // the row behind a closed text (:535), for k_text_scatter
+        int64_t id = TTS_EOS;
+        text_project_dev(&id, 1);
+        Q3_HIP_CHECK(hipMemcpyAsync(tts_eos_d, proj_out_d, (size_t)c.hidden * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        sync();
+    }
     for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
     graphs.clear();
 }
@@ -823,23 +832,28 @@ int Engine::head_proj(const bf16_t* Wm, const float* x, int ldx, const float* ga
 // All rows in one go: ids uploaded once, 16-row blocks (the last one padded with a repeat of the last id) through gather + fc1 + fc2
 // without a host round trip in between, one copy back.  Every block has the same shape, so a token's row does not depend on where in
 // the list — or in which job — it was projected.
-void Engine::text_project(const int64_t* ids, int n, float* out) {
+void Engine::proj_reserve(size_t rows) {
+    if (proj_cap >= rows) return;
+    sync();
+    if (proj_ids_d) (void)hipFree(proj_ids_d);
+    if (proj_out_d) (void)hipFree(proj_out_d);
+    proj_ids_d = nullptr; proj_out_d = nullptr; proj_cap = 0;
+    const size_t cap = std::max(rows, (size_t)256);
+    Q3_HIP_CHECK(hipMalloc((void**)&proj_ids_d, cap * sizeof(int64_t)));
+    Q3_HIP_CHECK(hipMalloc((void**)&proj_out_d, cap * (size_t)c.hidden * sizeof(float)));
+    proj_cap = cap;
+}
+
+void Engine::text_project_dev(const int64_t* ids, int n) {
     if (!finalized) throw Error("weights not finalized");
     if (n <= 0) return;
     const int TH = c.text_hidden, H = c.hidden;
     for (int i = 0; i < n; ++i) if (ids[i] < 0 || ids[i] >= c.text_vocab) throw Error("text id out of range");
     const int np = (n + 15) / 16 * 16;
-    if (proj_cap < (size_t)np) {
-        sync();
-        if (proj_ids_d) (void)hipFree(proj_ids_d);
-        if (proj_out_d) (void)hipFree(proj_out_d);
-        proj_cap = (size_t)std::max(np, 256);
-        Q3_HIP_CHECK(hipMalloc((void**)&proj_ids_d, proj_cap * sizeof(int64_t)));
-        Q3_HIP_CHECK(hipMalloc((void**)&proj_out_d, proj_cap * H * sizeof(float)));
-    }
-    std::vector<int64_t> padded((size_t)np, ids[n - 1]);
-    memcpy(padded.data(), ids, (size_t)n * sizeof(int64_t));
-    Q3_HIP_CHECK(hipMemcpyAsync(proj_ids_d, padded.data(), (size_t)np * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    proj_reserve((size_t)np);
+    proj_ids_h.assign((size_t)np, ids[n - 1]);   // outlives the upload: every caller synchronises before the next projection
+    memcpy(proj_ids_h.data(), ids, (size_t)n * sizeof(int64_t));
+    Q3_HIP_CHECK(hipMemcpyAsync(proj_ids_d, proj_ids_h.data(), (size_t)np * sizeof(int64_t), hipMemcpyHostToDevice, stream));
     for (int i0 = 0; i0 < np; i0 += 16) {
         launch_gather_rows_bf16(text_embed, TH, proj_ids_d + i0, 16, text_tmp, TH, stream);
         GemvArgs a;
@@ -849,8 +863,13 @@ void Engine::text_project(const int64_t* ids, int n, float* out) {
         b.W = fc2_w; b.x = text_tmp2; b.ldx = TH; b.bias = fc2_b; b.out = proj_out_d + (size_t)i0 * H; b.ldo = H; b.M = 16; b.N = H; b.K = TH; b.epi = EPI_BIAS;
         launch_gemv(b, stream);
     }
-    Q3_HIP_CHECK(hipMemcpyAsync(out, proj_out_d, (size_t)n * H * sizeof(float), hipMemcpyDeviceToHost, stream));
-    sync();   // also keeps `padded` alive until the upload is done
+}
+
+void Engine::text_project(const int64_t* ids, int n, float* out) {
+    if (n <= 0) { if (!finalized) throw Error("weights not finalized"); return; }
+    text_project_dev(ids, n);
+    Q3_HIP_CHECK(hipMemcpyAsync(out, proj_out_d, (size_t)n * c.hidden * sizeof(float), hipMemcpyDeviceToHost, stream));
+    sync();
 }
 
 void Engine::codec_embed(const int64_t* ids, int n, float* out) {
@@ -1284,6 +1303,18 @@ void Engine::build_prompt(const int64_t* ids, int n_ids, int lang, const float* 
     build_prompts(ids, offsets, 1, lang, speaker ? spk : nullptr, prompt, S, trailing, &toff, n_trailing);
 }
 
+// build_prompt for a text whose end is not known (live text): the same rows for the same first four ids, every later id a trailing row
+// (:531-534 without the tts_eos row of :535, which k_text_scatter appends when the text is closed)
+void Engine::build_prompt_open(const int64_t* ids, int n_ids, int lang, const float* speaker, float* prompt, int* S,
+                               float* trailing, int cap_rows, int* n_trailing) {
+    if (n_ids < 4) throw Error("token sequence too short: need at least 4 ids (the reference indexes input_ids[3])");
+    if (n_ids - 4 > cap_rows) throw Error("text too long for the trailing buffer");
+    const int32_t offsets[2] = { 0, n_ids };
+    const size_t toff = 0;
+    const float* spk[1] = { speaker };
+    build_prompts(ids, offsets, 1, lang, speaker ? spk : nullptr, prompt, S, trailing, &toff, n_trailing, true);
+}
+
 // ------------------------------------------------------------------------------------------------
 // fused generation: one frame = sampler + (n_groups-1) predictor passes + talker decode
 // ------------------------------------------------------------------------------------------------
@@ -1292,7 +1323,7 @@ void Engine::build_prompt(const int64_t* ids, int n_ids, int lang, const float* 
 // the host (tts_onnx.cpp:442-539, same order as build_prompt).  prompts: [n_utt][16][hidden]; trailing rows of utterance u start at row
 // toff[u] of `trailing`.
 void Engine::build_prompts(const int64_t* ids, const int32_t* offsets, int n_utt, int lang, const float* const* speakers,
-                           float* prompts, int* S_out, float* trailing, const size_t* toff, int* nt_out) {
+                           float* prompts, int* S_out, float* trailing, const size_t* toff, int* nt_out, bool open_text) {
     const int H = c.hidden;
     std::vector<int64_t> all = { TTS_BOS, TTS_EOS, TTS_PAD };
     std::vector<size_t> first((size_t)n_utt);
@@ -1300,7 +1331,8 @@ void Engine::build_prompts(const int64_t* ids, const int32_t* offsets, int n_utt
         const int n_ids = offsets[u + 1] - offsets[u];
         if (n_ids < 4) throw Error("token sequence too short: need at least 4 ids (the reference indexes input_ids[3])");
         first[(size_t)u] = all.size();
-        const int used = std::max(4, n_ids - 2);                  // ids[0..2] role, ids[3] first text, ids[4 .. n-2) trailing
+        // ids[0..2] role, ids[3] first text, ids[4 .. n-2) trailing; open text (build_prompt_open): the end is not known, ids[4 .. n) trailing
+        const int used = open_text ? n_ids : std::max(4, n_ids - 2);
         if (used - 4 + 1 > max_trailing) throw Error("text too long for the trailing buffer");
         all.insert(all.end(), ids + offsets[u], ids + offsets[u] + used);
     }
@@ -1335,10 +1367,11 @@ void Engine::build_prompts(const int64_t* ids, const int32_t* offsets, int n_utt
         for (int j = 0; j < H; ++j) prompt[(size_t)row * H + j] = ft[j] + ce[(size_t)(pad_count + 1) * H + j]; // :519-520
         ++row;
         S_out[u] = row;
-        int nt = (n_ids - 2) - 4;                                                                  // text_end - (text_start + 1), :531-534
+        int nt = (open_text ? n_ids : n_ids - 2) - 4;                                              // text_end - (text_start + 1), :531-534
         if (nt < 0) nt = 0;
         float* tr = trailing + toff[u] * H;
         if (nt > 0) memcpy(tr, rows + (size_t)4 * H, (size_t)nt * H * sizeof(float));
+        if (open_text) { nt_out[u] = nt; continue; }                                               // no tts_eos row: the text is still open
         memcpy(tr + (size_t)nt * H, tts_eos, (size_t)H * sizeof(float));                           // :535
         nt_out[u] = nt + 1;                                                                        // :536
     }
@@ -1438,6 +1471,7 @@ void Engine::stage_profile(int n_steps, double* out) {
     if (!finalized) throw Error("weights not finalized");
     const int nb = nb_in_use(), G = c.n_groups;
     if (nb == 0 || n_steps < 1) throw Error("stage_profile: no armed slot");
+    check_text_and_mark_stepped(nb);
     const size_t n_marks = 2 + 2 * (size_t)(G - 1) + 1;   // before/after sample0, after each {predictor pass, its sample}, after the talker
     stage_ev.resize(n_marks);
     for (auto& e : stage_ev) Q3_HIP_CHECK(hipEventCreate(&e));
@@ -1493,6 +1527,7 @@ void Engine::step_logits(int slot, float* out, int cols) {
     const int nb = nb_in_use(), G = c.n_groups;
     if (nb == 0 || slot < 0 || slot >= nb) throw Error("step_logits: slot not armed");
     if (cols < std::max(c.vocab, c.sub_vocab)) throw Error("step_logits: row buffer too narrow");
+    check_text_and_mark_stepped(nb);
     float* buf = nullptr;
     Q3_HIP_CHECK(hipMalloc((void**)&buf, (size_t)G * cols * sizeof(float)));
     Q3_HIP_CHECK(hipMemsetAsync(buf, 0, (size_t)G * cols * sizeof(float), stream));
@@ -1623,7 +1658,7 @@ void Engine::slots_begin(const SlotInit* in, int n, const q3tts_sampling& p, uin
             Q3_HIP_CHECK(hipMemcpyAsync(trailing_d + (size_t)q.slot * max_trailing * H, q.trailing, (size_t)q.n_trailing * H * sizeof(float), hipMemcpyHostToDevice, stream));
         slot_codec_stream_reset(q.slot);   // a new utterance: its streaming vocoder state starts over
         SlotState& s = st_h[q.slot];
-        s.n_frames = 0; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.prefix_len = 0; s.trailing_len = q.n_trailing;
+        s.n_frames = 0; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.prefix_len = 0; s.trailing_len = q.n_trailing; s.text_open = 0; stepped_h[q.slot] = 0;
         s.max_frames = q.max_frames > 0 ? std::min(q.max_frames, p.max_new_tokens) : p.max_new_tokens;
         s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
         // a new utterance (a re-admission after a preemption included) starts with an empty code0 history: ordered before its first step
@@ -1723,7 +1758,7 @@ void Engine::slot_begin_forced(const SlotInit& q, const q3tts_sampling& p, uint6
     else prefill_rows_long(slot, x, R, nullptr, base);   // behind a shared prefix: the chunk path at base, whatever R
     slot_codec_stream_reset(slot);
     SlotState& s = st_h[slot];   // after the prefill, which writes prompt_len = R and n_frames = 0
-    s.n_frames = F0; s.finished = 0; s.active = 1; s.prompt_len = S; s.prefix_len = base; s.trailing_len = q.n_trailing;
+    s.n_frames = F0; s.finished = 0; s.active = 1; s.prompt_len = S; s.prefix_len = base; s.trailing_len = q.n_trailing; s.text_open = 0; stepped_h[slot] = 0;
     s.max_frames = F0 + new_cap;
     s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
     Q3_HIP_CHECK(hipMemcpyAsync(st_d + slot, &s, sizeof(SlotState), hipMemcpyHostToDevice, stream));
@@ -1923,7 +1958,7 @@ void Engine::slots_begin_prefixed(const SlotInit* in, int n, const q3tts_samplin
             Q3_HIP_CHECK(hipMemcpyAsync(trailing_d + (size_t)q.slot * max_trailing * H, q.trailing, (size_t)q.n_trailing * H * sizeof(float), hipMemcpyHostToDevice, stream));
         slot_codec_stream_reset(q.slot);
         SlotState& s = st_h[q.slot];
-        s.n_frames = 0; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.prefix_len = Pof[(size_t)i]; s.trailing_len = q.n_trailing;
+        s.n_frames = 0; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.prefix_len = Pof[(size_t)i]; s.trailing_len = q.n_trailing; s.text_open = 0; stepped_h[q.slot] = 0;
         s.max_frames = cap_of(q);
         s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
         Q3_HIP_CHECK(hipMemsetAsync(seen_d + (size_t)q.slot * seen_ld, 0, (size_t)seen_ld * sizeof(uint32_t), stream));
@@ -2106,7 +2141,7 @@ void Engine::slots_begin_ragged(const SlotInit* in, int n, const q3tts_sampling&
         Q3_HIP_CHECK(hipMemcpyAsync(talker_pos_d + q.slot, &pos_h[(size_t)i], sizeof(int32_t), hipMemcpyHostToDevice, stream));
         slot_codec_stream_reset(q.slot);
         SlotState& s = st_h[q.slot];
-        s.n_frames = q.n_prefix; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.prefix_len = Pof[(size_t)i]; s.trailing_len = q.n_trailing;
+        s.n_frames = q.n_prefix; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.prefix_len = Pof[(size_t)i]; s.trailing_len = q.n_trailing; s.text_open = 0; stepped_h[q.slot] = 0;
         s.max_frames = q.n_prefix + cap_of(q);
         s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
         Q3_HIP_CHECK(hipMemcpyAsync(st_d + q.slot, &s, sizeof(SlotState), hipMemcpyHostToDevice, stream));
@@ -2118,6 +2153,7 @@ int Engine::decode_steps(int n_steps) {
     if (!finalized) throw Error("weights not finalized");
     int nb = nb_in_use();
     if (nb == 0) return 0;
+    if (n_steps > 0) check_text_and_mark_stepped(nb);
     // One captured graph per batch width: past 16 rows widths are rounded up to a multiple of 8 (the extra slots are unarmed, their rows
     // masked like any finished slot's), so a queue that drains from 64 slots to 17 replays 7 graphs instead of capturing 48.
     if (nb > 16) nb = std::min(B, (nb + 7) / 8 * 8);
@@ -2177,6 +2213,92 @@ void Engine::measure_skip_frames(int n) {
     launch_fill_synth(talker.kc, talker.kv_bf16 ? 1 : 0, total, 0x5EEDull, 0.f, 0.5f, stream);
     launch_fill_synth(talker.vc, talker.kv_bf16 ? 1 : 0, total, 0x5EEEull, 0.f, 0.5f, stream);
     sync();
+}
+
+// ------------------------------------------------------------------------------------------------
+// live text (q3_engine.h): open, append, status
+// ------------------------------------------------------------------------------------------------
+// A stalled step rewrites the slot's own talker row: its last sampler rebuilds the talker input row of the frame before (k_sample), the
+// position is unchanged, so the K / V row, the logits_t row and the last-hidden row come out as they were.  Before the slot's first step
+// those rows are the prefill's and the frame sum / talker_pos are not its own yet, so such a slot must not stall:
+// refused here, before anything is launched.  The mirror's n_frames is exact for a slot that has not stepped.
+void Engine::check_text_and_mark_stepped(int nb) {
+    for (int b = 0; b < nb && b < B; ++b) {
+        const SlotState& s = st_h[b];
+        if (s.active && s.text_open && !stepped_h[b] && s.trailing_len <= s.n_frames)
+            throw Error("slot " + std::to_string(b) + ": open text holds no row for the slot's first frame (append text or close it before the first step)");
+    }
+    for (int b = 0; b < nb && b < B; ++b) if (st_h[b].active) stepped_h[b] = 1;
+}
+
+void Engine::slot_text_open(int slot) {
+    if (!finalized) throw Error("weights not finalized");
+    if (slot < 0 || slot >= B) throw Error("slot out of range");
+    if (!st_h[slot].active) throw Error("slot_text_open: slot " + std::to_string(slot) + " is not armed");
+    if (c.hidden % 4) throw Error("slot_text_open: hidden must be a multiple of 4");
+    if (c.n_groups < 2) throw Error("slot_text_open: needs at least 2 code groups (a stalled slot's talker row is rebuilt by the last predictor sampler)");
+    // teacher-forced frames were built from the rows the begin held, tts_pad where it held none: rows appended there would never be read
+    if (st_h[slot].trailing_len < st_h[slot].n_frames)
+        throw Error("slot_text_open: slot " + std::to_string(slot) + " was begun behind " + std::to_string(st_h[slot].n_frames) + " forced frames with " +
+                    std::to_string(st_h[slot].trailing_len) + " text rows: the begin must hold the text rows of its forced frames");
+    if (stepped_h[slot]) throw Error("slot_text_open: slot " + std::to_string(slot) + " has stepped since its begin (open the text before the first step)");
+    st_h[slot].text_open = 1;
+    Q3_HIP_CHECK(hipMemcpyAsync(&st_d[slot].text_open, &st_h[slot].text_open, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    sync();
+}
+
+void Engine::slots_text_append(int n, const int32_t* slots, const float* rows, const int64_t* ids, const int32_t* offsets, const uint8_t* close) {
+    if (!finalized) throw Error("weights not finalized");
+    if (n <= 0) return;
+    if (!slots || !offsets || n > B) throw Error("text_append: bad arguments");
+    if (rows && n != 1) throw Error("text_append: projected rows are appended to one slot at a time");
+    const int H = c.hidden;
+    if (H % 4) throw Error("text_append: hidden must be a multiple of 4");
+    const int total = offsets[n] - offsets[0], o0 = offsets[0];
+    if (total > 0 && !rows && !ids) throw Error("text_append: null rows / ids");
+    std::vector<int32_t> desc((size_t)n * 8, 0);
+    int max_rows = 0;
+    for (int i = 0; i < n; ++i) {
+        const int b = slots[i], ni = offsets[i + 1] - offsets[i], cl = close && close[i] ? 1 : 0;
+        if (b < 0 || b >= B) throw Error("slot out of range");
+        if (ni < 0) throw Error("text_append: offsets must not decrease");
+        for (int k = 0; k < i; ++k) if (slots[k] == b) throw Error("text_append: slot " + std::to_string(b) + " is listed twice (duplicate slots)");
+        if (!st_h[b].active) throw Error("text_append: slot " + std::to_string(b) + " is not armed");
+        if (!st_h[b].text_open) throw Error("text_append: slot " + std::to_string(b) + ": text already closed");
+        if (st_h[b].trailing_len + ni + cl > max_trailing) throw Error("text too long for the trailing buffer");
+        int32_t* d = desc.data() + (size_t)i * 8;
+        d[0] = b; d[1] = offsets[i] - o0; d[2] = ni; d[3] = st_h[b].trailing_len; d[4] = cl;
+        max_rows = std::max(max_rows, ni + cl);
+    }
+    if (!rows) for (int k = 0; k < total; ++k) if (ids[o0 + k] < 0 || ids[o0 + k] >= c.text_vocab) throw Error("text_append: text id out of range [0, text_vocab)");
+    // nothing has moved up to here
+    if (total > 0) {
+        if (rows) {
+            proj_reserve((size_t)total);
+            Q3_HIP_CHECK(hipMemcpyAsync(proj_out_d, rows, (size_t)total * H * sizeof(float), hipMemcpyHostToDevice, stream));
+        } else text_project_dev(ids + o0, total);
+    }
+    Q3_HIP_CHECK(hipMemcpyAsync(text_desc_d, desc.data(), desc.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    TextScatterArgs a;
+    a.rows = proj_out_d; a.desc = text_desc_d; a.n = n; a.max_rows = max_rows;
+    a.trailing = trailing_d; a.max_trailing = max_trailing; a.H = H; a.n_slots = B; a.tts_eos = tts_eos_d; a.st = st_d;
+    if (max_rows > 0 && !a.rows) { proj_reserve(1); a.rows = proj_out_d; }
+    launch_text_scatter(a, stream);
+    sync();   // desc / rows are the caller's and this frame's
+    for (int i = 0; i < n; ++i) {
+        const int32_t* d = desc.data() + (size_t)i * 8;
+        st_h[d[0]].trailing_len = d[3] + d[2] + d[4];
+        st_h[d[0]].text_open = d[4] ? 0u : 1u;
+    }
+}
+
+void Engine::slot_text_status(int slot, int* n_text_rows, int* open, int* starved) {
+    if (slot < 0 || slot >= B) throw Error("slot out of range");
+    SlotState s;
+    Q3_HIP_CHECK(hipMemcpy(&s, st_d + slot, sizeof(SlotState), hipMemcpyDeviceToHost));
+    if (n_text_rows) *n_text_rows = s.trailing_len;
+    if (open) *open = s.text_open ? 1 : 0;
+    if (starved) *starved = s.text_open && s.n_frames >= s.trailing_len ? 1 : 0;
 }
 
 void Engine::slots_state(int nb, std::vector<SlotState>& out) {   // one copy for the whole batch (the scheduler polls it between step chunks)

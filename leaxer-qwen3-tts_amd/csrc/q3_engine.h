@@ -127,8 +127,9 @@ public:
     void build_prompt(const int64_t* ids, int n_ids, int lang, const float* speaker, float* prompt, int* S,
                       float* trailing, int cap_rows, int* n_trailing);
     void build_prompts(const int64_t* ids, const int32_t* offsets, int n_utt, int lang, const float* const* speakers,
-                       float* prompts, int* S_out, float* trailing, const size_t* toff, int* nt_out);
+                       float* prompts, int* S_out, float* trailing, const size_t* toff, int* nt_out, bool open_text = false);
     int64_t* proj_ids_d = nullptr; float* proj_out_d = nullptr; size_t proj_cap = 0;   // text_project staging (grow-only)
+    std::vector<int64_t> proj_ids_h;
     int64_t codec_decode_host(const int64_t* codes, int F, float* pcm, int64_t cap);
     int64_t codec_decode_dev(const int32_t* codes_dev, int F, float* pcm_dev, int64_t cap);
     // exact chunked / streaming decode: samples owned by frames [a, b), decoded from the window [a - left_context, b)
@@ -154,7 +155,8 @@ public:
     void codec_stream_push_batch(StreamPush* ps, int g);
     void codec_stream_push_batch_host(int n_streams, const int32_t* sids, const int64_t* codes, const int32_t* frame_offsets, float* const* pcm_out,
                                       int64_t cap, int64_t* pcm_len);
-    void slots_codec_decode_new(int n_slots, const int32_t* slots, float* const* pcm_out, int64_t cap, int64_t* pcm_len, int32_t* frame_begin, int32_t* frame_end);
+    void slots_codec_decode_new(int n_slots, const int32_t* slots, float* const* pcm_out, int64_t cap, int64_t* pcm_len, int32_t* frame_begin, int32_t* frame_end,
+                                const int32_t* frame_limit = nullptr);   // frame_limit[i] (optional): decode slot i's frames below it only
     void slot_codec_stream_reset(int slot);
     void codec_rope_tables(int P);
 
@@ -238,6 +240,22 @@ public:
     void frame_rows(const int64_t* codes, int n, int frame0, const float* trailing, int n_trailing, float* out);   // session-shaped, host I/O
     int64_t* frame_codes_d = nullptr; size_t frame_codes_cap = 0;   // staging of the given frames' ids (grow-only)
     float* frame_text_d = nullptr; size_t frame_text_rows = 0;      // frame_rows: the text rows it reads (grow-only)
+    // ---- live text: the trailing block of reference tts_onnx.cpp:531-536 grows while the slot generates ----
+    // Frame f reads text row f only (:833-842), so a slot needs to be one row ahead of its frame counter.  An open slot
+    // (SlotState::text_open) whose next frame has no row yet stalls in the sampler for that step and changes nothing; appends are
+    // stream-ordered between steps.  Every call validates everything before anything moves.
+    void slot_text_open(int slot);   // after any begin, before the slot's first step
+    // rows != null: n == 1, `rows` holds offsets[1] - offsets[0] projected rows [.][hidden] on the host; else ids [offsets[n]] go
+    // through ONE text_project pass on the device.  One k_text_scatter launch for all n slots either way.
+    void slots_text_append(int n, const int32_t* slots, const float* rows, const int64_t* ids, const int32_t* offsets, const uint8_t* close);
+    void slot_text_status(int slot, int* n_text_rows, int* open, int* starved);
+    void text_project_dev(const int64_t* ids, int n);   // text_project up to the copy back: rows [n][hidden] left in proj_out_d (stream-ordered)
+    void proj_reserve(size_t rows);
+    void check_text_and_mark_stepped(int nb);            // every stepping entry, before its launches: refuses an open slot without the row of its first frame, then marks the armed slots as stepped; an open slot that has not stepped since its begin needs the row of its first frame
+    void build_prompt_open(const int64_t* ids, int n_ids, int lang, const float* speaker, float* prompt, int* S, float* trailing, int cap_rows, int* n_trailing);
+    float* tts_eos_d = nullptr;      // text_project(TTS_EOS): the row build_prompts puts behind a whole text (:535)
+    int32_t* text_desc_d = nullptr;  // k_text_scatter records [B][8]
+    std::vector<uint8_t> stepped_h;  // per slot: stepped since its begin (host mirror; a stalled step of a fresh slot would overwrite its armed logits)
     int decode_steps(int n_steps);
     void slot_status(int slot, int* n_frames, int* finished);
     void slot_codes(int slot, int64_t* codes, int cap_frames);
@@ -324,6 +342,10 @@ public:
     int mfma_min_rows = 12;
     float *x_talk = nullptr, *qkv = nullptr, *attn = nullptr, *act = nullptr, *logits_t = nullptr, *logits_cp = nullptr;
     float *x_cp = nullptr, *x_cp1 = nullptr, *sum = nullptr, *xp = nullptr, *hn = nullptr, *logits_p = nullptr;
+    // `sum` [B][H] is more than step scratch since live text: row b must keep the running embedding sum of slot b's last sampled frame
+    // from one step to the next (and across other slots' begins), because the last sampler of a STALLED slot rebuilds the slot's talker
+    // input row from it (k_sample).  Only k_sample (rows of slots that sample) and the `_dev` predictor session write it; do not reuse
+    // it as a workspace.  x_talk, by contrast, does not survive a step (run_layers works in place on it).
     float *trailing_d = nullptr, *tts_pad_d = nullptr, *text_tmp = nullptr, *text_tmp2 = nullptr;
     int64_t* ids_d = nullptr;
     bf16_t *pl0h = nullptr, *pl0l = nullptr, *pl1h = nullptr, *pl1l = nullptr; // (hi, lo) activation planes for the MFMA GEMM path

@@ -359,6 +359,60 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
 
 std::vector<int> TTSEngine::synthesize_tokens_batch_streaming(const std::vector<std::vector<int64_t>>& token_ids, Language lang, const SamplingParams& params,
                                                               int chunk_frames, const std::function<bool(int, const float*, size_t, bool)>& on_audio) {
+    return synthesize_tokens_batch_streaming(token_ids, lang, params, chunk_frames, on_audio, nullptr);
+}
+
+// utterance u's frames out of a scheduler entry's codes_out [n_utt][max_new][n_groups]
+static void split_codes(const std::vector<int64_t>& all, const std::vector<int32_t>& frames, int max_new, int G, std::vector<std::vector<int64_t>>* codes) {
+    if (!codes) return;
+    codes->assign(frames.size(), std::vector<int64_t>());
+    for (size_t u = 0; u < frames.size(); ++u)
+        (*codes)[u].assign(all.begin() + (ptrdiff_t)(u * (size_t)max_new * G), all.begin() + (ptrdiff_t)((u * (size_t)max_new + (size_t)frames[u]) * G));
+}
+
+std::vector<int> TTSEngine::synthesize_tokens_live(int n_utt, const std::function<bool(int, std::vector<int64_t>&, bool&)>& text_source, Language lang,
+                                                   const SamplingParams& params, int chunk_frames,
+                                                   const std::function<bool(int, const float*, size_t, bool)>& on_audio,
+                                                   std::vector<std::vector<int64_t>>* codes) {
+    if (!ready_ || n_utt < 1 || chunk_frames < 1 || !on_audio || !text_source) return {};
+    q3tts_sampling sp{ params.temperature, params.top_p, params.top_k, params.repetition_penalty, params.max_new_tokens };
+    std::vector<int32_t> frames((size_t)n_utt, 0);
+    struct Ctx { const std::function<bool(int, const float*, size_t, bool)>* f; const std::function<bool(int, std::vector<int64_t>&, bool&)>* t;
+                 std::vector<std::vector<int64_t>> backlog; std::vector<char> closed; } ctx{ &on_audio, &text_source, {}, {} };
+    ctx.backlog.resize((size_t)n_utt); ctx.closed.assign((size_t)n_utt, 0);
+    const q3tts_audio_cb cb = [](void* user, int utt, int, int, const float* pcm, int64_t n, int finished) -> int {
+        return (*static_cast<Ctx*>(user)->f)(utt, pcm, (size_t)n, finished != 0) ? 1 : 0;
+    };
+    const q3tts_text_cb tcb = [](void* user, int utt, int64_t* ids, int cap, int32_t* n, int32_t* closed) -> int {
+        Ctx& c = *static_cast<Ctx*>(user);
+        std::vector<int64_t>& bl = c.backlog[(size_t)utt];
+        if (bl.empty() && !c.closed[(size_t)utt]) {
+            bool cl = false;
+            if (!(*c.t)(utt, bl, cl)) return 1;
+            c.closed[(size_t)utt] = cl ? 1 : 0;
+        }
+        const size_t m = std::min(bl.size(), (size_t)std::max(cap, 0));   // what does not fit this poll goes out at the next
+        std::copy(bl.begin(), bl.begin() + (ptrdiff_t)m, ids);
+        bl.erase(bl.begin(), bl.begin() + (ptrdiff_t)m);
+        *n = (int32_t)m;
+        *closed = bl.empty() && c.closed[(size_t)utt] ? 1 : 0;
+        return 0;
+    };
+    std::vector<int64_t> all;
+    if (codes) all.assign((size_t)n_utt * (size_t)params.max_new_tokens * (size_t)n_groups_, 0);
+    const int rc = q3tts_synthesize_live_host(h_, n_utt, tcb, &ctx, lang_index(lang), nullptr, &sp, nullptr, seed_, 0,
+                                              nullptr, 0, nullptr, frames.data(), codes ? all.data() : nullptr, chunk_frames, cb, &ctx);
+    if (rc != 0) {
+        std::cerr << "[TTSEngine] Synthesis error: " << q3tts_last_error(h_) << std::endl;
+        return {};
+    }
+    split_codes(all, frames, params.max_new_tokens, n_groups_, codes);
+    return std::vector<int>(frames.begin(), frames.end());
+}
+
+std::vector<int> TTSEngine::synthesize_tokens_batch_streaming(const std::vector<std::vector<int64_t>>& token_ids, Language lang, const SamplingParams& params,
+                                                              int chunk_frames, const std::function<bool(int, const float*, size_t, bool)>& on_audio,
+                                                              std::vector<std::vector<int64_t>>* codes) {
     if (!ready_ || token_ids.empty() || chunk_frames < 1 || !on_audio) return {};
     q3tts_sampling sp{ params.temperature, params.top_p, params.top_k, params.repetition_penalty, params.max_new_tokens };
     std::vector<int64_t> flat;
@@ -369,12 +423,15 @@ std::vector<int> TTSEngine::synthesize_tokens_batch_streaming(const std::vector<
     const q3tts_audio_cb cb = [](void* user, int utt, int, int, const float* pcm, int64_t n, int finished) -> int {
         return (*static_cast<Ctx*>(user)->f)(utt, pcm, (size_t)n, finished != 0) ? 1 : 0;
     };
+    std::vector<int64_t> all;
+    if (codes) all.assign(token_ids.size() * (size_t)params.max_new_tokens * (size_t)n_groups_, 0);
     const int rc = q3tts_synthesize_stream_host(h_, (int)token_ids.size(), flat.data(), offs.data(), lang_index(lang), nullptr, &sp, nullptr, seed_, 0,
-                                                nullptr, 0, nullptr, frames.data(), nullptr, chunk_frames, cb, &ctx);
+                                                nullptr, 0, nullptr, frames.data(), codes ? all.data() : nullptr, chunk_frames, cb, &ctx);
     if (rc != 0) {
         std::cerr << "[TTSEngine] Synthesis error: " << q3tts_last_error(h_) << std::endl;
         return {};
     }
+    split_codes(all, frames, params.max_new_tokens, n_groups_, codes);
     return std::vector<int>(frames.begin(), frames.end());
 }
 

@@ -81,6 +81,18 @@ public:
     // frames generated per utterance (empty on error).
     std::vector<int> synthesize_tokens_batch_streaming(const std::vector<std::vector<int64_t>>& token_ids, Language lang, const SamplingParams& params,
                                                        int chunk_frames, const std::function<bool(int, const float*, size_t, bool)>& on_audio);
+    // codes (optional): utterance u's frames, [frames][n_groups] flattened
+    std::vector<int> synthesize_tokens_batch_streaming(const std::vector<std::vector<int64_t>>& token_ids, Language lang, const SamplingParams& params,
+                                                       int chunk_frames, const std::function<bool(int, const float*, size_t, bool)>& on_audio,
+                                                       std::vector<std::vector<int64_t>>* codes);
+    // live text extension (q3tts_synthesize_live_host): the same delivery for n_utt texts that arrive while their audio is generated.
+    // text_source(utt, ids, closed) is polled between decode chunks while the utterance's text is open: it appends new ids to `ids`
+    // (possibly none; the utterance's first ids are the role ids, as token_ids above) and sets closed once no more will come; a false
+    // return cancels the job.  An utterance whose next frame has no text yet stalls and gets no audio that turn.
+    std::vector<int> synthesize_tokens_live(int n_utt, const std::function<bool(int, std::vector<int64_t>&, bool&)>& text_source, Language lang,
+                                            const SamplingParams& params, int chunk_frames,
+                                            const std::function<bool(int, const float*, size_t, bool)>& on_audio,
+                                            std::vector<std::vector<int64_t>>* codes = nullptr);
     void set_seed(uint64_t seed) { seed_ = seed; }
     // ids of `text` from the loaded tokenizer (reference io::tokenize, src/io/tokenizer.h:22)
     std::vector<int32_t> tokenize(const std::string& text) const;

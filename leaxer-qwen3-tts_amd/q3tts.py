@@ -97,10 +97,14 @@ EXPORTS = [
     "q3tts_frame_rows_host", "q3tts_slot_begin_codes", "q3tts_synthesize_continue_host",
     "q3tts_prefix_create", "q3tts_prefix_create_instruct", "q3tts_prefix_info", "q3tts_prefix_release",
     "q3tts_slot_begin_prefixed", "q3tts_slots_begin_prefixed", "q3tts_slots_begin_ragged", "q3tts_synthesize_prefixed_host",
+    "q3tts_slot_text_open", "q3tts_slot_text_append_host", "q3tts_slots_text_append_ids", "q3tts_slot_text_status",
+    "q3tts_build_prompt_open_host", "q3tts_synthesize_live_host",
 ]
 
 # q3tts_audio_cb: int (*)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished)
 AUDIO_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int64, C.c_int)
+# q3tts_text_cb: int (*)(void* user, int utt, int64_t* ids, int cap, int32_t* n, int32_t* closed)
+TEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
 
 _lib = None
 
@@ -163,6 +167,13 @@ def lib():
     L.q3tts_synthesize_prefixed_host.argtypes = [vp, i32, vp, vp, i32, vp, C.POINTER(Sampling), vp, C.c_uint64, i32, vp, i64, vp, vp, vp,
                                                  i32, AUDIO_CB, vp, vp]
     L.q3tts_decode_steps.argtypes = [vp, i32]
+    L.q3tts_slot_text_open.argtypes = [vp, i32]
+    L.q3tts_slot_text_append_host.argtypes = [vp, i32, vp, i32, i32]
+    L.q3tts_slots_text_append_ids.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.q3tts_slot_text_status.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.q3tts_build_prompt_open_host.argtypes = [vp, vp, i32, i32, vp, vp, C.POINTER(i32), vp, i32, C.POINTER(i32)]
+    L.q3tts_synthesize_live_host.argtypes = [vp, i32, TEXT_CB, vp, i32, vp, C.POINTER(Sampling), vp, C.c_uint64, i32, vp, i64, vp, vp, vp,
+                                             i32, AUDIO_CB, vp]
     L.q3tts_slot_status.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.q3tts_slot_codes_host.argtypes = [vp, i32, vp, i32]
     L.q3tts_slot_codec_decode_host.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
@@ -525,6 +536,53 @@ class Engine:
         self._ck(self.L.q3tts_build_prompt_host(self.h, _p(ids), ids.size, lang, _p(sp) if sp is not None else None,
                                                 _p(prompt), C.byref(S), _p(trailing), cap_rows, C.byref(nt)))
         return prompt[: S.value].copy(), trailing[: nt.value].copy()
+
+    def build_prompt_open(self, ids, lang=0, speaker=None, cap_rows=1024):
+        """build_prompt for a text whose end is not known (q3tts_build_prompt_open_host): every id behind the first text id becomes a
+        trailing row, no tts_eos row; begin a slot with the result, then slot_text_open"""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        prompt = np.zeros((16, self.cfg.hidden), np.float32)
+        trailing = np.zeros((max(cap_rows, 1), self.cfg.hidden), np.float32)
+        S, nt = C.c_int(0), C.c_int(0)
+        sp = np.ascontiguousarray(speaker, dtype=np.float32) if speaker is not None else None
+        if sp is not None and sp.size != self.cfg.hidden:
+            raise ValueError("speaker embedding has %d values, the model needs %d" % (sp.size, self.cfg.hidden))
+        self._ck(self.L.q3tts_build_prompt_open_host(self.h, _p(ids), ids.size, lang, _p(sp) if sp is not None else None,
+                                                     _p(prompt), C.byref(S), _p(trailing), cap_rows, C.byref(nt)))
+        return prompt[: S.value].copy(), trailing[: nt.value].copy()
+
+    # ---- live text: append text to generating slots (include/q3tts.h "live text") ----
+    def slot_text_open(self, slot):
+        """the slot's text may grow (after slot_begin*, before its first step): it stalls instead of reading the pad row"""
+        self._ck(self.L.q3tts_slot_text_open(self.h, int(slot)))
+
+    def slot_text_append(self, slot, rows=None, ids=None, close=False):
+        """projected rows [n][hidden] (rows=) or token ids (ids=) go behind the slot's text; close=True ends the text (tts_eos row)"""
+        if rows is not None and ids is not None:
+            raise ValueError("slot_text_append: rows or ids, not both")
+        if ids is not None:
+            return self.slots_text_append_ids([slot], [ids], [close])
+        r = np.zeros((0, self.cfg.hidden), np.float32) if rows is None else np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, self.cfg.hidden)
+        self._ck(self.L.q3tts_slot_text_append_host(self.h, int(slot), _p(r) if r.size else None, r.shape[0], int(bool(close))))
+
+    def slots_text_append_ids(self, slots, id_lists, close=None):
+        """q3tts_slots_text_append_ids: slot slots[i] takes id_lists[i]; one projection pass and one scatter launch for all of them"""
+        n = len(slots)
+        if len(id_lists) != n or (close is not None and len(close) != n):
+            raise ValueError("slots_text_append_ids: one entry per slot")
+        sl = np.ascontiguousarray(slots, np.int32)
+        parts = [np.asarray(t, np.int64).reshape(-1) for t in id_lists]
+        flat = np.ascontiguousarray(np.concatenate(parts)) if n else np.zeros(0, np.int64)
+        offs = np.zeros(n + 1, np.int32)
+        offs[1:] = np.cumsum([t.size for t in parts])
+        cl = np.zeros(n, np.uint8) if close is None else np.array([1 if c else 0 for c in close], np.uint8)
+        self._ck(self.L.q3tts_slots_text_append_ids(self.h, n, _p(sl), _p(flat) if flat.size else None, _p(offs), _p(cl)))
+
+    def slot_text_status(self, slot):
+        """(text rows held, open, starved): starved = open and the next frame's text row has not arrived"""
+        n, o, st = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._ck(self.L.q3tts_slot_text_status(self.h, int(slot), C.byref(n), C.byref(o), C.byref(st)))
+        return n.value, bool(o.value), bool(st.value)
 
     # ---- fused generation ----
     # ---- shared prompt prefix ----
@@ -927,6 +985,74 @@ class Engine:
             rc = self.L.q3tts_synthesize_stream_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
                                                      seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr),
                                                      _p(codes) if want_codes else None, int(chunk_frames), cb, None)
+        if raised:
+            raise raised[0]
+        self._ck(rc)
+        outs = [pcm[i][: pcm_len[i]] for i in range(n)]
+        cl = [codes[i, : nfr[i]] for i in range(n)] if want_codes else None
+        return outs, cl, nfr
+
+    def synthesize_live(self, n_utt, text_source, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
+                        max_new_per_utt=None):
+        """synthesize_stream for texts that arrive while their audio is generated (q3tts_synthesize_live_host): text_source(utt) ->
+        (ids, closed) is polled between decode chunks for every utterance whose text is open — new ids (possibly none) and whether the
+        text has ended; None cancels the job (RuntimeError "cancelled by callback").  An utterance's ids are those synthesize_stream
+        takes (role ids first).  An exception in either callback cancels the job and is re-raised.  Returns what synthesize_stream returns."""
+        n = int(n_utt)
+        cap = self.codec_decode_len(sp.max_new_tokens)
+        pcm = [np.zeros(cap, np.float32) for _ in range(n)]
+        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in pcm])
+        pcm_len = np.zeros(n, np.int64)
+        nfr = np.zeros(n, np.int32)
+        codes = np.zeros((n, sp.max_new_tokens, self.cfg.n_groups), np.int64) if want_codes else None
+        spk_keep, spk_ptrs = [], None
+        if speakers is not None:
+            if len(speakers) != n:
+                raise ValueError("speakers: one entry (embedding or None) per utterance")
+            spk_keep = [None if s_ is None else np.ascontiguousarray(s_, np.float32) for s_ in speakers]
+            for a in spk_keep:
+                if a is not None and a.size != self.cfg.hidden:
+                    raise ValueError("speaker embedding has %d values, the model needs %d" % (a.size, self.cfg.hidden))
+            spk_ptrs = C.cast((C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in spk_keep]), C.c_void_p)
+        caps = None if max_new_per_utt is None else np.ascontiguousarray(max_new_per_utt, np.int32)
+        if caps is not None and caps.shape != (n,):
+            raise ValueError("max_new_per_utt: one entry per utterance")
+        raised = []
+        backlog = {}   # ids a poll returned beyond the callback's capacity
+
+        def ttramp(_user, utt, ids, cap_ids, n_out, closed_out):
+            try:
+                if utt in backlog:
+                    new, closed = backlog.pop(utt)
+                else:
+                    r = text_source(utt)
+                    if r is None:   # the source gives the job up
+                        return 1
+                    new, closed = r
+                    new = [int(v) for v in new]
+                if len(new) > cap_ids:
+                    backlog[utt] = (new[cap_ids:], closed)
+                    new, closed = new[:cap_ids], False
+                for i, v in enumerate(new):
+                    ids[i] = v
+                n_out[0] = len(new)
+                closed_out[0] = 1 if closed else 0
+                return 0
+            except BaseException as ex:
+                raised.append(ex)
+                return 1
+
+        def tramp(_user, utt, fb, fe, p, ns, fin):
+            try:
+                a = np.ctypeslib.as_array(p, shape=(ns,)).copy() if ns > 0 else np.zeros(0, np.float32)
+                return 1 if on_audio(utt, fb, fe, a, bool(fin)) else 0
+            except BaseException as ex:
+                raised.append(ex)
+                return 1
+        cb, tcb = AUDIO_CB(tramp), TEXT_CB(ttramp)
+        rc = self.L.q3tts_synthesize_live_host(self.h, n, tcb, None, lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
+                                               seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr),
+                                               _p(codes) if want_codes else None, int(chunk_frames), cb, None)
         if raised:
             raise raised[0]
         self._ck(rc)
