@@ -45,6 +45,18 @@ typedef struct q3tts_config {
      * cp_hidden 1024) every predictor input row passes through cp.proj (Linear + bias, [HINT] Qwen3-TTS small_to_mtp_projection) first;
      * the predictor's code embeddings stay talker-wide.  The code_predictor session contract (tts_onnx.cpp:734-757) is unchanged. */
     int32_t cp_hidden;
+    /* audio encoder of the 12 Hz speech tokenizer (audio -> codes; [HINT] transformers MimiModel.encode, the first n_groups quantizers):
+     * SEANet encoder (causal convs: enc_kernel taps 1 -> enc_filters; per ratio a residual block of enc_res_kernel and 1 taps, then a
+     * conv of 2 x ratio taps, stride ratio, doubling the channels; enc_last_kernel taps -> enc_hidden), a transformer of enc_layers
+     * layers at that rate (LayerNorm, RoPE, causal window enc_window, LayerScale, GELU MLP), a stride-2 conv of 4 taps with replicate
+     * padding, and a split residual VQ (1 semantic + n_groups - 1 acoustic levels of enc_codebook rows x enc_vq_dim).  enc_ratios is in
+     * encoder order (first stage first).  enc_hidden == 0: no audio encoder (q3tts_has_audio_encoder() false, no enc.* tensor). */
+    int32_t enc_hidden, enc_filters, enc_n_ratios;
+    int32_t enc_ratios[4];
+    int32_t enc_kernel, enc_res_kernel, enc_last_kernel;
+    int32_t enc_layers, enc_heads, enc_head_dim, enc_ffn, enc_window;
+    int32_t enc_vq_dim, enc_codebook;
+    float enc_rope_theta, enc_norm_eps;
 } q3tts_config;
 
 /* SamplingParams, reference src/tts_onnx.h:99-105.  The reference declares repetition_penalty and never reads it; here it is the
@@ -82,6 +94,10 @@ typedef struct q3tts_engine q3tts_engine;
 
 /* ---- lifecycle (replaces TTSEngine ctor / load_model, tts_onnx.cpp:84-232) ---- */
 int q3tts_default_config(const char* name /* "0.6b" | "1.7b" */, q3tts_config* out);
+/* q3tts_default_config leaves the audio encoder off; this fills in the 12 Hz tokenizer's encoder dimensions ([HINT], unpinned: the Mimi
+ * encoder of transformers — 64 filters, ratios 4 5 6 8, hidden 512, 8 layers of 8 x 64 heads, ffn 2048, window 250, 2048 x 256
+ * codebooks).  The other fields are left as they are.  0 on success, -1 for a NULL pointer. */
+int q3tts_config_enable_audio_encoder(q3tts_config* cfg);
 q3tts_engine* q3tts_create(const q3tts_config* cfg, int device, int max_batch, int max_ctx, uint32_t flags);
 /* The same with a bounded KV page pool.  The talker's cache (the reference's KVCache, tts_onnx.h:108-115, grown by one token per run_decode)
  * is a pool of 64-token pages; a slot takes pages for prompt + max_new_tokens when it is armed (q3tts_slot_begin / the scheduler) or as its
@@ -486,6 +502,34 @@ int q3tts_mel_gpu_host(q3tts_engine* e, const float* audio, int64_t n, int32_t s
 int q3tts_speaker_embed_pcm_batch_host(q3tts_engine* e, int n_clips, const float* const* pcm, const int64_t* n_samples,
                                        const int32_t* sample_rates, float* embeds);
 
+/* ---- audio -> codes: the 12 Hz speech tokenizer's encoder ([HINT], unpinned: transformers MimiModel.encode; the arithmetic is verified
+ * against it, its effect on audio is not: no checkpoint was available) ----
+ * The producer of what q3tts_slot_begin_codes consumes (tts_onnx.cpp:824-842 is the arithmetic of a frame's row; the reference has no
+ * encoder).  All of it runs in fp32 on the GPU in a workspace the engine owns (grow-only, freed by q3tts_destroy).  A clip holds at most
+ * 1 440 000 samples at 24 kHz (60 s) and, at another rate, 23 040 000 samples before resampling; a batch is processed in consecutive groups of at most 2 880 000 samples.  An engine whose config
+ * has enc_hidden == 0 answers "model has no audio encoder". */
+int q3tts_has_audio_encoder(q3tts_engine* e);
+/* frames of a clip of n_samples samples at 24 kHz: ceil(n / samples per frame) through the convs' own padding rule; host-only.
+ * -1 without an encoder or for n_samples < 1. */
+int64_t q3tts_audio_encode_len(q3tts_engine* e, int64_t n_samples);
+/* pcm24k[n_samples] (mono, 24 kHz) -> codes_out[*n_frames][n_groups] int64, the layout q3tts_slot_codes_host returns and
+ * q3tts_slot_begin_codes takes.  cap_frames < the clip's frames is refused. */
+int q3tts_audio_encode_host(q3tts_engine* e, const float* pcm24k, int64_t n_samples, int64_t* codes_out, int cap_frames, int32_t* n_frames);
+/* n_clips clips at once, each at its own rate (clips not at 24 kHz go through the GPU resampler of q3tts_resample_gpu_host first): one
+ * set of launches per group, padding never crosses a clip boundary, and every clip's codes are bit-identical to encoding it alone.
+ * codes_out[i] receives n_frames[i] x n_groups ids (caps[i] frames of room). */
+int q3tts_audio_encode_batch_host(q3tts_engine* e, int n_clips, const float* const* pcm, const int64_t* n_samples, const int32_t* sample_rates,
+                                  int64_t* const* codes_out, const int32_t* caps, int32_t* n_frames);
+/* Parity aid: the rows the quantiser sees, latents[*n_frames][enc_hidden] (the stride-2 conv's output), and optionally the codes. */
+int q3tts_audio_encode_latents_host(q3tts_engine* e, const float* pcm24k, int64_t n_samples, float* latents, int64_t* codes_out, int cap_frames,
+                                    int32_t* n_frames);
+/* Parity aid: q3tts_audio_encode_batch_host that also returns each clip's latents, latents_out[i][n_frames[i]][enc_hidden] (caps[i] frames of
+ * room; codes_out or latents_out may be NULL, and so may single entries) */
+int q3tts_audio_encode_batch_latents_host(q3tts_engine* e, int n_clips, const float* const* pcm, const int64_t* n_samples, const int32_t* sample_rates,
+                                          int64_t* const* codes_out, float* const* latents_out, const int32_t* caps, int32_t* n_frames);
+/* Parity aid (engines created with Q3TTS_FLAG_TEST_HOOKS): the encoder's transformer alone on rows[n_rows][enc_hidden] -> out, same shape */
+int q3tts_test_audio_encoder_transformer_host(q3tts_engine* e, const float* rows, int n_rows, float* out);
+
 /* ---- text front end: the reference's byte-level BPE tokenizer ---- */
 /* Replaces leaxer_qwen::io::load_vocab / load_merges / is_tokenizer_ready / tokenize (reference
  * src/io/tokenizer.h:13-22, src/io/tokenizer.cpp:538-561) with the same ids for the same files and text.
@@ -503,6 +547,8 @@ int64_t q3tts_tokenize(const q3tts_tokenizer* t, const char* text, int64_t len, 
 /* ---- measurement hooks (bench.py) ---- */
 /* device time in ms of the last q3tts_decode_steps call, from HIP events on the engine's stream */
 int q3tts_last_decode_ms(q3tts_engine* e, float* ms, int* steps);
+/* device time in ms of the last q3tts_audio_encode_* call (uploads and launches of all its groups, HIP events on the engine's stream) */
+int q3tts_last_audio_encode_ms(q3tts_engine* e, float* ms);
 /* device time in ms of the last codec decode */
 int q3tts_last_codec_ms(q3tts_engine* e, float* ms);
 /* accumulated device time since the last reset: decode steps (HIP events around the graph

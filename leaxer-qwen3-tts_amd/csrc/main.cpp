@@ -4,7 +4,9 @@
 // --tokens "id,id,..." (pre-tokenised text between TTS_BOS and TTS_EOS, bypassing vocab.json/merges.txt),
 // --seed N, --instruct TEXT / --instruct-tokens "id,id,..." (a voice instruction in front of the prompt: the reference README's roadmap
 // row "Voice instructions (--instruct)"; combines with --ref), --save-codes FILE / --continue-codes FILE (with --tokens: write the
-// utterance's codec frames, one per line; generate behind recorded frames — the WAV then holds the new audio only).
+// utterance's codec frames, one per line; generate behind recorded frames — the WAV then holds the new audio only),
+// --encode WAV --save-codes FILE (audio -> codes with the 12 Hz tokenizer's encoder, nothing else), --ref WAV with --ref-text TEXT /
+// --ref-tokens "id,id,..." (in-context clone: the reference's codes and text in front of the utterance; --ref alone stays the x-vector clone).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -47,6 +49,9 @@ static void usage(const char* prog) {
     printf("  --save-codes FILE     with --tokens: write the utterance's codec frames, one frame per line (--continue-codes frames included)\n");
     printf("  --continue-codes FILE with --tokens: generate behind the recorded frames of FILE (as --save-codes writes them); the WAV holds the new audio only\n");
     printf("  --ref PATH            reference audio for voice clone (WAV; resampled to 24 kHz, ECAPA speaker encoder on the GPU)\n");
+    printf("  --ref-text TEXT       with --ref: in-context clone instead — the reference is encoded to codes and continued, TEXT is what it says\n");
+    printf("  --ref-tokens IDS      the same with the reference text as comma-separated token ids (for synthetic: models, with --tokens)\n");
+    printf("  --encode PATH         encode a WAV to codec frames with the audio encoder and write them to --save-codes FILE; nothing is synthesized\n");
     printf("  --temp FLOAT          temperature (default: 0.8; 0 samples at T=1 like the reference, use --top-k 1 for greedy)\n");
     printf("  --top-k N             top-k (default: 50)\n  --top-p FLOAT         top-p (default: 0.95)\n");
     printf("  --rep-penalty FLOAT   repetition penalty on the first codebook's ids (default: 1.0 = off; not a flag of the reference CLI)\n");
@@ -101,8 +106,19 @@ static Language lang_of(const std::string& s) {
     return Language::Auto;
 }
 
+// -p TEXT as --tokens frames its ids: IM_START ASSISTANT TTS_BOS <ids of the tokenizer> TTS_EOS IM_END; false with a message on stderr
+static bool frame_prompt(const TTSEngine& engine, const std::string& prompt, std::vector<int64_t>& ids) {
+    const std::vector<int32_t> t = engine.tokenize(prompt);
+    if (t.empty()) { fprintf(stderr, "Error: the text has no tokens (-p needs vocab.json + merges.txt)\n"); return false; }
+    ids = { config::IM_START, config::ASSISTANT, config::TTS_BOS };
+    ids.insert(ids.end(), t.begin(), t.end());
+    ids.push_back(config::TTS_EOS);
+    ids.push_back(config::IM_END);
+    return true;
+}
+
 int main(int argc, char** argv) {
-    std::string model, prompt, tokens, output = "output.wav", lang = "auto", ref, instruct, instruct_tokens, save_codes, continue_codes;
+    std::string model, prompt, tokens, output = "output.wav", lang = "auto", ref, instruct, instruct_tokens, save_codes, continue_codes, encode, ref_text, ref_tokens;
     bool have_prompt = false;
     SamplingParams sp;
     uint64_t seed = 0;
@@ -117,6 +133,9 @@ int main(int argc, char** argv) {
         else if ((a == "-o" || a == "--output") && more) output = argv[++i];
         else if (a == "--lang" && more) lang = argv[++i];
         else if (a == "--ref" && more) ref = argv[++i];
+        else if (a == "--ref-text" && more) ref_text = argv[++i];
+        else if (a == "--ref-tokens" && more) ref_tokens = argv[++i];
+        else if (a == "--encode" && more) encode = argv[++i];
         else if (a == "--instruct" && more) instruct = argv[++i];
         else if (a == "--instruct-tokens" && more) instruct_tokens = argv[++i];
         else if (a == "--save-codes" && more) save_codes = argv[++i];
@@ -130,6 +149,22 @@ int main(int argc, char** argv) {
         else if (a == "--stream-chunk" && more) stream_chunk = atoi(argv[++i]);
         else if (a == "--feed" && more) feed = atoi(argv[++i]);
     }
+    const bool icl = !ref_text.empty() || !ref_tokens.empty();
+    if (!encode.empty()) {   // audio -> codes, nothing else
+        if (model.empty() || save_codes.empty()) { fprintf(stderr, "Error: --encode needs --model and --save-codes FILE\n"); return 1; }
+        TTSEngine enc_engine(model, true);
+        if (!enc_engine.is_ready()) { fprintf(stderr, "Error: %s\n", enc_engine.get_error().c_str()); return 1; }
+        if (!enc_engine.has_audio_encoder()) { fprintf(stderr, "Error: model has no audio encoder\n"); return 1; }
+        const std::vector<int64_t> codes = enc_engine.encode_audio(encode);
+        if (codes.empty()) { fprintf(stderr, "Error: encoding failed\n"); return 1; }
+        if (!write_codes_file(save_codes, codes, (size_t)enc_engine.n_groups())) { fprintf(stderr, "Error: failed to write %s\n", save_codes.c_str()); return 1; }
+        printf("Encoded %zu frames\nCodes saved to: %s\n", codes.size() / (size_t)enc_engine.n_groups(), save_codes.c_str());
+        return 0;
+    }
+    if (icl && (ref.empty() || !instruct.empty() || !instruct_tokens.empty() || !continue_codes.empty() || stream_chunk > 0 || (!ref_tokens.empty() && tokens.empty()))) {
+        fprintf(stderr, "Error: --ref-text / --ref-tokens go with --ref (without --instruct, --continue-codes, --stream-chunk; --ref-tokens with --tokens)\n");
+        return 1;
+    }
     if (model.empty() || (!have_prompt && tokens.empty())) {
         fprintf(stderr, "Error: --model and --prompt (or --tokens) are required\n");
         usage(argv[0]);
@@ -142,8 +177,8 @@ int main(int argc, char** argv) {
     std::vector<int64_t> prefix;
     size_t prefix_groups = 0;
     if (!save_codes.empty() || !continue_codes.empty()) {
-        if (tokens.empty() || !ref.empty() || !instruct.empty() || !instruct_tokens.empty() || (stream_chunk > 0 && !continue_codes.empty())) {
-            fprintf(stderr, "Error: --save-codes / --continue-codes go with --tokens (without --ref, --instruct; --continue-codes without --stream-chunk)\n");
+        if (tokens.empty() || (!ref.empty() && !icl) || !instruct.empty() || !instruct_tokens.empty() || (stream_chunk > 0 && !continue_codes.empty())) {
+            fprintf(stderr, "Error: --save-codes / --continue-codes go with --tokens (without --instruct, and without --ref unless --ref-text / --ref-tokens make it an in-context clone; --continue-codes without --stream-chunk)\n");
             return 1;
         }
         if (!continue_codes.empty()) {
@@ -161,12 +196,12 @@ int main(int argc, char** argv) {
     if (!ref.empty()) printf("Reference: %s\n", ref.c_str());
     printf("Language: %s\nOutput: %s\n\n", lang.c_str(), output.c_str());
 
-    TTSEngine engine(model);
+    TTSEngine engine(model, icl);
     if (!engine.is_ready()) { fprintf(stderr, "Error: %s\n", engine.get_error().c_str()); return 1; }
     engine.set_seed(seed);
     printf("Synthesizing...\n");
     std::vector<float> audio;
-    if (!ref.empty()) {
+    if (!ref.empty() && !icl) {
         if (!engine.has_speaker_encoder()) { fprintf(stderr, "Error: speaker encoder not available for voice clone\n"); return 1; }
     }
     std::vector<int64_t> ids;
@@ -176,7 +211,23 @@ int main(int argc, char** argv) {
         ids.push_back(config::TTS_EOS);
         ids.push_back(config::IM_END);
     }
-    if (!instruct.empty() || !instruct_tokens.empty()) {   // a voice instruction in front of the prompt, with or without a cloned voice
+    if (icl) {   // in-context clone: the reference's codes (audio encoder) and text in front of the utterance
+        if (!engine.has_audio_encoder()) { fprintf(stderr, "Error: model has no audio encoder\n"); return 1; }
+        std::vector<int64_t> rids;
+        if (!ref_tokens.empty())
+            for (char* tok = strtok(&ref_tokens[0], ", "); tok; tok = strtok(nullptr, ", ")) rids.push_back(strtoll(tok, nullptr, 10));
+        else for (int32_t t : engine.tokenize(ref_text)) rids.push_back(t);
+        if (rids.empty()) { fprintf(stderr, "Error: the reference text has no tokens (--ref-text needs vocab.json + merges.txt)\n"); return 1; }
+        if (ids.empty() && !frame_prompt(engine, prompt, ids)) return 1;   // -p: the framing of --tokens around the tokenised text
+        std::vector<int64_t> all;
+        audio = engine.synthesize_clone_icl(ids, rids, ref, lang_of(lang), sp, &all);
+        const size_t G = (size_t)engine.n_groups();
+        if (!audio.empty()) printf("In-context clone: %zu reference text tokens, %zu frames in all\n", rids.size(), all.size() / G);
+        if (!audio.empty() && !save_codes.empty()) {
+            if (!write_codes_file(save_codes, all, G)) { fprintf(stderr, "Error: failed to write %s\n", save_codes.c_str()); return 1; }
+            printf("Codes saved to: %s\n", save_codes.c_str());
+        }
+    } else if (!instruct.empty() || !instruct_tokens.empty()) {   // a voice instruction in front of the prompt, with or without a cloned voice
         std::vector<int32_t> ins;
         if (!instruct_tokens.empty())
             for (char* tok = strtok(&instruct_tokens[0], ", "); tok; tok = strtok(nullptr, ", ")) ins.push_back((int32_t)strtol(tok, nullptr, 10));
@@ -199,14 +250,7 @@ int main(int argc, char** argv) {
         audio = engine.synthesize_clone(prompt, ref, lang_of(lang), sp);
     } else if (stream_chunk > 0 && (feed > 0 || !save_codes.empty())) {
         // the batch scheduler's delivery for one utterance; --feed: its ids reach the engine K at a time, one piece per poll (live text)
-        if (ids.empty()) {   // -p: the framing of --tokens around the tokenised text
-            const std::vector<int32_t> t = engine.tokenize(prompt);
-            if (t.empty()) { fprintf(stderr, "Error: the text has no tokens (-p needs vocab.json + merges.txt)\n"); return 1; }
-            ids = { config::IM_START, config::ASSISTANT, config::TTS_BOS };
-            ids.insert(ids.end(), t.begin(), t.end());
-            ids.push_back(config::TTS_EOS);
-            ids.push_back(config::IM_END);
-        }
+        if (ids.empty() && !frame_prompt(engine, prompt, ids)) return 1;   // -p: the framing of --tokens around the tokenised text
         size_t chunks = 0, given = 0, polls = 0;
         auto on_audio = [&](int, const float* p, size_t n, bool) {
             if (n > 0 && chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / config::SAMPLE_RATE);

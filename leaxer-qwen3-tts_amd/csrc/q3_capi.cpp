@@ -124,6 +124,18 @@ int q3tts_default_config(const char* name, q3tts_config* o) {
     return 0;
 }
 
+int q3tts_config_enable_audio_encoder(q3tts_config* o) {
+    if (!o) return -1;
+    // [HINT: transformers MimiConfig defaults, as the Qwen3-TTS 12 Hz tokenizer uses them] upsampling_ratios (8, 6, 5, 4) reversed
+    o->enc_hidden = 512; o->enc_filters = 64; o->enc_n_ratios = 4;
+    o->enc_ratios[0] = 4; o->enc_ratios[1] = 5; o->enc_ratios[2] = 6; o->enc_ratios[3] = 8;
+    o->enc_kernel = 7; o->enc_res_kernel = 3; o->enc_last_kernel = 3;
+    o->enc_layers = 8; o->enc_heads = 8; o->enc_head_dim = 64; o->enc_ffn = 2048; o->enc_window = 250;
+    o->enc_vq_dim = 256; o->enc_codebook = 2048;
+    o->enc_rope_theta = 10000.0f; o->enc_norm_eps = 1e-5f;
+    return 0;
+}
+
 int q3tts_config_num_tensors(const q3tts_config* cfg) {
     if (!cfg) return -1;
     try { return (int)q3::tensor_specs(*cfg).size(); } catch (...) { return -1; }
@@ -1149,6 +1161,67 @@ int q3tts_mel_host(const float* audio, int64_t n, float* mel, int64_t cap, int32
         return 0;
     } catch (...) { return -1; }
 }
+int q3tts_has_audio_encoder(q3tts_engine* h) { return h && h->e && h->e->has_audio_encoder() ? 1 : 0; }
+
+int64_t q3tts_audio_encode_len(q3tts_engine* h, int64_t n_samples) {
+    if (!h || !h->e) return -1;
+    if (!h->e->has_audio_encoder()) { h->err = "model has no audio encoder"; return -1; }
+    return h->e->audio_encode_len(n_samples);
+}
+
+int q3tts_audio_encode_batch_host(q3tts_engine* h, int n_clips, const float* const* pcm, const int64_t* n_samples, const int32_t* sample_rates,
+                                  int64_t* const* codes_out, const int32_t* caps, int32_t* n_frames) {
+    Q3_API_BEGIN(h)
+    if (!h->e->has_audio_encoder()) throw q3::Error("model has no audio encoder");
+    if (!h->e->finalized) throw q3::Error("weights not finalized");
+    if (!codes_out || !caps) throw q3::Error("audio encoder: NULL argument");
+    h->e->audio_encode(n_clips, pcm, n_samples, sample_rates, codes_out, nullptr, caps, n_frames);
+    return 0;
+    Q3_API_END(h)
+}
+
+int q3tts_audio_encode_batch_latents_host(q3tts_engine* h, int n_clips, const float* const* pcm, const int64_t* n_samples, const int32_t* sample_rates,
+                                          int64_t* const* codes_out, float* const* latents_out, const int32_t* caps, int32_t* n_frames) {
+    Q3_API_BEGIN(h)
+    if (!h->e->has_audio_encoder()) throw q3::Error("model has no audio encoder");
+    if (!h->e->finalized) throw q3::Error("weights not finalized");
+    h->e->audio_encode(n_clips, pcm, n_samples, sample_rates, codes_out, latents_out, caps, n_frames);
+    return 0;
+    Q3_API_END(h)
+}
+
+int q3tts_audio_encode_latents_host(q3tts_engine* h, const float* pcm24k, int64_t n_samples, float* latents, int64_t* codes_out, int cap_frames,
+                                    int32_t* n_frames) {
+    Q3_API_BEGIN(h)
+    if (!h->e->has_audio_encoder()) throw q3::Error("model has no audio encoder");
+    if (!h->e->finalized) throw q3::Error("weights not finalized");
+    const int32_t rate = 24000, cap = cap_frames;
+    int32_t nf = 0;
+    h->e->audio_encode(1, &pcm24k, &n_samples, &rate, codes_out ? &codes_out : nullptr, latents ? &latents : nullptr, &cap, &nf);
+    if (n_frames) *n_frames = nf;
+    return 0;
+    Q3_API_END(h)
+}
+
+int q3tts_audio_encode_host(q3tts_engine* h, const float* pcm24k, int64_t n_samples, int64_t* codes_out, int cap_frames, int32_t* n_frames) {
+    if (h && h->e && !codes_out) { h->err = "audio encoder: NULL argument"; return -1; }
+    return q3tts_audio_encode_latents_host(h, pcm24k, n_samples, nullptr, codes_out, cap_frames, n_frames);
+}
+
+int q3tts_last_audio_encode_ms(q3tts_engine* h, float* ms) {
+    if (!h || !h->e || !ms) return -1;
+    *ms = h->e->last_audio_encode_ms;
+    return 0;
+}
+
+int q3tts_test_audio_encoder_transformer_host(q3tts_engine* h, const float* rows, int n_rows, float* out) {
+    Q3_API_BEGIN(h)
+    if (!h->e->finalized) throw q3::Error("weights not finalized");
+    h->e->enc_transformer_host(rows, n_rows, out);
+    return 0;
+    Q3_API_END(h)
+}
+
 int q3tts_has_speaker_encoder(q3tts_engine* h) { return h && h->e && h->e->has_speaker() ? 1 : 0; }
 int q3tts_speaker_encoder_host(q3tts_engine* h, const float* mel, int frames, float* embed) {
     Q3_API_BEGIN(h) h->e->speaker_encode(mel, frames, embed); return 0; Q3_API_END(h)

@@ -460,4 +460,30 @@ struct MelTablesDev {
 };
 void launch_logmel(const float* raw, const float* rs, const SpkClip* clips, int n_clips, int max_T, const MelTablesDev& tb, float* mel, hipStream_t s);
 
+
+// ---- audio encoder of the 12 Hz tokenizer (q3_encoder_kernels.hip): fp32 throughout ----
+// Activations are time-major rows, clip after clip.  One clip at one rate level: its first row in the level's buffer and its rows.
+struct EncSpan { int32_t off = 0, T = 0; };
+// out[t][co] = res[t][co] + scale[co] * act(bias[co] + sum_{tap, ci} W[tap][co][ci] * f(in[t * stride - pad_left + tap * dil][ci])),
+// f = ELU when elu_in; rows outside [0, T_in) are zeros, or the clip's first / last row when replicate.  blockIdx.z = clip: the tile
+// grid starts at each clip's own t = 0 and no tap leaves the clip, so a clip's arithmetic does not depend on the rest of the batch.
+struct EncConvArgs {
+    const float* in = nullptr; float* out = nullptr;      // [rows][Cin], [rows][Cout]
+    const float* W = nullptr;                             // [taps][Cout][Cin]
+    const float* bias = nullptr; const float* scale = nullptr; const float* res = nullptr;   // optional; res [rows][Cout] may alias out
+    int Cin = 0, Cout = 0, taps = 1, dil = 1, stride = 1, pad_left = 0;
+    int replicate = 0, elu_in = 0, act = 0;               // act 1: exact (erf) GELU
+    const EncSpan* sin = nullptr; const EncSpan* sout = nullptr; int n_clips = 0, max_T_out = 0;
+};
+void launch_enc_conv(const EncConvArgs& a, hipStream_t s);      // Cin == 1: VALU kernel; otherwise implicit GEMM on the fp32 matrix cores
+void launch_enc_layernorm(const float* x, const float* w, const float* b, float eps, int rows, int C, float* out, hipStream_t s);
+// q and k of qkv [rows][3 * heads * d] rotated in place (rotate-half RoPE) at each row's position inside its clip; cs / sn [max_pos][d / 2]
+void launch_enc_rope(float* qkv, const float* cs, const float* sn, int max_pos, int heads, int d, const EncSpan* spans, int n_clips, int max_T, hipStream_t s);
+// causal sliding-window attention inside each clip: row i sees rows (i - window, i]; out [rows][heads * d]
+void launch_enc_attn(const float* qkv, float* out, int heads, int d, int window, float scale, const EncSpan* spans, int n_clips, int max_T, hipStream_t s);
+// split residual VQ: per frame both input projections ([D][H] each), then level g = 0 on the semantic residual and levels 1 .. G - 1 on the
+// acoustic one: nearest row of books[g] [CB][D] by direct squared distance (lowest index on a tie), residual -= that row.  codes [rows][G]
+void launch_rvq_encode(const float* lat, int rows, int H, const float* proj_sem, const float* proj_ac, const float* books, int G, int CB, int D,
+                       int32_t* codes, hipStream_t s);
+
 } // namespace q3

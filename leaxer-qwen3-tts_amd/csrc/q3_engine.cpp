@@ -48,6 +48,18 @@ Tensor& Engine::T(const std::string& n) {
 // tensor registry (names/shapes shared with the oracle and DESIGN.md section 3) — host-only, no HIP call: the importer and
 // q3tts_config_tensor_info walk it without a GPU; the engine allocates from it.
 // ------------------------------------------------------------------------------------------------
+// dims the encoder kernels and the registry are built for (q3_encoder.cpp states why)
+bool enc_config_ok(const q3tts_config& c) {
+    if (c.enc_hidden <= 0) return true;
+    if (c.enc_n_ratios < 1 || c.enc_n_ratios > 4 || c.enc_filters < 2 || c.enc_filters > 4096 || c.enc_filters % 2 || c.enc_hidden > 8192 || c.enc_hidden % 4) return false;
+    for (int s = 0; s < c.enc_n_ratios; ++s) if (c.enc_ratios[s] < 1 || c.enc_ratios[s] > 64) return false;
+    if (c.enc_kernel < 1 || c.enc_kernel > 64 || c.enc_res_kernel < 1 || c.enc_res_kernel > 64 || c.enc_last_kernel < 1 || c.enc_last_kernel > 64) return false;
+    if (c.enc_layers < 0 || c.enc_layers > 1024 || c.enc_heads < 1 || c.enc_heads > 256 || c.enc_head_dim < 2 || c.enc_head_dim > 128 || c.enc_head_dim % 2) return false;
+    if (c.enc_ffn < 1 || c.enc_ffn > 65536 || c.enc_window < 1 || c.enc_window > 1024) return false;
+    if (c.enc_vq_dim < 4 || c.enc_vq_dim > 1024 || c.enc_vq_dim % 4 || c.enc_codebook < 1 || c.enc_codebook > 65536) return false;
+    return c.enc_rope_theta > 0.f && c.enc_norm_eps > 0.f;
+}
+
 std::vector<TensorSpec> tensor_specs(const q3tts_config& c) {
     std::vector<TensorSpec> out;
     // counts that index fixed arrays or drive loops: an out-of-range config has no registry (callers report it)
@@ -159,6 +171,40 @@ std::vector<TensorSpec> tensor_specs(const q3tts_config& c) {
         conv("spk.asp.conv", 3 * SC, c.spk_att, 1);
         conv("spk.fc", c.spk_enc_dim, 6 * SC, 1);
     }
+    if (c.enc_hidden > 0) { // audio encoder of the 12 Hz tokenizer ([HINT] transformers MimiModel.encode), fp32, torch layouts
+        if (!enc_config_ok(c)) return out;   // malformed: the engine constructor reports it
+        auto conv = [&](const std::string& n, int cout, int cin, int k, bool bias = true) {
+            add(n + ".w", {cout, cin, k}, TK_W, false, 0, 1.0f / sqrtf((float)(cin * k)));
+            if (bias) add(n + ".b", {cout}, TK_BIAS, false);
+        };
+        auto lin = [&](const std::string& n, int nout, int nin, int fuse = 0) { add(n, {nout, nin}, TK_W, false, fuse, 1.0f / sqrtf((float)nin)); };
+        const int EH = c.enc_hidden, AO = c.enc_heads * c.enc_head_dim;
+        int dim = c.enc_filters;
+        conv("enc.conv_in", dim, 1, c.enc_kernel);
+        for (int s = 0; s < c.enc_n_ratios; ++s, dim *= 2) {
+            const std::string p = "enc.stages." + std::to_string(s) + ".";
+            conv(p + "res.conv1", dim / 2, dim, c.enc_res_kernel);
+            conv(p + "res.conv2", dim, dim / 2, 1);
+            conv(p + "down", 2 * dim, dim, 2 * c.enc_ratios[s]);
+        }
+        conv("enc.conv_out", EH, dim, c.enc_last_kernel);
+        for (int i = 0; i < c.enc_layers; ++i) {
+            const std::string p = "enc.layers." + std::to_string(i) + ".";
+            add(p + "input_norm.w", {EH}, TK_NORM, false); add(p + "input_norm.b", {EH}, TK_BIAS, false);
+            lin(p + "q_proj", AO, EH, 1); lin(p + "k_proj", AO, EH, 2); lin(p + "v_proj", AO, EH, 3);   // q | k | v rows contiguous: one GEMM
+            lin(p + "o_proj", EH, AO);
+            add(p + "attn_scale", {EH}, TK_SCALE, false);
+            add(p + "post_norm.w", {EH}, TK_NORM, false); add(p + "post_norm.b", {EH}, TK_BIAS, false);
+            lin(p + "fc1", c.enc_ffn, EH); lin(p + "fc2", EH, c.enc_ffn);
+            add(p + "mlp_scale", {EH}, TK_SCALE, false);
+        }
+        conv("enc.downsample", EH, EH, 4, false);
+        lin("enc.vq.sem.in_proj", c.enc_vq_dim, EH);
+        lin("enc.vq.ac.in_proj", c.enc_vq_dim, EH);
+        // codebook rows = embed_sum / clamp(cluster_usage, 1e-5), folded by the importer.  Synthetic fill: Engine::fill_synthetic
+        // rescales them to the projected latents (enc_calibrate_synthetic), level g at 0.75^g of their spread
+        for (int g = 0; g < c.n_groups; ++g) add("enc.vq.codebook." + std::to_string(g), {c.enc_codebook, c.enc_vq_dim}, TK_W, false, 0, 1.0f);
+    }
     return out;
 }
 
@@ -217,6 +263,8 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
         throw Error("speaker encoder dims out of range");
     // the encoder's output is spliced into the prompt as ONE talker-width row (build_prompts copies `hidden` floats from it)
     if (c.spk_enc_dim > 0 && c.spk_enc_dim != c.hidden) throw Error("speaker encoder output width must equal the talker width (spk_enc_dim == hidden)");
+    if (c.enc_hidden < 0) throw Error("enc_hidden must be >= 0");
+    if (!enc_config_ok(c)) throw Error("audio encoder dims out of range");
     {   // allocate the registry (q | k | v of a layer share one block so that their rows are contiguous)
         char* fused = nullptr; size_t fused_off = 0;
         const std::vector<TensorSpec> specs = tensor_specs(c);
@@ -393,6 +441,7 @@ Engine::~Engine() {
     if (seg_tab_d) (void)hipFree(seg_tab_d);
     codec_free();
     speaker_free();
+    encoder_free();
     free_packed_weights();
     for (void* p : allocs) (void)hipFree(p);
     if (active_h) (void)hipHostFree(active_h);
@@ -447,6 +496,7 @@ void Engine::fill_synthetic(uint64_t seed) {
         launch_fill_synth(t.dev, t.bf16 ? 1 : 0, t.numel, mix64(seed ^ fnv1a(t.name)), mean, sd, stream);
     }
     sync();
+    if (has_audio_encoder()) enc_calibrate_synthetic(seed);
     finalized = false;
 }
 
@@ -565,6 +615,7 @@ void Engine::finalize() {
     for (int j = 0; j < c.n_groups - 1; ++j) { cp_head.push_back(bp("cp.head." + std::to_string(j))); cp_embed_w.push_back(bp("cp.embed." + std::to_string(j))); }
     codec_finalize();
     speaker_finalize();
+    encoder_finalize();
     pack_mfma_weights();
     build_cp_qkv_table();
     finalized = true;

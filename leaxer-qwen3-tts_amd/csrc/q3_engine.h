@@ -33,6 +33,7 @@ struct TensorSpec { // registry entry without storage
     float synth_std = 0.02f;
 };
 std::vector<TensorSpec> tensor_specs(const q3tts_config& c); // host-only
+bool enc_config_ok(const q3tts_config& c);                   // the audio encoder's dims are ones the registry and the kernels cover
 
 struct DecLayerW { // one decoder layer, bf16 matrices
     const float *in_norm = nullptr, *post_norm = nullptr, *q_norm = nullptr, *k_norm = nullptr;
@@ -57,6 +58,7 @@ struct DecStack {
 struct CodecW; // q3_codec.cpp
 struct SpeakerW; // q3_speaker.cpp
 struct SpkFront; // q3_speaker.cpp
+struct EncoderW; // q3_encoder.cpp
 
 class Engine {
 public:
@@ -321,6 +323,24 @@ public:
     bool mel_gpu(const float* audio, int64_t n, int sample_rate, float* mel, int64_t cap, int* frames);
     // n_clips clips -> out [n_clips][spk_enc_dim]; a clip's embedding does not depend on the rest of the batch
     void speaker_embed_pcm(int n_clips, const float* const* pcm, const int64_t* n_samples, const int32_t* rates, float* out);
+
+    // ---- audio encoder of the 12 Hz tokenizer (q3_encoder.cpp): audio -> codes, fp32 throughout ----
+    EncoderW* enc = nullptr;
+    bool has_audio_encoder() const { return c.enc_hidden > 0; }
+    void encoder_finalize();
+    void encoder_free();
+    static constexpr int64_t kEncMaxClipSamples = 1440000;    // 60 s at 24 kHz: one clip
+    static constexpr int64_t kEncMaxRawSamples = 23040000;    // a clip (and a group's clips together) at another rate: samples to resample (60 s at 384 kHz, 92 MB)
+    static constexpr int64_t kEncMaxGroupSamples = 2880000;   // a batch is processed in consecutive groups of at most this many samples
+    int64_t audio_encode_len(int64_t n24) const;              // frames of a clip of n24 samples at 24 kHz (the convs' own ceil rule)
+    // n_clips clips (mono float, any rate) -> codes [frames][n_groups] int64 and / or latents [frames][enc_hidden] per clip (either array
+    // or entry may be null); caps[i] = frames of room in clip i's buffers.  One set of launches per group; a clip's result does not
+    // depend on the rest of the batch.  Validates everything before the first byte moves.
+    void audio_encode(int n_clips, const float* const* pcm, const int64_t* n_samples, const int32_t* rates, int64_t* const* codes_out,
+                      float* const* latents_out, const int32_t* caps, int32_t* n_frames);
+    float last_audio_encode_ms = 0.f;                         // device time of the last audio_encode call: uploads + launches of all its groups
+    void enc_transformer_host(const float* rows, int n_rows, float* out);   // parity aid: the transformer alone
+    void enc_calibrate_synthetic(uint64_t seed);              // fill_synthetic: codebooks at the scale of the projected latents
 
     // ---- internals ----
     DecStack talker, cp;

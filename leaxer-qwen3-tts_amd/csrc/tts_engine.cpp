@@ -2,6 +2,7 @@
 #include "tts_engine.h"
 
 #include <algorithm>
+#include <climits>
 #include <cctype>
 #include <cstdlib>
 #include <cstring>
@@ -25,7 +26,7 @@ Speaker parse_speaker(const std::string& name) { // reference src/tts_onnx.cpp:5
 
 static int lang_index(Language l) { return l == Language::Auto ? 0 : (int)(language_to_codec_id(l) - config::LANG_ENGLISH) + 1; }
 
-TTSEngine::TTSEngine(const std::string& model_dir) {
+TTSEngine::TTSEngine(const std::string& model_dir, bool audio_encoder) {
     const char* env_b = std::getenv("Q3TTS_MAX_BATCH");
     max_batch_ = env_b ? std::max(1, std::atoi(env_b)) : 1;
     const int device = std::getenv("Q3TTS_DEVICE") ? std::atoi(std::getenv("Q3TTS_DEVICE")) : 0;
@@ -35,6 +36,7 @@ TTSEngine::TTSEngine(const std::string& model_dir) {
     if (model_dir.rfind("synthetic:", 0) == 0 || model_dir.rfind("synthetic-1.7b:", 0) == 0) {   // seeded weights at the 0.6B / 1.7B dims
         const bool big = model_dir[9] == '-';
         q3tts_default_config(big ? "1.7b" : "0.6b", &cfg);
+        if (audio_encoder) q3tts_config_enable_audio_encoder(&cfg);
         h_ = q3tts_create(&cfg, device, max_batch_, max_ctx, 0);
         if (!h_) { error_msg_ = q3tts_last_error(nullptr); return; }
         if (q3tts_fill_synthetic(h_, std::strtoull(model_dir.c_str() + (big ? 15 : 10), nullptr, 10)) != 0 || q3tts_finalize(h_) != 0) { error_msg_ = q3tts_last_error(h_); return; }
@@ -240,6 +242,67 @@ std::vector<float> TTSEngine::synthesize_tokens_continue(const std::vector<int64
 std::vector<float> TTSEngine::synthesize_speaker(const std::string& text, Speaker, Language lang, const SamplingParams& params) {
     std::cerr << "[TTSEngine] Preset speakers require CustomVoice model (not yet supported)" << std::endl; // :327
     return synthesize(text, lang, params);
+}
+
+bool TTSEngine::has_audio_encoder() const { return h_ && q3tts_has_audio_encoder(h_) != 0; }
+
+std::vector<int64_t> TTSEngine::encode_audio(const std::vector<float>& pcm, int sample_rate) {
+    if (!ready_) return {};
+    if (!has_audio_encoder()) { std::cerr << "[TTSEngine] model has no audio encoder" << std::endl; return {}; }
+    if (pcm.empty() || sample_rate < 1) { std::cerr << "[TTSEngine] encode_audio: empty clip or bad sample rate" << std::endl; return {}; }
+    const int64_t n24 = (int64_t)((double)pcm.size() * 24000.0 / sample_rate) + 1;
+    const int64_t cap64 = q3tts_audio_encode_len(h_, n24);
+    if (cap64 < 1 || cap64 > INT32_MAX) { std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl; return {}; }
+    std::vector<int64_t> codes((size_t)cap64 * (size_t)n_groups_);
+    const float* clip = pcm.data();
+    const int64_t n = (int64_t)pcm.size();
+    const int32_t rate = sample_rate, cap = (int32_t)cap64;
+    int64_t* out = codes.data();
+    int32_t frames = 0;
+    if (q3tts_audio_encode_batch_host(h_, 1, &clip, &n, &rate, &out, &cap, &frames) != 0) {
+        std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl;
+        return {};
+    }
+    codes.resize((size_t)frames * (size_t)n_groups_);
+    return codes;
+}
+
+static bool read_wav_file(const std::string& path, std::vector<float>& pcm, int32_t& rate) {
+    int64_t n = 0;
+    if (q3tts_read_wav_host(path.c_str(), nullptr, 0, &n, &rate) != 0 || n < 1) { std::cerr << "[TTSEngine] Failed to read audio: " << path << std::endl; return false; }
+    pcm.resize((size_t)n);
+    if (q3tts_read_wav_host(path.c_str(), pcm.data(), n, &n, &rate) != 0) { std::cerr << "[TTSEngine] Failed to read audio: " << path << std::endl; return false; }
+    return true;
+}
+
+std::vector<int64_t> TTSEngine::encode_audio(const std::string& wav_path) {
+    std::vector<float> pcm;
+    int32_t rate = 0;
+    if (!read_wav_file(wav_path, pcm, rate)) return {};
+    return encode_audio(pcm, rate);
+}
+
+std::vector<float> TTSEngine::synthesize_clone_icl(const std::vector<int64_t>& token_ids, const std::vector<int64_t>& ref_text_ids,
+                                                   const std::string& ref_wav_path, Language lang, const SamplingParams& params,
+                                                   std::vector<int64_t>* all_codes) {
+    if (all_codes) all_codes->clear();
+    std::vector<float> pcm;
+    int32_t rate = 0;
+    if (!read_wav_file(ref_wav_path, pcm, rate)) return {};
+    return synthesize_clone_icl(token_ids, ref_text_ids, pcm, rate, lang, params, all_codes);
+}
+
+std::vector<float> TTSEngine::synthesize_clone_icl(const std::vector<int64_t>& token_ids, const std::vector<int64_t>& ref_text_ids,
+                                                   const std::vector<float>& ref_pcm, int ref_rate, Language lang, const SamplingParams& params,
+                                                   std::vector<int64_t>* all_codes) {
+    if (all_codes) all_codes->clear();
+    if (!ready_ || token_ids.size() < 3) return {};
+    const std::vector<int64_t> ref_codes = encode_audio(ref_pcm, ref_rate);
+    if (ref_codes.empty()) return {};
+    std::vector<int64_t> ids(token_ids.begin(), token_ids.begin() + 3);   // role ids, reference text, target text and tail
+    ids.insert(ids.end(), ref_text_ids.begin(), ref_text_ids.end());
+    ids.insert(ids.end(), token_ids.begin() + 3, token_ids.end());
+    return synthesize_tokens_continue(ids, ref_codes, lang, params, all_codes);
 }
 
 std::vector<float> TTSEngine::extract_speaker_embedding(const std::string& audio_path) { // reference tts_onnx.cpp:331-365

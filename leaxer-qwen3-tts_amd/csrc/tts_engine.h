@@ -48,7 +48,9 @@ public:
     // or the literal "synthetic:<seed>" for seeded random 0.6B weights (benchmarks, smoke tests).
     // vocab.json + merges.txt are looked up where the reference looks (<parent of model_dir>/models/
     // Qwen3-TTS-12Hz-0.6B-Base/, tts_onnx.cpp:110-112), then in model_dir.
-    explicit TTSEngine(const std::string& model_dir);
+    // audio_encoder: a synthetic: model is created with the 12 Hz tokenizer's encoder enabled (q3tts_config_enable_audio_encoder); a
+    // weight file has it when it carries the enc.* tensors, whatever this says
+    explicit TTSEngine(const std::string& model_dir, bool audio_encoder = false);
     ~TTSEngine();
     TTSEngine(const TTSEngine&) = delete;
     TTSEngine& operator=(const TTSEngine&) = delete;
@@ -129,6 +131,20 @@ public:
     std::vector<float> synthesize_tokens_continue(const std::vector<int64_t>& token_ids, const std::vector<int64_t>& prefix_codes,
                                                   Language lang = Language::Auto, const SamplingParams& params = SamplingParams(),
                                                   std::vector<int64_t>* all_codes = nullptr);
+    // Audio -> codes (include/q3tts.h: q3tts_audio_encode_batch_host; [HINT] the 12 Hz tokenizer's encoder, beside the reference's
+    // methods): mono samples at sample_rate -> frames of n_groups() ids, frame-major — what synthesize_tokens_continue takes.  Empty on error.
+    std::vector<int64_t> encode_audio(const std::vector<float>& pcm, int sample_rate);
+    std::vector<int64_t> encode_audio(const std::string& wav_path);
+    // In-context voice clone ([HINT]): the reference audio is encoded, the text becomes reference text +
+    // target text (ref_text_ids go between token_ids' three role ids and its text) and the utterance is continued behind the
+    // reference's codes; the returned samples are the target's only.  Exactly encode_audio + synthesize_tokens_continue.
+    std::vector<float> synthesize_clone_icl(const std::vector<int64_t>& token_ids, const std::vector<int64_t>& ref_text_ids,
+                                            const std::vector<float>& ref_pcm, int ref_rate, Language lang = Language::Auto,
+                                            const SamplingParams& params = SamplingParams(), std::vector<int64_t>* all_codes = nullptr);
+    std::vector<float> synthesize_clone_icl(const std::vector<int64_t>& token_ids, const std::vector<int64_t>& ref_text_ids,
+                                            const std::string& ref_wav_path, Language lang = Language::Auto,
+                                            const SamplingParams& params = SamplingParams(), std::vector<int64_t>* all_codes = nullptr);
+    bool has_audio_encoder() const;
     int n_groups() const { return n_groups_; }
     bool has_speaker_encoder() const; // true when the weight file carries the spk.* tensors (reference: speaker_encoder.onnx present)
     bool is_ready() const { return ready_; }

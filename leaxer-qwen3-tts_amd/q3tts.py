@@ -30,6 +30,12 @@ _CFG_FIELDS = [
     ("spk_enc_dim", C.c_int32), ("spk_mel", C.c_int32), ("spk_channels", C.c_int32), ("spk_scale", C.c_int32),
     ("spk_se", C.c_int32), ("spk_att", C.c_int32),
     ("cp_hidden", C.c_int32),
+    # audio encoder of the 12 Hz tokenizer (enc_hidden == 0: none); enc_ratios in encoder order
+    ("enc_hidden", C.c_int32), ("enc_filters", C.c_int32), ("enc_n_ratios", C.c_int32), ("enc_ratios", C.c_int32 * 4),
+    ("enc_kernel", C.c_int32), ("enc_res_kernel", C.c_int32), ("enc_last_kernel", C.c_int32),
+    ("enc_layers", C.c_int32), ("enc_heads", C.c_int32), ("enc_head_dim", C.c_int32), ("enc_ffn", C.c_int32), ("enc_window", C.c_int32),
+    ("enc_vq_dim", C.c_int32), ("enc_codebook", C.c_int32),
+    ("enc_rope_theta", C.c_float), ("enc_norm_eps", C.c_float),
 ]
 
 
@@ -39,6 +45,9 @@ class Config(C.Structure):
     def to_dict(self):
         d = {}
         for n, _ in _CFG_FIELDS:
+            if n.startswith("enc_") and self.enc_hidden == 0:
+                continue   # no audio encoder: the enc_* fields (all 0) are left out.  The oracle keeps its own shorter mirror of the struct and
+                #            existing tests compare the two dicts, so an encoder-less config must serialise as it did before; from_dict puts the zeros back
             v = getattr(self, n)
             d[n] = list(v) if hasattr(v, "__len__") else v
         return d
@@ -47,8 +56,9 @@ class Config(C.Structure):
     def from_dict(cls, d):
         c = cls()
         for n, t in _CFG_FIELDS:
-            v = d[n] if n in d or not (n.startswith("spk_") or n == "cp_hidden") else 0
+            v = d[n] if n in d or not (n.startswith("spk_") or n == "cp_hidden" or n.startswith("enc_")) else 0
             if hasattr(t, "_length_"):
+                v = v or []
                 arr = t()
                 for i, x in enumerate(v):
                     arr[i] = x
@@ -99,6 +109,8 @@ EXPORTS = [
     "q3tts_slot_begin_prefixed", "q3tts_slots_begin_prefixed", "q3tts_slots_begin_ragged", "q3tts_synthesize_prefixed_host",
     "q3tts_slot_text_open", "q3tts_slot_text_append_host", "q3tts_slots_text_append_ids", "q3tts_slot_text_status",
     "q3tts_build_prompt_open_host", "q3tts_synthesize_live_host",
+    "q3tts_config_enable_audio_encoder", "q3tts_has_audio_encoder", "q3tts_audio_encode_len", "q3tts_audio_encode_host",
+    "q3tts_audio_encode_batch_host", "q3tts_audio_encode_latents_host", "q3tts_audio_encode_batch_latents_host", "q3tts_last_audio_encode_ms", "q3tts_test_audio_encoder_transformer_host",
 ]
 
 # q3tts_audio_cb: int (*)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished)
@@ -204,6 +216,16 @@ def lib():
     L.q3tts_resample_gpu_host.argtypes = [vp, vp, i64, i32, i32, vp, i64]
     L.q3tts_mel_gpu_host.argtypes = [vp, vp, i64, i32, vp, i64, C.POINTER(C.c_int32)]
     L.q3tts_speaker_embed_pcm_batch_host.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.q3tts_config_enable_audio_encoder.argtypes = [C.POINTER(Config)]
+    L.q3tts_has_audio_encoder.argtypes = [vp]
+    L.q3tts_audio_encode_len.restype = i64
+    L.q3tts_audio_encode_len.argtypes = [vp, i64]
+    L.q3tts_audio_encode_host.argtypes = [vp, vp, i64, vp, i32, C.POINTER(C.c_int32)]
+    L.q3tts_audio_encode_batch_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.q3tts_audio_encode_batch_latents_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.q3tts_last_audio_encode_ms.argtypes = [vp, C.POINTER(f32)]
+    L.q3tts_audio_encode_latents_host.argtypes = [vp, vp, i64, vp, vp, i32, C.POINTER(C.c_int32)]
+    L.q3tts_test_audio_encoder_transformer_host.argtypes = [vp, vp, i32, vp]
     L.q3tts_codec_decode_chunked_host.argtypes = [vp, vp, i32, i32, i32, vp, i64, C.POINTER(i64)]
     L.q3tts_slot_codec_decode_range_host.argtypes = [vp, i32, i32, i32, i32, vp, i64, C.POINTER(i64)]
     L.q3tts_tokenizer_create.restype = vp
@@ -243,6 +265,13 @@ def default_config(name="0.6b"):
     if lib().q3tts_default_config(name.encode(), C.byref(c)) != 0:
         raise ValueError(f"unknown config {name!r}")
     return c
+
+
+def enable_audio_encoder(cfg):
+    """q3tts_config_enable_audio_encoder: the 12 Hz tokenizer's encoder dimensions filled into cfg (returned for chaining)"""
+    if lib().q3tts_config_enable_audio_encoder(C.byref(cfg)) != 0:
+        raise ValueError("q3tts_config_enable_audio_encoder failed")
+    return cfg
 
 
 def _p(a):
@@ -775,6 +804,98 @@ class Engine:
         out = np.zeros((n, self.cfg.spk_enc_dim), np.float32)
         self._ck(self.L.q3tts_speaker_embed_pcm_batch_host(self.h, n, ptrs, _p(ns) if n else None, _p(rt) if n else None, _p(out) if out.size else None))
         return out
+
+    # ---- audio -> codes: the 12 Hz tokenizer's encoder ----
+    @property
+    def has_audio_encoder(self):
+        return bool(self.L.q3tts_has_audio_encoder(self.h))
+
+    def audio_encode_len(self, n_samples):
+        """frames of a clip of n_samples samples at 24 kHz (host-only)"""
+        return int(self._ck(self.L.q3tts_audio_encode_len(self.h, int(n_samples))))
+
+    def audio_encode(self, pcm24k, want_latents=False):
+        """pcm24k (mono float, 24 kHz) -> codes [F][n_groups] int64, the layout slot_codes returns and slot_begin(prefix_codes=) takes;
+        want_latents: (codes, latents [F][enc_hidden]), the rows the quantiser sees (parity aid)"""
+        a = np.ascontiguousarray(pcm24k, np.float32).reshape(-1)
+        F = max(int(self.L.q3tts_audio_encode_len(self.h, a.size)), 1)
+        codes = np.zeros((F, self.cfg.n_groups), np.int64)
+        nf = C.c_int32(0)
+        if not want_latents:
+            self._ck(self.L.q3tts_audio_encode_host(self.h, _p(a), a.size, _p(codes), F, C.byref(nf)))
+            return codes[: nf.value]
+        lat = np.zeros((F, max(self.cfg.enc_hidden, 1)), np.float32)
+        self._ck(self.L.q3tts_audio_encode_latents_host(self.h, _p(a), a.size, _p(lat), _p(codes), F, C.byref(nf)))
+        return codes[: nf.value], lat[: nf.value]
+
+    def audio_encode_batch(self, clips, sample_rates=24000, want_latents=False):
+        """audio_encode for many clips at once (mono float arrays, any rate; a scalar rate applies to all): one set of launches,
+        each clip's codes identical to encoding it alone (q3tts_audio_encode_batch_host).  Returns a list of [F_i][n_groups] arrays;
+        want_latents: (that list, the list of latents [F_i][enc_hidden]) — the parity aid."""
+        n = len(clips)
+        keep = [np.ascontiguousarray(a, np.float32).reshape(-1) for a in clips]
+        rates = [int(sample_rates)] * n if np.isscalar(sample_rates) else [int(r) for r in sample_rates]
+        if len(rates) != n:
+            raise ValueError("sample_rates: one rate per clip, or one for all")
+        caps = [max(int(self.L.q3tts_audio_encode_len(self.h, int(a.size * 24000.0 / max(r, 1)) + 1)), 1) for a, r in zip(keep, rates)]
+        outs = [np.zeros((cp, self.cfg.n_groups), np.int64) for cp in caps]
+        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in keep])
+        optrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+        ns = np.array([a.size for a in keep], np.int64)
+        rt = np.array(rates, np.int32)
+        cp = np.array(caps, np.int32)
+        nf = np.zeros(max(n, 1), np.int32)
+        args = (self.h, n, ptrs, _p(ns) if n else None, _p(rt) if n else None, optrs)
+        if not want_latents:
+            self._ck(self.L.q3tts_audio_encode_batch_host(*args, _p(cp) if n else None, _p(nf)))
+            return [o[: nf[i]] for i, o in enumerate(outs)]
+        lats = [np.zeros((c_, max(self.cfg.enc_hidden, 1)), np.float32) for c_ in caps]
+        lptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in lats])
+        self._ck(self.L.q3tts_audio_encode_batch_latents_host(*args, lptrs, _p(cp) if n else None, _p(nf)))
+        return [o[: nf[i]] for i, o in enumerate(outs)], [a[: nf[i]] for i, a in enumerate(lats)]
+
+    def last_audio_encode_ms(self):
+        ms = C.c_float(0)
+        self._ck(self.L.q3tts_last_audio_encode_ms(self.h, C.byref(ms)))
+        return float(ms.value)
+
+    def audio_encoder_transformer(self, rows):
+        """parity aid (FLAG_TEST_HOOKS engines): the encoder's transformer alone on rows [n][enc_hidden]"""
+        r = np.ascontiguousarray(rows, np.float32)
+        out = np.zeros_like(r)
+        self._ck(self.L.q3tts_test_audio_encoder_transformer_host(self.h, _p(r), r.shape[0], _p(out)))
+        return out
+
+    def synthesize_icl(self, ref_pcm, ref_ids, ids, sp, lang=0, seed=0, stream_id=0, ignore_eos=False, speaker=None, slot=0, ref_rate=24000):
+        """In-context voice clone ([HINT]): the reference audio is encoded to codes, the prompt is built from
+        the reference text followed by the target text (ids: the framed target utterance as the other entries take it, ref_ids: the
+        reference's text ids alone, spliced in front of the target text), the slot is begun behind the reference codes, and the returned
+        samples are the target's only.  Returns (pcm, codes, n_ref_frames): codes cover reference + new frames."""
+        ref_codes = self.audio_encode_batch([ref_pcm], ref_rate)[0]
+        toks = self.frame_icl_ids(ref_ids, ids)
+        prompt, trailing = self.build_prompt(toks, lang, speaker)
+        self.slot_begin(slot, prompt, trailing, sp, seed, stream_id, ignore_eos, prefix_codes=ref_codes)
+        try:
+            left = sp.max_new_tokens
+            while left > 0:
+                n = min(32, left)
+                active = self.decode_steps(n)
+                left -= n
+                if active == 0:
+                    break
+            codes = self.slot_codes(slot)
+            F0 = ref_codes.shape[0]
+            pcm = self.slot_codec_decode_range(slot, F0, codes.shape[0], F0) if codes.shape[0] > F0 else np.zeros(0, np.float32)
+        finally:
+            self.slot_release(slot)
+        return pcm, codes, F0
+
+    @staticmethod
+    def frame_icl_ids(ref_ids, ids):
+        """ids = a framed utterance as every other entry takes it (3 role ids, the text, the template's 2-id tail); the reference's
+        text ids go between the role ids and the target text: text = reference text + target text"""
+        ids = np.asarray(ids, np.int64).reshape(-1)
+        return np.concatenate([ids[:3], np.asarray(ref_ids, np.int64).reshape(-1), ids[3:]])
 
     @staticmethod
     def _instruct_args(instructs, n):

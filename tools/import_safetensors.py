@@ -81,8 +81,32 @@ RULES = {
         (r"asp\.conv\.(weight|bias)", lambda m: f"spk.asp.conv.{m.group(1)[0]}"),
         (r"fc\.(weight|bias)", lambda m: f"spk.fc.{m.group(1)[0]}"),
     ],
+    # transformers MimiModel state_dict: the 12 Hz tokenizer's encoder half (SEANet encoder, encoder transformer, downsample, split RVQ).
+    # encoder.layers: 0 = first conv, per stage s a residual block at 1 + 3s and a strided conv at 3 + 3s (an ELU module between),
+    # the last conv at 2 + 3 x stages (14 with four stages; any index that is none of the others).  A codebook arrives as two buffers,
+    # embed_sum and cluster_usage: the second maps to "<name>#usage" and fold_codebooks divides (rows = embed_sum / clamp(usage, 1e-5)).
+    # Mimi ships 32 quantizers; those beyond the config's n_groups have no registry tensor and are left out.
+    "audio_encoder": [
+        (r"encoder\.layers\.0\.conv\.(weight|bias)", lambda m: f"enc.conv_in.{m.group(1)[0]}"),
+        (r"encoder\.layers\.(\d+)\.block\.([13])\.conv\.(weight|bias)",
+         lambda m: f"enc.stages.{(int(m.group(1)) - 1) // 3}.res.conv{(int(m.group(2)) + 1) // 2}.{m.group(3)[0]}"),
+        (r"encoder\.layers\.(\d+)\.conv\.(weight|bias)",
+         lambda m: (f"enc.stages.{int(m.group(1)) // 3 - 1}.down." if int(m.group(1)) % 3 == 0 else "enc.conv_out.") + m.group(2)[0]),
+        (r"encoder_transformer\.layers\.(\d+)\.(input|post_attention)_layernorm\.(weight|bias)",
+         lambda m: f"enc.layers.{m.group(1)}.{'input' if m.group(2) == 'input' else 'post'}_norm.{m.group(3)[0]}"),
+        (r"encoder_transformer\.layers\.(\d+)\.self_attn\.([qkvo])_proj\.weight", r"enc.layers.\1.\2_proj"),
+        (r"encoder_transformer\.layers\.(\d+)\.mlp\.fc([12])\.weight", r"enc.layers.\1.fc\2"),
+        (r"encoder_transformer\.layers\.(\d+)\.self_attn_layer_scale\.scale", r"enc.layers.\1.attn_scale"),
+        (r"encoder_transformer\.layers\.(\d+)\.mlp_layer_scale\.scale", r"enc.layers.\1.mlp_scale"),
+        (r"downsample\.conv\.weight", "enc.downsample.w"),
+        (r"quantizer\.(semantic|acoustic)_residual_vector_quantizer\.input_proj\.weight",
+         lambda m: f"enc.vq.{'sem' if m.group(1) == 'semantic' else 'ac'}.in_proj"),
+        (r"quantizer\.(semantic|acoustic)_residual_vector_quantizer\.layers\.(\d+)\.codebook\.(embed_sum|cluster_usage)",
+         lambda m: f"enc.vq.codebook.{int(m.group(2)) + (m.group(1) == 'acoustic')}" + ("#usage" if m.group(3) == "cluster_usage" else "")),
+    ],
 }
-DEFAULT_PREFIX = {"talker": "talker.", "predictor": "talker.code_predictor.", "code2wav": "decoder.", "speaker": "speaker_encoder."}  # [HINT]
+DEFAULT_PREFIX = {"talker": "talker.", "predictor": "talker.code_predictor.", "code2wav": "decoder.", "speaker": "speaker_encoder.",
+                  "audio_encoder": "speech_tokenizer.encoder."}  # [HINT]
 _DTYPES = {"F32": ("<f4", 4), "F16": ("<f2", 2), "BF16": (None, 2), "F64": ("<f8", 8)}
 
 
@@ -129,6 +153,25 @@ def write_safetensors(path, tensors, bf16=()):
         f.write(hj)
         for b in blobs:
             f.write(b)
+
+
+def fold_target(dst):
+    """registry name a mapped name contributes to ("<name>#usage" is the divisor of <name>)"""
+    return dst.split("#", 1)[0]
+
+
+def fold_codebooks(tensors):
+    """{name: array} with every "<name>#usage" folded into <name>: rows = embed_sum / clamp(cluster_usage, 1e-5) (MimiEuclideanCodebook.embed)"""
+    out = {}
+    for k, a in tensors.items():
+        if k.endswith("#usage"):
+            continue
+        u = tensors.get(k + "#usage")
+        out[k] = a if u is None else (np.asarray(a, np.float32) / np.maximum(np.asarray(u, np.float32).reshape(-1), 1e-5)[:, None]).astype(np.float32)
+    stray = [k for k in tensors if k.endswith("#usage") and fold_target(k) not in tensors]
+    if stray:
+        raise ValueError(f"cluster_usage without embed_sum: {stray[:4]}")
+    return out
 
 
 def map_names(names, prefixes=None, extra_rules=()):
@@ -217,6 +260,13 @@ def import_checkpoint(paths, cfg, prefixes=None, extra_rules=(), allow_missing=F
     mapping = map_names(src.keys(), prefixes, extra_rules)
     out = {}
     for name, dst in mapping.items():
+        if fold_target(dst).startswith("enc.vq.codebook.") and fold_target(dst) not in specs:
+            continue   # a quantizer level beyond n_groups (Mimi ships 32, the 12 Hz tokenizer uses the first 16), or no encoder in this config
+        if dst.endswith("#usage"):
+            if dst in out:
+                raise ValueError(f"two checkpoint tensors map to {dst}")
+            out[dst] = src[name]
+            continue
         if dst not in specs:
             raise ValueError(f"{name} -> {dst}: not a tensor of this config")
         a = src[name]
@@ -228,6 +278,7 @@ def import_checkpoint(paths, cfg, prefixes=None, extra_rules=(), allow_missing=F
         if dst in out:
             raise ValueError(f"two checkpoint tensors map to {dst}")
         out[dst] = a
+    out = fold_codebooks(out)
     missing = [n for n in specs if n not in out]
     if missing and not allow_missing:
         raise ValueError(f"{len(missing)} tensors not found in the checkpoint, e.g. {missing[:6]} (use --allow-missing, --prefix or --map)")
@@ -239,7 +290,7 @@ def main():
     ap.add_argument("files", nargs="+")
     ap.add_argument("--out")
     ap.add_argument("--config", default="0.6b", help='"0.6b", "1.7b" or a JSON file of q3tts_config fields')
-    ap.add_argument("--prefix", action="append", default=[], help="component=prefix (talker, predictor, code2wav, speaker)")
+    ap.add_argument("--prefix", action="append", default=[], help="component=prefix (talker, predictor, code2wav, speaker, audio_encoder)")
     ap.add_argument("--map", help='JSON list of [regex, replacement] applied to the full checkpoint name first')
     ap.add_argument("--allow-missing", action="store_true", help="write the file although registry tensors have no source (for inspection: "
                     "q3tts_load_weights_file refuses a file that does not carry every tensor, naming the missing ones)")
@@ -264,12 +315,14 @@ def main():
         for k in sorted(names):
             dst, note = ex[k]
             shape_note = ""
-            if dst is not None and dst in specs and int(np.prod(names[k])) != int(np.prod(specs[dst])):
+            if dst is not None and dst in specs and int(np.prod(names[k])) != int(np.prod(specs[dst])):  # noqa: E501
                 shape_note = f"  SHAPE MISMATCH: registry {specs[dst]}"
-            if dst is not None and dst not in specs:
+            if dst is not None and dst.endswith("#usage"):
+                shape_note = "  (divisor: rows = embed_sum / clamp(cluster_usage, 1e-5))"
+            elif dst is not None and dst not in specs:
                 shape_note = "  NOT A TENSOR OF THIS CONFIG"
             print(f"{k:80s} {str(tuple(names[k])):24s} -> {dst or '(unmapped)'}{shape_note}" + (f"   [{note}]" if note else ""))
-        got = {d for d, _ in ex.values() if d}
+        got = {fold_target(d) for d, _ in ex.values() if d}
         missing = [n for n in specs if n not in got]
         print(f"\n{len(names)} checkpoint tensors, {sum(d is not None for d, _ in ex.values())} mapped, "
               f"{sum(d is None for d, _ in ex.values())} unmapped; {len(missing)} of {len(specs)} registry tensors without a source")
