@@ -219,6 +219,25 @@ int q3tts_codec_stream_push_batch_host(q3tts_engine* e, int n_streams, const int
  * may alternate on a slot — and reads the codes where the sampler left them: they never leave HBM.  Slots must be distinct. */
 int q3tts_slots_codec_decode_new_host(q3tts_engine* e, int n_slots, const int32_t* slots, float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len,
                                       int32_t* frame_begin, int32_t* frame_end);
+/* run_vocoder (tts_onnx.cpp:759-776) carries no state; a carried-state stream that continues behind frames whose audio nobody wants
+ * needs their state, not their samples.  PRIMING puts g open streams that hold no frames yet into the state a push of their first
+ * n_s = frame_offsets[s + 1] - frame_offsets[s] frames (codes as in the batched push) would leave: the pre-transformer alone runs over
+ * all streams' rows in one set of launches per layer (padded [stream][longest] rows, scratch K / V), and two copy kernels move the
+ * tails a stream keeps — the last min(n_s, window - 1) rotated K / V rows of every layer, the last min(n_s, look-back) output rows —
+ * to the front of the stream's own buffers.  The conv decoder and the upsampling stages do not run, no sample is produced, and the
+ * stream's buffers stay as q3tts_codec_stream_begin sized them whatever n_s is.  The next push continues at frame n_s and equals the
+ * push behind a pushed history to fp32 rounding (the bound of the pushes themselves).  n_s == 0 leaves a stream untouched.  Everything
+ * is validated before anything moves — ids distinct and open, "stream already has frames", offsets non-decreasing from 0, codes inside
+ * the codebook, no n_s beyond the stream's max_frames.  q3tts_last_codec_ms reports the call's device time. */
+int q3tts_codec_stream_prime_batch_host(q3tts_engine* e, int n_streams, const int32_t* stream_ids, const int64_t* codes, const int32_t* frame_offsets);
+/* run_vocoder (tts_onnx.cpp:759-776) would decode these frames again with every call; here the slots' implicit streams (the ones
+ * q3tts_slots_codec_decode_new_host uses) are restarted and primed with the slots' first n_frames[i] frames, read from the slots' code
+ * buffers in HBM; the next q3tts_slots_codec_decode_new_host call starts at frame n_frames[i].  n_frames[i] <= the slot's frame count;
+ * slots distinct.  For a slot begun behind a prefix (q3tts_slot_begin_codes): n_frames[i] = n_prefix delivers the new frames only. */
+int q3tts_slots_codec_prime(q3tts_engine* e, int n_slots, const int32_t* slots, const int32_t* n_frames);
+/* state of a carried-state stream (run_vocoder, tts_onnx.cpp:759-776, keeps none): frames pushed or primed so far, K / V rows the
+ * sliding buffer can hold (P), bytes of the stream's K / V and row buffers; any output may be NULL */
+int q3tts_codec_stream_info(q3tts_engine* e, int stream_id, int* n_done, int* kv_capacity_rows, int64_t* bytes);
 /* ---- the same sessions, batch-first, on DEVICE pointers ----
  * For a host application that keeps embeddings, logits and ids in HBM: no PCIe round trip per call.  Row b of a call is slot b of the
  * engine (batch <= max_batch).  Tensors (float / id buffers) are device pointers on the engine's GPU, any allocator; control arrays
@@ -417,11 +436,25 @@ int q3tts_synthesize_instruct_host(q3tts_engine* e, int n_utt, const int64_t* id
  * the samples the NEW frames own, out of the decode of all the utterance's frames (the decoder is causal: that slice is exact, and it
  * joins the prefix's own audio without a seam), pcm_len[u] their count.  An utterance without a prefix gets what
  * q3tts_synthesize_schedule_host gives it, bit for bit.  Non-streaming only: delivery through a q3tts_audio_cb with a prefix is not
- * implemented. */
+ * implemented here (q3tts_synthesize_continue_stream_host is the streaming entry). */
 int q3tts_synthesize_continue_host(q3tts_engine* e, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                    const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                    float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                    const int64_t* prefix_codes, const int32_t* prefix_offsets);
+/* q3tts_synthesize_stream_host with teacher-forced frames per utterance (tts_onnx.cpp:824-842 is a frame's row, :759-776 the vocoder
+ * the chunks stand for): q3tts_synthesize_continue_host's arguments, in its order, then the stream entry's chunk_frames / cb / user.
+ * A prefixed utterance is begun through the continue entry's forced begin (on its own, or as a member of the one ragged begin under
+ * Q3TTS_FLAG_RAGGED_PREFILL), so its codes equal that entry's bit for bit; the fresh prefixed slots of an admission look are primed in
+ * one q3tts_slots_codec_prime call before the first decode chunk, so only the new frames are ever vocoded.  cb's frame_begin /
+ * frame_end count the utterance's frames with the prefix included: an utterance's first call has frame_begin == n_prefix.  pcm_out /
+ * pcm_len hold the new frames' samples only; n_frames and codes_out ([n_utt][P + max_new_tokens][n_groups]) are the continue entry's.
+ * Admission as in the stream entry (prompt + prefix frames + cap must fit, no preemption).  An utterance with an empty prefix range
+ * gets what q3tts_synthesize_stream_host gives it, bit for bit; prefix_codes == NULL is that entry. */
+int q3tts_synthesize_continue_stream_host(q3tts_engine* e, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                          const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                          float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                                          const int64_t* prefix_codes, const int32_t* prefix_offsets,
+                                          int chunk_frames, q3tts_audio_cb cb, void* user);
 /* ---- shared prompt prefix: run_prefill (tts_onnx.cpp:615-665) once for rows that many utterances have in front of their prompts ----
  * A prefix is n_rows talker input rows (an instruction's text_project rows, say), 1 <= n_rows < max_ctx, prefilled once in a borrowed
  * free slot; the K / V rows of its positions are kept on the engine in a compact store.  Slots begun behind it get a COPY of those rows

@@ -56,7 +56,8 @@ static void usage(const char* prog) {
     printf("  --top-k N             top-k (default: 50)\n  --top-p FLOAT         top-p (default: 0.95)\n");
     printf("  --rep-penalty FLOAT   repetition penalty on the first codebook's ids (default: 1.0 = off; not a flag of the reference CLI)\n");
     printf("  --max-tokens N        max codec frames (default: 2048)\n  --seed N              sampling seed (default: 0)\n");
-    printf("  --stream-chunk N      with --tokens: decode audio every N frames while generating (same samples as the one-shot decode)\n");
+    printf("  --stream-chunk N      with --tokens: decode audio every N frames while generating (same samples as the one-shot decode);\n");
+    printf("                        combines with --continue-codes and with --ref + --ref-text / --ref-tokens (the prefix is history, never decoded)\n");
     printf("  --feed K              with --stream-chunk: hand the text to the engine K tokens at a time while it generates (live text; same codes, and with --save-codes the same samples as without --feed)\n  -h, --help\n");
 }
 
@@ -161,8 +162,8 @@ int main(int argc, char** argv) {
         printf("Encoded %zu frames\nCodes saved to: %s\n", codes.size() / (size_t)enc_engine.n_groups(), save_codes.c_str());
         return 0;
     }
-    if (icl && (ref.empty() || !instruct.empty() || !instruct_tokens.empty() || !continue_codes.empty() || stream_chunk > 0 || (!ref_tokens.empty() && tokens.empty()))) {
-        fprintf(stderr, "Error: --ref-text / --ref-tokens go with --ref (without --instruct, --continue-codes, --stream-chunk; --ref-tokens with --tokens)\n");
+    if (icl && (ref.empty() || !instruct.empty() || !instruct_tokens.empty() || !continue_codes.empty() || (!ref_tokens.empty() && tokens.empty()))) {
+        fprintf(stderr, "Error: --ref-text / --ref-tokens go with --ref (without --instruct, --continue-codes; --ref-tokens with --tokens)\n");
         return 1;
     }
     if (model.empty() || (!have_prompt && tokens.empty())) {
@@ -177,8 +178,8 @@ int main(int argc, char** argv) {
     std::vector<int64_t> prefix;
     size_t prefix_groups = 0;
     if (!save_codes.empty() || !continue_codes.empty()) {
-        if (tokens.empty() || (!ref.empty() && !icl) || !instruct.empty() || !instruct_tokens.empty() || (stream_chunk > 0 && !continue_codes.empty())) {
-            fprintf(stderr, "Error: --save-codes / --continue-codes go with --tokens (without --instruct, and without --ref unless --ref-text / --ref-tokens make it an in-context clone; --continue-codes without --stream-chunk)\n");
+        if (tokens.empty() || (!ref.empty() && !icl) || !instruct.empty() || !instruct_tokens.empty()) {
+            fprintf(stderr, "Error: --save-codes / --continue-codes go with --tokens (without --instruct, and without --ref unless --ref-text / --ref-tokens make it an in-context clone)\n");
             return 1;
         }
         if (!continue_codes.empty()) {
@@ -220,7 +221,21 @@ int main(int argc, char** argv) {
         if (rids.empty()) { fprintf(stderr, "Error: the reference text has no tokens (--ref-text needs vocab.json + merges.txt)\n"); return 1; }
         if (ids.empty() && !frame_prompt(engine, prompt, ids)) return 1;   // -p: the framing of --tokens around the tokenised text
         std::vector<int64_t> all;
-        audio = engine.synthesize_clone_icl(ids, rids, ref, lang_of(lang), sp, &all);
+        if (stream_chunk > 0) {   // the same clone delivered in chunks: encode, frame the ids as synthesize_clone_icl does, continue behind the codes
+            const std::vector<int64_t> ref_codes = engine.encode_audio(ref);
+            if (ref_codes.empty() || ids.size() < 3) { fprintf(stderr, "Error: synthesis failed\n"); return 1; }
+            std::vector<int64_t> tids(ids.begin(), ids.begin() + 3);
+            tids.insert(tids.end(), rids.begin(), rids.end());
+            tids.insert(tids.end(), ids.begin() + 3, ids.end());
+            size_t chunks = 0;
+            const int nf = engine.synthesize_tokens_continue_streaming(tids, ref_codes, lang_of(lang), sp, stream_chunk, [&](const float* p, size_t n, bool) {
+                if (n > 0 && chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / config::SAMPLE_RATE);
+                audio.insert(audio.end(), p, p + n);
+                return false;
+            }, &all);
+            if (nf < 0) audio.clear();
+            else printf("Streamed %d new frames in %zu chunks\n", nf - (int)(ref_codes.size() / (size_t)engine.n_groups()), chunks);
+        } else audio = engine.synthesize_clone_icl(ids, rids, ref, lang_of(lang), sp, &all);
         const size_t G = (size_t)engine.n_groups();
         if (!audio.empty()) printf("In-context clone: %zu reference text tokens, %zu frames in all\n", rids.size(), all.size() / G);
         if (!audio.empty() && !save_codes.empty()) {
@@ -248,6 +263,25 @@ int main(int argc, char** argv) {
         else audio = engine.synthesize_tokens_clone(ids, spk, lang_of(lang), sp);
     } else if (!ref.empty()) {
         audio = engine.synthesize_clone(prompt, ref, lang_of(lang), sp);
+    } else if (stream_chunk > 0 && !continue_codes.empty()) {   // behind recorded frames, the new audio in chunks
+        if (!prefix.empty() && prefix_groups != (size_t)engine.n_groups()) {
+            fprintf(stderr, "Error: %s has %zu codes per frame, the model has %d\n", continue_codes.c_str(), prefix_groups, engine.n_groups());
+            return 1;
+        }
+        std::vector<int64_t> all;
+        size_t chunks = 0;
+        const size_t G = (size_t)engine.n_groups();
+        const int nf = engine.synthesize_tokens_continue_streaming(ids, prefix, lang_of(lang), sp, stream_chunk, [&](const float* p, size_t n, bool) {
+            if (n > 0 && chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / config::SAMPLE_RATE);
+            audio.insert(audio.end(), p, p + n);
+            return false;
+        }, &all);
+        if (nf < 0) audio.clear();
+        else printf("Frames: %zu recorded + %zu new, streamed in %zu chunks\n", prefix.size() / G, all.size() / G - prefix.size() / G, chunks);
+        if (!audio.empty() && !save_codes.empty()) {
+            if (!write_codes_file(save_codes, all, G)) { fprintf(stderr, "Error: failed to write %s\n", save_codes.c_str()); return 1; }
+            printf("Codes saved to: %s\n", save_codes.c_str());
+        }
     } else if (stream_chunk > 0 && (feed > 0 || !save_codes.empty())) {
         // the batch scheduler's delivery for one utterance; --feed: its ids reach the engine K at a time, one piece per poll (live text)
         if (ids.empty() && !frame_prompt(engine, prompt, ids)) return 1;   // -p: the framing of --tokens around the tokenised text

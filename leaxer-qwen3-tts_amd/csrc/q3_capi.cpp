@@ -323,6 +323,24 @@ int q3tts_slots_codec_decode_new_host(q3tts_engine* h, int n_slots, const int32_
     return 0;
     Q3_API_END(h)
 }
+int q3tts_codec_stream_prime_batch_host(q3tts_engine* h, int n_streams, const int32_t* stream_ids, const int64_t* codes, const int32_t* frame_offsets) {
+    Q3_API_BEGIN(h)
+    h->e->codec_stream_prime_batch_host(n_streams, stream_ids, codes, frame_offsets);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_slots_codec_prime(q3tts_engine* h, int n_slots, const int32_t* slots, const int32_t* n_frames) {
+    Q3_API_BEGIN(h)
+    h->e->slots_codec_prime(n_slots, slots, n_frames);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_codec_stream_info(q3tts_engine* h, int stream_id, int* n_done, int* kv_capacity_rows, int64_t* bytes) {
+    Q3_API_BEGIN(h)
+    h->e->codec_stream_info(stream_id, n_done, kv_capacity_rows, bytes);
+    return 0;
+    Q3_API_END(h)
+}
 int q3tts_slot_codec_decode_range_host(q3tts_engine* h, int slot, int frame_begin, int frame_end, int left_context, float* pcm, int64_t cap,
                                        int64_t* out_len) {
     Q3_API_BEGIN(h)
@@ -632,7 +650,8 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                   int chunk_frames, q3tts_audio_cb cb, void* user, const int64_t* instruct_ids, const int32_t* instruct_offsets,
-                                  const int32_t* prefix_ids = nullptr, q3tts_text_cb tcb = nullptr, void* tuser = nullptr);
+                                  const int32_t* prefix_ids = nullptr, q3tts_text_cb tcb = nullptr, void* tuser = nullptr,
+                                  const int64_t* prefix_codes = nullptr, const int32_t* prefix_offsets = nullptr);
 static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                     const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                     float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
@@ -886,6 +905,15 @@ int q3tts_synthesize_stream_host(q3tts_engine* h, int n_utt, const int64_t* ids,
     return synthesize_stream_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
                                   chunk_frames, cb, user, nullptr, nullptr);
 }
+// The same loop behind teacher-forced frames (include/q3tts.h; tts_onnx.cpp:824-842, :759-776): forced begins, primed vocoder streams
+int q3tts_synthesize_continue_stream_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                          const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                          float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                                          const int64_t* prefix_codes, const int32_t* prefix_offsets,
+                                          int chunk_frames, q3tts_audio_cb cb, void* user) {
+    return synthesize_stream_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
+                                  chunk_frames, cb, user, nullptr, nullptr, nullptr, nullptr, nullptr, prefix_codes, prefix_offsets);
+}
 // The same loop with the texts pulled through a callback while the audio is generated (include/q3tts.h; tts_onnx.cpp:531-536, :833-842)
 int q3tts_synthesize_live_host(q3tts_engine* h, int n_utt, q3tts_text_cb text_cb, void* text_user, int lang,
                                const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
@@ -899,7 +927,8 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                   int chunk_frames, q3tts_audio_cb cb, void* user, const int64_t* instruct_ids, const int32_t* instruct_offsets,
-                                  const int32_t* prefix_ids, q3tts_text_cb tcb, void* tuser) {
+                                  const int32_t* prefix_ids, q3tts_text_cb tcb, void* tuser,
+                                  const int64_t* prefix_codes, const int32_t* prefix_offsets) {
     Q3_API_BEGIN(h)
     Engine& e = *h->e;
     const int H = e.c.hidden, G = e.c.n_groups, B = e.B;
@@ -912,6 +941,20 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     (void)Engine::checked_penalty(*p);
     PrefixHold hold(e, prefix_ids, n_utt);
     auto pl = [&](int u) { return prefix_ids && prefix_ids[u] != -1 ? e.prefix_get(prefix_ids[u]).P : 0; };   // rows of utterance u's shared prefix
+    // teacher-forced frames per utterance (q3tts_synthesize_continue_stream_host), checked as the schedule entry checks them: pf(u) of
+    // them behind utterance u's prompt, P the longest
+    if (prefix_codes && !prefix_offsets) throw q3::Error("synthesize: prefix_codes without prefix_offsets");
+    if (prefix_codes && live_text) throw q3::Error("synthesize_live: live text behind prefix codes is not implemented");
+    auto pf = [&](int u) { return prefix_codes ? (int)(prefix_offsets[u + 1] - prefix_offsets[u]) : 0; };
+    auto pcodes = [&](int u) { return prefix_codes + (size_t)prefix_offsets[u] * (size_t)G; };
+    int P = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        if (pf(u) < 0 || (prefix_codes && prefix_offsets[u] < 0)) throw q3::Error("synthesize: prefix_offsets must start at >= 0 and not decrease");
+        if (pf(u) > 0 && pf(u) + p->max_new_tokens > e.max_frames_cap) throw q3::Error("synthesize: utterance " + std::to_string(u) + ": prefix frames + max_new_tokens exceeds the slot's frame capacity");
+        try { if (pf(u) > 0) e.check_frame_codes(pcodes(u), pf(u), true); }
+        catch (const q3::Error& ex) { throw q3::Error("synthesize: utterance " + std::to_string(u) + ": " + ex.msg); }
+        P = std::max(P, pf(u));
+    }
     for (int b = 0; b < B; ++b) e.slot_release(b);
     std::vector<Prep> prep;
     std::vector<float> prompts, trailing;
@@ -933,9 +976,11 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     auto cap_of = [&](int u) { return max_new_per_utt ? std::min(std::max(1, (int)max_new_per_utt[u]), p->max_new_tokens) : p->max_new_tokens; };
     std::deque<int> pending;
     for (int u = 0; u < n_utt; ++u) {
+        if (pf(u) > 0 && pl(u) + prep[(size_t)u].S + pf(u) + p->max_new_tokens > e.max_ctx)
+            throw q3::Error("synthesize: utterance " + std::to_string(u) + ": prefix + prompt + prefix frames + max_new_tokens exceeds max_ctx");
         if (pl(u) > 0 && pl(u) + prep[(size_t)u].S + p->max_new_tokens > e.max_ctx)
             throw q3::Error("synthesize: utterance " + std::to_string(u) + ": prefix + prompt + max_new_tokens exceeds max_ctx");
-        if (e.kv_pages_for(pl(u) + prep[(size_t)u].S + cap_of(u)) > e.kv_total_pages())
+        if (e.kv_pages_for(pl(u) + prep[(size_t)u].S + pf(u) + cap_of(u)) > e.kv_total_pages())
             throw q3::Error("synthesize: one utterance (prompt + max_new_tokens) needs more KV pages than the pool holds");
         pending.push_back(u);
         if (pcm_len) pcm_len[u] = 0;
@@ -998,7 +1043,7 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
             if (fin) {   // retired before the callback: whatever it does, the slot is free and the outputs are complete
                 if (n_frames) n_frames[u] = s.n_frames;
                 if (pcm_len) pcm_len[u] = written[(size_t)u];
-                if (codes_out) e.slot_codes(b, codes_out + (size_t)u * p->max_new_tokens * G, p->max_new_tokens);
+                if (codes_out) e.slot_codes(b, codes_out + (size_t)u * (size_t)(P + p->max_new_tokens) * G, P + p->max_new_tokens);
                 e.slot_release(b);
                 slot_utt[(size_t)b] = -1;
                 deliv[(size_t)b] = 0;
@@ -1037,7 +1082,7 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
             {   // admission in queue order, every utterance with the pages of its whole length
                 std::vector<int> free_slots, need;
                 for (int b = 0; b < B; ++b) if (slot_utt[(size_t)b] < 0) free_slots.push_back(b);
-                for (size_t i = 0; i < n_ready && i < free_slots.size(); ++i) need.push_back(e.kv_pages_for(pl(pending[i]) + prep[(size_t)pending[i]].S + cap_of(pending[i])));
+                for (size_t i = 0; i < n_ready && i < free_slots.size(); ++i) need.push_back(e.kv_pages_for(pl(pending[i]) + prep[(size_t)pending[i]].S + pf(pending[i]) + cap_of(pending[i])));
                 const int n_adm = q3::sched_admit_count(e.kv, need, (int)free_slots.size(), live, true);
                 for (int i = 0; i < n_adm; ++i) { slot_utt[(size_t)free_slots[(size_t)i]] = pending.front(); pending.pop_front(); fresh.push_back(free_slots[(size_t)i]); }
             }
@@ -1066,17 +1111,30 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
                     q.max_frames = max_new_per_utt ? std::max(1, (int)max_new_per_utt[u]) : 0;
                     q.kv_tokens = 0;   // prompt + cap, reserved now
                     if (prefix_ids) q.prefix_id = prefix_ids[u];
+                    if (pf(u) > 0) { q.prefix = pcodes(u); q.n_prefix = pf(u); }
                 }
-                if (e.flags & Q3TTS_FLAG_RAGGED_PREFILL) {   // the long prompts of the look in one ragged begin, the rest as before
+                if (e.flags & Q3TTS_FLAG_RAGGED_PREFILL) {   // the long prompts and the forced begins of the look in one ragged begin, the rest as before
                     std::vector<Engine::SlotInit> rag;
                     size_t keep = 0;
-                    for (size_t i = 0; i < init.size(); ++i) { if (init[i].S > 16) rag.push_back(init[i]); else init[keep++] = init[i]; }
+                    for (size_t i = 0; i < init.size(); ++i) { if (init[i].S > 16 || init[i].n_prefix > 0) rag.push_back(init[i]); else init[keep++] = init[i]; }
                     init.resize(keep);
                     if (!rag.empty()) e.slots_begin_ragged(rag.data(), (int)rag.size(), *p, seed, ignore_eos);
+                } else if (P > 0) {                          // forced begins, each on its own: the schedule entry's (q3tts_synthesize_continue_host)
+                    size_t keep = 0;
+                    for (size_t i = 0; i < init.size(); ++i) {
+                        if (init[i].n_prefix > 0) e.slots_begin(&init[i], 1, *p, seed, ignore_eos);
+                        else init[keep++] = init[i];
+                    }
+                    init.resize(keep);
                 }
                 if (init.empty()) { }
                 else if (prefix_ids) e.slots_begin_prefixed(init.data(), (int)init.size(), *p, seed, ignore_eos);
                 else e.slots_begin(init.data(), (int)init.size(), *p, seed, ignore_eos);
+                if (P > 0) {   // the vocoder streams of the look's prefixed slots take their prefixes as history, in one call: audio starts at the first new frame
+                    std::vector<int32_t> ps_slots, ps_n;
+                    for (int b : fresh) if (pf(slot_utt[(size_t)b]) > 0) { ps_slots.push_back(b); ps_n.push_back(pf(slot_utt[(size_t)b])); }
+                    if (!ps_slots.empty()) e.slots_codec_prime((int)ps_slots.size(), ps_slots.data(), ps_n.data());
+                }
                 live += (int)fresh.size();
                 e.sched_admitted += (int64_t)fresh.size();
                 e.sched_peak_live = std::max(e.sched_peak_live, live);

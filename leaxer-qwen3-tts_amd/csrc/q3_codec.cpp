@@ -1149,6 +1149,222 @@ void Engine::slots_codec_decode_new(int n_slots, const int32_t* slots, float* co
     if (pcm_len) for (int i = 0; i < n_slots; ++i) pcm_len[i] = ps[(size_t)i].n_own;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Priming: g open streams that hold no frames yet are put into the state a push of their first n frames would leave, without the audio.
+// A stream needs very little of its past: the last window - 1 rotated K / V rows of every pre-transformer layer (all a later query can
+// reach) and the last codec_stage_b_context() output rows (all the stages behind the transformer look back).  So only the
+// pre-transformer runs, in codec_pre_batch's whole-utterance layout — rows [stream][Fp], Fp the longest n, shorter ones padded with zero
+// rows (causal attention: padding never reaches a real row), scratch K / V [stream][head][Ps][d] per layer, every linear layer one
+// GEMM over all rows, attention with the stream as its batch dimension: the launch count does not depend on g — and two copy kernels
+// move the tails to the front of the streams' own buffers (k_prime_kv_tails after each layer's RoPE + store, k_prime_row_tails after the
+// final norm), found through a descriptor table uploaded once.  The conv decoder and the upsampling stages do not run, and the streams'
+// buffers keep the size codec_stream_begin gave them (a push of n frames grows them to hold n more rows, for good).
+// Workspace: the batched push's arena and descriptor table (engine stream only, like the push).
+// ------------------------------------------------------------------------------------------------
+void Engine::codec_stream_prime_batch(const StreamPush* ps, int g_all) {
+    if (!codec) throw Error("codec decoder not finalized");
+    CodecW& W = *codec;
+    const int CH = c.cd_hidden, NH = c.cd_heads, HD = c.cd_head_dim, FF = c.cd_ffn;
+    if (NH * HD != CH) throw Error("codec: heads*head_dim must equal hidden");
+    if (g_all < 0) throw Error("codec_stream_prime_batch: negative stream count");
+    const int keep = std::max(c.cd_window - 1, 0), ctxB = codec_stage_b_context();
+    // ---- every argument is checked before anything moves ----
+    std::vector<int> live;
+    int Fp = 0;
+    for (int i = 0; i < g_all; ++i) {
+        const StreamPush& q = ps[i];
+        if (q.sid < 0 || q.sid >= (int)W.streams.size() || !W.streams[(size_t)q.sid].used) throw Error("codec_stream_prime_batch: no such stream");
+        for (int k = 0; k < i; ++k) if (ps[k].sid == q.sid) throw Error("codec_stream_prime_batch: stream listed twice");
+        const CodecW::Stream& S = W.streams[(size_t)q.sid];
+        if (S.n_done != 0) throw Error("codec_stream_prime_batch: stream already has frames");
+        if (q.n < 0) throw Error("codec_stream_prime_batch: negative frame count");
+        if (q.n > S.cap) throw Error("codec_stream_prime_batch: more frames than the stream was opened for");
+        if (q.n > 0 && !q.codes_dev) throw Error("codec_stream_prime_batch: null codes");
+        // the tails land at the front of what codec_stream_begin allocated: they must fit it as it is
+        if (q.n > 0 && (!S.kv || !S.hpost || std::min(q.n, keep) > S.P || std::min(q.n, ctxB) > S.h_cap)) throw Error("codec_stream_prime_batch: the stream's buffers do not hold the kept rows");
+        if (q.n > 0) { live.push_back(i); Fp = std::max(Fp, q.n); }
+    }
+    const int g = (int)live.size();
+    if (g == 0) return;
+    if (g > 65535) throw Error("codec_stream_prime_batch: at most 65535 streams per call");
+    if ((int64_t)g * Fp > (int64_t)1 << 24) throw Error("codec_stream_prime_batch: more than 2^24 padded rows in one call");
+    int Ps = 1, pshift = 0;
+    while (Ps < Fp) { Ps <<= 1; ++pshift; }
+    codec_rope_tables(Ps);   // positions [0, Fp): the padded length
+    std::vector<CodecStreamDesc>& D = W.sbatch_desc_h;
+    D.assign((size_t)g, CodecStreamDesc());
+    for (int i = 0; i < g; ++i) {
+        const StreamPush& q = ps[live[(size_t)i]];
+        const CodecW::Stream& S = W.streams[(size_t)q.sid];
+        CodecStreamDesc& d = D[(size_t)i];
+        d.kv = S.kv; d.hpost = S.hpost; d.codes = q.codes_dev; d.P = S.P; d.k0 = 0; d.h0 = 0; d.a0 = 0; d.n = q.n; d.row_off = i * Fp;
+        d.ctx = std::min(q.n, ctxB); d.blk = i;
+    }
+    // ---- workspace ----
+    const size_t rows = (size_t)g * Fp;
+    const int T = (int)rows;
+    auto bytes_of = [](size_t nfloat) { return (nfloat * sizeof(float) + 255) & ~(size_t)255; };
+    const size_t kslab_floats = (size_t)32 * 128 * 4096;
+    const size_t need = bytes_of(rows * CH) * 3 + bytes_of(rows * 3 * CH) + bytes_of(rows * FF) * 2 + bytes_of((size_t)g * NH * Ps * HD) * 2 + bytes_of(kslab_floats);
+    if (W.sbatch_arena_bytes < need) {
+        sync();
+        if (W.sbatch_arena) (void)hipFree(W.sbatch_arena);
+        W.sbatch_arena = nullptr; W.sbatch_arena_bytes = 0;
+        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_arena, need));
+        W.sbatch_arena_bytes = need;
+    }
+    if (W.sbatch_desc_n < (size_t)g) {
+        sync();
+        if (W.sbatch_desc) (void)hipFree(W.sbatch_desc);
+        W.sbatch_desc = nullptr; W.sbatch_desc_n = 0;
+        const size_t cap = std::max((size_t)64, (size_t)g);
+        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_desc, cap * sizeof(CodecStreamDesc)));
+        W.sbatch_desc_n = cap;
+    }
+    if (W.batch_pages_n < g) {   // identity page table, one scratch cache block per stream (codec_pre_batch's; [n_cap, 2 n_cap) is its perm area)
+        sync();
+        if (W.batch_pages) (void)hipFree(W.batch_pages);
+        W.batch_pages = nullptr; W.batch_pages_n = 0;
+        std::vector<int> idt((size_t)g);
+        for (int i = 0; i < g; ++i) idt[(size_t)i] = i;
+        Q3_HIP_CHECK(hipMalloc((void**)&W.batch_pages, (size_t)2 * g * sizeof(int)));
+        Q3_HIP_CHECK(hipMemcpy(W.batch_pages, idt.data(), (size_t)g * sizeof(int), hipMemcpyHostToDevice));
+        W.batch_pages_n = g;
+    }
+    Q3_HIP_CHECK(hipMemcpyAsync(W.sbatch_desc, D.data(), (size_t)g * sizeof(CodecStreamDesc), hipMemcpyHostToDevice, stream));
+    size_t off = 0;
+    auto take = [&](size_t nfloat) { float* p = (float*)(W.sbatch_arena + off); off += bytes_of(nfloat); return p; };
+    float* h = take(rows * CH);
+    float* hn = take(rows * CH);
+    float* att = take(rows * CH);
+    float* qkvb = take(rows * 3 * CH);
+    float* ub = take(rows * FF);
+    float* gb = take(rows * FF);
+    float* kc = take((size_t)g * NH * Ps * HD);
+    float* vc = take((size_t)g * NH * Ps * HD);
+    float* kslab = take(kslab_floats);
+    auto conv = [&](ConvArgs a) {
+        a.slab = kslab; a.slab_floats = kslab_floats;
+        const auto it = W.planes.find(a.W);
+        if (it != W.planes.end()) { a.Wh = it->second.hi; a.Wl = it->second.lo; a.Whc = it->second.cm; a.w_scale_inv = it->second.scale_inv; a.w_lo_zero = it->second.lo_zero; }
+        launch_conv(a, stream);
+    };
+    auto gemm = [&](const float* in, int Cin, const float* Wm, int Cout, float* out) {
+        ConvArgs a; a.in = in; a.T_in = T; a.C_in = Cin; a.out = out; a.T_out = T; a.C_out = Cout; a.W = Wm;
+        return a;
+    };
+    Q3_HIP_CHECK(hipEventRecord(ev0, stream));
+    const CodecStreamDesc* dd = W.sbatch_desc;
+    Q3_HIP_CHECK(hipMemsetAsync(h, 0, rows * CH * sizeof(float), stream));   // padding rows: zeros through every layer
+    launch_code_embed_mean_streams(W.code_embed, dd, g, Fp, c.n_groups, c.cd_codebook, CH, h, stream);
+    for (int l = 0; l < c.cd_layers; ++l) {
+        const CodecW::Layer& L = W.layers[l];
+        launch_rmsnorm_rows(h, L.in_norm, c.cd_rms_eps, T, CH, hn, stream);
+        conv(gemm(hn, CH, L.qkv, 3 * CH, qkvb));
+        launch_rope_store(qkvb, 3 * CH, Fp, NH, NH, HD, W.rope_cos, W.rope_sin, kc, vc, Ps, stream, g);
+        launch_prime_kv_tails(kc, vc, Ps, dd, g, l, NH, HD, keep, stream);
+        AttnArgs a;
+        a.qkv = qkvb; a.ld_qkv = 3 * CH; a.out = att; a.ld_out = CH; a.kcache = kc; a.vcache = vc;
+        a.page_table = W.batch_pages; a.pages_per_slot = 1; a.page_shift = pshift; a.layer = 0; a.n_layers = 1;
+        a.pos_scalar = 0; a.slot_offset = 0; a.nb = g; a.n_new = Fp; a.nq = NH; a.nkv = NH; a.d = HD;
+        a.scale = 1.0f / sqrtf((float)HD); a.window = c.cd_window; a.new_from_raw = 0;
+        launch_attn(a, stream);
+        { ConvArgs x = gemm(att, CH, L.o, CH, h); x.res_scale = L.attn_scale; x.res = h; conv(x); }
+        launch_rmsnorm_rows(h, L.post_norm, c.cd_rms_eps, T, CH, hn, stream);
+        conv(gemm(hn, CH, L.up, FF, ub));
+        { ConvArgs x = gemm(hn, CH, L.gate, FF, gb); x.act = 2; x.mul = ub; conv(x); }
+        { ConvArgs x = gemm(gb, FF, L.down, CH, h); x.res_scale = L.mlp_scale; x.res = h; conv(x); }
+    }
+    launch_rmsnorm_rows(h, W.norm, c.cd_rms_eps, T, CH, hn, stream);
+    launch_prime_row_tails(hn, dd, g, CH, ctxB, stream);
+    Q3_HIP_CHECK(hipEventRecord(ev1, stream));
+    sync();
+    Q3_HIP_CHECK(hipEventElapsedTime(&last_codec_ms, ev0, ev1));
+    for (int i = 0; i < g; ++i) {   // the streams advance only now: a failure above leaves every one of them where it was
+        const CodecStreamDesc& d = D[(size_t)i];
+        CodecW::Stream& S = W.streams[(size_t)ps[live[(size_t)i]].sid];
+        S.n_done = d.n; S.kv_rows = std::min(d.n, keep); S.h_rows = d.ctx;
+    }
+}
+
+// host codes: stream s is primed with frames codes[frame_offsets[s] .. frame_offsets[s + 1]); validated as a whole before anything moves
+void Engine::codec_stream_prime_batch_host(int n_streams, const int32_t* sids, const int64_t* codes, const int32_t* frame_offsets) {
+    if (!codec) throw Error("codec decoder not finalized");
+    if (n_streams < 0) throw Error("codec_stream_prime_batch: negative stream count");
+    if (n_streams == 0) return;
+    if (!sids || !frame_offsets) throw Error("codec_stream_prime_batch: null argument");
+    CodecW& W = *codec;
+    const int G = c.n_groups;
+    if (frame_offsets[0] != 0) throw Error("codec_stream_prime_batch: frame_offsets must start at 0");
+    for (int i = 0; i < n_streams; ++i)
+        if (frame_offsets[i + 1] < frame_offsets[i]) throw Error("codec_stream_prime_batch: frame_offsets must not decrease");
+    const size_t total = (size_t)frame_offsets[n_streams] * G;
+    if (total > 0 && !codes) throw Error("codec_stream_prime_batch: null codes");
+    std::vector<int32_t> tmp(total);
+    for (size_t i = 0; i < total; ++i) {
+        if (codes[i] < 0 || codes[i] >= c.cd_codebook) throw Error("codec_decode: code out of range");
+        tmp[i] = (int32_t)codes[i];
+    }
+    std::vector<StreamPush> ps((size_t)n_streams);
+    for (int i = 0; i < n_streams; ++i) {   // the checks codec_stream_prime_batch repeats, made here before the staging buffer may grow
+        ps[(size_t)i].sid = sids[i]; ps[(size_t)i].n = frame_offsets[i + 1] - frame_offsets[i];
+        if (sids[i] < 0 || sids[i] >= (int)W.streams.size() || !W.streams[(size_t)sids[i]].used) throw Error("codec_stream_prime_batch: no such stream");
+        for (int k = 0; k < i; ++k) if (sids[k] == sids[i]) throw Error("codec_stream_prime_batch: stream listed twice");
+        if (W.streams[(size_t)sids[i]].n_done != 0) throw Error("codec_stream_prime_batch: stream already has frames");
+        if (ps[(size_t)i].n > W.streams[(size_t)sids[i]].cap) throw Error("codec_stream_prime_batch: more frames than the stream was opened for");
+    }
+    if (W.sbatch_codes_n < total) {
+        sync();
+        if (W.sbatch_codes) (void)hipFree(W.sbatch_codes);
+        W.sbatch_codes = nullptr; W.sbatch_codes_n = 0;
+        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_codes, total * sizeof(int32_t)));
+        W.sbatch_codes_n = total;
+    }
+    if (total > 0) Q3_HIP_CHECK(hipMemcpyAsync(W.sbatch_codes, tmp.data(), total * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    for (int i = 0; i < n_streams; ++i) ps[(size_t)i].codes_dev = W.sbatch_codes + (size_t)frame_offsets[i] * G;
+    try { codec_stream_prime_batch(ps.data(), n_streams); } catch (...) { try { sync(); } catch (...) { } throw; }   // tmp must outlive the upload
+    sync();
+}
+
+// The listed slots' implicit streams are restarted and primed with the slots' first n_frames[i] frames, read where the sampler (or the
+// forced begin) wrote them: slots_codec_decode_new then starts at frame n_frames[i] with those frames as history.
+void Engine::slots_codec_prime(int n_slots, const int32_t* slots, const int32_t* n_frames) {
+    if (!codec) throw Error("codec decoder not finalized");
+    if (n_slots < 0) throw Error("slots_codec_prime: negative slot count");
+    if (n_slots == 0) return;
+    if (!slots || !n_frames) throw Error("slots_codec_prime: null argument");
+    CodecW& W = *codec;
+    std::vector<SlotState> st;
+    slots_state(B, st);
+    for (int i = 0; i < n_slots; ++i) {
+        if (slots[i] < 0 || slots[i] >= B) throw Error("slot out of range");
+        for (int k = 0; k < i; ++k) if (slots[k] == slots[i]) throw Error("slots_codec_prime: slot listed twice");
+        const SlotState& s = st[(size_t)slots[i]];
+        const int have = s.active ? std::min(s.n_frames, max_frames_cap) : 0;
+        if (n_frames[i] < 0 || n_frames[i] > have) throw Error("slots_codec_prime: slot " + std::to_string(slots[i]) + ": more frames than the slot holds");
+    }
+    if ((int)W.slot_stream.size() < B) W.slot_stream.assign((size_t)B, -1);
+    std::vector<StreamPush> ps((size_t)n_slots);
+    for (int i = 0; i < n_slots; ++i) {
+        const int slot = slots[i];
+        int sid = W.slot_stream[(size_t)slot];
+        if (sid >= 0 && W.streams[(size_t)sid].used) codec_stream_end(sid);
+        sid = codec_stream_begin(max_frames_cap);
+        W.slot_stream[(size_t)slot] = sid;
+        ps[(size_t)i].sid = sid; ps[(size_t)i].n = n_frames[i];
+        ps[(size_t)i].codes_dev = codes_d + (size_t)slot * max_frames_cap * c.n_groups;
+    }
+    codec_stream_prime_batch(ps.data(), n_slots);
+}
+
+void Engine::codec_stream_info(int sid, int* n_done, int* kv_capacity_rows, int64_t* bytes) const {
+    if (!codec || sid < 0 || sid >= (int)codec->streams.size() || !codec->streams[(size_t)sid].used) throw Error("codec_stream: no such stream");
+    const CodecW::Stream& S = codec->streams[(size_t)sid];
+    if (n_done) *n_done = S.n_done;
+    if (kv_capacity_rows) *kv_capacity_rows = S.P;
+    if (bytes) *bytes = (int64_t)((size_t)c.cd_layers * 2 * c.cd_heads * S.P * c.cd_head_dim * sizeof(float) + (size_t)S.h_cap * c.cd_hidden * sizeof(float));
+}
+
 // the implicit stream behind q3tts_slot_codec_decode_range_host: consecutive exact ranges of a slot ([0, b1), [b1, b2), ...) are pushes
 int64_t Engine::slot_codec_stream_range(int slot, int a, int b, float* pcm, int64_t cap) {
     CodecW& W = *codec;

@@ -1490,4 +1490,37 @@ void launch_gather_stream_rows(const CodecStreamDesc* descs, int g, int Tw, int 
     if (g > 0 && Tw > 0) hipLaunchKernelGGL(k_gather_stream_rows, dim3(Tw, g), dim3(256), 0, s, descs, Tw, C, out);
 }
 
+// ---- priming: the mirror of the two stores above (k_rope_store_streams, k_rmsnorm_rows_streams) for rows that were computed in the
+// whole-utterance layout.  A stream keeps the newest `keep` K / V rows of a layer and the newest `ctx` output rows; here they go to the
+// FRONT of its buffers.  The rows of one (stream, k | v, head) are one contiguous run on both sides (r * d floats), copied as float4
+// (d % 4 == 0 and the scratch blocks' 256-byte alignment: the launcher's checks).  Nothing of a stream's buffer is read.
+// grid (2 * nkv, streams): block x = (k | v, head)
+__global__ __launch_bounds__(256) void k_prime_kv_tails(const float* kc0, const float* vc0, int Ps, const CodecStreamDesc* descs, int layer, int nkv, int d, int keep) {
+    const CodecStreamDesc S = descs[blockIdx.y];
+    const int r = S.n < keep ? S.n : keep;
+    if (r <= 0) return;
+    const int isv = (int)blockIdx.x / nkv, kh = (int)blockIdx.x % nkv;
+    const float4* src = (const float4*)((isv ? vc0 : kc0) + (((size_t)S.blk * nkv + kh) * Ps + (size_t)(S.n - r)) * d);
+    float4* dst = (float4*)(S.kv + (((size_t)layer * 2 + isv) * nkv + kh) * (size_t)S.P * d);
+    const int n4 = r * d / 4;
+    for (int i = threadIdx.x; i < n4; i += 256) dst[i] = src[i];
+}
+void launch_prime_kv_tails(const float* kc, const float* vc, int Ps, const CodecStreamDesc* descs, int g, int layer, int nkv, int d, int keep, hipStream_t s) {
+    if (d % 4 || g > 65535) throw Error("prime (K / V tails): head_dim must be a multiple of 4, at most 65535 streams");
+    if (g > 0 && keep > 0 && nkv > 0) hipLaunchKernelGGL(k_prime_kv_tails, dim3(2 * nkv, g), dim3(256), 0, s, kc, vc, Ps, descs, layer, nkv, d, keep);
+}
+// grid (ctx, streams): block x = kept row t, source row row_off + n - m + t with m = min(n, ctx)
+__global__ __launch_bounds__(256) void k_prime_row_tails(const float* h, const CodecStreamDesc* descs, int C, int ctx) {
+    const CodecStreamDesc S = descs[blockIdx.y];
+    const int m = S.n < ctx ? S.n : ctx, t = blockIdx.x;
+    if (t >= m) return;
+    const float4* src = (const float4*)(h + (size_t)(S.row_off + S.n - m + t) * C);
+    float4* dst = (float4*)(S.hpost + (size_t)t * C);
+    for (int i = threadIdx.x; i < C / 4; i += 256) dst[i] = src[i];
+}
+void launch_prime_row_tails(const float* h, const CodecStreamDesc* descs, int g, int C, int ctx, hipStream_t s) {
+    if (C % 4 || g > 65535) throw Error("prime (row tails): hidden must be a multiple of 4, at most 65535 streams");
+    if (g > 0 && ctx > 0) hipLaunchKernelGGL(k_prime_row_tails, dim3(ctx, g), dim3(256), 0, s, h, descs, C, ctx);
+}
+
 } // namespace q3

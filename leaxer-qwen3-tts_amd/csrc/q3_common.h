@@ -418,6 +418,12 @@ bool attn_streams_windowed(int heads, int d, int window, int ld_qkv, int ld_out)
 void launch_rmsnorm_rows_streams(const float* x, const float* w, float eps, const CodecStreamDesc* descs, int g, int n_max, int C, hipStream_t s);   // row -> hpost[h0 + t]
 // out [g][Tw][C]: sequence blk = the stream's hpost rows [h0 - ctx, h0 + n), zeros behind them
 void launch_gather_stream_rows(const CodecStreamDesc* descs, int g, int Tw, int C, float* out, hipStream_t s);
+// ---- priming (Engine::codec_stream_prime_batch): the tails a stream keeps, out of the whole-utterance layout into the streams' own buffers ----
+// The descriptors read here: kv, hpost, P (the stream's own), n (frames primed), row_off (first of its rows [stream][Fp]), blk (its scratch
+// K / V block).  Sources are the scratch K / V of one layer ([stream][head][Ps][d], after launch_rope_store) and the normalised output rows;
+// a stream's buffers are only written: rows [0, min(n, keep)) of layer `layer`'s K and V, rows [0, min(n, ctx)) of hpost.  n == 0: untouched.
+void launch_prime_kv_tails(const float* kc, const float* vc, int Ps, const CodecStreamDesc* descs, int g, int layer, int nkv, int d, int keep, hipStream_t s);
+void launch_prime_row_tails(const float* h, const CodecStreamDesc* descs, int g, int C, int ctx, hipStream_t s);
 
 
 // ---- speaker encoder + GPU audio front end of the clone path (q3_speaker_kernels.hip) ----

@@ -159,6 +159,12 @@ public:
                                       int64_t cap, int64_t* pcm_len);
     void slots_codec_decode_new(int n_slots, const int32_t* slots, float* const* pcm_out, int64_t cap, int64_t* pcm_len, int32_t* frame_begin, int32_t* frame_end,
                                 const int32_t* frame_limit = nullptr);   // frame_limit[i] (optional): decode slot i's frames below it only
+    // priming: g open streams without frames take the state a push of their first n frames would leave — pre-transformer only, the K / V
+    // and output-row tails copied into the streams' buffers, which keep the size codec_stream_begin gave them (StreamPush: sid, codes_dev, n)
+    void codec_stream_prime_batch(const StreamPush* ps, int g);
+    void codec_stream_prime_batch_host(int n_streams, const int32_t* sids, const int64_t* codes, const int32_t* frame_offsets);
+    void slots_codec_prime(int n_slots, const int32_t* slots, const int32_t* n_frames);
+    void codec_stream_info(int sid, int* n_done, int* kv_capacity_rows, int64_t* bytes) const;
     void slot_codec_stream_reset(int slot);
     void codec_rope_tables(int P);
 

@@ -239,6 +239,39 @@ std::vector<float> TTSEngine::synthesize_tokens_continue(const std::vector<int64
     return pcm;
 }
 
+int TTSEngine::synthesize_tokens_continue_streaming(const std::vector<int64_t>& token_ids, const std::vector<int64_t>& prefix_codes, Language lang,
+                                                    const SamplingParams& params, int chunk_frames,
+                                                    const std::function<bool(const float*, size_t, bool)>& on_audio, std::vector<int64_t>* all_codes) {
+    if (all_codes) all_codes->clear();
+    if (!ready_ || chunk_frames < 1 || !on_audio) return -1;
+    const size_t G = (size_t)n_groups_;
+    if (prefix_codes.size() % G != 0) {
+        std::cerr << "[TTSEngine] Synthesis error: prefix codes are not whole frames of " << G << " ids" << std::endl;
+        return -1;
+    }
+    const int F0 = (int)(prefix_codes.size() / G);
+    q3tts_sampling sp{ params.temperature, params.top_p, params.top_k, params.repetition_penalty, params.max_new_tokens };
+    sp.max_new_tokens = std::min(sp.max_new_tokens, max_ctx_ - F0 - 16);   // prompt rows: at most 16
+    if (sp.max_new_tokens < 1) {
+        std::cerr << "[TTSEngine] Synthesis error: the prefix does not fit the engine's context" << std::endl;
+        return -1;
+    }
+    const int32_t offs[2] = { 0, (int32_t)token_ids.size() }, poffs[2] = { 0, F0 };
+    std::vector<int64_t> codes((size_t)(F0 + sp.max_new_tokens) * G);
+    int32_t frames = 0;
+    struct Ctx { const std::function<bool(const float*, size_t, bool)>* f; } ctx{ &on_audio };
+    const q3tts_audio_cb cb = [](void* user, int, int, int, const float* pcm, int64_t n, int finished) -> int {
+        return (*static_cast<Ctx*>(user)->f)(pcm, (size_t)n, finished != 0) ? 1 : 0;
+    };
+    if (q3tts_synthesize_continue_stream_host(h_, 1, token_ids.data(), offs, lang_index(lang), nullptr, &sp, nullptr, seed_, 0, nullptr, 0, nullptr, &frames,
+                                              codes.data(), F0 > 0 ? prefix_codes.data() : nullptr, F0 > 0 ? poffs : nullptr, chunk_frames, cb, &ctx) != 0) {
+        std::cerr << "[TTSEngine] Synthesis error: " << q3tts_last_error(h_) << std::endl;
+        return -1;
+    }
+    if (all_codes) all_codes->assign(codes.begin(), codes.begin() + (size_t)frames * G);
+    return frames;
+}
+
 std::vector<float> TTSEngine::synthesize_speaker(const std::string& text, Speaker, Language lang, const SamplingParams& params) {
     std::cerr << "[TTSEngine] Preset speakers require CustomVoice model (not yet supported)" << std::endl; // :327
     return synthesize(text, lang, params);

@@ -131,6 +131,14 @@ public:
     std::vector<float> synthesize_tokens_continue(const std::vector<int64_t>& token_ids, const std::vector<int64_t>& prefix_codes,
                                                   Language lang = Language::Auto, const SamplingParams& params = SamplingParams(),
                                                   std::vector<int64_t>* all_codes = nullptr);
+    // The same with the new audio delivered while it is generated (include/q3tts.h: q3tts_synthesize_continue_stream_host; the shape of
+    // synthesize_tokens_batch_streaming for one utterance): every chunk_frames steps on_audio(pcm, n, finished) receives the samples of
+    // the new frames generated since the previous call — the prefix is history, never decoded to audio — the tail with finished = true,
+    // once and last; a true return cancels.  Returns the frames generated (prefix included), -1 on error.
+    int synthesize_tokens_continue_streaming(const std::vector<int64_t>& token_ids, const std::vector<int64_t>& prefix_codes, Language lang,
+                                             const SamplingParams& params, int chunk_frames,
+                                             const std::function<bool(const float*, size_t, bool)>& on_audio,
+                                             std::vector<int64_t>* all_codes = nullptr);
     // Audio -> codes (include/q3tts.h: q3tts_audio_encode_batch_host; [HINT] the 12 Hz tokenizer's encoder, beside the reference's
     // methods): mono samples at sample_rate -> frames of n_groups() ids, frame-major — what synthesize_tokens_continue takes.  Empty on error.
     std::vector<int64_t> encode_audio(const std::vector<float>& pcm, int sample_rate);

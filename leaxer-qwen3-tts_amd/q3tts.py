@@ -111,6 +111,7 @@ EXPORTS = [
     "q3tts_build_prompt_open_host", "q3tts_synthesize_live_host",
     "q3tts_config_enable_audio_encoder", "q3tts_has_audio_encoder", "q3tts_audio_encode_len", "q3tts_audio_encode_host",
     "q3tts_audio_encode_batch_host", "q3tts_audio_encode_latents_host", "q3tts_audio_encode_batch_latents_host", "q3tts_last_audio_encode_ms", "q3tts_test_audio_encoder_transformer_host",
+    "q3tts_codec_stream_prime_batch_host", "q3tts_slots_codec_prime", "q3tts_codec_stream_info", "q3tts_synthesize_continue_stream_host",
 ]
 
 # q3tts_audio_cb: int (*)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished)
@@ -169,6 +170,11 @@ def lib():
     L.q3tts_slot_begin_codes.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, C.POINTER(Sampling), C.c_uint64, C.c_uint32, i32]
     L.q3tts_frame_rows_host.argtypes = [vp, vp, i32, i32, vp, i32, vp]
     L.q3tts_synthesize_continue_host.argtypes = [vp, i32, vp, vp, i32, vp, C.POINTER(Sampling), vp, C.c_uint64, i32, vp, i64, vp, vp, vp, vp, vp]
+    L.q3tts_synthesize_continue_stream_host.argtypes = [vp, i32, vp, vp, i32, vp, C.POINTER(Sampling), vp, C.c_uint64, i32, vp, i64, vp, vp, vp, vp, vp,
+                                                        i32, AUDIO_CB, vp]
+    L.q3tts_codec_stream_prime_batch_host.argtypes = [vp, i32, vp, vp, vp]
+    L.q3tts_slots_codec_prime.argtypes = [vp, i32, vp, vp]
+    L.q3tts_codec_stream_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
     L.q3tts_prefix_create.argtypes = [vp, vp, i32, C.POINTER(i32)]
     L.q3tts_prefix_create_instruct.argtypes = [vp, vp, i32, C.POINTER(i32)]
     L.q3tts_prefix_info.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i64)]
@@ -500,6 +506,36 @@ class Engine:
         self.L.q3tts_codec_stream_push_batch_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         self._ck(self.L.q3tts_codec_stream_push_batch_host(self.h, n, _p(ids), _p(flat), _p(offs), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len)))
         return [pcm[i][: pcm_len[i]] for i in range(n)]
+
+    def codec_stream_prime_batch(self, sids, codes_list):
+        """open streams that hold no frames yet take the state a push of these frames would leave, without their audio
+        (q3tts_codec_stream_prime_batch_host): one [n_s][n_groups] code array per stream (n_s may be 0: the stream is left untouched).
+        Only the pre-transformer runs; the streams' buffers keep their size."""
+        n = len(sids)
+        if len(codes_list) != n:
+            raise ValueError("codec_stream_prime_batch: one code array per stream")
+        if n == 0:
+            return
+        cs = [np.ascontiguousarray(c_, np.int64).reshape(-1, self.cfg.n_groups) for c_ in codes_list]
+        offs = np.cumsum([0] + [c_.shape[0] for c_ in cs]).astype(np.int32)
+        flat = np.ascontiguousarray(np.concatenate(cs)) if offs[-1] else np.zeros((1, self.cfg.n_groups), np.int64)
+        self._ck(self.L.q3tts_codec_stream_prime_batch_host(self.h, n, _p(np.ascontiguousarray(sids, np.int32)), _p(flat), _p(offs)))
+
+    def slots_codec_prime(self, slots, n_frames):
+        """the listed slots' implicit vocoder streams are restarted and primed with the slots' first n_frames[i] frames
+        (q3tts_slots_codec_prime): the next slots_codec_decode_new starts at frame n_frames[i]"""
+        n = len(slots)
+        if len(n_frames) != n:
+            raise ValueError("slots_codec_prime: one frame count per slot")
+        if n == 0:
+            return
+        self._ck(self.L.q3tts_slots_codec_prime(self.h, n, _p(np.ascontiguousarray(slots, np.int32)), _p(np.ascontiguousarray(n_frames, np.int32))))
+
+    def codec_stream_info(self, sid):
+        """-> (n_done, kv_capacity_rows, bytes) of a carried-state stream (q3tts_codec_stream_info)"""
+        nd, kc, by = C.c_int(0), C.c_int(0), C.c_int64(0)
+        self._ck(self.L.q3tts_codec_stream_info(self.h, int(sid), C.byref(nd), C.byref(kc), C.byref(by)))
+        return nd.value, kc.value, by.value
 
     def slots_codec_decode_new(self, slots, max_new_frames=None):
         """samples of the frames each listed slot has generated since its previous streaming call, all slots in batched passes
@@ -890,6 +926,24 @@ class Engine:
             self.slot_release(slot)
         return pcm, codes, F0
 
+    def synthesize_icl_batch(self, ref_pcms, ref_ids_list, token_lists, sp, lang=0, seed=0, ignore_eos=False, speakers=None, ref_rates=24000,
+                             max_new_per_utt=None, chunk_frames=0, on_audio=None):
+        """synthesize_icl for many utterances at once ([HINT] framing): ONE audio_encode_batch call turns the
+        reference clips into codes, frame_icl_ids frames each utterance's ids, and the continue entry generates behind the reference
+        codes — streaming (on_audio, chunk_frames: synthesize_continue's) or not.  Returns, per utterance, the target's PCM, all codes
+        (reference + new frames) and n_ref_frames."""
+        n = len(token_lists)
+        if len(ref_pcms) != n or len(ref_ids_list) != n:
+            raise ValueError("synthesize_icl_batch: one reference clip and one reference id list per utterance")
+        if on_audio is not None and int(chunk_frames) < 1:
+            raise ValueError("synthesize_icl_batch: on_audio needs chunk_frames >= 1")
+        if on_audio is None and chunk_frames:
+            raise ValueError("synthesize_icl_batch: chunk_frames without on_audio")
+        ref_codes = self.audio_encode_batch(ref_pcms, ref_rates)
+        toks = [self.frame_icl_ids(r, t) for r, t in zip(ref_ids_list, token_lists)]
+        pcm, codes, _ = self.synthesize_continue(toks, ref_codes, sp, lang, seed, ignore_eos, speakers, max_new_per_utt, chunk_frames, on_audio)
+        return pcm, codes, [int(c_.shape[0]) for c_ in ref_codes]
+
     @staticmethod
     def frame_icl_ids(ref_ids, ids):
         """ids = a framed utterance as every other entry takes it (3 role ids, the text, the template's 2-id tail); the reference's
@@ -1019,13 +1073,21 @@ class Engine:
         cl = [codes[i, : nfr[i]] for i in range(n)] if want_codes else None
         return outs, cl, nfr
 
-    def synthesize_continue(self, token_lists, prefix_codes, sp, lang=0, seed=0, ignore_eos=False, speakers=None, max_new_per_utt=None):
+    def synthesize_continue(self, token_lists, prefix_codes, sp, lang=0, seed=0, ignore_eos=False, speakers=None, max_new_per_utt=None,
+                            chunk_frames=0, on_audio=None):
         """synthesize_batch with teacher-forced frames per utterance (q3tts_synthesize_continue_host): prefix_codes holds one
         [F0_u][n_groups] array (or None / empty: no prefix) per utterance.  Returns (pcm, codes, n_frames): codes[u] and n_frames[u]
-        cover prefix + new frames, pcm[u] holds the NEW frames' samples only (they join the prefix's audio without a seam)."""
+        cover prefix + new frames, pcm[u] holds the NEW frames' samples only (they join the prefix's audio without a seam).
+        on_audio (with chunk_frames >= 1): the audio is delivered while it is generated, as synthesize_stream delivers it
+        (q3tts_synthesize_continue_stream_host); frame_begin / frame_end count the prefix, so an utterance's first call starts at its
+        prefix length."""
         n = len(token_lists)
         if prefix_codes is None or len(prefix_codes) != n:
             raise ValueError("prefix_codes: one entry (codes or None) per utterance")
+        if on_audio is not None and int(chunk_frames) < 1:
+            raise ValueError("synthesize_continue: on_audio needs chunk_frames >= 1")
+        if on_audio is None and chunk_frames:
+            raise ValueError("synthesize_continue: chunk_frames without on_audio")
         pres = [self._frames(np.zeros((0, self.cfg.n_groups), np.int64) if c_ is None else c_, "synthesize_continue(prefix_codes)") for c_ in prefix_codes]
         poffs = np.zeros(n + 1, np.int32)
         poffs[1:] = np.cumsum([c_.shape[0] for c_ in pres])
@@ -1052,9 +1114,27 @@ class Engine:
         caps = None if max_new_per_utt is None else np.ascontiguousarray(max_new_per_utt, np.int32)
         if caps is not None and caps.shape != (n,):
             raise ValueError("max_new_per_utt: one entry per utterance")
-        self._ck(self.L.q3tts_synthesize_continue_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
-                                                       seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr), _p(codes),
-                                                       _p(pflat), _p(poffs)))
+        if on_audio is None:
+            self._ck(self.L.q3tts_synthesize_continue_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
+                                                           seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr), _p(codes),
+                                                           _p(pflat), _p(poffs)))
+            return [pcm[i][: pcm_len[i]] for i in range(n)], [codes[i, : nfr[i]] for i in range(n)], nfr
+        raised = []
+
+        def tramp(_user, utt, fb, fe, p, ns, fin):
+            try:
+                a = np.ctypeslib.as_array(p, shape=(ns,)).copy() if ns > 0 else np.zeros(0, np.float32)
+                return 1 if on_audio(utt, fb, fe, a, bool(fin)) else 0
+            except BaseException as ex:   # an exception must not cross the C frames: cancel the job, re-raise behind it
+                raised.append(ex)
+                return 1
+        cb = AUDIO_CB(tramp)
+        rc = self.L.q3tts_synthesize_continue_stream_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
+                                                          seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr), _p(codes),
+                                                          _p(pflat), _p(poffs), int(chunk_frames), cb, None)
+        if raised:
+            raise raised[0]
+        self._ck(rc)
         return [pcm[i][: pcm_len[i]] for i in range(n)], [codes[i, : nfr[i]] for i in range(n)], nfr
 
     def synthesize_stream(self, token_lists, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
