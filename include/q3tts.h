@@ -563,6 +563,41 @@ int q3tts_audio_encode_batch_latents_host(q3tts_engine* e, int n_clips, const fl
 /* Parity aid (engines created with Q3TTS_FLAG_TEST_HOOKS): the encoder's transformer alone on rows[n_rows][enc_hidden] -> out, same shape */
 int q3tts_test_audio_encoder_transformer_host(q3tts_engine* e, const float* rows, int n_rows, float* out);
 
+/* ---- audio -> codes while the audio arrives: carried-state pushes of many streams ([HINT], as the encoder above; beside the reference's
+ * clone front end tts_onnx.cpp:331-365, which has no encoder) ----
+ * A stream takes mono float samples at 24 kHz in pushes of any size (another rate is the caller's to resample first: the GPU resampler
+ * of q3tts_audio_encode_batch_host serves whole clips only) and returns the codes of the frames each push completes.
+ * Promise: the codes (and latents) of a stream, however its samples were cut into pushes and whatever other streams shared its
+ * calls, are bit-identical to q3tts_audio_encode_host of the concatenated audio.  After n samples floor(n / samples per frame)
+ * frames have been returned; the finishing push returns the 0 or 1 frames the one-shot's right edge completes.
+ * State per stream lives in device buffers of its own (per conv k - 1 input rows, per transformer layer window - 1 K and V rows;
+ * q3tts_audio_stream_info reports the bytes), kept by q3tts_audio_stream_end for the next begin and freed by q3tts_destroy.
+ * At most 1024 streams are open at a time.  q3tts_last_audio_encode_ms covers pushes too. */
+/* A new stream that will take at most max_samples samples (0: 1 440 000 = 60 s; at most 86 400 000 = one hour).  A stream longer than
+ * any before it regrows the RoPE tables (the same double-precision formula: existing rows keep their bits) and synchronises for it. */
+int q3tts_audio_stream_begin(q3tts_engine* e, int64_t max_samples, int* stream_id);
+/* host-only: frames the next push of n_samples (finish 0/1) to this stream would return; -1 when that push would be refused */
+int q3tts_audio_stream_push_len(q3tts_engine* e, int stream_id, int64_t n_samples, int finish);
+/* n_samples >= 0 more samples; finish != 0 ends the stream's audio (zeros / the repeated last row complete the last frame, as in the
+ * one-shot).  codes_out[*n_frames][n_groups] int64 in q3tts_audio_encode_host's layout: the NEW frames only.  n_samples == 0 without
+ * finish does nothing; finish on a stream that never got a sample returns 0 frames.  A push holds at most 1 440 000 samples. */
+int q3tts_audio_stream_push_host(q3tts_engine* e, int stream_id, const float* pcm24k, int64_t n_samples, int finish,
+                                 int64_t* codes_out, int cap_frames, int32_t* n_frames);
+/* Many streams in one call: one set of launches per group of at most 2 880 000 new samples, whatever the number of streams, and each
+ * stream's result is what pushing it alone gives.  The call is validated completely before any stream moves (ids distinct, open and
+ * not finished; sizes; each stream's total within its max_samples; caps[i] frames of room): a call refused by these checks leaves every
+ * stream where it was.  (A HIP error is another matter: streams advance group by group, so after one in a later group of a call of
+ * more than 2 880 000 new samples the streams of earlier groups have moved; end every stream of such a call.)  finish NULL: no stream finishes.  latents_out (NULL ok, and so may single entries) is the parity aid of
+ * q3tts_audio_encode_batch_latents_host: latents_out[i][n_frames[i]][enc_hidden]. */
+int q3tts_audio_stream_push_batch_host(q3tts_engine* e, int n_streams, const int32_t* stream_ids, const float* const* pcm24k,
+                                       const int64_t* n_samples, const int32_t* finish /* NULL: none */,
+                                       int64_t* const* codes_out, float* const* latents_out /* NULL ok: parity aid */,
+                                       const int32_t* caps, int32_t* n_frames);
+/* samples received, frames returned, finished 0/1 and the bytes of the stream's device state (any pointer may be NULL) */
+int q3tts_audio_stream_info(q3tts_engine* e, int stream_id, int64_t* n_samples, int32_t* n_frames, int* finished, int64_t* bytes);
+/* closes the stream (finished or not); its id and buffers serve a later q3tts_audio_stream_begin */
+int q3tts_audio_stream_end(q3tts_engine* e, int stream_id);
+
 /* ---- text front end: the reference's byte-level BPE tokenizer ---- */
 /* Replaces leaxer_qwen::io::load_vocab / load_merges / is_tokenizer_ready / tokenize (reference
  * src/io/tokenizer.h:13-22, src/io/tokenizer.cpp:538-561) with the same ids for the same files and text.
@@ -580,7 +615,7 @@ int64_t q3tts_tokenize(const q3tts_tokenizer* t, const char* text, int64_t len, 
 /* ---- measurement hooks (bench.py) ---- */
 /* device time in ms of the last q3tts_decode_steps call, from HIP events on the engine's stream */
 int q3tts_last_decode_ms(q3tts_engine* e, float* ms, int* steps);
-/* device time in ms of the last q3tts_audio_encode_* call (uploads and launches of all its groups, HIP events on the engine's stream) */
+/* device time in ms of the last q3tts_audio_encode_* or q3tts_audio_stream_push_* call (uploads and launches of all its groups, HIP events on the engine's stream) */
 int q3tts_last_audio_encode_ms(q3tts_engine* e, float* ms);
 /* device time in ms of the last codec decode */
 int q3tts_last_codec_ms(q3tts_engine* e, float* ms);

@@ -5,8 +5,10 @@
 // --seed N, --instruct TEXT / --instruct-tokens "id,id,..." (a voice instruction in front of the prompt: the reference README's roadmap
 // row "Voice instructions (--instruct)"; combines with --ref), --save-codes FILE / --continue-codes FILE (with --tokens: write the
 // utterance's codec frames, one per line; generate behind recorded frames — the WAV then holds the new audio only),
-// --encode WAV --save-codes FILE (audio -> codes with the 12 Hz tokenizer's encoder, nothing else), --ref WAV with --ref-text TEXT /
+// --encode WAV --save-codes FILE (audio -> codes with the 12 Hz tokenizer's encoder, nothing else; --encode-chunk MS pushes the file MS
+// milliseconds at a time through one encoder stream: for a 24 kHz file the same codes, and no 60 s limit), --ref WAV with --ref-text TEXT /
 // --ref-tokens "id,id,..." (in-context clone: the reference's codes and text in front of the utterance; --ref alone stays the x-vector clone).
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,6 +16,7 @@
 #include <sys/stat.h>
 #include <vector>
 
+#include "../../include/q3tts.h"
 #include "tts_engine.h"
 
 using namespace leaxer_qwen;
@@ -52,6 +55,7 @@ static void usage(const char* prog) {
     printf("  --ref-text TEXT       with --ref: in-context clone instead — the reference is encoded to codes and continued, TEXT is what it says\n");
     printf("  --ref-tokens IDS      the same with the reference text as comma-separated token ids (for synthetic: models, with --tokens)\n");
     printf("  --encode PATH         encode a WAV to codec frames with the audio encoder and write them to --save-codes FILE; nothing is synthesized\n");
+    printf("  --encode-chunk MS     with --encode: push the file MS milliseconds at a time through one encoder stream (a 24 kHz file gives the same codes; files over 60 s encode)\n");
     printf("  --temp FLOAT          temperature (default: 0.8; 0 samples at T=1 like the reference, use --top-k 1 for greedy)\n");
     printf("  --top-k N             top-k (default: 50)\n  --top-p FLOAT         top-p (default: 0.95)\n");
     printf("  --rep-penalty FLOAT   repetition penalty on the first codebook's ids (default: 1.0 = off; not a flag of the reference CLI)\n");
@@ -59,6 +63,20 @@ static void usage(const char* prog) {
     printf("  --stream-chunk N      with --tokens: decode audio every N frames while generating (same samples as the one-shot decode);\n");
     printf("                        combines with --continue-codes and with --ref + --ref-text / --ref-tokens (the prefix is history, never decoded)\n");
     printf("  --feed K              with --stream-chunk: hand the text to the engine K tokens at a time while it generates (live text; same codes, and with --save-codes the same samples as without --feed)\n  -h, --help\n");
+}
+
+// a WAV file as mono float at 24 kHz for --encode-chunk (an encoder stream takes 24 kHz only): read on the host and, when its rate
+// differs, resampled on the host too — plain --encode resamples such a file on the GPU, so only 24 kHz files give both the same codes
+static bool read_wav_24k(const std::string& path, std::vector<float>& pcm24k) {
+    int64_t n = 0; int32_t rate = 0;
+    if (q3tts_read_wav_host(path.c_str(), nullptr, 0, &n, &rate) != 0 || n < 1) return false;
+    std::vector<float> raw((size_t)n);
+    if (q3tts_read_wav_host(path.c_str(), raw.data(), n, &n, &rate) != 0) return false;
+    if (rate == 24000) { pcm24k.swap(raw); return true; }
+    const int64_t m = q3tts_resample_host(raw.data(), (int64_t)raw.size(), rate, 24000, nullptr, 0);
+    if (m < 1) return false;
+    pcm24k.resize((size_t)m);
+    return q3tts_resample_host(raw.data(), (int64_t)raw.size(), rate, 24000, pcm24k.data(), m) == m;
 }
 
 // one frame per line, the same number of integers on every line (blanks or commas between them); false with a message on stderr
@@ -123,7 +141,8 @@ int main(int argc, char** argv) {
     bool have_prompt = false;
     SamplingParams sp;
     uint64_t seed = 0;
-    int stream_chunk = 0, feed = 0;
+    int stream_chunk = 0, feed = 0, encode_chunk = 0;
+    bool have_encode_chunk = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         const bool more = i + 1 < argc;
@@ -137,6 +156,7 @@ int main(int argc, char** argv) {
         else if (a == "--ref-text" && more) ref_text = argv[++i];
         else if (a == "--ref-tokens" && more) ref_tokens = argv[++i];
         else if (a == "--encode" && more) encode = argv[++i];
+        else if (a == "--encode-chunk" && more) { encode_chunk = atoi(argv[++i]); have_encode_chunk = true; }
         else if (a == "--instruct" && more) instruct = argv[++i];
         else if (a == "--instruct-tokens" && more) instruct_tokens = argv[++i];
         else if (a == "--save-codes" && more) save_codes = argv[++i];
@@ -151,12 +171,31 @@ int main(int argc, char** argv) {
         else if (a == "--feed" && more) feed = atoi(argv[++i]);
     }
     const bool icl = !ref_text.empty() || !ref_tokens.empty();
+    if (have_encode_chunk && (encode.empty() || encode_chunk < 1)) {
+        fprintf(stderr, "Error: --encode-chunk MS (MS >= 1) goes with --encode\nUsage: %s -m MODEL --encode WAV --encode-chunk MS --save-codes FILE\n", argv[0]);
+        return 1;
+    }
     if (!encode.empty()) {   // audio -> codes, nothing else
         if (model.empty() || save_codes.empty()) { fprintf(stderr, "Error: --encode needs --model and --save-codes FILE\n"); return 1; }
         TTSEngine enc_engine(model, true);
         if (!enc_engine.is_ready()) { fprintf(stderr, "Error: %s\n", enc_engine.get_error().c_str()); return 1; }
         if (!enc_engine.has_audio_encoder()) { fprintf(stderr, "Error: model has no audio encoder\n"); return 1; }
-        const std::vector<int64_t> codes = enc_engine.encode_audio(encode);
+        std::vector<int64_t> codes;
+        if (have_encode_chunk) {   // the file through one encoder stream sized to it, encode_chunk ms per push
+            std::vector<float> pcm;
+            if (!read_wav_24k(encode, pcm) || pcm.empty()) { fprintf(stderr, "Error: failed to read %s\n", encode.c_str()); return 1; }
+            const int id = enc_engine.audio_stream_begin((int64_t)pcm.size());
+            if (id < 0) { fprintf(stderr, "Error: encoding failed\n"); return 1; }
+            const size_t step = std::min<size_t>((size_t)encode_chunk * 24, 1440000);
+            bool ok = true;
+            for (size_t i = 0; ok && i < pcm.size(); i += step) {
+                const size_t m = std::min(step, pcm.size() - i);
+                const std::vector<int64_t> part = enc_engine.audio_stream_push(id, pcm.data() + i, m, i + m == pcm.size(), &ok);
+                codes.insert(codes.end(), part.begin(), part.end());
+            }
+            enc_engine.audio_stream_end(id);
+            if (!ok) codes.clear();
+        } else codes = enc_engine.encode_audio(encode);
         if (codes.empty()) { fprintf(stderr, "Error: encoding failed\n"); return 1; }
         if (!write_codes_file(save_codes, codes, (size_t)enc_engine.n_groups())) { fprintf(stderr, "Error: failed to write %s\n", save_codes.c_str()); return 1; }
         printf("Encoded %zu frames\nCodes saved to: %s\n", codes.size() / (size_t)enc_engine.n_groups(), save_codes.c_str());

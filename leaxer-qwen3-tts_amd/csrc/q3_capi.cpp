@@ -1266,6 +1266,62 @@ int q3tts_audio_encode_host(q3tts_engine* h, const float* pcm24k, int64_t n_samp
     return q3tts_audio_encode_latents_host(h, pcm24k, n_samples, nullptr, codes_out, cap_frames, n_frames);
 }
 
+// ---- streamed audio -> codes (Engine::audio_stream_*) ----
+int q3tts_audio_stream_begin(q3tts_engine* h, int64_t max_samples, int* stream_id) {
+    Q3_API_BEGIN(h)
+    if (!h->e->has_audio_encoder()) throw q3::Error("model has no audio encoder");
+    if (!h->e->finalized) throw q3::Error("weights not finalized");
+    if (!stream_id) throw q3::Error("audio stream: NULL argument");
+    *stream_id = h->e->audio_stream_begin(max_samples);
+    return 0;
+    Q3_API_END(h)
+}
+
+int q3tts_audio_stream_push_len(q3tts_engine* h, int stream_id, int64_t n_samples, int finish) {
+    Q3_API_BEGIN(h)
+    return (int)h->e->audio_stream_push_len(stream_id, n_samples, finish != 0);
+    Q3_API_END(h)
+}
+
+int q3tts_audio_stream_push_batch_host(q3tts_engine* h, int n_streams, const int32_t* stream_ids, const float* const* pcm24k, const int64_t* n_samples,
+                                       const int32_t* finish, int64_t* const* codes_out, float* const* latents_out, const int32_t* caps, int32_t* n_frames) {
+    Q3_API_BEGIN(h)
+    if (!h->e->has_audio_encoder()) throw q3::Error("model has no audio encoder");
+    if (!h->e->finalized) throw q3::Error("weights not finalized");
+    if (!codes_out || !caps) throw q3::Error("audio stream push: NULL argument");
+    h->e->audio_stream_push_batch(n_streams, stream_ids, pcm24k, n_samples, finish, codes_out, latents_out, caps, n_frames);
+    return 0;
+    Q3_API_END(h)
+}
+
+int q3tts_audio_stream_push_host(q3tts_engine* h, int stream_id, const float* pcm24k, int64_t n_samples, int finish, int64_t* codes_out, int cap_frames,
+                                 int32_t* n_frames) {
+    Q3_API_BEGIN(h)
+    if (!h->e->has_audio_encoder()) throw q3::Error("model has no audio encoder");
+    if (!h->e->finalized) throw q3::Error("weights not finalized");
+    if (!codes_out) throw q3::Error("audio stream push: NULL argument");
+    const int32_t id = stream_id, fin = finish ? 1 : 0, cap = cap_frames;
+    int32_t nf = 0;
+    h->e->audio_stream_push_batch(1, &id, &pcm24k, &n_samples, &fin, &codes_out, nullptr, &cap, &nf);
+    if (n_frames) *n_frames = nf;
+    return 0;
+    Q3_API_END(h)
+}
+
+int q3tts_audio_stream_info(q3tts_engine* h, int stream_id, int64_t* n_samples, int32_t* n_frames, int* finished, int64_t* bytes) {
+    Q3_API_BEGIN(h)
+    h->e->audio_stream_info(stream_id, n_samples, n_frames, finished, bytes);
+    return 0;
+    Q3_API_END(h)
+}
+
+int q3tts_audio_stream_end(q3tts_engine* h, int stream_id) {
+    Q3_API_BEGIN(h)
+    h->e->audio_stream_end(stream_id);
+    return 0;
+    Q3_API_END(h)
+}
+
 int q3tts_last_audio_encode_ms(q3tts_engine* h, float* ms) {
     if (!h || !h->e || !ms) return -1;
     *ms = h->e->last_audio_encode_ms;

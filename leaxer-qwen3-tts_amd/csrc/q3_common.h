@@ -482,11 +482,28 @@ struct EncConvArgs {
     const EncSpan* sin = nullptr; const EncSpan* sout = nullptr; int n_clips = 0, max_T_out = 0;
 };
 void launch_enc_conv(const EncConvArgs& a, hipStream_t s);      // Cin == 1: VALU kernel; otherwise implicit GEMM on the fp32 matrix cores
+// Streamed pushes (q3_encoder.cpp).  One stream at one launch: the span holds the stream's NEW rows only, and what lies
+// before them comes from the stream's carry ring: `cap` rows of the launch's input width, absolute input row r in slot r mod cap.
+// n_in = input rows the stream had before this push (the chunk's row 0 is absolute row n_in); shift = chunk-local input row that
+// output row 0's stride origin falls on (n_out * stride - n_in, <= 0).  A conv reads src = t * stride + shift - pad_left + tap * dil:
+// src >= 0 is a chunk row, src < 0 absolute row n_in + src from the ring, rows before the stream's start are zeros (its first row
+// when replicate) and rows past the chunk are zeros (its last row when replicate): the one-shot's edges, met only at a stream's
+// first and finishing pushes.  RoPE and attention read n_in as the chunk's first absolute row and carry as the layer's K/V ring
+// ([window - 1][2 * heads * d]: rotated K, then V).
+struct EncHist { const float* carry = nullptr; int32_t n_in = 0, shift = 0, cap = 0, pad_ = 0; };
+void launch_enc_conv_hist(const EncConvArgs& a, const EncHist* hist /* device, [n_clips] */, hipStream_t s);
+// rows [0, rows) of src (row stride src_ld floats, `width` floats each) into ring slots (slot0 + i) mod cap of dst; rows <= cap
+struct EncCarryCopy { const float* src = nullptr; float* dst = nullptr; int32_t rows = 0, width = 0, src_ld = 0, slot0 = 0, cap = 0, pad_ = 0; };
+void launch_enc_carry_copy(const EncCarryCopy* tab /* device, [n] */, int n, int64_t max_floats /* largest rows * width */, hipStream_t s);
 void launch_enc_layernorm(const float* x, const float* w, const float* b, float eps, int rows, int C, float* out, hipStream_t s);
 // q and k of qkv [rows][3 * heads * d] rotated in place (rotate-half RoPE) at each row's position inside its clip; cs / sn [max_pos][d / 2]
-void launch_enc_rope(float* qkv, const float* cs, const float* sn, int max_pos, int heads, int d, const EncSpan* spans, int n_clips, int max_T, hipStream_t s);
+// hist (streamed pushes): position = hist[clip].n_in + row
+void launch_enc_rope(float* qkv, const float* cs, const float* sn, int max_pos, int heads, int d, const EncSpan* spans, int n_clips, int max_T, hipStream_t s,
+                     const EncHist* hist = nullptr);
 // causal sliding-window attention inside each clip: row i sees rows (i - window, i]; out [rows][heads * d]
-void launch_enc_attn(const float* qkv, float* out, int heads, int d, int window, float scale, const EncSpan* spans, int n_clips, int max_T, hipStream_t s);
+// hist (streamed pushes): keys before the chunk come from hist[clip].carry, the layer's K/V ring
+void launch_enc_attn(const float* qkv, float* out, int heads, int d, int window, float scale, const EncSpan* spans, int n_clips, int max_T, hipStream_t s,
+                     const EncHist* hist = nullptr);
 // split residual VQ: per frame both input projections ([D][H] each), then level g = 0 on the semantic residual and levels 1 .. G - 1 on the
 // acoustic one: nearest row of books[g] [CB][D] by direct squared distance (lowest index on a tie), residual -= that row.  codes [rows][G]
 void launch_rvq_encode(const float* lat, int rows, int H, const float* proj_sem, const float* proj_ac, const float* books, int G, int CB, int D,

@@ -24,6 +24,14 @@ struct EncLayerW {
     const float *ln1w = nullptr, *ln1b = nullptr, *qkv = nullptr, *o = nullptr, *s1 = nullptr;
     const float *ln2w = nullptr, *ln2b = nullptr, *fc1 = nullptr, *fc2 = nullptr, *s2 = nullptr;
 };
+// One audio stream's carried state.  rows[l]: rows emitted so far at rate level l (0 = samples received, l = 1 .. nr
+// behind stage l - 1, nr + 1 = frames).  buf: the stream's carry rings, one per conv with k > 1 (k - 1 raw input rows, before ELU)
+// and one per transformer layer ([window - 1][2 AO]: rotated K, then V); absolute row r of a ring's input sits in slot r mod cap.
+struct EncStream {
+    bool open = false, finished = false;
+    int64_t max_samples = 0, rows[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    float* buf = nullptr; size_t buf_floats = 0;
+};
 struct EncoderW {
     EncConvW conv_in, res1[4], res2[4], down[4], conv_out, ds;
     std::vector<EncLayerW> layers;
@@ -31,6 +39,7 @@ struct EncoderW {
     float* books = nullptr;                    // [n_groups][codebook][vq_dim], the level tables back to back
     float *rope_cs = nullptr, *rope_sn = nullptr; int rope_rows = 0;
     char* ws = nullptr; size_t ws_cap = 0;     // grow-only workspace
+    std::vector<EncStream> streams;            // streamed pushes: state in allocations of its own, never in ws
 };
 
 static constexpr size_t kEncAlign = 256;
@@ -53,6 +62,7 @@ int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 void Engine::encoder_free() {
     if (!enc) return;
     if (enc->ws) (void)hipFree(enc->ws);
+    for (EncStream& st : enc->streams) if (st.buf) (void)hipFree(st.buf);
     if (enc->books) (void)hipFree(enc->books);
     if (enc->rope_cs) (void)hipFree(enc->rope_cs);
     if (enc->rope_sn) (void)hipFree(enc->rope_sn);
@@ -68,6 +78,28 @@ int64_t Engine::audio_encode_len(int64_t n24) const {
     int64_t T = n24;
     for (int s = 0; s < c.enc_n_ratios; ++s) T = ceil_div(T, c.enc_ratios[s]);
     return ceil_div(T, 2);
+}
+
+// RoPE tables for rows [0, rows), computed in double: a row's bits do not depend on how many rows the tables have
+static void enc_rope_tables(Engine& e, int rows) {
+    EncoderW* enc = e.enc;
+    const q3tts_config& c = e.c;
+    const int half = c.enc_head_dim / 2;
+    if (enc->rope_rows != rows || !enc->rope_cs) {
+        if (enc->rope_cs) (void)hipFree(enc->rope_cs);
+        if (enc->rope_sn) (void)hipFree(enc->rope_sn);
+        enc->rope_cs = enc->rope_sn = nullptr; enc->rope_rows = 0;
+        Q3_HIP_CHECK(hipMalloc((void**)&enc->rope_cs, (size_t)rows * half * sizeof(float)));
+        Q3_HIP_CHECK(hipMalloc((void**)&enc->rope_sn, (size_t)rows * half * sizeof(float)));
+        enc->rope_rows = rows;
+    }
+    std::vector<float> cs((size_t)rows * half), sn((size_t)rows * half);
+    for (int j = 0; j < half; ++j) {
+        const double inv = 1.0 / std::pow((double)c.enc_rope_theta, (double)(2 * j) / (double)c.enc_head_dim);
+        for (int p = 0; p < rows; ++p) { cs[(size_t)p * half + j] = (float)std::cos(p * inv); sn[(size_t)p * half + j] = (float)std::sin(p * inv); }
+    }
+    Q3_HIP_CHECK(hipMemcpy(enc->rope_cs, cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice));
+    Q3_HIP_CHECK(hipMemcpy(enc->rope_sn, sn.data(), sn.size() * sizeof(float), hipMemcpyHostToDevice));
 }
 
 void Engine::encoder_finalize() {
@@ -104,31 +136,19 @@ void Engine::encoder_finalize() {
     // RoPE tables for every row a clip under the cap can have, computed in double
     int64_t prod = 1;
     for (int s = 0; s < c.enc_n_ratios; ++s) prod *= c.enc_ratios[s];
-    const int rows = (int)ceil_div(kEncMaxClipSamples, prod) + 1, half = c.enc_head_dim / 2;
-    if (enc->rope_rows != rows || !enc->rope_cs) {
-        if (enc->rope_cs) (void)hipFree(enc->rope_cs);
-        if (enc->rope_sn) (void)hipFree(enc->rope_sn);
-        enc->rope_cs = enc->rope_sn = nullptr;
-        Q3_HIP_CHECK(hipMalloc((void**)&enc->rope_cs, (size_t)rows * half * sizeof(float)));
-        Q3_HIP_CHECK(hipMalloc((void**)&enc->rope_sn, (size_t)rows * half * sizeof(float)));
-        enc->rope_rows = rows;
-    }
-    std::vector<float> cs((size_t)rows * half), sn((size_t)rows * half);
-    for (int j = 0; j < half; ++j) {
-        const double inv = 1.0 / std::pow((double)c.enc_rope_theta, (double)(2 * j) / (double)c.enc_head_dim);
-        for (int p = 0; p < rows; ++p) { cs[(size_t)p * half + j] = (float)std::cos(p * inv); sn[(size_t)p * half + j] = (float)std::sin(p * inv); }
-    }
-    Q3_HIP_CHECK(hipMemcpy(enc->rope_cs, cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice));
-    Q3_HIP_CHECK(hipMemcpy(enc->rope_sn, sn.data(), sn.size() * sizeof(float), hipMemcpyHostToDevice));
+    const int rows = (int)ceil_div(kEncMaxClipSamples, prod) + 1;
+    enc_rope_tables(*this, std::max(rows, enc->rope_rows));   // tables a stream has grown stay grown
     sync();
 }
 
 namespace {
 struct EncTfBufs { float *x = nullptr, *n = nullptr, *qkv = nullptr, *a = nullptr, *f = nullptr; };
+// streamed pushes: per layer the streams' K/V rings (device tables, one entry per span) and the ring update behind the attention
+struct EncTfCarry { std::vector<const EncHist*> hist; std::vector<const EncCarryCopy*> copy; int n_copy = 0; int64_t max_floats = 0; };
 }
 
 // the transformer over R rows laid out by `spans` (level of the 25 Hz rows), in place on b.x
-static void enc_run_transformer(Engine& e, const EncTfBufs& b, const EncSpan* spans, int n_clips, int R, int maxT) {
+static void enc_run_transformer(Engine& e, const EncTfBufs& b, const EncSpan* spans, int n_clips, int R, int maxT, const EncTfCarry* carry = nullptr) {
     const q3tts_config& c = e.c;
     const EncoderW& W = *e.enc;
     const int EH = c.enc_hidden, AO = c.enc_heads * c.enc_head_dim;
@@ -138,11 +158,14 @@ static void enc_run_transformer(Engine& e, const EncTfBufs& b, const EncSpan* sp
         q.sin = spans; q.sout = spans; q.n_clips = n_clips; q.max_T_out = maxT;
         launch_enc_conv(q, e.stream);
     };
-    for (const EncLayerW& w : W.layers) {
+    for (size_t li = 0; li < W.layers.size(); ++li) {
+        const EncLayerW& w = W.layers[li];
+        const EncHist* hist = carry ? carry->hist[li] : nullptr;
         launch_enc_layernorm(b.x, w.ln1w, w.ln1b, c.enc_norm_eps, R, EH, b.n, e.stream);
         lin(b.n, EH, w.qkv, 3 * AO, b.qkv, 0, nullptr, nullptr);
-        launch_enc_rope(b.qkv, W.rope_cs, W.rope_sn, W.rope_rows, c.enc_heads, c.enc_head_dim, spans, n_clips, maxT, e.stream);
-        launch_enc_attn(b.qkv, b.a, c.enc_heads, c.enc_head_dim, c.enc_window, 1.0f / sqrtf((float)c.enc_head_dim), spans, n_clips, maxT, e.stream);
+        launch_enc_rope(b.qkv, W.rope_cs, W.rope_sn, W.rope_rows, c.enc_heads, c.enc_head_dim, spans, n_clips, maxT, e.stream, hist);
+        launch_enc_attn(b.qkv, b.a, c.enc_heads, c.enc_head_dim, c.enc_window, 1.0f / sqrtf((float)c.enc_head_dim), spans, n_clips, maxT, e.stream, hist);
+        if (carry && carry->n_copy > 0) launch_enc_carry_copy(carry->copy[li], carry->n_copy, carry->max_floats, e.stream);
         lin(b.a, AO, w.o, EH, b.x, 0, w.s1, b.x);
         launch_enc_layernorm(b.x, w.ln2w, w.ln2b, c.enc_norm_eps, R, EH, b.n, e.stream);
         lin(b.n, EH, w.fc1, c.enc_ffn, b.f, 1, nullptr, nullptr);
@@ -280,6 +303,303 @@ void Engine::audio_encode(int n_clips, const float* const* pcm, const int64_t* n
             const EncSpan sp = spans[(size_t)(nr + 1) * n + i];
             if (codes_out && codes_out[g0 + i])
                 for (size_t k = 0; k < (size_t)sp.T * G; ++k) codes_out[g0 + i][k] = codes_h[(size_t)sp.off * G + k];
+        }
+        g0 = g1;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Streamed pushes.  A level's buffer holds the NEW rows of the push's streams back to back; what a conv or the
+// attention needs from before them it reads from the stream's carry rings (EncHist), and one k_enc_carry_copy launch behind each
+// consumer writes the push's last rows into the rings.  Rings are written from workspace rows only, so a push shorter than a ring
+// moves nothing inside it.  A normal push emits floor(n_in / stride) - n_out rows per level (complete outputs only), a finishing one
+// ceil(...) with the one-shot's right edge; the K walk of every kernel is the one-shot's, hence the same bits.
+// ------------------------------------------------------------------------------------------------
+namespace {
+// EncHist::n_in / shift and the kernels' ring-slot arithmetic (absolute row mod cap) are int32: a stream's sample count must fit
+static_assert(Engine::kEncMaxStreamSamples <= INT32_MAX, "a stream's absolute rows are int32 in EncHist and the encoder kernels");
+struct EncConvPlan { const EncConvW* w; int lin, lout, stride, elu, replicate, cap; size_t off; };   // off: the ring's first float in EncStream::buf
+struct EncStreamPlan { std::vector<EncConvPlan> convs; std::vector<size_t> kv_off; int kv_cap = 0; size_t kv_width = 0, floats = 0; };
+EncStreamPlan enc_stream_plan(const q3tts_config& c, const EncoderW& W) {
+    EncStreamPlan p;
+    const int nr = c.enc_n_ratios;
+    auto add = [&](const EncConvW& w, int lin, int lout, int stride, int elu, int rep) {
+        EncConvPlan q{ &w, lin, lout, stride, elu, rep, w.k - 1, p.floats };
+        p.floats += enc_aligned((size_t)q.cap * w.cin * sizeof(float)) / sizeof(float);
+        p.convs.push_back(q);
+    };
+    add(W.conv_in, 0, 0, 1, 0, 0);
+    for (int s = 0; s < nr; ++s) { add(W.res1[s], s, s, 1, 1, 0); add(W.res2[s], s, s, 1, 1, 0); add(W.down[s], s, s + 1, c.enc_ratios[s], 1, 0); }
+    add(W.conv_out, nr, nr, 1, 1, 0);
+    add(W.ds, nr, nr + 1, 2, 0, 1);
+    p.kv_cap = c.enc_window - 1; p.kv_width = (size_t)2 * c.enc_heads * c.enc_head_dim;
+    for (int l = 0; l < c.enc_layers; ++l) { p.kv_off.push_back(p.floats); p.floats += enc_aligned((size_t)p.kv_cap * p.kv_width * sizeof(float)) / sizeof(float); }
+    if (p.floats == 0) p.floats = 1;
+    return p;
+}
+// rows every level has after `add` more samples: floor per level, ceil when the stream finishes (the one-shot's T = ceil(T / stride))
+void enc_stream_advance(const q3tts_config& c, const int64_t* before, int64_t add, bool finish, int64_t* after) {
+    const int nr = c.enc_n_ratios;
+    after[0] = before[0] + add;
+    for (int l = 1; l <= nr + 1; ++l) {
+        const int64_t st = l <= nr ? c.enc_ratios[l - 1] : 2;
+        after[l] = finish ? ceil_div(after[l - 1], st) : after[l - 1] / st;
+    }
+}
+struct EncTab {   // the call's descriptor tables, built on the host and uploaded once
+    std::vector<char> h;
+    template <class T> size_t add(const std::vector<T>& v) {
+        const size_t o = h.size();
+        h.resize(o + enc_aligned(std::max<size_t>(1, v.size()) * sizeof(T)));
+        if (!v.empty()) std::memcpy(&h[o], v.data(), v.size() * sizeof(T));
+        return o;
+    }
+};
+}
+
+static EncStream& enc_stream_at(const Engine& e, int id, const char* who) {
+    if (!e.has_audio_encoder()) throw Error("model has no audio encoder");
+    if (!e.enc) throw Error("weights not finalized");
+    if (id < 0 || id >= (int)e.enc->streams.size() || !e.enc->streams[(size_t)id].open)
+        throw Error(std::string(who) + ": no open audio stream with id " + std::to_string(id));
+    return e.enc->streams[(size_t)id];
+}
+
+int Engine::audio_stream_begin(int64_t max_samples) {
+    if (!has_audio_encoder()) throw Error("model has no audio encoder");
+    if (!enc) throw Error("weights not finalized");
+    if (max_samples == 0) max_samples = kEncMaxClipSamples;
+    if (max_samples < 1 || max_samples > kEncMaxStreamSamples)
+        throw Error("audio stream: max_samples must be 0 (60 s) or 1.." + std::to_string(kEncMaxStreamSamples) + " (one hour), got " + std::to_string(max_samples));
+    int id = -1, n_open = 0;
+    for (size_t i = 0; i < enc->streams.size(); ++i) {
+        if (enc->streams[i].open) ++n_open;
+        else if (id < 0) id = (int)i;
+    }
+    if (n_open >= kEncMaxStreams) throw Error("audio stream: " + std::to_string(kEncMaxStreams) + " streams are open already");
+    int64_t prod = 1;
+    for (int s = 0; s < c.enc_n_ratios; ++s) prod *= c.enc_ratios[s];
+    const int rows = (int)ceil_div(max_samples, prod) + 1;
+    if (rows > enc->rope_rows) { sync(); enc_rope_tables(*this, rows); }   // the whole table again, by the same formula: existing rows keep their bits
+    const EncStreamPlan plan = enc_stream_plan(c, *enc);
+    if (id < 0) { enc->streams.emplace_back(); id = (int)enc->streams.size() - 1; }
+    EncStream& st = enc->streams[(size_t)id];
+    if (st.buf_floats < plan.floats) {
+        if (st.buf) (void)hipFree(st.buf);
+        st.buf = nullptr; st.buf_floats = 0;
+        Q3_HIP_CHECK(hipMalloc((void**)&st.buf, plan.floats * sizeof(float)));
+        st.buf_floats = plan.floats;
+    }
+    // no clearing: a ring slot is read only for an absolute row this stream has written
+    st.open = true; st.finished = false; st.max_samples = max_samples;
+    for (int64_t& r : st.rows) r = 0;
+    return id;
+}
+
+void Engine::audio_stream_end(int id) {
+    EncStream& st = enc_stream_at(*this, id, "audio_stream_end");
+    st.open = false; st.finished = false;
+}
+
+void Engine::audio_stream_info(int id, int64_t* n_samples, int32_t* n_frames, int* finished, int64_t* bytes) const {
+    const EncStream& st = enc_stream_at(*this, id, "audio_stream_info");
+    if (n_samples) *n_samples = st.rows[0];
+    if (n_frames) *n_frames = (int32_t)st.rows[c.enc_n_ratios + 1];
+    if (finished) *finished = st.finished ? 1 : 0;
+    if (bytes) *bytes = (int64_t)(st.buf_floats * sizeof(float));
+}
+
+int64_t Engine::audio_stream_push_len(int id, int64_t n_samples, bool finish) const {
+    const EncStream& st = enc_stream_at(*this, id, "audio_stream_push_len");
+    if (st.finished) throw Error("audio stream " + std::to_string(id) + " is finished");
+    if (n_samples < 0 || n_samples > kEncMaxClipSamples || st.rows[0] + n_samples > st.max_samples)
+        throw Error("audio stream " + std::to_string(id) + ": a push of " + std::to_string(n_samples) + " samples is outside the stream's limits");
+    int64_t after[8];
+    enc_stream_advance(c, st.rows, n_samples, finish, after);
+    return after[c.enc_n_ratios + 1] - st.rows[c.enc_n_ratios + 1];
+}
+
+void Engine::audio_stream_push_batch(int n_streams, const int32_t* ids, const float* const* pcm, const int64_t* n_samples, const int32_t* finish,
+                                     int64_t* const* codes_out, float* const* latents_out, const int32_t* caps, int32_t* n_frames) {
+    if (!has_audio_encoder()) throw Error("model has no audio encoder");
+    if (!enc) throw Error("weights not finalized");
+    if (n_streams < 1) throw Error("audio stream push: n_streams must be at least 1, got " + std::to_string(n_streams));
+    if (!ids || !pcm || !n_samples || !n_frames) throw Error("audio stream push: NULL argument");
+    const int nr = c.enc_n_ratios, NL = nr + 2, EH = c.enc_hidden, AO = c.enc_heads * c.enc_head_dim, G = c.n_groups;
+    // everything is validated before any stream moves
+    std::vector<int64_t> after((size_t)n_streams * 8, 0);
+    for (int i = 0; i < n_streams; ++i) {
+        const std::string who = "audio stream " + std::to_string(ids[i]) + ": ";
+        const EncStream& st = enc_stream_at(*this, ids[i], "audio stream push");
+        for (int j = 0; j < i; ++j) if (ids[j] == ids[i]) throw Error(who + "given twice in one push");
+        if (st.finished) throw Error(who + "is finished");
+        if (n_samples[i] < 0) throw Error(who + "n_samples must not be negative, got " + std::to_string(n_samples[i]));
+        if (n_samples[i] > 0 && !pcm[i]) throw Error(who + "NULL audio pointer");
+        if (n_samples[i] > kEncMaxClipSamples)
+            throw Error(who + "push too long: " + std::to_string(n_samples[i]) + " samples, the cap per push is " + std::to_string(kEncMaxClipSamples) + " (60 s)");
+        if (st.rows[0] + n_samples[i] > st.max_samples)
+            throw Error(who + "over its max_samples: " + std::to_string(st.rows[0]) + " + " + std::to_string(n_samples[i]) + " samples, the stream was begun for " + std::to_string(st.max_samples));
+        enc_stream_advance(c, st.rows, n_samples[i], finish && finish[i], &after[(size_t)i * 8]);
+        const int64_t F = after[(size_t)i * 8 + nr + 1] - st.rows[nr + 1];
+        if (F > 0 && ((codes_out && codes_out[i]) || (latents_out && latents_out[i]))) {
+            if (!caps || caps[i] < F) throw Error(who + "output buffer too small for " + std::to_string(F) + " frames");
+        }
+    }
+    const EncStreamPlan plan = enc_stream_plan(c, *enc);
+    last_audio_encode_ms = 0.f;
+
+    for (int g0 = 0; g0 < n_streams;) {
+        int g1 = g0; int64_t sum = 0;   // a group: at most kEncMaxGroupSamples new samples (its first stream always fits); a stream's push is never split
+        while (g1 < n_streams && g1 - g0 < 1024 && (g1 == g0 || sum + n_samples[g1] <= kEncMaxGroupSamples)) { sum += n_samples[g1]; ++g1; }
+        const int n = g1 - g0;
+        auto stream_of = [&](int i) -> EncStream& { return enc->streams[(size_t)ids[g0 + i]]; };
+        auto before = [&](int i, int l) { return stream_of(i).rows[l]; };
+        auto newr = [&](int i, int l) { return (int)(after[(size_t)(g0 + i) * 8 + l] - stream_of(i).rows[l]); };
+        // spans of the new rows: level 0 = samples, level s + 1 behind stage s, level nr + 1 = frames
+        std::vector<EncSpan> spans((size_t)NL * n);
+        std::vector<int64_t> tot((size_t)NL, 0);
+        for (int i = 0; i < n; ++i)
+            for (int l = 0; l < NL; ++l) {
+                spans[(size_t)l * n + i].off = (int32_t)tot[(size_t)l]; spans[(size_t)l * n + i].T = newr(i, l);
+                tot[(size_t)l] += newr(i, l);
+            }
+        size_t xmax = 1, mmax = 1;
+        { int dim = c.enc_filters;
+          for (int s = 0; s <= nr; ++s, dim *= 2) { xmax = std::max(xmax, (size_t)tot[(size_t)s] * dim); mmax = std::max(mmax, (size_t)tot[(size_t)s] * (dim / 2)); } }
+        const size_t R = (size_t)tot[(size_t)nr], F = (size_t)tot[(size_t)nr + 1], R1 = std::max<size_t>(1, R), F1 = std::max<size_t>(1, F);
+        const size_t tab_cap = (size_t)n * (plan.convs.size() * (2 * enc_aligned(sizeof(EncSpan)) + enc_aligned(sizeof(EncHist)) + enc_aligned(sizeof(EncCarryCopy)))
+                                            + (size_t)c.enc_layers * (enc_aligned(sizeof(EncHist)) + enc_aligned(sizeof(EncCarryCopy))) + enc_aligned(sizeof(EncSpan)));
+        struct Bufs { char* tab; float *x24, *X, *Y, *M; EncTfBufs tf; float* lat; int32_t* codes; size_t used; };
+        auto layout = [&](char* base) {
+            EncCarve cv(base);
+            Bufs b;
+            b.tab = (char*)cv.take_bytes(tab_cap);
+            b.x24 = cv.take(std::max<size_t>(1, (size_t)tot[0]));
+            b.X = cv.take(xmax); b.Y = cv.take(xmax); b.M = cv.take(mmax);
+            b.tf.x = cv.take(R1 * EH); b.tf.n = cv.take(R1 * EH); b.tf.qkv = cv.take(R1 * 3 * AO); b.tf.a = cv.take(R1 * AO); b.tf.f = cv.take(R1 * (size_t)c.enc_ffn);
+            b.lat = cv.take(F1 * EH);
+            b.codes = (int32_t*)cv.take_bytes(F1 * G * sizeof(int32_t));
+            b.used = cv.used;
+            return b;
+        };
+        enc_ws_reserve(*enc, layout(nullptr).used);
+        const Bufs b = layout(enc->ws);
+
+        // pass 1: every launch's tables (the streams that get a new row at the launch's output level; a stream that gets none is left out)
+        EncTab tab;
+        struct ConvStep { size_t sin, sout, hist, copy; int n = 0, maxT = 0, n_copy = 0; int64_t copy_floats = 0; const float* in; float* out; const float* res; };
+        std::vector<ConvStep> steps(plan.convs.size());
+        auto plan_conv = [&](size_t ci, const float* in, float* out, const float* res) {
+            const EncConvPlan& p = plan.convs[ci];
+            ConvStep& st = steps[ci];
+            st.in = in; st.out = out; st.res = res;
+            std::vector<EncSpan> si, so; std::vector<EncHist> hs; std::vector<EncCarryCopy> cp;
+            for (int i = 0; i < n; ++i) {
+                const int c_in = newr(i, p.lin);
+                float* ring = stream_of(i).buf + p.off;
+                if (newr(i, p.lout) >= 1) {
+                    si.push_back(spans[(size_t)p.lin * n + i]); so.push_back(spans[(size_t)p.lout * n + i]);
+                    EncHist h;
+                    h.carry = ring; h.n_in = (int32_t)before(i, p.lin); h.shift = (int32_t)(before(i, p.lout) * p.stride - before(i, p.lin)); h.cap = p.cap;
+                    hs.push_back(h);
+                    st.maxT = std::max(st.maxT, newr(i, p.lout));
+                }
+                if (c_in >= 1 && p.cap >= 1) {
+                    EncCarryCopy q;
+                    q.rows = std::min(c_in, p.cap); q.width = p.w->cin; q.src_ld = p.w->cin; q.cap = p.cap;
+                    q.src = in + ((size_t)spans[(size_t)p.lin * n + i].off + (size_t)(c_in - q.rows)) * p.w->cin;
+                    q.dst = ring; q.slot0 = (int32_t)((before(i, p.lin) + c_in - q.rows) % p.cap);
+                    cp.push_back(q);
+                    st.copy_floats = std::max<int64_t>(st.copy_floats, (int64_t)q.rows * q.width);
+                }
+            }
+            st.n = (int)hs.size(); st.n_copy = (int)cp.size();
+            st.sin = tab.add(si); st.sout = tab.add(so); st.hist = tab.add(hs); st.copy = tab.add(cp);
+        };
+        {
+            float *X = b.X, *Y = b.Y; size_t ci = 0;
+            plan_conv(ci++, b.x24, X, nullptr);
+            for (int s = 0; s < nr; ++s) {
+                plan_conv(ci++, X, b.M, nullptr);
+                plan_conv(ci++, b.M, X, X);
+                plan_conv(ci++, X, Y, nullptr);
+                std::swap(X, Y);
+            }
+            plan_conv(ci++, X, b.tf.x, nullptr);
+            plan_conv(ci++, b.tf.x, b.lat, nullptr);
+        }
+        std::vector<EncSpan> tf_spans; int tf_maxT = 0;
+        std::vector<size_t> tf_hist, tf_copy; int tf_n_copy = 0; int64_t tf_copy_floats = 0;
+        for (int i = 0; i < n; ++i) if (newr(i, nr) >= 1) { tf_spans.push_back(spans[(size_t)nr * n + i]); tf_maxT = std::max(tf_maxT, newr(i, nr)); }
+        const size_t tf_span_off = tab.add(tf_spans);
+        for (int l = 0; l < c.enc_layers; ++l) {
+            std::vector<EncHist> hs; std::vector<EncCarryCopy> cp;
+            for (int i = 0; i < n; ++i) {
+                const int rows = newr(i, nr);
+                if (rows < 1) continue;
+                float* ring = stream_of(i).buf + plan.kv_off[(size_t)l];
+                EncHist h; h.carry = ring; h.n_in = (int32_t)before(i, nr); h.cap = plan.kv_cap;
+                hs.push_back(h);
+                if (plan.kv_cap >= 1) {
+                    EncCarryCopy q;
+                    q.rows = std::min(rows, plan.kv_cap); q.width = 2 * AO; q.src_ld = 3 * AO; q.cap = plan.kv_cap;
+                    q.src = b.tf.qkv + ((size_t)spans[(size_t)nr * n + i].off + (size_t)(rows - q.rows)) * 3 * AO + AO;
+                    q.dst = ring; q.slot0 = (int32_t)((before(i, nr) + rows - q.rows) % plan.kv_cap);
+                    cp.push_back(q);
+                    tf_copy_floats = std::max<int64_t>(tf_copy_floats, (int64_t)q.rows * q.width);
+                }
+            }
+            tf_n_copy = (int)cp.size();
+            tf_hist.push_back(tab.add(hs)); tf_copy.push_back(tab.add(cp));
+        }
+        if (tab.h.size() > tab_cap) throw Error("audio stream push: descriptor tables larger than planned");
+
+        // pass 2: one upload of the tables, the samples, then the launches
+        Q3_HIP_CHECK(hipEventRecord(ev0, stream));
+        if (!tab.h.empty()) Q3_HIP_CHECK(hipMemcpyAsync(b.tab, tab.h.data(), tab.h.size(), hipMemcpyHostToDevice, stream));
+        for (int i = 0; i < n; ++i)
+            if (n_samples[g0 + i] > 0)
+                Q3_HIP_CHECK(hipMemcpyAsync(b.x24 + spans[(size_t)i].off, pcm[g0 + i], (size_t)n_samples[g0 + i] * sizeof(float), hipMemcpyHostToDevice, stream));
+        for (size_t ci = 0; ci < steps.size(); ++ci) {
+            const EncConvPlan& p = plan.convs[ci];
+            const ConvStep& st = steps[ci];
+            if (ci + 1 == steps.size() && !tf_spans.empty()) {   // the transformer sits between conv_out and the downsample conv
+                EncTfCarry tc;
+                for (int l = 0; l < c.enc_layers; ++l) { tc.hist.push_back((const EncHist*)(b.tab + tf_hist[(size_t)l])); tc.copy.push_back((const EncCarryCopy*)(b.tab + tf_copy[(size_t)l])); }
+                tc.n_copy = tf_n_copy; tc.max_floats = tf_copy_floats;
+                enc_run_transformer(*this, b.tf, (const EncSpan*)(b.tab + tf_span_off), (int)tf_spans.size(), (int)R, tf_maxT, &tc);
+            }
+            if (st.n > 0) {
+                EncConvArgs q;
+                q.in = st.in; q.out = st.out; q.W = p.w->w; q.bias = p.w->b; q.res = st.res;
+                q.Cin = p.w->cin; q.Cout = p.w->cout; q.taps = p.w->k; q.stride = p.stride; q.pad_left = p.w->k - p.stride; q.elu_in = p.elu; q.replicate = p.replicate;
+                q.sin = (const EncSpan*)(b.tab + st.sin); q.sout = (const EncSpan*)(b.tab + st.sout); q.n_clips = st.n; q.max_T_out = st.maxT;
+                launch_enc_conv_hist(q, (const EncHist*)(b.tab + st.hist), stream);
+            }
+            if (st.n_copy > 0) launch_enc_carry_copy((const EncCarryCopy*)(b.tab + st.copy), st.n_copy, st.copy_floats, stream);
+        }
+        if (F > 0) launch_rvq_encode(b.lat, (int)F, EH, enc->proj_sem, enc->proj_ac, enc->books, G, c.enc_codebook, c.enc_vq_dim, b.codes, stream);
+        Q3_HIP_CHECK(hipEventRecord(ev1, stream));
+
+        std::vector<int32_t> codes_h(F * G);
+        if (F > 0) Q3_HIP_CHECK(hipMemcpyAsync(codes_h.data(), b.codes, codes_h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        for (int i = 0; i < n; ++i) {
+            const EncSpan sp = spans[(size_t)(nr + 1) * n + i];
+            if (sp.T > 0 && latents_out && latents_out[g0 + i])
+                Q3_HIP_CHECK(hipMemcpyAsync(latents_out[g0 + i], b.lat + (size_t)sp.off * EH, (size_t)sp.T * EH * sizeof(float), hipMemcpyDeviceToHost, stream));
+        }
+        sync();
+        { float ms = 0.f; if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) last_audio_encode_ms += ms; }
+        for (int i = 0; i < n; ++i) {
+            const EncSpan sp = spans[(size_t)(nr + 1) * n + i];
+            n_frames[g0 + i] = sp.T;
+            if (codes_out && codes_out[g0 + i])
+                for (size_t k = 0; k < (size_t)sp.T * G; ++k) codes_out[g0 + i][k] = codes_h[(size_t)sp.off * G + k];
+        }
+        for (int i = 0; i < n; ++i) {   // the group's streams move
+            EncStream& st = stream_of(i);
+            for (int l = 0; l < NL; ++l) st.rows[l] = after[(size_t)(g0 + i) * 8 + l];
+            if (finish && finish[g0 + i]) st.finished = true;
         }
         g0 = g1;
     }

@@ -5,6 +5,9 @@
 // (EncSpan tables) and stays inside it, so a clip's arithmetic does not depend on what else is in the batch.
 #include <limits.h>
 
+#include <algorithm>
+#include <cstdint>
+
 #include "q3_common.h"
 
 namespace q3 {
@@ -27,10 +30,29 @@ static __device__ __forceinline__ float enc_gelu(float v) { return 0.5f * v * (1
 #define ET_K 32
 #define ET_LD 33   // padded LDS row: ds_read_b32 of a column is conflict-free
 
-__global__ __launch_bounds__(256) void k_enc_conv_mfma(EncConvArgs a) {
+// HIST (streamed pushes): the span is one stream's new rows; an input row before the chunk comes from the stream's
+// carry ring (EncHist), resolved per staged row.  The K walk, the MFMA order, the epilogue and every guard are the one-shot's, so an
+// output has the bits the one-shot gives it.  HIST = false compiles to the kernel as it was.
+// Row `src` (chunk-local, already shifted) of a stream's input: chunk row, carry-ring row, or nullptr (a zero row).  Every returned
+// pointer is inside the chunk's T rows or the ring's cap rows whatever the table holds.
+static __device__ __forceinline__ const float* enc_hist_row(const EncHist& hs, const float* in, int T, int src, int replicate, int Cin) {
+    if (replicate && src > T - 1) src = T - 1;       // finishing push: the last row repeated
+    if (src >= T) return nullptr;                    // finishing push: zeros complete the last output
+    int abs_row = hs.n_in + src;
+    if (replicate && abs_row < 0) abs_row = 0;       // the stream's first row repeated
+    if (abs_row < 0) return nullptr;
+    if (abs_row >= hs.n_in) return in + (size_t)(abs_row - hs.n_in) * Cin;
+    if (hs.cap < 1 || hs.n_in - abs_row > hs.cap) return nullptr;
+    return hs.carry + (size_t)(abs_row % hs.cap) * Cin;
+}
+
+template <bool HIST>
+static __device__ __forceinline__ void enc_conv_mfma_body(const EncConvArgs& a, const EncHist* hist) {
     __shared__ float As[ET_M][ET_LD];
     __shared__ float Bs[ET_N][ET_LD];
     const EncSpan si = a.sin[blockIdx.z], so = a.sout[blockIdx.z];
+    EncHist hs;
+    if constexpr (HIST) hs = hist[blockIdx.z];
     const int t0 = blockIdx.x * ET_M, co0 = blockIdx.y * ET_N;
     if (t0 >= so.T) return;   // whole workgroup: no barrier has been passed
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -53,11 +75,17 @@ __global__ __launch_bounds__(256) void k_enc_conv_mfma(EncConvArgs a) {
                 const int t = t0 + r;
                 int src = t * a.stride - a.pad_left + tap * a.dil;
                 bool ok = t < so.T;
-                if (a.replicate) src = src < 0 ? 0 : (src > si.T - 1 ? si.T - 1 : src);
-                else ok = ok && src >= 0 && src < si.T;
+                const float* prow = nullptr;
+                if constexpr (HIST) {
+                    if (ok) prow = enc_hist_row(hs, in, si.T, src + hs.shift, a.replicate, a.Cin);
+                    ok = prow != nullptr;
+                } else {
+                    if (a.replicate) src = src < 0 ? 0 : (src > si.T - 1 ? si.T - 1 : src);
+                    else ok = ok && src >= 0 && src < si.T;
+                }
                 float v[4] = { 0.f, 0.f, 0.f, 0.f };
                 if (ok) {
-                    const float* p = in + (size_t)src * a.Cin + ci;
+                    const float* p = (HIST ? prow : in + (size_t)src * a.Cin) + ci;
                     if (vec) {
                         if (ci < a.Cin) { const float4 q = *reinterpret_cast<const float4*>(p); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
                     } else {
@@ -112,10 +140,13 @@ __global__ __launch_bounds__(256) void k_enc_conv_mfma(EncConvArgs a) {
         a.out[o] = v;
     }
 }
+__global__ __launch_bounds__(256) void k_enc_conv_mfma(EncConvArgs a) { enc_conv_mfma_body<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void k_enc_conv_mfma_hist(EncConvArgs a, const EncHist* hist) { enc_conv_mfma_body<true>(a, hist); }
 
 // The 1-channel first conv (24 kHz samples -> enc_filters channels): VALU work, 64 output rows per workgroup, the clip's samples of
 // the tile's window in LDS.  Window = 63 * stride + (taps - 1) * dil + 1 <= 1024 samples (launch_enc_conv checks).
-__global__ __launch_bounds__(256) void k_enc_conv_c1(EncConvArgs a) {
+template <bool HIST>
+static __device__ __forceinline__ void enc_conv_c1_body(const EncConvArgs& a, const EncHist* hist) {
     __shared__ float xs[1024];
     const EncSpan si = a.sin[blockIdx.z], so = a.sout[blockIdx.z];
     const int t0 = blockIdx.x * 64;
@@ -125,8 +156,14 @@ __global__ __launch_bounds__(256) void k_enc_conv_c1(EncConvArgs a) {
     for (int i = threadIdx.x; i < win; i += 256) {
         int src = base + i;
         float v = 0.f;
-        if (a.replicate) src = src < 0 ? 0 : (src > si.T - 1 ? si.T - 1 : src);
-        if (src >= 0 && src < si.T) v = a.in[(size_t)si.off + src];
+        if constexpr (HIST) {
+            const EncHist hs = hist[blockIdx.z];
+            const float* p = enc_hist_row(hs, a.in + (size_t)si.off, si.T, src + hs.shift, a.replicate, 1);
+            if (p) v = *p;
+        } else {
+            if (a.replicate) src = src < 0 ? 0 : (src > si.T - 1 ? si.T - 1 : src);
+            if (src >= 0 && src < si.T) v = a.in[(size_t)si.off + src];
+        }
         xs[i] = a.elu_in ? enc_elu(v) : v;
     }
     __syncthreads();
@@ -143,21 +180,30 @@ __global__ __launch_bounds__(256) void k_enc_conv_c1(EncConvArgs a) {
         a.out[o] = v;
     }
 }
+__global__ __launch_bounds__(256) void k_enc_conv_c1(EncConvArgs a) { enc_conv_c1_body<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void k_enc_conv_c1_hist(EncConvArgs a, const EncHist* hist) { enc_conv_c1_body<true>(a, hist); }
 
-void launch_enc_conv(const EncConvArgs& a, hipStream_t s) {
+static void enc_launch_conv(const EncConvArgs& a, const EncHist* hist, hipStream_t s) {
     if (!a.in || !a.out || !a.W || !a.sin || !a.sout) throw Error("encoder conv: NULL argument");
     if (a.n_clips < 1 || a.n_clips > 65535 || a.max_T_out < 1) throw Error("encoder conv: 1..65535 clips with at least one output row");
     if (a.Cin < 1 || a.Cout < 1 || a.taps < 1 || a.dil < 1 || a.stride < 1) throw Error("encoder conv: bad shape");
     const int tiles = (a.max_T_out + 63) / 64;
     if (a.Cin == 1) {
         if (63 * a.stride + (a.taps - 1) * a.dil + 1 > 1024) throw Error("encoder conv: the 1-channel kernel covers windows of up to 1024 samples");
-        hipLaunchKernelGGL(k_enc_conv_c1, dim3(tiles, 1, a.n_clips), dim3(256), 0, s, a);
+        if (hist) hipLaunchKernelGGL(k_enc_conv_c1_hist, dim3(tiles, 1, a.n_clips), dim3(256), 0, s, a, hist);
+        else hipLaunchKernelGGL(k_enc_conv_c1, dim3(tiles, 1, a.n_clips), dim3(256), 0, s, a);
     } else {
         const int ny = (a.Cout + ET_N - 1) / ET_N;
         if (ny > 65535) throw Error("encoder conv: too many output channels");
-        hipLaunchKernelGGL(k_enc_conv_mfma, dim3(tiles, ny, a.n_clips), dim3(256), 0, s, a);
+        if (hist) hipLaunchKernelGGL(k_enc_conv_mfma_hist, dim3(tiles, ny, a.n_clips), dim3(256), 0, s, a, hist);
+        else hipLaunchKernelGGL(k_enc_conv_mfma, dim3(tiles, ny, a.n_clips), dim3(256), 0, s, a);
     }
     Q3_HIP_CHECK(hipGetLastError());
+}
+void launch_enc_conv(const EncConvArgs& a, hipStream_t s) { enc_launch_conv(a, nullptr, s); }
+void launch_enc_conv_hist(const EncConvArgs& a, const EncHist* hist, hipStream_t s) {
+    if (!hist) throw Error("encoder conv: NULL history table");
+    enc_launch_conv(a, hist, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -194,24 +240,36 @@ void launch_enc_layernorm(const float* x, const float* w, const float* b, float 
 }
 
 // rotate-half RoPE on the q and k thirds of qkv rows, position = row index inside the clip (tables made in double on the host)
-__global__ __launch_bounds__(256) void k_enc_rope(float* qkv, const float* cs, const float* sn, int max_pos, int heads, int d, const EncSpan* spans) {
+template <bool HIST>
+static __device__ __forceinline__ void enc_rope_body(float* qkv, const float* cs, const float* sn, int max_pos, int heads, int d, const EncSpan* spans, const EncHist* hist) {
     const EncSpan sp = spans[blockIdx.y];
     const int half = d >> 1, per_row = 2 * heads * half;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)sp.T * per_row) return;
     const int t = (int)(i / per_row), r = (int)(i - (int64_t)t * per_row);
     const int which = r / (heads * half), hh = (r - which * heads * half) / half, j = r % half;
-    const int pos = t < max_pos ? t : max_pos - 1;   // the host refuses clips longer than the tables
+    int pos = t;
+    if constexpr (HIST) pos += hist[blockIdx.y].n_in;   // the row's absolute index in its stream
+    pos = pos < max_pos ? pos : max_pos - 1;            // the host refuses clips (and sizes streams) so that nothing reaches this
     float* p = qkv + (size_t)(sp.off + t) * (3 * heads * d) + (size_t)which * heads * d + (size_t)hh * d;
     const float c = cs[(size_t)pos * half + j], sv = sn[(size_t)pos * half + j];
     const float x1 = p[j], x2 = p[j + half];
     p[j] = x1 * c - x2 * sv;
     p[j + half] = x2 * c + x1 * sv;
 }
-void launch_enc_rope(float* qkv, const float* cs, const float* sn, int max_pos, int heads, int d, const EncSpan* spans, int n_clips, int max_T, hipStream_t s) {
+__global__ __launch_bounds__(256) void k_enc_rope(float* qkv, const float* cs, const float* sn, int max_pos, int heads, int d, const EncSpan* spans) {
+    enc_rope_body<false>(qkv, cs, sn, max_pos, heads, d, spans, nullptr);
+}
+__global__ __launch_bounds__(256) void k_enc_rope_hist(float* qkv, const float* cs, const float* sn, int max_pos, int heads, int d, const EncSpan* spans, const EncHist* hist) {
+    enc_rope_body<true>(qkv, cs, sn, max_pos, heads, d, spans, hist);
+}
+void launch_enc_rope(float* qkv, const float* cs, const float* sn, int max_pos, int heads, int d, const EncSpan* spans, int n_clips, int max_T, hipStream_t s,
+                     const EncHist* hist) {
     if (n_clips < 1 || n_clips > 65535 || max_T < 1 || max_pos < 1) throw Error("encoder rope: bad shape");
     const int64_t per_clip = (int64_t)max_T * heads * d;
-    hipLaunchKernelGGL(k_enc_rope, dim3((unsigned)((per_clip + 255) / 256), n_clips), dim3(256), 0, s, qkv, cs, sn, max_pos, heads, d, spans);
+    const dim3 grid((unsigned)((per_clip + 255) / 256), n_clips);
+    if (hist) hipLaunchKernelGGL(k_enc_rope_hist, grid, dim3(256), 0, s, qkv, cs, sn, max_pos, heads, d, spans, hist);
+    else hipLaunchKernelGGL(k_enc_rope, grid, dim3(256), 0, s, qkv, cs, sn, max_pos, heads, d, spans);
     Q3_HIP_CHECK(hipGetLastError());
 }
 
@@ -221,7 +279,12 @@ void launch_enc_rope(float* qkv, const float* cs, const float* sn, int max_pos, 
 // and d <= 128 (launch check); every load is inside the clip's rows by construction (j0 >= 0, j0 + n - 1 = t < T).
 // ------------------------------------------------------------------------------------------------
 #define EA_WMAX 1024
-__global__ __launch_bounds__(256) void k_enc_attn(const float* qkv, float* out, int heads, int d, int window, float scale, const EncSpan* spans) {
+// HIST (streamed pushes): row t of the chunk is absolute row P + t of its stream; a key before the chunk comes from the layer's
+// K/V ring ([window - 1][2 AO]: rotated K, then V; absolute row r in slot r mod (window - 1)).  The lane <-> jj mapping, the per-lane
+// running sums, wave_sum and the sequential jj loop of P.V are the one-shot's, so the sums come out in the same order.  Ring rows read
+// are absolute rows [P - (window - 1), P) that exist (>= 0): slots < window - 1 by the modulo.
+template <bool HIST>
+static __device__ __forceinline__ void enc_attn_body(const float* qkv, float* out, int heads, int d, int window, float scale, const EncSpan* spans, const EncHist* hist) {
     __shared__ float sc[4][EA_WMAX];
     __shared__ float qs[4][128];
     const EncSpan sp = spans[blockIdx.y];
@@ -230,13 +293,19 @@ __global__ __launch_bounds__(256) void k_enc_attn(const float* qkv, float* out, 
     const int t = (int)(task / heads), h = (int)(task % heads);
     const bool valid = t < sp.T;
     const int AO = heads * d, ld = 3 * AO;
-    const int j0 = valid ? (t - window + 1 > 0 ? t - window + 1 : 0) : 0, n = valid ? t - j0 + 1 : 0;
-    const float* base = qkv + (size_t)sp.off * ld;
+    int P = 0; const float* ring = nullptr; const int cap = window - 1;
+    if constexpr (HIST) { P = hist[blockIdx.y].n_in; ring = hist[blockIdx.y].carry; }
+    const int pa = P + t;   // absolute row; j0 is absolute too
+    const int j0 = valid ? (pa - window + 1 > 0 ? pa - window + 1 : 0) : 0, n = valid ? pa - j0 + 1 : 0;
+    const float* base = qkv + (size_t)sp.off * ld;   // the chunk's row 0 (absolute row P): indexed by r - P for absolute rows r >= P
     if (valid) for (int i = lane; i < d; i += 64) qs[wave][i] = base[(size_t)t * ld + (size_t)h * d + i];
     __syncthreads();
     float m = -INFINITY;
     for (int jj = lane; jj < n; jj += 64) {
-        const float* kr = base + (size_t)(j0 + jj) * ld + AO + (size_t)h * d;
+        const int r = j0 + jj;
+        const float* kr;
+        if (HIST && r < P) kr = ring + (size_t)(r % cap) * (2 * AO) + (size_t)h * d;
+        else kr = base + (size_t)(r - P) * ld + AO + (size_t)h * d;
         float s = 0.f;
         for (int i = 0; i < d; i += 2) { const float2 kv = *reinterpret_cast<const float2*>(kr + i); s += qs[wave][i] * kv.x; s += qs[wave][i + 1] * kv.y; }
         s *= scale;
@@ -249,18 +318,64 @@ __global__ __launch_bounds__(256) void k_enc_attn(const float* qkv, float* out, 
     l = wave_sum(l);
     __syncthreads();
     if (!valid) return;
+    const int n_ring = HIST ? (P - j0 > 0 ? (P - j0 < n ? P - j0 : n) : 0) : 0;   // the first n_ring keys lie before the chunk
     for (int i = lane; i < d; i += 64) {
-        const float* vr = base + (size_t)j0 * ld + 2 * AO + (size_t)h * d + i;
         float acc = 0.f;
-        for (int jj = 0; jj < n; ++jj) acc += sc[wave][jj] * vr[(size_t)jj * ld];
+        if constexpr (HIST) {
+            if (n_ring > 0) {
+                int slot = j0 % cap;
+                for (int jj = 0; jj < n_ring; ++jj) {
+                    acc += sc[wave][jj] * ring[(size_t)slot * (2 * AO) + AO + (size_t)h * d + i];
+                    if (++slot == cap) slot = 0;
+                }
+            }
+        }
+        const float* vr = base + (size_t)(j0 + n_ring - P) * ld + 2 * AO + (size_t)h * d + i;
+        for (int jj = n_ring; jj < n; ++jj) acc += sc[wave][jj] * vr[(size_t)(jj - n_ring) * ld];
         out[(size_t)(sp.off + t) * AO + (size_t)h * d + i] = acc / l;
     }
 }
-void launch_enc_attn(const float* qkv, float* out, int heads, int d, int window, float scale, const EncSpan* spans, int n_clips, int max_T, hipStream_t s) {
+__global__ __launch_bounds__(256) void k_enc_attn(const float* qkv, float* out, int heads, int d, int window, float scale, const EncSpan* spans) {
+    enc_attn_body<false>(qkv, out, heads, d, window, scale, spans, nullptr);
+}
+__global__ __launch_bounds__(256) void k_enc_attn_hist(const float* qkv, float* out, int heads, int d, int window, float scale, const EncSpan* spans, const EncHist* hist) {
+    enc_attn_body<true>(qkv, out, heads, d, window, scale, spans, hist);
+}
+void launch_enc_attn(const float* qkv, float* out, int heads, int d, int window, float scale, const EncSpan* spans, int n_clips, int max_T, hipStream_t s,
+                     const EncHist* hist) {
     if (n_clips < 1 || n_clips > 65535 || max_T < 1 || heads < 1) throw Error("encoder attention: bad shape");
     if (window < 1 || window > EA_WMAX || d < 2 || d > 128 || (d & 1)) throw Error("encoder attention: built for windows of up to 1024 rows and even head dims of up to 128");
     const int64_t tasks = (int64_t)max_T * heads;
-    hipLaunchKernelGGL(k_enc_attn, dim3((unsigned)((tasks + 3) / 4), n_clips), dim3(256), 0, s, qkv, out, heads, d, window, scale, spans);
+    const dim3 grid((unsigned)((tasks + 3) / 4), n_clips);
+    if (hist) hipLaunchKernelGGL(k_enc_attn_hist, grid, dim3(256), 0, s, qkv, out, heads, d, window, scale, spans, hist);
+    else hipLaunchKernelGGL(k_enc_attn, grid, dim3(256), 0, s, qkv, out, heads, d, window, scale, spans);
+    Q3_HIP_CHECK(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_enc_carry_copy — a push's rows into the streams' carry rings, every stream of the push in one launch (blockIdx.y = table entry).
+// Row i < rows of src (row stride src_ld floats) goes to ring slot (slot0 + i) mod cap, `width` floats.  The host passes at most cap
+// rows per entry (the launcher's table is the host's; the kernel clamps rows to cap all the same), so no two rows of an entry share a
+// slot, and a ring is only ever written from workspace rows: nothing moves inside a ring, whatever the push's size.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_enc_carry_copy(const EncCarryCopy* tab) {
+    const EncCarryCopy c = tab[blockIdx.y];
+    if (c.cap < 1 || c.width < 1) return;
+    const int rows = c.rows < c.cap ? c.rows : c.cap;
+    const bool vec = !((c.width | c.src_ld) & 3) && !(((uintptr_t)c.src | (uintptr_t)c.dst) & 15);
+    const int per_row = vec ? c.width >> 2 : c.width;
+    const int64_t total = (int64_t)rows * per_row;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int r = (int)(i / per_row), e = (int)(i - (int64_t)r * per_row);
+        const int slot = (int)(((int64_t)c.slot0 + r) % c.cap);
+        if (vec) reinterpret_cast<float4*>(c.dst + (size_t)slot * c.width)[e] = reinterpret_cast<const float4*>(c.src + (size_t)r * c.src_ld)[e];
+        else c.dst[(size_t)slot * c.width + e] = c.src[(size_t)r * c.src_ld + e];
+    }
+}
+void launch_enc_carry_copy(const EncCarryCopy* tab, int n, int64_t max_floats, hipStream_t s) {
+    if (!tab || n < 1 || n > 65535 || max_floats < 1) throw Error("encoder carry copy: bad table");
+    const int64_t blocks = std::min<int64_t>((max_floats / 4 + 255) / 256 + 1, 1024);
+    hipLaunchKernelGGL(k_enc_carry_copy, dim3((unsigned)blocks, n), dim3(256), 0, s, tab);
     Q3_HIP_CHECK(hipGetLastError());
 }
 

@@ -344,8 +344,20 @@ public:
     // depend on the rest of the batch.  Validates everything before the first byte moves.
     void audio_encode(int n_clips, const float* const* pcm, const int64_t* n_samples, const int32_t* rates, int64_t* const* codes_out,
                       float* const* latents_out, const int32_t* caps, int32_t* n_frames);
-    float last_audio_encode_ms = 0.f;                         // device time of the last audio_encode call: uploads + launches of all its groups
+    float last_audio_encode_ms = 0.f;                         // device time of the last audio_encode / audio_stream_push_batch call: uploads + launches of all its groups
     void enc_transformer_host(const float* rows, int n_rows, float* out);   // parity aid: the transformer alone
+    // ---- streamed audio -> codes: carried-state pushes, bit-identical to audio_encode of the concatenated audio ----
+    static constexpr int64_t kEncMaxStreamSamples = 86400000; // one hour at 24 kHz: a stream's max_samples
+    static constexpr int kEncMaxStreams = 1024;               // open at the same time
+    int audio_stream_begin(int64_t max_samples);              // 0: kEncMaxClipSamples.  Regrows the RoPE tables when the stream can have more rows (syncs)
+    int64_t audio_stream_push_len(int id, int64_t n_samples, bool finish) const;   // host-only: frames that push would return
+    // n streams (distinct, open, not finished), each given n_samples[i] >= 0 more samples at 24 kHz (finish[i]: the stream's last
+    // push, right edge as the one-shot's) -> the NEW frames' codes [frames][n_groups] / latents [frames][enc_hidden].  Everything is
+    // validated before any stream moves; one set of launches per group of streams whatever their number.
+    void audio_stream_push_batch(int n, const int32_t* ids, const float* const* pcm, const int64_t* n_samples, const int32_t* finish,
+                                 int64_t* const* codes_out, float* const* latents_out, const int32_t* caps, int32_t* n_frames);
+    void audio_stream_info(int id, int64_t* n_samples, int32_t* n_frames, int* finished, int64_t* bytes) const;
+    void audio_stream_end(int id);                            // the stream's buffers stay for the next begin; freed in encoder_free
     void enc_calibrate_synthetic(uint64_t seed);              // fill_synthetic: codebooks at the scale of the projected latents
 
     // ---- internals ----

@@ -300,6 +300,33 @@ std::vector<int64_t> TTSEngine::encode_audio(const std::vector<float>& pcm, int 
     return codes;
 }
 
+int TTSEngine::audio_stream_begin(int64_t max_samples) {
+    if (!ready_) return -1;
+    int id = -1;
+    if (q3tts_audio_stream_begin(h_, max_samples, &id) != 0) { std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl; return -1; }
+    return id;
+}
+
+std::vector<int64_t> TTSEngine::audio_stream_push(int id, const float* pcm, size_t n, bool finish, bool* ok) {
+    if (ok) *ok = false;
+    if (!ready_) return {};
+    const int frames = q3tts_audio_stream_push_len(h_, id, (int64_t)n, finish ? 1 : 0);
+    if (frames < 0) { std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl; return {}; }
+    std::vector<int64_t> codes((size_t)std::max(frames, 1) * (size_t)n_groups_);
+    int32_t got = 0;
+    if (q3tts_audio_stream_push_host(h_, id, pcm, (int64_t)n, finish ? 1 : 0, codes.data(), std::max(frames, 1), &got) != 0) {
+        std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl;
+        return {};
+    }
+    codes.resize((size_t)got * (size_t)n_groups_);
+    if (ok) *ok = true;
+    return codes;
+}
+
+void TTSEngine::audio_stream_end(int id) {
+    if (ready_ && q3tts_audio_stream_end(h_, id) != 0) std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl;
+}
+
 static bool read_wav_file(const std::string& path, std::vector<float>& pcm, int32_t& rate) {
     int64_t n = 0;
     if (q3tts_read_wav_host(path.c_str(), nullptr, 0, &n, &rate) != 0 || n < 1) { std::cerr << "[TTSEngine] Failed to read audio: " << path << std::endl; return false; }

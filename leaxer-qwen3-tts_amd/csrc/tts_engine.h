@@ -143,6 +143,14 @@ public:
     // methods): mono samples at sample_rate -> frames of n_groups() ids, frame-major — what synthesize_tokens_continue takes.  Empty on error.
     std::vector<int64_t> encode_audio(const std::vector<float>& pcm, int sample_rate);
     std::vector<int64_t> encode_audio(const std::string& wav_path);
+    // Audio -> codes while the audio arrives (include/q3tts.h: q3tts_audio_stream_begin / _push_host / _end; [HINT] as encode_audio):
+    // a stream takes mono samples at 24 kHz in pushes of any size (at most 60 s each) and returns the frames each push completes;
+    // the concatenation is bit-identical to encode_audio of the concatenated samples.  max_samples: the most the stream will take
+    // (0: 60 s; at most one hour).  audio_stream_begin returns the stream id, -1 on error; a failed push returns no frames and sets
+    // *ok = false when ok is given.
+    int audio_stream_begin(int64_t max_samples = 0);
+    std::vector<int64_t> audio_stream_push(int id, const float* pcm, size_t n, bool finish = false, bool* ok = nullptr);
+    void audio_stream_end(int id);
     // In-context voice clone ([HINT]): the reference audio is encoded, the text becomes reference text +
     // target text (ref_text_ids go between token_ids' three role ids and its text) and the utterance is continued behind the
     // reference's codes; the returned samples are the target's only.  Exactly encode_audio + synthesize_tokens_continue.

@@ -110,6 +110,8 @@ EXPORTS = [
     "q3tts_slot_text_open", "q3tts_slot_text_append_host", "q3tts_slots_text_append_ids", "q3tts_slot_text_status",
     "q3tts_build_prompt_open_host", "q3tts_synthesize_live_host",
     "q3tts_config_enable_audio_encoder", "q3tts_has_audio_encoder", "q3tts_audio_encode_len", "q3tts_audio_encode_host",
+    "q3tts_audio_stream_begin", "q3tts_audio_stream_push_len", "q3tts_audio_stream_push_host", "q3tts_audio_stream_push_batch_host",
+    "q3tts_audio_stream_info", "q3tts_audio_stream_end",
     "q3tts_audio_encode_batch_host", "q3tts_audio_encode_latents_host", "q3tts_audio_encode_batch_latents_host", "q3tts_last_audio_encode_ms", "q3tts_test_audio_encoder_transformer_host",
     "q3tts_codec_stream_prime_batch_host", "q3tts_slots_codec_prime", "q3tts_codec_stream_info", "q3tts_synthesize_continue_stream_host",
 ]
@@ -230,6 +232,12 @@ def lib():
     L.q3tts_audio_encode_batch_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.q3tts_audio_encode_batch_latents_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.q3tts_last_audio_encode_ms.argtypes = [vp, C.POINTER(f32)]
+    L.q3tts_audio_stream_begin.argtypes = [vp, i64, C.POINTER(C.c_int)]
+    L.q3tts_audio_stream_push_len.argtypes = [vp, i32, i64, i32]
+    L.q3tts_audio_stream_push_host.argtypes = [vp, i32, vp, i64, i32, vp, i32, C.POINTER(C.c_int32)]
+    L.q3tts_audio_stream_push_batch_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.q3tts_audio_stream_info.argtypes = [vp, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+    L.q3tts_audio_stream_end.argtypes = [vp, i32]
     L.q3tts_audio_encode_latents_host.argtypes = [vp, vp, i64, vp, vp, i32, C.POINTER(C.c_int32)]
     L.q3tts_test_audio_encoder_transformer_host.argtypes = [vp, vp, i32, vp]
     L.q3tts_codec_decode_chunked_host.argtypes = [vp, vp, i32, i32, i32, vp, i64, C.POINTER(i64)]
@@ -890,6 +898,93 @@ class Engine:
         self._ck(self.L.q3tts_audio_encode_batch_latents_host(*args, lptrs, _p(cp) if n else None, _p(nf)))
         return [o[: nf[i]] for i, o in enumerate(outs)], [a[: nf[i]] for i, a in enumerate(lats)]
 
+    # ---- audio -> codes while the audio arrives (q3tts_audio_stream_*) ----
+    def audio_stream_begin(self, max_samples=0):
+        """a new encoder stream for at most max_samples samples at 24 kHz (0: 60 s; at most one hour) -> stream id"""
+        if int(max_samples) < 0:
+            raise ValueError("max_samples must be 0 (60 s) or positive")
+        sid = C.c_int(-1)
+        self._ck(self.L.q3tts_audio_stream_begin(self.h, int(max_samples), C.byref(sid)))
+        return int(sid.value)
+
+    def audio_stream_push_len(self, sid, n_samples, finish=False):
+        """frames the next push of n_samples to this stream would return (host-only)"""
+        if int(n_samples) < 0:
+            raise ValueError("n_samples must not be negative")
+        return int(self._ck(self.L.q3tts_audio_stream_push_len(self.h, int(sid), int(n_samples), 1 if finish else 0)))
+
+    @staticmethod
+    def _stream_pcm(pcm, what="pcm"):
+        a = np.asarray(pcm)
+        if a.size and a.dtype.kind != "f":
+            raise ValueError("%s: expected float samples (mono, 24 kHz), got dtype %s" % (what, a.dtype))
+        if a.ndim > 1 and a.size != max(a.shape):
+            raise ValueError("%s: expected mono samples [n], got shape %s" % (what, (a.shape,)))
+        return np.ascontiguousarray(a, np.float32).reshape(-1)
+
+    def audio_stream_push_batch(self, sids, pcms, finish=None, want_latents=False):
+        """one push to each of many streams in ONE call (q3tts_audio_stream_push_batch_host): pcms[i] are stream sids[i]'s next samples
+        (mono float, 24 kHz; may be empty), finish[i] ends stream i's audio (None: none; a bool applies to all).  Returns the list of
+        the NEW codes [F_i][n_groups] per stream, bit-identical to audio_encode of each stream's concatenated audio; want_latents:
+        (that list, the list of latents [F_i][enc_hidden])."""
+        n = len(sids)
+        if len(pcms) != n:
+            raise ValueError("one sample array per stream")
+        fin = [False] * n if finish is None else ([bool(finish)] * n if np.isscalar(finish) else [bool(f) for f in finish])
+        if len(fin) != n:
+            raise ValueError("finish: one flag per stream, one for all, or None")
+        if len(set(int(s) for s in sids)) != n:
+            raise ValueError("a stream may appear once per push")
+        keep = [Engine._stream_pcm(a, "pcms[%d]" % i) for i, a in enumerate(pcms)]
+        if n == 0:
+            return ([], []) if want_latents else []
+        per = 1
+        for r in list(self.cfg.enc_ratios)[: self.cfg.enc_n_ratios]:
+            per *= int(r)
+        caps = [a.size // (2 * per) + 2 for a in keep]
+        outs = [np.zeros((cp, self.cfg.n_groups), np.int64) for cp in caps]
+        lats = [np.zeros((cp, max(self.cfg.enc_hidden, 1)), np.float32) for cp in caps] if want_latents else None
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data if a.size else None for a in keep])
+        optrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        lptrs = (C.c_void_p * n)(*[a.ctypes.data for a in lats]) if want_latents else None
+        ids = np.array([int(s) for s in sids], np.int32)
+        ns = np.array([a.size for a in keep], np.int64)
+        fl = np.array(fin, np.int32)
+        cp = np.array(caps, np.int32)
+        nf = np.zeros(n, np.int32)
+        self._ck(self.L.q3tts_audio_stream_push_batch_host(self.h, n, _p(ids), ptrs, _p(ns), _p(fl), optrs, lptrs, _p(cp), _p(nf)))
+        codes = [o[: nf[i]] for i, o in enumerate(outs)]
+        return (codes, [a[: nf[i]] for i, a in enumerate(lats)]) if want_latents else codes
+
+    def audio_stream_push(self, sid, pcm, finish=False, want_latents=False):
+        """pcm (mono float, 24 kHz, any length up to 60 s) appended to stream sid -> the NEW frames' codes [F][n_groups];
+        finish: the stream's audio ends here.  want_latents: (codes, latents [F][enc_hidden])"""
+        r = self.audio_stream_push_batch([sid], [pcm], [finish], want_latents)
+        return (r[0][0], r[1][0]) if want_latents else r[0]
+
+    def audio_stream_info(self, sid):
+        """(samples received, frames returned, finished, bytes of device state)"""
+        ns, nf, fin, by = C.c_int64(0), C.c_int32(0), C.c_int(0), C.c_int64(0)
+        self._ck(self.L.q3tts_audio_stream_info(self.h, int(sid), C.byref(ns), C.byref(nf), C.byref(fin), C.byref(by)))
+        return int(ns.value), int(nf.value), bool(fin.value), int(by.value)
+
+    def audio_stream_end(self, sid):
+        self._ck(self.L.q3tts_audio_stream_end(self.h, int(sid)))
+
+    def audio_encode_long(self, pcm24k, chunk_samples=96000):
+        """audio_encode for any length up to one hour: the clip pushed chunk_samples at a time through one stream -> codes
+        [F][n_groups], bit-identical to what audio_encode gives where it accepts the clip"""
+        a = Engine._stream_pcm(pcm24k, "pcm24k")
+        if int(chunk_samples) < 1:
+            raise ValueError("chunk_samples must be at least 1")
+        if a.size < 1:
+            raise ValueError("pcm24k: no samples")
+        with AudioEncodeStream(self, a.size) as st:
+            for i in range(0, a.size, int(chunk_samples)):
+                st.push(a[i : i + int(chunk_samples)])
+            st.finish()
+            return st.codes
+
     def last_audio_encode_ms(self):
         ms = C.c_float(0)
         self._ck(self.L.q3tts_last_audio_encode_ms(self.h, C.byref(ms)))
@@ -1486,3 +1581,46 @@ def load_codes(path):
 
 def rng_uniform(seed, stream, frame, group):
     return float(lib().q3tts_rng_uniform(seed, stream, frame, group))
+
+
+class AudioEncodeStream:
+    """One encoder stream as a context manager: push(pcm) -> the new codes, finish() -> the last ones, .codes: everything so far
+    [F][n_groups].  The concatenation is bit-identical to Engine.audio_encode of the concatenated audio (24 kHz mono float)."""
+
+    def __init__(self, engine, max_samples=0):
+        self.engine = engine
+        self.sid = engine.audio_stream_begin(max_samples)
+        self._parts = []
+        self.finished = False
+
+    def push(self, pcm, finish=False):
+        if self.sid is None:
+            raise RuntimeError("the stream is closed")
+        if self.finished:
+            raise RuntimeError("the stream is finished")
+        codes = self.engine.audio_stream_push(self.sid, pcm, finish)
+        self.finished = bool(finish)
+        if codes.shape[0]:
+            self._parts.append(codes)
+        return codes
+
+    def finish(self):
+        return self.push(np.zeros(0, np.float32), finish=True)
+
+    @property
+    def codes(self):
+        if not self._parts:
+            return np.zeros((0, self.engine.cfg.n_groups), np.int64)
+        return np.concatenate(self._parts, axis=0)
+
+    def close(self):
+        if self.sid is not None:
+            self.engine.audio_stream_end(self.sid)
+            self.sid = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
