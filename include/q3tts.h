@@ -510,6 +510,12 @@ int q3tts_synthesize_prefixed_host(q3tts_engine* e, int n_utt, const int64_t* id
 int q3tts_read_wav_host(const char* path, float* out, int64_t cap, int64_t* n_samples, int32_t* sample_rate);
 /* io::resample (wav_reader.cpp:145-164): linear interpolation; returns the output length */
 int64_t q3tts_resample_host(const float* in, int64_t n, int32_t src_rate, int32_t dst_rate, float* out, int64_t cap);
+/* io::resample over audio that is still arriving: the output samples a stream at src_rate has emitted IN ALL once it holds n_received
+ * samples.  finish != 0: q3tts_resample_host's length.  finish == 0: the largest count whose every output i has both taps received
+ * unclamped, floor(i / ratio) + 1 <= n_received - 1, and lies below (size_t)((double)n_received * ratio), ratio = dst_rate / src_rate
+ * in double: whatever the final length, io::resample produces it.  Equal rates: n_received.  A push's length is the difference of
+ * two calls.  Host-only, no engine; -1 for a rate < 1 or n_received < 0. */
+int64_t q3tts_resample_stream_emitted(int32_t src_rate, int32_t dst_rate, int64_t n_received, int finish);
 /* MelExtractor::extract with the settings of tts_onnx.cpp:347-354 (24 kHz, n_fft = win = 1024, hop 256, 128 HTK
  * mels, 0-12 kHz, log power): mel[128][*frames].  Call with mel == NULL to learn *frames. */
 int q3tts_mel_host(const float* audio, int64_t n, float* mel, int64_t cap, int32_t* frames);
@@ -565,35 +571,62 @@ int q3tts_test_audio_encoder_transformer_host(q3tts_engine* e, const float* rows
 
 /* ---- audio -> codes while the audio arrives: carried-state pushes of many streams ([HINT], as the encoder above; beside the reference's
  * clone front end tts_onnx.cpp:331-365, which has no encoder) ----
- * A stream takes mono float samples at 24 kHz in pushes of any size (another rate is the caller's to resample first: the GPU resampler
- * of q3tts_audio_encode_batch_host serves whole clips only) and returns the codes of the frames each push completes.
- * Promise: the codes (and latents) of a stream, however its samples were cut into pushes and whatever other streams shared its
- * calls, are bit-identical to q3tts_audio_encode_host of the concatenated audio.  After n samples floor(n / samples per frame)
- * frames have been returned; the finishing push returns the 0 or 1 frames the one-shot's right edge completes.
+ * A stream takes mono samples at the source's own rate (1 .. 384 000 Hz) as float or int16, in pushes of any size, and returns the
+ * codes of the frames each push completes.  No caller has to resample first, or convert: a stream that is not 24 kHz float resamples on the GPU
+ * on the way in (io::resample's arithmetic on absolute sample indices; it carries its last ceil(rate / 24000) + 1 samples).
+ * Promise: the codes (and latents) of a stream begun at rate R, however its samples were cut into pushes and whatever streams of
+ * whatever rates and formats shared its calls, are bit-identical to q3tts_audio_encode_batch_host of the concatenated audio at rate
+ * R (q3tts_audio_encode_host at 24 kHz); int16 samples v are the float audio v / 32768.0f, q3tts_read_wav_host's conversion.
+ * An unfinished stream that holds N samples has fed the encoder E = q3tts_resample_stream_emitted(R, 24000, N, 0) samples at 24 kHz:
+ * output i is emitted once (1) both its taps have arrived, floor(i / ratio) + 1 <= N - 1, and (2) i < floor(N * ratio), so that the
+ * one-shot of any longer clip produces it (ratio = 24000.0 / R, in double).  Latency: floor(E / samples per frame) frames have been
+ * returned, at most one 24 kHz sample behind real time (at 24 kHz float E = N: none).  The finishing push emits what
+ * io::resample's clamped right edge adds and returns the 0 or 1 frames the one-shot's right edge completes.
  * State per stream lives in device buffers of its own (per conv k - 1 input rows, per transformer layer window - 1 K and V rows;
  * q3tts_audio_stream_info reports the bytes), kept by q3tts_audio_stream_end for the next begin and freed by q3tts_destroy.
  * At most 1024 streams are open at a time.  q3tts_last_audio_encode_ms covers pushes too. */
 /* A new stream that will take at most max_samples samples (0: 1 440 000 = 60 s; at most 86 400 000 = one hour).  A stream longer than
  * any before it regrows the RoPE tables (the same double-precision formula: existing rows keep their bits) and synchronises for it. */
 int q3tts_audio_stream_begin(q3tts_engine* e, int64_t max_samples, int* stream_id);
+/* The same for a source at sample_rate (1 .. 384 000; anything else is refused with the value) whose samples are float
+ * (Q3TTS_PCM_F32) or int16 (Q3TTS_PCM_S16).  max_samples counts the stream's OWN samples: 0 = 60 s at its rate, at most one hour.
+ * q3tts_audio_stream_begin is this at 24 000 / Q3TTS_PCM_F32. */
+#define Q3TTS_PCM_F32 0
+#define Q3TTS_PCM_S16 1
+int q3tts_audio_stream_begin_rate(q3tts_engine* e, int32_t sample_rate, int format, int64_t max_samples, int* stream_id);
+/* the rate and format a stream was begun with (either pointer may be NULL) */
+int q3tts_audio_stream_format(q3tts_engine* e, int stream_id, int32_t* sample_rate, int* format);
 /* host-only: frames the next push of n_samples (finish 0/1) to this stream would return; -1 when that push would be refused */
 int q3tts_audio_stream_push_len(q3tts_engine* e, int stream_id, int64_t n_samples, int finish);
 /* n_samples >= 0 more samples; finish != 0 ends the stream's audio (zeros / the repeated last row complete the last frame, as in the
  * one-shot).  codes_out[*n_frames][n_groups] int64 in q3tts_audio_encode_host's layout: the NEW frames only.  n_samples == 0 without
- * finish does nothing; finish on a stream that never got a sample returns 0 frames.  A push holds at most 1 440 000 samples. */
+ * finish does nothing; finish on a stream that never got a sample returns 0 frames.  A push holds at most 60 s of the stream's own
+ * samples (1 440 000 at 24 kHz).  n_samples counts the stream's own samples; this entry serves float streams of any rate and
+ * refuses an int16 stream by name. */
 int q3tts_audio_stream_push_host(q3tts_engine* e, int stream_id, const float* pcm24k, int64_t n_samples, int finish,
                                  int64_t* codes_out, int cap_frames, int32_t* n_frames);
+/* the same with the samples read in the stream's own format: float for Q3TTS_PCM_F32, int16_t for Q3TTS_PCM_S16 (staged as int16,
+ * half the upload, and converted on the GPU) */
+int q3tts_audio_stream_push_any_host(q3tts_engine* e, int stream_id, const void* pcm, int64_t n_samples, int finish,
+                                     int64_t* codes_out, int cap_frames, int32_t* n_frames);
 /* Many streams in one call: one set of launches per group of at most 2 880 000 new samples, whatever the number of streams, and each
  * stream's result is what pushing it alone gives.  The call is validated completely before any stream moves (ids distinct, open and
  * not finished; sizes; each stream's total within its max_samples; caps[i] frames of room): a call refused by these checks leaves every
  * stream where it was.  (A HIP error is another matter: streams advance group by group, so after one in a later group of a call of
  * more than 2 880 000 new samples the streams of earlier groups have moved; end every stream of such a call.)  finish NULL: no stream finishes.  latents_out (NULL ok, and so may single entries) is the parity aid of
- * q3tts_audio_encode_batch_latents_host: latents_out[i][n_frames[i]][enc_hidden]. */
+ * q3tts_audio_encode_batch_latents_host: latents_out[i][n_frames[i]][enc_hidden].
+ * The float entry serves Q3TTS_PCM_F32 streams of any rate and refuses an int16 stream by name. */
 int q3tts_audio_stream_push_batch_host(q3tts_engine* e, int n_streams, const int32_t* stream_ids, const float* const* pcm24k,
                                        const int64_t* n_samples, const int32_t* finish /* NULL: none */,
                                        int64_t* const* codes_out, float* const* latents_out /* NULL ok: parity aid */,
                                        const int32_t* caps, int32_t* n_frames);
-/* samples received, frames returned, finished 0/1 and the bytes of the stream's device state (any pointer may be NULL) */
+/* q3tts_audio_stream_push_batch_host with pcm[i] read in stream i's own format; streams of different rates and formats may share a
+ * call (groups are cut by new 24 kHz samples and by at most 23 040 000 samples to resample) */
+int q3tts_audio_stream_push_batch_any_host(q3tts_engine* e, int n_streams, const int32_t* stream_ids, const void* const* pcm,
+                                           const int64_t* n_samples, const int32_t* finish /* NULL: none */,
+                                           int64_t* const* codes_out, float* const* latents_out /* NULL ok: parity aid */,
+                                           const int32_t* caps, int32_t* n_frames);
+/* samples received (at the stream's own rate), frames returned, finished 0/1 and the bytes of the stream's device state (any pointer may be NULL) */
 int q3tts_audio_stream_info(q3tts_engine* e, int stream_id, int64_t* n_samples, int32_t* n_frames, int* finished, int64_t* bytes);
 /* closes the stream (finished or not); its id and buffers serve a later q3tts_audio_stream_begin */
 int q3tts_audio_stream_end(q3tts_engine* e, int stream_id);
@@ -643,7 +676,8 @@ int q3tts_prefill_profile(q3tts_engine* e, int n_slots, int n_rows, int reps, do
 int q3tts_measure_skip_frames(q3tts_engine* e, int n_frames);
 /* Test hook (engines created with Q3TTS_FLAG_TEST_HOOKS only): fills the vocoder's reusable workspace (lane arenas, batched-front arena,
  * streaming arena, pinned PCM staging, the job's code rows) with 0xFF bytes = NaN, so that a later decode which reads anything it did
- * not write itself produces NaN instead of plausible stale samples (tests/test_gpu_codec_stress.py). */
+ * not write itself produces NaN instead of plausible stale samples (tests/test_gpu_codec_stress.py).  The audio encoder's grow-only
+ * workspace is filled the same way: an encoder stream's state (rings, resampler carry) lives outside it and must not notice. */
 int q3tts_test_poison_workspace(q3tts_engine* e);
 /* Test hook (Q3TTS_FLAG_TEST_HOOKS engines): the last batched vocoder group's final conv as it lies in its lane's workspace — input rows
  * sx_out[nb][T][C] (cap_floats >= nb*T*C, else skipped) and output pcm_out[nb][T]; either may be NULL.  tools/vocoder_stress.py uses it to

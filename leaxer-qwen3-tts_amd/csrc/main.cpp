@@ -6,7 +6,7 @@
 // row "Voice instructions (--instruct)"; combines with --ref), --save-codes FILE / --continue-codes FILE (with --tokens: write the
 // utterance's codec frames, one per line; generate behind recorded frames — the WAV then holds the new audio only),
 // --encode WAV --save-codes FILE (audio -> codes with the 12 Hz tokenizer's encoder, nothing else; --encode-chunk MS pushes the file MS
-// milliseconds at a time through one encoder stream: for a 24 kHz file the same codes, and no 60 s limit), --ref WAV with --ref-text TEXT /
+// milliseconds at a time through one encoder stream opened at the file's own rate: the same codes, and no 60 s limit), --ref WAV with --ref-text TEXT /
 // --ref-tokens "id,id,..." (in-context clone: the reference's codes and text in front of the utterance; --ref alone stays the x-vector clone).
 #include <algorithm>
 #include <cstdio>
@@ -55,7 +55,7 @@ static void usage(const char* prog) {
     printf("  --ref-text TEXT       with --ref: in-context clone instead — the reference is encoded to codes and continued, TEXT is what it says\n");
     printf("  --ref-tokens IDS      the same with the reference text as comma-separated token ids (for synthetic: models, with --tokens)\n");
     printf("  --encode PATH         encode a WAV to codec frames with the audio encoder and write them to --save-codes FILE; nothing is synthesized\n");
-    printf("  --encode-chunk MS     with --encode: push the file MS milliseconds at a time through one encoder stream (a 24 kHz file gives the same codes; files over 60 s encode)\n");
+    printf("  --encode-chunk MS     with --encode: push the file MS milliseconds at a time through one encoder stream (the stream runs at the file's own rate: the same codes; files over 60 s encode)\n");
     printf("  --temp FLOAT          temperature (default: 0.8; 0 samples at T=1 like the reference, use --top-k 1 for greedy)\n");
     printf("  --top-k N             top-k (default: 50)\n  --top-p FLOAT         top-p (default: 0.95)\n");
     printf("  --rep-penalty FLOAT   repetition penalty on the first codebook's ids (default: 1.0 = off; not a flag of the reference CLI)\n");
@@ -65,18 +65,13 @@ static void usage(const char* prog) {
     printf("  --feed K              with --stream-chunk: hand the text to the engine K tokens at a time while it generates (live text; same codes, and with --save-codes the same samples as without --feed)\n  -h, --help\n");
 }
 
-// a WAV file as mono float at 24 kHz for --encode-chunk (an encoder stream takes 24 kHz only): read on the host and, when its rate
-// differs, resampled on the host too — plain --encode resamples such a file on the GPU, so only 24 kHz files give both the same codes
-static bool read_wav_24k(const std::string& path, std::vector<float>& pcm24k) {
-    int64_t n = 0; int32_t rate = 0;
+// a WAV file as mono float at its own rate for --encode-chunk: the encoder stream is opened at that rate and resamples on the GPU as
+// plain --encode does, so a file of any rate gives both the same codes
+static bool read_wav_mono(const std::string& path, std::vector<float>& pcm, int32_t& rate) {
+    int64_t n = 0;
     if (q3tts_read_wav_host(path.c_str(), nullptr, 0, &n, &rate) != 0 || n < 1) return false;
-    std::vector<float> raw((size_t)n);
-    if (q3tts_read_wav_host(path.c_str(), raw.data(), n, &n, &rate) != 0) return false;
-    if (rate == 24000) { pcm24k.swap(raw); return true; }
-    const int64_t m = q3tts_resample_host(raw.data(), (int64_t)raw.size(), rate, 24000, nullptr, 0);
-    if (m < 1) return false;
-    pcm24k.resize((size_t)m);
-    return q3tts_resample_host(raw.data(), (int64_t)raw.size(), rate, 24000, pcm24k.data(), m) == m;
+    pcm.resize((size_t)n);
+    return q3tts_read_wav_host(path.c_str(), pcm.data(), n, &n, &rate) == 0;
 }
 
 // one frame per line, the same number of integers on every line (blanks or commas between them); false with a message on stderr
@@ -182,11 +177,12 @@ int main(int argc, char** argv) {
         if (!enc_engine.has_audio_encoder()) { fprintf(stderr, "Error: model has no audio encoder\n"); return 1; }
         std::vector<int64_t> codes;
         if (have_encode_chunk) {   // the file through one encoder stream sized to it, encode_chunk ms per push
-            std::vector<float> pcm;
-            if (!read_wav_24k(encode, pcm) || pcm.empty()) { fprintf(stderr, "Error: failed to read %s\n", encode.c_str()); return 1; }
-            const int id = enc_engine.audio_stream_begin((int64_t)pcm.size());
+            std::vector<float> pcm; int32_t rate = 0;
+            if (!read_wav_mono(encode, pcm, rate) || pcm.empty()) { fprintf(stderr, "Error: failed to read %s\n", encode.c_str()); return 1; }
+            const int id = enc_engine.audio_stream_begin((int64_t)pcm.size(), rate);
             if (id < 0) { fprintf(stderr, "Error: encoding failed\n"); return 1; }
-            const size_t step = std::min<size_t>((size_t)encode_chunk * 24, 1440000);
+            // encode_chunk ms of the file's own samples, at least one, at most the 60 s a push holds
+            const size_t step = std::min<size_t>(std::max<size_t>((size_t)((int64_t)encode_chunk * rate / 1000), 1), (size_t)60 * (size_t)rate);
             bool ok = true;
             for (size_t i = 0; ok && i < pcm.size(); i += step) {
                 const size_t m = std::min(step, pcm.size() - i);

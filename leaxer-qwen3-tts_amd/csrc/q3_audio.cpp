@@ -111,6 +111,23 @@ std::vector<float> resample_linear(const std::vector<float>& a, int src_rate, in
     return out;
 }
 
+// The same resampler while the clip is still arriving (q3_audio.h).  Positions are resample_linear's own expression on absolute
+// indices, (double)i / ratio, so the count agrees with what the one-shot reads; the estimate is corrected by stepping on that
+// expression, never trusted.
+int64_t resample_stream_emitted(int src_rate, int dst_rate, int64_t n, bool finish) {
+    if (n <= 0 || src_rate < 1 || dst_rate < 1) return 0;
+    if (src_rate == dst_rate) return n;
+    const double ratio = (double)dst_rate / src_rate;
+    const int64_t len = (int64_t)(size_t)((double)(size_t)n * ratio);   // resample_linear's n_out for a clip of n samples
+    if (finish) return len;
+    if (n < 2) return 0;
+    auto tap = [&](int64_t i) { return (int64_t)(size_t)((double)(size_t)i / ratio); };   // output i reads samples tap(i) and tap(i) + 1
+    int64_t e = (int64_t)((double)(n - 1) * ratio);            // about the first output whose upper tap has not arrived
+    while (e > 0 && tap(e - 1) > n - 2) --e;
+    while (tap(e) <= n - 2) ++e;
+    return std::min(e, len);
+}
+
 // ---------------------------------------------------------------------------------------------
 // log-mel (reference mel.cpp:13-80 filterbank, :182-236 framing).  NOT librosa's: symmetric Hann
 // window, no centre padding, frames = (n - win)/hop + 1 (one zero-padded frame for shorter clips),

@@ -15,6 +15,14 @@ namespace q3 {
 // mono float samples in [-1, 1); empty on any failure (as the reference).  *sample_rate is set on success.
 std::vector<float> read_wav(const std::string& path, int* sample_rate);
 std::vector<float> resample_linear(const std::vector<float>& audio, int src_rate, int dst_rate);
+// resample_linear over audio that is still arriving: the number of output samples a stream at src_rate has emitted in all once it
+// holds n_received samples.  finish: resample_linear's own length.  Otherwise the largest count whose every output i (a) has both
+// taps inside the received samples unclamped, floor(i / ratio) + 1 <= n_received - 1, and (b) lies below
+// (size_t)((double)n_received * ratio): whatever the final length n >= n_received, resample_linear produces it.  Monotone in
+// n_received, never above the finished length of a longer clip; equal rates: n_received.  Host-only, pure.
+int64_t resample_stream_emitted(int src_rate, int dst_rate, int64_t n_received, bool finish);
+// the raw samples a stream keeps behind its last one for the outputs it holds back: ceil(src_rate / dst_rate) + 1
+inline int resample_stream_carry(int src_rate, int dst_rate) { return (src_rate + dst_rate - 1) / dst_rate + 1; }
 
 struct MelSpec { // the settings of tts_onnx.cpp:347-354
     int sample_rate = 24000, n_fft = 1024, hop = 256, win = 1024, n_mels = 128;

@@ -1205,6 +1205,10 @@ int64_t q3tts_resample_host(const float* in, int64_t n, int32_t src_rate, int32_
         return (int64_t)r.size();
     } catch (...) { return -1; }
 }
+int64_t q3tts_resample_stream_emitted(int32_t src_rate, int32_t dst_rate, int64_t n_received, int finish) {
+    if (src_rate <= 0 || dst_rate <= 0 || n_received < 0) return -1;
+    return q3::resample_stream_emitted(src_rate, dst_rate, n_received, finish != 0);
+}
 int q3tts_mel_host(const float* audio, int64_t n, float* mel, int64_t cap, int32_t* frames) {
     if (n < 0 || (n > 0 && !audio) || !frames) return -1;
     try {
@@ -1277,6 +1281,25 @@ int q3tts_audio_stream_begin(q3tts_engine* h, int64_t max_samples, int* stream_i
     Q3_API_END(h)
 }
 
+int q3tts_audio_stream_begin_rate(q3tts_engine* h, int32_t sample_rate, int format, int64_t max_samples, int* stream_id) {
+    Q3_API_BEGIN(h)
+    if (!h->e->has_audio_encoder()) throw q3::Error("model has no audio encoder");
+    if (!h->e->finalized) throw q3::Error("weights not finalized");
+    if (!stream_id) throw q3::Error("audio stream: NULL argument");
+    *stream_id = h->e->audio_stream_begin(max_samples, sample_rate, format);
+    return 0;
+    Q3_API_END(h)
+}
+
+int q3tts_audio_stream_format(q3tts_engine* h, int stream_id, int32_t* sample_rate, int* format) {
+    Q3_API_BEGIN(h)
+    int32_t fmt = 0;
+    h->e->audio_stream_format(stream_id, sample_rate, &fmt);
+    if (format) *format = fmt;
+    return 0;
+    Q3_API_END(h)
+}
+
 int q3tts_audio_stream_push_len(q3tts_engine* h, int stream_id, int64_t n_samples, int finish) {
     Q3_API_BEGIN(h)
     return (int)h->e->audio_stream_push_len(stream_id, n_samples, finish != 0);
@@ -1289,7 +1312,18 @@ int q3tts_audio_stream_push_batch_host(q3tts_engine* h, int n_streams, const int
     if (!h->e->has_audio_encoder()) throw q3::Error("model has no audio encoder");
     if (!h->e->finalized) throw q3::Error("weights not finalized");
     if (!codes_out || !caps) throw q3::Error("audio stream push: NULL argument");
-    h->e->audio_stream_push_batch(n_streams, stream_ids, pcm24k, n_samples, finish, codes_out, latents_out, caps, n_frames);
+    h->e->audio_stream_push_batch(n_streams, stream_ids, (const void* const*)pcm24k, n_samples, finish, codes_out, latents_out, caps, n_frames, true);
+    return 0;
+    Q3_API_END(h)
+}
+
+int q3tts_audio_stream_push_batch_any_host(q3tts_engine* h, int n_streams, const int32_t* stream_ids, const void* const* pcm, const int64_t* n_samples,
+                                           const int32_t* finish, int64_t* const* codes_out, float* const* latents_out, const int32_t* caps, int32_t* n_frames) {
+    Q3_API_BEGIN(h)
+    if (!h->e->has_audio_encoder()) throw q3::Error("model has no audio encoder");
+    if (!h->e->finalized) throw q3::Error("weights not finalized");
+    if (!codes_out || !caps) throw q3::Error("audio stream push: NULL argument");
+    h->e->audio_stream_push_batch(n_streams, stream_ids, pcm, n_samples, finish, codes_out, latents_out, caps, n_frames, false);
     return 0;
     Q3_API_END(h)
 }
@@ -1302,7 +1336,22 @@ int q3tts_audio_stream_push_host(q3tts_engine* h, int stream_id, const float* pc
     if (!codes_out) throw q3::Error("audio stream push: NULL argument");
     const int32_t id = stream_id, fin = finish ? 1 : 0, cap = cap_frames;
     int32_t nf = 0;
-    h->e->audio_stream_push_batch(1, &id, &pcm24k, &n_samples, &fin, &codes_out, nullptr, &cap, &nf);
+    const void* p = pcm24k;
+    h->e->audio_stream_push_batch(1, &id, &p, &n_samples, &fin, &codes_out, nullptr, &cap, &nf, true);
+    if (n_frames) *n_frames = nf;
+    return 0;
+    Q3_API_END(h)
+}
+
+int q3tts_audio_stream_push_any_host(q3tts_engine* h, int stream_id, const void* pcm, int64_t n_samples, int finish, int64_t* codes_out, int cap_frames,
+                                     int32_t* n_frames) {
+    Q3_API_BEGIN(h)
+    if (!h->e->has_audio_encoder()) throw q3::Error("model has no audio encoder");
+    if (!h->e->finalized) throw q3::Error("weights not finalized");
+    if (!codes_out) throw q3::Error("audio stream push: NULL argument");
+    const int32_t id = stream_id, fin = finish ? 1 : 0, cap = cap_frames;
+    int32_t nf = 0;
+    h->e->audio_stream_push_batch(1, &id, &pcm, &n_samples, &fin, &codes_out, nullptr, &cap, &nf, false);
     if (n_frames) *n_frames = nf;
     return 0;
     Q3_API_END(h)
@@ -1465,6 +1514,7 @@ int64_t q3tts_test_final_conv_partials(q3tts_engine* h, float* out, int64_t cap_
 int q3tts_test_poison_workspace(q3tts_engine* h) {
     Q3_API_BEGIN(h)
     h->e->codec_poison();
+    h->e->encoder_poison();
     return 0;
     Q3_API_END(h)
 }

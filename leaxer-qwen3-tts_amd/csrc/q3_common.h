@@ -458,6 +458,24 @@ void launch_spk_asp_pool(const float* scores, const float* x, int T, int C, floa
 
 // linear resampler of q3::resample_linear for the clips whose rates differ: rs[rs_off + i], i < n_rs, from raw[in_off ..]
 void launch_resample_linear(const float* raw, float* rs, const SpkClip* clips, int n_clips, int max_n_rs, hipStream_t s);
+// The same resampler for audio that is still arriving (encoder streams, q3_encoder.cpp).  One stream of one push:
+// the samples the stream has are its carry (floats, the last `n_before - carry_abs0` samples before this push) followed by the
+// push's n_new staged samples (float, or int16 converted as (float)v / 32768.0f).  Output i of the launch is the stream's absolute
+// output out0 + i: position, taps and weight from that absolute index in double, as q3::resample_linear forms them; the upper tap
+// is clamped to n_total - 1, which only a finishing push reaches.  All indices are 64-bit: an hour at 384 kHz is 1.38e9 samples.
+// The launch also writes the stream's next carry, the last `keep` samples of (carry, new), into carry_out: the other of the
+// stream's two carry buffers, never the one being read.
+struct EncRsStream {
+    const float* carry_in = nullptr; float* carry_out = nullptr;
+    int64_t carry_abs0 = 0;             // absolute index of carry_in[0]
+    int64_t n_before = 0, n_total = 0;  // samples received before / with this push (n_before = absolute index of the first new sample)
+    int64_t out0 = 0;                   // absolute index of the first new output
+    int64_t in_off = 0;                 // byte offset of the new samples in the staging buffer (a multiple of 4)
+    int32_t n_new = 0, n_out = 0, keep = 0;   // keep == 0: the carry stays (a push without samples)
+    int32_t x24_off = 0;                // first new output in the push's 24 kHz buffer
+    int32_t src_rate = 0, s16 = 0;
+};
+void launch_resample_linear_streams(const void* staged, float* x24, const EncRsStream* tab /* device, [n] */, int n, int max_work /* largest n_out + keep */, hipStream_t s);
 // log-mel of q3::log_mel for the clone path's MelSpec (n_fft = win = 1024, hop 256, 128 bands): mel + 128 * row_off is the clip's [128][T]
 struct MelTablesDev {
     const float *window = nullptr, *tw_re = nullptr, *tw_im = nullptr;   // [1024], [512], [512]

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "q3_audio.h"
 #include "q3_engine.h"
 
 namespace q3 {
@@ -27,11 +28,19 @@ struct EncLayerW {
 // One audio stream's carried state.  rows[l]: rows emitted so far at rate level l (0 = samples received, l = 1 .. nr
 // behind stage l - 1, nr + 1 = frames).  buf: the stream's carry rings, one per conv with k > 1 (k - 1 raw input rows, before ELU)
 // and one per transformer layer ([window - 1][2 AO]: rotated K, then V); absolute row r of a ring's input sits in slot r mod cap.
+// A stream at another rate or sample format than 24 kHz float resamples on the way in: rows[0] then counts the 24 kHz
+// samples fed to the encoder, n_raw the stream's own samples received, and behind the rings buf holds two carry buffers of
+// kEncCarryFloats floats: the last min(carry_len, n_raw) raw samples, as floats, are in buffer carry_cur; a push writes the other one.
 struct EncStream {
     bool open = false, finished = false;
     int64_t max_samples = 0, rows[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     float* buf = nullptr; size_t buf_floats = 0;
+    int rate = 24000, s16 = 0, carry_len = 0, carry_cur = 0;
+    int64_t n_raw = 0;
+    size_t carry_off = 0;   // the first carry buffer's first float in buf
+    bool plain() const { return rate == 24000 && !s16; }
 };
+static constexpr size_t kEncCarryFloats = 64;   // a carry buffer: ceil(384000 / 24000) + 1 = 17 samples at most, one 256-byte line
 struct EncoderW {
     EncConvW conv_in, res1[4], res2[4], down[4], conv_out, ds;
     std::vector<EncLayerW> layers;
@@ -71,6 +80,13 @@ void Engine::encoder_free() {
     for (int s = 0; s < 4; ++s) { drop(enc->res1[s]); drop(enc->res2[s]); drop(enc->down[s]); }
     delete enc;
     enc = nullptr;
+}
+
+void Engine::encoder_poison() {
+    if (!(flags & Q3TTS_FLAG_TEST_HOOKS)) throw Error("encoder_poison needs Q3TTS_FLAG_TEST_HOOKS");
+    if (!enc || !enc->ws) return;
+    sync();
+    Q3_HIP_CHECK(hipMemset(enc->ws, 0xFF, enc->ws_cap));
 }
 
 int64_t Engine::audio_encode_len(int64_t n24) const {
@@ -365,12 +381,18 @@ static EncStream& enc_stream_at(const Engine& e, int id, const char* who) {
     return e.enc->streams[(size_t)id];
 }
 
-int Engine::audio_stream_begin(int64_t max_samples) {
+int Engine::audio_stream_begin(int64_t max_samples, int sample_rate, int format) {
     if (!has_audio_encoder()) throw Error("model has no audio encoder");
     if (!enc) throw Error("weights not finalized");
-    if (max_samples == 0) max_samples = kEncMaxClipSamples;
-    if (max_samples < 1 || max_samples > kEncMaxStreamSamples)
-        throw Error("audio stream: max_samples must be 0 (60 s) or 1.." + std::to_string(kEncMaxStreamSamples) + " (one hour), got " + std::to_string(max_samples));
+    if (sample_rate < 1 || sample_rate > kEncMaxStreamRate)
+        throw Error("audio stream: sample_rate must be 1.." + std::to_string(kEncMaxStreamRate) + ", got " + std::to_string(sample_rate));
+    if (format != Q3TTS_PCM_F32 && format != Q3TTS_PCM_S16)
+        throw Error("audio stream: format must be Q3TTS_PCM_F32 (0) or Q3TTS_PCM_S16 (1), got " + std::to_string(format));
+    const int64_t hour = (int64_t)3600 * sample_rate;   // at 24 kHz: kEncMaxStreamSamples
+    if (max_samples == 0) max_samples = (int64_t)60 * sample_rate;
+    if (max_samples < 1 || max_samples > hour)
+        throw Error("audio stream: max_samples must be 0 (60 s) or 1.." + std::to_string(hour) + " (one hour), got " + std::to_string(max_samples));
+    const int64_t max24 = resample_stream_emitted(sample_rate, 24000, max_samples, true);   // what the encoder sees of it at most
     int id = -1, n_open = 0;
     for (size_t i = 0; i < enc->streams.size(); ++i) {
         if (enc->streams[i].open) ++n_open;
@@ -379,20 +401,23 @@ int Engine::audio_stream_begin(int64_t max_samples) {
     if (n_open >= kEncMaxStreams) throw Error("audio stream: " + std::to_string(kEncMaxStreams) + " streams are open already");
     int64_t prod = 1;
     for (int s = 0; s < c.enc_n_ratios; ++s) prod *= c.enc_ratios[s];
-    const int rows = (int)ceil_div(max_samples, prod) + 1;
+    const int rows = (int)ceil_div(max24, prod) + 1;
     if (rows > enc->rope_rows) { sync(); enc_rope_tables(*this, rows); }   // the whole table again, by the same formula: existing rows keep their bits
     const EncStreamPlan plan = enc_stream_plan(c, *enc);
     if (id < 0) { enc->streams.emplace_back(); id = (int)enc->streams.size() - 1; }
     EncStream& st = enc->streams[(size_t)id];
-    if (st.buf_floats < plan.floats) {
+    const size_t floats = plan.floats + 2 * kEncCarryFloats;   // every stream has room for a carry: an id may come back at another rate
+    if (st.buf_floats < floats) {
         if (st.buf) (void)hipFree(st.buf);
         st.buf = nullptr; st.buf_floats = 0;
-        Q3_HIP_CHECK(hipMalloc((void**)&st.buf, plan.floats * sizeof(float)));
-        st.buf_floats = plan.floats;
+        Q3_HIP_CHECK(hipMalloc((void**)&st.buf, floats * sizeof(float)));
+        st.buf_floats = floats;
     }
-    // no clearing: a ring slot is read only for an absolute row this stream has written
+    // no clearing: a ring slot, and a carry sample, is read only for an absolute row this stream has written
     st.open = true; st.finished = false; st.max_samples = max_samples;
     for (int64_t& r : st.rows) r = 0;
+    st.rate = sample_rate; st.s16 = format == Q3TTS_PCM_S16 ? 1 : 0; st.n_raw = 0; st.carry_cur = 0; st.carry_off = plan.floats;
+    st.carry_len = resample_stream_carry(sample_rate, 24000);
     return id;
 }
 
@@ -403,43 +428,57 @@ void Engine::audio_stream_end(int id) {
 
 void Engine::audio_stream_info(int id, int64_t* n_samples, int32_t* n_frames, int* finished, int64_t* bytes) const {
     const EncStream& st = enc_stream_at(*this, id, "audio_stream_info");
-    if (n_samples) *n_samples = st.rows[0];
+    if (n_samples) *n_samples = st.n_raw;
     if (n_frames) *n_frames = (int32_t)st.rows[c.enc_n_ratios + 1];
     if (finished) *finished = st.finished ? 1 : 0;
     if (bytes) *bytes = (int64_t)(st.buf_floats * sizeof(float));
 }
 
+void Engine::audio_stream_format(int id, int32_t* sample_rate, int32_t* format) const {
+    const EncStream& st = enc_stream_at(*this, id, "audio_stream_format");
+    if (sample_rate) *sample_rate = st.rate;
+    if (format) *format = st.s16 ? Q3TTS_PCM_S16 : Q3TTS_PCM_F32;
+}
+
+// the 24 kHz samples a push of n of the stream's own samples feeds the encoder: the host rule after the push minus before it
+static int64_t enc_stream_new24(const EncStream& st, int64_t n, bool finish) {
+    if (st.rate == 24000) return n;
+    return resample_stream_emitted(st.rate, 24000, st.n_raw + n, finish) - st.rows[0];
+}
+
 int64_t Engine::audio_stream_push_len(int id, int64_t n_samples, bool finish) const {
     const EncStream& st = enc_stream_at(*this, id, "audio_stream_push_len");
     if (st.finished) throw Error("audio stream " + std::to_string(id) + " is finished");
-    if (n_samples < 0 || n_samples > kEncMaxClipSamples || st.rows[0] + n_samples > st.max_samples)
+    if (n_samples < 0 || n_samples > (int64_t)60 * st.rate || st.n_raw + n_samples > st.max_samples)
         throw Error("audio stream " + std::to_string(id) + ": a push of " + std::to_string(n_samples) + " samples is outside the stream's limits");
     int64_t after[8];
-    enc_stream_advance(c, st.rows, n_samples, finish, after);
+    enc_stream_advance(c, st.rows, enc_stream_new24(st, n_samples, finish), finish, after);
     return after[c.enc_n_ratios + 1] - st.rows[c.enc_n_ratios + 1];
 }
 
-void Engine::audio_stream_push_batch(int n_streams, const int32_t* ids, const float* const* pcm, const int64_t* n_samples, const int32_t* finish,
-                                     int64_t* const* codes_out, float* const* latents_out, const int32_t* caps, int32_t* n_frames) {
+void Engine::audio_stream_push_batch(int n_streams, const int32_t* ids, const void* const* pcm, const int64_t* n_samples, const int32_t* finish,
+                                     int64_t* const* codes_out, float* const* latents_out, const int32_t* caps, int32_t* n_frames, bool float_only) {
     if (!has_audio_encoder()) throw Error("model has no audio encoder");
     if (!enc) throw Error("weights not finalized");
     if (n_streams < 1) throw Error("audio stream push: n_streams must be at least 1, got " + std::to_string(n_streams));
     if (!ids || !pcm || !n_samples || !n_frames) throw Error("audio stream push: NULL argument");
     const int nr = c.enc_n_ratios, NL = nr + 2, EH = c.enc_hidden, AO = c.enc_heads * c.enc_head_dim, G = c.n_groups;
     // everything is validated before any stream moves
-    std::vector<int64_t> after((size_t)n_streams * 8, 0);
+    std::vector<int64_t> after((size_t)n_streams * 8, 0), n24((size_t)n_streams, 0);
     for (int i = 0; i < n_streams; ++i) {
         const std::string who = "audio stream " + std::to_string(ids[i]) + ": ";
         const EncStream& st = enc_stream_at(*this, ids[i], "audio stream push");
         for (int j = 0; j < i; ++j) if (ids[j] == ids[i]) throw Error(who + "given twice in one push");
         if (st.finished) throw Error(who + "is finished");
+        if (float_only && st.s16) throw Error(who + "takes int16 samples (Q3TTS_PCM_S16): push it through q3tts_audio_stream_push_any_host, not a float entry");
         if (n_samples[i] < 0) throw Error(who + "n_samples must not be negative, got " + std::to_string(n_samples[i]));
         if (n_samples[i] > 0 && !pcm[i]) throw Error(who + "NULL audio pointer");
-        if (n_samples[i] > kEncMaxClipSamples)
-            throw Error(who + "push too long: " + std::to_string(n_samples[i]) + " samples, the cap per push is " + std::to_string(kEncMaxClipSamples) + " (60 s)");
-        if (st.rows[0] + n_samples[i] > st.max_samples)
-            throw Error(who + "over its max_samples: " + std::to_string(st.rows[0]) + " + " + std::to_string(n_samples[i]) + " samples, the stream was begun for " + std::to_string(st.max_samples));
-        enc_stream_advance(c, st.rows, n_samples[i], finish && finish[i], &after[(size_t)i * 8]);
+        if (n_samples[i] > (int64_t)60 * st.rate)
+            throw Error(who + "push too long: " + std::to_string(n_samples[i]) + " samples, the cap per push is " + std::to_string((int64_t)60 * st.rate) + " (60 s)");
+        if (st.n_raw + n_samples[i] > st.max_samples)
+            throw Error(who + "over its max_samples: " + std::to_string(st.n_raw) + " + " + std::to_string(n_samples[i]) + " samples, the stream was begun for " + std::to_string(st.max_samples));
+        n24[(size_t)i] = enc_stream_new24(st, n_samples[i], finish && finish[i]);   // the host rule first: every cap below is about what it gives
+        enc_stream_advance(c, st.rows, n24[(size_t)i], finish && finish[i], &after[(size_t)i * 8]);
         const int64_t F = after[(size_t)i * 8 + nr + 1] - st.rows[nr + 1];
         if (F > 0 && ((codes_out && codes_out[i]) || (latents_out && latents_out[i]))) {
             if (!caps || caps[i] < F) throw Error(who + "output buffer too small for " + std::to_string(F) + " frames");
@@ -449,8 +488,12 @@ void Engine::audio_stream_push_batch(int n_streams, const int32_t* ids, const fl
     last_audio_encode_ms = 0.f;
 
     for (int g0 = 0; g0 < n_streams;) {
-        int g1 = g0; int64_t sum = 0;   // a group: at most kEncMaxGroupSamples new samples (its first stream always fits); a stream's push is never split
-        while (g1 < n_streams && g1 - g0 < 1024 && (g1 == g0 || sum + n_samples[g1] <= kEncMaxGroupSamples)) { sum += n_samples[g1]; ++g1; }
+        // a group: at most kEncMaxGroupSamples new samples at 24 kHz and kEncMaxRawSamples to resample (its first stream always fits); a stream's push is never split
+        int g1 = g0; int64_t sum = 0, raw_sum = 0;
+        auto raw_of = [&](int i) { return enc->streams[(size_t)ids[i]].plain() ? (int64_t)0 : n_samples[i]; };
+        while (g1 < n_streams && g1 - g0 < 1024 && (g1 == g0 || (sum + n24[(size_t)g1] <= kEncMaxGroupSamples && raw_sum + raw_of(g1) <= kEncMaxRawSamples))) {
+            sum += n24[(size_t)g1]; raw_sum += raw_of(g1); ++g1;
+        }
         const int n = g1 - g0;
         auto stream_of = [&](int i) -> EncStream& { return enc->streams[(size_t)ids[g0 + i]]; };
         auto before = [&](int i, int l) { return stream_of(i).rows[l]; };
@@ -463,17 +506,37 @@ void Engine::audio_stream_push_batch(int n_streams, const int32_t* ids, const fl
                 spans[(size_t)l * n + i].off = (int32_t)tot[(size_t)l]; spans[(size_t)l * n + i].T = newr(i, l);
                 tot[(size_t)l] += newr(i, l);
             }
+        // the streams that resample on the way in: their new samples are staged as they came, float or int16
+        std::vector<EncRsStream> rs; size_t staged_bytes = 0; int rs_work = 0;
+        for (int i = 0; i < n; ++i) {
+            EncStream& st = stream_of(i);
+            const int64_t add = n_samples[g0 + i];
+            if (st.plain() || (add == 0 && newr(i, 0) == 0)) continue;
+            EncRsStream d;
+            const int64_t held = std::min<int64_t>(st.carry_len, st.n_raw);
+            d.carry_in = st.buf + st.carry_off + (size_t)st.carry_cur * kEncCarryFloats;
+            d.carry_out = st.buf + st.carry_off + (size_t)(1 - st.carry_cur) * kEncCarryFloats;
+            d.carry_abs0 = st.n_raw - held; d.n_before = st.n_raw; d.n_total = st.n_raw + add; d.out0 = st.rows[0];
+            d.in_off = (int64_t)staged_bytes; d.n_new = (int32_t)add; d.n_out = newr(i, 0);
+            d.keep = add > 0 ? (int32_t)std::min<int64_t>(st.carry_len, d.n_total) : 0;
+            d.x24_off = spans[(size_t)i].off; d.src_rate = st.rate; d.s16 = st.s16;
+            staged_bytes += ((size_t)add * (st.s16 ? 2 : 4) + 3) / 4 * 4;
+            rs_work = std::max(rs_work, d.n_out + d.keep);
+            rs.push_back(d);
+        }
         size_t xmax = 1, mmax = 1;
         { int dim = c.enc_filters;
           for (int s = 0; s <= nr; ++s, dim *= 2) { xmax = std::max(xmax, (size_t)tot[(size_t)s] * dim); mmax = std::max(mmax, (size_t)tot[(size_t)s] * (dim / 2)); } }
         const size_t R = (size_t)tot[(size_t)nr], F = (size_t)tot[(size_t)nr + 1], R1 = std::max<size_t>(1, R), F1 = std::max<size_t>(1, F);
         const size_t tab_cap = (size_t)n * (plan.convs.size() * (2 * enc_aligned(sizeof(EncSpan)) + enc_aligned(sizeof(EncHist)) + enc_aligned(sizeof(EncCarryCopy)))
-                                            + (size_t)c.enc_layers * (enc_aligned(sizeof(EncHist)) + enc_aligned(sizeof(EncCarryCopy))) + enc_aligned(sizeof(EncSpan)));
-        struct Bufs { char* tab; float *x24, *X, *Y, *M; EncTfBufs tf; float* lat; int32_t* codes; size_t used; };
+                                            + (size_t)c.enc_layers * (enc_aligned(sizeof(EncHist)) + enc_aligned(sizeof(EncCarryCopy))) + enc_aligned(sizeof(EncSpan)))
+                               + enc_aligned(std::max<size_t>(1, rs.size()) * sizeof(EncRsStream));
+        struct Bufs { char* tab; char* staged; float *x24, *X, *Y, *M; EncTfBufs tf; float* lat; int32_t* codes; size_t used; };
         auto layout = [&](char* base) {
             EncCarve cv(base);
             Bufs b;
             b.tab = (char*)cv.take_bytes(tab_cap);
+            b.staged = (char*)cv.take_bytes(staged_bytes + 4);   // + 4: a stream without new samples still has an address to clamp to
             b.x24 = cv.take(std::max<size_t>(1, (size_t)tot[0]));
             b.X = cv.take(xmax); b.Y = cv.take(xmax); b.M = cv.take(mmax);
             b.tf.x = cv.take(R1 * EH); b.tf.n = cv.take(R1 * EH); b.tf.qkv = cv.take(R1 * 3 * AO); b.tf.a = cv.take(R1 * AO); b.tf.f = cv.take(R1 * (size_t)c.enc_ffn);
@@ -552,14 +615,23 @@ void Engine::audio_stream_push_batch(int n_streams, const int32_t* ids, const fl
             tf_n_copy = (int)cp.size();
             tf_hist.push_back(tab.add(hs)); tf_copy.push_back(tab.add(cp));
         }
+        const size_t rs_off = tab.add(rs);
         if (tab.h.size() > tab_cap) throw Error("audio stream push: descriptor tables larger than planned");
 
         // pass 2: one upload of the tables, the samples, then the launches
         Q3_HIP_CHECK(hipEventRecord(ev0, stream));
         if (!tab.h.empty()) Q3_HIP_CHECK(hipMemcpyAsync(b.tab, tab.h.data(), tab.h.size(), hipMemcpyHostToDevice, stream));
-        for (int i = 0; i < n; ++i)
-            if (n_samples[g0 + i] > 0)
-                Q3_HIP_CHECK(hipMemcpyAsync(b.x24 + spans[(size_t)i].off, pcm[g0 + i], (size_t)n_samples[g0 + i] * sizeof(float), hipMemcpyHostToDevice, stream));
+        for (int i = 0, k = 0; i < n; ++i) {
+            const EncStream& st = stream_of(i);
+            const size_t add = (size_t)n_samples[g0 + i];
+            if (st.plain()) {
+                if (add > 0) Q3_HIP_CHECK(hipMemcpyAsync(b.x24 + spans[(size_t)i].off, pcm[g0 + i], add * sizeof(float), hipMemcpyHostToDevice, stream));
+            } else if (add > 0 || newr(i, 0) > 0) {
+                if (add > 0) Q3_HIP_CHECK(hipMemcpyAsync(b.staged + rs[(size_t)k].in_off, pcm[g0 + i], add * (st.s16 ? 2 : 4), hipMemcpyHostToDevice, stream));
+                ++k;
+            }
+        }
+        if (rs_work > 0) launch_resample_linear_streams(b.staged, b.x24, (const EncRsStream*)(b.tab + rs_off), (int)rs.size(), rs_work, stream);
         for (size_t ci = 0; ci < steps.size(); ++ci) {
             const EncConvPlan& p = plan.convs[ci];
             const ConvStep& st = steps[ci];
@@ -599,6 +671,7 @@ void Engine::audio_stream_push_batch(int n_streams, const int32_t* ids, const fl
         for (int i = 0; i < n; ++i) {   // the group's streams move
             EncStream& st = stream_of(i);
             for (int l = 0; l < NL; ++l) st.rows[l] = after[(size_t)(g0 + i) * 8 + l];
+            if (n_samples[g0 + i] > 0) { st.n_raw += n_samples[g0 + i]; if (!st.plain()) st.carry_cur = 1 - st.carry_cur; }
             if (finish && finish[g0 + i]) st.finished = true;
         }
         g0 = g1;

@@ -335,6 +335,7 @@ public:
     bool has_audio_encoder() const { return c.enc_hidden > 0; }
     void encoder_finalize();
     void encoder_free();
+    void encoder_poison();                                    // test hook: NaN bytes over the encoder's workspace (stream state lives outside it)
     static constexpr int64_t kEncMaxClipSamples = 1440000;    // 60 s at 24 kHz: one clip
     static constexpr int64_t kEncMaxRawSamples = 23040000;    // a clip (and a group's clips together) at another rate: samples to resample (60 s at 384 kHz, 92 MB)
     static constexpr int64_t kEncMaxGroupSamples = 2880000;   // a batch is processed in consecutive groups of at most this many samples
@@ -349,14 +350,20 @@ public:
     // ---- streamed audio -> codes: carried-state pushes, bit-identical to audio_encode of the concatenated audio ----
     static constexpr int64_t kEncMaxStreamSamples = 86400000; // one hour at 24 kHz: a stream's max_samples
     static constexpr int kEncMaxStreams = 1024;               // open at the same time
-    int audio_stream_begin(int64_t max_samples);              // 0: kEncMaxClipSamples.  Regrows the RoPE tables when the stream can have more rows (syncs)
-    int64_t audio_stream_push_len(int id, int64_t n_samples, bool finish) const;   // host-only: frames that push would return
-    // n streams (distinct, open, not finished), each given n_samples[i] >= 0 more samples at 24 kHz (finish[i]: the stream's last
-    // push, right edge as the one-shot's) -> the NEW frames' codes [frames][n_groups] / latents [frames][enc_hidden].  Everything is
-    // validated before any stream moves; one set of launches per group of streams whatever their number.
-    void audio_stream_push_batch(int n, const int32_t* ids, const float* const* pcm, const int64_t* n_samples, const int32_t* finish,
-                                 int64_t* const* codes_out, float* const* latents_out, const int32_t* caps, int32_t* n_frames);
-    void audio_stream_info(int id, int64_t* n_samples, int32_t* n_frames, int* finished, int64_t* bytes) const;
+    static constexpr int kEncMaxStreamRate = 384000;          // the rate kEncMaxRawSamples is worded for; a stream's carry is then 17 samples at most
+    // A stream at sample_rate (1 .. kEncMaxStreamRate) in format Q3TTS_PCM_F32 / _S16 (other than 24 kHz float it resamples
+    // on the way in, bit-identical to audio_encode at that rate).  max_samples counts the stream's own samples: 0 = 60 s, at most one
+    // hour.  Regrows the RoPE tables when the stream can have more rows (syncs)
+    int audio_stream_begin(int64_t max_samples, int sample_rate = 24000, int format = Q3TTS_PCM_F32);
+    int64_t audio_stream_push_len(int id, int64_t n_samples, bool finish) const;   // host-only: frames that push of the stream's own samples would return
+    // n streams (distinct, open, not finished), each given n_samples[i] >= 0 more samples of its own rate and format (finish[i]: the
+    // stream's last push, right edge as the one-shot's) -> the NEW frames' codes [frames][n_groups] / latents [frames][enc_hidden].
+    // Everything is validated before any stream moves; one set of launches per group of streams whatever their number, rates and
+    // formats.  float_only: the caller's samples are float, an int16 stream is refused.
+    void audio_stream_push_batch(int n, const int32_t* ids, const void* const* pcm, const int64_t* n_samples, const int32_t* finish,
+                                 int64_t* const* codes_out, float* const* latents_out, const int32_t* caps, int32_t* n_frames, bool float_only = false);
+    void audio_stream_info(int id, int64_t* n_samples, int32_t* n_frames, int* finished, int64_t* bytes) const;   // n_samples: received, at the stream's own rate
+    void audio_stream_format(int id, int32_t* sample_rate, int32_t* format) const;
     void audio_stream_end(int id);                            // the stream's buffers stay for the next begin; freed in encoder_free
     void enc_calibrate_synthetic(uint64_t seed);              // fill_synthetic: codebooks at the scale of the projected latents
 

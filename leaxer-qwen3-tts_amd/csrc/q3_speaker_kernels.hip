@@ -184,6 +184,39 @@ __global__ __launch_bounds__(256) void k_resample_linear(const float* raw, float
     rs[cl.rs_off + i] = (float)((double)a[k] * (1.0 - w) + (double)a[k1] * w);
 }
 
+// k_resample_linear for encoder streams: the clip is still arriving, so a sample is either in the stream's carry or among the push's
+// new ones.  Both addresses are clamped into their buffers and both loads issued; the value is selected afterwards.
+__device__ __forceinline__ float rs_stream_sample(const EncRsStream& d, const float* fnew, const int16_t* snew, int64_t k) {
+    int64_t jn = k - d.n_before, jc = k - d.carry_abs0;
+    const bool is_new = jn >= 0;
+    const int64_t last_new = d.n_new > 0 ? d.n_new - 1 : 0, last_c = d.n_before - d.carry_abs0 > 0 ? d.n_before - d.carry_abs0 - 1 : 0;
+    jn = jn < 0 ? 0 : (jn > last_new ? last_new : jn);
+    jc = jc < 0 ? 0 : (jc > last_c ? last_c : jc);
+    const float vn = d.s16 ? (float)snew[jn] / 32768.0f : fnew[jn];   // the staging buffer always holds at least one padded element
+    const float vc = d.carry_in[jc];
+    return is_new ? vn : vc;
+}
+__global__ __launch_bounds__(256) void k_stream_resample_linear(const char* staged, float* x24, const EncRsStream* tab) {
+    const EncRsStream d = tab[blockIdx.y];
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= d.n_out + d.keep) return;
+    const float* fnew = (const float*)(staged + d.in_off);
+    const int16_t* snew = (const int16_t*)(staged + d.in_off);
+    if (t >= d.n_out) {   // the next carry: the last `keep` samples the stream has
+        const int j = t - d.n_out;
+        d.carry_out[j] = rs_stream_sample(d, fnew, snew, d.n_total - d.keep + j);
+        return;
+    }
+    const int64_t i = d.out0 + t, last = d.n_total - 1;
+    const double ratio = 24000.0 / d.src_rate;
+    const double pos = (double)i / ratio;
+    int64_t k = (int64_t)pos;
+    if (k > last) k = last;   // never taken for an output the host rule emits; keeps the taps inside the stream whatever the table says
+    const double w = pos - (double)k;
+    const int64_t k1 = k + 1 < last ? k + 1 : last;
+    x24[d.x24_off + t] = (float)((double)rs_stream_sample(d, fnew, snew, k) * (1.0 - w) + (double)rs_stream_sample(d, fnew, snew, k1) * w);
+}
+
 // One frame per workgroup: window -> the host's radix-2 decimation-in-time FFT (same butterflies, same twiddle table, so the same
 // roundings) -> power -> one lane per mel band sums its triangle in the host's order -> logf(e + 1e-10f).  The complex frame lives in
 // LDS; index i is stored at i + i / 32, which spreads the stride-2 .. stride-32 accesses of the first five stages over the banks.
@@ -268,6 +301,11 @@ void launch_resample_linear(const float* raw, float* rs, const SpkClip* clips, i
     hipLaunchKernelGGL(k_resample_linear, dim3((max_n_rs + 255) / 256, n_clips), dim3(256), 0, s, raw, rs, clips);
     Q3_HIP_CHECK(hipGetLastError());
 }
+void launch_resample_linear_streams(const void* staged, float* x24, const EncRsStream* tab, int n, int max_work, hipStream_t s) {
+    if (n < 1 || n > 65535 || max_work < 1) throw Error("stream resample: 1..65535 streams with at least one output or carry sample");
+    hipLaunchKernelGGL(k_stream_resample_linear, dim3((max_work + 255) / 256, n), dim3(256), 0, s, (const char*)staged, x24, tab);
+}
+
 void launch_logmel(const float* raw, const float* rs, const SpkClip* clips, int n_clips, int max_T, const MelTablesDev& tb, float* mel, hipStream_t s) {
     if (n_clips < 1 || n_clips > 65535 || max_T < 1) throw Error("log-mel: 1..65535 clips with at least one frame");
     hipLaunchKernelGGL(k_logmel, dim3(max_T, n_clips), dim3(256), 0, s, raw, rs, clips, tb, mel);

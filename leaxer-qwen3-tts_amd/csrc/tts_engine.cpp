@@ -300,21 +300,39 @@ std::vector<int64_t> TTSEngine::encode_audio(const std::vector<float>& pcm, int 
     return codes;
 }
 
-int TTSEngine::audio_stream_begin(int64_t max_samples) {
+int TTSEngine::audio_stream_begin(int64_t max_samples) { return audio_stream_begin(max_samples, 24000, false); }
+
+int TTSEngine::audio_stream_begin(int64_t max_samples, int sample_rate, bool pcm16) {
     if (!ready_) return -1;
     int id = -1;
-    if (q3tts_audio_stream_begin(h_, max_samples, &id) != 0) { std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl; return -1; }
+    if (q3tts_audio_stream_begin_rate(h_, sample_rate, pcm16 ? Q3TTS_PCM_S16 : Q3TTS_PCM_F32, max_samples, &id) != 0) { std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl; return -1; }
     return id;
 }
 
 std::vector<int64_t> TTSEngine::audio_stream_push(int id, const float* pcm, size_t n, bool finish, bool* ok) {
+    return audio_stream_push_any(id, pcm, n, finish, ok, false);
+}
+
+std::vector<int64_t> TTSEngine::audio_stream_push(int id, const int16_t* pcm, size_t n, bool finish, bool* ok) {
+    return audio_stream_push_any(id, pcm, n, finish, ok, true);
+}
+
+std::vector<int64_t> TTSEngine::audio_stream_push_any(int id, const void* pcm, size_t n, bool finish, bool* ok, bool pcm16) {
     if (ok) *ok = false;
     if (!ready_) return {};
+    if (pcm16) {   // int16 samples go to a stream begun for them only: the engine reads them in the stream's format
+        int fmt = Q3TTS_PCM_F32;
+        if (q3tts_audio_stream_format(h_, id, nullptr, &fmt) != 0) { std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl; return {}; }
+        if (fmt != Q3TTS_PCM_S16) { std::cerr << "[TTSEngine] audio stream " << id << " takes float samples, not int16" << std::endl; return {}; }
+    }
     const int frames = q3tts_audio_stream_push_len(h_, id, (int64_t)n, finish ? 1 : 0);
     if (frames < 0) { std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl; return {}; }
     std::vector<int64_t> codes((size_t)std::max(frames, 1) * (size_t)n_groups_);
     int32_t got = 0;
-    if (q3tts_audio_stream_push_host(h_, id, pcm, (int64_t)n, finish ? 1 : 0, codes.data(), std::max(frames, 1), &got) != 0) {
+    // the float entry refuses an int16 stream by name; the other one reads the samples in the stream's own format, so it gets int16 only
+    const int rc = pcm16 ? q3tts_audio_stream_push_any_host(h_, id, pcm, (int64_t)n, finish ? 1 : 0, codes.data(), std::max(frames, 1), &got)
+                         : q3tts_audio_stream_push_host(h_, id, (const float*)pcm, (int64_t)n, finish ? 1 : 0, codes.data(), std::max(frames, 1), &got);
+    if (rc != 0) {
         std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl;
         return {};
     }

@@ -144,12 +144,15 @@ public:
     std::vector<int64_t> encode_audio(const std::vector<float>& pcm, int sample_rate);
     std::vector<int64_t> encode_audio(const std::string& wav_path);
     // Audio -> codes while the audio arrives (include/q3tts.h: q3tts_audio_stream_begin / _push_host / _end; [HINT] as encode_audio):
-    // a stream takes mono samples at 24 kHz in pushes of any size (at most 60 s each) and returns the frames each push completes;
-    // the concatenation is bit-identical to encode_audio of the concatenated samples.  max_samples: the most the stream will take
-    // (0: 60 s; at most one hour).  audio_stream_begin returns the stream id, -1 on error; a failed push returns no frames and sets
-    // *ok = false when ok is given.
+    // a stream takes mono samples at its source's rate (24 kHz unless begun otherwise; float, or int16 when begun with pcm16) in
+    // pushes of any size (at most 60 s each) and returns the frames each push completes; the concatenation is bit-identical to
+    // encode_audio of the concatenated samples at that rate (int16 v is the float v / 32768).  max_samples: the most of its own
+    // samples the stream will take (0: 60 s; at most one hour).  audio_stream_begin returns the stream id, -1 on error; a failed
+    // push returns no frames and sets *ok = false when ok is given.
     int audio_stream_begin(int64_t max_samples = 0);
+    int audio_stream_begin(int64_t max_samples, int sample_rate /* 24000: the overload above */, bool pcm16 = false);
     std::vector<int64_t> audio_stream_push(int id, const float* pcm, size_t n, bool finish = false, bool* ok = nullptr);
+    std::vector<int64_t> audio_stream_push(int id, const int16_t* pcm, size_t n, bool finish = false, bool* ok = nullptr);   // streams begun with pcm16
     void audio_stream_end(int id);
     // In-context voice clone ([HINT]): the reference audio is encoded, the text becomes reference text +
     // target text (ref_text_ids go between token_ids' three role ids and its text) and the utterance is continued behind the
@@ -168,6 +171,7 @@ public:
 
 private:
     bool wrap_text(const std::string& text, std::vector<int64_t>& ids) const;
+    std::vector<int64_t> audio_stream_push_any(int id, const void* pcm, size_t n, bool finish, bool* ok, bool pcm16);
     q3tts_engine* h_ = nullptr;
     q3tts_tokenizer* tok_ = nullptr;
     bool ready_ = false;

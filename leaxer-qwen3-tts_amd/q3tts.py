@@ -112,6 +112,8 @@ EXPORTS = [
     "q3tts_config_enable_audio_encoder", "q3tts_has_audio_encoder", "q3tts_audio_encode_len", "q3tts_audio_encode_host",
     "q3tts_audio_stream_begin", "q3tts_audio_stream_push_len", "q3tts_audio_stream_push_host", "q3tts_audio_stream_push_batch_host",
     "q3tts_audio_stream_info", "q3tts_audio_stream_end",
+    "q3tts_audio_stream_begin_rate", "q3tts_audio_stream_format", "q3tts_audio_stream_push_any_host", "q3tts_audio_stream_push_batch_any_host",
+    "q3tts_resample_stream_emitted",
     "q3tts_audio_encode_batch_host", "q3tts_audio_encode_latents_host", "q3tts_audio_encode_batch_latents_host", "q3tts_last_audio_encode_ms", "q3tts_test_audio_encoder_transformer_host",
     "q3tts_codec_stream_prime_batch_host", "q3tts_slots_codec_prime", "q3tts_codec_stream_info", "q3tts_synthesize_continue_stream_host",
 ]
@@ -238,6 +240,12 @@ def lib():
     L.q3tts_audio_stream_push_batch_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.q3tts_audio_stream_info.argtypes = [vp, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int64)]
     L.q3tts_audio_stream_end.argtypes = [vp, i32]
+    L.q3tts_audio_stream_begin_rate.argtypes = [vp, i32, i32, i64, C.POINTER(C.c_int)]
+    L.q3tts_audio_stream_format.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int)]
+    L.q3tts_audio_stream_push_any_host.argtypes = [vp, i32, vp, i64, i32, vp, i32, C.POINTER(C.c_int32)]
+    L.q3tts_audio_stream_push_batch_any_host.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.q3tts_resample_stream_emitted.argtypes = [i32, i32, i64, i32]
+    L.q3tts_resample_stream_emitted.restype = i64
     L.q3tts_audio_encode_latents_host.argtypes = [vp, vp, i64, vp, vp, i32, C.POINTER(C.c_int32)]
     L.q3tts_test_audio_encoder_transformer_host.argtypes = [vp, vp, i32, vp]
     L.q3tts_codec_decode_chunked_host.argtypes = [vp, vp, i32, i32, i32, vp, i64, C.POINTER(i64)]
@@ -900,12 +908,30 @@ class Engine:
 
     # ---- audio -> codes while the audio arrives (q3tts_audio_stream_*) ----
     def audio_stream_begin(self, max_samples=0):
-        """a new encoder stream for at most max_samples samples at 24 kHz (0: 60 s; at most one hour) -> stream id"""
+        """a new encoder stream for at most max_samples samples at 24 kHz (0: 60 s; at most one hour) -> stream id;
+        audio_stream_begin_rate at 24 000 Hz / float32"""
         if int(max_samples) < 0:
             raise ValueError("max_samples must be 0 (60 s) or positive")
+        return Engine.audio_stream_begin_rate(self, 24000, "float32", max_samples)
+
+    def audio_stream_begin_rate(self, sample_rate, dtype="float32", max_samples=0):
+        """a new encoder stream at sample_rate (1 .. 384000) whose samples are pushed as dtype "float32" or "int16", for at most
+        max_samples of its OWN samples (0: 60 s; at most one hour) -> stream id (q3tts_audio_stream_begin_rate).  Other than 24 kHz
+        float32 the stream resamples on the GPU on the way in, bit-identical to audio_encode_batch of the whole audio at that rate
+        (int16 v is the float v / 32768)."""
+        if int(max_samples) < 0:
+            raise ValueError("max_samples must be 0 (60 s) or positive")
+        fmt = _pcm_format(dtype)
         sid = C.c_int(-1)
-        self._ck(self.L.q3tts_audio_stream_begin(self.h, int(max_samples), C.byref(sid)))
+        self._ck(self.L.q3tts_audio_stream_begin_rate(self.h, int(sample_rate), fmt, int(max_samples), C.byref(sid)))
+        self.__dict__.setdefault("_audio_stream_fmt", {})[int(sid.value)] = (int(sample_rate), fmt == PCM_S16)
         return int(sid.value)
+
+    def audio_stream_format(self, sid):
+        """(sample_rate, dtype name) the stream was begun with"""
+        sr, fmt = C.c_int32(0), C.c_int(0)
+        self._ck(self.L.q3tts_audio_stream_format(self.h, int(sid), C.byref(sr), C.byref(fmt)))
+        return int(sr.value), ("int16" if fmt.value == PCM_S16 else "float32")
 
     def audio_stream_push_len(self, sid, n_samples, finish=False):
         """frames the next push of n_samples to this stream would return (host-only)"""
@@ -914,8 +940,14 @@ class Engine:
         return int(self._ck(self.L.q3tts_audio_stream_push_len(self.h, int(sid), int(n_samples), 1 if finish else 0)))
 
     @staticmethod
-    def _stream_pcm(pcm, what="pcm"):
+    def _stream_pcm(pcm, what="pcm", s16=False):
         a = np.asarray(pcm)
+        if s16:
+            if a.size and a.dtype != np.int16:
+                raise ValueError("%s: expected int16 samples (the stream was begun with dtype int16), got dtype %s" % (what, a.dtype))
+            if a.ndim > 1 and a.size != max(a.shape):
+                raise ValueError("%s: expected mono samples [n], got shape %s" % (what, (a.shape,)))
+            return np.ascontiguousarray(a, np.int16).reshape(-1)
         if a.size and a.dtype.kind != "f":
             raise ValueError("%s: expected float samples (mono, 24 kHz), got dtype %s" % (what, a.dtype))
         if a.ndim > 1 and a.size != max(a.shape):
@@ -924,7 +956,7 @@ class Engine:
 
     def audio_stream_push_batch(self, sids, pcms, finish=None, want_latents=False):
         """one push to each of many streams in ONE call (q3tts_audio_stream_push_batch_host): pcms[i] are stream sids[i]'s next samples
-        (mono float, 24 kHz; may be empty), finish[i] ends stream i's audio (None: none; a bool applies to all).  Returns the list of
+        (mono, at the stream's own rate, float or, for a stream begun with dtype int16, and only for it, int16; may be empty), finish[i] ends stream i's audio (None: none; a bool applies to all).  Returns the list of
         the NEW codes [F_i][n_groups] per stream, bit-identical to audio_encode of each stream's concatenated audio; want_latents:
         (that list, the list of latents [F_i][enc_hidden])."""
         n = len(sids)
@@ -935,13 +967,25 @@ class Engine:
             raise ValueError("finish: one flag per stream, one for all, or None")
         if len(set(int(s) for s in sids)) != n:
             raise ValueError("a stream may appear once per push")
-        keep = [Engine._stream_pcm(a, "pcms[%d]" % i) for i, a in enumerate(pcms)]
         if n == 0:
             return ([], []) if want_latents else []
+        # int16 arrays for the streams begun with dtype int16, and only for them (begin recorded it; an id it never saw counts as float32
+        # and is the engine's to refuse)
+        begun = vars(self).get("_audio_stream_fmt", {})
+        keep = [Engine._stream_pcm(a, "pcms[%d]" % i, s16=begun.get(int(sids[i]), (24000, False))[1]) for i, a in enumerate(pcms)]
         per = 1
         for r in list(self.cfg.enc_ratios)[: self.cfg.enc_n_ratios]:
             per *= int(r)
-        caps = [a.size // (2 * per) + 2 for a in keep]
+        # frames of room per stream, from the host rule: the 24 kHz samples this push adds, E(after) - E(before)
+        caps = []
+        for i, a in enumerate(keep):
+            stt = self._stream_state(sids[i])
+            if stt is None:                                                # not an open stream: the call below says so
+                caps.append(2)
+                continue
+            rate, _, got, fed = stt
+            new24 = resample_stream_emitted(rate, 24000, got + a.size, fin[i]) - fed
+            caps.append(max(new24, 0) // (2 * per) + 2)
         outs = [np.zeros((cp, self.cfg.n_groups), np.int64) for cp in caps]
         lats = [np.zeros((cp, max(self.cfg.enc_hidden, 1)), np.float32) for cp in caps] if want_latents else None
         ptrs = (C.c_void_p * n)(*[a.ctypes.data if a.size else None for a in keep])
@@ -952,12 +996,22 @@ class Engine:
         fl = np.array(fin, np.int32)
         cp = np.array(caps, np.int32)
         nf = np.zeros(n, np.int32)
-        self._ck(self.L.q3tts_audio_stream_push_batch_host(self.h, n, _p(ids), ptrs, _p(ns), _p(fl), optrs, lptrs, _p(cp), _p(nf)))
+        push = self.L.q3tts_audio_stream_push_batch_any_host if any(a.dtype == np.int16 for a in keep) else self.L.q3tts_audio_stream_push_batch_host
+        self._ck(push(self.h, n, _p(ids), ptrs, _p(ns), _p(fl), optrs, lptrs, _p(cp), _p(nf)))
         codes = [o[: nf[i]] for i, o in enumerate(outs)]
         return (codes, [a[: nf[i]] for i, a in enumerate(lats)]) if want_latents else codes
 
+    def _stream_state(self, sid):
+        """(rate, is int16, samples received, 24 kHz samples fed to the encoder) of an open stream, None for an id the engine refuses"""
+        sr, fmt, ns = C.c_int32(0), C.c_int(0), C.c_int64(0)
+        if self.L.q3tts_audio_stream_format(self.h, int(sid), C.byref(sr), C.byref(fmt)) != 0:
+            return None
+        if self.L.q3tts_audio_stream_info(self.h, int(sid), C.byref(ns), None, None, None) != 0:
+            return None
+        return int(sr.value), fmt.value == PCM_S16, int(ns.value), resample_stream_emitted(int(sr.value), 24000, int(ns.value), False)
+
     def audio_stream_push(self, sid, pcm, finish=False, want_latents=False):
-        """pcm (mono float, 24 kHz, any length up to 60 s) appended to stream sid -> the NEW frames' codes [F][n_groups];
+        """pcm (mono, the stream's own rate and sample format, any length up to 60 s) appended to stream sid -> the NEW frames' codes [F][n_groups];
         finish: the stream's audio ends here.  want_latents: (codes, latents [F][enc_hidden])"""
         r = self.audio_stream_push_batch([sid], [pcm], [finish], want_latents)
         return (r[0][0], r[1][0]) if want_latents else r[0]
@@ -970,16 +1024,27 @@ class Engine:
 
     def audio_stream_end(self, sid):
         self._ck(self.L.q3tts_audio_stream_end(self.h, int(sid)))
+        vars(self).get("_audio_stream_fmt", {}).pop(int(sid), None)
 
     def audio_encode_long(self, pcm24k, chunk_samples=96000):
         """audio_encode for any length up to one hour: the clip pushed chunk_samples at a time through one stream -> codes
         [F][n_groups], bit-identical to what audio_encode gives where it accepts the clip"""
         a = Engine._stream_pcm(pcm24k, "pcm24k")
+        return Engine._encode_long(self, a, chunk_samples, 24000, "pcm24k")
+
+    def audio_encode_long_rate(self, pcm, sample_rate, chunk_samples=None):
+        """audio_encode_long for a clip at sample_rate (mono float32, or int16), pushed chunk_samples of its own samples at a time
+        (None: 4 s) through one stream begun at that rate -> codes [F][n_groups], bit-identical to what audio_encode_batch gives at
+        that rate where it accepts the clip.  Nothing is resampled on the host."""
+        a = Engine._stream_pcm(pcm, "pcm", s16=np.asarray(pcm).dtype == np.int16)
+        return Engine._encode_long(self, a, 4 * int(sample_rate) if chunk_samples is None else chunk_samples, sample_rate, "pcm")
+
+    def _encode_long(self, a, chunk_samples, sample_rate, what):
         if int(chunk_samples) < 1:
             raise ValueError("chunk_samples must be at least 1")
         if a.size < 1:
-            raise ValueError("pcm24k: no samples")
-        with AudioEncodeStream(self, a.size) as st:
+            raise ValueError("%s: no samples" % what)
+        with AudioEncodeStream(self, a.size, sample_rate=sample_rate, dtype="int16" if a.dtype == np.int16 else "float32") as st:
             for i in range(0, a.size, int(chunk_samples)):
                 st.push(a[i : i + int(chunk_samples)])
             st.finish()
@@ -1489,6 +1554,27 @@ def resample(audio, src_rate, dst_rate):
     return out[:n]
 
 
+def resample_stream_emitted(src_rate, dst_rate, n_received, finish=False):
+    """q3tts_resample_stream_emitted: the output samples a stream at src_rate has emitted in all once it holds n_received samples
+    (finish: resample's own length).  A push's length is the difference of two calls.  Host-only."""
+    n = int(lib().q3tts_resample_stream_emitted(int(src_rate), int(dst_rate), int(n_received), 1 if finish else 0))
+    if n < 0:
+        raise ValueError("resample_stream_emitted: rates must be positive and n_received not negative")
+    return n
+
+
+PCM_F32, PCM_S16 = 0, 1
+
+
+def _pcm_format(dtype):
+    name = np.dtype(dtype).name if not isinstance(dtype, str) else dtype
+    if name in ("float32", "f32"):
+        return PCM_F32
+    if name in ("int16", "s16"):
+        return PCM_S16
+    raise ValueError("dtype must be float32 or int16, got %r" % (dtype,))
+
+
 def log_mel(audio):
     """MelExtractor::extract with the clone path's settings (tts_onnx.cpp:347-354): [128][frames].  Host-only."""
     a = np.ascontiguousarray(audio, np.float32)
@@ -1585,11 +1671,12 @@ def rng_uniform(seed, stream, frame, group):
 
 class AudioEncodeStream:
     """One encoder stream as a context manager: push(pcm) -> the new codes, finish() -> the last ones, .codes: everything so far
-    [F][n_groups].  The concatenation is bit-identical to Engine.audio_encode of the concatenated audio (24 kHz mono float)."""
+    [F][n_groups].  The concatenation is bit-identical to Engine.audio_encode_batch of the concatenated audio at sample_rate (mono;
+    dtype float32 or int16)."""
 
-    def __init__(self, engine, max_samples=0):
+    def __init__(self, engine, max_samples=0, sample_rate=24000, dtype="float32"):
         self.engine = engine
-        self.sid = engine.audio_stream_begin(max_samples)
+        self.sid = engine.audio_stream_begin_rate(sample_rate, dtype, max_samples)
         self._parts = []
         self.finished = False
 

@@ -97,6 +97,11 @@ int main(int argc, char** argv) {
             if (sr <= 0) { fprintf(stderr, "read_wav: samples without a rate\n"); return 2; }
             if (sr <= 384000 && a.size() < 200000) {
                 std::vector<float> rs = q3::resample_linear(a, sr, 24000);
+                // the streaming rule of the same resampler: the finished length is resample_linear's, and what is emitted before never exceeds it
+                const int64_t n = (int64_t)a.size(), held = q3::resample_stream_emitted(sr, 24000, n, false);
+                if (q3::resample_stream_emitted(sr, 24000, n, true) != (int64_t)rs.size() || held < 0 || held > (int64_t)rs.size() ||
+                    held < q3::resample_stream_emitted(sr, 24000, n - 1, false)) { fprintf(stderr, "resample_stream_emitted: disagrees with resample_linear\n"); return 2; }
+                checksum += held;
                 int frames = 0;
                 std::vector<float> mel = q3::log_mel(rs, q3::MelSpec(), &frames);
                 checksum += frames + (long long)mel.size();
