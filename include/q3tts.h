@@ -631,6 +631,59 @@ int q3tts_audio_stream_info(q3tts_engine* e, int stream_id, int64_t* n_samples, 
 /* closes the stream (finished or not); its id and buffers serve a later q3tts_audio_stream_begin */
 int q3tts_audio_stream_end(q3tts_engine* e, int stream_id);
 
+/* ---- audio out at the sink's rate: carried-state band-limited resampler ([HINT] no counterpart in the reference, whose main.cpp writes
+ * 24 kHz only) ----
+ * Everything above delivers 24 kHz float.  A sink delivers the same audio at its own rate R (4 000 .. 192 000 Hz) as float
+ * (Q3TTS_PCM_F32) or int16 (Q3TTS_PCM_S16), resampled on the GPU between the vocoder and the device -> host copy, all streams of a push
+ * in one launch.  24 000 / Q3TTS_PCM_F32 is "no sink": no launch, the same bytes as before.
+ * The resampler: g = gcd(R, 24000), L = R / g, M = 24000 / g; output j sits at input position j M / L.  s = min(1, R / 24000), half-width
+ * H = 16 / s input samples, half = ceil(H), taps = 2 half, cut-off f = 0.92 s.  Table row p (0 <= p < L), tap t: d = (t - half + 1) - p / L,
+ * h = f sinc(f d) I0(10 sqrt(1 - (d / H)^2)) / I0(10) for |d| < H, else 0 (sinc(x) = sin(pi x) / (pi x)); each row is formed in double,
+ * divided by its own sum and rounded to float.  Output j: kc = floor(j M / L), p = (j M) mod L, y[j] = sum_t tab[p][t] x[kc - half + 1 + t]
+ * with t ascending in fp32 (unfused), x[k] = 0 for k < 0 and, once the sink is finished, for k >= n.  A sample's bits depend on its
+ * absolute index alone: never on how the audio was cut into pushes or on which sinks shared a launch.
+ * A sink that has received N samples and is not finished has emitted E(N) = max(0, ceil((N - half) L / M)) outputs: those whose last
+ * tap kc + half <= N - 1 has arrived (latency: half input samples; 0.67 ms at >= 24 kHz, 2 ms at 8 kHz, 4 ms at 4 kHz).  Finished, it has
+ * emitted ceil(n L / M).  A push delivers E(after) - E(before).  R = 24000: no filter, no latency, E(N) = N.
+ * int16 is the CLI's rule (save_wav16): clip to [-1, 1], then (int16_t)(v * 32767.0f), truncating; converted on the GPU.
+ * Known limit: a primed stream's sink (q3tts_codec_stream_prime_batch_host, q3tts_synthesize_continue_stream_host) starts from silence,
+ * x[k] = 0 for k < 0, so behind a prefix the first `half` input samples' worth of output differs from a resample of prefix +
+ * continuation.  At 24 kHz the seam stays exact. */
+/* Host only, no engine.  The plan for `rate`: any output pointer may be NULL; table (NULL ok) receives the L * taps floats the device
+ * uses when cap >= L * taps.  -1 for a rate outside 4 000 .. 192 000 or one whose table would exceed 2^22 floats (191 999: L = 191 999);
+ * q3tts_sink_last_error() then names the rate (thread-local, valid until the thread's next sink_plan / sink_emitted call). */
+int q3tts_sink_plan(int32_t rate, int32_t* L, int32_t* M, int32_t* half, int32_t* taps, float* table, int64_t cap);
+const char* q3tts_sink_last_error(void);
+/* Host only: outputs a sink at `rate` has emitted in all after n_received samples at 24 kHz (finished != 0: the whole clip's
+ * ceil(n L / M)).  -1 for a rate q3tts_sink_plan refuses or n_received < 0. */
+int64_t q3tts_sink_emitted(int32_t rate, int64_t n_received, int finished);
+/* Sinks on their own: the stage by itself, fed 24 kHz float from the host.  A sink accepts at most one hour of input (86 400 000
+ * samples), a push at most 1 440 000.  At most 4096 sinks are open at a time (vocoder streams' sinks included). */
+int q3tts_pcm_sink_begin(q3tts_engine* e, int32_t sample_rate, int format, int* sink_id);
+/* n sinks (distinct, open, not finished), sink i given n_in[i] >= 0 more samples pcm24[i]; finish[i] != 0 (finish NULL: none) flushes
+ * the tail with this push and closes the sink's audio (n_in[i] == 0 allowed).  out[i] is float* or int16_t* by the sink's format,
+ * with room for cap_samples; out_len[i] is the push's length by the rule above (min(out_len, cap_samples) samples are written).  The call
+ * is validated completely before any sink moves.  n_in[i] == 0 without finish leaves the sink as it was. */
+int q3tts_pcm_sink_push_batch_host(q3tts_engine* e, int n, const int32_t* sink_ids, const float* const* pcm24, const int64_t* n_in,
+                                   const uint8_t* finish, void* const* out, int64_t cap_samples, int64_t* out_len);
+int q3tts_pcm_sink_end(q3tts_engine* e, int sink_id);
+/* Vocoder streams.  A stream delivers through a sink from its first sample on: refused, by name, once the stream has delivered a
+ * sample.  24 000 / Q3TTS_PCM_F32 takes the sink away again. */
+int q3tts_codec_stream_set_sink(q3tts_engine* e, int stream_id, int32_t sample_rate, int format);
+/* q3tts_codec_stream_push_batch_host with pcm_out[s] read in stream s's format (float without a sink) and pcm_cap / pcm_len counted in
+ * its samples.  finish[s] != 0 (NULL: none; only for streams with a sink) flushes the sink's tail with this push; a push of 0 frames
+ * with finish is allowed.  The float entries keep serving streams without a sink and refuse a stream with one by name. */
+int q3tts_codec_stream_push_batch_any_host(q3tts_engine* e, int n_streams, const int32_t* stream_ids, const int64_t* codes, const int32_t* frame_offsets,
+                                           void* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, const uint8_t* finish);
+/* The scheduler: one setter for the four streaming entries (q3tts_synthesize_stream_host, _live_host, _instruct_host with a callback,
+ * _continue_stream_host).  While a sink is set they deliver through sink->cb in the sink's format (pcm is float* or int16_t*), their
+ * own cb argument may be NULL, and a non-NULL pcm_out is refused by name.  The finished = 1 call carries the flushed tail, so an
+ * utterance's calls add up to ceil(n24 L / M) samples; pcm_len counts the sink's samples.  Codes, frame counts and RNG use are
+ * untouched.  sink == NULL: none.  The struct is copied. */
+typedef int (*q3tts_audio_any_cb)(void* user, int utt, int frame_begin, int frame_end, const void* pcm, int64_t n_samples, int finished);
+typedef struct { int32_t sample_rate; int32_t format; q3tts_audio_any_cb cb; void* user; } q3tts_sink;
+int q3tts_engine_set_sink(q3tts_engine* e, const q3tts_sink* sink);
+
 /* ---- text front end: the reference's byte-level BPE tokenizer ---- */
 /* Replaces leaxer_qwen::io::load_vocab / load_merges / is_tokenizer_ready / tokenize (reference
  * src/io/tokenizer.h:13-22, src/io/tokenizer.cpp:538-561) with the same ids for the same files and text.

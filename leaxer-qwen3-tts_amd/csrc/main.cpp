@@ -40,6 +40,19 @@ static int save_wav16(const char* path, const std::vector<float>& audio, uint32_
     return ok ? 0 : -1;
 }
 
+// the same file from samples that already are int16 (--out-rate: the engine's sink converted them on the GPU, by the rule above)
+static int save_wav16_raw(const char* path, const std::vector<int16_t>& s, uint32_t rate) {
+    FILE* f = fopen(path, "wb");
+    if (!f) return -1;
+    const uint32_t data = (uint32_t)(s.size() * 2), riff = 36 + data, fmt = 16, bytes_per_s = rate * 2;
+    const uint16_t pcm = 1, ch = 1, align = 2, bits = 16;
+    bool ok = put(f, "RIFF", 4) && put(f, &riff, 4) && put(f, "WAVEfmt ", 8) && put(f, &fmt, 4) && put(f, &pcm, 2) && put(f, &ch, 2) &&
+              put(f, &rate, 4) && put(f, &bytes_per_s, 4) && put(f, &align, 2) && put(f, &bits, 2) && put(f, "data", 4) && put(f, &data, 4);
+    ok = ok && put(f, s.data(), s.size() * 2);
+    fclose(f);
+    return ok ? 0 : -1;
+}
+
 static void usage(const char* prog) {
     printf("Usage: %s [options]\n\nQwen3-TTS synthesis on MI355X (HIP)\n\nOptions:\n", prog);
     printf("  -m, --model DIR       model directory holding model.q3w, or synthetic:<seed> / synthetic-1.7b:<seed> (required)\n");
@@ -62,6 +75,7 @@ static void usage(const char* prog) {
     printf("  --max-tokens N        max codec frames (default: 2048)\n  --seed N              sampling seed (default: 0)\n");
     printf("  --stream-chunk N      with --tokens: decode audio every N frames while generating (same samples as the one-shot decode);\n");
     printf("                        combines with --continue-codes and with --ref + --ref-text / --ref-tokens (the prefix is history, never decoded)\n");
+    printf("  --out-rate R          write the WAV at R Hz (4000 .. 192000; default 24000): band-limited resampling on the GPU, in the stream's sink with --stream-chunk\n");
     printf("  --feed K              with --stream-chunk: hand the text to the engine K tokens at a time while it generates (live text; same codes, and with --save-codes the same samples as without --feed)\n  -h, --help\n");
 }
 
@@ -136,7 +150,7 @@ int main(int argc, char** argv) {
     bool have_prompt = false;
     SamplingParams sp;
     uint64_t seed = 0;
-    int stream_chunk = 0, feed = 0, encode_chunk = 0;
+    int stream_chunk = 0, feed = 0, encode_chunk = 0, out_rate = config::SAMPLE_RATE;
     bool have_encode_chunk = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -164,6 +178,7 @@ int main(int argc, char** argv) {
         else if (a == "--seed" && more) seed = strtoull(argv[++i], nullptr, 10);
         else if (a == "--stream-chunk" && more) stream_chunk = atoi(argv[++i]);
         else if (a == "--feed" && more) feed = atoi(argv[++i]);
+        else if (a == "--out-rate" && more) out_rate = atoi(argv[++i]);
     }
     const bool icl = !ref_text.empty() || !ref_tokens.empty();
     if (have_encode_chunk && (encode.empty() || encode_chunk < 1)) {
@@ -235,8 +250,21 @@ int main(int argc, char** argv) {
     TTSEngine engine(model, icl);
     if (!engine.is_ready()) { fprintf(stderr, "Error: %s\n", engine.get_error().c_str()); return 1; }
     engine.set_seed(seed);
+    // --out-rate: the engine delivers int16 at that rate (the streaming paths through their sink, whole clips through convert_output
+    // below); 24000 leaves everything as it is.  `audio` then holds the chunks' int16 samples, two to a float, counted by audio16
+    const bool resample_out = out_rate != config::SAMPLE_RATE;
+    if (resample_out && !engine.set_output_format(out_rate, true)) { fprintf(stderr, "Error: --out-rate %d: %s\n", out_rate, engine.get_error().c_str()); return 1; }
+    std::vector<int16_t> audio16;
     printf("Synthesizing...\n");
     std::vector<float> audio;
+    bool streamed16 = false;
+    auto have_audio = [&]() { return !audio.empty() || !audio16.empty(); };
+    auto take = [&](const float* p, size_t n) {   // a streaming chunk: float at 24 kHz, or the sink's int16 behind the same pointer
+        if (!resample_out) { audio.insert(audio.end(), p, p + n); return; }
+        const int16_t* q = reinterpret_cast<const int16_t*>(p);
+        audio16.insert(audio16.end(), q, q + n);
+        streamed16 = true;
+    };
     if (!ref.empty() && !icl) {
         if (!engine.has_speaker_encoder()) { fprintf(stderr, "Error: speaker encoder not available for voice clone\n"); return 1; }
     }
@@ -264,16 +292,16 @@ int main(int argc, char** argv) {
             tids.insert(tids.end(), ids.begin() + 3, ids.end());
             size_t chunks = 0;
             const int nf = engine.synthesize_tokens_continue_streaming(tids, ref_codes, lang_of(lang), sp, stream_chunk, [&](const float* p, size_t n, bool) {
-                if (n > 0 && chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / config::SAMPLE_RATE);
-                audio.insert(audio.end(), p, p + n);
+                if (n > 0 && chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / out_rate);
+                take(p, n);
                 return false;
             }, &all);
-            if (nf < 0) audio.clear();
+            if (nf < 0) { audio.clear(); audio16.clear(); }
             else printf("Streamed %d new frames in %zu chunks\n", nf - (int)(ref_codes.size() / (size_t)engine.n_groups()), chunks);
         } else audio = engine.synthesize_clone_icl(ids, rids, ref, lang_of(lang), sp, &all);
         const size_t G = (size_t)engine.n_groups();
-        if (!audio.empty()) printf("In-context clone: %zu reference text tokens, %zu frames in all\n", rids.size(), all.size() / G);
-        if (!audio.empty() && !save_codes.empty()) {
+        if (have_audio()) printf("In-context clone: %zu reference text tokens, %zu frames in all\n", rids.size(), all.size() / G);
+        if (have_audio() && !save_codes.empty()) {
             if (!write_codes_file(save_codes, all, G)) { fprintf(stderr, "Error: failed to write %s\n", save_codes.c_str()); return 1; }
             printf("Codes saved to: %s\n", save_codes.c_str());
         }
@@ -307,13 +335,13 @@ int main(int argc, char** argv) {
         size_t chunks = 0;
         const size_t G = (size_t)engine.n_groups();
         const int nf = engine.synthesize_tokens_continue_streaming(ids, prefix, lang_of(lang), sp, stream_chunk, [&](const float* p, size_t n, bool) {
-            if (n > 0 && chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / config::SAMPLE_RATE);
-            audio.insert(audio.end(), p, p + n);
+            if (n > 0 && chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / out_rate);
+            take(p, n);
             return false;
         }, &all);
-        if (nf < 0) audio.clear();
+        if (nf < 0) { audio.clear(); audio16.clear(); }
         else printf("Frames: %zu recorded + %zu new, streamed in %zu chunks\n", prefix.size() / G, all.size() / G - prefix.size() / G, chunks);
-        if (!audio.empty() && !save_codes.empty()) {
+        if (have_audio() && !save_codes.empty()) {
             if (!write_codes_file(save_codes, all, G)) { fprintf(stderr, "Error: failed to write %s\n", save_codes.c_str()); return 1; }
             printf("Codes saved to: %s\n", save_codes.c_str());
         }
@@ -322,8 +350,8 @@ int main(int argc, char** argv) {
         if (ids.empty() && !frame_prompt(engine, prompt, ids)) return 1;   // -p: the framing of --tokens around the tokenised text
         size_t chunks = 0, given = 0, polls = 0;
         auto on_audio = [&](int, const float* p, size_t n, bool) {
-            if (n > 0 && chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / config::SAMPLE_RATE);
-            audio.insert(audio.end(), p, p + n);
+            if (n > 0 && chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / out_rate);
+            take(p, n);
             return false;
         };
         std::vector<std::vector<int64_t>> codes;
@@ -337,7 +365,7 @@ int main(int argc, char** argv) {
                 return true;
             }, lang_of(lang), sp, stream_chunk, on_audio, save_codes.empty() ? nullptr : &codes);
         } else nf = engine.synthesize_tokens_batch_streaming({ ids }, lang_of(lang), sp, stream_chunk, on_audio, &codes);
-        if (nf.empty()) audio.clear();
+        if (nf.empty()) { audio.clear(); audio16.clear(); }
         else {
             printf("Streamed %d frames in %zu chunks\n", nf[0], chunks);
             if (feed > 0) printf("Text fed in %zu pieces of up to %d tokens\n", polls, feed);
@@ -346,13 +374,22 @@ int main(int argc, char** argv) {
             if (!write_codes_file(save_codes, codes[0], (size_t)engine.n_groups())) { fprintf(stderr, "Error: failed to write %s\n", save_codes.c_str()); return 1; }
             printf("Codes saved to: %s\n", save_codes.c_str());
         }
+    } else if (!ids.empty() && stream_chunk > 0 && resample_out) {   // the same through the scheduler, whose streams carry the sink
+        size_t chunks = 0;
+        const std::vector<int> nf = engine.synthesize_tokens_batch_streaming({ ids }, lang_of(lang), sp, stream_chunk, [&](int, const float* p, size_t n, bool) {
+            if (n > 0 && chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / out_rate);
+            take(p, n);
+            return false;
+        });
+        if (nf.empty()) audio16.clear();
+        else printf("Streamed %d frames in %zu chunks of %d frames\n", nf[0], chunks, stream_chunk);
     } else if (!ids.empty() && stream_chunk > 0) {   // chunks of audio as their frames are generated; the file holds their concatenation
         size_t chunks = 0;
         const int nf = engine.synthesize_tokens_streaming(ids, lang_of(lang), sp, stream_chunk, -1, [&](const float* p, size_t n) {
-            if (chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / config::SAMPLE_RATE);
-            audio.insert(audio.end(), p, p + n);
+            if (chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / out_rate);
+            take(p, n);
         });
-        if (nf < 0) audio.clear();
+        if (nf < 0) { audio.clear(); audio16.clear(); }
         else printf("Streamed %d frames in %zu chunks\n", nf, chunks);
     } else if (!ids.empty() && (!save_codes.empty() || !continue_codes.empty())) {
         if (!prefix.empty() && prefix_groups != (size_t)engine.n_groups()) {
@@ -362,14 +399,25 @@ int main(int argc, char** argv) {
         std::vector<int64_t> all;
         audio = engine.synthesize_tokens_continue(ids, prefix, lang_of(lang), sp, &all);
         const size_t G = (size_t)engine.n_groups();
-        if (!audio.empty()) printf("Frames: %zu recorded + %zu new\n", prefix.size() / G, all.size() / G - prefix.size() / G);
-        if (!audio.empty() && !save_codes.empty()) {
+        if (have_audio()) printf("Frames: %zu recorded + %zu new\n", prefix.size() / G, all.size() / G - prefix.size() / G);
+        if (have_audio() && !save_codes.empty()) {
             if (!write_codes_file(save_codes, all, G)) { fprintf(stderr, "Error: failed to write %s\n", save_codes.c_str()); return 1; }
             printf("Codes saved to: %s\n", save_codes.c_str());
         }
     } else if (!ids.empty()) {
         audio = engine.synthesize_tokens(ids, lang_of(lang), sp);
     } else audio = engine.synthesize(prompt, lang_of(lang), sp);
+    if (resample_out) {
+        if (!streamed16) {   // a whole clip at 24 kHz: one push + finish through the resampler the streams use
+            if (audio.empty()) { fprintf(stderr, "Error: synthesis failed\n"); return 1; }
+            if (!engine.convert_output(audio, nullptr, &audio16)) { fprintf(stderr, "Error: --out-rate conversion failed\n"); return 1; }
+        }
+        if (audio16.empty()) { fprintf(stderr, "Error: synthesis failed\n"); return 1; }
+        printf("Generated %.2f seconds of audio\n", (float)audio16.size() / out_rate);
+        if (save_wav16_raw(output.c_str(), audio16, (uint32_t)out_rate) != 0) { fprintf(stderr, "Error: failed to write WAV\n"); return 1; }
+        printf("Saved to: %s\n", output.c_str());
+        return 0;
+    }
     if (audio.empty()) { fprintf(stderr, "Error: synthesis failed\n"); return 1; }
     printf("Generated %.2f seconds of audio\n", (float)audio.size() / config::SAMPLE_RATE);
     if (save_wav16(output.c_str(), audio, config::SAMPLE_RATE) != 0) { fprintf(stderr, "Error: failed to write WAV\n"); return 1; }

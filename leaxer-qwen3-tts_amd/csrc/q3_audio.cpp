@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <stdexcept>
 
 namespace q3 {
 
@@ -126,6 +127,68 @@ int64_t resample_stream_emitted(int src_rate, int dst_rate, int64_t n, bool fini
     while (e > 0 && tap(e - 1) > n - 2) --e;
     while (tap(e) <= n - 2) ++e;
     return std::min(e, len);
+}
+
+// ---- sink plans (q3_audio.h) ----
+static double bessel_i0(double x) {   // power series: converges fast for the |x| <= 10 used here
+    const double q = x * x / 4.0;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 200; ++k) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < sum * 1e-18) break;
+    }
+    return sum;
+}
+void sink_plan_dims(int rate, SinkPlan* plan) {
+    if (rate < kSinkMinRate || rate > kSinkMaxRate)
+        throw std::invalid_argument("pcm sink: sample rate " + std::to_string(rate) + " is outside " + std::to_string(kSinkMinRate) + " .. " + std::to_string(kSinkMaxRate));
+    SinkPlan d;
+    d.rate = rate;
+    if (rate != 24000) {
+        int a = rate, b = 24000;
+        while (b) { const int t = a % b; a = b; b = t; }
+        d.L = rate / a; d.M = 24000 / a;
+        // half = ceil(16 / s) = ceil(16 * 24000 / R) below 24 kHz, in integers
+        d.half = rate >= 24000 ? 16 : (int)((16LL * 24000 + rate - 1) / rate);
+        d.taps = 2 * d.half;
+        if ((int64_t)d.L * d.taps > kSinkMaxTable)
+            throw std::invalid_argument("pcm sink: sample rate " + std::to_string(rate) + " needs a table of " + std::to_string((int64_t)d.L * d.taps) + " floats (" +
+                        std::to_string(d.L) + " phases x " + std::to_string(d.taps) + " taps), more than " + std::to_string(kSinkMaxTable));
+    }
+    *plan = d;
+}
+SinkPlan sink_plan(int rate) {
+    SinkPlan d;
+    sink_plan_dims(rate, &d);
+    if (d.taps == 0) return d;
+    const double pi = 3.14159265358979323846;
+    const double s = rate >= 24000 ? 1.0 : (double)rate / 24000.0, H = 16.0 / s, f = 0.92 * s, i0b = bessel_i0(10.0);
+    d.table.assign((size_t)d.L * d.taps, 0.f);
+    std::vector<double> row((size_t)d.taps);
+    for (int p = 0; p < d.L; ++p) {
+        double sum = 0.0;
+        for (int t = 0; t < d.taps; ++t) {
+            const double x = (double)(t - d.half + 1) - (double)p / (double)d.L;
+            double h = 0.0;
+            if (std::fabs(x) < H) {
+                const double fx = f * x, r = x / H;
+                const double sinc = fx == 0.0 ? 1.0 : std::sin(pi * fx) / (pi * fx);
+                h = f * sinc * bessel_i0(10.0 * std::sqrt(1.0 - r * r)) / i0b;
+            }
+            row[(size_t)t] = h;
+            sum += h;
+        }
+        for (int t = 0; t < d.taps; ++t) d.table[(size_t)p * d.taps + t] = (float)(row[(size_t)t] / sum);
+    }
+    return d;
+}
+int64_t sink_emitted(const SinkPlan& d, int64_t n, bool finished) {
+    if (n <= 0) return 0;
+    if (d.taps == 0) return n;
+    const int64_t m = finished ? n : n - d.half;
+    if (m <= 0) return 0;
+    return (m * d.L + d.M - 1) / d.M;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -24,6 +24,23 @@ int64_t resample_stream_emitted(int src_rate, int dst_rate, int64_t n_received, 
 // the raw samples a stream keeps behind its last one for the outputs it holds back: ceil(src_rate / dst_rate) + 1
 inline int resample_stream_carry(int src_rate, int dst_rate) { return (src_rate + dst_rate - 1) / dst_rate + 1; }
 
+// ---- the output side: band-limited polyphase resampler from 24 kHz to a sink's rate ----
+// Plan for sink rate R (kSinkMinRate .. kSinkMaxRate): g = gcd(R, 24000), L = R / g, M = 24000 / g; output j sits at input position
+// j * M / L.  s = min(1, R / 24000), half-width H = 16 / s input samples, half = ceil(H), taps = 2 * half, cut-off f = 0.92 * s.
+// Row p, tap t: d = (t - half + 1) - p / L; h = f sinc(f d) I0(10 sqrt(1 - (d / H)^2)) / I0(10) for |d| < H, else 0; each row is formed
+// in double, divided by its own sum (DC gain exactly 1 per phase) and rounded to float.  R == 24000: L = M = 1, half = taps = 0, no
+// table (pass-through).  sink_plan throws std::invalid_argument naming the rate when it is out of range or its table would exceed kSinkMaxTable floats.
+constexpr int kSinkMinRate = 4000, kSinkMaxRate = 192000;
+constexpr int64_t kSinkMaxTable = (int64_t)1 << 22;
+struct SinkPlan { int rate = 24000, L = 1, M = 1, half = 0, taps = 0; std::vector<float> table; /* [L][taps] */ };
+void sink_plan_dims(int rate, SinkPlan* plan);   // everything but the table (and the same refusals)
+SinkPlan sink_plan(int rate);
+// outputs a sink at `rate` has emitted in all after n_received samples at 24 kHz: unfinished max(0, ceil((n - half) L / M)) — exactly the
+// outputs whose last tap kc + half <= n - 1 has arrived — finished ceil(n L / M).  rate 24000: n.  Pure integer arithmetic.
+int64_t sink_emitted(const SinkPlan& dims, int64_t n_received, bool finished);
+// input samples a sink carries from push to push: 2 * half + ceil(M / L)
+inline int sink_carry(const SinkPlan& d) { return d.taps == 0 ? 0 : 2 * d.half + (d.M + d.L - 1) / d.L; }
+
 struct MelSpec { // the settings of tts_onnx.cpp:347-354
     int sample_rate = 24000, n_fft = 1024, hop = 256, win = 1024, n_mels = 128;
     float fmin = 0.0f, fmax = 12000.0f;

@@ -17,6 +17,7 @@ using q3::Engine;
 struct q3tts_engine {
     Engine* e = nullptr;
     std::string err;
+    q3tts_sink sink = { 0, 0, nullptr, nullptr };   // q3tts_engine_set_sink (sample_rate 0: none)
 };
 static std::string g_create_err;
 
@@ -335,6 +336,80 @@ int q3tts_slots_codec_prime(q3tts_engine* h, int n_slots, const int32_t* slots, 
     return 0;
     Q3_API_END(h)
 }
+// ---- PCM sinks (include/q3tts.h "audio out at the sink's rate") ----
+static thread_local std::string g_sink_err;
+const char* q3tts_sink_last_error(void) { return g_sink_err.c_str(); }
+int q3tts_sink_plan(int32_t rate, int32_t* L, int32_t* M, int32_t* half, int32_t* taps, float* table, int64_t cap) {
+    g_sink_err.clear();
+    try {
+        q3::SinkPlan d;
+        q3::sink_plan_dims(rate, &d);
+        if (L) *L = d.L;
+        if (M) *M = d.M;
+        if (half) *half = d.half;
+        if (taps) *taps = d.taps;
+        if (table && d.taps > 0 && cap >= (int64_t)d.L * d.taps) {
+            const q3::SinkPlan full = q3::sink_plan(rate);
+            memcpy(table, full.table.data(), full.table.size() * sizeof(float));
+        }
+        return 0;
+    } catch (const std::exception& ex) { g_sink_err = ex.what(); return -1; }
+    catch (...) { g_sink_err = "unknown error"; return -1; }
+}
+int64_t q3tts_sink_emitted(int32_t rate, int64_t n_received, int finished) {
+    g_sink_err.clear();
+    try {
+        if (n_received < 0) throw std::invalid_argument("pcm sink: negative sample count");
+        q3::SinkPlan d;
+        q3::sink_plan_dims(rate, &d);
+        return q3::sink_emitted(d, n_received, finished != 0);
+    } catch (const std::exception& ex) { g_sink_err = ex.what(); return -1; }
+    catch (...) { g_sink_err = "unknown error"; return -1; }
+}
+int q3tts_pcm_sink_begin(q3tts_engine* h, int32_t sample_rate, int format, int* sink_id) {
+    Q3_API_BEGIN(h)
+    if (!sink_id) throw q3::Error("pcm sink: NULL argument");
+    *sink_id = h->e->pcm_sink_begin(sample_rate, format);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_pcm_sink_push_batch_host(q3tts_engine* h, int n, const int32_t* sink_ids, const float* const* pcm24, const int64_t* n_in,
+                                   const uint8_t* finish, void* const* out, int64_t cap_samples, int64_t* out_len) {
+    Q3_API_BEGIN(h)
+    h->e->pcm_sink_push_batch_host(n, sink_ids, pcm24, n_in, finish, out, cap_samples, out_len);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_pcm_sink_end(q3tts_engine* h, int sink_id) {
+    Q3_API_BEGIN(h)
+    h->e->pcm_sink_end(sink_id);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_codec_stream_set_sink(q3tts_engine* h, int stream_id, int32_t sample_rate, int format) {
+    Q3_API_BEGIN(h)
+    h->e->codec_stream_set_sink(stream_id, sample_rate, format);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_codec_stream_push_batch_any_host(q3tts_engine* h, int n_streams, const int32_t* stream_ids, const int64_t* codes, const int32_t* frame_offsets,
+                                           void* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, const uint8_t* finish) {
+    Q3_API_BEGIN(h)
+    h->e->codec_stream_push_batch_host(n_streams, stream_ids, codes, frame_offsets, (float* const*)pcm_out, pcm_cap, pcm_len, finish, false);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_engine_set_sink(q3tts_engine* h, const q3tts_sink* sink) {
+    Q3_API_BEGIN(h)
+    if (!sink) { h->sink = q3tts_sink{ 0, 0, nullptr, nullptr }; return 0; }
+    if (sink->format != Q3TTS_PCM_F32 && sink->format != Q3TTS_PCM_S16) throw q3::Error("engine_set_sink: format " + std::to_string(sink->format) + " is neither Q3TTS_PCM_F32 nor Q3TTS_PCM_S16");
+    if (!sink->cb) throw q3::Error("engine_set_sink: null callback");
+    (void)h->e->pcm_sink_plan(sink->sample_rate);   // refuses a bad rate by name, and has the table uploaded before the first utterance
+    h->sink = *sink;
+    return 0;
+    Q3_API_END(h)
+}
+
 int q3tts_codec_stream_info(q3tts_engine* h, int stream_id, int* n_done, int* kv_capacity_rows, int64_t* bytes) {
     Q3_API_BEGIN(h)
     h->e->codec_stream_info(stream_id, n_done, kv_capacity_rows, bytes);
@@ -935,7 +1010,10 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     if (n_utt <= 0) return 0;
     const bool live_text = tcb != nullptr;   // q3tts_synthesize_live_host: the texts arrive through tcb, prompts are built at admission
     if ((!live_text && (!ids || !offsets)) || !p) throw q3::Error("synthesize: null argument");
-    if (!cb) throw q3::Error("synthesize_stream: null callback");
+    const q3tts_sink sink = h->sink;
+    const bool sunk = sink.sample_rate > 0;   // deliver through the engine's sink (q3tts_engine_set_sink)
+    if (!cb && !sunk) throw q3::Error("synthesize_stream: null callback");
+    if (sunk && pcm_out) throw q3::Error("synthesize_stream: pcm_out must be NULL while a sink is set (q3tts_engine_set_sink): audio leaves through the sink's callback");
     if (chunk_frames < 1) throw q3::Error("synthesize_stream: chunk_frames must be positive");
     if (pcm_cap < 0) throw q3::Error("synthesize: negative pcm_cap");
     (void)Engine::checked_penalty(*p);
@@ -988,8 +1066,19 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     }
     const int cf = std::min(chunk_frames, e.max_frames_cap);   // samples of cf frames at the start of an utterance / further in
     const int64_t chunk_cap = std::max(q3tts_codec_decode_len(&e.c, cf), q3tts_codec_decode_len(&e.c, cf + 1) - q3tts_codec_decode_len(&e.c, 1));
-    std::vector<float> chunk_pcm((size_t)B * chunk_cap);
+    // with a sink a chunk's buffer holds the sink's samples: the chunk's share plus the flushed tail, by the host rule's closed form
+    const q3::SinkPlan* splan = sunk ? &e.pcm_sink_plan(sink.sample_rate).plan : nullptr;
+    const int64_t sink_cap = sunk ? ((chunk_cap + splan->half) * splan->L + splan->M - 1) / splan->M + 2 : 0;
+    const int64_t chunk_floats = sunk ? (sink_cap * (sink.format == Q3TTS_PCM_S16 ? 2 : 4) + 3) / 4 : chunk_cap;   // per slot, 4-byte aligned
+    const int64_t deliver_cap = sunk ? sink_cap : chunk_cap;
+    std::vector<float> chunk_pcm((size_t)B * chunk_floats);
     std::vector<float*> pcm_ptr((size_t)B);
+    std::vector<int32_t> final_frames((size_t)B, -1);
+    struct SlotSinkScope {   // the slots' implicit streams take the sink for the duration of this call only
+        Engine& e;
+        SlotSinkScope(Engine& en, int rate, int fmt) : e(en) { e.slot_sink_rate = rate; e.slot_sink_format = fmt; }
+        ~SlotSinkScope() { e.slot_sink_rate = 0; e.slot_sink_format = 0; }
+    } sink_scope(e, sunk && !(sink.sample_rate == 24000 && sink.format == Q3TTS_PCM_F32) ? sink.sample_rate : 0, sink.format);
     std::vector<int32_t> slots, fb((size_t)B), fe((size_t)B);
     std::vector<int64_t> plen((size_t)B), written((size_t)n_utt, 0);
     std::vector<Engine::SlotInit> init;
@@ -1024,11 +1113,13 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
                 if (!(deliv[(size_t)b] < target[(size_t)b] || (fin && first))) continue;   // nothing of this slot leaves in this round
                 flim[slots.size()] = std::min(target[(size_t)b], (deliv[(size_t)b] / cf + 1) * cf);
             }
-            pcm_ptr[slots.size()] = chunk_pcm.data() + slots.size() * (size_t)chunk_cap;
+            pcm_ptr[slots.size()] = chunk_pcm.data() + slots.size() * (size_t)chunk_floats;
+            final_frames[slots.size()] = fin ? s.n_frames : -1;
             slots.push_back(b);
         }
         if (slots.empty()) return false;
-        e.slots_codec_decode_new((int)slots.size(), slots.data(), pcm_ptr.data(), chunk_cap, plen.data(), fb.data(), fe.data(), live_text ? flim.data() : nullptr);
+        e.slots_codec_decode_new((int)slots.size(), slots.data(), pcm_ptr.data(), deliver_cap, plen.data(), fb.data(), fe.data(), live_text ? flim.data() : nullptr,
+                                 final_frames.data());
         for (size_t i = 0; i < slots.size(); ++i) {
             const int b = slots[i], u = slot_utt[(size_t)b];
             const q3::SlotState& s = st[(size_t)b];
@@ -1036,7 +1127,7 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
             const bool fin = (s.finished || s.n_frames >= s.max_frames) && (!live_text || fe[i] >= s.n_frames);
             deliv[(size_t)b] = fe[i];
             held[(size_t)b] = fin ? 0 : s.n_frames - fe[i];
-            if (plen[i] > chunk_cap) throw q3::Error("synthesize_stream: a chunk produced more samples than its buffer holds");
+            if (plen[i] > deliver_cap) throw q3::Error("synthesize_stream: a chunk produced more samples than its buffer holds");
             if (pcm_out && pcm_out[u] && plen[i] > 0 && written[(size_t)u] < pcm_cap)
                 memcpy(pcm_out[u] + written[(size_t)u], pcm_ptr[i], (size_t)std::min(plen[i], pcm_cap - written[(size_t)u]) * sizeof(float));
             written[(size_t)u] += plen[i];
@@ -1050,7 +1141,8 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
                 --live;
             }
             if (plen[i] > 0 || fin)
-                if (cb(user, u, fb[i], fe[i], pcm_ptr[i], plen[i], fin ? 1 : 0) != 0) throw q3::Error("cancelled by callback");
+                if ((sunk ? sink.cb(sink.user, u, fb[i], fe[i], pcm_ptr[i], plen[i], fin ? 1 : 0) : cb(user, u, fb[i], fe[i], pcm_ptr[i], plen[i], fin ? 1 : 0)) != 0)
+                    throw q3::Error("cancelled by callback");
         }
         return true;
     };

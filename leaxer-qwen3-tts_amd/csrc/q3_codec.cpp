@@ -66,7 +66,9 @@ struct CodecW {
     // max_ctx 2112).  kv: [layer][k | v][head][P][d] with P = pow2 >= 2 (window - 1) + the largest push so far; `kv_rows` rows are stored,
     // the last of them position n_done - 1; when a push would not fit, the newest window - 1 rows move to the front (the only ones a
     // later query can reach).  hpost: [h_cap][hidden], `h_rows` stored, the newest codec_stage_b_context() rows kept the same way.
-    struct Stream { bool used = false; int cap = 0, P = 0, pshift = 0, n_done = 0, kv_rows = 0, h_cap = 0, h_rows = 0; float* kv = nullptr; float* hpost = nullptr; };
+    // sink: the stream's PCM sink (Engine::sinks; -1: the stream delivers 24 kHz float); delivered: a push has returned samples
+    struct Stream { bool used = false; int cap = 0, P = 0, pshift = 0, n_done = 0, kv_rows = 0, h_cap = 0, h_rows = 0; float* kv = nullptr; float* hpost = nullptr;
+                    int sink = -1; bool delivered = false; };
     std::vector<Stream> streams;
     char* stream_arena = nullptr; size_t stream_arena_bytes = 0;
     std::vector<int> slot_stream;          // slot -> stream id (-1: none): q3tts_slot_codec_decode_range_host's implicit stream
@@ -714,7 +716,7 @@ int Engine::codec_stream_begin(int max_frames) {
     S.kv_rows = 0; S.h_rows = 0;                       // nothing of the buffers' previous stream is kept
     codec_stream_fit(sid, std::min(max_frames, 64));
     S.cap = max_frames;
-    S.used = true; S.n_done = 0;
+    S.used = true; S.n_done = 0; S.sink = -1; S.delivered = false;
     int P = 1;
     while (P < max_frames) P <<= 1;
     codec_rope_tables(P);   // positions are absolute in the RoPE tables (grow-only, shared)
@@ -768,6 +770,23 @@ void Engine::codec_stream_end(int sid) {
     if (!codec || sid < 0 || sid >= (int)codec->streams.size() || !codec->streams[(size_t)sid].used) throw Error("codec_stream_end: no such stream");
     codec->streams[(size_t)sid].used = false;        // buffers are kept for the next stream of this size
     codec->streams[(size_t)sid].n_done = 0;
+    if (codec->streams[(size_t)sid].sink >= 0) pcm_sink_end(codec->streams[(size_t)sid].sink);
+    codec->streams[(size_t)sid].sink = -1;
+}
+
+void Engine::codec_stream_set_sink(int sid, int rate, int format) {
+    if (!codec || sid < 0 || sid >= (int)codec->streams.size() || !codec->streams[(size_t)sid].used) throw Error("codec_stream_set_sink: no such stream");
+    CodecW::Stream& S = codec->streams[(size_t)sid];
+    if (S.delivered) throw Error("codec_stream_set_sink: stream " + std::to_string(sid) + " has already delivered samples");
+    if (format != Q3TTS_PCM_F32 && format != Q3TTS_PCM_S16) throw Error("codec_stream_set_sink: format " + std::to_string(format) + " is neither Q3TTS_PCM_F32 nor Q3TTS_PCM_S16");
+    const int id = rate == 24000 && format == Q3TTS_PCM_F32 ? -1 : pcm_sink_begin(rate, format);   // 24 kHz float is "no sink"; a bad rate throws before the old sink goes
+    if (S.sink >= 0) pcm_sink_end(S.sink);
+    S.sink = id;
+}
+
+int Engine::codec_stream_sink(int sid) const {
+    if (!codec || sid < 0 || sid >= (int)codec->streams.size() || !codec->streams[(size_t)sid].used) throw Error("codec_stream: no such stream");
+    return codec->streams[(size_t)sid].sink;
 }
 
 int Engine::codec_stream_frames(int sid) const {
@@ -782,6 +801,7 @@ int64_t Engine::codec_stream_push_dev(int sid, const int32_t* codes_dev, int n, 
     CodecW& W = *codec;
     CodecW::Stream& S = W.streams[(size_t)sid];
     if (n < 1) throw Error("codec_stream_push: no frames");
+    if (S.sink >= 0) throw Error("codec_stream_push: stream " + std::to_string(sid) + " has a sink: push it through the batched entry that takes any format");
     if (S.n_done + n > S.cap) throw Error("codec_stream_push: more frames than the stream was opened for");
     const int CH = c.cd_hidden, NH = c.cd_heads, HD = c.cd_head_dim, FF = c.cd_ffn;
     const int a0 = S.n_done, b0 = a0 + n, T = n;
@@ -853,7 +873,7 @@ int64_t Engine::codec_stream_push_dev(int sid, const int32_t* codes_dev, int n, 
     if (h0 < a0 - sB) throw Error("codec_stream_push: the kept transformer rows do not cover the look-back window");
     const int64_t n_win = codec_run(nullptr, b0 - sB, &pcm_d, 0, S.hpost + (size_t)(h0 - (a0 - sB)) * CH, 1);
     if (first < 0 || first + n_own != n_win) throw Error("codec_stream_push: window arithmetic does not match the decoder length formula");
-    S.n_done = b0; S.kv_rows = k0 + n; S.h_rows = h0 + n;
+    S.n_done = b0; S.kv_rows = k0 + n; S.h_rows = h0 + n; S.delivered = S.delivered || n_own > 0;
     if (pcm_dev) *pcm_dev = pcm_d + first;
     return n_own;
 }
@@ -911,8 +931,41 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
         if (q.n > 0 && !q.codes_dev) throw Error("codec_stream_push_batch: null codes");
         if (q.n > 0) live.push_back(i);
     }
+    // streams with a sink: their pushes' lengths by the host rule (which refuses a finished or full sink), before anything moves
+    auto len_all = [&](int nfr) -> int64_t { return nfr <= 0 ? 0 : q3tts_codec_decode_len(&c, nfr); };
+    std::vector<SinkPush> sp((size_t)g_all);     // entry i belongs to ps[i]; sink == -1: none
+    size_t sink_bytes = 0;
+    int n_sinks = 0;
+    for (int i = 0; i < g_all; ++i) {
+        const StreamPush& q = ps[i];
+        const CodecW::Stream& S = W.streams[(size_t)q.sid];
+        if (S.sink < 0) { if (q.finish) throw Error("codec_stream_push_batch: finish on stream " + std::to_string(q.sid) + ", which has no sink"); continue; }
+        SinkPush& k = sp[(size_t)i];
+        k.sink = S.sink; k.n_new = len_all(S.n_done + q.n) - len_all(S.n_done); k.finish = q.finish; k.out_host = q.pcm; k.cap = q.cap;
+        sink_bytes += pcm_sink_out_bytes(k.sink, k.n_new, k.finish);
+        ++n_sinks;
+    }
+    if (n_sinks > 0) pcm_sinks_reserve(n_sinks, sink_bytes);
+    std::vector<SinkPush> sp_run;                // the sinks of one launch, and where each came from
+    std::vector<int> sp_src;
+    auto run_sinks = [&]() {
+        if (sp_run.empty()) return;
+        pcm_sinks_launch(sp_run.data(), (int)sp_run.size());
+        for (size_t k = 0; k < sp_run.size(); ++k) { sp[(size_t)sp_src[k]] = sp_run[k]; ps[sp_src[k]].n_own = sp_run[k].n_out; }
+        sp_run.clear(); sp_src.clear();
+    };
+    auto commit_sinks = [&]() {
+        for (int i = 0; i < g_all; ++i) if (sp[(size_t)i].sink >= 0) pcm_sinks_commit(&sp[(size_t)i], 1);
+    };
     const int g = (int)live.size();
-    if (g == 0) return;
+    if (g == 0) {   // no frames anywhere: only sinks that finish have something to deliver
+        for (int i = 0; i < g_all; ++i) if (sp[(size_t)i].sink >= 0 && sp[(size_t)i].finish) { sp_run.push_back(sp[(size_t)i]); sp_src.push_back(i); }
+        if (sp_run.empty()) return;
+        run_sinks();
+        sync();
+        commit_sinks();
+        return;
+    }
     if (g > 65535) throw Error("codec_stream_push_batch: at most 65535 streams per call");
     const int ctxB = codec_stage_b_context();
     // group key: left-context length min(a0, ctxB); mature streams (the common case) first
@@ -1041,6 +1094,13 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
             const int64_t first = len_of(d.a0) - up * (d.a0 - d.ctx), n_own = len_of(d.a0 + d.n) - len_of(d.a0);
             if (first < 0 || first + n_own > Tp || (d.ctx + d.n == G.Tw && first + n_own != Tp)) throw Error("codec_stream_push_batch: window arithmetic does not match the decoder length formula");
             q.n_own = n_own;
+            if (sp[(size_t)live[(size_t)i]].sink >= 0) {   // through its sink, in the group's one launch (run_sinks), from where the samples lie
+                SinkPush k = sp[(size_t)live[(size_t)i]];
+                if (k.n_new != n_own) throw Error("codec_stream_push_batch: a sink's input length does not match the decoder length formula");
+                k.x_dev = pcm_seq + first;
+                sp_run.push_back(k); sp_src.push_back(live[(size_t)i]);
+                return;
+            }
             const int64_t m = std::min(n_own, q.cap);
             if (m > 0 && q.pcm) Q3_HIP_CHECK(hipMemcpyAsync(q.pcm, pcm_seq + first, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, stream));
         };
@@ -1049,28 +1109,37 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
             const int64_t Tp = codec_run(nullptr, G.Tw, &pcm_d, 0, hup, 2, gk, ustride);
             if (last_group) Q3_HIP_CHECK(hipEventRecord(ev1, stream));
             for (int i = G.i0; i < G.i1; ++i) deliver(i, pcm_d + (size_t)(i - G.i0) * Tp, Tp);
+            run_sinks();
         } else {                     // one stream in the group, or a decoder the batched conv kernels do not cover: sequence by sequence
             for (int i = G.i0; i < G.i1; ++i) {
                 float* pcm_d = nullptr;
                 const int64_t Tp = codec_run(nullptr, G.Tw, &pcm_d, 0, hup + (size_t)(i - G.i0) * ustride, 2);
                 if (last_group && i + 1 == G.i1) Q3_HIP_CHECK(hipEventRecord(ev1, stream));
                 deliver(i, pcm_d, Tp);
+                run_sinks();   // before the next sequence's decode reuses the lane's workspace
             }
         }
     }
+    // sinks that finish without new frames
+    for (int i = 0; i < g_all; ++i) if (ps[i].n == 0 && sp[(size_t)i].sink >= 0 && sp[(size_t)i].finish) { sp_run.push_back(sp[(size_t)i]); sp_src.push_back(i); }
+    run_sinks();
+    if (n_sinks > 0) Q3_HIP_CHECK(hipEventRecord(ev1, stream));   // the push's time includes its sinks
     sync();
     Q3_HIP_CHECK(hipEventElapsedTime(&last_codec_ms, ev0, ev1));
     total_codec_ms += last_codec_ms; total_codec_frames += T;
     for (int i = 0; i < g; ++i) {   // the streams advance only now: a failure above leaves every one of them where it was
         const CodecStreamDesc& d = D[(size_t)i];
-        CodecW::Stream& S = W.streams[(size_t)ps[live[(size_t)i]].sid];
+        const StreamPush& q = ps[live[(size_t)i]];
+        CodecW::Stream& S = W.streams[(size_t)q.sid];
         S.n_done = d.a0 + d.n; S.kv_rows = d.k0 + d.n; S.h_rows = d.h0 + d.n;
+        S.delivered = S.delivered || q.n_own > 0 || (S.sink >= 0 && sp[(size_t)live[(size_t)i]].n_new > 0);
     }
+    commit_sinks();
 }
 
 // host codes: stream s receives frames codes[frame_offsets[s] .. frame_offsets[s + 1]); validated as a whole before anything moves
 void Engine::codec_stream_push_batch_host(int n_streams, const int32_t* sids, const int64_t* codes, const int32_t* frame_offsets, float* const* pcm_out,
-                                          int64_t cap, int64_t* pcm_len) {
+                                          int64_t cap, int64_t* pcm_len, const uint8_t* finish, bool float_only) {
     if (!codec) throw Error("codec decoder not finalized");
     if (n_streams < 0) throw Error("codec_stream_push_batch: negative stream count");
     if (n_streams == 0) return;
@@ -1092,13 +1161,16 @@ void Engine::codec_stream_push_batch_host(int n_streams, const int32_t* sids, co
     for (int i = 0; i < n_streams; ++i) {   // the checks codec_stream_push_batch repeats, made here before the staging buffer may grow
         ps[(size_t)i].sid = sids[i]; ps[(size_t)i].n = frame_offsets[i + 1] - frame_offsets[i];
         ps[(size_t)i].pcm = pcm_out ? pcm_out[i] : nullptr; ps[(size_t)i].cap = cap;
+        ps[(size_t)i].finish = finish && finish[i];
+        if (float_only && sids[i] >= 0 && sids[i] < (int)W.streams.size() && W.streams[(size_t)sids[i]].used && W.streams[(size_t)sids[i]].sink >= 0)
+            throw Error("codec_stream_push_batch: stream " + std::to_string(sids[i]) + " has a sink: the float entry serves streams without one");
         if (pcm_len) pcm_len[i] = 0;
     }
-    if (W.sbatch_codes_n < total) {
+    if (W.sbatch_codes_n < total || !W.sbatch_codes) {
         sync();
         if (W.sbatch_codes) (void)hipFree(W.sbatch_codes);
         W.sbatch_codes = nullptr; W.sbatch_codes_n = 0;
-        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_codes, total * sizeof(int32_t)));
+        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_codes, std::max(total, (size_t)1) * sizeof(int32_t)));
         W.sbatch_codes_n = total;
     }
     if (total > 0) Q3_HIP_CHECK(hipMemcpyAsync(W.sbatch_codes, tmp.data(), total * sizeof(int32_t), hipMemcpyHostToDevice, stream));
@@ -1110,7 +1182,7 @@ void Engine::codec_stream_push_batch_host(int n_streams, const int32_t* sids, co
 // For every listed slot: the frames generated since the slot's previous streaming call, through the slot's implicit stream (the one
 // slot_codec_stream_range uses: the two interleave), all slots in batched passes.  The codes are read where the sampler wrote them.
 void Engine::slots_codec_decode_new(int n_slots, const int32_t* slots, float* const* pcm_out, int64_t cap, int64_t* pcm_len, int32_t* frame_begin, int32_t* frame_end,
-                                   const int32_t* frame_limit) {
+                                   const int32_t* frame_limit, const int32_t* final_frames) {
     if (!codec) throw Error("codec decoder not finalized");
     if (n_slots < 0) throw Error("slots_codec_decode_new: negative slot count");
     if (n_slots == 0) return;
@@ -1137,10 +1209,13 @@ void Engine::slots_codec_decode_new(int n_slots, const int32_t* slots, float* co
             sid = codec_stream_begin(max_frames_cap);
             W.slot_stream[(size_t)slot] = sid;
         }
+        // the scheduler's sink: a stream that has delivered nothing yet takes it (a primed stream included: its sink starts from silence)
+        if (slot_sink_rate > 0 && W.streams[(size_t)sid].sink < 0 && !W.streams[(size_t)sid].delivered) codec_stream_set_sink(sid, slot_sink_rate, slot_sink_format);
         const int a = W.streams[(size_t)sid].n_done;
         StreamPush& q = ps[(size_t)i];
         q.sid = sid; q.n = nf - a; q.codes_dev = codes_d + ((size_t)slot * max_frames_cap + a) * c.n_groups;
         q.pcm = pcm_out ? pcm_out[i] : nullptr; q.cap = cap;
+        q.finish = W.streams[(size_t)sid].sink >= 0 && final_frames && final_frames[i] >= 0 && nf >= final_frames[i];
         if (frame_begin) frame_begin[i] = a;
         if (frame_end) frame_end[i] = nf;
         if (pcm_len) pcm_len[i] = 0;

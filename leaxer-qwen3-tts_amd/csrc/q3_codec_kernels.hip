@@ -1523,4 +1523,82 @@ void launch_prime_row_tails(const float* h, const CodecStreamDesc* descs, int g,
     if (g > 0 && ctx > 0) hipLaunchKernelGGL(k_prime_row_tails, dim3(ctx, g), dim3(256), 0, s, h, descs, C, ctx);
 }
 
+// ------------------------------------------------------------------------------------------------
+// PCM sinks (PcmSinkDesc, q3_common.h): the polyphase windowed-sinc resampler between the vocoder and the device -> host copy.
+// A workgroup owns 256 consecutive outputs of one sink.  Their inputs, 255 M / L + taps consecutive samples, are staged once in LDS; the
+// sink's table rows too when they fit (row stride odd, so that lanes on different phases spread over the banks), otherwise rows are
+// read through L1.  One thread folds one output, taps in ascending order: a sample's bits depend on its absolute index alone.
+// ------------------------------------------------------------------------------------------------
+// sample k of the sink, from its carry or from the push's new samples: both addresses clamped, both loads issued, then selected; zero
+// outside [0, n_total)
+__device__ __forceinline__ float pcm_sink_sample(const PcmSinkDesc& d, int64_t k) {
+    int64_t jn = k - d.n_before, jc = k - d.carry_abs0;
+    const bool is_new = jn >= 0, inside = k >= 0 && k < d.n_total;
+    const int64_t last_new = d.n_new > 0 ? d.n_new - 1 : 0, last_c = d.n_before - d.carry_abs0 > 0 ? d.n_before - d.carry_abs0 - 1 : 0;
+    jn = jn < 0 ? 0 : (jn > last_new ? last_new : jn);
+    jc = jc < 0 ? 0 : (jc > last_c ? last_c : jc);
+    const float vn = d.x_new[jn];
+    const float vc = d.carry_in[jc];
+    const float v = is_new ? vn : vc;
+    return inside ? v : 0.0f;
+}
+__device__ __forceinline__ void pcm_sink_store(const PcmSinkDesc& d, int i, float y) {
+    if (d.s16) {
+        const float v = y > 1.0f ? 1.0f : (y < -1.0f ? -1.0f : y);
+        ((int16_t*)d.out)[i] = (int16_t)(v * 32767.0f);
+    } else {
+        ((float*)d.out)[i] = y;
+    }
+}
+__global__ __launch_bounds__(256) void k_pcm_sink(const PcmSinkDesc* descs) {
+    extern __shared__ float sink_lds[];
+    const PcmSinkDesc d = descs[blockIdx.y];
+    const int b0 = blockIdx.x * 256, tid = threadIdx.x, t = b0 + tid;
+    if (b0 >= d.n_out + d.keep) return;   // the whole workgroup
+    if (t >= d.n_out && t < d.n_out + d.keep) d.carry_out[t - d.n_out] = pcm_sink_sample(d, d.n_total - d.keep + (t - d.n_out));
+    if (b0 >= d.n_out) return;            // a workgroup of carry threads only (uniform)
+    if (d.taps == 0) {                    // 24 kHz: only the format changes (uniform)
+        if (t < d.n_out) pcm_sink_store(d, t, pcm_sink_sample(d, d.out0 + t));
+        return;
+    }
+    float* xs = sink_lds;
+    float* ts = sink_lds + kPcmSinkLdsX;
+    const int nb = d.n_out - b0 < 256 ? d.n_out - b0 : 256;
+    // the workgroup's first output: 64-bit once, 32-bit per thread (r0 + 255 M < 2^31)
+    const int64_t jm = (d.out0 + b0) * (int64_t)d.M;
+    const int64_t q0 = jm / d.L;
+    const uint32_t r0 = (uint32_t)(jm - q0 * d.L);
+    const int64_t x_lo = q0 - d.half + 1;                                     // absolute index of xs[0]
+    const int span = (int)((r0 + (uint32_t)(nb - 1) * (uint32_t)d.M) / (uint32_t)d.L) + d.taps;   // <= kPcmSinkLdsX
+    for (int s = tid; s < span; s += 256) xs[s] = pcm_sink_sample(d, x_lo + s);
+    const int stride = d.taps | 1;
+    if (d.tab_lds) {
+        const int n_tab = d.L * d.taps;
+        for (int s = tid; s < n_tab; s += 256) {
+            const int p = s / d.taps;
+            ts[p * stride + (s - p * d.taps)] = d.tab[s];
+        }
+    }
+    __syncthreads();
+    if (tid >= nb) return;
+    const uint32_t rm = r0 + (uint32_t)tid * (uint32_t)d.M;
+    const uint32_t dk = rm / (uint32_t)d.L, p = rm - dk * (uint32_t)d.L;
+    const float* x = xs + dk;
+    float acc = 0.0f;
+    if (d.tab_lds) {
+        const float* h = ts + p * stride;
+        for (int i = 0; i < d.taps; ++i) acc = acc + h[i] * x[i];
+    } else {
+        const float* h = d.tab + (size_t)p * d.taps;
+        for (int i = 0; i < d.taps; ++i) acc = acc + h[i] * x[i];
+    }
+    pcm_sink_store(d, t, acc);
+}
+void launch_pcm_sinks(const PcmSinkDesc* tab, int n, int max_work, bool any_tab_lds, hipStream_t s) {
+    if (n < 1 || n > 65535 || max_work < 1) throw Error("pcm sink: 1..65535 sinks with at least one output or carry sample");
+    const size_t lds = (size_t)(kPcmSinkLdsX + (any_tab_lds ? kPcmSinkLdsTab : 0)) * sizeof(float);
+    hipLaunchKernelGGL(k_pcm_sink, dim3((max_work + 255) / 256, n), dim3(256), lds, s, tab);
+    Q3_HIP_CHECK(hipGetLastError());
+}
+
 } // namespace q3

@@ -425,6 +425,31 @@ void launch_gather_stream_rows(const CodecStreamDesc* descs, int g, int Tw, int 
 void launch_prime_kv_tails(const float* kc, const float* vc, int Ps, const CodecStreamDesc* descs, int g, int layer, int nkv, int d, int keep, hipStream_t s);
 void launch_prime_row_tails(const float* h, const CodecStreamDesc* descs, int g, int C, int ctx, hipStream_t s);
 
+// ---- PCM sinks (q3_codec.cpp): 24 kHz float PCM -> the sink's rate and format, band-limited, with carried state ----
+// One sink of one push.  The samples the sink has are its carry (the last `n_before - carry_abs0` samples before this push) followed
+// by the push's n_new samples at x_new (device; the vocoder's PCM where it lies, or staged host samples).  Output i of the launch is the
+// sink's absolute output j = out0 + i: kc = floor(j M / L), p = (j M) mod L, y = sum_t tab[p][t] * x[kc - half + 1 + t], t ascending in
+// fp32, x[k] = 0 for k < 0 and k >= n_total (which only a finishing push reaches).  taps == 0 (24 kHz): y[j] = x[j].  The result is
+// written to out[i] as float, or as int16 by the CLI's rule (clip to [-1, 1], (int16_t)(v * 32767.0f)).  Threads [n_out, n_out + keep)
+// write the sink's next carry, the last `keep` samples of (carry, new), into carry_out: the other of the sink's two carry buffers.
+struct PcmSinkDesc {
+    const float* carry_in = nullptr; float* carry_out = nullptr;
+    const float* x_new = nullptr;       // n_new samples (never null: a push without samples points at the carry)
+    const float* tab = nullptr;         // [L][taps] on the device
+    void* out = nullptr;                // n_out samples in the sink's format
+    int64_t carry_abs0 = 0;             // absolute index of carry_in[0]
+    int64_t n_before = 0, n_total = 0;  // samples received before / with this push
+    int64_t out0 = 0;                   // absolute index of the first new output
+    int32_t n_new = 0, n_out = 0, keep = 0;   // keep == 0: the carry stays
+    int32_t L = 1, M = 1, half = 0, taps = 0, s16 = 0;
+    int32_t tab_lds = 0;                // the table's rows are staged in LDS (pcm_sink_tab_in_lds)
+};
+constexpr int kPcmSinkLdsX = 256 * 6 + 192 + 8;      // inputs of 256 outputs at the lowest rate (M / L <= 6, taps <= 192)
+constexpr int kPcmSinkLdsTab = 12288;                // floats of table (rows padded to an odd stride) kept in LDS
+inline int pcm_sink_tab_stride(int taps) { return taps | 1; }
+inline bool pcm_sink_tab_in_lds(int L, int taps) { return taps > 0 && (int64_t)L * pcm_sink_tab_stride(taps) <= kPcmSinkLdsTab; }
+void launch_pcm_sinks(const PcmSinkDesc* tab /* device, [n] */, int n, int max_work /* largest n_out + keep */, bool any_tab_lds, hipStream_t s);
+
 
 // ---- speaker encoder + GPU audio front end of the clone path (q3_speaker_kernels.hip) ----
 // One reference clip of a batch.  Activations of a batch lie clip after clip along time ([sum T][C]); every kernel that looks across

@@ -439,6 +439,7 @@ Engine::~Engine() {
     if (frame_text_d) (void)hipFree(frame_text_d);
     if (rag_x_d) (void)hipFree(rag_x_d);
     if (seg_tab_d) (void)hipFree(seg_tab_d);
+    pcm_sink_free();
     codec_free();
     speaker_free();
     encoder_free();

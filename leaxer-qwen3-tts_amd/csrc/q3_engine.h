@@ -1,11 +1,13 @@
 // q3_engine.h — the device-resident engine behind the C-ABI (include/q3tts.h).
 #pragma once
 #include <functional>
+#include <map>
 #include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
+#include "q3_audio.h"
 #include "q3_common.h"
 #include "q3_kvpool.h"
 
@@ -153,12 +155,16 @@ public:
     int64_t slot_codec_stream_range(int slot, int a, int b, float* pcm, int64_t cap);
     // batched push: n new frames (device codes) for each of g distinct streams in one set of launches; n == 0 leaves a stream untouched.
     // PCM lands in the callers' host buffers (min(n_own, cap) samples); validated as a whole before any stream advances
-    struct StreamPush { int sid = -1; const int32_t* codes_dev = nullptr; int n = 0; float* pcm = nullptr; int64_t cap = 0; int64_t n_own = 0; };
+    struct StreamPush { int sid = -1; const int32_t* codes_dev = nullptr; int n = 0; float* pcm = nullptr; int64_t cap = 0; int64_t n_own = 0;
+                        bool finish = false; /* a stream with a sink: flush its tail with this push (n == 0 allowed) */ };
     void codec_stream_push_batch(StreamPush* ps, int g);
+    // finish[i] (optional): stream i's sink flushes its tail with this push.  float_only: a stream with a sink is refused (pcm_out is
+    // read as float); otherwise pcm_out[i] is read in the stream's sink's format and cap / pcm_len count its samples
     void codec_stream_push_batch_host(int n_streams, const int32_t* sids, const int64_t* codes, const int32_t* frame_offsets, float* const* pcm_out,
-                                      int64_t cap, int64_t* pcm_len);
+                                      int64_t cap, int64_t* pcm_len, const uint8_t* finish = nullptr, bool float_only = true);
     void slots_codec_decode_new(int n_slots, const int32_t* slots, float* const* pcm_out, int64_t cap, int64_t* pcm_len, int32_t* frame_begin, int32_t* frame_end,
-                                const int32_t* frame_limit = nullptr);   // frame_limit[i] (optional): decode slot i's frames below it only
+                                const int32_t* frame_limit = nullptr,    // frame_limit[i] (optional): decode slot i's frames below it only
+                                const int32_t* final_frames = nullptr);  // final_frames[i] >= 0 (optional): the utterance ends at that frame count; the push that reaches it flushes the slot's sink
     // priming: g open streams without frames take the state a push of their first n frames would leave — pre-transformer only, the K / V
     // and output-row tails copied into the streams' buffers, which keep the size codec_stream_begin gave them (StreamPush: sid, codes_dev, n)
     void codec_stream_prime_batch(const StreamPush* ps, int g);
@@ -167,6 +173,44 @@ public:
     void codec_stream_info(int sid, int* n_done, int* kv_capacity_rows, int64_t* bytes) const;
     void slot_codec_stream_reset(int slot);
     void codec_rope_tables(int P);
+
+    // ---- PCM sinks (q3_pcm_sink.cpp): 24 kHz float on the device -> the sink's rate and format, carried state ----
+    static constexpr int kPcmSinkCarry = 256;                        // floats per carry buffer (2 * half + ceil(M / L) <= 198)
+    static constexpr int kMaxPcmSinks = 4096;                        // open at the same time (vocoder streams' sinks included)
+    static constexpr int64_t kPcmSinkMaxSamples = 86400000;          // one hour of 24 kHz input per sink
+    static constexpr int64_t kPcmSinkMaxPush = 1440000;              // one push of the standalone entry: 60 s
+    struct SinkPlanDev { SinkPlan plan; float* tab_d = nullptr; };
+    std::map<int, SinkPlanDev> sink_plans;                           // by rate: built once, uploaded, kept (node addresses are stable)
+    const SinkPlanDev& pcm_sink_plan(int rate);
+    // carry: [2][kPcmSinkCarry] floats in the sink's own allocation; a push reads buffer `cur` and writes the other, the host flips
+    // them when the push has completed.  carry_abs0: absolute index of the first carried sample.
+    struct PcmSink { bool used = false, finished = false; int rate = 24000, format = 0, cur = 0; const SinkPlanDev* plan = nullptr;
+                     int64_t n_in = 0, n_out = 0, carry_abs0 = 0; float* carry = nullptr; };
+    std::vector<PcmSink> sinks;
+    int pcm_sink_begin(int rate, int format);
+    void pcm_sink_end(int id);
+    void pcm_sink_free();
+    const PcmSink& pcm_sink_get(int id) const;
+    int64_t pcm_sink_push_len(int id, int64_t n_new, bool finish) const;   // host-only: samples that push would deliver; throws when it would be refused
+    size_t pcm_sink_out_bytes(int id, int64_t n_new, bool finish) const;   // that push's share of the packed output buffer
+    // x_dev: n_new samples on the device; out_host: min(n_out, cap) samples in the sink's format land there; desc: internal
+    struct SinkPush { int sink = -1; const float* x_dev = nullptr; int64_t n_new = 0; bool finish = false; void* out_host = nullptr; int64_t cap = 0;
+                      int64_t n_out = 0; int desc = -1; };
+    void pcm_sinks_reserve(int n_total, size_t out_bytes_total);     // once per call, before anything is enqueued
+    void pcm_sinks_launch(SinkPush* ps, int n);                      // one launch + the device -> host copies; no sink moves
+    void pcm_sinks_commit(const SinkPush* ps, int n);                // after the sync: counters advance, carries flip
+    void pcm_sink_push_batch_host(int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in, const uint8_t* finish,
+                                  void* const* out, int64_t cap, int64_t* out_len);
+    PcmSinkDesc* sink_desc_d = nullptr; size_t sink_desc_cap = 0, sink_desc_used = 0;
+    std::vector<PcmSinkDesc> sink_desc_h;
+    char* sink_out_d = nullptr; size_t sink_out_bytes = 0, sink_out_used = 0;   // packed outputs of a call (grow-only workspace)
+    float* sink_in_d = nullptr; size_t sink_in_floats = 0;                       // the standalone entry's staged input
+    // vocoder streams: a stream with a sink delivers at the sink's rate (codec_stream_push_batch; StreamPush::pcm is then read as the
+    // sink's format and n_own counts its samples).  Refused once the stream has delivered a sample.  24 000 / float: no sink.
+    void codec_stream_set_sink(int sid, int rate, int format);
+    int codec_stream_sink(int sid) const;                            // -1: none
+    // the scheduler's sink (q3tts_engine_set_sink): slots' implicit streams begin with it.  rate 0: none
+    int slot_sink_rate = 0, slot_sink_format = 0;
 
     // ---- batch-first session ops on DEVICE pointers (include/q3tts.h "_dev" entry points): row b <-> slot b ----
     // caller stream: the engine's stream first waits for what the caller has enqueued, the caller's stream then waits for the call's work

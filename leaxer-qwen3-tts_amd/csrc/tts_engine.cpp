@@ -263,8 +263,11 @@ int TTSEngine::synthesize_tokens_continue_streaming(const std::vector<int64_t>& 
     const q3tts_audio_cb cb = [](void* user, int, int, int, const float* pcm, int64_t n, int finished) -> int {
         return (*static_cast<Ctx*>(user)->f)(pcm, (size_t)n, finished != 0) ? 1 : 0;
     };
-    if (q3tts_synthesize_continue_stream_host(h_, 1, token_ids.data(), offs, lang_index(lang), nullptr, &sp, nullptr, seed_, 0, nullptr, 0, nullptr, &frames,
-                                              codes.data(), F0 > 0 ? prefix_codes.data() : nullptr, F0 > 0 ? poffs : nullptr, chunk_frames, cb, &ctx) != 0) {
+    if (sink_on()) sink_fn_ = [&](int, const void* pcm, int64_t n, int finished) { return on_audio((const float*)pcm, (size_t)n, finished != 0) ? 1 : 0; };
+    const int rc = q3tts_synthesize_continue_stream_host(h_, 1, token_ids.data(), offs, lang_index(lang), nullptr, &sp, nullptr, seed_, 0, nullptr, 0, nullptr, &frames,
+                                                         codes.data(), F0 > 0 ? prefix_codes.data() : nullptr, F0 > 0 ? poffs : nullptr, chunk_frames, cb, &ctx);
+    sink_fn_ = nullptr;
+    if (rc != 0) {
         std::cerr << "[TTSEngine] Synthesis error: " << q3tts_last_error(h_) << std::endl;
         return -1;
     }
@@ -275,6 +278,62 @@ int TTSEngine::synthesize_tokens_continue_streaming(const std::vector<int64_t>& 
 std::vector<float> TTSEngine::synthesize_speaker(const std::string& text, Speaker, Language lang, const SamplingParams& params) {
     std::cerr << "[TTSEngine] Preset speakers require CustomVoice model (not yet supported)" << std::endl; // :327
     return synthesize(text, lang, params);
+}
+
+bool TTSEngine::set_output_format(int sample_rate, bool pcm16) {
+    if (!ready_) return false;
+    if (sample_rate == config::SAMPLE_RATE && !pcm16) {
+        (void)q3tts_engine_set_sink(h_, nullptr);
+        out_rate_ = sample_rate; out_pcm16_ = false;
+        return true;
+    }
+    q3tts_sink sk;
+    sk.sample_rate = sample_rate; sk.format = pcm16 ? Q3TTS_PCM_S16 : Q3TTS_PCM_F32; sk.user = this;
+    sk.cb = [](void* user, int utt, int, int, const void* pcm, int64_t n, int finished) -> int {
+        TTSEngine* self = static_cast<TTSEngine*>(user);
+        return self->sink_fn_ ? self->sink_fn_(utt, pcm, n, finished) : 0;
+    };
+    if (q3tts_engine_set_sink(h_, &sk) != 0) {
+        error_msg_ = q3tts_last_error(h_);
+        std::cerr << "[TTSEngine] Output format: " << error_msg_ << std::endl;
+        return false;
+    }
+    out_rate_ = sample_rate; out_pcm16_ = pcm16;
+    return true;
+}
+
+bool TTSEngine::convert_output(const std::vector<float>& pcm24, std::vector<float>* f32, std::vector<int16_t>* s16) {
+    if (f32) f32->clear();
+    if (s16) s16->clear();
+    if (!ready_ || (out_pcm16_ ? !s16 : !f32)) return false;
+    if (!sink_on()) { *f32 = pcm24; return true; }
+    int id = -1;
+    auto fail = [&]() {
+        std::cerr << "[TTSEngine] Output conversion error: " << q3tts_last_error(h_) << std::endl;
+        if (id >= 0) (void)q3tts_pcm_sink_end(h_, id);
+        if (f32) f32->clear();
+        if (s16) s16->clear();
+        return false;
+    };
+    if (q3tts_pcm_sink_begin(h_, out_rate_, out_pcm16_ ? Q3TTS_PCM_S16 : Q3TTS_PCM_F32, &id) != 0) return fail();
+    const size_t step = 1440000;   // the most one push takes
+    size_t done = 0;
+    do {
+        const size_t m = std::min(step, pcm24.size() - done);
+        const int64_t n_in = (int64_t)m;
+        const uint8_t fin = done + m == pcm24.size() ? 1 : 0;
+        const int64_t before = q3tts_sink_emitted(out_rate_, (int64_t)done, 0), after = q3tts_sink_emitted(out_rate_, (int64_t)(done + m), fin);
+        if (before < 0 || after < before) return fail();
+        const size_t have = out_pcm16_ ? s16->size() : f32->size();
+        if (out_pcm16_) s16->resize(have + (size_t)(after - before)); else f32->resize(have + (size_t)(after - before));
+        const float* in = pcm24.data() + done;
+        void* out = out_pcm16_ ? (void*)(s16->data() + have) : (void*)(f32->data() + have);
+        int64_t len = 0;
+        if (q3tts_pcm_sink_push_batch_host(h_, 1, &id, &in, &n_in, &fin, &out, after - before, &len) != 0 || len != after - before) return fail();
+        done += m;
+    } while (done < pcm24.size());
+    (void)q3tts_pcm_sink_end(h_, id);
+    return true;
 }
 
 bool TTSEngine::has_audio_encoder() const { return h_ && q3tts_has_audio_encoder(h_) != 0; }
@@ -541,8 +600,10 @@ std::vector<int> TTSEngine::synthesize_tokens_live(int n_utt, const std::functio
     };
     std::vector<int64_t> all;
     if (codes) all.assign((size_t)n_utt * (size_t)params.max_new_tokens * (size_t)n_groups_, 0);
+    if (sink_on()) sink_fn_ = [&](int utt, const void* pcm, int64_t n, int finished) { return on_audio(utt, (const float*)pcm, (size_t)n, finished != 0) ? 1 : 0; };
     const int rc = q3tts_synthesize_live_host(h_, n_utt, tcb, &ctx, lang_index(lang), nullptr, &sp, nullptr, seed_, 0,
                                               nullptr, 0, nullptr, frames.data(), codes ? all.data() : nullptr, chunk_frames, cb, &ctx);
+    sink_fn_ = nullptr;
     if (rc != 0) {
         std::cerr << "[TTSEngine] Synthesis error: " << q3tts_last_error(h_) << std::endl;
         return {};
@@ -566,8 +627,10 @@ std::vector<int> TTSEngine::synthesize_tokens_batch_streaming(const std::vector<
     };
     std::vector<int64_t> all;
     if (codes) all.assign(token_ids.size() * (size_t)params.max_new_tokens * (size_t)n_groups_, 0);
+    if (sink_on()) sink_fn_ = [&](int utt, const void* pcm, int64_t n, int finished) { return on_audio(utt, (const float*)pcm, (size_t)n, finished != 0) ? 1 : 0; };
     const int rc = q3tts_synthesize_stream_host(h_, (int)token_ids.size(), flat.data(), offs.data(), lang_index(lang), nullptr, &sp, nullptr, seed_, 0,
                                                 nullptr, 0, nullptr, frames.data(), codes ? all.data() : nullptr, chunk_frames, cb, &ctx);
+    sink_fn_ = nullptr;
     if (rc != 0) {
         std::cerr << "[TTSEngine] Synthesis error: " << q3tts_last_error(h_) << std::endl;
         return {};

@@ -163,6 +163,18 @@ public:
     std::vector<float> synthesize_clone_icl(const std::vector<int64_t>& token_ids, const std::vector<int64_t>& ref_text_ids,
                                             const std::string& ref_wav_path, Language lang = Language::Auto,
                                             const SamplingParams& params = SamplingParams(), std::vector<int64_t>* all_codes = nullptr);
+    // Output format (include/q3tts.h: q3tts_engine_set_sink, q3tts_pcm_sink_*; beside the reference's methods, which deliver 24 kHz
+    // float only).  While a format other than 24 000 Hz float is set, the scheduler's streaming methods
+    // (synthesize_tokens_batch_streaming, synthesize_tokens_live, synthesize_tokens_continue_streaming) deliver their chunks at
+    // sample_rate (4 000 .. 192 000), band-limited on the GPU; the finishing chunk carries the resampler's tail.  With pcm16 the
+    // pointer a callback receives addresses int16_t samples (cast it; n still counts samples).  set_output_format(24000, false) is
+    // the default again.  false (and get_error()) for a rate the engine refuses.  The non-streaming methods keep returning 24 kHz
+    // float: convert_output brings a whole clip to the set format in one push + finish of the same resampler (exactly one of
+    // f32 / s16 is filled, by the format; at 24 000 Hz float f32 is the input).
+    bool set_output_format(int sample_rate, bool pcm16 = false);
+    int output_rate() const { return out_rate_; }
+    bool output_pcm16() const { return out_pcm16_; }
+    bool convert_output(const std::vector<float>& pcm24, std::vector<float>* f32, std::vector<int16_t>* s16);
     bool has_audio_encoder() const;
     int n_groups() const { return n_groups_; }
     bool has_speaker_encoder() const; // true when the weight file carries the spk.* tensors (reference: speaker_encoder.onnx present)
@@ -182,6 +194,10 @@ private:
     int cfg_hidden_ = 1024;
     int max_ctx_ = 0;
     int n_groups_ = config::NUM_CODE_GROUPS;
+    int out_rate_ = config::SAMPLE_RATE;
+    bool out_pcm16_ = false;
+    std::function<int(int, const void*, int64_t, int)> sink_fn_;   // the running streaming call's delivery, while an output format is set
+    bool sink_on() const { return out_rate_ != config::SAMPLE_RATE || out_pcm16_; }
 };
 
 inline int64_t language_to_codec_id(Language lang) { // reference src/tts_onnx.h:230-238

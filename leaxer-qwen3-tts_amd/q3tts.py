@@ -116,10 +116,20 @@ EXPORTS = [
     "q3tts_resample_stream_emitted",
     "q3tts_audio_encode_batch_host", "q3tts_audio_encode_latents_host", "q3tts_audio_encode_batch_latents_host", "q3tts_last_audio_encode_ms", "q3tts_test_audio_encoder_transformer_host",
     "q3tts_codec_stream_prime_batch_host", "q3tts_slots_codec_prime", "q3tts_codec_stream_info", "q3tts_synthesize_continue_stream_host",
+    "q3tts_sink_plan", "q3tts_sink_last_error", "q3tts_sink_emitted", "q3tts_pcm_sink_begin", "q3tts_pcm_sink_push_batch_host", "q3tts_pcm_sink_end",
+    "q3tts_codec_stream_set_sink", "q3tts_codec_stream_push_batch_any_host", "q3tts_engine_set_sink",
 ]
 
 # q3tts_audio_cb: int (*)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished)
 AUDIO_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int64, C.c_int)
+# q3tts_audio_any_cb: the same with const void* pcm, read in the sink's format
+AUDIO_ANY_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int)
+
+
+class Sink(C.Structure):   # q3tts_sink
+    _fields_ = [("sample_rate", C.c_int32), ("format", C.c_int32), ("cb", AUDIO_ANY_CB), ("user", C.c_void_p)]
+
+
 # q3tts_text_cb: int (*)(void* user, int utt, int64_t* ids, int cap, int32_t* n, int32_t* closed)
 TEXT_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32))
 
@@ -484,12 +494,97 @@ class Engine:
         self._ck(self.L.q3tts_codec_decode_chunked_host(self.h, _p(c), c.shape[0], chunk_frames, left_context, _p(pcm), n, C.byref(out_len)))
         return pcm[: out_len.value]
 
-    def codec_stream_begin(self, max_frames):
-        """streaming vocoder with carried state: -> stream id (q3tts_codec_stream_begin)"""
+    def codec_stream_begin(self, max_frames, sample_rate=24000, dtype="float32"):
+        """streaming vocoder with carried state: -> stream id (q3tts_codec_stream_begin).  sample_rate / dtype other than 24000 /
+        float32 give the stream a sink (q3tts_codec_stream_set_sink): codec_stream_push_batch then delivers at that rate, as float32
+        or int16."""
+        fmt = _pcm_format(dtype)
         sid = C.c_int(-1)
         self.L.q3tts_codec_stream_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         self._ck(self.L.q3tts_codec_stream_begin(self.h, int(max_frames), C.byref(sid)))
+        self.__dict__.setdefault("_codec_stream_fmt", {}).pop(sid.value, None)
+        if int(sample_rate) != 24000 or fmt != PCM_F32:
+            try:
+                self.codec_stream_set_sink(sid.value, sample_rate, dtype)
+            except Exception:
+                self.codec_stream_end(sid.value)
+                raise
         return sid.value
+
+    def codec_stream_set_sink(self, sid, sample_rate, dtype="float32"):
+        """q3tts_codec_stream_set_sink: refused once the stream has delivered a sample; 24000 / float32 takes the sink away"""
+        fmt = _pcm_format(dtype)
+        self.L.q3tts_codec_stream_set_sink.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int]
+        self._ck(self.L.q3tts_codec_stream_set_sink(self.h, int(sid), int(sample_rate), fmt))
+        d = self.__dict__.setdefault("_codec_stream_fmt", {})
+        if int(sample_rate) == 24000 and fmt == PCM_F32:
+            d.pop(int(sid), None)
+        else:
+            d[int(sid)] = (int(sample_rate), fmt)
+
+    # ---- PCM sinks on their own (include/q3tts.h "audio out at the sink's rate") ----
+    def pcm_sink_begin(self, sample_rate, dtype="float32"):
+        """a sink that takes 24 kHz float32 and delivers sample_rate (4000 .. 192000) as float32 or int16 -> sink id"""
+        fmt = _pcm_format(dtype)
+        sid = C.c_int(-1)
+        self.L.q3tts_pcm_sink_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.POINTER(C.c_int)]
+        self._ck(self.L.q3tts_pcm_sink_begin(self.h, int(sample_rate), fmt, C.byref(sid)))
+        self.__dict__.setdefault("_pcm_sink_fmt", {})[sid.value] = (int(sample_rate), fmt)
+        return sid.value
+
+    def pcm_sink_push_batch(self, ids, pcm_list, finish=None):
+        """more 24 kHz samples for many sinks in one launch (q3tts_pcm_sink_push_batch_host); finish: one flag per sink (its tail is
+        flushed with this push) -> one array per sink in its own dtype"""
+        n = len(ids)
+        if n == 0:
+            return []
+        if len(pcm_list) != n or (finish is not None and len(finish) != n):
+            raise ValueError("pcm_sink_push_batch: one sample array (and one finish flag) per sink")
+        fmts = self.__dict__.setdefault("_pcm_sink_fmt", {})
+        xs = [np.ascontiguousarray(a, np.float32).reshape(-1) for a in pcm_list]
+        fin = np.zeros(n, np.uint8) if finish is None else np.ascontiguousarray([1 if f else 0 for f in finish], np.uint8)
+        lens = np.array([x.size for x in xs], np.int64)
+        cap = 1
+        for i in range(n):
+            rate, _ = fmts.get(int(ids[i]), (192000, PCM_F32))
+            cap = max(cap, (int(lens[i]) + 200) * max(rate, 24000) // 24000 + 8)
+        outs = [np.empty(cap, np.int16 if fmts.get(int(ids[i]), (0, PCM_F32))[1] == PCM_S16 else np.float32) for i in range(n)]
+        xptr = (C.c_void_p * n)(*[x.ctypes.data if x.size else None for x in xs])
+        optr = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        out_len = np.zeros(n, np.int64)
+        self.L.q3tts_pcm_sink_push_batch_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        self._ck(self.L.q3tts_pcm_sink_push_batch_host(self.h, n, _p(np.ascontiguousarray(ids, np.int32)), C.cast(xptr, C.c_void_p), _p(lens), _p(fin),
+                                                       C.cast(optr, C.c_void_p), cap, _p(out_len)))
+        return [outs[i][: out_len[i]] for i in range(n)]
+
+    def pcm_sink_end(self, sink_id):
+        self.L.q3tts_pcm_sink_end.argtypes = [C.c_void_p, C.c_int]
+        self._ck(self.L.q3tts_pcm_sink_end(self.h, int(sink_id)))
+        self.__dict__.setdefault("_pcm_sink_fmt", {}).pop(int(sink_id), None)
+
+    def set_sink(self, sample_rate=None, dtype="float32", on_audio=None):
+        """q3tts_engine_set_sink: the streaming entries deliver through on_audio(utt, frame_begin, frame_end, pcm, finished) at
+        sample_rate as float32 or int16; sample_rate None takes the sink away.  An exception in on_audio cancels the job; it is kept
+        in self._sink_raised for the caller to re-raise."""
+        self.L.q3tts_engine_set_sink.argtypes = [C.c_void_p, C.c_void_p]
+        if sample_rate is None:
+            self._ck(self.L.q3tts_engine_set_sink(self.h, None))
+            self._sink_keep = None
+            return
+        fmt = _pcm_format(dtype)
+        npdt = np.int16 if fmt == PCM_S16 else np.float32
+        self._sink_raised = []
+
+        def tramp(_user, utt, fb, fe, p, ns, fin):
+            try:
+                a = np.frombuffer((C.c_char * (int(ns) * npdt().itemsize)).from_address(p), npdt).copy() if ns > 0 else np.zeros(0, npdt)
+                return 1 if on_audio(utt, fb, fe, a, bool(fin)) else 0
+            except BaseException as ex:   # an exception must not cross the C frames
+                self._sink_raised.append(ex)
+                return 1
+        sk = Sink(int(sample_rate), fmt, AUDIO_ANY_CB(tramp), None)
+        self._ck(self.L.q3tts_engine_set_sink(self.h, C.cast(C.pointer(sk), C.c_void_p)))
+        self._sink_keep = sk   # the callback object must outlive the jobs
 
     def codec_stream_push(self, sid, codes):
         """the next frames' codes [n][n_groups] -> the samples they own"""
@@ -501,16 +596,31 @@ class Engine:
         self._ck(self.L.q3tts_codec_stream_push_host(self.h, sid, _p(c), c.shape[0], _p(pcm), cap, C.byref(n)))
         return pcm[: n.value]
 
-    def codec_stream_push_batch(self, sids, codes_list):
+    def codec_stream_push_batch(self, sids, codes_list, finish=None):
         """the next frames of many streams in one batched pass (q3tts_codec_stream_push_batch_host): one [n_s][n_groups] code array per
-        stream (n_s may be 0: the stream is left untouched) -> one PCM array each"""
+        stream (n_s may be 0: the stream is left untouched) -> one PCM array each.  A stream begun with a sample_rate / dtype returns
+        its own format (q3tts_codec_stream_push_batch_any_host); finish: one flag per stream, a sink's tail is flushed with this push."""
         n = len(sids)
         if n == 0:
             return []
-        if len(codes_list) != n:
-            raise ValueError("codec_stream_push_batch: one code array per stream")
+        if len(codes_list) != n or (finish is not None and len(finish) != n):
+            raise ValueError("codec_stream_push_batch: one code array (and one finish flag) per stream")
         cs = [np.ascontiguousarray(c_, np.int64).reshape(-1, self.cfg.n_groups) for c_ in codes_list]
-        return self._push_batch(np.ascontiguousarray(sids, np.int32), cs, np.cumsum([0] + [c_.shape[0] for c_ in cs]).astype(np.int32))
+        ids = np.ascontiguousarray(sids, np.int32)
+        offs = np.cumsum([0] + [c_.shape[0] for c_ in cs]).astype(np.int32)
+        fmts = self.__dict__.setdefault("_codec_stream_fmt", {})
+        if finish is None and not any(int(i) in fmts for i in ids):
+            return self._push_batch(ids, cs, offs)
+        flat = np.ascontiguousarray(np.concatenate(cs)) if sum(c_.shape[0] for c_ in cs) else np.zeros((1, self.cfg.n_groups), np.int64)
+        n24 = self.codec_decode_len(max(max(c_.shape[0] for c_ in cs), 1)) + 4096
+        cap = max((n24 + 200) * max(fmts.get(int(i), (24000, PCM_F32))[0], 24000) // 24000 + 8 for i in ids)
+        pcm = [np.empty(cap, np.int16 if fmts.get(int(i), (24000, PCM_F32))[1] == PCM_S16 else np.float32) for i in ids]
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in pcm])
+        pcm_len = np.zeros(n, np.int64)
+        fin = np.zeros(n, np.uint8) if finish is None else np.ascontiguousarray([1 if f else 0 for f in finish], np.uint8)
+        self.L.q3tts_codec_stream_push_batch_any_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        self._ck(self.L.q3tts_codec_stream_push_batch_any_host(self.h, n, _p(ids), _p(flat), _p(offs), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(fin)))
+        return [pcm[i][: pcm_len[i]] for i in range(n)]
 
     def _push_batch(self, ids, cs, offs):
         n = len(ids)
@@ -574,6 +684,7 @@ class Engine:
     def codec_stream_end(self, sid):
         self.L.q3tts_codec_stream_end.argtypes = [C.c_void_p, C.c_int]
         self._ck(self.L.q3tts_codec_stream_end(self.h, sid))
+        self.__dict__.setdefault("_codec_stream_fmt", {}).pop(int(sid), None)
 
     def slot_codec_decode_range(self, slot, frame_begin, frame_end, left_context):
         """samples owned by frames [frame_begin, frame_end) of a slot (streaming while it generates)"""
@@ -1297,8 +1408,29 @@ class Engine:
         self._ck(rc)
         return [pcm[i][: pcm_len[i]] for i in range(n)], [codes[i, : nfr[i]] for i in range(n)], nfr
 
+    def _sink_job(self, sample_rate, dtype, on_audio, n, run):
+        """a streaming job through a sink of its own: run(None-pcm_out) with the sink set, the sink taken away afterwards; the chunks
+        on_audio saw are also returned joined per utterance"""
+        fmt = _pcm_format("float32" if dtype is None else dtype)
+        got = [[] for _ in range(n)]
+
+        def tee(utt, fb, fe, a, fin):
+            got[utt].append(a)
+            return on_audio(utt, fb, fe, a, fin) if on_audio is not None else 0
+        self.set_sink(24000 if sample_rate is None else sample_rate, "int16" if fmt == PCM_S16 else "float32", tee)
+        try:
+            rc = run()
+        finally:
+            raised = self._sink_raised
+            self.set_sink(None)
+        if raised:
+            raise raised[0]
+        self._ck(rc)
+        npdt = np.int16 if fmt == PCM_S16 else np.float32
+        return [np.concatenate(g) if g else np.zeros(0, npdt) for g in got]
+
     def synthesize_stream(self, token_lists, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
-                          max_new_per_utt=None, instructs=None):
+                          max_new_per_utt=None, instructs=None, sample_rate=None, dtype=None):
         """synthesize_batch that delivers audio while it generates (q3tts_synthesize_stream_host): every chunk_frames steps
         on_audio(utt, frame_begin, frame_end, pcm, finished) is called once per utterance with new audio (pcm: a copy); a truthy return
         cancels the job (RuntimeError "cancelled by callback").  Returns what synthesize_batch returns."""
@@ -1338,6 +1470,17 @@ class Engine:
         self.L.q3tts_synthesize_stream_host.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.POINTER(Sampling), vp, C.c_uint64, C.c_int, vp, C.c_int64, vp, vp, vp,
                                                         C.c_int, AUDIO_CB, vp]
         ins_flat, ins_offs = self._instruct_args(instructs, n)
+        if sample_rate is not None or dtype is not None:   # through a sink (q3tts_engine_set_sink): sample_rate / dtype are the chunks' and the result's
+            def run():
+                if ins_flat is not None:
+                    return self.L.q3tts_synthesize_instruct_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
+                                                                 seed, int(ignore_eos), None, 0, _p(pcm_len), _p(nfr),
+                                                                 _p(codes) if want_codes else None, int(chunk_frames), cb, None, _p(ins_flat), _p(ins_offs))
+                return self.L.q3tts_synthesize_stream_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
+                                                           seed, int(ignore_eos), None, 0, _p(pcm_len), _p(nfr),
+                                                           _p(codes) if want_codes else None, int(chunk_frames), cb, None)
+            outs = self._sink_job(sample_rate, dtype, on_audio, n, run)
+            return outs, ([codes[i, : nfr[i]] for i in range(n)] if want_codes else None), nfr
         if ins_flat is not None:
             rc = self.L.q3tts_synthesize_instruct_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
                                                        seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr),
@@ -1354,7 +1497,7 @@ class Engine:
         return outs, cl, nfr
 
     def synthesize_live(self, n_utt, text_source, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
-                        max_new_per_utt=None):
+                        max_new_per_utt=None, sample_rate=None, dtype=None):
         """synthesize_stream for texts that arrive while their audio is generated (q3tts_synthesize_live_host): text_source(utt) ->
         (ids, closed) is polled between decode chunks for every utterance whose text is open — new ids (possibly none) and whether the
         text has ended; None cancels the job (RuntimeError "cancelled by callback").  An utterance's ids are those synthesize_stream
@@ -1411,6 +1554,18 @@ class Engine:
                 raised.append(ex)
                 return 1
         cb, tcb = AUDIO_CB(tramp), TEXT_CB(ttramp)
+        if sample_rate is not None or dtype is not None:   # through a sink, as synthesize_stream
+            def run():
+                return self.L.q3tts_synthesize_live_host(self.h, n, tcb, None, lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
+                                                         seed, int(ignore_eos), None, 0, _p(pcm_len), _p(nfr),
+                                                         _p(codes) if want_codes else None, int(chunk_frames), cb, None)
+            try:
+                outs = self._sink_job(sample_rate, dtype, on_audio, n, run)
+            except BaseException:
+                if raised:
+                    raise raised[0]
+                raise
+            return outs, ([codes[i, : nfr[i]] for i in range(n)] if want_codes else None), nfr
         rc = self.L.q3tts_synthesize_live_host(self.h, n, tcb, None, lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
                                                seed, int(ignore_eos), C.cast(ptrs, C.c_void_p), cap, _p(pcm_len), _p(nfr),
                                                _p(codes) if want_codes else None, int(chunk_frames), cb, None)
@@ -1564,6 +1719,35 @@ def resample_stream_emitted(src_rate, dst_rate, n_received, finish=False):
 
 
 PCM_F32, PCM_S16 = 0, 1
+
+
+def sink_plan(sample_rate, want_table=True):
+    """q3tts_sink_plan: -> (L, M, half, taps, table [L][taps] float32, or None) of the output resampler for sample_rate.  Host-only;
+    ValueError naming the rate when it is refused."""
+    Lb = lib()
+    Lb.q3tts_sink_plan.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int64]
+    Lb.q3tts_sink_last_error.restype = C.c_char_p
+    L_, M_, h_, t_ = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    if Lb.q3tts_sink_plan(int(sample_rate), C.byref(L_), C.byref(M_), C.byref(h_), C.byref(t_), None, 0) != 0:
+        raise ValueError(Lb.q3tts_sink_last_error().decode())
+    tab = None
+    if want_table:
+        tab = np.zeros((L_.value, t_.value), np.float32)
+        if tab.size and Lb.q3tts_sink_plan(int(sample_rate), None, None, None, None, _p(tab), tab.size) != 0:
+            raise ValueError(Lb.q3tts_sink_last_error().decode())
+    return L_.value, M_.value, h_.value, t_.value, tab
+
+
+def sink_emitted(sample_rate, n_received, finished=False):
+    """q3tts_sink_emitted: the samples a sink at sample_rate has delivered in all after n_received samples at 24 kHz.  Host-only."""
+    Lb = lib()
+    Lb.q3tts_sink_emitted.argtypes = [C.c_int32, C.c_int64, C.c_int]
+    Lb.q3tts_sink_emitted.restype = C.c_int64
+    Lb.q3tts_sink_last_error.restype = C.c_char_p
+    n = int(Lb.q3tts_sink_emitted(int(sample_rate), int(n_received), 1 if finished else 0))
+    if n < 0:
+        raise ValueError(Lb.q3tts_sink_last_error().decode())
+    return n
 
 
 def _pcm_format(dtype):
