@@ -684,6 +684,59 @@ typedef int (*q3tts_audio_any_cb)(void* user, int utt, int frame_begin, int fram
 typedef struct { int32_t sample_rate; int32_t format; q3tts_audio_any_cb cb; void* user; } q3tts_sink;
 int q3tts_engine_set_sink(q3tts_engine* e, const q3tts_sink* sink);
 
+/* ---- speaking rate: carried-state WSOLA time stretch ([HINT] no counterpart in the reference, which has no speed control; DESIGN.md
+ * 4m) ----
+ * A speed S, an integer in permille (500 .. 2000), makes the audio S / 1000 times as fast at the same pitch: waveform-similarity
+ * overlap-add (Verhelst & Roelands 1993) with a fixed synthesis hop, on the GPU between the vocoder and the sink, all stretchers of a push
+ * in one launch.  S = 1000 is "no stage": no launch, the same bytes as before (the stretcher is not the identity there, so 1000 bypasses it).
+ * Constants at 24 kHz: frame N = 720, synthesis hop Hs = 360, search tolerance D = 240 (2 D + 1 = 481 lags).  Window w[i] = 0.5 - 0.5 cos(2 pi i
+ * / N), formed in double and rounded to float (w[i] + w[i + Hs] = 1).  Positions are 64-bit integers: a_m = floor(m Hs S / 1000); the chosen
+ * segment start p_m = a_m + delta_m with delta_m in [-D, D]; p_{-1} = -Hs; x[k] = 0 for k < 0 and, once the stretcher is finished with n
+ * samples, for k >= n.  Frame m >= 0: template t[i] = x[p_{m-1} + Hs + i], 0 <= i < N; for each lag c(delta) = (s0 + s1) + (s2 + s3) with
+ * s_q = sum of t[i] x[a_m + delta + i] over i = q (mod 4), i ascending, every product and add rounded to fp32, unfused; delta_m is the lag
+ * with the largest c, the smallest delta among equals; y[m Hs + i] = (w[Hs + i] t[i]) + (w[i] x[p_m + i]) for 0 <= i < Hs: two fp32 products
+ * and one fp32 add.  So the output is a function of the input and S alone: never of how the audio was cut into pushes or of which
+ * stretchers shared a launch.
+ * Frame m is ready after R received samples when need(m) <= R, need(m) = max(a_m + D + N, a_{m-1} + D + Hs + N) (second term for m >= 1):
+ * integers only, independent of every delta.  Unfinished, a stretcher has emitted E(R) = Hs #{m : need(m) <= R}; finished with n samples,
+ * T = ceil(1000 n / S): ceil(T / Hs) frames, the last block cut to T.  A push delivers E(after) - E(before).  Latency: at most N + D + Hs
+ * input samples (55 ms).  The stretcher carries its input from a_{F-1} - D on (F: the next frame; fewer than 2 D + N + 2 Hs = 1920 floats),
+ * p_{F-1} and the frame counter, in two alternating buffers of its own.
+ * Known limit: a primed stream's stretcher (q3tts_codec_stream_prime_batch_host, q3tts_synthesize_continue_stream_host) starts from
+ * silence, x[k] = 0 for k < 0, like its sink: the first frame's template is zero, not the prefix's last samples. */
+/* Host only, no engine.  Outputs a stretcher at speed_permille has emitted in all after n_received samples (finished != 0: the whole
+ * clip's ceil(1000 n / S)).  -1 for a speed outside 500 .. 2000 or n_received < 0; q3tts_speed_last_error() then names the value
+ * (thread-local, valid until the thread's next speed_emitted / speed_window call).  1000 is answered by the same rule. */
+int64_t q3tts_speed_emitted(int32_t speed_permille, int64_t n_received, int finished);
+const char* q3tts_speed_last_error(void);
+/* Host only: the window the device uses, 720 floats; -1 when table is NULL or cap < 720. */
+int q3tts_speed_window(float* table, int64_t cap);
+/* Stretchers on their own: the stage by itself, fed 24 kHz float from the host.  A stretcher accepts at most one hour of input
+ * (86 400 000 samples), a push at most 1 440 000.  At most 4096 stretchers are open at a time (vocoder streams' included).  1000 is
+ * refused: it is no stage. */
+int q3tts_speed_begin(q3tts_engine* e, int32_t speed_permille, int* id);
+/* n stretchers (distinct, open, not finished), stretcher i given n_in[i] >= 0 more samples pcm24[i]; finish[i] != 0 (finish NULL: none)
+ * flushes the tail with this push and closes the stretcher's audio (n_in[i] == 0 allowed).  out[i] has room for cap_samples floats;
+ * out_len[i] is the push's length by the rule above (min(out_len, cap_samples) samples are written).  offsets_out (NULL ok) and
+ * offsets_out[i] (NULL ok): room for cap_samples / 360 + 1 offsets, receives the delta of every frame the push completed; n_offsets[i]
+ * (NULL ok): how many those are.  The call is validated completely before any stretcher moves.  n_in[i] == 0 without finish leaves the
+ * stretcher as it was; a push that completes no frame still updates the carry. */
+int q3tts_speed_push_batch_host(q3tts_engine* e, int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in,
+                                const uint8_t* finish, float* const* out, int64_t cap_samples, int64_t* out_len,
+                                int32_t* const* offsets_out, int64_t* n_offsets);
+int q3tts_speed_end(q3tts_engine* e, int id);
+/* Vocoder streams.  A stream delivers time-stretched from its first sample on: refused, by name, once the stream has delivered a
+ * sample.  1000 takes the stage away again.  q3tts_codec_stream_push_batch_any_host serves such streams: the stretcher runs on the
+ * push's PCM where it lies, and its output feeds the stream's sink in the same push when it has one (the sink's input length is the
+ * stretcher's push length); finish[s] flushes the stretcher first, then the sink, and is allowed on a stream with a speed and no
+ * sink.  The float entries refuse a stream with a speed by name, as they refuse one with a sink. */
+int q3tts_codec_stream_set_speed(q3tts_engine* e, int stream_id, int32_t speed_permille);
+/* The scheduler: one setter for the four streaming entries, beside q3tts_engine_set_sink.  With a sink set, delivery goes through
+ * the sink's callback in the sink's format; without one, through the entry's own float callback (a non-NULL pcm_out then receives the
+ * stretched audio).  The finished = 1 call carries the flushed tail, so an utterance's calls add up to ceil(1000 n24 / S) samples at
+ * 24 kHz.  Codes, frame counts and RNG use are untouched.  1000: none. */
+int q3tts_engine_set_speed(q3tts_engine* e, int32_t speed_permille);
+
 /* ---- text front end: the reference's byte-level BPE tokenizer ---- */
 /* Replaces leaxer_qwen::io::load_vocab / load_merges / is_tokenizer_ready / tokenize (reference
  * src/io/tokenizer.h:13-22, src/io/tokenizer.cpp:538-561) with the same ids for the same files and text.

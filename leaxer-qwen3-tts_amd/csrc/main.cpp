@@ -9,6 +9,7 @@
 // milliseconds at a time through one encoder stream opened at the file's own rate: the same codes, and no 60 s limit), --ref WAV with --ref-text TEXT /
 // --ref-tokens "id,id,..." (in-context clone: the reference's codes and text in front of the utterance; --ref alone stays the x-vector clone).
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -76,6 +77,7 @@ static void usage(const char* prog) {
     printf("  --stream-chunk N      with --tokens: decode audio every N frames while generating (same samples as the one-shot decode);\n");
     printf("                        combines with --continue-codes and with --ref + --ref-text / --ref-tokens (the prefix is history, never decoded)\n");
     printf("  --out-rate R          write the WAV at R Hz (4000 .. 192000; default 24000): band-limited resampling on the GPU, in the stream's sink with --stream-chunk\n");
+    printf("  --speed X             speaking rate (0.5 .. 2.0; default 1.0): X times as fast at the same pitch, WSOLA time stretch on the GPU; composes with --out-rate and --stream-chunk\n");
     printf("  --feed K              with --stream-chunk: hand the text to the engine K tokens at a time while it generates (live text; same codes, and with --save-codes the same samples as without --feed)\n  -h, --help\n");
 }
 
@@ -152,6 +154,7 @@ int main(int argc, char** argv) {
     uint64_t seed = 0;
     int stream_chunk = 0, feed = 0, encode_chunk = 0, out_rate = config::SAMPLE_RATE;
     bool have_encode_chunk = false;
+    double speed = 1.0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         const bool more = i + 1 < argc;
@@ -179,6 +182,7 @@ int main(int argc, char** argv) {
         else if (a == "--stream-chunk" && more) stream_chunk = atoi(argv[++i]);
         else if (a == "--feed" && more) feed = atoi(argv[++i]);
         else if (a == "--out-rate" && more) out_rate = atoi(argv[++i]);
+        else if (a == "--speed" && more) speed = atof(argv[++i]);
     }
     const bool icl = !ref_text.empty() || !ref_tokens.empty();
     if (have_encode_chunk && (encode.empty() || encode_chunk < 1)) {
@@ -254,6 +258,11 @@ int main(int argc, char** argv) {
     // below); 24000 leaves everything as it is.  `audio` then holds the chunks' int16 samples, two to a float, counted by audio16
     const bool resample_out = out_rate != config::SAMPLE_RATE;
     if (resample_out && !engine.set_output_format(out_rate, true)) { fprintf(stderr, "Error: --out-rate %d: %s\n", out_rate, engine.get_error().c_str()); return 1; }
+    // --speed: S = round(1000 X) permille; 1000 is no stage (the bytes written without the flag)
+    const long speed_permille = std::lround(1000.0 * speed);
+    if (!(speed == speed) || speed_permille < 500 || speed_permille > 2000) { fprintf(stderr, "Error: --speed %g is outside 0.5 .. 2.0\n", speed); return 1; }
+    const bool sped = speed_permille != 1000;
+    if (sped && !engine.set_speed((float)speed)) { fprintf(stderr, "Error: --speed %g: %s\n", speed, engine.get_error().c_str()); return 1; }
     std::vector<int16_t> audio16;
     printf("Synthesizing...\n");
     std::vector<float> audio;

@@ -191,6 +191,33 @@ int64_t sink_emitted(const SinkPlan& d, int64_t n, bool finished) {
     return (m * d.L + d.M - 1) / d.M;
 }
 
+// ---- speaking rate (q3_audio.h) ----
+void speed_check(int speed) {
+    if (speed < kSpeedMin || speed > kSpeedMax)
+        throw std::invalid_argument("speed: " + std::to_string(speed) + " permille is outside " + std::to_string(kSpeedMin) + " .. " + std::to_string(kSpeedMax));
+}
+int64_t speed_frames(int speed, int64_t n, bool finished) {
+    if (n <= 0) return 0;
+    if (finished) return ((n * 1000 + speed - 1) / speed + kSpeedHs - 1) / kSpeedHs;
+    // need(m) <= a_m + Hs + D + N <= m Hs S / 1000 + Hs + D + N, so every m up to m0 is ready; need(m) >= a_m + D + N > m Hs S / 1000 - 1
+    // + D + N, so the walk from m0 ends within 1000 / S + 2 steps
+    const int64_t slack = n - (kSpeedHs + kSpeedD + kSpeedN);
+    int64_t m = slack >= 0 ? slack * 1000 / ((int64_t)kSpeedHs * speed) : 0;
+    if (speed_need(speed, m) > n) return 0;   // only m == 0 can come here
+    while (speed_need(speed, m) <= n) ++m;
+    return m;
+}
+int64_t speed_emitted(int speed, int64_t n, bool finished) {
+    if (n <= 0) return 0;
+    return finished ? (n * 1000 + speed - 1) / speed : kSpeedHs * speed_frames(speed, n, false);
+}
+std::vector<float> speed_window() {
+    std::vector<float> w((size_t)kSpeedN);
+    const double pi = 3.14159265358979323846;
+    for (int i = 0; i < kSpeedN; ++i) w[(size_t)i] = (float)(0.5 - 0.5 * std::cos(2.0 * pi * (double)i / (double)kSpeedN));
+    return w;
+}
+
 // ---------------------------------------------------------------------------------------------
 // log-mel (reference mel.cpp:13-80 filterbank, :182-236 framing).  NOT librosa's: symmetric Hann
 // window, no centre padding, frames = (n - win)/hop + 1 (one zero-padded frame for shorter clips),

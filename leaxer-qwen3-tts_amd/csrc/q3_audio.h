@@ -6,6 +6,7 @@
 #ifndef Q3_AUDIO_H
 #define Q3_AUDIO_H
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -40,6 +41,26 @@ SinkPlan sink_plan(int rate);
 int64_t sink_emitted(const SinkPlan& dims, int64_t n_received, bool finished);
 // input samples a sink carries from push to push: 2 * half + ceil(M / L)
 inline int sink_carry(const SinkPlan& d) { return d.taps == 0 ? 0 : 2 * d.half + (d.M + d.L - 1) / d.L; }
+
+// ---- speaking rate: WSOLA time stretch at 24 kHz (the arithmetic is fixed in include/q3tts.h) ----
+// Frame length N, synthesis hop Hs, search tolerance D; speed S in permille (kSpeedMin .. kSpeedMax, 1000: no stage).  Analysis
+// position a_m = floor(m Hs S / 1000).  Everything here is 64-bit integer arithmetic and independent of the offsets the search picks.
+constexpr int kSpeedN = 720, kSpeedHs = 360, kSpeedD = 240;
+constexpr int kSpeedMin = 500, kSpeedMax = 2000;
+constexpr int kSpeedCarry = 2 * kSpeedD + kSpeedN + 2 * kSpeedHs;   // 1920: strict upper bound of the samples a stretcher carries
+void speed_check(int speed);   // throws std::invalid_argument naming the speed when it is outside kSpeedMin .. kSpeedMax
+inline int64_t speed_pos(int speed, int64_t m) { return m * kSpeedHs * speed / 1000; }
+// frame m is ready once need(m) = max(a_m + D + N, a_{m-1} + D + Hs + N) samples have been received (second term for m >= 1)
+inline int64_t speed_need(int speed, int64_t m) {
+    const int64_t a = speed_pos(speed, m) + kSpeedD + kSpeedN;
+    return m >= 1 ? std::max(a, speed_pos(speed, m - 1) + kSpeedD + kSpeedHs + kSpeedN) : a;
+}
+// frames a stretcher has completed after n_received samples: unfinished #{m : need(m) <= n}, finished ceil(ceil(1000 n / S) / Hs)
+int64_t speed_frames(int speed, int64_t n_received, bool finished);
+// outputs it has emitted in all: unfinished Hs * frames, finished ceil(1000 n / S)
+int64_t speed_emitted(int speed, int64_t n_received, bool finished);
+// the window w[i] = 0.5 - 0.5 cos(2 pi i / N), formed in double and rounded to float (kSpeedN entries)
+std::vector<float> speed_window();
 
 struct MelSpec { // the settings of tts_onnx.cpp:347-354
     int sample_rate = 24000, n_fft = 1024, hop = 256, win = 1024, n_mels = 128;

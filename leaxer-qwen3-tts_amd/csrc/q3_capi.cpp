@@ -18,6 +18,7 @@ struct q3tts_engine {
     Engine* e = nullptr;
     std::string err;
     q3tts_sink sink = { 0, 0, nullptr, nullptr };   // q3tts_engine_set_sink (sample_rate 0: none)
+    int32_t speed = 1000;                           // q3tts_engine_set_speed (1000: none)
 };
 static std::string g_create_err;
 
@@ -406,6 +407,60 @@ int q3tts_engine_set_sink(q3tts_engine* h, const q3tts_sink* sink) {
     if (!sink->cb) throw q3::Error("engine_set_sink: null callback");
     (void)h->e->pcm_sink_plan(sink->sample_rate);   // refuses a bad rate by name, and has the table uploaded before the first utterance
     h->sink = *sink;
+    return 0;
+    Q3_API_END(h)
+}
+
+// ---- speaking rate (include/q3tts.h "speaking rate") ----
+static thread_local std::string g_speed_err;
+const char* q3tts_speed_last_error(void) { return g_speed_err.c_str(); }
+int64_t q3tts_speed_emitted(int32_t speed_permille, int64_t n_received, int finished) {
+    g_speed_err.clear();
+    try {
+        q3::speed_check(speed_permille);
+        if (n_received < 0) throw std::invalid_argument("speed: negative sample count " + std::to_string(n_received));
+        return q3::speed_emitted(speed_permille, n_received, finished != 0);
+    } catch (const std::exception& ex) { g_speed_err = ex.what(); return -1; }
+    catch (...) { g_speed_err = "unknown error"; return -1; }
+}
+int q3tts_speed_window(float* table, int64_t cap) {
+    g_speed_err.clear();
+    if (!table || cap < q3::kSpeedN) { g_speed_err = "speed window: the table holds " + std::to_string(q3::kSpeedN) + " floats"; return -1; }
+    const std::vector<float> w = q3::speed_window();
+    memcpy(table, w.data(), w.size() * sizeof(float));
+    return 0;
+}
+int q3tts_speed_begin(q3tts_engine* h, int32_t speed_permille, int* id) {
+    Q3_API_BEGIN(h)
+    if (!id) throw q3::Error("speed: NULL argument");
+    *id = h->e->speed_begin(speed_permille);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_speed_push_batch_host(q3tts_engine* h, int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in,
+                                const uint8_t* finish, float* const* out, int64_t cap_samples, int64_t* out_len,
+                                int32_t* const* offsets_out, int64_t* n_offsets) {
+    Q3_API_BEGIN(h)
+    h->e->speed_push_batch_host(n, ids, pcm24, n_in, finish, out, cap_samples, out_len, offsets_out, n_offsets);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_speed_end(q3tts_engine* h, int id) {
+    Q3_API_BEGIN(h)
+    h->e->speed_end(id);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_codec_stream_set_speed(q3tts_engine* h, int stream_id, int32_t speed_permille) {
+    Q3_API_BEGIN(h)
+    h->e->codec_stream_set_speed(stream_id, speed_permille);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_engine_set_speed(q3tts_engine* h, int32_t speed_permille) {
+    Q3_API_BEGIN(h)
+    try { q3::speed_check(speed_permille); } catch (const std::invalid_argument& ex) { throw q3::Error(std::string("engine_set_speed: ") + ex.what()); }
+    h->speed = speed_permille;
     return 0;
     Q3_API_END(h)
 }
@@ -1067,18 +1122,23 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     const int cf = std::min(chunk_frames, e.max_frames_cap);   // samples of cf frames at the start of an utterance / further in
     const int64_t chunk_cap = std::max(q3tts_codec_decode_len(&e.c, cf), q3tts_codec_decode_len(&e.c, cf + 1) - q3tts_codec_decode_len(&e.c, 1));
     // with a sink a chunk's buffer holds the sink's samples: the chunk's share plus the flushed tail, by the host rule's closed form
+    // with a speed (q3tts_engine_set_speed) the chunk first passes its stretcher: at most the chunk plus what the stretcher held back
+    // (N + D + Hs input samples), 1000 / S times as long, plus the cut last block
+    const int speed = h->speed;
+    const bool sped = speed != 1000;
+    const int64_t stage_cap = sped ? ((chunk_cap + q3::kSpeedN + q3::kSpeedD + q3::kSpeedHs) * 1000 + speed - 1) / speed + q3::kSpeedHs : chunk_cap;
     const q3::SinkPlan* splan = sunk ? &e.pcm_sink_plan(sink.sample_rate).plan : nullptr;
-    const int64_t sink_cap = sunk ? ((chunk_cap + splan->half) * splan->L + splan->M - 1) / splan->M + 2 : 0;
-    const int64_t chunk_floats = sunk ? (sink_cap * (sink.format == Q3TTS_PCM_S16 ? 2 : 4) + 3) / 4 : chunk_cap;   // per slot, 4-byte aligned
-    const int64_t deliver_cap = sunk ? sink_cap : chunk_cap;
+    const int64_t sink_cap = sunk ? ((stage_cap + splan->half) * splan->L + splan->M - 1) / splan->M + 2 : 0;
+    const int64_t chunk_floats = sunk ? (sink_cap * (sink.format == Q3TTS_PCM_S16 ? 2 : 4) + 3) / 4 : stage_cap;   // per slot, 4-byte aligned
+    const int64_t deliver_cap = sunk ? sink_cap : stage_cap;
     std::vector<float> chunk_pcm((size_t)B * chunk_floats);
     std::vector<float*> pcm_ptr((size_t)B);
     std::vector<int32_t> final_frames((size_t)B, -1);
     struct SlotSinkScope {   // the slots' implicit streams take the sink for the duration of this call only
         Engine& e;
-        SlotSinkScope(Engine& en, int rate, int fmt) : e(en) { e.slot_sink_rate = rate; e.slot_sink_format = fmt; }
-        ~SlotSinkScope() { e.slot_sink_rate = 0; e.slot_sink_format = 0; }
-    } sink_scope(e, sunk && !(sink.sample_rate == 24000 && sink.format == Q3TTS_PCM_F32) ? sink.sample_rate : 0, sink.format);
+        SlotSinkScope(Engine& en, int rate, int fmt, int spd) : e(en) { e.slot_sink_rate = rate; e.slot_sink_format = fmt; e.slot_speed = spd; }
+        ~SlotSinkScope() { e.slot_sink_rate = 0; e.slot_sink_format = 0; e.slot_speed = 0; }
+    } sink_scope(e, sunk && !(sink.sample_rate == 24000 && sink.format == Q3TTS_PCM_F32) ? sink.sample_rate : 0, sink.format, sped ? speed : 0);
     std::vector<int32_t> slots, fb((size_t)B), fe((size_t)B);
     std::vector<int64_t> plen((size_t)B), written((size_t)n_utt, 0);
     std::vector<Engine::SlotInit> init;

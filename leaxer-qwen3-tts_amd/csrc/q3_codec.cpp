@@ -68,7 +68,8 @@ struct CodecW {
     // later query can reach).  hpost: [h_cap][hidden], `h_rows` stored, the newest codec_stage_b_context() rows kept the same way.
     // sink: the stream's PCM sink (Engine::sinks; -1: the stream delivers 24 kHz float); delivered: a push has returned samples
     struct Stream { bool used = false; int cap = 0, P = 0, pshift = 0, n_done = 0, kv_rows = 0, h_cap = 0, h_rows = 0; float* kv = nullptr; float* hpost = nullptr;
-                    int sink = -1; bool delivered = false; };
+                    int sink = -1; bool delivered = false;
+                    int speed = -1; /* the stream's stretcher (Engine::stretchers; -1: none), ahead of its sink */ };
     std::vector<Stream> streams;
     char* stream_arena = nullptr; size_t stream_arena_bytes = 0;
     std::vector<int> slot_stream;          // slot -> stream id (-1: none): q3tts_slot_codec_decode_range_host's implicit stream
@@ -716,7 +717,7 @@ int Engine::codec_stream_begin(int max_frames) {
     S.kv_rows = 0; S.h_rows = 0;                       // nothing of the buffers' previous stream is kept
     codec_stream_fit(sid, std::min(max_frames, 64));
     S.cap = max_frames;
-    S.used = true; S.n_done = 0; S.sink = -1; S.delivered = false;
+    S.used = true; S.n_done = 0; S.sink = -1; S.speed = -1; S.delivered = false;
     int P = 1;
     while (P < max_frames) P <<= 1;
     codec_rope_tables(P);   // positions are absolute in the RoPE tables (grow-only, shared)
@@ -772,6 +773,17 @@ void Engine::codec_stream_end(int sid) {
     codec->streams[(size_t)sid].n_done = 0;
     if (codec->streams[(size_t)sid].sink >= 0) pcm_sink_end(codec->streams[(size_t)sid].sink);
     codec->streams[(size_t)sid].sink = -1;
+    if (codec->streams[(size_t)sid].speed >= 0) speed_end(codec->streams[(size_t)sid].speed);
+    codec->streams[(size_t)sid].speed = -1;
+}
+
+void Engine::codec_stream_set_speed(int sid, int speed) {
+    if (!codec || sid < 0 || sid >= (int)codec->streams.size() || !codec->streams[(size_t)sid].used) throw Error("codec_stream_set_speed: no such stream");
+    CodecW::Stream& S = codec->streams[(size_t)sid];
+    if (S.delivered) throw Error("codec_stream_set_speed: stream " + std::to_string(sid) + " has already delivered samples");
+    const int id = speed == 1000 ? -1 : speed_begin(speed);   // 1000 is "no stage"; a bad speed throws before the old stretcher goes
+    if (S.speed >= 0) speed_end(S.speed);
+    S.speed = id;
 }
 
 void Engine::codec_stream_set_sink(int sid, int rate, int format) {
@@ -802,6 +814,7 @@ int64_t Engine::codec_stream_push_dev(int sid, const int32_t* codes_dev, int n, 
     CodecW::Stream& S = W.streams[(size_t)sid];
     if (n < 1) throw Error("codec_stream_push: no frames");
     if (S.sink >= 0) throw Error("codec_stream_push: stream " + std::to_string(sid) + " has a sink: push it through the batched entry that takes any format");
+    if (S.speed >= 0) throw Error("codec_stream_push: stream " + std::to_string(sid) + " has a speed: push it through the batched entry that takes any format");
     if (S.n_done + n > S.cap) throw Error("codec_stream_push: more frames than the stream was opened for");
     const int CH = c.cd_hidden, NH = c.cd_heads, HD = c.cd_head_dim, FF = c.cd_ffn;
     const int a0 = S.n_done, b0 = a0 + n, T = n;
@@ -936,31 +949,71 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
     std::vector<SinkPush> sp((size_t)g_all);     // entry i belongs to ps[i]; sink == -1: none
     size_t sink_bytes = 0;
     int n_sinks = 0;
+    // streams with a speed: the stretcher stands ahead of the sink, whose input is then the stretcher's push (the same host rules)
+    std::vector<SpeedPush> vp((size_t)g_all);    // entry i belongs to ps[i]; id == -1: none
+    size_t speed_floats = 0, speed_frames_total = 0;
+    int n_speed = 0;
     for (int i = 0; i < g_all; ++i) {
         const StreamPush& q = ps[i];
         const CodecW::Stream& S = W.streams[(size_t)q.sid];
-        if (S.sink < 0) { if (q.finish) throw Error("codec_stream_push_batch: finish on stream " + std::to_string(q.sid) + ", which has no sink"); continue; }
+        int64_t n24 = len_all(S.n_done + q.n) - len_all(S.n_done);
+        if (S.speed >= 0) {
+            SpeedPush& v = vp[(size_t)i];
+            v.id = S.speed; v.n_new = n24; v.finish = q.finish;
+            if (S.sink < 0) { v.out_host = q.pcm; v.cap = q.cap; }
+            n24 = speed_push_len(v.id, v.n_new, v.finish);
+            speed_floats += speed_out_floats(n24);
+            speed_frames_total += (size_t)speed_push_frames(v.id, v.n_new, v.finish);
+            ++n_speed;
+        }
+        if (S.sink < 0) {
+            if (q.finish && S.speed < 0) throw Error("codec_stream_push_batch: finish on stream " + std::to_string(q.sid) + ", which has no sink");
+            continue;
+        }
         SinkPush& k = sp[(size_t)i];
-        k.sink = S.sink; k.n_new = len_all(S.n_done + q.n) - len_all(S.n_done); k.finish = q.finish; k.out_host = q.pcm; k.cap = q.cap;
+        k.sink = S.sink; k.n_new = n24; k.finish = q.finish; k.out_host = q.pcm; k.cap = q.cap;
         sink_bytes += pcm_sink_out_bytes(k.sink, k.n_new, k.finish);
         ++n_sinks;
     }
     if (n_sinks > 0) pcm_sinks_reserve(n_sinks, sink_bytes);
+    if (n_speed > 0) speed_reserve(n_speed, speed_floats, speed_frames_total);
     std::vector<SinkPush> sp_run;                // the sinks of one launch, and where each came from
     std::vector<int> sp_src;
+    std::vector<SpeedPush> vp_run;               // the same for the stretchers, which launch first
+    std::vector<int> vp_src;
     auto run_sinks = [&]() {
+        if (!vp_run.empty()) {
+            speed_launch(vp_run.data(), (int)vp_run.size());
+            for (size_t k = 0; k < vp_run.size(); ++k) { vp[(size_t)vp_src[k]] = vp_run[k]; ps[vp_src[k]].n_own = vp_run[k].n_out; }
+            vp_run.clear(); vp_src.clear();
+            for (size_t k = 0; k < sp_run.size(); ++k) {   // a sink behind a stretcher reads the stretcher's output where it lies
+                const SpeedPush& v = vp[(size_t)sp_src[k]];
+                if (v.id < 0) continue;
+                if (sp_run[k].n_new != v.n_out) throw Error("codec_stream_push_batch: a sink's input length does not match its stretcher's push");
+                sp_run[k].x_dev = v.out_dev;
+            }
+        }
         if (sp_run.empty()) return;
         pcm_sinks_launch(sp_run.data(), (int)sp_run.size());
         for (size_t k = 0; k < sp_run.size(); ++k) { sp[(size_t)sp_src[k]] = sp_run[k]; ps[sp_src[k]].n_own = sp_run[k].n_out; }
         sp_run.clear(); sp_src.clear();
     };
     auto commit_sinks = [&]() {
+        for (int i = 0; i < g_all; ++i) if (vp[(size_t)i].id >= 0) speed_commit(&vp[(size_t)i], 1);
         for (int i = 0; i < g_all; ++i) if (sp[(size_t)i].sink >= 0) pcm_sinks_commit(&sp[(size_t)i], 1);
+    };
+    auto finish_idle = [&]() -> bool {   // streams that finish without new frames: the stretcher's tail, then the sink's
+        bool any = false;
+        for (int i = 0; i < g_all; ++i) {
+            if (ps[i].n != 0 || !ps[i].finish) continue;
+            if (vp[(size_t)i].id >= 0) { vp_run.push_back(vp[(size_t)i]); vp_src.push_back(i); any = true; }
+            if (sp[(size_t)i].sink >= 0) { sp_run.push_back(sp[(size_t)i]); sp_src.push_back(i); any = true; }
+        }
+        return any;
     };
     const int g = (int)live.size();
     if (g == 0) {   // no frames anywhere: only sinks that finish have something to deliver
-        for (int i = 0; i < g_all; ++i) if (sp[(size_t)i].sink >= 0 && sp[(size_t)i].finish) { sp_run.push_back(sp[(size_t)i]); sp_src.push_back(i); }
-        if (sp_run.empty()) return;
+        if (!finish_idle()) return;
         run_sinks();
         sync();
         commit_sinks();
@@ -1094,13 +1147,21 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
             const int64_t first = len_of(d.a0) - up * (d.a0 - d.ctx), n_own = len_of(d.a0 + d.n) - len_of(d.a0);
             if (first < 0 || first + n_own > Tp || (d.ctx + d.n == G.Tw && first + n_own != Tp)) throw Error("codec_stream_push_batch: window arithmetic does not match the decoder length formula");
             q.n_own = n_own;
+            const bool sped = vp[(size_t)live[(size_t)i]].id >= 0;
+            if (sped) {   // through its stretcher, in the group's one launch (run_sinks), from where the samples lie
+                SpeedPush v = vp[(size_t)live[(size_t)i]];
+                if (v.n_new != n_own) throw Error("codec_stream_push_batch: a stretcher's input length does not match the decoder length formula");
+                v.x_dev = pcm_seq + first;
+                vp_run.push_back(v); vp_src.push_back(live[(size_t)i]);
+            }
             if (sp[(size_t)live[(size_t)i]].sink >= 0) {   // through its sink, in the group's one launch (run_sinks), from where the samples lie
                 SinkPush k = sp[(size_t)live[(size_t)i]];
-                if (k.n_new != n_own) throw Error("codec_stream_push_batch: a sink's input length does not match the decoder length formula");
-                k.x_dev = pcm_seq + first;
+                if (!sped && k.n_new != n_own) throw Error("codec_stream_push_batch: a sink's input length does not match the decoder length formula");
+                k.x_dev = pcm_seq + first;   // behind a stretcher: replaced by the stretcher's output in run_sinks
                 sp_run.push_back(k); sp_src.push_back(live[(size_t)i]);
                 return;
             }
+            if (sped) return;
             const int64_t m = std::min(n_own, q.cap);
             if (m > 0 && q.pcm) Q3_HIP_CHECK(hipMemcpyAsync(q.pcm, pcm_seq + first, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, stream));
         };
@@ -1120,10 +1181,9 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
             }
         }
     }
-    // sinks that finish without new frames
-    for (int i = 0; i < g_all; ++i) if (ps[i].n == 0 && sp[(size_t)i].sink >= 0 && sp[(size_t)i].finish) { sp_run.push_back(sp[(size_t)i]); sp_src.push_back(i); }
+    (void)finish_idle();
     run_sinks();
-    if (n_sinks > 0) Q3_HIP_CHECK(hipEventRecord(ev1, stream));   // the push's time includes its sinks
+    if (n_sinks > 0 || n_speed > 0) Q3_HIP_CHECK(hipEventRecord(ev1, stream));   // the push's time includes its sinks
     sync();
     Q3_HIP_CHECK(hipEventElapsedTime(&last_codec_ms, ev0, ev1));
     total_codec_ms += last_codec_ms; total_codec_frames += T;
@@ -1132,7 +1192,7 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
         const StreamPush& q = ps[live[(size_t)i]];
         CodecW::Stream& S = W.streams[(size_t)q.sid];
         S.n_done = d.a0 + d.n; S.kv_rows = d.k0 + d.n; S.h_rows = d.h0 + d.n;
-        S.delivered = S.delivered || q.n_own > 0 || (S.sink >= 0 && sp[(size_t)live[(size_t)i]].n_new > 0);
+        S.delivered = S.delivered || q.n_own > 0 || (S.sink >= 0 && sp[(size_t)live[(size_t)i]].n_new > 0) || (S.speed >= 0 && vp[(size_t)live[(size_t)i]].n_new > 0);
     }
     commit_sinks();
 }
@@ -1164,6 +1224,8 @@ void Engine::codec_stream_push_batch_host(int n_streams, const int32_t* sids, co
         ps[(size_t)i].finish = finish && finish[i];
         if (float_only && sids[i] >= 0 && sids[i] < (int)W.streams.size() && W.streams[(size_t)sids[i]].used && W.streams[(size_t)sids[i]].sink >= 0)
             throw Error("codec_stream_push_batch: stream " + std::to_string(sids[i]) + " has a sink: the float entry serves streams without one");
+        if (float_only && sids[i] >= 0 && sids[i] < (int)W.streams.size() && W.streams[(size_t)sids[i]].used && W.streams[(size_t)sids[i]].speed >= 0)
+            throw Error("codec_stream_push_batch: stream " + std::to_string(sids[i]) + " has a speed: the float entry serves streams without one");
         if (pcm_len) pcm_len[i] = 0;
     }
     if (W.sbatch_codes_n < total || !W.sbatch_codes) {
@@ -1211,11 +1273,12 @@ void Engine::slots_codec_decode_new(int n_slots, const int32_t* slots, float* co
         }
         // the scheduler's sink: a stream that has delivered nothing yet takes it (a primed stream included: its sink starts from silence)
         if (slot_sink_rate > 0 && W.streams[(size_t)sid].sink < 0 && !W.streams[(size_t)sid].delivered) codec_stream_set_sink(sid, slot_sink_rate, slot_sink_format);
+        if (slot_speed > 0 && slot_speed != 1000 && W.streams[(size_t)sid].speed < 0 && !W.streams[(size_t)sid].delivered) codec_stream_set_speed(sid, slot_speed);
         const int a = W.streams[(size_t)sid].n_done;
         StreamPush& q = ps[(size_t)i];
         q.sid = sid; q.n = nf - a; q.codes_dev = codes_d + ((size_t)slot * max_frames_cap + a) * c.n_groups;
         q.pcm = pcm_out ? pcm_out[i] : nullptr; q.cap = cap;
-        q.finish = W.streams[(size_t)sid].sink >= 0 && final_frames && final_frames[i] >= 0 && nf >= final_frames[i];
+        q.finish = (W.streams[(size_t)sid].sink >= 0 || W.streams[(size_t)sid].speed >= 0) && final_frames && final_frames[i] >= 0 && nf >= final_frames[i];
         if (frame_begin) frame_begin[i] = a;
         if (frame_end) frame_end[i] = nf;
         if (pcm_len) pcm_len[i] = 0;

@@ -450,6 +450,29 @@ inline int pcm_sink_tab_stride(int taps) { return taps | 1; }
 inline bool pcm_sink_tab_in_lds(int L, int taps) { return taps > 0 && (int64_t)L * pcm_sink_tab_stride(taps) <= kPcmSinkLdsTab; }
 void launch_pcm_sinks(const PcmSinkDesc* tab /* device, [n] */, int n, int max_work /* largest n_out + keep */, bool any_tab_lds, hipStream_t s);
 
+// ---- speaking rate (q3_speed.cpp): WSOLA time stretch of 24 kHz float PCM, with carried state ----
+// One stretcher of one push.  Its samples are, as for a sink, the carry ([carry_abs0, n_before)) followed by the push's n_new samples at
+// x_new; x[k] = 0 for k < 0 and k >= n_total.  The launch's workgroup walks frames frame0 .. frame0 + n_frames - 1 in order (frame m:
+// a_m = floor(m Hs S / 1000), template t[i] = x[p_{m-1} + Hs + i], c(delta) = (s0 + s1) + (s2 + s3) over the 2 D + 1 lags, s_q the fp32
+// sum of t[i] x[a_m + delta + i] over i = q mod 4 ascending; the largest c wins, the smallest delta among equals; p_m = a_m + delta_m;
+// y[m Hs + i] = w[Hs + i] t[i] + w[i] x[p_m + i]) and writes out[0 .. n_out) (n_out <= n_frames Hs: the last block of a finished
+// stretcher is cut), offs[f] = delta of frame frame0 + f, the next carry x[keep_abs0 .. keep_abs0 + keep) into carry_out, and
+// state_out = { p of the last frame, frame0 + n_frames }.  p_{frame0 - 1} is state_in[0] (frame0 == 0: -Hs).
+struct SpeedDesc {
+    const float* carry_in = nullptr; float* carry_out = nullptr;
+    const float* x_new = nullptr;       // n_new samples (never null: a push without samples points at the carry)
+    const float* win = nullptr;         // the window, kSpeedN floats on the device
+    float* out = nullptr;               // n_out samples
+    int32_t* offs = nullptr;            // n_frames offsets
+    const int64_t* state_in = nullptr; int64_t* state_out = nullptr;   // { p, frames done }
+    int64_t carry_abs0 = 0;             // absolute index of carry_in[0]
+    int64_t n_before = 0, n_total = 0;  // samples received before / with this push
+    int64_t frame0 = 0;                 // the first frame of this push
+    int64_t keep_abs0 = 0;              // absolute index of carry_out[0]
+    int32_t n_new = 0, n_frames = 0, n_out = 0, keep = 0, speed = 1000;
+};
+void launch_wsola(const SpeedDesc* tab /* device, [n] */, int n, hipStream_t s);
+
 
 // ---- speaker encoder + GPU audio front end of the clone path (q3_speaker_kernels.hip) ----
 // One reference clip of a batch.  Activations of a batch lie clip after clip along time ([sum T][C]); every kernel that looks across

@@ -440,6 +440,7 @@ Engine::~Engine() {
     if (rag_x_d) (void)hipFree(rag_x_d);
     if (seg_tab_d) (void)hipFree(seg_tab_d);
     pcm_sink_free();
+    speed_free();
     codec_free();
     speaker_free();
     encoder_free();

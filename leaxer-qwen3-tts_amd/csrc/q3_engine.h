@@ -212,6 +212,42 @@ public:
     // the scheduler's sink (q3tts_engine_set_sink): slots' implicit streams begin with it.  rate 0: none
     int slot_sink_rate = 0, slot_sink_format = 0;
 
+    // ---- speaking rate (q3_speed.cpp): WSOLA time stretch of 24 kHz float on the device, carried state ----
+    static constexpr int kMaxStretchers = 4096;                      // open at the same time (vocoder streams' included)
+    // mem: the stretcher's own allocation, [2][kSpeedCarry] floats of carry followed by [2][2] int64 of state { p, frames }; a push
+    // reads half `cur` and writes the other, the host flips them when the push has completed.  carry_abs0: absolute index of the
+    // first carried sample; frames: frames completed (the host rule's count, which the device's state repeats)
+    struct Stretcher { bool used = false, finished = false; int speed = 1000, cur = 0; int64_t n_in = 0, n_out = 0, frames = 0, carry_abs0 = 0; float* mem = nullptr; };
+    std::vector<Stretcher> stretchers;
+    float* speed_win_d = nullptr;                                    // the window: a host table, built once and uploaded
+    int speed_begin(int speed);
+    void speed_end(int id);
+    void speed_free();
+    const Stretcher& speed_get(int id) const;
+    int64_t speed_push_len(int id, int64_t n_new, bool finish) const;      // host-only: samples that push would deliver; throws when it would be refused
+    int64_t speed_push_frames(int id, int64_t n_new, bool finish) const;   // frames it would complete
+    // x_dev: n_new samples on the device; out_host (NULL ok): min(n_out, cap) floats land there; offs_host (NULL ok): min(n_frames,
+    // offs_cap) offsets.  n_out, n_frames, out_dev (the push's samples on the device, valid until the call's next reserve), desc: set
+    // by speed_launch
+    struct SpeedPush { int id = -1; const float* x_dev = nullptr; int64_t n_new = 0; bool finish = false; float* out_host = nullptr; int64_t cap = 0;
+                       int32_t* offs_host = nullptr; int64_t offs_cap = 0; int64_t n_out = 0, n_frames = 0; const float* out_dev = nullptr; int desc = -1; };
+    void speed_reserve(int n_total, size_t out_floats_total, size_t frames_total);   // once per call, before anything is enqueued
+    void speed_launch(SpeedPush* ps, int n);                         // one launch + the device -> host copies; no stretcher moves
+    void speed_commit(const SpeedPush* ps, int n);                   // after the sync: counters advance, carries flip
+    static size_t speed_out_floats(int64_t n_out) { return ((size_t)n_out + 63) & ~(size_t)63; }
+    void speed_push_batch_host(int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in, const uint8_t* finish,
+                               float* const* out, int64_t cap, int64_t* out_len, int32_t* const* offsets_out, int64_t* n_offsets);
+    SpeedDesc* speed_desc_d = nullptr; size_t speed_desc_cap = 0, speed_desc_used = 0;
+    std::vector<SpeedDesc> speed_desc_h;
+    float* speed_out_d = nullptr; size_t speed_out_cap = 0, speed_out_used = 0;      // packed outputs of a call (grow-only workspace)
+    int32_t* speed_offs_d = nullptr; size_t speed_offs_cap = 0, speed_offs_used = 0; // the frames' offsets of a call
+    float* speed_in_d = nullptr; size_t speed_in_floats = 0;                         // the standalone entry's staged input
+    // vocoder streams: a stream with a speed delivers its audio time-stretched (codec_stream_push_batch), before its sink if it has
+    // one.  Refused once the stream has delivered a sample.  1000: no stage.
+    void codec_stream_set_speed(int sid, int speed);
+    // the scheduler's speed (q3tts_engine_set_speed): slots' implicit streams begin with it.  0 or 1000: none
+    int slot_speed = 0;
+
     // ---- batch-first session ops on DEVICE pointers (include/q3tts.h "_dev" entry points): row b <-> slot b ----
     // caller stream: the engine's stream first waits for what the caller has enqueued, the caller's stream then waits for the call's work
     void stream_join(hipStream_t caller);

@@ -1,6 +1,8 @@
 // tts_engine.cpp — leaxer_qwen::TTSEngine over the C-ABI (include/q3tts.h).
 #include "tts_engine.h"
 
+#include <cmath>
+
 #include <algorithm>
 #include <climits>
 #include <cctype>
@@ -158,6 +160,7 @@ std::vector<float> TTSEngine::synthesize_tokens_clone(const std::vector<int64_t>
         return {};
     }
     pcm.resize((size_t)std::min<int64_t>(len, cap));
+    (void)apply_speed(pcm);
     return pcm;
 }
 
@@ -203,6 +206,7 @@ std::vector<float> TTSEngine::synthesize_tokens_instruct(const std::vector<int64
         return {};
     }
     pcm.resize((size_t)std::min<int64_t>(len, cap));
+    (void)apply_speed(pcm);
     return pcm;
 }
 
@@ -236,6 +240,7 @@ std::vector<float> TTSEngine::synthesize_tokens_continue(const std::vector<int64
     }
     if (all_codes) all_codes->assign(codes.begin(), codes.begin() + (size_t)frames * G);
     pcm.resize((size_t)std::min<int64_t>(len, cap));
+    (void)apply_speed(pcm);
     return pcm;
 }
 
@@ -334,6 +339,52 @@ bool TTSEngine::convert_output(const std::vector<float>& pcm24, std::vector<floa
     } while (done < pcm24.size());
     (void)q3tts_pcm_sink_end(h_, id);
     return true;
+}
+
+bool TTSEngine::set_speed(float speed) {
+    if (!ready_) return false;
+    const long S = std::lround(1000.0 * (double)speed);
+    if (!(speed == speed) || S < 500 || S > 2000) {
+        error_msg_ = "speed " + std::to_string(speed) + " is outside 0.5 .. 2.0";
+        std::cerr << "[TTSEngine] Speed: " << error_msg_ << std::endl;
+        return false;
+    }
+    if (q3tts_engine_set_speed(h_, (int32_t)S) != 0) {
+        error_msg_ = q3tts_last_error(h_);
+        std::cerr << "[TTSEngine] Speed: " << error_msg_ << std::endl;
+        return false;
+    }
+    speed_ = (int)S;
+    return true;
+}
+
+bool TTSEngine::stretch_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out) {
+    const int64_t n_in = (int64_t)n;
+    const uint8_t fin = finish ? 1 : 0;
+    const int64_t before = q3tts_speed_emitted(speed_, (int64_t)received_before, 0), after = q3tts_speed_emitted(speed_, (int64_t)(received_before + n), fin);
+    if (before < 0 || after < before) return false;
+    const size_t have = out.size();
+    out.resize(have + (size_t)(after - before));
+    float* dst = out.data() + have;
+    int64_t len = 0;
+    return q3tts_speed_push_batch_host(h_, 1, &id, &in, &n_in, &fin, &dst, after - before, &len, nullptr, nullptr) == 0 && len == after - before;
+}
+
+bool TTSEngine::apply_speed(std::vector<float>& pcm24) {
+    if (!ready_) return false;
+    if (speed_ == 1000 || pcm24.empty()) return true;
+    int id = -1;
+    std::vector<float> out;
+    bool ok = q3tts_speed_begin(h_, speed_, &id) == 0;
+    const size_t step = 1440000;   // the most one push takes
+    for (size_t done = 0; ok && done < pcm24.size(); done += step) {
+        const size_t m = std::min(step, pcm24.size() - done);
+        ok = stretch_push(id, pcm24.data() + done, m, done + m == pcm24.size(), done, out);
+    }
+    if (!ok) std::cerr << "[TTSEngine] Speed error: " << q3tts_last_error(h_) << std::endl;
+    if (id >= 0) (void)q3tts_speed_end(h_, id);
+    if (ok) pcm24.swap(out); else pcm24.clear();
+    return ok;
 }
 
 bool TTSEngine::has_audio_encoder() const { return h_ && q3tts_has_audio_encoder(h_) != 0; }
@@ -488,7 +539,7 @@ std::vector<std::vector<float>> TTSEngine::synthesize_tokens_batch(const std::ve
         for (auto& v : out) v.clear();
         return out;
     }
-    for (size_t i = 0; i < out.size(); ++i) out[i].resize((size_t)std::min<int64_t>(lens[i], cap));
+    for (size_t i = 0; i < out.size(); ++i) { out[i].resize((size_t)std::min<int64_t>(lens[i], cap)); (void)apply_speed(out[i]); }
     return out;
 }
 
@@ -519,7 +570,7 @@ std::vector<std::vector<float>> TTSEngine::synthesize_tokens_batch_instruct_shar
                                                   ptrs.data(), cap, lens.data(), frames.data(), nullptr, 0, nullptr, nullptr, pids.data());
     if (rc != 0) { (void)fail(); (void)q3tts_prefix_release(h_, pid); return out; }
     (void)q3tts_prefix_release(h_, pid);
-    for (size_t i = 0; i < out.size(); ++i) out[i].resize((size_t)std::min<int64_t>(lens[i], cap));
+    for (size_t i = 0; i < out.size(); ++i) { out[i].resize((size_t)std::min<int64_t>(lens[i], cap)); (void)apply_speed(out[i]); }
     return out;
 }
 
@@ -538,20 +589,38 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
     if (q3tts_slot_begin(h_, 0, prompt.data(), S, trailing.data(), nt, &sp, seed_, 0, 0) != 0) return fail();
     std::vector<float> pcm((size_t)chunk_frames * 1920 + 1920);
     int done = 0;
+    // with a speed the chunks pass a stretcher of this call's own; its tail leaves in one more chunk at the end
+    int stretcher = -1;
+    size_t received = 0;
+    std::vector<float> fast;
+    if (speed_ != 1000 && q3tts_speed_begin(h_, speed_, &stretcher) != 0) return fail();
+    auto fail_s = [&]() { const int rc = fail(); if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher); return rc; };
     for (;;) {
         const int want = std::min(chunk_frames, params.max_new_tokens - done);
         const int active = want > 0 ? q3tts_decode_steps(h_, want) : 0;
-        if (active < 0) return fail();
+        if (active < 0) return fail_s();
         int nf = 0, fin = 0;
-        if (q3tts_slot_status(h_, 0, &nf, &fin) != 0) return fail();
+        if (q3tts_slot_status(h_, 0, &nf, &fin) != 0) return fail_s();
         if (nf > done) {
             int64_t n = 0;
             const int ctx = left_context_frames < 0 ? nf : left_context_frames;
-            if (q3tts_slot_codec_decode_range_host(h_, 0, done, nf, ctx, pcm.data(), (int64_t)pcm.size(), &n) != 0) return fail();
-            on_audio(pcm.data(), (size_t)std::min<int64_t>(n, (int64_t)pcm.size()));
+            if (q3tts_slot_codec_decode_range_host(h_, 0, done, nf, ctx, pcm.data(), (int64_t)pcm.size(), &n) != 0) return fail_s();
+            const size_t got = (size_t)std::min<int64_t>(n, (int64_t)pcm.size());
+            if (stretcher >= 0) {
+                fast.clear();
+                if (!stretch_push(stretcher, pcm.data(), got, false, received, fast)) return fail_s();
+                received += got;
+                if (!fast.empty()) on_audio(fast.data(), fast.size());
+            } else on_audio(pcm.data(), got);
             done = nf;
         }
         if (active == 0 || want <= 0) break;
+    }
+    if (stretcher >= 0) {
+        fast.clear();
+        if (!stretch_push(stretcher, pcm.data(), 0, true, received, fast)) return fail_s();
+        if (!fast.empty()) on_audio(fast.data(), fast.size());
+        (void)q3tts_speed_end(h_, stretcher);
     }
     (void)q3tts_slot_release(h_, 0);
     return done;

@@ -175,6 +175,15 @@ public:
     int output_rate() const { return out_rate_; }
     bool output_pcm16() const { return out_pcm16_; }
     bool convert_output(const std::vector<float>& pcm24, std::vector<float>* f32, std::vector<int16_t>* s16);
+    // Speaking rate (include/q3tts.h: q3tts_engine_set_speed, q3tts_speed_*; the reference has no speed control).  speed 1.25 makes
+    // every synthesize* method's audio 25 % faster at the same pitch (WSOLA on the GPU); the engine works in permille,
+    // S = round(1000 * speed), 500 .. 2000, and 1.0 is no stage at all.  The scheduler's streaming methods stretch inside their
+    // streams (ahead of the output format's resampler; the finishing chunk carries the tail), synthesize_tokens_streaming through a
+    // stretcher of its own behind the chunks, the one-shot methods run the stage over the whole clip (apply_speed).  false (and
+    // get_error(), naming the range) for a speed the engine refuses.
+    bool set_speed(float speed);
+    int speed_permille() const { return speed_; }
+    bool apply_speed(std::vector<float>& pcm24);   // the whole clip through the stage, in place; speed 1.0 leaves it as it is
     bool has_audio_encoder() const;
     int n_groups() const { return n_groups_; }
     bool has_speaker_encoder() const; // true when the weight file carries the spk.* tensors (reference: speaker_encoder.onnx present)
@@ -197,6 +206,9 @@ private:
     int out_rate_ = config::SAMPLE_RATE;
     bool out_pcm16_ = false;
     std::function<int(int, const void*, int64_t, int)> sink_fn_;   // the running streaming call's delivery, while an output format is set
+    int speed_ = 1000;
+    // one push of a stretcher of this engine: out receives the push's samples (appended)
+    bool stretch_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);
     bool sink_on() const { return out_rate_ != config::SAMPLE_RATE || out_pcm16_; }
 };
 

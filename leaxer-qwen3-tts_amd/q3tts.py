@@ -118,6 +118,8 @@ EXPORTS = [
     "q3tts_codec_stream_prime_batch_host", "q3tts_slots_codec_prime", "q3tts_codec_stream_info", "q3tts_synthesize_continue_stream_host",
     "q3tts_sink_plan", "q3tts_sink_last_error", "q3tts_sink_emitted", "q3tts_pcm_sink_begin", "q3tts_pcm_sink_push_batch_host", "q3tts_pcm_sink_end",
     "q3tts_codec_stream_set_sink", "q3tts_codec_stream_push_batch_any_host", "q3tts_engine_set_sink",
+    "q3tts_speed_emitted", "q3tts_speed_last_error", "q3tts_speed_window", "q3tts_speed_begin", "q3tts_speed_push_batch_host", "q3tts_speed_end",
+    "q3tts_codec_stream_set_speed", "q3tts_engine_set_speed",
 ]
 
 # q3tts_audio_cb: int (*)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished)
@@ -494,10 +496,11 @@ class Engine:
         self._ck(self.L.q3tts_codec_decode_chunked_host(self.h, _p(c), c.shape[0], chunk_frames, left_context, _p(pcm), n, C.byref(out_len)))
         return pcm[: out_len.value]
 
-    def codec_stream_begin(self, max_frames, sample_rate=24000, dtype="float32"):
+    def codec_stream_begin(self, max_frames, sample_rate=24000, dtype="float32", speed=None):
         """streaming vocoder with carried state: -> stream id (q3tts_codec_stream_begin).  sample_rate / dtype other than 24000 /
         float32 give the stream a sink (q3tts_codec_stream_set_sink): codec_stream_push_batch then delivers at that rate, as float32
-        or int16."""
+        or int16.  speed (permille, 500 .. 2000; None or 1000: none) gives it a stretcher ahead of the sink
+        (q3tts_codec_stream_set_speed)."""
         fmt = _pcm_format(dtype)
         sid = C.c_int(-1)
         self.L.q3tts_codec_stream_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -509,7 +512,69 @@ class Engine:
             except Exception:
                 self.codec_stream_end(sid.value)
                 raise
+        if speed is not None:
+            try:
+                self.codec_stream_set_speed(sid.value, speed)
+            except Exception:
+                self.codec_stream_end(sid.value)
+                raise
         return sid.value
+
+    def codec_stream_set_speed(self, sid, speed):
+        """q3tts_codec_stream_set_speed: speed in permille; refused once the stream has delivered a sample; 1000 takes the stage away"""
+        self.L.q3tts_codec_stream_set_speed.argtypes = [C.c_void_p, C.c_int, C.c_int32]
+        self._ck(self.L.q3tts_codec_stream_set_speed(self.h, int(sid), int(speed)))
+        d = self.__dict__.setdefault("_codec_stream_speed", {})
+        if int(speed) == 1000:
+            d.pop(int(sid), None)
+        else:
+            d[int(sid)] = int(speed)
+
+    # ---- the speaking-rate stage on its own (include/q3tts.h "speaking rate") ----
+    def speed_begin(self, speed):
+        """a stretcher that takes 24 kHz float32 and delivers it speed / 1000 times as fast (speed: permille, 500 .. 2000, not 1000)
+        -> stretcher id"""
+        sid = C.c_int(-1)
+        self.L.q3tts_speed_begin.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
+        self._ck(self.L.q3tts_speed_begin(self.h, int(speed), C.byref(sid)))
+        self.__dict__.setdefault("_speed_of", {})[sid.value] = int(speed)
+        return sid.value
+
+    def speed_push_batch(self, ids, pcm_list, finish=None, want_offsets=False):
+        """more 24 kHz samples for many stretchers in one launch (q3tts_speed_push_batch_host); finish: one flag per stretcher (its
+        tail is flushed with this push) -> one float32 array per stretcher; want_offsets: (arrays, per stretcher the int32 offsets
+        of the frames the push completed)"""
+        n = len(ids)
+        if n == 0:
+            return ([], []) if want_offsets else []
+        if len(pcm_list) != n or (finish is not None and len(finish) != n):
+            raise ValueError("speed_push_batch: one sample array (and one finish flag) per stretcher")
+        xs = [np.ascontiguousarray(a, np.float32).reshape(-1) for a in pcm_list]
+        fin = np.zeros(n, np.uint8) if finish is None else np.ascontiguousarray([1 if f else 0 for f in finish], np.uint8)
+        lens = np.array([x.size for x in xs], np.int64)
+        cap = (int(lens.max()) + 1320) * 2 + 720     # the slowest speed doubles the push plus what the stretcher held back
+        outs = [np.empty(cap, np.float32) for _ in range(n)]
+        offs = [np.empty(cap // 360 + 1, np.int32) for _ in range(n)]
+        xptr = (C.c_void_p * n)(*[x.ctypes.data if x.size else None for x in xs])
+        optr = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        fptr = (C.c_void_p * n)(*[o.ctypes.data for o in offs])
+        out_len, n_offs = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        self.L.q3tts_speed_push_batch_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p]
+        self._ck(self.L.q3tts_speed_push_batch_host(self.h, n, _p(np.ascontiguousarray(ids, np.int32)), C.cast(xptr, C.c_void_p), _p(lens), _p(fin),
+                                                    C.cast(optr, C.c_void_p), cap, _p(out_len), C.cast(fptr, C.c_void_p) if want_offsets else None, _p(n_offs)))
+        res = [outs[i][: out_len[i]] for i in range(n)]
+        return (res, [offs[i][: n_offs[i]] for i in range(n)]) if want_offsets else res
+
+    def speed_end(self, stretcher_id):
+        self.L.q3tts_speed_end.argtypes = [C.c_void_p, C.c_int]
+        self._ck(self.L.q3tts_speed_end(self.h, int(stretcher_id)))
+        self.__dict__.setdefault("_speed_of", {}).pop(int(stretcher_id), None)
+
+    def set_speed(self, speed=None):
+        """q3tts_engine_set_speed: the streaming entries deliver time-stretched (speed: permille); None or 1000 takes the stage away"""
+        self.L.q3tts_engine_set_speed.argtypes = [C.c_void_p, C.c_int32]
+        self._ck(self.L.q3tts_engine_set_speed(self.h, 1000 if speed is None else int(speed)))
 
     def codec_stream_set_sink(self, sid, sample_rate, dtype="float32"):
         """q3tts_codec_stream_set_sink: refused once the stream has delivered a sample; 24000 / float32 takes the sink away"""
@@ -609,10 +674,13 @@ class Engine:
         ids = np.ascontiguousarray(sids, np.int32)
         offs = np.cumsum([0] + [c_.shape[0] for c_ in cs]).astype(np.int32)
         fmts = self.__dict__.setdefault("_codec_stream_fmt", {})
-        if finish is None and not any(int(i) in fmts for i in ids):
+        spds = self.__dict__.setdefault("_codec_stream_speed", {})
+        if finish is None and not any(int(i) in fmts or int(i) in spds for i in ids):
             return self._push_batch(ids, cs, offs)
         flat = np.ascontiguousarray(np.concatenate(cs)) if sum(c_.shape[0] for c_ in cs) else np.zeros((1, self.cfg.n_groups), np.int64)
         n24 = self.codec_decode_len(max(max(c_.shape[0] for c_ in cs), 1)) + 4096
+        if any(int(i) in spds for i in ids):
+            n24 = (n24 + 1320) * 2 + 720   # behind a stretcher: the slowest speed doubles the push plus what it held back
         cap = max((n24 + 200) * max(fmts.get(int(i), (24000, PCM_F32))[0], 24000) // 24000 + 8 for i in ids)
         pcm = [np.empty(cap, np.int16 if fmts.get(int(i), (24000, PCM_F32))[1] == PCM_S16 else np.float32) for i in ids]
         ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in pcm])
@@ -685,6 +753,7 @@ class Engine:
         self.L.q3tts_codec_stream_end.argtypes = [C.c_void_p, C.c_int]
         self._ck(self.L.q3tts_codec_stream_end(self.h, sid))
         self.__dict__.setdefault("_codec_stream_fmt", {}).pop(int(sid), None)
+        self.__dict__.setdefault("_codec_stream_speed", {}).pop(int(sid), None)
 
     def slot_codec_decode_range(self, slot, frame_begin, frame_end, left_context):
         """samples owned by frames [frame_begin, frame_end) of a slot (streaming while it generates)"""
@@ -1408,7 +1477,7 @@ class Engine:
         self._ck(rc)
         return [pcm[i][: pcm_len[i]] for i in range(n)], [codes[i, : nfr[i]] for i in range(n)], nfr
 
-    def _sink_job(self, sample_rate, dtype, on_audio, n, run):
+    def _sink_job(self, sample_rate, dtype, on_audio, n, run, speed=None):
         """a streaming job through a sink of its own: run(None-pcm_out) with the sink set, the sink taken away afterwards; the chunks
         on_audio saw are also returned joined per utterance"""
         fmt = _pcm_format("float32" if dtype is None else dtype)
@@ -1417,12 +1486,18 @@ class Engine:
         def tee(utt, fb, fe, a, fin):
             got[utt].append(a)
             return on_audio(utt, fb, fe, a, fin) if on_audio is not None else 0
-        self.set_sink(24000 if sample_rate is None else sample_rate, "int16" if fmt == PCM_S16 else "float32", tee)
+        self.set_speed(speed)   # refuses a bad speed before the sink is set
+        try:
+            self.set_sink(24000 if sample_rate is None else sample_rate, "int16" if fmt == PCM_S16 else "float32", tee)
+        except BaseException:
+            self.set_speed(None)
+            raise
         try:
             rc = run()
         finally:
             raised = self._sink_raised
             self.set_sink(None)
+            self.set_speed(None)
         if raised:
             raise raised[0]
         self._ck(rc)
@@ -1430,7 +1505,7 @@ class Engine:
         return [np.concatenate(g) if g else np.zeros(0, npdt) for g in got]
 
     def synthesize_stream(self, token_lists, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
-                          max_new_per_utt=None, instructs=None, sample_rate=None, dtype=None):
+                          max_new_per_utt=None, instructs=None, sample_rate=None, dtype=None, speed=None):
         """synthesize_batch that delivers audio while it generates (q3tts_synthesize_stream_host): every chunk_frames steps
         on_audio(utt, frame_begin, frame_end, pcm, finished) is called once per utterance with new audio (pcm: a copy); a truthy return
         cancels the job (RuntimeError "cancelled by callback").  Returns what synthesize_batch returns."""
@@ -1470,7 +1545,9 @@ class Engine:
         self.L.q3tts_synthesize_stream_host.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.POINTER(Sampling), vp, C.c_uint64, C.c_int, vp, C.c_int64, vp, vp, vp,
                                                         C.c_int, AUDIO_CB, vp]
         ins_flat, ins_offs = self._instruct_args(instructs, n)
-        if sample_rate is not None or dtype is not None:   # through a sink (q3tts_engine_set_sink): sample_rate / dtype are the chunks' and the result's
+        if speed is not None and int(speed) == 1000:
+            speed = None   # no stage
+        if sample_rate is not None or dtype is not None or speed is not None:   # through a sink (q3tts_engine_set_sink): sample_rate / dtype are the chunks' and the result's; speed (permille): time-stretched first (q3tts_engine_set_speed)
             def run():
                 if ins_flat is not None:
                     return self.L.q3tts_synthesize_instruct_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
@@ -1479,7 +1556,7 @@ class Engine:
                 return self.L.q3tts_synthesize_stream_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
                                                            seed, int(ignore_eos), None, 0, _p(pcm_len), _p(nfr),
                                                            _p(codes) if want_codes else None, int(chunk_frames), cb, None)
-            outs = self._sink_job(sample_rate, dtype, on_audio, n, run)
+            outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed)
             return outs, ([codes[i, : nfr[i]] for i in range(n)] if want_codes else None), nfr
         if ins_flat is not None:
             rc = self.L.q3tts_synthesize_instruct_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
@@ -1497,7 +1574,7 @@ class Engine:
         return outs, cl, nfr
 
     def synthesize_live(self, n_utt, text_source, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
-                        max_new_per_utt=None, sample_rate=None, dtype=None):
+                        max_new_per_utt=None, sample_rate=None, dtype=None, speed=None):
         """synthesize_stream for texts that arrive while their audio is generated (q3tts_synthesize_live_host): text_source(utt) ->
         (ids, closed) is polled between decode chunks for every utterance whose text is open — new ids (possibly none) and whether the
         text has ended; None cancels the job (RuntimeError "cancelled by callback").  An utterance's ids are those synthesize_stream
@@ -1554,13 +1631,15 @@ class Engine:
                 raised.append(ex)
                 return 1
         cb, tcb = AUDIO_CB(tramp), TEXT_CB(ttramp)
-        if sample_rate is not None or dtype is not None:   # through a sink, as synthesize_stream
+        if speed is not None and int(speed) == 1000:
+            speed = None
+        if sample_rate is not None or dtype is not None or speed is not None:   # through a sink and / or a stretcher, as synthesize_stream
             def run():
                 return self.L.q3tts_synthesize_live_host(self.h, n, tcb, None, lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
                                                          seed, int(ignore_eos), None, 0, _p(pcm_len), _p(nfr),
                                                          _p(codes) if want_codes else None, int(chunk_frames), cb, None)
             try:
-                outs = self._sink_job(sample_rate, dtype, on_audio, n, run)
+                outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed)
             except BaseException:
                 if raised:
                     raise raised[0]
@@ -1748,6 +1827,31 @@ def sink_emitted(sample_rate, n_received, finished=False):
     if n < 0:
         raise ValueError(Lb.q3tts_sink_last_error().decode())
     return n
+
+
+def speed_emitted(speed, n_received, finished=False):
+    """q3tts_speed_emitted: the samples a stretcher at speed (permille) has delivered in all after n_received samples.  Host-only;
+    ValueError naming the value when it is refused."""
+    Lb = lib()
+    Lb.q3tts_speed_emitted.argtypes = [C.c_int32, C.c_int64, C.c_int]
+    Lb.q3tts_speed_emitted.restype = C.c_int64
+    Lb.q3tts_speed_last_error.restype = C.c_char_p
+    if not -2 ** 31 <= int(speed) < 2 ** 31 or not -2 ** 63 <= int(n_received) < 2 ** 63:
+        raise ValueError("speed_emitted: %d / %d does not fit the C types" % (int(speed), int(n_received)))
+    n = int(Lb.q3tts_speed_emitted(int(speed), int(n_received), 1 if finished else 0))
+    if n < 0:
+        raise ValueError(Lb.q3tts_speed_last_error().decode())
+    return n
+
+
+def speed_window():
+    """q3tts_speed_window: the 720-entry float32 window the device uses.  Host-only."""
+    Lb = lib()
+    Lb.q3tts_speed_window.argtypes = [C.c_void_p, C.c_int64]
+    w = np.zeros(720, np.float32)
+    if Lb.q3tts_speed_window(_p(w), w.size) != 0:
+        raise ValueError("speed_window failed")
+    return w
 
 
 def _pcm_format(dtype):
