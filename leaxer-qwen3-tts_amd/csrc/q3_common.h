@@ -70,6 +70,8 @@ struct GemvArgs {
     int M = 0, N = 0, K = 0;
     int epi = EPI_STORE;
     bool nt = false;              // non-temporal weight loads (streamed-once weights)
+    bool xlds = true;             // fast path, rows as they lie in memory: each wave loads a quarter of the activation rows (and of gamma), the workgroup
+                                  // shares them through LDS; false: every wave loads them whole (Q3TTS_GEMV_XLDS=0, the A/B knob).  Same bits.
     // optional: x rows are the combination of split-T attention partials (o_proj prologue)
     const float* po = nullptr;    // [(row*heads + h)*S + s][d] un-normalised sum(p*v)
     const float* pm = nullptr;    // [(row*heads + h)*S + s] running max

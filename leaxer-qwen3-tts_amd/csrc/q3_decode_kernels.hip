@@ -21,8 +21,8 @@ namespace q3 {
 
 // -DQ3_SAMPLE_PROF: phase timestamps (100 MHz wall clock) of the last workgroup-0 run of an instrumented kernel; tools/ only
 #ifdef Q3_SAMPLE_PROF
-__device__ long long g_kernel_prof[32];
-void sample_prof_read(long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_kernel_prof), sizeof(long long) * 32); }
+__device__ long long g_kernel_prof[40];
+void sample_prof_read(long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_kernel_prof), sizeof(long long) * 40); }
 #define KP_MARK(k) do { if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) g_kernel_prof[k] = wall_clock64(); } while (0)
 #else
 #define KP_MARK(k) do { } while (0)
@@ -245,7 +245,8 @@ static void gemv_r(const GemvArgs& a, hipStream_t s) {
 // registers (its RMSNorm statistics come from those same registers), so the kernel is one memory
 // latency deep.  COMB: the activation rows are the combination of split-T attention partials.  PSUM (gate/up after a kv-head-split
 // o_proj): the activation rows are x + the 8 o_proj partial rows, summed in a fixed order; the workgroup shares the sum through LDS
-// and stores its slice of it to a.xmid, the down projection's residual operand.
+// and stores its slice of it to a.xmid, the down projection's residual operand.  XLDS (the other launches): the four waves load a quarter
+// of the activation rows and of gamma each, ahead of the weights, and share them through LDS; same values in the same registers.
 // ================================================================================================
 static __device__ __forceinline__ uint4 ldw_rt(const bf16_t* p, bool nt) {
     u32x4 v;
@@ -257,7 +258,7 @@ static __device__ __forceinline__ uint4 ldw_rt(const bf16_t* p, bool nt) {
 // The leading scalar parameters repeat the fields the first loads need: the file is built with -amdgpu-kernarg-preload-count=16, so the
 // command processor hands them to the wave in SGPRs at launch instead of the wave fetching its kernarg segment first (~0.35 us per
 // launch on a chain of dependent GEMVs; a by-value struct is not preloadable).
-template <int MT, int NCH, int RW, int EPI, bool NORM, bool COMB, bool PSUM = false>
+template <int MT, int NCH, int RW, int EPI, bool NORM, bool COMB, bool PSUM = false, bool XLDS = false>
 __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* pW2, const float* px, const float* pgamma, const float* pepi,
                                                 int pN, int pM, int pldx, int pldepi, int pnt, GemvArgs a) {
     constexpr int K = NCH * 512;
@@ -265,10 +266,29 @@ __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* p
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // provably wave-uniform: row addresses stay scalar
     const int n0 = (blockIdx.x * 4 + wave) * RW;
     const int N = pN, M = pM;
-    __shared__ float xs[(COMB || PSUM) ? MT * K : 1];
+    __shared__ __attribute__((aligned(16))) float xs[(COMB || PSUM || XLDS) ? MT * K : 1];
+    __shared__ __attribute__((aligned(16))) float gs[(XLDS && NORM) ? K : 1];
+    static_assert(!XLDS || (NCH % 2 == 0 && !COMB && !PSUM), "XLDS: plain path, whole 16-byte loads per quarter row");
+    // XLDS: wave w loads only quarter w of every activation row and of gamma, 16 bytes per lane (NCH / 2 instructions per row where the
+    // whole row takes 2 NCH in each of the four waves), and the workgroup shares the quarters through LDS
+    constexpr int NQ = XLDS ? NCH / 2 : 1;
+    f32x4 xq[MT][NQ], gq[NQ];
+    auto load_quarters = [&]() {
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            const int k = wave * (K / 4) + i * 256 + lane * 4;
+#pragma unroll
+            for (int m = 0; m < MT; ++m) xq[m][i] = *reinterpret_cast<const f32x4*>(px + (size_t)(m < M ? m : 0) * pldx + k);
+            if (NORM) gq[i] = *reinterpret_cast<const f32x4*>(pgamma + k);
+        }
+    };
 
     KP_MARK(30); KP_MARK(31);   // back to back: the first one absorbs the kernarg fetch, their distance is the cost of a mark
     KP_MARK(8);
+    // The quarters lead the weights: so few instructions delay them by next to nothing, vmcnt counts in order, so the wait in front of
+    // the LDS round below leaves the weights in flight, and the round and the RMSNorm statistics run under the weights' latency.  Behind
+    // the weights the same round sits on the critical path and the step is slower than without it (profiles/gemv_xlds_ab.txt).
+    if (XLDS) { load_quarters(); __builtin_amdgcn_sched_barrier(0); }
     // 1. weights: everything this wave will ever read, in flight at once
     uint4 w[RW][NCH], w2[RW][NCH];
 #pragma unroll
@@ -399,7 +419,7 @@ __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* p
                 xv[m][c][0] = x0.x; xv[m][c][1] = x0.y; xv[m][c][2] = x0.z; xv[m][c][3] = x0.w;
                 xv[m][c][4] = x1.x; xv[m][c][5] = x1.y; xv[m][c][6] = x1.z; xv[m][c][7] = x1.w;
             }
-    } else {
+    } else if (!XLDS) {
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -411,9 +431,39 @@ __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* p
                 xv[m][c][4] = x1.x; xv[m][c][5] = x1.y; xv[m][c][6] = x1.z; xv[m][c][7] = x1.w;
             }
     }
-    if (NORM && !PSUM) load_gamma();
+    if (NORM && !PSUM && !XLDS) load_gamma();
     KP_MARK(9);
     __builtin_amdgcn_sched_barrier(0); // all loads of the kernel are in flight past this point
+    if (XLDS) {
+        // The four waves' quarters make the rows in LDS; every wave then takes its c * 512 + lane * 8 registers from there.  The 16-byte
+        // unit q = k / 4 of a row sits at (q & ~127) | (q & 1) << 6 | (q & 127) >> 1: a chunk's even units, then its odd ones, so both
+        // reads of a chunk are 64 consecutive units (a lane-stride of 32 bytes would use half the banks).
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            const int q = wave * (K / 16) + i * 64 + lane;
+            const int at = ((q & ~127) | ((q & 1) << 6) | ((q & 127) >> 1)) * 4;
+#pragma unroll
+            for (int m = 0; m < MT; ++m) *reinterpret_cast<f32x4*>(&xs[m * K + at]) = xq[m][i];
+            if (NORM) *reinterpret_cast<f32x4*>(&gs[at]) = gq[i];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                const f32x4 x0 = *reinterpret_cast<const f32x4*>(&xs[m * K + c * 512 + lane * 4]);
+                const f32x4 x1 = *reinterpret_cast<const f32x4*>(&xs[m * K + c * 512 + 256 + lane * 4]);
+                xv[m][c][0] = x0.x; xv[m][c][1] = x0.y; xv[m][c][2] = x0.z; xv[m][c][3] = x0.w;
+                xv[m][c][4] = x1.x; xv[m][c][5] = x1.y; xv[m][c][6] = x1.z; xv[m][c][7] = x1.w;
+            }
+            if (NORM) {
+                const f32x4 g0 = *reinterpret_cast<const f32x4*>(&gs[c * 512 + lane * 4]);
+                const f32x4 g1 = *reinterpret_cast<const f32x4*>(&gs[c * 512 + 256 + lane * 4]);
+                g[c][0] = g0.x; g[c][1] = g0.y; g[c][2] = g0.z; g[c][3] = g0.w; g[c][4] = g1.x; g[c][5] = g1.y; g[c][6] = g1.z; g[c][7] = g1.w;
+            }
+        }
+    }
+    KP_MARK(32);   // the activation rows (and gamma) are in this wave's registers, or on their way (!XLDS)
     if (NORM) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
@@ -495,18 +545,13 @@ bool gemv_fast_path(const GemvArgs& a) {
     return true;
 }
 
-template <int MT, int NCH, int RW>
-static void gemv1_launch(const GemvArgs& a, int grid, hipStream_t s) {
-    const bool norm = a.gamma != nullptr, comb = a.po != nullptr;
-#define Q3_G1(EPI, NORM, COMB) Q3_G1P(EPI, NORM, COMB, false)
-#define Q3_G1P(EPI, NORM, COMB, PSUM) hipLaunchKernelGGL((k_gemv1<MT, NCH, RW, EPI, NORM, COMB, PSUM>), dim3(grid), dim3(256), 0, s, a.W, a.W2, a.x, a.gamma, \
+#define Q3_G1P(EPI, NORM, COMB, PSUM, XLDS) hipLaunchKernelGGL((k_gemv1<MT, NCH, RW, EPI, NORM, COMB, PSUM, XLDS>), dim3(grid), dim3(256), 0, s, a.W, a.W2, a.x, a.gamma, \
         (a.epi == EPI_RESIDUAL ? a.res : a.bias), a.N, a.M, a.ldx, a.ldres, (int)a.nt, a)
-    if (comb) { Q3_G1(EPI_RESIDUAL, false, true); return; }
-    if (a.psum) {   // gemv_fast_path: SwiGLU + norm, K = 1024 or 2048 (wider ones would spill)
-        if constexpr (RW <= 3 && NCH % 2 == 0 && NCH <= 4) Q3_G1P(EPI_SWIGLU, true, false, true);
-        else throw Error("gemv: partial-sum prologue not built for this shape");
-        return;
-    }
+// the plain path (activation rows as they lie in memory); XLDS: GemvArgs::xlds
+template <int MT, int NCH, int RW, bool XLDS>
+static void gemv1_plain(const GemvArgs& a, int grid, hipStream_t s) {
+    const bool norm = a.gamma != nullptr;
+#define Q3_G1(EPI, NORM, COMB) Q3_G1P(EPI, NORM, COMB, false, XLDS)
     switch (a.epi) {
     case EPI_STORE: if (norm) Q3_G1(EPI_STORE, true, false); else Q3_G1(EPI_STORE, false, false); break;
     case EPI_SWIGLU:   // gemv1_rw never gives a SwiGLU launch four rows per wave (two weight matrices: the register file); not instantiated
@@ -518,8 +563,19 @@ static void gemv1_launch(const GemvArgs& a, int grid, hipStream_t s) {
     default: Q3_G1(EPI_BIAS_SILU, false, false); break;
     }
 #undef Q3_G1
-#undef Q3_G1P
 }
+template <int MT, int NCH, int RW>
+static void gemv1_launch(const GemvArgs& a, int grid, hipStream_t s) {
+    if (a.po != nullptr) { Q3_G1P(EPI_RESIDUAL, false, true, false, false); return; }
+    if (a.psum) {   // gemv_fast_path: SwiGLU + norm, K = 1024 or 2048 (wider ones would spill)
+        if constexpr (RW <= 3 && NCH % 2 == 0 && NCH <= 4) Q3_G1P(EPI_SWIGLU, true, false, true, false);
+        else throw Error("gemv: partial-sum prologue not built for this shape");
+        return;
+    }
+    if (a.xlds) gemv1_plain<MT, NCH, RW, true>(a, grid, s);
+    else gemv1_plain<MT, NCH, RW, false>(a, grid, s);
+}
+#undef Q3_G1P
 template <int MT, int NCH>
 static void gemv1_rwsel(const GemvArgs& a, hipStream_t s) {
     const int rw = gemv1_rw(a);

@@ -239,6 +239,7 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
     if (const char* sv = knob("Q3TTS_ATTN_STREAM")) attn_stream = atoi(sv) != 0;
     if (const char* sv = knob("Q3TTS_ATTN_STREAM_ONE")) attn_stream_one = atoi(sv) != 0;
     if (const char* sv = knob("Q3TTS_KVH_OPROJ")) kvh_oproj = atoi(sv) != 0;
+    if (flags & Q3TTS_FLAG_TEST_HOOKS) if (const char* sv = knob("Q3TTS_GEMV_XLDS")) gemv_xlds = atoi(sv) != 0;   // this engine's own flag (see prefill_seg)
     if (const char* sv = knob("Q3TTS_CP_QKV_TABLE")) cp_qkv_table_on = atoi(sv) != 0;
     if (const char* sv = knob("Q3TTS_PREFILL_CHUNK")) prefill_chunk = std::min(128, std::max(16, atoi(sv)));
     if (flags & Q3TTS_FLAG_TEST_HOOKS) if (const char* sv = knob("Q3TTS_PREFILL_SEG")) prefill_seg = atoi(sv) != 0;   // this engine's own flag: a default engine beside a hook engine keeps its launches
@@ -581,7 +582,7 @@ void Engine::build_cp_qkv_table() {
         for (int j = 0; j < NG; ++j) {
             launch_bf16_to_f32(cp_embed_w[j], rows, (int64_t)SV * H, stream);
             for (int code = 0; code < SV; ++code)
-                launch_gemv(qkv_gemv_args(cp, 0, rows + (size_t)code * H, cp.H, cp_qkv_tab + ((size_t)j * SV + code) * QKV, 1), stream);
+                gemv(qkv_gemv_args(cp, 0, rows + (size_t)code * H, cp.H, cp_qkv_tab + ((size_t)j * SV + code) * QKV, 1));
         }
         sync();
     } catch (...) {
@@ -708,7 +709,7 @@ bool Engine::run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new,
             g.W = w.qkv; g.xh = pl0h; g.xl = pl0l; g.ldx = ldp; g.out = qkv_slab_d; g.ldo = QKV; g.M = M; g.N = QKV; g.K = W.H; g.epi = EPI_SLAB; g.nt = W.nt;
             launch_gemm2(g, ks_q, 4, stream);
         } else if (!(qkv_in && l == 0)) {
-            launch_gemv(qkv_gemv_args(W, l, x, ldx, qkv, M), stream);
+            gemv(qkv_gemv_args(W, l, x, ldx, qkv, M));
         }
         if (!mfma && !chunk_attn && nb == 1 && pos_dev == nullptr && slot_map == nullptr && W.n_splits == 1 && W.pages_per_slot == 1 && !W.kv_bf16 && !W.kv_round &&
             !(flags & Q3TTS_FLAG_NO_FUSED_CP)) {
@@ -737,8 +738,8 @@ bool Engine::run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new,
                     fg.psum = nullptr; fg.xmid = nullptr;
                     launch_cp_attn_oproj(f, n_new, stream);
                 }
-                launch_gemv(fg, stream);
-                launch_gemv(dg, stream);
+                gemv(fg);
+                gemv(dg);
                 continue;
             }
         }
@@ -843,10 +844,10 @@ bool Engine::run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new,
                 launch_attn_combine(a, stream);
                 o.po = nullptr; o.pm = nullptr; o.pl = nullptr;
             }
-            launch_gemv(o, stream);
+            gemv(o);
         }
-        launch_gemv(f, stream);
-        launch_gemv(d, stream);
+        gemv(f);
+        gemv(d);
     }
     return mfma && final_gamma != nullptr;
 }
@@ -875,7 +876,7 @@ int Engine::head_proj(const bf16_t* Wm, const float* x, int ldx, const float* ga
     GemvArgs g;
     g.W = Wm; g.x = x; g.ldx = ldx; g.gamma = gamma; g.eps = eps; g.xn_out = xn_out; g.ld_xn = ld_xn;
     g.out = out; g.ldo = ldo; g.M = M; g.N = N; g.K = K; g.epi = EPI_STORE; g.nt = nt;
-    launch_gemv(g, stream);
+    gemv(g);
     return 1;
 }
 
@@ -911,10 +912,10 @@ void Engine::text_project_dev(const int64_t* ids, int n) {
         launch_gather_rows_bf16(text_embed, TH, proj_ids_d + i0, 16, text_tmp, TH, stream);
         GemvArgs a;
         a.W = fc1_w; a.x = text_tmp; a.ldx = TH; a.bias = fc1_b; a.out = text_tmp2; a.ldo = TH; a.M = 16; a.N = TH; a.K = TH; a.epi = EPI_BIAS_SILU;
-        launch_gemv(a, stream);
+        gemv(a);
         GemvArgs b;
         b.W = fc2_w; b.x = text_tmp2; b.ldx = TH; b.bias = fc2_b; b.out = proj_out_d + (size_t)i0 * H; b.ldo = H; b.M = 16; b.N = H; b.K = TH; b.epi = EPI_BIAS;
-        launch_gemv(b, stream);
+        gemv(b);
     }
 }
 
@@ -1086,7 +1087,7 @@ void Engine::talker_decode(int slot, const float* embed, float* logits, float* l
     GemvArgs g;
     g.W = codec_head; g.x = xp; g.ldx = H; g.gamma = talker_norm; g.eps = c.rms_eps; g.xn_out = hn; g.ld_xn = H;
     g.out = logits_p; g.ldo = V; g.M = 1; g.N = V; g.K = H; g.epi = EPI_STORE; g.nt = true;
-    launch_gemv(g, stream);
+    gemv(g);
     launch_copy_rows(logits_p, V, logits_t + (size_t)slot * V, V, 1, V, stream);
     launch_copy_rows(hn, H, x_cp + (size_t)slot * 2 * H, H, 1, H, stream);
     pos += 1;
@@ -1327,7 +1328,7 @@ void Engine::code_predictor(const float* seq, int n, int step, float* logits) {
     GemvArgs g;
     g.W = cp_head[step]; g.x = xc + (size_t)(n - 1) * Hc; g.ldx = Hc; g.gamma = cp_norm; g.eps = c.cp_rms_eps;
     g.out = logits_p; g.ldo = SV; g.M = 1; g.N = SV; g.K = Hc; g.epi = EPI_STORE;
-    launch_gemv(g, stream);
+    gemv(g);
     Q3_HIP_CHECK(hipMemcpyAsync(logits, logits_p, (size_t)SV * sizeof(float), hipMemcpyDeviceToHost, stream));
     sync();
 }
@@ -1435,7 +1436,7 @@ float* Engine::cp_project(float* rows, int ld, int M) {
     if (!cp_projected()) return rows;
     GemvArgs g;
     g.W = cp_proj_w; g.x = rows; g.ldx = ld; g.bias = cp_proj_b; g.out = x_cpp; g.ldo = cp_width(); g.M = M; g.N = cp_width(); g.K = c.hidden; g.epi = EPI_BIAS;
-    launch_gemv(g, stream);
+    gemv(g);
     return x_cpp;
 }
 

@@ -28,7 +28,7 @@ eng.decode_steps(8)
 acc = np.zeros(5); n = 0
 for _ in range(16):
     eng.decode_steps(1)
-    buf = (C.c_longlong * 32)()
+    buf = (C.c_longlong * 40)()
     L.q3_kernel_prof(buf)
     t = np.array(buf[:], dtype=np.float64) * 10.0
     v = np.array([t[12], t[13], t[14], t[15], t[23]])

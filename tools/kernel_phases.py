@@ -20,7 +20,7 @@ L = C.CDLL(os.environ["Q3TTS_LIB"])
 
 
 def marks():
-    buf = (C.c_longlong * 32)()
+    buf = (C.c_longlong * 40)()
     L.q3_kernel_prof(buf)
     return np.array(buf[:], dtype=np.float64) * 10.0   # ns
 
@@ -51,16 +51,16 @@ ids = frame_tokens(rng.integers(0, 151643, 16))
 p, tr = eng.build_prompt(ids, 0)
 eng.slot_begin(0, p, tr, q3tts.Sampling(max_new_tokens=200), seed=1, ignore_eos=True)
 eng.decode_steps(150)   # context ~160: two attention splits
-acc_g, acc_c, acc_a, n = np.zeros(4), np.zeros(7), np.zeros(6), 0
+acc_g, acc_c, acc_a, n = np.zeros(5), np.zeros(7), np.zeros(6), 0
 for i in range(40):
     eng.decode_steps(1)
     t = marks()
-    acc_g += t[8:12] - t[8]
+    acc_g += t[[8, 9, 32, 10, 11]] - t[8]   # mark 32: the activation rows are in registers (behind the LDS round when they are staged)
     acc_c += t[16:23] - t[16]
     acc_a += t[24:30] - t[24]
     n += 1
 g, c = acc_g / n, acc_c / n
-print(f"{'k_gemv1 (last = codec head)':28s} issue_loads={g[1]:.0f}ns norm+wait={g[2] - g[1]:.0f}ns dot+reduce={g[3] - g[2]:.0f}ns total={g[3]:.0f}ns")
+print(f"{'k_gemv1 (last = codec head)':28s} issue_loads={g[1]:.0f}ns stage={g[2] - g[1]:.0f}ns norm+wait={g[3] - g[2]:.0f}ns dot+reduce={g[4] - g[3]:.0f}ns total={g[4]:.0f}ns")
 print(f"{'k_cp_attn_oproj (last layer)':28s} issue_loads={c[1]:.0f}ns norm+rope={c[2] - c[1]:.0f}ns lds_fragments={c[3] - c[2]:.0f}ns scores+merge(wave 0)={c[6] - c[3]:.0f}ns "
       f"block_barrier={c[4] - c[6]:.0f}ns gemv={c[5] - c[4]:.0f}ns total={c[5]:.0f}ns")
 a = acc_a / n
