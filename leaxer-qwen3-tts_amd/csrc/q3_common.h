@@ -83,6 +83,8 @@ struct GemvArgs {
     // summed in kv-head order; every workgroup stores its slice of that sum to xmid [M][K] (the down projection's residual)
     const float* psum = nullptr;
     float* xmid = nullptr;
+    bool psum_lead = true;        // psum launches: x, the partial rows and gamma (one 16-byte unit per thread, shared through LDS) are issued ahead of the
+                                  // weight loads; false: behind them, gamma whole in every wave (Q3TTS_GEMV_PSUM_LEAD=0, the A/B knob).  Same bits.
 };
 void launch_gemv(const GemvArgs& a, hipStream_t s);
 bool gemv_fast_path(const GemvArgs& a); // single-pass kernel available (M <= 2, K in {1024,2048,3072})
@@ -159,6 +161,8 @@ struct CpAttnOprojArgs {
     int nq = 0, nkv = 0, d = 0;
     const bf16_t* W = nullptr; int K = 0, N = 0; // o_proj [N][K]
     float* x = nullptr; int ldx = 0;             // residual stream rows [n_new][ldx], updated in place
+    bool lead = true;                            // launch_cp_attn_kvh: the attention's operands are issued ahead of the o_proj weight loads; false: the
+                                                 // weights first (Q3TTS_CP_KVH_LEAD=0, the A/B knob).  Same bits.
 };
 bool cp_attn_oproj_ok(const CpAttnOprojArgs& a, int n_new);
 void launch_cp_attn_oproj(const CpAttnOprojArgs& a, int n_new, hipStream_t s);

@@ -247,6 +247,7 @@ static void gemv_r(const GemvArgs& a, hipStream_t s) {
 // o_proj): the activation rows are x + the 8 o_proj partial rows, summed in a fixed order; the workgroup shares the sum through LDS
 // and stores its slice of it to a.xmid, the down projection's residual operand.  XLDS (the other launches): the four waves load a quarter
 // of the activation rows and of gamma each, ahead of the weights, and share them through LDS; same values in the same registers.
+// PLEAD (PSUM's default): x, the partial rows and one 16-byte unit of gamma per thread are issued ahead of the weights as well.
 // ================================================================================================
 static __device__ __forceinline__ uint4 ldw_rt(const bf16_t* p, bool nt) {
     u32x4 v;
@@ -258,7 +259,7 @@ static __device__ __forceinline__ uint4 ldw_rt(const bf16_t* p, bool nt) {
 // The leading scalar parameters repeat the fields the first loads need: the file is built with -amdgpu-kernarg-preload-count=16, so the
 // command processor hands them to the wave in SGPRs at launch instead of the wave fetching its kernarg segment first (~0.35 us per
 // launch on a chain of dependent GEMVs; a by-value struct is not preloadable).
-template <int MT, int NCH, int RW, int EPI, bool NORM, bool COMB, bool PSUM = false, bool XLDS = false>
+template <int MT, int NCH, int RW, int EPI, bool NORM, bool COMB, bool PSUM = false, bool XLDS = false, bool PLEAD = false>
 __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* pW2, const float* px, const float* pgamma, const float* pepi,
                                                 int pN, int pM, int pldx, int pldepi, int pnt, GemvArgs a) {
     constexpr int K = NCH * 512;
@@ -267,8 +268,9 @@ __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* p
     const int n0 = (blockIdx.x * 4 + wave) * RW;
     const int N = pN, M = pM;
     __shared__ __attribute__((aligned(16))) float xs[(COMB || PSUM || XLDS) ? MT * K : 1];
-    __shared__ __attribute__((aligned(16))) float gs[(XLDS && NORM) ? K : 1];
+    __shared__ __attribute__((aligned(16))) float gs[((XLDS || PLEAD) && NORM) ? K : 1];
     static_assert(!XLDS || (NCH % 2 == 0 && !COMB && !PSUM), "XLDS: plain path, whole 16-byte loads per quarter row");
+    static_assert(!PLEAD || (PSUM && NORM), "PLEAD: the partial-sum prologue's load order");
     // XLDS: wave w loads only quarter w of every activation row and of gamma, 16 bytes per lane (NCH / 2 instructions per row where the
     // whole row takes 2 NCH in each of the four waves), and the workgroup shares the quarters through LDS
     constexpr int NQ = XLDS ? NCH / 2 : 1;
@@ -289,6 +291,34 @@ __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* p
     // the LDS round below leaves the weights in flight, and the round and the RMSNorm statistics run under the weights' latency.  Behind
     // the weights the same round sits on the critical path and the step is slower than without it (profiles/gemv_xlds_ab.txt).
     if (XLDS) { load_quarters(); __builtin_amdgcn_sched_barrier(0); }
+    // PSUM: thread t owns elements 4 t + 1024 i of every row: x and the 8 partial rows (kv heads ascending).  PLEAD issues them here,
+    // ahead of the weights like the quarters above and for the same reason, with the thread's own 16-byte unit of gamma (every row
+    // element is owned by one thread of the workgroup, so gamma goes through LDS once instead of whole into each of the four waves).
+    // The launcher repeats a.psum in pepi, which SwiGLU does not use: loads that lead the weights must not wait for the kernarg fetch.
+    constexpr int NI = PSUM ? K / 1024 : 1, NP = 8;
+    static_assert(!PSUM || K % 1024 == 0, "PSUM: K must be a multiple of 1024");
+    float4 xin[PSUM ? MT : 1][NI], pin[PSUM ? MT : 1][NI][PSUM ? NP : 1];
+    f32x4 gu[NI];
+    const float* ppsum = PLEAD ? pepi : a.psum;
+    auto load_psum = [&]() {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const int mr = m < M ? m : 0;
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int k4 = i * 1024 + threadIdx.x * 4;
+                xin[m][i] = *reinterpret_cast<const float4*>(px + (size_t)mr * pldx + k4);
+#pragma unroll
+                for (int h = 0; h < NP; ++h) pin[m][i][h] = *reinterpret_cast<const float4*>(ppsum + ((size_t)h * M + mr) * K + k4);
+            }
+        }
+    };
+    if (PLEAD) {
+        load_psum();
+#pragma unroll
+        for (int i = 0; i < NI; ++i) gu[i] = *reinterpret_cast<const f32x4*>(pgamma + i * 1024 + threadIdx.x * 4);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     // 1. weights: everything this wave will ever read, in flight at once
     uint4 w[RW][NCH], w2[RW][NCH];
 #pragma unroll
@@ -321,24 +351,13 @@ __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* p
     // 2. activations
     float xv[MT][NCH][8];
     if (PSUM) {
-        // thread t owns elements 4 t + 1024 i: x and the 8 partial rows (kv heads ascending) are loaded in one round with gamma, then
-        // x + (p0 + p1 + ... + p7) goes to LDS and, for the chunks this workgroup owns (chunk % grid == block), to a.xmid
-        constexpr int NI = K / 1024, NP = 8;
-        static_assert(K % 1024 == 0, "PSUM: K must be a multiple of 1024");
-        float4 xin[MT][NI], pin[MT][NI][NP];
-#pragma unroll
-        for (int m = 0; m < MT; ++m) {
-            const int mr = m < M ? m : 0;
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                const int k4 = i * 1024 + threadIdx.x * 4;
-                xin[m][i] = *reinterpret_cast<const float4*>(px + (size_t)mr * pldx + k4);
-#pragma unroll
-                for (int h = 0; h < NP; ++h) pin[m][i][h] = *reinterpret_cast<const float4*>(a.psum + ((size_t)h * M + mr) * K + k4);
-            }
+        // x + (p0 + p1 + ... + p7) goes to LDS and, for the chunks this workgroup owns (chunk % grid == block), to a.xmid.  !PLEAD: the
+        // rows are loaded here, in one round with gamma behind the weights (Q3TTS_GEMV_PSUM_LEAD=0, the A/B knob)
+        if (!PLEAD) {
+            load_psum();
+            if (NORM) load_gamma();
+            __builtin_amdgcn_sched_barrier(0);
         }
-        if (NORM) load_gamma();
-        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -348,7 +367,11 @@ __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* p
 #pragma unroll
                 for (int h = 1; h < NP; ++h) { ps.x += pin[m][i][h].x; ps.y += pin[m][i][h].y; ps.z += pin[m][i][h].z; ps.w += pin[m][i][h].w; }
                 const float4 v = make_float4(xin[m][i].x + ps.x, xin[m][i].y + ps.y, xin[m][i].z + ps.z, xin[m][i].w + ps.w);
-                *reinterpret_cast<float4*>(&xs[m * K + k4]) = v;
+                // PLEAD: the XLDS layout (a chunk's even 16-byte units, then its odd ones: both reads of a chunk are 64 consecutive units)
+                const int q = k4 / 4;
+                const int at = PLEAD ? ((q & ~127) | ((q & 1) << 6) | ((q & 127) >> 1)) * 4 : k4;
+                *reinterpret_cast<float4*>(&xs[m * K + at]) = v;
+                if (PLEAD && m == 0) *reinterpret_cast<f32x4*>(&gs[at]) = gu[i];
                 if (m < M && (k4 / 4) % gridDim.x == blockIdx.x) *reinterpret_cast<float4*>(a.xmid + (size_t)m * K + k4) = v;
             }
         __syncthreads();
@@ -356,11 +379,19 @@ __global__ __launch_bounds__(256) void k_gemv1(const bf16_t* pW, const bf16_t* p
         for (int m = 0; m < MT; ++m)
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
-                const float4 x0 = *reinterpret_cast<const float4*>(&xs[m * K + c * 512 + lane * 8]);
-                const float4 x1 = *reinterpret_cast<const float4*>(&xs[m * K + c * 512 + lane * 8 + 4]);
+                const float4 x0 = *reinterpret_cast<const float4*>(&xs[m * K + c * 512 + (PLEAD ? lane * 4 : lane * 8)]);
+                const float4 x1 = *reinterpret_cast<const float4*>(&xs[m * K + c * 512 + (PLEAD ? 256 + lane * 4 : lane * 8 + 4)]);
                 xv[m][c][0] = x0.x; xv[m][c][1] = x0.y; xv[m][c][2] = x0.z; xv[m][c][3] = x0.w;
                 xv[m][c][4] = x1.x; xv[m][c][5] = x1.y; xv[m][c][6] = x1.z; xv[m][c][7] = x1.w;
             }
+        if (PLEAD) {
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                const f32x4 g0 = *reinterpret_cast<const f32x4*>(&gs[c * 512 + lane * 4]);
+                const f32x4 g1 = *reinterpret_cast<const f32x4*>(&gs[c * 512 + 256 + lane * 4]);
+                g[c][0] = g0.x; g[c][1] = g0.y; g[c][2] = g0.z; g[c][3] = g0.w; g[c][4] = g1.x; g[c][5] = g1.y; g[c][6] = g1.z; g[c][7] = g1.w;
+            }
+        }
     } else if (COMB) {
         for (int k8 = threadIdx.x * 8; k8 < K; k8 += 2048) {
             const int head = k8 / a.pd, e0 = k8 % a.pd;
@@ -545,13 +576,13 @@ bool gemv_fast_path(const GemvArgs& a) {
     return true;
 }
 
-#define Q3_G1P(EPI, NORM, COMB, PSUM, XLDS) hipLaunchKernelGGL((k_gemv1<MT, NCH, RW, EPI, NORM, COMB, PSUM, XLDS>), dim3(grid), dim3(256), 0, s, a.W, a.W2, a.x, a.gamma, \
-        (a.epi == EPI_RESIDUAL ? a.res : a.bias), a.N, a.M, a.ldx, a.ldres, (int)a.nt, a)
+#define Q3_G1P(EPI, NORM, COMB, PSUM, XLDS, PLEAD) hipLaunchKernelGGL((k_gemv1<MT, NCH, RW, EPI, NORM, COMB, PSUM, XLDS, PLEAD>), dim3(grid), dim3(256), 0, s, a.W, a.W2, a.x, a.gamma, \
+        (a.psum ? a.psum : a.epi == EPI_RESIDUAL ? a.res : a.bias), a.N, a.M, a.ldx, a.ldres, (int)a.nt, a)
 // the plain path (activation rows as they lie in memory); XLDS: GemvArgs::xlds
 template <int MT, int NCH, int RW, bool XLDS>
 static void gemv1_plain(const GemvArgs& a, int grid, hipStream_t s) {
     const bool norm = a.gamma != nullptr;
-#define Q3_G1(EPI, NORM, COMB) Q3_G1P(EPI, NORM, COMB, false, XLDS)
+#define Q3_G1(EPI, NORM, COMB) Q3_G1P(EPI, NORM, COMB, false, XLDS, false)
     switch (a.epi) {
     case EPI_STORE: if (norm) Q3_G1(EPI_STORE, true, false); else Q3_G1(EPI_STORE, false, false); break;
     case EPI_SWIGLU:   // gemv1_rw never gives a SwiGLU launch four rows per wave (two weight matrices: the register file); not instantiated
@@ -566,9 +597,9 @@ static void gemv1_plain(const GemvArgs& a, int grid, hipStream_t s) {
 }
 template <int MT, int NCH, int RW>
 static void gemv1_launch(const GemvArgs& a, int grid, hipStream_t s) {
-    if (a.po != nullptr) { Q3_G1P(EPI_RESIDUAL, false, true, false, false); return; }
+    if (a.po != nullptr) { Q3_G1P(EPI_RESIDUAL, false, true, false, false, false); return; }
     if (a.psum) {   // gemv_fast_path: SwiGLU + norm, K = 1024 or 2048 (wider ones would spill)
-        if constexpr (RW <= 3 && NCH % 2 == 0 && NCH <= 4) Q3_G1P(EPI_SWIGLU, true, false, true, false);
+        if constexpr (RW <= 3 && NCH % 2 == 0 && NCH <= 4) { if (a.psum_lead) Q3_G1P(EPI_SWIGLU, true, false, true, false, true); else Q3_G1P(EPI_SWIGLU, true, false, true, false, false); }
         else throw Error("gemv: partial-sum prologue not built for this shape");
         return;
     }
@@ -2526,10 +2557,17 @@ static __device__ __forceinline__ void kvh_gemv_store(const uint4 (&w)[4], const
 // 2 h + 1 and do exactly what a wave of k_cp_attn_oproj does for its head; waves 2 and 3 only hold weights.  All addresses are known at
 // launch (host-known position, contiguous per-slot cache): weights, q/k/v rows, norm / RoPE operands and h's cached K/V are one memory
 // round.  Column chunk 0 of head h appends h's new K/V rows to the cache.  NEW = new rows (1, or 2 for the first pass), U as there.
-template <int NEW, int U>
-__global__ __launch_bounds__(256) void k_cp_attn_kvh(const bf16_t* pW, const float* pqkv, const float* pkc, const float* pvc, float* ppart,
+// LEAD (the default): waves 0 and 1 issue their operands ahead of the weights, which are needed last; !LEAD: the weights first.
+template <int NEW, int U, bool LEAD>
+__global__ __launch_bounds__(256) void k_cp_attn_kvh(const bf16_t* pW, const float* pqkv, const float* pa0, const float* pa1, float* ppart,
                                                      const float* pcos, const float* psin, uint32_t pk0, uint32_t pk1, CpAttnOprojArgs a) {
-    // leading scalars preloaded into SGPRs (see k_gemv1): pk0 = base | page_tokens << 16, pk1 = N
+    // leading scalars preloaded into SGPRs (see k_gemv1): pk0 = base | page_tokens << 16, pk1 = N.  (pa0, pa1): LEAD: the norm gains, which
+    // the RMSNorm at the head of the critical path needs (the cache pointers come with the kernarg fetch: the cached rows are needed later,
+    // behind the gains they would otherwise wait with); !LEAD: the cache pointers, the gains from the kernarg segment
+    const float* pqn = LEAD ? pa0 : a.q_norm;
+    const float* pkn = LEAD ? pa1 : a.k_norm;
+    const float* pkc = LEAD ? (const float*)a.kc : pa0;
+    const float* pvc = LEAD ? (const float*)a.vc : pa1;
     const int pbase = (int)(pk0 & 0xFFFFu), ppage_tokens = (int)(pk0 >> 16), pN = (int)pk1;
     constexpr int LDQ = 4096;
     constexpr int D = 128, HALF = 64, EPL = 8, G = 2, NKV = 8, NQ = 16, K = 2048, KS = G * D;
@@ -2546,9 +2584,14 @@ __global__ __launch_bounds__(256) void k_cp_attn_kvh(const bf16_t* pW, const flo
     __shared__ float attn_s[NEW][KS];
 
     // ---- the one memory round ----
+    // vmcnt counts in issue order: with the weights in front, the wait ahead of the RMSNorm below is a wait for the weights as well, and
+    // they are 16 KB from HBM that nothing needs before the last barrier.  LEAD puts the attention's operands (the previous launch's
+    // output and the cache) in front in the two waves that have any, so that wait leaves the four weight loads in flight.
     uint4 w[4];
-    kvh_load_w(w, pW, pN, K, n0, kvh * KS, lane);
-    __builtin_amdgcn_sched_barrier(0);
+    if (!LEAD) {
+        kvh_load_w(w, pW, pN, K, n0, kvh * KS, lane);
+        __builtin_amdgcn_sched_barrier(0);
+    }
 
     if (wave < G) {
         struct VecOps { float x0, x1, v0, v1, n0, n1, cs, sn; };
@@ -2561,12 +2604,13 @@ __global__ __launch_bounds__(256) void k_cp_attn_kvh(const bf16_t* pW, const flo
             const float* rowp = pqkv + (size_t)j * LDQ;
             const float* src = rowp + (is_q ? head * D : (NQ + kvh) * D);
             const float* vs = rowp + (NQ + NKV + kvh) * D;
-            const float* nw = is_q ? a.q_norm : a.k_norm;
+            const float* nw = is_q ? pqn : pkn;
             vec[v].x0 = src[lane]; vec[v].x1 = src[lane + HALF];
             vec[v].v0 = vs[lane]; vec[v].v1 = vs[lane + HALF];
             vec[v].n0 = nw[lane]; vec[v].n1 = nw[lane + HALF];
             vec[v].cs = pcos[(size_t)(base + j) * HALF + lane]; vec[v].sn = psin[(size_t)(base + j) * HALF + lane];
         }
+        if (LEAD) __builtin_amdgcn_sched_barrier(0);   // the cache pointers' wait for the kernarg fetch stays behind the loads above
         const int tg = lane >> 4, sub = lane & 15;
         float kr[U][EPL], vr[U][EPL];
 #pragma unroll
@@ -2581,6 +2625,10 @@ __global__ __launch_bounds__(256) void k_cp_attn_kvh(const bf16_t* pW, const flo
             vr[u][0] = v0.x; vr[u][1] = v0.y; vr[u][2] = v0.z; vr[u][3] = v0.w; vr[u][4] = v1.x; vr[u][5] = v1.y; vr[u][6] = v1.z; vr[u][7] = v1.w;
         }
         __builtin_amdgcn_sched_barrier(0);
+        if (LEAD) {
+            kvh_load_w(w, pW, pN, K, n0, kvh * KS, lane);
+            __builtin_amdgcn_sched_barrier(0);
+        }
 
         // ---- 1. q / k RMSNorm + RoPE; wave-private staging ----
 #pragma unroll
@@ -2671,6 +2719,8 @@ __global__ __launch_bounds__(256) void k_cp_attn_kvh(const bf16_t* pW, const flo
                 *reinterpret_cast<float4*>(dst + 4) = make_float4(o[4] * il, o[5] * il, o[6] * il, o[7] * il);
             }
         }
+    } else if (LEAD) {
+        kvh_load_w(w, pW, pN, K, n0, kvh * KS, lane);
     }
     __syncthreads();
     // ---- 3. o_proj K-slice: partial rows of kv head h ----
@@ -2682,11 +2732,13 @@ void launch_cp_attn_kvh(const CpAttnOprojArgs& a, int n_new, float* part, hipStr
     if (!cp_attn_oproj_ok(a, n_new) || part == nullptr) throw Error("cp_attn_kvh: unsupported shape");
     const int U = a.base <= 4 ? 1 : (a.base <= 8 ? 2 : (a.base <= 12 ? 3 : 4));
     const dim3 grid(((a.N + KVH_COLS - 1) / KVH_COLS) * 8), block(256);
-#define Q3_CAK(NEW, UU) hipLaunchKernelGGL((k_cp_attn_kvh<NEW, UU>), grid, block, 0, s, a.W, a.qkv, (const float*)a.kc, (const float*)a.vc, part, \
+#define Q3_CAK1(NEW, UU, LEAD) hipLaunchKernelGGL((k_cp_attn_kvh<NEW, UU, LEAD>), grid, block, 0, s, a.W, a.qkv, LEAD ? a.q_norm : (const float*)a.kc, LEAD ? a.k_norm : (const float*)a.vc, part, \
         a.rope_cos, a.rope_sin, (uint32_t)a.base | (uint32_t)a.page_tokens << 16, (uint32_t)a.N, a)
+#define Q3_CAK(NEW, UU) do { if (a.lead) Q3_CAK1(NEW, UU, true); else Q3_CAK1(NEW, UU, false); } while (0)
     if (n_new == 1) { if (U == 1) Q3_CAK(1, 1); else if (U == 2) Q3_CAK(1, 2); else if (U == 3) Q3_CAK(1, 3); else Q3_CAK(1, 4); }
     else { if (U == 1) Q3_CAK(2, 1); else if (U == 2) Q3_CAK(2, 2); else Q3_CAK(2, 3); }   // cp_attn_oproj_ok: two new rows only over <= 12 cached tokens
 #undef Q3_CAK
+#undef Q3_CAK1
     Q3_HIP_CHECK(hipGetLastError());
 }
 

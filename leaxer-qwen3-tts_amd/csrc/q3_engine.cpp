@@ -240,6 +240,8 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
     if (const char* sv = knob("Q3TTS_ATTN_STREAM_ONE")) attn_stream_one = atoi(sv) != 0;
     if (const char* sv = knob("Q3TTS_KVH_OPROJ")) kvh_oproj = atoi(sv) != 0;
     if (flags & Q3TTS_FLAG_TEST_HOOKS) if (const char* sv = knob("Q3TTS_GEMV_XLDS")) gemv_xlds = atoi(sv) != 0;   // this engine's own flag (see prefill_seg)
+    if (flags & Q3TTS_FLAG_TEST_HOOKS) if (const char* sv = knob("Q3TTS_GEMV_PSUM_LEAD")) gemv_psum_lead = atoi(sv) != 0;   // this engine's own flags, as above
+    if (flags & Q3TTS_FLAG_TEST_HOOKS) if (const char* sv = knob("Q3TTS_CP_KVH_LEAD")) cp_kvh_lead = atoi(sv) != 0;
     if (const char* sv = knob("Q3TTS_CP_QKV_TABLE")) cp_qkv_table_on = atoi(sv) != 0;
     if (const char* sv = knob("Q3TTS_PREFILL_CHUNK")) prefill_chunk = std::min(128, std::max(16, atoi(sv)));
     if (flags & Q3TTS_FLAG_TEST_HOOKS) if (const char* sv = knob("Q3TTS_PREFILL_SEG")) prefill_seg = atoi(sv) != 0;   // this engine's own flag: a default engine beside a hook engine keeps its launches
@@ -722,6 +724,7 @@ bool Engine::run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new,
             f.qkv = qkv; f.ld_qkv = QKV; f.kc = W.kc + coff; f.vc = W.vc + coff; f.page_tokens = ptok; f.base = pos_scalar;
             f.q_norm = w.q_norm; f.k_norm = w.k_norm; f.eps = W.eps; f.rope_cos = W.rope_cos; f.rope_sin = W.rope_sin;
             f.scale = 1.0f / sqrtf((float)W.d); f.nq = W.nq; f.nkv = W.nkv; f.d = W.d; f.W = w.o; f.K = AO; f.N = W.H; f.x = x; f.ldx = ldx;
+            f.lead = cp_kvh_lead;
             if (cp_attn_oproj_ok(f, n_new)) {
                 GemvArgs fg;
                 fg.W = w.gate; fg.W2 = w.up; fg.x = x; fg.ldx = ldx; fg.gamma = w.post_norm; fg.eps = W.eps; fg.out = act; fg.ldo = W.ffn;

@@ -496,7 +496,9 @@ public:
     void free_cp_qkv_table();      // also drops the captured graphs: an nb = 1 graph has the table's address baked in
     GemvArgs qkv_gemv_args(const DecStack& W, int l, const float* x, int ldx, float* out, int M) const;   // a layer's QKV projection on the GEMV path
     bool gemv_xlds = true;       // Q3TTS_GEMV_XLDS=0 at engine creation: GemvArgs::xlds of this engine's GEMV launches (A/B knob, tests' second path; same bits)
-    void gemv(GemvArgs g) const { g.xlds = gemv_xlds; launch_gemv(g, stream); }
+    bool gemv_psum_lead = true;  // Q3TTS_GEMV_PSUM_LEAD=0 at engine creation: GemvArgs::psum_lead of this engine's gate/up launches behind a kv-head-split o_proj (A/B knob, tests' second path; same bits)
+    bool cp_kvh_lead = true;     // Q3TTS_CP_KVH_LEAD=0 at engine creation: CpAttnOprojArgs::lead of this engine's k_cp_attn_kvh launches (A/B knob, tests' second path; same bits)
+    void gemv(GemvArgs g) const { g.xlds = gemv_xlds; g.psum_lead = gemv_psum_lead; launch_gemv(g, stream); }
     bool kvh_oproj = true;       // Q3TTS_KVH_OPROJ=0 at engine creation: o_proj keeps the whole K in one launch (k_cp_attn_oproj / COMB GEMV; A/B knob, tests' second path)
     // split-K seam of the batched step (GemmArgs::seam): arrival / claim counters, one region per seam launch of the step (generation-valued words:
     // never reset), and the per-(row, 64-column tile) sums of squares behind the two residual seams of a layer
