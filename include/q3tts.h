@@ -737,6 +737,61 @@ int q3tts_codec_stream_set_speed(q3tts_engine* e, int stream_id, int32_t speed_p
  * 24 kHz.  Codes, frame counts and RNG use are untouched.  1000: none. */
 int q3tts_engine_set_speed(q3tts_engine* e, int32_t speed_permille);
 
+/* ---- output level: carried-state gain and look-ahead limiter ([HINT] no counterpart in the reference, which has no volume control; its
+ * dead wav_writer.cpp peak-normalises a whole clip, which a streaming engine cannot do) ----
+ * A third stage at 24 kHz between the stretcher and the sink: vocoder -> stretcher -> level -> sink, on the GPU, all stages of a push in
+ * one launch.  Parameters: gain_cb, integer centibels, -600 .. +400; ceiling_permille, 0 = gain only, 1 .. 1000 = limiter at
+ * T = (float)(ceiling / 1000.0).  (0, 0) is "no stage": no launch, the same bytes as before.
+ * Gain: g = 10^(gain_cb / 200), formed in double and rounded to float (q3tts_level_gain returns the very value the device uses).
+ * Gain only (ceiling 0): y[k] = g x[k], one fp32 product; no latency, E(R) = R.
+ * Limiter, look-ahead window W = 128 samples (5.3 ms):
+ *   1. v[k] = g x[k], a[k] = |v[k]|;
+ *   2. r[k] = (a[k] > T) ? T / a[k] : 1.0f, a correctly rounded fp32 division;
+ *   3. r[k] = 1 for k < 0 and, once the stage is finished with n samples, for k >= n;
+ *   4. m[k] = min(r[k], .., r[k + 127]);
+ *   5. q[k] = (int32)floor(m[k] * 65536.0f), in [0, 65536];
+ *   6. S[k] = q[k] + q[k - 1] + .. + q[k - 127], an integer <= 2^23, exact in any order;
+ *   7. s[k] = (float)S[k] * 2^-23, exact;
+ *   8. y[k] = min(max(v[k] * s[k], -T), T): one fp32 product, then the clamp.
+ * Every fp32 operation is a single rounded operation and the minimum and the integer sum are order-free, so a sample's bits depend on
+ * its absolute index, the input and the parameters alone: never on how the audio was cut into pushes, on which stages shared a launch
+ * or on how the kernel tiles its work.  Every q in S[k] comes from a window that contains k, so s[k] <= r[k] and |y[k]| <= T; where no
+ * sample within +-127 of k exceeds T, s[k] = 1 exactly and y[k] = v[k] bit for bit.
+ * A limiter that has received R samples and is not finished has emitted E(R) = max(0, R - 127) outputs; finished with n samples, n.  A
+ * push delivers E(after) - E(before).  It carries the last 254 values of v in two alternating buffers of its own, and its counters.
+ * Non-finite input: the formulas apply as written.
+ * Known limits: a primed stream's level stage (q3tts_codec_stream_prime_batch_host, q3tts_synthesize_continue_stream_host) starts from
+ * r = 1 history, like its sink and its stretcher start from silence; the sink's band-limited resampling behind the limiter can
+ * overshoot T slightly, and the int16 conversion's clip stays behind it. */
+/* Host only, no engine.  g for gain_cb; -1.0f for a gain outside -600 .. +400 (q3tts_level_last_error() then names the value;
+ * thread-local, valid until the thread's next level_gain / level_emitted call). */
+float q3tts_level_gain(int32_t gain_cb);
+/* Host only: outputs a stage with these parameters has emitted in all after n_received samples.  -1 for parameters out of range or
+ * n_received < 0.  (0, 0) is answered by the same rule. */
+int64_t q3tts_level_emitted(int32_t gain_cb, int32_t ceiling_permille, int64_t n_received, int finished);
+const char* q3tts_level_last_error(void);
+/* Level stages on their own: the stage by itself, fed 24 kHz float from the host.  A stage accepts at most one hour of input
+ * (86 400 000 samples), a push at most 1 440 000.  At most 4096 stages are open at a time (vocoder streams' included).  (0, 0) is
+ * refused: it is no stage. */
+int q3tts_level_begin(q3tts_engine* e, int32_t gain_cb, int32_t ceiling_permille, int* id);
+/* n stages (distinct, open, not finished), stage i given n_in[i] >= 0 more samples pcm24[i]; finish[i] != 0 (finish NULL: none) flushes
+ * the tail with this push and closes the stage's audio (n_in[i] == 0 allowed).  out[i] has room for cap_samples floats; out_len[i] is
+ * the push's length by the rule above (min(out_len, cap_samples) samples are written).  The call is validated completely before any
+ * stage moves.  n_in[i] == 0 without finish leaves the stage as it was; a push that emits nothing still updates the carry. */
+int q3tts_level_push_batch_host(q3tts_engine* e, int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in,
+                                const uint8_t* finish, float* const* out, int64_t cap_samples, int64_t* out_len);
+int q3tts_level_end(q3tts_engine* e, int id);
+/* Vocoder streams.  A stream delivers through a level stage from its first sample on: refused, by name, once the stream has delivered
+ * a sample.  (0, 0) takes the stage away again.  q3tts_codec_stream_push_batch_any_host serves such streams: the stage reads the push's
+ * PCM (or its stretcher's output) where it lies and feeds the stream's sink in the same push when it has one; finish[s] flushes the
+ * stretcher, then the level stage, then the sink, and is allowed on a stream with a level stage and no sink.  The float entries refuse
+ * a stream with a level stage by name. */
+int q3tts_codec_stream_set_level(q3tts_engine* e, int stream_id, int32_t gain_cb, int32_t ceiling_permille);
+/* The scheduler: one setter for the four streaming entries, beside q3tts_engine_set_sink / q3tts_engine_set_speed.  The finished = 1
+ * call carries the limiter's tail, so an utterance's calls add up to the length they have without the stage.  Codes, frame counts
+ * and RNG use are untouched.  (0, 0): none. */
+int q3tts_engine_set_level(q3tts_engine* e, int32_t gain_cb, int32_t ceiling_permille);
+
 /* ---- text front end: the reference's byte-level BPE tokenizer ---- */
 /* Replaces leaxer_qwen::io::load_vocab / load_merges / is_tokenizer_ready / tokenize (reference
  * src/io/tokenizer.h:13-22, src/io/tokenizer.cpp:538-561) with the same ids for the same files and text.

@@ -218,6 +218,15 @@ std::vector<float> speed_window() {
     return w;
 }
 
+// ---- output level (q3_audio.h) ----
+void level_check(int gain_cb, int ceiling) {
+    if (gain_cb < kLevelGainMin || gain_cb > kLevelGainMax)
+        throw std::invalid_argument("level: gain " + std::to_string(gain_cb) + " centibels is outside " + std::to_string(kLevelGainMin) + " .. " + std::to_string(kLevelGainMax));
+    if (ceiling < 0 || ceiling > 1000)
+        throw std::invalid_argument("level: ceiling " + std::to_string(ceiling) + " permille is outside 0 .. 1000");
+}
+float level_gain(int gain_cb) { return (float)std::pow(10.0, (double)gain_cb / 200.0); }
+
 // ---------------------------------------------------------------------------------------------
 // log-mel (reference mel.cpp:13-80 filterbank, :182-236 framing).  NOT librosa's: symmetric Hann
 // window, no centre padding, frames = (n - win)/hop + 1 (one zero-padded frame for shorter clips),

@@ -62,6 +62,18 @@ int64_t speed_emitted(int speed, int64_t n_received, bool finished);
 // the window w[i] = 0.5 - 0.5 cos(2 pi i / N), formed in double and rounded to float (kSpeedN entries)
 std::vector<float> speed_window();
 
+// ---- output level: gain and look-ahead limiter at 24 kHz (the arithmetic is fixed in include/q3tts.h) ----
+// gain in centibels (kLevelGainMin .. kLevelGainMax), ceiling in permille (0: gain only; 1 .. 1000: limiter at T = (float)(ceiling /
+// 1000.0)); (0, 0) is no stage.  Look-ahead window W = kLevelW samples; a limiter carries the last kLevelCarry = 2 W - 2 values of v.
+constexpr int kLevelGainMin = -600, kLevelGainMax = 400, kLevelW = 128, kLevelCarry = 2 * kLevelW - 2;
+void level_check(int gain_cb, int ceiling_permille);   // throws std::invalid_argument naming the value that is out of range
+float level_gain(int gain_cb);                         // 10^(gain_cb / 200), formed in double and rounded to float
+inline float level_ceiling(int ceiling_permille) { return (float)((double)ceiling_permille / 1000.0); }
+// outputs a stage has emitted in all after n_received samples: gain only n; limiter unfinished max(0, n - (W - 1)), finished n
+inline int64_t level_emitted(int ceiling_permille, int64_t n_received, bool finished) {
+    return ceiling_permille == 0 || finished ? n_received : std::max<int64_t>(0, n_received - (kLevelW - 1));
+}
+
 struct MelSpec { // the settings of tts_onnx.cpp:347-354
     int sample_rate = 24000, n_fft = 1024, hop = 256, win = 1024, n_mels = 128;
     float fmin = 0.0f, fmax = 12000.0f;

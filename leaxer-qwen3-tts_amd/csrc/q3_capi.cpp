@@ -19,6 +19,7 @@ struct q3tts_engine {
     std::string err;
     q3tts_sink sink = { 0, 0, nullptr, nullptr };   // q3tts_engine_set_sink (sample_rate 0: none)
     int32_t speed = 1000;                           // q3tts_engine_set_speed (1000: none)
+    int32_t gain_cb = 0, ceiling = 0;               // q3tts_engine_set_level ((0, 0): none)
 };
 static std::string g_create_err;
 
@@ -461,6 +462,60 @@ int q3tts_engine_set_speed(q3tts_engine* h, int32_t speed_permille) {
     Q3_API_BEGIN(h)
     try { q3::speed_check(speed_permille); } catch (const std::invalid_argument& ex) { throw q3::Error(std::string("engine_set_speed: ") + ex.what()); }
     h->speed = speed_permille;
+    return 0;
+    Q3_API_END(h)
+}
+
+// ---- output level (include/q3tts.h "output level") ----
+static thread_local std::string g_level_err;
+const char* q3tts_level_last_error(void) { return g_level_err.c_str(); }
+float q3tts_level_gain(int32_t gain_cb) {
+    g_level_err.clear();
+    try {
+        q3::level_check(gain_cb, 0);
+        return q3::level_gain(gain_cb);
+    } catch (const std::exception& ex) { g_level_err = ex.what(); return -1.0f; }
+    catch (...) { g_level_err = "unknown error"; return -1.0f; }
+}
+int64_t q3tts_level_emitted(int32_t gain_cb, int32_t ceiling_permille, int64_t n_received, int finished) {
+    g_level_err.clear();
+    try {
+        q3::level_check(gain_cb, ceiling_permille);
+        if (n_received < 0) throw std::invalid_argument("level: negative sample count " + std::to_string(n_received));
+        return q3::level_emitted(ceiling_permille, n_received, finished != 0);
+    } catch (const std::exception& ex) { g_level_err = ex.what(); return -1; }
+    catch (...) { g_level_err = "unknown error"; return -1; }
+}
+int q3tts_level_begin(q3tts_engine* h, int32_t gain_cb, int32_t ceiling_permille, int* id) {
+    Q3_API_BEGIN(h)
+    if (!id) throw q3::Error("level: NULL argument");
+    *id = h->e->level_begin(gain_cb, ceiling_permille);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_level_push_batch_host(q3tts_engine* h, int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in,
+                                const uint8_t* finish, float* const* out, int64_t cap_samples, int64_t* out_len) {
+    Q3_API_BEGIN(h)
+    h->e->level_push_batch_host(n, ids, pcm24, n_in, finish, out, cap_samples, out_len);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_level_end(q3tts_engine* h, int id) {
+    Q3_API_BEGIN(h)
+    h->e->level_end(id);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_codec_stream_set_level(q3tts_engine* h, int stream_id, int32_t gain_cb, int32_t ceiling_permille) {
+    Q3_API_BEGIN(h)
+    h->e->codec_stream_set_level(stream_id, gain_cb, ceiling_permille);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_engine_set_level(q3tts_engine* h, int32_t gain_cb, int32_t ceiling_permille) {
+    Q3_API_BEGIN(h)
+    try { q3::level_check(gain_cb, ceiling_permille); } catch (const std::invalid_argument& ex) { throw q3::Error(std::string("engine_set_level: ") + ex.what()); }
+    h->gain_cb = gain_cb; h->ceiling = ceiling_permille;
     return 0;
     Q3_API_END(h)
 }
@@ -1126,7 +1181,10 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     // (N + D + Hs input samples), 1000 / S times as long, plus the cut last block
     const int speed = h->speed;
     const bool sped = speed != 1000;
-    const int64_t stage_cap = sped ? ((chunk_cap + q3::kSpeedN + q3::kSpeedD + q3::kSpeedHs) * 1000 + speed - 1) / speed + q3::kSpeedHs : chunk_cap;
+    // with a level (q3tts_engine_set_level) the limiter hands on what it held back as well: at most W - 1 samples more
+    const bool levelled = h->gain_cb != 0 || h->ceiling != 0;
+    const int64_t stage_cap = (sped ? ((chunk_cap + q3::kSpeedN + q3::kSpeedD + q3::kSpeedHs) * 1000 + speed - 1) / speed + q3::kSpeedHs : chunk_cap)
+                              + (h->ceiling != 0 ? q3::kLevelW - 1 : 0);
     const q3::SinkPlan* splan = sunk ? &e.pcm_sink_plan(sink.sample_rate).plan : nullptr;
     const int64_t sink_cap = sunk ? ((stage_cap + splan->half) * splan->L + splan->M - 1) / splan->M + 2 : 0;
     const int64_t chunk_floats = sunk ? (sink_cap * (sink.format == Q3TTS_PCM_S16 ? 2 : 4) + 3) / 4 : stage_cap;   // per slot, 4-byte aligned
@@ -1136,9 +1194,12 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     std::vector<int32_t> final_frames((size_t)B, -1);
     struct SlotSinkScope {   // the slots' implicit streams take the sink for the duration of this call only
         Engine& e;
-        SlotSinkScope(Engine& en, int rate, int fmt, int spd) : e(en) { e.slot_sink_rate = rate; e.slot_sink_format = fmt; e.slot_speed = spd; }
-        ~SlotSinkScope() { e.slot_sink_rate = 0; e.slot_sink_format = 0; e.slot_speed = 0; }
-    } sink_scope(e, sunk && !(sink.sample_rate == 24000 && sink.format == Q3TTS_PCM_F32) ? sink.sample_rate : 0, sink.format, sped ? speed : 0);
+        SlotSinkScope(Engine& en, int rate, int fmt, int spd, int gcb, int ceil) : e(en) {
+            e.slot_sink_rate = rate; e.slot_sink_format = fmt; e.slot_speed = spd; e.slot_gain_cb = gcb; e.slot_ceiling = ceil;
+        }
+        ~SlotSinkScope() { e.slot_sink_rate = 0; e.slot_sink_format = 0; e.slot_speed = 0; e.slot_gain_cb = 0; e.slot_ceiling = 0; }
+    } sink_scope(e, sunk && !(sink.sample_rate == 24000 && sink.format == Q3TTS_PCM_F32) ? sink.sample_rate : 0, sink.format, sped ? speed : 0,
+                 levelled ? h->gain_cb : 0, levelled ? h->ceiling : 0);
     std::vector<int32_t> slots, fb((size_t)B), fe((size_t)B);
     std::vector<int64_t> plen((size_t)B), written((size_t)n_utt, 0);
     std::vector<Engine::SlotInit> init;

@@ -69,7 +69,8 @@ struct CodecW {
     // sink: the stream's PCM sink (Engine::sinks; -1: the stream delivers 24 kHz float); delivered: a push has returned samples
     struct Stream { bool used = false; int cap = 0, P = 0, pshift = 0, n_done = 0, kv_rows = 0, h_cap = 0, h_rows = 0; float* kv = nullptr; float* hpost = nullptr;
                     int sink = -1; bool delivered = false;
-                    int speed = -1; /* the stream's stretcher (Engine::stretchers; -1: none), ahead of its sink */ };
+                    int speed = -1; /* the stream's stretcher (Engine::stretchers; -1: none), ahead of its sink */
+                    int level = -1; /* the stream's level stage (Engine::levelers; -1: none), between the stretcher and the sink */ };
     std::vector<Stream> streams;
     char* stream_arena = nullptr; size_t stream_arena_bytes = 0;
     std::vector<int> slot_stream;          // slot -> stream id (-1: none): q3tts_slot_codec_decode_range_host's implicit stream
@@ -717,7 +718,7 @@ int Engine::codec_stream_begin(int max_frames) {
     S.kv_rows = 0; S.h_rows = 0;                       // nothing of the buffers' previous stream is kept
     codec_stream_fit(sid, std::min(max_frames, 64));
     S.cap = max_frames;
-    S.used = true; S.n_done = 0; S.sink = -1; S.speed = -1; S.delivered = false;
+    S.used = true; S.n_done = 0; S.sink = -1; S.speed = -1; S.level = -1; S.delivered = false;
     int P = 1;
     while (P < max_frames) P <<= 1;
     codec_rope_tables(P);   // positions are absolute in the RoPE tables (grow-only, shared)
@@ -775,6 +776,18 @@ void Engine::codec_stream_end(int sid) {
     codec->streams[(size_t)sid].sink = -1;
     if (codec->streams[(size_t)sid].speed >= 0) speed_end(codec->streams[(size_t)sid].speed);
     codec->streams[(size_t)sid].speed = -1;
+    if (codec->streams[(size_t)sid].level >= 0) level_end(codec->streams[(size_t)sid].level);
+    codec->streams[(size_t)sid].level = -1;
+}
+
+void Engine::codec_stream_set_level(int sid, int gain_cb, int ceiling) {
+    if (!codec || sid < 0 || sid >= (int)codec->streams.size() || !codec->streams[(size_t)sid].used) throw Error("codec_stream_set_level: no such stream");
+    CodecW::Stream& S = codec->streams[(size_t)sid];
+    if (S.delivered) throw Error("codec_stream_set_level: stream " + std::to_string(sid) + " has already delivered samples");
+    try { level_check(gain_cb, ceiling); } catch (const std::invalid_argument& ex) { throw Error(std::string("codec_stream_set_level: ") + ex.what()); }
+    const int id = gain_cb == 0 && ceiling == 0 ? -1 : level_begin(gain_cb, ceiling);   // (0, 0) is "no stage"; a refusal comes before the old stage goes
+    if (S.level >= 0) level_end(S.level);
+    S.level = id;
 }
 
 void Engine::codec_stream_set_speed(int sid, int speed) {
@@ -815,6 +828,7 @@ int64_t Engine::codec_stream_push_dev(int sid, const int32_t* codes_dev, int n, 
     if (n < 1) throw Error("codec_stream_push: no frames");
     if (S.sink >= 0) throw Error("codec_stream_push: stream " + std::to_string(sid) + " has a sink: push it through the batched entry that takes any format");
     if (S.speed >= 0) throw Error("codec_stream_push: stream " + std::to_string(sid) + " has a speed: push it through the batched entry that takes any format");
+    if (S.level >= 0) throw Error("codec_stream_push: stream " + std::to_string(sid) + " has a level: push it through the batched entry that takes any format");
     if (S.n_done + n > S.cap) throw Error("codec_stream_push: more frames than the stream was opened for");
     const int CH = c.cd_hidden, NH = c.cd_heads, HD = c.cd_head_dim, FF = c.cd_ffn;
     const int a0 = S.n_done, b0 = a0 + n, T = n;
@@ -953,6 +967,10 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
     std::vector<SpeedPush> vp((size_t)g_all);    // entry i belongs to ps[i]; id == -1: none
     size_t speed_floats = 0, speed_frames_total = 0;
     int n_speed = 0;
+    // streams with a level: the stage stands behind the stretcher and ahead of the sink, by the same host rules
+    std::vector<LevelPush> lp((size_t)g_all);    // entry i belongs to ps[i]; id == -1: none
+    size_t level_floats = 0;
+    int n_level = 0;
     for (int i = 0; i < g_all; ++i) {
         const StreamPush& q = ps[i];
         const CodecW::Stream& S = W.streams[(size_t)q.sid];
@@ -960,14 +978,22 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
         if (S.speed >= 0) {
             SpeedPush& v = vp[(size_t)i];
             v.id = S.speed; v.n_new = n24; v.finish = q.finish;
-            if (S.sink < 0) { v.out_host = q.pcm; v.cap = q.cap; }
+            if (S.sink < 0 && S.level < 0) { v.out_host = q.pcm; v.cap = q.cap; }
             n24 = speed_push_len(v.id, v.n_new, v.finish);
             speed_floats += speed_out_floats(n24);
             speed_frames_total += (size_t)speed_push_frames(v.id, v.n_new, v.finish);
             ++n_speed;
         }
+        if (S.level >= 0) {
+            LevelPush& l = lp[(size_t)i];
+            l.id = S.level; l.n_new = n24; l.finish = q.finish;
+            if (S.sink < 0) { l.out_host = q.pcm; l.cap = q.cap; }
+            n24 = level_push_len(l.id, l.n_new, l.finish);
+            level_floats += level_out_floats(n24);
+            ++n_level;
+        }
         if (S.sink < 0) {
-            if (q.finish && S.speed < 0) throw Error("codec_stream_push_batch: finish on stream " + std::to_string(q.sid) + ", which has no sink");
+            if (q.finish && S.speed < 0 && S.level < 0) throw Error("codec_stream_push_batch: finish on stream " + std::to_string(q.sid) + ", which has no sink");
             continue;
         }
         SinkPush& k = sp[(size_t)i];
@@ -977,20 +1003,40 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
     }
     if (n_sinks > 0) pcm_sinks_reserve(n_sinks, sink_bytes);
     if (n_speed > 0) speed_reserve(n_speed, speed_floats, speed_frames_total);
+    if (n_level > 0) level_reserve(n_level, level_floats);
     std::vector<SinkPush> sp_run;                // the sinks of one launch, and where each came from
     std::vector<int> sp_src;
     std::vector<SpeedPush> vp_run;               // the same for the stretchers, which launch first
     std::vector<int> vp_src;
+    std::vector<LevelPush> lp_run;               // and for the level stages, which launch between the two
+    std::vector<int> lp_src;
     auto run_sinks = [&]() {
         if (!vp_run.empty()) {
             speed_launch(vp_run.data(), (int)vp_run.size());
             for (size_t k = 0; k < vp_run.size(); ++k) { vp[(size_t)vp_src[k]] = vp_run[k]; ps[vp_src[k]].n_own = vp_run[k].n_out; }
             vp_run.clear(); vp_src.clear();
+            for (size_t k = 0; k < lp_run.size(); ++k) {   // a level stage behind a stretcher reads the stretcher's output where it lies
+                const SpeedPush& v = vp[(size_t)lp_src[k]];
+                if (v.id < 0) continue;
+                if (lp_run[k].n_new != v.n_out) throw Error("codec_stream_push_batch: a level stage's input length does not match its stretcher's push");
+                lp_run[k].x_dev = v.out_dev;
+            }
             for (size_t k = 0; k < sp_run.size(); ++k) {   // a sink behind a stretcher reads the stretcher's output where it lies
                 const SpeedPush& v = vp[(size_t)sp_src[k]];
-                if (v.id < 0) continue;
+                if (v.id < 0 || lp[(size_t)sp_src[k]].id >= 0) continue;
                 if (sp_run[k].n_new != v.n_out) throw Error("codec_stream_push_batch: a sink's input length does not match its stretcher's push");
                 sp_run[k].x_dev = v.out_dev;
+            }
+        }
+        if (!lp_run.empty()) {
+            level_launch(lp_run.data(), (int)lp_run.size());
+            for (size_t k = 0; k < lp_run.size(); ++k) { lp[(size_t)lp_src[k]] = lp_run[k]; ps[lp_src[k]].n_own = lp_run[k].n_out; }
+            lp_run.clear(); lp_src.clear();
+            for (size_t k = 0; k < sp_run.size(); ++k) {   // a sink behind a level stage reads the stage's output where it lies
+                const LevelPush& l = lp[(size_t)sp_src[k]];
+                if (l.id < 0) continue;
+                if (sp_run[k].n_new != l.n_out) throw Error("codec_stream_push_batch: a sink's input length does not match its level stage's push");
+                sp_run[k].x_dev = l.out_dev;
             }
         }
         if (sp_run.empty()) return;
@@ -1000,6 +1046,7 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
     };
     auto commit_sinks = [&]() {
         for (int i = 0; i < g_all; ++i) if (vp[(size_t)i].id >= 0) speed_commit(&vp[(size_t)i], 1);
+        for (int i = 0; i < g_all; ++i) if (lp[(size_t)i].id >= 0) level_commit(&lp[(size_t)i], 1);
         for (int i = 0; i < g_all; ++i) if (sp[(size_t)i].sink >= 0) pcm_sinks_commit(&sp[(size_t)i], 1);
     };
     auto finish_idle = [&]() -> bool {   // streams that finish without new frames: the stretcher's tail, then the sink's
@@ -1007,6 +1054,7 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
         for (int i = 0; i < g_all; ++i) {
             if (ps[i].n != 0 || !ps[i].finish) continue;
             if (vp[(size_t)i].id >= 0) { vp_run.push_back(vp[(size_t)i]); vp_src.push_back(i); any = true; }
+            if (lp[(size_t)i].id >= 0) { lp_run.push_back(lp[(size_t)i]); lp_src.push_back(i); any = true; }
             if (sp[(size_t)i].sink >= 0) { sp_run.push_back(sp[(size_t)i]); sp_src.push_back(i); any = true; }
         }
         return any;
@@ -1154,14 +1202,21 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
                 v.x_dev = pcm_seq + first;
                 vp_run.push_back(v); vp_src.push_back(live[(size_t)i]);
             }
+            const bool levelled = lp[(size_t)live[(size_t)i]].id >= 0;
+            if (levelled) {   // through its level stage, in the group's one launch (run_sinks)
+                LevelPush l = lp[(size_t)live[(size_t)i]];
+                if (!sped && l.n_new != n_own) throw Error("codec_stream_push_batch: a level stage's input length does not match the decoder length formula");
+                l.x_dev = pcm_seq + first;   // behind a stretcher: replaced by the stretcher's output in run_sinks
+                lp_run.push_back(l); lp_src.push_back(live[(size_t)i]);
+            }
             if (sp[(size_t)live[(size_t)i]].sink >= 0) {   // through its sink, in the group's one launch (run_sinks), from where the samples lie
                 SinkPush k = sp[(size_t)live[(size_t)i]];
-                if (!sped && k.n_new != n_own) throw Error("codec_stream_push_batch: a sink's input length does not match the decoder length formula");
+                if (!sped && !levelled && k.n_new != n_own) throw Error("codec_stream_push_batch: a sink's input length does not match the decoder length formula");
                 k.x_dev = pcm_seq + first;   // behind a stretcher: replaced by the stretcher's output in run_sinks
                 sp_run.push_back(k); sp_src.push_back(live[(size_t)i]);
                 return;
             }
-            if (sped) return;
+            if (sped || levelled) return;
             const int64_t m = std::min(n_own, q.cap);
             if (m > 0 && q.pcm) Q3_HIP_CHECK(hipMemcpyAsync(q.pcm, pcm_seq + first, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, stream));
         };
@@ -1183,7 +1238,7 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
     }
     (void)finish_idle();
     run_sinks();
-    if (n_sinks > 0 || n_speed > 0) Q3_HIP_CHECK(hipEventRecord(ev1, stream));   // the push's time includes its sinks
+    if (n_sinks > 0 || n_speed > 0 || n_level > 0) Q3_HIP_CHECK(hipEventRecord(ev1, stream));   // the push's time includes its sinks
     sync();
     Q3_HIP_CHECK(hipEventElapsedTime(&last_codec_ms, ev0, ev1));
     total_codec_ms += last_codec_ms; total_codec_frames += T;
@@ -1192,7 +1247,8 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
         const StreamPush& q = ps[live[(size_t)i]];
         CodecW::Stream& S = W.streams[(size_t)q.sid];
         S.n_done = d.a0 + d.n; S.kv_rows = d.k0 + d.n; S.h_rows = d.h0 + d.n;
-        S.delivered = S.delivered || q.n_own > 0 || (S.sink >= 0 && sp[(size_t)live[(size_t)i]].n_new > 0) || (S.speed >= 0 && vp[(size_t)live[(size_t)i]].n_new > 0);
+        S.delivered = S.delivered || q.n_own > 0 || (S.sink >= 0 && sp[(size_t)live[(size_t)i]].n_new > 0) || (S.speed >= 0 && vp[(size_t)live[(size_t)i]].n_new > 0)
+                      || (S.level >= 0 && lp[(size_t)live[(size_t)i]].n_new > 0);
     }
     commit_sinks();
 }
@@ -1226,6 +1282,8 @@ void Engine::codec_stream_push_batch_host(int n_streams, const int32_t* sids, co
             throw Error("codec_stream_push_batch: stream " + std::to_string(sids[i]) + " has a sink: the float entry serves streams without one");
         if (float_only && sids[i] >= 0 && sids[i] < (int)W.streams.size() && W.streams[(size_t)sids[i]].used && W.streams[(size_t)sids[i]].speed >= 0)
             throw Error("codec_stream_push_batch: stream " + std::to_string(sids[i]) + " has a speed: the float entry serves streams without one");
+        if (float_only && sids[i] >= 0 && sids[i] < (int)W.streams.size() && W.streams[(size_t)sids[i]].used && W.streams[(size_t)sids[i]].level >= 0)
+            throw Error("codec_stream_push_batch: stream " + std::to_string(sids[i]) + " has a level: the float entry serves streams without one");
         if (pcm_len) pcm_len[i] = 0;
     }
     if (W.sbatch_codes_n < total || !W.sbatch_codes) {
@@ -1274,11 +1332,12 @@ void Engine::slots_codec_decode_new(int n_slots, const int32_t* slots, float* co
         // the scheduler's sink: a stream that has delivered nothing yet takes it (a primed stream included: its sink starts from silence)
         if (slot_sink_rate > 0 && W.streams[(size_t)sid].sink < 0 && !W.streams[(size_t)sid].delivered) codec_stream_set_sink(sid, slot_sink_rate, slot_sink_format);
         if (slot_speed > 0 && slot_speed != 1000 && W.streams[(size_t)sid].speed < 0 && !W.streams[(size_t)sid].delivered) codec_stream_set_speed(sid, slot_speed);
+        if ((slot_gain_cb != 0 || slot_ceiling != 0) && W.streams[(size_t)sid].level < 0 && !W.streams[(size_t)sid].delivered) codec_stream_set_level(sid, slot_gain_cb, slot_ceiling);
         const int a = W.streams[(size_t)sid].n_done;
         StreamPush& q = ps[(size_t)i];
         q.sid = sid; q.n = nf - a; q.codes_dev = codes_d + ((size_t)slot * max_frames_cap + a) * c.n_groups;
         q.pcm = pcm_out ? pcm_out[i] : nullptr; q.cap = cap;
-        q.finish = (W.streams[(size_t)sid].sink >= 0 || W.streams[(size_t)sid].speed >= 0) && final_frames && final_frames[i] >= 0 && nf >= final_frames[i];
+        q.finish = (W.streams[(size_t)sid].sink >= 0 || W.streams[(size_t)sid].speed >= 0 || W.streams[(size_t)sid].level >= 0) && final_frames && final_frames[i] >= 0 && nf >= final_frames[i];
         if (frame_begin) frame_begin[i] = a;
         if (frame_end) frame_end[i] = nf;
         if (pcm_len) pcm_len[i] = 0;

@@ -479,6 +479,25 @@ struct SpeedDesc {
 };
 void launch_wsola(const SpeedDesc* tab /* device, [n] */, int n, hipStream_t s);
 
+// ---- output level (q3_level.cpp): gain and look-ahead limiter on 24 kHz float PCM, with carried state ----
+// One stage of one push.  v[k] = g x[k]: for k < n_before the carry holds it (carry_in[j] = v[n_before - kLevelCarry + j]; entries of
+// negative k are never read), for n_before <= k < n_total it is g * x_new[k - n_before]; v[k] = 0 (so r[k] = 1) for k < 0 and k >=
+// n_total, which only a finishing push reaches.  Output i of the launch is the stage's absolute sample out0 + i.  limit == 0: y = v.
+// limit != 0: the header's r, 128-wide minimum, quantisation, 128-wide integer sum, product and clamp; the stage's last workgroup
+// writes v[n_total - kLevelCarry .. n_total) into carry_out, the other of the stage's two carry buffers (keep == 0: the carry stays).
+struct LevelDesc {
+    const float* carry_in = nullptr; float* carry_out = nullptr;
+    const float* x_new = nullptr;       // n_new samples (never null: a push without samples points at the carry)
+    float* out = nullptr;               // n_out samples
+    int64_t n_before = 0, n_total = 0;  // samples received before / with this push
+    int64_t out0 = 0;                   // absolute index of the first new output
+    int32_t n_new = 0, n_out = 0, limit = 0, keep = 0;
+    float g = 1.0f, T = 1.0f;
+};
+constexpr int kLevelTile = 1024;        // outputs of one workgroup
+constexpr int level_tiles(int64_t n_out) { return n_out <= 0 ? 1 : (int)((n_out + kLevelTile - 1) / kLevelTile); }
+void launch_level(const LevelDesc* tab /* device, [n] */, int n, int max_tiles, hipStream_t s);
+
 
 // ---- speaker encoder + GPU audio front end of the clone path (q3_speaker_kernels.hip) ----
 // One reference clip of a batch.  Activations of a batch lie clip after clip along time ([sum T][C]); every kernel that looks across

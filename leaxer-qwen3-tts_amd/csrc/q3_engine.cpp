@@ -444,6 +444,7 @@ Engine::~Engine() {
     if (seg_tab_d) (void)hipFree(seg_tab_d);
     pcm_sink_free();
     speed_free();
+    level_free();
     codec_free();
     speaker_free();
     encoder_free();

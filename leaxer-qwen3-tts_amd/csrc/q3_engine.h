@@ -248,6 +248,38 @@ public:
     // the scheduler's speed (q3tts_engine_set_speed): slots' implicit streams begin with it.  0 or 1000: none
     int slot_speed = 0;
 
+    // ---- output level (q3_level.cpp): gain and look-ahead limiter on 24 kHz float on the device, carried state ----
+    static constexpr int kMaxLevelers = 4096;                        // open at the same time (vocoder streams' included)
+    // mem: a limiter's own allocation, [2][kLevelCarry] floats of carry (the last 254 values of v); a push reads half `cur` and writes
+    // the other, the host flips them when the push has completed.  The counters live here: the host rule needs nothing from the device.
+    // A gain-only stage (ceiling 0) carries nothing.
+    struct Leveler { bool used = false, finished = false; int gain_cb = 0, ceiling = 0, cur = 0; int64_t n_in = 0, n_out = 0; float* mem = nullptr; };
+    std::vector<Leveler> levelers;
+    int level_begin(int gain_cb, int ceiling);
+    void level_end(int id);
+    void level_free();
+    const Leveler& level_get(int id) const;
+    int64_t level_push_len(int id, int64_t n_new, bool finish) const;      // host-only: samples that push would deliver; throws when it would be refused
+    // x_dev: n_new samples on the device; out_host (NULL ok): min(n_out, cap) floats land there.  n_out, out_dev (the push's samples on
+    // the device, valid until the call's next reserve), desc: set by level_launch
+    struct LevelPush { int id = -1; const float* x_dev = nullptr; int64_t n_new = 0; bool finish = false; float* out_host = nullptr; int64_t cap = 0;
+                       int64_t n_out = 0; const float* out_dev = nullptr; int desc = -1; };
+    void level_reserve(int n_total, size_t out_floats_total);        // once per call, before anything is enqueued
+    void level_launch(LevelPush* ps, int n);                         // one launch + the device -> host copies; no stage moves
+    void level_commit(const LevelPush* ps, int n);                   // after the sync: counters advance, carries flip
+    static size_t level_out_floats(int64_t n_out) { return ((size_t)n_out + 63) & ~(size_t)63; }
+    void level_push_batch_host(int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in, const uint8_t* finish,
+                               float* const* out, int64_t cap, int64_t* out_len);
+    LevelDesc* level_desc_d = nullptr; size_t level_desc_cap = 0, level_desc_used = 0;
+    std::vector<LevelDesc> level_desc_h;
+    float* level_out_d = nullptr; size_t level_out_cap = 0, level_out_used = 0;      // packed outputs of a call (grow-only workspace)
+    float* level_in_d = nullptr; size_t level_in_floats = 0;                         // the standalone entry's staged input
+    // vocoder streams: a stream with a level stage delivers its audio through it (codec_stream_push_batch), behind its stretcher and
+    // ahead of its sink if it has them.  Refused once the stream has delivered a sample.  (0, 0): no stage.
+    void codec_stream_set_level(int sid, int gain_cb, int ceiling);
+    // the scheduler's level (q3tts_engine_set_level): slots' implicit streams begin with it.  (0, 0): none
+    int slot_gain_cb = 0, slot_ceiling = 0;
+
     // ---- batch-first session ops on DEVICE pointers (include/q3tts.h "_dev" entry points): row b <-> slot b ----
     // caller stream: the engine's stream first waits for what the caller has enqueued, the caller's stream then waits for the call's work
     void stream_join(hipStream_t caller);

@@ -370,9 +370,62 @@ bool TTSEngine::stretch_push(int id, const float* in, size_t n, bool finish, siz
     return q3tts_speed_push_batch_host(h_, 1, &id, &in, &n_in, &fin, &dst, after - before, &len, nullptr, nullptr) == 0 && len == after - before;
 }
 
+bool TTSEngine::set_level(float gain_db, float ceiling) {
+    if (!ready_) return false;
+    const long G = std::lround(10.0 * (double)gain_db), T = std::lround(1000.0 * (double)ceiling);
+    if (!(gain_db == gain_db) || G < -600 || G > 400) {
+        error_msg_ = "gain " + std::to_string(gain_db) + " dB is outside -60 .. +40";
+        std::cerr << "[TTSEngine] Level: " << error_msg_ << std::endl;
+        return false;
+    }
+    if (!(ceiling == ceiling) || T < 0 || T > 1000 || (ceiling > 0.0f && T == 0)) {
+        error_msg_ = "ceiling " + std::to_string(ceiling) + " is outside 0.001 .. 1.0 (0: no limiter)";
+        std::cerr << "[TTSEngine] Level: " << error_msg_ << std::endl;
+        return false;
+    }
+    if (q3tts_engine_set_level(h_, (int32_t)G, (int32_t)T) != 0) {
+        error_msg_ = q3tts_last_error(h_);
+        std::cerr << "[TTSEngine] Level: " << error_msg_ << std::endl;
+        return false;
+    }
+    gain_cb_ = (int)G; ceiling_ = (int)T;
+    return true;
+}
+
+bool TTSEngine::level_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out) {
+    const int64_t n_in = (int64_t)n;
+    const uint8_t fin = finish ? 1 : 0;
+    const int64_t before = q3tts_level_emitted(gain_cb_, ceiling_, (int64_t)received_before, 0), after = q3tts_level_emitted(gain_cb_, ceiling_, (int64_t)(received_before + n), fin);
+    if (before < 0 || after < before) return false;
+    const size_t have = out.size();
+    out.resize(have + (size_t)(after - before));
+    float* dst = out.data() + have;
+    int64_t len = 0;
+    return q3tts_level_push_batch_host(h_, 1, &id, &in, &n_in, &fin, &dst, after - before, &len) == 0 && len == after - before;
+}
+
+bool TTSEngine::apply_level(std::vector<float>& pcm24) {
+    if (!ready_) return false;
+    if ((gain_cb_ == 0 && ceiling_ == 0) || pcm24.empty()) return true;
+    int id = -1;
+    std::vector<float> out;
+    bool ok = q3tts_level_begin(h_, gain_cb_, ceiling_, &id) == 0;
+    const size_t step = 1440000;   // the most one push takes
+    for (size_t done = 0; ok && done < pcm24.size(); done += step) {
+        const size_t m = std::min(step, pcm24.size() - done);
+        ok = level_push(id, pcm24.data() + done, m, done + m == pcm24.size(), done, out);
+    }
+    if (!ok) std::cerr << "[TTSEngine] Level error: " << q3tts_last_error(h_) << std::endl;
+    if (id >= 0) (void)q3tts_level_end(h_, id);
+    if (ok) pcm24.swap(out); else pcm24.clear();
+    return ok;
+}
+
+// the whole clip through the stretcher and then the level stage (each only when set): every one-shot method ends here
 bool TTSEngine::apply_speed(std::vector<float>& pcm24) {
     if (!ready_) return false;
-    if (speed_ == 1000 || pcm24.empty()) return true;
+    if (pcm24.empty()) return true;
+    if (speed_ == 1000) return apply_level(pcm24);
     int id = -1;
     std::vector<float> out;
     bool ok = q3tts_speed_begin(h_, speed_, &id) == 0;
@@ -384,7 +437,7 @@ bool TTSEngine::apply_speed(std::vector<float>& pcm24) {
     if (!ok) std::cerr << "[TTSEngine] Speed error: " << q3tts_last_error(h_) << std::endl;
     if (id >= 0) (void)q3tts_speed_end(h_, id);
     if (ok) pcm24.swap(out); else pcm24.clear();
-    return ok;
+    return ok && apply_level(pcm24);
 }
 
 bool TTSEngine::has_audio_encoder() const { return h_ && q3tts_has_audio_encoder(h_) != 0; }
@@ -594,7 +647,29 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
     size_t received = 0;
     std::vector<float> fast;
     if (speed_ != 1000 && q3tts_speed_begin(h_, speed_, &stretcher) != 0) return fail();
-    auto fail_s = [&]() { const int rc = fail(); if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher); return rc; };
+    // with a level the chunks (the stretcher's, when there is one) pass a level stage of this call's own in the same way
+    int leveler = -1;
+    size_t levelled = 0;
+    std::vector<float> loud;
+    if ((gain_cb_ != 0 || ceiling_ != 0) && q3tts_level_begin(h_, gain_cb_, ceiling_, &leveler) != 0) {
+        const int rc = fail();
+        if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
+        return rc;
+    }
+    auto fail_s = [&]() {
+        const int rc = fail();
+        if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
+        if (leveler >= 0) (void)q3tts_level_end(h_, leveler);
+        return rc;
+    };
+    auto emit = [&](const float* p, size_t n, bool last) -> bool {   // a chunk at 24 kHz on its way out
+        if (leveler < 0) { if (n > 0) on_audio(p, n); return true; }
+        loud.clear();
+        if (!level_push(leveler, p, n, last, levelled, loud)) return false;
+        levelled += n;
+        if (!loud.empty()) on_audio(loud.data(), loud.size());
+        return true;
+    };
     for (;;) {
         const int want = std::min(chunk_frames, params.max_new_tokens - done);
         const int active = want > 0 ? q3tts_decode_steps(h_, want) : 0;
@@ -610,8 +685,8 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
                 fast.clear();
                 if (!stretch_push(stretcher, pcm.data(), got, false, received, fast)) return fail_s();
                 received += got;
-                if (!fast.empty()) on_audio(fast.data(), fast.size());
-            } else on_audio(pcm.data(), got);
+                if (!emit(fast.data(), fast.size(), false)) return fail_s();
+            } else if (!emit(pcm.data(), got, false)) return fail_s();
             done = nf;
         }
         if (active == 0 || want <= 0) break;
@@ -619,9 +694,10 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
     if (stretcher >= 0) {
         fast.clear();
         if (!stretch_push(stretcher, pcm.data(), 0, true, received, fast)) return fail_s();
-        if (!fast.empty()) on_audio(fast.data(), fast.size());
+        if (!emit(fast.data(), fast.size(), leveler >= 0)) return fail_s();
         (void)q3tts_speed_end(h_, stretcher);
-    }
+    } else if (leveler >= 0 && !emit(pcm.data(), 0, true)) return fail_s();
+    if (leveler >= 0) (void)q3tts_level_end(h_, leveler);
     (void)q3tts_slot_release(h_, 0);
     return done;
 }

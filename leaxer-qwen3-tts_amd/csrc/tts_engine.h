@@ -183,7 +183,17 @@ public:
     // get_error(), naming the range) for a speed the engine refuses.
     bool set_speed(float speed);
     int speed_permille() const { return speed_; }
-    bool apply_speed(std::vector<float>& pcm24);   // the whole clip through the stage, in place; speed 1.0 leaves it as it is
+    bool apply_speed(std::vector<float>& pcm24);   // the whole clip through the stage, in place; speed 1.0 leaves it as it is; then apply_level
+    // Output level (include/q3tts.h: q3tts_engine_set_level, q3tts_level_*; the reference has no volume control).  gain_db decibels of
+    // gain, rounded to centibels (-60 .. +40); ceiling the limiter's linear ceiling, rounded to permille (0: gain only; otherwise 0.001 ..
+    // 1.0); (0, 0) is no stage at all.  The stage stands behind the stretcher and ahead of the sink on every path that honours
+    // set_speed, in the same way: inside the scheduler's streaming pushes, as a stage of its own behind synthesize_tokens_streaming's
+    // chunks, over the whole clip in the one-shot methods (apply_level, which apply_speed calls last).  false (and get_error(), naming
+    // the range) for values the engine refuses.
+    bool set_level(float gain_db, float ceiling);
+    int gain_centibels() const { return gain_cb_; }
+    int ceiling_permille() const { return ceiling_; }
+    bool apply_level(std::vector<float>& pcm24);   // the whole clip through the stage, in place; (0, 0) leaves it as it is
     bool has_audio_encoder() const;
     int n_groups() const { return n_groups_; }
     bool has_speaker_encoder() const; // true when the weight file carries the spk.* tensors (reference: speaker_encoder.onnx present)
@@ -207,6 +217,8 @@ private:
     bool out_pcm16_ = false;
     std::function<int(int, const void*, int64_t, int)> sink_fn_;   // the running streaming call's delivery, while an output format is set
     int speed_ = 1000;
+    int gain_cb_ = 0, ceiling_ = 0;
+    bool level_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);
     // one push of a stretcher of this engine: out receives the push's samples (appended)
     bool stretch_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);
     bool sink_on() const { return out_rate_ != config::SAMPLE_RATE || out_pcm16_; }
