@@ -950,6 +950,8 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
     std::vector<int64_t> hold_mark((size_t)n_utt, 0);
     int64_t n_retired = 0;
     e.sched_admitted = e.sched_preempted = 0; e.sched_peak_live = 0;
+    const char* const quantum_env = getenv("Q3TTS_SCHED_QUANTUM");
+    const int quantum = quantum_env ? std::max(1, atoi(quantum_env)) : 4;
     try {
         while (!pending.empty() || live > 0) {
             fresh.clear();
@@ -1003,7 +1005,7 @@ static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* i
             // (with EOS suppressed nothing can finish earlier than that, so the look-ahead only bounds how long the host is away)
             // While utterances wait in the queue a look is at least `quantum` steps away: a finished slot idles a few (masked, nearly free)
             // steps, and the slots that finish within the quantum are re-armed together, sharing one prefill pass.
-            static const int quantum = getenv("Q3TTS_SCHED_QUANTUM") ? std::max(1, atoi(getenv("Q3TTS_SCHED_QUANTUM"))) : 4;
+            // (Q3TTS_SCHED_QUANTUM is read above, once per job: a process can run jobs at more than one quantum)
             const int look = std::min(rem, ignore_eos ? 64 : (live <= 16 ? 4 : 8));
             const int steps = std::max(!pending.empty() && live > 16 ? quantum : 1, look);
             if (!reserve_all) {
