@@ -371,20 +371,20 @@ int64_t q3tts_sink_emitted(int32_t rate, int64_t n_received, int finished) {
 int q3tts_pcm_sink_begin(q3tts_engine* h, int32_t sample_rate, int format, int* sink_id) {
     Q3_API_BEGIN(h)
     if (!sink_id) throw q3::Error("pcm sink: NULL argument");
-    *sink_id = h->e->pcm_sink_begin(sample_rate, format);
+    *sink_id = h->e->sink.begin(sample_rate, format);
     return 0;
     Q3_API_END(h)
 }
 int q3tts_pcm_sink_push_batch_host(q3tts_engine* h, int n, const int32_t* sink_ids, const float* const* pcm24, const int64_t* n_in,
                                    const uint8_t* finish, void* const* out, int64_t cap_samples, int64_t* out_len) {
     Q3_API_BEGIN(h)
-    h->e->pcm_sink_push_batch_host(n, sink_ids, pcm24, n_in, finish, out, cap_samples, out_len);
+    h->e->sink.push_batch_host(n, sink_ids, pcm24, n_in, finish, out, cap_samples, out_len);
     return 0;
     Q3_API_END(h)
 }
 int q3tts_pcm_sink_end(q3tts_engine* h, int sink_id) {
     Q3_API_BEGIN(h)
-    h->e->pcm_sink_end(sink_id);
+    h->e->sink.end(sink_id);
     return 0;
     Q3_API_END(h)
 }
@@ -406,7 +406,7 @@ int q3tts_engine_set_sink(q3tts_engine* h, const q3tts_sink* sink) {
     if (!sink) { h->sink = q3tts_sink{ 0, 0, nullptr, nullptr }; return 0; }
     if (sink->format != Q3TTS_PCM_F32 && sink->format != Q3TTS_PCM_S16) throw q3::Error("engine_set_sink: format " + std::to_string(sink->format) + " is neither Q3TTS_PCM_F32 nor Q3TTS_PCM_S16");
     if (!sink->cb) throw q3::Error("engine_set_sink: null callback");
-    (void)h->e->pcm_sink_plan(sink->sample_rate);   // refuses a bad rate by name, and has the table uploaded before the first utterance
+    (void)h->e->sink.plan_for(sink->sample_rate);   // refuses a bad rate by name, and has the table uploaded before the first utterance
     h->sink = *sink;
     return 0;
     Q3_API_END(h)
@@ -434,7 +434,7 @@ int q3tts_speed_window(float* table, int64_t cap) {
 int q3tts_speed_begin(q3tts_engine* h, int32_t speed_permille, int* id) {
     Q3_API_BEGIN(h)
     if (!id) throw q3::Error("speed: NULL argument");
-    *id = h->e->speed_begin(speed_permille);
+    *id = h->e->speed.begin(speed_permille);
     return 0;
     Q3_API_END(h)
 }
@@ -442,13 +442,13 @@ int q3tts_speed_push_batch_host(q3tts_engine* h, int n, const int32_t* ids, cons
                                 const uint8_t* finish, float* const* out, int64_t cap_samples, int64_t* out_len,
                                 int32_t* const* offsets_out, int64_t* n_offsets) {
     Q3_API_BEGIN(h)
-    h->e->speed_push_batch_host(n, ids, pcm24, n_in, finish, out, cap_samples, out_len, offsets_out, n_offsets);
+    h->e->speed.push_batch_host(n, ids, pcm24, n_in, finish, (void* const*)out, cap_samples, out_len, offsets_out, n_offsets);
     return 0;
     Q3_API_END(h)
 }
 int q3tts_speed_end(q3tts_engine* h, int id) {
     Q3_API_BEGIN(h)
-    h->e->speed_end(id);
+    h->e->speed.end(id);
     return 0;
     Q3_API_END(h)
 }
@@ -489,20 +489,20 @@ int64_t q3tts_level_emitted(int32_t gain_cb, int32_t ceiling_permille, int64_t n
 int q3tts_level_begin(q3tts_engine* h, int32_t gain_cb, int32_t ceiling_permille, int* id) {
     Q3_API_BEGIN(h)
     if (!id) throw q3::Error("level: NULL argument");
-    *id = h->e->level_begin(gain_cb, ceiling_permille);
+    *id = h->e->level.begin(gain_cb, ceiling_permille);
     return 0;
     Q3_API_END(h)
 }
 int q3tts_level_push_batch_host(q3tts_engine* h, int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in,
                                 const uint8_t* finish, float* const* out, int64_t cap_samples, int64_t* out_len) {
     Q3_API_BEGIN(h)
-    h->e->level_push_batch_host(n, ids, pcm24, n_in, finish, out, cap_samples, out_len);
+    h->e->level.push_batch_host(n, ids, pcm24, n_in, finish, (void* const*)out, cap_samples, out_len);
     return 0;
     Q3_API_END(h)
 }
 int q3tts_level_end(q3tts_engine* h, int id) {
     Q3_API_BEGIN(h)
-    h->e->level_end(id);
+    h->e->level.end(id);
     return 0;
     Q3_API_END(h)
 }
@@ -1187,21 +1187,19 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     const bool levelled = h->gain_cb != 0 || h->ceiling != 0;
     const int64_t stage_cap = (sped ? ((chunk_cap + q3::kSpeedN + q3::kSpeedD + q3::kSpeedHs) * 1000 + speed - 1) / speed + q3::kSpeedHs : chunk_cap)
                               + (h->ceiling != 0 ? q3::kLevelW - 1 : 0);
-    const q3::SinkPlan* splan = sunk ? &e.pcm_sink_plan(sink.sample_rate).plan : nullptr;
+    const q3::SinkPlan* splan = sunk ? &e.sink.plan_for(sink.sample_rate).plan : nullptr;
     const int64_t sink_cap = sunk ? ((stage_cap + splan->half) * splan->L + splan->M - 1) / splan->M + 2 : 0;
     const int64_t chunk_floats = sunk ? (sink_cap * (sink.format == Q3TTS_PCM_S16 ? 2 : 4) + 3) / 4 : stage_cap;   // per slot, 4-byte aligned
     const int64_t deliver_cap = sunk ? sink_cap : stage_cap;
     std::vector<float> chunk_pcm((size_t)B * chunk_floats);
     std::vector<float*> pcm_ptr((size_t)B);
     std::vector<int32_t> final_frames((size_t)B, -1);
-    struct SlotSinkScope {   // the slots' implicit streams take the sink for the duration of this call only
+    struct SlotStagesScope {   // the slots' implicit streams take the stages for the duration of this call only
         Engine& e;
-        SlotSinkScope(Engine& en, int rate, int fmt, int spd, int gcb, int ceil) : e(en) {
-            e.slot_sink_rate = rate; e.slot_sink_format = fmt; e.slot_speed = spd; e.slot_gain_cb = gcb; e.slot_ceiling = ceil;
-        }
-        ~SlotSinkScope() { e.slot_sink_rate = 0; e.slot_sink_format = 0; e.slot_speed = 0; e.slot_gain_cb = 0; e.slot_ceiling = 0; }
-    } sink_scope(e, sunk && !(sink.sample_rate == 24000 && sink.format == Q3TTS_PCM_F32) ? sink.sample_rate : 0, sink.format, sped ? speed : 0,
-                 levelled ? h->gain_cb : 0, levelled ? h->ceiling : 0);
+        SlotStagesScope(Engine& en, const Engine::SlotStages& s) : e(en) { e.slot_stages = s; }
+        ~SlotStagesScope() { e.slot_stages = Engine::SlotStages(); }
+    } stages_scope(e, Engine::SlotStages{ sunk && !(sink.sample_rate == 24000 && sink.format == Q3TTS_PCM_F32) ? sink.sample_rate : 0, sink.format,
+                                          sped ? speed : 0, levelled ? h->gain_cb : 0, levelled ? h->ceiling : 0 });
     std::vector<int32_t> slots, fb((size_t)B), fe((size_t)B);
     std::vector<int64_t> plen((size_t)B), written((size_t)n_utt, 0);
     std::vector<Engine::SlotInit> init;

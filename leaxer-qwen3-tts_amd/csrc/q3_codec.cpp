@@ -66,11 +66,12 @@ struct CodecW {
     // max_ctx 2112).  kv: [layer][k | v][head][P][d] with P = pow2 >= 2 (window - 1) + the largest push so far; `kv_rows` rows are stored,
     // the last of them position n_done - 1; when a push would not fit, the newest window - 1 rows move to the front (the only ones a
     // later query can reach).  hpost: [h_cap][hidden], `h_rows` stored, the newest codec_stage_b_context() rows kept the same way.
-    // sink: the stream's PCM sink (Engine::sinks; -1: the stream delivers 24 kHz float); delivered: a push has returned samples
+    // stage: the stream's stages by Engine::StageKind, in the order its audio passes them (ids of Engine::stages[k]; -1: none, all -1:
+    // the stream delivers 24 kHz float); delivered: a push has returned samples
     struct Stream { bool used = false; int cap = 0, P = 0, pshift = 0, n_done = 0, kv_rows = 0, h_cap = 0, h_rows = 0; float* kv = nullptr; float* hpost = nullptr;
-                    int sink = -1; bool delivered = false;
-                    int speed = -1; /* the stream's stretcher (Engine::stretchers; -1: none), ahead of its sink */
-                    int level = -1; /* the stream's level stage (Engine::levelers; -1: none), between the stretcher and the sink */ };
+                    int stage[Engine::SK_N] = { -1, -1, -1 }; bool delivered = false;
+                    const char* has() const {   // what the float entries refuse the stream by; nullptr: no stage
+                        return stage[Engine::SK_SINK] >= 0 ? " has a sink" : stage[Engine::SK_SPEED] >= 0 ? " has a speed" : stage[Engine::SK_LEVEL] >= 0 ? " has a level" : nullptr; } };
     std::vector<Stream> streams;
     char* stream_arena = nullptr; size_t stream_arena_bytes = 0;
     std::vector<int> slot_stream;          // slot -> stream id (-1: none): q3tts_slot_codec_decode_range_host's implicit stream
@@ -718,7 +719,8 @@ int Engine::codec_stream_begin(int max_frames) {
     S.kv_rows = 0; S.h_rows = 0;                       // nothing of the buffers' previous stream is kept
     codec_stream_fit(sid, std::min(max_frames, 64));
     S.cap = max_frames;
-    S.used = true; S.n_done = 0; S.sink = -1; S.speed = -1; S.level = -1; S.delivered = false;
+    S.used = true; S.n_done = 0; S.delivered = false;
+    for (int& id : S.stage) id = -1;
     int P = 1;
     while (P < max_frames) P <<= 1;
     codec_rope_tables(P);   // positions are absolute in the RoPE tables (grow-only, shared)
@@ -768,67 +770,60 @@ void Engine::codec_stream_fit(int sid, int n) {
     }
 }
 
+static CodecW::Stream& open_stream(CodecW* W, int sid, const char* fn) {   // the open stream behind an id, or fn's refusal
+    if (!W || sid < 0 || sid >= (int)W->streams.size() || !W->streams[(size_t)sid].used) throw Error(std::string(fn) + ": no such stream");
+    return W->streams[(size_t)sid];
+}
+
 void Engine::codec_stream_end(int sid) {
-    if (!codec || sid < 0 || sid >= (int)codec->streams.size() || !codec->streams[(size_t)sid].used) throw Error("codec_stream_end: no such stream");
-    codec->streams[(size_t)sid].used = false;        // buffers are kept for the next stream of this size
-    codec->streams[(size_t)sid].n_done = 0;
-    if (codec->streams[(size_t)sid].sink >= 0) pcm_sink_end(codec->streams[(size_t)sid].sink);
-    codec->streams[(size_t)sid].sink = -1;
-    if (codec->streams[(size_t)sid].speed >= 0) speed_end(codec->streams[(size_t)sid].speed);
-    codec->streams[(size_t)sid].speed = -1;
-    if (codec->streams[(size_t)sid].level >= 0) level_end(codec->streams[(size_t)sid].level);
-    codec->streams[(size_t)sid].level = -1;
+    CodecW::Stream& S = open_stream(codec, sid, "codec_stream_end");
+    S.used = false;        // buffers are kept for the next stream of this size
+    S.n_done = 0;
+    for (int k = 0; k < SK_N; ++k) {
+        if (S.stage[k] >= 0) stages[k]->end(S.stage[k]);
+        S.stage[k] = -1;
+    }
+}
+
+// The setters: the stream must not have delivered a sample; `make` begins the new stage or returns -1 for the "no stage" values, and a
+// refusal of it comes before the old stage goes.
+static void stream_set_stage(Engine& e, int sid, const char* fn, int kind, const std::function<int()>& make) {
+    CodecW::Stream& S = open_stream(e.codec, sid, fn);
+    if (S.delivered) throw Error(std::string(fn) + ": stream " + std::to_string(sid) + " has already delivered samples");
+    const int id = make();
+    if (S.stage[kind] >= 0) e.stages[kind]->end(S.stage[kind]);
+    S.stage[kind] = id;
 }
 
 void Engine::codec_stream_set_level(int sid, int gain_cb, int ceiling) {
-    if (!codec || sid < 0 || sid >= (int)codec->streams.size() || !codec->streams[(size_t)sid].used) throw Error("codec_stream_set_level: no such stream");
-    CodecW::Stream& S = codec->streams[(size_t)sid];
-    if (S.delivered) throw Error("codec_stream_set_level: stream " + std::to_string(sid) + " has already delivered samples");
-    try { level_check(gain_cb, ceiling); } catch (const std::invalid_argument& ex) { throw Error(std::string("codec_stream_set_level: ") + ex.what()); }
-    const int id = gain_cb == 0 && ceiling == 0 ? -1 : level_begin(gain_cb, ceiling);   // (0, 0) is "no stage"; a refusal comes before the old stage goes
-    if (S.level >= 0) level_end(S.level);
-    S.level = id;
+    stream_set_stage(*this, sid, "codec_stream_set_level", SK_LEVEL, [&] {
+        try { level_check(gain_cb, ceiling); } catch (const std::invalid_argument& ex) { throw Error(std::string("codec_stream_set_level: ") + ex.what()); }
+        return gain_cb == 0 && ceiling == 0 ? -1 : level.begin(gain_cb, ceiling);
+    });
 }
 
-void Engine::codec_stream_set_speed(int sid, int speed) {
-    if (!codec || sid < 0 || sid >= (int)codec->streams.size() || !codec->streams[(size_t)sid].used) throw Error("codec_stream_set_speed: no such stream");
-    CodecW::Stream& S = codec->streams[(size_t)sid];
-    if (S.delivered) throw Error("codec_stream_set_speed: stream " + std::to_string(sid) + " has already delivered samples");
-    const int id = speed == 1000 ? -1 : speed_begin(speed);   // 1000 is "no stage"; a bad speed throws before the old stretcher goes
-    if (S.speed >= 0) speed_end(S.speed);
-    S.speed = id;
+void Engine::codec_stream_set_speed(int sid, int speed_permille) {
+    stream_set_stage(*this, sid, "codec_stream_set_speed", SK_SPEED, [&] { return speed_permille == 1000 ? -1 : speed.begin(speed_permille); });
 }
 
 void Engine::codec_stream_set_sink(int sid, int rate, int format) {
-    if (!codec || sid < 0 || sid >= (int)codec->streams.size() || !codec->streams[(size_t)sid].used) throw Error("codec_stream_set_sink: no such stream");
-    CodecW::Stream& S = codec->streams[(size_t)sid];
-    if (S.delivered) throw Error("codec_stream_set_sink: stream " + std::to_string(sid) + " has already delivered samples");
-    if (format != Q3TTS_PCM_F32 && format != Q3TTS_PCM_S16) throw Error("codec_stream_set_sink: format " + std::to_string(format) + " is neither Q3TTS_PCM_F32 nor Q3TTS_PCM_S16");
-    const int id = rate == 24000 && format == Q3TTS_PCM_F32 ? -1 : pcm_sink_begin(rate, format);   // 24 kHz float is "no sink"; a bad rate throws before the old sink goes
-    if (S.sink >= 0) pcm_sink_end(S.sink);
-    S.sink = id;
-}
-
-int Engine::codec_stream_sink(int sid) const {
-    if (!codec || sid < 0 || sid >= (int)codec->streams.size() || !codec->streams[(size_t)sid].used) throw Error("codec_stream: no such stream");
-    return codec->streams[(size_t)sid].sink;
+    stream_set_stage(*this, sid, "codec_stream_set_sink", SK_SINK, [&] {
+        if (format != Q3TTS_PCM_F32 && format != Q3TTS_PCM_S16) throw Error("codec_stream_set_sink: format " + std::to_string(format) + " is neither Q3TTS_PCM_F32 nor Q3TTS_PCM_S16");
+        return rate == 24000 && format == Q3TTS_PCM_F32 ? -1 : sink.begin(rate, format);
+    });
 }
 
 int Engine::codec_stream_frames(int sid) const {
-    if (!codec || sid < 0 || sid >= (int)codec->streams.size() || !codec->streams[(size_t)sid].used) throw Error("codec_stream: no such stream");
-    return codec->streams[(size_t)sid].n_done;
+    return open_stream(codec, sid, "codec_stream").n_done;
 }
 
 // n new frames (codes_dev: int32 [n][n_groups] on the device) -> the samples they own, *pcm_dev pointing into the engine's decode arena
 // (valid until the next decode on the engine's stream); returns the sample count
 int64_t Engine::codec_stream_push_dev(int sid, const int32_t* codes_dev, int n, float** pcm_dev) {
-    if (!codec || sid < 0 || sid >= (int)codec->streams.size() || !codec->streams[(size_t)sid].used) throw Error("codec_stream_push: no such stream");
+    CodecW::Stream& S = open_stream(codec, sid, "codec_stream_push");
     CodecW& W = *codec;
-    CodecW::Stream& S = W.streams[(size_t)sid];
     if (n < 1) throw Error("codec_stream_push: no frames");
-    if (S.sink >= 0) throw Error("codec_stream_push: stream " + std::to_string(sid) + " has a sink: push it through the batched entry that takes any format");
-    if (S.speed >= 0) throw Error("codec_stream_push: stream " + std::to_string(sid) + " has a speed: push it through the batched entry that takes any format");
-    if (S.level >= 0) throw Error("codec_stream_push: stream " + std::to_string(sid) + " has a level: push it through the batched entry that takes any format");
+    if (S.has()) throw Error("codec_stream_push: stream " + std::to_string(sid) + S.has() + ": push it through the batched entry that takes any format");
     if (S.n_done + n > S.cap) throw Error("codec_stream_push: more frames than the stream was opened for");
     const int CH = c.cd_hidden, NH = c.cd_heads, HD = c.cd_head_dim, FF = c.cd_ffn;
     const int a0 = S.n_done, b0 = a0 + n, T = n;
@@ -958,113 +953,75 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
         if (q.n > 0 && !q.codes_dev) throw Error("codec_stream_push_batch: null codes");
         if (q.n > 0) live.push_back(i);
     }
-    // streams with a sink: their pushes' lengths by the host rule (which refuses a finished or full sink), before anything moves
+    // streams with stages: their pushes' lengths by the host rules (which refuse a finished or full stage), before anything moves.  A
+    // stage's input is the push of the stream's nearest earlier stage, or the vocoder's; only the last one delivers to the caller.
     auto len_all = [&](int nfr) -> int64_t { return nfr <= 0 ? 0 : q3tts_codec_decode_len(&c, nfr); };
-    std::vector<SinkPush> sp((size_t)g_all);     // entry i belongs to ps[i]; sink == -1: none
-    size_t sink_bytes = 0;
-    int n_sinks = 0;
-    // streams with a speed: the stretcher stands ahead of the sink, whose input is then the stretcher's push (the same host rules)
-    std::vector<SpeedPush> vp((size_t)g_all);    // entry i belongs to ps[i]; id == -1: none
-    size_t speed_floats = 0, speed_frames_total = 0;
-    int n_speed = 0;
-    // streams with a level: the stage stands behind the stretcher and ahead of the sink, by the same host rules
-    std::vector<LevelPush> lp((size_t)g_all);    // entry i belongs to ps[i]; id == -1: none
-    size_t level_floats = 0;
-    int n_level = 0;
+    std::vector<StagePush> sp[SK_N];             // sp[k][i] belongs to ps[i]; id == -1: stream i has no stage of kind k
+    size_t st_out[SK_N] = {}, st_offs[SK_N] = {};
+    int st_n[SK_N] = {}, st_any = 0;
+    for (int k = 0; k < SK_N; ++k) sp[k].assign((size_t)g_all, StagePush());
     for (int i = 0; i < g_all; ++i) {
         const StreamPush& q = ps[i];
         const CodecW::Stream& S = W.streams[(size_t)q.sid];
         int64_t n24 = len_all(S.n_done + q.n) - len_all(S.n_done);
-        if (S.speed >= 0) {
-            SpeedPush& v = vp[(size_t)i];
-            v.id = S.speed; v.n_new = n24; v.finish = q.finish;
-            if (S.sink < 0 && S.level < 0) { v.out_host = q.pcm; v.cap = q.cap; }
-            n24 = speed_push_len(v.id, v.n_new, v.finish);
-            speed_floats += speed_out_floats(n24);
-            speed_frames_total += (size_t)speed_push_frames(v.id, v.n_new, v.finish);
-            ++n_speed;
+        int last = -1;
+        for (int k = 0; k < SK_N; ++k) {
+            if (S.stage[k] < 0) continue;
+            StagePush& v = sp[k][(size_t)i];
+            v.id = S.stage[k]; v.n_new = n24; v.finish = q.finish;
+            st_out[k] += stages[k]->plan(v); st_offs[k] += (size_t)v.n_frames;
+            ++st_n[k]; ++st_any;
+            n24 = v.n_out; last = k;
         }
-        if (S.level >= 0) {
-            LevelPush& l = lp[(size_t)i];
-            l.id = S.level; l.n_new = n24; l.finish = q.finish;
-            if (S.sink < 0) { l.out_host = q.pcm; l.cap = q.cap; }
-            n24 = level_push_len(l.id, l.n_new, l.finish);
-            level_floats += level_out_floats(n24);
-            ++n_level;
-        }
-        if (S.sink < 0) {
-            if (q.finish && S.speed < 0 && S.level < 0) throw Error("codec_stream_push_batch: finish on stream " + std::to_string(q.sid) + ", which has no sink");
+        if (last < 0) {
+            if (q.finish) throw Error("codec_stream_push_batch: finish on stream " + std::to_string(q.sid) + ", which has no sink");
             continue;
         }
-        SinkPush& k = sp[(size_t)i];
-        k.sink = S.sink; k.n_new = n24; k.finish = q.finish; k.out_host = q.pcm; k.cap = q.cap;
-        sink_bytes += pcm_sink_out_bytes(k.sink, k.n_new, k.finish);
-        ++n_sinks;
+        sp[last][(size_t)i].out_host = q.pcm; sp[last][(size_t)i].cap = q.cap;
     }
-    if (n_sinks > 0) pcm_sinks_reserve(n_sinks, sink_bytes);
-    if (n_speed > 0) speed_reserve(n_speed, speed_floats, speed_frames_total);
-    if (n_level > 0) level_reserve(n_level, level_floats);
-    std::vector<SinkPush> sp_run;                // the sinks of one launch, and where each came from
-    std::vector<int> sp_src;
-    std::vector<SpeedPush> vp_run;               // the same for the stretchers, which launch first
-    std::vector<int> vp_src;
-    std::vector<LevelPush> lp_run;               // and for the level stages, which launch between the two
-    std::vector<int> lp_src;
-    auto run_sinks = [&]() {
-        if (!vp_run.empty()) {
-            speed_launch(vp_run.data(), (int)vp_run.size());
-            for (size_t k = 0; k < vp_run.size(); ++k) { vp[(size_t)vp_src[k]] = vp_run[k]; ps[vp_src[k]].n_own = vp_run[k].n_out; }
-            vp_run.clear(); vp_src.clear();
-            for (size_t k = 0; k < lp_run.size(); ++k) {   // a level stage behind a stretcher reads the stretcher's output where it lies
-                const SpeedPush& v = vp[(size_t)lp_src[k]];
-                if (v.id < 0) continue;
-                if (lp_run[k].n_new != v.n_out) throw Error("codec_stream_push_batch: a level stage's input length does not match its stretcher's push");
-                lp_run[k].x_dev = v.out_dev;
-            }
-            for (size_t k = 0; k < sp_run.size(); ++k) {   // a sink behind a stretcher reads the stretcher's output where it lies
-                const SpeedPush& v = vp[(size_t)sp_src[k]];
-                if (v.id < 0 || lp[(size_t)sp_src[k]].id >= 0) continue;
-                if (sp_run[k].n_new != v.n_out) throw Error("codec_stream_push_batch: a sink's input length does not match its stretcher's push");
-                sp_run[k].x_dev = v.out_dev;
+    for (int k = 0; k < SK_N; ++k) if (st_n[k] > 0) stages[k]->reserve(st_n[k], st_out[k], st_offs[k]);
+    auto prev_stage = [&](int k, int i) { do --k; while (k >= 0 && sp[k][(size_t)i].id < 0); return k; };   // stream i's nearest stage ahead of kind k; -1: the vocoder
+    std::vector<StagePush> run[SK_N];            // per kind the pushes of one launch, and where each came from
+    std::vector<int> src[SK_N];
+    auto run_stages = [&]() {                    // at most one launch per kind, in the stages' order
+        for (int k = 0; k < SK_N; ++k) {
+            if (run[k].empty()) continue;
+            stages[k]->launch(run[k].data(), (int)run[k].size());
+            for (size_t j = 0; j < run[k].size(); ++j) { sp[k][(size_t)src[k][j]] = run[k][j]; ps[src[k][j]].n_own = run[k][j].n_out; }
+            run[k].clear(); src[k].clear();
+            for (int m = k + 1; m < SK_N; ++m) for (size_t j = 0; j < run[m].size(); ++j) {   // the stage behind this one reads its output where it lies
+                const int i = src[m][j];
+                if (prev_stage(m, i) != k) continue;
+                if (run[m][j].n_new != sp[k][(size_t)i].n_out)
+                    throw Error(std::string("codec_stream_push_batch: a ") + stages[m]->noun + "'s input length does not match its " + stages[k]->noun + "'s push");
+                run[m][j].x_dev = sp[k][(size_t)i].out_dev;
             }
         }
-        if (!lp_run.empty()) {
-            level_launch(lp_run.data(), (int)lp_run.size());
-            for (size_t k = 0; k < lp_run.size(); ++k) { lp[(size_t)lp_src[k]] = lp_run[k]; ps[lp_src[k]].n_own = lp_run[k].n_out; }
-            lp_run.clear(); lp_src.clear();
-            for (size_t k = 0; k < sp_run.size(); ++k) {   // a sink behind a level stage reads the stage's output where it lies
-                const LevelPush& l = lp[(size_t)sp_src[k]];
-                if (l.id < 0) continue;
-                if (sp_run[k].n_new != l.n_out) throw Error("codec_stream_push_batch: a sink's input length does not match its level stage's push");
-                sp_run[k].x_dev = l.out_dev;
-            }
-        }
-        if (sp_run.empty()) return;
-        pcm_sinks_launch(sp_run.data(), (int)sp_run.size());
-        for (size_t k = 0; k < sp_run.size(); ++k) { sp[(size_t)sp_src[k]] = sp_run[k]; ps[sp_src[k]].n_own = sp_run[k].n_out; }
-        sp_run.clear(); sp_src.clear();
     };
-    auto commit_sinks = [&]() {
-        for (int i = 0; i < g_all; ++i) if (vp[(size_t)i].id >= 0) speed_commit(&vp[(size_t)i], 1);
-        for (int i = 0; i < g_all; ++i) if (lp[(size_t)i].id >= 0) level_commit(&lp[(size_t)i], 1);
-        for (int i = 0; i < g_all; ++i) if (sp[(size_t)i].sink >= 0) pcm_sinks_commit(&sp[(size_t)i], 1);
+    auto commit_stages = [&]() {
+        for (int k = 0; k < SK_N; ++k) for (int i = 0; i < g_all; ++i) if (sp[k][(size_t)i].id >= 0) stages[k]->commit(&sp[k][(size_t)i], 1);
     };
-    auto finish_idle = [&]() -> bool {   // streams that finish without new frames: the stretcher's tail, then the sink's
+    auto queue_stages = [&](int i, const float* x_dev) -> bool {   // stream i's stages join the next launches; x_dev feeds the first of them
         bool any = false;
-        for (int i = 0; i < g_all; ++i) {
-            if (ps[i].n != 0 || !ps[i].finish) continue;
-            if (vp[(size_t)i].id >= 0) { vp_run.push_back(vp[(size_t)i]); vp_src.push_back(i); any = true; }
-            if (lp[(size_t)i].id >= 0) { lp_run.push_back(lp[(size_t)i]); lp_src.push_back(i); any = true; }
-            if (sp[(size_t)i].sink >= 0) { sp_run.push_back(sp[(size_t)i]); sp_src.push_back(i); any = true; }
+        for (int k = 0; k < SK_N; ++k) {
+            if (sp[k][(size_t)i].id < 0) continue;
+            run[k].push_back(sp[k][(size_t)i]); src[k].push_back(i);
+            run[k].back().x_dev = x_dev;         // behind another stage: replaced by that stage's output in run_stages
+            any = true;
         }
         return any;
     };
+    auto finish_idle = [&]() -> bool {   // streams that finish without new frames: each stage's tail, in the stages' order
+        bool any = false;
+        for (int i = 0; i < g_all; ++i) if (ps[i].n == 0 && ps[i].finish && queue_stages(i, nullptr)) any = true;
+        return any;
+    };
     const int g = (int)live.size();
-    if (g == 0) {   // no frames anywhere: only sinks that finish have something to deliver
+    if (g == 0) {   // no frames anywhere: only stages that finish have something to deliver
         if (!finish_idle()) return;
-        run_sinks();
+        run_stages();
         sync();
-        commit_sinks();
+        commit_stages();
         return;
     }
     if (g > 65535) throw Error("codec_stream_push_batch: at most 65535 streams per call");
@@ -1195,28 +1152,14 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
             const int64_t first = len_of(d.a0) - up * (d.a0 - d.ctx), n_own = len_of(d.a0 + d.n) - len_of(d.a0);
             if (first < 0 || first + n_own > Tp || (d.ctx + d.n == G.Tw && first + n_own != Tp)) throw Error("codec_stream_push_batch: window arithmetic does not match the decoder length formula");
             q.n_own = n_own;
-            const bool sped = vp[(size_t)live[(size_t)i]].id >= 0;
-            if (sped) {   // through its stretcher, in the group's one launch (run_sinks), from where the samples lie
-                SpeedPush v = vp[(size_t)live[(size_t)i]];
-                if (v.n_new != n_own) throw Error("codec_stream_push_batch: a stretcher's input length does not match the decoder length formula");
-                v.x_dev = pcm_seq + first;
-                vp_run.push_back(v); vp_src.push_back(live[(size_t)i]);
-            }
-            const bool levelled = lp[(size_t)live[(size_t)i]].id >= 0;
-            if (levelled) {   // through its level stage, in the group's one launch (run_sinks)
-                LevelPush l = lp[(size_t)live[(size_t)i]];
-                if (!sped && l.n_new != n_own) throw Error("codec_stream_push_batch: a level stage's input length does not match the decoder length formula");
-                l.x_dev = pcm_seq + first;   // behind a stretcher: replaced by the stretcher's output in run_sinks
-                lp_run.push_back(l); lp_src.push_back(live[(size_t)i]);
-            }
-            if (sp[(size_t)live[(size_t)i]].sink >= 0) {   // through its sink, in the group's one launch (run_sinks), from where the samples lie
-                SinkPush k = sp[(size_t)live[(size_t)i]];
-                if (!sped && !levelled && k.n_new != n_own) throw Error("codec_stream_push_batch: a sink's input length does not match the decoder length formula");
-                k.x_dev = pcm_seq + first;   // behind a stretcher: replaced by the stretcher's output in run_sinks
-                sp_run.push_back(k); sp_src.push_back(live[(size_t)i]);
+            int k0 = 0;
+            while (k0 < SK_N && sp[k0][(size_t)live[(size_t)i]].id < 0) ++k0;
+            if (k0 < SK_N) {   // through its stages, each in the group's one launch of its kind (run_stages), from where the samples lie
+                if (sp[k0][(size_t)live[(size_t)i]].n_new != n_own)
+                    throw Error(std::string("codec_stream_push_batch: a ") + stages[k0]->noun + "'s input length does not match the decoder length formula");
+                (void)queue_stages(live[(size_t)i], pcm_seq + first);
                 return;
             }
-            if (sped || levelled) return;
             const int64_t m = std::min(n_own, q.cap);
             if (m > 0 && q.pcm) Q3_HIP_CHECK(hipMemcpyAsync(q.pcm, pcm_seq + first, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, stream));
         };
@@ -1225,20 +1168,20 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
             const int64_t Tp = codec_run(nullptr, G.Tw, &pcm_d, 0, hup, 2, gk, ustride);
             if (last_group) Q3_HIP_CHECK(hipEventRecord(ev1, stream));
             for (int i = G.i0; i < G.i1; ++i) deliver(i, pcm_d + (size_t)(i - G.i0) * Tp, Tp);
-            run_sinks();
+            run_stages();
         } else {                     // one stream in the group, or a decoder the batched conv kernels do not cover: sequence by sequence
             for (int i = G.i0; i < G.i1; ++i) {
                 float* pcm_d = nullptr;
                 const int64_t Tp = codec_run(nullptr, G.Tw, &pcm_d, 0, hup + (size_t)(i - G.i0) * ustride, 2);
                 if (last_group && i + 1 == G.i1) Q3_HIP_CHECK(hipEventRecord(ev1, stream));
                 deliver(i, pcm_d, Tp);
-                run_sinks();   // before the next sequence's decode reuses the lane's workspace
+                run_stages();   // before the next sequence's decode reuses the lane's workspace
             }
         }
     }
     (void)finish_idle();
-    run_sinks();
-    if (n_sinks > 0 || n_speed > 0 || n_level > 0) Q3_HIP_CHECK(hipEventRecord(ev1, stream));   // the push's time includes its sinks
+    run_stages();
+    if (st_any > 0) Q3_HIP_CHECK(hipEventRecord(ev1, stream));   // the push's time includes its stages
     sync();
     Q3_HIP_CHECK(hipEventElapsedTime(&last_codec_ms, ev0, ev1));
     total_codec_ms += last_codec_ms; total_codec_frames += T;
@@ -1247,10 +1190,10 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
         const StreamPush& q = ps[live[(size_t)i]];
         CodecW::Stream& S = W.streams[(size_t)q.sid];
         S.n_done = d.a0 + d.n; S.kv_rows = d.k0 + d.n; S.h_rows = d.h0 + d.n;
-        S.delivered = S.delivered || q.n_own > 0 || (S.sink >= 0 && sp[(size_t)live[(size_t)i]].n_new > 0) || (S.speed >= 0 && vp[(size_t)live[(size_t)i]].n_new > 0)
-                      || (S.level >= 0 && lp[(size_t)live[(size_t)i]].n_new > 0);
+        S.delivered = S.delivered || q.n_own > 0;
+        for (int k = 0; k < SK_N; ++k) S.delivered = S.delivered || (S.stage[k] >= 0 && sp[k][(size_t)live[(size_t)i]].n_new > 0);
     }
-    commit_sinks();
+    commit_stages();
 }
 
 // host codes: stream s receives frames codes[frame_offsets[s] .. frame_offsets[s + 1]); validated as a whole before anything moves
@@ -1278,12 +1221,8 @@ void Engine::codec_stream_push_batch_host(int n_streams, const int32_t* sids, co
         ps[(size_t)i].sid = sids[i]; ps[(size_t)i].n = frame_offsets[i + 1] - frame_offsets[i];
         ps[(size_t)i].pcm = pcm_out ? pcm_out[i] : nullptr; ps[(size_t)i].cap = cap;
         ps[(size_t)i].finish = finish && finish[i];
-        if (float_only && sids[i] >= 0 && sids[i] < (int)W.streams.size() && W.streams[(size_t)sids[i]].used && W.streams[(size_t)sids[i]].sink >= 0)
-            throw Error("codec_stream_push_batch: stream " + std::to_string(sids[i]) + " has a sink: the float entry serves streams without one");
-        if (float_only && sids[i] >= 0 && sids[i] < (int)W.streams.size() && W.streams[(size_t)sids[i]].used && W.streams[(size_t)sids[i]].speed >= 0)
-            throw Error("codec_stream_push_batch: stream " + std::to_string(sids[i]) + " has a speed: the float entry serves streams without one");
-        if (float_only && sids[i] >= 0 && sids[i] < (int)W.streams.size() && W.streams[(size_t)sids[i]].used && W.streams[(size_t)sids[i]].level >= 0)
-            throw Error("codec_stream_push_batch: stream " + std::to_string(sids[i]) + " has a level: the float entry serves streams without one");
+        if (float_only && sids[i] >= 0 && sids[i] < (int)W.streams.size() && W.streams[(size_t)sids[i]].used && W.streams[(size_t)sids[i]].has())
+            throw Error("codec_stream_push_batch: stream " + std::to_string(sids[i]) + W.streams[(size_t)sids[i]].has() + ": the float entry serves streams without one");
         if (pcm_len) pcm_len[i] = 0;
     }
     if (W.sbatch_codes_n < total || !W.sbatch_codes) {
@@ -1329,15 +1268,19 @@ void Engine::slots_codec_decode_new(int n_slots, const int32_t* slots, float* co
             sid = codec_stream_begin(max_frames_cap);
             W.slot_stream[(size_t)slot] = sid;
         }
-        // the scheduler's sink: a stream that has delivered nothing yet takes it (a primed stream included: its sink starts from silence)
-        if (slot_sink_rate > 0 && W.streams[(size_t)sid].sink < 0 && !W.streams[(size_t)sid].delivered) codec_stream_set_sink(sid, slot_sink_rate, slot_sink_format);
-        if (slot_speed > 0 && slot_speed != 1000 && W.streams[(size_t)sid].speed < 0 && !W.streams[(size_t)sid].delivered) codec_stream_set_speed(sid, slot_speed);
-        if ((slot_gain_cb != 0 || slot_ceiling != 0) && W.streams[(size_t)sid].level < 0 && !W.streams[(size_t)sid].delivered) codec_stream_set_level(sid, slot_gain_cb, slot_ceiling);
+        // the scheduler's stages: a stream that has delivered nothing yet takes them (a primed stream included: they start from silence)
+        const SlotStages& ss = slot_stages;
+        const int* have = W.streams[(size_t)sid].stage;
+        if (!W.streams[(size_t)sid].delivered) {
+            if (ss.sink_rate > 0 && have[SK_SINK] < 0) codec_stream_set_sink(sid, ss.sink_rate, ss.sink_format);
+            if (ss.speed > 0 && ss.speed != 1000 && have[SK_SPEED] < 0) codec_stream_set_speed(sid, ss.speed);
+            if ((ss.gain_cb != 0 || ss.ceiling != 0) && have[SK_LEVEL] < 0) codec_stream_set_level(sid, ss.gain_cb, ss.ceiling);
+        }
         const int a = W.streams[(size_t)sid].n_done;
         StreamPush& q = ps[(size_t)i];
         q.sid = sid; q.n = nf - a; q.codes_dev = codes_d + ((size_t)slot * max_frames_cap + a) * c.n_groups;
         q.pcm = pcm_out ? pcm_out[i] : nullptr; q.cap = cap;
-        q.finish = (W.streams[(size_t)sid].sink >= 0 || W.streams[(size_t)sid].speed >= 0 || W.streams[(size_t)sid].level >= 0) && final_frames && final_frames[i] >= 0 && nf >= final_frames[i];
+        q.finish = W.streams[(size_t)sid].has() && final_frames && final_frames[i] >= 0 && nf >= final_frames[i];
         if (frame_begin) frame_begin[i] = a;
         if (frame_end) frame_end[i] = nf;
         if (pcm_len) pcm_len[i] = 0;

@@ -442,9 +442,7 @@ Engine::~Engine() {
     if (frame_text_d) (void)hipFree(frame_text_d);
     if (rag_x_d) (void)hipFree(rag_x_d);
     if (seg_tab_d) (void)hipFree(seg_tab_d);
-    pcm_sink_free();
-    speed_free();
-    level_free();
+    for (Stage* s : stages) { s->free_all(); s->ws_free(); }
     codec_free();
     speaker_free();
     encoder_free();

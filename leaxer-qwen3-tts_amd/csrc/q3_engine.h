@@ -10,6 +10,7 @@
 #include "q3_audio.h"
 #include "q3_common.h"
 #include "q3_kvpool.h"
+#include "q3_stage.h"
 
 namespace q3 {
 
@@ -174,111 +175,107 @@ public:
     void slot_codec_stream_reset(int slot);
     void codec_rope_tables(int P);
 
-    // ---- PCM sinks (q3_pcm_sink.cpp): 24 kHz float on the device -> the sink's rate and format, carried state ----
+    // ---- carried-state stages behind the vocoder: 24 kHz float on the device in, the stage's samples out ----
+    // Three kinds in one fixed order: the stretcher (q3_speed.cpp, 4m), the level stage (q3_level.cpp, 4n), the PCM sink
+    // (q3_pcm_sink.cpp, 4l).  Stage (q3_stage.cpp) is what they share: a call reserves once (the only place the workspaces may grow,
+    // before anything is enqueued), launches once per set of stages whose input is ready, and commits after the stream's sync.
+    enum StageKind { SK_SPEED = 0, SK_LEVEL = 1, SK_SINK = 2, SK_N = 3 };
+    static constexpr int kMaxStages = 4096;                          // of a kind, open at the same time (vocoder streams' included)
+    static constexpr int64_t kStageMaxPush = 1440000;                // one push of a standalone entry: 60 s
+    // x_dev: n_new samples on the device; out_host (NULL ok): min(n_out, cap) samples in the stage's output format land there;
+    // offs_host (NULL ok, the stretcher's): min(n_frames, offs_cap) frame offsets.  n_out, n_frames, out_dev / offs_dev (the push's
+    // output on the device, valid until the call's next reserve) and desc are set by plan and launch
+    struct StagePush { int id = -1; const float* x_dev = nullptr; int64_t n_new = 0; bool finish = false; void* out_host = nullptr; int64_t cap = 0;
+                       int32_t* offs_host = nullptr; int64_t offs_cap = 0; int64_t n_out = 0, n_frames = 0;
+                       const float* out_dev = nullptr; const int32_t* offs_dev = nullptr; int desc = -1; };
+    struct DevBuf { char* p = nullptr; size_t cap = 0; };           // a grow-only device workspace; cap in elements
+    void ws_grow(DevBuf& b, size_t want, size_t el);                 // syncs and reallocates (64 elements at least) when b holds fewer than want
+    struct Stage {
+        Engine& e;
+        const char *name, *noun, *count_noun;                        // the refusals' words: "level", "level stage", "stage"
+        bool has_offs = false;                                       // the kind keeps frame offsets (the stretcher)
+        Stage(Engine& en, const char* nm, const char* nn, const char* cn) : e(en), name(nm), noun(nn), count_noun(cn) {}
+        virtual ~Stage() {}
+        // ---- what a kind supplies ----
+        virtual void end(int id) = 0; virtual void free_all() = 0;   // free_all: the kind's own allocations (ws_free is the shared part)
+        virtual int64_t push_len(int id, int64_t n_new, bool finish) const = 0;   // host-only: samples that push would deliver; throws when it would be refused
+        virtual size_t out_el(int id) const { return sizeof(float); }             // bytes per delivered sample
+        virtual bool idle(StagePush& q) const { return q.n_new == 0 && q.n_out == 0; }   // an empty push: the carry stays, nothing is emitted
+        virtual size_t desc_size() const = 0; virtual const void* desc_at(size_t i) const = 0;
+        virtual void desc_reset(size_t n) = 0;                       // the call's host descriptors: never resized during the call (uploads read them until the sync)
+        virtual bool fill(StagePush& q, size_t di, char* out, int32_t* offs) = 0;   // descriptor di of a live push; false drops it
+        virtual void issue(size_t d0, int n_live) = 0;               // the kind's launch over uploaded descriptors [d0, d0 + n_live)
+        virtual void commit_one(const StagePush& q) = 0;             // counters advance, carries flip by the kind's rule
+        // ---- what they share (q3_stage.cpp) ----
+        DevBuf desc, out, in, offs;                                  // descriptors, packed outputs (bytes), a standalone entry's staged input (floats), the stretcher's frame offsets
+        size_t desc_n = 0, desc_used = 0, out_used = 0, offs_used = 0;   // descriptors the call reserved; what its launches have taken
+        static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }   // a push's share of the packed output
+        size_t plan(StagePush& q) const;                             // sets n_out (and n_frames) of a push about to be reserved, returns its output bytes; throws like push_len
+        void reserve(int n_total, size_t out_bytes_total, size_t offs_total = 0);   // once per call, before anything is enqueued
+        void launch(StagePush* ps, int n);                           // one descriptor upload + one launch + the device -> host copies; no stage moves
+        void commit(const StagePush* ps, int n) { for (int i = 0; i < n; ++i) commit_one(ps[i]); }   // after the sync
+        void push_batch_host(int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in, const uint8_t* finish,
+                             void* const* out_host, int64_t cap, int64_t* out_len, int32_t* const* offsets_out = nullptr, int64_t* n_offsets = nullptr);
+        void ws_free();
+    };
+    template <class Desc, class Slot> struct StageOf : Stage {   // a kind's typed halves: its host descriptors and its table (q3_stage.h)
+        StageOf(Engine& en, const char* nm, const char* nn, const char* cn, const char* none) : Stage(en, nm, nn, cn), tab{ nm, nn, none, kMaxStages, {} } {}
+        StageTable<Slot, Error> tab;
+        std::vector<Desc> desc_h;
+        void end(int id) override { tab.end(id); }
+        size_t desc_size() const override { return sizeof(Desc); }
+        void desc_reset(size_t n) override { desc_h.assign(n, Desc()); }
+        const void* desc_at(size_t i) const override { return &desc_h[i]; }
+    };
+
+    // the stretcher.  mem: its own allocation, [2][kSpeedCarry] floats of carry followed by [2][2] int64 of state { p, frames }.
+    // carry_abs0: absolute index of the first carried sample; frames: completed (the host rule's count, which the device's state repeats)
+    struct Stretcher : StageSlot { int speed = 1000; int64_t frames = 0, carry_abs0 = 0; float* mem = nullptr; };
+    struct SpeedStage : StageOf<SpeedDesc, Stretcher> {
+        explicit SpeedStage(Engine& en) : StageOf(en, "speed", "stretcher", "stretcher", "no such stretcher") { has_offs = true; }
+        float* win_d = nullptr;                                      // the window: a host table, built once and uploaded
+        int begin(int speed);
+        void free_all() override;
+        int64_t push_len(int id, int64_t n_new, bool finish) const override;
+        bool idle(StagePush& q) const override;                      // sets n_frames, the frames the push would complete
+        bool fill(StagePush& q, size_t di, char* out, int32_t* offs) override;
+        void issue(size_t d0, int n_live) override; void commit_one(const StagePush& q) override;
+    } speed{*this};
+    // the level stage: gain and look-ahead limiter.  mem: a limiter's own allocation, [2][kLevelCarry] floats of carry (the last 254
+    // values of v); a gain-only stage (ceiling 0) carries nothing.  The host rule needs nothing from the device.
+    struct Leveler : StageSlot { int gain_cb = 0, ceiling = 0; float* mem = nullptr; };
+    struct LevelStage : StageOf<LevelDesc, Leveler> {
+        explicit LevelStage(Engine& en) : StageOf(en, "level", "level stage", "stage", "no such level stage") {}
+        int begin(int gain_cb, int ceiling);
+        void free_all() override;
+        int64_t push_len(int id, int64_t n_new, bool finish) const override;
+        bool fill(StagePush& q, size_t di, char* out, int32_t* offs) override;
+        void issue(size_t d0, int n_live) override; void commit_one(const StagePush& q) override;
+    } level{*this};
+    // the PCM sink.  carry: [2][kPcmSinkCarry] floats in the sink's own allocation.  carry_abs0: absolute index of the first carried sample
     static constexpr int kPcmSinkCarry = 256;                        // floats per carry buffer (2 * half + ceil(M / L) <= 198)
-    static constexpr int kMaxPcmSinks = 4096;                        // open at the same time (vocoder streams' sinks included)
-    static constexpr int64_t kPcmSinkMaxSamples = 86400000;          // one hour of 24 kHz input per sink
-    static constexpr int64_t kPcmSinkMaxPush = 1440000;              // one push of the standalone entry: 60 s
     struct SinkPlanDev { SinkPlan plan; float* tab_d = nullptr; };
-    std::map<int, SinkPlanDev> sink_plans;                           // by rate: built once, uploaded, kept (node addresses are stable)
-    const SinkPlanDev& pcm_sink_plan(int rate);
-    // carry: [2][kPcmSinkCarry] floats in the sink's own allocation; a push reads buffer `cur` and writes the other, the host flips
-    // them when the push has completed.  carry_abs0: absolute index of the first carried sample.
-    struct PcmSink { bool used = false, finished = false; int rate = 24000, format = 0, cur = 0; const SinkPlanDev* plan = nullptr;
-                     int64_t n_in = 0, n_out = 0, carry_abs0 = 0; float* carry = nullptr; };
-    std::vector<PcmSink> sinks;
-    int pcm_sink_begin(int rate, int format);
-    void pcm_sink_end(int id);
-    void pcm_sink_free();
-    const PcmSink& pcm_sink_get(int id) const;
-    int64_t pcm_sink_push_len(int id, int64_t n_new, bool finish) const;   // host-only: samples that push would deliver; throws when it would be refused
-    size_t pcm_sink_out_bytes(int id, int64_t n_new, bool finish) const;   // that push's share of the packed output buffer
-    // x_dev: n_new samples on the device; out_host: min(n_out, cap) samples in the sink's format land there; desc: internal
-    struct SinkPush { int sink = -1; const float* x_dev = nullptr; int64_t n_new = 0; bool finish = false; void* out_host = nullptr; int64_t cap = 0;
-                      int64_t n_out = 0; int desc = -1; };
-    void pcm_sinks_reserve(int n_total, size_t out_bytes_total);     // once per call, before anything is enqueued
-    void pcm_sinks_launch(SinkPush* ps, int n);                      // one launch + the device -> host copies; no sink moves
-    void pcm_sinks_commit(const SinkPush* ps, int n);                // after the sync: counters advance, carries flip
-    void pcm_sink_push_batch_host(int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in, const uint8_t* finish,
-                                  void* const* out, int64_t cap, int64_t* out_len);
-    PcmSinkDesc* sink_desc_d = nullptr; size_t sink_desc_cap = 0, sink_desc_used = 0;
-    std::vector<PcmSinkDesc> sink_desc_h;
-    char* sink_out_d = nullptr; size_t sink_out_bytes = 0, sink_out_used = 0;   // packed outputs of a call (grow-only workspace)
-    float* sink_in_d = nullptr; size_t sink_in_floats = 0;                       // the standalone entry's staged input
-    // vocoder streams: a stream with a sink delivers at the sink's rate (codec_stream_push_batch; StreamPush::pcm is then read as the
-    // sink's format and n_own counts its samples).  Refused once the stream has delivered a sample.  24 000 / float: no sink.
-    void codec_stream_set_sink(int sid, int rate, int format);
-    int codec_stream_sink(int sid) const;                            // -1: none
-    // the scheduler's sink (q3tts_engine_set_sink): slots' implicit streams begin with it.  rate 0: none
-    int slot_sink_rate = 0, slot_sink_format = 0;
+    struct PcmSink : StageSlot { int rate = 24000, format = 0; const SinkPlanDev* plan = nullptr; int64_t carry_abs0 = 0; float* carry = nullptr; };
+    struct SinkStage : StageOf<PcmSinkDesc, PcmSink> {
+        explicit SinkStage(Engine& en) : StageOf(en, "pcm sink", "sink", "sink", "no such sink") {}
+        std::map<int, SinkPlanDev> plans;                            // by rate: built once, uploaded, kept (node addresses are stable)
+        const SinkPlanDev& plan_for(int rate);
+        int begin(int rate, int format);
+        void free_all() override;
+        int64_t push_len(int id, int64_t n_new, bool finish) const override;
+        size_t out_el(int id) const override { return tab.get(id).format == Q3TTS_PCM_S16 ? 2 : 4; }
+        bool fill(StagePush& q, size_t di, char* out, int32_t* offs) override;
+        void issue(size_t d0, int n_live) override; void commit_one(const StagePush& q) override;
+    } sink{*this};
+    Stage* const stages[SK_N] = { &speed, &level, &sink };           // by StageKind: the order a stream's audio passes them in
 
-    // ---- speaking rate (q3_speed.cpp): WSOLA time stretch of 24 kHz float on the device, carried state ----
-    static constexpr int kMaxStretchers = 4096;                      // open at the same time (vocoder streams' included)
-    // mem: the stretcher's own allocation, [2][kSpeedCarry] floats of carry followed by [2][2] int64 of state { p, frames }; a push
-    // reads half `cur` and writes the other, the host flips them when the push has completed.  carry_abs0: absolute index of the
-    // first carried sample; frames: frames completed (the host rule's count, which the device's state repeats)
-    struct Stretcher { bool used = false, finished = false; int speed = 1000, cur = 0; int64_t n_in = 0, n_out = 0, frames = 0, carry_abs0 = 0; float* mem = nullptr; };
-    std::vector<Stretcher> stretchers;
-    float* speed_win_d = nullptr;                                    // the window: a host table, built once and uploaded
-    int speed_begin(int speed);
-    void speed_end(int id);
-    void speed_free();
-    const Stretcher& speed_get(int id) const;
-    int64_t speed_push_len(int id, int64_t n_new, bool finish) const;      // host-only: samples that push would deliver; throws when it would be refused
-    int64_t speed_push_frames(int id, int64_t n_new, bool finish) const;   // frames it would complete
-    // x_dev: n_new samples on the device; out_host (NULL ok): min(n_out, cap) floats land there; offs_host (NULL ok): min(n_frames,
-    // offs_cap) offsets.  n_out, n_frames, out_dev (the push's samples on the device, valid until the call's next reserve), desc: set
-    // by speed_launch
-    struct SpeedPush { int id = -1; const float* x_dev = nullptr; int64_t n_new = 0; bool finish = false; float* out_host = nullptr; int64_t cap = 0;
-                       int32_t* offs_host = nullptr; int64_t offs_cap = 0; int64_t n_out = 0, n_frames = 0; const float* out_dev = nullptr; int desc = -1; };
-    void speed_reserve(int n_total, size_t out_floats_total, size_t frames_total);   // once per call, before anything is enqueued
-    void speed_launch(SpeedPush* ps, int n);                         // one launch + the device -> host copies; no stretcher moves
-    void speed_commit(const SpeedPush* ps, int n);                   // after the sync: counters advance, carries flip
-    static size_t speed_out_floats(int64_t n_out) { return ((size_t)n_out + 63) & ~(size_t)63; }
-    void speed_push_batch_host(int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in, const uint8_t* finish,
-                               float* const* out, int64_t cap, int64_t* out_len, int32_t* const* offsets_out, int64_t* n_offsets);
-    SpeedDesc* speed_desc_d = nullptr; size_t speed_desc_cap = 0, speed_desc_used = 0;
-    std::vector<SpeedDesc> speed_desc_h;
-    float* speed_out_d = nullptr; size_t speed_out_cap = 0, speed_out_used = 0;      // packed outputs of a call (grow-only workspace)
-    int32_t* speed_offs_d = nullptr; size_t speed_offs_cap = 0, speed_offs_used = 0; // the frames' offsets of a call
-    float* speed_in_d = nullptr; size_t speed_in_floats = 0;                         // the standalone entry's staged input
-    // vocoder streams: a stream with a speed delivers its audio time-stretched (codec_stream_push_batch), before its sink if it has
-    // one.  Refused once the stream has delivered a sample.  1000: no stage.
+    // vocoder streams: a stream delivers its audio through the stages it has (codec_stream_push_batch; behind a sink StreamPush::pcm is read as
+    // the sink's format, n_own counts its samples).  Refused once the stream has delivered a sample.  1000, (0, 0), 24 000 Hz float: no stage.
     void codec_stream_set_speed(int sid, int speed);
-    // the scheduler's speed (q3tts_engine_set_speed): slots' implicit streams begin with it.  0 or 1000: none
-    int slot_speed = 0;
-
-    // ---- output level (q3_level.cpp): gain and look-ahead limiter on 24 kHz float on the device, carried state ----
-    static constexpr int kMaxLevelers = 4096;                        // open at the same time (vocoder streams' included)
-    // mem: a limiter's own allocation, [2][kLevelCarry] floats of carry (the last 254 values of v); a push reads half `cur` and writes
-    // the other, the host flips them when the push has completed.  The counters live here: the host rule needs nothing from the device.
-    // A gain-only stage (ceiling 0) carries nothing.
-    struct Leveler { bool used = false, finished = false; int gain_cb = 0, ceiling = 0, cur = 0; int64_t n_in = 0, n_out = 0; float* mem = nullptr; };
-    std::vector<Leveler> levelers;
-    int level_begin(int gain_cb, int ceiling);
-    void level_end(int id);
-    void level_free();
-    const Leveler& level_get(int id) const;
-    int64_t level_push_len(int id, int64_t n_new, bool finish) const;      // host-only: samples that push would deliver; throws when it would be refused
-    // x_dev: n_new samples on the device; out_host (NULL ok): min(n_out, cap) floats land there.  n_out, out_dev (the push's samples on
-    // the device, valid until the call's next reserve), desc: set by level_launch
-    struct LevelPush { int id = -1; const float* x_dev = nullptr; int64_t n_new = 0; bool finish = false; float* out_host = nullptr; int64_t cap = 0;
-                       int64_t n_out = 0; const float* out_dev = nullptr; int desc = -1; };
-    void level_reserve(int n_total, size_t out_floats_total);        // once per call, before anything is enqueued
-    void level_launch(LevelPush* ps, int n);                         // one launch + the device -> host copies; no stage moves
-    void level_commit(const LevelPush* ps, int n);                   // after the sync: counters advance, carries flip
-    static size_t level_out_floats(int64_t n_out) { return ((size_t)n_out + 63) & ~(size_t)63; }
-    void level_push_batch_host(int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in, const uint8_t* finish,
-                               float* const* out, int64_t cap, int64_t* out_len);
-    LevelDesc* level_desc_d = nullptr; size_t level_desc_cap = 0, level_desc_used = 0;
-    std::vector<LevelDesc> level_desc_h;
-    float* level_out_d = nullptr; size_t level_out_cap = 0, level_out_used = 0;      // packed outputs of a call (grow-only workspace)
-    float* level_in_d = nullptr; size_t level_in_floats = 0;                         // the standalone entry's staged input
-    // vocoder streams: a stream with a level stage delivers its audio through it (codec_stream_push_batch), behind its stretcher and
-    // ahead of its sink if it has them.  Refused once the stream has delivered a sample.  (0, 0): no stage.
     void codec_stream_set_level(int sid, int gain_cb, int ceiling);
-    // the scheduler's level (q3tts_engine_set_level): slots' implicit streams begin with it.  (0, 0): none
-    int slot_gain_cb = 0, slot_ceiling = 0;
+    void codec_stream_set_sink(int sid, int rate, int format);
+    // the scheduler's stages (q3tts_engine_set_sink / _speed / _level): slots' implicit streams begin with them.  Zeros: none
+    struct SlotStages { int sink_rate = 0, sink_format = 0, speed = 0, gain_cb = 0, ceiling = 0; } slot_stages;
 
     // ---- batch-first session ops on DEVICE pointers (include/q3tts.h "_dev" entry points): row b <-> slot b ----
     // caller stream: the engine's stream first waits for what the caller has enqueued, the caller's stream then waits for the call's work

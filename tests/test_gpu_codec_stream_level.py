@@ -127,6 +127,44 @@ def test_streams_with_speed_level_and_sink(eng, codes, plain):
         assert np.array_equal(one[1][k], plain[pushes][1][k]), k
 
 
+def test_every_subset_of_stages_in_one_push_sequence(eng, codes, plain):
+    """Eight streams with the eight subsets of {stretcher, level stage, sink} share every call, so each launch set hands over along
+    every pair of stages at once.  Ragged pushes (1 .. 8 frames, then 5 each: the second call's streams differ in left context);
+    in the last call two streams finish without frames beside streams that bring frames.  The stream without a stage never
+    finishes.  Reference: the same calls on eight plain streams, fed through the standalone stages."""
+    subsets = [(s, l, k) for s in (False, True) for l in (False, True) for k in (False, True)]      # index 0: no stage
+    cb = gain_for(max(np.abs(np.concatenate(plain[(1, 3, 25)][i])).max() for i in range(2)))
+    args = [((1250,) if s else None, (cb, CEIL) if l else None, (8000, "int16") if k else None) for s, l, k in subsets]
+    kinds = [dict(**(dict(speed=1250) if s else {}), **(dict(gain_db=cb / 10.0, ceiling=CEIL / 1000.0) if l else {}),
+                  **(dict(sample_rate=8000, dtype="int16") if k else {})) for s, l, k in subsets]
+    idle = (5, 7)                                            # stretcher + sink and all three: the tails alone, each pair handed over
+    frames = [[i + 1 for i in range(8)], [5] * 8, [0 if i in idle else 3 for i in range(8)]]
+
+    def run(kinds, staged):
+        sids = [eng.codec_stream_begin(NF, **kw) for kw in kinds]
+        parts, at = [[] for _ in kinds], [0] * len(kinds)
+        for c, ns in enumerate(frames):
+            fin = [c + 1 == len(frames) and s for s in staged]
+            out = eng.codec_stream_push_batch(sids, [codes[i % 2][at[i]:at[i] + n] for i, n in enumerate(ns)], finish=fin if any(staged) else None)
+            for i, o in enumerate(out):
+                parts[i].append(o)
+                at[i] += ns[i]
+        for s in sids:
+            eng.codec_stream_end(s)
+        return parts
+    base = run([{}] * 8, [False] * 8)
+    got = run(kinds, [any(sub) for sub in subsets])
+    for i, (speed, level, sink) in enumerate(args):
+        assert sum(p.size for p in base[i]) == eng.codec_decode_len(sum(f[i] for f in frames)), i
+        ref = chain(eng, base[i], speed=speed, level=level, sink=sink)
+        for c in range(len(frames)):
+            assert got[i][c].dtype == ref[c].dtype and got[i][c].size == ref[c].size, (i, c)
+            assert got[i][c].tobytes() == ref[c].tobytes(), (i, c)
+        assert np.abs(np.concatenate(got[i]).astype(np.float64)).max() > 0, i
+        if any(subsets[i]) and i in idle:
+            assert base[i][-1].size == 0 and got[i][-1].size > 0, i                      # the last call delivered the stages' tails alone
+
+
 def test_refusals(eng, codes, plain):
     p0 = plain[(1, 3, 25)]
     a = eng.codec_stream_begin(NF, gain_db=6.0, ceiling=0.9)
