@@ -792,6 +792,65 @@ int q3tts_codec_stream_set_level(q3tts_engine* e, int stream_id, int32_t gain_cb
  * and RNG use are untouched.  (0, 0): none. */
 int q3tts_engine_set_level(q3tts_engine* e, int32_t gain_cb, int32_t ceiling_permille);
 
+/* ---- pitch: carried-state TD-PSOLA shift of the fundamental ([HINT] no counterpart in the reference, which has no pitch control;
+ * DESIGN.md 4o) ----
+ * The FIRST stage behind the vocoder at 24 kHz: vocoder -> pitch -> stretcher -> level -> sink, on the GPU, all stages of a push in one
+ * launch.  It delivers the same audio at the same length with the fundamental multiplied by r / 1000 and the spectral envelope left
+ * where it is (time-domain pitch-synchronous overlap-add; Moulines & Charpentier 1990).  r: integer permille, 500 .. 2000.  1000 is "no
+ * stage": no launch, the same bytes as before.
+ * Constants: Pmin = 48, Pmax = 400, Pu = 120, W = 240; VOICED2 = 0.25f, OCTAVE2 = 0.81f (squared correlations 0.5 and 0.9);
+ * FLOOR = 0.0625f; synthesis positions carry F = 20 fraction bits.  x[k] = 0 for k < 0 and, once the stage is finished with n
+ * samples, for k >= n.
+ * Analysis marks: a_0 = 0, a_{j+1} = a_j + P_j.  Mark j is searched when a_j >= W and a_j + W + Pmax + 1 <= n (while the stage is not
+ * finished a mark is only looked at once that much has arrived); otherwise it is unvoiced.  The search, with t[i] = x[a_j - W + i],
+ * i = 0 .. 479, for every lag L = 47 .. 401:
+ *   num(L) = (s0 + s1) + (s2 + s3), s_q the fp32 sum of t[i] * x[a_j - W + L + i] over i = q mod 4 ascending (product rounded, then added);
+ *   E_lag(L) likewise of x[a_j - W + L + i]^2, E_t likewise of t[i]^2;  den = E_t * E_lag;
+ *   score(L) = den > 0 ? (num * |num|) / den : 0, a correctly rounded fp32 division.
+ * A candidate is a lag 48 .. 400 with score(L) >= score(L - 1) and score(L) >= score(L + 1).  best = the largest candidate score
+ * (no candidate: unvoiced).  The mark is voiced when best >= VOICED2; then P_j = the SMALLEST candidate with score >= OCTAVE2 * best
+ * (one fp32 product).  An unvoiced mark has P_j = Pu.  Mark 0 is unvoiced (a_0 < W).
+ * Synthesis marks: s_0 = 0 in 64-bit fixed point, t_i = s_i >> F.  Mark i takes the analysis mark j nearest to t_i, the later of two
+ * equally near, and s_{i+1} = s_i + ((P_j * 1000) << F) / r (integer division) when that mark is voiced, s_i + (P_j << F) when not.
+ * Marks are placed for t_i < n + Pmax.
+ * Grains: mark i adds, for m = 0 .. 2 P_j - 1 and k = t_i - P_j + m >= 0, acc[k] = acc[k] + h[m] * x[a_j - P_j + m] (product rounded,
+ * then added) and wsum[k] = wsum[k] + h[m], with h[m] = (float)(0.5 - 0.5 cos(pi m / P_j)) formed in double (a table per P, built on
+ * the host).  Grains are added in mark order.  y[k] = acc[k] / (wsum[k] > FLOOR ? wsum[k] : FLOOR) for 0 <= k < n.
+ * Every fp32 operation is a single rounded operation in a fixed order, so a sample's bits depend on the input, r and its absolute index
+ * alone: never on how the audio was cut into pushes or on which stages shared a launch.  Unvoiced audio (every mark at hop Pu, windows
+ * summing to 1) comes out as it went in up to the rounding of sum(h x) / sum(h).
+ * Host rule: a synthesis mark at t is placed once t + GATE samples have arrived, GATE = Pmax / 2 + W + Pmax + 1 = 841 (its analysis mark
+ * lies at most Pmax / 2 behind t and is searched over W + Pmax + 1 samples); output k is final once every mark up to k + Pmax is placed.
+ * So a stage that has received R samples and is not finished has emitted E(R) = max(0, R - LA), LA = Pmax + GATE - 1 = 1240 (51.7 ms);
+ * finished with n samples, n.  A push delivers E(after) - E(before).  The stage carries its last 2 560 input samples, the 1 024
+ * entries of acc and wsum beyond the last emitted sample and eight words of mark state in two alternating halves of its own.
+ * Non-finite input: the formulas apply as written (a comparison with a NaN is false); periods and indices stay in their ranges.
+ * Known limits: a primed stream's pitch stage (q3tts_codec_stream_prime_batch_host, q3tts_synthesize_continue_stream_host) starts from
+ * silence, like the other stages.  VOICED2 and OCTAVE2 are untuned on real voices. */
+/* Host only, no engine.  round(1000 * 2^(cents / 1200)) in double; -1 for cents outside -1200 .. +1200 or not finite
+ * (q3tts_pitch_last_error() then says so; thread-local, valid until the thread's next pitch_ratio / pitch_emitted call). */
+int32_t q3tts_pitch_ratio(double cents);
+/* Host only: outputs a stage has emitted in all after n_received samples (the rule does not depend on r).  -1 for n_received < 0. */
+int64_t q3tts_pitch_emitted(int64_t n_received, int finished);
+const char* q3tts_pitch_last_error(void);
+/* Pitch stages on their own: the stage by itself, fed 24 kHz float from the host.  A stage accepts at most one hour of input
+ * (86 400 000 samples), a push at most 1 440 000.  At most 4096 stages are open at a time (vocoder streams' included).  1000 is
+ * refused: it is no stage. */
+int q3tts_pitch_begin(q3tts_engine* e, int32_t ratio_permille, int* id);
+/* As q3tts_level_push_batch_host: n stages (distinct, open, not finished), validated completely before any stage moves. */
+int q3tts_pitch_push_batch_host(q3tts_engine* e, int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in,
+                                const uint8_t* finish, float* const* out, int64_t cap_samples, int64_t* out_len);
+int q3tts_pitch_end(q3tts_engine* e, int id);
+/* Vocoder streams.  A stream delivers through a pitch stage from its first sample on: refused, by name, once the stream has delivered
+ * a sample.  1000 takes the stage away again.  q3tts_codec_stream_push_batch_any_host serves such streams: the stage reads the push's
+ * PCM where it lies and feeds the stream's later stages in the same push; finish[s] flushes pitch, stretcher, level, sink in that
+ * order and is allowed on a stream with a pitch stage and no sink.  The float entries refuse a stream with a pitch stage by name. */
+int q3tts_codec_stream_set_pitch(q3tts_engine* e, int stream_id, int32_t ratio_permille);
+/* The scheduler: one setter for the four streaming entries, beside q3tts_engine_set_sink / _speed / _level.  The finished = 1 call
+ * carries the stage's tail, so an utterance's calls add up to the length they have without the stage.  Codes, frame counts and RNG
+ * use are untouched.  1000: none. */
+int q3tts_engine_set_pitch(q3tts_engine* e, int32_t ratio_permille);
+
 /* ---- text front end: the reference's byte-level BPE tokenizer ---- */
 /* Replaces leaxer_qwen::io::load_vocab / load_merges / is_tokenizer_ready / tokenize (reference
  * src/io/tokenizer.h:13-22, src/io/tokenizer.cpp:538-561) with the same ids for the same files and text.

@@ -227,6 +227,20 @@ void level_check(int gain_cb, int ceiling) {
 }
 float level_gain(int gain_cb) { return (float)std::pow(10.0, (double)gain_cb / 200.0); }
 
+// ---- pitch (q3_audio.h) ----
+void pitch_check(int ratio) {
+    if (ratio < kPitchMin || ratio > kPitchMax)
+        throw std::invalid_argument("pitch: " + std::to_string(ratio) + " permille is outside " + std::to_string(kPitchMin) + " .. " + std::to_string(kPitchMax));
+}
+int pitch_ratio(double cents) { return (int)std::llround(1000.0 * std::pow(2.0, cents / 1200.0)); }
+std::vector<float> pitch_windows() {
+    std::vector<float> w((size_t)kPitchWindowFloats);
+    const double pi = 3.14159265358979323846;
+    for (int P = kPitchPmin; P <= kPitchPmax; ++P)
+        for (int m = 0; m < 2 * P; ++m) w[(size_t)(pitch_window_offset(P) + m)] = (float)(0.5 - 0.5 * std::cos(pi * (double)m / (double)P));
+    return w;
+}
+
 // ---------------------------------------------------------------------------------------------
 // log-mel (reference mel.cpp:13-80 filterbank, :182-236 framing).  NOT librosa's: symmetric Hann
 // window, no centre padding, frames = (n - win)/hop + 1 (one zero-padded frame for shorter clips),

@@ -74,6 +74,35 @@ inline int64_t level_emitted(int ceiling_permille, int64_t n_received, bool fini
     return ceiling_permille == 0 || finished ? n_received : std::max<int64_t>(0, n_received - (kLevelW - 1));
 }
 
+// ---- pitch: TD-PSOLA shift of the fundamental at 24 kHz (the arithmetic is fixed in include/q3tts.h) ----
+// Ratio r in permille (kPitchMin .. kPitchMax, 1000: no stage).  Periods kPitchPmin .. kPitchPmax, an unvoiced mark's kPitchPu, the
+// search template's half-width kPitchW.  A search at mark a reads x[a - W, a + kPitchReach): lags Pmin - 1 .. Pmax + 1 of a 2 W window.
+// A synthesis mark at t is placed once kPitchGate samples from t on have arrived (its analysis mark lies at most Pmax / 2 behind t);
+// output k is final once every mark up to k + Pmax is placed, so kPitchLA = Pmax + kPitchGate - 1.  Synthesis positions carry
+// kPitchFrac fraction bits.  The two constants most likely to want tuning on real voices are kPitchVoiced2 and kPitchOctave2
+// (squared correlations: 0.5 and 0.9), used by k_psola and restated in tests/pitch_ref.py.
+constexpr int kPitchMin = 500, kPitchMax = 2000;
+constexpr int kPitchPmin = 48, kPitchPmax = 400, kPitchPu = 120, kPitchW = 240;
+constexpr int kPitchLags = kPitchPmax - kPitchPmin + 3;                  // 355 scores: lags Pmin - 1 .. Pmax + 1
+constexpr int kPitchReach = kPitchW + kPitchPmax + 1;                    // 641
+constexpr int kPitchRegion = kPitchW + kPitchReach;                      // 881 samples of one search
+constexpr int kPitchGate = kPitchPmax / 2 + kPitchReach;                 // 841
+constexpr int kPitchLA = kPitchPmax + kPitchGate - 1;                    // 1240 samples, 51.7 ms
+constexpr int kPitchFrac = 20;
+constexpr float kPitchVoiced2 = 0.25f, kPitchOctave2 = 0.81f, kPitchFloor = 0.0625f;
+constexpr int kPitchRing = 1024;                                         // the two output accumulators beyond the last emitted sample (at most kPitchLA - kPitchGate + kPitchPmax = 799 are live)
+constexpr int kPitchCarry = 2560;                                        // input samples a stage carries (at most 2 Pmax + kPitchGate + 2 Pmax - 1 = 2440 can be read again)
+constexpr int kPitchStateWords = 8;                                      // int64: a_cur, P_cur, v_cur, has_next, P_next, v_next, s, marks placed
+constexpr int kPitchHalfFloats = kPitchCarry + 2 * kPitchRing + 2 * kPitchStateWords;   // one half of a stage's allocation
+void pitch_check(int ratio);   // throws std::invalid_argument naming the ratio when it is outside kPitchMin .. kPitchMax
+int pitch_ratio(double cents); // round(1000 * 2^(cents / 1200)), in double
+// outputs a stage has emitted in all after n_received samples: unfinished max(0, n - kPitchLA), finished n.  Independent of every period.
+inline int64_t pitch_emitted(int64_t n_received, bool finished) { return finished ? n_received : std::max<int64_t>(0, n_received - kPitchLA); }
+// the windows: for P = Pmin .. Pmax the 2 P values 0.5 - 0.5 cos(pi m / P), formed in double and rounded to float, P after P
+constexpr int pitch_window_offset(int P) { return P * (P - 1) - kPitchPmin * (kPitchPmin - 1); }
+constexpr int kPitchWindowFloats = (kPitchPmax + 1) * kPitchPmax - kPitchPmin * (kPitchPmin - 1);   // 158 144
+std::vector<float> pitch_windows();
+
 struct MelSpec { // the settings of tts_onnx.cpp:347-354
     int sample_rate = 24000, n_fft = 1024, hop = 256, win = 1024, n_mels = 128;
     float fmin = 0.0f, fmax = 12000.0f;

@@ -20,6 +20,7 @@ struct q3tts_engine {
     q3tts_sink sink = { 0, 0, nullptr, nullptr };   // q3tts_engine_set_sink (sample_rate 0: none)
     int32_t speed = 1000;                           // q3tts_engine_set_speed (1000: none)
     int32_t gain_cb = 0, ceiling = 0;               // q3tts_engine_set_level ((0, 0): none)
+    int32_t pitch = 1000;                           // q3tts_engine_set_pitch (1000: none)
 };
 static std::string g_create_err;
 
@@ -516,6 +517,54 @@ int q3tts_engine_set_level(q3tts_engine* h, int32_t gain_cb, int32_t ceiling_per
     Q3_API_BEGIN(h)
     try { q3::level_check(gain_cb, ceiling_permille); } catch (const std::invalid_argument& ex) { throw q3::Error(std::string("engine_set_level: ") + ex.what()); }
     h->gain_cb = gain_cb; h->ceiling = ceiling_permille;
+    return 0;
+    Q3_API_END(h)
+}
+
+// ---- pitch (include/q3tts.h "pitch") ----
+static thread_local std::string g_pitch_err;
+const char* q3tts_pitch_last_error(void) { return g_pitch_err.c_str(); }
+int32_t q3tts_pitch_ratio(double cents) {
+    g_pitch_err.clear();
+    if (!(cents >= -1200.0 && cents <= 1200.0)) { g_pitch_err = "pitch: " + std::to_string(cents) + " cents is outside -1200 .. +1200"; return -1; }
+    return q3::pitch_ratio(cents);
+}
+int64_t q3tts_pitch_emitted(int64_t n_received, int finished) {
+    g_pitch_err.clear();
+    if (n_received < 0) { g_pitch_err = "pitch: negative sample count " + std::to_string(n_received); return -1; }
+    return q3::pitch_emitted(n_received, finished != 0);
+}
+int q3tts_pitch_begin(q3tts_engine* h, int32_t ratio_permille, int* id) {
+    Q3_API_BEGIN(h)
+    if (!id) throw q3::Error("pitch: NULL argument");
+    *id = h->e->pitch.begin(ratio_permille);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_pitch_push_batch_host(q3tts_engine* h, int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in,
+                                const uint8_t* finish, float* const* out, int64_t cap_samples, int64_t* out_len) {
+    Q3_API_BEGIN(h)
+    h->e->pitch.push_batch_host(n, ids, pcm24, n_in, finish, (void* const*)out, cap_samples, out_len);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_pitch_end(q3tts_engine* h, int id) {
+    Q3_API_BEGIN(h)
+    h->e->pitch.end(id);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_codec_stream_set_pitch(q3tts_engine* h, int stream_id, int32_t ratio_permille) {
+    Q3_API_BEGIN(h)
+    try { q3::pitch_check(ratio_permille); } catch (const std::invalid_argument& ex) { throw q3::Error(std::string("codec_stream_set_pitch: ") + ex.what()); }
+    h->e->codec_stream_set_pitch(stream_id, ratio_permille);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_engine_set_pitch(q3tts_engine* h, int32_t ratio_permille) {
+    Q3_API_BEGIN(h)
+    try { q3::pitch_check(ratio_permille); } catch (const std::invalid_argument& ex) { throw q3::Error(std::string("engine_set_pitch: ") + ex.what()); }
+    h->pitch = ratio_permille;
     return 0;
     Q3_API_END(h)
 }
@@ -1185,7 +1234,10 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     const bool sped = speed != 1000;
     // with a level (q3tts_engine_set_level) the limiter hands on what it held back as well: at most W - 1 samples more
     const bool levelled = h->gain_cb != 0 || h->ceiling != 0;
-    const int64_t stage_cap = (sped ? ((chunk_cap + q3::kSpeedN + q3::kSpeedD + q3::kSpeedHs) * 1000 + speed - 1) / speed + q3::kSpeedHs : chunk_cap)
+    // with a pitch (q3tts_engine_set_pitch) the stage in front hands on what it held back: at most kPitchLA samples more
+    const bool pitched = h->pitch != 1000;
+    const int64_t pitch_cap = chunk_cap + (pitched ? q3::kPitchLA : 0);
+    const int64_t stage_cap = (sped ? ((pitch_cap + q3::kSpeedN + q3::kSpeedD + q3::kSpeedHs) * 1000 + speed - 1) / speed + q3::kSpeedHs : pitch_cap)
                               + (h->ceiling != 0 ? q3::kLevelW - 1 : 0);
     const q3::SinkPlan* splan = sunk ? &e.sink.plan_for(sink.sample_rate).plan : nullptr;
     const int64_t sink_cap = sunk ? ((stage_cap + splan->half) * splan->L + splan->M - 1) / splan->M + 2 : 0;
@@ -1199,7 +1251,7 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
         SlotStagesScope(Engine& en, const Engine::SlotStages& s) : e(en) { e.slot_stages = s; }
         ~SlotStagesScope() { e.slot_stages = Engine::SlotStages(); }
     } stages_scope(e, Engine::SlotStages{ sunk && !(sink.sample_rate == 24000 && sink.format == Q3TTS_PCM_F32) ? sink.sample_rate : 0, sink.format,
-                                          sped ? speed : 0, levelled ? h->gain_cb : 0, levelled ? h->ceiling : 0 });
+                                          sped ? speed : 0, levelled ? h->gain_cb : 0, levelled ? h->ceiling : 0, pitched ? h->pitch : 0 });
     std::vector<int32_t> slots, fb((size_t)B), fe((size_t)B);
     std::vector<int64_t> plen((size_t)B), written((size_t)n_utt, 0);
     std::vector<Engine::SlotInit> init;

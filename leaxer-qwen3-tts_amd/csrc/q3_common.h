@@ -498,6 +498,26 @@ constexpr int kLevelTile = 1024;        // outputs of one workgroup
 constexpr int level_tiles(int64_t n_out) { return n_out <= 0 ? 1 : (int)((n_out + kLevelTile - 1) / kLevelTile); }
 void launch_level(const LevelDesc* tab /* device, [n] */, int n, int max_tiles, hipStream_t s);
 
+// ---- pitch (q3_pitch.cpp): TD-PSOLA shift of the fundamental of 24 kHz float PCM, with carried state ----
+// One stage of one push.  Its samples are the carry ([carry_abs0, n_before)) followed by the push's n_new samples at x_new; x[k] = 0 for
+// k < 0 and k >= n_total.  half_in / half_out: the two halves of the stage's allocation, each kPitchCarry floats of input, kPitchRing
+// floats of grain sum and kPitchRing of window sum (entry m belongs to output out0 + m, resp. out0 + n_out + m), then kPitchStateWords
+// int64 of mark state.  The launch's workgroup places every synthesis mark whose gate has arrived (t + kPitchGate <= n_total; finish: t
+// < n_total + Pmax), writes out[0 .. n_out) (outputs out0 ..), the next carry x[keep_abs0 .. keep_abs0 + keep) and the state into
+// half_out.  first: the stage has received nothing yet, so accumulators and state start from their initial values, not from half_in.
+struct PitchDesc {
+    const float* half_in = nullptr; float* half_out = nullptr;
+    const float* x_new = nullptr;       // n_new samples (never null: a push without samples points at the carry)
+    const float* win = nullptr;         // the windows, kPitchWindowFloats floats on the device
+    float* out = nullptr;               // n_out samples
+    int64_t carry_abs0 = 0;             // absolute index of the carried input's first sample
+    int64_t n_before = 0, n_total = 0;  // samples received before / with this push
+    int64_t out0 = 0;                   // absolute index of the first new output
+    int64_t keep_abs0 = 0;              // absolute index of the next carry's first sample
+    int32_t n_new = 0, n_out = 0, keep = 0, ratio = 1000, finish = 0, first = 0;
+};
+void launch_psola(const PitchDesc* tab /* device, [n] */, int n, hipStream_t s);
+
 
 // ---- speaker encoder + GPU audio front end of the clone path (q3_speaker_kernels.hip) ----
 // One reference clip of a batch.  Activations of a batch lie clip after clip along time ([sum T][C]); every kernel that looks across

@@ -176,10 +176,11 @@ public:
     void codec_rope_tables(int P);
 
     // ---- carried-state stages behind the vocoder: 24 kHz float on the device in, the stage's samples out ----
-    // Three kinds in one fixed order: the stretcher (q3_speed.cpp, 4m), the level stage (q3_level.cpp, 4n), the PCM sink
-    // (q3_pcm_sink.cpp, 4l).  Stage (q3_stage.cpp) is what they share: a call reserves once (the only place the workspaces may grow,
-    // before anything is enqueued), launches once per set of stages whose input is ready, and commits after the stream's sync.
-    enum StageKind { SK_SPEED = 0, SK_LEVEL = 1, SK_SINK = 2, SK_N = 3 };
+    // Four kinds in one fixed order: the pitch stage (q3_pitch.cpp, 4o), the stretcher (q3_speed.cpp, 4m), the level stage
+    // (q3_level.cpp, 4n), the PCM sink (q3_pcm_sink.cpp, 4l).  Stage (q3_stage.cpp) is what they share: a call reserves once (the only
+    // place the workspaces may grow, before anything is enqueued), launches once per set of stages whose input is ready, and commits
+    // after the stream's sync.
+    enum StageKind { SK_PITCH = 0, SK_SPEED = 1, SK_LEVEL = 2, SK_SINK = 3, SK_N = 4 };
     static constexpr int kMaxStages = 4096;                          // of a kind, open at the same time (vocoder streams' included)
     static constexpr int64_t kStageMaxPush = 1440000;                // one push of a standalone entry: 60 s
     // x_dev: n_new samples on the device; out_host (NULL ok): min(n_out, cap) samples in the stage's output format land there;
@@ -228,6 +229,18 @@ public:
         const void* desc_at(size_t i) const override { return &desc_h[i]; }
     };
 
+    // the pitch stage.  mem: its own allocation, two halves of kPitchHalfFloats floats (carried input, the two output accumulators, the
+    // mark state).  carry_abs0: absolute index of the first carried sample.  The host rule needs nothing from the device.
+    struct Shifter : StageSlot { int ratio = 1000; int64_t carry_abs0 = 0; float* mem = nullptr; };
+    struct PitchStage : StageOf<PitchDesc, Shifter> {
+        explicit PitchStage(Engine& en) : StageOf(en, "pitch", "pitch stage", "stage", "no such pitch stage") {}
+        float* win_d = nullptr;                                      // the windows: a host table, built once and uploaded
+        int begin(int ratio);
+        void free_all() override;
+        int64_t push_len(int id, int64_t n_new, bool finish) const override;
+        bool fill(StagePush& q, size_t di, char* out, int32_t* offs) override;
+        void issue(size_t d0, int n_live) override; void commit_one(const StagePush& q) override;
+    } pitch{*this};
     // the stretcher.  mem: its own allocation, [2][kSpeedCarry] floats of carry followed by [2][2] int64 of state { p, frames }.
     // carry_abs0: absolute index of the first carried sample; frames: completed (the host rule's count, which the device's state repeats)
     struct Stretcher : StageSlot { int speed = 1000; int64_t frames = 0, carry_abs0 = 0; float* mem = nullptr; };
@@ -267,15 +280,16 @@ public:
         bool fill(StagePush& q, size_t di, char* out, int32_t* offs) override;
         void issue(size_t d0, int n_live) override; void commit_one(const StagePush& q) override;
     } sink{*this};
-    Stage* const stages[SK_N] = { &speed, &level, &sink };           // by StageKind: the order a stream's audio passes them in
+    Stage* const stages[SK_N] = { &pitch, &speed, &level, &sink };           // by StageKind: the order a stream's audio passes them in
 
     // vocoder streams: a stream delivers its audio through the stages it has (codec_stream_push_batch; behind a sink StreamPush::pcm is read as
     // the sink's format, n_own counts its samples).  Refused once the stream has delivered a sample.  1000, (0, 0), 24 000 Hz float: no stage.
+    void codec_stream_set_pitch(int sid, int ratio);
     void codec_stream_set_speed(int sid, int speed);
     void codec_stream_set_level(int sid, int gain_cb, int ceiling);
     void codec_stream_set_sink(int sid, int rate, int format);
-    // the scheduler's stages (q3tts_engine_set_sink / _speed / _level): slots' implicit streams begin with them.  Zeros: none
-    struct SlotStages { int sink_rate = 0, sink_format = 0, speed = 0, gain_cb = 0, ceiling = 0; } slot_stages;
+    // the scheduler's stages (q3tts_engine_set_sink / _speed / _level / _pitch): slots' implicit streams begin with them.  Zeros: none
+    struct SlotStages { int sink_rate = 0, sink_format = 0, speed = 0, gain_cb = 0, ceiling = 0, pitch = 0; } slot_stages;
 
     // ---- batch-first session ops on DEVICE pointers (include/q3tts.h "_dev" entry points): row b <-> slot b ----
     // caller stream: the engine's stream first waits for what the caller has enqueued, the caller's stream then waits for the call's work

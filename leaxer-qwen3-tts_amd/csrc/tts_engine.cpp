@@ -370,6 +370,52 @@ bool TTSEngine::stretch_push(int id, const float* in, size_t n, bool finish, siz
     return q3tts_speed_push_batch_host(h_, 1, &id, &in, &n_in, &fin, &dst, after - before, &len, nullptr, nullptr) == 0 && len == after - before;
 }
 
+bool TTSEngine::set_pitch(float semitones) {
+    if (!ready_) return false;
+    const int32_t r = semitones == semitones ? q3tts_pitch_ratio(100.0 * (double)semitones) : -1;
+    if (r < 0) {
+        error_msg_ = "pitch " + std::to_string(semitones) + " semitones is outside -12 .. +12";
+        std::cerr << "[TTSEngine] Pitch: " << error_msg_ << std::endl;
+        return false;
+    }
+    if (q3tts_engine_set_pitch(h_, r) != 0) {
+        error_msg_ = q3tts_last_error(h_);
+        std::cerr << "[TTSEngine] Pitch: " << error_msg_ << std::endl;
+        return false;
+    }
+    pitch_ = (int)r;
+    return true;
+}
+
+bool TTSEngine::pitch_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out) {
+    const int64_t n_in = (int64_t)n;
+    const uint8_t fin = finish ? 1 : 0;
+    const int64_t before = q3tts_pitch_emitted((int64_t)received_before, 0), after = q3tts_pitch_emitted((int64_t)(received_before + n), fin);
+    if (before < 0 || after < before) return false;
+    const size_t have = out.size();
+    out.resize(have + (size_t)(after - before));
+    float* dst = out.data() + have;
+    int64_t len = 0;
+    return q3tts_pitch_push_batch_host(h_, 1, &id, &in, &n_in, &fin, &dst, after - before, &len) == 0 && len == after - before;
+}
+
+bool TTSEngine::apply_pitch(std::vector<float>& pcm24) {
+    if (!ready_) return false;
+    if (pitch_ == 1000 || pcm24.empty()) return true;
+    int id = -1;
+    std::vector<float> out;
+    bool ok = q3tts_pitch_begin(h_, pitch_, &id) == 0;
+    const size_t step = 1440000;   // the most one push takes
+    for (size_t done = 0; ok && done < pcm24.size(); done += step) {
+        const size_t m = std::min(step, pcm24.size() - done);
+        ok = pitch_push(id, pcm24.data() + done, m, done + m == pcm24.size(), done, out);
+    }
+    if (!ok) std::cerr << "[TTSEngine] Pitch error: " << q3tts_last_error(h_) << std::endl;
+    if (id >= 0) (void)q3tts_pitch_end(h_, id);
+    if (ok) pcm24.swap(out); else pcm24.clear();
+    return ok;
+}
+
 bool TTSEngine::set_level(float gain_db, float ceiling) {
     if (!ready_) return false;
     const long G = std::lround(10.0 * (double)gain_db), T = std::lround(1000.0 * (double)ceiling);
@@ -421,10 +467,11 @@ bool TTSEngine::apply_level(std::vector<float>& pcm24) {
     return ok;
 }
 
-// the whole clip through the stretcher and then the level stage (each only when set): every one-shot method ends here
+// the whole clip through the pitch stage, the stretcher and then the level stage (each only when set): every one-shot method ends here
 bool TTSEngine::apply_speed(std::vector<float>& pcm24) {
     if (!ready_) return false;
     if (pcm24.empty()) return true;
+    if (!apply_pitch(pcm24)) return false;
     if (speed_ == 1000) return apply_level(pcm24);
     int id = -1;
     std::vector<float> out;
@@ -647,6 +694,15 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
     size_t received = 0;
     std::vector<float> fast;
     if (speed_ != 1000 && q3tts_speed_begin(h_, speed_, &stretcher) != 0) return fail();
+    // with a pitch the chunks first pass a pitch stage of this call's own, ahead of the stretcher
+    int shifter = -1;
+    size_t shifted = 0;
+    std::vector<float> low;
+    if (pitch_ != 1000 && q3tts_pitch_begin(h_, pitch_, &shifter) != 0) {
+        const int rc = fail();
+        if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
+        return rc;
+    }
     // with a level the chunks (the stretcher's, when there is one) pass a level stage of this call's own in the same way
     int leveler = -1;
     size_t levelled = 0;
@@ -654,11 +710,13 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
     if ((gain_cb_ != 0 || ceiling_ != 0) && q3tts_level_begin(h_, gain_cb_, ceiling_, &leveler) != 0) {
         const int rc = fail();
         if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
+        if (shifter >= 0) (void)q3tts_pitch_end(h_, shifter);
         return rc;
     }
     auto fail_s = [&]() {
         const int rc = fail();
         if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
+        if (shifter >= 0) (void)q3tts_pitch_end(h_, shifter);
         if (leveler >= 0) (void)q3tts_level_end(h_, leveler);
         return rc;
     };
@@ -669,6 +727,21 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
         levelled += n;
         if (!loud.empty()) on_audio(loud.data(), loud.size());
         return true;
+    };
+    auto feed = [&](const float* p, size_t n, bool last) -> bool {   // a chunk from the vocoder: pitch stage, stretcher, then emit
+        if (shifter >= 0) {
+            low.clear();
+            if (!pitch_push(shifter, p, n, last, shifted, low)) return false;
+            shifted += n;
+            p = low.data(); n = low.size();
+        }
+        if (stretcher >= 0) {
+            fast.clear();
+            if (!stretch_push(stretcher, p, n, last, received, fast)) return false;
+            received += n;
+            p = fast.data(); n = fast.size();
+        }
+        return emit(p, n, last && leveler >= 0);
     };
     for (;;) {
         const int want = std::min(chunk_frames, params.max_new_tokens - done);
@@ -681,22 +754,14 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
             const int ctx = left_context_frames < 0 ? nf : left_context_frames;
             if (q3tts_slot_codec_decode_range_host(h_, 0, done, nf, ctx, pcm.data(), (int64_t)pcm.size(), &n) != 0) return fail_s();
             const size_t got = (size_t)std::min<int64_t>(n, (int64_t)pcm.size());
-            if (stretcher >= 0) {
-                fast.clear();
-                if (!stretch_push(stretcher, pcm.data(), got, false, received, fast)) return fail_s();
-                received += got;
-                if (!emit(fast.data(), fast.size(), false)) return fail_s();
-            } else if (!emit(pcm.data(), got, false)) return fail_s();
+            if (!feed(pcm.data(), got, false)) return fail_s();
             done = nf;
         }
         if (active == 0 || want <= 0) break;
     }
-    if (stretcher >= 0) {
-        fast.clear();
-        if (!stretch_push(stretcher, pcm.data(), 0, true, received, fast)) return fail_s();
-        if (!emit(fast.data(), fast.size(), leveler >= 0)) return fail_s();
-        (void)q3tts_speed_end(h_, stretcher);
-    } else if (leveler >= 0 && !emit(pcm.data(), 0, true)) return fail_s();
+    if ((shifter >= 0 || stretcher >= 0 || leveler >= 0) && !feed(pcm.data(), 0, true)) return fail_s();   // the stages' tails, in their order
+    if (shifter >= 0) (void)q3tts_pitch_end(h_, shifter);
+    if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
     if (leveler >= 0) (void)q3tts_level_end(h_, leveler);
     (void)q3tts_slot_release(h_, 0);
     return done;

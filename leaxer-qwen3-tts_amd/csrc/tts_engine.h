@@ -194,6 +194,15 @@ public:
     int gain_centibels() const { return gain_cb_; }
     int ceiling_permille() const { return ceiling_; }
     bool apply_level(std::vector<float>& pcm24);   // the whole clip through the stage, in place; (0, 0) leaves it as it is
+    // Pitch (include/q3tts.h: q3tts_engine_set_pitch, q3tts_pitch_*; the reference has no pitch control).  semitones -12 .. +12; the
+    // engine works in permille, r = round(1000 * 2^(semitones / 12)), and 0 semitones is no stage at all.  TD-PSOLA on the GPU: the
+    // fundamental moves, the spectral envelope stays.  The stage stands first behind the vocoder on every path that honours set_speed,
+    // in the same way: inside the scheduler's streaming pushes, as a stage of its own ahead of synthesize_tokens_streaming's
+    // stretcher, over the whole clip in the one-shot methods (apply_pitch, which apply_speed calls first).  false (and get_error(),
+    // naming the range) for a value the engine refuses.
+    bool set_pitch(float semitones);
+    int pitch_permille() const { return pitch_; }
+    bool apply_pitch(std::vector<float>& pcm24);   // the whole clip through the stage, in place; 0 semitones leaves it as it is
     bool has_audio_encoder() const;
     int n_groups() const { return n_groups_; }
     bool has_speaker_encoder() const; // true when the weight file carries the spk.* tensors (reference: speaker_encoder.onnx present)
@@ -218,6 +227,8 @@ private:
     std::function<int(int, const void*, int64_t, int)> sink_fn_;   // the running streaming call's delivery, while an output format is set
     int speed_ = 1000;
     int gain_cb_ = 0, ceiling_ = 0;
+    int pitch_ = 1000;
+    bool pitch_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);
     bool level_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);
     // one push of a stretcher of this engine: out receives the push's samples (appended)
     bool stretch_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);

@@ -122,6 +122,8 @@ EXPORTS = [
     "q3tts_codec_stream_set_speed", "q3tts_engine_set_speed",
     "q3tts_level_gain", "q3tts_level_emitted", "q3tts_level_last_error", "q3tts_level_begin", "q3tts_level_push_batch_host", "q3tts_level_end",
     "q3tts_codec_stream_set_level", "q3tts_engine_set_level",
+    "q3tts_pitch_ratio", "q3tts_pitch_emitted", "q3tts_pitch_last_error", "q3tts_pitch_begin", "q3tts_pitch_push_batch_host", "q3tts_pitch_end",
+    "q3tts_codec_stream_set_pitch", "q3tts_engine_set_pitch",
 ]
 
 # q3tts_audio_cb: int (*)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished)
@@ -498,12 +500,13 @@ class Engine:
         self._ck(self.L.q3tts_codec_decode_chunked_host(self.h, _p(c), c.shape[0], chunk_frames, left_context, _p(pcm), n, C.byref(out_len)))
         return pcm[: out_len.value]
 
-    def codec_stream_begin(self, max_frames, sample_rate=24000, dtype="float32", speed=None, gain_db=None, ceiling=None):
+    def codec_stream_begin(self, max_frames, sample_rate=24000, dtype="float32", speed=None, gain_db=None, ceiling=None, pitch=None):
         """streaming vocoder with carried state: -> stream id (q3tts_codec_stream_begin).  sample_rate / dtype other than 24000 /
         float32 give the stream a sink (q3tts_codec_stream_set_sink): codec_stream_push_batch then delivers at that rate, as float32
         or int16.  speed (permille, 500 .. 2000; None or 1000: none) gives it a stretcher ahead of the sink
         (q3tts_codec_stream_set_speed).  gain_db / ceiling (level_params: rounded to centibels / permille; None: 0) give it a level
-        stage between the two (q3tts_codec_stream_set_level)."""
+        stage between the two (q3tts_codec_stream_set_level).  pitch (permille, 500 .. 2000; None or 1000: none) gives it a pitch
+        stage in front of them all (q3tts_codec_stream_set_pitch)."""
         fmt = _pcm_format(dtype)
         sid = C.c_int(-1)
         self.L.q3tts_codec_stream_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -527,7 +530,62 @@ class Engine:
             except Exception:
                 self.codec_stream_end(sid.value)
                 raise
+        if pitch is not None:
+            try:
+                self.codec_stream_set_pitch(sid.value, pitch)
+            except Exception:
+                self.codec_stream_end(sid.value)
+                raise
         return sid.value
+
+    def codec_stream_set_pitch(self, sid, ratio):
+        """q3tts_codec_stream_set_pitch: ratio in permille; refused once the stream has delivered a sample; 1000 takes the stage away"""
+        self.L.q3tts_codec_stream_set_pitch.argtypes = [C.c_void_p, C.c_int, C.c_int32]
+        self._ck(self.L.q3tts_codec_stream_set_pitch(self.h, int(sid), int(ratio)))
+        d = self.__dict__.setdefault("_codec_stream_pitch", {})
+        if int(ratio) == 1000:
+            d.pop(int(sid), None)
+        else:
+            d[int(sid)] = int(ratio)
+
+    # ---- the pitch stage on its own (include/q3tts.h "pitch") ----
+    def pitch_begin(self, ratio):
+        """a stage that takes 24 kHz float32 and delivers it at the same length with the fundamental multiplied by ratio / 1000
+        (permille, 500 .. 2000, not 1000) -> stage id"""
+        sid = C.c_int(-1)
+        self.L.q3tts_pitch_begin.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
+        self._ck(self.L.q3tts_pitch_begin(self.h, int(ratio), C.byref(sid)))
+        return sid.value
+
+    def pitch_push_batch(self, ids, pcm_list, finish=None):
+        """more 24 kHz samples for many pitch stages in one launch (q3tts_pitch_push_batch_host); finish: one flag per stage (its
+        tail is flushed with this push) -> one float32 array per stage"""
+        n = len(ids)
+        if n == 0:
+            return []
+        if len(pcm_list) != n or (finish is not None and len(finish) != n):
+            raise ValueError("pitch_push_batch: one sample array (and one finish flag) per stage")
+        xs = [np.ascontiguousarray(a, np.float32).reshape(-1) for a in pcm_list]
+        fin = np.zeros(n, np.uint8) if finish is None else np.ascontiguousarray([1 if f else 0 for f in finish], np.uint8)
+        lens = np.array([x.size for x in xs], np.int64)
+        cap = int(lens.max()) + 1248                 # the push plus what the stage held back
+        outs = [np.empty(cap, np.float32) for _ in range(n)]
+        xptr = (C.c_void_p * n)(*[x.ctypes.data if x.size else None for x in xs])
+        optr = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        out_len = np.zeros(n, np.int64)
+        self.L.q3tts_pitch_push_batch_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        self._ck(self.L.q3tts_pitch_push_batch_host(self.h, n, _p(np.ascontiguousarray(ids, np.int32)), C.cast(xptr, C.c_void_p), _p(lens), _p(fin),
+                                                    C.cast(optr, C.c_void_p), cap, _p(out_len)))
+        return [outs[i][: out_len[i]] for i in range(n)]
+
+    def pitch_end(self, stage_id):
+        self.L.q3tts_pitch_end.argtypes = [C.c_void_p, C.c_int]
+        self._ck(self.L.q3tts_pitch_end(self.h, int(stage_id)))
+
+    def set_pitch(self, ratio=1000):
+        """q3tts_engine_set_pitch: the streaming entries deliver through a pitch stage; 1000 takes it away"""
+        self.L.q3tts_engine_set_pitch.argtypes = [C.c_void_p, C.c_int32]
+        self._ck(self.L.q3tts_engine_set_pitch(self.h, int(ratio)))
 
     def codec_stream_set_level(self, sid, gain_cb, ceiling_permille):
         """q3tts_codec_stream_set_level: gain in centibels, ceiling in permille (0: gain only); refused once the stream has delivered a
@@ -735,10 +793,13 @@ class Engine:
         fmts = self.__dict__.setdefault("_codec_stream_fmt", {})
         spds = self.__dict__.setdefault("_codec_stream_speed", {})
         lvls = self.__dict__.setdefault("_codec_stream_level", {})
-        if finish is None and not any(int(i) in fmts or int(i) in spds or int(i) in lvls for i in ids):
+        pits = self.__dict__.setdefault("_codec_stream_pitch", {})
+        if finish is None and not any(int(i) in fmts or int(i) in spds or int(i) in lvls or int(i) in pits for i in ids):
             return self._push_batch(ids, cs, offs)
         flat = np.ascontiguousarray(np.concatenate(cs)) if sum(c_.shape[0] for c_ in cs) else np.zeros((1, self.cfg.n_groups), np.int64)
         n24 = self.codec_decode_len(max(max(c_.shape[0] for c_ in cs), 1)) + 4096
+        if any(int(i) in pits for i in ids):
+            n24 += 1248                    # behind a pitch stage: plus what it held back
         if any(int(i) in spds for i in ids):
             n24 = (n24 + 1320) * 2 + 720   # behind a stretcher: the slowest speed doubles the push plus what it held back
         if any(int(i) in lvls for i in ids):
@@ -817,6 +878,7 @@ class Engine:
         self.__dict__.setdefault("_codec_stream_fmt", {}).pop(int(sid), None)
         self.__dict__.setdefault("_codec_stream_speed", {}).pop(int(sid), None)
         self.__dict__.setdefault("_codec_stream_level", {}).pop(int(sid), None)
+        self.__dict__.setdefault("_codec_stream_pitch", {}).pop(int(sid), None)
 
     def slot_codec_decode_range(self, slot, frame_begin, frame_end, left_context):
         """samples owned by frames [frame_begin, frame_end) of a slot (streaming while it generates)"""
@@ -1540,7 +1602,7 @@ class Engine:
         self._ck(rc)
         return [pcm[i][: pcm_len[i]] for i in range(n)], [codes[i, : nfr[i]] for i in range(n)], nfr
 
-    def _sink_job(self, sample_rate, dtype, on_audio, n, run, speed=None, level=(0, 0)):
+    def _sink_job(self, sample_rate, dtype, on_audio, n, run, speed=None, level=(0, 0), pitch=None):
         """a streaming job through a sink of its own: run(None-pcm_out) with the sink set, the sink taken away afterwards; the chunks
         on_audio saw are also returned joined per utterance"""
         fmt = _pcm_format("float32" if dtype is None else dtype)
@@ -1552,10 +1614,12 @@ class Engine:
         self.set_speed(speed)   # refuses a bad speed before the sink is set
         try:
             self.set_level(*level)
+            self.set_pitch(1000 if pitch is None else pitch)
             self.set_sink(24000 if sample_rate is None else sample_rate, "int16" if fmt == PCM_S16 else "float32", tee)
         except BaseException:
             self.set_speed(None)
             self.set_level(0, 0)
+            self.set_pitch(1000)
             raise
         try:
             rc = run()
@@ -1564,6 +1628,7 @@ class Engine:
             self.set_sink(None)
             self.set_speed(None)
             self.set_level(0, 0)
+            self.set_pitch(1000)
         if raised:
             raise raised[0]
         self._ck(rc)
@@ -1571,7 +1636,7 @@ class Engine:
         return [np.concatenate(g) if g else np.zeros(0, npdt) for g in got]
 
     def synthesize_stream(self, token_lists, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
-                          max_new_per_utt=None, instructs=None, sample_rate=None, dtype=None, speed=None, gain_db=None, ceiling=None):
+                          max_new_per_utt=None, instructs=None, sample_rate=None, dtype=None, speed=None, gain_db=None, ceiling=None, pitch=None):
         """synthesize_batch that delivers audio while it generates (q3tts_synthesize_stream_host): every chunk_frames steps
         on_audio(utt, frame_begin, frame_end, pcm, finished) is called once per utterance with new audio (pcm: a copy); a truthy return
         cancels the job (RuntimeError "cancelled by callback").  Returns what synthesize_batch returns."""
@@ -1614,7 +1679,9 @@ class Engine:
         if speed is not None and int(speed) == 1000:
             speed = None   # no stage
         level = level_params(gain_db, ceiling)   # gain_db / ceiling: the chunks pass a level stage behind the stretcher (q3tts_engine_set_level)
-        if sample_rate is not None or dtype is not None or speed is not None or level != (0, 0):   # through a sink (q3tts_engine_set_sink): sample_rate / dtype are the chunks' and the result's; speed (permille): time-stretched first (q3tts_engine_set_speed)
+        if pitch is not None and int(pitch) == 1000:
+            pitch = None   # no stage; otherwise (permille) the chunks pass a pitch stage first (q3tts_engine_set_pitch)
+        if sample_rate is not None or dtype is not None or speed is not None or level != (0, 0) or pitch is not None:   # through a sink (q3tts_engine_set_sink): sample_rate / dtype are the chunks' and the result's; speed (permille): time-stretched first (q3tts_engine_set_speed)
             def run():
                 if ins_flat is not None:
                     return self.L.q3tts_synthesize_instruct_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
@@ -1623,7 +1690,7 @@ class Engine:
                 return self.L.q3tts_synthesize_stream_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
                                                            seed, int(ignore_eos), None, 0, _p(pcm_len), _p(nfr),
                                                            _p(codes) if want_codes else None, int(chunk_frames), cb, None)
-            outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed, level)
+            outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed, level, pitch)
             return outs, ([codes[i, : nfr[i]] for i in range(n)] if want_codes else None), nfr
         if ins_flat is not None:
             rc = self.L.q3tts_synthesize_instruct_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
@@ -1641,7 +1708,7 @@ class Engine:
         return outs, cl, nfr
 
     def synthesize_live(self, n_utt, text_source, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
-                        max_new_per_utt=None, sample_rate=None, dtype=None, speed=None, gain_db=None, ceiling=None):
+                        max_new_per_utt=None, sample_rate=None, dtype=None, speed=None, gain_db=None, ceiling=None, pitch=None):
         """synthesize_stream for texts that arrive while their audio is generated (q3tts_synthesize_live_host): text_source(utt) ->
         (ids, closed) is polled between decode chunks for every utterance whose text is open — new ids (possibly none) and whether the
         text has ended; None cancels the job (RuntimeError "cancelled by callback").  An utterance's ids are those synthesize_stream
@@ -1701,13 +1768,15 @@ class Engine:
         if speed is not None and int(speed) == 1000:
             speed = None
         level = level_params(gain_db, ceiling)
-        if sample_rate is not None or dtype is not None or speed is not None or level != (0, 0):   # through a sink and / or a stretcher, as synthesize_stream
+        if pitch is not None and int(pitch) == 1000:
+            pitch = None
+        if sample_rate is not None or dtype is not None or speed is not None or level != (0, 0) or pitch is not None:   # through a sink and / or a stretcher, as synthesize_stream
             def run():
                 return self.L.q3tts_synthesize_live_host(self.h, n, tcb, None, lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
                                                          seed, int(ignore_eos), None, 0, _p(pcm_len), _p(nfr),
                                                          _p(codes) if want_codes else None, int(chunk_frames), cb, None)
             try:
-                outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed, level)
+                outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed, level, pitch)
             except BaseException:
                 if raised:
                     raise raised[0]
@@ -1920,6 +1989,34 @@ def level_params(gain_db=None, ceiling=None):
     if ceiling is not None and float(ceiling) > 0 and c == 0:
         raise ValueError("level: ceiling %r rounds to 0 permille, which means no limiter" % (ceiling,))
     return g, c
+
+
+def pitch_ratio(cents):
+    """q3tts_pitch_ratio: round(1000 * 2^(cents / 1200)), the permille ratio of a shift by cents.  Host-only; ValueError outside
+    -1200 .. 1200."""
+    Lb = lib()
+    Lb.q3tts_pitch_ratio.argtypes = [C.c_double]
+    Lb.q3tts_pitch_ratio.restype = C.c_int32
+    Lb.q3tts_pitch_last_error.restype = C.c_char_p
+    r = int(Lb.q3tts_pitch_ratio(float(cents)))
+    if r < 0:
+        raise ValueError(Lb.q3tts_pitch_last_error().decode())
+    return r
+
+
+def pitch_emitted(n_received, finished=False):
+    """q3tts_pitch_emitted: the samples a pitch stage has delivered in all after n_received samples.  Host-only; ValueError for a
+    negative count."""
+    Lb = lib()
+    Lb.q3tts_pitch_emitted.argtypes = [C.c_int64, C.c_int]
+    Lb.q3tts_pitch_emitted.restype = C.c_int64
+    Lb.q3tts_pitch_last_error.restype = C.c_char_p
+    if not -2**63 <= int(n_received) < 2**63:
+        raise ValueError("pitch_emitted: %d does not fit the C type" % int(n_received))
+    n = int(Lb.q3tts_pitch_emitted(int(n_received), 1 if finished else 0))
+    if n < 0:
+        raise ValueError(Lb.q3tts_pitch_last_error().decode())
+    return n
 
 
 def level_gain(gain_cb):
