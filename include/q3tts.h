@@ -851,6 +851,78 @@ int q3tts_codec_stream_set_pitch(q3tts_engine* e, int stream_id, int32_t ratio_p
  * use are untouched.  1000: none. */
 int q3tts_engine_set_pitch(q3tts_engine* e, int32_t ratio_permille);
 
+/* ---- loudness: carried-state BS.1770 meter and normaliser ([HINT] no counterpart in the reference, whose wav_writer.cpp peak
+ * normalisation is dead code and needs the whole clip) ----
+ * A stage between the stretcher and the level stage at 24 kHz: vocoder -> pitch -> stretcher -> loudness -> level -> sink, on the GPU,
+ * all stages of a push in one launch.  It measures programme loudness as ITU-R BS.1770-4 does and, given a target, moves a gain towards
+ * it by at most 1 dB per 100 ms; a boost is caught by the limiter behind it.
+ * Parameters: target_dlufs, the target in tenths of a LUFS, -400 .. -50, or 0: meter only.  range_cb, the largest boost or cut in
+ * centibels, 0 .. 400; R = 10^(range_cb / 200).  start_cb, the gain before anything is measured, -400 .. 400;
+ * G_-1 = (float)10^(start_cb / 200) (a caller that served this voice before passes the last gain it was told).  There is no "no stage"
+ * value: not setting the stage is "no stage".  (0, ., .) is meter only: y[k] = x[k] bit for bit, E(R) = R, no latency, and the
+ * measurement is still produced (its G_b stay G_-1).
+ * 1. K-weighting at fs = 24 000, in double: two biquads re-derived from BS.1770's analogue prototype by the bilinear transform.
+ *    Shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / fs), Vh = 10^(G / 20),
+ *    Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2; b = ((Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0),
+ *    a = (2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0).  High-pass: f0 = 38.13547087602444, Q = 0.5003270373238773; b = (1, -2, 1), a as
+ *    above with this K and Q.  At 48 000 the formulas give the BS.1770-4 table to 9e-16.
+ * 2. Recursion: x[k] widened exactly to double; ff = (b0 x[k] + b1 x[k-1]) + b2 x[k-2], u[k] = (ff - a2 u[k-2]) - a1 u[k-1], every
+ *    operation one rounded fp64 operation in this order; the second biquad has the same shape on u and gives v.  History is zero before
+ *    sample 0.  The library is built with -ffp-contract=off, so these are the host's IEEE operations.
+ * 3. Energy: z = v[k] v[k], q[k] = (int64)floor((z < 4.0 ? z : 4.0) 2^32).  Sub-block b covers samples [2400 b, 2400 b + 2400);
+ *    E_b = sum of its q: an integer sum, exact in any order, below 2^46.
+ * 4. Gate: for b >= 3, W_b = E_{b-3} + E_{b-2} + E_{b-1} + E_b, the standard's 400 ms block at 75 % overlap.  W_b counts when
+ *    W_b >= 4834272 = floor(9600 2^32 10^((-70 + 0.691) / 10)).  A = the sum of the counted W, N their number (A stays below 2^63 over
+ *    the one hour a stage accepts).  The -10 LU relative gate is not applied on the device; q3tts_loudness_lufs applies it.
+ * 5. Gain after sub-block b: N = 0 or meter only: T = G_{b-1}.  Otherwise P = (double)A / ((double)N 41231686041600.0),
+ *    d = sqrt(PT / P) with PT = 10^((target_dlufs / 10 + 0.691) / 10) formed once on the host, d clamped to [1 / R, R] in double (1 / R
+ *    one division on the host), T = (float)d.  Slew, 1 dB per sub-block: G_b = min(max(T, G_{b-1} DN), G_{b-1} UP),
+ *    UP = (float)10^(1/20), DN = (float)10^(-1/20), fp32 products.  Division, sqrt and int -> double are correctly rounded.
+ * 6. Output: for k in sub-block b, i = k - 2400 b: y[k] = x[k] (G_{b-1} + (G_b - G_{b-1}) ((float)i / 2400.0f)), each operation one
+ *    rounded fp32 operation.  Samples of a final partial sub-block: y[k] = x[k] G of the last complete one, unramped.
+ * 7. Host rule: a stage that has received R samples and is not finished has emitted E(R) = 2400 floor(R / 2400); finished with n
+ *    samples, n.  A push delivers E(after) - E(before).  The latency is 100 ms: what a causal measurement costs.
+ * 8. Carry, in two alternating halves: six doubles of filter history; E of the last three sub-blocks and the running sum of the open
+ *    one; A, N and G; the fewer than 2400 input samples not yet emitted.
+ * So samples, energies and gains depend on the input and the parameters alone: never on how the audio was cut into pushes or on which
+ * stages shared a launch.  Non-finite input: the formulas apply as written (z < 4.0 is false for a NaN, so its q is 4 2^32).
+ * Known limits: a primed stream's loudness stage (q3tts_codec_stream_prime_batch_host, q3tts_synthesize_continue_stream_host) starts
+ * from zero history and start_cb, like the other stages start from silence. */
+#define Q3TTS_LOUDNESS_MOMENTARY 0   /* the last window of four sub-blocks (400 ms) */
+#define Q3TTS_LOUDNESS_SHORT_TERM 1  /* the last thirty sub-blocks (3 s) */
+#define Q3TTS_LOUDNESS_INTEGRATED 2  /* BS.1770: windows of four, the absolute gate (W >= 4834272), then the relative gate 10 LU below their mean */
+/* Host only, no engine.  The ten doubles { b0, b1, b2, a1, a2 } of the shelf, then of the high-pass, by the formulas above at `rate`
+ * (8000 .. 384000); at 24 000 the very doubles the device uses.  -1 outside the range (q3tts_loudness_last_error() then says so;
+ * thread-local, valid until the thread's next loudness_coeffs / _emitted / _lufs call). */
+int q3tts_loudness_coeffs(int32_t rate, double out[10]);
+/* Host only: outputs a stage has emitted in all after n_received samples (of the parameters only target_dlufs == 0 matters).  -1 for
+ * n_received < 0 or a target out of range, which the message names. */
+int64_t q3tts_loudness_emitted(int32_t target_dlufs, int64_t n_received, int finished);
+/* Host only: LUFS of n sub-block energies E_b as a push reports them, -0.691 + 10 log10(mean square).  -inf when the span has not
+ * arrived yet or nothing passes the gates; NaN for a bad argument (q3tts_loudness_last_error()). */
+double q3tts_loudness_lufs(const int64_t* E, int64_t n, int mode);
+const char* q3tts_loudness_last_error(void);
+/* Loudness stages on their own: the stage by itself, fed 24 kHz float from the host.  A stage accepts at most one hour of input
+ * (86 400 000 samples), a push at most 1 440 000.  At most 4096 stages are open at a time (vocoder streams' included).  A value out of
+ * range is refused with the value named. */
+int q3tts_loudness_begin(q3tts_engine* e, int32_t target_dlufs, int32_t range_cb, int32_t start_cb, int* id);
+/* As q3tts_level_push_batch_host: n stages (distinct, open, not finished), validated completely before any stage moves.  Optional
+ * report (as the stretcher's offsets_out): energies_out[i] and gains_out[i] (either NULL ok; n_in[i] / 2400 + 1 entries each) receive
+ * E_b and G_b of the sub-blocks push i completed, n_blocks[i] (NULL ok) their number. */
+int q3tts_loudness_push_batch_host(q3tts_engine* e, int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in,
+                                   const uint8_t* finish, float* const* out, int64_t cap_samples, int64_t* out_len,
+                                   int64_t* const* energies_out, float* const* gains_out, int64_t* n_blocks);
+int q3tts_loudness_end(q3tts_engine* e, int id);
+/* Vocoder streams.  A stream delivers through a loudness stage from its first sample on: refused, by name, once the stream has
+ * delivered a sample.  q3tts_codec_stream_push_batch_any_host serves such streams: the stage reads its input where the stage in front
+ * left it and feeds the stream's later stages in the same push; finish[s] flushes pitch, stretcher, loudness, level, sink in that order
+ * and is allowed on a stream with a loudness stage and no sink.  The float entries refuse a stream with a loudness stage by name. */
+int q3tts_codec_stream_set_loudness(q3tts_engine* e, int stream_id, int32_t target_dlufs, int32_t range_cb, int32_t start_cb);
+/* The scheduler: one setter for the four streaming entries, beside q3tts_engine_set_sink / _speed / _level / _pitch.  enabled 0 takes
+ * the stage away (the other arguments are not looked at).  The finished = 1 call carries the stage's tail, so an utterance's calls add
+ * up to the length they have without the stage.  Codes, frame counts and RNG use are untouched; the callback's signature stays. */
+int q3tts_engine_set_loudness(q3tts_engine* e, int enabled, int32_t target_dlufs, int32_t range_cb, int32_t start_cb);
+
 /* ---- text front end: the reference's byte-level BPE tokenizer ---- */
 /* Replaces leaxer_qwen::io::load_vocab / load_merges / is_tokenizer_ready / tokenize (reference
  * src/io/tokenizer.h:13-22, src/io/tokenizer.cpp:538-561) with the same ids for the same files and text.

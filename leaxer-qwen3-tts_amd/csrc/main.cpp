@@ -79,6 +79,8 @@ static void usage(const char* prog) {
     printf("  --out-rate R          write the WAV at R Hz (4000 .. 192000; default 24000): band-limited resampling on the GPU, in the stream's sink with --stream-chunk\n");
     printf("  --speed X             speaking rate (0.5 .. 2.0; default 1.0): X times as fast at the same pitch, WSOLA time stretch on the GPU; composes with --out-rate and --stream-chunk\n");
     printf("  --pitch ST            pitch shift in semitones (-12 .. +12; default 0): the fundamental moves, the formants stay, TD-PSOLA on the GPU ahead of --speed; composes with --speed, --gain, --limit and --out-rate\n");
+    printf("  --loudness LUFS       programme loudness to aim for (-40 .. -5; default: none): a BS.1770 meter and a gain that follows it by at most 1 dB per 100 ms, on the GPU behind --speed and ahead of --gain / --limit; 100 ms latency; composes with --pitch, --speed, --gain, --limit and --out-rate\n");
+    printf("  --loudness-range DB   with --loudness: the largest boost or cut (0 .. 40; default 20)\n");
     printf("  --gain DB             output gain in decibels (-60 .. +40, rounded to 0.1 dB; default 0), applied on the GPU behind --speed and ahead of --out-rate\n");
     printf("  --limit X             look-ahead limiter behind the gain: no sample leaves the stage above X (0.001 .. 1.0, rounded to 0.001; default: none), 5.3 ms look-ahead\n");
     printf("  --feed K              with --stream-chunk: hand the text to the engine K tokens at a time while it generates (live text; same codes, and with --save-codes the same samples as without --feed)\n  -h, --help\n");
@@ -157,7 +159,8 @@ int main(int argc, char** argv) {
     uint64_t seed = 0;
     int stream_chunk = 0, feed = 0, encode_chunk = 0, out_rate = config::SAMPLE_RATE;
     bool have_encode_chunk = false;
-    double speed = 1.0, gain_db = 0.0, limit = 0.0, pitch_st = 0.0;
+    double speed = 1.0, gain_db = 0.0, limit = 0.0, pitch_st = 0.0, loudness = 0.0, loudness_range = 20.0;
+    bool have_loudness = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         const bool more = i + 1 < argc;
@@ -187,6 +190,8 @@ int main(int argc, char** argv) {
         else if (a == "--out-rate" && more) out_rate = atoi(argv[++i]);
         else if (a == "--speed" && more) speed = atof(argv[++i]);
         else if (a == "--pitch" && more) pitch_st = atof(argv[++i]);
+        else if (a == "--loudness" && more) { loudness = atof(argv[++i]); have_loudness = true; }
+        else if (a == "--loudness-range" && more) loudness_range = atof(argv[++i]);
         else if (a == "--gain" && more) gain_db = atof(argv[++i]);
         else if (a == "--limit" && more) limit = atof(argv[++i]);
     }
@@ -272,6 +277,11 @@ int main(int argc, char** argv) {
     // --pitch: r = round(1000 2^(ST / 12)) permille; 0 semitones is no stage (the bytes written without the flag)
     if (!(pitch_st == pitch_st) || pitch_st < -12.0 || pitch_st > 12.0) { fprintf(stderr, "Error: --pitch %g is outside -12 .. +12\n", pitch_st); return 1; }
     if (pitch_st != 0.0 && !engine.set_pitch((float)pitch_st)) { fprintf(stderr, "Error: --pitch %g: %s\n", pitch_st, engine.get_error().c_str()); return 1; }
+    // --loudness / --loudness-range: tenths of a LUFS and centibels; without the flag there is no stage (the bytes written before)
+    if (have_loudness && !engine.set_loudness((float)loudness, (float)loudness_range)) {
+        fprintf(stderr, "Error: --loudness %g --loudness-range %g: %s\n", loudness, loudness_range, engine.get_error().c_str());
+        return 1;
+    }
     // --gain / --limit: centibels and permille; neither given is no stage (the bytes written without the flags)
     if ((gain_db != 0.0 || limit != 0.0) && !engine.set_level((float)gain_db, (float)limit)) {
         fprintf(stderr, "Error: --gain %g --limit %g: %s\n", gain_db, limit, engine.get_error().c_str());

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <stdexcept>
 
 namespace q3 {
@@ -239,6 +240,59 @@ std::vector<float> pitch_windows() {
     for (int P = kPitchPmin; P <= kPitchPmax; ++P)
         for (int m = 0; m < 2 * P; ++m) w[(size_t)(pitch_window_offset(P) + m)] = (float)(0.5 - 0.5 * std::cos(pi * (double)m / (double)P));
     return w;
+}
+
+// ---- loudness (q3_audio.h) ----
+void loudness_check(int target, int range, int start) {
+    if (target != 0 && (target < kLoudTargetMin || target > kLoudTargetMax))
+        throw std::invalid_argument("loudness: target " + std::to_string(target) + " tenths of a LUFS is outside " + std::to_string(kLoudTargetMin) + " .. " + std::to_string(kLoudTargetMax) + " (0: meter only)");
+    if (range < 0 || range > kLoudRangeMax)
+        throw std::invalid_argument("loudness: range " + std::to_string(range) + " centibels is outside 0 .. " + std::to_string(kLoudRangeMax));
+    if (start < kLoudStartMin || start > kLoudStartMax)
+        throw std::invalid_argument("loudness: start gain " + std::to_string(start) + " centibels is outside " + std::to_string(kLoudStartMin) + " .. " + std::to_string(kLoudStartMax));
+}
+void loudness_coeffs(int rate, double out[10]) {
+    const double pi = 3.14159265358979323846;
+    {   // the shelf
+        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+        const double K = std::tan(pi * f0 / (double)rate), Vh = std::pow(10.0, G / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+        const double KQ = K / Q, K2 = K * K, a0 = 1.0 + KQ + K2;
+        out[0] = (Vh + Vb * KQ + K2) / a0; out[1] = 2.0 * (K2 - Vh) / a0; out[2] = (Vh - Vb * KQ + K2) / a0;
+        out[3] = 2.0 * (K2 - 1.0) / a0; out[4] = (1.0 - KQ + K2) / a0;
+    }
+    {   // the high-pass
+        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+        const double K = std::tan(pi * f0 / (double)rate);
+        const double KQ = K / Q, K2 = K * K, a0 = 1.0 + KQ + K2;
+        out[5] = 1.0; out[6] = -2.0; out[7] = 1.0;
+        out[8] = 2.0 * (K2 - 1.0) / a0; out[9] = (1.0 - KQ + K2) / a0;
+    }
+}
+double loudness_lufs(const int64_t* E, int64_t n, int mode) {
+    const double ninf = -std::numeric_limits<double>::infinity();
+    auto lufs = [&](double mean_square) { return mean_square > 0.0 ? -0.691 + 10.0 * std::log10(mean_square) : ninf; };
+    if (mode == 0 || mode == 1) {   // the last 4 / 30 sub-blocks, ungated
+        const int64_t span = mode == 0 ? 4 : 30;
+        if (n < span) return ninf;
+        double s = 0.0;
+        for (int64_t b = n - span; b < n; ++b) s += (double)E[b];
+        return lufs(s / ((double)span * (double)kLoudBlock * 4294967296.0));
+    }
+    // integrated: windows of four at 75 % overlap; the absolute gate; the relative gate 10 LU below the mean of what passed it
+    double sum_abs = 0.0; int64_t n_abs = 0;
+    for (int64_t b = 3; b < n; ++b) {
+        const int64_t W = E[b - 3] + E[b - 2] + E[b - 1] + E[b];
+        if (W >= kLoudGate) { sum_abs += (double)W / kLoudNorm; ++n_abs; }
+    }
+    if (n_abs == 0) return ninf;
+    const double rel = 0.1 * (sum_abs / (double)n_abs);
+    double sum_rel = 0.0; int64_t n_rel = 0;
+    for (int64_t b = 3; b < n; ++b) {
+        const int64_t W = E[b - 3] + E[b - 2] + E[b - 1] + E[b];
+        const double z = (double)W / kLoudNorm;
+        if (W >= kLoudGate && z > rel) { sum_rel += z; ++n_rel; }
+    }
+    return n_rel == 0 ? ninf : lufs(sum_rel / (double)n_rel);
 }
 
 // ---------------------------------------------------------------------------------------------

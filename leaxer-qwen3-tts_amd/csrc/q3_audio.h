@@ -103,6 +103,31 @@ constexpr int pitch_window_offset(int P) { return P * (P - 1) - kPitchPmin * (kP
 constexpr int kPitchWindowFloats = (kPitchPmax + 1) * kPitchPmax - kPitchPmin * (kPitchPmin - 1);   // 158 144
 std::vector<float> pitch_windows();
 
+// ---- loudness: BS.1770 meter and normaliser at 24 kHz (the arithmetic is fixed in include/q3tts.h) ----
+// target in tenths of a LUFS (kLoudTargetMin .. kLoudTargetMax; 0: meter only), range in centibels (0 .. kLoudRangeMax), start gain in
+// centibels (kLoudStartMin .. kLoudStartMax).  A sub-block is kLoudBlock samples (100 ms); four of them are the standard's 400 ms block.
+// A window of four counts from kLoudGate on: floor(9600 2^32 10^((-70 + 0.691) / 10)); kLoudNorm = 9600 2^32 turns a window's integer
+// energy into a mean square.  A stage's half: kLoudStateWords 8-byte words (six doubles of filter history x[k-1], x[k-2], u[k-1],
+// u[k-2], v[k-1], v[k-2]; then int64 E_{b-1}, E_{b-2}, E_{b-3}, the open sub-block's sum, A, N; then G's bits) and kLoudBlock floats of
+// input not yet emitted.
+constexpr int kLoudTargetMin = -400, kLoudTargetMax = -50, kLoudRangeMax = 400, kLoudStartMin = -400, kLoudStartMax = 400;
+constexpr int kLoudBlock = 2400;
+constexpr int64_t kLoudGate = 4834272;
+constexpr double kLoudNorm = 41231686041600.0;
+constexpr float kLoudUp = (float)1.1220184543019633, kLoudDn = (float)0.8912509381337456;   // (float)10^(1/20), (float)10^(-1/20)
+constexpr int kLoudStateWords = 16;
+constexpr size_t kLoudHalfBytes = (size_t)kLoudStateWords * 8 + (size_t)kLoudBlock * sizeof(float);
+void loudness_check(int target_dlufs, int range_cb, int start_cb);   // throws std::invalid_argument naming the value that is out of range
+// the two biquads at `rate`: out = { b0, b1, b2, a1, a2 } of the shelf, then of the high-pass (the header's formulas, in double)
+void loudness_coeffs(int rate, double out[10]);
+// outputs a stage has emitted in all after n_received samples: meter only n; else unfinished kLoudBlock floor(n / kLoudBlock), finished n
+inline int64_t loudness_emitted(int target_dlufs, int64_t n_received, bool finished) {
+    return target_dlufs == 0 || finished ? n_received : kLoudBlock * (n_received / kLoudBlock);
+}
+// LUFS of n sub-block energies: mode 0 momentary (the last four), 1 short-term (the last thirty), 2 integrated (absolute gate, then the
+// relative gate at -10 LU).  -inf when the span is not there or nothing passes the gates.
+double loudness_lufs(const int64_t* E, int64_t n, int mode);
+
 struct MelSpec { // the settings of tts_onnx.cpp:347-354
     int sample_rate = 24000, n_fft = 1024, hop = 256, win = 1024, n_mels = 128;
     float fmin = 0.0f, fmax = 12000.0f;

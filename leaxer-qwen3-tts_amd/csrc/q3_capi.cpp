@@ -21,6 +21,8 @@ struct q3tts_engine {
     int32_t speed = 1000;                           // q3tts_engine_set_speed (1000: none)
     int32_t gain_cb = 0, ceiling = 0;               // q3tts_engine_set_level ((0, 0): none)
     int32_t pitch = 1000;                           // q3tts_engine_set_pitch (1000: none)
+    bool loud = false;                              // q3tts_engine_set_loudness / _clear_loudness
+    int32_t loud_target = 0, loud_range = 0, loud_start = 0;
 };
 static std::string g_create_err;
 
@@ -565,6 +567,84 @@ int q3tts_engine_set_pitch(q3tts_engine* h, int32_t ratio_permille) {
     Q3_API_BEGIN(h)
     try { q3::pitch_check(ratio_permille); } catch (const std::invalid_argument& ex) { throw q3::Error(std::string("engine_set_pitch: ") + ex.what()); }
     h->pitch = ratio_permille;
+    return 0;
+    Q3_API_END(h)
+}
+
+// ---- loudness (include/q3tts.h "loudness") ----
+static thread_local std::string g_loud_err;
+const char* q3tts_loudness_last_error(void) { return g_loud_err.c_str(); }
+int q3tts_loudness_coeffs(int32_t rate, double out[10]) {
+    g_loud_err.clear();
+    if (!out) { g_loud_err = "loudness: NULL argument"; return -1; }
+    if (rate < 8000 || rate > 384000) { g_loud_err = "loudness: rate " + std::to_string(rate) + " is outside 8000 .. 384000"; return -1; }
+    q3::loudness_coeffs(rate, out);
+    return 0;
+}
+int64_t q3tts_loudness_emitted(int32_t target_dlufs, int64_t n_received, int finished) {
+    g_loud_err.clear();
+    if (n_received < 0) { g_loud_err = "loudness: negative sample count " + std::to_string(n_received); return -1; }
+    try { q3::loudness_check(target_dlufs, 0, 0); } catch (const std::invalid_argument& ex) { g_loud_err = ex.what(); return -1; }
+    return q3::loudness_emitted(target_dlufs, n_received, finished != 0);
+}
+double q3tts_loudness_lufs(const int64_t* E, int64_t n, int mode) {
+    g_loud_err.clear();
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (n < 0 || (n > 0 && !E)) { g_loud_err = "loudness: " + std::string(n < 0 ? "negative sub-block count" : "NULL argument"); return nan; }
+    if (mode < Q3TTS_LOUDNESS_MOMENTARY || mode > Q3TTS_LOUDNESS_INTEGRATED) { g_loud_err = "loudness: mode " + std::to_string(mode) + " is none of momentary (0), short-term (1), integrated (2)"; return nan; }
+    for (int64_t b = 0; b < n; ++b) if (E[b] < 0 || E[b] > ((int64_t)1 << 46)) { g_loud_err = "loudness: energy " + std::to_string(E[b]) + " is no sub-block's"; return nan; }
+    return q3::loudness_lufs(E, n, mode);
+}
+int q3tts_loudness_begin(q3tts_engine* h, int32_t target_dlufs, int32_t range_cb, int32_t start_cb, int* id) {
+    Q3_API_BEGIN(h)
+    if (!id) throw q3::Error("loudness: NULL argument");
+    *id = h->e->loud.begin(target_dlufs, range_cb, start_cb);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_loudness_push_batch_host(q3tts_engine* h, int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in, const uint8_t* finish,
+                                   float* const* out, int64_t cap_samples, int64_t* out_len, int64_t* const* energies_out, float* const* gains_out,
+                                   int64_t* n_blocks) {
+    Q3_API_BEGIN(h)
+    // the stage reports four 4-byte words per sub-block a push closes (its energies, then its gains): staged here, handed on below
+    const bool report = (energies_out || gains_out) && n > 0 && n <= 65535 && n_in;
+    std::vector<std::vector<int32_t>> words(report ? (size_t)n : 0);
+    std::vector<int32_t*> wptr(report ? (size_t)n : 0);
+    for (size_t i = 0; i < words.size(); ++i) {
+        words[i].assign(4 * (size_t)(std::max<int64_t>(0, std::min<int64_t>(n_in[i], q3::Engine::kStageMaxPush)) / q3::kLoudBlock + 1), 0);
+        wptr[i] = words[i].data();
+    }
+    std::vector<int64_t> n_words(n > 0 && n <= 65535 ? (size_t)n : 0, 0);
+    h->e->loud.push_batch_host(n, ids, pcm24, n_in, finish, (void* const*)out, cap_samples, out_len, report ? wptr.data() : nullptr, n_words.empty() ? nullptr : n_words.data());
+    for (size_t i = 0; i < n_words.size(); ++i) {
+        const int64_t nb = n_words[i] / 4;
+        if (n_blocks) n_blocks[i] = nb;
+        if (!report || nb == 0) continue;
+        if (energies_out && energies_out[i]) memcpy(energies_out[i], words[i].data(), (size_t)nb * sizeof(int64_t));
+        if (gains_out && gains_out[i]) memcpy(gains_out[i], words[i].data() + 2 * nb, (size_t)nb * sizeof(float));
+    }
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_loudness_end(q3tts_engine* h, int id) {
+    Q3_API_BEGIN(h)
+    h->e->loud.end(id);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_codec_stream_set_loudness(q3tts_engine* h, int stream_id, int32_t target_dlufs, int32_t range_cb, int32_t start_cb) {
+    Q3_API_BEGIN(h)
+    h->e->codec_stream_set_loudness(stream_id, target_dlufs, range_cb, start_cb);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_engine_set_loudness(q3tts_engine* h, int enabled, int32_t target_dlufs, int32_t range_cb, int32_t start_cb) {
+    Q3_API_BEGIN(h)
+    if (enabled) {
+        try { q3::loudness_check(target_dlufs, range_cb, start_cb); } catch (const std::invalid_argument& ex) { throw q3::Error(std::string("engine_set_loudness: ") + ex.what()); }
+        h->loud_target = target_dlufs; h->loud_range = range_cb; h->loud_start = start_cb;
+    }
+    h->loud = enabled != 0;
     return 0;
     Q3_API_END(h)
 }
@@ -1238,7 +1318,8 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
     const bool pitched = h->pitch != 1000;
     const int64_t pitch_cap = chunk_cap + (pitched ? q3::kPitchLA : 0);
     const int64_t stage_cap = (sped ? ((pitch_cap + q3::kSpeedN + q3::kSpeedD + q3::kSpeedHs) * 1000 + speed - 1) / speed + q3::kSpeedHs : pitch_cap)
-                              + (h->ceiling != 0 ? q3::kLevelW - 1 : 0);
+                              + (h->ceiling != 0 ? q3::kLevelW - 1 : 0)
+                              + (h->loud ? q3::kLoudBlock - 1 : 0);   // a loudness stage (q3tts_engine_set_loudness) holds back less than one sub-block
     const q3::SinkPlan* splan = sunk ? &e.sink.plan_for(sink.sample_rate).plan : nullptr;
     const int64_t sink_cap = sunk ? ((stage_cap + splan->half) * splan->L + splan->M - 1) / splan->M + 2 : 0;
     const int64_t chunk_floats = sunk ? (sink_cap * (sink.format == Q3TTS_PCM_S16 ? 2 : 4) + 3) / 4 : stage_cap;   // per slot, 4-byte aligned
@@ -1251,7 +1332,8 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
         SlotStagesScope(Engine& en, const Engine::SlotStages& s) : e(en) { e.slot_stages = s; }
         ~SlotStagesScope() { e.slot_stages = Engine::SlotStages(); }
     } stages_scope(e, Engine::SlotStages{ sunk && !(sink.sample_rate == 24000 && sink.format == Q3TTS_PCM_F32) ? sink.sample_rate : 0, sink.format,
-                                          sped ? speed : 0, levelled ? h->gain_cb : 0, levelled ? h->ceiling : 0, pitched ? h->pitch : 0 });
+                                          sped ? speed : 0, levelled ? h->gain_cb : 0, levelled ? h->ceiling : 0, pitched ? h->pitch : 0,
+                                          h->loud ? 1 : 0, h->loud_target, h->loud_range, h->loud_start });
     std::vector<int32_t> slots, fb((size_t)B), fe((size_t)B);
     std::vector<int64_t> plen((size_t)B), written((size_t)n_utt, 0);
     std::vector<Engine::SlotInit> init;

@@ -69,9 +69,10 @@ struct CodecW {
     // stage: the stream's stages by Engine::StageKind, in the order its audio passes them (ids of Engine::stages[k]; -1: none, all -1:
     // the stream delivers 24 kHz float); delivered: a push has returned samples
     struct Stream { bool used = false; int cap = 0, P = 0, pshift = 0, n_done = 0, kv_rows = 0, h_cap = 0, h_rows = 0; float* kv = nullptr; float* hpost = nullptr;
-                    int stage[Engine::SK_N] = { -1, -1, -1, -1 }; bool delivered = false;
+                    int stage[Engine::SK_N] = { -1, -1, -1, -1, -1 }; bool delivered = false;
                     const char* has() const {   // what the float entries refuse the stream by; nullptr: no stage
-                        return stage[Engine::SK_SINK] >= 0 ? " has a sink" : stage[Engine::SK_SPEED] >= 0 ? " has a speed" : stage[Engine::SK_LEVEL] >= 0 ? " has a level" : stage[Engine::SK_PITCH] >= 0 ? " has a pitch" : nullptr; } };
+                        return stage[Engine::SK_SINK] >= 0 ? " has a sink" : stage[Engine::SK_SPEED] >= 0 ? " has a speed" : stage[Engine::SK_LEVEL] >= 0 ? " has a level" : stage[Engine::SK_PITCH] >= 0 ? " has a pitch"
+                             : stage[Engine::SK_LOUD] >= 0 ? " has a loudness" : nullptr; } };
     std::vector<Stream> streams;
     char* stream_arena = nullptr; size_t stream_arena_bytes = 0;
     std::vector<int> slot_stream;          // slot -> stream id (-1: none): q3tts_slot_codec_decode_range_host's implicit stream
@@ -806,6 +807,13 @@ void Engine::codec_stream_set_pitch(int sid, int ratio) {
     stream_set_stage(*this, sid, "codec_stream_set_pitch", SK_PITCH, [&] { return ratio == 1000 ? -1 : pitch.begin(ratio); });
 }
 
+void Engine::codec_stream_set_loudness(int sid, int target, int range, int start) {   // every value is a stage (target 0: a meter)
+    stream_set_stage(*this, sid, "codec_stream_set_loudness", SK_LOUD, [&] {
+        try { loudness_check(target, range, start); } catch (const std::invalid_argument& ex) { throw Error(std::string("codec_stream_set_loudness: ") + ex.what()); }
+        return loud.begin(target, range, start);
+    });
+}
+
 void Engine::codec_stream_set_speed(int sid, int speed_permille) {
     stream_set_stage(*this, sid, "codec_stream_set_speed", SK_SPEED, [&] { return speed_permille == 1000 ? -1 : speed.begin(speed_permille); });
 }
@@ -1279,6 +1287,7 @@ void Engine::slots_codec_decode_new(int n_slots, const int32_t* slots, float* co
             if (ss.pitch > 0 && ss.pitch != 1000 && have[SK_PITCH] < 0) codec_stream_set_pitch(sid, ss.pitch);
             if (ss.sink_rate > 0 && have[SK_SINK] < 0) codec_stream_set_sink(sid, ss.sink_rate, ss.sink_format);
             if (ss.speed > 0 && ss.speed != 1000 && have[SK_SPEED] < 0) codec_stream_set_speed(sid, ss.speed);
+            if (ss.loud != 0 && have[SK_LOUD] < 0) codec_stream_set_loudness(sid, ss.loud_target, ss.loud_range, ss.loud_start);
             if ((ss.gain_cb != 0 || ss.ceiling != 0) && have[SK_LEVEL] < 0) codec_stream_set_level(sid, ss.gain_cb, ss.ceiling);
         }
         const int a = W.streams[(size_t)sid].n_done;

@@ -518,6 +518,26 @@ struct PitchDesc {
 };
 void launch_psola(const PitchDesc* tab /* device, [n] */, int n, hipStream_t s);
 
+// ---- loudness (q3_loudness.cpp): BS.1770 meter and normaliser of 24 kHz float PCM, with carried state ----
+// One stage of one push.  half_in / half_out: the two halves of the stage's allocation (q3_audio.h: kLoudHalfBytes each: the state words,
+// then the input of the open sub-block, samples [kLoudBlock floor(n_before / kLoudBlock), n_before)).  The launch's workgroup filters
+// the push's n_new samples at x_new, adds their energy to the open sub-block and closes every sub-block that ends at or before n_total:
+// its E and G go to energies[j] / gains[j] (j counts the push's sub-blocks, n_blocks in all) and, when the stage is no meter, its
+// kLoudBlock ramped samples to out.  finish: the samples of the last, partial sub-block follow at the last gain.  A meter's out is the
+// push's input.  first: the stage has received nothing yet, so its state starts from zeros and g_start, not from half_in.
+struct LoudDesc {
+    const char* half_in = nullptr; char* half_out = nullptr;
+    const float* x_new = nullptr;       // n_new samples (never null: a push without samples points at the carry)
+    float* out = nullptr;               // n_out samples
+    int64_t* energies = nullptr; float* gains = nullptr;   // n_blocks each
+    double c[10] = {};                  // loudness_coeffs(24000)
+    double pt = 0.0, r_lo = 1.0, r_hi = 1.0;   // PT = 10^((target / 10 + 0.691) / 10); 1 / R and R
+    int64_t n_before = 0, n_total = 0;  // samples received before / with this push
+    float g_start = 1.0f;               // G_-1
+    int32_t n_new = 0, n_out = 0, n_blocks = 0, meter = 0, finish = 0, first = 0;
+};
+void launch_loudness(const LoudDesc* tab /* device, [n] */, int n, hipStream_t s);
+
 
 // ---- speaker encoder + GPU audio front end of the clone path (q3_speaker_kernels.hip) ----
 // One reference clip of a batch.  Activations of a batch lie clip after clip along time ([sum T][C]); every kernel that looks across

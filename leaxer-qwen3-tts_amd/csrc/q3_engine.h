@@ -176,15 +176,15 @@ public:
     void codec_rope_tables(int P);
 
     // ---- carried-state stages behind the vocoder: 24 kHz float on the device in, the stage's samples out ----
-    // Four kinds in one fixed order: the pitch stage (q3_pitch.cpp, 4o), the stretcher (q3_speed.cpp, 4m), the level stage
-    // (q3_level.cpp, 4n), the PCM sink (q3_pcm_sink.cpp, 4l).  Stage (q3_stage.cpp) is what they share: a call reserves once (the only
+    // Five kinds in one fixed order: the pitch stage (q3_pitch.cpp, 4o), the stretcher (q3_speed.cpp, 4m), the loudness stage
+    // (q3_loudness.cpp, 4p), the level stage (q3_level.cpp, 4n), the PCM sink (q3_pcm_sink.cpp, 4l).  Stage (q3_stage.cpp) is what they share: a call reserves once (the only
     // place the workspaces may grow, before anything is enqueued), launches once per set of stages whose input is ready, and commits
     // after the stream's sync.
-    enum StageKind { SK_PITCH = 0, SK_SPEED = 1, SK_LEVEL = 2, SK_SINK = 3, SK_N = 4 };
+    enum StageKind { SK_PITCH = 0, SK_SPEED = 1, SK_LOUD = 2, SK_LEVEL = 3, SK_SINK = 4, SK_N = 5 };
     static constexpr int kMaxStages = 4096;                          // of a kind, open at the same time (vocoder streams' included)
     static constexpr int64_t kStageMaxPush = 1440000;                // one push of a standalone entry: 60 s
     // x_dev: n_new samples on the device; out_host (NULL ok): min(n_out, cap) samples in the stage's output format land there;
-    // offs_host (NULL ok, the stretcher's): min(n_frames, offs_cap) frame offsets.  n_out, n_frames, out_dev / offs_dev (the push's
+    // offs_host (NULL ok, the stretcher's and the loudness stage's): min(n_frames, offs_cap) per-frame words.  n_out, n_frames, out_dev / offs_dev (the push's
     // output on the device, valid until the call's next reserve) and desc are set by plan and launch
     struct StagePush { int id = -1; const float* x_dev = nullptr; int64_t n_new = 0; bool finish = false; void* out_host = nullptr; int64_t cap = 0;
                        int32_t* offs_host = nullptr; int64_t offs_cap = 0; int64_t n_out = 0, n_frames = 0;
@@ -194,7 +194,7 @@ public:
     struct Stage {
         Engine& e;
         const char *name, *noun, *count_noun;                        // the refusals' words: "level", "level stage", "stage"
-        bool has_offs = false;                                       // the kind keeps frame offsets (the stretcher)
+        bool has_offs = false;                                       // the kind keeps per-frame words (the stretcher's offsets, the loudness stage's report)
         Stage(Engine& en, const char* nm, const char* nn, const char* cn) : e(en), name(nm), noun(nn), count_noun(cn) {}
         virtual ~Stage() {}
         // ---- what a kind supplies ----
@@ -254,6 +254,20 @@ public:
         bool fill(StagePush& q, size_t di, char* out, int32_t* offs) override;
         void issue(size_t d0, int n_live) override; void commit_one(const StagePush& q) override;
     } speed{*this};
+    // the loudness stage: BS.1770 meter and normaliser.  mem: its own allocation, two halves of kLoudHalfBytes (state words, then the
+    // open sub-block's input).  pt, r_lo, r_hi, g_start: formed once on the host from the parameters.  A push's n_frames is four words
+    // per sub-block it closes: its int64 energies, then its float gains.  The host rule needs nothing from the device.
+    struct Normaliser : StageSlot { int target = 0; double pt = 0.0, r_lo = 1.0, r_hi = 1.0; float g_start = 1.0f; char* mem = nullptr; };
+    struct LoudStage : StageOf<LoudDesc, Normaliser> {
+        explicit LoudStage(Engine& en) : StageOf(en, "loudness", "loudness stage", "stage", "no such loudness stage") { has_offs = true; loudness_coeffs(24000, coeffs); }
+        double coeffs[10];                                           // the two biquads at 24 kHz
+        int begin(int target_dlufs, int range_cb, int start_cb);
+        void free_all() override;
+        int64_t push_len(int id, int64_t n_new, bool finish) const override;
+        bool idle(StagePush& q) const override;                      // sets n_frames, four words per sub-block the push would close
+        bool fill(StagePush& q, size_t di, char* out, int32_t* offs) override;
+        void issue(size_t d0, int n_live) override; void commit_one(const StagePush& q) override;
+    } loud{*this};
     // the level stage: gain and look-ahead limiter.  mem: a limiter's own allocation, [2][kLevelCarry] floats of carry (the last 254
     // values of v); a gain-only stage (ceiling 0) carries nothing.  The host rule needs nothing from the device.
     struct Leveler : StageSlot { int gain_cb = 0, ceiling = 0; float* mem = nullptr; };
@@ -280,16 +294,18 @@ public:
         bool fill(StagePush& q, size_t di, char* out, int32_t* offs) override;
         void issue(size_t d0, int n_live) override; void commit_one(const StagePush& q) override;
     } sink{*this};
-    Stage* const stages[SK_N] = { &pitch, &speed, &level, &sink };           // by StageKind: the order a stream's audio passes them in
+    Stage* const stages[SK_N] = { &pitch, &speed, &loud, &level, &sink };         // by StageKind: the order a stream's audio passes them in
 
     // vocoder streams: a stream delivers its audio through the stages it has (codec_stream_push_batch; behind a sink StreamPush::pcm is read as
     // the sink's format, n_own counts its samples).  Refused once the stream has delivered a sample.  1000, (0, 0), 24 000 Hz float: no stage.
     void codec_stream_set_pitch(int sid, int ratio);
     void codec_stream_set_speed(int sid, int speed);
+    void codec_stream_set_loudness(int sid, int target_dlufs, int range_cb, int start_cb);
     void codec_stream_set_level(int sid, int gain_cb, int ceiling);
     void codec_stream_set_sink(int sid, int rate, int format);
-    // the scheduler's stages (q3tts_engine_set_sink / _speed / _level / _pitch): slots' implicit streams begin with them.  Zeros: none
-    struct SlotStages { int sink_rate = 0, sink_format = 0, speed = 0, gain_cb = 0, ceiling = 0, pitch = 0; } slot_stages;
+    // the scheduler's stages (q3tts_engine_set_sink / _speed / _level / _pitch / _loudness): slots' implicit streams begin with them.
+    // Zeros: none (loud: whether there is a loudness stage at all, since target 0 is a meter)
+    struct SlotStages { int sink_rate = 0, sink_format = 0, speed = 0, gain_cb = 0, ceiling = 0, pitch = 0, loud = 0, loud_target = 0, loud_range = 0, loud_start = 0; } slot_stages;
 
     // ---- batch-first session ops on DEVICE pointers (include/q3tts.h "_dev" entry points): row b <-> slot b ----
     // caller stream: the engine's stream first waits for what the caller has enqueued, the caller's stream then waits for the call's work

@@ -416,6 +416,62 @@ bool TTSEngine::apply_pitch(std::vector<float>& pcm24) {
     return ok;
 }
 
+bool TTSEngine::set_loudness(float lufs, float range_db) {
+    if (!ready_) return false;
+    const long T = std::lround(10.0 * (double)lufs), R = std::lround(10.0 * (double)range_db);
+    if (!(lufs == lufs) || T < -400 || T > -50) {
+        error_msg_ = "loudness " + std::to_string(lufs) + " LUFS is outside -40 .. -5";
+        std::cerr << "[TTSEngine] Loudness: " << error_msg_ << std::endl;
+        return false;
+    }
+    if (!(range_db == range_db) || R < 0 || R > 400) {
+        error_msg_ = "loudness range " + std::to_string(range_db) + " dB is outside 0 .. 40";
+        std::cerr << "[TTSEngine] Loudness: " << error_msg_ << std::endl;
+        return false;
+    }
+    if (q3tts_engine_set_loudness(h_, 1, (int32_t)T, (int32_t)R, 0) != 0) {
+        error_msg_ = q3tts_last_error(h_);
+        std::cerr << "[TTSEngine] Loudness: " << error_msg_ << std::endl;
+        return false;
+    }
+    loud_ = true; loud_target_ = (int)T; loud_range_ = (int)R;
+    return true;
+}
+
+void TTSEngine::clear_loudness() {
+    if (ready_) (void)q3tts_engine_set_loudness(h_, 0, 0, 0, 0);
+    loud_ = false;
+}
+
+bool TTSEngine::loudness_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out) {
+    const int64_t n_in = (int64_t)n;
+    const uint8_t fin = finish ? 1 : 0;
+    const int64_t before = q3tts_loudness_emitted(loud_target_, (int64_t)received_before, 0), after = q3tts_loudness_emitted(loud_target_, (int64_t)(received_before + n), fin);
+    if (before < 0 || after < before) return false;
+    const size_t have = out.size();
+    out.resize(have + (size_t)(after - before));
+    float* dst = out.data() + have;
+    int64_t len = 0;
+    return q3tts_loudness_push_batch_host(h_, 1, &id, &in, &n_in, &fin, &dst, after - before, &len, nullptr, nullptr, nullptr) == 0 && len == after - before;
+}
+
+bool TTSEngine::apply_loudness(std::vector<float>& pcm24) {
+    if (!ready_) return false;
+    if (!loud_ || pcm24.empty()) return true;
+    int id = -1;
+    std::vector<float> out;
+    bool ok = q3tts_loudness_begin(h_, loud_target_, loud_range_, 0, &id) == 0;
+    const size_t step = 1440000;   // the most one push takes
+    for (size_t done = 0; ok && done < pcm24.size(); done += step) {
+        const size_t m = std::min(step, pcm24.size() - done);
+        ok = loudness_push(id, pcm24.data() + done, m, done + m == pcm24.size(), done, out);
+    }
+    if (!ok) std::cerr << "[TTSEngine] Loudness error: " << q3tts_last_error(h_) << std::endl;
+    if (id >= 0) (void)q3tts_loudness_end(h_, id);
+    if (ok) pcm24.swap(out); else pcm24.clear();
+    return ok;
+}
+
 bool TTSEngine::set_level(float gain_db, float ceiling) {
     if (!ready_) return false;
     const long G = std::lround(10.0 * (double)gain_db), T = std::lround(1000.0 * (double)ceiling);
@@ -467,12 +523,13 @@ bool TTSEngine::apply_level(std::vector<float>& pcm24) {
     return ok;
 }
 
-// the whole clip through the pitch stage, the stretcher and then the level stage (each only when set): every one-shot method ends here
+// the whole clip through the pitch stage, the stretcher, the loudness stage and then the level stage (each only when set): every
+// one-shot method ends here
 bool TTSEngine::apply_speed(std::vector<float>& pcm24) {
     if (!ready_) return false;
     if (pcm24.empty()) return true;
     if (!apply_pitch(pcm24)) return false;
-    if (speed_ == 1000) return apply_level(pcm24);
+    if (speed_ == 1000) return apply_loudness(pcm24) && apply_level(pcm24);
     int id = -1;
     std::vector<float> out;
     bool ok = q3tts_speed_begin(h_, speed_, &id) == 0;
@@ -484,7 +541,7 @@ bool TTSEngine::apply_speed(std::vector<float>& pcm24) {
     if (!ok) std::cerr << "[TTSEngine] Speed error: " << q3tts_last_error(h_) << std::endl;
     if (id >= 0) (void)q3tts_speed_end(h_, id);
     if (ok) pcm24.swap(out); else pcm24.clear();
-    return ok && apply_level(pcm24);
+    return ok && apply_loudness(pcm24) && apply_level(pcm24);
 }
 
 bool TTSEngine::has_audio_encoder() const { return h_ && q3tts_has_audio_encoder(h_) != 0; }
@@ -703,6 +760,16 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
         if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
         return rc;
     }
+    // with a loudness the stretcher's chunks pass a loudness stage of this call's own, ahead of the level stage
+    int normaliser = -1;
+    size_t normalised = 0;
+    std::vector<float> even;
+    if (loud_ && q3tts_loudness_begin(h_, loud_target_, loud_range_, 0, &normaliser) != 0) {
+        const int rc = fail();
+        if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
+        if (shifter >= 0) (void)q3tts_pitch_end(h_, shifter);
+        return rc;
+    }
     // with a level the chunks (the stretcher's, when there is one) pass a level stage of this call's own in the same way
     int leveler = -1;
     size_t levelled = 0;
@@ -711,12 +778,14 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
         const int rc = fail();
         if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
         if (shifter >= 0) (void)q3tts_pitch_end(h_, shifter);
+        if (normaliser >= 0) (void)q3tts_loudness_end(h_, normaliser);
         return rc;
     }
     auto fail_s = [&]() {
         const int rc = fail();
         if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
         if (shifter >= 0) (void)q3tts_pitch_end(h_, shifter);
+        if (normaliser >= 0) (void)q3tts_loudness_end(h_, normaliser);
         if (leveler >= 0) (void)q3tts_level_end(h_, leveler);
         return rc;
     };
@@ -728,7 +797,7 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
         if (!loud.empty()) on_audio(loud.data(), loud.size());
         return true;
     };
-    auto feed = [&](const float* p, size_t n, bool last) -> bool {   // a chunk from the vocoder: pitch stage, stretcher, then emit
+    auto feed = [&](const float* p, size_t n, bool last) -> bool {   // a chunk from the vocoder: pitch stage, stretcher, loudness stage, then emit
         if (shifter >= 0) {
             low.clear();
             if (!pitch_push(shifter, p, n, last, shifted, low)) return false;
@@ -740,6 +809,12 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
             if (!stretch_push(stretcher, p, n, last, received, fast)) return false;
             received += n;
             p = fast.data(); n = fast.size();
+        }
+        if (normaliser >= 0) {
+            even.clear();
+            if (!loudness_push(normaliser, p, n, last, normalised, even)) return false;
+            normalised += n;
+            p = even.data(); n = even.size();
         }
         return emit(p, n, last && leveler >= 0);
     };
@@ -759,9 +834,10 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
         }
         if (active == 0 || want <= 0) break;
     }
-    if ((shifter >= 0 || stretcher >= 0 || leveler >= 0) && !feed(pcm.data(), 0, true)) return fail_s();   // the stages' tails, in their order
+    if ((shifter >= 0 || stretcher >= 0 || normaliser >= 0 || leveler >= 0) && !feed(pcm.data(), 0, true)) return fail_s();   // the stages' tails, in their order
     if (shifter >= 0) (void)q3tts_pitch_end(h_, shifter);
     if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
+    if (normaliser >= 0) (void)q3tts_loudness_end(h_, normaliser);
     if (leveler >= 0) (void)q3tts_level_end(h_, leveler);
     (void)q3tts_slot_release(h_, 0);
     return done;

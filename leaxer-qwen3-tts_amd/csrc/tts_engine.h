@@ -194,6 +194,15 @@ public:
     int gain_centibels() const { return gain_cb_; }
     int ceiling_permille() const { return ceiling_; }
     bool apply_level(std::vector<float>& pcm24);   // the whole clip through the stage, in place; (0, 0) leaves it as it is
+    // Loudness (include/q3tts.h: q3tts_engine_set_loudness, q3tts_loudness_*; the reference has no loudness control).  lufs: the
+    // target, -40 .. -5 (rounded to 0.1); range_db: the largest boost or cut, 0 .. 40.  A BS.1770 meter and a gain that moves towards the
+    // target by at most 1 dB per 100 ms, on the GPU between the stretcher and the level stage, on every path that honours set_speed, in
+    // the same way (apply_loudness, which apply_speed calls before apply_level).  The stage delivers 100 ms late; the last call of a
+    // streaming method carries its tail.  false (and get_error(), naming the range) for a value the engine refuses.
+    bool set_loudness(float lufs, float range_db = 20.0f);
+    void clear_loudness();                            // no stage again
+    bool has_loudness() const { return loud_; }
+    bool apply_loudness(std::vector<float>& pcm24);   // the whole clip through the stage, in place; no stage leaves it as it is
     // Pitch (include/q3tts.h: q3tts_engine_set_pitch, q3tts_pitch_*; the reference has no pitch control).  semitones -12 .. +12; the
     // engine works in permille, r = round(1000 * 2^(semitones / 12)), and 0 semitones is no stage at all.  TD-PSOLA on the GPU: the
     // fundamental moves, the spectral envelope stays.  The stage stands first behind the vocoder on every path that honours set_speed,
@@ -228,6 +237,9 @@ private:
     int speed_ = 1000;
     int gain_cb_ = 0, ceiling_ = 0;
     int pitch_ = 1000;
+    bool loud_ = false;
+    int loud_target_ = -160, loud_range_ = 200;
+    bool loudness_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);
     bool pitch_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);
     bool level_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);
     // one push of a stretcher of this engine: out receives the push's samples (appended)

@@ -124,6 +124,8 @@ EXPORTS = [
     "q3tts_codec_stream_set_level", "q3tts_engine_set_level",
     "q3tts_pitch_ratio", "q3tts_pitch_emitted", "q3tts_pitch_last_error", "q3tts_pitch_begin", "q3tts_pitch_push_batch_host", "q3tts_pitch_end",
     "q3tts_codec_stream_set_pitch", "q3tts_engine_set_pitch",
+    "q3tts_loudness_coeffs", "q3tts_loudness_emitted", "q3tts_loudness_lufs", "q3tts_loudness_last_error", "q3tts_loudness_begin",
+    "q3tts_loudness_push_batch_host", "q3tts_loudness_end", "q3tts_codec_stream_set_loudness", "q3tts_engine_set_loudness",
 ]
 
 # q3tts_audio_cb: int (*)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished)
@@ -500,13 +502,16 @@ class Engine:
         self._ck(self.L.q3tts_codec_decode_chunked_host(self.h, _p(c), c.shape[0], chunk_frames, left_context, _p(pcm), n, C.byref(out_len)))
         return pcm[: out_len.value]
 
-    def codec_stream_begin(self, max_frames, sample_rate=24000, dtype="float32", speed=None, gain_db=None, ceiling=None, pitch=None):
+    def codec_stream_begin(self, max_frames, sample_rate=24000, dtype="float32", speed=None, gain_db=None, ceiling=None,
+                           loudness=None, loudness_range=None, loudness_start=None, pitch=None):
         """streaming vocoder with carried state: -> stream id (q3tts_codec_stream_begin).  sample_rate / dtype other than 24000 /
         float32 give the stream a sink (q3tts_codec_stream_set_sink): codec_stream_push_batch then delivers at that rate, as float32
         or int16.  speed (permille, 500 .. 2000; None or 1000: none) gives it a stretcher ahead of the sink
         (q3tts_codec_stream_set_speed).  gain_db / ceiling (level_params: rounded to centibels / permille; None: 0) give it a level
         stage between the two (q3tts_codec_stream_set_level).  pitch (permille, 500 .. 2000; None or 1000: none) gives it a pitch
-        stage in front of them all (q3tts_codec_stream_set_pitch)."""
+        stage in front of them all (q3tts_codec_stream_set_pitch).  loudness (LUFS, -40 .. -5, or 0: meter only; None: none) with
+        loudness_range / loudness_start (dB; loudness_params) gives it a loudness stage between the stretcher and the level stage
+        (q3tts_codec_stream_set_loudness)."""
         fmt = _pcm_format(dtype)
         sid = C.c_int(-1)
         self.L.q3tts_codec_stream_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -536,7 +541,71 @@ class Engine:
             except Exception:
                 self.codec_stream_end(sid.value)
                 raise
+        if loudness is not None:
+            try:
+                self.codec_stream_set_loudness(sid.value, *loudness_params(loudness, loudness_range, loudness_start))
+            except Exception:
+                self.codec_stream_end(sid.value)
+                raise
         return sid.value
+
+    def codec_stream_set_loudness(self, sid, target_dlufs, range_cb=200, start_cb=0):
+        """q3tts_codec_stream_set_loudness: target in tenths of a LUFS (0: meter only), range and start gain in centibels; refused once
+        the stream has delivered a sample"""
+        self.L.q3tts_codec_stream_set_loudness.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32]
+        self._ck(self.L.q3tts_codec_stream_set_loudness(self.h, int(sid), int(target_dlufs), int(range_cb), int(start_cb)))
+        self.__dict__.setdefault("_codec_stream_loud", {})[int(sid)] = (int(target_dlufs), int(range_cb), int(start_cb))
+
+    # ---- the loudness stage on its own (include/q3tts.h "loudness") ----
+    def loudness_begin(self, target_dlufs, range_cb=200, start_cb=0):
+        """a stage that takes 24 kHz float32, measures it (BS.1770) and delivers it with a gain that moves towards target_dlufs
+        (tenths of a LUFS, -400 .. -50; 0: meter only) by at most range_cb centibels, starting from start_cb -> stage id"""
+        sid = C.c_int(-1)
+        self.L.q3tts_loudness_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int)]
+        self._ck(self.L.q3tts_loudness_begin(self.h, int(target_dlufs), int(range_cb), int(start_cb), C.byref(sid)))
+        return sid.value
+
+    def loudness_push_batch(self, ids, pcm_list, finish=None, report=False):
+        """more 24 kHz samples for many loudness stages in one launch (q3tts_loudness_push_batch_host); finish: one flag per stage
+        (its tail is flushed with this push) -> one float32 array per stage; report: -> (samples, energies int64, gains float32) per
+        stage, E_b and G_b of the sub-blocks the push completed"""
+        n = len(ids)
+        if n == 0:
+            return []
+        if len(pcm_list) != n or (finish is not None and len(finish) != n):
+            raise ValueError("loudness_push_batch: one sample array (and one finish flag) per stage")
+        xs = [np.ascontiguousarray(a, np.float32).reshape(-1) for a in pcm_list]
+        fin = np.zeros(n, np.uint8) if finish is None else np.ascontiguousarray([1 if f else 0 for f in finish], np.uint8)
+        lens = np.array([x.size for x in xs], np.int64)
+        cap = int(lens.max()) + 2400                 # the push plus what the stage held back
+        outs = [np.empty(cap, np.float32) for _ in range(n)]
+        es = [np.zeros(x.size // 2400 + 1, np.int64) for x in xs]
+        gs = [np.zeros(x.size // 2400 + 1, np.float32) for x in xs]
+        xptr = (C.c_void_p * n)(*[x.ctypes.data if x.size else None for x in xs])
+        optr = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        eptr = (C.c_void_p * n)(*[a.ctypes.data for a in es])
+        gptr = (C.c_void_p * n)(*[a.ctypes.data for a in gs])
+        out_len, nb = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        self.L.q3tts_loudness_push_batch_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p]
+        self._ck(self.L.q3tts_loudness_push_batch_host(self.h, n, _p(np.ascontiguousarray(ids, np.int32)), C.cast(xptr, C.c_void_p), _p(lens), _p(fin),
+                                                       C.cast(optr, C.c_void_p), cap, _p(out_len), C.cast(eptr, C.c_void_p) if report else None,
+                                                       C.cast(gptr, C.c_void_p) if report else None, _p(nb)))
+        if report:
+            return [(outs[i][: out_len[i]], es[i][: nb[i]], gs[i][: nb[i]]) for i in range(n)]
+        return [outs[i][: out_len[i]] for i in range(n)]
+
+    def loudness_end(self, stage_id):
+        self.L.q3tts_loudness_end.argtypes = [C.c_void_p, C.c_int]
+        self._ck(self.L.q3tts_loudness_end(self.h, int(stage_id)))
+
+    def set_loudness(self, target_dlufs=None, range_cb=200, start_cb=0):
+        """q3tts_engine_set_loudness: the streaming entries deliver through a loudness stage; None takes it away"""
+        self.L.q3tts_engine_set_loudness.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32]
+        if target_dlufs is None:
+            self._ck(self.L.q3tts_engine_set_loudness(self.h, 0, 0, 0, 0))
+        else:
+            self._ck(self.L.q3tts_engine_set_loudness(self.h, 1, int(target_dlufs), int(range_cb), int(start_cb)))
 
     def codec_stream_set_pitch(self, sid, ratio):
         """q3tts_codec_stream_set_pitch: ratio in permille; refused once the stream has delivered a sample; 1000 takes the stage away"""
@@ -794,7 +863,8 @@ class Engine:
         spds = self.__dict__.setdefault("_codec_stream_speed", {})
         lvls = self.__dict__.setdefault("_codec_stream_level", {})
         pits = self.__dict__.setdefault("_codec_stream_pitch", {})
-        if finish is None and not any(int(i) in fmts or int(i) in spds or int(i) in lvls or int(i) in pits for i in ids):
+        louds = self.__dict__.setdefault("_codec_stream_loud", {})
+        if finish is None and not any(int(i) in fmts or int(i) in spds or int(i) in lvls or int(i) in pits or int(i) in louds for i in ids):
             return self._push_batch(ids, cs, offs)
         flat = np.ascontiguousarray(np.concatenate(cs)) if sum(c_.shape[0] for c_ in cs) else np.zeros((1, self.cfg.n_groups), np.int64)
         n24 = self.codec_decode_len(max(max(c_.shape[0] for c_ in cs), 1)) + 4096
@@ -802,6 +872,8 @@ class Engine:
             n24 += 1248                    # behind a pitch stage: plus what it held back
         if any(int(i) in spds for i in ids):
             n24 = (n24 + 1320) * 2 + 720   # behind a stretcher: the slowest speed doubles the push plus what it held back
+        if any(int(i) in louds for i in ids):
+            n24 += 2400                    # behind a loudness stage: plus what it held back
         if any(int(i) in lvls for i in ids):
             n24 += 128                     # behind a limiter: plus what it held back
         cap = max((n24 + 200) * max(fmts.get(int(i), (24000, PCM_F32))[0], 24000) // 24000 + 8 for i in ids)
@@ -879,6 +951,7 @@ class Engine:
         self.__dict__.setdefault("_codec_stream_speed", {}).pop(int(sid), None)
         self.__dict__.setdefault("_codec_stream_level", {}).pop(int(sid), None)
         self.__dict__.setdefault("_codec_stream_pitch", {}).pop(int(sid), None)
+        self.__dict__.setdefault("_codec_stream_loud", {}).pop(int(sid), None)
 
     def slot_codec_decode_range(self, slot, frame_begin, frame_end, left_context):
         """samples owned by frames [frame_begin, frame_end) of a slot (streaming while it generates)"""
@@ -1602,7 +1675,7 @@ class Engine:
         self._ck(rc)
         return [pcm[i][: pcm_len[i]] for i in range(n)], [codes[i, : nfr[i]] for i in range(n)], nfr
 
-    def _sink_job(self, sample_rate, dtype, on_audio, n, run, speed=None, level=(0, 0), pitch=None):
+    def _sink_job(self, sample_rate, dtype, on_audio, n, run, speed=None, level=(0, 0), pitch=None, loud=None):
         """a streaming job through a sink of its own: run(None-pcm_out) with the sink set, the sink taken away afterwards; the chunks
         on_audio saw are also returned joined per utterance"""
         fmt = _pcm_format("float32" if dtype is None else dtype)
@@ -1615,11 +1688,13 @@ class Engine:
         try:
             self.set_level(*level)
             self.set_pitch(1000 if pitch is None else pitch)
+            self.set_loudness(*(loud if loud is not None else (None,)))
             self.set_sink(24000 if sample_rate is None else sample_rate, "int16" if fmt == PCM_S16 else "float32", tee)
         except BaseException:
             self.set_speed(None)
             self.set_level(0, 0)
             self.set_pitch(1000)
+            self.set_loudness(None)
             raise
         try:
             rc = run()
@@ -1629,6 +1704,7 @@ class Engine:
             self.set_speed(None)
             self.set_level(0, 0)
             self.set_pitch(1000)
+            self.set_loudness(None)
         if raised:
             raise raised[0]
         self._ck(rc)
@@ -1636,7 +1712,7 @@ class Engine:
         return [np.concatenate(g) if g else np.zeros(0, npdt) for g in got]
 
     def synthesize_stream(self, token_lists, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
-                          max_new_per_utt=None, instructs=None, sample_rate=None, dtype=None, speed=None, gain_db=None, ceiling=None, pitch=None):
+                          max_new_per_utt=None, instructs=None, sample_rate=None, dtype=None, speed=None, gain_db=None, ceiling=None, loudness=None, pitch=None):
         """synthesize_batch that delivers audio while it generates (q3tts_synthesize_stream_host): every chunk_frames steps
         on_audio(utt, frame_begin, frame_end, pcm, finished) is called once per utterance with new audio (pcm: a copy); a truthy return
         cancels the job (RuntimeError "cancelled by callback").  Returns what synthesize_batch returns."""
@@ -1681,7 +1757,8 @@ class Engine:
         level = level_params(gain_db, ceiling)   # gain_db / ceiling: the chunks pass a level stage behind the stretcher (q3tts_engine_set_level)
         if pitch is not None and int(pitch) == 1000:
             pitch = None   # no stage; otherwise (permille) the chunks pass a pitch stage first (q3tts_engine_set_pitch)
-        if sample_rate is not None or dtype is not None or speed is not None or level != (0, 0) or pitch is not None:   # through a sink (q3tts_engine_set_sink): sample_rate / dtype are the chunks' and the result's; speed (permille): time-stretched first (q3tts_engine_set_speed)
+        loud = None if loudness is None else loudness_params(loudness)   # LUFS, or (LUFS, range dB, start dB): a loudness stage behind the stretcher (q3tts_engine_set_loudness)
+        if sample_rate is not None or dtype is not None or speed is not None or level != (0, 0) or pitch is not None or loud is not None:   # through a sink (q3tts_engine_set_sink): sample_rate / dtype are the chunks' and the result's; speed (permille): time-stretched first (q3tts_engine_set_speed)
             def run():
                 if ins_flat is not None:
                     return self.L.q3tts_synthesize_instruct_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
@@ -1690,7 +1767,7 @@ class Engine:
                 return self.L.q3tts_synthesize_stream_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
                                                            seed, int(ignore_eos), None, 0, _p(pcm_len), _p(nfr),
                                                            _p(codes) if want_codes else None, int(chunk_frames), cb, None)
-            outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed, level, pitch)
+            outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed, level, pitch, loud)
             return outs, ([codes[i, : nfr[i]] for i in range(n)] if want_codes else None), nfr
         if ins_flat is not None:
             rc = self.L.q3tts_synthesize_instruct_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
@@ -1708,7 +1785,7 @@ class Engine:
         return outs, cl, nfr
 
     def synthesize_live(self, n_utt, text_source, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
-                        max_new_per_utt=None, sample_rate=None, dtype=None, speed=None, gain_db=None, ceiling=None, pitch=None):
+                        max_new_per_utt=None, sample_rate=None, dtype=None, speed=None, gain_db=None, ceiling=None, loudness=None, pitch=None):
         """synthesize_stream for texts that arrive while their audio is generated (q3tts_synthesize_live_host): text_source(utt) ->
         (ids, closed) is polled between decode chunks for every utterance whose text is open — new ids (possibly none) and whether the
         text has ended; None cancels the job (RuntimeError "cancelled by callback").  An utterance's ids are those synthesize_stream
@@ -1770,13 +1847,14 @@ class Engine:
         level = level_params(gain_db, ceiling)
         if pitch is not None and int(pitch) == 1000:
             pitch = None
-        if sample_rate is not None or dtype is not None or speed is not None or level != (0, 0) or pitch is not None:   # through a sink and / or a stretcher, as synthesize_stream
+        loud = None if loudness is None else loudness_params(loudness)
+        if sample_rate is not None or dtype is not None or speed is not None or level != (0, 0) or pitch is not None or loud is not None:   # through a sink and / or a stretcher, as synthesize_stream
             def run():
                 return self.L.q3tts_synthesize_live_host(self.h, n, tcb, None, lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
                                                          seed, int(ignore_eos), None, 0, _p(pcm_len), _p(nfr),
                                                          _p(codes) if want_codes else None, int(chunk_frames), cb, None)
             try:
-                outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed, level, pitch)
+                outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed, level, pitch, loud)
             except BaseException:
                 if raised:
                     raise raised[0]
@@ -1989,6 +2067,60 @@ def level_params(gain_db=None, ceiling=None):
     if ceiling is not None and float(ceiling) > 0 and c == 0:
         raise ValueError("level: ceiling %r rounds to 0 permille, which means no limiter" % (ceiling,))
     return g, c
+
+
+def loudness_params(loudness, loudness_range=None, loudness_start=None):
+    """(LUFS, range dB, start dB) -> (target_dlufs, range_cb, start_cb), rounded to the units of the C-ABI.  loudness may itself be the
+    triple.  Range None: 20 dB; start None: 0 dB.  loudness 0 is meter only."""
+    if isinstance(loudness, (tuple, list)):
+        loudness, loudness_range, loudness_start = (list(loudness) + [None, None])[:3]
+    return (int(round(10.0 * float(loudness))), 200 if loudness_range is None else int(round(10.0 * float(loudness_range))),
+            0 if loudness_start is None else int(round(10.0 * float(loudness_start))))
+
+
+def loudness_coeffs(rate=24000):
+    """q3tts_loudness_coeffs: the ten doubles { b0, b1, b2, a1, a2 } of the K-weighting's shelf, then of its high-pass, at rate.
+    Host-only; ValueError outside 8000 .. 384000."""
+    Lb = lib()
+    Lb.q3tts_loudness_coeffs.argtypes = [C.c_int32, C.c_void_p]
+    Lb.q3tts_loudness_coeffs.restype = C.c_int
+    Lb.q3tts_loudness_last_error.restype = C.c_char_p
+    out = np.zeros(10, np.float64)
+    if Lb.q3tts_loudness_coeffs(int(rate), out.ctypes.data) != 0:
+        raise ValueError(Lb.q3tts_loudness_last_error().decode())
+    return out
+
+
+def loudness_emitted(target_dlufs, n_received, finished=False):
+    """q3tts_loudness_emitted: the samples a loudness stage has delivered in all after n_received samples.  Host-only; ValueError for
+    a negative count."""
+    Lb = lib()
+    Lb.q3tts_loudness_emitted.argtypes = [C.c_int32, C.c_int64, C.c_int]
+    Lb.q3tts_loudness_emitted.restype = C.c_int64
+    Lb.q3tts_loudness_last_error.restype = C.c_char_p
+    if not -2**63 <= int(n_received) < 2**63:
+        raise ValueError("loudness_emitted: %d does not fit the C type" % int(n_received))
+    n = int(Lb.q3tts_loudness_emitted(int(target_dlufs), int(n_received), 1 if finished else 0))
+    if n < 0:
+        raise ValueError(Lb.q3tts_loudness_last_error().decode())
+    return n
+
+
+LOUDNESS_MODES = {"momentary": 0, "short-term": 1, "integrated": 2}
+
+
+def loudness_lufs(energies, mode="integrated"):
+    """q3tts_loudness_lufs: LUFS of the sub-block energies a loudness stage reported; mode momentary (the last 400 ms), short-term
+    (the last 3 s) or integrated (BS.1770's two gates).  -inf when nothing passes.  Host-only."""
+    Lb = lib()
+    Lb.q3tts_loudness_lufs.argtypes = [C.c_void_p, C.c_int64, C.c_int]
+    Lb.q3tts_loudness_lufs.restype = C.c_double
+    Lb.q3tts_loudness_last_error.restype = C.c_char_p
+    E = np.ascontiguousarray(energies, np.int64).reshape(-1)
+    v = float(Lb.q3tts_loudness_lufs(E.ctypes.data if E.size else None, E.size, LOUDNESS_MODES[mode] if isinstance(mode, str) else int(mode)))
+    if v != v:
+        raise ValueError(Lb.q3tts_loudness_last_error().decode())
+    return v
 
 
 def pitch_ratio(cents):
