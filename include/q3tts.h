@@ -508,6 +508,10 @@ int q3tts_synthesize_prefixed_host(q3tts_engine* e, int n_utt, const int64_t* id
 /* io::read_wav (src/io/wav_reader.h:13, wav_reader.cpp:28-143): mono float samples; -1 when the reference
  * returns an empty vector.  Call with out == NULL to learn *n_samples. */
 int q3tts_read_wav_host(const char* path, float* out, int64_t cap, int64_t* n_samples, int32_t* sample_rate);
+/* The bytes of a G.711 WAV (format tag 7 mu-law / 6 A-law, 8 bits, mono), which q3tts_read_wav_host refuses: *format is
+ * Q3TTS_PCM_MULAW (2) / Q3TTS_PCM_ALAW (3), the bytes are what an encoder stream of that format takes.  -2 for a G.711 file with more
+ * than one channel (stereo is not read), -1 for anything else.  Sizing call: out NULL. */
+int q3tts_read_wav_g711_host(const char* path, uint8_t* out, int64_t cap, int64_t* n_samples, int32_t* sample_rate, int* format);
 /* io::resample (wav_reader.cpp:145-164): linear interpolation; returns the output length */
 int64_t q3tts_resample_host(const float* in, int64_t n, int32_t src_rate, int32_t dst_rate, float* out, int64_t cap);
 /* io::resample over audio that is still arriving: the output samples a stream at src_rate has emitted IN ALL once it holds n_received
@@ -589,10 +593,31 @@ int q3tts_test_audio_encoder_transformer_host(q3tts_engine* e, const float* rows
  * any before it regrows the RoPE tables (the same double-precision formula: existing rows keep their bits) and synchronises for it. */
 int q3tts_audio_stream_begin(q3tts_engine* e, int64_t max_samples, int* stream_id);
 /* The same for a source at sample_rate (1 .. 384 000; anything else is refused with the value) whose samples are float
- * (Q3TTS_PCM_F32) or int16 (Q3TTS_PCM_S16).  max_samples counts the stream's OWN samples: 0 = 60 s at its rate, at most one hour.
+ * (Q3TTS_PCM_F32), int16 (Q3TTS_PCM_S16) or G.711 bytes (Q3TTS_PCM_MULAW / _ALAW, below).  max_samples counts the stream's OWN samples: 0 = 60 s at its rate, at most one hour.
  * q3tts_audio_stream_begin is this at 24 000 / Q3TTS_PCM_F32. */
 #define Q3TTS_PCM_F32 0
 #define Q3TTS_PCM_S16 1
+/* ---- G.711 (ITU-T G.711; RTP payload types 0 and 8, WAV format tags 7 and 6) ----
+ * Two more sample formats for the encoder streams (in) and the sinks (out): one uint8_t per sample, mu-law or A-law.  Both laws are
+ * defined on the int16 the engine already makes, as sign-magnitude codes: enc(-s) == enc(s) ^ 0x80 for s in 1 .. 32767 (not the
+ * `pcm >> 2` of a negative two's-complement value that some C libraries use).
+ * Out (sinks): s = (int16_t)(clip(y, -1, 1) * 32767.0f), the int16 rule above, unchanged; the byte is enc(s).
+ *   mu-law enc(s): m = min(|s|, 32635) + 132 (|s| in 32 bits); e = floor(log2 m) - 7 (0 .. 7, by count-leading-zeros: integers only,
+ *     no table); mant = (m >> (e + 3)) & 15; byte = ~((s < 0 ? 0x80 : 0) | e << 4 | mant) & 0xFF.  Silence is 0xFF.
+ *   A-law enc(s): a = min(|s|, 32767) >> 3; a < 32: e = 0, mant = a >> 1; otherwise e = floor(log2 a) - 4 (1 .. 7), mant = (a >> e) & 15;
+ *     byte = ((s >= 0 ? 0x80 : 0) | e << 4 | mant) ^ 0x55.  Silence is 0xD5.
+ * In (encoder streams): the byte decodes to an int16 s and the sample is (float)s / 32768.0f, the int16 ingest rule.
+ *   mu-law dec(b): u = ~b & 0xFF; e = (u >> 4) & 7; mant = u & 15; m = (((mant << 3) + 132) << e) - 132; s = u & 0x80 ? -m : m.  Range +-32124.
+ *   A-law dec(b): x = b ^ 0x55; e = (x >> 4) & 7; mant = x & 15; m = e == 0 ? (mant << 4) + 8 : ((mant << 4) + 0x108) << (e - 1);
+ *     s = x & 0x80 ? m : -m.  Range +-32256.
+ * enc(dec(b)) == b for every byte except mu-law 0x7F (negative zero, which re-encodes as 0xFF).
+ * Sample counts, push limits, max_samples, q3tts_sink_emitted and q3tts_resample_stream_emitted do not depend on the format. */
+#define Q3TTS_PCM_MULAW 2
+#define Q3TTS_PCM_ALAW 3
+/* Host only, no engine: the same inline functions the kernels use.  n samples; -1 for a format other than Q3TTS_PCM_MULAW / _ALAW,
+ * n < 0 or a NULL pointer with n > 0. */
+int q3tts_g711_encode_host(int format, const int16_t* in, int64_t n, uint8_t* out);
+int q3tts_g711_decode_host(int format, const uint8_t* in, int64_t n, int16_t* out);
 int q3tts_audio_stream_begin_rate(q3tts_engine* e, int32_t sample_rate, int format, int64_t max_samples, int* stream_id);
 /* the rate and format a stream was begun with (either pointer may be NULL) */
 int q3tts_audio_stream_format(q3tts_engine* e, int stream_id, int32_t* sample_rate, int* format);
@@ -602,11 +627,11 @@ int q3tts_audio_stream_push_len(q3tts_engine* e, int stream_id, int64_t n_sample
  * one-shot).  codes_out[*n_frames][n_groups] int64 in q3tts_audio_encode_host's layout: the NEW frames only.  n_samples == 0 without
  * finish does nothing; finish on a stream that never got a sample returns 0 frames.  A push holds at most 60 s of the stream's own
  * samples (1 440 000 at 24 kHz).  n_samples counts the stream's own samples; this entry serves float streams of any rate and
- * refuses an int16 stream by name. */
+ * refuses an int16 or G.711 stream by name. */
 int q3tts_audio_stream_push_host(q3tts_engine* e, int stream_id, const float* pcm24k, int64_t n_samples, int finish,
                                  int64_t* codes_out, int cap_frames, int32_t* n_frames);
 /* the same with the samples read in the stream's own format: float for Q3TTS_PCM_F32, int16_t for Q3TTS_PCM_S16 (staged as int16,
- * half the upload, and converted on the GPU) */
+ * half the upload, and converted on the GPU), uint8_t for Q3TTS_PCM_MULAW / _ALAW (staged as bytes, a quarter, decoded on the GPU) */
 int q3tts_audio_stream_push_any_host(q3tts_engine* e, int stream_id, const void* pcm, int64_t n_samples, int finish,
                                      int64_t* codes_out, int cap_frames, int32_t* n_frames);
 /* Many streams in one call: one set of launches per group of at most 2 880 000 new samples, whatever the number of streams, and each
@@ -615,7 +640,7 @@ int q3tts_audio_stream_push_any_host(q3tts_engine* e, int stream_id, const void*
  * stream where it was.  (A HIP error is another matter: streams advance group by group, so after one in a later group of a call of
  * more than 2 880 000 new samples the streams of earlier groups have moved; end every stream of such a call.)  finish NULL: no stream finishes.  latents_out (NULL ok, and so may single entries) is the parity aid of
  * q3tts_audio_encode_batch_latents_host: latents_out[i][n_frames[i]][enc_hidden].
- * The float entry serves Q3TTS_PCM_F32 streams of any rate and refuses an int16 stream by name. */
+ * The float entry serves Q3TTS_PCM_F32 streams of any rate and refuses an int16 or G.711 stream by name. */
 int q3tts_audio_stream_push_batch_host(q3tts_engine* e, int n_streams, const int32_t* stream_ids, const float* const* pcm24k,
                                        const int64_t* n_samples, const int32_t* finish /* NULL: none */,
                                        int64_t* const* codes_out, float* const* latents_out /* NULL ok: parity aid */,
@@ -634,7 +659,7 @@ int q3tts_audio_stream_end(q3tts_engine* e, int stream_id);
 /* ---- audio out at the sink's rate: carried-state band-limited resampler ([HINT] no counterpart in the reference, whose main.cpp writes
  * 24 kHz only) ----
  * Everything above delivers 24 kHz float.  A sink delivers the same audio at its own rate R (4 000 .. 192 000 Hz) as float
- * (Q3TTS_PCM_F32) or int16 (Q3TTS_PCM_S16), resampled on the GPU between the vocoder and the device -> host copy, all streams of a push
+ * (Q3TTS_PCM_F32), int16 (Q3TTS_PCM_S16) or G.711 bytes (Q3TTS_PCM_MULAW / _ALAW: the byte of that int16, "G.711" above), resampled on the GPU between the vocoder and the device -> host copy, all streams of a push
  * in one launch.  24 000 / Q3TTS_PCM_F32 is "no sink": no launch, the same bytes as before.
  * The resampler: g = gcd(R, 24000), L = R / g, M = 24000 / g; output j sits at input position j M / L.  s = min(1, R / 24000), half-width
  * H = 16 / s input samples, half = ceil(H), taps = 2 half, cut-off f = 0.92 s.  Table row p (0 <= p < L), tap t: d = (t - half + 1) - p / L,
@@ -661,7 +686,7 @@ int64_t q3tts_sink_emitted(int32_t rate, int64_t n_received, int finished);
  * samples), a push at most 1 440 000.  At most 4096 sinks are open at a time (vocoder streams' sinks included). */
 int q3tts_pcm_sink_begin(q3tts_engine* e, int32_t sample_rate, int format, int* sink_id);
 /* n sinks (distinct, open, not finished), sink i given n_in[i] >= 0 more samples pcm24[i]; finish[i] != 0 (finish NULL: none) flushes
- * the tail with this push and closes the sink's audio (n_in[i] == 0 allowed).  out[i] is float* or int16_t* by the sink's format,
+ * the tail with this push and closes the sink's audio (n_in[i] == 0 allowed).  out[i] is float*, int16_t* or uint8_t* by the sink's format,
  * with room for cap_samples; out_len[i] is the push's length by the rule above (min(out_len, cap_samples) samples are written).  The call
  * is validated completely before any sink moves.  n_in[i] == 0 without finish leaves the sink as it was. */
 int q3tts_pcm_sink_push_batch_host(q3tts_engine* e, int n, const int32_t* sink_ids, const float* const* pcm24, const int64_t* n_in,
@@ -676,7 +701,7 @@ int q3tts_codec_stream_set_sink(q3tts_engine* e, int stream_id, int32_t sample_r
 int q3tts_codec_stream_push_batch_any_host(q3tts_engine* e, int n_streams, const int32_t* stream_ids, const int64_t* codes, const int32_t* frame_offsets,
                                            void* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, const uint8_t* finish);
 /* The scheduler: one setter for the four streaming entries (q3tts_synthesize_stream_host, _live_host, _instruct_host with a callback,
- * _continue_stream_host).  While a sink is set they deliver through sink->cb in the sink's format (pcm is float* or int16_t*), their
+ * _continue_stream_host).  While a sink is set they deliver through sink->cb in the sink's format (pcm is float*, int16_t* or, for G.711, uint8_t*), their
  * own cb argument may be NULL, and a non-NULL pcm_out is refused by name.  The finished = 1 call carries the flushed tail, so an
  * utterance's calls add up to ceil(n24 L / M) samples; pcm_len counts the sink's samples.  Codes, frame counts and RNG use are
  * untouched.  sink == NULL: none.  The struct is copied. */

@@ -7,6 +7,7 @@
 // utterance's codec frames, one per line; generate behind recorded frames — the WAV then holds the new audio only),
 // --encode WAV --save-codes FILE (audio -> codes with the 12 Hz tokenizer's encoder, nothing else; --encode-chunk MS pushes the file MS
 // milliseconds at a time through one encoder stream opened at the file's own rate: the same codes, and no 60 s limit), --ref WAV with --ref-text TEXT /
+// --out-format pcm16|mulaw|alaw (G.711 bytes from the engine's sink, WAV format tags 7 / 6; --encode and --ref with --ref-text also read such files),
 // --ref-tokens "id,id,..." (in-context clone: the reference's codes and text in front of the utterance; --ref alone stays the x-vector clone).
 #include <algorithm>
 #include <cmath>
@@ -54,6 +55,23 @@ static int save_wav16_raw(const char* path, const std::vector<int16_t>& s, uint3
     return ok ? 0 : -1;
 }
 
+// G.711 (--out-format mulaw / alaw): the sink's bytes as they came.  WAVE_FORMAT_MULAW (7) / WAVE_FORMAT_ALAW (6): an 18-byte fmt
+// chunk (cbSize 0), a fact chunk with the sample count, the data chunk padded to an even length (the pad byte counts in the RIFF
+// size, not in the data size).
+static int save_wav_g711(const char* path, const std::vector<uint8_t>& s, uint32_t rate, int format) {
+    FILE* f = fopen(path, "wb");
+    if (!f) return -1;
+    const uint32_t data = (uint32_t)s.size(), pad = data & 1u, riff = 4 + (8 + 18) + (8 + 4) + (8 + data + pad), fmt = 18, fact = 4, bytes_per_s = rate;
+    const uint16_t tag = format == Q3TTS_PCM_MULAW ? 7 : 6, ch = 1, align = 1, bits = 8, cb = 0;
+    const uint8_t zero = 0;
+    bool ok = put(f, "RIFF", 4) && put(f, &riff, 4) && put(f, "WAVEfmt ", 8) && put(f, &fmt, 4) && put(f, &tag, 2) && put(f, &ch, 2) &&
+              put(f, &rate, 4) && put(f, &bytes_per_s, 4) && put(f, &align, 2) && put(f, &bits, 2) && put(f, &cb, 2) &&
+              put(f, "fact", 4) && put(f, &fact, 4) && put(f, &data, 4) && put(f, "data", 4) && put(f, &data, 4);
+    ok = ok && put(f, s.data(), s.size()) && (!pad || put(f, &zero, 1));
+    fclose(f);
+    return ok ? 0 : -1;
+}
+
 static void usage(const char* prog) {
     printf("Usage: %s [options]\n\nQwen3-TTS synthesis on MI355X (HIP)\n\nOptions:\n", prog);
     printf("  -m, --model DIR       model directory holding model.q3w, or synthetic:<seed> / synthetic-1.7b:<seed> (required)\n");
@@ -68,6 +86,7 @@ static void usage(const char* prog) {
     printf("  --ref PATH            reference audio for voice clone (WAV; resampled to 24 kHz, ECAPA speaker encoder on the GPU)\n");
     printf("  --ref-text TEXT       with --ref: in-context clone instead — the reference is encoded to codes and continued, TEXT is what it says\n");
     printf("  --ref-tokens IDS      the same with the reference text as comma-separated token ids (for synthetic: models, with --tokens)\n");
+    printf("                        (--encode and --ref with --ref-text / --ref-tokens also read G.711 WAVs, mu-law or A-law, 8 bits mono: their bytes go through an encoder stream as they are)\n");
     printf("  --encode PATH         encode a WAV to codec frames with the audio encoder and write them to --save-codes FILE; nothing is synthesized\n");
     printf("  --encode-chunk MS     with --encode: push the file MS milliseconds at a time through one encoder stream (the stream runs at the file's own rate: the same codes; files over 60 s encode)\n");
     printf("  --temp FLOAT          temperature (default: 0.8; 0 samples at T=1 like the reference, use --top-k 1 for greedy)\n");
@@ -77,6 +96,7 @@ static void usage(const char* prog) {
     printf("  --stream-chunk N      with --tokens: decode audio every N frames while generating (same samples as the one-shot decode);\n");
     printf("                        combines with --continue-codes and with --ref + --ref-text / --ref-tokens (the prefix is history, never decoded)\n");
     printf("  --out-rate R          write the WAV at R Hz (4000 .. 192000; default 24000): band-limited resampling on the GPU, in the stream's sink with --stream-chunk\n");
+    printf("  --out-format F        sample format of the WAV: pcm16 (default), mulaw or alaw (G.711, 8 bits: WAV format tags 7 / 6), encoded on the GPU in the sink; composes with --out-rate (a telephone line: --out-rate 8000), --stream-chunk and the stage flags\n");
     printf("  --speed X             speaking rate (0.5 .. 2.0; default 1.0): X times as fast at the same pitch, WSOLA time stretch on the GPU; composes with --out-rate and --stream-chunk\n");
     printf("  --pitch ST            pitch shift in semitones (-12 .. +12; default 0): the fundamental moves, the formants stay, TD-PSOLA on the GPU ahead of --speed; composes with --speed, --gain, --limit and --out-rate\n");
     printf("  --loudness LUFS       programme loudness to aim for (-40 .. -5; default: none): a BS.1770 meter and a gain that follows it by at most 1 dB per 100 ms, on the GPU behind --speed and ahead of --gain / --limit; 100 ms latency; composes with --pitch, --speed, --gain, --limit and --out-rate\n");
@@ -93,6 +113,35 @@ static bool read_wav_mono(const std::string& path, std::vector<float>& pcm, int3
     if (q3tts_read_wav_host(path.c_str(), nullptr, 0, &n, &rate) != 0 || n < 1) return false;
     pcm.resize((size_t)n);
     return q3tts_read_wav_host(path.c_str(), pcm.data(), n, &n, &rate) == 0;
+}
+
+// a G.711 WAV (which read_wav_mono refuses) as its bytes: 0, or -1 when it is none either, or -2 (said on stderr) when it is stereo
+static int read_wav_g711_file(const std::string& path, std::vector<uint8_t>& bytes, int32_t& rate, int& format) {
+    int64_t n = 0;
+    const int rc = q3tts_read_wav_g711_host(path.c_str(), nullptr, 0, &n, &rate, &format);
+    if (rc == -2) fprintf(stderr, "Error: %s is a stereo G.711 file: only mono G.711 is read\n", path.c_str());
+    if (rc != 0 || n < 1) return rc != 0 ? rc : -1;
+    bytes.resize((size_t)n);
+    return q3tts_read_wav_g711_host(path.c_str(), bytes.data(), n, &n, &rate, &format) == 0 ? 0 : -1;
+}
+
+// the bytes of a G.711 file through one encoder stream opened at the file's rate and format, `step` samples per push (0: whole-file
+// pushes of at most the 60 s a push holds); empty on error
+static std::vector<int64_t> encode_g711(TTSEngine& engine, const std::vector<uint8_t>& bytes, int32_t rate, int format, size_t step) {
+    std::vector<int64_t> codes;
+    const int id = engine.audio_stream_begin_encoded((int64_t)bytes.size(), rate, format);
+    if (id < 0) return codes;
+    const size_t most = (size_t)60 * (size_t)rate;
+    step = step == 0 ? most : std::min(step, most);
+    bool ok = true;
+    for (size_t i = 0; ok && i < bytes.size(); i += step) {
+        const size_t m = std::min(step, bytes.size() - i);
+        const std::vector<int64_t> part = engine.audio_stream_push(id, bytes.data() + i, m, i + m == bytes.size(), &ok);
+        codes.insert(codes.end(), part.begin(), part.end());
+    }
+    engine.audio_stream_end(id);
+    if (!ok) codes.clear();
+    return codes;
 }
 
 // one frame per line, the same number of integers on every line (blanks or commas between them); false with a message on stderr
@@ -153,7 +202,7 @@ static bool frame_prompt(const TTSEngine& engine, const std::string& prompt, std
 }
 
 int main(int argc, char** argv) {
-    std::string model, prompt, tokens, output = "output.wav", lang = "auto", ref, instruct, instruct_tokens, save_codes, continue_codes, encode, ref_text, ref_tokens;
+    std::string model, prompt, tokens, output = "output.wav", lang = "auto", ref, instruct, instruct_tokens, save_codes, continue_codes, encode, ref_text, ref_tokens, out_format = "pcm16";
     bool have_prompt = false;
     SamplingParams sp;
     uint64_t seed = 0;
@@ -188,6 +237,7 @@ int main(int argc, char** argv) {
         else if (a == "--stream-chunk" && more) stream_chunk = atoi(argv[++i]);
         else if (a == "--feed" && more) feed = atoi(argv[++i]);
         else if (a == "--out-rate" && more) out_rate = atoi(argv[++i]);
+        else if (a == "--out-format" && more) out_format = argv[++i];
         else if (a == "--speed" && more) speed = atof(argv[++i]);
         else if (a == "--pitch" && more) pitch_st = atof(argv[++i]);
         else if (a == "--loudness" && more) { loudness = atof(argv[++i]); have_loudness = true; }
@@ -196,6 +246,11 @@ int main(int argc, char** argv) {
         else if (a == "--limit" && more) limit = atof(argv[++i]);
     }
     const bool icl = !ref_text.empty() || !ref_tokens.empty();
+    if (out_format != "pcm16" && out_format != "mulaw" && out_format != "alaw") {
+        fprintf(stderr, "Error: --out-format %s is none of pcm16, mulaw, alaw\n", out_format.c_str());
+        return 1;
+    }
+    const int out_g711 = out_format == "mulaw" ? Q3TTS_PCM_MULAW : (out_format == "alaw" ? Q3TTS_PCM_ALAW : 0);   // 0: pcm16
     if (have_encode_chunk && (encode.empty() || encode_chunk < 1)) {
         fprintf(stderr, "Error: --encode-chunk MS (MS >= 1) goes with --encode\nUsage: %s -m MODEL --encode WAV --encode-chunk MS --save-codes FILE\n", argv[0]);
         return 1;
@@ -206,9 +261,18 @@ int main(int argc, char** argv) {
         if (!enc_engine.is_ready()) { fprintf(stderr, "Error: %s\n", enc_engine.get_error().c_str()); return 1; }
         if (!enc_engine.has_audio_encoder()) { fprintf(stderr, "Error: model has no audio encoder\n"); return 1; }
         std::vector<int64_t> codes;
-        if (have_encode_chunk) {   // the file through one encoder stream sized to it, encode_chunk ms per push
-            std::vector<float> pcm; int32_t rate = 0;
-            if (!read_wav_mono(encode, pcm, rate) || pcm.empty()) { fprintf(stderr, "Error: failed to read %s\n", encode.c_str()); return 1; }
+        std::vector<float> pcm; int32_t rate = 0;
+        std::vector<uint8_t> g711; int g711_format = 0;
+        if (!read_wav_mono(encode, pcm, rate) || pcm.empty()) {   // not a file the reader takes: a G.711 file goes through a stream of its own format
+            pcm.clear();
+            const int rc = read_wav_g711_file(encode, g711, rate, g711_format);
+            if (rc == -2) return 1;
+            if (rc != 0) g711.clear();
+        }
+        if (!g711.empty()) {
+            codes = encode_g711(enc_engine, g711, rate, g711_format, have_encode_chunk ? std::max<size_t>((size_t)((int64_t)encode_chunk * rate / 1000), 1) : 0);
+        } else if (have_encode_chunk) {   // the file through one encoder stream sized to it, encode_chunk ms per push
+            if (pcm.empty()) { fprintf(stderr, "Error: failed to read %s\n", encode.c_str()); return 1; }
             const int id = enc_engine.audio_stream_begin((int64_t)pcm.size(), rate);
             if (id < 0) { fprintf(stderr, "Error: encoding failed\n"); return 1; }
             // encode_chunk ms of the file's own samples, at least one, at most the 60 s a push holds
@@ -266,9 +330,15 @@ int main(int argc, char** argv) {
     if (!engine.is_ready()) { fprintf(stderr, "Error: %s\n", engine.get_error().c_str()); return 1; }
     engine.set_seed(seed);
     // --out-rate: the engine delivers int16 at that rate (the streaming paths through their sink, whole clips through convert_output
-    // below); 24000 leaves everything as it is.  `audio` then holds the chunks' int16 samples, two to a float, counted by audio16
+    // below); 24000 leaves everything as it is.  --out-format mulaw / alaw: the sink delivers G.711 bytes instead, at 24000 too (the
+    // format-only sink).  The chunks' samples are collected in audio16 / audio8.
     const bool resample_out = out_rate != config::SAMPLE_RATE;
-    if (resample_out && !engine.set_output_format(out_rate, true)) { fprintf(stderr, "Error: --out-rate %d: %s\n", out_rate, engine.get_error().c_str()); return 1; }
+    const bool sink_out = resample_out || out_g711 != 0;
+    if (sink_out && !engine.set_output_encoding(out_rate, out_g711 ? out_g711 : Q3TTS_PCM_S16)) {
+        if (resample_out) fprintf(stderr, "Error: --out-rate %d: %s\n", out_rate, engine.get_error().c_str());
+        else fprintf(stderr, "Error: --out-format %s: %s\n", out_format.c_str(), engine.get_error().c_str());
+        return 1;
+    }
     // --speed: S = round(1000 X) permille; 1000 is no stage (the bytes written without the flag)
     const long speed_permille = std::lround(1000.0 * speed);
     if (!(speed == speed) || speed_permille < 500 || speed_permille > 2000) { fprintf(stderr, "Error: --speed %g is outside 0.5 .. 2.0\n", speed); return 1; }
@@ -288,16 +358,37 @@ int main(int argc, char** argv) {
         return 1;
     }
     std::vector<int16_t> audio16;
+    std::vector<uint8_t> audio8;
     printf("Synthesizing...\n");
     std::vector<float> audio;
     bool streamed16 = false;
-    auto have_audio = [&]() { return !audio.empty() || !audio16.empty(); };
-    auto take = [&](const float* p, size_t n) {   // a streaming chunk: float at 24 kHz, or the sink's int16 behind the same pointer
-        if (!resample_out) { audio.insert(audio.end(), p, p + n); return; }
-        const int16_t* q = reinterpret_cast<const int16_t*>(p);
-        audio16.insert(audio16.end(), q, q + n);
+    auto have_audio = [&]() { return !audio.empty() || !audio16.empty() || !audio8.empty(); };
+    auto take = [&](const float* p, size_t n) {   // a streaming chunk: float at 24 kHz, or the sink's int16 / G.711 bytes behind the same pointer
+        if (!sink_out) { audio.insert(audio.end(), p, p + n); return; }
+        if (out_g711) {
+            const uint8_t* q = reinterpret_cast<const uint8_t*>(p);
+            audio8.insert(audio8.end(), q, q + n);
+        } else {
+            const int16_t* q = reinterpret_cast<const int16_t*>(p);
+            audio16.insert(audio16.end(), q, q + n);
+        }
         streamed16 = true;
     };
+    // --ref with --ref-text / --ref-tokens: a G.711 reference (which the reader refuses) is encoded through a stream of its own format
+    std::vector<int64_t> g711_ref_codes;
+    if (icl) {
+        int64_t probe = 0; int32_t rate = 0;
+        if (q3tts_read_wav_host(ref.c_str(), nullptr, 0, &probe, &rate) != 0 || probe < 1) {
+            std::vector<uint8_t> g711; int g711_format = 0;
+            const int rc = read_wav_g711_file(ref, g711, rate, g711_format);
+            if (rc == -2) return 1;
+            if (rc == 0 && !g711.empty()) {
+                if (!engine.has_audio_encoder()) { fprintf(stderr, "Error: model has no audio encoder\n"); return 1; }
+                g711_ref_codes = encode_g711(engine, g711, rate, g711_format, 0);
+                if (g711_ref_codes.empty()) { fprintf(stderr, "Error: synthesis failed\n"); return 1; }
+            }
+        }
+    }
     if (!ref.empty() && !icl) {
         if (!engine.has_speaker_encoder()) { fprintf(stderr, "Error: speaker encoder not available for voice clone\n"); return 1; }
     }
@@ -318,7 +409,7 @@ int main(int argc, char** argv) {
         if (ids.empty() && !frame_prompt(engine, prompt, ids)) return 1;   // -p: the framing of --tokens around the tokenised text
         std::vector<int64_t> all;
         if (stream_chunk > 0) {   // the same clone delivered in chunks: encode, frame the ids as synthesize_clone_icl does, continue behind the codes
-            const std::vector<int64_t> ref_codes = engine.encode_audio(ref);
+            const std::vector<int64_t> ref_codes = g711_ref_codes.empty() ? engine.encode_audio(ref) : g711_ref_codes;
             if (ref_codes.empty() || ids.size() < 3) { fprintf(stderr, "Error: synthesis failed\n"); return 1; }
             std::vector<int64_t> tids(ids.begin(), ids.begin() + 3);
             tids.insert(tids.end(), rids.begin(), rids.end());
@@ -329,8 +420,13 @@ int main(int argc, char** argv) {
                 take(p, n);
                 return false;
             }, &all);
-            if (nf < 0) { audio.clear(); audio16.clear(); }
+            if (nf < 0) { audio.clear(); audio16.clear(); audio8.clear(); }
             else printf("Streamed %d new frames in %zu chunks\n", nf - (int)(ref_codes.size() / (size_t)engine.n_groups()), chunks);
+        } else if (!g711_ref_codes.empty() && ids.size() >= 3) {   // what synthesize_clone_icl does behind its own encode
+            std::vector<int64_t> tids(ids.begin(), ids.begin() + 3);
+            tids.insert(tids.end(), rids.begin(), rids.end());
+            tids.insert(tids.end(), ids.begin() + 3, ids.end());
+            audio = engine.synthesize_tokens_continue(tids, g711_ref_codes, lang_of(lang), sp, &all);
         } else audio = engine.synthesize_clone_icl(ids, rids, ref, lang_of(lang), sp, &all);
         const size_t G = (size_t)engine.n_groups();
         if (have_audio()) printf("In-context clone: %zu reference text tokens, %zu frames in all\n", rids.size(), all.size() / G);
@@ -372,7 +468,7 @@ int main(int argc, char** argv) {
             take(p, n);
             return false;
         }, &all);
-        if (nf < 0) { audio.clear(); audio16.clear(); }
+        if (nf < 0) { audio.clear(); audio16.clear(); audio8.clear(); }
         else printf("Frames: %zu recorded + %zu new, streamed in %zu chunks\n", prefix.size() / G, all.size() / G - prefix.size() / G, chunks);
         if (have_audio() && !save_codes.empty()) {
             if (!write_codes_file(save_codes, all, G)) { fprintf(stderr, "Error: failed to write %s\n", save_codes.c_str()); return 1; }
@@ -398,7 +494,7 @@ int main(int argc, char** argv) {
                 return true;
             }, lang_of(lang), sp, stream_chunk, on_audio, save_codes.empty() ? nullptr : &codes);
         } else nf = engine.synthesize_tokens_batch_streaming({ ids }, lang_of(lang), sp, stream_chunk, on_audio, &codes);
-        if (nf.empty()) { audio.clear(); audio16.clear(); }
+        if (nf.empty()) { audio.clear(); audio16.clear(); audio8.clear(); }
         else {
             printf("Streamed %d frames in %zu chunks\n", nf[0], chunks);
             if (feed > 0) printf("Text fed in %zu pieces of up to %d tokens\n", polls, feed);
@@ -414,13 +510,13 @@ int main(int argc, char** argv) {
             take(p, n);
             return false;
         });
-        if (nf.empty()) audio16.clear();
+        if (nf.empty()) { audio16.clear(); audio8.clear(); }
         else printf("Streamed %d frames in %zu chunks of %d frames\n", nf[0], chunks, stream_chunk);
     } else if (!ids.empty() && stream_chunk > 0) {   // chunks of audio as their frames are generated; the file holds their concatenation
         size_t chunks = 0;
         const int nf = engine.synthesize_tokens_streaming(ids, lang_of(lang), sp, stream_chunk, -1, [&](const float* p, size_t n) {
             if (chunks++ == 0) printf("First %.2f seconds of audio ready\n", (float)n / out_rate);
-            take(p, n);
+            audio.insert(audio.end(), p, p + n);   // 24 kHz float whatever the output format (here the rate is 24000): converted below
         });
         if (nf < 0) { audio.clear(); audio16.clear(); }
         else printf("Streamed %d frames in %zu chunks\n", nf, chunks);
@@ -440,10 +536,17 @@ int main(int argc, char** argv) {
     } else if (!ids.empty()) {
         audio = engine.synthesize_tokens(ids, lang_of(lang), sp);
     } else audio = engine.synthesize(prompt, lang_of(lang), sp);
-    if (resample_out) {
+    if (sink_out) {
         if (!streamed16) {   // a whole clip at 24 kHz: one push + finish through the resampler the streams use
             if (audio.empty()) { fprintf(stderr, "Error: synthesis failed\n"); return 1; }
-            if (!engine.convert_output(audio, nullptr, &audio16)) { fprintf(stderr, "Error: --out-rate conversion failed\n"); return 1; }
+            if (!engine.convert_output(audio, nullptr, &audio16, &audio8)) { fprintf(stderr, "Error: %s conversion failed\n", resample_out ? "--out-rate" : "--out-format"); return 1; }
+        }
+        if (out_g711) {
+            if (audio8.empty()) { fprintf(stderr, "Error: synthesis failed\n"); return 1; }
+            printf("Generated %.2f seconds of audio\n", (float)audio8.size() / out_rate);
+            if (save_wav_g711(output.c_str(), audio8, (uint32_t)out_rate, out_g711) != 0) { fprintf(stderr, "Error: failed to write WAV\n"); return 1; }
+            printf("Saved to: %s\n", output.c_str());
+            return 0;
         }
         if (audio16.empty()) { fprintf(stderr, "Error: synthesis failed\n"); return 1; }
         printf("Generated %.2f seconds of audio\n", (float)audio16.size() / out_rate);

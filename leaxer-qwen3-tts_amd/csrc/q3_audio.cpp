@@ -94,6 +94,45 @@ std::vector<float> read_wav(const std::string& path, int* sample_rate) {
     return out;
 }
 
+// G.711 WAVs (format tag 7 mu-law / 6 A-law, 8 bits, mono), which read_wav returns nothing for: the bytes as they lie, for an encoder
+// stream of that format.  [HINT] no counterpart in the reference.  Chunks are walked with their pad bytes; the last "data" chunk
+// supplies the bytes, cut where the file ends (a zero byte is not silence in either law).
+std::vector<uint8_t> read_wav_g711(const std::string& path, int* sample_rate, int* format) {
+    File fl(path.c_str());
+    if (!fl.f) return {};
+    uint8_t hdr[12];
+    if (!fl.get(hdr, 12) || memcmp(hdr, "RIFF", 4) != 0 || memcmp(hdr + 8, "WAVE", 4) != 0) return {};
+    unsigned tag = 0, channels = 0, bits = 0;
+    uint32_t rate = 0;
+    bool have_fmt = false;
+    std::vector<uint8_t> data;
+    for (;;) {
+        uint8_t ch[8];
+        if (!fl.get(ch, 8)) break;
+        const uint32_t size = le32(ch + 4);
+        if (memcmp(ch, "fmt ", 4) == 0) {
+            uint8_t fm[16];
+            if (size < 16 || !fl.get(fm, 16)) return {};
+            tag = le16(fm); channels = le16(fm + 2); rate = le32(fm + 4); bits = le16(fm + 14);
+            have_fmt = true;
+            if (fseek(fl.f, (long)(size - 16) + (long)(size & 1), SEEK_CUR) != 0) break;
+        } else if (memcmp(ch, "data", 4) == 0) {
+            if (size > (uint32_t)1 << 30) return {};
+            data.assign((size_t)size, 0);
+            data.resize(size ? fread(data.data(), 1, (size_t)size, fl.f) : 0);
+            if (size & 1) (void)fseek(fl.f, 1, SEEK_CUR);
+        } else if (fseek(fl.f, (long)size + (long)(size & 1), SEEK_CUR) != 0) {
+            break;
+        }
+    }
+    if (!have_fmt || (tag != 6 && tag != 7) || bits != 8 || !rate || rate > 0x7FFFFFFFu) return {};
+    if (channels != 1)
+        throw std::invalid_argument("read_wav_g711: " + path + " has " + std::to_string(channels) + " channels: stereo G.711 is not read, only mono");
+    *sample_rate = (int)rate;
+    *format = tag == 7 ? 2 /* Q3TTS_PCM_MULAW */ : 3 /* Q3TTS_PCM_ALAW */;
+    return data;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Linear-interpolation resampler (reference wav_reader.cpp:145-164): out[i] samples the input at
 // i * src/dst, positions and weights in double, floor(n * dst/src) output samples, no anti-alias filter.

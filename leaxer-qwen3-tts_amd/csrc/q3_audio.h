@@ -15,6 +15,10 @@ namespace q3 {
 
 // mono float samples in [-1, 1); empty on any failure (as the reference).  *sample_rate is set on success.
 std::vector<float> read_wav(const std::string& path, int* sample_rate);
+// The bytes of a G.711 WAV (format tag 7 mu-law / 6 A-law, 8 bits, mono), which read_wav returns nothing for; *format is set to
+// Q3TTS_PCM_MULAW (2) / Q3TTS_PCM_ALAW (3).  A G.711 file with more than one channel throws std::invalid_argument naming it; anything
+// else (another tag, other bits, no file) gives an empty result.  read_wav itself is the reference's reader and stays as it is.
+std::vector<uint8_t> read_wav_g711(const std::string& path, int* sample_rate, int* format);
 std::vector<float> resample_linear(const std::vector<float>& audio, int src_rate, int dst_rate);
 // resample_linear over audio that is still arriving: the number of output samples a stream at src_rate has emitted in all once it
 // holds n_received samples.  finish: resample_linear's own length.  Otherwise the largest count whose every output i (a) has both

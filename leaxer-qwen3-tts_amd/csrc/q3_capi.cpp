@@ -371,6 +371,17 @@ int64_t q3tts_sink_emitted(int32_t rate, int64_t n_received, int finished) {
     } catch (const std::exception& ex) { g_sink_err = ex.what(); return -1; }
     catch (...) { g_sink_err = "unknown error"; return -1; }
 }
+// G.711 on the host (include/q3tts.h "G.711"): the inline functions of q3_common.h that pcm_sink_store and rs_stream_sample use
+int q3tts_g711_encode_host(int format, const int16_t* in, int64_t n, uint8_t* out) {
+    if (!q3::pcm_format_g711(format) || n < 0 || (n > 0 && (!in || !out))) return -1;
+    for (int64_t i = 0; i < n; ++i) out[i] = q3::g711_enc(format, in[i]);
+    return 0;
+}
+int q3tts_g711_decode_host(int format, const uint8_t* in, int64_t n, int16_t* out) {
+    if (!q3::pcm_format_g711(format) || n < 0 || (n > 0 && (!in || !out))) return -1;
+    for (int64_t i = 0; i < n; ++i) out[i] = q3::g711_dec(format, in[i]);
+    return 0;
+}
 int q3tts_pcm_sink_begin(q3tts_engine* h, int32_t sample_rate, int format, int* sink_id) {
     Q3_API_BEGIN(h)
     if (!sink_id) throw q3::Error("pcm sink: NULL argument");
@@ -407,7 +418,7 @@ int q3tts_codec_stream_push_batch_any_host(q3tts_engine* h, int n_streams, const
 int q3tts_engine_set_sink(q3tts_engine* h, const q3tts_sink* sink) {
     Q3_API_BEGIN(h)
     if (!sink) { h->sink = q3tts_sink{ 0, 0, nullptr, nullptr }; return 0; }
-    if (sink->format != Q3TTS_PCM_F32 && sink->format != Q3TTS_PCM_S16) throw q3::Error("engine_set_sink: format " + std::to_string(sink->format) + " is neither Q3TTS_PCM_F32 nor Q3TTS_PCM_S16");
+    if (!q3::pcm_format_known(sink->format)) throw q3::Error("engine_set_sink: format " + std::to_string(sink->format) + " is neither Q3TTS_PCM_F32 nor Q3TTS_PCM_S16, nor Q3TTS_PCM_MULAW (2) or Q3TTS_PCM_ALAW (3)");
     if (!sink->cb) throw q3::Error("engine_set_sink: null callback");
     (void)h->e->sink.plan_for(sink->sample_rate);   // refuses a bad rate by name, and has the table uploaded before the first utterance
     h->sink = *sink;
@@ -1322,7 +1333,7 @@ static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids
                               + (h->loud ? q3::kLoudBlock - 1 : 0);   // a loudness stage (q3tts_engine_set_loudness) holds back less than one sub-block
     const q3::SinkPlan* splan = sunk ? &e.sink.plan_for(sink.sample_rate).plan : nullptr;
     const int64_t sink_cap = sunk ? ((stage_cap + splan->half) * splan->L + splan->M - 1) / splan->M + 2 : 0;
-    const int64_t chunk_floats = sunk ? (sink_cap * (sink.format == Q3TTS_PCM_S16 ? 2 : 4) + 3) / 4 : stage_cap;   // per slot, 4-byte aligned
+    const int64_t chunk_floats = sunk ? (sink_cap * (int64_t)q3::pcm_format_bytes(sink.format) + 3) / 4 : stage_cap;   // per slot, 4-byte aligned
     const int64_t deliver_cap = sunk ? sink_cap : stage_cap;
     std::vector<float> chunk_pcm((size_t)B * chunk_floats);
     std::vector<float*> pcm_ptr((size_t)B);
@@ -1543,6 +1554,20 @@ int q3tts_read_wav_host(const char* path, float* out, int64_t cap, int64_t* n_sa
         for (int64_t i = 0; i < (int64_t)a.size() && i < cap && out; ++i) out[i] = a[(size_t)i];
         return 0;
     } catch (...) { return -1; }
+}
+int q3tts_read_wav_g711_host(const char* path, uint8_t* out, int64_t cap, int64_t* n_samples, int32_t* sample_rate, int* format) {
+    if (!path || !n_samples || !sample_rate || !format) return -1;
+    try {
+        int sr = 0, fmt = 0;
+        const std::vector<uint8_t> a = q3::read_wav_g711(path, &sr, &fmt);
+        if (a.empty()) return -1;
+        *n_samples = (int64_t)a.size();
+        *sample_rate = sr;
+        *format = fmt;
+        if (out && cap > 0) memcpy(out, a.data(), (size_t)std::min<int64_t>(cap, (int64_t)a.size()));
+        return 0;
+    } catch (const std::invalid_argument&) { return -2; }
+    catch (...) { return -1; }
 }
 int64_t q3tts_resample_host(const float* in, int64_t n, int32_t src_rate, int32_t dst_rate, float* out, int64_t cap) {
     if (n < 0 || (n > 0 && !in) || src_rate <= 0 || dst_rate <= 0) return -1;

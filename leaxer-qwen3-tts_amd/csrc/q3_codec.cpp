@@ -820,7 +820,7 @@ void Engine::codec_stream_set_speed(int sid, int speed_permille) {
 
 void Engine::codec_stream_set_sink(int sid, int rate, int format) {
     stream_set_stage(*this, sid, "codec_stream_set_sink", SK_SINK, [&] {
-        if (format != Q3TTS_PCM_F32 && format != Q3TTS_PCM_S16) throw Error("codec_stream_set_sink: format " + std::to_string(format) + " is neither Q3TTS_PCM_F32 nor Q3TTS_PCM_S16");
+        if (!pcm_format_known(format)) throw Error("codec_stream_set_sink: format " + std::to_string(format) + " is neither Q3TTS_PCM_F32 nor Q3TTS_PCM_S16, nor Q3TTS_PCM_MULAW (2) or Q3TTS_PCM_ALAW (3)");
         return rate == 24000 && format == Q3TTS_PCM_F32 ? -1 : sink.begin(rate, format);
     });
 }

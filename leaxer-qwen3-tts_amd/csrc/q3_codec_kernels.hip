@@ -1543,12 +1543,14 @@ __device__ __forceinline__ float pcm_sink_sample(const PcmSinkDesc& d, int64_t k
     return inside ? v : 0.0f;
 }
 __device__ __forceinline__ void pcm_sink_store(const PcmSinkDesc& d, int i, float y) {
-    if (d.s16) {
-        const float v = y > 1.0f ? 1.0f : (y < -1.0f ? -1.0f : y);
-        ((int16_t*)d.out)[i] = (int16_t)(v * 32767.0f);
-    } else {
+    if (d.format == Q3TTS_PCM_F32) {   // the format is the sink's: uniform over the workgroup
         ((float*)d.out)[i] = y;
+        return;
     }
+    const float v = y > 1.0f ? 1.0f : (y < -1.0f ? -1.0f : y);
+    const int16_t s = (int16_t)(v * 32767.0f);
+    if (d.format == Q3TTS_PCM_S16) ((int16_t*)d.out)[i] = s;
+    else ((uint8_t*)d.out)[i] = g711_enc(d.format, s);   // one byte store per lane
 }
 __global__ __launch_bounds__(256) void k_pcm_sink(const PcmSinkDesc* descs) {
     extern __shared__ float sink_lds[];

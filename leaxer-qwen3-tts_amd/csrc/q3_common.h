@@ -46,6 +46,47 @@ inline float bf16_to_f32(bf16_t b) {
     return f;
 }
 
+// G.711 (include/q3tts.h "G.711"): the laws on int16, integers only, shared by the host helpers and the kernels
+// (pcm_sink_store, rs_stream_sample).  floor(log2 m) is 31 - clz(m); m >= 132 (mu-law) and a >= 32 (A-law) where it is taken.
+__host__ __device__ inline int g711_log2(uint32_t v) { return 31 - __builtin_clz(v); }
+__host__ __device__ inline uint8_t g711_mulaw_enc(int16_t s) {
+    const int32_t mag = s < 0 ? -(int32_t)s : (int32_t)s;
+    const uint32_t m = (uint32_t)(mag > 32635 ? 32635 : mag) + 132u;
+    const int e = g711_log2(m) - 7;
+    const uint32_t mant = (m >> (e + 3)) & 15u;
+    return (uint8_t)(~((s < 0 ? 0x80u : 0u) | ((uint32_t)e << 4) | mant) & 0xFFu);
+}
+__host__ __device__ inline uint8_t g711_alaw_enc(int16_t s) {
+    const int32_t mag = s < 0 ? -(int32_t)s : (int32_t)s;
+    const uint32_t a = (uint32_t)(mag > 32767 ? 32767 : mag) >> 3;
+    const int e = a < 32u ? 0 : g711_log2(a) - 4;
+    const uint32_t mant = a < 32u ? a >> 1 : (a >> e) & 15u;
+    return (uint8_t)(((s >= 0 ? 0x80u : 0u) | ((uint32_t)e << 4) | mant) ^ 0x55u);
+}
+__host__ __device__ inline int16_t g711_mulaw_dec(uint8_t b) {
+    const uint32_t u = ~(uint32_t)b & 0xFFu;
+    const int e = (int)(u >> 4) & 7;
+    const int32_t m = (int32_t)((((u & 15u) << 3) + 132u) << e) - 132;
+    return (int16_t)(u & 0x80u ? -m : m);
+}
+__host__ __device__ inline int16_t g711_alaw_dec(uint8_t b) {
+    const uint32_t x = (uint32_t)b ^ 0x55u;
+    const int e = (int)(x >> 4) & 7;
+    const uint32_t mant = x & 15u;
+    const int32_t m = e == 0 ? (int32_t)((mant << 4) + 8u) : (int32_t)(((mant << 4) + 0x108u) << (e - 1));
+    return (int16_t)(x & 0x80u ? m : -m);
+}
+__host__ __device__ inline uint8_t g711_enc(int format, int16_t s) { return format == Q3TTS_PCM_MULAW ? g711_mulaw_enc(s) : g711_alaw_enc(s); }
+__host__ __device__ inline int16_t g711_dec(int format, uint8_t b) { return format == Q3TTS_PCM_MULAW ? g711_mulaw_dec(b) : g711_alaw_dec(b); }
+inline bool pcm_format_known(int format) { return format >= Q3TTS_PCM_F32 && format <= Q3TTS_PCM_ALAW; }
+inline bool pcm_format_g711(int format) { return format == Q3TTS_PCM_MULAW || format == Q3TTS_PCM_ALAW; }
+// bytes of one sample in a Q3TTS_PCM_* format
+inline size_t pcm_format_bytes(int format) { return format == Q3TTS_PCM_F32 ? 4 : (format == Q3TTS_PCM_S16 ? 2 : 1); }
+inline const char* pcm_format_name(int format) {
+    return format == Q3TTS_PCM_F32 ? "float (Q3TTS_PCM_F32)" : format == Q3TTS_PCM_S16 ? "int16 (Q3TTS_PCM_S16)"
+         : format == Q3TTS_PCM_MULAW ? "mu-law (Q3TTS_PCM_MULAW)" : "A-law (Q3TTS_PCM_ALAW)";
+}
+
 // ------------------------------------------------------------------------------------------------
 // kernel argument blocks + launchers (q3_decode_kernels.hip)
 // ------------------------------------------------------------------------------------------------
@@ -436,7 +477,7 @@ void launch_prime_row_tails(const float* h, const CodecStreamDesc* descs, int g,
 // by the push's n_new samples at x_new (device; the vocoder's PCM where it lies, or staged host samples).  Output i of the launch is the
 // sink's absolute output j = out0 + i: kc = floor(j M / L), p = (j M) mod L, y = sum_t tab[p][t] * x[kc - half + 1 + t], t ascending in
 // fp32, x[k] = 0 for k < 0 and k >= n_total (which only a finishing push reaches).  taps == 0 (24 kHz): y[j] = x[j].  The result is
-// written to out[i] as float, or as int16 by the CLI's rule (clip to [-1, 1], (int16_t)(v * 32767.0f)).  Threads [n_out, n_out + keep)
+// written to out[i] as float, as int16 by the CLI's rule (clip to [-1, 1], (int16_t)(v * 32767.0f)), or as the G.711 byte of that int16.  Threads [n_out, n_out + keep)
 // write the sink's next carry, the last `keep` samples of (carry, new), into carry_out: the other of the sink's two carry buffers.
 struct PcmSinkDesc {
     const float* carry_in = nullptr; float* carry_out = nullptr;
@@ -447,7 +488,7 @@ struct PcmSinkDesc {
     int64_t n_before = 0, n_total = 0;  // samples received before / with this push
     int64_t out0 = 0;                   // absolute index of the first new output
     int32_t n_new = 0, n_out = 0, keep = 0;   // keep == 0: the carry stays
-    int32_t L = 1, M = 1, half = 0, taps = 0, s16 = 0;
+    int32_t L = 1, M = 1, half = 0, taps = 0, format = 0;   // format: Q3TTS_PCM_* of `out`
     int32_t tab_lds = 0;                // the table's rows are staged in LDS (pcm_sink_tab_in_lds)
 };
 constexpr int kPcmSinkLdsX = 256 * 6 + 192 + 8;      // inputs of 256 outputs at the lowest rate (M / L <= 6, taps <= 192)
@@ -573,7 +614,7 @@ void launch_spk_asp_pool(const float* scores, const float* x, int T, int C, floa
 void launch_resample_linear(const float* raw, float* rs, const SpkClip* clips, int n_clips, int max_n_rs, hipStream_t s);
 // The same resampler for audio that is still arriving (encoder streams, q3_encoder.cpp).  One stream of one push:
 // the samples the stream has are its carry (floats, the last `n_before - carry_abs0` samples before this push) followed by the
-// push's n_new staged samples (float, or int16 converted as (float)v / 32768.0f).  Output i of the launch is the stream's absolute
+// push's n_new staged samples (float, int16 converted as (float)v / 32768.0f, or G.711 bytes decoded to that int16).  Output i of the launch is the stream's absolute
 // output out0 + i: position, taps and weight from that absolute index in double, as q3::resample_linear forms them; the upper tap
 // is clamped to n_total - 1, which only a finishing push reaches.  All indices are 64-bit: an hour at 384 kHz is 1.38e9 samples.
 // The launch also writes the stream's next carry, the last `keep` samples of (carry, new), into carry_out: the other of the
@@ -586,7 +627,7 @@ struct EncRsStream {
     int64_t in_off = 0;                 // byte offset of the new samples in the staging buffer (a multiple of 4)
     int32_t n_new = 0, n_out = 0, keep = 0;   // keep == 0: the carry stays (a push without samples)
     int32_t x24_off = 0;                // first new output in the push's 24 kHz buffer
-    int32_t src_rate = 0, s16 = 0;
+    int32_t src_rate = 0, format = 0;   // format: Q3TTS_PCM_* of the staged samples
 };
 void launch_resample_linear_streams(const void* staged, float* x24, const EncRsStream* tab /* device, [n] */, int n, int max_work /* largest n_out + keep */, hipStream_t s);
 // log-mel of q3::log_mel for the clone path's MelSpec (n_fft = win = 1024, hop 256, 128 bands): mel + 128 * row_off is the clip's [128][T]

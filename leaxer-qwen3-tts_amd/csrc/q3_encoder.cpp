@@ -35,10 +35,10 @@ struct EncStream {
     bool open = false, finished = false;
     int64_t max_samples = 0, rows[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     float* buf = nullptr; size_t buf_floats = 0;
-    int rate = 24000, s16 = 0, carry_len = 0, carry_cur = 0;
+    int rate = 24000, format = Q3TTS_PCM_F32, carry_len = 0, carry_cur = 0;
     int64_t n_raw = 0;
     size_t carry_off = 0;   // the first carry buffer's first float in buf
-    bool plain() const { return rate == 24000 && !s16; }
+    bool plain() const { return rate == 24000 && format == Q3TTS_PCM_F32; }
 };
 static constexpr size_t kEncCarryFloats = 64;   // a carry buffer: ceil(384000 / 24000) + 1 = 17 samples at most, one 256-byte line
 struct EncoderW {
@@ -386,8 +386,8 @@ int Engine::audio_stream_begin(int64_t max_samples, int sample_rate, int format)
     if (!enc) throw Error("weights not finalized");
     if (sample_rate < 1 || sample_rate > kEncMaxStreamRate)
         throw Error("audio stream: sample_rate must be 1.." + std::to_string(kEncMaxStreamRate) + ", got " + std::to_string(sample_rate));
-    if (format != Q3TTS_PCM_F32 && format != Q3TTS_PCM_S16)
-        throw Error("audio stream: format must be Q3TTS_PCM_F32 (0) or Q3TTS_PCM_S16 (1), got " + std::to_string(format));
+    if (!pcm_format_known(format))
+        throw Error("audio stream: format must be Q3TTS_PCM_F32 (0) or Q3TTS_PCM_S16 (1), got " + std::to_string(format) + "; or Q3TTS_PCM_MULAW (2) or Q3TTS_PCM_ALAW (3)");
     const int64_t hour = (int64_t)3600 * sample_rate;   // at 24 kHz: kEncMaxStreamSamples
     if (max_samples == 0) max_samples = (int64_t)60 * sample_rate;
     if (max_samples < 1 || max_samples > hour)
@@ -416,7 +416,7 @@ int Engine::audio_stream_begin(int64_t max_samples, int sample_rate, int format)
     // no clearing: a ring slot, and a carry sample, is read only for an absolute row this stream has written
     st.open = true; st.finished = false; st.max_samples = max_samples;
     for (int64_t& r : st.rows) r = 0;
-    st.rate = sample_rate; st.s16 = format == Q3TTS_PCM_S16 ? 1 : 0; st.n_raw = 0; st.carry_cur = 0; st.carry_off = plan.floats;
+    st.rate = sample_rate; st.format = format; st.n_raw = 0; st.carry_cur = 0; st.carry_off = plan.floats;
     st.carry_len = resample_stream_carry(sample_rate, 24000);
     return id;
 }
@@ -437,7 +437,7 @@ void Engine::audio_stream_info(int id, int64_t* n_samples, int32_t* n_frames, in
 void Engine::audio_stream_format(int id, int32_t* sample_rate, int32_t* format) const {
     const EncStream& st = enc_stream_at(*this, id, "audio_stream_format");
     if (sample_rate) *sample_rate = st.rate;
-    if (format) *format = st.s16 ? Q3TTS_PCM_S16 : Q3TTS_PCM_F32;
+    if (format) *format = st.format;
 }
 
 // the 24 kHz samples a push of n of the stream's own samples feeds the encoder: the host rule after the push minus before it
@@ -470,7 +470,8 @@ void Engine::audio_stream_push_batch(int n_streams, const int32_t* ids, const vo
         const EncStream& st = enc_stream_at(*this, ids[i], "audio stream push");
         for (int j = 0; j < i; ++j) if (ids[j] == ids[i]) throw Error(who + "given twice in one push");
         if (st.finished) throw Error(who + "is finished");
-        if (float_only && st.s16) throw Error(who + "takes int16 samples (Q3TTS_PCM_S16): push it through q3tts_audio_stream_push_any_host, not a float entry");
+        if (float_only && st.format == Q3TTS_PCM_S16) throw Error(who + "takes int16 samples (Q3TTS_PCM_S16): push it through q3tts_audio_stream_push_any_host, not a float entry");
+        if (float_only && pcm_format_g711(st.format)) throw Error(who + "takes " + pcm_format_name(st.format) + " bytes: push it through q3tts_audio_stream_push_any_host, not a float entry");
         if (n_samples[i] < 0) throw Error(who + "n_samples must not be negative, got " + std::to_string(n_samples[i]));
         if (n_samples[i] > 0 && !pcm[i]) throw Error(who + "NULL audio pointer");
         if (n_samples[i] > (int64_t)60 * st.rate)
@@ -506,7 +507,7 @@ void Engine::audio_stream_push_batch(int n_streams, const int32_t* ids, const vo
                 spans[(size_t)l * n + i].off = (int32_t)tot[(size_t)l]; spans[(size_t)l * n + i].T = newr(i, l);
                 tot[(size_t)l] += newr(i, l);
             }
-        // the streams that resample on the way in: their new samples are staged as they came, float or int16
+        // the streams that resample on the way in: their new samples are staged as they came: float, int16 or G.711 bytes
         std::vector<EncRsStream> rs; size_t staged_bytes = 0; int rs_work = 0;
         for (int i = 0; i < n; ++i) {
             EncStream& st = stream_of(i);
@@ -519,8 +520,8 @@ void Engine::audio_stream_push_batch(int n_streams, const int32_t* ids, const vo
             d.carry_abs0 = st.n_raw - held; d.n_before = st.n_raw; d.n_total = st.n_raw + add; d.out0 = st.rows[0];
             d.in_off = (int64_t)staged_bytes; d.n_new = (int32_t)add; d.n_out = newr(i, 0);
             d.keep = add > 0 ? (int32_t)std::min<int64_t>(st.carry_len, d.n_total) : 0;
-            d.x24_off = spans[(size_t)i].off; d.src_rate = st.rate; d.s16 = st.s16;
-            staged_bytes += ((size_t)add * (st.s16 ? 2 : 4) + 3) / 4 * 4;
+            d.x24_off = spans[(size_t)i].off; d.src_rate = st.rate; d.format = st.format;
+            staged_bytes += ((size_t)add * pcm_format_bytes(st.format) + 3) / 4 * 4;
             rs_work = std::max(rs_work, d.n_out + d.keep);
             rs.push_back(d);
         }
@@ -627,7 +628,7 @@ void Engine::audio_stream_push_batch(int n_streams, const int32_t* ids, const vo
             if (st.plain()) {
                 if (add > 0) Q3_HIP_CHECK(hipMemcpyAsync(b.x24 + spans[(size_t)i].off, pcm[g0 + i], add * sizeof(float), hipMemcpyHostToDevice, stream));
             } else if (add > 0 || newr(i, 0) > 0) {
-                if (add > 0) Q3_HIP_CHECK(hipMemcpyAsync(b.staged + rs[(size_t)k].in_off, pcm[g0 + i], add * (st.s16 ? 2 : 4), hipMemcpyHostToDevice, stream));
+                if (add > 0) Q3_HIP_CHECK(hipMemcpyAsync(b.staged + rs[(size_t)k].in_off, pcm[g0 + i], add * pcm_format_bytes(st.format), hipMemcpyHostToDevice, stream));
                 ++k;
             }
         }

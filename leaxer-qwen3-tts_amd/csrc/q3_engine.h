@@ -290,7 +290,7 @@ public:
         int begin(int rate, int format);
         void free_all() override;
         int64_t push_len(int id, int64_t n_new, bool finish) const override;
-        size_t out_el(int id) const override { return tab.get(id).format == Q3TTS_PCM_S16 ? 2 : 4; }
+        size_t out_el(int id) const override { return pcm_format_bytes(tab.get(id).format); }
         bool fill(StagePush& q, size_t di, char* out, int32_t* offs) override;
         void issue(size_t d0, int n_live) override; void commit_one(const StagePush& q) override;
     } sink{*this};

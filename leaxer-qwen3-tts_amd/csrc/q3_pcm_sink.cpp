@@ -1,6 +1,6 @@
 // q3_pcm_sink.cpp — PCM sinks: the output side's mirror of the encoder streams' resampler (4k).  A sink takes 24 kHz
 // float PCM that already lies on the device (the vocoder's, or samples staged by the standalone entry) and delivers it at its own rate
-// (4 000 .. 192 000 Hz) as float or int16: a windowed-sinc polyphase resampler (q3_audio.h: sink_plan) whose state is the last
+// (4 000 .. 192 000 Hz) as float, int16 or G.711 bytes: a windowed-sinc polyphase resampler (q3_audio.h: sink_plan) whose state is the last
 // 2 * half + ceil(M / L) input samples.  All sinks of a call share one launch (launch_pcm_sinks); how many samples a push delivers
 // is the host rule sink_emitted and nothing else.  Reserve / launch / commit and the standalone entry are Stage's (q3_stage.cpp).
 // [HINT] no counterpart in the reference, which writes 24 kHz only (main.cpp).
@@ -25,7 +25,7 @@ const Engine::SinkPlanDev& Engine::SinkStage::plan_for(int rate) {
 }
 
 int Engine::SinkStage::begin(int rate, int format) {
-    if (format != Q3TTS_PCM_F32 && format != Q3TTS_PCM_S16) throw Error("pcm sink: format " + std::to_string(format) + " is neither Q3TTS_PCM_F32 nor Q3TTS_PCM_S16");
+    if (!pcm_format_known(format)) throw Error("pcm sink: format " + std::to_string(format) + " is neither Q3TTS_PCM_F32 nor Q3TTS_PCM_S16, nor Q3TTS_PCM_MULAW (2) or Q3TTS_PCM_ALAW (3)");
     const SinkPlanDev& pd = plan_for(rate);
     const int id = tab.free_id();
     float*& carry = tab.slots[(size_t)id].carry;
@@ -60,7 +60,7 @@ bool Engine::SinkStage::fill(StagePush& q, size_t di, char* out, int32_t*) {
     if (q.n_new > 2147483647LL || q.n_out > 2147483647LL - 256) throw Error("pcm sink: push too large");
     d.n_new = (int32_t)q.n_new; d.n_out = (int32_t)q.n_out;
     d.keep = q.n_new > 0 ? (int32_t)std::min<int64_t>(d.n_total, sink_carry(P)) : 0;
-    d.L = P.L; d.M = P.M; d.half = P.half; d.taps = P.taps; d.s16 = S.format == Q3TTS_PCM_S16;
+    d.L = P.L; d.M = P.M; d.half = P.half; d.taps = P.taps; d.format = S.format;
     d.tab_lds = pcm_sink_tab_in_lds(P.L, P.taps) ? 1 : 0;
     return d.n_out + d.keep != 0;   // 24 kHz float never comes here; a finish that adds nothing is dropped
 }

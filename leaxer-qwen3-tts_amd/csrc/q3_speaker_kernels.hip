@@ -186,13 +186,16 @@ __global__ __launch_bounds__(256) void k_resample_linear(const float* raw, float
 
 // k_resample_linear for encoder streams: the clip is still arriving, so a sample is either in the stream's carry or among the push's
 // new ones.  Both addresses are clamped into their buffers and both loads issued; the value is selected afterwards.
-__device__ __forceinline__ float rs_stream_sample(const EncRsStream& d, const float* fnew, const int16_t* snew, int64_t k) {
+__device__ __forceinline__ float rs_stream_sample(const EncRsStream& d, const char* staged_new, int64_t k) {
     int64_t jn = k - d.n_before, jc = k - d.carry_abs0;
     const bool is_new = jn >= 0;
     const int64_t last_new = d.n_new > 0 ? d.n_new - 1 : 0, last_c = d.n_before - d.carry_abs0 > 0 ? d.n_before - d.carry_abs0 - 1 : 0;
     jn = jn < 0 ? 0 : (jn > last_new ? last_new : jn);
     jc = jc < 0 ? 0 : (jc > last_c ? last_c : jc);
-    const float vn = d.s16 ? (float)snew[jn] / 32768.0f : fnew[jn];   // the staging buffer always holds at least one padded element
+    float vn;   // the staging buffer always holds at least one padded element; the format is the stream's (uniform over blockIdx.y)
+    if (d.format == Q3TTS_PCM_F32) vn = ((const float*)staged_new)[jn];
+    else if (d.format == Q3TTS_PCM_S16) vn = (float)((const int16_t*)staged_new)[jn] / 32768.0f;
+    else vn = (float)g711_dec(d.format, ((const uint8_t*)staged_new)[jn]) / 32768.0f;
     const float vc = d.carry_in[jc];
     return is_new ? vn : vc;
 }
@@ -200,11 +203,10 @@ __global__ __launch_bounds__(256) void k_stream_resample_linear(const char* stag
     const EncRsStream d = tab[blockIdx.y];
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= d.n_out + d.keep) return;
-    const float* fnew = (const float*)(staged + d.in_off);
-    const int16_t* snew = (const int16_t*)(staged + d.in_off);
+    const char* snew = staged + d.in_off;
     if (t >= d.n_out) {   // the next carry: the last `keep` samples the stream has
         const int j = t - d.n_out;
-        d.carry_out[j] = rs_stream_sample(d, fnew, snew, d.n_total - d.keep + j);
+        d.carry_out[j] = rs_stream_sample(d, snew, d.n_total - d.keep + j);
         return;
     }
     const int64_t i = d.out0 + t, last = d.n_total - 1;
@@ -214,7 +216,7 @@ __global__ __launch_bounds__(256) void k_stream_resample_linear(const char* stag
     if (k > last) k = last;   // never taken for an output the host rule emits; keeps the taps inside the stream whatever the table says
     const double w = pos - (double)k;
     const int64_t k1 = k + 1 < last ? k + 1 : last;
-    x24[d.x24_off + t] = (float)((double)rs_stream_sample(d, fnew, snew, k) * (1.0 - w) + (double)rs_stream_sample(d, fnew, snew, k1) * w);
+    x24[d.x24_off + t] = (float)((double)rs_stream_sample(d, snew, k) * (1.0 - w) + (double)rs_stream_sample(d, snew, k1) * w);
 }
 
 // One frame per workgroup: window -> the host's radix-2 decimation-in-time FFT (same butterflies, same twiddle table, so the same

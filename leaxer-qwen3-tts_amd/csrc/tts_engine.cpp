@@ -285,15 +285,17 @@ std::vector<float> TTSEngine::synthesize_speaker(const std::string& text, Speake
     return synthesize(text, lang, params);
 }
 
-bool TTSEngine::set_output_format(int sample_rate, bool pcm16) {
+bool TTSEngine::set_output_format(int sample_rate, bool pcm16) { return set_output_encoding(sample_rate, pcm16 ? Q3TTS_PCM_S16 : Q3TTS_PCM_F32); }
+
+bool TTSEngine::set_output_encoding(int sample_rate, int format) {
     if (!ready_) return false;
-    if (sample_rate == config::SAMPLE_RATE && !pcm16) {
+    if (sample_rate == config::SAMPLE_RATE && format == Q3TTS_PCM_F32) {
         (void)q3tts_engine_set_sink(h_, nullptr);
-        out_rate_ = sample_rate; out_pcm16_ = false;
+        out_rate_ = sample_rate; out_format_ = Q3TTS_PCM_F32;
         return true;
     }
     q3tts_sink sk;
-    sk.sample_rate = sample_rate; sk.format = pcm16 ? Q3TTS_PCM_S16 : Q3TTS_PCM_F32; sk.user = this;
+    sk.sample_rate = sample_rate; sk.format = format; sk.user = this;
     sk.cb = [](void* user, int utt, int, int, const void* pcm, int64_t n, int finished) -> int {
         TTSEngine* self = static_cast<TTSEngine*>(user);
         return self->sink_fn_ ? self->sink_fn_(utt, pcm, n, finished) : 0;
@@ -303,14 +305,18 @@ bool TTSEngine::set_output_format(int sample_rate, bool pcm16) {
         std::cerr << "[TTSEngine] Output format: " << error_msg_ << std::endl;
         return false;
     }
-    out_rate_ = sample_rate; out_pcm16_ = pcm16;
+    out_rate_ = sample_rate; out_format_ = format;
     return true;
 }
 
-bool TTSEngine::convert_output(const std::vector<float>& pcm24, std::vector<float>* f32, std::vector<int16_t>* s16) {
+bool TTSEngine::convert_output(const std::vector<float>& pcm24, std::vector<float>* f32, std::vector<int16_t>* s16) { return convert_output(pcm24, f32, s16, nullptr); }
+
+bool TTSEngine::convert_output(const std::vector<float>& pcm24, std::vector<float>* f32, std::vector<int16_t>* s16, std::vector<uint8_t>* g711) {
     if (f32) f32->clear();
     if (s16) s16->clear();
-    if (!ready_ || (out_pcm16_ ? !s16 : !f32)) return false;
+    if (g711) g711->clear();
+    const bool as_f32 = out_format_ == Q3TTS_PCM_F32, as_s16 = out_format_ == Q3TTS_PCM_S16;
+    if (!ready_ || (as_f32 ? !f32 : as_s16 ? !s16 : !g711)) return false;
     if (!sink_on()) { *f32 = pcm24; return true; }
     int id = -1;
     auto fail = [&]() {
@@ -318,9 +324,10 @@ bool TTSEngine::convert_output(const std::vector<float>& pcm24, std::vector<floa
         if (id >= 0) (void)q3tts_pcm_sink_end(h_, id);
         if (f32) f32->clear();
         if (s16) s16->clear();
+        if (g711) g711->clear();
         return false;
     };
-    if (q3tts_pcm_sink_begin(h_, out_rate_, out_pcm16_ ? Q3TTS_PCM_S16 : Q3TTS_PCM_F32, &id) != 0) return fail();
+    if (q3tts_pcm_sink_begin(h_, out_rate_, out_format_, &id) != 0) return fail();
     const size_t step = 1440000;   // the most one push takes
     size_t done = 0;
     do {
@@ -329,10 +336,10 @@ bool TTSEngine::convert_output(const std::vector<float>& pcm24, std::vector<floa
         const uint8_t fin = done + m == pcm24.size() ? 1 : 0;
         const int64_t before = q3tts_sink_emitted(out_rate_, (int64_t)done, 0), after = q3tts_sink_emitted(out_rate_, (int64_t)(done + m), fin);
         if (before < 0 || after < before) return fail();
-        const size_t have = out_pcm16_ ? s16->size() : f32->size();
-        if (out_pcm16_) s16->resize(have + (size_t)(after - before)); else f32->resize(have + (size_t)(after - before));
+        const size_t have = as_f32 ? f32->size() : as_s16 ? s16->size() : g711->size(), want = have + (size_t)(after - before);
+        if (as_f32) f32->resize(want); else if (as_s16) s16->resize(want); else g711->resize(want);
         const float* in = pcm24.data() + done;
-        void* out = out_pcm16_ ? (void*)(s16->data() + have) : (void*)(f32->data() + have);
+        void* out = as_f32 ? (void*)(f32->data() + have) : as_s16 ? (void*)(s16->data() + have) : (void*)(g711->data() + have);
         int64_t len = 0;
         if (q3tts_pcm_sink_push_batch_host(h_, 1, &id, &in, &n_in, &fin, &out, after - before, &len) != 0 || len != after - before) return fail();
         done += m;
@@ -576,21 +583,34 @@ int TTSEngine::audio_stream_begin(int64_t max_samples, int sample_rate, bool pcm
     return id;
 }
 
+int TTSEngine::audio_stream_begin_encoded(int64_t max_samples, int sample_rate, int format) {
+    if (!ready_) return -1;
+    int id = -1;
+    if (q3tts_audio_stream_begin_rate(h_, sample_rate, format, max_samples, &id) != 0) { std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl; return -1; }
+    return id;
+}
+
 std::vector<int64_t> TTSEngine::audio_stream_push(int id, const float* pcm, size_t n, bool finish, bool* ok) {
-    return audio_stream_push_any(id, pcm, n, finish, ok, false);
+    return audio_stream_push_any(id, pcm, n, finish, ok, 0);
 }
 
 std::vector<int64_t> TTSEngine::audio_stream_push(int id, const int16_t* pcm, size_t n, bool finish, bool* ok) {
-    return audio_stream_push_any(id, pcm, n, finish, ok, true);
+    return audio_stream_push_any(id, pcm, n, finish, ok, 1);
 }
 
-std::vector<int64_t> TTSEngine::audio_stream_push_any(int id, const void* pcm, size_t n, bool finish, bool* ok, bool pcm16) {
+std::vector<int64_t> TTSEngine::audio_stream_push(int id, const uint8_t* pcm, size_t n, bool finish, bool* ok) {
+    return audio_stream_push_any(id, pcm, n, finish, ok, 2);
+}
+
+std::vector<int64_t> TTSEngine::audio_stream_push_any(int id, const void* pcm, size_t n, bool finish, bool* ok, int kind) {
     if (ok) *ok = false;
     if (!ready_) return {};
-    if (pcm16) {   // int16 samples go to a stream begun for them only: the engine reads them in the stream's format
+    const bool pcm16 = kind != 0;   // below: anything but float goes through the entry that reads the stream's own format
+    if (kind != 0) {   // int16 samples and G.711 bytes go to a stream begun for them only: the engine reads them in the stream's format
         int fmt = Q3TTS_PCM_F32;
         if (q3tts_audio_stream_format(h_, id, nullptr, &fmt) != 0) { std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl; return {}; }
-        if (fmt != Q3TTS_PCM_S16) { std::cerr << "[TTSEngine] audio stream " << id << " takes float samples, not int16" << std::endl; return {}; }
+        const bool fits = kind == 1 ? fmt == Q3TTS_PCM_S16 : (fmt == Q3TTS_PCM_MULAW || fmt == Q3TTS_PCM_ALAW);
+        if (!fits) { std::cerr << "[TTSEngine] audio stream " << id << " takes " << (fmt == Q3TTS_PCM_F32 ? "float samples" : fmt == Q3TTS_PCM_S16 ? "int16 samples" : "G.711 bytes") << ", not " << (kind == 1 ? "int16" : "G.711 bytes") << std::endl; return {}; }
     }
     const int frames = q3tts_audio_stream_push_len(h_, id, (int64_t)n, finish ? 1 : 0);
     if (frames < 0) { std::cerr << "[TTSEngine] " << q3tts_last_error(h_) << std::endl; return {}; }

@@ -153,6 +153,9 @@ public:
     int audio_stream_begin(int64_t max_samples, int sample_rate /* 24000: the overload above */, bool pcm16 = false);
     std::vector<int64_t> audio_stream_push(int id, const float* pcm, size_t n, bool finish = false, bool* ok = nullptr);
     std::vector<int64_t> audio_stream_push(int id, const int16_t* pcm, size_t n, bool finish = false, bool* ok = nullptr);   // streams begun with pcm16
+    // the same for a source in any Q3TTS_PCM_* format; Q3TTS_PCM_MULAW / _ALAW streams take G.711 bytes through the uint8_t overload
+    int audio_stream_begin_encoded(int64_t max_samples, int sample_rate, int format);
+    std::vector<int64_t> audio_stream_push(int id, const uint8_t* pcm, size_t n, bool finish = false, bool* ok = nullptr);
     void audio_stream_end(int id);
     // In-context voice clone ([HINT]): the reference audio is encoded, the text becomes reference text +
     // target text (ref_text_ids go between token_ids' three role ids and its text) and the utterance is continued behind the
@@ -173,8 +176,14 @@ public:
     // f32 / s16 is filled, by the format; at 24 000 Hz float f32 is the input).
     bool set_output_format(int sample_rate, bool pcm16 = false);
     int output_rate() const { return out_rate_; }
-    bool output_pcm16() const { return out_pcm16_; }
+    bool output_pcm16() const { return out_format_ == 1; }
     bool convert_output(const std::vector<float>& pcm24, std::vector<float>* f32, std::vector<int16_t>* s16);
+    // The same with any Q3TTS_PCM_* format (0 float, 1 int16, 2 mu-law, 3 A-law): Q3TTS_PCM_MULAW / _ALAW deliver G.711 bytes (include/q3tts.h "G.711": the byte of the
+    // int16 the pcm16 format gives), one uint8_t per sample in the callbacks' pointer and in convert_output's g711.
+    // set_output_format(rate, pcm16) is set_output_encoding(rate, pcm16 ? Q3TTS_PCM_S16 : Q3TTS_PCM_F32).
+    bool set_output_encoding(int sample_rate, int format);
+    int output_encoding() const { return out_format_; }
+    bool convert_output(const std::vector<float>& pcm24, std::vector<float>* f32, std::vector<int16_t>* s16, std::vector<uint8_t>* g711);
     // Speaking rate (include/q3tts.h: q3tts_engine_set_speed, q3tts_speed_*; the reference has no speed control).  speed 1.25 makes
     // every synthesize* method's audio 25 % faster at the same pitch (WSOLA on the GPU); the engine works in permille,
     // S = round(1000 * speed), 500 .. 2000, and 1.0 is no stage at all.  The scheduler's streaming methods stretch inside their
@@ -220,7 +229,7 @@ public:
 
 private:
     bool wrap_text(const std::string& text, std::vector<int64_t>& ids) const;
-    std::vector<int64_t> audio_stream_push_any(int id, const void* pcm, size_t n, bool finish, bool* ok, bool pcm16);
+    std::vector<int64_t> audio_stream_push_any(int id, const void* pcm, size_t n, bool finish, bool* ok, int kind);   // kind: 0 float, 1 int16, 2 G.711 bytes
     q3tts_engine* h_ = nullptr;
     q3tts_tokenizer* tok_ = nullptr;
     bool ready_ = false;
@@ -232,7 +241,7 @@ private:
     int max_ctx_ = 0;
     int n_groups_ = config::NUM_CODE_GROUPS;
     int out_rate_ = config::SAMPLE_RATE;
-    bool out_pcm16_ = false;
+    int out_format_ = 0;   // Q3TTS_PCM_F32 (include/q3tts.h)
     std::function<int(int, const void*, int64_t, int)> sink_fn_;   // the running streaming call's delivery, while an output format is set
     int speed_ = 1000;
     int gain_cb_ = 0, ceiling_ = 0;
@@ -244,7 +253,7 @@ private:
     bool level_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);
     // one push of a stretcher of this engine: out receives the push's samples (appended)
     bool stretch_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);
-    bool sink_on() const { return out_rate_ != config::SAMPLE_RATE || out_pcm16_; }
+    bool sink_on() const { return out_rate_ != config::SAMPLE_RATE || out_format_ != 0; }
 };
 
 inline int64_t language_to_codec_id(Language lang) { // reference src/tts_onnx.h:230-238

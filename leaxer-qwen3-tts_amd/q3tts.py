@@ -118,6 +118,7 @@ EXPORTS = [
     "q3tts_codec_stream_prime_batch_host", "q3tts_slots_codec_prime", "q3tts_codec_stream_info", "q3tts_synthesize_continue_stream_host",
     "q3tts_sink_plan", "q3tts_sink_last_error", "q3tts_sink_emitted", "q3tts_pcm_sink_begin", "q3tts_pcm_sink_push_batch_host", "q3tts_pcm_sink_end",
     "q3tts_codec_stream_set_sink", "q3tts_codec_stream_push_batch_any_host", "q3tts_engine_set_sink",
+    "q3tts_g711_encode_host", "q3tts_g711_decode_host", "q3tts_read_wav_g711_host",
     "q3tts_speed_emitted", "q3tts_speed_last_error", "q3tts_speed_window", "q3tts_speed_begin", "q3tts_speed_push_batch_host", "q3tts_speed_end",
     "q3tts_codec_stream_set_speed", "q3tts_engine_set_speed",
     "q3tts_level_gain", "q3tts_level_emitted", "q3tts_level_last_error", "q3tts_level_begin", "q3tts_level_push_batch_host", "q3tts_level_end",
@@ -775,7 +776,7 @@ class Engine:
 
     # ---- PCM sinks on their own (include/q3tts.h "audio out at the sink's rate") ----
     def pcm_sink_begin(self, sample_rate, dtype="float32"):
-        """a sink that takes 24 kHz float32 and delivers sample_rate (4000 .. 192000) as float32 or int16 -> sink id"""
+        """a sink that takes 24 kHz float32 and delivers sample_rate (4000 .. 192000) as float32, int16 or G.711 bytes ("mulaw" / "alaw", np.uint8) -> sink id"""
         fmt = _pcm_format(dtype)
         sid = C.c_int(-1)
         self.L.q3tts_pcm_sink_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.POINTER(C.c_int)]
@@ -799,7 +800,7 @@ class Engine:
         for i in range(n):
             rate, _ = fmts.get(int(ids[i]), (192000, PCM_F32))
             cap = max(cap, (int(lens[i]) + 200) * max(rate, 24000) // 24000 + 8)
-        outs = [np.empty(cap, np.int16 if fmts.get(int(ids[i]), (0, PCM_F32))[1] == PCM_S16 else np.float32) for i in range(n)]
+        outs = [np.empty(cap, _PCM_NP[fmts.get(int(ids[i]), (0, PCM_F32))[1]]) for i in range(n)]
         xptr = (C.c_void_p * n)(*[x.ctypes.data if x.size else None for x in xs])
         optr = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
         out_len = np.zeros(n, np.int64)
@@ -815,7 +816,7 @@ class Engine:
 
     def set_sink(self, sample_rate=None, dtype="float32", on_audio=None):
         """q3tts_engine_set_sink: the streaming entries deliver through on_audio(utt, frame_begin, frame_end, pcm, finished) at
-        sample_rate as float32 or int16; sample_rate None takes the sink away.  An exception in on_audio cancels the job; it is kept
+        sample_rate as float32, int16 or G.711 bytes ("mulaw" / "alaw", np.uint8); sample_rate None takes the sink away.  An exception in on_audio cancels the job; it is kept
         in self._sink_raised for the caller to re-raise."""
         self.L.q3tts_engine_set_sink.argtypes = [C.c_void_p, C.c_void_p]
         if sample_rate is None:
@@ -823,7 +824,7 @@ class Engine:
             self._sink_keep = None
             return
         fmt = _pcm_format(dtype)
-        npdt = np.int16 if fmt == PCM_S16 else np.float32
+        npdt = _PCM_NP[fmt]
         self._sink_raised = []
 
         def tramp(_user, utt, fb, fe, p, ns, fin):
@@ -877,7 +878,7 @@ class Engine:
         if any(int(i) in lvls for i in ids):
             n24 += 128                     # behind a limiter: plus what it held back
         cap = max((n24 + 200) * max(fmts.get(int(i), (24000, PCM_F32))[0], 24000) // 24000 + 8 for i in ids)
-        pcm = [np.empty(cap, np.int16 if fmts.get(int(i), (24000, PCM_F32))[1] == PCM_S16 else np.float32) for i in ids]
+        pcm = [np.empty(cap, _PCM_NP[fmts.get(int(i), (24000, PCM_F32))[1]]) for i in ids]
         ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in pcm])
         pcm_len = np.zeros(n, np.int64)
         fin = np.zeros(n, np.uint8) if finish is None else np.ascontiguousarray([1 if f else 0 for f in finish], np.uint8)
@@ -1293,23 +1294,23 @@ class Engine:
         return Engine.audio_stream_begin_rate(self, 24000, "float32", max_samples)
 
     def audio_stream_begin_rate(self, sample_rate, dtype="float32", max_samples=0):
-        """a new encoder stream at sample_rate (1 .. 384000) whose samples are pushed as dtype "float32" or "int16", for at most
+        """a new encoder stream at sample_rate (1 .. 384000) whose samples are pushed as dtype "float32", "int16", or G.711 bytes ("mulaw" / "alaw", np.uint8), for at most
         max_samples of its OWN samples (0: 60 s; at most one hour) -> stream id (q3tts_audio_stream_begin_rate).  Other than 24 kHz
         float32 the stream resamples on the GPU on the way in, bit-identical to audio_encode_batch of the whole audio at that rate
-        (int16 v is the float v / 32768)."""
+        (int16 v is the float v / 32768; a G.711 byte is decoded to that int16 on the GPU)."""
         if int(max_samples) < 0:
             raise ValueError("max_samples must be 0 (60 s) or positive")
         fmt = _pcm_format(dtype)
         sid = C.c_int(-1)
         self._ck(self.L.q3tts_audio_stream_begin_rate(self.h, int(sample_rate), fmt, int(max_samples), C.byref(sid)))
-        self.__dict__.setdefault("_audio_stream_fmt", {})[int(sid.value)] = (int(sample_rate), fmt == PCM_S16)
+        self.__dict__.setdefault("_audio_stream_fmt", {})[int(sid.value)] = (int(sample_rate), fmt)
         return int(sid.value)
 
     def audio_stream_format(self, sid):
         """(sample_rate, dtype name) the stream was begun with"""
         sr, fmt = C.c_int32(0), C.c_int(0)
         self._ck(self.L.q3tts_audio_stream_format(self.h, int(sid), C.byref(sr), C.byref(fmt)))
-        return int(sr.value), ("int16" if fmt.value == PCM_S16 else "float32")
+        return int(sr.value), _PCM_NAMES[fmt.value]
 
     def audio_stream_push_len(self, sid, n_samples, finish=False):
         """frames the next push of n_samples to this stream would return (host-only)"""
@@ -1318,14 +1319,15 @@ class Engine:
         return int(self._ck(self.L.q3tts_audio_stream_push_len(self.h, int(sid), int(n_samples), 1 if finish else 0)))
 
     @staticmethod
-    def _stream_pcm(pcm, what="pcm", s16=False):
+    def _stream_pcm(pcm, what="pcm", fmt=0):
         a = np.asarray(pcm)
-        if s16:
-            if a.size and a.dtype != np.int16:
-                raise ValueError("%s: expected int16 samples (the stream was begun with dtype int16), got dtype %s" % (what, a.dtype))
+        if fmt != PCM_F32:
+            want = np.int16 if fmt == PCM_S16 else np.uint8
+            if a.size and a.dtype != want:
+                raise ValueError("%s: expected %s samples (the stream was begun with dtype %s), got dtype %s" % (what, np.dtype(want).name, _PCM_NAMES[fmt], a.dtype))
             if a.ndim > 1 and a.size != max(a.shape):
                 raise ValueError("%s: expected mono samples [n], got shape %s" % (what, (a.shape,)))
-            return np.ascontiguousarray(a, np.int16).reshape(-1)
+            return np.ascontiguousarray(a, want).reshape(-1)
         if a.size and a.dtype.kind != "f":
             raise ValueError("%s: expected float samples (mono, 24 kHz), got dtype %s" % (what, a.dtype))
         if a.ndim > 1 and a.size != max(a.shape):
@@ -1334,7 +1336,7 @@ class Engine:
 
     def audio_stream_push_batch(self, sids, pcms, finish=None, want_latents=False):
         """one push to each of many streams in ONE call (q3tts_audio_stream_push_batch_host): pcms[i] are stream sids[i]'s next samples
-        (mono, at the stream's own rate, float or, for a stream begun with dtype int16, and only for it, int16; may be empty), finish[i] ends stream i's audio (None: none; a bool applies to all).  Returns the list of
+        (mono, at the stream's own rate, float or, for a stream begun with dtype int16 / mulaw / alaw, and only for it, int16 / uint8; may be empty), finish[i] ends stream i's audio (None: none; a bool applies to all).  Returns the list of
         the NEW codes [F_i][n_groups] per stream, bit-identical to audio_encode of each stream's concatenated audio; want_latents:
         (that list, the list of latents [F_i][enc_hidden])."""
         n = len(sids)
@@ -1347,10 +1349,10 @@ class Engine:
             raise ValueError("a stream may appear once per push")
         if n == 0:
             return ([], []) if want_latents else []
-        # int16 arrays for the streams begun with dtype int16, and only for them (begin recorded it; an id it never saw counts as float32
-        # and is the engine's to refuse)
+        # int16 / uint8 arrays for the streams begun with dtype int16 / mulaw / alaw, and only for them (begin recorded it; an id it never
+        # saw counts as float32 and is the engine's to refuse)
         begun = vars(self).get("_audio_stream_fmt", {})
-        keep = [Engine._stream_pcm(a, "pcms[%d]" % i, s16=begun.get(int(sids[i]), (24000, False))[1]) for i, a in enumerate(pcms)]
+        keep = [Engine._stream_pcm(a, "pcms[%d]" % i, fmt=begun.get(int(sids[i]), (24000, PCM_F32))[1]) for i, a in enumerate(pcms)]
         per = 1
         for r in list(self.cfg.enc_ratios)[: self.cfg.enc_n_ratios]:
             per *= int(r)
@@ -1374,19 +1376,19 @@ class Engine:
         fl = np.array(fin, np.int32)
         cp = np.array(caps, np.int32)
         nf = np.zeros(n, np.int32)
-        push = self.L.q3tts_audio_stream_push_batch_any_host if any(a.dtype == np.int16 for a in keep) else self.L.q3tts_audio_stream_push_batch_host
+        push = self.L.q3tts_audio_stream_push_batch_any_host if any(a.dtype != np.float32 for a in keep) else self.L.q3tts_audio_stream_push_batch_host
         self._ck(push(self.h, n, _p(ids), ptrs, _p(ns), _p(fl), optrs, lptrs, _p(cp), _p(nf)))
         codes = [o[: nf[i]] for i, o in enumerate(outs)]
         return (codes, [a[: nf[i]] for i, a in enumerate(lats)]) if want_latents else codes
 
     def _stream_state(self, sid):
-        """(rate, is int16, samples received, 24 kHz samples fed to the encoder) of an open stream, None for an id the engine refuses"""
+        """(rate, format, samples received, 24 kHz samples fed to the encoder) of an open stream, None for an id the engine refuses"""
         sr, fmt, ns = C.c_int32(0), C.c_int(0), C.c_int64(0)
         if self.L.q3tts_audio_stream_format(self.h, int(sid), C.byref(sr), C.byref(fmt)) != 0:
             return None
         if self.L.q3tts_audio_stream_info(self.h, int(sid), C.byref(ns), None, None, None) != 0:
             return None
-        return int(sr.value), fmt.value == PCM_S16, int(ns.value), resample_stream_emitted(int(sr.value), 24000, int(ns.value), False)
+        return int(sr.value), int(fmt.value), int(ns.value), resample_stream_emitted(int(sr.value), 24000, int(ns.value), False)
 
     def audio_stream_push(self, sid, pcm, finish=False, want_latents=False):
         """pcm (mono, the stream's own rate and sample format, any length up to 60 s) appended to stream sid -> the NEW frames' codes [F][n_groups];
@@ -1414,7 +1416,7 @@ class Engine:
         """audio_encode_long for a clip at sample_rate (mono float32, or int16), pushed chunk_samples of its own samples at a time
         (None: 4 s) through one stream begun at that rate -> codes [F][n_groups], bit-identical to what audio_encode_batch gives at
         that rate where it accepts the clip.  Nothing is resampled on the host."""
-        a = Engine._stream_pcm(pcm, "pcm", s16=np.asarray(pcm).dtype == np.int16)
+        a = Engine._stream_pcm(pcm, "pcm", fmt=PCM_S16 if np.asarray(pcm).dtype == np.int16 else PCM_F32)
         return Engine._encode_long(self, a, 4 * int(sample_rate) if chunk_samples is None else chunk_samples, sample_rate, "pcm")
 
     def _encode_long(self, a, chunk_samples, sample_rate, what):
@@ -1689,7 +1691,7 @@ class Engine:
             self.set_level(*level)
             self.set_pitch(1000 if pitch is None else pitch)
             self.set_loudness(*(loud if loud is not None else (None,)))
-            self.set_sink(24000 if sample_rate is None else sample_rate, "int16" if fmt == PCM_S16 else "float32", tee)
+            self.set_sink(24000 if sample_rate is None else sample_rate, _PCM_NAMES[fmt], tee)
         except BaseException:
             self.set_speed(None)
             self.set_level(0, 0)
@@ -1708,7 +1710,7 @@ class Engine:
         if raised:
             raise raised[0]
         self._ck(rc)
-        npdt = np.int16 if fmt == PCM_S16 else np.float32
+        npdt = _PCM_NP[fmt]
         return [np.concatenate(g) if g else np.zeros(0, npdt) for g in got]
 
     def synthesize_stream(self, token_lists, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
@@ -2012,7 +2014,9 @@ def resample_stream_emitted(src_rate, dst_rate, n_received, finish=False):
     return n
 
 
-PCM_F32, PCM_S16 = 0, 1
+PCM_F32, PCM_S16, PCM_MULAW, PCM_ALAW = 0, 1, 2, 3
+_PCM_NAMES = {PCM_F32: "float32", PCM_S16: "int16", PCM_MULAW: "mulaw", PCM_ALAW: "alaw"}
+_PCM_NP = {PCM_F32: np.float32, PCM_S16: np.int16, PCM_MULAW: np.uint8, PCM_ALAW: np.uint8}
 
 
 def sink_plan(sample_rate, want_table=True):
@@ -2196,7 +2200,45 @@ def _pcm_format(dtype):
         return PCM_F32
     if name in ("int16", "s16"):
         return PCM_S16
-    raise ValueError("dtype must be float32 or int16, got %r" % (dtype,))
+    if name in ("mulaw", "ulaw"):
+        return PCM_MULAW
+    if name == "alaw":
+        return PCM_ALAW
+    raise ValueError("dtype must be float32 or int16, or the G.711 names mulaw / ulaw / alaw, got %r" % (dtype,))
+
+
+def _g711_format(law):
+    fmt = law if isinstance(law, (int, np.integer)) else _pcm_format(law)
+    return int(fmt)
+
+
+def g711_encode(law, pcm16):
+    """int16 samples -> G.711 bytes (np.uint8) under law "mulaw" / "ulaw" / "alaw" (or PCM_MULAW / PCM_ALAW): the arithmetic of
+    include/q3tts.h "G.711", the functions the sink kernel uses.  Host-only.  Any other law raises ValueError."""
+    a = np.asarray(pcm16)
+    if a.size and a.dtype != np.int16:
+        raise ValueError("g711_encode: expected int16 samples, got dtype %s" % a.dtype)
+    a = np.ascontiguousarray(a, np.int16)
+    out = np.empty(a.shape, np.uint8)
+    Lb = lib()
+    Lb.q3tts_g711_encode_host.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+    if Lb.q3tts_g711_encode_host(_g711_format(law), _p(a), a.size, _p(out)) != 0:
+        raise ValueError("g711_encode: law must be mulaw (2) or alaw (3), got %r" % (law,))
+    return out
+
+
+def g711_decode(law, data):
+    """G.711 bytes (np.uint8) -> int16 samples; the functions the encoder streams' kernel uses.  Host-only."""
+    a = np.asarray(data)
+    if a.size and a.dtype != np.uint8:
+        raise ValueError("g711_decode: expected uint8 bytes, got dtype %s" % a.dtype)
+    a = np.ascontiguousarray(a, np.uint8)
+    out = np.empty(a.shape, np.int16)
+    Lb = lib()
+    Lb.q3tts_g711_decode_host.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+    if Lb.q3tts_g711_decode_host(_g711_format(law), _p(a), a.size, _p(out)) != 0:
+        raise ValueError("g711_decode: law must be mulaw (2) or alaw (3), got %r" % (law,))
+    return out
 
 
 def log_mel(audio):
@@ -2296,7 +2338,7 @@ def rng_uniform(seed, stream, frame, group):
 class AudioEncodeStream:
     """One encoder stream as a context manager: push(pcm) -> the new codes, finish() -> the last ones, .codes: everything so far
     [F][n_groups].  The concatenation is bit-identical to Engine.audio_encode_batch of the concatenated audio at sample_rate (mono;
-    dtype float32 or int16)."""
+    dtype float32 or int16, or "mulaw" / "alaw" for G.711 bytes as np.uint8)."""
 
     def __init__(self, engine, max_samples=0, sample_rate=24000, dtype="float32"):
         self.engine = engine
