@@ -5,24 +5,19 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <vector>
 
 #include "q3_audio.h"
 #include "q3_bpe.h"
 #include "q3_engine.h"
+#include "q3_job.h"
 
 using q3::Engine;
 
 struct q3tts_engine {
     Engine* e = nullptr;
     std::string err;
-    q3tts_sink sink = { 0, 0, nullptr, nullptr };   // q3tts_engine_set_sink (sample_rate 0: none)
-    int32_t speed = 1000;                           // q3tts_engine_set_speed (1000: none)
-    int32_t gain_cb = 0, ceiling = 0;               // q3tts_engine_set_level ((0, 0): none)
-    int32_t pitch = 1000;                           // q3tts_engine_set_pitch (1000: none)
-    bool loud = false;                              // q3tts_engine_set_loudness / _clear_loudness
-    int32_t loud_target = 0, loud_range = 0, loud_start = 0;
+    q3::StageSettings stages;   // what the q3tts_engine_set_* entries leave for the streaming jobs (q3_job.h)
 };
 static std::string g_create_err;
 
@@ -35,71 +30,6 @@ static std::string g_create_err;
     catch (const q3::Error& ex) { (h)->err = ex.msg; return -1; } \
     catch (const std::exception& ex) { (h)->err = ex.what(); return -1; } \
     catch (...) { (h)->err = "unknown error"; return -1; }
-
-// The vocoder phase of a job: utterance u's codes are row u of the engine's job buffer (Engine::codec_job_codes, stride row_frames frames),
-// got_frames[u] of them valid.  Shared by the scheduler (below) and q3tts_codec_decode_batch_host.
-static void vocoder_job(q3::Engine& e, int n_utt, const std::vector<int32_t>& got_frames, int row_frames, float* const* pcm_out, int64_t pcm_cap,
-                        int64_t* pcm_len) {
-    // Vocoder, once the decode queue is empty.  Utterances are taken longest first, in blocks of similar length (the shortest at least half
-    // the longest, at most 2^16 padded frames): a block's pre-transformer and upsampling stages run as one batched pass, its conv decoder in
-    // groups of up to 32 utterances per set of launches (about 4.7 MB of workspace per frame: groups sized to ~8 GB), each group padded to its
-    // own longest member.  Padding is exact: every layer is causal.  Single utterances, the exact-fp32 codec and configs whose decoder the
-    // batched kernels do not cover go one utterance at a time over the side lanes.
-    // A failure in here (arena / pinned-buffer allocation, a launch error) must not leave lanes holding this job's pcm_out / pcm_len
-    // pointers: the next job's drain would write through them.  codec_async_abort() waits for the lanes and forgets their items.
-    try {
-    std::vector<int> order((size_t)n_utt);
-    for (int u = 0; u < n_utt; ++u) { order[(size_t)u] = u; if (pcm_len) pcm_len[u] = 0; }
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return got_frames[(size_t)x] > got_frames[(size_t)y]; });
-    const bool batchable = e.codec_batchable();
-    std::vector<int> nf;
-    std::vector<float*> up;
-    std::vector<int64_t*> lp;
-    for (int y0 = 0; y0 < n_utt;) {
-        const int F0 = got_frames[(size_t)order[(size_t)y0]];
-        if (F0 <= 0) break;                                            // sorted: the rest of the job produced no frame
-        int y1 = y0 + 1;
-        // a block is a batch dimension of the batched kernels (gridDim.y / .z <= 65535): at most 4096 sequences and 2^16 padded frames, and
-        // no activation matrix of its batched front may reach 4 GB (k_conv_split addresses rows with 32-bit byte offsets): the widest is
-        // the ConvNeXt hidden [frames x upsampling][4 x cd_hidden] — at 0.6B dims exactly 4 GB at 2^16 frames, hence the strict bound
-        int64_t up_front = 1;
-        for (int i = 0; i < e.c.cd_n_up; ++i) up_front *= e.c.cd_up_ratios[i];
-        const int64_t widest = std::max<int64_t>((int64_t)4 * e.c.cd_hidden * up_front, std::max<int64_t>(e.c.cd_ffn, (int64_t)3 * e.c.cd_hidden));
-        const int64_t frame_cap = std::min<int64_t>((int64_t)1 << 16, (((int64_t)1 << 32) - 1) / ((int64_t)sizeof(float) * widest));
-        while (y1 < n_utt && y1 - y0 < 4096 && (int64_t)(y1 - y0 + 1) * F0 <= frame_cap && got_frames[(size_t)order[(size_t)y1]] * 2 >= F0) ++y1;
-        const int nblk = y1 - y0;
-        if (nblk >= 2 && batchable && F0 <= frame_cap / 2) {
-            int rows = 0;
-            e.codec_lanes_join();                                      // the previous block's groups still read the batched buffers
-            const float* hb = e.codec_pre_batch(e.codec_job_codes(0, row_frames), row_frames, nblk, F0, true, &rows, order.data() + y0);
-            const size_t ustride = (size_t)rows * e.c.cd_hidden;
-            const int group = (int)std::max<int64_t>(1, std::min<int64_t>(32, ((int64_t)8 << 30) / ((int64_t)4700000 * F0)));
-            for (int g0 = 0; g0 < nblk; g0 += group) {
-                const int g = std::min(group, nblk - g0);
-                nf.assign((size_t)g, 0); up.assign((size_t)g, nullptr); lp.assign((size_t)g, nullptr);
-                for (int k = 0; k < g; ++k) {
-                    const int u = order[(size_t)(y0 + g0 + k)];
-                    nf[(size_t)k] = got_frames[(size_t)u];
-                    if (pcm_len) lp[(size_t)k] = pcm_len + u;
-                    if (pcm_out) up[(size_t)k] = pcm_out[u];
-                }
-                e.codec_async_submit_group(hb + (size_t)g0 * ustride, ustride, nf[0], g, nf.data(), up.data(), pcm_cap, lp.data());
-            }
-        } else {
-            for (int y = y0; y < y1; ++y) {
-                const int u = order[(size_t)y];
-                e.codec_async_submit_dev(e.codec_job_codes(u, row_frames), got_frames[(size_t)u], pcm_out ? pcm_out[u] : nullptr, pcm_cap, pcm_len ? pcm_len + u : nullptr);
-            }
-        }
-        y0 = y1;
-    }
-    e.codec_async_drain();
-    } catch (...) {
-        e.codec_async_abort();
-        for (int u = 0; u < n_utt; ++u) if (pcm_len) pcm_len[u] = 0;
-        throw;
-    }
-}
 
 extern "C" {
 
@@ -272,7 +202,7 @@ int q3tts_codec_decode_batch_host(q3tts_engine* h, int n_utt, const int64_t* cod
         }
     }
     e.codec_job_upload(rows.data(), n_utt, row_frames);
-    vocoder_job(e, n_utt, nf, row_frames, pcm_out, pcm_cap, pcm_len);
+    q3::vocoder_job(e, n_utt, nf, row_frames, pcm_out, pcm_cap, pcm_len);
     return 0;
     Q3_API_END(h)
 }
@@ -417,11 +347,11 @@ int q3tts_codec_stream_push_batch_any_host(q3tts_engine* h, int n_streams, const
 }
 int q3tts_engine_set_sink(q3tts_engine* h, const q3tts_sink* sink) {
     Q3_API_BEGIN(h)
-    if (!sink) { h->sink = q3tts_sink{ 0, 0, nullptr, nullptr }; return 0; }
+    if (!sink) { h->stages.sink = q3tts_sink{ 0, 0, nullptr, nullptr }; return 0; }
     if (!q3::pcm_format_known(sink->format)) throw q3::Error("engine_set_sink: format " + std::to_string(sink->format) + " is neither Q3TTS_PCM_F32 nor Q3TTS_PCM_S16, nor Q3TTS_PCM_MULAW (2) or Q3TTS_PCM_ALAW (3)");
     if (!sink->cb) throw q3::Error("engine_set_sink: null callback");
     (void)h->e->sink.plan_for(sink->sample_rate);   // refuses a bad rate by name, and has the table uploaded before the first utterance
-    h->sink = *sink;
+    h->stages.sink = *sink;
     return 0;
     Q3_API_END(h)
 }
@@ -475,7 +405,7 @@ int q3tts_codec_stream_set_speed(q3tts_engine* h, int stream_id, int32_t speed_p
 int q3tts_engine_set_speed(q3tts_engine* h, int32_t speed_permille) {
     Q3_API_BEGIN(h)
     try { q3::speed_check(speed_permille); } catch (const std::invalid_argument& ex) { throw q3::Error(std::string("engine_set_speed: ") + ex.what()); }
-    h->speed = speed_permille;
+    h->stages.speed = speed_permille;
     return 0;
     Q3_API_END(h)
 }
@@ -529,7 +459,7 @@ int q3tts_codec_stream_set_level(q3tts_engine* h, int stream_id, int32_t gain_cb
 int q3tts_engine_set_level(q3tts_engine* h, int32_t gain_cb, int32_t ceiling_permille) {
     Q3_API_BEGIN(h)
     try { q3::level_check(gain_cb, ceiling_permille); } catch (const std::invalid_argument& ex) { throw q3::Error(std::string("engine_set_level: ") + ex.what()); }
-    h->gain_cb = gain_cb; h->ceiling = ceiling_permille;
+    h->stages.gain_cb = gain_cb; h->stages.ceiling = ceiling_permille;
     return 0;
     Q3_API_END(h)
 }
@@ -577,7 +507,7 @@ int q3tts_codec_stream_set_pitch(q3tts_engine* h, int stream_id, int32_t ratio_p
 int q3tts_engine_set_pitch(q3tts_engine* h, int32_t ratio_permille) {
     Q3_API_BEGIN(h)
     try { q3::pitch_check(ratio_permille); } catch (const std::invalid_argument& ex) { throw q3::Error(std::string("engine_set_pitch: ") + ex.what()); }
-    h->pitch = ratio_permille;
+    h->stages.pitch = ratio_permille;
     return 0;
     Q3_API_END(h)
 }
@@ -653,9 +583,9 @@ int q3tts_engine_set_loudness(q3tts_engine* h, int enabled, int32_t target_dlufs
     Q3_API_BEGIN(h)
     if (enabled) {
         try { q3::loudness_check(target_dlufs, range_cb, start_cb); } catch (const std::invalid_argument& ex) { throw q3::Error(std::string("engine_set_loudness: ") + ex.what()); }
-        h->loud_target = target_dlufs; h->loud_range = range_cb; h->loud_start = start_cb;
+        h->stages.loud_target = target_dlufs; h->stages.loud_range = range_cb; h->stages.loud_start = start_cb;
     }
-    h->loud = enabled != 0;
+    h->stages.loud = enabled != 0;
     return 0;
     Q3_API_END(h)
 }
@@ -907,115 +837,67 @@ int q3tts_slot_release(q3tts_engine* h, int slot) {
     Q3_API_BEGIN(h) h->e->slot_release(slot); return 0; Q3_API_END(h)
 }
 
+// ---- the synthesize entries: each fills a q3::JobArgs by name and runs the offline or the streaming job (q3_job.h) ----
+// what every entry passes under the same names: the voice's language, sampling, and where the results go
+#define Q3_JOB_ARGS(a)                                                                                                             \
+    q3::JobArgs a;                                                                                                                 \
+    a.n_utt = n_utt; a.lang = lang; a.p = p; a.seed = seed; a.ignore_eos = ignore_eos;                                             \
+    a.pcm_out = pcm_out; a.pcm_cap = pcm_cap; a.pcm_len = pcm_len; a.n_frames = n_frames; a.codes_out = codes_out;
+static int run_job(q3tts_engine* h, q3::JobArgs& a, bool stream) {   // a streaming job takes the engine's sink and stages as they are now
+    Q3_API_BEGIN(h)
+    if (stream) { a.stages = h->stages; q3::job_stream(*h->e, a); }
+    else q3::job_offline(*h->e, a);
+    return 0;
+    Q3_API_END(h)
+}
+
 // synthesize_tokens (reference src/tts_onnx.cpp:405-436) over a batch of independent utterances:
 // waves of up to max_batch slots; prompt assembly -> prefill -> fused decode -> vocoder.
 int q3tts_synthesize_batch_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                 const q3tts_sampling* p, uint64_t seed, int ignore_eos,
                                 float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
                                 int64_t* codes_out) {
-    return q3tts_synthesize_clone_batch_host(h, n_utt, ids, offsets, lang, nullptr, p, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out);
+    Q3_JOB_ARGS(a)
+    a.ids = ids; a.offsets = offsets;
+    return run_job(h, a, false);
 }
 
-// Continuous batching: utterances queue for the engine's max_batch slots; a slot that finishes (EOS or max_new_tokens) stashes its codes
-// and is re-armed with the next utterance at the following look, so ragged lengths do not idle the batch; the vocoder runs over the
-// side lanes once the decode queue is empty.  Results do not depend on the schedule: the RNG stream of an utterance is its index,
-// never its slot.
 int q3tts_synthesize_clone_batch_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                       const float* const* speakers, const q3tts_sampling* p, uint64_t seed, int ignore_eos,
                                       float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
                                       int64_t* codes_out) {
-    return q3tts_synthesize_schedule_host(h, n_utt, ids, offsets, lang, speakers, p, nullptr, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out);
-}
-
-// Prompt rows of every utterance of a job, assembled before the first step in one projection pass (Engine::build_prompts: one utterance
-// at a time it is a handful of small synchronous device round trips each).  Utterance u's prompt starts at row prep[u].poff of `prompts`;
-// with an instruction (include/q3tts.h: q3tts_synthesize_instruct_host) its text_project rows come first, all instructions of the job
-// through one further projection pass.
-struct Prep { int S = 0, nt = 0; size_t poff = 0, toff = 0; };
-static void assemble_prompts(Engine& e, int n_utt, const int64_t* ids, const int32_t* offsets, int lang, const float* const* speakers,
-                             const int64_t* instruct_ids, const int32_t* instruct_offsets,
-                             std::vector<Prep>& prep, std::vector<float>& prompts, std::vector<float>& trailing) {
-    const size_t H = (size_t)e.c.hidden;
-    prep.assign((size_t)n_utt, Prep());
-    if (instruct_ids && !instruct_offsets) throw q3::Error("synthesize: instruct_ids without instruct_offsets");
-    auto n_ins = [&](int u) { return instruct_ids ? (int)(instruct_offsets[u + 1] - instruct_offsets[u]) : 0; };
-    size_t prow = 0, trow = 0, n_ins_all = 0;
-    for (int u = 0; u < n_utt; ++u) {
-        if (n_ins(u) < 0) throw q3::Error("synthesize: instruct_offsets must not decrease");
-        prep[(size_t)u].poff = prow; prep[(size_t)u].toff = trow;
-        prow += 16 + (size_t)n_ins(u); n_ins_all += (size_t)n_ins(u);
-        trow += (size_t)std::max(1, offsets[u + 1] - offsets[u] - 3);   // trailing rows: text tokens minus the first, plus tts_eos
-    }
-    trailing.resize(trow * H);
-    std::vector<size_t> toffs((size_t)n_utt);
-    std::vector<int> Ss((size_t)n_utt), nts((size_t)n_utt);
-    for (int u = 0; u < n_utt; ++u) toffs[(size_t)u] = prep[(size_t)u].toff;
-    if (n_ins_all == 0) {
-        prompts.resize(prow * H);
-        e.build_prompts(ids, offsets, n_utt, lang, speakers, prompts.data(), Ss.data(), trailing.data(), toffs.data(), nts.data());
-    } else {
-        std::vector<float> base((size_t)n_utt * 16 * H), ins(n_ins_all * H);
-        e.build_prompts(ids, offsets, n_utt, lang, speakers, base.data(), Ss.data(), trailing.data(), toffs.data(), nts.data());
-        const int64_t i0 = instruct_offsets[0];
-        if (n_ins_all > (size_t)e.max_ctx * (size_t)n_utt) throw q3::Error("synthesize: instructions longer than max_ctx");
-        e.text_project(instruct_ids + i0, (int)n_ins_all, ins.data());
-        prompts.resize(prow * H);
-        for (int u = 0; u < n_utt; ++u) {
-            float* dst = prompts.data() + prep[(size_t)u].poff * H;
-            const size_t ni = (size_t)n_ins(u);
-            if (ni > 0) memcpy(dst, ins.data() + (size_t)(instruct_offsets[u] - i0) * H, ni * H * sizeof(float));
-            memcpy(dst + ni * H, base.data() + (size_t)u * 16 * H, (size_t)Ss[(size_t)u] * H * sizeof(float));
-            Ss[(size_t)u] += (int)ni;
-        }
-    }
-    for (int u = 0; u < n_utt; ++u) { prep[(size_t)u].S = Ss[(size_t)u]; prep[(size_t)u].nt = nts[(size_t)u]; }
-}
-
-static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
-                                  const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
-                                  float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
-                                  int chunk_frames, q3tts_audio_cb cb, void* user, const int64_t* instruct_ids, const int32_t* instruct_offsets,
-                                  const int32_t* prefix_ids = nullptr, q3tts_text_cb tcb = nullptr, void* tuser = nullptr,
-                                  const int64_t* prefix_codes = nullptr, const int32_t* prefix_offsets = nullptr);
-static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
-                                    const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
-                                    float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
-                                    int64_t* codes_out, const int64_t* instruct_ids, const int32_t* instruct_offsets,
-                                    const int64_t* prefix_codes = nullptr, const int32_t* prefix_offsets = nullptr, const int32_t* prefix_ids = nullptr);
-
-// The job's shared prompt prefixes (q3tts_synthesize_prefixed_host): validated up front, held against q3tts_prefix_release while the job runs
-struct PrefixHold {
-    Engine& e; std::vector<int> ids;
-    PrefixHold(Engine& en, const int32_t* prefix_ids, int n_utt) : e(en) {
-        for (int u = 0; prefix_ids && u < n_utt; ++u) if (prefix_ids[u] != -1) (void)e.prefix_get(prefix_ids[u]);   // throws on an unknown id, nothing held yet
-        for (int u = 0; prefix_ids && u < n_utt; ++u) if (prefix_ids[u] != -1) { e.prefix_pin(prefix_ids[u], 1); ids.push_back(prefix_ids[u]); }
-    }
-    ~PrefixHold() { for (int id : ids) { try { e.prefix_pin(id, -1); } catch (...) { } } }
-};
-
-int q3tts_synthesize_prefixed_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
-                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
-                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
-                                   int chunk_frames, q3tts_audio_cb cb, void* user, const int32_t* prefix_ids) {
-    if (!cb) return synthesize_schedule_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
-                                             nullptr, nullptr, nullptr, nullptr, prefix_ids);
-    return synthesize_stream_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
-                                  chunk_frames, cb, user, nullptr, nullptr, prefix_ids);
+    Q3_JOB_ARGS(a)
+    a.ids = ids; a.offsets = offsets; a.speakers = speakers;
+    return run_job(h, a, false);
 }
 
 int q3tts_synthesize_schedule_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                    const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                    float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
                                    int64_t* codes_out) {
-    return synthesize_schedule_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out, nullptr, nullptr);
+    Q3_JOB_ARGS(a)
+    a.ids = ids; a.offsets = offsets; a.speakers = speakers; a.max_new_per_utt = max_new_per_utt;
+    return run_job(h, a, false);
+}
+
+int q3tts_synthesize_prefixed_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
+                                   const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
+                                   float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
+                                   int chunk_frames, q3tts_audio_cb cb, void* user, const int32_t* prefix_ids) {
+    Q3_JOB_ARGS(a)
+    a.ids = ids; a.offsets = offsets; a.speakers = speakers; a.max_new_per_utt = max_new_per_utt;
+    a.prefix_ids = prefix_ids; a.chunk_frames = chunk_frames; a.cb = cb; a.user = user;
+    return run_job(h, a, cb != nullptr);
 }
 
 int q3tts_synthesize_continue_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                    const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                    float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                    const int64_t* prefix_codes, const int32_t* prefix_offsets) {
-    return synthesize_schedule_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
-                                    nullptr, nullptr, prefix_codes, prefix_offsets);
+    Q3_JOB_ARGS(a)
+    a.ids = ids; a.offsets = offsets; a.speakers = speakers; a.max_new_per_utt = max_new_per_utt;
+    a.prefix_codes = prefix_codes; a.prefix_offsets = prefix_offsets;
+    return run_job(h, a, false);
 }
 
 int q3tts_synthesize_instruct_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
@@ -1023,214 +905,20 @@ int q3tts_synthesize_instruct_host(q3tts_engine* h, int n_utt, const int64_t* id
                                    float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                    int chunk_frames, q3tts_audio_cb cb, void* user,
                                    const int64_t* instruct_ids, const int32_t* instruct_offsets) {
-    if (!cb) return synthesize_schedule_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
-                                             instruct_ids, instruct_offsets);
-    return synthesize_stream_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
-                                  chunk_frames, cb, user, instruct_ids, instruct_offsets);
+    Q3_JOB_ARGS(a)
+    a.ids = ids; a.offsets = offsets; a.speakers = speakers; a.max_new_per_utt = max_new_per_utt;
+    a.instruct_ids = instruct_ids; a.instruct_offsets = instruct_offsets; a.chunk_frames = chunk_frames; a.cb = cb; a.user = user;
+    return run_job(h, a, cb != nullptr);
 }
 
-static int synthesize_schedule_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
-                                    const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
-                                    float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames,
-                                    int64_t* codes_out, const int64_t* instruct_ids, const int32_t* instruct_offsets,
-                                    const int64_t* prefix_codes, const int32_t* prefix_offsets, const int32_t* prefix_ids) {
-    Q3_API_BEGIN(h)
-    Engine& e = *h->e;
-    const int H = e.c.hidden, G = e.c.n_groups, B = e.B;
-    if (n_utt <= 0) return 0;
-    if (!ids || !offsets || !p) throw q3::Error("synthesize: null argument");
-    if (pcm_cap < 0) throw q3::Error("synthesize: negative pcm_cap");
-    (void)Engine::checked_penalty(*p);   // refused before any slot is touched
-    PrefixHold hold(e, prefix_ids, n_utt);
-    // rows of the shared prompt prefix in front of utterance u's prompt (0 without one): part of its context, not of prep[u].S
-    auto pl = [&](int u) { return prefix_ids && prefix_ids[u] != -1 ? e.prefix_get(prefix_ids[u]).P : 0; };
-    // teacher-forced frames per utterance (q3tts_synthesize_continue_host): pf(u) of them behind utterance u's prompt, P the longest
-    if (prefix_codes && !prefix_offsets) throw q3::Error("synthesize: prefix_codes without prefix_offsets");
-    auto pf = [&](int u) { return prefix_codes ? (int)(prefix_offsets[u + 1] - prefix_offsets[u]) : 0; };
-    auto pcodes = [&](int u) { return prefix_codes + (size_t)prefix_offsets[u] * (size_t)G; };
-    int P = 0;
-    for (int u = 0; u < n_utt; ++u) {
-        if (pf(u) < 0 || (prefix_codes && prefix_offsets[u] < 0)) throw q3::Error("synthesize: prefix_offsets must start at >= 0 and not decrease");
-        if (pf(u) > 0 && pf(u) + p->max_new_tokens > e.max_frames_cap) throw q3::Error("synthesize: utterance " + std::to_string(u) + ": prefix frames + max_new_tokens exceeds the slot's frame capacity");
-        try { if (pf(u) > 0) e.check_frame_codes(pcodes(u), pf(u), true); }
-        catch (const q3::Error& ex) { throw q3::Error("synthesize: utterance " + std::to_string(u) + ": " + ex.msg); }
-        P = std::max(P, pf(u));
-    }
-    for (int b = 0; b < B; ++b) e.slot_release(b);
-    const int row_frames = std::max(1, std::min(P + p->max_new_tokens, e.max_frames_cap));
-    e.codec_async_prepare(row_frames, n_utt);
-    std::vector<int32_t> got_frames((size_t)n_utt, 0);
-    std::vector<Prep> prep;
-    std::vector<float> prompts, trailing;
-    assemble_prompts(e, n_utt, ids, offsets, lang, speakers, instruct_ids, instruct_offsets, prep, prompts, trailing);
-    // KV pages.  With EOS suppressed every length is known: an utterance is admitted when the pool holds prompt + cap and never waits again.
-    // Otherwise a slot owns what its context has reached plus the coming look (on-demand growth), so utterances that end early never hold
-    // the pages of their cap; when the pool runs dry the YOUNGEST live utterance is preempted — its pages go back, it returns to the head
-    // of the queue and is generated again from its prompt later (same RNG stream, same codes) — so the oldest always finishes.
-    std::vector<Engine::SlotInit> init, rag;
-    const bool ragged = (e.flags & Q3TTS_FLAG_RAGGED_PREFILL) != 0;
-    std::vector<int> slot_utt((size_t)B, -1), done_frames((size_t)B, 0), fresh, retired;
-    std::vector<q3::SlotState> st;
-    std::deque<int> pending;
-    auto cap_of = [&](int u) { return max_new_per_utt ? std::min(std::max(1, (int)max_new_per_utt[u]), p->max_new_tokens) : p->max_new_tokens; };
-    for (int u = 0; u < n_utt; ++u) {
-        if ((pf(u) > 0 || pl(u) > 0) && pl(u) + prep[(size_t)u].S + pf(u) + p->max_new_tokens > e.max_ctx)
-            throw q3::Error("synthesize: utterance " + std::to_string(u) + ": prefix + prompt + prefix frames + max_new_tokens exceeds max_ctx");
-        if (e.kv_pages_for(pl(u) + prep[(size_t)u].S + pf(u) + cap_of(u)) > e.kv_total_pages())
-            throw q3::Error("synthesize: one utterance (prompt + max_new_tokens) needs more KV pages than the pool holds");
-        pending.push_back(u);
-    }
-    const bool reserve_all = ignore_eos != 0;
-    const int first_look = 8;
-    int live = 0;
-    // A preempted utterance is not re-admitted on the pages it just gave back: it waits until a live utterance has retired or the pool
-    // holds what it owned when it was preempted plus one page of head-room — otherwise a pool just above one utterance's cap re-admits
-    // and preempts the same utterance look after look, paying a prefill and discarding its frames each time.
-    std::vector<int> hold_pages((size_t)n_utt, 0);
-    std::vector<int64_t> hold_mark((size_t)n_utt, 0);
-    int64_t n_retired = 0;
-    e.sched_admitted = e.sched_preempted = 0; e.sched_peak_live = 0;
-    const char* const quantum_env = getenv("Q3TTS_SCHED_QUANTUM");
-    const int quantum = quantum_env ? std::max(1, atoi(quantum_env)) : 4;
-    try {
-        while (!pending.empty() || live > 0) {
-            fresh.clear();
-            {   // admission in queue order (q3_kvpool.h: sched_admit_count)
-                std::vector<int> free_slots, need;
-                for (int b = 0; b < B; ++b) if (slot_utt[(size_t)b] < 0) free_slots.push_back(b);
-                for (size_t i = 0; i < pending.size() && i < free_slots.size(); ++i) {
-                    const int u = pending[i], all = pl(u) + prep[(size_t)u].S + pf(u) + cap_of(u);
-                    int pages = e.kv_pages_for(reserve_all ? all : std::min(all, pl(u) + prep[(size_t)u].S + pf(u) + first_look));
-                    if (hold_pages[(size_t)u] > 0 && n_retired == hold_mark[(size_t)u] && live > 0) pages = std::max(pages, std::min(hold_pages[(size_t)u], e.kv_total_pages()));
-                    need.push_back(pages);
-                }
-                const int n_adm = q3::sched_admit_count(e.kv, need, (int)free_slots.size(), live, reserve_all);
-                for (int i = 0; i < n_adm; ++i) { slot_utt[(size_t)free_slots[(size_t)i]] = pending.front(); pending.pop_front(); fresh.push_back(free_slots[(size_t)i]); }
-            }
-            if (!fresh.empty()) {
-                init.clear();
-                for (size_t i = 0; i < fresh.size(); ++i) {
-                    const int b = fresh[i], u = slot_utt[(size_t)b];
-                    const Prep& pr = prep[(size_t)u];
-                    Engine::SlotInit q;
-                    q.slot = b; q.prompt = prompts.data() + pr.poff * H; q.S = pr.S; q.trailing = trailing.data() + pr.toff * H; q.n_trailing = pr.nt;
-                    q.stream_id = (uint32_t)u;
-                    q.max_frames = max_new_per_utt ? std::max(1, (int)max_new_per_utt[u]) : 0;
-                    q.kv_tokens = reserve_all ? 0 : pl(u) + pr.S + pf(u) + first_look;
-                    if (prefix_ids) q.prefix_id = prefix_ids[u];
-                    if (ragged && (pf(u) > 0 || q.S > 16)) {   // Q3TTS_FLAG_RAGGED_PREFILL: what would be begun on its own joins one ragged begin
-                        if (pf(u) > 0) { q.prefix = pcodes(u); q.n_prefix = pf(u); done_frames[(size_t)b] = pf(u); }
-                        rag.push_back(q);
-                    } else if (pf(u) > 0) {   // forced begin, on its own (a re-admission after a preemption too); the slot starts pf(u) frames in
-                        q.prefix = pcodes(u); q.n_prefix = pf(u);
-                        e.slots_begin(&q, 1, *p, seed, ignore_eos);
-                        done_frames[(size_t)b] = pf(u);
-                    } else init.push_back(q);
-                }
-                if (!rag.empty()) { e.slots_begin_ragged(rag.data(), (int)rag.size(), *p, seed, ignore_eos); rag.clear(); }
-                if (!init.empty()) {   // equal-length prompts share one prefill pass (behind their prefixes: at per-member bases)
-                    if (prefix_ids) e.slots_begin_prefixed(init.data(), (int)init.size(), *p, seed, ignore_eos);
-                    else e.slots_begin(init.data(), (int)init.size(), *p, seed, ignore_eos);
-                }
-                live += (int)fresh.size();
-                e.sched_admitted += (int64_t)fresh.size();
-                e.sched_peak_live = std::max(e.sched_peak_live, live);
-            }
-            // steps until the next look: never past the earliest slot that can reach max_new_tokens, short when few utterances are live
-            int rem = p->max_new_tokens;
-            for (int b = 0; b < B; ++b) {
-                const int u = slot_utt[(size_t)b];
-                if (u >= 0) rem = std::min(rem, pf(u) + cap_of(u) - done_frames[(size_t)b]);
-            }
-            // (with EOS suppressed nothing can finish earlier than that, so the look-ahead only bounds how long the host is away)
-            // While utterances wait in the queue a look is at least `quantum` steps away: a finished slot idles a few (masked, nearly free)
-            // steps, and the slots that finish within the quantum are re-armed together, sharing one prefill pass.
-            // (Q3TTS_SCHED_QUANTUM is read above, once per job: a process can run jobs at more than one quantum)
-            const int look = std::min(rem, ignore_eos ? 64 : (live <= 16 ? 4 : 8));
-            const int steps = std::max(!pending.empty() && live > 16 ? quantum : 1, look);
-            if (!reserve_all) {
-                // every live slot gets pages for the positions these steps write; oldest first, so that when the pool runs dry it is the
-                // youngest that goes back to the queue (q3_kvpool.h: sched_grow)
-                std::vector<int> order, want, changed;
-                for (int b = 0; b < B; ++b) if (slot_utt[(size_t)b] >= 0) order.push_back(b);
-                std::sort(order.begin(), order.end(), [&](int x, int y) {
-                    return done_frames[(size_t)x] != done_frames[(size_t)y] ? done_frames[(size_t)x] > done_frames[(size_t)y] : slot_utt[(size_t)x] < slot_utt[(size_t)y]; });
-                for (int b : order) {
-                    const int u = slot_utt[(size_t)b];
-                    want.push_back(pl(u) + std::min(prep[(size_t)u].S + pf(u) + cap_of(u), prep[(size_t)u].S + done_frames[(size_t)b] + steps));
-                }
-                const std::vector<int> victims = q3::sched_grow(e.kv, order, want, &changed);
-                for (int vb : victims) {          // youngest first: pushed to the front one by one, the oldest of them ends up first in the queue
-                    const int vu = slot_utt[(size_t)vb];
-                    hold_pages[(size_t)vu] = e.kv_pages_for(pl(vu) + prep[(size_t)vu].S + done_frames[(size_t)vb]) + 1;
-                    hold_mark[(size_t)vu] = n_retired;
-                    e.slot_release(vb);           // deactivates the slot (its pages are already back in the pool)
-                    pending.push_front(vu);
-                    slot_utt[(size_t)vb] = -1; done_frames[(size_t)vb] = 0;
-                    --live; ++e.sched_preempted;
-                }
-                for (int b : changed) e.kv_upload_row(b);
-            }
-            e.decode_steps(steps);
-            e.slots_state(B, st);
-            retired.clear();
-            for (int b = 0; b < B; ++b) {
-                const int u = slot_utt[(size_t)b];
-                if (u < 0) continue;
-                const q3::SlotState& s = st[(size_t)b];
-                done_frames[(size_t)b] = s.n_frames;
-                if (!(s.finished || s.n_frames >= s.max_frames)) continue;
-                got_frames[(size_t)u] = s.n_frames;
-                if (n_frames) n_frames[u] = s.n_frames;
-                e.codec_stash(b, s.n_frames, u, row_frames);
-                retired.push_back(b);
-            }
-            for (int b : retired) {
-                const int u = slot_utt[(size_t)b];
-                if (codes_out) e.slot_codes(b, codes_out + (size_t)u * (size_t)(P + p->max_new_tokens) * G, P + p->max_new_tokens);
-                e.slot_release(b);
-                slot_utt[(size_t)b] = -1; done_frames[(size_t)b] = 0;
-                --live; ++n_retired;
-            }
-        }
-    } catch (...) {
-        try { e.codec_async_drain(); } catch (...) { }
-        for (int b = 0; b < B; ++b) { try { e.slot_release(b); } catch (...) { } }
-        throw;
-    }
-    if (P == 0) { vocoder_job(e, n_utt, got_frames, row_frames, pcm_out, pcm_cap, pcm_len); return 0; }
-    // With prefixes every utterance is decoded whole into a buffer of the job's own, and the caller receives the samples its new frames
-    // own: [L(prefix), L(all)) of the whole decode (causal decoder: exact).  An utterance without a prefix receives all of its decode.
-    std::vector<std::vector<float>> whole((size_t)n_utt);
-    std::vector<float*> wp((size_t)n_utt, nullptr);
-    std::vector<int64_t> wl((size_t)n_utt, 0);
-    int64_t wcap = 1;
-    for (int u = 0; u < n_utt; ++u) {
-        const int64_t L = got_frames[(size_t)u] > 0 ? q3tts_codec_decode_len(&e.c, got_frames[(size_t)u]) : 0;
-        if (pcm_out && pcm_out[u]) { whole[(size_t)u].resize((size_t)std::max<int64_t>(L, 1)); wp[(size_t)u] = whole[(size_t)u].data(); }
-        wcap = std::max(wcap, L);
-    }
-    for (int u = 0; u < n_utt; ++u) if (wp[(size_t)u]) { whole[(size_t)u].resize((size_t)wcap); wp[(size_t)u] = whole[(size_t)u].data(); }   // one capacity for the job
-    vocoder_job(e, n_utt, got_frames, row_frames, pcm_out ? wp.data() : nullptr, wcap, wl.data());
-    for (int u = 0; u < n_utt; ++u) {
-        const int64_t first = pf(u) > 0 ? q3tts_codec_decode_len(&e.c, pf(u)) : 0, own = std::max<int64_t>(0, wl[(size_t)u] - first);
-        if (pcm_len) pcm_len[u] = own;
-        if (wp[(size_t)u] && own > 0) memcpy(pcm_out[u], wp[(size_t)u] + first, (size_t)std::min(own, pcm_cap) * sizeof(float));
-    }
-    return 0;
-    Q3_API_END(h)
-}
-
-// ---- voice-clone front end (host audio code + the speaker encoder on the GPU) ----
-// q3tts_synthesize_schedule_host with the audio delivered chunk by chunk: decode chunk_frames steps, vocode every live slot's new frames
-// in batched passes (Engine::slots_codec_decode_new), call back, retire / re-arm.  Admission reserves prompt + cap for every utterance
-// (no growth, no preemption: delivered audio cannot be taken back), so the loop needs none of the schedule entry's page policy.
+// q3tts_synthesize_schedule_host with the audio delivered chunk by chunk (q3::job_stream)
 int q3tts_synthesize_stream_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
                                  const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
                                  float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                  int chunk_frames, q3tts_audio_cb cb, void* user) {
-    return synthesize_stream_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
-                                  chunk_frames, cb, user, nullptr, nullptr);
+    Q3_JOB_ARGS(a)
+    a.ids = ids; a.offsets = offsets; a.speakers = speakers; a.max_new_per_utt = max_new_per_utt; a.chunk_frames = chunk_frames; a.cb = cb; a.user = user;
+    return run_job(h, a, true);
 }
 // The same loop behind teacher-forced frames (include/q3tts.h; tts_onnx.cpp:824-842, :759-776): forced begins, primed vocoder streams
 int q3tts_synthesize_continue_stream_host(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
@@ -1238,8 +926,10 @@ int q3tts_synthesize_continue_stream_host(q3tts_engine* h, int n_utt, const int6
                                           float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                           const int64_t* prefix_codes, const int32_t* prefix_offsets,
                                           int chunk_frames, q3tts_audio_cb cb, void* user) {
-    return synthesize_stream_impl(h, n_utt, ids, offsets, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
-                                  chunk_frames, cb, user, nullptr, nullptr, nullptr, nullptr, nullptr, prefix_codes, prefix_offsets);
+    Q3_JOB_ARGS(a)
+    a.ids = ids; a.offsets = offsets; a.speakers = speakers; a.max_new_per_utt = max_new_per_utt;
+    a.prefix_codes = prefix_codes; a.prefix_offsets = prefix_offsets; a.chunk_frames = chunk_frames; a.cb = cb; a.user = user;
+    return run_job(h, a, true);
 }
 // The same loop with the texts pulled through a callback while the audio is generated (include/q3tts.h; tts_onnx.cpp:531-536, :833-842)
 int q3tts_synthesize_live_host(q3tts_engine* h, int n_utt, q3tts_text_cb text_cb, void* text_user, int lang,
@@ -1247,300 +937,9 @@ int q3tts_synthesize_live_host(q3tts_engine* h, int n_utt, q3tts_text_cb text_cb
                                float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
                                int chunk_frames, q3tts_audio_cb cb, void* user) {
     if (!text_cb) { if (h) h->err = "synthesize_live: null text callback"; return -1; }
-    return synthesize_stream_impl(h, n_utt, nullptr, nullptr, lang, speakers, p, max_new_per_utt, seed, ignore_eos, pcm_out, pcm_cap, pcm_len, n_frames, codes_out,
-                                  chunk_frames, cb, user, nullptr, nullptr, nullptr, text_cb, text_user);
-}
-static int synthesize_stream_impl(q3tts_engine* h, int n_utt, const int64_t* ids, const int32_t* offsets, int lang,
-                                  const float* const* speakers, const q3tts_sampling* p, const int32_t* max_new_per_utt, uint64_t seed, int ignore_eos,
-                                  float* const* pcm_out, int64_t pcm_cap, int64_t* pcm_len, int32_t* n_frames, int64_t* codes_out,
-                                  int chunk_frames, q3tts_audio_cb cb, void* user, const int64_t* instruct_ids, const int32_t* instruct_offsets,
-                                  const int32_t* prefix_ids, q3tts_text_cb tcb, void* tuser,
-                                  const int64_t* prefix_codes, const int32_t* prefix_offsets) {
-    Q3_API_BEGIN(h)
-    Engine& e = *h->e;
-    const int H = e.c.hidden, G = e.c.n_groups, B = e.B;
-    if (n_utt <= 0) return 0;
-    const bool live_text = tcb != nullptr;   // q3tts_synthesize_live_host: the texts arrive through tcb, prompts are built at admission
-    if ((!live_text && (!ids || !offsets)) || !p) throw q3::Error("synthesize: null argument");
-    const q3tts_sink sink = h->sink;
-    const bool sunk = sink.sample_rate > 0;   // deliver through the engine's sink (q3tts_engine_set_sink)
-    if (!cb && !sunk) throw q3::Error("synthesize_stream: null callback");
-    if (sunk && pcm_out) throw q3::Error("synthesize_stream: pcm_out must be NULL while a sink is set (q3tts_engine_set_sink): audio leaves through the sink's callback");
-    if (chunk_frames < 1) throw q3::Error("synthesize_stream: chunk_frames must be positive");
-    if (pcm_cap < 0) throw q3::Error("synthesize: negative pcm_cap");
-    (void)Engine::checked_penalty(*p);
-    PrefixHold hold(e, prefix_ids, n_utt);
-    auto pl = [&](int u) { return prefix_ids && prefix_ids[u] != -1 ? e.prefix_get(prefix_ids[u]).P : 0; };   // rows of utterance u's shared prefix
-    // teacher-forced frames per utterance (q3tts_synthesize_continue_stream_host), checked as the schedule entry checks them: pf(u) of
-    // them behind utterance u's prompt, P the longest
-    if (prefix_codes && !prefix_offsets) throw q3::Error("synthesize: prefix_codes without prefix_offsets");
-    if (prefix_codes && live_text) throw q3::Error("synthesize_live: live text behind prefix codes is not implemented");
-    auto pf = [&](int u) { return prefix_codes ? (int)(prefix_offsets[u + 1] - prefix_offsets[u]) : 0; };
-    auto pcodes = [&](int u) { return prefix_codes + (size_t)prefix_offsets[u] * (size_t)G; };
-    int P = 0;
-    for (int u = 0; u < n_utt; ++u) {
-        if (pf(u) < 0 || (prefix_codes && prefix_offsets[u] < 0)) throw q3::Error("synthesize: prefix_offsets must start at >= 0 and not decrease");
-        if (pf(u) > 0 && pf(u) + p->max_new_tokens > e.max_frames_cap) throw q3::Error("synthesize: utterance " + std::to_string(u) + ": prefix frames + max_new_tokens exceeds the slot's frame capacity");
-        try { if (pf(u) > 0) e.check_frame_codes(pcodes(u), pf(u), true); }
-        catch (const q3::Error& ex) { throw q3::Error("synthesize: utterance " + std::to_string(u) + ": " + ex.msg); }
-        P = std::max(P, pf(u));
-    }
-    for (int b = 0; b < B; ++b) e.slot_release(b);
-    std::vector<Prep> prep;
-    std::vector<float> prompts, trailing;
-    if (!live_text) assemble_prompts(e, n_utt, ids, offsets, lang, speakers, instruct_ids, instruct_offsets, prep, prompts, trailing);
-    else { prep.assign((size_t)n_utt, Prep()); for (int u = 0; u < n_utt; ++u) prep[(size_t)u].S = 16; }   // the most a prompt takes, for the page checks; set at admission
-    // live text: what each utterance has received (got), whether its source is done, and how many ids are in its slot (prompt or appended).
-    // The last two ids received are the chat template's tail once the text closes (every entry drops them): held back while it is open.
-    std::vector<std::vector<int64_t>> got((size_t)(live_text ? n_utt : 0));
-    std::vector<uint8_t> t_closed((size_t)n_utt, 0), t_sealed((size_t)n_utt, 0);
-    std::vector<int> t_fed((size_t)n_utt, 0);
-    std::vector<uint8_t> t_gave((size_t)n_utt, 0);   // the source returned ids (or closed) at this turn's poll
-    std::vector<int32_t> flim((size_t)h->e->B, 0), held((size_t)h->e->B, 0), target((size_t)h->e->B, 0), deliv((size_t)h->e->B, 0);
-    auto usable = [&](int u) { const int n = (int)got[(size_t)u].size(); return t_closed[(size_t)u] ? std::max(4, n - 2) : std::max(0, n - 2); };
-    auto admissible = [&](int u) { return !live_text || usable(u) >= 5 || (t_closed[(size_t)u] && got[(size_t)u].size() >= 4); };
-    std::vector<int64_t> poll_ids(256), app_ids;
-    std::vector<int32_t> app_slots, app_off;
-    std::vector<uint8_t> app_close;
-    std::vector<int32_t> tl_host((size_t)B, 0), nf_host((size_t)B, 0);   // live text: each live slot's text rows and frames as of the last look
-    auto cap_of = [&](int u) { return max_new_per_utt ? std::min(std::max(1, (int)max_new_per_utt[u]), p->max_new_tokens) : p->max_new_tokens; };
-    std::deque<int> pending;
-    for (int u = 0; u < n_utt; ++u) {
-        if (pf(u) > 0 && pl(u) + prep[(size_t)u].S + pf(u) + p->max_new_tokens > e.max_ctx)
-            throw q3::Error("synthesize: utterance " + std::to_string(u) + ": prefix + prompt + prefix frames + max_new_tokens exceeds max_ctx");
-        if (pl(u) > 0 && pl(u) + prep[(size_t)u].S + p->max_new_tokens > e.max_ctx)
-            throw q3::Error("synthesize: utterance " + std::to_string(u) + ": prefix + prompt + max_new_tokens exceeds max_ctx");
-        if (e.kv_pages_for(pl(u) + prep[(size_t)u].S + pf(u) + cap_of(u)) > e.kv_total_pages())
-            throw q3::Error("synthesize: one utterance (prompt + max_new_tokens) needs more KV pages than the pool holds");
-        pending.push_back(u);
-        if (pcm_len) pcm_len[u] = 0;
-        if (n_frames) n_frames[u] = 0;
-    }
-    const int cf = std::min(chunk_frames, e.max_frames_cap);   // samples of cf frames at the start of an utterance / further in
-    const int64_t chunk_cap = std::max(q3tts_codec_decode_len(&e.c, cf), q3tts_codec_decode_len(&e.c, cf + 1) - q3tts_codec_decode_len(&e.c, 1));
-    // with a sink a chunk's buffer holds the sink's samples: the chunk's share plus the flushed tail, by the host rule's closed form
-    // with a speed (q3tts_engine_set_speed) the chunk first passes its stretcher: at most the chunk plus what the stretcher held back
-    // (N + D + Hs input samples), 1000 / S times as long, plus the cut last block
-    const int speed = h->speed;
-    const bool sped = speed != 1000;
-    // with a level (q3tts_engine_set_level) the limiter hands on what it held back as well: at most W - 1 samples more
-    const bool levelled = h->gain_cb != 0 || h->ceiling != 0;
-    // with a pitch (q3tts_engine_set_pitch) the stage in front hands on what it held back: at most kPitchLA samples more
-    const bool pitched = h->pitch != 1000;
-    const int64_t pitch_cap = chunk_cap + (pitched ? q3::kPitchLA : 0);
-    const int64_t stage_cap = (sped ? ((pitch_cap + q3::kSpeedN + q3::kSpeedD + q3::kSpeedHs) * 1000 + speed - 1) / speed + q3::kSpeedHs : pitch_cap)
-                              + (h->ceiling != 0 ? q3::kLevelW - 1 : 0)
-                              + (h->loud ? q3::kLoudBlock - 1 : 0);   // a loudness stage (q3tts_engine_set_loudness) holds back less than one sub-block
-    const q3::SinkPlan* splan = sunk ? &e.sink.plan_for(sink.sample_rate).plan : nullptr;
-    const int64_t sink_cap = sunk ? ((stage_cap + splan->half) * splan->L + splan->M - 1) / splan->M + 2 : 0;
-    const int64_t chunk_floats = sunk ? (sink_cap * (int64_t)q3::pcm_format_bytes(sink.format) + 3) / 4 : stage_cap;   // per slot, 4-byte aligned
-    const int64_t deliver_cap = sunk ? sink_cap : stage_cap;
-    std::vector<float> chunk_pcm((size_t)B * chunk_floats);
-    std::vector<float*> pcm_ptr((size_t)B);
-    std::vector<int32_t> final_frames((size_t)B, -1);
-    struct SlotStagesScope {   // the slots' implicit streams take the stages for the duration of this call only
-        Engine& e;
-        SlotStagesScope(Engine& en, const Engine::SlotStages& s) : e(en) { e.slot_stages = s; }
-        ~SlotStagesScope() { e.slot_stages = Engine::SlotStages(); }
-    } stages_scope(e, Engine::SlotStages{ sunk && !(sink.sample_rate == 24000 && sink.format == Q3TTS_PCM_F32) ? sink.sample_rate : 0, sink.format,
-                                          sped ? speed : 0, levelled ? h->gain_cb : 0, levelled ? h->ceiling : 0, pitched ? h->pitch : 0,
-                                          h->loud ? 1 : 0, h->loud_target, h->loud_range, h->loud_start });
-    std::vector<int32_t> slots, fb((size_t)B), fe((size_t)B);
-    std::vector<int64_t> plen((size_t)B), written((size_t)n_utt, 0);
-    std::vector<Engine::SlotInit> init;
-    std::vector<int> slot_utt((size_t)B, -1), fresh;
-    std::vector<q3::SlotState> st;
-    int live = 0;
-    e.sched_admitted = e.sched_preempted = 0; e.sched_peak_live = 0;
-    // Live text: audio leaves in the pushes q3tts_synthesize_stream_host makes — frames up to the next multiple of chunk_frames, one
-    // push per round — so a text that arrives in time gives the very samples of the whole text.  Frames past the last multiple
-    // wait (held), except those of a finished slot (its tail) and of a starved slot whose source had nothing this turn (a
-    // silent source must not hold audio back).  Without live text there is one round and every slot is at its frame count.
-    auto plan_delivery = [&]() {   // live text: how far each live slot's audio may go this turn
-        for (int b = 0; b < B; ++b) {
-            const int u = slot_utt[(size_t)b];
-            if (u < 0) continue;
-            const q3::SlotState& s = st[(size_t)b];
-            const bool fin = s.finished || s.n_frames >= s.max_frames;
-            const bool flush = fin || (s.text_open && s.n_frames >= s.trailing_len && !t_gave[(size_t)u]);
-            target[(size_t)b] = flush ? s.n_frames : s.n_frames / cf * cf;
-            nf_host[(size_t)b] = s.n_frames;
-        }
-    };
-    // one push per live slot with frames to deliver (live text: up to its limit of this round) and the callbacks behind it; a finished
-    // slot is retired with its last frames.  false: no slot had anything left.
-    auto deliver_round = [&](bool first) -> bool {
-        slots.clear();
-        for (int b = 0; b < B; ++b) {
-            if (slot_utt[(size_t)b] < 0) continue;
-            const q3::SlotState& s = st[(size_t)b];
-            const bool fin = s.finished || s.n_frames >= s.max_frames;
-            if (live_text) {
-                if (!(deliv[(size_t)b] < target[(size_t)b] || (fin && first))) continue;   // nothing of this slot leaves in this round
-                flim[slots.size()] = std::min(target[(size_t)b], (deliv[(size_t)b] / cf + 1) * cf);
-            }
-            pcm_ptr[slots.size()] = chunk_pcm.data() + slots.size() * (size_t)chunk_floats;
-            final_frames[slots.size()] = fin ? s.n_frames : -1;
-            slots.push_back(b);
-        }
-        if (slots.empty()) return false;
-        e.slots_codec_decode_new((int)slots.size(), slots.data(), pcm_ptr.data(), deliver_cap, plen.data(), fb.data(), fe.data(), live_text ? flim.data() : nullptr,
-                                 final_frames.data());
-        for (size_t i = 0; i < slots.size(); ++i) {
-            const int b = slots[i], u = slot_utt[(size_t)b];
-            const q3::SlotState& s = st[(size_t)b];
-            // live text: finished AND its last frames are in this round; without live text fe[i] is always the frame count
-            const bool fin = (s.finished || s.n_frames >= s.max_frames) && (!live_text || fe[i] >= s.n_frames);
-            deliv[(size_t)b] = fe[i];
-            held[(size_t)b] = fin ? 0 : s.n_frames - fe[i];
-            if (plen[i] > deliver_cap) throw q3::Error("synthesize_stream: a chunk produced more samples than its buffer holds");
-            if (pcm_out && pcm_out[u] && plen[i] > 0 && written[(size_t)u] < pcm_cap)
-                memcpy(pcm_out[u] + written[(size_t)u], pcm_ptr[i], (size_t)std::min(plen[i], pcm_cap - written[(size_t)u]) * sizeof(float));
-            written[(size_t)u] += plen[i];
-            if (fin) {   // retired before the callback: whatever it does, the slot is free and the outputs are complete
-                if (n_frames) n_frames[u] = s.n_frames;
-                if (pcm_len) pcm_len[u] = written[(size_t)u];
-                if (codes_out) e.slot_codes(b, codes_out + (size_t)u * (size_t)(P + p->max_new_tokens) * G, P + p->max_new_tokens);
-                e.slot_release(b);
-                slot_utt[(size_t)b] = -1;
-                deliv[(size_t)b] = 0;
-                --live;
-            }
-            if (plen[i] > 0 || fin)
-                if ((sunk ? sink.cb(sink.user, u, fb[i], fe[i], pcm_ptr[i], plen[i], fin ? 1 : 0) : cb(user, u, fb[i], fe[i], pcm_ptr[i], plen[i], fin ? 1 : 0)) != 0)
-                    throw q3::Error("cancelled by callback");
-        }
-        return true;
-    };
-    try {
-        while (!pending.empty() || live > 0) {
-            fresh.clear();
-            bool skip_decode = false;
-            if (live_text) {   // poll every utterance whose text is open, live or queued
-                for (int u = 0; u < n_utt; ++u) {
-                    if (t_closed[(size_t)u]) continue;
-                    bool known = false;
-                    for (int b = 0; b < B && !known; ++b) known = slot_utt[(size_t)b] == u;
-                    for (size_t i = 0; i < pending.size() && !known; ++i) known = pending[i] == u;
-                    if (!known) continue;
-                    int32_t n_new = 0, cl = 0;
-                    t_gave[(size_t)u] = 0;
-                    if (tcb(tuser, u, poll_ids.data(), (int)poll_ids.size(), &n_new, &cl) != 0) throw q3::Error("cancelled by callback");
-                    if (n_new < 0 || n_new > (int)poll_ids.size()) throw q3::Error("synthesize_live: the text callback returned a bad id count");
-                    got[(size_t)u].insert(got[(size_t)u].end(), poll_ids.begin(), poll_ids.begin() + n_new);
-                    t_gave[(size_t)u] = n_new > 0 || cl;
-                    if (cl) {
-                        t_closed[(size_t)u] = 1;
-                        if (got[(size_t)u].size() < 4) throw q3::Error("token sequence too short: need at least 4 ids (the reference indexes input_ids[3])");
-                    }
-                }
-            }
-            size_t n_ready = 0;   // queued utterances, from the front, that hold enough text to begin
-            while (n_ready < pending.size() && admissible(pending[n_ready])) ++n_ready;
-            {   // admission in queue order, every utterance with the pages of its whole length
-                std::vector<int> free_slots, need;
-                for (int b = 0; b < B; ++b) if (slot_utt[(size_t)b] < 0) free_slots.push_back(b);
-                for (size_t i = 0; i < n_ready && i < free_slots.size(); ++i) need.push_back(e.kv_pages_for(pl(pending[i]) + prep[(size_t)pending[i]].S + pf(pending[i]) + cap_of(pending[i])));
-                const int n_adm = q3::sched_admit_count(e.kv, need, (int)free_slots.size(), live, true);
-                for (int i = 0; i < n_adm; ++i) { slot_utt[(size_t)free_slots[(size_t)i]] = pending.front(); pending.pop_front(); fresh.push_back(free_slots[(size_t)i]); }
-            }
-            if (live_text && !fresh.empty()) {   // the prompts of this look's admissions, from the ids they hold now (build_prompt_open)
-                prompts.assign(fresh.size() * 16 * (size_t)H, 0.f);
-                size_t trow = 0;
-                for (size_t i = 0; i < fresh.size(); ++i) { prep[(size_t)slot_utt[(size_t)fresh[i]]].toff = trow; trow += (size_t)std::max(1, usable(slot_utt[(size_t)fresh[i]]) - 4); }
-                trailing.assign(trow * (size_t)H, 0.f);
-                for (size_t i = 0; i < fresh.size(); ++i) {
-                    const int u = slot_utt[(size_t)fresh[i]], nu = usable(u);
-                    Prep& pr = prep[(size_t)u];
-                    pr.poff = i * 16;
-                    e.build_prompt_open(got[(size_t)u].data(), nu, lang, speakers ? speakers[u] : nullptr, prompts.data() + pr.poff * H, &pr.S,
-                                        trailing.data() + pr.toff * H, e.max_trailing, &pr.nt);
-                    t_fed[(size_t)u] = nu;
-                }
-            }
-            if (!fresh.empty()) {
-                init.assign(fresh.size(), Engine::SlotInit());
-                for (size_t i = 0; i < fresh.size(); ++i) {
-                    const int b = fresh[i], u = slot_utt[(size_t)b];
-                    const Prep& pr = prep[(size_t)u];
-                    Engine::SlotInit& q = init[i];
-                    q.slot = b; q.prompt = prompts.data() + pr.poff * H; q.S = pr.S; q.trailing = trailing.data() + pr.toff * H; q.n_trailing = pr.nt;
-                    q.stream_id = (uint32_t)u;
-                    q.max_frames = max_new_per_utt ? std::max(1, (int)max_new_per_utt[u]) : 0;
-                    q.kv_tokens = 0;   // prompt + cap, reserved now
-                    if (prefix_ids) q.prefix_id = prefix_ids[u];
-                    if (pf(u) > 0) { q.prefix = pcodes(u); q.n_prefix = pf(u); }
-                }
-                if (e.flags & Q3TTS_FLAG_RAGGED_PREFILL) {   // the long prompts and the forced begins of the look in one ragged begin, the rest as before
-                    std::vector<Engine::SlotInit> rag;
-                    size_t keep = 0;
-                    for (size_t i = 0; i < init.size(); ++i) { if (init[i].S > 16 || init[i].n_prefix > 0) rag.push_back(init[i]); else init[keep++] = init[i]; }
-                    init.resize(keep);
-                    if (!rag.empty()) e.slots_begin_ragged(rag.data(), (int)rag.size(), *p, seed, ignore_eos);
-                } else if (P > 0) {                          // forced begins, each on its own: the schedule entry's (q3tts_synthesize_continue_host)
-                    size_t keep = 0;
-                    for (size_t i = 0; i < init.size(); ++i) {
-                        if (init[i].n_prefix > 0) e.slots_begin(&init[i], 1, *p, seed, ignore_eos);
-                        else init[keep++] = init[i];
-                    }
-                    init.resize(keep);
-                }
-                if (init.empty()) { }
-                else if (prefix_ids) e.slots_begin_prefixed(init.data(), (int)init.size(), *p, seed, ignore_eos);
-                else e.slots_begin(init.data(), (int)init.size(), *p, seed, ignore_eos);
-                if (P > 0) {   // the vocoder streams of the look's prefixed slots take their prefixes as history, in one call: audio starts at the first new frame
-                    std::vector<int32_t> ps_slots, ps_n;
-                    for (int b : fresh) if (pf(slot_utt[(size_t)b]) > 0) { ps_slots.push_back(b); ps_n.push_back(pf(slot_utt[(size_t)b])); }
-                    if (!ps_slots.empty()) e.slots_codec_prime((int)ps_slots.size(), ps_slots.data(), ps_n.data());
-                }
-                live += (int)fresh.size();
-                e.sched_admitted += (int64_t)fresh.size();
-                e.sched_peak_live = std::max(e.sched_peak_live, live);
-            }
-            if (live_text) {
-                for (int b : fresh) { e.slot_text_open(b); tl_host[(size_t)b] = prep[(size_t)slot_utt[(size_t)b]].nt; nf_host[(size_t)b] = 0; }
-                // the new ids of every live slot, and the close of those whose source is done, in one call
-                app_slots.clear(); app_ids.clear(); app_off.assign(1, 0); app_close.clear();
-                for (int b = 0; b < B; ++b) {
-                    const int u = slot_utt[(size_t)b];
-                    if (u < 0 || t_sealed[(size_t)u]) continue;
-                    const int nu = usable(u);
-                    if (nu == t_fed[(size_t)u] && !t_closed[(size_t)u]) continue;
-                    app_slots.push_back(b);
-                    app_ids.insert(app_ids.end(), got[(size_t)u].begin() + t_fed[(size_t)u], got[(size_t)u].begin() + nu);
-                    app_off.push_back((int32_t)app_ids.size());
-                    app_close.push_back(t_closed[(size_t)u]);
-                    tl_host[(size_t)b] += nu - t_fed[(size_t)u] + (t_closed[(size_t)u] ? 1 : 0);
-                    t_fed[(size_t)u] = nu;
-                    if (t_closed[(size_t)u]) t_sealed[(size_t)u] = 1;
-                }
-                if (!app_slots.empty()) e.slots_text_append((int)app_slots.size(), app_slots.data(), nullptr, app_ids.data(), app_off.data(), app_close.data());
-                if (live == 0) {
-                    if (n_ready > 0) throw q3::Error("synthesize_stream: no utterance could be admitted");
-                    continue;   // every queued utterance waits for text: poll again
-                }
-                bool all_starved = true;
-                for (int b = 0; b < B && all_starved; ++b) {
-                    const int u = slot_utt[(size_t)b];
-                    if (u >= 0 && (t_sealed[(size_t)u] || nf_host[(size_t)b] < tl_host[(size_t)b])) all_starved = false;
-                }
-                bool any_held = false;   // frames generated but not delivered yet (held for the chunk cadence, below)
-                for (int b = 0; b < B; ++b) if (slot_utt[(size_t)b] >= 0 && held[(size_t)b] > 0) any_held = true;
-                if (all_starved && !any_held) continue;   // nothing would move: poll again at once
-                skip_decode = all_starved;                // no step would move a slot, but a silent source releases the held frames
-            }
-            if (live == 0) throw q3::Error("synthesize_stream: no utterance could be admitted");
-            if (!skip_decode) e.decode_steps(chunk_frames);
-            e.slots_state(B, st);
-            if (live_text) plan_delivery();
-            for (bool first = true; deliver_round(first) && live_text; first = false) { }
-        }
-    } catch (...) {
-        for (int b = 0; b < B; ++b) { try { e.slot_release(b); } catch (...) { } }
-        throw;
-    }
-    return 0;
-    Q3_API_END(h)
+    Q3_JOB_ARGS(a)
+    a.text_cb = text_cb; a.text_user = text_user; a.speakers = speakers; a.max_new_per_utt = max_new_per_utt; a.chunk_frames = chunk_frames; a.cb = cb; a.user = user;
+    return run_job(h, a, true);
 }
 
 int q3tts_read_wav_host(const char* path, float* out, int64_t cap, int64_t* n_samples, int32_t* sample_rate) {

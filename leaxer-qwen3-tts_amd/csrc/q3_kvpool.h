@@ -81,6 +81,17 @@ inline int sched_admit_count(const KvPool& pool, const std::vector<int>& need, i
     return n;
 }
 
+// Steps until the next look.  `rem` = frames the live slot nearest its cap may still produce (max_new_tokens when none is live), `live` =
+// utterances running, `queued` = utterances wait for a slot.  Never past the earliest slot that can reach max_new_tokens, short when few
+// utterances are live (with EOS suppressed nothing can finish earlier than that, so the look-ahead only bounds how long the host is away).
+// While utterances wait in the queue a look is at least `quantum` steps away: a finished slot idles a few (masked, nearly free)
+// steps, and the slots that finish within the quantum are re-armed together, sharing one prefill pass — so a look may run past `rem`.
+// (the scheduler reads Q3TTS_SCHED_QUANTUM once per job: a process can run jobs at more than one quantum)
+inline int sched_look_steps(int rem, int live, bool queued, bool ignore_eos, int quantum) {
+    const int look = std::min(rem, ignore_eos ? 64 : (live <= 16 ? 4 : 8));
+    return std::max(queued && live > 16 ? quantum : 1, look);
+}
+
 // Growth before a look of `steps` decode steps: `want_tokens[k]` for the k-th running utterance in `order` (oldest first).  Grows each
 // slot in that order; when the pool runs dry the youngest still running is preempted (its pages come back) until the growth fits —
 // in the end the grower itself.  Returns the slots preempted, youngest first; `changed` collects the slots whose table row must be

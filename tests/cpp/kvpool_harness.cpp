@@ -1,6 +1,6 @@
 // Drives csrc/q3_kvpool.h (the talker's KV page pool and the scheduler's page policy) without a GPU: reads commands from stdin, prints the
 // pool's state after each.  tests/test_cpu_kvpool.py compiles this with g++ and checks invariants and exact expectations.
-//   init SLOTS PPS SHIFT POOL_PAGES | reserve SLOT TOKENS EXACT | admit RESERVE_ALL LIVE FREE_SLOTS N need... | grow N (slot want)... | dump
+//   init SLOTS PPS SHIFT POOL_PAGES | reserve SLOT TOKENS EXACT | admit RESERVE_ALL LIVE FREE_SLOTS N need... | grow N (slot want)... | look REM LIVE QUEUED IGNORE_EOS QUANTUM | dump
 #include <iostream>
 #include <sstream>
 #include "q3_kvpool.h"
@@ -49,6 +49,10 @@ int main() {
             for (int v : changed) std::cout << " " << v;
             std::cout << "\n";
             dump(pool, "grow");
+        }
+        else if (cmd == "look") {
+            int rem, live, queued, ie, quantum; in >> rem >> live >> queued >> ie >> quantum;
+            std::cout << "look " << q3::sched_look_steps(rem, live, queued != 0, ie != 0, quantum) << "\n";
         }
         else if (cmd == "dump") dump(pool, "dump");
     }

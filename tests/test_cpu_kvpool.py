@@ -95,6 +95,22 @@ def test_admission_rule(harness):
     assert adm == [2, 1, 3, 1, 1]
 
 
+def test_look_length_rule(harness):
+    rows = [   # rem, live, queued, ignore_eos, quantum -> steps
+        (100, 4, 0, 0, 4, 4),
+        (100, 16, 1, 0, 4, 4),        # the quantum holds only above 16 live utterances
+        (100, 17, 0, 0, 4, 8),
+        (100, 17, 1, 0, 12, 12),
+        (2, 17, 1, 0, 4, 4),          # while utterances wait a look may run past the nearest cap: those steps are masked
+        (2, 17, 0, 0, 4, 2),
+        (100, 40, 1, 1, 4, 64),
+        (30, 2, 0, 1, 4, 30),
+        (1, 1, 0, 0, 4, 1),
+    ]
+    out = harness("\n".join("look %d %d %d %d %d" % r[:5] for r in rows))
+    assert [int(ln.split()[1]) for ln in out] == [r[5] for r in rows]
+
+
 def test_growth_preempts_the_youngest_and_never_the_oldest(harness):
     out = harness("\n".join([
         "init 4 5 6 6",
