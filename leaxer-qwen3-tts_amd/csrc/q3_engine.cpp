@@ -663,7 +663,7 @@ static int seam_gu_ksplit(int K) {
 
 bool Engine::seam_applies(const DecStack& W, int M, float* x, int ldx, bool has_slot_map) const {
     const int AO = W.nq * W.d, NTH = W.H / 64;
-    const bool mfma = M >= mfma_min_rows && W.H % 128 == 0 && AO % 128 == 0 && W.ffn % 128 == 0 && W.H <= 4096;
+    const bool mfma = M >= mfma_min_rows && mfma_dims_ok(W);
     if (!mfma || !seam_step || !seam_on || has_slot_map || M > 128 || NTH > 64 || NTH % 4 != 0 || W.L < 1) return false;
     const int ks_q = seam_gu_ksplit(W.H);
     GemmArgs t1, t2, t3;
@@ -679,7 +679,7 @@ bool Engine::run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new,
                         const float* final_gamma, float final_eps, float* final_xn, int final_ld_xn, const int* slot_map) {
     const int M = nb * n_new, QKV = (W.nq + 2 * W.nkv) * W.d, AO = W.nq * W.d;
     // M >= mfma_min_rows: bf16-MFMA skinny GEMM over (hi, lo) activation planes; below it the single-pass GEMV family
-    const bool mfma = M >= mfma_min_rows && W.H % 128 == 0 && AO % 128 == 0 && W.ffn % 128 == 0 && W.H <= 4096;
+    const bool mfma = M >= mfma_min_rows && mfma_dims_ok(W);
     const int ks_q = mfma ? std::min(4, pick_ksplit(W.H)) : 1;
     // Split-K seam (decode step only): the three finish launches of a layer pass fold into their GEMMs — o_proj and down reduce their
     // slabs in-launch and leave gamma * x planes plus per-tile sums of squares (the consumer applies 1 / rms: deferred RMSNorm), gate/up
@@ -968,14 +968,7 @@ void Engine::prefill_rows_in_xp(int slot, int S) {
 }
 
 float* Engine::long_rows(int S) {
-    if ((size_t)S > long_x_rows) {
-        sync();
-        if (long_x_d) (void)hipFree(long_x_d);
-        long_x_d = nullptr; long_x_rows = 0;
-        const size_t rows = std::min((size_t)max_ctx, std::max((size_t)S, (size_t)256));
-        Q3_HIP_CHECK(hipMalloc((void**)&long_x_d, rows * c.hidden * sizeof(float)));
-        long_x_rows = rows;
-    }
+    if ((size_t)S > long_x_rows) regrow(long_x_d, long_x_rows, std::min((size_t)max_ctx, std::max((size_t)S, (size_t)256)), c.hidden);
     return long_x_d;
 }
 
@@ -1008,7 +1001,7 @@ void Engine::prefill_rows_long(int slot, float* x, int S, float* logits_host, in
     if (S < 1 || base0 < 0 || base0 + S > max_ctx) throw Error("prefill length must be 1..max_ctx rows");
     if (seam_step) throw Error("prefill_rows_long: not inside a decode step");
     long_ws_ensure();
-    struct Scope { Engine& e; explicit Scope(Engine& en) : e(en) { e.long_ws_swap(); e.chunk_attn = true; } ~Scope() { e.chunk_attn = false; e.long_ws_swap(); } } scope(*this);
+    LongWsScope scope(*this);
     float* const hnw = lws.hn; float* const lgw = lws.logits;   // not swapped: the chunk's normalised rows and logits
     const float* last_lg = nullptr;
     int n_last = 0;
@@ -1020,7 +1013,6 @@ void Engine::prefill_rows_long(int slot, float* x, int S, float* logits_host, in
         one[0].slot = slot; one[0].base = base0; one[0].rows = S;
         seg_tables_build(one, sch);
     }
-    struct SegScope { Engine& e; ~SegScope() { e.seg_attn = nullptr; } } seg_scope{*this};
     SegAttn sa;
     for (int base = 0, ci = 0; base < S; base += prefill_chunk, ++ci) {
         const int n = std::min(prefill_chunk, S - base);
@@ -1136,25 +1128,21 @@ void Engine::talker_prefill_dev(const float* embeds, int nb, int S, const int32_
     if (!embeds) throw Error("talker_prefill_dev: null input");
     const int H = c.hidden, V = c.vocab;
     for (int b = 0; b < nb; ++b) if (lens && (lens[b] < 1 || lens[b] > S)) throw Error("talker_prefill_dev: lens[b] must be 1..S");
-    auto len_of = [&](int b) { return lens ? (int)lens[b] : S; };
-    const bool mfma_ok = H % 128 == 0 && (c.n_heads * c.head_dim) % 128 == 0 && c.ffn % 128 == 0 && H <= 4096;   // run_layers' MFMA condition
+    std::vector<BeginMember> m((size_t)nb);   // row b is slot b: slots_begin's groups (q3_begin_plan.h) over consecutive slots
+    for (int b = 0; b < nb; ++b) { m[(size_t)b].slot = b; m[(size_t)b].S = lens ? (int)lens[b] : S; }
     std::vector<int32_t> pos_h;
-    int b0 = 0;
-    while (b0 < nb) {
-        const int L = len_of(b0), cap = mfma_ok && L <= 16 ? std::max(1, std::min(std::min(rows_max, 128) / L, 128)) : 1;
-        int g = 1;
-        while (b0 + g < nb && g < cap && len_of(b0 + g) == L) ++g;
+    for (const BeginGroup& gr : begin_groups(BEGIN_PLAIN, m.data(), nb, begin_limits())) {
+        const int b0 = gr.i0, g = gr.g, L = m[(size_t)b0].S;
         for (int k = 0; k < g; ++k) kv_reserve(b0 + k, L, false);
-        if (L > 16) {   // a long prompt: one slot at a time through the chunked path
+        if (L > 16) {   // a long prompt (a group of its own): through the chunked path
             float* x = long_rows(L);
             Q3_HIP_CHECK(hipMemcpyAsync(x, embeds + (size_t)b0 * S * H, (size_t)L * H * sizeof(float), hipMemcpyDeviceToDevice, stream));
             prefill_rows_long(b0, x, L, nullptr);
             if (logits_last) launch_copy_rows(long_last_logits, V, logits_last + (size_t)b0 * V, V, 1, V, stream);
             if (last_hidden) launch_copy_rows(long_last_hidden, H, last_hidden + (size_t)b0 * H, H, 1, H, stream);
-            b0 += 1;
             continue;
         }
-        if (g == 1 || g * L < mfma_min_rows) {
+        if (!gr.batched) {
             for (int k = 0; k < g; ++k) {
                 const int slot = b0 + k;
                 Q3_HIP_CHECK(hipMemcpyAsync(xp, embeds + (size_t)slot * S * H, (size_t)L * H * sizeof(float), hipMemcpyDeviceToDevice, stream));
@@ -1176,7 +1164,6 @@ void Engine::talker_prefill_dev(const float* embeds, int nb, int S, const int32_
             for (int k = 0; k < g; ++k) { st_h[b0 + k].prompt_len = L; st_h[b0 + k].n_frames = 0; }
             sync();   // pos_h is reused by the next group
         }
-        b0 += g;
     }
     // every entry point returns after its launches and copies have completed (include/q3tts.h): the single-slot path above queues
     // asynchronous copies from host memory (a stack-local position in prefill_rows_in_xp, the page-table mirror row in kv_upload_row)
@@ -1616,593 +1603,6 @@ int Engine::nb_in_use() const {
     int nb = 0;
     for (int b = 0; b < B; ++b) if (st_h[b].active) nb = b + 1;
     return nb;
-}
-
-void Engine::slot_begin(int slot, const float* prompt, int S, const float* trailing, int n_trailing,
-                        const q3tts_sampling& p, uint64_t seed, uint32_t stream_id, int ignore_eos) {
-    SlotInit in;
-    in.slot = slot; in.prompt = prompt; in.S = S; in.trailing = trailing; in.n_trailing = n_trailing; in.stream_id = stream_id;
-    slots_begin(&in, 1, p, seed, ignore_eos);
-}
-
-// Prefill of several slots at once: slots with equal prompt length share one pass through the talker stack (rows = slots x S,
-// groups of at most 128 rows on the MFMA path), only the last row of each prompt goes through the codec head.  One
-// synchronisation for the whole set instead of two per slot.
-void Engine::slots_begin(const SlotInit* in, int n, const q3tts_sampling& p, uint64_t seed, int ignore_eos) {
-    if (!finalized) throw Error("weights not finalized");
-    const int H = c.hidden, V = c.vocab;
-    const float rep_penalty = checked_penalty(p);   // before anything is reserved or armed
-    for (int i = 0; i < n; ++i) {
-        if (in[i].slot < 0 || in[i].slot >= B) throw Error("slot out of range");
-        if (in[i].n_trailing < 0 || in[i].n_trailing > max_trailing) throw Error("too many trailing text rows");
-        if (in[i].S < 1 || in[i].S > max_ctx) throw Error("prefill length must be 1..max_ctx rows");
-        if (p.max_new_tokens < 1 || in[i].S + p.max_new_tokens > max_ctx) throw Error("prompt + max_new_tokens exceeds max_ctx");
-        if (in[i].n_prefix < 0 || (in[i].n_prefix > 0 && !in[i].prefix)) throw Error("prefix codes: n_prefix must be >= 0 (and the codes given)");
-        if (in[i].n_prefix > 0) {
-            if (in[i].S + in[i].n_prefix + p.max_new_tokens > max_ctx) throw Error("prompt + prefix frames + max_new_tokens exceeds max_ctx");
-            if (in[i].n_prefix + p.max_new_tokens > max_frames_cap) throw Error("prefix frames + max_new_tokens exceeds the slot's frame capacity");
-            if (n != 1) throw Error("slots_begin: a slot with prefix codes is begun on its own");
-            check_frame_codes(in[i].prefix, in[i].n_prefix, true);
-        }
-    }
-    if (n == 1 && in[0].n_prefix > 0) { slot_begin_forced(in[0], p, seed, ignore_eos, rep_penalty); return; }
-    {   // KV pages for the prompt and every frame the slot may generate, all or nothing: nothing is armed if the pool cannot hold the set
-        int need = 0;
-        auto tokens_of = [&](const SlotInit& q) {
-            const int all = q.S + (q.max_frames > 0 ? std::min(q.max_frames, p.max_new_tokens) : p.max_new_tokens);
-            return q.kv_tokens > 0 ? std::min(all, std::max(q.kv_tokens, q.S)) : all;   // a caller that grows the share itself (the scheduler)
-        };
-        auto want_of = [&](const SlotInit& q) { return kv_pages_for(tokens_of(q)); };
-        for (int i = 0; i < n; ++i) need += want_of(in[i]) - kv_slot_pages(in[i].slot);
-        if (need > kv_free_pages()) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "KV page pool exhausted: %d slots need %d more pages, %d of %d free", n, need, kv_free_pages(), kv_total_pages());
-            throw Error(msg);
-        }
-        for (int pass = 0; pass < 2; ++pass)   // slots that give pages back first
-            for (int i = 0; i < n; ++i)
-                if ((want_of(in[i]) <= kv_slot_pages(in[i].slot)) == (pass == 0)) kv_reserve(in[i].slot, tokens_of(in[i]), true);
-    }
-    int i0 = 0;
-    std::vector<int32_t> pos_h, map_h;
-    while (i0 < n) {
-        // a group: entries with the same S, at most rows_max / S of them (and <= 128 rows); consecutive slot ids write their results in
-        // place, scattered ones (the scheduler re-arming whatever finished) go through a slot map and a scatter of the head's rows
-        const bool mfma_ok = H % 128 == 0 && (c.n_heads * c.head_dim) % 128 == 0 && c.ffn % 128 == 0 && H <= 4096;   // run_layers' MFMA condition
-        // (a prompt of more than 16 rows is prefilled on its own, in chunks: talker_prefill's long path)
-        const int S = in[i0].S, cap = mfma_ok && S <= 16 ? std::max(1, std::min(std::min(rows_max, 128) / S, 128)) : 1;
-        int g = 1;
-        bool consecutive = true;
-        while (i0 + g < n && g < cap && in[i0 + g].S == S) { consecutive = consecutive && in[i0 + g].slot == in[i0].slot + g; ++g; }
-        for (int k = 1; k < g; ++k)   // a slot may appear once per group (its cache rows are written by one row group only)
-            for (int j = 0; j < k; ++j) if (in[i0 + k].slot == in[i0 + j].slot) throw Error("slots_begin: slot listed twice");
-        if (g == 1 || g * S < mfma_min_rows) {
-            for (int k = 0; k < g; ++k) talker_prefill(in[i0 + k].slot, in[i0 + k].prompt, S, nullptr, nullptr);
-        } else {
-            const int slot0 = in[i0].slot;
-            for (int k = 0; k < g; ++k)
-                Q3_HIP_CHECK(hipMemcpyAsync(xp + (size_t)k * S * H, in[i0 + k].prompt, (size_t)S * H * sizeof(float), hipMemcpyHostToDevice, stream));
-            pos_h.assign((size_t)g, S);
-            if (consecutive) {
-                const bool pr = run_layers(talker, xp, H, g, S, slot0, nullptr, 0, talker_norm, c.rms_eps, hn, H);
-                if (!pr) throw Error("batched prefill expects the MFMA path");   // M = g*S >= mfma_min_rows by construction
-                // codec head on the last row of every prompt straight into the fused path's logits; normalised last rows -> predictor input
-                head_proj(codec_head, xp, H, talker_norm, c.rms_eps, nullptr, 0, logits_t + (size_t)slot0 * V, V, g, V, H, true, true, S - 1, S);
-                launch_copy_rows(hn + (size_t)(S - 1) * H, S * H, x_cp + (size_t)slot0 * 2 * H, 2 * H, g, H, stream);
-                Q3_HIP_CHECK(hipMemcpyAsync(talker_pos_d + slot0, pos_h.data(), (size_t)g * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-            } else {
-                map_h.resize((size_t)g);
-                for (int k = 0; k < g; ++k) map_h[(size_t)k] = in[i0 + k].slot;
-                Q3_HIP_CHECK(hipMemcpyAsync(slot_map_d, map_h.data(), (size_t)g * sizeof(int), hipMemcpyHostToDevice, stream));
-                const bool pr = run_layers(talker, xp, H, g, S, 0, nullptr, 0, talker_norm, c.rms_eps, hn, H, slot_map_d);
-                if (!pr) throw Error("batched prefill expects the MFMA path");
-                head_proj(codec_head, xp, H, talker_norm, c.rms_eps, nullptr, 0, logits_g, V, g, V, H, true, true, S - 1, S);
-                for (int k = 0; k < g; ++k) {
-                    const int sl = in[i0 + k].slot;
-                    launch_copy_rows(logits_g + (size_t)k * V, V, logits_t + (size_t)sl * V, V, 1, V, stream);
-                    launch_copy_rows(hn + (size_t)(k * S + S - 1) * H, H, x_cp + (size_t)sl * 2 * H, 2 * H, 1, H, stream);
-                    Q3_HIP_CHECK(hipMemcpyAsync(talker_pos_d + sl, pos_h.data(), sizeof(int32_t), hipMemcpyHostToDevice, stream));
-                }
-            }
-            sync();   // pos_h / map_h are reused by the next group
-        }
-        i0 += g;
-    }
-    for (int i = 0; i < n; ++i) {
-        const SlotInit& q = in[i];
-        if (q.n_trailing > 0)
-            Q3_HIP_CHECK(hipMemcpyAsync(trailing_d + (size_t)q.slot * max_trailing * H, q.trailing, (size_t)q.n_trailing * H * sizeof(float), hipMemcpyHostToDevice, stream));
-        slot_codec_stream_reset(q.slot);   // a new utterance: its streaming vocoder state starts over
-        SlotState& s = st_h[q.slot];
-        s.n_frames = 0; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.prefix_len = 0; s.trailing_len = q.n_trailing; s.text_open = 0; stepped_h[q.slot] = 0;
-        s.max_frames = q.max_frames > 0 ? std::min(q.max_frames, p.max_new_tokens) : p.max_new_tokens;
-        s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
-        // a new utterance (a re-admission after a preemption included) starts with an empty code0 history: ordered before its first step
-        Q3_HIP_CHECK(hipMemsetAsync(seen_d + (size_t)q.slot * seen_ld, 0, (size_t)seen_ld * sizeof(uint32_t), stream));
-        Q3_HIP_CHECK(hipMemcpyAsync(st_d + q.slot, &s, sizeof(SlotState), hipMemcpyHostToDevice, stream));
-    }
-    sync();
-}
-
-void Engine::check_frame_codes(const int64_t* codes, int n, bool strict) const {
-    const int G = c.n_groups;
-    for (int f = 0; f < n; ++f)
-        for (int g = 0; g < G; ++g) {
-            const int64_t v = codes[(size_t)f * G + g];
-            const bool ok = g == 0 ? v >= 0 && v < c.vocab && !(strict && ((v >= c.suppress_begin && v < c.suppress_end) || v == c.codec_eos)) : v >= 0 && v < c.sub_vocab;
-            if (!ok) {
-                char msg[200];
-                snprintf(msg, sizeof msg, "frame codes: frame %d group %d holds %lld, outside %s", f, g, (long long)v,
-                         g != 0 ? "[0, sub_vocab)" : (strict ? "[0, vocab) without the suppressed ids (EOS among them)" : "[0, vocab)"));
-                throw Error(msg);
-            }
-        }
-}
-
-void Engine::frame_rows_launch(const int64_t* codes, int n, int frame0, const float* trailing_dev, int trailing_len, float* out_dev,
-                               int32_t* codes_out, uint32_t* seen) {
-    const int G = c.n_groups;
-    if ((size_t)n * G > frame_codes_cap) {
-        sync();
-        if (frame_codes_d) (void)hipFree(frame_codes_d);
-        frame_codes_d = nullptr; frame_codes_cap = 0;
-        const size_t cap = std::max((size_t)n, (size_t)256) * G;
-        Q3_HIP_CHECK(hipMalloc((void**)&frame_codes_d, cap * sizeof(int64_t)));
-        frame_codes_cap = cap;
-    }
-    Q3_HIP_CHECK(hipMemcpyAsync(frame_codes_d, codes, (size_t)n * G * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-    FrameRowsArgs a;
-    a.codes = frame_codes_d; a.n = n; a.n_groups = G; a.H = c.hidden;
-    a.embed0 = codec_embed_w; a.V0 = c.vocab; a.SV = c.sub_vocab;
-    for (int g = 0; g < G - 1; ++g) a.embed_sub[g] = cp_embed_w[(size_t)g];
-    a.trailing = trailing_dev; a.frame0 = frame0; a.trailing_len = trailing_len; a.tts_pad = tts_pad_d;
-    a.out = out_dev; a.ldo = c.hidden; a.codes_out = codes_out; a.seen = seen;
-    launch_frame_rows(a, stream);
-}
-
-// q3tts_frame_rows_host: the kernel on its own, for callers and tests
-void Engine::frame_rows(const int64_t* codes, int n, int frame0, const float* trailing, int n_trailing, float* out) {
-    if (!finalized) throw Error("weights not finalized");
-    if (n < 0 || frame0 < 0 || n_trailing < 0) throw Error("frame_rows: negative argument");
-    if (n == 0) return;
-    if (!codes || !out || (n_trailing > 0 && !trailing)) throw Error("frame_rows: null argument");
-    if (n > max_ctx) throw Error("frame_rows: more frames than max_ctx in one call");
-    check_frame_codes(codes, n, false);
-    const int H = c.hidden;
-    const int n_text = std::max(0, std::min(n_trailing - frame0, n));   // frames frame0 .. frame0 + n_text - 1 have a text row, the rest tts_pad
-    if ((size_t)n_text > frame_text_rows) {
-        sync();
-        if (frame_text_d) (void)hipFree(frame_text_d);
-        frame_text_d = nullptr; frame_text_rows = 0;
-        const size_t rows = std::max((size_t)n_text, (size_t)64);
-        Q3_HIP_CHECK(hipMalloc((void**)&frame_text_d, rows * H * sizeof(float)));
-        frame_text_rows = rows;
-    }
-    float* x = long_rows(n);
-    if (n_text > 0) Q3_HIP_CHECK(hipMemcpyAsync(frame_text_d, trailing + (size_t)frame0 * H, (size_t)n_text * H * sizeof(float), hipMemcpyHostToDevice, stream));
-    frame_rows_launch(codes, n, frame0, frame_text_d, frame0 + n_text, x, nullptr, nullptr);
-    Q3_HIP_CHECK(hipMemcpyAsync(out, x, (size_t)n * H * sizeof(float), hipMemcpyDeviceToHost, stream));
-    sync();
-}
-
-// Forced begin (include/q3tts.h: q3tts_slot_begin_codes): the slot as q3tts_slot_begin would have it after generating exactly q.prefix
-// as its first frames.  The forced frames' rows are made on the device behind the prompt rows and the S + F0 rows take the prefill the
-// same rows would take as a prompt (one pass up to 16 rows, causal chunks beyond); the launch that makes the rows also records the
-// frames (codes, code0 bitmap).  Validated by slots_begin.
-void Engine::slot_begin_forced(const SlotInit& q, const q3tts_sampling& p, uint64_t seed, int ignore_eos, float rep_penalty, int base) {
-    const int H = c.hidden, G = c.n_groups, S = q.S, F0 = q.n_prefix, R = S + F0, slot = q.slot;
-    const int new_cap = q.max_frames > 0 ? std::min(q.max_frames, p.max_new_tokens) : p.max_new_tokens;
-    {   // KV pages for prompt, prefix and every new frame (or what the caller grows from): nothing is armed if the pool cannot hold them
-        const int all = base + R + new_cap, tokens = q.kv_tokens > 0 ? std::min(all, std::max(q.kv_tokens, base + R)) : all;
-        const int need = kv_pages_for(tokens) - kv_slot_pages(slot);
-        if (need > kv_free_pages()) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "KV page pool exhausted: 1 slots need %d more pages, %d of %d free", need, kv_free_pages(), kv_total_pages());
-            throw Error(msg);
-        }
-        kv_reserve(slot, tokens, true);
-    }
-    float* x = R <= 16 ? xp : long_rows(R);
-    float* tr = trailing_d + (size_t)slot * max_trailing * H;
-    uint32_t* seen = seen_d + (size_t)slot * seen_ld;
-    Q3_HIP_CHECK(hipMemcpyAsync(x, q.prompt, (size_t)S * H * sizeof(float), hipMemcpyHostToDevice, stream));
-    if (q.n_trailing > 0) Q3_HIP_CHECK(hipMemcpyAsync(tr, q.trailing, (size_t)q.n_trailing * H * sizeof(float), hipMemcpyHostToDevice, stream));
-    // the code0 history starts empty and then holds the prefix: cleared before the launch that sets its bits, and not again behind it
-    Q3_HIP_CHECK(hipMemsetAsync(seen, 0, (size_t)seen_ld * sizeof(uint32_t), stream));
-    frame_rows_launch(q.prefix, F0, 0, tr, q.n_trailing, x + (size_t)S * H, codes_d + (size_t)slot * max_frames_cap * G, seen);
-    if (R <= 16 && base == 0) prefill_rows_in_xp(slot, R);
-    else prefill_rows_long(slot, x, R, nullptr, base);   // behind a shared prefix: the chunk path at base, whatever R
-    slot_codec_stream_reset(slot);
-    SlotState& s = st_h[slot];   // after the prefill, which writes prompt_len = R and n_frames = 0
-    s.n_frames = F0; s.finished = 0; s.active = 1; s.prompt_len = S; s.prefix_len = base; s.trailing_len = q.n_trailing; s.text_open = 0; stepped_h[slot] = 0;
-    s.max_frames = F0 + new_cap;
-    s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
-    Q3_HIP_CHECK(hipMemcpyAsync(st_d + slot, &s, sizeof(SlotState), hipMemcpyHostToDevice, stream));
-    sync();
-}
-
-// ------------------------------------------------------------------------------------------------
-// shared prompt prefix (q3_engine.h)
-// ------------------------------------------------------------------------------------------------
-const Engine::Prefix& Engine::prefix_get(int id) const {
-    auto it = prefixes.find(id);
-    if (it == prefixes.end()) throw Error("unknown prefix id " + std::to_string(id) + " (never created, or released)");
-    return it->second;
-}
-
-void Engine::prefix_pin(int id, int delta) {
-    auto it = prefixes.find(id);
-    if (it == prefixes.end()) throw Error("unknown prefix id " + std::to_string(id) + " (never created, or released)");
-    it->second.users += delta;
-}
-
-void Engine::kv_prefix_copy(const Prefix& pf, const int* slots_dev, int n_dst, int slot0, bool scatter) {
-    KvPrefixCopyArgs a;
-    a.kcache = talker.kc; a.vcache = talker.vc; a.kstore = pf.k; a.vstore = pf.v;
-    a.page_table = talker.page_table; a.pages_per_slot = talker.pages_per_slot;
-    a.slots = slots_dev; a.n_dst = n_dst; a.slot0 = slot0; a.scatter = scatter ? 1 : 0;
-    a.n_lk = talker.L * talker.nkv; a.P = pf.P; a.row16 = talker.d * (talker.kv_bf16 ? 2 : 4) / 16;
-    if (talker.page_shift != 6 || (talker.d * (talker.kv_bf16 ? 2 : 4)) % 16 != 0) throw Error("kv prefix copy: 64-token pages and token rows of whole 16-byte units");
-    launch_kv_prefix_copy(a, stream);
-}
-
-int Engine::prefix_create(const float* rows, int P) {
-    if (!finalized) throw Error("weights not finalized");
-    if (!rows) throw Error("prefix_create: null rows");
-    if (P < 1 || P >= max_ctx) throw Error("prefix_create: 1 <= rows < max_ctx");
-    if ((int)prefixes.size() >= kMaxPrefixes) throw Error("prefix_create: " + std::to_string(kMaxPrefixes) + " prefixes are live already (release one)");
-    int slot = -1;   // borrowed: not armed and holding no pages (a session-shaped prefill's cache rows are left alone)
-    for (int b = B - 1; b >= 0 && slot < 0; --b) if (!st_h[b].active && kv_slot_pages(b) == 0) slot = b;
-    if (slot < 0) throw Error("prefix_create: no free slot to prefill the prefix in (every slot is armed or holds KV pages)");
-    if (kv_pages_for(P) > kv_free_pages()) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "KV page pool exhausted: a prefix of %d rows needs %d pages, %d of %d free", P, kv_pages_for(P), kv_free_pages(), kv_total_pages());
-        throw Error(msg);
-    }
-    const int H = c.hidden;
-    Prefix pf;
-    pf.P = P;
-    const size_t half = (size_t)P * talker.L * talker.nkv * talker.d * (talker.kv_bf16 ? 2 : 4);
-    pf.bytes = (int64_t)(2 * half);
-    float* x = P <= 16 ? xp : long_rows(P);   // before the store exists: long_rows may throw
-    Q3_HIP_CHECK(hipMalloc(&pf.k, half));
-    if (hipMalloc(&pf.v, half) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(pf.k); throw Error("prefix_create: out of device memory for the store"); }
-    const SlotState keep = st_h[slot];
-    try {
-        kv_reserve(slot, P, true);
-        Q3_HIP_CHECK(hipMemcpyAsync(x, rows, (size_t)P * H * sizeof(float), hipMemcpyHostToDevice, stream));
-        if (P <= 16) { prefill_rows_in_xp(slot, P); sync(); }
-        else prefill_rows_long(slot, x, P, nullptr);
-        kv_prefix_copy(pf, nullptr, 1, slot, false);
-        sync();
-    } catch (...) {
-        st_h[slot] = keep;
-        try { kv_release(slot); sync(); } catch (...) { }
-        (void)hipFree(pf.k); (void)hipFree(pf.v);
-        throw;
-    }
-    st_h[slot] = keep;
-    kv_release(slot);
-    sync();   // the table row's upload reads the host mirror
-    const int id = prefix_next_id++;
-    prefixes[id] = pf;
-    return id;
-}
-
-void Engine::prefix_release(int id) {
-    auto it = prefixes.find(id);
-    if (it == prefixes.end()) throw Error("unknown prefix id " + std::to_string(id) + " (never created, or released)");
-    if (it->second.users > 0) throw Error("prefix_release: prefix " + std::to_string(id) + " is in use by a running job");
-    sync();
-    (void)hipFree(it->second.k); (void)hipFree(it->second.v);
-    prefixes.erase(it);
-}
-
-// run_prefill (tts_onnx.cpp:615-665) for slots begun behind shared prefixes: see q3_engine.h.
-void Engine::slots_begin_prefixed(const SlotInit* in, int n, const q3tts_sampling& p, uint64_t seed, int ignore_eos) {
-    bool any = false;
-    for (int i = 0; i < n; ++i) any = any || in[i].prefix_id != -1;
-    if (!any) { slots_begin(in, n, p, seed, ignore_eos); return; }   // no prefix anywhere: today's path, untouched
-    if (!finalized) throw Error("weights not finalized");
-    const int H = c.hidden, V = c.vocab;
-    const float rep_penalty = checked_penalty(p);
-    std::vector<int> Pof((size_t)n, 0);
-    for (int i = 0; i < n; ++i) {
-        const SlotInit& q = in[i];
-        if (q.slot < 0 || q.slot >= B) throw Error("slot out of range");
-        if (q.n_trailing < 0 || q.n_trailing > max_trailing) throw Error("too many trailing text rows");
-        if (q.S < 1 || q.S > max_ctx) throw Error("prefill length must be 1..max_ctx rows");
-        if (!q.prompt) throw Error("slots_begin_prefixed: null prompt");
-        if (q.prefix_id != -1) Pof[(size_t)i] = prefix_get(q.prefix_id).P;
-        if (q.n_prefix < 0 || (q.n_prefix > 0 && !q.prefix)) throw Error("prefix codes: n_prefix must be >= 0 (and the codes given)");
-        if (p.max_new_tokens < 1 || Pof[(size_t)i] + q.S + q.n_prefix + p.max_new_tokens > max_ctx) throw Error("prefix + prompt + prefix frames + max_new_tokens exceeds max_ctx");
-        if (q.n_prefix > 0) {
-            if (q.n_prefix + p.max_new_tokens > max_frames_cap) throw Error("prefix frames + max_new_tokens exceeds the slot's frame capacity");
-            check_frame_codes(q.prefix, q.n_prefix, true);
-        }
-        for (int j = 0; j < i; ++j) if (in[j].slot == q.slot) throw Error("slots_begin_prefixed: slot listed twice");
-    }
-    auto cap_of = [&](const SlotInit& q) { return q.max_frames > 0 ? std::min(q.max_frames, p.max_new_tokens) : p.max_new_tokens; };
-    auto tokens_of = [&](int i) {
-        const SlotInit& q = in[i];
-        const int own = Pof[(size_t)i] + q.S + q.n_prefix, all = own + cap_of(q);
-        return q.kv_tokens > 0 ? std::min(all, std::max(q.kv_tokens, own)) : all;
-    };
-    {   // KV pages for the whole set, all or nothing (as slots_begin)
-        int need = 0;
-        for (int i = 0; i < n; ++i) need += kv_pages_for(tokens_of(i)) - kv_slot_pages(in[i].slot);
-        if (need > kv_free_pages()) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "KV page pool exhausted: %d slots need %d more pages, %d of %d free", n, need, kv_free_pages(), kv_total_pages());
-            throw Error(msg);
-        }
-        for (int pass = 0; pass < 2; ++pass)
-            for (int i = 0; i < n; ++i)
-                if ((kv_pages_for(tokens_of(i)) <= kv_slot_pages(in[i].slot)) == (pass == 0)) kv_reserve(in[i].slot, tokens_of(i), true);
-    }
-    if (!grp_pos_d) { grp_pos_d = (int*)dmalloc(128 * sizeof(int)); grp_x_d = (float*)dmalloc((size_t)128 * H * sizeof(float)); }
-    std::vector<int32_t> pos_h, map_h;
-    {   // each prefix's rows into the pages of its slots: one launch per prefix (per 128 slots)
-        std::vector<char> done((size_t)n, 0);
-        for (int i = 0; i < n; ++i) {
-            if (done[(size_t)i] || in[i].prefix_id == -1) continue;
-            map_h.clear();
-            for (int j = i; j < n; ++j) if (in[j].prefix_id == in[i].prefix_id) { map_h.push_back(in[j].slot); done[(size_t)j] = 1; }
-            const Prefix& pf = prefix_get(in[i].prefix_id);
-            for (size_t o = 0; o < map_h.size(); o += 128) {
-                const int m = (int)std::min<size_t>(128, map_h.size() - o);
-                Q3_HIP_CHECK(hipMemcpyAsync(slot_map_d, map_h.data() + o, (size_t)m * sizeof(int), hipMemcpyHostToDevice, stream));
-                kv_prefix_copy(pf, slot_map_d, m, 0, true);
-                sync();   // map_h and slot_map_d are reused
-            }
-        }
-    }
-    const bool mfma_ok = H % 128 == 0 && (c.n_heads * c.head_dim) % 128 == 0 && c.ffn % 128 == 0 && H <= 4096;   // run_layers' MFMA condition
-    auto batchable = [&](int i) { return mfma_ok && in[i].S <= 16 && in[i].n_prefix == 0; };
-    std::vector<char> armed((size_t)n, 0);   // the forced begin arms its slot itself
-    int i0 = 0;
-    while (i0 < n) {
-        const int S = in[i0].S, cap = batchable(i0) ? 128 / S : 1;
-        int g = 1;
-        while (i0 + g < n && g < cap && batchable(i0 + g) && in[i0 + g].S == S) ++g;
-        if (g == 1 || g * S < mfma_min_rows) {   // one at a time: the single-slot chunk path at base P (no prefix: what slots_begin does)
-            for (int k = 0; k < g; ++k) {
-                const SlotInit& q = in[i0 + k];
-                const int P = Pof[(size_t)(i0 + k)];
-                if (q.n_prefix > 0) { slot_begin_forced(q, p, seed, ignore_eos, rep_penalty, P); armed[(size_t)(i0 + k)] = 1; }
-                else if (q.prefix_id == -1) talker_prefill(q.slot, q.prompt, S, nullptr, nullptr);
-                else {
-                    float* x = long_rows(S);
-                    Q3_HIP_CHECK(hipMemcpyAsync(x, q.prompt, (size_t)S * H * sizeof(float), hipMemcpyHostToDevice, stream));
-                    prefill_rows_long(q.slot, x, S, nullptr, P);
-                }
-            }
-        } else {   // one pass for the group: chunk attention at per-member bases, the codec head on each member's last row
-            long_ws_ensure();
-            pos_h.resize((size_t)g); map_h.resize((size_t)g);
-            int pmax = 0;
-            for (int k = 0; k < g; ++k) {
-                Q3_HIP_CHECK(hipMemcpyAsync(grp_x_d + (size_t)k * S * H, in[i0 + k].prompt, (size_t)S * H * sizeof(float), hipMemcpyHostToDevice, stream));
-                pos_h[(size_t)k] = Pof[(size_t)(i0 + k)]; map_h[(size_t)k] = in[i0 + k].slot;
-                pmax = std::max(pmax, Pof[(size_t)(i0 + k)]);
-            }
-            Q3_HIP_CHECK(hipMemcpyAsync(grp_pos_d, pos_h.data(), (size_t)g * sizeof(int), hipMemcpyHostToDevice, stream));
-            Q3_HIP_CHECK(hipMemcpyAsync(slot_map_d, map_h.data(), (size_t)g * sizeof(int), hipMemcpyHostToDevice, stream));
-            {
-                struct Scope { Engine& e; explicit Scope(Engine& en) : e(en) { e.long_ws_swap(); e.chunk_attn = true; } ~Scope() { e.chunk_attn = false; e.long_ws_swap(); } } scope(*this);
-                float* const hnw = lws.hn;   // not swapped
-                const bool pr = run_layers(talker, grp_x_d, H, g, S, 0, grp_pos_d, pmax, talker_norm, c.rms_eps, hnw, H, slot_map_d);
-                if (!pr) throw Error("batched prefill expects the MFMA path");
-                head_proj(codec_head, grp_x_d, H, talker_norm, c.rms_eps, nullptr, 0, logits_g, V, g, V, H, true, true, S - 1, S);
-                for (int k = 0; k < g; ++k) {
-                    const int sl = in[i0 + k].slot;
-                    launch_copy_rows(logits_g + (size_t)k * V, V, logits_t + (size_t)sl * V, V, 1, V, stream);
-                    launch_copy_rows(hnw + (size_t)(k * S + S - 1) * H, H, x_cp + (size_t)sl * 2 * H, 2 * H, 1, H, stream);
-                    pos_h[(size_t)k] += S;
-                }
-            }
-            for (int k = 0; k < g; ++k)
-                Q3_HIP_CHECK(hipMemcpyAsync(talker_pos_d + in[i0 + k].slot, &pos_h[(size_t)k], sizeof(int32_t), hipMemcpyHostToDevice, stream));
-            sync();   // pos_h / map_h are reused by the next group
-        }
-        i0 += g;
-    }
-    for (int i = 0; i < n; ++i) {
-        if (armed[(size_t)i]) continue;
-        const SlotInit& q = in[i];
-        if (q.n_trailing > 0)
-            Q3_HIP_CHECK(hipMemcpyAsync(trailing_d + (size_t)q.slot * max_trailing * H, q.trailing, (size_t)q.n_trailing * H * sizeof(float), hipMemcpyHostToDevice, stream));
-        slot_codec_stream_reset(q.slot);
-        SlotState& s = st_h[q.slot];
-        s.n_frames = 0; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.prefix_len = Pof[(size_t)i]; s.trailing_len = q.n_trailing; s.text_open = 0; stepped_h[q.slot] = 0;
-        s.max_frames = cap_of(q);
-        s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
-        Q3_HIP_CHECK(hipMemsetAsync(seen_d + (size_t)q.slot * seen_ld, 0, (size_t)seen_ld * sizeof(uint32_t), stream));
-        Q3_HIP_CHECK(hipMemcpyAsync(st_d + q.slot, &s, sizeof(SlotState), hipMemcpyHostToDevice, stream));
-    }
-    sync();
-}
-
-// ------------------------------------------------------------------------------------------------
-// ragged prefill (q3_engine.h)
-// ------------------------------------------------------------------------------------------------
-float* Engine::rag_rows(size_t rows) {
-    if (rows > rag_x_rows) {
-        sync();
-        if (rag_x_d) (void)hipFree(rag_x_d);
-        rag_x_d = nullptr; rag_x_rows = 0;
-        const size_t cap = std::max(rows, (size_t)512);
-        Q3_HIP_CHECK(hipMalloc((void**)&rag_x_d, cap * c.hidden * sizeof(float)));
-        rag_x_rows = cap;
-    }
-    return rag_x_d;
-}
-
-void Engine::seg_tables_build(const std::vector<SegMember>& members, std::vector<SegChunk>& chunks) {
-    const int TQ = attn_prefill_tile_rows(talker.nq, talker.nkv), CH = prefill_chunk;
-    sync();   // seg_tab_h may still be read by the previous call's upload
-    seg_tab_h.clear();
-    chunks.clear();
-    std::vector<int32_t> seg, row_seg, tiles, last;
-    auto flush = [&](SegChunk& ch) {
-        ch.n_seg = (int)seg.size() / 4; ch.n_tiles = (int)tiles.size() / 2; ch.n_last = (int)last.size();
-        ch.seg = seg_tab_h.size(); seg_tab_h.insert(seg_tab_h.end(), seg.begin(), seg.end());
-        ch.row_seg = seg_tab_h.size(); seg_tab_h.insert(seg_tab_h.end(), row_seg.begin(), row_seg.end());
-        ch.tiles = seg_tab_h.size(); seg_tab_h.insert(seg_tab_h.end(), tiles.begin(), tiles.end());
-        ch.last = seg_tab_h.size(); seg_tab_h.insert(seg_tab_h.end(), last.begin(), last.end());
-        chunks.push_back(ch);
-        seg.clear(); row_seg.clear(); tiles.clear(); last.clear();
-    };
-    SegChunk cur;
-    int row = 0;   // rows staged so far
-    for (size_t mi = 0; mi < members.size(); ++mi) {
-        const SegMember& m = members[mi];
-        if (m.rows < 1 || m.base < 0 || m.slot < 0 || m.slot >= B || m.base + m.rows > kv_slot_pages(m.slot) * 64)
-            throw Error("ragged prefill: a member's rows do not fit its slot's pages");
-        for (int done = 0; done < m.rows;) {
-            if (cur.rows == CH) { flush(cur); cur = SegChunk(); cur.row0 = row; }
-            const int n = std::min(m.rows - done, CH - cur.rows), si = (int)seg.size() / 4;
-            seg.push_back(m.slot); seg.push_back(m.base + done); seg.push_back(cur.rows); seg.push_back(n);
-            for (int r = 0; r < n; ++r) row_seg.push_back(si);
-            for (int r = 0; r < n; r += TQ) { tiles.push_back(si); tiles.push_back(r); }
-            cur.rows += n; done += n; row += n;
-            if (done == m.rows) { last.push_back(cur.rows - 1); cur.last_member.push_back((int)mi); }
-        }
-    }
-    if (cur.rows > 0) flush(cur);
-    if (seg_tab_h.size() > seg_tab_cap) {
-        if (seg_tab_d) (void)hipFree(seg_tab_d);
-        seg_tab_d = nullptr; seg_tab_cap = 0;
-        const size_t cap = std::max(seg_tab_h.size(), (size_t)4096);
-        Q3_HIP_CHECK(hipMalloc((void**)&seg_tab_d, cap * sizeof(int32_t)));
-        seg_tab_cap = cap;
-    }
-    Q3_HIP_CHECK(hipMemcpyAsync(seg_tab_d, seg_tab_h.data(), seg_tab_h.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-}
-
-// run_prefill (tts_onnx.cpp:615-665) and the frame loop's talker input rows (:824-842) for many slots at once: see q3_engine.h.
-void Engine::slots_begin_ragged(const SlotInit* in, int n, const q3tts_sampling& p, uint64_t seed, int ignore_eos) {
-    if (n < 1) return;
-    if (n == 1) { slots_begin_prefixed(in, 1, p, seed, ignore_eos); return; }   // one member: exactly its one-at-a-time begin
-    if (!finalized) throw Error("weights not finalized");
-    const int H = c.hidden, V = c.vocab, G = c.n_groups;
-    const float rep_penalty = checked_penalty(p);
-    std::vector<int> Pof((size_t)n, 0);
-    size_t total = 0;
-    for (int i = 0; i < n; ++i) {   // slots_begin_prefixed's checks and messages, for every member before anything is reserved
-        const SlotInit& q = in[i];
-        if (q.slot < 0 || q.slot >= B) throw Error("slot out of range");
-        if (q.n_trailing < 0 || q.n_trailing > max_trailing) throw Error("too many trailing text rows");
-        if (q.S < 1 || q.S > max_ctx) throw Error("prefill length must be 1..max_ctx rows");
-        if (!q.prompt) throw Error("slots_begin_ragged: null prompt");
-        if (q.n_trailing > 0 && !q.trailing) throw Error("slots_begin_ragged: trailing rows announced but not given");
-        if (q.prefix_id != -1) Pof[(size_t)i] = prefix_get(q.prefix_id).P;
-        if (q.n_prefix < 0 || (q.n_prefix > 0 && !q.prefix)) throw Error("prefix codes: n_prefix must be >= 0 (and the codes given)");
-        if (p.max_new_tokens < 1 || Pof[(size_t)i] + q.S + q.n_prefix + p.max_new_tokens > max_ctx) throw Error("prefix + prompt + prefix frames + max_new_tokens exceeds max_ctx");
-        if (q.n_prefix > 0) {
-            if (q.n_prefix + p.max_new_tokens > max_frames_cap) throw Error("prefix frames + max_new_tokens exceeds the slot's frame capacity");
-            check_frame_codes(q.prefix, q.n_prefix, true);
-        }
-        for (int j = 0; j < i; ++j) if (in[j].slot == q.slot) throw Error("slots_begin_ragged: slot listed twice");
-        total += (size_t)(q.S + q.n_prefix);
-    }
-    auto cap_of = [&](const SlotInit& q) { return q.max_frames > 0 ? std::min(q.max_frames, p.max_new_tokens) : p.max_new_tokens; };
-    auto tokens_of = [&](int i) {
-        const SlotInit& q = in[i];
-        const int own = Pof[(size_t)i] + q.S + q.n_prefix, all = own + cap_of(q);
-        return q.kv_tokens > 0 ? std::min(all, std::max(q.kv_tokens, own)) : all;
-    };
-    {   // KV pages for the whole set, all or nothing (as slots_begin)
-        int need = 0;
-        for (int i = 0; i < n; ++i) need += kv_pages_for(tokens_of(i)) - kv_slot_pages(in[i].slot);
-        if (need > kv_free_pages()) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "KV page pool exhausted: %d slots need %d more pages, %d of %d free", n, need, kv_free_pages(), kv_total_pages());
-            throw Error(msg);
-        }
-        for (int pass = 0; pass < 2; ++pass)
-            for (int i = 0; i < n; ++i)
-                if ((kv_pages_for(tokens_of(i)) <= kv_slot_pages(in[i].slot)) == (pass == 0)) kv_reserve(in[i].slot, tokens_of(i), true);
-    }
-    const bool mfma_ok = H % 128 == 0 && (c.n_heads * c.head_dim) % 128 == 0 && c.ffn % 128 == 0 && H <= 4096;   // run_layers' MFMA condition
-    if (!mfma_ok || !attn_prefill_seg_ok(talker.d, talker.nq, talker.nkv) || total < (size_t)mfma_min_rows || seam_step) {
-        // the members one at a time, each exactly as its own begin (its pages are reserved already: that call's reservation changes nothing)
-        for (int i = 0; i < n; ++i) slots_begin_prefixed(in + i, 1, p, seed, ignore_eos);
-        return;
-    }
-    std::vector<int32_t> map_h;
-    {   // each prefix's rows into the pages of its slots: one launch per prefix (per 128 slots), as slots_begin_prefixed
-        std::vector<char> done((size_t)n, 0);
-        for (int i = 0; i < n; ++i) {
-            if (done[(size_t)i] || in[i].prefix_id == -1) continue;
-            map_h.clear();
-            for (int j = i; j < n; ++j) if (in[j].prefix_id == in[i].prefix_id) { map_h.push_back(in[j].slot); done[(size_t)j] = 1; }
-            const Prefix& pf = prefix_get(in[i].prefix_id);
-            for (size_t o = 0; o < map_h.size(); o += 128) {
-                const int m = (int)std::min<size_t>(128, map_h.size() - o);
-                Q3_HIP_CHECK(hipMemcpyAsync(slot_map_d, map_h.data() + o, (size_t)m * sizeof(int), hipMemcpyHostToDevice, stream));
-                kv_prefix_copy(pf, slot_map_d, m, 0, true);
-                sync();   // map_h and slot_map_d are reused
-            }
-        }
-    }
-    // ---- the members' rows, contiguous in call order: prompt rows from the host, forced frames' rows made on the device ----
-    float* const x = rag_rows(total);
-    long_ws_ensure();
-    if (!rag_last_x_d) { rag_last_x_d = (float*)dmalloc((size_t)128 * H * sizeof(float)); rag_last_hn_d = (float*)dmalloc((size_t)128 * H * sizeof(float)); }
-    std::vector<SegMember> members((size_t)n);
-    {
-        size_t r = 0;
-        for (int i = 0; i < n; ++i) {
-            const SlotInit& q = in[i];
-            float* tr = trailing_d + (size_t)q.slot * max_trailing * H;
-            uint32_t* seen = seen_d + (size_t)q.slot * seen_ld;
-            Q3_HIP_CHECK(hipMemcpyAsync(x + r * H, q.prompt, (size_t)q.S * H * sizeof(float), hipMemcpyHostToDevice, stream));
-            if (q.n_trailing > 0) Q3_HIP_CHECK(hipMemcpyAsync(tr, q.trailing, (size_t)q.n_trailing * H * sizeof(float), hipMemcpyHostToDevice, stream));
-            // the code0 history starts empty and then holds the forced frames: cleared before the launch that sets its bits, not behind it
-            Q3_HIP_CHECK(hipMemsetAsync(seen, 0, (size_t)seen_ld * sizeof(uint32_t), stream));
-            if (q.n_prefix > 0)
-                frame_rows_launch(q.prefix, q.n_prefix, 0, tr, q.n_trailing, x + (r + (size_t)q.S) * H, codes_d + (size_t)q.slot * max_frames_cap * G, seen);
-            members[(size_t)i].slot = q.slot; members[(size_t)i].base = Pof[(size_t)i]; members[(size_t)i].rows = q.S + q.n_prefix;
-            r += (size_t)(q.S + q.n_prefix);
-        }
-    }
-    std::vector<SegChunk> chunks;
-    seg_tables_build(members, chunks);
-    {
-        struct Scope { Engine& e; explicit Scope(Engine& en) : e(en) { e.long_ws_swap(); e.chunk_attn = true; } ~Scope() { e.seg_attn = nullptr; e.chunk_attn = false; e.long_ws_swap(); } } scope(*this);
-        float* const hnw = lws.hn;   // not swapped
-        SegAttn sa;
-        for (const SegChunk& ch : chunks) {
-            sa.seg = seg_tab_d + ch.seg; sa.row_seg = seg_tab_d + ch.row_seg; sa.tiles = seg_tab_d + ch.tiles; sa.n_seg = ch.n_seg; sa.n_tiles = ch.n_tiles;
-            seg_attn = &sa;
-            float* xc = x + (size_t)ch.row0 * H;
-            run_layers(talker, xc, H, 1, ch.rows, 0, nullptr, 0, talker_norm, c.rms_eps, hnw, H);
-            ++ragged_passes;
-            if (ch.n_last == 0) continue;
-            // final norm + codec head on the rows that end a member: gathered by row index, then scattered to their slots
-            launch_gather_rows_f32(xc, H, seg_tab_d + ch.last, ch.n_last, rag_last_x_d, H, H, stream);
-            head_proj(codec_head, rag_last_x_d, H, talker_norm, c.rms_eps, rag_last_hn_d, H, logits_g, V, ch.n_last, V, H, true);
-            for (int k = 0; k < ch.n_last; ++k) {
-                const int sl = in[ch.last_member[(size_t)k]].slot;
-                launch_copy_rows(logits_g + (size_t)k * V, V, logits_t + (size_t)sl * V, V, 1, V, stream);
-                launch_copy_rows(rag_last_hn_d + (size_t)k * H, H, x_cp + (size_t)sl * 2 * H, 2 * H, 1, H, stream);
-            }
-        }
-    }
-    std::vector<int32_t> pos_h((size_t)n);
-    for (int i = 0; i < n; ++i) {   // the armed state, per slot what its one-at-a-time begin sets
-        const SlotInit& q = in[i];
-        pos_h[(size_t)i] = Pof[(size_t)i] + q.S + q.n_prefix;
-        Q3_HIP_CHECK(hipMemcpyAsync(talker_pos_d + q.slot, &pos_h[(size_t)i], sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        slot_codec_stream_reset(q.slot);
-        SlotState& s = st_h[q.slot];
-        s.n_frames = q.n_prefix; s.finished = 0; s.active = 1; s.prompt_len = q.S; s.prefix_len = Pof[(size_t)i]; s.trailing_len = q.n_trailing; s.text_open = 0; stepped_h[q.slot] = 0;
-        s.max_frames = q.n_prefix + cap_of(q);
-        s.top_k = p.top_k; s.ignore_eos = ignore_eos; s.temperature = p.temperature; s.top_p = p.top_p; s.stream_id = q.stream_id; s.rep_penalty = rep_penalty; s.seed = seed;
-        Q3_HIP_CHECK(hipMemcpyAsync(st_d + q.slot, &s, sizeof(SlotState), hipMemcpyHostToDevice, stream));
-    }
-    sync();   // pos_h, the tables' host copy and the callers' rows are read by the copies above
 }
 
 int Engine::decode_steps(int n_steps) {

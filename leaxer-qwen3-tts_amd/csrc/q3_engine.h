@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "q3_audio.h"
+#include "q3_begin_plan.h"
 #include "q3_common.h"
 #include "q3_kvpool.h"
 #include "q3_stage.h"
@@ -120,6 +121,8 @@ public:
     struct LongWs { float *qkv = nullptr, *attn = nullptr, *act = nullptr, *slab = nullptr, *gu_slab = nullptr, *qkv_slab = nullptr, *hn = nullptr, *logits = nullptr;
                     bf16_t *p0h = nullptr, *p0l = nullptr, *p1h = nullptr, *p1l = nullptr; int rows = 0; } lws;
     void long_ws_swap();                        // exchanges run_layers' row workspaces (and ws_rows) with lws
+    // a pass in the long workspace with the chunk attention (prefill_rows_long, the prefixed group, the ragged chunks); leaves no segment tables behind
+    struct LongWsScope { Engine& e; explicit LongWsScope(Engine& en) : e(en) { e.long_ws_swap(); e.chunk_attn = true; } ~LongWsScope() { e.seg_attn = nullptr; e.chunk_attn = false; e.long_ws_swap(); } };
     float* long_x_d = nullptr; size_t long_x_rows = 0;
     const float *long_last_logits = nullptr, *long_last_hidden = nullptr;
     int prefill_chunk = 128;                    // Q3TTS_PREFILL_CHUNK (16..128) at engine creation: A/B knob, lets a test cross chunk boundaries at a short prompt
@@ -325,7 +328,11 @@ public:
     hipEvent_t ev_join = nullptr, ev_fork = nullptr;
     void predictor_passes(int nb, const SampleArgs& s0, bool sp0, bool spn, const std::function<void()>& mark);
 
-    // ---- fused generation ----
+    // ---- fused generation: beginning utterances in slots (q3_begin.cpp) ----
+    // Three entries, because which prompts share a pass decides the bits: slots_begin (equal-length groups in xp), slots_begin_prefixed
+    // (groups at per-member bases in the long workspace) and slots_begin_ragged (segments over 128-row chunks).  Their refusals, the
+    // quantities derived from a member, the grouping rule and what differs between the entries are in ONE place, q3_begin_plan.h; what
+    // surrounds their launches is the helpers below, each written once.
     struct SlotInit { int slot = 0; const float* prompt = nullptr; int S = 0; const float* trailing = nullptr; int n_trailing = 0; uint32_t stream_id = 0;
                       int max_frames = 0; /* 0: the call's max_new_tokens */
                       int kv_tokens = 0;  /* KV pages reserved now, in tokens; 0: prompt + max_frames (the slot never needs more) */
@@ -337,12 +344,22 @@ public:
     void slots_begin(const SlotInit* in, int n, const q3tts_sampling& p, uint64_t seed, int ignore_eos); // batched prefill of equal-length prompts
     void slot_begin(int slot, const float* prompt, int S, const float* trailing, int n_trailing,
                     const q3tts_sampling& p, uint64_t seed, uint32_t stream_id, int ignore_eos);
-    void slot_begin_forced(const SlotInit& q, const q3tts_sampling& p, uint64_t seed, int ignore_eos, float rep_penalty, int base = 0);   // slots_begin's path for n_prefix > 0 (base: rows of a shared prefix in front)
+    void slot_begin_forced(const SlotInit& q, const q3tts_sampling& p, uint64_t seed, int ignore_eos, float rep_penalty, int base = 0);   // the path for n_prefix > 0, one slot (base: rows of a shared prefix in front)
+    // run_layers' MFMA condition on a stack's dims (the rows are the caller's: M >= mfma_min_rows): the slab GEMMs tile H, nq * d and ffn by 128
+    static bool mfma_dims_ok(const DecStack& W) { return W.H % 128 == 0 && (W.nq * W.d) % 128 == 0 && W.ffn % 128 == 0 && W.H <= 4096; }
+    BeginLimits begin_limits() const { return BeginLimits{B, max_ctx, max_trailing, max_frames_cap, rows_max, mfma_min_rows, mfma_dims_ok(talker)}; }
+    std::vector<BeginMember> begin_members(BeginEntry e, const SlotInit* in, int n, int max_new);   // the members' views, checked by the entry's rules (throws)
+    void kv_reserve_set(const BeginMember* m, int n, int max_new);                 // KV pages (begin_tokens) for the whole set, all or nothing
+    void prefix_fan_out(const SlotInit* in, int n);                                // each prefix's rows into the pages of its slots
+    void scatter_last_rows(const float* logits_row, const float* hidden_row, int slot);   // -> logits_t[slot], x_cp[slot]
+    void stage_slot_inputs(const SlotInit& q);                                     // trailing rows up, code0 history cleared
+    // the only writer of the armed SlotState (P: prefix rows in front).  stage_inputs == false: the caller staged them in front of frame_rows_launch
+    void arm_slot(const SlotInit& q, int P, float rep_penalty, const q3tts_sampling& p, uint64_t seed, int ignore_eos, bool stage_inputs);
     // ---- shared prompt prefix (run_prefill, tts_onnx.cpp:615-665, once for many utterances) ----
     // A prefix is P talker input rows prefilled once in a borrowed slot; their K / V rows are kept in a compact store
     // [layer][kvh][P][head_dim] per cache (the cache's element type).  slots_begin_prefixed copies the store into each slot's own pages
-    // (no page is shared) and prefills only the utterance's rows at base P: members with equal S <= 16 share one pass through the
-    // layers (launch_attn_prefill's group form at per-member bases, up to 128 rows), the rest go one at a time through
+    // (no page is shared) and prefills only the utterance's rows at base P: members that begin_groups puts in one group share one pass
+    // through the layers (launch_attn_prefill's group form at per-member bases, up to 128 rows), the rest go one at a time through
     // prefill_rows_long(base0 = P).  Every prefix_id == -1: exactly slots_begin.
     struct Prefix { int P = 0; void* k = nullptr; void* v = nullptr; int64_t bytes = 0; int users = 0; };
     std::unordered_map<int, Prefix> prefixes;   // live prefixes by id (ids are never reused)
@@ -360,8 +377,8 @@ public:
     // and the KV pages reserved (all or nothing) before anything is armed; the members' rows are staged contiguously in call order,
     // cut into chunks of prefill_chunk rows (a member that does not fit the rest of a chunk continues in the next one at base + rows
     // done) and every chunk takes ONE run_layers pass in the long workspace with the segment form of the chunk attention; the final
-    // norm + codec head run on the rows that end a member.  n == 1, dims off run_layers' MFMA condition or off the segment kernels'
-    // instantiations, and calls of fewer than mfma_min_rows rows begin their members one at a time (slots_begin_prefixed with n = 1).
+    // norm + codec head run on the rows that end a member.  n == 1, and whatever begin_ragged_one_at_a_time names (dims, the segment
+    // kernels' instantiations, fewer than mfma_min_rows rows), begin their members one at a time (slots_begin_prefixed with n = 1).
     void slots_begin_ragged(const SlotInit* in, int n, const q3tts_sampling& p, uint64_t seed, int ignore_eos);
     struct SegMember { int slot = 0, base = 0, rows = 0; };
     struct SegChunk { int row0 = 0, rows = 0, n_seg = 0, n_tiles = 0, n_last = 0;      // rows [row0, row0 + rows) of the staged sequence
@@ -586,6 +603,14 @@ public:
     std::unordered_map<int, hipGraphExec_t> graphs; // keyed by nb
 
     void* dmalloc(size_t bytes);
+    // a grow-only staging buffer's regrow to n x el elements (cap counts n): the stream drains first, since the old buffer may be in flight, unless the caller just did
+    template <class T> void regrow(T*& p, size_t& cap, size_t n, size_t el = 1, bool drained = false) {
+        if (!drained) sync();
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+        Q3_HIP_CHECK(hipMalloc((void**)&p, n * el * sizeof(T)));
+        cap = n;
+    }
     // final_gamma != null (MFMA path only): the last layer's finish kernel also applies the stack's final RMSNorm,
     // leaving (hi, lo) planes of the normalised rows in pl0 (+ fp32 rows in final_xn); returns true in that case
     bool run_layers(const DecStack& W, float* x, int ldx, int nb, int n_new, int slot_offset, const int* pos_dev, int pos_scalar,

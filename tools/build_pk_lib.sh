@@ -18,5 +18,5 @@ hipcc $F -x hip -c "$S/q3_speaker_kernels.hip" -o sk.o &
 wait
 B="$ROOT/leaxer-qwen3-tts_amd/build"
 hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/tools/exp/libpk.so" ck.o dk.o gk.o sk.o \
-    "$B/q3_engine.cpp.o" "$B/q3_codec.cpp.o" "$B/q3_speaker.cpp.o" "$B/q3_audio.cpp.o" "$B/q3_bpe.cpp.o" "$B/q3_job.cpp.o" "$B/q3_capi.cpp.o"
+    "$B/q3_engine.cpp.o" "$B/q3_begin.cpp.o" "$B/q3_codec.cpp.o" "$B/q3_speaker.cpp.o" "$B/q3_audio.cpp.o" "$B/q3_bpe.cpp.o" "$B/q3_job.cpp.o" "$B/q3_capi.cpp.o"
 echo "$ROOT/tools/exp/libpk.so"

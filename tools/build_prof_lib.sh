@@ -28,5 +28,5 @@ EOC
 hipcc --offload-arch=gfx950 -O2 -std=c++17 -fPIC -x hip -c prof_api.cpp -o prof_api.o
 B="$ROOT/leaxer-qwen3-tts_amd/build"
 hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/tools/exp/libprof.so" dk_prof.o $CK $([ "$SKIP_CODEC" = "1" ] && echo conv_stub.o) gk_prof.o prof_api.o \
-    "$B/q3_speaker_kernels.hip.o" "$B/q3_engine.cpp.o" "$B/q3_codec.cpp.o" "$B/q3_speaker.cpp.o" "$B/q3_audio.cpp.o" "$B/q3_bpe.cpp.o" "$B/q3_job.cpp.o" "$B/q3_capi.cpp.o"
+    "$B/q3_speaker_kernels.hip.o" "$B/q3_engine.cpp.o" "$B/q3_begin.cpp.o" "$B/q3_codec.cpp.o" "$B/q3_speaker.cpp.o" "$B/q3_audio.cpp.o" "$B/q3_bpe.cpp.o" "$B/q3_job.cpp.o" "$B/q3_capi.cpp.o"
 echo "$ROOT/tools/exp/libprof.so"

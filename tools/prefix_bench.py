@@ -39,7 +39,7 @@ rt.hipEventSynchronize.argtypes = [C.c_void_p]
 rt.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
 ev0, ev1 = C.c_void_p(), C.c_void_p()
 assert rt.hipEventCreate(C.byref(ev0)) == 0 and rt.hipEventCreate(C.byref(ev1)) == 0
-stream = eng.stream()
+stream = eng.stream   # a property
 
 rng = np.random.default_rng(0)
 ins = (rng.standard_normal((P, H)) * 0.1).astype(np.float32)
