@@ -196,10 +196,7 @@ int q3tts_codec_decode_batch_host(q3tts_engine* h, int n_utt, const int64_t* cod
     for (int u = 0; u < n_utt; ++u) {
         const int64_t* src = codes + (size_t)frame_offsets[u] * G;
         int32_t* dst = rows.data() + (size_t)u * row_frames * G;
-        for (size_t i = 0; i < (size_t)nf[(size_t)u] * G; ++i) {
-            if (src[i] < 0 || src[i] >= e.c.cd_codebook) throw q3::Error("codec_decode: code out of range");   // as q3tts_codec_decode_host
-            dst[i] = (int32_t)src[i];
-        }
+        q3::stage_codes<q3::Error>(src, (size_t)nf[(size_t)u] * G, e.c.cd_codebook, dst);   // as q3tts_codec_decode_host
     }
     e.codec_job_upload(rows.data(), n_utt, row_frames);
     q3::vocoder_job(e, n_utt, nf, row_frames, pcm_out, pcm_cap, pcm_len);
@@ -606,14 +603,7 @@ int q3tts_slot_codec_decode_range_host(q3tts_engine* h, int slot, int frame_begi
 }
 
 int64_t q3tts_codec_decode_len(const q3tts_config* c, int F) {
-    int64_t T = F;
-    for (int s = 0; s < c->cd_n_up; ++s) T *= c->cd_up_ratios[s];
-    for (int i = 0; i < c->cd_n_blocks; ++i) {
-        const int r = c->cd_up_rates[i], k = 2 * r, pad = k - r;
-        const int left = c->cd_tconv_trim == 0 ? pad : 0;
-        T = (T - 1) * r + k - left - pad;
-    }
-    return T;
+    return q3::codec_decode_len(*c, F);
 }
 
 int q3tts_sample_host(q3tts_engine* h, const float* logits, int n, const q3tts_sampling* p, float u, int suppress, int64_t* token) {

@@ -54,7 +54,7 @@ struct CodecW {
     int32_t* job_codes = nullptr; size_t job_codes_n = 0;
     const float* dbg_sx = nullptr; const float* dbg_pcm = nullptr; int dbg_T = 0, dbg_C = 0, dbg_nb = 0;   // test hook: the last batched group's final conv
     char* batch_arena = nullptr; size_t batch_arena_bytes = 0;   // batched pre-transformer of a job (codec_pre_batch)
-    int* batch_pages = nullptr; int batch_pages_n = 0;           // identity page table, one cache block per utterance   // codes of a scheduler job's finished utterances, [utterance][max_new][groups]
+    int* batch_pages = nullptr; size_t batch_pages_n = 0;          // identity page table, one cache block per utterance   // codes of a scheduler job's finished utterances, [utterance][max_new][groups]
     hipEvent_t lane_done[NLANE] = {};
     hipEvent_t fork = nullptr, win0 = nullptr, win1 = nullptr;
     bool window_open = false, win0_recorded = false;
@@ -262,8 +262,6 @@ void Engine::codec_rope_tables(int P) {
     if (W.rope_P >= P) return;
     const int HD = c.cd_head_dim;
     for (int i = 0; i < W.nlane; ++i) Q3_HIP_CHECK(hipStreamSynchronize(W.lane_stream[i])); // tables may be in use
-    if (W.rope_cos) (void)hipFree(W.rope_cos);
-    if (W.rope_sin) (void)hipFree(W.rope_sin);
     const int half = HD / 2;
     std::vector<float> cs((size_t)P * half), sn((size_t)P * half);
     for (int p = 0; p < P; ++p)
@@ -272,11 +270,92 @@ void Engine::codec_rope_tables(int P) {
             const float ang = (float)p * inv;
             cs[(size_t)p * half + i] = cosf(ang); sn[(size_t)p * half + i] = sinf(ang);
         }
-    Q3_HIP_CHECK(hipMalloc((void**)&W.rope_cos, cs.size() * sizeof(float)));
-    Q3_HIP_CHECK(hipMalloc((void**)&W.rope_sin, sn.size() * sizeof(float)));
+    // the old tables are freed by regrow (every lane drained above); rope_P counts again once both new ones are filled
+    size_t cap = 0;
+    W.rope_P = 0;
+    regrow(W.rope_cos, cap, cs.size(), 1, true);
+    regrow(W.rope_sin, cap, sn.size(), 1, true);
     Q3_HIP_CHECK(hipMemcpy(W.rope_cos, cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice));
     Q3_HIP_CHECK(hipMemcpy(W.rope_sin, sn.data(), sn.size() * sizeof(float), hipMemcpyHostToDevice));
     W.rope_P = P;
+}
+
+// ------------------------------------------------------------------------------------------------
+// What the five decode paths share: the conv launcher, the attention arguments, the pre-transformer's layer loop and the
+// workspace rule.  A path keeps what differs: its rows, the order it carves its arena in, its K / V store and attention, the code
+// embedding in front of the loop and the final norm behind it.
+// ------------------------------------------------------------------------------------------------
+// Every conv / linear launch: the weight's (hi, lo, cm) planes, the SnakeBeta constants and the caller's split-K slab are attached here.
+// plan: codec_run's sizing pass, which launches nothing; batch: sequences per launch of its conv decoder
+struct ConvLauncher {
+    const CodecW& W; float* slab; hipStream_t stream; int batch = 1; bool plan = false;
+    void operator()(ConvArgs a) const {
+        if (plan) return;
+        a.slab = slab; a.slab_floats = CODEC_KSLAB_FLOATS; a.batch = batch;
+        const auto it = W.planes.find(a.W);
+        if (it != W.planes.end()) { a.Wh = it->second.hi; a.Wl = it->second.lo; a.Whc = it->second.cm; a.w_scale_inv = it->second.scale_inv; a.w_lo_zero = it->second.lo_zero; }
+        if (a.snake_alpha) { const auto sp = W.snake_pre.find(a.snake_alpha); if (sp != W.snake_pre.end()) a.snake_pre = sp->second; }
+        if (a.mid_alpha) { const auto sp = W.snake_pre.find(a.mid_alpha); if (sp != W.snake_pre.end()) a.mid_pre = sp->second; }
+        launch_conv(a, stream);
+    }
+};
+
+// The vocoder's windowed attention over one layer's roped, stored K / V ([block][head][2^page_shift][d], one block per sequence through
+// page_table): nb sequences of n_new rows each, the first of them at cache row pos_scalar
+static AttnArgs codec_attn_args(const q3tts_config& c, const float* qkv, float* out, float* kc, float* vc, const int* page_table, int page_shift, int pos_scalar, int nb, int n_new) {
+    AttnArgs a;
+    a.qkv = qkv; a.ld_qkv = 3 * c.cd_hidden; a.out = out; a.ld_out = c.cd_hidden; a.kcache = kc; a.vcache = vc;
+    a.page_table = page_table; a.pages_per_slot = 1; a.page_shift = page_shift; a.layer = 0; a.n_layers = 1;
+    a.pos_scalar = pos_scalar; a.slot_offset = 0; a.nb = nb; a.n_new = n_new; a.nq = c.cd_heads; a.nkv = c.cd_heads; a.d = c.cd_head_dim;
+    a.scale = 1.0f / sqrtf((float)c.cd_head_dim); a.window = c.cd_window; a.new_from_raw = 0;
+    return a;
+}
+
+// The pre-transformer's layers over T rows of h, in place: RMSNorm, QKV GEMM, store_and_attend(l), o_proj with residual scale, RMSNorm,
+// up, gate . up, down with residual scale.  store_and_attend(l) is the caller's launches between the QKV GEMM and o_proj (RoPE + K / V
+// store of qkvb's rows, attention into att): the only thing that differs per path.  The six row buffers are the caller's; nothing is allocated.
+struct PreBufs { float *h, *hn, *att, *qkvb, *ub, *gb; };
+template <class StoreAttend>
+static void pre_transformer_layers(const q3tts_config& c, const CodecW& W, int T, const PreBufs& b, const ConvLauncher& conv, StoreAttend&& store_and_attend, hipStream_t stream) {
+    const int CH = c.cd_hidden, FF = c.cd_ffn;
+    auto gemm = [&](const float* in, int Cin, const float* Wm, int Cout, float* out) {
+        ConvArgs a; a.in = in; a.T_in = T; a.C_in = Cin; a.out = out; a.T_out = T; a.C_out = Cout; a.W = Wm;
+        return a;
+    };
+    for (int l = 0; l < c.cd_layers; ++l) {
+        const CodecW::Layer& L = W.layers[l];
+        launch_rmsnorm_rows(b.h, L.in_norm, c.cd_rms_eps, T, CH, b.hn, stream);
+        conv(gemm(b.hn, CH, L.qkv, 3 * CH, b.qkvb));
+        store_and_attend(l);
+        { ConvArgs a = gemm(b.att, CH, L.o, CH, b.h); a.res_scale = L.attn_scale; a.res = b.h; conv(a); }
+        launch_rmsnorm_rows(b.h, L.post_norm, c.cd_rms_eps, T, CH, b.hn, stream);
+        conv(gemm(b.hn, CH, L.up, FF, b.ub));
+        { ConvArgs a = gemm(b.hn, CH, L.gate, FF, b.gb); a.act = 2; a.mul = b.ub; conv(a); }
+        { ConvArgs a = gemm(b.gb, FF, L.down, CH, b.h); a.res_scale = L.mlp_scale; a.res = b.h; conv(a); }
+    }
+}
+
+// Engine::regrow's order (free, null and zero capacity, allocate, set capacity) for a lane's pinned staging buffer.  No drain: the caller
+// has drained the lane, so no copy into the old buffer is in flight.
+static void regrow_pinned(float*& p, size_t& cap, size_t n) {
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+    Q3_HIP_CHECK(hipHostMalloc((void**)&p, n * sizeof(float)));
+    cap = n;
+}
+
+// identity page table of the whole-utterance layouts, one scratch cache block per sequence: [0, n); [n_cap, 2 n_cap): codec_pre_batch's
+// perm area.  The capacity counts only once the identity is in the new buffer.
+static void codec_identity_pages(Engine& e, int n) {
+    CodecW& W = *e.codec;
+    if (W.batch_pages_n >= (size_t)n) return;
+    size_t cap = 0;
+    W.batch_pages_n = 0;
+    e.regrow(W.batch_pages, cap, (size_t)n, 2);
+    std::vector<int> idt((size_t)n);
+    for (int i = 0; i < n; ++i) idt[(size_t)i] = i;
+    Q3_HIP_CHECK(hipMemcpy(W.batch_pages, idt.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    W.batch_pages_n = cap;
 }
 
 int64_t Engine::codec_run(const int32_t* codes_dev, int F, float** pcm_dev, int lane, const float* h_in, int h_stage, int nbatch, size_t h_ustride) {
@@ -296,24 +375,9 @@ int64_t Engine::codec_run(const int32_t* codes_dev, int F, float** pcm_dev, int 
     float* pcm = nullptr;
     for (int pass = 0; pass < 2; ++pass) { // pass 0 sizes the arena, pass 1 launches
         const bool plan = pass == 0;
-        size_t off = 0;
-        auto take = [&](size_t nfloat) -> float* {
-            const size_t bytes = (nfloat * sizeof(float) + 255) & ~(size_t)255;
-            float* p = plan ? nullptr : (float*)(W.arena[lane] + off);
-            off += bytes;
-            return p;
-        };
-        const size_t kslab_floats = (size_t)32 * 128 * 4096;   // split-K partial sums of the short pre-transformer / ConvNeXt GEMMs
-        float* kslab = take(kslab_floats);
-        auto conv = [&](ConvArgs a) {
-            if (plan) return;
-            a.slab = kslab; a.slab_floats = kslab_floats; a.batch = nbatch;
-            const auto it = W.planes.find(a.W);
-            if (it != W.planes.end()) { a.Wh = it->second.hi; a.Wl = it->second.lo; a.Whc = it->second.cm; a.w_scale_inv = it->second.scale_inv; a.w_lo_zero = it->second.lo_zero; }
-            if (a.snake_alpha) { const auto sp = W.snake_pre.find(a.snake_alpha); if (sp != W.snake_pre.end()) a.snake_pre = sp->second; }
-            if (a.mid_alpha) { const auto sp = W.snake_pre.find(a.mid_alpha); if (sp != W.snake_pre.end()) a.mid_pre = sp->second; }
-            launch_conv(a, stream);
-        };
+        CodecBump take{ plan ? nullptr : W.arena[lane] };
+        float* kslab = take(CODEC_KSLAB_FLOATS);
+        const ConvLauncher conv{ W, kslab, stream, nbatch, plan };
         auto gemm = [&](const float* in, int T, int Cin, const float* Wm, const float* bias, int Cout, float* out) {
             ConvArgs a; a.in = in; a.T_in = T; a.C_in = Cin; a.out = out; a.T_out = T; a.C_out = Cout; a.W = Wm; a.bias = bias;
             return a;
@@ -327,27 +391,14 @@ int64_t Engine::codec_run(const int32_t* codes_dev, int F, float** pcm_dev, int 
         float* gb = take((size_t)F * FF);
         float* kc = take((size_t)NH * P * HD);
         float* vc = take((size_t)NH * P * HD);
-        if (!plan && !h_in) launch_code_embed_mean(W.code_embed, codes_dev, F, c.n_groups, c.cd_codebook, CH, h, stream);
-        for (int l = 0; l < (h_in ? 0 : c.cd_layers); ++l) {   // h_in: the pre-transformer of this utterance already ran in codec_pre_batch
-            const CodecW::Layer& L = W.layers[l];
-            if (!plan) launch_rmsnorm_rows(h, L.in_norm, c.cd_rms_eps, F, CH, hn, stream);
-            conv(gemm(hn, F, CH, L.qkv, nullptr, 3 * CH, qkvb));
-            if (!plan) {
+        if (!plan && !h_in) {   // h_in: the pre-transformer of this utterance already ran (codec_pre_batch, a push)
+            launch_code_embed_mean(W.code_embed, codes_dev, F, c.n_groups, c.cd_codebook, CH, h, stream);
+            pre_transformer_layers(c, W, F, PreBufs{ h, hn, att, qkvb, ub, gb }, conv, [&](int) {
                 launch_rope_store(qkvb, 3 * CH, F, NH, NH, HD, W.rope_cos, W.rope_sin, kc, vc, P, stream);
-                AttnArgs a;
-                a.qkv = qkvb; a.ld_qkv = 3 * CH; a.out = att; a.ld_out = CH; a.kcache = kc; a.vcache = vc;
-                a.page_table = W.page_table; a.pages_per_slot = 1; a.page_shift = pshift; a.layer = 0; a.n_layers = 1;
-                a.pos_scalar = 0; a.slot_offset = 0; a.nb = 1; a.n_new = F; a.nq = NH; a.nkv = NH; a.d = HD;
-                a.scale = 1.0f / sqrtf((float)HD); a.window = c.cd_window; a.new_from_raw = 0;
-                launch_attn(a, stream);
-            }
-            { ConvArgs a = gemm(att, F, CH, L.o, nullptr, CH, h); a.res_scale = L.attn_scale; a.res = h; conv(a); }
-            if (!plan) launch_rmsnorm_rows(h, L.post_norm, c.cd_rms_eps, F, CH, hn, stream);
-            conv(gemm(hn, F, CH, L.up, nullptr, FF, ub));
-            { ConvArgs a = gemm(hn, F, CH, L.gate, nullptr, FF, gb); a.act = 2; a.mul = ub; conv(a); }
-            { ConvArgs a = gemm(gb, F, FF, L.down, nullptr, CH, h); a.res_scale = L.mlp_scale; a.res = h; conv(a); }
+                launch_attn(codec_attn_args(c, qkvb, att, kc, vc, W.page_table, pshift, 0, 1, F), stream);
+            }, stream);
+            launch_rmsnorm_rows(h, W.norm, c.cd_rms_eps, F, CH, h, stream);
         }
-        if (!plan && !h_in) launch_rmsnorm_rows(h, W.norm, c.cd_rms_eps, F, CH, h, stream);
         // ---- ConvNeXt upsampling stages ----
         float* cur = h_in ? const_cast<float*>(h_in) : h;
         int Tc = F;
@@ -430,12 +481,10 @@ int64_t Engine::codec_run(const int32_t* codes_dev, int F, float** pcm_dev, int 
           a.taps = 7; a.clamp = 1; conv(a); }
         if (!plan && nbatch > 1) { W.dbg_sx = sx; W.dbg_pcm = pcm; W.dbg_T = Tc; W.dbg_C = C; W.dbg_nb = nbatch; }
         n_pcm = Tc;
-        if (plan && off > W.arena_bytes[lane]) {
-            Q3_HIP_CHECK(hipStreamSynchronize(stream));
-            if (W.arena[lane]) (void)hipFree(W.arena[lane]);
-            W.arena[lane] = nullptr;
-            Q3_HIP_CHECK(hipMalloc((void**)&W.arena[lane], off));
-            W.arena_bytes[lane] = off;
+        if (plan && take.off > W.arena_bytes[lane]) {
+            Q3_HIP_CHECK(hipStreamSynchronize(stream));   // the lane's stream, not the engine's
+            W.dbg_sx = W.dbg_pcm = nullptr;               // they may point into the arena that goes
+            regrow(W.arena[lane], W.arena_bytes[lane], take.off, 1, true);
         }
     }
     *pcm_dev = pcm;
@@ -447,8 +496,7 @@ int64_t Engine::codec_run(const int32_t* codes_dev, int F, float** pcm_dev, int 
 // expands on its own), the depthwise causal conv stops at each sequence's first row, the pointwise layers are plain GEMMs.  take(n)
 // hands out n floats of the caller's arena, conv(a) launches with the caller's slab and weight planes.  Shared by codec_pre_batch (whole
 // utterances) and the batched push (the streams' windows).  *per leaves as the rows per sequence of the result.
-template <class Take, class Conv>
-static float* upsample_blocks(const q3tts_config& c, const CodecW& W, float* cur, int T, int* per, Take&& take, Conv&& conv, hipStream_t stream) {
+static float* upsample_blocks(const q3tts_config& c, const CodecW& W, float* cur, int T, int* per, CodecBump& take, const ConvLauncher& conv, hipStream_t stream) {
     const int CH = c.cd_hidden;
     int Tc = T;
     for (int s2 = 0; s2 < c.cd_n_up; ++s2) {
@@ -485,36 +533,15 @@ const float* Engine::codec_pre_batch(const int32_t* codes_dev, int codes_stride_
     while (P < Fp) { P <<= 1; ++pshift; }
     if (W.rope_P < P) throw Error("codec_pre_batch: RoPE tables not prepared");
     const size_t rows = (size_t)n * Fp;
-    auto bytes_of = [](size_t nfloat) { return (nfloat * sizeof(float) + 255) & ~(size_t)255; };
-    const size_t kslab_floats = (size_t)32 * 128 * 4096;
-    size_t need = bytes_of(rows * CH) * 3 + bytes_of(rows * 3 * CH) + bytes_of(rows * FF) * 2 + bytes_of((size_t)n * NH * P * HD) * 2 + bytes_of(kslab_floats);
-    if (with_upsampling) {   // per stage: y, ln (CH each) and the 4x wide hidden, at the stage's output rate
-        size_t r = rows;
-        for (int s2 = 0; s2 < c.cd_n_up; ++s2) { r *= (size_t)c.cd_up_ratios[s2]; need += bytes_of(r * CH) * 2 + bytes_of(r * 4 * CH); }
-    }
-    if (W.batch_arena_bytes < need) {
-        sync();
-        if (W.batch_arena) (void)hipFree(W.batch_arena);
-        W.batch_arena = nullptr;
-        Q3_HIP_CHECK(hipMalloc((void**)&W.batch_arena, need));
-        W.batch_arena_bytes = need;
-    }
-    if (W.batch_pages_n < n) {   // [0, n): identity page table; [n_cap, 2 n_cap): the job's utterance order (perm)
-        sync();
-        if (W.batch_pages) (void)hipFree(W.batch_pages);
-        std::vector<int> idt((size_t)n);
-        for (int i = 0; i < n; ++i) idt[(size_t)i] = i;
-        Q3_HIP_CHECK(hipMalloc((void**)&W.batch_pages, (size_t)2 * n * sizeof(int)));
-        Q3_HIP_CHECK(hipMemcpy(W.batch_pages, idt.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-        W.batch_pages_n = n;
-    }
+    const size_t need = codec_batch_arena_bytes(c, (size_t)n, (size_t)Fp, (size_t)P, with_upsampling);
+    if (W.batch_arena_bytes < need) regrow(W.batch_arena, W.batch_arena_bytes, need);
+    codec_identity_pages(*this, n);   // [0, n): identity page table; [n_cap, 2 n_cap): the job's utterance order (perm)
     const int* perm_d = nullptr;
     if (perm_host) {   // row block y of every buffer holds utterance perm[y] (the scheduler sorts by length so that decoder groups pad little)
         Q3_HIP_CHECK(hipMemcpyAsync(W.batch_pages + W.batch_pages_n, perm_host, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream));
         perm_d = W.batch_pages + W.batch_pages_n;
     }
-    size_t off = 0;
-    auto take = [&](size_t nfloat) { float* p = (float*)(W.batch_arena + off); off += bytes_of(nfloat); return p; };
+    CodecBump take{ W.batch_arena };
     float* h = take(rows * CH);
     float* hn = take(rows * CH);
     float* att = take(rows * CH);
@@ -523,38 +550,14 @@ const float* Engine::codec_pre_batch(const int32_t* codes_dev, int codes_stride_
     float* gb = take(rows * FF);
     float* kc = take((size_t)n * NH * P * HD);
     float* vc = take((size_t)n * NH * P * HD);
-    float* kslab = take(kslab_floats);
+    const ConvLauncher conv{ W, take(CODEC_KSLAB_FLOATS), stream };
     const int T = (int)rows;
     if (!W.win0_recorded) { Q3_HIP_CHECK(hipEventRecord(W.win0, stream)); W.win0_recorded = true; }   // the vocoder window starts here
-    auto conv = [&](ConvArgs a) {
-        a.slab = kslab; a.slab_floats = kslab_floats;
-        const auto it = W.planes.find(a.W);
-        if (it != W.planes.end()) { a.Wh = it->second.hi; a.Wl = it->second.lo; a.Whc = it->second.cm; a.w_scale_inv = it->second.scale_inv; a.w_lo_zero = it->second.lo_zero; }
-        if (a.snake_alpha) { const auto sp = W.snake_pre.find(a.snake_alpha); if (sp != W.snake_pre.end()) a.snake_pre = sp->second; }
-        launch_conv(a, stream);
-    };
-    auto gemm = [&](const float* in, int Cin, const float* Wm, int Cout, float* out) {
-        ConvArgs a; a.in = in; a.T_in = T; a.C_in = Cin; a.out = out; a.T_out = T; a.C_out = Cout; a.W = Wm;
-        return a;
-    };
     launch_code_embed_mean(W.code_embed, codes_dev, Fp, c.n_groups, c.cd_codebook, CH, h, stream, n, (size_t)codes_stride_frames * c.n_groups, perm_d);
-    for (int l = 0; l < c.cd_layers; ++l) {
-        const CodecW::Layer& L = W.layers[l];
-        launch_rmsnorm_rows(h, L.in_norm, c.cd_rms_eps, T, CH, hn, stream);
-        conv(gemm(hn, CH, L.qkv, 3 * CH, qkvb));
+    pre_transformer_layers(c, W, T, PreBufs{ h, hn, att, qkvb, ub, gb }, conv, [&](int) {
         launch_rope_store(qkvb, 3 * CH, Fp, NH, NH, HD, W.rope_cos, W.rope_sin, kc, vc, P, stream, n);
-        AttnArgs a;
-        a.qkv = qkvb; a.ld_qkv = 3 * CH; a.out = att; a.ld_out = CH; a.kcache = kc; a.vcache = vc;
-        a.page_table = W.batch_pages; a.pages_per_slot = 1; a.page_shift = pshift; a.layer = 0; a.n_layers = 1;
-        a.pos_scalar = 0; a.slot_offset = 0; a.nb = n; a.n_new = Fp; a.nq = NH; a.nkv = NH; a.d = HD;
-        a.scale = 1.0f / sqrtf((float)HD); a.window = c.cd_window; a.new_from_raw = 0;
-        launch_attn(a, stream);
-        { ConvArgs g = gemm(att, CH, L.o, CH, h); g.res_scale = L.attn_scale; g.res = h; conv(g); }
-        launch_rmsnorm_rows(h, L.post_norm, c.cd_rms_eps, T, CH, hn, stream);
-        conv(gemm(hn, CH, L.up, FF, ub));
-        { ConvArgs g = gemm(hn, CH, L.gate, FF, gb); g.act = 2; g.mul = ub; conv(g); }
-        { ConvArgs g = gemm(gb, FF, L.down, CH, h); g.res_scale = L.mlp_scale; g.res = h; conv(g); }
-    }
+        launch_attn(codec_attn_args(c, qkvb, att, kc, vc, W.batch_pages, pshift, 0, n, Fp), stream);
+    }, stream);
     launch_rmsnorm_rows(h, W.norm, c.cd_rms_eps, T, CH, h, stream);
     if (rows_per_utt_out) *rows_per_utt_out = Fp;
     if (!with_upsampling) return h;
@@ -606,12 +609,7 @@ void Engine::codec_async_prepare(int max_frames, int n_utt) {
         (void)hipFree(tmp);
     }
     const size_t need = (size_t)n_utt * max_frames * c.n_groups;
-    if (W.job_codes_n < need) {
-        sync();
-        if (W.job_codes) (void)hipFree(W.job_codes);
-        Q3_HIP_CHECK(hipMalloc((void**)&W.job_codes, need * sizeof(int32_t)));
-        W.job_codes_n = need;
-    }
+    if (W.job_codes_n < need) regrow(W.job_codes, W.job_codes_n, need);
     W.rr = 0;   // a job's first utterances always land on the same lanes (their arenas are already sized)
     W.win0_recorded = false;
     if (!W.fork) { Q3_HIP_CHECK(hipEventCreateWithFlags(&W.fork, hipEventDisableTiming)); Q3_HIP_CHECK(hipEventCreate(&W.win0)); Q3_HIP_CHECK(hipEventCreate(&W.win1)); }
@@ -670,11 +668,7 @@ void Engine::codec_async_submit_dev(const int32_t* codes_dev, int nf, float* use
     float* pcm_d = nullptr;
     const int64_t n = codec_run(codes_dev, nf, &pcm_d, lane, h_in, h_stage);
     const int64_t m = std::min(n, cap);
-    if ((size_t)m > W.pinned_floats[lane]) {
-        if (W.pinned[lane]) (void)hipHostFree(W.pinned[lane]);
-        Q3_HIP_CHECK(hipHostMalloc((void**)&W.pinned[lane], (size_t)m * sizeof(float)));
-        W.pinned_floats[lane] = (size_t)m;
-    }
+    if ((size_t)m > W.pinned_floats[lane]) regrow_pinned(W.pinned[lane], W.pinned_floats[lane], (size_t)m);
     if (m > 0) Q3_HIP_CHECK(hipMemcpyAsync(W.pinned[lane], pcm_d, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, ls));
     Q3_HIP_CHECK(hipEventRecord(W.lane_done[lane], ls));
     CodecW::Pending& p = W.pend[lane];
@@ -693,19 +687,7 @@ void Engine::codec_async_submit_dev(const int32_t* codes_dev, int nf, float* use
 // range decode does for the whole network.  Work per push: O(n + context), exact (same kernels as the one-shot decode on the same rows;
 // only the GEMM tile shapes a short launch picks differ).
 // ------------------------------------------------------------------------------------------------
-int Engine::codec_stage_b_context() const {
-    // frames the stages behind the pre-transformer look back, from the config: rows of lookback at each layer's rate / rows per frame
-    double frames = 0.0, rate = 1.0;
-    for (int s = 0; s < c.cd_n_up; ++s) { rate *= c.cd_up_ratios[s]; frames += 6.0 / rate; }            // ConvNeXt: depthwise causal k7 at the stage's output rate
-    frames += 6.0 / rate;                                                                                    // conv_in k7
-    for (int i = 0; i < c.cd_n_blocks; ++i) {
-        frames += 1.0 / rate;                                                                                // transposed conv k = 2 r: one input row back
-        rate *= c.cd_up_rates[i];
-        frames += 6.0 * (1 + 3 + 9) / rate;                                                                  // three 7-tap convs, dilations 1, 3, 9
-    }
-    frames += 6.0 / rate;                                                                                    // conv_out k7
-    return (int)frames + 3;                                                                                  // + margin for the transposed convs' trimming
-}
+int Engine::codec_stage_b_context() const { return q3::codec_stage_b_context(c); }
 
 int Engine::codec_stream_begin(int max_frames) {
     if (!codec) throw Error("codec decoder not finalized");
@@ -841,97 +823,52 @@ int64_t Engine::codec_stream_push_dev(int sid, const int32_t* codes_dev, int n, 
     const int a0 = S.n_done, b0 = a0 + n, T = n;
     codec_stream_fit(sid, n);
     const int k0 = S.kv_rows, h0 = S.h_rows;   // where this push's rows go in the sliding buffers (position a0 = K / V row k0 = hpost row h0)
-    auto bytes_of = [](size_t nfloat) { return (nfloat * sizeof(float) + 255) & ~(size_t)255; };
-    const size_t kslab_floats = (size_t)32 * 128 * 4096;
-    const size_t need = bytes_of((size_t)T * CH) * 3 + bytes_of((size_t)T * 3 * CH) + bytes_of((size_t)T * FF) * 2 + bytes_of(kslab_floats);
-    if (W.stream_arena_bytes < need) {
-        sync();
-        if (W.stream_arena) (void)hipFree(W.stream_arena);
-        W.stream_arena = nullptr;
-        Q3_HIP_CHECK(hipMalloc((void**)&W.stream_arena, need));
-        W.stream_arena_bytes = need;
-    }
-    size_t off = 0;
-    auto take = [&](size_t nfloat) { float* p = (float*)(W.stream_arena + off); off += bytes_of(nfloat); return p; };
+    const size_t need = codec_stream_arena_bytes(c, (size_t)T);
+    if (W.stream_arena_bytes < need) regrow(W.stream_arena, W.stream_arena_bytes, need);
+    CodecBump take{ W.stream_arena };
     float* h = take((size_t)T * CH);
     float* hn = take((size_t)T * CH);
     float* att = take((size_t)T * CH);
     float* qkvb = take((size_t)T * 3 * CH);
     float* ub = take((size_t)T * FF);
     float* gb = take((size_t)T * FF);
-    float* kslab = take(kslab_floats);
-    auto conv = [&](ConvArgs a) {
-        a.slab = kslab; a.slab_floats = kslab_floats;
-        const auto it = W.planes.find(a.W);
-        if (it != W.planes.end()) { a.Wh = it->second.hi; a.Wl = it->second.lo; a.Whc = it->second.cm; a.w_scale_inv = it->second.scale_inv; a.w_lo_zero = it->second.lo_zero; }
-        launch_conv(a, stream);
-    };
-    auto gemm = [&](const float* in, int Cin, const float* Wm, int Cout, float* out) {
-        ConvArgs a; a.in = in; a.T_in = T; a.C_in = Cin; a.out = out; a.T_out = T; a.C_out = Cout; a.W = Wm;
-        return a;
-    };
+    const ConvLauncher conv{ W, take(CODEC_KSLAB_FLOATS), stream };
     // ---- the pre-transformer on the new rows: positions [a0, b0), keys / values of earlier frames from the stream's caches ----
     const int half = HD / 2;
     const size_t layer_kv = (size_t)NH * S.P * HD;
     launch_code_embed_mean(W.code_embed, codes_dev, T, c.n_groups, c.cd_codebook, CH, h, stream);
-    for (int l = 0; l < c.cd_layers; ++l) {
-        const CodecW::Layer& L = W.layers[l];
+    pre_transformer_layers(c, W, T, PreBufs{ h, hn, att, qkvb, ub, gb }, conv, [&](int l) {
         float* kc = S.kv + (size_t)l * 2 * layer_kv;
         float* vc = kc + layer_kv;
-        launch_rmsnorm_rows(h, L.in_norm, c.cd_rms_eps, T, CH, hn, stream);
-        conv(gemm(hn, CH, L.qkv, 3 * CH, qkvb));
         // row t of this push is position a0 + t: the tables and the cache rows start there
         launch_rope_store(qkvb, 3 * CH, T, NH, NH, HD, W.rope_cos + (size_t)a0 * half, W.rope_sin + (size_t)a0 * half, kc + (size_t)k0 * HD, vc + (size_t)k0 * HD, S.P, stream);
-        AttnArgs a;
-        a.qkv = qkvb; a.ld_qkv = 3 * CH; a.out = att; a.ld_out = CH; a.kcache = kc; a.vcache = vc;
-        a.page_table = W.page_table; a.pages_per_slot = 1; a.page_shift = S.pshift; a.layer = 0; a.n_layers = 1;
-        a.pos_scalar = k0;   // cache rows are addressed relative to the sliding buffer; every row a window can reach is in it (RoPE is already applied, absolute)
-        a.slot_offset = 0; a.nb = 1; a.n_new = T; a.nq = NH; a.nkv = NH; a.d = HD;
-        a.scale = 1.0f / sqrtf((float)HD); a.window = c.cd_window; a.new_from_raw = 0;
-        launch_attn(a, stream);
-        { ConvArgs g = gemm(att, CH, L.o, CH, h); g.res_scale = L.attn_scale; g.res = h; conv(g); }
-        launch_rmsnorm_rows(h, L.post_norm, c.cd_rms_eps, T, CH, hn, stream);
-        conv(gemm(hn, CH, L.up, FF, ub));
-        { ConvArgs g = gemm(hn, CH, L.gate, FF, gb); g.act = 2; g.mul = ub; conv(g); }
-        { ConvArgs g = gemm(gb, FF, L.down, CH, h); g.res_scale = L.mlp_scale; g.res = h; conv(g); }
-    }
+        // pos_scalar = k0: cache rows are addressed relative to the sliding buffer; every row a window can reach is in it (RoPE is already applied, absolute)
+        launch_attn(codec_attn_args(c, qkvb, att, kc, vc, W.page_table, S.pshift, k0, 1, T), stream);
+    }, stream);
     launch_rmsnorm_rows(h, W.norm, c.cd_rms_eps, T, CH, S.hpost + (size_t)h0 * CH, stream);
     // ---- everything behind the transformer over the window [sB, b0) of its kept output rows ----
     const int sB = std::max(0, a0 - codec_stage_b_context());   // h0 >= a0 - sB: codec_stream_fit keeps that many rows
-    int64_t up = 1;
-    for (int i = 0; i < c.cd_n_up; ++i) up *= c.cd_up_ratios[i];
-    for (int i = 0; i < c.cd_n_blocks; ++i) up *= c.cd_up_rates[i];
-    auto len_of = [&](int nfr) -> int64_t { return nfr <= 0 ? 0 : q3tts_codec_decode_len(&c, nfr); };
-    const int64_t first = len_of(a0) - up * sB, n_own = len_of(b0) - len_of(a0);
+    const CodecCut cut = codec_window_cut(c, a0, n, a0 - sB);
     float* pcm_d = nullptr;
     if (h0 < a0 - sB) throw Error("codec_stream_push: the kept transformer rows do not cover the look-back window");
     const int64_t n_win = codec_run(nullptr, b0 - sB, &pcm_d, 0, S.hpost + (size_t)(h0 - (a0 - sB)) * CH, 1);
-    if (first < 0 || first + n_own != n_win) throw Error("codec_stream_push: window arithmetic does not match the decoder length formula");
-    S.n_done = b0; S.kv_rows = k0 + n; S.h_rows = h0 + n; S.delivered = S.delivered || n_own > 0;
-    if (pcm_dev) *pcm_dev = pcm_d + first;
-    return n_own;
+    if (!cut.matches(n_win)) throw Error("codec_stream_push: window arithmetic does not match the decoder length formula");
+    S.n_done = b0; S.kv_rows = k0 + n; S.h_rows = h0 + n; S.delivered = S.delivered || cut.n_own > 0;
+    if (pcm_dev) *pcm_dev = pcm_d + cut.first;
+    return cut.n_own;
 }
 
 int64_t Engine::codec_stream_push_host(int sid, const int64_t* codes, int n, float* pcm, int64_t cap) {
     if (n < 1) throw Error("codec_stream_push: no frames");
-    const int G = c.n_groups;
-    std::vector<int32_t> tmp((size_t)n * G);
-    for (size_t i = 0; i < tmp.size(); ++i) {
-        if (codes[i] < 0 || codes[i] >= c.cd_codebook) throw Error("codec_decode: code out of range");
-        tmp[i] = (int32_t)codes[i];
-    }
+    std::vector<int32_t> tmp((size_t)n * c.n_groups);
+    stage_codes<Error>(codes, tmp.size(), c.cd_codebook, tmp.data());
     if (n > max_frames_cap) throw Error("codec_stream_push: more frames in one push than the engine's frame capacity");
     Q3_HIP_CHECK(hipMemcpyAsync(codes_scratch_d, tmp.data(), tmp.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     float* pcm_d = nullptr;
-    Q3_HIP_CHECK(hipEventRecord(ev0, stream));
+    CodecTimed t(*this);
     const int64_t n_own = codec_stream_push_dev(sid, codes_scratch_d, n, &pcm_d);
-    Q3_HIP_CHECK(hipEventRecord(ev1, stream));
-    const int64_t m = std::min(n_own, cap);
-    if (m > 0 && pcm) Q3_HIP_CHECK(hipMemcpyAsync(pcm, pcm_d, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, stream));
-    sync();
-    Q3_HIP_CHECK(hipEventElapsedTime(&last_codec_ms, ev0, ev1));
-    total_codec_ms += last_codec_ms; total_codec_frames += n;
-    return n_own;
+    t.stop();
+    return t.deliver(pcm_d, n_own, pcm, cap, n);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -967,7 +904,6 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
     }
     // streams with stages: their pushes' lengths by the host rules (which refuse a finished or full stage), before anything moves.  A
     // stage's input is the push of the stream's nearest earlier stage, or the vocoder's; only the last one delivers to the caller.
-    auto len_all = [&](int nfr) -> int64_t { return nfr <= 0 ? 0 : q3tts_codec_decode_len(&c, nfr); };
     std::vector<StagePush> sp[SK_N];             // sp[k][i] belongs to ps[i]; id == -1: stream i has no stage of kind k
     size_t st_out[SK_N] = {}, st_offs[SK_N] = {};
     int st_n[SK_N] = {}, st_any = 0;
@@ -975,7 +911,7 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
     for (int i = 0; i < g_all; ++i) {
         const StreamPush& q = ps[i];
         const CodecW::Stream& S = W.streams[(size_t)q.sid];
-        int64_t n24 = len_all(S.n_done + q.n) - len_all(S.n_done);
+        int64_t n24 = codec_len_of(c, S.n_done + q.n) - codec_len_of(c, S.n_done);
         int last = -1;
         for (int k = 0; k < SK_N; ++k) {
             if (S.stage[k] < 0) continue;
@@ -1038,9 +974,7 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
     }
     if (g > 65535) throw Error("codec_stream_push_batch: at most 65535 streams per call");
     const int ctxB = codec_stage_b_context();
-    // group key: left-context length min(a0, ctxB); mature streams (the common case) first
-    std::stable_sort(live.begin(), live.end(), [&](int x, int y) {
-        return std::min(W.streams[(size_t)ps[x].sid].n_done, ctxB) > std::min(W.streams[(size_t)ps[y].sid].n_done, ctxB); });
+    codec_push_order(live, [&](int x) { return std::min(W.streams[(size_t)ps[x].sid].n_done, ctxB); });   // mature streams (the common case) first
     std::vector<CodecStreamDesc>& D = W.sbatch_desc_h;
     D.assign((size_t)g, CodecStreamDesc());
     int T = 0, n_max = 0;
@@ -1056,104 +990,50 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
         if (W.rope_P < d.a0 + d.n) throw Error("codec_stream_push_batch: RoPE tables not prepared");
         T += q.n; n_max = std::max(n_max, q.n);
     }
-    // groups [i0, i1) of equal left context, cut so that a group's conv decoder stays inside ~16 GB of workspace (4.7 MB per frame at 0.6B dims)
-    struct Group { int i0, i1, Tw; };
-    std::vector<Group> groups;
-    int64_t up_front = 1, up = 1;
-    for (int i = 0; i < c.cd_n_up; ++i) up_front *= c.cd_up_ratios[i];
-    up = up_front;
-    for (int i = 0; i < c.cd_n_blocks; ++i) up *= c.cd_up_rates[i];
+    const std::vector<CodecGroup> groups = codec_push_groups(g, [&](int i) { return D[(size_t)i].ctx; }, [&](int i) { return D[(size_t)i].n; });
     size_t back_rows = 0;   // rows of the largest group's gathered block
-    for (int i0 = 0; i0 < g;) {
-        int i1 = i0, Tw = 0;
-        while (i1 < g && D[(size_t)i1].ctx == D[(size_t)i0].ctx) {
-            const int Tw1 = std::max(Tw, D[(size_t)i1].ctx + D[(size_t)i1].n);
-            if (i1 > i0 && (int64_t)(i1 - i0 + 1) * Tw1 * 4700000 > ((int64_t)16 << 30)) break;
-            Tw = Tw1; ++i1;
-        }
-        for (int i = i0; i < i1; ++i) D[(size_t)i].blk = i - i0;
-        groups.push_back(Group{ i0, i1, Tw });
-        back_rows = std::max(back_rows, (size_t)(i1 - i0) * Tw);
-        i0 = i1;
+    for (const CodecGroup& G : groups) {
+        for (int i = G.i0; i < G.i1; ++i) D[(size_t)i].blk = i - G.i0;
+        back_rows = std::max(back_rows, (size_t)(G.i1 - G.i0) * G.Tw);
     }
     // ---- workspace ----
-    auto bytes_of = [](size_t nfloat) { return (nfloat * sizeof(float) + 255) & ~(size_t)255; };
-    const size_t kslab_floats = (size_t)32 * 128 * 4096;
-    size_t need = bytes_of((size_t)T * CH) * 3 + bytes_of((size_t)T * 3 * CH) + bytes_of((size_t)T * FF) * 2 + bytes_of(kslab_floats) + bytes_of(back_rows * CH);
-    { size_t r = back_rows; for (int s2 = 0; s2 < c.cd_n_up; ++s2) { r *= (size_t)c.cd_up_ratios[s2]; need += bytes_of(r * CH) * 2 + bytes_of(r * 4 * CH); } }
-    if (W.sbatch_arena_bytes < need) {
-        sync();
-        if (W.sbatch_arena) (void)hipFree(W.sbatch_arena);
-        W.sbatch_arena = nullptr; W.sbatch_arena_bytes = 0;
-        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_arena, need));
-        W.sbatch_arena_bytes = need;
-    }
-    if (W.sbatch_desc_n < (size_t)g) {
-        sync();
-        if (W.sbatch_desc) (void)hipFree(W.sbatch_desc);
-        W.sbatch_desc = nullptr; W.sbatch_desc_n = 0;
-        const size_t cap = std::max((size_t)64, (size_t)g);
-        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_desc, cap * sizeof(CodecStreamDesc)));
-        W.sbatch_desc_n = cap;
-    }
+    const size_t need = codec_sbatch_push_bytes(c, (size_t)T, back_rows);
+    if (W.sbatch_arena_bytes < need) regrow(W.sbatch_arena, W.sbatch_arena_bytes, need);
+    if (W.sbatch_desc_n < (size_t)g) regrow(W.sbatch_desc, W.sbatch_desc_n, std::max((size_t)64, (size_t)g));
     Q3_HIP_CHECK(hipMemcpyAsync(W.sbatch_desc, D.data(), (size_t)g * sizeof(CodecStreamDesc), hipMemcpyHostToDevice, stream));
-    size_t off = 0;
-    auto take = [&](size_t nfloat) { float* p = (float*)(W.sbatch_arena + off); off += bytes_of(nfloat); return p; };
+    CodecBump take{ W.sbatch_arena };
     float* h = take((size_t)T * CH);
     float* hn = take((size_t)T * CH);
     float* att = take((size_t)T * CH);
     float* qkvb = take((size_t)T * 3 * CH);
     float* ub = take((size_t)T * FF);
     float* gb = take((size_t)T * FF);
-    float* kslab = take(kslab_floats);
+    const ConvLauncher conv{ W, take(CODEC_KSLAB_FLOATS), stream };
     float* win = take(back_rows * CH);
-    const size_t off_back = off;
-    auto conv = [&](ConvArgs a) {
-        a.slab = kslab; a.slab_floats = kslab_floats;
-        const auto it = W.planes.find(a.W);
-        if (it != W.planes.end()) { a.Wh = it->second.hi; a.Wl = it->second.lo; a.Whc = it->second.cm; a.w_scale_inv = it->second.scale_inv; a.w_lo_zero = it->second.lo_zero; }
-        launch_conv(a, stream);
-    };
-    auto gemm = [&](const float* in, int Cin, const float* Wm, int Cout, float* out) {
-        ConvArgs a; a.in = in; a.T_in = T; a.C_in = Cin; a.out = out; a.T_out = T; a.C_out = Cout; a.W = Wm;
-        return a;
-    };
+    const size_t off_back = take.off;
     Q3_HIP_CHECK(hipEventRecord(ev0, stream));
     // ---- the pre-transformer on all streams' new rows ----
     const CodecStreamDesc* dd = W.sbatch_desc;
     const bool win_attn = attn_streams_windowed(NH, HD, c.cd_window, 3 * CH, CH);
     launch_code_embed_mean_streams(W.code_embed, dd, g, n_max, c.n_groups, c.cd_codebook, CH, h, stream);
-    for (int l = 0; l < c.cd_layers; ++l) {
-        const CodecW::Layer& L = W.layers[l];
-        launch_rmsnorm_rows(h, L.in_norm, c.cd_rms_eps, T, CH, hn, stream);
-        conv(gemm(hn, CH, L.qkv, 3 * CH, qkvb));
+    pre_transformer_layers(c, W, T, PreBufs{ h, hn, att, qkvb, ub, gb }, conv, [&](int l) {
         launch_rope_store_streams(qkvb, 3 * CH, dd, g, n_max, l, NH, NH, HD, W.rope_cos, W.rope_sin, stream);
         if (win_attn) launch_attn_streams(qkvb, 3 * CH, att, CH, dd, g, n_max, l, NH, HD, c.cd_window, 1.0f / sqrtf((float)HD), stream);
         else for (int i = 0; i < g; ++i) {   // head sizes k_attn_win does not take (tiny configs): k_attn, exactly the single push's launch
             const CodecStreamDesc& d = D[(size_t)i];
-            AttnArgs a;
-            a.qkv = qkvb + (size_t)d.row_off * 3 * CH; a.ld_qkv = 3 * CH; a.out = att + (size_t)d.row_off * CH; a.ld_out = CH;
-            a.kcache = d.kv + (size_t)l * 2 * NH * d.P * HD; a.vcache = a.kcache + (size_t)NH * d.P * HD;
-            a.page_table = W.page_table; a.pages_per_slot = 1; a.page_shift = W.streams[(size_t)ps[live[(size_t)i]].sid].pshift; a.layer = 0; a.n_layers = 1;
-            a.pos_scalar = d.k0; a.slot_offset = 0; a.nb = 1; a.n_new = d.n; a.nq = NH; a.nkv = NH; a.d = HD;
-            a.scale = 1.0f / sqrtf((float)HD); a.window = c.cd_window; a.new_from_raw = 0;
-            launch_attn(a, stream);
+            float* kc = d.kv + (size_t)l * 2 * NH * d.P * HD;
+            launch_attn(codec_attn_args(c, qkvb + (size_t)d.row_off * 3 * CH, att + (size_t)d.row_off * CH, kc, kc + (size_t)NH * d.P * HD, W.page_table,
+                                        W.streams[(size_t)ps[live[(size_t)i]].sid].pshift, d.k0, 1, d.n), stream);
         }
-        { ConvArgs a = gemm(att, CH, L.o, CH, h); a.res_scale = L.attn_scale; a.res = h; conv(a); }
-        launch_rmsnorm_rows(h, L.post_norm, c.cd_rms_eps, T, CH, hn, stream);
-        conv(gemm(hn, CH, L.up, FF, ub));
-        { ConvArgs a = gemm(hn, CH, L.gate, FF, gb); a.act = 2; a.mul = ub; conv(a); }
-        { ConvArgs a = gemm(gb, FF, L.down, CH, h); a.res_scale = L.mlp_scale; a.res = h; conv(a); }
-    }
+    }, stream);
     launch_rmsnorm_rows_streams(h, W.norm, c.cd_rms_eps, dd, g, n_max, CH, stream);
     // ---- everything behind the transformer, one group of equal left context at a time ----
-    auto len_of = [&](int nfr) -> int64_t { return nfr <= 0 ? 0 : q3tts_codec_decode_len(&c, nfr); };
     const bool batchable = codec_batchable();
     for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const Group& G = groups[gi];
+        const CodecGroup& G = groups[gi];
         const int gk = G.i1 - G.i0;
         launch_gather_stream_rows(dd + G.i0, gk, G.Tw, CH, win, stream);
-        off = off_back;
+        take.off = off_back;
         int per = G.Tw;
         const float* hup = upsample_blocks(c, W, win, gk * G.Tw, &per, take, conv, stream);
         const size_t ustride = (size_t)per * CH;
@@ -1161,8 +1041,9 @@ void Engine::codec_stream_push_batch(StreamPush* ps, int g_all) {
         auto deliver = [&](int i, const float* pcm_seq, int64_t Tp) {   // stream i's own samples out of its window's
             const CodecStreamDesc& d = D[(size_t)i];
             StreamPush& q = ps[live[(size_t)i]];
-            const int64_t first = len_of(d.a0) - up * (d.a0 - d.ctx), n_own = len_of(d.a0 + d.n) - len_of(d.a0);
-            if (first < 0 || first + n_own > Tp || (d.ctx + d.n == G.Tw && first + n_own != Tp)) throw Error("codec_stream_push_batch: window arithmetic does not match the decoder length formula");
+            const CodecCut cut = codec_window_cut(c, d.a0, d.n, d.ctx);
+            const int64_t first = cut.first, n_own = cut.n_own;
+            if (!cut.matches(Tp, d.ctx + d.n == G.Tw)) throw Error("codec_stream_push_batch: window arithmetic does not match the decoder length formula");
             q.n_own = n_own;
             int k0 = 0;
             while (k0 < SK_N && sp[k0][(size_t)live[(size_t)i]].id < 0) ++k0;
@@ -1224,10 +1105,7 @@ void Engine::codec_stream_push_batch_host(int n_streams, const int32_t* sids, co
     const size_t total = (size_t)frame_offsets[n_streams] * G;
     if (total > 0 && !codes) throw Error("codec_stream_push_batch: null codes");
     std::vector<int32_t> tmp(total);
-    for (size_t i = 0; i < total; ++i) {
-        if (codes[i] < 0 || codes[i] >= c.cd_codebook) throw Error("codec_decode: code out of range");
-        tmp[i] = (int32_t)codes[i];
-    }
+    stage_codes<Error>(codes, total, c.cd_codebook, tmp.data());
     std::vector<StreamPush> ps((size_t)n_streams);
     for (int i = 0; i < n_streams; ++i) {   // the checks codec_stream_push_batch repeats, made here before the staging buffer may grow
         ps[(size_t)i].sid = sids[i]; ps[(size_t)i].n = frame_offsets[i + 1] - frame_offsets[i];
@@ -1237,13 +1115,7 @@ void Engine::codec_stream_push_batch_host(int n_streams, const int32_t* sids, co
             throw Error("codec_stream_push_batch: stream " + std::to_string(sids[i]) + W.streams[(size_t)sids[i]].has() + ": the float entry serves streams without one");
         if (pcm_len) pcm_len[i] = 0;
     }
-    if (W.sbatch_codes_n < total || !W.sbatch_codes) {
-        sync();
-        if (W.sbatch_codes) (void)hipFree(W.sbatch_codes);
-        W.sbatch_codes = nullptr; W.sbatch_codes_n = 0;
-        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_codes, std::max(total, (size_t)1) * sizeof(int32_t)));
-        W.sbatch_codes_n = total;
-    }
+    if (W.sbatch_codes_n < total || !W.sbatch_codes) regrow(W.sbatch_codes, W.sbatch_codes_n, std::max(total, (size_t)1));
     if (total > 0) Q3_HIP_CHECK(hipMemcpyAsync(W.sbatch_codes, tmp.data(), total * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     for (int i = 0; i < n_streams; ++i) ps[(size_t)i].codes_dev = W.sbatch_codes + (size_t)frame_offsets[i] * G;
     try { codec_stream_push_batch(ps.data(), n_streams); } catch (...) { try { sync(); } catch (...) { } throw; }   // tmp must outlive the upload
@@ -1357,37 +1229,12 @@ void Engine::codec_stream_prime_batch(const StreamPush* ps, int g_all) {
     // ---- workspace ----
     const size_t rows = (size_t)g * Fp;
     const int T = (int)rows;
-    auto bytes_of = [](size_t nfloat) { return (nfloat * sizeof(float) + 255) & ~(size_t)255; };
-    const size_t kslab_floats = (size_t)32 * 128 * 4096;
-    const size_t need = bytes_of(rows * CH) * 3 + bytes_of(rows * 3 * CH) + bytes_of(rows * FF) * 2 + bytes_of((size_t)g * NH * Ps * HD) * 2 + bytes_of(kslab_floats);
-    if (W.sbatch_arena_bytes < need) {
-        sync();
-        if (W.sbatch_arena) (void)hipFree(W.sbatch_arena);
-        W.sbatch_arena = nullptr; W.sbatch_arena_bytes = 0;
-        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_arena, need));
-        W.sbatch_arena_bytes = need;
-    }
-    if (W.sbatch_desc_n < (size_t)g) {
-        sync();
-        if (W.sbatch_desc) (void)hipFree(W.sbatch_desc);
-        W.sbatch_desc = nullptr; W.sbatch_desc_n = 0;
-        const size_t cap = std::max((size_t)64, (size_t)g);
-        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_desc, cap * sizeof(CodecStreamDesc)));
-        W.sbatch_desc_n = cap;
-    }
-    if (W.batch_pages_n < g) {   // identity page table, one scratch cache block per stream (codec_pre_batch's; [n_cap, 2 n_cap) is its perm area)
-        sync();
-        if (W.batch_pages) (void)hipFree(W.batch_pages);
-        W.batch_pages = nullptr; W.batch_pages_n = 0;
-        std::vector<int> idt((size_t)g);
-        for (int i = 0; i < g; ++i) idt[(size_t)i] = i;
-        Q3_HIP_CHECK(hipMalloc((void**)&W.batch_pages, (size_t)2 * g * sizeof(int)));
-        Q3_HIP_CHECK(hipMemcpy(W.batch_pages, idt.data(), (size_t)g * sizeof(int), hipMemcpyHostToDevice));
-        W.batch_pages_n = g;
-    }
+    const size_t need = codec_sbatch_prime_bytes(c, (size_t)g, (size_t)Fp, (size_t)Ps);
+    if (W.sbatch_arena_bytes < need) regrow(W.sbatch_arena, W.sbatch_arena_bytes, need);
+    if (W.sbatch_desc_n < (size_t)g) regrow(W.sbatch_desc, W.sbatch_desc_n, std::max((size_t)64, (size_t)g));
+    codec_identity_pages(*this, g);   // one scratch cache block per stream
     Q3_HIP_CHECK(hipMemcpyAsync(W.sbatch_desc, D.data(), (size_t)g * sizeof(CodecStreamDesc), hipMemcpyHostToDevice, stream));
-    size_t off = 0;
-    auto take = [&](size_t nfloat) { float* p = (float*)(W.sbatch_arena + off); off += bytes_of(nfloat); return p; };
+    CodecBump take{ W.sbatch_arena };
     float* h = take(rows * CH);
     float* hn = take(rows * CH);
     float* att = take(rows * CH);
@@ -1396,39 +1243,16 @@ void Engine::codec_stream_prime_batch(const StreamPush* ps, int g_all) {
     float* gb = take(rows * FF);
     float* kc = take((size_t)g * NH * Ps * HD);
     float* vc = take((size_t)g * NH * Ps * HD);
-    float* kslab = take(kslab_floats);
-    auto conv = [&](ConvArgs a) {
-        a.slab = kslab; a.slab_floats = kslab_floats;
-        const auto it = W.planes.find(a.W);
-        if (it != W.planes.end()) { a.Wh = it->second.hi; a.Wl = it->second.lo; a.Whc = it->second.cm; a.w_scale_inv = it->second.scale_inv; a.w_lo_zero = it->second.lo_zero; }
-        launch_conv(a, stream);
-    };
-    auto gemm = [&](const float* in, int Cin, const float* Wm, int Cout, float* out) {
-        ConvArgs a; a.in = in; a.T_in = T; a.C_in = Cin; a.out = out; a.T_out = T; a.C_out = Cout; a.W = Wm;
-        return a;
-    };
+    const ConvLauncher conv{ W, take(CODEC_KSLAB_FLOATS), stream };
     Q3_HIP_CHECK(hipEventRecord(ev0, stream));
     const CodecStreamDesc* dd = W.sbatch_desc;
     Q3_HIP_CHECK(hipMemsetAsync(h, 0, rows * CH * sizeof(float), stream));   // padding rows: zeros through every layer
     launch_code_embed_mean_streams(W.code_embed, dd, g, Fp, c.n_groups, c.cd_codebook, CH, h, stream);
-    for (int l = 0; l < c.cd_layers; ++l) {
-        const CodecW::Layer& L = W.layers[l];
-        launch_rmsnorm_rows(h, L.in_norm, c.cd_rms_eps, T, CH, hn, stream);
-        conv(gemm(hn, CH, L.qkv, 3 * CH, qkvb));
+    pre_transformer_layers(c, W, T, PreBufs{ h, hn, att, qkvb, ub, gb }, conv, [&](int l) {
         launch_rope_store(qkvb, 3 * CH, Fp, NH, NH, HD, W.rope_cos, W.rope_sin, kc, vc, Ps, stream, g);
         launch_prime_kv_tails(kc, vc, Ps, dd, g, l, NH, HD, keep, stream);
-        AttnArgs a;
-        a.qkv = qkvb; a.ld_qkv = 3 * CH; a.out = att; a.ld_out = CH; a.kcache = kc; a.vcache = vc;
-        a.page_table = W.batch_pages; a.pages_per_slot = 1; a.page_shift = pshift; a.layer = 0; a.n_layers = 1;
-        a.pos_scalar = 0; a.slot_offset = 0; a.nb = g; a.n_new = Fp; a.nq = NH; a.nkv = NH; a.d = HD;
-        a.scale = 1.0f / sqrtf((float)HD); a.window = c.cd_window; a.new_from_raw = 0;
-        launch_attn(a, stream);
-        { ConvArgs x = gemm(att, CH, L.o, CH, h); x.res_scale = L.attn_scale; x.res = h; conv(x); }
-        launch_rmsnorm_rows(h, L.post_norm, c.cd_rms_eps, T, CH, hn, stream);
-        conv(gemm(hn, CH, L.up, FF, ub));
-        { ConvArgs x = gemm(hn, CH, L.gate, FF, gb); x.act = 2; x.mul = ub; conv(x); }
-        { ConvArgs x = gemm(gb, FF, L.down, CH, h); x.res_scale = L.mlp_scale; x.res = h; conv(x); }
-    }
+        launch_attn(codec_attn_args(c, qkvb, att, kc, vc, W.batch_pages, pshift, 0, g, Fp), stream);
+    }, stream);
     launch_rmsnorm_rows(h, W.norm, c.cd_rms_eps, T, CH, hn, stream);
     launch_prime_row_tails(hn, dd, g, CH, ctxB, stream);
     Q3_HIP_CHECK(hipEventRecord(ev1, stream));
@@ -1455,10 +1279,7 @@ void Engine::codec_stream_prime_batch_host(int n_streams, const int32_t* sids, c
     const size_t total = (size_t)frame_offsets[n_streams] * G;
     if (total > 0 && !codes) throw Error("codec_stream_prime_batch: null codes");
     std::vector<int32_t> tmp(total);
-    for (size_t i = 0; i < total; ++i) {
-        if (codes[i] < 0 || codes[i] >= c.cd_codebook) throw Error("codec_decode: code out of range");
-        tmp[i] = (int32_t)codes[i];
-    }
+    stage_codes<Error>(codes, total, c.cd_codebook, tmp.data());
     std::vector<StreamPush> ps((size_t)n_streams);
     for (int i = 0; i < n_streams; ++i) {   // the checks codec_stream_prime_batch repeats, made here before the staging buffer may grow
         ps[(size_t)i].sid = sids[i]; ps[(size_t)i].n = frame_offsets[i + 1] - frame_offsets[i];
@@ -1467,13 +1288,7 @@ void Engine::codec_stream_prime_batch_host(int n_streams, const int32_t* sids, c
         if (W.streams[(size_t)sids[i]].n_done != 0) throw Error("codec_stream_prime_batch: stream already has frames");
         if (ps[(size_t)i].n > W.streams[(size_t)sids[i]].cap) throw Error("codec_stream_prime_batch: more frames than the stream was opened for");
     }
-    if (W.sbatch_codes_n < total) {
-        sync();
-        if (W.sbatch_codes) (void)hipFree(W.sbatch_codes);
-        W.sbatch_codes = nullptr; W.sbatch_codes_n = 0;
-        Q3_HIP_CHECK(hipMalloc((void**)&W.sbatch_codes, total * sizeof(int32_t)));
-        W.sbatch_codes_n = total;
-    }
+    if (W.sbatch_codes_n < total) regrow(W.sbatch_codes, W.sbatch_codes_n, total);
     if (total > 0) Q3_HIP_CHECK(hipMemcpyAsync(W.sbatch_codes, tmp.data(), total * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     for (int i = 0; i < n_streams; ++i) ps[(size_t)i].codes_dev = W.sbatch_codes + (size_t)frame_offsets[i] * G;
     try { codec_stream_prime_batch(ps.data(), n_streams); } catch (...) { try { sync(); } catch (...) { } throw; }   // tmp must outlive the upload
@@ -1533,15 +1348,10 @@ int64_t Engine::slot_codec_stream_range(int slot, int a, int b, float* pcm, int6
     CodecW::Stream& S = W.streams[(size_t)sid];
     if (S.n_done < a) codec_stream_push_dev(sid, codes + (size_t)S.n_done * c.n_groups, a - S.n_done, nullptr);   // frames nobody asked the audio of
     float* pcm_d = nullptr;
-    Q3_HIP_CHECK(hipEventRecord(ev0, stream));
+    CodecTimed t(*this);
     const int64_t n_own = codec_stream_push_dev(sid, codes + (size_t)a * c.n_groups, b - a, &pcm_d);
-    Q3_HIP_CHECK(hipEventRecord(ev1, stream));
-    const int64_t m = std::min(n_own, cap);
-    if (m > 0 && pcm) Q3_HIP_CHECK(hipMemcpyAsync(pcm, pcm_d, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, stream));
-    sync();
-    Q3_HIP_CHECK(hipEventElapsedTime(&last_codec_ms, ev0, ev1));
-    total_codec_ms += last_codec_ms; total_codec_frames += b - a;
-    return n_own;
+    t.stop();
+    return t.deliver(pcm_d, n_own, pcm, cap, b - a);
 }
 void Engine::slot_codec_stream_reset(int slot) {
     if (!codec) return;
@@ -1560,6 +1370,7 @@ void Engine::codec_poison() {
     if (!codec) return;
     CodecW& W = *codec;
     for (int i = 0; i < W.nlane; ++i) Q3_HIP_CHECK(hipStreamSynchronize(W.lane_stream[i]));
+    W.dbg_sx = W.dbg_pcm = nullptr;   // the last batched group's rows are gone with everything else
     for (int i = 0; i < CodecW::NLANE; ++i) {
         if (W.arena[i]) Q3_HIP_CHECK(hipMemset(W.arena[i], 0xFF, W.arena_bytes[i]));
         if (W.pinned[i]) memset(W.pinned[i], 0xFF, W.pinned_floats[i] * sizeof(float));
@@ -1578,7 +1389,7 @@ void Engine::codec_debug_group(float* sx_out, float* pcm_out, int64_t cap_floats
     if (!(flags & Q3TTS_FLAG_TEST_HOOKS)) throw Error("codec_debug_group needs Q3TTS_FLAG_TEST_HOOKS");
     CodecW& W = *codec;
     *T = W.dbg_T; *C = W.dbg_C; *nb = W.dbg_nb;
-    if (!W.dbg_sx) return;
+    if (!W.dbg_sx || !W.dbg_pcm) throw Error("codec_debug_group: no batched group's rows to read (none has run, or its lane's workspace was regrown or poisoned since)");
     Q3_HIP_CHECK(hipDeviceSynchronize());
     const int64_t n = (int64_t)W.dbg_nb * W.dbg_T * W.dbg_C;
     if (sx_out && n <= cap_floats) Q3_HIP_CHECK(hipMemcpy(sx_out, W.dbg_sx, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
@@ -1629,16 +1440,12 @@ void Engine::codec_async_submit_group(const float* h_group, size_t h_ustride, in
     int64_t total = 0;
     int frames = 0;
     for (int u = 0; u < g; ++u) {
-        const int64_t n = nf[u] > 0 ? q3tts_codec_decode_len(&c, nf[u]) : 0;
+        const int64_t n = codec_len_of(c, nf[u]);
         p.items.push_back(CodecW::Item{ user_pcm ? user_pcm[u] : nullptr, n, cap, total, len_out ? len_out[u] : nullptr });
         total += std::min(n, cap);
         frames += std::max(nf[u], 0);
     }
-    if ((size_t)total > W.pinned_floats[lane]) {
-        if (W.pinned[lane]) (void)hipHostFree(W.pinned[lane]);
-        Q3_HIP_CHECK(hipHostMalloc((void**)&W.pinned[lane], (size_t)total * sizeof(float)));
-        W.pinned_floats[lane] = (size_t)total;
-    }
+    if ((size_t)total > W.pinned_floats[lane]) regrow_pinned(W.pinned[lane], W.pinned_floats[lane], (size_t)total);
     for (int u = 0; u < g; ++u) {
         const CodecW::Item& it = p.items[(size_t)u];
         const int64_t m = std::min(it.n, it.cap);

@@ -1799,15 +1799,10 @@ int64_t Engine::slot_codec_decode(int slot, float* pcm, int64_t cap) {
     slot_status(slot, &nf, nullptr);
     if (nf <= 0) return 0; // reference returns an empty vector when no frame was generated (tts_onnx.cpp:418)
     float* pcm_d = nullptr;
-    Q3_HIP_CHECK(hipEventRecord(ev0, stream));
+    CodecTimed t(*this);
     const int64_t n = codec_run(codes_d + (size_t)slot * max_frames_cap * c.n_groups, nf, &pcm_d);
-    Q3_HIP_CHECK(hipEventRecord(ev1, stream));
-    const int64_t m = std::min(n, cap);
-    if (m > 0 && pcm) Q3_HIP_CHECK(hipMemcpyAsync(pcm, pcm_d, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, stream));
-    sync();
-    Q3_HIP_CHECK(hipEventElapsedTime(&last_codec_ms, ev0, ev1));
-    total_codec_ms += last_codec_ms; total_codec_frames += nf;
-    return n;
+    t.stop();
+    return t.deliver(pcm_d, n, pcm, cap, nf);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1818,28 +1813,18 @@ int64_t Engine::slot_codec_decode(int slot, float* pcm, int64_t cap) {
 // reference performs (tts_onnx.cpp:430) up to RoPE rounding; a shorter context trades exactness for bounded work
 // (transformers' chunked_decode uses 25 frames — and also drops L(1)-many samples per chunk, which this does not).
 // ------------------------------------------------------------------------------------------------
-static int64_t codec_len_of(const q3tts_config& c, int n) { return n <= 0 ? 0 : q3tts_codec_decode_len(&c, n); }
-
 int64_t Engine::codec_decode_range_dev(const int32_t* codes_dev, int a, int b, int left_context, float* pcm, int64_t cap) {
     if (!finalized) throw Error("weights not finalized");
     if (a < 0 || b <= a || b > max_frames_cap) throw Error("codec_decode_range: frame range out of range");
     if (left_context < 0) throw Error("codec_decode_range: negative left context");
     const int s = std::max(0, a - left_context);
-    int64_t up = 1;
-    for (int i = 0; i < c.cd_n_up; ++i) up *= c.cd_up_ratios[i];
-    for (int i = 0; i < c.cd_n_blocks; ++i) up *= c.cd_up_rates[i];
-    const int64_t first = codec_len_of(c, a) - up * s, n_own = codec_len_of(c, b) - codec_len_of(c, a);
+    const CodecCut cut = codec_window_cut(c, a, b - a, a - s);
     float* pcm_d = nullptr;
-    Q3_HIP_CHECK(hipEventRecord(ev0, stream));
+    CodecTimed t(*this);
     const int64_t n_win = codec_run(codes_dev + (size_t)s * c.n_groups, b - s, &pcm_d);
-    Q3_HIP_CHECK(hipEventRecord(ev1, stream));
-    if (first < 0 || first + n_own != n_win) throw Error("codec_decode_range: window arithmetic does not match the decoder length formula");
-    const int64_t m = std::min(n_own, cap);
-    if (m > 0 && pcm) Q3_HIP_CHECK(hipMemcpyAsync(pcm, pcm_d + first, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, stream));
-    sync();
-    Q3_HIP_CHECK(hipEventElapsedTime(&last_codec_ms, ev0, ev1));
-    total_codec_ms += last_codec_ms; total_codec_frames += b - s;
-    return n_own;
+    t.stop();
+    if (!cut.matches(n_win)) throw Error("codec_decode_range: window arithmetic does not match the decoder length formula");
+    return t.deliver(pcm_d + cut.first, cut.n_own, pcm, cap, b - s);
 }
 
 int64_t Engine::slot_codec_decode_range(int slot, int a, int b, int left_context, float* pcm, int64_t cap) {
@@ -1857,10 +1842,7 @@ int64_t Engine::codec_decode_chunked_host(const int64_t* codes, int F, int chunk
     if (chunk < 1) throw Error("codec_decode_chunked: chunk must be positive");
     const int G = c.n_groups;
     std::vector<int32_t> tmp((size_t)F * G);
-    for (size_t i = 0; i < tmp.size(); ++i) {
-        if (codes[i] < 0 || codes[i] >= c.cd_codebook) throw Error("codec_decode: code out of range");
-        tmp[i] = (int32_t)codes[i];
-    }
+    stage_codes<Error>(codes, tmp.size(), c.cd_codebook, tmp.data());
     const bool no_carry = knob("Q3TTS_CODEC_NO_CARRY") != nullptr;
     if (left_context >= F && !no_carry) {   // exact mode: one carried-state stream, every chunk a push
         const int sid = codec_stream_begin(F);
@@ -1887,24 +1869,15 @@ int64_t Engine::codec_decode_chunked_host(const int64_t* codes, int F, int chunk
 int64_t Engine::codec_decode_host(const int64_t* codes, int F, float* pcm, int64_t cap) {
     if (!finalized) throw Error("weights not finalized");
     if (F < 1 || F > max_frames_cap) throw Error("codec_decode: F out of range");
-    const int G = c.n_groups;
-    std::vector<int32_t> tmp((size_t)F * G);
-    for (size_t i = 0; i < tmp.size(); ++i) {
-        if (codes[i] < 0 || codes[i] >= c.cd_codebook) throw Error("codec_decode: code out of range");
-        tmp[i] = (int32_t)codes[i];
-    }
+    std::vector<int32_t> tmp((size_t)F * c.n_groups);
+    stage_codes<Error>(codes, tmp.size(), c.cd_codebook, tmp.data());
     int32_t* cd = codes_scratch_d;
     Q3_HIP_CHECK(hipMemcpyAsync(cd, tmp.data(), tmp.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     float* pcm_d = nullptr;
-    Q3_HIP_CHECK(hipEventRecord(ev0, stream));
+    CodecTimed t(*this);
     const int64_t n = codec_run(cd, F, &pcm_d);
-    Q3_HIP_CHECK(hipEventRecord(ev1, stream));
-    const int64_t m = std::min(n, cap);
-    if (m > 0 && pcm) Q3_HIP_CHECK(hipMemcpyAsync(pcm, pcm_d, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, stream));
-    sync();
-    Q3_HIP_CHECK(hipEventElapsedTime(&last_codec_ms, ev0, ev1));
-    total_codec_ms += last_codec_ms; total_codec_frames += F;
-    return n;
+    t.stop();
+    return t.deliver(pcm_d, n, pcm, cap, F);
 }
 
 // run_vocoder with everything already in HBM: codes int32 [F][n_groups] and the PCM destination are device pointers of the caller
@@ -1914,15 +1887,10 @@ int64_t Engine::codec_decode_dev(const int32_t* codes_dev, int F, float* pcm_dev
     if (!codes_dev) throw Error("codec_decode_dev: null codes");
     if (F < 1 || F > max_frames_cap) throw Error("codec_decode: F out of range");
     float* pcm_d = nullptr;
-    Q3_HIP_CHECK(hipEventRecord(ev0, stream));
+    CodecTimed t(*this);
     const int64_t n = codec_run(codes_dev, F, &pcm_d);
-    Q3_HIP_CHECK(hipEventRecord(ev1, stream));
-    const int64_t m = std::min(n, cap);
-    if (m > 0 && pcm_dev) Q3_HIP_CHECK(hipMemcpyAsync(pcm_dev, pcm_d, (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    sync();
-    Q3_HIP_CHECK(hipEventElapsedTime(&last_codec_ms, ev0, ev1));
-    total_codec_ms += last_codec_ms; total_codec_frames += F;
-    return n;
+    t.stop();
+    return t.deliver(pcm_d, n, pcm_dev, cap, F, hipMemcpyDeviceToDevice);
 }
 
 // Algorithmic bytes of one decode step: every talker weight once, every

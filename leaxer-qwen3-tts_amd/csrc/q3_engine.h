@@ -9,6 +9,7 @@
 
 #include "q3_audio.h"
 #include "q3_begin_plan.h"
+#include "q3_codec_plan.h"
 #include "q3_common.h"
 #include "q3_kvpool.h"
 #include "q3_stage.h"
@@ -626,6 +627,23 @@ public:
                   float* slab_out = nullptr);
     int nb_in_use() const;
     void sync();
+};
+
+// A timed vocoder entry on the engine's stream: the constructor records ev0 in front of the entry's launches, stop() records ev1 behind
+// them, deliver() copies the first min(n, cap) samples out, drains the stream and adds the time and the frames to the totals.  A failure
+// anywhere before that leaves last_codec_ms and the totals as they were.
+struct CodecTimed {
+    Engine& e;
+    explicit CodecTimed(Engine& en) : e(en) { Q3_HIP_CHECK(hipEventRecord(e.ev0, e.stream)); }
+    void stop() { Q3_HIP_CHECK(hipEventRecord(e.ev1, e.stream)); }
+    int64_t deliver(const float* src, int64_t n, float* dst, int64_t cap, int frames, hipMemcpyKind kind = hipMemcpyDeviceToHost) {
+        const int64_t m = std::min(n, cap);
+        if (m > 0 && dst) Q3_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)m * sizeof(float), kind, e.stream));
+        e.sync();
+        Q3_HIP_CHECK(hipEventElapsedTime(&e.last_codec_ms, e.ev0, e.ev1));
+        e.total_codec_ms += e.last_codec_ms; e.total_codec_frames += frames;
+        return n;
+    }
 };
 
 } // namespace q3
