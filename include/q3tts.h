@@ -108,6 +108,21 @@ q3tts_engine* q3tts_create(const q3tts_config* cfg, int device, int max_batch, i
  * hold the pages of their cap, and when the pool runs dry the youngest running utterance is preempted and generated again later. */
 q3tts_engine* q3tts_create_pooled(const q3tts_config* cfg, int device, int max_batch, int max_ctx, int64_t kv_pool_tokens, uint32_t flags);
 int q3tts_kv_pool_info(q3tts_engine* e, int* page_tokens, int* total_pages, int* free_pages);
+/* One set of weights for several engines on a GPU (the reference loads its sessions once per TTSEngine, tts_onnx.cpp:91-107; a server
+ * with one handle per worker thread would otherwise hold one copy per handle).  A new engine on the donor's GPU with the donor's config,
+ * holding the donor's finalized weights (registry and everything finalize derives from it: packed copies, codec planes, repacked
+ * convs, codebooks, the layer-0 QKV table) instead of a copy.  Slots, KV pool, workspaces, streams, graphs, codec / encoder streams
+ * and stages are its own; it is ready at once (no q3tts_finalize).  The KV flags, NO_GRAPH, NO_FUSED_CP, RAGGED_PREFILL and TEST_HOOKS
+ * may differ from the donor's; Q3TTS_FLAG_FP32_CODEC must not (it selects a different derived layout).  May be called while the donor
+ * generates on another thread: neither the donor's stream nor its workspaces are touched.  NULL, with q3tts_last_error(NULL), when the
+ * donor is NULL or not finalized, when that flag differs, or on any argument q3tts_create_pooled refuses.
+ * While more than one engine holds a set, q3tts_set_tensor_host, q3tts_fill_synthetic and q3tts_load_weights_file fail on every holder
+ * ("weights are shared by N engines") and q3tts_finalize returns 0 and does nothing; the read-only calls work on every holder.  Holders
+ * may be destroyed in any order, also while another one generates; the last q3tts_destroy frees the weights. */
+q3tts_engine* q3tts_create_sharing(q3tts_engine* donor, int max_batch, int max_ctx, int64_t kv_pool_tokens, uint32_t flags);
+/* bytes of HBM the engine's weight set holds (registry + derived copies), how many engines hold that set, and how many bytes of weights
+ * or derived weight copies this engine owns outside the shared set (0 when everything applicable is shared).  Any pointer may be NULL. */
+int q3tts_weights_info(q3tts_engine* e, int64_t* shared_bytes, int* holders, int64_t* private_weight_bytes);
 /* The last q3tts_synthesize_* call on this engine: utterances admitted to a slot (re-admissions count), utterances preempted because the
  * pool ran dry (each is generated again from its prompt: same RNG stream, same codes), most utterances running at once. */
 int q3tts_sched_stats(q3tts_engine* e, int64_t* admitted, int64_t* preempted, int* peak_live);

@@ -110,6 +110,35 @@ q3tts_engine* q3tts_create_pooled(const q3tts_config* cfg, int device, int max_b
     return nullptr;
 }
 
+q3tts_engine* q3tts_create_sharing(q3tts_engine* donor, int max_batch, int max_ctx, int64_t kv_pool_tokens, uint32_t flags) {
+    if (!donor || !donor->e) { g_create_err = "weight sharing: null donor"; return nullptr; }
+    try {
+        // of the donor only what never changes after its creation is read: config, device, flags, the pointer to its set
+        const Engine& d = *donor->e;
+        if (!d.ws.is_published()) throw q3::Error("weight sharing: the donor's weights are not finalized");
+        if ((flags ^ d.flags) & Q3TTS_FLAG_FP32_CODEC)
+            throw q3::Error("weight sharing: Q3TTS_FLAG_FP32_CODEC must equal the donor's (the codec's derived weight layout depends on it)");
+        if (const char* ng = getenv("Q3TTS_NO_GRAPH")) if (ng[0] == '1') flags |= Q3TTS_FLAG_NO_GRAPH; // profiling aid
+        (void)hipSetDevice(d.device);
+        q3tts_engine* h = new q3tts_engine;
+        try { h->e = new Engine(d.c, d.device, max_batch, max_ctx, flags, kv_pool_tokens, d.hold.set); }
+        catch (...) { delete h; throw; }
+        return h;
+    } catch (const q3::Error& ex) { g_create_err = ex.msg; }
+    catch (const std::exception& ex) { g_create_err = ex.what(); }
+    catch (...) { g_create_err = "unknown error"; }
+    return nullptr;
+}
+
+int q3tts_weights_info(q3tts_engine* h, int64_t* shared_bytes, int* holders, int64_t* private_weight_bytes) {
+    Q3_API_BEGIN(h)
+    if (shared_bytes) *shared_bytes = h->e->ws.n_bytes();
+    if (holders) *holders = h->e->ws.n_holders();
+    if (private_weight_bytes) *private_weight_bytes = h->e->private_weight_bytes();
+    return 0;
+    Q3_API_END(h)
+}
+
 void q3tts_destroy(q3tts_engine* h) {
     if (!h) return;
     delete h->e;
@@ -1331,6 +1360,7 @@ int q3tts_read_weights_config(const char* path, q3tts_config* out) {
 
 int q3tts_load_weights_file(q3tts_engine* h, const char* path) {
     Q3_API_BEGIN(h)
+    h->e->check_unshared();
     File fl(path, "rb");
     if (!fl.f) throw q3::Error(std::string("cannot open ") + path);
     q3tts_config cfg;

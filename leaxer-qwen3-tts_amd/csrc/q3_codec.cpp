@@ -18,7 +18,9 @@ namespace q3 {
 struct PackedConv { const float* w = nullptr; const float* b = nullptr; int cin = 0, cout = 0, k = 0; };
 struct SnakeP { const float *alpha = nullptr, *beta = nullptr; int C = 0; };
 
-struct CodecW {
+// The weight half: a function of the checkpoint (and of Q3TTS_FLAG_FP32_CODEC, which decides whether the planes exist) alone.  It lives
+// in the engine's WeightSet; every holder's CodecW reads it through references of the same names.
+struct CodecWeights {
     struct Layer { const float *in_norm, *post_norm, *qkv, *o, *gate, *up, *down, *attn_scale, *mlp_scale; };
     std::vector<Layer> layers;
     const float *norm = nullptr, *code_embed = nullptr;
@@ -39,6 +41,36 @@ struct CodecW {
     std::unordered_map<const float*, Planes> planes;
     // SnakeBeta constants [2][C] (exp(alpha) | 1 / (exp(beta) + 1e-9)) keyed by the alpha pointer (owned; split-precision path only)
     std::unordered_map<const float*, float*> snake_pre;
+    int64_t bytes = 0;   // HBM of the owned copies (counted in the set's bytes)
+};
+
+void codec_weights_free(CodecWeights* w) {
+    if (!w) return;
+    for (float* p : w->packed) (void)hipFree(p);
+    for (auto& kv : w->planes) {
+        (void)hipFree(kv.second.hi);   // lo lives in the same allocation
+        if (kv.second.cm) (void)hipFree(kv.second.cm);
+        if (kv.second.fh) (void)hipFree(kv.second.fh);   // fl lives in the same allocation
+    }
+    for (auto& kv : w->snake_pre) (void)hipFree(kv.second);
+    delete w;
+}
+
+// The run-time half, one per engine: lanes, arenas, pinned buffers, RoPE tables, streams.
+struct CodecW {
+    using Layer = CodecWeights::Layer; using Up = CodecWeights::Up; using Res = CodecWeights::Res; using Block = CodecWeights::Block; using Planes = CodecWeights::Planes;
+    explicit CodecW(const CodecWeights& w)
+        : layers(w.layers), norm(w.norm), code_embed(w.code_embed), up(w.up), conv_in(w.conv_in), conv_out(w.conv_out), blocks(w.blocks),
+          snake_out(w.snake_out), n_lo_zero(w.n_lo_zero), n_lo_used(w.n_lo_used), planes(w.planes), snake_pre(w.snake_pre) {}
+    const std::vector<Layer>& layers;
+    const float* const& norm; const float* const& code_embed;
+    const std::vector<Up>& up;
+    const PackedConv &conv_in, &conv_out;
+    const std::vector<Block>& blocks;
+    const SnakeP& snake_out;
+    const int &n_lo_zero, &n_lo_used;
+    const std::unordered_map<const float*, Planes>& planes;
+    const std::unordered_map<const float*, float*>& snake_pre;
     // run-time workspace: one bump arena per codec stream (lane 0 = the engine's own stream)
     static constexpr int NLANE = 32;   // capacity; `nlane` of them are used (Q3TTS_CODEC_LANES)
     int nlane = 9;                      // lane 0 = the engine's stream (synchronous entry points), the others decode asynchronously
@@ -86,13 +118,6 @@ struct CodecW {
 
 void Engine::codec_free() {
     if (!codec) return;
-    for (float* p : codec->packed) (void)hipFree(p);
-    for (auto& kv : codec->planes) {
-        (void)hipFree(kv.second.hi);   // lo lives in the same allocation
-        if (kv.second.cm) (void)hipFree(kv.second.cm);
-        if (kv.second.fh) (void)hipFree(kv.second.fh);   // fl lives in the same allocation
-    }
-    for (auto& kv : codec->snake_pre) (void)hipFree(kv.second);
     for (int i = 0; i < CodecW::NLANE; ++i) {
         if (codec->arena[i]) (void)hipFree(codec->arena[i]);
         if (codec->pinned[i]) (void)hipHostFree(codec->pinned[i]);
@@ -122,12 +147,12 @@ void Engine::codec_plane_stats(int* two_product, int* three_product) const {
 
 void Engine::codec_finalize() {
     codec_free();
-    codec = new CodecW;
-    CodecW& W = *codec;
+    if (ws.codec) { ws.add_bytes(-ws.codec->bytes); codec_weights_free(ws.codec); ws.codec = nullptr; }
+    ws.codec = new CodecWeights;
+    CodecWeights& W = *ws.codec;
     auto fp = [&](const std::string& n) { return (const float*)T(n).dev; };
     auto pack = [&](const std::string& prefix, int cin, int cout, int k, bool transposed) {
-        float* out = nullptr;
-        Q3_HIP_CHECK(hipMalloc((void**)&out, (size_t)cin * cout * k * sizeof(float)));
+        float* out = (float*)ws.take((size_t)cin * cout * k * sizeof(float), W.bytes);
         W.packed.push_back(out);
         launch_repack_conv(fp(prefix + ".w"), out, cin, cout, k, transposed ? 1 : 0, stream);
         PackedConv p; p.w = out; p.b = fp(prefix + ".b"); p.cin = cin; p.cout = cout; p.k = k;
@@ -137,7 +162,7 @@ void Engine::codec_finalize() {
     const int CH = c.cd_hidden, D = c.cd_decoder_dim;
     for (int i = 0; i < c.cd_layers; ++i) {
         const std::string p = "cd.layers." + std::to_string(i) + ".";
-        CodecW::Layer L;
+        CodecWeights::Layer L;
         L.in_norm = fp(p + "input_norm"); L.post_norm = fp(p + "post_norm"); L.qkv = fp(p + "q_proj"); L.o = fp(p + "o_proj");
         L.gate = fp(p + "gate_proj"); L.up = fp(p + "up_proj"); L.down = fp(p + "down_proj");
         L.attn_scale = fp(p + "attn_scale"); L.mlp_scale = fp(p + "mlp_scale");
@@ -146,7 +171,7 @@ void Engine::codec_finalize() {
     W.norm = fp("cd.norm"); W.code_embed = fp("cd.code_embed");
     for (int s = 0; s < c.cd_n_up; ++s) {
         const std::string p = "cd.up." + std::to_string(s) + ".";
-        CodecW::Up u;
+        CodecWeights::Up u;
         u.tconv = pack(p + "tconv", CH, CH, c.cd_up_ratios[s], true);
         u.dw_w = fp(p + "cnx.dw.w"); u.dw_b = fp(p + "cnx.dw.b"); u.ln_w = fp(p + "cnx.ln.w"); u.ln_b = fp(p + "cnx.ln.b");
         u.pw1_w = fp(p + "cnx.pw1.w"); u.pw1_b = fp(p + "cnx.pw1.b"); u.pw2_w = fp(p + "cnx.pw2.w"); u.pw2_b = fp(p + "cnx.pw2.b");
@@ -157,7 +182,7 @@ void Engine::codec_finalize() {
     for (int i = 0; i < c.cd_n_blocks; ++i) {
         const int cin = D >> i, cout = D >> (i + 1), r = c.cd_up_rates[i];
         const std::string p = "cd.dec.blocks." + std::to_string(i) + ".";
-        CodecW::Block B;
+        CodecWeights::Block B;
         B.act = snake(p + "snake");
         B.tconv = pack(p + "tconv", cin, cout, 2 * r, true);
         for (int u = 0; u < 3; ++u) {
@@ -190,7 +215,7 @@ void Engine::codec_finalize() {
             const int k = amax > 0.f ? std::min(12 - e, 126) : 0;
             bf16_t *hi = nullptr, *lo = nullptr;   // one allocation, lo right behind hi: k_conv_split addresses both planes as base + 32-bit offset
             const size_t np = (n + 7) / 8 * 8;
-            Q3_HIP_CHECK(hipMalloc((void**)&hi, 2 * np * sizeof(bf16_t)));
+            hi = (bf16_t*)ws.take(2 * np * sizeof(bf16_t), W.bytes);
             lo = hi + np;
             launch_split_planes(w, hi, lo, n, ldexpf(1.0f, k), stream);
             unsigned lo_bits = 0;
@@ -198,13 +223,13 @@ void Engine::codec_finalize() {
             launch_or_mag16(lo, n, amax_d, stream);
             Q3_HIP_CHECK(hipMemcpyAsync(&lo_bits, amax_d, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
             sync();
-            CodecW::Planes pl{ hi, lo, ldexpf(1.0f, -k), lo_bits == 0 };
+            CodecWeights::Planes pl{ hi, lo, ldexpf(1.0f, -k), lo_bits == 0 };
             if (taps > 0 && cin % 32 == 0 && (size_t)taps * cout * cin == n) {   // the chunk-major copy for the 32-wide-chunk kernels
-                Q3_HIP_CHECK(hipMalloc((void**)&pl.cm, 2 * np * sizeof(bf16_t)));
+                pl.cm = (bf16_t*)ws.take(2 * np * sizeof(bf16_t), W.bytes);
                 launch_repack_planes_cm(hi, pl.cm, taps, cout, cin, np, stream);
             }
             if (taps == 1 && cout == 96 && cin == 96) {                           // a fused unit's second conv: B fragments
-                Q3_HIP_CHECK(hipMalloc((void**)&pl.fh, 2 * n * sizeof(bf16_t)));
+                pl.fh = (bf16_t*)ws.take(2 * n * sizeof(bf16_t), W.bytes);
                 pl.fl = pl.fh + n;
                 launch_pack_w2_frags(hi, pl.fh, 96, stream);
                 launch_pack_w2_frags(lo, pl.fl, 96, stream);
@@ -226,14 +251,22 @@ void Engine::codec_finalize() {
         for (const CodecW::Block& B : W.blocks) { pc(B.tconv); for (int u = 0; u < 3; ++u) { pc(B.res[u].c1); pc(B.res[u].c2); } }
         auto pre = [&](const SnakeP& sp) {   // exp(alpha), 1 / (exp(beta) + 1e-9) once per activation instead of once per 32-row block of every launch
             if (!sp.alpha || !sp.beta || sp.C <= 0 || W.snake_pre.count(sp.alpha)) return;
-            float* d = nullptr;
-            Q3_HIP_CHECK(hipMalloc((void**)&d, (size_t)2 * sp.C * sizeof(float)));
+            float* d = (float*)ws.take((size_t)2 * sp.C * sizeof(float), W.bytes);
             launch_snake_pre(sp.alpha, sp.beta, d, sp.C, stream);
             W.snake_pre[sp.alpha] = d;
         };
         for (const CodecW::Block& B : W.blocks) { pre(B.act); for (int u = 0; u < 3; ++u) { pre(B.res[u].a1); pre(B.res[u].a2); } }
         pre(W.snake_out);
     }
+    sync();
+    codec_runtime_init();
+}
+
+void Engine::codec_runtime_init() {
+    codec_free();
+    if (!ws.codec) throw Error("codec decoder not finalized");
+    codec = new CodecW(*ws.codec);
+    CodecW& W = *codec;
     if (const char* ev = getenv("Q3TTS_CODEC_LANES")) W.nlane = std::max(1, std::min((int)CodecW::NLANE, atoi(ev)));
     W.lane_stream[0] = stream;
     for (int i = 1; i < W.nlane; ++i) {

@@ -41,11 +41,31 @@ struct EncStream {
     bool plain() const { return rate == 24000 && format == Q3TTS_PCM_F32; }
 };
 static constexpr size_t kEncCarryFloats = 64;   // a carry buffer: ceil(384000 / 24000) + 1 = 17 samples at most, one 256-byte line
-struct EncoderW {
+// The weight half, in the engine's WeightSet: repacked convs, layer pointers, codebooks.
+struct EncWeights {
     EncConvW conv_in, res1[4], res2[4], down[4], conv_out, ds;
     std::vector<EncLayerW> layers;
     const float *proj_sem = nullptr, *proj_ac = nullptr;
     float* books = nullptr;                    // [n_groups][codebook][vq_dim], the level tables back to back
+    int64_t bytes = 0;                         // HBM of the owned copies (counted in the set's bytes)
+};
+void encoder_weights_free(EncWeights* w) {
+    if (!w) return;
+    if (w->books) (void)hipFree(w->books);
+    auto drop = [](EncConvW& cv) { if (cv.owned && cv.w) (void)hipFree(cv.w); cv.w = nullptr; };
+    drop(w->conv_in); drop(w->conv_out); drop(w->ds);
+    for (int s = 0; s < 4; ++s) { drop(w->res1[s]); drop(w->res2[s]); drop(w->down[s]); }
+    delete w;
+}
+// The run-time half, one per engine; it reads the weights through references of the same names.
+struct EncoderW {
+    explicit EncoderW(const EncWeights& w)
+        : conv_in(w.conv_in), res1(w.res1), res2(w.res2), down(w.down), conv_out(w.conv_out), ds(w.ds), layers(w.layers), proj_sem(w.proj_sem),
+          proj_ac(w.proj_ac), books(w.books) {}
+    const EncConvW& conv_in; const EncConvW (&res1)[4]; const EncConvW (&res2)[4]; const EncConvW (&down)[4]; const EncConvW &conv_out, &ds;
+    const std::vector<EncLayerW>& layers;
+    const float* const& proj_sem; const float* const& proj_ac;
+    float* const& books;
     float *rope_cs = nullptr, *rope_sn = nullptr; int rope_rows = 0;
     char* ws = nullptr; size_t ws_cap = 0;     // grow-only workspace
     std::vector<EncStream> streams;            // streamed pushes: state in allocations of its own, never in ws
@@ -72,12 +92,8 @@ void Engine::encoder_free() {
     if (!enc) return;
     if (enc->ws) (void)hipFree(enc->ws);
     for (EncStream& st : enc->streams) if (st.buf) (void)hipFree(st.buf);
-    if (enc->books) (void)hipFree(enc->books);
     if (enc->rope_cs) (void)hipFree(enc->rope_cs);
     if (enc->rope_sn) (void)hipFree(enc->rope_sn);
-    auto drop = [](EncConvW& cv) { if (cv.owned && cv.w) (void)hipFree(cv.w); cv.w = nullptr; };
-    drop(enc->conv_in); drop(enc->conv_out); drop(enc->ds);
-    for (int s = 0; s < 4; ++s) { drop(enc->res1[s]); drop(enc->res2[s]); drop(enc->down[s]); }
     delete enc;
     enc = nullptr;
 }
@@ -121,11 +137,12 @@ static void enc_rope_tables(Engine& e, int rows) {
 void Engine::encoder_finalize() {
     if (!has_audio_encoder()) return;
     if (c.enc_hidden % 4) throw Error("audio encoder: enc_hidden must be a multiple of 4");
-    if (!enc) enc = new EncoderW();
+    if (!ws.enc) ws.enc = new EncWeights();
+    EncWeights* enc = ws.enc;   // shadows the run-time part down to encoder_runtime_init
     auto pack = [&](EncConvW& cv, const std::string& n, bool bias = true) {
         const Tensor& w = T(n + ".w");
         cv.cout = (int)w.shape[0]; cv.cin = (int)w.shape[1]; cv.k = (int)w.shape[2];
-        if (!cv.w) { Q3_HIP_CHECK(hipMalloc((void**)&cv.w, (size_t)w.numel * sizeof(float))); cv.owned = true; }
+        if (!cv.w) { cv.w = (float*)ws.take((size_t)w.numel * sizeof(float), enc->bytes); cv.owned = true; }
         launch_repack_conv((const float*)w.dev, cv.w, cv.cin, cv.cout, cv.k, 0, stream);
         cv.b = bias ? (const float*)T(n + ".b").dev : nullptr;
     };
@@ -146,15 +163,21 @@ void Engine::encoder_finalize() {
     }
     enc->proj_sem = fp("enc.vq.sem.in_proj"); enc->proj_ac = fp("enc.vq.ac.in_proj");
     const size_t book = (size_t)c.enc_codebook * c.enc_vq_dim;
-    if (!enc->books) Q3_HIP_CHECK(hipMalloc((void**)&enc->books, book * c.n_groups * sizeof(float)));
+    if (!enc->books) enc->books = (float*)ws.take(book * c.n_groups * sizeof(float), enc->bytes);
     for (int g = 0; g < c.n_groups; ++g)
         Q3_HIP_CHECK(hipMemcpyAsync(enc->books + (size_t)g * book, T("enc.vq.codebook." + std::to_string(g)).dev, book * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    encoder_runtime_init();
+    sync();
+}
+
+void Engine::encoder_runtime_init() {
+    if (!ws.enc) throw Error("weights not finalized");
+    if (!enc) enc = new EncoderW(*ws.enc);
     // RoPE tables for every row a clip under the cap can have, computed in double
     int64_t prod = 1;
     for (int s = 0; s < c.enc_n_ratios; ++s) prod *= c.enc_ratios[s];
     const int rows = (int)ceil_div(kEncMaxClipSamples, prod) + 1;
     enc_rope_tables(*this, std::max(rows, enc->rope_rows));   // tables a stream has grown stay grown
-    sync();
 }
 
 namespace {

@@ -219,8 +219,17 @@ KnobScope::~KnobScope() { if (on) g_hook_engines.fetch_sub(1, std::memory_order_
 // ------------------------------------------------------------------------------------------------
 // construction
 // ------------------------------------------------------------------------------------------------
-Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_, uint32_t flags_, int64_t kv_pool_tokens)
-    : c(cfg), device(device_), B(max_batch), max_ctx(max_ctx_), flags(flags_) {
+// an engine's hold on its set: a fresh set of its own, or one more holder of a published one
+static std::shared_ptr<WeightSet> held_set(std::shared_ptr<WeightSet> shared, int device) {
+    if (!shared) { shared = std::make_shared<WeightSet>(device); shared->hold(); return shared; }
+    if (!shared->join()) throw Error("weight sharing: the donor's weights are not finalized");
+    return shared;
+}
+
+Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_, uint32_t flags_, int64_t kv_pool_tokens, std::shared_ptr<WeightSet> shared)
+    : c(cfg), device(device_), B(max_batch), max_ctx(max_ctx_), flags(flags_), hold(held_set(shared, device_)), ws(*hold.set),
+      tensors(ws.tensors), tindex(ws.tindex), finalized(ws.ready), packed_w(ws.packed_w) {
+    const bool sharer = shared != nullptr;
     if (flags & Q3TTS_FLAG_TEST_HOOKS) knob_scope.enable();   // before the first knob() below
     if (B < 1 || B > 1024) throw Error("max_batch out of range");
     if (kv_pool_tokens < 0) throw Error("kv_pool_tokens must be >= 0");
@@ -268,7 +277,7 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
     if (c.spk_enc_dim > 0 && c.spk_enc_dim != c.hidden) throw Error("speaker encoder output width must equal the talker width (spk_enc_dim == hidden)");
     if (c.enc_hidden < 0) throw Error("enc_hidden must be >= 0");
     if (!enc_config_ok(c)) throw Error("audio encoder dims out of range");
-    {   // allocate the registry (q | k | v of a layer share one block so that their rows are contiguous)
+    if (!sharer) {   // allocate the registry (q | k | v of a layer share one block so that their rows are contiguous)
         char* fused = nullptr; size_t fused_off = 0;
         const std::vector<TensorSpec> specs = tensor_specs(c);
         if (specs.empty()) throw Error("model config out of range (layer / group / block counts)");
@@ -285,10 +294,10 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
                     for (int d = 0; d < specs[k].ndim; ++d) n *= (size_t)specs[k].shape[d];
                     total += n * (specs[k].bf16 ? 2 : 4);
                 }
-                fused = (char*)dmalloc(total); fused_off = 0;
+                fused = (char*)ws.dmalloc(total); fused_off = 0;
             }
             if (sp.fuse > 0) { t.dev = fused + fused_off; fused_off += bytes; }
-            else t.dev = dmalloc(bytes);
+            else t.dev = ws.dmalloc(bytes);
             tindex[t.name] = (int)tensors.size();
             tensors.push_back(t);
         }
@@ -318,8 +327,10 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
     hn = fm((size_t)std::max(16, rows_max) * H);
     logits_p = fm((size_t)16 * std::max(c.vocab, c.sub_vocab));
     trailing_d = fm((size_t)B * max_trailing * H);
-    tts_pad_d = fm(H);
-    tts_eos_d = fm(H);
+    if (!sharer) {   // model-wide rows, filled by finalize: the set's
+        for (float** p : { &ws.tts_pad_d, &ws.tts_eos_d }) { *p = (float*)ws.dmalloc((size_t)H * sizeof(float)); Q3_HIP_CHECK(hipMemsetAsync(*p, 0, (size_t)H * sizeof(float), stream)); }
+    }
+    tts_pad_d = ws.tts_pad_d; tts_eos_d = ws.tts_eos_d;
     text_tmp = fm((size_t)16 * c.text_hidden);
     text_tmp2 = fm((size_t)16 * c.text_hidden);
     ldp = (std::max(std::max(H, AO), std::max(c.ffn, c.cp_ffn)) + 7) / 8 * 8;
@@ -426,6 +437,7 @@ Engine::Engine(const q3tts_config& cfg, int device_, int max_batch, int max_ctx_
         S->pl = fm((size_t)rows_max * S->nq * ns);
     }
     sync();
+    if (sharer) bind_shared();
 }
 
 Engine::~Engine() {
@@ -446,8 +458,7 @@ Engine::~Engine() {
     codec_free();
     speaker_free();
     encoder_free();
-    free_packed_weights();
-    for (void* p : allocs) (void)hipFree(p);
+    for (void* p : allocs) (void)hipFree(p);   // the set goes with its last holder (hold's destructor, behind this body)
     if (active_h) (void)hipHostFree(active_h);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
@@ -459,7 +470,47 @@ Engine::~Engine() {
 // ------------------------------------------------------------------------------------------------
 // weights
 // ------------------------------------------------------------------------------------------------
+void* WeightSet::dmalloc(size_t bytes) {
+    void* p = nullptr;
+    if (bytes == 0) bytes = 16;
+    Q3_HIP_CHECK(hipMalloc(&p, bytes));
+    allocs.push_back(p);
+    add_bytes((int64_t)bytes);
+    return p;
+}
+void* WeightSet::take(size_t bytes, int64_t& tally) {
+    void* p = nullptr;
+    if (bytes == 0) bytes = 16;
+    Q3_HIP_CHECK(hipMalloc(&p, bytes));
+    add_bytes((int64_t)bytes);
+    tally += (int64_t)bytes;
+    return p;
+}
+void WeightSet::free_packed() {
+    if (cp_qkv_tab) (void)hipFree(cp_qkv_tab);
+    cp_qkv_tab = nullptr;
+    drop(cp_qkv_tab_bytes);
+    for (auto& pr : packed_w) { unregister_packed_weight(pr.first); (void)hipFree(pr.second); }
+    packed_w.clear();
+    drop(packed_bytes);
+}
+WeightSet::~WeightSet() {
+    (void)hipSetDevice(device);
+    free_packed();
+    codec_weights_free(codec);
+    speaker_weights_free(spk);
+    encoder_weights_free(enc);
+    if (mel_tables_d) (void)hipFree(mel_tables_d);
+    for (void* p : allocs) (void)hipFree(p);
+}
+
+void Engine::check_unshared() const {
+    const std::string why = ws.mutation_refusal();
+    if (!why.empty()) throw Error(why);
+}
+
 void Engine::set_tensor(const std::string& name, const float* data, int64_t n) {
+    check_unshared();
     Tensor& t = T(name);
     if (t.numel != n) throw Error("tensor '" + name + "': expected " + std::to_string(t.numel) + " elements, got " + std::to_string(n));
     if (t.bf16) {
@@ -470,6 +521,7 @@ void Engine::set_tensor(const std::string& name, const float* data, int64_t n) {
         Q3_HIP_CHECK(hipMemcpy(t.dev, data, (size_t)n * 4, hipMemcpyHostToDevice));
     }
     finalized = false;
+    ws.publish(false);
 }
 
 void Engine::get_tensor(const std::string& name, float* out, int64_t n) {
@@ -488,6 +540,8 @@ void Engine::get_tensor(const std::string& name, float* out, int64_t n) {
 // SURVEY.md section 8d synthetic weights: matrices N(0, 0.02^2) bf16-representable, norm gains 1,
 // SnakeBeta alpha = beta = 0, LayerScale / ConvNeXt gamma 0.01, biases N(0, 0.02^2).
 void Engine::fill_synthetic(uint64_t seed) {
+    check_unshared();
+    ws.publish(false);
     for (Tensor& t : tensors) {
         float mean = 0.f, sd = 0.f;
         switch (t.kind) {
@@ -508,16 +562,14 @@ void Engine::fill_synthetic(uint64_t seed) {
 // bf16 projection weights (1.05 GB at 0.6B dims, 3 GB at 1.7B), registered under the row-major pointer the launch sites keep using.
 void Engine::free_packed_weights() {
     free_cp_qkv_table();   // derived from the same weights: dropped and rebuilt with the packed copies
-    for (auto& pr : packed_w) { unregister_packed_weight(pr.first); (void)hipFree(pr.second); }
-    packed_w.clear();
+    ws.free_packed();
 }
 void Engine::pack_mfma_weights() {
     free_packed_weights();
     auto pack = [&](const bf16_t* W, int N, int K) {
         if (W == nullptr || N < 1 || K < 32 || K % 32 != 0) return;
         for (auto& pr : packed_w) if (pr.first == W) return;
-        bf16_t* P = nullptr;
-        Q3_HIP_CHECK(hipMalloc((void**)&P, packed_mfma_b_elems(N, K) * sizeof(bf16_t)));
+        bf16_t* P = (bf16_t*)ws.take(packed_mfma_b_elems(N, K) * sizeof(bf16_t), ws.packed_bytes);
         launch_pack_mfma_b(W, P, N, K, stream);
         packed_w.emplace_back(W, P);
     };
@@ -565,36 +617,45 @@ bool Engine::cp_qkv_table_applies() const {
 void Engine::free_cp_qkv_table() {
     for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
     graphs.clear();
-    if (cp_qkv_tab) (void)hipFree(cp_qkv_tab);
-    cp_qkv_tab = nullptr;
+    cp_qkv_tab = nullptr;   // the view; the table itself is the set's (WeightSet::free_packed)
 }
 
 // One GEMV launch per (group, code), each the launch run_layers would issue for that input row: the bf16 embedding widened to fp32
 // (what the sampler leaves in x_cp1) through the k_gemv1 instantiation of the step, same gamma / eps / nt.  (n_groups - 2) x sub_vocab
 // launches on the engine's stream, back to back.
+// The table belongs to the set and is built at most once (ShareBook::build_once, under the set's build mutex): by finalize when it
+// applies to the finalizing engine, else by the first sharer it applies to, on that engine's own stream.  It is published (the set's
+// pointer written) only after the launches completed, so another holder's stream never reads rows in flight.  The rows are the M = 1
+// k_gemv1 launch over the set's weights whoever builds them.
 void Engine::build_cp_qkv_table() {
     free_cp_qkv_table();
     if (!cp_qkv_table_applies()) return;
     const int H = c.hidden, SV = c.sub_vocab, NG = c.n_groups - 2, QKV = (cp.nq + 2 * cp.nkv) * cp.d;
-    float* rows = nullptr;
-    try {
-        Q3_HIP_CHECK(hipMalloc((void**)&cp_qkv_tab, (size_t)NG * SV * QKV * sizeof(float)));
-        Q3_HIP_CHECK(hipMalloc((void**)&rows, (size_t)SV * H * sizeof(float)));
-        for (int j = 0; j < NG; ++j) {
-            launch_bf16_to_f32(cp_embed_w[j], rows, (int64_t)SV * H, stream);
-            for (int code = 0; code < SV; ++code)
-                gemv(qkv_gemv_args(cp, 0, rows + (size_t)code * H, cp.H, cp_qkv_tab + ((size_t)j * SV + code) * QKV, 1));
+    ws.build_once([&] { return ws.cp_qkv_tab != nullptr; }, [&]() -> int64_t {
+        float *rows = nullptr, *tab = nullptr;
+        const size_t tab_bytes = (size_t)NG * SV * QKV * sizeof(float);
+        try {
+            Q3_HIP_CHECK(hipMalloc((void**)&tab, tab_bytes));
+            Q3_HIP_CHECK(hipMalloc((void**)&rows, (size_t)SV * H * sizeof(float)));
+            for (int j = 0; j < NG; ++j) {
+                launch_bf16_to_f32(cp_embed_w[j], rows, (int64_t)SV * H, stream);
+                for (int code = 0; code < SV; ++code)
+                    gemv(qkv_gemv_args(cp, 0, rows + (size_t)code * H, cp.H, tab + ((size_t)j * SV + code) * QKV, 1));
+            }
+            sync();
+        } catch (...) {
+            if (rows) (void)hipFree(rows);
+            if (tab) (void)hipFree(tab);
+            throw;
         }
-        sync();
-    } catch (...) {
-        if (rows) (void)hipFree(rows);
-        free_cp_qkv_table();
-        throw;
-    }
-    (void)hipFree(rows);
+        (void)hipFree(rows);
+        ws.cp_qkv_tab = tab; ws.cp_qkv_tab_bytes = (int64_t)tab_bytes;
+        return (int64_t)tab_bytes;
+    });
+    cp_qkv_tab = ws.cp_qkv_tab;
 }
 
-void Engine::finalize() {
+void Engine::bind_weights() {
     auto fp = [&](const std::string& n) { return (const float*)T(n).dev; };
     auto bp = [&](const std::string& n) { return (const bf16_t*)T(n).dev; };
     auto fill_stack = [&](DecStack& S, const std::string& prefix) {
@@ -617,6 +678,25 @@ void Engine::finalize() {
     cp_proj_b = cp_projected() ? fp("cp.proj.b") : nullptr;
     cp_head.clear(); cp_embed_w.clear();
     for (int j = 0; j < c.n_groups - 1; ++j) { cp_head.push_back(bp("cp.head." + std::to_string(j))); cp_embed_w.push_back(bp("cp.embed." + std::to_string(j))); }
+}
+
+// A sharer comes up on a published set: its own pointer views and run-time parts, nothing derived again.  No launch reads or writes
+// the set except the table's builder, and nothing of the donor's (stream, workspaces) is touched.
+void Engine::bind_shared() {
+    bind_weights();
+    codec_runtime_init();
+    spk = ws.spk;
+    front_finalize();
+    if (has_audio_encoder()) encoder_runtime_init();
+    build_cp_qkv_table();
+    sync();
+}
+
+void Engine::finalize() {
+    if (ws.finalize_is_noop()) return;   // a published set that other engines hold too: nothing to do, nothing may be rebuilt under them
+    check_unshared();                    // unpublished and held by others cannot happen (a set is joined only while published); refuse rather than rebuild
+    ws.publish(false);
+    bind_weights();
     codec_finalize();
     speaker_finalize();
     encoder_finalize();
@@ -638,6 +718,8 @@ void Engine::finalize() {
     }
     for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
     graphs.clear();
+    sync();             // every path above ends synchronised; this one makes it unconditional before the set can be joined
+    ws.publish(true);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@
 #include "q3_common.h"
 #include "q3_kvpool.h"
 #include "q3_stage.h"
+#include "q3_weight_share.h"
 
 namespace q3 {
 
@@ -60,15 +61,50 @@ struct DecStack {
     float *po = nullptr, *pm = nullptr, *pl = nullptr; // attention partials [rows][nq][n_splits]([d])
 };
 
-struct CodecW; // q3_codec.cpp
-struct SpeakerW; // q3_speaker.cpp
-struct SpkFront; // q3_speaker.cpp
-struct EncoderW; // q3_encoder.cpp
+struct CodecW; // q3_codec.cpp: the vocoder's run-time part (lanes, arenas, streams); reads its weights through CodecWeights
+struct CodecWeights; // q3_codec.cpp: layer list, repacked convs, (hi, lo) planes and their chunk-major / fragment copies, SnakeBeta constants
+struct SpeakerW; // q3_speaker.cpp: the speaker encoder's repacked convs (weights only)
+struct SpkFront; // q3_speaker.cpp: the clone front end's workspace; its mel tables are the set's
+struct EncoderW; // q3_encoder.cpp: the audio encoder's run-time part (RoPE tables, workspace, streams)
+struct EncWeights; // q3_encoder.cpp: repacked convs, layer pointers, codebooks
+void codec_weights_free(CodecWeights* w);
+void speaker_weights_free(SpeakerW* w);
+void encoder_weights_free(EncWeights* w);
+
+// Everything that is a function of the checkpoint alone ("The weight set"): the registry and every copy finalize derives
+// from it.  Immutable once published; engines created by q3tts_create_sharing hold the donor's set instead of a copy.  The last holder's
+// destruction frees the HBM.  Nothing in it is sized by max_batch or max_ctx, and nothing in it is written while an engine runs, except
+// the layer-0 QKV table, which the first holder it applies to adds once (ShareBook::build_once).
+struct WeightSet : ShareBook {
+    explicit WeightSet(int dev) : device(dev) {}
+    ~WeightSet();
+    WeightSet(const WeightSet&) = delete;
+    WeightSet& operator=(const WeightSet&) = delete;
+    int device;
+    std::vector<Tensor> tensors;
+    std::unordered_map<std::string, int> tindex;
+    std::vector<void*> allocs;                 // the registry's storage, tts_pad / tts_eos, the speaker encoder's repacked convs
+    bool ready = false;                        // Engine::finalized: the derived copies match the registry
+    std::vector<std::pair<const bf16_t*, bf16_t*>> packed_w;   // fragment-packed bf16 copies, registered under their row-major pointers
+    CodecWeights* codec = nullptr;
+    SpeakerW* spk = nullptr;
+    EncWeights* enc = nullptr;
+    void* mel_tables_d = nullptr;              // the log-mel front end's tables (q3_speaker.cpp: front_finalize)
+    float *tts_pad_d = nullptr, *tts_eos_d = nullptr;
+    float* cp_qkv_tab = nullptr; int64_t cp_qkv_tab_bytes = 0;   // Engine::cp_qkv_tab
+    void* dmalloc(size_t bytes);               // counted in bytes, freed with the set
+    void* take(size_t bytes, int64_t& tally);  // a derived copy's allocation: counted in bytes and in the piece's own tally
+    void drop(int64_t& tally) { add_bytes(-tally); tally = 0; }   // the piece was freed
+    int64_t packed_bytes = 0, mel_bytes = 0;
+    void free_packed();                        // the packed copies and the table (re-finalize, destruction)
+};
 
 class Engine {
 public:
     // kv_pool_tokens: capacity of the talker's KV page pool in tokens (0: max_batch x max_ctx, every slot can reach max_ctx at once)
-    Engine(const q3tts_config& cfg, int device, int max_batch, int max_ctx, uint32_t flags, int64_t kv_pool_tokens = 0);
+    // shared non-null: the engine holds that (published) set instead of allocating a registry, and comes up finalized (bind_shared)
+    Engine(const q3tts_config& cfg, int device, int max_batch, int max_ctx, uint32_t flags, int64_t kv_pool_tokens = 0,
+           std::shared_ptr<WeightSet> shared = nullptr);
     ~Engine();
 
     // ---- talker KV page pool: 64-token pages handed to slots on demand (page 0 is a scratch page every unowned table entry points at,
@@ -91,11 +127,17 @@ public:
     bool null_stream = false;
     std::string err;
 
-    // ---- weights ----
-    std::vector<Tensor> tensors;
-    std::unordered_map<std::string, int> tindex;
-    std::vector<void*> allocs;
-    bool finalized = false;
+    // ---- weights: the set's, through references, so that every reader keeps its spelling ----
+    SetHold<WeightSet> hold;
+    WeightSet& ws;
+    std::vector<Tensor>& tensors;
+    std::unordered_map<std::string, int>& tindex;
+    bool& finalized;
+    std::vector<void*> allocs;                 // this engine's own workspaces (nothing derived from the checkpoint)
+    void check_unshared() const;               // set_tensor / fill_synthetic / load_weights: refused while another engine holds the set
+    void bind_weights();                       // this engine's pointer views into the registry (DecStack layers, heads, embeddings)
+    void bind_shared();                        // a sharer's construction: views + run-time parts on a published set, + the table if it is the first it applies to
+    int64_t private_weight_bytes() const { return 0; }   // derived copies this engine owns outside the set: none
     Tensor& T(const std::string& n);
     void set_tensor(const std::string& name, const float* data, int64_t n);
     void get_tensor(const std::string& name, float* out, int64_t n);
@@ -431,7 +473,7 @@ public:
     void measure_skip_frames(int n);                    // measurement aid: armed slots jump n frames ahead over a synthetic KV cache
     void pack_mfma_weights();                           // fragment-packed copies of the projection matrices for k_gemv16 / k_gemm3 (finalize)
     void free_packed_weights();
-    std::vector<std::pair<const bf16_t*, bf16_t*>> packed_w;
+    std::vector<std::pair<const bf16_t*, bf16_t*>>& packed_w;
     void prefill_profile(int nb, int S, int reps, double* ms_per_pass);   // device time of a batched prefill pass (diagnostic)
     void stage_profile(int n_steps, double* out_ms4);   // eager steps with events at the stage boundaries (diagnostic)
     // one EAGER step of the armed slots that also keeps, for slot `slot`, the logits row every one of the frame's n_groups decisions was
@@ -448,7 +490,8 @@ public:
 
     // ---- codec decoder (q3_codec.cpp) ----
     CodecW* codec = nullptr;
-    void codec_finalize();
+    void codec_finalize();                      // the set's CodecWeights (again), then codec_runtime_init
+    void codec_runtime_init();                  // this engine's CodecW over ws.codec: lanes, page table
     void codec_plane_stats(int* two_product, int* three_product) const;   // weight tensors on the 2-product (lo plane empty) / 3-product split path
     // returns the sample count; h_in: this utterance's rows from codec_pre_batch (h_stage 1: after the pre-transformer, 2: after the upsampling stages too)
     int64_t codec_run(const int32_t* codes_dev, int F, float** pcm_dev, int lane = 0, const float* h_in = nullptr, int h_stage = 1, int nbatch = 1, size_t h_ustride = 0);
@@ -479,7 +522,7 @@ public:
     // GPU front end for audio already in memory (mono float, any rate).  Each call stages its clips in one pinned copy, runs on the
     // engine's stream in the engine-owned workspace (grow-only, freed with the engine) and ends with one stream sync.
     SpkFront* spkf = nullptr;
-    void front_finalize();                      // the log-mel tables of q3_audio.cpp's make_plan, uploaded once
+    void front_finalize();                      // the log-mel tables of q3_audio.cpp's make_plan, uploaded once per set
     // q3::resample_linear on the GPU, bit for bit; returns the output length, writes min(length, cap) samples when out != null
     int64_t resample_gpu(const float* in, int64_t n, int src_rate, int dst_rate, float* out, int64_t cap);
     // resample to 24 kHz (when sample_rate != 24000) + q3::log_mel: mel [128][*frames]; mel == null only sizes.  false: no frame (empty clip)
@@ -490,7 +533,8 @@ public:
     // ---- audio encoder of the 12 Hz tokenizer (q3_encoder.cpp): audio -> codes, fp32 throughout ----
     EncoderW* enc = nullptr;
     bool has_audio_encoder() const { return c.enc_hidden > 0; }
-    void encoder_finalize();
+    void encoder_finalize();                                  // the set's EncWeights (again), then encoder_runtime_init
+    void encoder_runtime_init();                              // this engine's EncoderW over ws.enc: RoPE tables; streams and workspace grow later
     void encoder_free();
     void encoder_poison();                                    // test hook: NaN bytes over the encoder's workspace (stream state lives outside it)
     static constexpr int64_t kEncMaxClipSamples = 1440000;    // 60 s at 24 kHz: one clip
@@ -565,12 +609,14 @@ public:
     // would issue (qkv_gemv_args: bit-identical).  The sampler of group g copies row (g, code) into qkv (SampleArgs::qkv_tab) and
     // announces it through qkv_in_ready; run_layers then starts the pass at its attention launch.  Built only by engines of one or two
     // slots whose predictor takes the fused b = 1 path (cp_qkv_table_applies); wider engines keep the GEMV when they drain to one slot.
+    // The table is the set's (WeightSet::cp_qkv_tab): built at most once, by the first holder it applies to, on that holder's stream,
+    // and published after its launches completed; this member is the engine's view of it (null where the table does not apply).
     float* cp_qkv_tab = nullptr;
     bool cp_qkv_table_on = true;   // Q3TTS_CP_QKV_TABLE=0 at engine creation: no table, the GEMV is launched (A/B knob, tests' second path)
     bool qkv_in_ready = false;     // predictor_passes -> run_layers: the sampler in front already wrote layer 0's qkv row
     bool cp_qkv_table_applies() const;
     void build_cp_qkv_table();
-    void free_cp_qkv_table();      // also drops the captured graphs: an nb = 1 graph has the table's address baked in
+    void free_cp_qkv_table();      // drops this engine's view and the captured graphs: an nb = 1 graph has the table's address baked in
     GemvArgs qkv_gemv_args(const DecStack& W, int l, const float* x, int ldx, float* out, int M) const;   // a layer's QKV projection on the GEMV path
     bool gemv_xlds = true;       // Q3TTS_GEMV_XLDS=0 at engine creation: GemvArgs::xlds of this engine's GEMV launches (A/B knob, tests' second path; same bits)
     bool gemv_psum_lead = true;  // Q3TTS_GEMV_PSUM_LEAD=0 at engine creation: GemvArgs::psum_lead of this engine's gate/up launches behind a kv-head-split o_proj (A/B knob, tests' second path; same bits)

@@ -16,15 +16,17 @@ struct SpkConv {
     const float* b = nullptr;
     int cin = 0, cout = 0, k = 1;
 };
+// Weights only: the repacked convs live in the engine's WeightSet (their storage in its allocs), every holder's `spk` points at them.
 struct SpeakerW {
     SpkConv tdnn0, tdnn1[3], res[3][16], tdnn2[3], se1[3], se2[3], mfa, asp_tdnn, asp_conv, fc;
 };
+void speaker_weights_free(SpeakerW* w) { delete w; }
 
 // GPU front end of the clone path (in-memory audio -> resample -> log-mel -> batched encoder): the extractor's tables on the device,
-// one pinned staging buffer and one device workspace, both grow-only, owned by the engine and freed with it.
+// one pinned staging buffer and one device workspace, both grow-only, owned by the engine and freed with it.  The tables themselves
+// are the set's (WeightSet::mel_tables_d): tb is this engine's view of them.
 struct SpkFront {
     MelTablesDev tb;
-    void* tables_d = nullptr;
     char* ws = nullptr; size_t ws_cap = 0;
     char* pin = nullptr; size_t pin_cap = 0;
 };
@@ -37,10 +39,8 @@ static constexpr size_t kAlign = 256;
 static size_t aligned(size_t b) { return (b + kAlign - 1) / kAlign * kAlign; }
 
 void Engine::speaker_free() {
-    delete spk;
-    spk = nullptr;
+    spk = nullptr;   // the set's
     if (spkf) {
-        if (spkf->tables_d) (void)hipFree(spkf->tables_d);
         if (spkf->ws) (void)hipFree(spkf->ws);
         if (spkf->pin) (void)hipHostFree(spkf->pin);
         delete spkf;
@@ -65,11 +65,15 @@ void Engine::front_finalize() {
     memcpy(&h[3072], p.lo.data(), 128 * 4);
     memcpy(&h[3200], p.mid.data(), 128 * 4);
     memcpy(&h[3328], p.hi.data(), 128 * 4);
-    std::unique_ptr<SpkFront> f(new SpkFront());
-    Q3_HIP_CHECK(hipMalloc(&f->tables_d, h.size() * 4));
-    spkf = f.release();
-    Q3_HIP_CHECK(hipMemcpy(spkf->tables_d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    const uint32_t* d = (const uint32_t*)spkf->tables_d;
+    ws.build_once([&] { return ws.mel_tables_d != nullptr; }, [&]() -> int64_t {   // once per set; the copy is synchronous
+        void* t = nullptr;
+        Q3_HIP_CHECK(hipMalloc(&t, h.size() * 4));
+        if (hipMemcpy(t, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(t); throw Error("log-mel tables: upload failed"); }
+        ws.mel_tables_d = t; ws.mel_bytes = (int64_t)(h.size() * 4);
+        return ws.mel_bytes;
+    });
+    spkf = new SpkFront();
+    const uint32_t* d = (const uint32_t*)ws.mel_tables_d;
     spkf->tb.window = (const float*)d; spkf->tb.tw_re = (const float*)(d + 1024); spkf->tb.tw_im = (const float*)(d + 1536);
     spkf->tb.rev = d + 2048;
     spkf->tb.lo = (const int32_t*)(d + 3072); spkf->tb.mid = (const int32_t*)(d + 3200); spkf->tb.hi = (const int32_t*)(d + 3328);
@@ -78,11 +82,12 @@ void Engine::front_finalize() {
 void Engine::speaker_finalize() {
     front_finalize();
     if (!has_speaker()) return;
-    if (!spk) spk = new SpeakerW();
+    if (!ws.spk) ws.spk = new SpeakerW();
+    spk = ws.spk;
     auto pack = [&](SpkConv& cv, const std::string& n) {
         const Tensor& w = T(n + ".w");
         cv.cout = (int)w.shape[0]; cv.cin = (int)w.shape[1]; cv.k = (int)w.shape[2];
-        if (!cv.w) cv.w = (float*)dmalloc((size_t)w.numel * sizeof(float));
+        if (!cv.w) cv.w = (float*)ws.dmalloc((size_t)w.numel * sizeof(float));
         launch_spk_repack((const float*)w.dev, cv.w, cv.cout, cv.cin, cv.k, stream);
         cv.b = (const float*)T(n + ".b").dev;
     };

@@ -52,6 +52,25 @@ TTSEngine::TTSEngine(const std::string& model_dir, bool audio_encoder) {
     spk_dim_ = cfg.spk_enc_dim;
     cfg_hidden_ = cfg.hidden;
     n_groups_ = cfg.n_groups;
+    model_dir_ = model_dir;
+    if (!load_tokenizer(model_dir)) return;
+    ready_ = true;
+}
+
+std::unique_ptr<TTSEngine> TTSEngine::share_weights(const TTSEngine& donor) {
+    if (!donor.ready_ || !donor.h_) { std::cerr << "[TTSEngine] share_weights: the donor is not ready" << std::endl; return nullptr; }
+    std::unique_ptr<TTSEngine> t(new TTSEngine());
+    t->max_batch_ = donor.max_batch_; t->max_ctx_ = donor.max_ctx_;
+    t->h_ = q3tts_create_sharing(donor.h_, donor.max_batch_, donor.max_ctx_, 0, 0);
+    if (!t->h_) { std::cerr << "[TTSEngine] share_weights: " << q3tts_last_error(nullptr) << std::endl; return nullptr; }
+    t->spk_dim_ = donor.spk_dim_; t->cfg_hidden_ = donor.cfg_hidden_; t->n_groups_ = donor.n_groups_;
+    t->model_dir_ = donor.model_dir_;
+    if (!t->load_tokenizer(t->model_dir_)) { std::cerr << "[TTSEngine] share_weights: " << t->error_msg_ << std::endl; return nullptr; }
+    t->ready_ = true;
+    return t;
+}
+
+bool TTSEngine::load_tokenizer(const std::string& model_dir) {
     // tokenizer files: where the reference looks (tts_onnx.cpp:110-121: <parent of model_dir>/models/
     // Qwen3-TTS-12Hz-0.6B-Base/{vocab.json,merges.txt}), then model_dir itself.  Present but unreadable is
     // an error, absent is a warning and text synthesis stays unavailable — as in the reference.
@@ -66,12 +85,12 @@ TTSEngine::TTSEngine(const std::string& model_dir, bool audio_encoder) {
         if (!tok_ || q3tts_tokenizer_load_vocab(tok_, (base / "vocab.json").string().c_str()) != 0 ||
             q3tts_tokenizer_load_merges(tok_, (base / "merges.txt").string().c_str()) != 0) {
             error_msg_ = "Failed to load tokenizer";
-            return;
+            return false;
         }
     } else {
         std::cerr << "[TTSEngine] Warning: Tokenizer not found at " << ref_base << std::endl;
     }
-    ready_ = true;
+    return true;
 }
 
 TTSEngine::~TTSEngine() {

@@ -8,6 +8,7 @@
 
 #include <cstdint>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -54,6 +55,10 @@ public:
     ~TTSEngine();
     TTSEngine(const TTSEngine&) = delete;
     TTSEngine& operator=(const TTSEngine&) = delete;
+    // A second ready engine on the donor's GPU over the same model directory's tokenizer and the donor's weights, held, not copied
+    // (q3tts_create_sharing): one engine per worker thread costs one set of weights.  Slots, KV cache, streams and every setting
+    // (seed, output format, speed, level, pitch, loudness: at their defaults) are its own.  Null, with the reason on stderr, on failure.
+    static std::unique_ptr<TTSEngine> share_weights(const TTSEngine& donor);
 
     std::vector<float> synthesize(const std::string& text, Language lang = Language::Auto,
                                   const SamplingParams& params = SamplingParams());
@@ -228,6 +233,9 @@ public:
     const std::string& get_error() const { return error_msg_; }
 
 private:
+    TTSEngine() = default;                              // share_weights fills it in
+    bool load_tokenizer(const std::string& model_dir);  // false: present but unreadable (error_msg_ set); absent is a warning
+    std::string model_dir_;
     bool wrap_text(const std::string& text, std::vector<int64_t>& ids) const;
     std::vector<int64_t> audio_stream_push_any(int id, const void* pcm, size_t n, bool finish, bool* ok, int kind);   // kind: 0 float, 1 int16, 2 G.711 bytes
     q3tts_engine* h_ = nullptr;

@@ -127,6 +127,7 @@ EXPORTS = [
     "q3tts_codec_stream_set_pitch", "q3tts_engine_set_pitch",
     "q3tts_loudness_coeffs", "q3tts_loudness_emitted", "q3tts_loudness_lufs", "q3tts_loudness_last_error", "q3tts_loudness_begin",
     "q3tts_loudness_push_batch_host", "q3tts_loudness_end", "q3tts_codec_stream_set_loudness", "q3tts_engine_set_loudness",
+    "q3tts_create_sharing", "q3tts_weights_info",
 ]
 
 # q3tts_audio_cb: int (*)(void* user, int utt, int frame_begin, int frame_end, const float* pcm, int64_t n_samples, int finished)
@@ -160,6 +161,9 @@ def lib():
     L.q3tts_create_pooled.restype = vp
     L.q3tts_create_pooled.argtypes = [C.POINTER(Config), i32, i32, i32, C.c_int64, C.c_uint32]
     L.q3tts_kv_pool_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.q3tts_create_sharing.restype = vp
+    L.q3tts_create_sharing.argtypes = [vp, i32, i32, C.c_int64, C.c_uint32]
+    L.q3tts_weights_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]
     L.q3tts_sched_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
     L.q3tts_destroy.argtypes = [vp]
     L.q3tts_last_error.restype = C.c_char_p
@@ -332,6 +336,28 @@ class Engine:
         self.h = self.L.q3tts_create_pooled(C.byref(cfg), device, max_batch, max_ctx, kv_pool_tokens, flags)
         if not self.h:
             raise RuntimeError("q3tts_create failed: " + self.L.q3tts_last_error(None).decode())
+
+    def share(self, max_batch=1, max_ctx=None, flags=None, kv_pool_tokens=0):
+        """A second engine on this engine's GPU that holds this engine's finalized weights instead of a copy (q3tts_create_sharing).
+        Slots, KV pool, workspaces, streams and graphs are its own; it is ready at once.  None: this engine's value.  May be called
+        while this engine generates on another thread.  While both live, the weights cannot be changed on either."""
+        other = Engine.__new__(Engine)
+        other.L = self.L
+        other.cfg = self.cfg
+        other.max_batch = max_batch
+        other.max_ctx = self.max_ctx if max_ctx is None else max_ctx
+        other.flags = self.flags if flags is None else flags
+        other.h = self.L.q3tts_create_sharing(self.h, max_batch, other.max_ctx, kv_pool_tokens, other.flags)
+        if not other.h:
+            raise RuntimeError("q3tts_create_sharing failed: " + self.L.q3tts_last_error(None).decode())
+        return other
+
+    def weights_info(self):
+        """{'shared_bytes': HBM of the weight set (registry + derived copies), 'holders': engines that hold it,
+        'private_weight_bytes': weights or derived copies this engine owns outside the set (0: everything is shared)}"""
+        a, b, c = C.c_int64(), C.c_int32(), C.c_int64()
+        self._ck(self.L.q3tts_weights_info(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"shared_bytes": a.value, "holders": b.value, "private_weight_bytes": c.value}
 
     def kv_pool_info(self):
         """(tokens per page, pages in the pool, pages free)"""
