@@ -963,6 +963,70 @@ int q3tts_codec_stream_set_loudness(q3tts_engine* e, int stream_id, int32_t targ
  * up to the length they have without the stage.  Codes, frame counts and RNG use are untouched; the callback's signature stays. */
 int q3tts_engine_set_loudness(q3tts_engine* e, int enabled, int32_t target_dlufs, int32_t range_cb, int32_t start_cb);
 
+/* ---- tone: carried-state parametric equaliser ([HINT] no counterpart in the reference, which has no equaliser) ----
+ * A stage between the stretcher and the loudness stage at 24 kHz, so that the meter measures what is heard and the limiter stands
+ * behind anything that can boost.  With it the order of the six stages is
+ *   vocoder -> pitch -> stretcher -> tone -> loudness -> level -> sink
+ * on the GPU, all tone stages of a push in one launch.  A stage is a cascade of n = 1 .. 8 biquad sections, each one of
+ * { kind, freq_hz, gain_cb, q_permille }: kind high-pass, low-pass, low shelf, high shelf or peak; freq_hz 20 .. 11000; gain_cb
+ * -240 .. +240 in 0.1 dB steps (must be 0 for a high- or low-pass); q_permille 100 .. 10000 (Q 0.1 .. 10).  There is no "no stage"
+ * value: no sections is no stage, no launch, and the bytes delivered without one.  A value out of range is refused with the field,
+ * the section's index and the value named.
+ * 1. Coefficients, in double on the host, the RBJ Audio-EQ-Cookbook forms: w0 = 2 pi freq_hz / 24000, c = cos(w0),
+ *    alpha = sin(w0) / (2 Q), Q = q_permille / 1000, A = 10^(gain_dB / 40) = 10^(gain_cb / 400).
+ *    High-pass: b = ((1 + c) / 2, -(1 + c), (1 + c) / 2), a = (1 + alpha, -2 c, 1 - alpha).
+ *    Low-pass:  b = ((1 - c) / 2, 1 - c, (1 - c) / 2), a as the high-pass's.
+ *    Peak:      b = (1 + alpha A, -2 c, 1 - alpha A), a = (1 + alpha / A, -2 c, 1 - alpha / A).
+ *    Shelves, with s = 2 sqrt(A) alpha, p = A + 1, m = A - 1:
+ *    low shelf  b = (A ((p - m c) + s), 2 A (m - p c), A ((p - m c) - s)), a = ((p + m c) + s, -2 (m + p c), (p + m c) - s);
+ *    high shelf b = (A ((p + m c) + s), -2 A (m + p c), A ((p + m c) - s)), a = ((p - m c) + s, 2 (m - p c), (p - m c) - s).
+ *    Each of b0 b1 b2 a1 a2 is divided by a0.  q3tts_tone_coeffs returns the very doubles the device uses; a restatement takes them
+ *    from there, so that nothing rests on two maths libraries agreeing in the last bit.
+ * 2. Recursion, the loudness stage's biquad repeated: s_0[k] = (double)x[k]; for section j = 1 .. n:
+ *    ff = (b0 s_{j-1}[k] + b1 s_{j-1}[k-1]) + b2 s_{j-1}[k-2], s_j[k] = (ff - a2 s_j[k-2]) - a1 s_j[k-1]; y[k] = (float)s_n[k].
+ *    Every operation is one rounded IEEE fp64 operation in this order (the library is built with -ffp-contract=off); nothing is rounded
+ *    to float between sections; all history is zero before sample 0; subnormals are kept (gradual underflow) in the fp64 arithmetic and
+ *    in the final conversion, which rounds to nearest even.
+ * 3. Host rule: a stage that has received N samples has emitted N.  No latency, no look-ahead; finish flushes nothing, and a push of 0
+ *    samples with finish is allowed.
+ * 4. Carry, in two alternating halves: two doubles per signal s_0 .. s_n, (n + 1) * 2 in all.
+ * So a sample's bits depend on its absolute index, the input and the sections alone: never on how the audio was cut into pushes or on
+ * which stages shared a launch.  Non-finite input: the formulas apply as written (a NaN stays in the history).
+ * Known limits: a primed stream's tone stage (q3tts_codec_stream_prime_batch_host, q3tts_synthesize_continue_stream_host) starts from
+ * zero history, like the other stages start from silence.  The sections of a stage cannot change while it runs. */
+#define Q3TTS_TONE_HIGHPASS 1
+#define Q3TTS_TONE_LOWPASS 2
+#define Q3TTS_TONE_LOWSHELF 3
+#define Q3TTS_TONE_HIGHSHELF 4
+#define Q3TTS_TONE_PEAK 5
+#define Q3TTS_TONE_MAX_SECTIONS 8
+typedef struct { int32_t kind, freq_hz, gain_cb, q_permille; } q3tts_tone_section;
+/* Host only, no engine.  out[j] = { b0, b1, b2, a1, a2 } of section j by the formulas above.  -1 for n outside 1 .. 8 or a value out
+ * of range (q3tts_tone_last_error() then names it; thread-local, valid until the thread's next tone_coeffs / tone_parse call). */
+int q3tts_tone_coeffs(int32_t n, const q3tts_tone_section* sections, double (*out)[5]);
+/* Host only: the sections of a spec string, at most 8 into out, their number into *n.  A spec is a preset's name (telephone, rumble,
+ * presence, warm) or sections separated by commas, kind:Hz:Q for hp and lp, kind:Hz:dB:Q for ls, hs and peak, as in
+ * "hp:300:0.707,peak:2500:+3:1.0,lp:3400:0.707".  dB is rounded to 0.1, Q to 0.001.  -1 for what it cannot read or what is out of range
+ * (q3tts_tone_last_error()).  The presets are unheard and untuned: no checkpoint exists yet. */
+int q3tts_tone_parse(const char* spec, q3tts_tone_section* out, int32_t* n);
+const char* q3tts_tone_last_error(void);
+/* Tone stages on their own: the stage by itself, fed 24 kHz float from the host.  A stage accepts at most one hour of input
+ * (86 400 000 samples), a push at most 1 440 000.  At most 4096 stages are open at a time (vocoder streams' included). */
+int q3tts_tone_begin(q3tts_engine* e, int32_t n, const q3tts_tone_section* sections, int* id);
+/* As q3tts_level_push_batch_host: n stages (distinct, open, not finished), validated completely before any stage moves; out_len[i]
+ * is n_in[i]. */
+int q3tts_tone_push_batch_host(q3tts_engine* e, int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in,
+                               const uint8_t* finish, float* const* out, int64_t cap_samples, int64_t* out_len);
+int q3tts_tone_end(q3tts_engine* e, int id);
+/* Vocoder streams.  A stream delivers through a tone stage from its first sample on: refused, by name, once the stream has delivered
+ * a sample.  n = 0 takes the stage away again.  q3tts_codec_stream_push_batch_any_host serves such streams: the stage reads its input
+ * where the stage in front left it and feeds the stream's later stages in the same push; finish[s] is allowed on a stream with a tone
+ * stage and no sink.  The float entries refuse a stream with a tone stage by name. */
+int q3tts_codec_stream_set_tone(q3tts_engine* e, int stream_id, int32_t n, const q3tts_tone_section* sections);
+/* The scheduler: one setter for the four streaming entries, beside q3tts_engine_set_sink / _speed / _level / _pitch / _loudness.
+ * n = 0 takes the stage away.  Lengths, codes, frame counts and RNG use are untouched; the callback's signature stays. */
+int q3tts_engine_set_tone(q3tts_engine* e, int32_t n, const q3tts_tone_section* sections);
+
 /* ---- text front end: the reference's byte-level BPE tokenizer ---- */
 /* Replaces leaxer_qwen::io::load_vocab / load_merges / is_tokenizer_ready / tokenize (reference
  * src/io/tokenizer.h:13-22, src/io/tokenizer.cpp:538-561) with the same ids for the same files and text.

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libq3tts_hip.so")
-SOURCES = ["q3_decode_kernels.hip", "q3_gemm_kernels.hip", "q3_codec_kernels.hip", "q3_speaker_kernels.hip", "q3_encoder_kernels.hip", "q3_speed_kernels.hip", "q3_level_kernels.hip", "q3_pitch_kernels.hip", "q3_loudness_kernels.hip", "q3_engine.cpp", "q3_begin.cpp", "q3_codec.cpp", "q3_stage.cpp", "q3_pcm_sink.cpp", "q3_speed.cpp", "q3_level.cpp", "q3_pitch.cpp", "q3_loudness.cpp",
+SOURCES = ["q3_decode_kernels.hip", "q3_gemm_kernels.hip", "q3_codec_kernels.hip", "q3_speaker_kernels.hip", "q3_encoder_kernels.hip", "q3_speed_kernels.hip", "q3_level_kernels.hip", "q3_pitch_kernels.hip", "q3_loudness_kernels.hip", "q3_tone_kernels.hip", "q3_engine.cpp", "q3_begin.cpp", "q3_codec.cpp", "q3_stage.cpp", "q3_pcm_sink.cpp", "q3_speed.cpp", "q3_level.cpp", "q3_pitch.cpp", "q3_loudness.cpp", "q3_tone.cpp",
            "q3_speaker.cpp", "q3_encoder.cpp", "q3_audio.cpp", "q3_bpe.cpp", "q3_job.cpp", "q3_capi.cpp"]
 HEADERS = ["q3_common.h", "q3_engine.h", "q3_kvpool.h", "q3_stage.h", "q3_weight_share.h", "q3_begin_plan.h", "q3_codec_plan.h", "q3_job.h", "q3_bpe.h", "q3_audio.h", os.path.join("..", "..", "include", "q3tts.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall", "-Wno-unused-function",

@@ -99,6 +99,7 @@ static void usage(const char* prog) {
     printf("  --out-format F        sample format of the WAV: pcm16 (default), mulaw or alaw (G.711, 8 bits: WAV format tags 7 / 6), encoded on the GPU in the sink; composes with --out-rate (a telephone line: --out-rate 8000), --stream-chunk and the stage flags\n");
     printf("  --speed X             speaking rate (0.5 .. 2.0; default 1.0): X times as fast at the same pitch, WSOLA time stretch on the GPU; composes with --out-rate and --stream-chunk\n");
     printf("  --pitch ST            pitch shift in semitones (-12 .. +12; default 0): the fundamental moves, the formants stay, TD-PSOLA on the GPU ahead of --speed; composes with --speed, --gain, --limit and --out-rate\n");
+    printf("  --eq SPEC             tone: a preset (telephone, rumble, presence, warm; unheard and untuned) or up to 8 sections kind:Hz[:dB]:Q separated by commas, kind one of hp, lp, ls, hs, peak, e.g. hp:300:0.707,peak:2500:+3:1.0,lp:3400:0.707; biquads in double on the GPU behind --speed and ahead of --loudness; no latency; composes with every stage flag, --out-rate and --out-format\n");
     printf("  --loudness LUFS       programme loudness to aim for (-40 .. -5; default: none): a BS.1770 meter and a gain that follows it by at most 1 dB per 100 ms, on the GPU behind --speed and ahead of --gain / --limit; 100 ms latency; composes with --pitch, --speed, --gain, --limit and --out-rate\n");
     printf("  --loudness-range DB   with --loudness: the largest boost or cut (0 .. 40; default 20)\n");
     printf("  --gain DB             output gain in decibels (-60 .. +40, rounded to 0.1 dB; default 0), applied on the GPU behind --speed and ahead of --out-rate\n");
@@ -210,6 +211,7 @@ int main(int argc, char** argv) {
     bool have_encode_chunk = false;
     double speed = 1.0, gain_db = 0.0, limit = 0.0, pitch_st = 0.0, loudness = 0.0, loudness_range = 20.0;
     bool have_loudness = false;
+    std::string eq;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         const bool more = i + 1 < argc;
@@ -240,6 +242,7 @@ int main(int argc, char** argv) {
         else if (a == "--out-format" && more) out_format = argv[++i];
         else if (a == "--speed" && more) speed = atof(argv[++i]);
         else if (a == "--pitch" && more) pitch_st = atof(argv[++i]);
+        else if (a == "--eq" && more) eq = argv[++i];
         else if (a == "--loudness" && more) { loudness = atof(argv[++i]); have_loudness = true; }
         else if (a == "--loudness-range" && more) loudness_range = atof(argv[++i]);
         else if (a == "--gain" && more) gain_db = atof(argv[++i]);
@@ -326,6 +329,10 @@ int main(int argc, char** argv) {
     if (!ref.empty()) printf("Reference: %s\n", ref.c_str());
     printf("Language: %s\nOutput: %s\n\n", lang.c_str(), output.c_str());
 
+    if (!eq.empty()) {   // a spec that cannot be read is refused before the model is loaded
+        q3tts_tone_section sections[Q3TTS_TONE_MAX_SECTIONS]; int32_t n_sections = 0;
+        if (q3tts_tone_parse(eq.c_str(), sections, &n_sections) != 0) { fprintf(stderr, "Error: --eq %s: %s\n", eq.c_str(), q3tts_tone_last_error()); return 1; }
+    }
     TTSEngine engine(model, icl);
     if (!engine.is_ready()) { fprintf(stderr, "Error: %s\n", engine.get_error().c_str()); return 1; }
     engine.set_seed(seed);
@@ -347,6 +354,8 @@ int main(int argc, char** argv) {
     // --pitch: r = round(1000 2^(ST / 12)) permille; 0 semitones is no stage (the bytes written without the flag)
     if (!(pitch_st == pitch_st) || pitch_st < -12.0 || pitch_st > 12.0) { fprintf(stderr, "Error: --pitch %g is outside -12 .. +12\n", pitch_st); return 1; }
     if (pitch_st != 0.0 && !engine.set_pitch((float)pitch_st)) { fprintf(stderr, "Error: --pitch %g: %s\n", pitch_st, engine.get_error().c_str()); return 1; }
+    // --eq: a preset or sections; without the flag there is no stage (the bytes written before)
+    if (!eq.empty() && !engine.set_tone(eq.c_str())) { fprintf(stderr, "Error: --eq %s: %s\n", eq.c_str(), engine.get_error().c_str()); return 1; }
     // --loudness / --loudness-range: tenths of a LUFS and centibels; without the flag there is no stage (the bytes written before)
     if (have_loudness && !engine.set_loudness((float)loudness, (float)loudness_range)) {
         fprintf(stderr, "Error: --loudness %g --loudness-range %g: %s\n", loudness, loudness_range, engine.get_error().c_str());

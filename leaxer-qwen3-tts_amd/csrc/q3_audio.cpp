@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <stdexcept>
@@ -332,6 +333,84 @@ double loudness_lufs(const int64_t* E, int64_t n, int mode) {
         if (W >= kLoudGate && z > rel) { sum_rel += z; ++n_rel; }
     }
     return n_rel == 0 ? ninf : lufs(sum_rel / (double)n_rel);
+}
+
+// ---- tone (q3_audio.h) ----
+static const char* const kToneFields[4] = { "kind", "freq_hz", "gain_cb", "q_permille" };
+static std::invalid_argument tone_refusal(int j, int field, int64_t v, const std::string& why) {
+    return std::invalid_argument("tone: section " + std::to_string(j) + " " + kToneFields[field] + " " + std::to_string(v) + " " + why);
+}
+void tone_check(int n, const ToneSection* s) {
+    if (n < 1 || n > kToneMaxSections) throw std::invalid_argument("tone: " + std::to_string(n) + " sections is outside 1 .. " + std::to_string(kToneMaxSections));
+    if (!s) throw std::invalid_argument("tone: NULL argument");
+    for (int j = 0; j < n; ++j) {
+        if (s[j].kind < kToneHighpass || s[j].kind > kTonePeak) throw tone_refusal(j, 0, s[j].kind, "is none of high-pass (1), low-pass (2), low shelf (3), high shelf (4), peak (5)");
+        if (s[j].freq_hz < kToneFreqMin || s[j].freq_hz > kToneFreqMax) throw tone_refusal(j, 1, s[j].freq_hz, "Hz is outside " + std::to_string(kToneFreqMin) + " .. " + std::to_string(kToneFreqMax));
+        if (s[j].gain_cb < -kToneGainMax || s[j].gain_cb > kToneGainMax) throw tone_refusal(j, 2, s[j].gain_cb, "centibels is outside " + std::to_string(-kToneGainMax) + " .. " + std::to_string(kToneGainMax));
+        if (s[j].gain_cb != 0 && s[j].kind <= kToneLowpass) throw tone_refusal(j, 2, s[j].gain_cb, "centibels must be 0 for a high-pass or a low-pass");
+        if (s[j].q_permille < kToneQMin || s[j].q_permille > kToneQMax) throw tone_refusal(j, 3, s[j].q_permille, "is outside " + std::to_string(kToneQMin) + " .. " + std::to_string(kToneQMax));
+    }
+}
+void tone_coeffs(int n, const ToneSection* s, double (*out)[5]) {
+    const double pi = 3.14159265358979323846;
+    for (int j = 0; j < n; ++j) {
+        const double w0 = 2.0 * pi * (double)s[j].freq_hz / 24000.0, cw = std::cos(w0), alpha = std::sin(w0) / (2.0 * ((double)s[j].q_permille / 1000.0));
+        const double A = std::pow(10.0, (double)s[j].gain_cb / 400.0);
+        double b0, b1, b2, a0, a1, a2;
+        switch (s[j].kind) {
+        case kToneHighpass: b0 = (1.0 + cw) / 2.0; b1 = -(1.0 + cw); b2 = b0; a0 = 1.0 + alpha; a1 = -2.0 * cw; a2 = 1.0 - alpha; break;
+        case kToneLowpass:  b0 = (1.0 - cw) / 2.0; b1 = 1.0 - cw; b2 = b0; a0 = 1.0 + alpha; a1 = -2.0 * cw; a2 = 1.0 - alpha; break;
+        case kTonePeak:     b0 = 1.0 + alpha * A; b1 = -2.0 * cw; b2 = 1.0 - alpha * A; a0 = 1.0 + alpha / A; a1 = -2.0 * cw; a2 = 1.0 - alpha / A; break;
+        case kToneLowshelf: {
+            const double sq = 2.0 * std::sqrt(A) * alpha, p = A + 1.0, m = A - 1.0;
+            b0 = A * ((p - m * cw) + sq); b1 = 2.0 * A * (m - p * cw); b2 = A * ((p - m * cw) - sq);
+            a0 = (p + m * cw) + sq; a1 = -2.0 * (m + p * cw); a2 = (p + m * cw) - sq; break; }
+        default: {          // kToneHighshelf
+            const double sq = 2.0 * std::sqrt(A) * alpha, p = A + 1.0, m = A - 1.0;
+            b0 = A * ((p + m * cw) + sq); b1 = -2.0 * A * (m + p * cw); b2 = A * ((p + m * cw) - sq);
+            a0 = (p - m * cw) + sq; a1 = 2.0 * (m - p * cw); a2 = (p - m * cw) - sq; break; }
+        }
+        out[j][0] = b0 / a0; out[j][1] = b1 / a0; out[j][2] = b2 / a0; out[j][3] = a1 / a0; out[j][4] = a2 / a0;
+    }
+}
+// The presets have never been heard: no checkpoint exists, so they are textbook starting points, untuned.
+static const struct { const char* name; const char* spec; } kTonePresets[] = {
+    { "telephone", "hp:300:0.707,hp:300:0.707,peak:2500:+3:1.0,lp:3400:0.707,lp:3400:0.707" },
+    { "rumble", "hp:80:0.707" },
+    { "presence", "peak:3000:+4:0.9,hs:8000:+2:0.707" },
+    { "warm", "ls:200:+3:0.707,hs:6000:-4:0.707" },
+};
+std::vector<ToneSection> tone_parse(const std::string& spec_in) {
+    std::string spec = spec_in;
+    for (const auto& p : kTonePresets) if (spec == p.name) spec = p.spec;
+    if (spec.empty()) throw std::invalid_argument("tone: empty spec (a preset: telephone, rumble, presence, warm; or kind:Hz[:dB]:Q sections separated by commas)");
+    // a number in a field: the whole field must be one; scaled and rounded to the integer the stage takes
+    auto number = [](const std::string& f, int j, const char* what, double scale) -> int32_t {
+        char* end = nullptr;
+        const double v = f.empty() ? 0.0 : std::strtod(f.c_str(), &end);
+        if (f.empty() || !end || *end != '\0' || !(v > -1e6 && v < 1e6)) throw std::invalid_argument("tone: section " + std::to_string(j) + " " + what + " '" + f + "' is no number");
+        return (int32_t)std::llround(v * scale);
+    };
+    std::vector<ToneSection> out;
+    size_t pos = 0;
+    for (int j = 0; pos <= spec.size(); ++j) {
+        const size_t comma = std::min(spec.find(',', pos), spec.size());
+        const std::string sec = spec.substr(pos, comma - pos);
+        pos = comma + 1;
+        std::vector<std::string> f;
+        for (size_t a = 0; a <= sec.size();) { const size_t c = std::min(sec.find(':', a), sec.size()); f.push_back(sec.substr(a, c - a)); a = c + 1; }
+        ToneSection s{ 0, 0, 0, 0 };
+        s.kind = f[0] == "hp" ? kToneHighpass : f[0] == "lp" ? kToneLowpass : f[0] == "ls" ? kToneLowshelf : f[0] == "hs" ? kToneHighshelf : f[0] == "peak" ? kTonePeak : 0;
+        if (s.kind == 0) throw std::invalid_argument("tone: section " + std::to_string(j) + " kind '" + f[0] + "' is none of hp, lp, ls, hs, peak");
+        const bool gained = s.kind > kToneLowpass;
+        if (f.size() != (gained ? 4u : 3u)) throw std::invalid_argument("tone: section " + std::to_string(j) + " '" + sec + "' is not " + (gained ? "kind:Hz:dB:Q" : "kind:Hz:Q"));
+        s.freq_hz = number(f[1], j, "freq_hz", 1.0);
+        if (gained) s.gain_cb = number(f[2], j, "gain_cb", 10.0);
+        s.q_permille = number(f.back(), j, "q_permille", 1000.0);
+        out.push_back(s);
+    }
+    tone_check((int)out.size(), out.data());
+    return out;
 }
 
 // ---------------------------------------------------------------------------------------------

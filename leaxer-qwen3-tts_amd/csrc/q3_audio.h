@@ -132,6 +132,25 @@ inline int64_t loudness_emitted(int target_dlufs, int64_t n_received, bool finis
 // relative gate at -10 LU).  -inf when the span is not there or nothing passes the gates.
 double loudness_lufs(const int64_t* E, int64_t n, int mode);
 
+// ---- tone: a cascade of 1 .. kToneMaxSections biquads at 24 kHz (the arithmetic is fixed in include/q3tts.h) ----
+// A section is { kind, freq_hz, gain_cb, q_permille }, all integers (q3tts_tone_section has the same layout).  The coefficients are the
+// RBJ Audio-EQ-Cookbook forms in double, normalised by a0: w0 = 2 pi f / 24000, alpha = sin(w0) / (2 Q), A = 10^(gain_cb / 400).  A
+// stage carries two doubles per signal (the input and each section's output): kToneStateDoubles per half at the most.  It emits what
+// it receives: no latency, nothing held back, nothing flushed.
+constexpr int kToneMaxSections = 8, kToneHighpass = 1, kToneLowpass = 2, kToneLowshelf = 3, kToneHighshelf = 4, kTonePeak = 5;
+constexpr int kToneFreqMin = 20, kToneFreqMax = 11000, kToneGainMax = 240, kToneQMin = 100, kToneQMax = 10000;
+constexpr int kToneStateDoubles = 2 * (kToneMaxSections + 1);
+constexpr int kToneSegment = 2048;   // samples k_tone stages through LDS at a time (tests/test_gpu_tone.py reads it here to cut pushes around it)
+struct ToneSection { int32_t kind, freq_hz, gain_cb, q_permille; };
+// throws std::invalid_argument naming the field, the section's index and the value that is out of range (n outside 1 .. 8 as well)
+void tone_check(int n, const ToneSection* sections);
+// out[j] = { b0, b1, b2, a1, a2 } of section j at 24 kHz; the sections must have passed tone_check
+void tone_coeffs(int n, const ToneSection* sections, double (*out)[5]);
+// sections from a spec string: a preset's name (telephone, rumble, presence, warm) or comma-separated kind:Hz[:dB]:Q with kind one of
+// hp, lp, ls, hs, peak (dB only, and always, for ls, hs and peak).  Throws std::invalid_argument naming what it could not read; the
+// values are range-checked by tone_check.
+std::vector<ToneSection> tone_parse(const std::string& spec);
+
 struct MelSpec { // the settings of tts_onnx.cpp:347-354
     int sample_rate = 24000, n_fft = 1024, hop = 256, win = 1024, n_mels = 128;
     float fmin = 0.0f, fmax = 12000.0f;

@@ -616,6 +616,69 @@ int q3tts_engine_set_loudness(q3tts_engine* h, int enabled, int32_t target_dlufs
     Q3_API_END(h)
 }
 
+// ---- tone (include/q3tts.h "tone") ----
+static_assert(sizeof(q3tts_tone_section) == sizeof(q3::ToneSection) && offsetof(q3tts_tone_section, q_permille) == offsetof(q3::ToneSection, q_permille), "q3tts_tone_section is q3::ToneSection");
+static const q3::ToneSection* tone_sections_of(const q3tts_tone_section* s) { return reinterpret_cast<const q3::ToneSection*>(s); }
+static thread_local std::string g_tone_err;
+const char* q3tts_tone_last_error(void) { return g_tone_err.c_str(); }
+int q3tts_tone_coeffs(int32_t n, const q3tts_tone_section* sections, double (*out)[5]) {
+    g_tone_err.clear();
+    try {
+        if (!out) throw std::invalid_argument("tone: NULL argument");
+        q3::tone_check(n, tone_sections_of(sections));
+        q3::tone_coeffs(n, tone_sections_of(sections), out);
+        return 0;
+    } catch (const std::exception& ex) { g_tone_err = ex.what(); return -1; }
+    catch (...) { g_tone_err = "unknown error"; return -1; }
+}
+int q3tts_tone_parse(const char* spec, q3tts_tone_section* out, int32_t* n) {
+    g_tone_err.clear();
+    try {
+        if (!spec || !out || !n) throw std::invalid_argument("tone: NULL argument");
+        const std::vector<q3::ToneSection> v = q3::tone_parse(spec);
+        for (size_t j = 0; j < v.size(); ++j) out[j] = q3tts_tone_section{ v[j].kind, v[j].freq_hz, v[j].gain_cb, v[j].q_permille };
+        *n = (int32_t)v.size();
+        return 0;
+    } catch (const std::exception& ex) { g_tone_err = ex.what(); return -1; }
+    catch (...) { g_tone_err = "unknown error"; return -1; }
+}
+int q3tts_tone_begin(q3tts_engine* h, int32_t n, const q3tts_tone_section* sections, int* id) {
+    Q3_API_BEGIN(h)
+    if (!id) throw q3::Error("tone: NULL argument");
+    *id = h->e->tone.begin(n, tone_sections_of(sections));
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_tone_push_batch_host(q3tts_engine* h, int n, const int32_t* ids, const float* const* pcm24, const int64_t* n_in,
+                               const uint8_t* finish, float* const* out, int64_t cap_samples, int64_t* out_len) {
+    Q3_API_BEGIN(h)
+    h->e->tone.push_batch_host(n, ids, pcm24, n_in, finish, (void* const*)out, cap_samples, out_len);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_tone_end(q3tts_engine* h, int id) {
+    Q3_API_BEGIN(h)
+    h->e->tone.end(id);
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_codec_stream_set_tone(q3tts_engine* h, int stream_id, int32_t n, const q3tts_tone_section* sections) {
+    Q3_API_BEGIN(h)
+    h->e->codec_stream_set_tone(stream_id, n, tone_sections_of(sections));
+    return 0;
+    Q3_API_END(h)
+}
+int q3tts_engine_set_tone(q3tts_engine* h, int32_t n, const q3tts_tone_section* sections) {
+    Q3_API_BEGIN(h)
+    if (n != 0) {
+        try { q3::tone_check(n, tone_sections_of(sections)); } catch (const std::invalid_argument& ex) { throw q3::Error(std::string("engine_set_tone: ") + ex.what()); }
+        for (int j = 0; j < n; ++j) h->stages.tone[j] = tone_sections_of(sections)[j];
+    }
+    h->stages.tone_n = n;
+    return 0;
+    Q3_API_END(h)
+}
+
 int q3tts_codec_stream_info(q3tts_engine* h, int stream_id, int* n_done, int* kv_capacity_rows, int64_t* bytes) {
     Q3_API_BEGIN(h)
     h->e->codec_stream_info(stream_id, n_done, kv_capacity_rows, bytes);

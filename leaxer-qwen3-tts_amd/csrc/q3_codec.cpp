@@ -101,10 +101,10 @@ struct CodecW {
     // stage: the stream's stages by Engine::StageKind, in the order its audio passes them (ids of Engine::stages[k]; -1: none, all -1:
     // the stream delivers 24 kHz float); delivered: a push has returned samples
     struct Stream { bool used = false; int cap = 0, P = 0, pshift = 0, n_done = 0, kv_rows = 0, h_cap = 0, h_rows = 0; float* kv = nullptr; float* hpost = nullptr;
-                    int stage[Engine::SK_N] = { -1, -1, -1, -1, -1 }; bool delivered = false;
+                    int stage[Engine::SK_N] = { -1, -1, -1, -1, -1, -1 }; bool delivered = false;
                     const char* has() const {   // what the float entries refuse the stream by; nullptr: no stage
                         return stage[Engine::SK_SINK] >= 0 ? " has a sink" : stage[Engine::SK_SPEED] >= 0 ? " has a speed" : stage[Engine::SK_LEVEL] >= 0 ? " has a level" : stage[Engine::SK_PITCH] >= 0 ? " has a pitch"
-                             : stage[Engine::SK_LOUD] >= 0 ? " has a loudness" : nullptr; } };
+                             : stage[Engine::SK_LOUD] >= 0 ? " has a loudness" : stage[Engine::SK_TONE] >= 0 ? " has a tone" : nullptr; } };
     std::vector<Stream> streams;
     char* stream_arena = nullptr; size_t stream_arena_bytes = 0;
     std::vector<int> slot_stream;          // slot -> stream id (-1: none): q3tts_slot_codec_decode_range_host's implicit stream
@@ -829,6 +829,14 @@ void Engine::codec_stream_set_loudness(int sid, int target, int range, int start
     });
 }
 
+void Engine::codec_stream_set_tone(int sid, int n, const ToneSection* sections) {
+    stream_set_stage(*this, sid, "codec_stream_set_tone", SK_TONE, [&] {
+        if (n == 0) return -1;
+        try { tone_check(n, sections); } catch (const std::invalid_argument& ex) { throw Error(std::string("codec_stream_set_tone: ") + ex.what()); }
+        return tone.begin(n, sections);
+    });
+}
+
 void Engine::codec_stream_set_speed(int sid, int speed_permille) {
     stream_set_stage(*this, sid, "codec_stream_set_speed", SK_SPEED, [&] { return speed_permille == 1000 ? -1 : speed.begin(speed_permille); });
 }
@@ -1192,6 +1200,7 @@ void Engine::slots_codec_decode_new(int n_slots, const int32_t* slots, float* co
             if (ss.pitch > 0 && ss.pitch != 1000 && have[SK_PITCH] < 0) codec_stream_set_pitch(sid, ss.pitch);
             if (ss.sink_rate > 0 && have[SK_SINK] < 0) codec_stream_set_sink(sid, ss.sink_rate, ss.sink_format);
             if (ss.speed > 0 && ss.speed != 1000 && have[SK_SPEED] < 0) codec_stream_set_speed(sid, ss.speed);
+            if (ss.tone_n > 0 && have[SK_TONE] < 0) codec_stream_set_tone(sid, ss.tone_n, ss.tone);
             if (ss.loud != 0 && have[SK_LOUD] < 0) codec_stream_set_loudness(sid, ss.loud_target, ss.loud_range, ss.loud_start);
             if ((ss.gain_cb != 0 || ss.ceiling != 0) && have[SK_LEVEL] < 0) codec_stream_set_level(sid, ss.gain_cb, ss.ceiling);
         }

@@ -579,6 +579,20 @@ struct LoudDesc {
 };
 void launch_loudness(const LoudDesc* tab /* device, [n] */, int n, hipStream_t s);
 
+// ---- tone (q3_tone.cpp): a cascade of 1 .. 8 biquads on 24 kHz float PCM, with carried state ----
+// One stage of one push.  state_in / state_out: the two halves of the stage's allocation, (n_sections + 1) * 2 doubles each: signal s
+// (0: the input, s: section s's output) keeps its last sample at [2 s] and the one before at [2 s + 1].  The launch's wave filters the
+// push's n_new >= 1 samples at x_new into out (as many) and writes the state behind them into state_out.  first: the stage has received
+// nothing yet, so its history is zero, not state_in.
+struct ToneDesc {
+    const double* state_in = nullptr; double* state_out = nullptr;
+    const float* x_new = nullptr;       // n_new samples
+    float* out = nullptr;               // n_new samples
+    double c[8][5] = {};                // tone_coeffs: b0 b1 b2 a1 a2 of each section
+    int32_t n_new = 0, n_sections = 0, first = 0, pad = 0;
+};
+void launch_tone(const ToneDesc* tab /* device, [n] */, int n, hipStream_t s);
+
 
 // ---- speaker encoder + GPU audio front end of the clone path (q3_speaker_kernels.hip) ----
 // One reference clip of a batch.  Activations of a batch lie clip after clip along time ([sum T][C]); every kernel that looks across

@@ -222,11 +222,11 @@ public:
     void codec_rope_tables(int P);
 
     // ---- carried-state stages behind the vocoder: 24 kHz float on the device in, the stage's samples out ----
-    // Five kinds in one fixed order: the pitch stage (q3_pitch.cpp, 4o), the stretcher (q3_speed.cpp, 4m), the loudness stage
-    // (q3_loudness.cpp, 4p), the level stage (q3_level.cpp, 4n), the PCM sink (q3_pcm_sink.cpp, 4l).  Stage (q3_stage.cpp) is what they share: a call reserves once (the only
+    // Six kinds in one fixed order: the pitch stage (q3_pitch.cpp, 4o), the stretcher (q3_speed.cpp, 4m), the tone stage (q3_tone.cpp,
+    // 4r), the loudness stage (q3_loudness.cpp, 4p), the level stage (q3_level.cpp, 4n), the PCM sink (q3_pcm_sink.cpp, 4l).  Stage (q3_stage.cpp) is what they share: a call reserves once (the only
     // place the workspaces may grow, before anything is enqueued), launches once per set of stages whose input is ready, and commits
     // after the stream's sync.
-    enum StageKind { SK_PITCH = 0, SK_SPEED = 1, SK_LOUD = 2, SK_LEVEL = 3, SK_SINK = 4, SK_N = 5 };
+    enum StageKind { SK_PITCH = 0, SK_SPEED = 1, SK_TONE = 2, SK_LOUD = 3, SK_LEVEL = 4, SK_SINK = 5, SK_N = 6 };
     static constexpr int kMaxStages = 4096;                          // of a kind, open at the same time (vocoder streams' included)
     static constexpr int64_t kStageMaxPush = 1440000;                // one push of a standalone entry: 60 s
     // x_dev: n_new samples on the device; out_host (NULL ok): min(n_out, cap) samples in the stage's output format land there;
@@ -300,6 +300,17 @@ public:
         bool fill(StagePush& q, size_t di, char* out, int32_t* offs) override;
         void issue(size_t d0, int n_live) override; void commit_one(const StagePush& q) override;
     } speed{*this};
+    // the tone stage: a cascade of n biquads.  c: their coefficients, formed once at begin.  mem: its own allocation, two halves of
+    // kToneStateDoubles doubles (two per signal).  The host rule is the identity.
+    struct Equaliser : StageSlot { int n = 0; double c[kToneMaxSections][5] = {}; double* mem = nullptr; };
+    struct ToneStage : StageOf<ToneDesc, Equaliser> {
+        explicit ToneStage(Engine& en) : StageOf(en, "tone", "tone stage", "stage", "no such tone stage") {}
+        int begin(int n, const ToneSection* sections);
+        void free_all() override;
+        int64_t push_len(int id, int64_t n_new, bool finish) const override;
+        bool fill(StagePush& q, size_t di, char* out, int32_t* offs) override;
+        void issue(size_t d0, int n_live) override; void commit_one(const StagePush& q) override;
+    } tone{*this};
     // the loudness stage: BS.1770 meter and normaliser.  mem: its own allocation, two halves of kLoudHalfBytes (state words, then the
     // open sub-block's input).  pt, r_lo, r_hi, g_start: formed once on the host from the parameters.  A push's n_frames is four words
     // per sub-block it closes: its int64 energies, then its float gains.  The host rule needs nothing from the device.
@@ -340,18 +351,20 @@ public:
         bool fill(StagePush& q, size_t di, char* out, int32_t* offs) override;
         void issue(size_t d0, int n_live) override; void commit_one(const StagePush& q) override;
     } sink{*this};
-    Stage* const stages[SK_N] = { &pitch, &speed, &loud, &level, &sink };         // by StageKind: the order a stream's audio passes them in
+    Stage* const stages[SK_N] = { &pitch, &speed, &tone, &loud, &level, &sink };         // by StageKind: the order a stream's audio passes them in
 
     // vocoder streams: a stream delivers its audio through the stages it has (codec_stream_push_batch; behind a sink StreamPush::pcm is read as
     // the sink's format, n_own counts its samples).  Refused once the stream has delivered a sample.  1000, (0, 0), 24 000 Hz float: no stage.
     void codec_stream_set_pitch(int sid, int ratio);
     void codec_stream_set_speed(int sid, int speed);
+    void codec_stream_set_tone(int sid, int n, const ToneSection* sections);   // n == 0: no stage
     void codec_stream_set_loudness(int sid, int target_dlufs, int range_cb, int start_cb);
     void codec_stream_set_level(int sid, int gain_cb, int ceiling);
     void codec_stream_set_sink(int sid, int rate, int format);
-    // the scheduler's stages (q3tts_engine_set_sink / _speed / _level / _pitch / _loudness): slots' implicit streams begin with them.
+    // the scheduler's stages (q3tts_engine_set_sink / _speed / _level / _pitch / _loudness / _tone): slots' implicit streams begin with them.
     // Zeros: none (loud: whether there is a loudness stage at all, since target 0 is a meter)
-    struct SlotStages { int sink_rate = 0, sink_format = 0, speed = 0, gain_cb = 0, ceiling = 0, pitch = 0, loud = 0, loud_target = 0, loud_range = 0, loud_start = 0; } slot_stages;
+    struct SlotStages { int sink_rate = 0, sink_format = 0, speed = 0, gain_cb = 0, ceiling = 0, pitch = 0, loud = 0, loud_target = 0, loud_range = 0, loud_start = 0,
+                        tone_n = 0; ToneSection tone[kToneMaxSections] = {}; } slot_stages;
 
     // ---- batch-first session ops on DEVICE pointers (include/q3tts.h "_dev" entry points): row b <-> slot b ----
     // caller stream: the engine's stream first waits for what the caller has enqueued, the caller's stream then waits for the call's work

@@ -81,6 +81,7 @@ Engine::SlotStages slot_stages_of(const StageSettings& s) {
     o.sink_format = s.sink.format;
     o.speed = s.speed != 1000 ? s.speed : 0; o.pitch = s.pitch != 1000 ? s.pitch : 0;
     o.gain_cb = levelled ? s.gain_cb : 0; o.ceiling = levelled ? s.ceiling : 0;
+    o.tone_n = s.tone_n; for (int j = 0; j < s.tone_n; ++j) o.tone[j] = s.tone[j];
     o.loud = s.loud ? 1 : 0; o.loud_target = s.loud_target; o.loud_range = s.loud_range; o.loud_start = s.loud_start;
     return o;
 }
@@ -94,6 +95,7 @@ ChunkCapacity chunk_capacity(Engine& e, const StageSettings& s, int64_t cap) {
     // with a speed (q3tts_engine_set_speed) the chunk first passes its stretcher: at most the chunk plus what the stretcher held back
     // (N + D + Hs input samples), 1000 / S times as long, plus the cut last block
     if (s.speed != 1000) cap = ((cap + kSpeedN + kSpeedD + kSpeedHs) * 1000 + s.speed - 1) / s.speed + kSpeedHs;
+    // a tone stage (q3tts_engine_set_tone) emits what it receives: no term
     // a loudness stage (q3tts_engine_set_loudness) holds back less than one sub-block
     if (s.loud) cap += kLoudBlock - 1;
     // with a level (q3tts_engine_set_level) the limiter hands on what it held back as well: at most W - 1 samples more

@@ -17,6 +17,8 @@ struct StageSettings {
     int32_t pitch = 1000;                           // q3tts_engine_set_pitch (1000: none)
     bool loud = false;                              // q3tts_engine_set_loudness / _clear_loudness
     int32_t loud_target = 0, loud_range = 0, loud_start = 0;
+    int32_t tone_n = 0;                             // q3tts_engine_set_tone (0: none)
+    ToneSection tone[kToneMaxSections] = {};
 };
 
 // Everything a q3tts_synthesize_* entry passes, by name; what an entry does not have stays absent.

@@ -1,6 +1,6 @@
 // q3_stage.cpp — what the carried-state stages behind the vocoder share on the device side: the grow-only workspaces
 // of a call, the launch loop over a set of pushes and the standalone entry that stages its input from the host.  What a kind supplies
-// (descriptor fill, launch, commit rule, begin) is in q3_pitch.cpp, q3_speed.cpp, q3_loudness.cpp, q3_level.cpp and q3_pcm_sink.cpp; the host-side table in q3_stage.h.
+// (descriptor fill, launch, commit rule, begin) is in q3_pitch.cpp, q3_speed.cpp, q3_tone.cpp, q3_loudness.cpp, q3_level.cpp and q3_pcm_sink.cpp; the host-side table in q3_stage.h.
 #include <algorithm>
 #include <vector>
 

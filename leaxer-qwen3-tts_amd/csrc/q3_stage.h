@@ -1,5 +1,5 @@
 // q3_stage.h — host-side bookkeeping that the carried-state stages behind the vocoder share (the pitch stage 4o, the
-// stretcher 4m, the loudness stage 4p, the level stage 4n, the PCM sink 4l): the table of open stages with its ids, the counters of each, the refusals of a push and the commit
+// stretcher 4m, the tone stage 4r, the loudness stage 4p, the level stage 4n, the PCM sink 4l): the table of open stages with its ids, the counters of each, the refusals of a push and the commit
 // of one.  No HIP in here: a stage keeps its device allocation in its own Slot; tests/test_cpu_stage_table.py drives this header from
 // a plain g++ harness.  [HINT] no counterpart in the reference, which has no such stage.
 #pragma once

@@ -442,6 +442,65 @@ bool TTSEngine::apply_pitch(std::vector<float>& pcm24) {
     return ok;
 }
 
+bool TTSEngine::set_tone(const char* spec) {
+    if (!ready_) return false;
+    q3tts_tone_section s[Q3TTS_TONE_MAX_SECTIONS];
+    int32_t n = 0;
+    if (q3tts_tone_parse(spec, s, &n) != 0) {
+        error_msg_ = q3tts_tone_last_error();
+        std::cerr << "[TTSEngine] Tone: " << error_msg_ << std::endl;
+        return false;
+    }
+    if (q3tts_engine_set_tone(h_, n, s) != 0) {
+        error_msg_ = q3tts_last_error(h_);
+        std::cerr << "[TTSEngine] Tone: " << error_msg_ << std::endl;
+        return false;
+    }
+    tone_n_ = n;
+    tone_spec_ = spec;
+    return true;
+}
+
+int TTSEngine::tone_begin(int* id) {
+    q3tts_tone_section s[Q3TTS_TONE_MAX_SECTIONS];
+    int32_t n = 0;
+    if (q3tts_tone_parse(tone_spec_.c_str(), s, &n) != 0) return -1;   // set_tone accepted this spec
+    return q3tts_tone_begin(h_, n, s, id);
+}
+
+void TTSEngine::clear_tone() {
+    if (ready_) (void)q3tts_engine_set_tone(h_, 0, nullptr);
+    tone_n_ = 0;
+    tone_spec_.clear();
+}
+
+bool TTSEngine::tone_push(int id, const float* in, size_t n, bool finish, std::vector<float>& out) {   // the stage emits what it receives
+    const int64_t n_in = (int64_t)n;
+    const uint8_t fin = finish ? 1 : 0;
+    const size_t have = out.size();
+    out.resize(have + n);
+    float* dst = out.data() + have;
+    int64_t len = 0;
+    return q3tts_tone_push_batch_host(h_, 1, &id, &in, &n_in, &fin, &dst, n_in, &len) == 0 && len == n_in;
+}
+
+bool TTSEngine::apply_tone(std::vector<float>& pcm24) {
+    if (!ready_) return false;
+    if (tone_n_ == 0 || pcm24.empty()) return true;
+    int id = -1;
+    std::vector<float> out;
+    bool ok = tone_begin(&id) == 0;
+    const size_t step = 1440000;   // the most one push takes
+    for (size_t done = 0; ok && done < pcm24.size(); done += step) {
+        const size_t m = std::min(step, pcm24.size() - done);
+        ok = tone_push(id, pcm24.data() + done, m, done + m == pcm24.size(), out);
+    }
+    if (!ok) std::cerr << "[TTSEngine] Tone error: " << q3tts_last_error(h_) << std::endl;
+    if (id >= 0) (void)q3tts_tone_end(h_, id);
+    if (ok) pcm24.swap(out); else pcm24.clear();
+    return ok;
+}
+
 bool TTSEngine::set_loudness(float lufs, float range_db) {
     if (!ready_) return false;
     const long T = std::lround(10.0 * (double)lufs), R = std::lround(10.0 * (double)range_db);
@@ -549,13 +608,13 @@ bool TTSEngine::apply_level(std::vector<float>& pcm24) {
     return ok;
 }
 
-// the whole clip through the pitch stage, the stretcher, the loudness stage and then the level stage (each only when set): every
+// the whole clip through the pitch stage, the stretcher, the tone stage, the loudness stage and then the level stage (each only when set): every
 // one-shot method ends here
 bool TTSEngine::apply_speed(std::vector<float>& pcm24) {
     if (!ready_) return false;
     if (pcm24.empty()) return true;
     if (!apply_pitch(pcm24)) return false;
-    if (speed_ == 1000) return apply_loudness(pcm24) && apply_level(pcm24);
+    if (speed_ == 1000) return apply_tone(pcm24) && apply_loudness(pcm24) && apply_level(pcm24);
     int id = -1;
     std::vector<float> out;
     bool ok = q3tts_speed_begin(h_, speed_, &id) == 0;
@@ -567,7 +626,7 @@ bool TTSEngine::apply_speed(std::vector<float>& pcm24) {
     if (!ok) std::cerr << "[TTSEngine] Speed error: " << q3tts_last_error(h_) << std::endl;
     if (id >= 0) (void)q3tts_speed_end(h_, id);
     if (ok) pcm24.swap(out); else pcm24.clear();
-    return ok && apply_loudness(pcm24) && apply_level(pcm24);
+    return ok && apply_tone(pcm24) && apply_loudness(pcm24) && apply_level(pcm24);
 }
 
 bool TTSEngine::has_audio_encoder() const { return h_ && q3tts_has_audio_encoder(h_) != 0; }
@@ -799,6 +858,15 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
         if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
         return rc;
     }
+    // with a tone the stretcher's chunks pass a tone stage of this call's own, ahead of the loudness stage
+    int equaliser = -1;
+    std::vector<float> shaped;
+    if (tone_n_ > 0 && tone_begin(&equaliser) != 0) {
+        const int rc = fail();
+        if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
+        if (shifter >= 0) (void)q3tts_pitch_end(h_, shifter);
+        return rc;
+    }
     // with a loudness the stretcher's chunks pass a loudness stage of this call's own, ahead of the level stage
     int normaliser = -1;
     size_t normalised = 0;
@@ -807,6 +875,7 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
         const int rc = fail();
         if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
         if (shifter >= 0) (void)q3tts_pitch_end(h_, shifter);
+        if (equaliser >= 0) (void)q3tts_tone_end(h_, equaliser);
         return rc;
     }
     // with a level the chunks (the stretcher's, when there is one) pass a level stage of this call's own in the same way
@@ -817,6 +886,7 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
         const int rc = fail();
         if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
         if (shifter >= 0) (void)q3tts_pitch_end(h_, shifter);
+        if (equaliser >= 0) (void)q3tts_tone_end(h_, equaliser);
         if (normaliser >= 0) (void)q3tts_loudness_end(h_, normaliser);
         return rc;
     }
@@ -824,6 +894,7 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
         const int rc = fail();
         if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
         if (shifter >= 0) (void)q3tts_pitch_end(h_, shifter);
+        if (equaliser >= 0) (void)q3tts_tone_end(h_, equaliser);
         if (normaliser >= 0) (void)q3tts_loudness_end(h_, normaliser);
         if (leveler >= 0) (void)q3tts_level_end(h_, leveler);
         return rc;
@@ -836,7 +907,7 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
         if (!loud.empty()) on_audio(loud.data(), loud.size());
         return true;
     };
-    auto feed = [&](const float* p, size_t n, bool last) -> bool {   // a chunk from the vocoder: pitch stage, stretcher, loudness stage, then emit
+    auto feed = [&](const float* p, size_t n, bool last) -> bool {   // a chunk from the vocoder: pitch stage, stretcher, tone stage, loudness stage, then emit
         if (shifter >= 0) {
             low.clear();
             if (!pitch_push(shifter, p, n, last, shifted, low)) return false;
@@ -848,6 +919,11 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
             if (!stretch_push(stretcher, p, n, last, received, fast)) return false;
             received += n;
             p = fast.data(); n = fast.size();
+        }
+        if (equaliser >= 0) {
+            shaped.clear();
+            if (!tone_push(equaliser, p, n, last, shaped)) return false;
+            p = shaped.data(); n = shaped.size();
         }
         if (normaliser >= 0) {
             even.clear();
@@ -873,9 +949,10 @@ int TTSEngine::synthesize_tokens_streaming(const std::vector<int64_t>& token_ids
         }
         if (active == 0 || want <= 0) break;
     }
-    if ((shifter >= 0 || stretcher >= 0 || normaliser >= 0 || leveler >= 0) && !feed(pcm.data(), 0, true)) return fail_s();   // the stages' tails, in their order
+    if ((shifter >= 0 || stretcher >= 0 || equaliser >= 0 || normaliser >= 0 || leveler >= 0) && !feed(pcm.data(), 0, true)) return fail_s();   // the stages' tails, in their order
     if (shifter >= 0) (void)q3tts_pitch_end(h_, shifter);
     if (stretcher >= 0) (void)q3tts_speed_end(h_, stretcher);
+    if (equaliser >= 0) (void)q3tts_tone_end(h_, equaliser);
     if (normaliser >= 0) (void)q3tts_loudness_end(h_, normaliser);
     if (leveler >= 0) (void)q3tts_level_end(h_, leveler);
     (void)q3tts_slot_release(h_, 0);

@@ -217,6 +217,15 @@ public:
     void clear_loudness();                            // no stage again
     bool has_loudness() const { return loud_; }
     bool apply_loudness(std::vector<float>& pcm24);   // the whole clip through the stage, in place; no stage leaves it as it is
+    // Tone (include/q3tts.h: q3tts_engine_set_tone, q3tts_tone_*; the reference has no equaliser).  spec: a preset's name (telephone,
+    // rumble, presence, warm; unheard and untuned) or sections "kind:Hz[:dB]:Q" separated by commas, as q3tts_tone_parse reads them.  A
+    // cascade of 1 .. 8 biquads on the GPU between the stretcher and the loudness stage, on every path that honours set_speed, in the
+    // same way (apply_tone, which apply_speed calls before apply_loudness).  No latency.  false (and get_error(), naming the field) for
+    // a spec the engine refuses.
+    bool set_tone(const char* spec);
+    void clear_tone();                            // no stage again
+    bool has_tone() const { return tone_n_ > 0; }
+    bool apply_tone(std::vector<float>& pcm24);   // the whole clip through the stage, in place; no stage leaves it as it is
     // Pitch (include/q3tts.h: q3tts_engine_set_pitch, q3tts_pitch_*; the reference has no pitch control).  semitones -12 .. +12; the
     // engine works in permille, r = round(1000 * 2^(semitones / 12)), and 0 semitones is no stage at all.  TD-PSOLA on the GPU: the
     // fundamental moves, the spectral envelope stays.  The stage stands first behind the vocoder on every path that honours set_speed,
@@ -256,6 +265,10 @@ private:
     int pitch_ = 1000;
     bool loud_ = false;
     int loud_target_ = -160, loud_range_ = 200;
+    int tone_n_ = 0;
+    std::string tone_spec_;   // the spec set_tone accepted; this header stands alone (no q3tts.h), so the sections are formed from it where a stage begins
+    int tone_begin(int* id);  // a tone stage of this engine's spec (q3tts_tone_begin's return)
+    bool tone_push(int id, const float* in, size_t n, bool finish, std::vector<float>& out);
     bool loudness_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);
     bool pitch_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);
     bool level_push(int id, const float* in, size_t n, bool finish, size_t received_before, std::vector<float>& out);

@@ -127,6 +127,8 @@ EXPORTS = [
     "q3tts_codec_stream_set_pitch", "q3tts_engine_set_pitch",
     "q3tts_loudness_coeffs", "q3tts_loudness_emitted", "q3tts_loudness_lufs", "q3tts_loudness_last_error", "q3tts_loudness_begin",
     "q3tts_loudness_push_batch_host", "q3tts_loudness_end", "q3tts_codec_stream_set_loudness", "q3tts_engine_set_loudness",
+    "q3tts_tone_coeffs", "q3tts_tone_parse", "q3tts_tone_last_error", "q3tts_tone_begin", "q3tts_tone_push_batch_host", "q3tts_tone_end",
+    "q3tts_codec_stream_set_tone", "q3tts_engine_set_tone",
     "q3tts_create_sharing", "q3tts_weights_info",
 ]
 
@@ -530,7 +532,7 @@ class Engine:
         return pcm[: out_len.value]
 
     def codec_stream_begin(self, max_frames, sample_rate=24000, dtype="float32", speed=None, gain_db=None, ceiling=None,
-                           loudness=None, loudness_range=None, loudness_start=None, pitch=None):
+                           loudness=None, loudness_range=None, loudness_start=None, *, tone=None, pitch=None):
         """streaming vocoder with carried state: -> stream id (q3tts_codec_stream_begin).  sample_rate / dtype other than 24000 /
         float32 give the stream a sink (q3tts_codec_stream_set_sink): codec_stream_push_batch then delivers at that rate, as float32
         or int16.  speed (permille, 500 .. 2000; None or 1000: none) gives it a stretcher ahead of the sink
@@ -538,7 +540,8 @@ class Engine:
         stage between the two (q3tts_codec_stream_set_level).  pitch (permille, 500 .. 2000; None or 1000: none) gives it a pitch
         stage in front of them all (q3tts_codec_stream_set_pitch).  loudness (LUFS, -40 .. -5, or 0: meter only; None: none) with
         loudness_range / loudness_start (dB; loudness_params) gives it a loudness stage between the stretcher and the level stage
-        (q3tts_codec_stream_set_loudness)."""
+        (q3tts_codec_stream_set_loudness).  tone (a spec string or a list of sections, tone_sections; None: none) gives it a tone
+        stage between the stretcher and the loudness stage (q3tts_codec_stream_set_tone)."""
         fmt = _pcm_format(dtype)
         sid = C.c_int(-1)
         self.L.q3tts_codec_stream_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -574,7 +577,66 @@ class Engine:
             except Exception:
                 self.codec_stream_end(sid.value)
                 raise
+        if tone is not None:
+            try:
+                self.codec_stream_set_tone(sid.value, tone)
+            except Exception:
+                self.codec_stream_end(sid.value)
+                raise
         return sid.value
+
+    def codec_stream_set_tone(self, sid, tone):
+        """q3tts_codec_stream_set_tone: tone a spec string or a list of sections (tone_sections); refused once the stream has delivered
+        a sample; None or no sections take the stage away"""
+        arr = _tone_array(tone)
+        self.L.q3tts_codec_stream_set_tone.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p]
+        self._ck(self.L.q3tts_codec_stream_set_tone(self.h, int(sid), arr.shape[0], _p(arr) if arr.shape[0] else None))
+        d = self.__dict__.setdefault("_codec_stream_tone", {})
+        if arr.shape[0] == 0:
+            d.pop(int(sid), None)
+        else:
+            d[int(sid)] = arr
+
+    # ---- the tone stage on its own (include/q3tts.h "tone") ----
+    def tone_begin(self, tone):
+        """a stage that takes 24 kHz float32 and delivers it through a cascade of 1 .. 8 biquads; tone a spec string or a list of
+        sections (tone_sections) -> stage id"""
+        arr = _tone_array(tone)
+        sid = C.c_int(-1)
+        self.L.q3tts_tone_begin.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int)]
+        self._ck(self.L.q3tts_tone_begin(self.h, arr.shape[0], _p(arr) if arr.shape[0] else None, C.byref(sid)))
+        return sid.value
+
+    def tone_push_batch(self, ids, pcm_list, finish=None):
+        """more 24 kHz samples for many tone stages in one launch (q3tts_tone_push_batch_host); finish: one flag per stage (nothing is
+        flushed: the stage only closes) -> one float32 array per stage, as long as its input"""
+        n = len(ids)
+        if n == 0:
+            return []
+        if len(pcm_list) != n or (finish is not None and len(finish) != n):
+            raise ValueError("tone_push_batch: one sample array (and one finish flag) per stage")
+        xs = [np.ascontiguousarray(a, np.float32).reshape(-1) for a in pcm_list]
+        fin = np.zeros(n, np.uint8) if finish is None else np.ascontiguousarray([1 if f else 0 for f in finish], np.uint8)
+        lens = np.array([x.size for x in xs], np.int64)
+        cap = int(lens.max())
+        outs = [np.empty(max(cap, 1), np.float32) for _ in range(n)]
+        xptr = (C.c_void_p * n)(*[x.ctypes.data if x.size else None for x in xs])
+        optr = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        out_len = np.zeros(n, np.int64)
+        self.L.q3tts_tone_push_batch_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        self._ck(self.L.q3tts_tone_push_batch_host(self.h, n, _p(np.ascontiguousarray(ids, np.int32)), C.cast(xptr, C.c_void_p), _p(lens), _p(fin),
+                                                   C.cast(optr, C.c_void_p), cap, _p(out_len)))
+        return [outs[i][: out_len[i]] for i in range(n)]
+
+    def tone_end(self, stage_id):
+        self.L.q3tts_tone_end.argtypes = [C.c_void_p, C.c_int]
+        self._ck(self.L.q3tts_tone_end(self.h, int(stage_id)))
+
+    def set_tone(self, tone=None):
+        """q3tts_engine_set_tone: the streaming entries deliver through a tone stage; None takes it away"""
+        arr = _tone_array(tone)
+        self.L.q3tts_engine_set_tone.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        self._ck(self.L.q3tts_engine_set_tone(self.h, arr.shape[0], _p(arr) if arr.shape[0] else None))
 
     def codec_stream_set_loudness(self, sid, target_dlufs, range_cb=200, start_cb=0):
         """q3tts_codec_stream_set_loudness: target in tenths of a LUFS (0: meter only), range and start gain in centibels; refused once
@@ -891,7 +953,8 @@ class Engine:
         lvls = self.__dict__.setdefault("_codec_stream_level", {})
         pits = self.__dict__.setdefault("_codec_stream_pitch", {})
         louds = self.__dict__.setdefault("_codec_stream_loud", {})
-        if finish is None and not any(int(i) in fmts or int(i) in spds or int(i) in lvls or int(i) in pits or int(i) in louds for i in ids):
+        tones = self.__dict__.setdefault("_codec_stream_tone", {})   # a tone stage adds nothing to a push's length
+        if finish is None and not any(int(i) in fmts or int(i) in spds or int(i) in lvls or int(i) in pits or int(i) in louds or int(i) in tones for i in ids):
             return self._push_batch(ids, cs, offs)
         flat = np.ascontiguousarray(np.concatenate(cs)) if sum(c_.shape[0] for c_ in cs) else np.zeros((1, self.cfg.n_groups), np.int64)
         n24 = self.codec_decode_len(max(max(c_.shape[0] for c_ in cs), 1)) + 4096
@@ -979,6 +1042,7 @@ class Engine:
         self.__dict__.setdefault("_codec_stream_level", {}).pop(int(sid), None)
         self.__dict__.setdefault("_codec_stream_pitch", {}).pop(int(sid), None)
         self.__dict__.setdefault("_codec_stream_loud", {}).pop(int(sid), None)
+        self.__dict__.setdefault("_codec_stream_tone", {}).pop(int(sid), None)
 
     def slot_codec_decode_range(self, slot, frame_begin, frame_end, left_context):
         """samples owned by frames [frame_begin, frame_end) of a slot (streaming while it generates)"""
@@ -1703,7 +1767,7 @@ class Engine:
         self._ck(rc)
         return [pcm[i][: pcm_len[i]] for i in range(n)], [codes[i, : nfr[i]] for i in range(n)], nfr
 
-    def _sink_job(self, sample_rate, dtype, on_audio, n, run, speed=None, level=(0, 0), pitch=None, loud=None):
+    def _sink_job(self, sample_rate, dtype, on_audio, n, run, speed=None, level=(0, 0), pitch=None, loud=None, tone=None):
         """a streaming job through a sink of its own: run(None-pcm_out) with the sink set, the sink taken away afterwards; the chunks
         on_audio saw are also returned joined per utterance"""
         fmt = _pcm_format("float32" if dtype is None else dtype)
@@ -1717,12 +1781,14 @@ class Engine:
             self.set_level(*level)
             self.set_pitch(1000 if pitch is None else pitch)
             self.set_loudness(*(loud if loud is not None else (None,)))
+            self.set_tone(tone)
             self.set_sink(24000 if sample_rate is None else sample_rate, _PCM_NAMES[fmt], tee)
         except BaseException:
             self.set_speed(None)
             self.set_level(0, 0)
             self.set_pitch(1000)
             self.set_loudness(None)
+            self.set_tone(None)
             raise
         try:
             rc = run()
@@ -1733,6 +1799,7 @@ class Engine:
             self.set_level(0, 0)
             self.set_pitch(1000)
             self.set_loudness(None)
+            self.set_tone(None)
         if raised:
             raise raised[0]
         self._ck(rc)
@@ -1740,7 +1807,7 @@ class Engine:
         return [np.concatenate(g) if g else np.zeros(0, npdt) for g in got]
 
     def synthesize_stream(self, token_lists, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
-                          max_new_per_utt=None, instructs=None, sample_rate=None, dtype=None, speed=None, gain_db=None, ceiling=None, loudness=None, pitch=None):
+                          max_new_per_utt=None, instructs=None, sample_rate=None, dtype=None, speed=None, gain_db=None, ceiling=None, loudness=None, *, tone=None, pitch=None):
         """synthesize_batch that delivers audio while it generates (q3tts_synthesize_stream_host): every chunk_frames steps
         on_audio(utt, frame_begin, frame_end, pcm, finished) is called once per utterance with new audio (pcm: a copy); a truthy return
         cancels the job (RuntimeError "cancelled by callback").  Returns what synthesize_batch returns."""
@@ -1786,7 +1853,9 @@ class Engine:
         if pitch is not None and int(pitch) == 1000:
             pitch = None   # no stage; otherwise (permille) the chunks pass a pitch stage first (q3tts_engine_set_pitch)
         loud = None if loudness is None else loudness_params(loudness)   # LUFS, or (LUFS, range dB, start dB): a loudness stage behind the stretcher (q3tts_engine_set_loudness)
-        if sample_rate is not None or dtype is not None or speed is not None or level != (0, 0) or pitch is not None or loud is not None:   # through a sink (q3tts_engine_set_sink): sample_rate / dtype are the chunks' and the result's; speed (permille): time-stretched first (q3tts_engine_set_speed)
+        if tone is not None and _tone_array(tone).shape[0] == 0:
+            tone = None   # no stage; otherwise (a spec or sections) the chunks pass a tone stage behind the stretcher (q3tts_engine_set_tone)
+        if sample_rate is not None or dtype is not None or speed is not None or level != (0, 0) or pitch is not None or loud is not None or tone is not None:   # through a sink (q3tts_engine_set_sink): sample_rate / dtype are the chunks' and the result's; speed (permille): time-stretched first (q3tts_engine_set_speed)
             def run():
                 if ins_flat is not None:
                     return self.L.q3tts_synthesize_instruct_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
@@ -1795,7 +1864,7 @@ class Engine:
                 return self.L.q3tts_synthesize_stream_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
                                                            seed, int(ignore_eos), None, 0, _p(pcm_len), _p(nfr),
                                                            _p(codes) if want_codes else None, int(chunk_frames), cb, None)
-            outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed, level, pitch, loud)
+            outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed, level, pitch, loud, tone)
             return outs, ([codes[i, : nfr[i]] for i in range(n)] if want_codes else None), nfr
         if ins_flat is not None:
             rc = self.L.q3tts_synthesize_instruct_host(self.h, n, _p(flat), _p(offs), lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
@@ -1813,7 +1882,7 @@ class Engine:
         return outs, cl, nfr
 
     def synthesize_live(self, n_utt, text_source, sp, chunk_frames, on_audio, lang=0, seed=0, ignore_eos=False, want_codes=True, speakers=None,
-                        max_new_per_utt=None, sample_rate=None, dtype=None, speed=None, gain_db=None, ceiling=None, loudness=None, pitch=None):
+                        max_new_per_utt=None, sample_rate=None, dtype=None, speed=None, gain_db=None, ceiling=None, loudness=None, *, tone=None, pitch=None):
         """synthesize_stream for texts that arrive while their audio is generated (q3tts_synthesize_live_host): text_source(utt) ->
         (ids, closed) is polled between decode chunks for every utterance whose text is open — new ids (possibly none) and whether the
         text has ended; None cancels the job (RuntimeError "cancelled by callback").  An utterance's ids are those synthesize_stream
@@ -1876,13 +1945,15 @@ class Engine:
         if pitch is not None and int(pitch) == 1000:
             pitch = None
         loud = None if loudness is None else loudness_params(loudness)
-        if sample_rate is not None or dtype is not None or speed is not None or level != (0, 0) or pitch is not None or loud is not None:   # through a sink and / or a stretcher, as synthesize_stream
+        if tone is not None and _tone_array(tone).shape[0] == 0:
+            tone = None
+        if sample_rate is not None or dtype is not None or speed is not None or level != (0, 0) or pitch is not None or loud is not None or tone is not None:   # through a sink and / or a stretcher, as synthesize_stream
             def run():
                 return self.L.q3tts_synthesize_live_host(self.h, n, tcb, None, lang, spk_ptrs, C.byref(sp), None if caps is None else _p(caps),
                                                          seed, int(ignore_eos), None, 0, _p(pcm_len), _p(nfr),
                                                          _p(codes) if want_codes else None, int(chunk_frames), cb, None)
             try:
-                outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed, level, pitch, loud)
+                outs = self._sink_job(sample_rate, dtype, on_audio, n, run, speed, level, pitch, loud, tone)
             except BaseException:
                 if raised:
                     raise raised[0]
@@ -2106,6 +2177,51 @@ def loudness_params(loudness, loudness_range=None, loudness_start=None):
         loudness, loudness_range, loudness_start = (list(loudness) + [None, None])[:3]
     return (int(round(10.0 * float(loudness))), 200 if loudness_range is None else int(round(10.0 * float(loudness_range))),
             0 if loudness_start is None else int(round(10.0 * float(loudness_start))))
+
+
+TONE_KINDS = {"highpass": 1, "lowpass": 2, "lowshelf": 3, "highshelf": 4, "peak": 5}
+
+
+def tone_sections(spec):
+    """q3tts_tone_parse: the sections of a spec string as an int32 array [n][4] of (kind, freq_hz, gain_cb, q_permille).  A spec is a
+    preset's name (telephone, rumble, presence, warm: unheard and untuned) or sections separated by commas, kind:Hz:Q for hp and lp,
+    kind:Hz:dB:Q for ls, hs and peak, e.g. "hp:300:0.707,peak:2500:+3:1.0,lp:3400:0.707".  Host-only; ValueError names what could not be
+    read or is out of range."""
+    Lb = lib()
+    Lb.q3tts_tone_parse.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p]
+    Lb.q3tts_tone_parse.restype = C.c_int
+    Lb.q3tts_tone_last_error.restype = C.c_char_p
+    out = np.zeros((8, 4), np.int32)
+    n = C.c_int32(0)
+    if Lb.q3tts_tone_parse(str(spec).encode(), out.ctypes.data, C.byref(n)) != 0:
+        raise ValueError(Lb.q3tts_tone_last_error().decode())
+    return out[: n.value].copy()
+
+
+def _tone_array(tone):
+    """None / a spec string / rows of (kind, freq_hz, gain_cb, q_permille) -> int32 [n][4]; the library checks the values"""
+    if tone is None:
+        return np.zeros((0, 4), np.int32)
+    if isinstance(tone, str):
+        return tone_sections(tone)
+    a = np.asarray(tone)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("tone: sections are integers (kind, freq_hz, gain_cb, q_permille)")
+    return np.ascontiguousarray(a, np.int32).reshape(-1, 4)
+
+
+def tone_coeffs(tone):
+    """q3tts_tone_coeffs: float64 [n][5], { b0, b1, b2, a1, a2 } of every section, the very doubles the device uses.  tone a spec
+    string or a list of sections.  Host-only; ValueError names the field, the section and the value that is out of range."""
+    arr = _tone_array(tone)
+    Lb = lib()
+    Lb.q3tts_tone_coeffs.argtypes = [C.c_int32, C.c_void_p, C.c_void_p]
+    Lb.q3tts_tone_coeffs.restype = C.c_int
+    Lb.q3tts_tone_last_error.restype = C.c_char_p
+    out = np.zeros((max(arr.shape[0], 1), 5), np.float64)
+    if Lb.q3tts_tone_coeffs(arr.shape[0], arr.ctypes.data if arr.shape[0] else None, out.ctypes.data) != 0:
+        raise ValueError(Lb.q3tts_tone_last_error().decode())
+    return out[: arr.shape[0]]
 
 
 def loudness_coeffs(rate=24000):
